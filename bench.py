@@ -14,11 +14,16 @@ collective and no RCCL anywhere.  Two ways to get N GPUs:
   * under torch.distributed.run (the driver's launcher, one rank per GPU) the ranks meet on a gloo (CPU) process group for the
     barrier, the max-over-ranks of the step time and the sum of solved counts.
 
-One JSON line is printed by rank 0 (contract in the task description) with two extra objects:
+One JSON line is printed by rank 0 (contract in the task description) with an extra object:
   roofline      HBM roofline of the dominant kernel, algorithmic bytes from the work counters the kernel keeps, duration from
                 HIP events on the launch stream.
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, the outputs (--dump-outputs) and the line.
+--full adds the measurements and checks that take runs of their own (--no-* and --cpu-sample select among them):
   cpu_baseline  the CPU oracle (a port of the same algorithm; the reference's qpOASES / OSQP paths cannot be built here) on a
-                bounded sample of the same workload, all host cores.
+                bounded sample of the same workload, all host cores;
+  pipelined, resident_8192, sparse_config5 (with grid_128), backsolve_kernel, backsolve_in_situ (see below).
+--dump-outputs DIR writes what the timed path returned in its last step (x, y and the statistics of every instance) as float64 .npy
+files: with the same arguments the inputs are the same from run to run, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -92,6 +97,33 @@ def run_devices(devices, make_batch, steps, warmup, barrier):
     return time.perf_counter() - t0, bts, tsum
 
 
+DUMP_BUDGET = 60 * 10**6        # bytes of arrays --dump-outputs may write (64 MB at most with the .npy headers)
+
+
+def dump_outputs(path, sols):
+    """x, y and the statistics of the last step as float64 DIR/<name>.npy, rows in instance-id order (ids in instances.npy); `sols` are the
+    solution() triples of this process's shards in shard order.  When the whole batch exceeds DUMP_BUDGET a fixed sample of instances (numpy
+    seed 0, ids sorted) stands for it."""
+    import numpy as np
+    from lcqpow_amd.capi import Stats
+    fields = [f for f, _ in Stats._fields_]
+    per_shard = len(sols[0][0])
+    total = per_shard * len(sols)
+    row_bytes = 8 * (sols[0][0].shape[1] + sols[0][1].shape[1] + len(fields) + 1)
+    rows = np.arange(total)
+    if total * row_bytes > DUMP_BUDGET:
+        rows = np.sort(np.random.default_rng(0).choice(total, max(1, DUMP_BUDGET // row_bytes), replace=False))
+    shard, local = rows // per_shard, rows % per_shard
+    out = {"instances": rows.astype(np.float64),
+           "x": np.stack([sols[s][0][i] for s, i in zip(shard, local)]),
+           "y": np.stack([sols[s][1][i] for s, i in zip(shard, local)])}
+    for f in fields:
+        out["stat_" + f] = np.array([sols[s][2][i][f] for s, i in zip(shard, local)], dtype=np.float64)
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -102,16 +134,22 @@ def main():
     ap.add_argument("--n", type=int, default=None)
     ap.add_argument("--nC", type=int, default=None)
     ap.add_argument("--nComp", type=int, default=None)
-    ap.add_argument("--cpu-sample", type=int, default=128, help="CPU baseline: 8 x instances per worker of the steady-state run (128 = 16 per worker; 0 = skip)")
-    ap.add_argument("--no-backsolve", action="store_true", help="skip the standalone back-solve kernel measurement")
-    ap.add_argument("--no-pipelined", action="store_true", help="skip the two-batches-in-flight measurement")
-    ap.add_argument("--no-resident", action="store_true", help="skip the 8192-resident-instances measurement")
-    ap.add_argument("--no-sparse", action="store_true", help="skip the sparse_config5 object (BASELINE configs[4]) of the default line")
+    ap.add_argument("--cpu-sample", type=int, default=128, help="CPU baseline (--full): 8 x instances per worker of the steady-state run (128 = 16 per worker; 0 = skip)")
+    ap.add_argument("--no-backsolve", action="store_true", help="with --full: skip the standalone back-solve kernel measurement")
+    ap.add_argument("--no-pipelined", action="store_true", help="with --full: skip the two-batches-in-flight measurement")
+    ap.add_argument("--no-resident", action="store_true", help="with --full: skip the 8192-resident-instances measurement")
+    ap.add_argument("--no-sparse", action="store_true", help="with --full: skip the sparse_config5 object (BASELINE configs[4])")
     ap.add_argument("--sparse-batch", type=int, default=65536, help="instances of the sparse_config5 object")
     ap.add_argument("--grid-batch", type=int, default=1024, help="instances of the grid_128 object inside sparse_config5 (the general sparse LDL'; 0 = skip)")
     ap.add_argument("--devices", type=str, default=None, help="comma-separated device ids of the N shards (default 0..N-1; under torch.distributed.run: rank r takes entry r). "
                     "A device may appear more than once: `--gpus 2 --devices 0,0` rehearses the N = 2 path -- two shards, aggregation, JSON -- on a one-GPU box")
+    ap.add_argument("--full", action="store_true", help="also run the measurements and checks beside the headline: pipelined, resident_8192, sparse_config5, "
+                    "the back-solve objects and the CPU baseline (off by default: a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write x, y and the statistics of the last timed step as float64 DIR/<name>.npy "
+                    "(at most 64 MB: a fixed, seeded sample of instances for larger batches; under the launcher rank 0 writes its shard)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     sparse = args.workload == "sparse"
     B = args.batch or (65536 if sparse else 1024)
     n = args.n or (4096 if sparse else 256)
@@ -204,6 +242,8 @@ def main():
     bt = bts[0]
     sols = [b_.solution() for b_ in bts]
     x, y, st = sols[0]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, sols)      # (rank 0 solves instances [0, B) under the launcher too)
     n_ok = sum(sum(1 for s in so[2] if s["returnValue"] == 0) for so in sols)
     if dist is not None:
         import torch
@@ -300,7 +340,7 @@ def main():
                             "note": "product call: lcqpow_amd.BatchPipeline / LCQPow::BatchPipeline, two batch objects in flight on two streams; every step still does setup + homotopy"}
         pipe.close(); bt2.close()
 
-    if main_proc and world == 1 and not sparse and not args.no_pipelined:
+    if args.full and main_proc and world == 1 and not sparse and not args.no_pipelined:
         extra("pipelined", extra_pipelined)
 
     def extra_resident():
@@ -317,7 +357,7 @@ def main():
                                 "roofline_frac": btR.algorithmic_bytes() / (kR * 1e-3) / 1e9 / HBM_PEAK_GBS}
         btR.close()
 
-    if main_proc and world == 1 and not sparse and not args.no_resident and shape == (256, 512, 64) and B == 1024:
+    if args.full and main_proc and world == 1 and not sparse and not args.no_resident and shape == (256, 512, 64) and B == 1024:
         extra("resident_8192", extra_resident)
 
     def sparse_object(Bs, ns=4096, nCs=2048, nKs=512):
@@ -467,7 +507,7 @@ def main():
                                    "single_core_value": single, "gpu_over_cpu": obj["value"] / (cnt / dtc), "max_abs_dx_vs_gpu": dx}
         out["sparse_config5"]["grid_128"] = obj
 
-    if main_proc and world == 1 and not sparse and not args.no_sparse and shape == (256, 512, 64) and B == 1024:
+    if args.full and main_proc and world == 1 and not sparse and not args.no_sparse and shape == (256, 512, 64) and B == 1024:
         extra("sparse_config5", extra_sparse)
         if "error" not in out.get("sparse_config5", {"error": 1}) and args.grid_batch > 0:
             extra("sparse_config5.grid_128", extra_grid)
@@ -492,7 +532,7 @@ def main():
                                    "note": "algorithmic bytes 8 N (N+2) per pair; of the diagonal 64x64 blocks only the triangle each pass needs is fetched"}
         del K, rhs
 
-    if main_proc and not sparse and not args.no_backsolve:
+    if args.full and main_proc and not sparse and not args.no_backsolve:
         extra("backsolve_kernel", extra_backsolve)
 
     def extra_backsolve_in_situ():
@@ -539,7 +579,7 @@ def main():
                                             "k_lcqp_run time); the factor of an instance (0.5 MB) is re-read 118 times per LCQP, partly from the Infinity "
                                             "Cache, so the figure is algorithmic bytes over time, not HBM traffic"}
 
-    if main_proc and world == 1 and not sparse and not args.no_backsolve and shape == (256, 512, 64):
+    if args.full and main_proc and world == 1 and not sparse and not args.no_backsolve and shape == (256, 512, 64):
         extra("backsolve_in_situ", extra_backsolve_in_situ)
 
     def extra_cpu_baseline():
@@ -595,7 +635,7 @@ def main():
                                          f"(an instance's working set exceeds a core's L3 share; stream read rate of all cores in this run: {stream:.0f} GB/s)",
                                "max_abs_dx_vs_gpu": dx}
 
-    if main_proc and world == 1 and args.cpu_sample > 0:
+    if args.full and main_proc and world == 1 and args.cpu_sample > 0:
         extra("cpu_baseline", extra_cpu_baseline)
 
     for b_ in bts:

@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_bench_json_contract():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "16",
-                        "--n", "64", "--nC", "96", "--nComp", "16", "--cpu-sample", "4"], capture_output=True, text=True, timeout=600)
+                        "--n", "64", "--nC", "96", "--nComp", "16", "--cpu-sample", "4", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -55,7 +55,7 @@ def test_bench_refuses_a_smaller_run_than_asked_for():
 @pytest.mark.gpu
 def test_bench_sparse_workload_line():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "sparse", "--steps", "1", "--warmup", "1", "--batch", "8",
-                        "--n", "512", "--nC", "256", "--nComp", "64", "--cpu-sample", "4"], capture_output=True, text=True, timeout=600)
+                        "--n", "512", "--nC", "256", "--nComp", "64", "--cpu-sample", "4", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert d["unit"] == "LCQPs/s" and d["config"]["solved"] == 8 and "sparse" in d["config"]["workload"]
@@ -140,10 +140,10 @@ def test_cpp_shards_on_one_device_equal_one_batch():
 
 @pytest.mark.gpu
 def test_bench_in_situ_backsolve_object():
-    """the default workload's line carries the back-solves of the PRODUCT path (wg_trsv inside k_lcqp_run) beside the stand-alone kernel: bytes
+    """the default workload's --full line carries the back-solves of the PRODUCT path (wg_trsv inside k_lcqp_run) beside the stand-alone kernel: bytes
     counted by the kernel, time from the stamped build of the same sources, results of the stamped build bit-identical to the product's"""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1", "--warmup", "1", "--cpu-sample", "0", "--no-pipelined",
-                        "--no-resident", "--no-sparse"], capture_output=True, text=True, timeout=900)
+                        "--no-resident", "--no-sparse", "--full"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout + r.stderr
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
     assert "errors" not in d
@@ -152,3 +152,51 @@ def test_bench_in_situ_backsolve_object():
     assert 50 < b["triangular_solves_per_lcqp"] < 400 and 0.02 < b["share_of_instance_cycles"] < 0.6 and 0.5 < b["mean_busy_share_of_launch"] <= 1.0
     assert abs(b["algorithmic_bytes_per_launch"] - b["triangular_solves_per_lcqp"] * 1024 * 8 * 256 * 258 / 2) < 1e-6 * b["algorithmic_bytes_per_launch"]
     assert b["frac"] > 0.1
+
+
+MOVED_OBJECTS = ("pipelined", "resident_8192", "sparse_config5", "backsolve_kernel", "backsolve_in_situ", "cpu_baseline")
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """a plain run (no --full) times the headline and nothing beside it; --steps sets the number of timed steps; --dump-outputs writes the
+    last step's x, y and statistics as float64 .npy files, and two runs with the same arguments write the same arrays"""
+    import numpy as np
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "16", "--n", "64", "--nC", "96", "--nComp", "16"]
+    lines, dumps = [], []
+    for k in range(2):
+        dk = tmp_path / f"run{k}"
+        lines.append(_one_json_line(subprocess.run(cmd + ["--dump-outputs", str(dk)], capture_output=True, text=True, timeout=600)))
+        dumps.append({f.name[:-4]: np.load(f) for f in dk.glob("*.npy")})
+    d = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "config", "roofline"):
+        assert k in d, k
+    assert not [k for k in MOVED_OBJECTS if k in d] and "errors" not in d
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["unit"] == "LCQPs/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert abs(d["value"] - 16 * 3 / (d["ms_per_step"] * 3e-3)) <= 1e-6 * d["value"]
+    out = dumps[0]
+    assert all(a.dtype == np.float64 for a in out.values()) and sum(a.nbytes for a in out.values()) <= 64 * 10**6
+    assert out["x"].shape == (16, 64) and out["y"].shape == (16, 64 + 96 + 2 * 16) and np.array_equal(out["instances"], np.arange(16))
+    assert int((out["stat_returnValue"] == 0).sum()) == d["config"]["solved"] == 16
+    assert out.keys() == dumps[1].keys() and all(np.array_equal(out[k], dumps[1][k]) for k in out)
+
+
+def test_bench_dump_outputs_sample(tmp_path, monkeypatch):
+    """above the byte budget --dump-outputs writes a fixed, seeded sample of instances, ids sorted, rows taken from the right shard (CPU)"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 50 * 8 * (3 + 5 + 13 + 1))        # room for 50 of the 2 x 100 instances
+    def shard(s):
+        ids = np.arange(100) + 100 * s
+        return (np.repeat(ids[:, None], 3, axis=1).astype(float), -np.repeat(ids[:, None], 5, axis=1).astype(float),
+                [dict(iterTotal=int(i), iterOuter=0, subproblemIter=0, status=0, qpSolverExitFlag=0, returnValue=0, rhoOpt=0.5 * i, admmIter=0,
+                      trials=0, factorizations=0, corrections=0, qpSolves=0, reserved=0) for i in ids])
+    outs = []
+    for k in range(2):
+        bench.dump_outputs(str(tmp_path / f"d{k}"), [shard(0), shard(1)])
+        outs.append({f.name[:-4]: np.load(f) for f in (tmp_path / f"d{k}").glob("*.npy")})
+    ids = outs[0]["instances"]
+    assert len(ids) == 50 and np.all(np.diff(ids) > 0) and ids[0] >= 0 and ids[-1] < 200 and (ids >= 100).any() and (ids < 100).any()
+    assert np.array_equal(outs[0]["x"][:, 0], ids) and np.array_equal(outs[0]["y"][:, 4], -ids) and np.array_equal(outs[0]["stat_rhoOpt"], 0.5 * ids)
+    assert all(a.dtype == np.float64 for a in outs[0].values()) and all(np.array_equal(outs[0][k], outs[1][k]) for k in outs[0])

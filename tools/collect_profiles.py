@@ -34,7 +34,7 @@ out = {"kernel": "k_lcqp_run<2>", "workload": ["dense", 1024, 256, 512, 64], "so
        "FETCH_SIZE_KiB": fetch, "WRITE_SIZE_KiB": write,
        "traffic_bytes_guide_recipe": (2 * fetch + write) * 1024, "traffic_bytes_uncorrected": (fetch + write) * 1024,
        "backsolve_FETCH_SIZE_KiB": mean_counter("pmc_fetch_size.csv", "k_backsolve", "FETCH_SIZE"),
-       "note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes of `python3 bench.py --steps 1 --warmup 0 --cpu-sample 0 --no-pipelined "
+       "note": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE in separate passes of `python3 bench.py --steps 1 --warmup 0 --full --cpu-sample 0 --no-pipelined "
                "--no-resident` (tools/run_profiles.sh); traffic = (2*FETCH_SIZE + WRITE_SIZE)*1024 per MI355X_MICROARCH.md (HBM); source_hash = "
                "bench.kernel_source_hash(workload) of the profiled sources (dense: the translation units of the dense kernels; sparse: all): bench.py reports the figure only while it matches"}
 bs = json.load(open(os.path.join(dst, "bench_sparse.json")))

@@ -5,7 +5,7 @@ O=$R/gpurun_out/${1:-fetchvar}
 mkdir -p $O
 export LCQPOW_HIP_LIBRARY=$R/$2
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc FETCH_SIZE -d $O/fetch --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 --cpu-sample 0 --no-pipelined --no-resident --no-sparse > $O/bench.json 2> $O/err.txt
+rocprofv3 --pmc FETCH_SIZE -d $O/fetch --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 --full --cpu-sample 0 --no-pipelined --no-resident --no-sparse > $O/bench.json 2> $O/err.txt
 python3 - $O <<'PY'
 import csv, glob, sys, collections
 acc = collections.defaultdict(list)

@@ -6,15 +6,15 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${1:-r3}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-D="--cpu-sample 0 --no-pipelined --no-resident --no-sparse"
+D="--full --cpu-sample 0 --no-pipelined --no-resident --no-sparse"
 S="--workload sparse --steps 1 --warmup 0 --cpu-sample 0"
-python3 $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 rocprofv3 --kernel-trace --stats -d $O/trace --output-format csv -- python3 $R/bench.py --steps 3 --warmup 1 $D > $O/bench_under_rocprof.json 2>> $O/rocprof.err
 rocprofv3 --pmc FETCH_SIZE -d $O/fetch --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 $D > /dev/null 2>> $O/rocprof.err
 rocprofv3 --pmc WRITE_SIZE -d $O/write --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 $D > /dev/null 2>> $O/rocprof.err
 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY -d $O/sq --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 $D --no-backsolve > /dev/null 2>> $O/rocprof.err
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_INSTS_VALU -d $O/mfma --output-format csv -- python3 $R/bench.py --steps 1 --warmup 0 $D --no-backsolve > /dev/null 2>> $O/rocprof.err
-python3 $R/bench.py --workload sparse --steps 2 --warmup 1 > $O/bench_sparse.json 2> $O/bench_sparse.err
+python3 $R/bench.py --workload sparse --steps 2 --warmup 1 --full > $O/bench_sparse.json 2> $O/bench_sparse.err
 rocprofv3 --kernel-trace --stats -d $O/trace_sparse --output-format csv -- python3 $R/bench.py $S > /dev/null 2>> $O/rocprof.err
 rocprofv3 --pmc FETCH_SIZE -d $O/fetch_sparse --output-format csv -- python3 $R/bench.py $S > /dev/null 2>> $O/rocprof.err
 rocprofv3 --pmc WRITE_SIZE -d $O/write_sparse --output-format csv -- python3 $R/bench.py $S > /dev/null 2>> $O/rocprof.err
