@@ -384,7 +384,7 @@ __device__ __forceinline__ void ti_reset(Ctx<NCH>& c, int& nT, int& ns)
 // The fused pass for up to 64*NK slots: a wave takes rows j = w, w+4, ..., keeps D rows (D*NK loads of 512 bytes) in flight, and
 // for each row forms u = row.t (one wavefront reduction) and accumulates u*row -- the row is read once.
 // Column s of Ti is zero in the rows above crow[s] (Ti is triangular in creation order), and a lane does not load what it knows to be zero:
-// half the bytes of the pass (-DLCQP_TI_FULL_ROWS reads the full rows: cross-check).
+// half the bytes of the pass.
 template <int NK, int D>
 __device__ __forceinline__ void ti_apply_fast(const double* __restrict__ Ti, int ld, const double* tv, double* out, int nT, int ns, double* red, const int* crow, const int* slotRow)
 {
@@ -394,11 +394,7 @@ __device__ __forceinline__ void ti_apply_fast(const double* __restrict__ Ti, int
 #pragma unroll
     for (int k = 0; k < NK; k++) {
         const int sl = 64 * k + l; tr[k] = (sl < ns) ? tv[sl] : 0.0; acc[k] = 0.0;
-#ifdef LCQP_TI_FULL_ROWS
-        first[k] = (sl < ns) ? 0 : (1 << 30);
-#else
         first[k] = (sl < ns && slotRow[sl] >= 0) ? crow[sl] : (1 << 30);      // (a free slot: its column is zero everywhere)
-#endif
     }
     for (int j0 = w; j0 < nT; j0 += NWAVE * D) {
         double rv[D][NK];
@@ -665,11 +661,7 @@ __device__ __forceinline__ void ti_delete(Ctx<NCH>& c, int p, int& nT, int& ns)
     }
     for (int col = t; col < ns; col += WG) {
         // column col is zero above row crow[col] (everywhere for a free slot): rotations of zeros are skipped, in whole blocks of 16 rows
-#ifdef LCQP_TI_FULL_ROWS
-        const int cr = i0;
-#else
         const int cr = (col == p) ? i0 : ((idx[col] >= 0) ? crow[col] : (1 << 30));
-#endif
         double carry = (cr <= i0) ? Ti[(size_t)i0 * ld + col] : 0.0;
         const int jz = max(1, min(cr - i0, m));                 // rows i0 + 1 ... i0 + jz - 1 of this column are zero, and so is the carry
         for (int j = 1 + 16 * ((jz - 1) / 16); j < m; j += 16) {
@@ -741,12 +733,7 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
     constexpr int np = 128 * NCH;
     // every size sweeps through row lists (round 2 kept the plain sweep at np = 1024 because the list sweep returned wrong residuals in that
     // instantiation of the old kernel; in the round-3 kernel it is correct on every np = 1024 shape and on its own:
-    // tests/test_gpu_parity.py::test_row_list_sweep); -DLCQP_PLAIN_SWEEPS keeps the plain sweeps as a cross-check
-#ifdef LCQP_PLAIN_SWEEPS
-    constexpr bool LISTS = false;
-#else
-    constexpr bool LISTS = true;
-#endif
+    // tests/test_gpu_parity.py::test_row_list_sweep)
     const lcqp_options_t& o = c.db->opt;
     const int t = tid_here(), mE = c.mE, capS = c.capS;
     double *x = c.V(V_XT), *r1 = c.V(V_R1), *cv = c.V(V_C), *du = c.V(V_DU), *qx = c.V(V_TMP), *xs = c.V(V_XS);
@@ -845,24 +832,14 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
                       [&](int r, MapID3 v) {
                           int s = v.s;
                           if (((s == ST_LOWER && v.a > ytol) || (s == ST_UPPER && v.a < -ytol)) && (!damp || r == rLeave)) { ylv[r] = v.a; yt[r] = 0.0; st[r] = ST_INACT; s = ST_INACT; cntLv++; }
-                          if (LISTS) mg[r] = (s != ST_INACT) ? -1.0 : v.b - v.c * dl;
+                          mg[r] = (s != ST_INACT) ? -1.0 : v.b - v.c * dl;
                       });
             nlv = block_sum_i(cntLv, c.lds);
             changed = nlv > 0;
             // (b) stage 1: E_r x of the inactive rows the margins cannot rule out, and of the active rows flagged dependent
             const bool depRows = ROBUST && uniform_i(c.info->ndep) > 0;
-            int nread;
-            if (LISTS) {
-#ifdef LCQP_SCREEN_ALL      // test hook: every inactive row is read (the list machinery without the screening)
-                nread = wg_compact(mE, [&](int r) { return st[r] == ST_INACT || (depRows && dep[r]); }, list, c.lds);
-#else
-                nread = wg_compact(mE, [&](int r) { return (st[r] == ST_INACT) ? !(mg[r] > 1e-10) : (depRows && dep[r] != 0); }, list, c.lds);
-#endif
-                wg_rows<NCH, true>(c.E, list, nread, x, ex, nullptr, c.lds, [](int, double) {}, hotc, hotv);
-            } else {
-                nread = mE;
-                wg_rows<NCH>(c.E, nullptr, mE, x, ex, nullptr, c.lds, [](int, double) {}, hotc, hotv);
-            }
+            const int nread = wg_compact(mE, [&](int r) { return (st[r] == ST_INACT) ? !(mg[r] > 1e-10) : (depRows && dep[r] != 0); }, list, c.lds);
+            wg_rows<NCH, true>(c.E, list, nread, x, ex, nullptr, c.lds, [](int, double) {}, hotc, hotv);
             // Entering rows are capped (oracle: qp_polish, same arithmetic): when more than max(n/8, 16) inactive rows are violated -- a cold
             // start, where every violated row would enter at once, overshoot and oscillate for eight to ten trials with a factor rebuild
             // each -- only those at or above a cut enter (twelve bisection steps on [0, largest violation]); the others stay inactive with
@@ -873,11 +850,11 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
                 vcut = INFINITY;
                 if (!changed) {
                     double vm = 0.0;
-                    for (int a = t; a < nread; a += WG) vm = fmax(vm, violation(LISTS ? list[a] : a));
+                    for (int a = t; a < nread; a += WG) vm = fmax(vm, violation(list[a]));
                     vm = block_max(vm, c.lds);
                     if (vm > 0.0) {
                         int rb = 1 << 30;
-                        for (int a = t; a < nread; a += WG) { const int r = LISTS ? list[a] : a; if (violation(r) >= vm) rb = min(rb, r); }
+                        for (int a = t; a < nread; a += WG) { const int r = list[a]; if (violation(r) >= vm) rb = min(rb, r); }
                         rEnter = (int)(-block_max((double)(-rb), c.lds) + 0.5);
                         vcut = vm;
                     }
@@ -885,18 +862,15 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
             } else
             if (capOn) {
                 double vm = 0.0, cv = 0.0, vmax, nviol;
-                for (int a = t; a < nread; a += WG) { const double v = violation(LISTS ? list[a] : a); if (v > 0.0) { cv += 1.0; vm = fmax(vm, v); } }
+                for (int a = t; a < nread; a += WG) { const double v = violation(list[a]); if (v > 0.0) { cv += 1.0; vm = fmax(vm, v); } }
                 block_max_sum(vm, cv, vmax, nviol, c.lds);
-#ifndef LCQP_CAP_DIV
-#define LCQP_CAP_DIV 8      // (experiment switch; the oracle uses 8.  Same-box A/B of n/3, /4, /5, /6, /8, /12, /16: 31.3, 31.5-32.0, 30.6, 30.3-30.6, 30.0-30.2, 31.1, 31.9 ms)
-#endif
-                const int cap = max(c.n / LCQP_CAP_DIV, 16);
+                const int cap = max(c.n / 8, 16);      // (the oracle uses 8)
                 if (nviol > (double)cap) {
                     double lo = 0.0, hi = vmax;
                     for (int it = 0; it < 12; it++) {
                         const double mid = 0.5 * (lo + hi);
                         int cnt = 0;
-                        for (int a = t; a < nread; a += WG) cnt += (violation(LISTS ? list[a] : a) >= mid);
+                        for (int a = t; a < nread; a += WG) cnt += (violation(list[a]) >= mid);
                         if (block_sum_i(cnt, c.lds) > cap) lo = mid; else hi = mid;
                     }
                     vcut = uniform_d(lo);      // the lower end: a few more than cap rows (with the upper end a tie of many equally violated rows would never enter)
@@ -905,7 +879,7 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
             // violated rows enter; fresh margins for the others; the two rules for rows flagged dependent
             int chg = 0, cntLv2 = 0, nDense = 0;
             for (int a = t; a < nread; a += WG) {
-                const int r = LISTS ? list[a] : a;
+                const int r = list[a];
                 const int s = st[r];
                 nDense += (hotc[r] < 0);
                 const double e = ex[r], ftol = o.feasTol * (1.0 + fabs(e));
@@ -913,7 +887,7 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
                     const bool may = !damp || r == rEnter;
                     if (may && e < l[r] - ftol && l[r] - e >= vcut) { st[r] = ST_LOWER; chg |= 1; }
                     else if (may && e > u[r] + ftol && e - u[r] >= vcut) { st[r] = ST_UPPER; chg |= 1; }
-                    else if (LISTS) mg[r] = fmin(e - (l[r] - ftol), (u[r] + ftol) - e);      // (negative for a violated row that waits)
+                    else mg[r] = fmin(e - (l[r] - ftol), (u[r] + ftol) - e);      // (negative for a violated row that waits)
                 } else if (depRows && dep[r]) {
                     bool viol, inside = false;
                     if (s == ST_LOWER) { viol = e < l[r] - ftol; inside = e > l[r] + ftol; }
@@ -937,27 +911,20 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
         PROF(c, P_RESID);
         if (need_true) {
             // (c) stage 2: the true residual -- Q and the active rows of E (cold entry: every row)
-            int nact = mE;
             int* lact = c.I(I_LIST2);
             wg_symv<NCH>(c.Q, nullptr, c.n, x, nullptr, qx, nullptr, nullptr, nullptr, c.lds);
-            if (LISTS) {
-                nact = wg_compact(mE, [&](int r) { return cold || st[r] != ST_INACT; }, lact, c.lds);
-                // du: the residual of the QP as given (the next hot start and A'y need it without the proximal term); r1: with it
-                wg_rows<NCH, true>(c.E, lact, nact, x, ex, yt, c.lds, [&](int i, double s) { const double ro = -g[i] - qx[i] - s; du[i] = ro; r1[i] = ro - spv * (x[i] - xref[i]); cv[i] = fabs(g[i]) + fabs(qx[i]) + fabs(s); }, hotc, hotv);
-            } else {
-                wg_rows<NCH>(c.E, nullptr, mE, x, ex, yt, c.lds, [&](int i, double s) { const double ro = -g[i] - qx[i] - s; du[i] = ro; r1[i] = ro - spv * (x[i] - xref[i]); cv[i] = fabs(g[i]) + fabs(qx[i]) + fabs(s); }, hotc, hotv);
-            }
+            const int nact = wg_compact(mE, [&](int r) { return cold || st[r] != ST_INACT; }, lact, c.lds);
+            // du: the residual of the QP as given (the next hot start and A'y need it without the proximal term); r1: with it
+            wg_rows<NCH, true>(c.E, lact, nact, x, ex, yt, c.lds, [&](int i, double s) { const double ro = -g[i] - qx[i] - s; du[i] = ro; r1[i] = ro - spv * (x[i] - xref[i]); cv[i] = fabs(g[i]) + fabs(qx[i]) + fabs(s); }, hotc, hotv);
             c.cSweeps++;
             if (cold) {
                 if (t == 0) c.info->work[4] += (double)(nact - uniform_i(c.info->nHot));
-                if (LISTS) {
-                    wg_map<4>(mE, [&](int r) { return MapID3{st[r], ex[r], l[r], u[r]}; },
-                              [&](int r, MapID3 v) {
-                                  const double e = v.a, ftol = o.feasTol * (1.0 + fabs(e));
-                                  mg[r] = (v.s != ST_INACT) ? -1.0 : fmin(e - (v.b - ftol), (v.c + ftol) - e);
-                              });
-                    __syncthreads();
-                }
+                wg_map<4>(mE, [&](int r) { return MapID3{st[r], ex[r], l[r], u[r]}; },
+                          [&](int r, MapID3 v) {
+                              const double e = v.a, ftol = o.feasTol * (1.0 + fabs(e));
+                              mg[r] = (v.s != ST_INACT) ? -1.0 : fmin(e - (v.b - ftol), (v.c + ftol) - e);
+                          });
+                __syncthreads();
             } else {
                 // (round 6; oracle: the same) THE RESIDUAL'S OWN ROUNDING FLOOR.  r1 is a sum of three vectors, g, Qx and E'y: it cannot be evaluated,
                 // let alone reduced by a correction, below a few dozen roundings of the largest.  On a QP whose solution lies far out along a flat
@@ -969,7 +936,7 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
                 const double rtolS = uniform_d(fmax(rtolG, 64.0 * 2.221e-16 * rscale));
                 double res_eq = 0.0, bmax = 0.0, nDense2 = 0.0;
                 for (int a = t; a < nact; a += WG) {
-                    const int r = LISTS ? lact[a] : a;
+                    const int r = lact[a];
                     const int s = st[r];
                     nDense2 += (hotc[r] < 0) ? 1.0 : 0.0;
                     if (s == ST_INACT) continue;
@@ -1122,11 +1089,7 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
             PROF(c, P_CORR_L1);
             if (na > 0) {
                 // (plain loads: the same rows are read again a few microseconds later; same-box A/B 35.1 -> 33.8 ms)
-#ifdef LCQP_NO_ET_KEEP
-                wg_rows<NCH>(c.Et, idx, nsl, cv, dy, nullptr, c.lds, [](int, double) {});
-#else
                 wg_rows<NCH, false, true>(c.Et, idx, nsl, cv, dy, nullptr, c.lds, [](int, double) {});
-#endif
                 for (int a = t; a < nsp; a += WG) dy[a] = (a < nsl && idx[a] >= 0) ? dy[a] - r2[a] : 0.0;
                 __syncthreads();
                 PROF(c, P_CORR_ROWS);

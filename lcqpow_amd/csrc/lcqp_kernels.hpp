@@ -463,11 +463,8 @@ __device__ __forceinline__ void trsm_rows_streamed(const DevBatch& db)
 template <int NCH>
 __global__ __launch_bounds__(WG) void k_trsm(DevBatch db)
 {
-#ifndef LCQP_TILE_VALU
     if constexpr (NCH <= 2) trsm_rows_resident<NCH>(db);
-    else
-#endif
-        trsm_rows_streamed<NCH>(db);
+    else trsm_rows_streamed<NCH>(db);
 }
 
 // the streamed form for every size: 52 registers and 36 KB of LDS, a workgroup fits where ONE instance of k_lcqp_run has finished
@@ -741,14 +738,12 @@ __global__ __launch_bounds__(WG) void k_util_rows_list(int m, int nlist, const d
 template <int NCH>
 static void launch_run(int grid, hipStream_t s, const LaunchArgs& a)
 {
-#ifndef LCQP_NO_LDS_ROWS      // experiment switch: the row state in global memory for every size
     if constexpr (NCH <= 2) {
         // the row state sits behind the routines' scratch (arena[0, LDS_ROWS_OFF)): the sweeps need 6 np doubles there, the triangular solves
         // 5 np, the widest pass over the inverse factor 4 capS, the rotations 3 capS
         static_assert(6 * 128 * NCH <= LDS_ROWS_OFF, "k_lcqp_run<NCH, true>: the sweeps' scratch must end below the row state");
         if (a.db.mEcap <= LDS_ROWS_MAX && 4 * a.db.capS <= LDS_ROWS_OFF) { hipLaunchKernelGGL((k_lcqp_run<NCH, true, LCQP_VARIANT>), dim3(grid), dim3(WG), 0, s, a.db); return; }
     }
-#endif
     hipLaunchKernelGGL((k_lcqp_run<NCH, false, LCQP_VARIANT>), dim3(grid), dim3(WG), 0, s, a.db);
 }
 

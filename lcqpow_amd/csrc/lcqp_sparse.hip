@@ -38,15 +38,7 @@ namespace {
 constexpr int SP_WMAX = 63;
 constexpr int SP_KBMAX = 16;   // border nodes of the bordered band (rows / variables too dense for a band)
 constexpr int WGS = 64;      // one wavefront per workgroup; 64 / G instances in it
-#ifndef SP_WAVES_PER_SIMD
-#define SP_WAVES_PER_SIMD 2  // register budget of k_sparse_sched: 512 / SP_WAVES_PER_SIMD per lane
-#endif
-#ifndef SP_SWEEP_RING
-#define SP_SWEEP_RING 8      // coefficient chunks (8 steps each) of a band sweep in flight at G = 8: seven chunks = 56 steps ahead of use, 8 800 / 5 600 clocks of
-                             // the forward / backward sweep (with 4: 3 800 / 2 400, less than a round trip to memory on a busy machine -- the sweeps of a full
-                             // machine took 1.7 x the time of a lone instance's; profiles/round5/sparse_sweep_ring8_ab.log: +5.5 % at B = 1024, +3.6 % at 4096,
-                             // -1.6 % at 16 384, +-0 at 65 536; round 4 had measured it at 65 536 only)
-#endif
+constexpr int SCHED_WAVES_PER_SIMD = 2;   // register budget of k_sparse_sched at G <= 8: 512 / SCHED_WAVES_PER_SIMD per lane
 enum { NV_G, NV_GTIL, NV_GPHI, NV_XK, NV_PK, NV_XNEW, NV_GK, NV_QX, NV_CX, NV_QP, NV_CP, NV_TMP, NV_XQ, NV_XA, NV_XT, NV_R1,
        NV_X0, NV_NUM };
 enum { MV_L, MV_U, MV_RHOV, MV_YQ, MV_YA, MV_ZA, MV_YT, MV_EX, MV_YK, MV_Y0, MV_LX, MV_LX2, MV_NUM };
@@ -734,15 +726,8 @@ __device__ __forceinline__ void sp_general_front(SpCtx<64>& c, int f, FA F, doub
     const unsigned Loff = (unsigned)mt[8], CBoff = (unsigned)mt[9];
     const int ff = np + nb;
     auto sync = [&]() { if (LDSF) wave_sync(); else g_sync(); };
-#ifdef GEN_PROFILE      // (diagnostic: the parts of a front on the profile slots the rest of the engine hardly uses: zero -> products, assembly -> status test, children -> vectors, elimination -> factorisation, stores -> rhs)
-#define GPROF(c, P) SPROF(c, P)
-#else
-#define GPROF(c, P) do { } while (0)
-#endif
-    GPROF(c, SP_LCQP);
     for (int e = t; e < ff * ff; e += 64) F[e] = 0.0;
     sync();
-    GPROF(c, SP_PRODUCTS);
     {   // the entries of K whose column is a pivot of this front (one entry of Q or E each: distinct positions); rows of E gated by value
         GD Qv = c.Qx(), Ev = c.Ex();
         for (int e = asm0 + t; e < asm1; e += 64) {
@@ -758,7 +743,6 @@ __device__ __forceinline__ void sp_general_front(SpCtx<64>& c, int f, FA F, doub
         else F[j + ff * j] = in(node - n) ? -ddual(node - n) : -1.0;
     }
     sync();
-    GPROF(c, SP_ASSEMBLE);
     for (int ci = ch0; ci < ch1; ci++) {      // extend-add: the children's update blocks, one child after the other
         const int* cm = db.gChildInfo + (size_t)ci * 4;
         const int nbc = cm[0];
@@ -770,7 +754,6 @@ __device__ __forceinline__ void sp_general_front(SpCtx<64>& c, int f, FA F, doub
         }
         sync();
     }
-    GPROF(c, SP_VECTORS);
     double* dv = c.win + GEN_MAX_FRONT * GEN_JB;      // 1 / D of the block's pivots (behind the largest panel either variant uses)
     GD Lp = Lst + (int)Loff;
     for (int j0 = 0; j0 < np; j0 += GEN_JB) {
@@ -866,13 +849,11 @@ __device__ __forceinline__ void sp_general_front(SpCtx<64>& c, int f, FA F, doub
         }
         sync();
     }
-    GPROF(c, LDSF ? SP_FACTOR : SP_LCQP);      // (elimination of a front in LDS / of a front in memory)
     {   // the update block goes onto the stack (its place was fixed by the host: where its children's blocks lay)
         GD CB = stack + (int)CBoff;
         for (int e = t; e < nb * nb; e += 64) { const int b = e / nb, a = e - b * nb; if (a >= b) CB[a + nb * b] = (double)F[(np + a) + ff * (np + b)]; }
     }
     g_sync();
-    GPROF(c, SP_RHS);
 }
 
 template <class Dd, class Use>
@@ -935,14 +916,9 @@ __device__ __forceinline__ void sp_general_sweep(SpCtx<64>& c, GD Lst, GD b)
             // address that does not depend on the chain -- a pivot step is a broadcast and a fused multiply-add, ~30 clocks, where the version
             // through LDS (below, kept for larger fronts) paid a read - modify - write round trip of the right-hand side per pivot, ~1000 clocks
             // with one wavefront per SIMD.  Backward in axpy form too (a finished x_i leaves every earlier row), so no reduction sits in the chain.
-            const int ldp = ff | 1;                                 // odd leading dimension: the row access of the backward sweep is free of bank conflicts
-            double* Pf = c.win;
             wave_sync();
             // forward: lane t reads ITS entry of column j straight from the factor (coalesced; the addresses do not depend on the chain, so the
-            // loads of all columns are in flight together) -- no staging in LDS; backward needs rows of the panel: staged with an odd leading dimension
-#ifdef GEN_STAGE_BACKWARD
-            if (!FWD) for (int e = t; e < ff * np; e += 64) { const int cc = e / ff, i = e - cc * ff; Pf[i + ldp * cc] = (i > cc) ? (double)Lp[i + ff * cc] : 0.0; }
-#endif
+            // loads of all columns are in flight together) -- no staging in LDS
             double x = (t < ff) ? (double)b[t < np ? piv0 + t : rows[t - np]] : 0.0;
             wave_sync();
             if (FWD) {
@@ -955,16 +931,8 @@ __device__ __forceinline__ void sp_general_sweep(SpCtx<64>& c, GD Lst, GD b)
                 }
                 if (t < ff) b[t < np ? piv0 + t : rows[t - np]] = x;
             } else {
-#ifdef GEN_STAGE_BACKWARD
-                for (int i = ff - 1; i >= 1; i--) {
-                    const double xi = wave_bcast(x, i);
-                    const double lit = (t < i && t < np) ? Pf[i + ldp * t] : 0.0;      // L[i][t]: a row of the panel
-                    x -= lit * xi;
-                }
-#else
                 // backward: lane t (a pivot) walks down ITS column of the panel, L[i][t] for i = ff-1 .. t+1 -- contiguous per lane (a cache line serves
-                // eight steps), a stride of ff between the lanes; again no address depends on the chain, eight loads in flight (a row-major copy of
-                // the panels for coalesced rows was measured: slower, 3.43 -> 3.59 s, the extra stores cost more than the strides)
+                // eight steps), a stride of ff between the lanes; again no address depends on the chain, eight loads in flight
                 for (int i0 = ff - 1; i0 >= 1; i0 -= 8) {
                     double lv[8];
 #pragma unroll
@@ -972,7 +940,6 @@ __device__ __forceinline__ void sp_general_sweep(SpCtx<64>& c, GD Lst, GD b)
 #pragma unroll
                     for (int u = 0; u < 8; u++) { const int i = i0 - u; if (i >= 1) { const double xi = wave_bcast(x, i); x -= lv[u] * xi; } }
                 }
-#endif
                 if (t < np) b[piv0 + t] = x;
             }
             g_sync();
@@ -1097,7 +1064,9 @@ __device__ __forceinline__ void sp_factor_band(SpCtx<G>& c, GD KF, GD Kd, double
 template <int G, bool FWD>
 __device__ __forceinline__ void band_sweep(GD K, GD Kd, GD b, int Np, int gl)
 {
-    constexpr int CH = G < 16 ? G : 16, NCHUNK = 64 / CH, BPS = 64 / G, RING = (G == 8) ? SP_SWEEP_RING : 2;
+    // RING: coefficient chunks (CH steps each) in flight.  At G = 8 eight: seven chunks = 56 steps ahead of use, 8 800 / 5 600 clocks of the
+    // forward / backward sweep, more than a round trip to memory on a busy machine (profiles/round5/sparse_sweep_ring8_ab.log)
+    constexpr int CH = G < 16 ? G : 16, NCHUNK = 64 / CH, BPS = 64 / G, RING = (G == 8) ? 8 : 2;
     static_assert(RING >= 2 && NCHUNK % RING == 0, "the ring slots are assigned statically per 64 positions: RING has to divide 64 / CH (6 gave wrong coefficients and a run without end)");
     gl = here(gl);
     auto at = [&](int p) -> int { return FWD ? p : Np - 1 - p; };
@@ -1942,19 +1911,8 @@ __global__ __launch_bounds__(WGS) void k_sparse_setup(SpBatch db)
 // whichever wavefront runs its next phase.
 // agent scope: a pool is served by wavefronts of several XCDs, whose L2s are not coherent with each other -- the release writes the L2 back, the
 // acquire invalidates L1 and L2 (workgroup-scope fences in their place: stale vectors, more iterates, 15 - 25 % SLOWER; profiles/round4)
-#ifdef SP_XCD_POOLS
-// EXPERIMENT (round 5, -DSP_XCD_POOLS; needs a pool count that is a multiple of 8, LCQP_SPARSE_POOL): a pool is served only by wavefronts of
-// ONE XCD (chosen by the XCC id the wavefront reads from its hardware register: wavefronts do not migrate), so everything an instance's
-// phases read and write goes through one L2 and the hand-over needs no L2 write-back and no L2 invalidation: the release waits for the
-// stores to reach L2 (the vector L1 is write-through), the acquire invalidates the vector L1 only.  Measured (profiles/round5/
-// sparse_xcd_pools_light_fences_dropped.log): same results, 10 400 - 10 800 against 12 700 LCQPs/s at B = 65 536, 73 against 11 000 at
-// B = 16 384 (one pool per XCD: the wavefronts of an XCD all wait on one pool's queues).  The L2 invalidations are not where the traffic is.
-#define SP_ACQUIRE() do { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); asm volatile("buffer_inv sc0" ::: "memory"); } while (0)
-#define SP_RELEASE() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); } while (0)
-#else
 #define SP_ACQUIRE() __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent")
 #define SP_RELEASE() __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent")
-#endif
 __device__ __forceinline__ int q_load(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ unsigned long long q_load64(const unsigned long long* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void q_store64(unsigned long long* p, unsigned long long v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -1965,22 +1923,7 @@ __device__ __forceinline__ unsigned long long q_slot(int seq, int id) { return (
 // sparse products and element-wise loops, 60 % of the time) take ONE instance with all 64 lanes -- a wavefront instruction then reads 512
 // contiguous bytes of one instance instead of eight 64-byte pieces of eight instances, the access pattern this part streams best
 // (tools/micro/stream_pattern.py: 2.4 TB/s for eight far-apart pieces per wavefront, 5.8 TB/s for one stream).
-#ifndef SP_WIDE_LANES
-#define SP_WIDE_LANES 64      // (experiment switch: 0 = every phase with G lanes per instance, the first phase machine of round 4)
-#endif
-#ifndef SP_CHAIN
-#define SP_CHAIN 1            // (experiment switch: 0 = every phase change goes through the queues)
-#endif
-#ifndef SP_WIDE_BATCH
-#define SP_WIDE_BATCH 16      // passes of a streaming step: instances popped at once = SP_WIDE_BATCH * 64 / SP_WIDE_LANES
-#endif
-#ifndef SP_CHAIN_BAND
-#define SP_CHAIN_BAND 1
-#endif
-#ifndef SP_BAND_BATCH
-#define SP_BAND_BATCH 1       // passes of a band step
-#endif
-static_assert(SP_WIDE_BATCH * (SP_WIDE_LANES ? 64 / SP_WIDE_LANES : 8) <= 64 && SP_BAND_BATCH <= 8, "a step holds its instances one per lane");
+constexpr int WIDE_BATCH_MAX = 16;      // instances of a streaming step at most (one per lane)
 template <int G, int GP>
 __device__ __forceinline__ int sp_run_phase(const SpBatch& db, int ph, int b, int w0, int lane)
 {
@@ -1998,7 +1941,7 @@ __device__ __forceinline__ int sp_run_phase(const SpBatch& db, int ph, int b, in
     GD gk = c.V(NV_GK);
     int next;
     if constexpr (GP == G) {
-        // every phase can run with the band's lane group (the streaming ones do when SP_WIDE_LANES == 0 or G == 64)
+        // every phase can run with the band's lane group (the streaming ones do at G == 64)
         switch (ph) {
             case PH_START:   c.cAdmm = c.cTrials = c.cFact = c.cCorr = c.cSweeps = 0; c.bytes = 0.0; next = sp_ph_start<GP>(c, S); break;
             case PH_ROUND:   next = sp_ph_round<GP>(c, S, gk); break;
@@ -2023,22 +1966,16 @@ __device__ __forceinline__ int sp_run_phase(const SpBatch& db, int ph, int b, in
 }
 
 template <int G>
-__global__ __launch_bounds__(WGS, (G <= 8 ? SP_WAVES_PER_SIMD : 1)) void k_sparse_sched(SpBatch db)
+__global__ __launch_bounds__(WGS, (G <= 8 ? SCHED_WAVES_PER_SIMD : 1)) void k_sparse_sched(SpBatch db)
 {
     constexpr int IPW = 64 / G;
-    constexpr int GW = (SP_WIDE_LANES > G) ? SP_WIDE_LANES : G;      // lanes per instance of the streaming phases
+    constexpr int GW = 64;      // lanes per instance of the streaming phases
     constexpr int IPWW = 64 / GW;
     __shared__ int s_id[WGS], s_next[WGS], s_ctl[2];      // the step's instances, where each goes next; [0] how many they are, [1] polls without work in a row
     // the pool's queues, derived afresh in front of the pop and in front of the push: nothing of the scheduler is alive across a phase
     struct Q { int w0, mask; unsigned long long* ring; int* ctl; int* remaining; };
     auto queues = [&]() {
-#ifdef SP_XCD_POOLS
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        int pool = (int)(xcc & 7u) + 8 * (int)((blockIdx.x >> 3) % (unsigned)(db.nPools >> 3));
-#else
         int pool = blockIdx.x % db.nPools;
-#endif
         asm volatile("" : "+s"(pool));
         Q q;
         q.w0 = pool * db.poolSize; q.mask = db.poolSize - 1;
@@ -2069,12 +2006,12 @@ __global__ __launch_bounds__(WGS, (G <= 8 ? SP_WAVES_PER_SIMD : 1)) void k_spars
             if (ph >= 0) {
                 // instances of a streaming step: they run one after the other on this wavefront, so a long step makes the last of them wait
                 // for the others while wavefronts elsewhere poll -- P = unfinished instances per SIMD of the machine up to 4, P / 2 beyond,
-                // at most SP_WIDE_BATCH (the fences of a step are paid once for all of them: full steps for batches that fill the
+                // at most WIDE_BATCH_MAX (the fences of a step are paid once for all of them: full steps for batches that fill the
                 // machine).  profiles/round5/sparse_wide_batch_rule.log: against 16 per step +20 % at B = 1024, +15 % at 2048, +11 % at
                 // 4096, +7 % at 8192, the same from 16 384 on
-                int wb = SP_WIDE_BATCH;
-                if (isWide(ph)) { const int P = q_load(remaining) / db.wideDiv; wb = max(1, min(SP_WIDE_BATCH, P <= 4 ? P : max(4, P >> 1))); }
-                take = min(best, isWide(ph) ? IPWW * wb : IPW * SP_BAND_BATCH);
+                int wb = WIDE_BATCH_MAX;
+                if (isWide(ph)) { const int P = q_load(remaining) / db.wideDiv; wb = max(1, min(WIDE_BATCH_MAX, P <= 4 ? P : max(4, P >> 1))); }
+                take = min(best, isWide(ph) ? IPWW * wb : IPW);
                 if (atomicCAS(&ctl[ph * QCTL + 2], best, best - take) == best) base = atomicAdd(&ctl[ph * QCTL + 1], take);
                 else { ph = -1; take = 0; }      // somebody else moved the counter: look again
             }
@@ -2089,11 +2026,8 @@ __global__ __launch_bounds__(WGS, (G <= 8 ? SP_WAVES_PER_SIMD : 1)) void k_spars
             if (lane == 0) s_ctl[1] = idle;
             // back off: a wavefront that finds nothing polls again later and later (each poll reads the pool's counters through the L2 all
             // wavefronts of the pool share; with s_sleep(32) per poll a quarter of idle wavefronts halved the rate of the working ones:
-            // profiles/round5/sparse_waves.log) -- 2^min(idle, SP_BACKOFF_MAX) / 8 sleeps of 127 x 64 clocks, at most ~ 60 us
-#ifndef SP_BACKOFF_MAX
-#define SP_BACKOFF_MAX 7
-#endif
-            if (idle > 2) { const int reps = (1 << min(idle, SP_BACKOFF_MAX)) >> 3; for (int k = 0; k < max(reps, 1); k++) __builtin_amdgcn_s_sleep(127); }
+            // profiles/round5/sparse_waves.log) -- 2^min(idle, 7) / 8 sleeps of 127 x 64 clocks, at most ~ 60 us
+            if (idle > 2) { const int reps = (1 << min(idle, 7)) >> 3; for (int k = 0; k < max(reps, 1); k++) __builtin_amdgcn_s_sleep(127); }
 #ifdef LCQP_SCHED_PROFILE
             if (lane == 0) { atomicAdd(&db.qprof[PH_NUM * 3 + 0], __builtin_amdgcn_s_memtime() - tq0); atomicAdd(&db.qprof[PH_NUM * 3 + 1], 1ull); }
 #endif
@@ -2119,7 +2053,7 @@ __global__ __launch_bounds__(WGS, (G <= 8 ? SP_WAVES_PER_SIMD : 1)) void k_spars
         s_id[lane] = myid;
         __builtin_amdgcn_wave_barrier();
         if (wide) {
-            // streaming phases: the instances popped (up to SP_WIDE_BATCH) one after the other, GW lanes each, so that the fences of the step
+            // streaming phases: the instances popped (up to WIDE_BATCH_MAX) one after the other, GW lanes each, so that the fences of the step
             // -- the release writes back the whole XCD's L2 -- are paid once for all of them.  A streaming phase that leads to another one
             // (an accepted trial -> the end of its QP -> the first trial of the next) stays here: same lanes, same instance, its own stores in
             // program order -- no queue, no fences.
@@ -2129,19 +2063,19 @@ __global__ __launch_bounds__(WGS, (G <= 8 ? SP_WAVES_PER_SIMD : 1)) void k_spars
                 if (bj >= 0)
                     for (int p = ph;; p = nj) {
                         nj = sp_run_phase<G, GW>(db, p, bj, w0, ln);
-                        if (SP_CHAIN == 0 || !(nj == PH_TRIAL || nj == PH_QPEND)) break;
+                        if (!(nj == PH_TRIAL || nj == PH_QPEND)) break;
                     }
                 if ((ln & (GW - 1)) == 0) s_next[j + ln / GW] = nj;
             }
         } else {
-            // band phases: 64 / G instances side by side, SP_BAND_BATCH such passes per step
+            // band phases: 64 / G instances side by side, one such pass per step
             for (int j = 0; j < take; j += IPW) {
                 const int l0 = here(lane), bj = s_id[j + l0 / G];
                 int nj = -1;
                 if (bj >= 0)
                     for (int p = ph;; p = nj) {      // (a factorisation is always followed by its correction: same lanes, same instances)
                         nj = sp_run_phase<G, G>(db, p, here(bj), w0, here(l0));      // (re-laundered per pass: nothing of the instance's addressing is carried around the loop)
-                        if (SP_CHAIN_BAND == 0 || !(p == PH_FACTOR && nj == PH_CORRECT)) break;
+                        if (!(p == PH_FACTOR && nj == PH_CORRECT)) break;
                     }
                 if ((l0 & (G - 1)) == 0) s_next[j + l0 / G] = nj;
             }
@@ -2209,13 +2143,10 @@ static void sp_launch(const SpBatch& db, hipStream_t stream, hipEvent_t mid)
     // QP ends; with a wavefront per instance (up to 256) or per four instances B = 64 gains 52 %, 256: 44 %, 512: 39 %, 1024: 23 %, 2048: 12 %,
     // 8192: 4 % (4096: +-0); idle wavefronts back off exponentially, so the surplus costs nothing.
     int waves = std::max(grid, std::max(std::min(db.B, 256), db.B / 4));
-    const int resident = cus * 4 * (G <= 8 ? SP_WAVES_PER_SIMD : 1);      // (k_sparse_sched's launch bounds)
-    waves = std::min(waves, resident);
-    if (const char* e = std::getenv("LCQP_SPARSE_WAVES")) { const int v = std::atoi(e); if (v >= 1) waves = std::min(v, resident); }      // experiment switch
+    waves = std::min(waves, cus * 4 * (G <= 8 ? SCHED_WAVES_PER_SIMD : 1));      // resident at once (k_sparse_sched's launch bounds)
     waves = ((waves + db.nPools - 1) / db.nPools) * db.nPools;
     SpBatch dbs = db;
     dbs.wideDiv = std::max(1, cus * 4 / std::max(1, db.nPools));
-    if (const char* e = std::getenv("LCQP_SPARSE_WIDE_DIV")) { const int v = std::atoi(e); if (v >= 1) dbs.wideDiv = v; }      // experiment switch
     hipLaunchKernelGGL(k_sparse_sched<G>, dim3(waves), dim3(WGS), ldsBytes, stream, dbs);
 }
 
@@ -2798,7 +2729,7 @@ extern "C" int lcqp_hip_sparse_get_solution(lcqp_hip_sparse_t* h, double* x, dou
 // (products, assembly, factorisation, forward sweeps, backward sweeps, vector operations, LCQP level, -)
 extern "C" int lcqp_hip_sparse_read_profile(lcqp_hip_sparse_t* h, double* out)
 try {
-#if defined(LCQP_PROFILE) || defined(SP_DEBUG)
+#ifdef LCQP_PROFILE
     if (!h || !out) return LCQP_INVALID_ARGUMENT;
     SpBatch& d = h->db;
     SPCHK(hipSetDevice(h->device));

@@ -49,15 +49,10 @@ struct Lds {
 
 // Matrix streams (rows of Q, E, Et, the factor L1): every byte is used once per pass and the matrices of a batch (12 GB) never fit a
 // cache, so these loads are non-temporal and leave L2 / the Infinity Cache to what IS re-read: the vectors and the inverse factor T
-// (139 KB per instance).  Same-box A/B 40.1 -> 38.3 ms (profiles/round3); -DLCQP_NO_NT_STREAMS restores plain loads.
-#ifndef LCQP_NO_NT_STREAMS
+// (139 KB per instance).  Same-box A/B 40.1 -> 38.3 ms (profiles/round3).
 typedef double d2v_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ double2 ld_stream(const double2* p) { const d2v_t v = __builtin_nontemporal_load(reinterpret_cast<const d2v_t*>(p)); return double2{v.x, v.y}; }
 __device__ __forceinline__ double ld_stream(const double* p) { return __builtin_nontemporal_load(p); }
-#else
-__device__ __forceinline__ double2 ld_stream(const double2* p) { return *p; }
-__device__ __forceinline__ double ld_stream(const double* p) { return *p; }
-#endif
 
 // Everything a thread computes from its thread number and uniform values is invariant in every loop of a kernel, and the compiler
 // hoists it all to the top of the kernel (hundreds of addresses and masks, spilled to scratch at once).  An empty volatile asm cannot
@@ -65,9 +60,6 @@ __device__ __forceinline__ double ld_stream(const double* p) { return *p; }
 __device__ __forceinline__ int tid_here() { int t = threadIdx.x; asm volatile("" : "+v"(t)); return t; }
 __device__ __forceinline__ int lane_id() { return tid_here() & 63; }
 __device__ __forceinline__ int wave_id() { return tid_here() >> 6; }
-#ifndef LCQP_SEQ_WAVE
-#define LCQP_SEQ_WAVE 1
-#endif
 
 __device__ __forceinline__ double wave_sum(double v)
 {
@@ -303,11 +295,9 @@ __device__ __forceinline__ void wg_combine(const double (&acc)[2 * NCH], Lds lds
 // Rows in flight: a wave keeps ROWS_IN_FLIGHT rows (2 KiB each at np = 256) of every swept matrix outstanding before it
 // consumes the oldest one.  The kernel is bound by the bytes it keeps in flight, not by issue (4 waves per SIMD, 84 % of the
 // wave cycles parked on memory with one row per wave outstanding -- profiles/round1/final/pmc_sq.txt), so the sweeps
-// load LCQP_DEPTH rows, then consume them.  Rows beyond n are read from the zero padding (np is a multiple of 128).
-#ifndef LCQP_DEPTH
-#define LCQP_DEPTH 4
-#endif
-static_assert(LCQP_DEPTH == 1 || LCQP_DEPTH == 2 || LCQP_DEPTH == 4 || LCQP_DEPTH == 8, "LCQP_DEPTH: the sweeps read NWAVE * LCQP_DEPTH rows per step and rely on that dividing the padded sizes (a build with 3, 5 or 6 reads past the matrix)");
+// load ROWS_IN_FLIGHT rows, then consume them.  Rows beyond n are read from the zero padding (np is a multiple of 128).
+constexpr int ROWS_IN_FLIGHT = 4;
+static_assert(ROWS_IN_FLIGHT == 2 || ROWS_IN_FLIGHT == 4 || ROWS_IN_FLIGHT == 8, "ROWS_IN_FLIGHT: the sweeps read NWAVE * ROWS_IN_FLIGHT rows per step and rely on that dividing the padded sizes (3, 5 or 6 reads past the matrix)");
 // DCAP: at most this many rows in flight (a call site that keeps many registers live across the sweep passes 1)
 template <int NCH, bool TWO_M, bool TWO_V, int DCAP = 8>
 __device__ __forceinline__ void wg_symv_t(const double* __restrict__ M0, const double* __restrict__ M1, int n,
@@ -315,7 +305,7 @@ __device__ __forceinline__ void wg_symv_t(const double* __restrict__ M0, const d
                         double* o00, double* o10, double* o01, double* o11, Lds lds)
 {
     constexpr int np = 128 * NCH;
-    constexpr int D0 = (NCH > 8 || (TWO_M && NCH >= 4)) ? 1 : (TWO_M ? (LCQP_DEPTH >= 2 ? LCQP_DEPTH / 2 : 1) : LCQP_DEPTH);
+    constexpr int D0 = (NCH > 8 || (TWO_M && NCH >= 4)) ? 1 : (TWO_M ? ROWS_IN_FLIGHT / 2 : ROWS_IN_FLIGHT);
     constexpr int D = D0 < DCAP ? D0 : DCAP;      // (np = 2048: a row is 8 KiB per wave already; the two-matrix sweep runs once per homotopy)
     static_assert((wg_ncopy(NCH) + 2) * np <= arena_doubles(NCH), "wg_symv: the partial copies and two staged vectors must fit the LDS arena");
     double* sv0 = lds.arena + wg_ncopy(NCH) * np;
@@ -451,7 +441,7 @@ __device__ __forceinline__ void wg_rows(const double* __restrict__ Mx, const int
         acc[2 * k] = acc[2 * k + 1] = 0.0;
     }
     const int nchunk = (m + 15) >> 4;
-    constexpr int D = (NCH > 8) ? 1 : ((NCH == 4 && LCQP_DEPTH > 2) ? 2 : LCQP_DEPTH);     // rows a wave keeps in flight (see wg_symv_t; np = 512 at 128 VGPRs: two rows of 4 KiB, four spill)
+    constexpr int D = (NCH > 8) ? 1 : (NCH == 4 ? 2 : ROWS_IN_FLIGHT);     // rows a wave keeps in flight (see wg_symv_t; np = 512 at 128 VGPRs: two rows of 4 KiB, four spill)
     for (int ch = w; ch < nchunk; ch += NWAVE) {
         const int a0 = ch << 4;
         const int mya = a0 + l;
@@ -533,14 +523,10 @@ __device__ __forceinline__ void wg_trsv(const double* __restrict__ F, int ld, in
             const double* Fd = F + (size_t)(64 * I) * ld + 64 * I;
             double f[16];
 #pragma unroll
-            for (int cc = 0; cc < 16; cc++) {      // only the triangle is fetched: lanes outside it issue no load (LCQP_TRSV_FULL_DIAG: all)
+            for (int cc = 0; cc < 16; cc++) {      // only the triangle is fetched: lanes outside it issue no load
                 const int c = 16 * w + cc;
-#ifdef LCQP_TRSV_FULL_DIAG
-                f[cc] = Fd[(size_t)c * ld + l];
-#else
                 f[cc] = 0.0;
                 if (forward ? (c <= l) : (c >= l)) f[cc] = ld_stream(Fd + (size_t)c * ld + l);
-#endif
             }
             double acc = 0.0;
 #pragma unroll
@@ -586,52 +572,26 @@ __device__ __forceinline__ void wg_trsv(const double* __restrict__ F, int ld, in
 // ---------------------------------------------------------------------------------------------
 // 64x64 output tiles are accumulated from k-major LDS panels As[16][TILE_PL], Bs[16][TILE_PL]
 // (As[k][i] = A operand of output row i, Bs[k][j] = B operand of output column j).
-// Default: fp64 matrix cores, v_mfma_f64_16x16x4_f64 -- wave w owns output rows 16w..16w+15 as four 16x16
+// fp64 matrix cores, v_mfma_f64_16x16x4_f64 -- wave w owns output rows 16w..16w+15 as four 16x16
 // blocks; acc[a][b] is block a (columns 16a..16a+15), accumulator register b:
 //     row = 16w + (lane>>4) + 4b,   col = 16a + (lane&15)            (C/D layout of the f64 MFMA)
 // A operand: one f64 per lane, A[i = lane&15][k = lane>>4]; B operand: B[k = lane>>4][j = lane&15].
-// -DLCQP_TILE_VALU selects the 4x4-per-thread v_fma_f64 micro-kernel instead (same peak rate on gfx950;
-// kept as the cross-check of the MFMA lane maps): row = 4*(tid>>4) + a, col = 4*(tid&15) + b.
 // ---------------------------------------------------------------------------------------------
 constexpr int TILE_PL = 80;   // panel pitch in doubles: 160 dwords = 32 mod 64 banks -> conflict-free MFMA operand reads
 typedef double d4_t __attribute__((ext_vector_type(4)));
 
 __device__ __forceinline__ int tile_li(int a, int b)
 {
-#ifdef LCQP_TILE_VALU
-    (void)b; return 4 * (tid_here() >> 4) + a;
-#else
     (void)a; return 16 * wave_id() + (lane_id() >> 4) + 4 * b;
-#endif
 }
 __device__ __forceinline__ int tile_lj(int a, int b)
 {
-#ifdef LCQP_TILE_VALU
-    (void)a; return 4 * (tid_here() & 15) + b;
-#else
     (void)b; return 16 * a + (lane_id() & 15);
-#endif
 }
 
 // acc += As' * Bs over the 16 staged k values
 __device__ __forceinline__ void tile_panel(double (&acc)[4][4], const double* As, const double* Bs)
 {
-#ifdef LCQP_TILE_VALU
-    const int ty = tid_here() >> 4, tx = tid_here() & 15;
-#pragma unroll
-    for (int kk = 0; kk < 16; kk++) {
-        const double2 av0 = *reinterpret_cast<const double2*>(As + kk * TILE_PL + 4 * ty);
-        const double2 av1 = *reinterpret_cast<const double2*>(As + kk * TILE_PL + 4 * ty + 2);
-        const double2 bv0 = *reinterpret_cast<const double2*>(Bs + kk * TILE_PL + 4 * tx);
-        const double2 bv1 = *reinterpret_cast<const double2*>(Bs + kk * TILE_PL + 4 * tx + 2);
-        const double a[4] = {av0.x, av0.y, av1.x, av1.y};
-        const double b[4] = {bv0.x, bv0.y, bv1.x, bv1.y};
-#pragma unroll
-        for (int i = 0; i < 4; i++)
-#pragma unroll
-            for (int j = 0; j < 4; j++) acc[i][j] += a[i] * b[j];
-    }
-#else
     const int il = lane_id() & 15, kl = lane_id() >> 4, w = wave_id();
     d4_t c[4];
 #pragma unroll
@@ -647,7 +607,6 @@ __device__ __forceinline__ void tile_panel(double (&acc)[4][4], const double* As
     }
 #pragma unroll
     for (int a = 0; a < 4; a++) { acc[a][0] = c[a][0]; acc[a][1] = c[a][1]; acc[a][2] = c[a][2]; acc[a][3] = c[a][3]; }
-#endif
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -721,7 +680,6 @@ __device__ __forceinline__ double wg_chol(double* F, int ld, int nblk, int nreal
     double* dl = lds.arena + 64 * TILE_LD;
     // the smallest pivot and the failure flag are kept in LDS (dl[8], dl[9]; thread 0 writes them), not in registers around the loops
     if (t == 0) { dl[8] = INFINITY; dl[9] = 0.0; }
-#if LCQP_SEQ_WAVE
     // Which wave runs the sequential stretches (the 16x16 sub-block chains below).  With wave 0 in every workgroup, the stretches of the
     // workgroups that share a CU queue up on ONE SIMD when the dispatcher has put every wave 0 there (k_factor: 0.40 ms with one workgroup
     // per two CUs, 1.30 ms with four per CU).  The waves say where they are (HW_REG_HW_ID: slot [3:0], SIMD [5:4]); the workgroup in slot k
@@ -731,7 +689,6 @@ __device__ __forceinline__ double wg_chol(double* F, int ld, int nblk, int nreal
         asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
         if (lane_id() == 0) dl[10 + wave_id()] = (double)(hw & 0x3fu);
     }
-#endif
     const int nn = 64 * nblk;
     if (tau > 0.0) {
         for (int i = t; i < nn; i += WG) d0[i] = F[(size_t)i * ld + i];
@@ -762,14 +719,10 @@ __device__ __forceinline__ double wg_chol(double* F, int ld, int nblk, int nreal
         const int nsub = (tau > 0.0) ? min(4, max(0, (nreal - o + 15) >> 4)) : 4;
         for (int jb = 0; jb < nsub; jb++) {
             const int c0 = 16 * jb;
-#if LCQP_SEQ_WAVE
             int sw = 0;
             { const int want = ((int)dl[10]) & 3;
               for (int w = 1; w < 4; w++) if (((((int)dl[10 + w]) >> 4) & 3) == want) sw = w;
               if (((((int)dl[10]) >> 4) & 3) == want) sw = 0; }
-#else
-            const int sw = 0;
-#endif
             if ((t >> 6) == sw) {
                 __builtin_amdgcn_s_setprio(3);   // the only sequential stretch: let it win issue slots from streaming waves
                 const int l = t & 63;
@@ -972,12 +925,8 @@ __device__ __forceinline__ void wg_tile_tn(double (&acc)[4][4], const double* __
 // operands, so every XCD gets a contiguous range of logical ids (bijective for any grid; cdna_hip_programming.md §5.5 T1).  A speed choice only.
 __device__ __forceinline__ int xcd_contiguous(int bid, int nwg)
 {
-#ifdef LCQP_NO_XCD_REMAP
-    (void)nwg; return bid;
-#else
     const int q = nwg >> 3, r = nwg & 7, x = bid & 7;
     return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (bid >> 3);
-#endif
 }
 
 // lower-triangular tile index -> (I, J), I >= J
