@@ -11,15 +11,16 @@
 //     and an active-set polish on [Q + delta I, Ea'; Ea, -delta2 I] in iterative-refinement form, refactorised only when the
 //     working set changes.  oracle/lcqp_oracle_sparse.c is the same algorithm in scalar C.
 // The KKT matrices are factorised as BAND matrices in a reverse Cuthill-McKee ordering computed once per pattern on the host
-// (all instances of a batch share it): LDL' with a sliding G x G window in registers (G <= 16) or LDS (half bandwidth w <= G - 1 <= 63), triangular
+// (lcqp_sparse_pattern.hpp; all instances of a batch share it): LDL' with a sliding G x G window in registers (G <= 16) or LDS (half bandwidth w <= G - 1 <= 63), triangular
 // solves that keep the G pending rows of an instance in its G lanes (axpy form both ways, no reductions in the chain; the finished
 // entry is broadcast inside the lane group by DPP).  A group of lanes behaves like a small workgroup of its own: every branch
 // condition is uniform inside a group, groups of one wavefront diverge through the execution mask, there are no workgroup barriers.
-// Patterns whose KKT band is wider (e.g. the arrow-shaped circle example) are refused here; the host layer runs them on the
-// dense kernels behind the same OSQP_SPARSE surface.
+// Patterns whose KKT band is wider take a bordered band (a few dense nodes behind the band, e.g. the arrow-shaped circle example) or the
+// general sparse LDL' (lcqp_sparse_general.hpp); what neither holds is refused here, and the host layer runs it on the dense kernels behind
+// the same OSQP_SPARSE surface.
 #include "lcqp_wg.hpp"
 #include "../../include/lcqp_hip.h"
-#include "lcqp_sparse_general.hpp"
+#include "lcqp_sparse_pattern.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -27,7 +28,6 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
-#include <queue>
 #include <string>
 #include <vector>
 
@@ -35,8 +35,6 @@ using namespace lcqp;
 
 namespace {
 
-constexpr int SP_WMAX = 63;
-constexpr int SP_KBMAX = 16;   // border nodes of the bordered band (rows / variables too dense for a band)
 constexpr int WGS = 64;      // one wavefront per workgroup; 64 / G instances in it
 constexpr int SCHED_WAVES_PER_SIMD = 2;   // register budget of k_sparse_sched at G <= 8: 512 / SCHED_WAVES_PER_SIMD per lane
 enum { NV_G, NV_GTIL, NV_GPHI, NV_XK, NV_PK, NV_XNEW, NV_GK, NV_QX, NV_CX, NV_QP, NV_CP, NV_TMP, NV_XQ, NV_XA, NV_XT, NV_R1,
@@ -706,7 +704,7 @@ __device__ __forceinline__ void sp_factor_reg(SpCtx<G>& c, GD KF, GD Kd, double 
 // written.  No pivoting: K is quasi-definite for delta, delta2 > 0, and every symmetric permutation of a quasi-definite matrix factorises.
 constexpr int GEN_JB = 8;
 constexpr int GEN_LDS_FRONT = 64;        // fronts up to this size are factorised inside LDS
-constexpr int GEN_MAX_FRONT = 576;       // panel of the largest front: 576 x 8 doubles beside nothing else in the 40 KB of a wavefront
+using lcqp_pattern::GEN_MAX_FRONT;       // the panel of the largest front (lcqp_sparse_pattern.hpp refuses larger ones)
 
 constexpr int GEN_META = 12;
 constexpr int GEN_BITS_OFF = GEN_MAX_FRONT * GEN_JB + 16;        // doubles: the working set as a bit set behind the panel and 1 / D of a block
@@ -2160,12 +2158,12 @@ extern "C" const char* lcqp_hip_sparse_last_error(void) { return g_sp_err.c_str(
 
 struct lcqp_hip_sparse {
     SpBatch db;
-    int device, nnzA;
+    int device;
     hipStream_t stream;
     hipEvent_t ev0, ev1, ev2;
     std::vector<void*> allocs;
     std::vector<int> csr2csc;      // value order: E (CSR) entry k comes from entry csr2csc[k] of the caller's CSC arrays
-    // two orderings of the band (lcqp_hip_sparse_create): [0] reverse Cuthill-McKee, [1] the same with every row behind its first variable
+    // the two orderings of the band (lcqp_sparse_pattern.hpp: Pattern::ord): device copies of their maps, the permutation for get_ordering
     struct Ord { std::vector<int> perm; int *iperm, *bandQ, *bandE, *bsrc, *bgate, *bdiag, *pnode, *Upos; bool rowsFollow; } ord[2];
     bool hasB;
     int useB;                      // ordering of the last sp_choose_ordering
@@ -2203,224 +2201,24 @@ static T* sp_alloc(lcqp_hip_sparse* h, size_t count, const T* init = nullptr)
     return (T*)p;
 }
 
-// reverse Cuthill-McKee ordering of the KKT graph: nodes 0..n-1 variables, n..n+m-1 rows
-static void rcm_order(int N, const std::vector<std::vector<int>>& adj, std::vector<int>& perm)
-{
-    std::vector<int> deg(N), order; std::vector<char> seen(N, 0);
-    for (int i = 0; i < N; i++) deg[i] = (int)adj[i].size();
-    order.reserve(N);
-    auto bfs = [&](int start, std::vector<int>& out, std::vector<char>& mark) {
-        std::queue<int> q; q.push(start); mark[start] = 1;
-        while (!q.empty()) {
-            const int v = q.front(); q.pop(); out.push_back(v);
-            std::vector<int> nb;
-            for (int u : adj[v]) if (!mark[u]) { mark[u] = 1; nb.push_back(u); }
-            std::sort(nb.begin(), nb.end(), [&](int a, int b) { return deg[a] != deg[b] ? deg[a] < deg[b] : a < b; });
-            for (int u : nb) q.push(u);
-        }
-    };
-    for (int s0 = 0; s0 < N; s0++) {
-        if (seen[s0]) continue;
-        // pseudo-peripheral start: the last node of a BFS from the minimum-degree node of the component, twice
-        int start = s0;
-        for (int pass = 0; pass < 2; pass++) {
-            std::vector<int> tmp; std::vector<char> mk(seen.begin(), seen.end());
-            bfs(start, tmp, mk);
-            if (pass == 0) { int best = tmp[0]; for (int v : tmp) if (deg[v] < deg[best]) best = v; start = best; }
-            else start = tmp.back();
-        }
-        bfs(start, order, seen);
-    }
-    perm.assign(order.rbegin(), order.rend());
-}
-
+// the pattern analysis (lcqp_sparse_pattern.hpp), then the device copies of its arrays and the storage of the batch
 extern "C" lcqp_hip_sparse_t* lcqp_hip_sparse_create(int batch, int nV, int nC, int nComp, const int* Qp, const int* Qi, const int* Ap, const int* Ai, int device)
 try {
     if (batch <= 0 || nV <= 0 || nC < 0 || nComp <= 0 || !Qp || !Qi || !Ap || !Ai) { g_sp_err = "invalid arguments"; return nullptr; }
-    const int n = nV, m = nC + 2 * nComp, N = n + m;
-    // the pattern is taken at its word below, so it is checked first: column pointers start at 0 and never decrease; row indices inside a
-    // column strictly increase (sorted, no duplicates: a duplicate would share one band slot and lose a value); Q structurally symmetric
-    // (both triangles given, as the reference hands Q to OSQP's P -- only entries with a mirror image reach the band)
-    for (int pass = 0; pass < 2; pass++) {
-        const int* P = pass ? Ap : Qp; const int* I = pass ? Ai : Qi; const int rows = pass ? m : n;
-        if (P[0] != 0) { g_sp_err = "column pointers must start at 0"; return nullptr; }
-        for (int c = 0; c < n; c++) {
-            if (P[c + 1] < P[c]) { g_sp_err = "column pointers must not decrease"; return nullptr; }
-            for (int k = P[c]; k < P[c + 1]; k++) {
-                if (I[k] < 0 || I[k] >= rows) { g_sp_err = pass ? "row index out of bounds" : "Q index out of bounds"; return nullptr; }
-                if (k > P[c] && I[k] <= I[k - 1]) { g_sp_err = "row indices of a column must be sorted and free of duplicates"; return nullptr; }
-            }
-        }
-    }
-    for (int c = 0; c < n; c++)
-        for (int k = Qp[c]; k < Qp[c + 1]; k++) {
-            const int r = Qi[k];
-            if (r == c) continue;
-            if (!std::binary_search(Qi + Qp[r], Qi + Qp[r + 1], c)) { g_sp_err = "Q must be structurally symmetric (both triangles given)"; return nullptr; }
-        }
-    const int nnzQ = Qp[n], nnzA = Ap[n];
-    // CSC of the stacked matrix -> CSR (pattern and the value permutation)
-    std::vector<int> Ep(m + 1, 0), Ei(nnzA), csr2csc(nnzA), ETp(Ap, Ap + n + 1), ETi(Ai, Ai + nnzA), ETmap(nnzA);
-    for (int k = 0; k < nnzA; k++) { if (Ai[k] < 0 || Ai[k] >= m) { g_sp_err = "row index out of bounds"; return nullptr; } Ep[Ai[k] + 1]++; }
-    for (int r = 0; r < m; r++) Ep[r + 1] += Ep[r];
-    { std::vector<int> cur(Ep.begin(), Ep.end() - 1);
-      for (int c = 0; c < n; c++) for (int k = Ap[c]; k < Ap[c + 1]; k++) { const int d = cur[Ai[k]]++; Ei[d] = c; csr2csc[d] = k; ETmap[k] = d; } }
-    // KKT graph and ordering
-    std::vector<std::vector<int>> adj(N);
-    for (int i = 0; i < n; i++) for (int k = Qp[i]; k < Qp[i + 1]; k++) { const int j = Qi[k]; if (j < 0 || j >= n) { g_sp_err = "Q index out of bounds"; return nullptr; } if (j != i) adj[i].push_back(j); }
-    for (int r = 0; r < m; r++) for (int k = Ep[r]; k < Ep[r + 1]; k++) { adj[n + r].push_back(Ei[k]); adj[Ei[k]].push_back(n + r); }
-    for (auto& a : adj) { std::sort(a.begin(), a.end()); a.erase(std::unique(a.begin(), a.end()), a.end()); }
-    // Ordering: reverse Cuthill-McKee; while the half bandwidth exceeds what a lane group covers, the node of highest degree moves to the
-    // border (at most SP_KBMAX nodes), the positions behind the band.  Arrow-shaped KKT matrices (a coupling row, a shared variable:
-    // examples/OptimizeOnCircle.cpp:44) become a narrow band plus a few border nodes.
-    std::vector<int> permA, border;
-    bool general = false;
-    if (const char* e = std::getenv("LCQP_SPARSE_GENERAL")) general = std::atoi(e) == 1;      // test hook: the general LDL' on a pattern the band engine would take
-    lcqp_general::Symbolic sym;
-    std::vector<char> isBorder(N, 0);
-    std::vector<std::vector<int>> sub(N);
-    auto bandwidth = [&](const std::vector<int>& pm) {
-        std::vector<int> ip(N);
-        for (int p = 0; p < N; p++) ip[pm[p]] = p;
-        int wv = 0;
-        for (int v = 0; v < N; v++) if (!isBorder[v]) for (int u : sub[v]) wv = std::max(wv, std::abs(ip[v] - ip[u]));
-        return wv;
-    };
-    int wA = 0;
-    for (; !general;) {
-        for (int v = 0; v < N; v++) { sub[v].clear(); if (!isBorder[v]) for (int u : adj[v]) if (!isBorder[u]) sub[v].push_back(u); }
-        std::vector<int> full;
-        rcm_order(N, sub, full);
-        permA.clear();
-        for (int v : full) if (!isBorder[v]) permA.push_back(v);
-        for (int v : border) permA.push_back(v);
-        wA = bandwidth(permA);
-        if (wA <= SP_WMAX) break;
-        if ((int)border.size() >= SP_KBMAX) {
-            // neither a banded nor a bordered problem: the general sparse LDL' (round 6; until then such a pattern was refused here and ran densified)
-            general = true;
-            break;
-        }
-        int best = -1; size_t deg = 0;
-        for (int v = 0; v < N; v++) if (!isBorder[v] && sub[v].size() > deg) { deg = sub[v].size(); best = v; }
-        if (best < 0) { g_sp_err = "ordering failed"; return nullptr; }
-        isBorder[best] = 1; border.push_back(best);
-    }
-    if (general) {
-        sym = lcqp_general::analyze(n, m, adj, Qp, Qi, Ep.data(), Ei.data(), 32);
-        if (sym.maxFront > GEN_MAX_FRONT || sym.Lsize >= (1LL << 28) || sym.stackSize >= (1LL << 28)) {
-            g_sp_err = "general sparse LDL' of this pattern: largest front " + std::to_string(sym.maxFront) + " (limit " + std::to_string(GEN_MAX_FRONT) + "), " +
-                       std::to_string((long long)sym.Lsize) + " factor entries: too dense for the sparse engine (use the dense kernels)";
-            return nullptr;
-        }
-        border.clear(); std::fill(isBorder.begin(), isBorder.end(), 0);
-        permA = sym.perm; wA = 0;
-        for (int v = 0; v < N; v++) sub[v] = adj[v];
-    }
-    const int kb = (int)border.size(), Nband = N - kb;
-    // A second ordering of the same band nodes for batches whose Hessians are safely definite (chosen at run time, sp_choose_ordering): a
-    // constraint row eliminated before every variable it touches gets the bare dual regularisation as its pivot (the LDL' is not pivoted),
-    // which rules out the light regularisation of the polish (sp_polish).  Here such rows move to just behind their first variable, so that
-    // every row pivot is -(delta2 + e D^-1 e').  With a Hessian that is nearly flat in that variable the same move is harmful (two active
-    // rows that hinge on it cancel), hence the choice by the data.
-    // Reverse Cuthill-McKee happens to put most multiplier nodes in front of their variables, and a band is as wide backwards: the second
-    // ordering is the first one reversed, and what rows are still in front of all their variables move behind the first of them.
-    std::vector<int> permB(permA);
-    std::reverse(permB.begin(), permB.begin() + Nband);
-    {
-        std::vector<int> pos(N, -1), base(permB);
-        for (int p = 0; p < Nband; p++) pos[base[p]] = p;
-        std::vector<std::pair<double, int>> key(Nband);
-        for (int p = 0; p < Nband; p++) {
-            const int v = base[p];
-            double k = p;
-            if (v >= n) {
-                int first = 1 << 30;
-                for (int u : sub[v]) if (u < n && pos[u] >= 0) first = std::min(first, pos[u]);
-                if (first != (1 << 30) && first > p) k = first + 0.5;
-            }
-            key[p] = {k, v};
-        }
-        std::stable_sort(key.begin(), key.end(), [](const std::pair<double, int>& a, const std::pair<double, int>& b) { return a.first < b.first; });
-        for (int p = 0; p < Nband; p++) permB[p] = key[p].second;
-    }
-    const int wB = bandwidth(permB);
-    auto lanes_for = [](int wv) { return wv < 8 ? 8 : (wv < 16 ? 16 : (wv < 32 ? 32 : 64)); };
-    const bool hasB = !general && wB <= SP_WMAX && lanes_for(wB) == lanes_for(wA);      // not at the price of a wider lane group
-    int w = hasB ? std::max(wA, wB) : wA;
-    if (w < 1) w = 1;
-    // lanes per instance: the smallest of 8, 16, 32, 64 above the half bandwidth (LCQP_SPARSE_LANES raises it: test hook); the general LDL' takes a wavefront
-    int G = general ? 64 : lanes_for(w);
-    if (const char* e = std::getenv("LCQP_SPARSE_LANES")) { const int v = std::atoi(e); if ((v == 16 || v == 32 || v == 64) && v > G) G = v; }
-    const int ld = G, wS = G - 1;          // band rows are stored G wide: entry k of row i is K[i][i - (G-1) + k] (zero outside the true band)
-    // what depends on the ordering: inverse permutation, band slot of every entry of Q and E (-1: not in the band -- an upper-triangle entry
-    // of Q, or an entry of the border), where every off-diagonal band entry comes from (assembly inside the factorisation: -1 nothing,
-    // k < nnzQ the entry k of Q, nnzQ + k the entry k of E in CSR order), the node behind a band position, the band positions of U
-    struct OrdMaps { std::vector<int> perm, iperm, bandQ, bandE, bsrc, bgate, bdiag, Upos; };
-    std::vector<int> qdiag(n, -1), Erow(nnzA);
-    for (int i = 0; i < n; i++) for (int k = Qp[i]; k < Qp[i + 1]; k++) if (Qi[k] == i) qdiag[i] = k;
-    for (int r = 0; r < m; r++) for (int k = Ep[r]; k < Ep[r + 1]; k++) Erow[k] = r;
-    // the border: per border node its entries with band nodes (U) and with border nodes of lower index (C); the enumeration order does not
-    // depend on the ordering of the band
-    std::vector<int> Uptr(kb + 1, 0), Uother, Usrc, Ugate, Cptr(kb + 1, 0), Cb2, Csrc, Cgate, bidx(N, -1);
-    for (int b = 0; b < kb; b++) bidx[border[b]] = b;
-    for (int b = 0; b < kb; b++) {
-        const int v = border[b];
-        auto put = [&](int other, int src, int gate) {
-            if (bidx[other] < 0) { Uother.push_back(other); Usrc.push_back(src); Ugate.push_back(gate); }
-            else if (bidx[other] < b) { Cb2.push_back(bidx[other]); Csrc.push_back(src); Cgate.push_back(gate); }
-        };
-        if (v < n) {
-            for (int k = Qp[v]; k < Qp[v + 1]; k++) if (Qi[k] != v) put(Qi[k], k, -1);                       // Q is symmetric: row v = column v
-            for (int kc = ETp[v]; kc < ETp[v + 1]; kc++) put(n + ETi[kc], nnzQ + ETmap[kc], ETi[kc]);       // column v of E
-        } else {
-            const int r = v - n;
-            for (int k = Ep[r]; k < Ep[r + 1]; k++) put(Ei[k], nnzQ + k, r);
-        }
-        Uptr[b + 1] = (int)Uother.size(); Cptr[b + 1] = (int)Cb2.size();
-    }
-    const int nU = (int)Uother.size(), nCb = (int)Cb2.size();
-    auto build_maps = [&](const std::vector<int>& pm) {
-        OrdMaps M;
-        M.perm = pm; M.iperm.assign(N, 0);
-        for (int p = 0; p < N; p++) M.iperm[pm[p]] = p;
-        if (general) {      // no band: the maps of the band engines stay empty (sp_assemble / sp_factor_reg are never entered)
-            M.bandQ.assign(nnzQ, -1); M.bandE.assign(nnzA, -1); M.bsrc.assign(1, -1); M.bgate.assign(1, -1); M.bdiag.assign(N, -1); M.Upos.assign(1, 0);
-            return M;
-        }
-        M.bandQ.assign(nnzQ, -1); M.bandE.assign(nnzA, -1); M.bsrc.assign((size_t)N * ld, -1);
-        for (int i = 0; i < n; i++) for (int k = Qp[i]; k < Qp[i + 1]; k++) { const int pi = M.iperm[i], pj = M.iperm[Qi[k]]; if (pj <= pi && pi < Nband) M.bandQ[k] = pi * ld + wS - (pi - pj); }
-        for (int r = 0; r < m; r++) for (int k = Ep[r]; k < Ep[r + 1]; k++) { const int pr = M.iperm[n + r], pc = M.iperm[Ei[k]]; const int hi = std::max(pr, pc), lo = std::min(pr, pc); if (hi < Nband) M.bandE[k] = hi * ld + wS - (hi - lo); }
-        for (int i = 0; i < n; i++) for (int k = Qp[i]; k < Qp[i + 1]; k++) if (Qi[k] != i && M.bandQ[k] >= 0) M.bsrc[M.bandQ[k]] = k;
-        for (int r = 0; r < m; r++) for (int k = Ep[r]; k < Ep[r + 1]; k++) if (M.bandE[k] >= 0) M.bsrc[M.bandE[k]] = nnzQ + k;
-        // the same information one level of indirection shorter (sp_factor_reg: load_row): the gating row of every band entry, the diagonal of every position
-        M.bgate.assign((size_t)N * ld, -1);
-        for (int r = 0; r < m; r++) for (int k = Ep[r]; k < Ep[r + 1]; k++) if (M.bandE[k] >= 0) M.bgate[M.bandE[k]] = r;
-        if (G <= 16) {
-            // sp_factor_reg keeps a row in UPPER form relative to its diagonal: entry k of row r is K[r + k][r] = the lower-form entry
-            // (r + k, ld - 1 - k); the diagonal slot (k = 0) is described by bdiag
-            std::vector<int> su((size_t)N * ld, -1), gu((size_t)N * ld, -1);
-            for (int r = 0; r < N; r++)
-                for (int k = 1; k < ld && r + k < N; k++) { su[(size_t)r * ld + k] = M.bsrc[(size_t)(r + k) * ld + (ld - 1 - k)]; gu[(size_t)r * ld + k] = M.bgate[(size_t)(r + k) * ld + (ld - 1 - k)]; }
-            M.bsrc.swap(su); M.bgate.swap(gu);
-        }
-        M.bdiag.assign(N, -1);
-        for (int p_ = 0; p_ < N; p_++) {
-            const int node = pm[p_];
-            if (p_ >= Nband) M.bdiag[p_] = INT_MIN;
-            else if (node < n) M.bdiag[p_] = qdiag[node];
-            else M.bdiag[p_] = -2 - (node - n);
-        }
-        M.Upos.resize(nU);
-        for (int e = 0; e < nU; e++) M.Upos[e] = M.iperm[Uother[e]];
-        return M;
-    };
-    OrdMaps mapsA = build_maps(permA), mapsB = hasB ? build_maps(permB) : OrdMaps();
+    lcqp_pattern::Hooks hooks;
+    if (const char* e = std::getenv("LCQP_SPARSE_GENERAL")) hooks.general = std::atoi(e) == 1;      // test hook: the general LDL' on a pattern the band engine would take
+    if (const char* e = std::getenv("LCQP_SPARSE_LANES")) hooks.lanes = std::atoi(e);               // test hook: a wider lane group than the band needs
+    lcqp_pattern::Pattern P;
+    if (!lcqp_pattern::analyse_pattern(nV, nC, nComp, Qp, Qi, Ap, Ai, hooks, P, g_sp_err)) return nullptr;
+    const int n = P.n, m = P.m, N = P.N, nnzQ = P.nnzQ, nnzA = P.nnzE, w = P.w, G = P.G, ld = G, kb = P.kb;
+    const int nU = (int)P.Usrc.size(), nCb = (int)P.Csrc.size();
+    const bool general = P.general;
+    const lcqp_general::Symbolic& sym = P.sym;
     if (hipSetDevice(device) != hipSuccess) { g_sp_err = "hipSetDevice failed"; return nullptr; }
     lcqp_hip_sparse* h = new (std::nothrow) lcqp_hip_sparse();
     if (!h) return nullptr;
     struct Guard { lcqp_hip_sparse* h; ~Guard() { if (h) lcqp_hip_sparse_destroy(h); } } guard{h};      // an exception below must not leak the handle
-    h->device = device; h->nnzA = nnzA; h->loaded = false; h->ran = false; h->csr2csc = csr2csc; h->hasB = hasB; h->useB = 0; h->qdiagHost = qdiag; h->diagRatio.assign(batch, 1.0);
+    h->device = device; h->loaded = false; h->ran = false; h->csr2csc = P.csr2csc; h->hasB = P.hasB; h->useB = 0; h->qdiagHost = P.qdiag; h->diagRatio.assign(batch, 1.0);
     h->stream = nullptr; h->ev0 = h->ev1 = h->ev2 = nullptr;
     SpBatch& d = h->db;
     memset(&d, 0, sizeof(d));
@@ -2452,48 +2250,32 @@ try {
     bool ok = hipStreamCreate(&h->stream) == hipSuccess && hipEventCreate(&h->ev0) == hipSuccess && hipEventCreate(&h->ev1) == hipSuccess &&
               hipEventCreate(&h->ev2) == hipSuccess;
     const size_t B = batch;
-    ok = ok && (d.Qp = sp_alloc<int>(h, n + 1, Qp)) && (d.Qi = sp_alloc<int>(h, nnzQ, Qi)) && (d.Ep = sp_alloc<int>(h, m + 1, Ep.data())) &&
-         (d.Ei = sp_alloc<int>(h, nnzA, Ei.data())) && (d.ETp = sp_alloc<int>(h, n + 1, ETp.data())) && (d.ETi = sp_alloc<int>(h, nnzA, ETi.data())) &&
-         (d.ETmap = sp_alloc<int>(h, nnzA, ETmap.data())) &&
-         (d.qdiag = sp_alloc<int>(h, n, qdiag.data())) && (d.Erow = sp_alloc<int>(h, nnzA, Erow.data()));
-    for (int k = 0; k < (hasB ? 2 : 1); k++) {
-        OrdMaps& M = k ? mapsB : mapsA;
+    ok = ok && (d.Qp = sp_alloc<int>(h, n + 1, Qp)) && (d.Qi = sp_alloc<int>(h, nnzQ, Qi)) && (d.Ep = sp_alloc<int>(h, m + 1, P.Ep.data())) &&
+         (d.Ei = sp_alloc<int>(h, nnzA, P.Ei.data())) && (d.ETp = sp_alloc<int>(h, n + 1, P.ETp.data())) && (d.ETi = sp_alloc<int>(h, nnzA, P.ETi.data())) &&
+         (d.ETmap = sp_alloc<int>(h, nnzA, P.ETmap.data())) &&
+         (d.qdiag = sp_alloc<int>(h, n, P.qdiag.data())) && (d.Erow = sp_alloc<int>(h, nnzA, P.Erow.data()));
+    for (int k = 0; k < (P.hasB ? 2 : 1); k++) {
+        const lcqp_pattern::Ordering& M = P.ord[k];
         lcqp_hip_sparse::Ord& o = h->ord[k];
-        // the light regularisation needs every row of the band behind one of its variables (sp_polish)
-        o.rowsFollow = true;
-        for (int r = 0; r < m; r++) {
-            if (M.iperm[n + r] >= Nband) continue;
-            bool follows = false;
-            for (int e = Ep[r]; e < Ep[r + 1]; e++) follows = follows || M.iperm[Ei[e]] < M.iperm[n + r];
-            o.rowsFollow = o.rowsFollow && follows;
-        }
         ok = ok && (o.iperm = sp_alloc<int>(h, N, M.iperm.data())) && (o.bandQ = sp_alloc<int>(h, nnzQ, M.bandQ.data())) &&
              (o.bandE = sp_alloc<int>(h, nnzA, M.bandE.data())) && (o.bsrc = sp_alloc<int>(h, M.bsrc.size(), M.bsrc.data())) &&
              (o.bgate = sp_alloc<int>(h, M.bgate.size(), M.bgate.data())) && (o.bdiag = sp_alloc<int>(h, M.bdiag.size(), M.bdiag.data())) &&
              (o.pnode = sp_alloc<int>(h, N, M.perm.data())) && (o.Upos = sp_alloc<int>(h, nU, M.Upos.data()));
-        o.perm = std::move(M.perm);
+        o.perm = M.perm; o.rowsFollow = M.rowsFollow;
     }
     if (ok) sp_choose_ordering(h);
     if (kb > 0)
-        ok = ok && (d.bnode = sp_alloc<int>(h, kb, border.data())) && (d.Uptr = sp_alloc<int>(h, kb + 1, Uptr.data())) &&
-             (d.Usrc = sp_alloc<int>(h, nU, Usrc.data())) && (d.Ugate = sp_alloc<int>(h, nU, Ugate.data())) && (d.Cptr = sp_alloc<int>(h, kb + 1, Cptr.data())) &&
-             (d.Cb2 = sp_alloc<int>(h, nCb, Cb2.data())) && (d.Csrc = sp_alloc<int>(h, nCb, Csrc.data())) && (d.Cgate = sp_alloc<int>(h, nCb, Cgate.data())) &&
+        ok = ok && (d.bnode = sp_alloc<int>(h, kb, P.border.data())) && (d.Uptr = sp_alloc<int>(h, kb + 1, P.Uptr.data())) &&
+             (d.Usrc = sp_alloc<int>(h, nU, P.Usrc.data())) && (d.Ugate = sp_alloc<int>(h, nU, P.Ugate.data())) && (d.Cptr = sp_alloc<int>(h, kb + 1, P.Cptr.data())) &&
+             (d.Cb2 = sp_alloc<int>(h, nCb, P.Cb2.data())) && (d.Csrc = sp_alloc<int>(h, nCb, P.Csrc.data())) && (d.Cgate = sp_alloc<int>(h, nCb, P.Cgate.data())) &&
              (d.bW = sp_alloc<double>(h, (size_t)batch * 2 * kb * d.Np)) && (d.bUv = sp_alloc<double>(h, (size_t)batch * 2 * nU)) &&
              (d.bS = sp_alloc<double>(h, (size_t)batch * 2 * kb * kb));
     // ELL slabs of the three gathers (g_ell): rows of Q, rows of E, columns of E
-    auto make_ell = [&](EllMat& e, int rows, const std::vector<int>& ptr, const std::vector<int>& idx, const int* map, const int* dptr, const int* didx, const int* dmap) {
-        int mx = 0;
-        for (int i = 0; i < rows; i++) mx = std::max(mx, ptr[i + 1] - ptr[i]);
-        const int W = mx <= 4 ? 4 : 8;
-        std::vector<int> ei((size_t)W * rows, 0), ep((size_t)W * rows, -1);
-        for (int i = 0; i < rows; i++)
-            for (int q = 0; q < W && ptr[i] + q < ptr[i + 1]; q++) { const int k = ptr[i] + q; ei[(size_t)q * rows + i] = idx[k]; ep[(size_t)q * rows + i] = map ? map[k] : k; }
-        e.rows = rows; e.W = W; e.tails = mx > W ? 1 : 0; e.ptr = dptr; e.cidx = didx; e.cmap = dmap;
-        e.epos = nullptr;      // without a map the position of entry q of row i is ptr[i] + q (g_ell): no position slab
-        return (e.eidx = sp_alloc<int>(h, ei.size(), ei.data())) && (!map || (e.epos = sp_alloc<int>(h, ep.size(), ep.data())));
+    auto ell = [&](EllMat& e, const lcqp_pattern::Ell& s, int rows, const int* dptr, const int* didx, const int* dmap) {
+        e.rows = rows; e.W = s.W; e.tails = s.tails; e.ptr = dptr; e.cidx = didx; e.cmap = dmap; e.epos = nullptr;
+        return (e.eidx = sp_alloc<int>(h, s.eidx.size(), s.eidx.data())) && (s.epos.empty() || (e.epos = sp_alloc<int>(h, s.epos.size(), s.epos.data())));
     };
-    ok = ok && make_ell(d.ellQ, n, std::vector<int>(Qp, Qp + n + 1), std::vector<int>(Qi, Qi + nnzQ), nullptr, d.Qp, d.Qi, nullptr) &&
-         make_ell(d.ellE, m, Ep, Ei, nullptr, d.Ep, d.Ei, nullptr) && make_ell(d.ellT, n, ETp, ETi, ETmap.data(), d.ETp, d.ETi, d.ETmap);
+    ok = ok && ell(d.ellQ, P.ellQ, n, d.Qp, d.Qi, nullptr) && ell(d.ellE, P.ellE, m, d.Ep, d.Ei, nullptr) && ell(d.ellT, P.ellT, n, d.ETp, d.ETi, d.ETmap);
     ok = ok && (d.Qx = sp_alloc<double>(h, B * nnzQ)) && (d.Ex = sp_alloc<double>(h, B * nnzA)) &&
          (d.Kb = sp_alloc<double>(h, (G > 16 && !general) ? B * N * ld : 0)) &&      // the band array is only written by the LDS-window factorisation
          (d.KaF = sp_alloc<double>(h, B * d.kfStride)) && (d.KaD = sp_alloc<double>(h, B * Np)) &&

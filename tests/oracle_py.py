@@ -389,7 +389,7 @@ def kkt_ordering(nV, Qp, Qi, Ep, Ei, wmax=63, kbmax=16, rows_follow=False):
     """Ordering of the KKT graph [Q E'; E .] with scipy (independent of the product's own analysis): reverse Cuthill-McKee; while the
     half bandwidth exceeds wmax, the node of highest degree moves to the border (the last positions).  rows_follow: the band is taken backwards and every row that
     would still be eliminated before all of its variables moves to just behind the first of them (the ordering the product uses for batches
-    of safely definite Hessians, lcqp_hip_sparse_create); if that widens the band beyond wmax the plain ordering is kept.
+    of safely definite Hessians, lcqpow_amd/csrc/lcqp_sparse_pattern.hpp); if that widens the band beyond wmax the plain ordering is kept.
     Returns (perm, w, kb): perm[position] = node (node < nV: variable, else row node - nV), w = half bandwidth of the first N - kb positions."""
     import scipy.sparse as sp
     from scipy.sparse.csgraph import reverse_cuthill_mckee
