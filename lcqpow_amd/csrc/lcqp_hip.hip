@@ -1,6 +1,7 @@
 // lcqp_hip.hip -- kernels and C-ABI of liblcqpow_hip.so (gfx950 only; see include/lcqp_hip.h).
 #include "lcqp_dev.hpp"
 #include "lcqp_launch.hpp"
+#include "lcqp_host_rt.hpp"
 #include "../../include/lcqp_synth.h"
 
 #include <algorithm>
@@ -8,11 +9,12 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <new>
+#include <memory>
 #include <string>
 #include <vector>
 
 using namespace lcqp;
+using namespace lcqp_rt;
 
 
 // =================================================================================================
@@ -62,22 +64,7 @@ extern "C" int lcqp_hip_request_hw_queues(int n)
     return setenv("GPU_MAX_HW_QUEUES", buf, /*overwrite=*/0) == 0 ? 0 : LCQP_HIP_ERROR;
 }
 
-static thread_local std::string g_err;
-static int set_err(const char* what, hipError_t e)
-{
-    g_err = std::string(what) + ": " + hipGetErrorString(e);
-    return LCQP_HIP_ERROR;
-}
-#define HIPCHK(call)                                               \
-    do {                                                           \
-        hipError_t e_ = (call);                                    \
-        if (e_ != hipSuccess) return set_err(#call, e_);           \
-    } while (0)
-#define HIPCHKN(call)                                              \
-    do {                                                           \
-        hipError_t e_ = (call);                                    \
-        if (e_ != hipSuccess) { set_err(#call, e_); return nullptr; } \
-    } while (0)
+static thread_local std::string g_err;      // the dense, QP, util and CSC entry points (lcqp_host_rt.hpp: HIPCHK(g_err, ...))
 
 extern "C" const char* lcqp_hip_last_error(void) { return g_err.c_str(); }
 extern "C" int lcqp_hip_device_count(void)
@@ -111,24 +98,31 @@ extern "C" void lcqp_hip_options_default(lcqp_options_t* o)
     o->admmFirst = 0; o->admmHot = 0; o->maxTrials = 16; o->maxRounds = 40;      // maxTrials: 12 until round 3 -- cold starts of the synthetic workload need up to 14 trials, and a polish that runs out of trials costs an ADMM round (the factor L_K, ten iterations, a second cold polish): those instances were the tail of the launch
 }
 
+// a pinned staging slot of loadLCQP and the event of the copies that last read it
+struct StageSlot {
+    void* buf = nullptr;
+    Event done{hipEventDisableTiming};
+    ~StageSlot() { if (buf) (void)hipHostFree(buf); }
+};
+
+// The members are released in reverse order after the destructor's synchronisation: device memory, staging slots, events, streams.
 struct lcqp_hip_batch {
     DevBatch db;
     int device;
-    hipStream_t stream;
-    hipEvent_t ev0, ev1, ev2;
-    // the setup has two independent branches (C = L'R + R'L and its compression; L1 -> Et -> M): the short one runs beside the long one
-    hipStream_t side;
-    hipEvent_t evFork, evJoin;
-    int numCU;
-    bool overlapped;      // lcqp_hip_batch_set_overlapped
+    // the setup has two independent branches (C = L'R + R'L and its compression; L1 -> Et -> M): the short one runs on `side`
+    Stream stream, side;
+    Event ev0, ev1, ev2;                  // run: setup from ev0 to ev1, homotopy from ev1 to ev2
+    Event evFork{hipEventDisableTiming}, evJoin{hipEventDisableTiming};
     // two pinned staging slots for loadLCQP: instance k is packed into slot k&1 while slot (k-1)&1 is in flight
-    void* stage[2];
-    hipEvent_t stageDone[2];
-    size_t stageBytes;
-    std::vector<void*> allocs;
-    bool setupDone, ran, anyLoaded;
+    StageSlot stage[2];
+    size_t stageBytes = 0;
+    DevMem mem{stream};
+    int numCU = 256;
+    bool overlapped = false;      // lcqp_hip_batch_set_overlapped
+    bool ran = false, anyLoaded = false;
     int nch;
-    size_t bytesTotal;
+    explicit lcqp_hip_batch(int dev) : db(), device(dev) {}
+    ~lcqp_hip_batch() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
 };
 
 // -DLCQP_ONLY_NCH=k (experiment builds, tools/gpu_ab.py): link only the kernels of one padded size
@@ -185,41 +179,17 @@ static void dispatch_db(lcqp_hip_batch* h, int kid, int grid, const int* list = 
     lcqp_dispatch(h->nch, kid, grid, on ? on : h->stream, a);
 }
 
-template <class T>
-static int dev_alloc(lcqp_hip_batch* h, T** p, size_t count, bool zero)
-{
-    void* q = nullptr;
-    size_t bytes = (count ? count : 1) * sizeof(T);
-    HIPCHK(hipMalloc(&q, bytes));
-    h->allocs.push_back(q);
-    h->bytesTotal += bytes;
-    if (zero) HIPCHK(hipMemsetAsync(q, 0, bytes, h->stream));
-    *p = (T*)q;
-    return 0;
-}
-
 extern "C" lcqp_hip_batch_t* lcqp_hip_batch_create(int batch, int nV, int nC, int nComp, int withBox, int device)
 try {
     if (batch <= 0 || nV <= 0 || nC < 0 || nComp < 0) { g_err = "invalid dimensions"; return nullptr; }
     if (nV > 4096) { g_err = "nV > 4096 is not supported by the dense kernels of this build (padded sizes 128 ... 4096; the sparse engine takes larger banded / bordered problems)"; return nullptr; }
-    HIPCHKN(hipSetDevice(device));
-    lcqp_hip_batch* h = new (std::nothrow) lcqp_hip_batch();
-    if (!h) { g_err = "out of host memory"; return nullptr; }
-    h->device = device; h->setupDone = false; h->ran = false; h->anyLoaded = false; h->bytesTotal = 0;
-    h->stage[0] = h->stage[1] = nullptr; h->stageBytes = 0;
-    h->stream = nullptr; h->ev0 = h->ev1 = h->ev2 = nullptr; h->side = nullptr; h->evFork = h->evJoin = nullptr;
-    h->numCU = 256; h->overlapped = false;
+    if (hipError_t e = hipSetDevice(device)) { hip_fail(g_err, "hipSetDevice(device)", e); return nullptr; }
+    std::unique_ptr<lcqp_hip_batch> h(new lcqp_hip_batch(device));
+    for (hipError_t e : {h->stream.status, h->side.status, h->ev0.status, h->ev1.status, h->ev2.status, h->evFork.status, h->evJoin.status,
+                         h->stage[0].done.status, h->stage[1].done.status})
+        if (e != hipSuccess) { hip_fail(g_err, "stream/event creation", e); return nullptr; }
     { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) h->numCU = cu; }
     DevBatch& d = h->db;
-    memset(&d, 0, sizeof(d));
-    hipError_t e0 = hipStreamCreate(&h->stream);
-    if (e0 == hipSuccess) e0 = hipEventCreate(&h->ev0);
-    if (e0 == hipSuccess) e0 = hipEventCreate(&h->ev1);
-    if (e0 == hipSuccess) e0 = hipEventCreate(&h->ev2);
-    if (e0 == hipSuccess) e0 = hipStreamCreate(&h->side);
-    if (e0 == hipSuccess) e0 = hipEventCreateWithFlags(&h->evFork, hipEventDisableTiming);
-    if (e0 == hipSuccess) e0 = hipEventCreateWithFlags(&h->evJoin, hipEventDisableTiming);
-    if (e0 != hipSuccess) { set_err("stream/event creation", e0); lcqp_hip_batch_destroy(h); return nullptr; }
     d.B = batch; d.n = nV; d.nC = nC; d.nComp = nComp; d.mA = nC + 2 * nComp;
     h->nch = padded_nch(nV);      // 512 < nV <= 1024 runs the np = 1024 instantiation; 1024 < nV <= 2048: np = 2048 (96 KiB of LDS, one workgroup per CU, one row in flight per wave)
     d.np = 128 * h->nch;
@@ -233,108 +203,44 @@ try {
     d.capS = ((capNa + 63) / 64) * 64;
     if (d.capS < 64) d.capS = 64;
     d.nd = nV + d.mA;
-    lcqp_hip_options_default(&d.opt);
-    const size_t B = batch, np = d.np, mE = d.mEcap;
-    int rc = 0;
-    rc |= dev_alloc(h, &d.Q, B * np * np, true);
-    rc |= dev_alloc(h, &d.C, B * np * np, true);
-    rc |= dev_alloc(h, &d.E, B * mE * np, true);
-    rc |= dev_alloc(h, &d.Et, B * mE * np, true);
-    rc |= dev_alloc(h, &d.F1, B * np * np, true);
-    rc |= dev_alloc(h, &d.FK, B * np * np, true);
-    rc |= dev_alloc(h, &d.S, B * (size_t)d.capS * d.capS, true);
     d.mMld = ((d.mEcap + 63) / 64) * 64;
-    rc |= dev_alloc(h, &d.MM, B * (size_t)d.mMld * d.mMld, true);
-    rc |= dev_alloc(h, &d.crow, B * (size_t)d.capS, true);
     d.capC = 8 * d.np;                                     // C goes into compressed rows when it has at most 8 non-zeros per row on average
-    rc |= dev_alloc(h, &d.Cp, B * (np + 1), true);
-    rc |= dev_alloc(h, &d.Ci, B * (size_t)d.capC, true);
-    rc |= dev_alloc(h, &d.Cv, B * (size_t)d.capC, true);
-    rc |= dev_alloc(h, &d.S2, B * (size_t)d.capS * d.capS, true);
-    rc |= dev_alloc(h, &d.DS, B * (size_t)(d.capS / 64) * 4096, true);
-    rc |= dev_alloc(h, &d.D1, B * (size_t)d.nblk * 4096, true);
-    rc |= dev_alloc(h, &d.dscr, B * 4096, true);
-    rc |= dev_alloc(h, &d.nv, B * V_NUM * np, true);
-    rc |= dev_alloc(h, &d.mv, B * M_NUM * mE, true);
-    rc |= dev_alloc(h, &d.sv, B * S_NUM * (size_t)d.capS, true);
-    rc |= dev_alloc(h, &d.mi, B * I_NUM * mE, true);
-    rc |= dev_alloc(h, &d.idx, B * (size_t)d.capS, true);
-    rc |= dev_alloc(h, &d.boxidx, B * np, true);
-    rc |= dev_alloc(h, &d.lbL, B * (size_t)(nComp ? nComp : 1), true);
-    rc |= dev_alloc(h, &d.lbR, B * (size_t)(nComp ? nComp : 1), true);
-    rc |= dev_alloc(h, &d.yk, B * (size_t)d.nd, true);
-    rc |= dev_alloc(h, &d.y0, B * (size_t)d.nd, true);
-    rc |= dev_alloc(h, &d.xout, B * (size_t)nV, true);
-    rc |= dev_alloc(h, &d.yout, B * (size_t)d.nd, true);
-    rc |= dev_alloc(h, &d.stats, B, true);
-    rc |= dev_alloc(h, &d.info, B, true);
-    rc |= dev_alloc(h, &d.prof, B * 16, true);
-    if (rc != 0 || hipStreamSynchronize(h->stream) != hipSuccess) { lcqp_hip_batch_destroy(h); return nullptr; }
-    return h;
+    lcqp_hip_options_default(&d.opt);
+    const size_t B = batch, np = d.np, mE = d.mEcap, nLR = nComp ? nComp : 1;
+    DevMem& m = h->mem;      // zero-filled on the batch's stream
+    const bool ok = m.alloc(g_err, d.Q, B * np * np) && m.alloc(g_err, d.C, B * np * np) && m.alloc(g_err, d.E, B * mE * np) &&
+                    m.alloc(g_err, d.Et, B * mE * np) && m.alloc(g_err, d.F1, B * np * np) && m.alloc(g_err, d.FK, B * np * np) &&
+                    m.alloc(g_err, d.S, B * d.capS * d.capS) && m.alloc(g_err, d.MM, B * d.mMld * d.mMld) && m.alloc(g_err, d.crow, B * d.capS) &&
+                    m.alloc(g_err, d.Cp, B * (np + 1)) && m.alloc(g_err, d.Ci, B * d.capC) && m.alloc(g_err, d.Cv, B * d.capC) &&
+                    m.alloc(g_err, d.S2, B * d.capS * d.capS) && m.alloc(g_err, d.DS, B * (d.capS / 64) * 4096) &&
+                    m.alloc(g_err, d.D1, B * d.nblk * 4096) && m.alloc(g_err, d.dscr, B * 4096) && m.alloc(g_err, d.nv, B * V_NUM * np) &&
+                    m.alloc(g_err, d.mv, B * M_NUM * mE) && m.alloc(g_err, d.sv, B * S_NUM * d.capS) && m.alloc(g_err, d.mi, B * I_NUM * mE) &&
+                    m.alloc(g_err, d.idx, B * d.capS) && m.alloc(g_err, d.boxidx, B * np) && m.alloc(g_err, d.lbL, B * nLR) &&
+                    m.alloc(g_err, d.lbR, B * nLR) && m.alloc(g_err, d.yk, B * d.nd) && m.alloc(g_err, d.y0, B * d.nd) &&
+                    m.alloc(g_err, d.xout, B * nV) && m.alloc(g_err, d.yout, B * d.nd) && m.alloc(g_err, d.stats, B) &&
+                    m.alloc(g_err, d.info, B) && m.alloc(g_err, d.prof, B * 16);
+    if (!ok) return nullptr;
+    if (hipError_t e = hipStreamSynchronize(h->stream)) { hip_fail(g_err, "hipStreamSynchronize(h->stream)", e); return nullptr; }
+    return h.release();
 }
 catch (...) { g_err = "out of host memory"; return nullptr; }   // nothing throws across the C boundary
 
 extern "C" void lcqp_hip_batch_destroy(lcqp_hip_batch_t* h)
 try {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : h->allocs) (void)hipFree(p);
-    for (int k = 0; k < 2; k++) if (h->stage[k]) { (void)hipHostFree(h->stage[k]); (void)hipEventDestroy(h->stageDone[k]); }
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->ev2) (void)hipEventDestroy(h->ev2);
-    if (h->evFork) (void)hipEventDestroy(h->evFork);
-    if (h->evJoin) (void)hipEventDestroy(h->evJoin);
-    if (h->side) (void)hipStreamDestroy(h->side);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;      // ~lcqp_hip_batch: set the device, synchronise, then the members
 }
 catch (...) { }   // nothing throws across the C boundary
 
+// storeSteps: the first 1024 iterates
 extern "C" int lcqp_hip_batch_set_options(lcqp_hip_batch_t* h, const lcqp_options_t* opt)
 try {
-    if (!h || !opt) return LCQP_INVALID_ARGUMENT;
-    if (opt->nDynamicPenalty > 64) { g_err = "nDynamicPenalty > 64 unsupported"; return LCQP_HIP_UNSUPPORTED; }
-    {
-        // tracking vectors of OutputStatistics (src/OutputStatistics.cpp:131-164), first 1024 iterates; the buffers are sized
-        // for the largest maxIterations seen with storeSteps on and grow when a later setOptions raises it
-        DevBatch& d = h->db;
-        const int want = opt->maxIterations + 1 < 1024 ? opt->maxIterations + 1 : 1024;
-        const int have = d.traceCap < 0 ? -d.traceCap : d.traceCap;
-        if (opt->storeSteps && have < want) {
-            HIPCHK(hipSetDevice(h->device));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            for (void* old : {(void*)d.traceS, (void*)d.traceX})      // a regrow frees the smaller buffers
-                if (old) { (void)hipFree(old); h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), old), h->allocs.end()); }
-            d.traceS = d.traceX = nullptr; d.traceCap = 0;
-            if (dev_alloc(h, &d.traceS, (size_t)d.B * want * 8, true) || dev_alloc(h, &d.traceX, (size_t)d.B * want * d.n, true)) return LCQP_HIP_ERROR;
-            if (!d.traceLen && dev_alloc(h, &d.traceLen, (size_t)d.B, true)) return LCQP_HIP_ERROR;
-            d.traceCap = want;
-        } else if (opt->storeSteps) d.traceCap = have;
-        else if (have > 0) d.traceCap = -have;                    // keep the buffers, stop recording
-    }
-    h->db.opt = *opt;
-    h->setupDone = false;   // rho / sigma / prox weights enter the factorisations
-    return 0;
+    return set_options(g_err, h, opt, 1024);
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 
 extern "C" int lcqp_hip_batch_get_trace(lcqp_hip_batch_t* h, int instance, int cap, double* scalars, double* x, int* len)
 try {
-    if (!h || instance < 0 || instance >= h->db.B || !len) return LCQP_INVALID_ARGUMENT;
-    DevBatch& d = h->db;
-    *len = 0;
-    if (d.traceCap <= 0) return 0;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    int n = 0;
-    HIPCHK(hipMemcpy(&n, d.traceLen + instance, sizeof(int), hipMemcpyDeviceToHost));
-    if (n > cap) n = cap;
-    if (scalars && n) HIPCHK(hipMemcpy(scalars, d.traceS + (size_t)instance * d.traceCap * 8, sizeof(double) * 8 * n, hipMemcpyDeviceToHost));
-    if (x && n) HIPCHK(hipMemcpy(x, d.traceX + (size_t)instance * d.traceCap * d.n, sizeof(double) * (size_t)d.n * n, hipMemcpyDeviceToHost));
-    *len = n;
-    return 0;
+    return get_trace(g_err, h, instance, cap, scalars, x, len);
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 
@@ -342,16 +248,13 @@ catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothin
 extern "C" int lcqp_hip_batch_read_profile(lcqp_hip_batch_t* h, unsigned long long* out)
 try {
     if (!h || !out) return LCQP_INVALID_ARGUMENT;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(out, h->db.prof, sizeof(unsigned long long) * (size_t)h->db.B * 16, hipMemcpyDeviceToHost));
+    if (int rc = synchronize(g_err, h)) return rc;
+    HIPCHK(g_err, hipMemcpy(out, h->db.prof, sizeof(unsigned long long) * (size_t)h->db.B * 16, hipMemcpyDeviceToHost));
     return 0;
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 
-extern "C" void* lcqp_hip_batch_stream(lcqp_hip_batch_t* h) { return h ? (void*)h->stream : nullptr; }
-
-static inline double bnd(const double* p, size_t i, double dflt) { return p ? p[i] : dflt; }
+extern "C" void* lcqp_hip_batch_stream(lcqp_hip_batch_t* h) { return h ? (void*)h->stream.s : nullptr; }
 
 extern "C" int lcqp_hip_batch_load(lcqp_hip_batch_t* h, int first, int count,
                                    const double* Q, const double* g, const double* L, const double* R,
@@ -368,33 +271,26 @@ try {
     if (!A && nC > 0) return LCQP_INVALID_CONSTRAINT_MATRIX;         // src/LCQProblem.cpp:569-570
     if (!L || !R) return LCQP_INVALID_COMPLEMENTARITY_MATRIX;        // :611-612
     if ((lb || ub) && d.boxcap == 0) { g_err = "batch was created without box-bound capacity"; return LCQP_INVALID_ARGUMENT; }
-    HIPCHK(hipSetDevice(h->device));
-    // A batch may mix instances with and without lbL / lbR (round 6): an absent bound vector is the zero vector (setComplementarityBounds
-    // :726-785), and the phi expressions of :969-996 with zeros -- phi_const = 0, g_phi = 0, g_tilde = g + rho 0 -- are the arithmetic of an
-    // instance loaded without them, bit for bit.  The batch-wide flag only says whether ANY instance carries bounds, i.e. whether the
-    // kernels read the (zero-filled) arrays at all; a (re)load starting at instance 0, or the first load of the object, starts it over.
-    const int hasL = lbL ? 1 : 0, hasR = lbR ? 1 : 0;
-    if (!h->anyLoaded || first == 0) { d.hasLbL = hasL; d.hasLbR = hasR; h->anyLoaded = true; }
-    else { d.hasLbL |= hasL; d.hasLbR |= hasR; }
+    HIPCHK(g_err, hipSetDevice(h->device));
     // pinned staging: [Qp | Ep | nvb | mvb | ybuf | lbuf | rbuf | info | bidx]
     const size_t nQ = (size_t)np * np, nE = (size_t)mE * np, nNV = (size_t)V_NUM * np, nMV = (size_t)M_NUM * mE;
     const size_t nY = (size_t)d.nd, nLR = (size_t)(nComp ? nComp : 1);
     const size_t infoDbl = (sizeof(InstInfo) + 7) / 8, bidxDbl = ((size_t)np * sizeof(int) + 7) / 8;
     const size_t slotBytes = sizeof(double) * (nQ + nE + nNV + nMV + nY + 2 * nLR + infoDbl + bidxDbl);
     if (h->stageBytes < slotBytes) {
-        for (int k = 0; k < 2; k++) {
-            if (h->stage[k]) { (void)hipHostFree(h->stage[k]); (void)hipEventDestroy(h->stageDone[k]); h->stage[k] = nullptr; }
-            HIPCHK(hipHostMalloc(&h->stage[k], slotBytes, hipHostMallocDefault));
-            HIPCHK(hipEventCreateWithFlags(&h->stageDone[k], hipEventDisableTiming));
-            HIPCHK(hipEventRecord(h->stageDone[k], h->stream));
+        h->stageBytes = 0;
+        for (StageSlot& st : h->stage) {
+            if (st.buf) (void)hipHostFree(st.buf);
+            st.buf = nullptr;
+            HIPCHK(g_err, hipHostMalloc(&st.buf, slotBytes, hipHostMallocDefault));
         }
         h->stageBytes = slotBytes;
     }
     for (int k = 0; k < count; k++) {
         const size_t b = (size_t)first + k;
-        const int slot = k & 1;
-        HIPCHK(hipEventSynchronize(h->stageDone[slot]));            // the copies that last used this slot are done
-        double* Qp = (double*)h->stage[slot];
+        StageSlot& slot = h->stage[k & 1];
+        HIPCHK(g_err, hipEventSynchronize(slot.done));            // the copies that last used this slot are done
+        double* Qp = (double*)slot.buf;
         double* Ep = Qp + nQ; double* nvb = Ep + nE; double* mvb = nvb + nNV; double* ybuf = mvb + nMV;
         double* lbuf = ybuf + nY; double* rbuf = lbuf + nLR;
         InstInfo* info = (InstInfo*)(rbuf + nLR);
@@ -407,20 +303,8 @@ try {
             memcpy(&Ep[(size_t)(nC + r) * np], L + ((size_t)k * nComp + r) * n, sizeof(double) * n);
             memcpy(&Ep[(size_t)(nC + nComp + r) * np], R + ((size_t)k * nComp + r) * n, sizeof(double) * n);
         }
-        double* lE = &mvb[(size_t)M_L * mE];
-        double* uE = &mvb[(size_t)M_U * mE];
-        for (int r = 0; r < nC; r++) { lE[r] = bnd(lbA, (size_t)k * nC + r, -INFINITY); uE[r] = bnd(ubA, (size_t)k * nC + r, INFINITY); }
-        // setComplementarityBounds :726-785
-        for (int i = 0; i < nComp; i++) {
-            if (lbL && lbL[(size_t)k * nComp + i] <= -INFINITY) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
-            if (lbR && lbR[(size_t)k * nComp + i] <= -INFINITY) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
-            lE[nC + i] = bnd(lbL, (size_t)k * nComp + i, 0.0);
-            uE[nC + i] = bnd(ubL, (size_t)k * nComp + i, INFINITY);
-            lE[nC + nComp + i] = bnd(lbR, (size_t)k * nComp + i, 0.0);
-            uE[nC + nComp + i] = bnd(ubR, (size_t)k * nComp + i, INFINITY);
-            lbuf[i] = bnd(lbL, (size_t)k * nComp + i, 0.0);
-            rbuf[i] = bnd(lbR, (size_t)k * nComp + i, 0.0);
-        }
+        int rc = pack_row_bounds(d, h->anyLoaded, first, k, lbA, ubA, lbL, ubL, lbR, ubR, &mvb[(size_t)M_L * mE], &mvb[(size_t)M_U * mE], lbuf, rbuf);
+        if (rc) return rc;
         double* vg = &nvb[(size_t)V_G * np];
         double* vlb = &nvb[(size_t)V_LB * np];
         double* vub = &nvb[(size_t)V_UB * np];
@@ -435,24 +319,24 @@ try {
             if (std::isfinite(vlb[i]) || std::isfinite(vub[i])) bidx[nfin++] = i;
         }
         info->nfin = nfin; info->mE = mA + nfin; info->hasY0 = y0 ? 1 : 0;
-        HIPCHK(hipMemcpyAsync(d.Q + b * nQ, Qp, sizeof(double) * nQ, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(d.E + b * nE, Ep, sizeof(double) * nE, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(d.nv + b * nNV, nvb, sizeof(double) * nNV, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(d.mv + b * nMV, mvb, sizeof(double) * nMV, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(d.boxidx + b * np, bidx, sizeof(int) * np, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(d.info + b, info, sizeof(InstInfo), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(g_err, hipMemcpyAsync(d.Q + b * nQ, Qp, sizeof(double) * nQ, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(g_err, hipMemcpyAsync(d.E + b * nE, Ep, sizeof(double) * nE, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(g_err, hipMemcpyAsync(d.nv + b * nNV, nvb, sizeof(double) * nNV, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(g_err, hipMemcpyAsync(d.mv + b * nMV, mvb, sizeof(double) * nMV, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(g_err, hipMemcpyAsync(d.boxidx + b * np, bidx, sizeof(int) * np, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(g_err, hipMemcpyAsync(d.info + b, info, sizeof(InstInfo), hipMemcpyHostToDevice, h->stream));
         if (nComp) {
-            HIPCHK(hipMemcpyAsync(d.lbL + b * nComp, lbuf, sizeof(double) * nComp, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(hipMemcpyAsync(d.lbR + b * nComp, rbuf, sizeof(double) * nComp, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(g_err, hipMemcpyAsync(d.lbL + b * nComp, lbuf, sizeof(double) * nComp, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(g_err, hipMemcpyAsync(d.lbR + b * nComp, rbuf, sizeof(double) * nComp, hipMemcpyHostToDevice, h->stream));
         }
         if (y0) {
             memcpy(ybuf, y0 + (size_t)k * d.nd, sizeof(double) * d.nd);
-            HIPCHK(hipMemcpyAsync(d.y0 + b * nY, ybuf, sizeof(double) * nY, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(g_err, hipMemcpyAsync(d.y0 + b * nY, ybuf, sizeof(double) * nY, hipMemcpyHostToDevice, h->stream));
         }
-        HIPCHK(hipEventRecord(h->stageDone[slot], h->stream));
+        HIPCHK(g_err, hipEventRecord(slot.done, h->stream));
     }
-    HIPCHK(hipStreamSynchronize(h->stream));
-    h->setupDone = false;
+    HIPCHK(g_err, hipStreamSynchronize(h->stream));
+    h->anyLoaded = true;
     return 0;
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
@@ -460,14 +344,13 @@ catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothin
 extern "C" int lcqp_hip_batch_generate_synthetic(lcqp_hip_batch_t* h, uint64_t seed0, uint64_t firstInstance)
 try {
     if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(g_err, hipSetDevice(h->device));
     DevBatch& d = h->db;
     if (d.nComp * 2 > d.n) { g_err = "synthetic generator needs 2*nComp <= nV"; return LCQP_INVALID_ARGUMENT; }
     d.hasLbL = d.hasLbR = 0; h->anyLoaded = true;
     dispatch_db(h, ID_k_synth_fill, d.B, nullptr, 0, seed0, firstInstance);
     dispatch_db(h, ID_k_synth_Q, d.B * (d.nblk * (d.nblk + 1) / 2));
-    HIPCHK(hipGetLastError());
-    h->setupDone = false;
+    HIPCHK(g_err, hipGetLastError());
     return 0;
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
@@ -476,15 +359,14 @@ extern "C" int lcqp_hip_batch_read_problem(lcqp_hip_batch_t* h, int b, double* Q
                                            double* A, double* lbA, double* ubA)
 try {
     if (!h || b < 0 || b >= h->db.B) return LCQP_INVALID_ARGUMENT;
-    HIPCHK(hipSetDevice(h->device));
+    if (int rc = synchronize(g_err, h)) return rc;
     DevBatch& d = h->db;
     const int n = d.n, nC = d.nC, nComp = d.nComp, np = d.np, mE = d.mEcap;
-    HIPCHK(hipStreamSynchronize(h->stream));
     std::vector<double> Qp((size_t)np * np), Ep((size_t)mE * np), nvb((size_t)V_NUM * np), mvb((size_t)M_NUM * mE);
-    HIPCHK(hipMemcpy(Qp.data(), d.Q + (size_t)b * np * np, sizeof(double) * np * np, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(Ep.data(), d.E + (size_t)b * mE * np, sizeof(double) * mE * np, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(nvb.data(), d.nv + (size_t)b * V_NUM * np, sizeof(double) * V_NUM * np, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(mvb.data(), d.mv + (size_t)b * M_NUM * mE, sizeof(double) * M_NUM * mE, hipMemcpyDeviceToHost));
+    HIPCHK(g_err, hipMemcpy(Qp.data(), d.Q + (size_t)b * np * np, sizeof(double) * np * np, hipMemcpyDeviceToHost));
+    HIPCHK(g_err, hipMemcpy(Ep.data(), d.E + (size_t)b * mE * np, sizeof(double) * mE * np, hipMemcpyDeviceToHost));
+    HIPCHK(g_err, hipMemcpy(nvb.data(), d.nv + (size_t)b * V_NUM * np, sizeof(double) * V_NUM * np, hipMemcpyDeviceToHost));
+    HIPCHK(g_err, hipMemcpy(mvb.data(), d.mv + (size_t)b * M_NUM * mE, sizeof(double) * M_NUM * mE, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) {
         if (Q) memcpy(Q + (size_t)i * n, &Qp[(size_t)i * np], sizeof(double) * n);
         if (g) g[i] = nvb[(size_t)V_G * np + i];
@@ -515,11 +397,11 @@ static int launch_setup(lcqp_hip_batch* h)
     // (profiles/round6/README.md): the side branch beside k_trsm, or beside k_trsm and k_build_M -- both 0.2 ms slower.
     const bool fork = d.nComp > 0;
     if (fork) {
-        HIPCHK(hipEventRecord(h->evFork, on));
-        HIPCHK(hipStreamWaitEvent(h->side, h->evFork, 0));
+        HIPCHK(g_err, hipEventRecord(h->evFork, on));
+        HIPCHK(g_err, hipStreamWaitEvent(h->side, h->evFork, 0));
         dispatch_db(h, ID_k_build_C, d.B * ntile, nullptr, 0, 0, 0, h->side);
         dispatch_db(h, ID_k_compress_C, d.B, nullptr, 0, 0, 0, h->side);
-        HIPCHK(hipEventRecord(h->evJoin, h->side));
+        HIPCHK(g_err, hipEventRecord(h->evJoin, h->side));
     }
     // more than three workgroups per CU (np <= 256: 36 KB of LDS each): the instantiation held to 128 registers, so that four are resident and
     // the batch needs one round
@@ -527,10 +409,9 @@ static int launch_setup(lcqp_hip_batch* h)
     dispatch_db(h, h->overlapped ? ID_k_trsm_streamed : ID_k_trsm, d.B * nrb);
     // the join sits in front of the last setup kernel, not behind it: an event recorded right after a stream wait carried a late time stamp
     // (the homotopy kernel appeared 2 ms shorter than rocprofv3 and the wall clock say), and the side branch has long finished by then
-    if (fork) HIPCHK(hipStreamWaitEvent(on, h->evJoin, 0));
+    if (fork) HIPCHK(g_err, hipStreamWaitEvent(on, h->evJoin, 0));
     dispatch_db(h, ID_k_build_M, d.B * nmt);
-    HIPCHK(hipGetLastError());
-    h->setupDone = true;
+    HIPCHK(g_err, hipGetLastError());
     return 0;
 }
 
@@ -544,7 +425,7 @@ extern "C" int lcqp_hip_batch_set_overlapped(lcqp_hip_batch_t* h, int overlapped
 extern "C" int lcqp_hip_batch_setup(lcqp_hip_batch_t* h)
 try {
     if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(g_err, hipSetDevice(h->device));
     return launch_setup(h);
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
@@ -556,14 +437,14 @@ catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothin
 extern "C" int lcqp_hip_batch_run(lcqp_hip_batch_t* h)
 try {
     if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    HIPCHK(g_err, hipSetDevice(h->device));
+    HIPCHK(g_err, hipEventRecord(h->ev0, h->stream));
     int rc = launch_setup(h);   // the factorisations are part of runSolver's cost (initializeSolver :885)
     if (rc) return rc;
-    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    HIPCHK(g_err, hipEventRecord(h->ev1, h->stream));
     dispatch_db(h, ID_k_lcqp_run, h->db.B);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(h->ev2, h->stream));
+    HIPCHK(g_err, hipGetLastError());
+    HIPCHK(g_err, hipEventRecord(h->ev2, h->stream));
     h->ran = true;
     return 0;
 }
@@ -571,34 +452,19 @@ catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothin
 
 extern "C" int lcqp_hip_batch_synchronize(lcqp_hip_batch_t* h)
 try {
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    return synchronize(g_err, h);
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 
 extern "C" int lcqp_hip_batch_last_timing(lcqp_hip_batch_t* h, float* setup_ms, float* solve_ms)
 try {
-    if (!h || !h->ran) return LCQP_INVALID_ARGUMENT;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipEventSynchronize(h->ev2));
-    if (setup_ms) HIPCHK(hipEventElapsedTime(setup_ms, h->ev0, h->ev1));
-    if (solve_ms) HIPCHK(hipEventElapsedTime(solve_ms, h->ev1, h->ev2));
-    return 0;
+    return last_timing(g_err, h, setup_ms, solve_ms);
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 
 extern "C" int lcqp_hip_batch_get_solution(lcqp_hip_batch_t* h, double* x, double* y, lcqp_stats_t* stats)
 try {
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    HIPCHK(hipSetDevice(h->device));
-    DevBatch& d = h->db;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    if (x) HIPCHK(hipMemcpy(x, d.xout, sizeof(double) * (size_t)d.B * d.n, hipMemcpyDeviceToHost));
-    if (y) HIPCHK(hipMemcpy(y, d.yout, sizeof(double) * (size_t)d.B * d.nd, hipMemcpyDeviceToHost));
-    if (stats) HIPCHK(hipMemcpy(stats, d.stats, sizeof(lcqp_stats_t) * (size_t)d.B, hipMemcpyDeviceToHost));
-    return 0;
+    return get_solution(g_err, h, h ? h->db.nd : 0, x, y, stats);
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 
@@ -641,10 +507,9 @@ extern "C" int lcqp_hip_batch_work_sums(lcqp_hip_batch_t* h, double out[6])
 try {
     if (!h || !out) return LCQP_INVALID_ARGUMENT;
     DevBatch& d = h->db;
-    HIPCHK(hipSetDevice(h->device));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    if (int rc = synchronize(g_err, h)) return rc;
     std::vector<InstInfo> info(d.B);
-    HIPCHK(hipMemcpy(info.data(), d.info, sizeof(InstInfo) * (size_t)d.B, hipMemcpyDeviceToHost));
+    HIPCHK(g_err, hipMemcpy(info.data(), d.info, sizeof(InstInfo) * (size_t)d.B, hipMemcpyDeviceToHost));
     for (int k = 0; k < 6; k++) out[k] = 0.0;
     for (int b = 0; b < d.B; b++) for (int k = 0; k < 6; k++) out[k] += info[b].work[k];
     return 0;
@@ -817,18 +682,23 @@ catch (...) { }   // nothing throws across the C boundary
 // =================================================================================================
 // building blocks (tests, micro-benchmarks)
 // =================================================================================================
-struct TmpBuf {
-    std::vector<void*> p;
-    ~TmpBuf() { for (void* q : p) (void)hipFree(q); }
-    double* get(size_t count, bool zero = true)
-    {
-        void* q = nullptr;
-        if (hipMalloc(&q, (count ? count : 1) * sizeof(double)) != hipSuccess) return nullptr;
-        if (zero) (void)hipMemset(q, 0, (count ? count : 1) * sizeof(double));
-        p.push_back(q);
-        return (double*)q;
-    }
-};
+// mean time of `repeat` launches (at least one) after one warm-up launch, all on the null stream
+template <class Launch>
+static int time_launches(int repeat, float* ms, Launch launch)
+{
+    Event e0, e1;      // destroyed on every return
+    if (hipError_t e = e0.status ? e0.status : e1.status) return hip_fail(g_err, "hipEventCreate", e);
+    if (repeat < 1) repeat = 1;
+    launch();
+    HIPCHK(g_err, hipEventRecord(e0, 0));
+    for (int r = 0; r < repeat; r++) launch();
+    HIPCHK(g_err, hipEventRecord(e1, 0));
+    HIPCHK(g_err, hipEventSynchronize(e1));
+    float t = 0.f;
+    HIPCHK(g_err, hipEventElapsedTime(&t, e0, e1));
+    if (ms) *ms = t / repeat;
+    return 0;
+}
 
 static int upload_padded(double* dst, const double* src, int batch, int rows, int cols, int ld, int rowsPad)
 {
@@ -837,7 +707,7 @@ static int upload_padded(double* dst, const double* src, int batch, int rows, in
     for (int b = 0; b < batch; b++) {
         std::fill(buf.begin(), buf.end(), 0.0);
         for (int r = 0; r < rows; r++) memcpy(&buf[(size_t)r * ld], src + ((size_t)b * rows + r) * cols, sizeof(double) * cols);
-        HIPCHK(hipMemcpy(dst + (size_t)b * rowsPad * ld, buf.data(), sizeof(double) * rowsPad * ld, hipMemcpyHostToDevice));
+        HIPCHK(g_err, hipMemcpy(dst + (size_t)b * rowsPad * ld, buf.data(), sizeof(double) * rowsPad * ld, hipMemcpyHostToDevice));
     }
     return 0;
 }
@@ -845,7 +715,7 @@ static int download_padded(double* dst, const double* src, int batch, int rows, 
 {
     std::vector<double> buf((size_t)rowsPad * ld);
     for (int b = 0; b < batch; b++) {
-        HIPCHK(hipMemcpy(buf.data(), src + (size_t)b * rowsPad * ld, sizeof(double) * rowsPad * ld, hipMemcpyDeviceToHost));
+        HIPCHK(g_err, hipMemcpy(buf.data(), src + (size_t)b * rowsPad * ld, sizeof(double) * rowsPad * ld, hipMemcpyDeviceToHost));
         for (int r = 0; r < rows; r++) memcpy(dst + ((size_t)b * rows + r) * cols, &buf[(size_t)r * ld], sizeof(double) * cols);
     }
     return 0;
@@ -855,14 +725,16 @@ extern "C" int lcqp_hip_util_symv(int batch, int n, double alpha, const double* 
 try {
     if (n <= 0 || n > 4096 || batch <= 0) return LCQP_HIP_UNSUPPORTED;
     const int nch = padded_nch(n), np = 128 * nch;
-    TmpBuf tb;
-    double *dA = tb.get((size_t)batch * np * np), *db_ = tb.get((size_t)batch * np), *dc = tb.get((size_t)batch * np), *dd = tb.get((size_t)batch * np);
-    if (!dA || !db_ || !dc || !dd) return set_err("hipMalloc", hipErrorOutOfMemory);
+    DevMem tb;
+    double *dA, *db_, *dc, *dd;
+    if (!tb.alloc(g_err, dA, (size_t)batch * np * np) || !tb.alloc(g_err, db_, (size_t)batch * np) || !tb.alloc(g_err, dc, (size_t)batch * np) ||
+        !tb.alloc(g_err, dd, (size_t)batch * np))
+        return LCQP_HIP_ERROR;
     int rc = upload_padded(dA, A, batch, n, n, np, np); if (rc) return rc;
     rc = upload_padded(db_, bv, batch, 1, n, np, 1); if (rc) return rc;
     rc = upload_padded(dc, cv, batch, 1, n, np, 1); if (rc) return rc;
     { LaunchArgs la; la.n = n; la.alpha = alpha; la.A = dA; la.b = db_; la.c = dc; la.d = dd; lcqp_dispatch(nch, ID_k_util_symv, batch, 0, la); }
-    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(g_err, hipDeviceSynchronize());
     return download_padded(dv, dd, batch, 1, n, np, 1);
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
@@ -871,19 +743,16 @@ static int util_rows(int batch, int m, int n, const double* A, const double* x, 
 {
     if (n <= 0 || n > 4096 || batch <= 0 || m <= 0) return LCQP_HIP_UNSUPPORTED;
     const int nch = padded_nch(n), np = 128 * nch;
-    TmpBuf tb;
-    double* dA = tb.get((size_t)batch * m * np);
-    double* dx = x ? tb.get((size_t)batch * np) : nullptr;
-    double* dd = dots ? tb.get((size_t)batch * m) : nullptr;
-    double* dcf = coef ? tb.get((size_t)batch * m) : nullptr;
-    double* dout = outT ? tb.get((size_t)batch * np) : nullptr;
-    if (!dA) return set_err("hipMalloc", hipErrorOutOfMemory);
+    DevMem tb;
+    double *dA, *dx = nullptr, *dd = nullptr, *dcf = nullptr, *dout = nullptr;
+    if (!tb.alloc(g_err, dA, (size_t)batch * m * np) || (x && !tb.alloc(g_err, dx, (size_t)batch * np)) || (dots && !tb.alloc(g_err, dd, (size_t)batch * m)) ||
+        (coef && !tb.alloc(g_err, dcf, (size_t)batch * m, coef)) || (outT && !tb.alloc(g_err, dout, (size_t)batch * np)))
+        return LCQP_HIP_ERROR;
     int rc = upload_padded(dA, A, batch, m, n, np, m); if (rc) return rc;
     if (x) { rc = upload_padded(dx, x, batch, 1, n, np, 1); if (rc) return rc; }
-    if (coef) HIPCHK(hipMemcpy(dcf, coef, sizeof(double) * (size_t)batch * m, hipMemcpyHostToDevice));
     { LaunchArgs la; la.m = m; la.A = dA; la.x = dx; la.dots = dd; la.coef = dcf; la.outT = dout; lcqp_dispatch(nch, ID_k_util_rows, batch, 0, la); }
-    HIPCHK(hipDeviceSynchronize());
-    if (dots) HIPCHK(hipMemcpy(dots, dd, sizeof(double) * (size_t)batch * m, hipMemcpyDeviceToHost));
+    HIPCHK(g_err, hipDeviceSynchronize());
+    if (dots) HIPCHK(g_err, hipMemcpy(dots, dd, sizeof(double) * (size_t)batch * m, hipMemcpyDeviceToHost));
     if (outT) return download_padded(outT, dout, batch, 1, n, np, 1);
     return 0;
 }
@@ -893,22 +762,19 @@ extern "C" int lcqp_hip_util_rows_list(int batch, int m, int n, const double* A,
 try {
     if (n <= 0 || n > 4096 || batch <= 0 || m <= 0 || nlist < 0 || nlist > m || !list) return LCQP_HIP_UNSUPPORTED;
     const int nch = padded_nch(n), np = 128 * nch;
-    TmpBuf tb;
-    double* dA = tb.get((size_t)batch * m * np);
-    double* dx = x ? tb.get((size_t)batch * np) : nullptr;
-    double* dd = dots ? tb.get((size_t)batch * m) : nullptr;
-    double* dcf = coef ? tb.get((size_t)batch * m) : nullptr;
-    double* dout = outT ? tb.get((size_t)batch * np) : nullptr;
-    int* dl = reinterpret_cast<int*>(tb.get(((size_t)batch * std::max(nlist, 1) + 1) / 2 + 1));
-    if (!dA || !dl) return set_err("hipMalloc", hipErrorOutOfMemory);
+    DevMem tb;
+    double *dA, *dx = nullptr, *dd = nullptr, *dcf = nullptr, *dout = nullptr;
+    int* dl;
+    if (!tb.alloc(g_err, dA, (size_t)batch * m * np) || (x && !tb.alloc(g_err, dx, (size_t)batch * np)) ||
+        (dots && !tb.alloc(g_err, dd, (size_t)batch * m, dots)) ||      // rows outside the list keep the caller's values
+        (coef && !tb.alloc(g_err, dcf, (size_t)batch * m, coef)) || (outT && !tb.alloc(g_err, dout, (size_t)batch * np)) ||
+        !tb.alloc(g_err, dl, (size_t)batch * nlist, list))
+        return LCQP_HIP_ERROR;
     int rc = upload_padded(dA, A, batch, m, n, np, m); if (rc) return rc;
     if (x) { rc = upload_padded(dx, x, batch, 1, n, np, 1); if (rc) return rc; }
-    if (coef) HIPCHK(hipMemcpy(dcf, coef, sizeof(double) * (size_t)batch * m, hipMemcpyHostToDevice));
-    if (dots) HIPCHK(hipMemcpy(dd, dots, sizeof(double) * (size_t)batch * m, hipMemcpyHostToDevice));      // rows outside the list keep the caller's values
-    if (nlist > 0) HIPCHK(hipMemcpy(dl, list, sizeof(int) * (size_t)batch * nlist, hipMemcpyHostToDevice));
     { LaunchArgs la; la.m = m; la.n = nlist; la.A = dA; la.list = dl; la.x = dx; la.dots = dd; la.coef = dcf; la.outT = dout; lcqp_dispatch(nch, ID_k_util_rows_list, batch, 0, la); }
-    HIPCHK(hipDeviceSynchronize());
-    if (dots) HIPCHK(hipMemcpy(dots, dd, sizeof(double) * (size_t)batch * m, hipMemcpyDeviceToHost));
+    HIPCHK(g_err, hipDeviceSynchronize());
+    if (dots) HIPCHK(g_err, hipMemcpy(dots, dd, sizeof(double) * (size_t)batch * m, hipMemcpyDeviceToHost));
     if (outT) return download_padded(outT, dout, batch, 1, n, np, 1);
     return 0;
 }
@@ -980,12 +846,14 @@ struct lcqp_hip_csc {
     int *p, *i, *tp, *ti;        // CSC of A and CSC of A' (device)
     double *x, *tx;
     double *vin, *vout, *vadd;   // staging vectors of length max(m, n)
+    DevMem mem;
+    ~lcqp_hip_csc() { (void)hipSetDevice(device); }      // then the memory
 };
 
 extern "C" lcqp_hip_csc_t* lcqp_hip_csc_create(int m, int n, int nnz, const int* p, const int* i, const double* x, int device)
 try {
     if (m <= 0 || n <= 0 || nnz < 0 || !p || (nnz && (!i || !x))) { g_err = "invalid CSC arguments"; return nullptr; }
-    HIPCHKN(hipSetDevice(device));
+    if (hipError_t e = hipSetDevice(device)) { hip_fail(g_err, "hipSetDevice(device)", e); return nullptr; }
     // transpose on the host: counting sort by row index (stable, so columns stay ascending inside a row)
     std::vector<int> tp(m + 1, 0), ti(nnz ? nnz : 1);
     std::vector<double> tx(nnz ? nnz : 1);
@@ -994,33 +862,21 @@ try {
     std::vector<int> cur(tp.begin(), tp.end() - 1);
     for (int c = 0; c < n; c++)
         for (int k = p[c]; k < p[c + 1]; k++) { const int d = cur[i[k]]++; ti[d] = c; tx[d] = x[k]; }
-    lcqp_hip_csc* h = new lcqp_hip_csc();
-    memset(h, 0, sizeof(*h));
+    std::unique_ptr<lcqp_hip_csc> h(new lcqp_hip_csc());
     h->m = m; h->n = n; h->nnz = nnz; h->device = device;
-    const size_t nz = nnz ? nnz : 1, mx = (size_t)(m > n ? m : n);
-    if (hipMalloc((void**)&h->p, sizeof(int) * (n + 1)) != hipSuccess || hipMalloc((void**)&h->i, sizeof(int) * nz) != hipSuccess ||
-        hipMalloc((void**)&h->x, sizeof(double) * nz) != hipSuccess || hipMalloc((void**)&h->tp, sizeof(int) * (m + 1)) != hipSuccess ||
-        hipMalloc((void**)&h->ti, sizeof(int) * nz) != hipSuccess || hipMalloc((void**)&h->tx, sizeof(double) * nz) != hipSuccess ||
-        hipMalloc((void**)&h->vin, sizeof(double) * mx) != hipSuccess || hipMalloc((void**)&h->vout, sizeof(double) * mx) != hipSuccess ||
-        hipMalloc((void**)&h->vadd, sizeof(double) * mx) != hipSuccess) { g_err = "hipMalloc failed"; lcqp_hip_csc_destroy(h); return nullptr; }
-    HIPCHKN(hipMemcpy(h->p, p, sizeof(int) * (n + 1), hipMemcpyHostToDevice));
-    HIPCHKN(hipMemcpy(h->tp, tp.data(), sizeof(int) * (m + 1), hipMemcpyHostToDevice));
-    if (nnz) {
-        HIPCHKN(hipMemcpy(h->i, i, sizeof(int) * nnz, hipMemcpyHostToDevice));
-        HIPCHKN(hipMemcpy(h->x, x, sizeof(double) * nnz, hipMemcpyHostToDevice));
-        HIPCHKN(hipMemcpy(h->ti, ti.data(), sizeof(int) * nnz, hipMemcpyHostToDevice));
-        HIPCHKN(hipMemcpy(h->tx, tx.data(), sizeof(double) * nnz, hipMemcpyHostToDevice));
-    }
-    return h;
+    const size_t mx = (size_t)(m > n ? m : n);
+    DevMem& dm = h->mem;
+    const bool ok = dm.alloc(g_err, h->p, n + 1, p) && dm.alloc(g_err, h->i, nnz, i) && dm.alloc(g_err, h->x, nnz, x) &&
+                    dm.alloc(g_err, h->tp, m + 1, tp.data()) && dm.alloc(g_err, h->ti, nnz, ti.data()) && dm.alloc(g_err, h->tx, nnz, tx.data()) &&
+                    dm.alloc(g_err, h->vin, mx) && dm.alloc(g_err, h->vout, mx) && dm.alloc(g_err, h->vadd, mx);
+    if (!ok) return nullptr;
+    if (hipError_t e = hipStreamSynchronize(nullptr)) { hip_fail(g_err, "hipStreamSynchronize(nullptr)", e); return nullptr; }      // the zero-fills
+    return h.release();
 }
 catch (...) { g_err = "out of host memory"; return nullptr; }   // nothing throws across the C boundary
 
 extern "C" void lcqp_hip_csc_destroy(lcqp_hip_csc_t* h)
 try {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    (void)hipFree(h->p); (void)hipFree(h->i); (void)hipFree(h->x); (void)hipFree(h->tp); (void)hipFree(h->ti); (void)hipFree(h->tx);
-    (void)hipFree(h->vin); (void)hipFree(h->vout); (void)hipFree(h->vadd);
     delete h;
 }
 catch (...) { }   // nothing throws across the C boundary
@@ -1031,28 +887,19 @@ extern "C" int lcqp_hip_csc_apply(lcqp_hip_csc_t* h, int transposed, double alph
                                   int repeat, float* ms)
 try {
     if (!h || !b || !d) return LCQP_INVALID_ARGUMENT;
-    HIPCHK(hipSetDevice(h->device));
+    HIPCHK(g_err, hipSetDevice(h->device));
     const int nin = transposed ? h->m : h->n, nout = transposed ? h->n : h->m;
-    HIPCHK(hipMemcpy(h->vin, b, sizeof(double) * nin, hipMemcpyHostToDevice));
-    if (c) HIPCHK(hipMemcpy(h->vadd, c, sizeof(double) * nout, hipMemcpyHostToDevice));
+    HIPCHK(g_err, hipMemcpy(h->vin, b, sizeof(double) * nin, hipMemcpyHostToDevice));
+    if (c) HIPCHK(g_err, hipMemcpy(h->vadd, c, sizeof(double) * nout, hipMemcpyHostToDevice));
     const int* ptr = transposed ? h->p : h->tp;     // A'b gathers over the columns of A, A b over the columns of A'
     const int* idx = transposed ? h->i : h->ti;
     const double* val = transposed ? h->x : h->tx;
     const int grid = (nout * 16 + 255) / 256;
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    if (repeat < 1) repeat = 1;
-    hipLaunchKernelGGL(k_seg_gather, dim3(grid), dim3(256), 0, 0, nout, ptr, idx, val, h->vin, alpha, c ? h->vadd : nullptr, h->vout);
-    HIPCHK(hipEventRecord(e0, 0));
-    for (int r = 0; r < repeat; r++)
+    const int rc = time_launches(repeat, ms, [&] {
         hipLaunchKernelGGL(k_seg_gather, dim3(grid), dim3(256), 0, 0, nout, ptr, idx, val, h->vin, alpha, c ? h->vadd : nullptr, h->vout);
-    HIPCHK(hipEventRecord(e1, 0));
-    HIPCHK(hipEventSynchronize(e1));
-    float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, e0, e1));
-    if (ms) *ms = t / repeat;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    HIPCHK(hipMemcpy(d, h->vout, sizeof(double) * nout, hipMemcpyDeviceToHost));
+    });
+    if (rc) return rc;
+    HIPCHK(g_err, hipMemcpy(d, h->vout, sizeof(double) * nout, hipMemcpyDeviceToHost));
     return 0;
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
@@ -1069,30 +916,19 @@ extern "C" int lcqp_hip_bench_rows(int batch, int m, int n, int mode, int repeat
 try {
     if (n <= 0 || n > 4096 || batch <= 0 || m <= 0) return LCQP_HIP_UNSUPPORTED;
     const int nch = padded_nch(n), np = 128 * nch;
-    TmpBuf tb;
-    double *dA = tb.get((size_t)batch * m * np, false), *dx = tb.get((size_t)batch * np, false), *dd = tb.get((size_t)batch * m, false);
-    double *dcf = tb.get((size_t)batch * m, false), *dout = tb.get((size_t)batch * np, false);
-    if (!dA || !dx || !dd || !dcf || !dout) return set_err("hipMalloc", hipErrorOutOfMemory);
+    DevMem tb;
+    double *dA, *dx, *dd, *dcf, *dout;
+    if (!tb.alloc(g_err, dA, (size_t)batch * m * np) || !tb.alloc(g_err, dx, (size_t)batch * np) || !tb.alloc(g_err, dd, (size_t)batch * m) ||
+        !tb.alloc(g_err, dcf, (size_t)batch * m) || !tb.alloc(g_err, dout, (size_t)batch * np))
+        return LCQP_HIP_ERROR;
     hipLaunchKernelGGL(k_fill_random, dim3(2048), dim3(256), 0, 0, dA, (size_t)batch * m * np, 1ULL);
     hipLaunchKernelGGL(k_fill_random, dim3(256), dim3(256), 0, 0, dx, (size_t)batch * np, 2ULL);
     hipLaunchKernelGGL(k_fill_random, dim3(256), dim3(256), 0, 0, dcf, (size_t)batch * m, 3ULL);
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    const double* px = (mode & 1) ? dx : nullptr;
-    double* pd = (mode & 1) ? dd : nullptr;
-    const double* pc = (mode & 2) ? dcf : nullptr;
-    double* po = (mode & 2) ? dout : nullptr;
-    for (int r = 0; r <= repeat; r++) {
-        if (r == 1) HIPCHK(hipEventRecord(e0, 0));
-        { LaunchArgs la; la.m = m; la.A = dA; la.x = px; la.dots = pd; la.coef = pc; la.outT = po; lcqp_dispatch(nch, ID_k_util_rows, batch, 0, la); }
-    }
-    HIPCHK(hipEventRecord(e1, 0));
-    HIPCHK(hipEventSynchronize(e1));
-    float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, e0, e1));
-    if (ms) *ms = t / (repeat > 0 ? repeat : 1);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return 0;
+    LaunchArgs la;
+    la.m = m; la.A = dA;
+    la.x = (mode & 1) ? dx : nullptr; la.dots = (mode & 1) ? dd : nullptr;
+    la.coef = (mode & 2) ? dcf : nullptr; la.outT = (mode & 2) ? dout : nullptr;
+    return time_launches(repeat, ms, [&] { lcqp_dispatch(nch, ID_k_util_rows, batch, 0, la); });
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 
@@ -1100,13 +936,12 @@ extern "C" int lcqp_hip_chol_solve(int batch, int n, const double* K, const doub
 try {
     if (n <= 0 || n > LCQP_MAX_ACTIVE || batch <= 0) return LCQP_HIP_UNSUPPORTED;   // k_chol / k_backsolve use the 35 KiB arena
     const int np = ((n + 63) / 64) * 64, nblk = np / 64;
-    TmpBuf tb;
-    double *dF = tb.get((size_t)batch * np * np), *dscr = tb.get((size_t)batch * 4096), *drhs = tb.get((size_t)batch * np), *dx = tb.get((size_t)batch * np);
-    int* dfail = nullptr;
-    HIPCHK(hipMalloc((void**)&dfail, sizeof(int) * batch));
-    tb.p.push_back(dfail);
-    HIPCHK(hipMemset(dfail, 0, sizeof(int) * batch));
-    if (!dF || !dscr || !drhs || !dx) return set_err("hipMalloc", hipErrorOutOfMemory);
+    DevMem tb;
+    double *dF, *dscr, *drhs, *dx;
+    int* dfail;
+    if (!tb.alloc(g_err, dF, (size_t)batch * np * np) || !tb.alloc(g_err, dscr, (size_t)batch * 4096) || !tb.alloc(g_err, drhs, (size_t)batch * np) ||
+        !tb.alloc(g_err, dx, (size_t)batch * np) || !tb.alloc(g_err, dfail, batch))
+        return LCQP_HIP_ERROR;
     // pad with a unit diagonal
     {
         std::vector<double> buf((size_t)np * np);
@@ -1114,27 +949,16 @@ try {
             std::fill(buf.begin(), buf.end(), 0.0);
             for (int i = 0; i < n; i++) memcpy(&buf[(size_t)i * np], K + ((size_t)bb * n + i) * n, sizeof(double) * n);
             for (int i = n; i < np; i++) buf[(size_t)i * np + i] = 1.0;
-            HIPCHK(hipMemcpy(dF + (size_t)bb * np * np, buf.data(), sizeof(double) * np * np, hipMemcpyHostToDevice));
+            HIPCHK(g_err, hipMemcpy(dF + (size_t)bb * np * np, buf.data(), sizeof(double) * np * np, hipMemcpyHostToDevice));
         }
     }
     int rc = upload_padded(drhs, b, batch, 1, n, np, 1); if (rc) return rc;
     hipLaunchKernelGGL(k_chol, dim3(batch), dim3(WG), 0, 0, np, nblk, n, dF, dscr, dfail);
-    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(g_err, hipDeviceSynchronize());
     std::vector<int> fail(batch);
-    HIPCHK(hipMemcpy(fail.data(), dfail, sizeof(int) * batch, hipMemcpyDeviceToHost));
+    HIPCHK(g_err, hipMemcpy(fail.data(), dfail, sizeof(int) * batch, hipMemcpyDeviceToHost));
     for (int i = 0; i < batch; i++) if (fail[i]) { g_err = "matrix not positive definite"; return LCQP_SUBPROBLEM_SOLVER_ERROR; }
-    hipEvent_t e0, e1;
-    HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
-    if (repeat < 1) repeat = 1;
-    hipLaunchKernelGGL(k_backsolve, dim3(batch), dim3(WG), 0, 0, np, nblk, dF, drhs, dx);   // warm-up
-    HIPCHK(hipEventRecord(e0, 0));
-    for (int r = 0; r < repeat; r++) hipLaunchKernelGGL(k_backsolve, dim3(batch), dim3(WG), 0, 0, np, nblk, dF, drhs, dx);
-    HIPCHK(hipEventRecord(e1, 0));
-    HIPCHK(hipEventSynchronize(e1));
-    float t = 0.f;
-    HIPCHK(hipEventElapsedTime(&t, e0, e1));
-    if (ms) *ms = t / repeat;
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    return download_padded(x, dx, batch, 1, n, np, 1);
+    rc = time_launches(repeat, ms, [&] { hipLaunchKernelGGL(k_backsolve, dim3(batch), dim3(WG), 0, 0, np, nblk, dF, drhs, dx); });
+    return rc ? rc : download_padded(x, dx, batch, 1, n, np, 1);
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary

@@ -1,0 +1,187 @@
+// lcqp_host_rt.hpp -- host runtime shared by the C ABIs of the dense (lcqp_hip.hip) and sparse (lcqp_sparse.hip) arms: error reporting,
+// owners of streams, events and device memory, and the entry-point bodies both arms have in common.  Host code only.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "../../include/lcqp_hip.h"
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+#include <type_traits>
+#include <vector>
+
+namespace lcqp_rt {
+
+// "<call>: <HIP reason>" into an arm's error slot (lcqp_hip_last_error / lcqp_hip_sparse_last_error)
+inline int hip_fail(std::string& slot, const char* call, hipError_t e)
+{
+    slot = std::string(call) + ": " + hipGetErrorString(e);
+    return LCQP_HIP_ERROR;
+}
+#define HIPCHK(slot, call)                                                 \
+    do {                                                                   \
+        hipError_t e_ = (call);                                            \
+        if (e_ != hipSuccess) return lcqp_rt::hip_fail(slot, #call, e_);   \
+    } while (0)
+
+// a stream / an event, created by the constructor (its result in `status`) and destroyed by the destructor
+struct Stream {
+    hipStream_t s = nullptr;
+    hipError_t status = hipStreamCreate(&s);
+    Stream() = default;
+    Stream(const Stream&) = delete; Stream& operator=(const Stream&) = delete;
+    ~Stream() { if (s) (void)hipStreamDestroy(s); }
+    operator hipStream_t() const { return s; }
+};
+struct Event {
+    hipEvent_t e = nullptr;
+    hipError_t status;
+    explicit Event(unsigned flags = hipEventDefault) : status(hipEventCreateWithFlags(&e, flags)) {}
+    Event(const Event&) = delete; Event& operator=(const Event&) = delete;
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    operator hipEvent_t() const { return e; }
+};
+
+// The device memory of a handle or of one call: `count` elements of T (at least one), copied from `init` or zero-filled on `zeroOn`
+// (a handle's *_create synchronises that stream before it returns).  release() frees one allocation, the destructor all of them.
+struct DevMem {
+    hipStream_t zeroOn = nullptr;
+    std::vector<void*> ptrs;
+    DevMem() = default;
+    explicit DevMem(hipStream_t s) : zeroOn(s) {}
+    DevMem(const DevMem&) = delete; DevMem& operator=(const DevMem&) = delete;
+    ~DevMem() { for (void* p : ptrs) (void)hipFree(p); }
+    template <class T>
+    bool alloc(std::string& err, T*& p, size_t count, const std::remove_const_t<T>* init = nullptr)
+    {
+        const size_t bytes = (count ? count : 1) * sizeof(T);
+        void* q = nullptr;
+        ptrs.reserve(ptrs.size() + 1);      // the push_back below cannot throw: nothing leaks
+        if (hipError_t e = hipMalloc(&q, bytes)) { hip_fail(err, "hipMalloc", e); return false; }
+        ptrs.push_back(q);
+        p = static_cast<T*>(q);
+        const hipError_t e = init ? hipMemcpy(q, init, sizeof(T) * count, hipMemcpyHostToDevice) : hipMemsetAsync(q, 0, bytes, zeroOn);
+        if (e != hipSuccess) { hip_fail(err, init ? "hipMemcpy" : "hipMemsetAsync", e); return false; }
+        return true;
+    }
+    void release(const void* p)
+    {
+        auto it = std::find(ptrs.begin(), ptrs.end(), p);
+        if (it == ptrs.end()) return;
+        (void)hipFree(*it);
+        ptrs.erase(it);
+    }
+};
+
+inline double bnd(const double* p, size_t i, double dflt) { return p ? p[i] : dflt; }
+
+// ---- entry-point bodies of both arms: H is lcqp_hip_batch or lcqp_hip_sparse (device, stream, ev0 .. ev2, mem, ran and the batch
+// struct db with the fields of the same names, DevBatch / SpBatch)
+
+// *_synchronize: the device of the handle current, its stream drained
+template <class H>
+int synchronize(std::string& err, H* h)
+{
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    HIPCHK(err, hipSetDevice(h->device));
+    HIPCHK(err, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// *_set_options.  The per-iterate tracking buffers (options.storeSteps, src/OutputStatistics.cpp:131-164) hold the first `depth` iterates
+// at most; they are kept at the largest trace the handle was asked for (a regrow frees the smaller ones), and the kernels record only
+// while storeSteps is on: traceCap < 0 keeps the buffers of a handle whose tracking has been switched off again.
+template <class H>
+int set_options(std::string& err, H* h, const lcqp_options_t* opt, int depth)
+{
+    if (!h || !opt) return LCQP_INVALID_ARGUMENT;
+    if (opt->nDynamicPenalty > 64) { err = "nDynamicPenalty > 64 unsupported"; return LCQP_HIP_UNSUPPORTED; }
+    auto& d = h->db;
+    const int want = opt->storeSteps ? std::min(std::max(opt->maxIterations + 1, 1), depth) : 0;
+    const int have = d.traceCap < 0 ? -d.traceCap : d.traceCap;
+    if (want > have) {
+        if (int rc = synchronize(err, h)) return rc;
+        h->mem.release(d.traceS); h->mem.release(d.traceX); h->mem.release(d.traceLen);
+        d.traceS = d.traceX = nullptr; d.traceLen = nullptr; d.traceCap = 0;
+        if (!h->mem.alloc(err, d.traceS, (size_t)d.B * want * 8) || !h->mem.alloc(err, d.traceX, (size_t)d.B * want * d.n) ||
+            !h->mem.alloc(err, d.traceLen, (size_t)d.B)) {
+            err = "out of device memory for the iterate trace: " + err;
+            return LCQP_HIP_ERROR;
+        }
+        d.traceCap = want;
+    } else d.traceCap = opt->storeSteps ? have : -have;
+    d.opt = *opt;
+    return 0;
+}
+
+// *_get_trace: the trace of one instance of the last run, at most `cap` iterates
+template <class H>
+int get_trace(std::string& err, H* h, int instance, int cap, double* scalars, double* x, int* len)
+{
+    if (!h || !len) return LCQP_INVALID_ARGUMENT;
+    const auto& d = h->db;
+    *len = 0;
+    if (instance < 0 || instance >= d.B) return LCQP_INVALID_ARGUMENT;
+    if (d.traceCap <= 0) return 0;      // no buffers, or tracking switched off: an empty trace
+    if (int rc = synchronize(err, h)) return rc;
+    int n = 0;
+    HIPCHK(err, hipMemcpy(&n, d.traceLen + instance, sizeof(int), hipMemcpyDeviceToHost));
+    n = std::min(n, std::min(cap, d.traceCap));
+    if (n > 0 && scalars) HIPCHK(err, hipMemcpy(scalars, d.traceS + (size_t)instance * d.traceCap * 8, sizeof(double) * 8 * n, hipMemcpyDeviceToHost));
+    if (n > 0 && x) HIPCHK(err, hipMemcpy(x, d.traceX + (size_t)instance * d.traceCap * d.n, sizeof(double) * (size_t)d.n * n, hipMemcpyDeviceToHost));
+    *len = n;
+    return 0;
+}
+
+// *_last_timing: setup (ev0 -> ev1) and solve (ev1 -> ev2) of the last run
+template <class H>
+int last_timing(std::string& err, H* h, float* setup_ms, float* solve_ms)
+{
+    if (!h || !h->ran) return LCQP_INVALID_ARGUMENT;
+    HIPCHK(err, hipSetDevice(h->device));
+    HIPCHK(err, hipEventSynchronize(h->ev2));
+    if (setup_ms) HIPCHK(err, hipEventElapsedTime(setup_ms, h->ev0, h->ev1));
+    if (solve_ms) HIPCHK(err, hipEventElapsedTime(solve_ms, h->ev1, h->ev2));
+    return 0;
+}
+
+// *_get_solution: x [B][n], y [B][ndual], the statistics [B]
+template <class H>
+int get_solution(std::string& err, H* h, int ndual, double* x, double* y, lcqp_stats_t* stats)
+{
+    if (int rc = synchronize(err, h)) return rc;
+    const auto& d = h->db;
+    if (x) HIPCHK(err, hipMemcpy(x, d.xout, sizeof(double) * (size_t)d.B * d.n, hipMemcpyDeviceToHost));
+    if (y) HIPCHK(err, hipMemcpy(y, d.yout, sizeof(double) * (size_t)d.B * ndual, hipMemcpyDeviceToHost));
+    if (stats) HIPCHK(err, hipMemcpy(stats, d.stats, sizeof(lcqp_stats_t) * (size_t)d.B, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// Row bounds of instance k of a load (setConstraints / setComplementarityBounds, src/LCQProblem.cpp:563-626, 726-785): lE / uE rows
+// [0, nC) from lbA / ubA (default -inf / +inf), rows nC + i and nC + nComp + i from lbL / ubL and lbR / ubR (default 0 / +inf); lo / ro:
+// the lower bounds the phi terms read.  A lower complementarity bound of -inf is refused.
+// A batch may mix instances with and without lbL / lbR: an absent bound vector is the zero vector, and the phi expressions of :969-996
+// with zeros are the arithmetic of an instance loaded without them, bit for bit.  The batch-wide flags only say whether ANY instance
+// carries bounds, i.e. whether the kernels read the (zero-filled) arrays at all; the first load of the handle, or a load starting at
+// instance 0, starts them over (k == 0), the other instances and loads add to them.
+template <class D>
+int pack_row_bounds(D& d, bool loaded, int first, int k, const double* lbA, const double* ubA, const double* lbL, const double* ubL,
+                    const double* lbR, const double* ubR, double* lE, double* uE, double* lo, double* ro)
+{
+    const int nC = d.nC, nComp = d.nComp;
+    const int hasL = lbL ? 1 : 0, hasR = lbR ? 1 : 0;
+    if (k == 0 && (!loaded || first == 0)) { d.hasLbL = hasL; d.hasLbR = hasR; }
+    else { d.hasLbL |= hasL; d.hasLbR |= hasR; }
+    for (int r = 0; r < nC; r++) { lE[r] = bnd(lbA, (size_t)k * nC + r, -INFINITY); uE[r] = bnd(ubA, (size_t)k * nC + r, INFINITY); }
+    for (int i = 0; i < nComp; i++) {
+        const size_t j = (size_t)k * nComp + i;
+        if (bnd(lbL, j, 0.0) <= -INFINITY || bnd(lbR, j, 0.0) <= -INFINITY) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
+        lE[nC + i] = lo[i] = bnd(lbL, j, 0.0);
+        uE[nC + i] = bnd(ubL, j, INFINITY);
+        lE[nC + nComp + i] = ro[i] = bnd(lbR, j, 0.0);
+        uE[nC + nComp + i] = bnd(ubR, j, INFINITY);
+    }
+    return 0;
+}
+
+}  // namespace lcqp_rt

@@ -21,13 +21,14 @@
 #include "lcqp_wg.hpp"
 #include "../../include/lcqp_hip.h"
 #include "lcqp_sparse_pattern.hpp"
+#include "lcqp_host_rt.hpp"
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
-#include <new>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -2153,23 +2154,28 @@ static void sp_launch(const SpBatch& db, hipStream_t stream, hipEvent_t mid)
 // =================================================================================================
 // host side
 // =================================================================================================
+using namespace lcqp_rt;
+
 static thread_local std::string g_sp_err;
 extern "C" const char* lcqp_hip_sparse_last_error(void) { return g_sp_err.c_str(); }
 
+// The members are released in reverse order after the destructor's synchronisation: device memory, events, stream.
 struct lcqp_hip_sparse {
     SpBatch db;
     int device;
-    hipStream_t stream;
-    hipEvent_t ev0, ev1, ev2;
-    std::vector<void*> allocs;
+    Stream stream;
+    Event ev0, ev1, ev2;           // run: setup from ev0 to ev1, homotopy from ev1 to ev2
+    DevMem mem{stream};            // zero-fills on the handle's stream
     std::vector<int> csr2csc;      // value order: E (CSR) entry k comes from entry csr2csc[k] of the caller's CSC arrays
     // the two orderings of the band (lcqp_sparse_pattern.hpp: Pattern::ord): device copies of their maps, the permutation for get_ordering
-    struct Ord { std::vector<int> perm; int *iperm, *bandQ, *bandE, *bsrc, *bgate, *bdiag, *pnode, *Upos; bool rowsFollow; } ord[2];
-    bool hasB;
-    int useB;                      // ordering of the last sp_choose_ordering
+    struct Ord { std::vector<int> perm; int *iperm, *bandQ, *bandE, *bsrc, *bgate, *bdiag, *pnode, *Upos; bool rowsFollow; } ord[2] = {};
+    bool hasB = false;
+    int useB = 0;                  // ordering of the last sp_choose_ordering
     std::vector<int> qdiagHost;    // entry of Q_ii in the value array
     std::vector<double> diagRatio; // per instance: min_i Q_ii / max_i Q_ii of the loaded Hessian (1: not loaded yet)
-    bool loaded, ran;
+    bool loaded = false, ran = false;
+    explicit lcqp_hip_sparse(int dev) : db(), device(dev) {}
+    ~lcqp_hip_sparse() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
 };
 
 // Ordering [1] and the light regularisation of the polish are for batches whose Hessians are safely definite, judged by their diagonals
@@ -2186,21 +2192,6 @@ static void sp_choose_ordering(lcqp_hip_sparse* h)
     h->useB = k;
 }
 
-#define SPCHK(call)                                                                             \
-    do { hipError_t e_ = (call); if (e_ != hipSuccess) { g_sp_err = std::string(#call) + ": " + hipGetErrorString(e_); return LCQP_HIP_ERROR; } } while (0)
-
-template <class T>
-static T* sp_alloc(lcqp_hip_sparse* h, size_t count, const T* init = nullptr)
-{
-    void* p = nullptr;
-    const size_t bytes = (count ? count : 1) * sizeof(T);
-    if (hipMalloc(&p, bytes) != hipSuccess) return nullptr;
-    h->allocs.push_back(p);
-    if (init) { if (hipMemcpy(p, init, count * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return nullptr; }
-    else if (hipMemset(p, 0, bytes) != hipSuccess) return nullptr;
-    return (T*)p;
-}
-
 // the pattern analysis (lcqp_sparse_pattern.hpp), then the device copies of its arrays and the storage of the batch
 extern "C" lcqp_hip_sparse_t* lcqp_hip_sparse_create(int batch, int nV, int nC, int nComp, const int* Qp, const int* Qi, const int* Ap, const int* Ai, int device)
 try {
@@ -2214,14 +2205,12 @@ try {
     const int nU = (int)P.Usrc.size(), nCb = (int)P.Csrc.size();
     const bool general = P.general;
     const lcqp_general::Symbolic& sym = P.sym;
-    if (hipSetDevice(device) != hipSuccess) { g_sp_err = "hipSetDevice failed"; return nullptr; }
-    lcqp_hip_sparse* h = new (std::nothrow) lcqp_hip_sparse();
-    if (!h) return nullptr;
-    struct Guard { lcqp_hip_sparse* h; ~Guard() { if (h) lcqp_hip_sparse_destroy(h); } } guard{h};      // an exception below must not leak the handle
-    h->device = device; h->loaded = false; h->ran = false; h->csr2csc = P.csr2csc; h->hasB = P.hasB; h->useB = 0; h->qdiagHost = P.qdiag; h->diagRatio.assign(batch, 1.0);
-    h->stream = nullptr; h->ev0 = h->ev1 = h->ev2 = nullptr;
+    if (hipError_t e = hipSetDevice(device)) { hip_fail(g_sp_err, "hipSetDevice failed", e); return nullptr; }
+    std::unique_ptr<lcqp_hip_sparse> h(new lcqp_hip_sparse(device));
+    for (hipError_t e : {h->stream.status, h->ev0.status, h->ev1.status, h->ev2.status})
+        if (e != hipSuccess) { hip_fail(g_sp_err, "stream/event creation", e); return nullptr; }
+    h->csr2csc = P.csr2csc; h->hasB = P.hasB; h->qdiagHost = P.qdiag; h->diagRatio.assign(batch, 1.0);
     SpBatch& d = h->db;
-    memset(&d, 0, sizeof(d));
     d.B = batch; d.n = n; d.m = m; d.nC = nC; d.nComp = nComp; d.N = N; d.Np = ((N + 63) / 64) * 64; d.w = w; d.ld = ld; d.nnzQ = nnzQ; d.nnzE = nnzA; d.G = G; d.kb = kb; d.nU = nU; d.nCb = nCb;
     d.general = general ? 1 : 0;
     d.kfStride = general ? (size_t)sym.Lsize : (size_t)d.Np * G;
@@ -2247,44 +2236,44 @@ try {
     }
     const size_t Np = d.Np;
     lcqp_hip_options_default(&d.opt);
-    bool ok = hipStreamCreate(&h->stream) == hipSuccess && hipEventCreate(&h->ev0) == hipSuccess && hipEventCreate(&h->ev1) == hipSuccess &&
-              hipEventCreate(&h->ev2) == hipSuccess;
     const size_t B = batch;
-    ok = ok && (d.Qp = sp_alloc<int>(h, n + 1, Qp)) && (d.Qi = sp_alloc<int>(h, nnzQ, Qi)) && (d.Ep = sp_alloc<int>(h, m + 1, P.Ep.data())) &&
-         (d.Ei = sp_alloc<int>(h, nnzA, P.Ei.data())) && (d.ETp = sp_alloc<int>(h, n + 1, P.ETp.data())) && (d.ETi = sp_alloc<int>(h, nnzA, P.ETi.data())) &&
-         (d.ETmap = sp_alloc<int>(h, nnzA, P.ETmap.data())) &&
-         (d.qdiag = sp_alloc<int>(h, n, P.qdiag.data())) && (d.Erow = sp_alloc<int>(h, nnzA, P.Erow.data()));
+    DevMem& mm = h->mem;
+    std::string& err = g_sp_err;
+    bool ok = mm.alloc(err, d.Qp, n + 1, Qp) && mm.alloc(err, d.Qi, nnzQ, Qi) && mm.alloc(err, d.Ep, m + 1, P.Ep.data()) &&
+         mm.alloc(err, d.Ei, nnzA, P.Ei.data()) && mm.alloc(err, d.ETp, n + 1, P.ETp.data()) && mm.alloc(err, d.ETi, nnzA, P.ETi.data()) &&
+         mm.alloc(err, d.ETmap, nnzA, P.ETmap.data()) &&
+         mm.alloc(err, d.qdiag, n, P.qdiag.data()) && mm.alloc(err, d.Erow, nnzA, P.Erow.data());
     for (int k = 0; k < (P.hasB ? 2 : 1); k++) {
         const lcqp_pattern::Ordering& M = P.ord[k];
         lcqp_hip_sparse::Ord& o = h->ord[k];
-        ok = ok && (o.iperm = sp_alloc<int>(h, N, M.iperm.data())) && (o.bandQ = sp_alloc<int>(h, nnzQ, M.bandQ.data())) &&
-             (o.bandE = sp_alloc<int>(h, nnzA, M.bandE.data())) && (o.bsrc = sp_alloc<int>(h, M.bsrc.size(), M.bsrc.data())) &&
-             (o.bgate = sp_alloc<int>(h, M.bgate.size(), M.bgate.data())) && (o.bdiag = sp_alloc<int>(h, M.bdiag.size(), M.bdiag.data())) &&
-             (o.pnode = sp_alloc<int>(h, N, M.perm.data())) && (o.Upos = sp_alloc<int>(h, nU, M.Upos.data()));
+        ok = ok && mm.alloc(err, o.iperm, N, M.iperm.data()) && mm.alloc(err, o.bandQ, nnzQ, M.bandQ.data()) &&
+             mm.alloc(err, o.bandE, nnzA, M.bandE.data()) && mm.alloc(err, o.bsrc, M.bsrc.size(), M.bsrc.data()) &&
+             mm.alloc(err, o.bgate, M.bgate.size(), M.bgate.data()) && mm.alloc(err, o.bdiag, M.bdiag.size(), M.bdiag.data()) &&
+             mm.alloc(err, o.pnode, N, M.perm.data()) && mm.alloc(err, o.Upos, nU, M.Upos.data());
         o.perm = M.perm; o.rowsFollow = M.rowsFollow;
     }
-    if (ok) sp_choose_ordering(h);
+    if (ok) sp_choose_ordering(h.get());
     if (kb > 0)
-        ok = ok && (d.bnode = sp_alloc<int>(h, kb, P.border.data())) && (d.Uptr = sp_alloc<int>(h, kb + 1, P.Uptr.data())) &&
-             (d.Usrc = sp_alloc<int>(h, nU, P.Usrc.data())) && (d.Ugate = sp_alloc<int>(h, nU, P.Ugate.data())) && (d.Cptr = sp_alloc<int>(h, kb + 1, P.Cptr.data())) &&
-             (d.Cb2 = sp_alloc<int>(h, nCb, P.Cb2.data())) && (d.Csrc = sp_alloc<int>(h, nCb, P.Csrc.data())) && (d.Cgate = sp_alloc<int>(h, nCb, P.Cgate.data())) &&
-             (d.bW = sp_alloc<double>(h, (size_t)batch * 2 * kb * d.Np)) && (d.bUv = sp_alloc<double>(h, (size_t)batch * 2 * nU)) &&
-             (d.bS = sp_alloc<double>(h, (size_t)batch * 2 * kb * kb));
+        ok = ok && mm.alloc(err, d.bnode, kb, P.border.data()) && mm.alloc(err, d.Uptr, kb + 1, P.Uptr.data()) &&
+             mm.alloc(err, d.Usrc, nU, P.Usrc.data()) && mm.alloc(err, d.Ugate, nU, P.Ugate.data()) && mm.alloc(err, d.Cptr, kb + 1, P.Cptr.data()) &&
+             mm.alloc(err, d.Cb2, nCb, P.Cb2.data()) && mm.alloc(err, d.Csrc, nCb, P.Csrc.data()) && mm.alloc(err, d.Cgate, nCb, P.Cgate.data()) &&
+             mm.alloc(err, d.bW, (size_t)batch * 2 * kb * d.Np) && mm.alloc(err, d.bUv, (size_t)batch * 2 * nU) &&
+             mm.alloc(err, d.bS, (size_t)batch * 2 * kb * kb);
     // ELL slabs of the three gathers (g_ell): rows of Q, rows of E, columns of E
     auto ell = [&](EllMat& e, const lcqp_pattern::Ell& s, int rows, const int* dptr, const int* didx, const int* dmap) {
         e.rows = rows; e.W = s.W; e.tails = s.tails; e.ptr = dptr; e.cidx = didx; e.cmap = dmap; e.epos = nullptr;
-        return (e.eidx = sp_alloc<int>(h, s.eidx.size(), s.eidx.data())) && (s.epos.empty() || (e.epos = sp_alloc<int>(h, s.epos.size(), s.epos.data())));
+        return mm.alloc(err, e.eidx, s.eidx.size(), s.eidx.data()) && (s.epos.empty() || mm.alloc(err, e.epos, s.epos.size(), s.epos.data()));
     };
     ok = ok && ell(d.ellQ, P.ellQ, n, d.Qp, d.Qi, nullptr) && ell(d.ellE, P.ellE, m, d.Ep, d.Ei, nullptr) && ell(d.ellT, P.ellT, n, d.ETp, d.ETi, d.ETmap);
-    ok = ok && (d.Qx = sp_alloc<double>(h, B * nnzQ)) && (d.Ex = sp_alloc<double>(h, B * nnzA)) &&
-         (d.Kb = sp_alloc<double>(h, (G > 16 && !general) ? B * N * ld : 0)) &&      // the band array is only written by the LDS-window factorisation
-         (d.KaF = sp_alloc<double>(h, B * d.kfStride)) && (d.KaD = sp_alloc<double>(h, B * Np)) &&
-         (d.KpF = sp_alloc<double>(h, B * d.kfStride)) && (d.KpD = sp_alloc<double>(h, B * Np)) &&
-         (d.K0 = sp_alloc<double>(h, G <= 16 ? B * Np * G : 0)) &&
-         (d.nv = sp_alloc<double>(h, B * NV_NUM * n)) && (d.mv = sp_alloc<double>(h, B * MV_NUM * m)) && (d.Nv = sp_alloc<double>(h, B * 2 * Np)) &&
-         (d.lbL = sp_alloc<double>(h, B * nComp)) && (d.lbR = sp_alloc<double>(h, B * nComp)) && (d.mi = sp_alloc<int>(h, B * MI_NUM * m)) &&
-         (d.info = sp_alloc<SpInfo>(h, B)) && (d.stats = sp_alloc<lcqp_stats_t>(h, B)) && (d.xout = sp_alloc<double>(h, B * n)) &&
-         (d.yout = sp_alloc<double>(h, B * m));
+    ok = ok && mm.alloc(err, d.Qx, B * nnzQ) && mm.alloc(err, d.Ex, B * nnzA) &&
+         mm.alloc(err, d.Kb, (G > 16 && !general) ? B * N * ld : 0) &&      // the band array is only written by the LDS-window factorisation
+         mm.alloc(err, d.KaF, B * d.kfStride) && mm.alloc(err, d.KaD, B * Np) &&
+         mm.alloc(err, d.KpF, B * d.kfStride) && mm.alloc(err, d.KpD, B * Np) &&
+         mm.alloc(err, d.K0, G <= 16 ? B * Np * G : 0) &&
+         mm.alloc(err, d.nv, B * NV_NUM * n) && mm.alloc(err, d.mv, B * MV_NUM * m) && mm.alloc(err, d.Nv, B * 2 * Np) &&
+         mm.alloc(err, d.lbL, B * nComp) && mm.alloc(err, d.lbR, B * nComp) && mm.alloc(err, d.mi, B * MI_NUM * m) &&
+         mm.alloc(err, d.info, B) && mm.alloc(err, d.stats, B) && mm.alloc(err, d.xout, B * n) &&
+         mm.alloc(err, d.yout, B * m);
     if (general) {
         std::vector<unsigned> lo(sym.Loff.begin(), sym.Loff.end()), co(sym.CBoff.begin(), sym.CBoff.end());
         std::vector<int> meta((size_t)sym.nF * GEN_META, 0), cinfo(std::max<size_t>(sym.child.size(), 1) * 4, 0);
@@ -2294,17 +2283,17 @@ try {
             mt[6] = sym.childPtr[f]; mt[7] = sym.childPtr[f + 1]; mt[8] = (int)sym.Loff[f]; mt[9] = (int)sym.CBoff[f];
         }
         for (size_t ci = 0; ci < sym.child.size(); ci++) { const int ch = sym.child[ci]; cinfo[4 * ci] = sym.nb[ch]; cinfo[4 * ci + 1] = (int)sym.CBoff[ch]; cinfo[4 * ci + 2] = sym.rowPtr[ch]; }
-        ok = ok && (d.gPiv0 = sp_alloc<int>(h, sym.piv0.size(), sym.piv0.data())) && (d.gNp = sp_alloc<int>(h, sym.np.size(), sym.np.data())) &&
-             (d.gNb = sp_alloc<int>(h, sym.nb.size(), sym.nb.data())) && (d.gRowPtr = sp_alloc<int>(h, sym.rowPtr.size(), sym.rowPtr.data())) &&
-             (d.gRows = sp_alloc<int>(h, std::max<size_t>(sym.rows.size(), 1), sym.rows.empty() ? nullptr : sym.rows.data())) &&
-             (d.gChildPtr = sp_alloc<int>(h, sym.childPtr.size(), sym.childPtr.data())) &&
-             (d.gChild = sp_alloc<int>(h, std::max<size_t>(sym.child.size(), 1), sym.child.empty() ? nullptr : sym.child.data())) &&
-             (d.gRel = sp_alloc<int>(h, std::max<size_t>(sym.rel.size(), 1), sym.rel.empty() ? nullptr : sym.rel.data())) &&
-             (d.gAsmPtr = sp_alloc<int>(h, sym.asmPtr.size(), sym.asmPtr.data())) && (d.gAsmSrc = sp_alloc<int>(h, sym.asmSrc.size(), sym.asmSrc.data())) &&
-             (d.gAsmGate = sp_alloc<int>(h, sym.asmGate.size(), sym.asmGate.data())) && (d.gAsmPos = sp_alloc<int>(h, sym.asmPos.size(), sym.asmPos.data())) &&
-             (d.gLoff = sp_alloc<unsigned>(h, lo.size(), lo.data())) && (d.gCBoff = sp_alloc<unsigned>(h, co.size(), co.data())) &&
-             (d.gMeta = sp_alloc<int>(h, meta.size(), meta.data())) && (d.gChildInfo = sp_alloc<int>(h, cinfo.size(), cinfo.data())) &&
-             (d.gStack = sp_alloc<double>(h, B * d.gStackSize)) && (d.gFront = sp_alloc<double>(h, B * (size_t)d.gMaxFront * d.gMaxFront));
+        ok = ok && mm.alloc(err, d.gPiv0, sym.piv0.size(), sym.piv0.data()) && mm.alloc(err, d.gNp, sym.np.size(), sym.np.data()) &&
+             mm.alloc(err, d.gNb, sym.nb.size(), sym.nb.data()) && mm.alloc(err, d.gRowPtr, sym.rowPtr.size(), sym.rowPtr.data()) &&
+             mm.alloc(err, d.gRows, std::max<size_t>(sym.rows.size(), 1), sym.rows.empty() ? nullptr : sym.rows.data()) &&
+             mm.alloc(err, d.gChildPtr, sym.childPtr.size(), sym.childPtr.data()) &&
+             mm.alloc(err, d.gChild, std::max<size_t>(sym.child.size(), 1), sym.child.empty() ? nullptr : sym.child.data()) &&
+             mm.alloc(err, d.gRel, std::max<size_t>(sym.rel.size(), 1), sym.rel.empty() ? nullptr : sym.rel.data()) &&
+             mm.alloc(err, d.gAsmPtr, sym.asmPtr.size(), sym.asmPtr.data()) && mm.alloc(err, d.gAsmSrc, sym.asmSrc.size(), sym.asmSrc.data()) &&
+             mm.alloc(err, d.gAsmGate, sym.asmGate.size(), sym.asmGate.data()) && mm.alloc(err, d.gAsmPos, sym.asmPos.size(), sym.asmPos.data()) &&
+             mm.alloc(err, d.gLoff, lo.size(), lo.data()) && mm.alloc(err, d.gCBoff, co.size(), co.data()) &&
+             mm.alloc(err, d.gMeta, meta.size(), meta.data()) && mm.alloc(err, d.gChildInfo, cinfo.size(), cinfo.data()) &&
+             mm.alloc(err, d.gStack, B * d.gStackSize) && mm.alloc(err, d.gFront, B * (size_t)d.gMaxFront * d.gMaxFront);
     }
     {
         // pools of the phase machine (k_sparse_sched): the largest power of two of instances whose per-instance arrays all stay below 4 GiB
@@ -2317,26 +2306,18 @@ try {
         while ((size_t)(2 * pool) * perInst < ((size_t)1 << 32) && pool < batch) pool *= 2;
         if (const char* e = std::getenv("LCQP_SPARSE_POOL")) { const int v = std::atoi(e); if (v >= 1 && v < pool && (v & (v - 1)) == 0) pool = v; }      // test hook: several small pools
         d.poolSize = pool; d.nPools = (batch + pool - 1) / pool;
-        ok = ok && (d.state = sp_alloc<SpState>(h, B)) && (d.qring = sp_alloc<unsigned long long>(h, (size_t)d.nPools * PH_NUM * pool)) &&
-             (d.qctl = sp_alloc<int>(h, (size_t)d.nPools * (PH_NUM + 1) * QCTL)) && (d.qprof = sp_alloc<unsigned long long>(h, (PH_NUM + 1) * 3));
+        ok = ok && mm.alloc(err, d.state, B) && mm.alloc(err, d.qring, (size_t)d.nPools * PH_NUM * pool) &&
+             mm.alloc(err, d.qctl, (size_t)d.nPools * (PH_NUM + 1) * QCTL) && mm.alloc(err, d.qprof, (PH_NUM + 1) * 3);
     }
-    if (!ok) { g_sp_err = "device allocation failed"; return nullptr; }      // (the guard destroys the handle)
-    guard.h = nullptr;
-    return h;
+    if (!ok) { g_sp_err = "device allocation failed: " + g_sp_err; return nullptr; }
+    if (hipError_t e = hipStreamSynchronize(h->stream)) { hip_fail(g_sp_err, "hipStreamSynchronize(h->stream)", e); return nullptr; }      // the zero-fills
+    return h.release();
 }
 catch (...) { g_sp_err = "out of host memory"; return nullptr; }
 
 extern "C" void lcqp_hip_sparse_destroy(lcqp_hip_sparse_t* h)
 try {
-    if (!h) return;
-    (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void* p : h->allocs) (void)hipFree(p);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->ev2) (void)hipEventDestroy(h->ev2);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    delete h;      // ~lcqp_hip_sparse: set the device, synchronise, then the members
 }
 catch (...) { }
 
@@ -2352,50 +2333,19 @@ extern "C" int lcqp_hip_sparse_get_ordering(const lcqp_hip_sparse_t* h, int* per
     return 0;
 }
 
+// storeSteps: the first 4096 iterates
 extern "C" int lcqp_hip_sparse_set_options(lcqp_hip_sparse_t* h, const lcqp_options_t* opt)
-{
-    if (!h || !opt) return LCQP_INVALID_ARGUMENT;
-    if (opt->nDynamicPenalty > 64) { g_sp_err = "nDynamicPenalty > 64 unsupported"; return LCQP_HIP_UNSUPPORTED; }
-    h->db.opt = *opt;
-    // per-iterate tracking buffers: kept at the largest trace this handle was asked for (a regrow frees the smaller ones); the kernel records
-    // only while storeSteps is on -- traceCap < 0 keeps the buffers of a handle whose tracking has been switched off again
-    SpBatch& d = h->db;
-    const int want = opt->storeSteps ? std::min(std::max(opt->maxIterations + 1, 1), 4096) : 0;
-    const int have = d.traceCap < 0 ? -d.traceCap : d.traceCap;
-    if (want > have) {
-        if (hipSetDevice(h->device) != hipSuccess) { g_sp_err = "hipSetDevice failed"; return LCQP_HIP_ERROR; }
-        (void)hipStreamSynchronize(h->stream);
-        for (void* old : {(void*)d.traceS, (void*)d.traceX, (void*)d.traceLen})
-            if (old) { (void)hipFree(old); h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), old), h->allocs.end()); }
-        d.traceS = d.traceX = nullptr; d.traceLen = nullptr; d.traceCap = 0;
-        double *ts = sp_alloc<double>(h, (size_t)d.B * want * 8), *tx = sp_alloc<double>(h, (size_t)d.B * want * d.n);
-        int* tl = sp_alloc<int>(h, (size_t)d.B);
-        if (!ts || !tx || !tl) { g_sp_err = "out of device memory for the iterate trace"; return LCQP_HIP_ERROR; }
-        d.traceS = ts; d.traceX = tx; d.traceLen = tl; d.traceCap = want;
-    } else d.traceCap = opt->storeSteps ? have : -have;
-    return 0;
+try {
+    return set_options(g_sp_err, h, opt, 4096);
 }
+catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 
 /* per-iterate trace of one instance of the last run (needs options.storeSteps), as lcqp_hip_batch_get_trace */
 extern "C" int lcqp_hip_sparse_get_trace(lcqp_hip_sparse_t* h, int instance, int cap, double* scalars, double* x, int* len)
-{
-    if (!h || !len) return LCQP_INVALID_ARGUMENT;
-    SpBatch& d = h->db;
-    *len = 0;
-    if (instance < 0 || instance >= d.B) return LCQP_INVALID_ARGUMENT;
-    if (d.traceCap <= 0) return 0;      // no buffers, or tracking switched off: an empty trace
-    SPCHK(hipSetDevice(h->device));
-    SPCHK(hipStreamSynchronize(h->stream));
-    int n = 0;
-    SPCHK(hipMemcpy(&n, d.traceLen + instance, sizeof(int), hipMemcpyDeviceToHost));
-    n = std::min(n, std::min(cap, d.traceCap));
-    if (n > 0 && scalars) SPCHK(hipMemcpy(scalars, d.traceS + (size_t)instance * d.traceCap * 8, sizeof(double) * 8 * n, hipMemcpyDeviceToHost));
-    if (n > 0 && x) SPCHK(hipMemcpy(x, d.traceX + (size_t)instance * d.traceCap * d.n, sizeof(double) * (size_t)d.n * n, hipMemcpyDeviceToHost));
-    *len = n;
-    return 0;
+try {
+    return get_trace(g_sp_err, h, instance, cap, scalars, x, len);
 }
-
-static inline double spb(const double* p, size_t i, double dflt) { return p ? p[i] : dflt; }
+catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 
 // LCQProblem::loadLCQP (sparse overload, src/LCQProblem.cpp:390-441) for instances [first, first + count): values only -- the
 // pattern was given to lcqp_hip_sparse_create.  Qx: [count][nnzQ]; Ax: [count][nnzA] in the CSC order of the stacked [A; L; R].
@@ -2405,41 +2355,30 @@ extern "C" int lcqp_hip_sparse_load(lcqp_hip_sparse_t* h, int first, int count, 
 try {
     if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
     SpBatch& d = h->db;
-    const int n = d.n, m = d.m, nC = d.nC, nK = d.nComp;
+    const int n = d.n, m = d.m, nK = d.nComp;
     if (first < 0 || count <= 0 || first + count > d.B || !Qx || !Ax) return LCQP_INVALID_ARGUMENT;
     if (!g) return LCQP_INVALID_OBJECTIVE_LINEAR_TERM;
-    SPCHK(hipSetDevice(h->device));
-    const int hasL = lbL ? 1 : 0, hasR = lbR ? 1 : 0;
-    // instances with and without lbL / lbR may share a batch: an absent vector is the zero vector, the same arithmetic (lcqp_hip_batch_load)
-    if (!h->loaded || first == 0) { d.hasLbL = hasL; d.hasLbR = hasR; }
-    else { d.hasLbL |= hasL; d.hasLbR |= hasR; }
+    HIPCHK(g_sp_err, hipSetDevice(h->device));
     std::vector<double> ex(d.nnzE), nvb((size_t)NV_NUM * n), mvb((size_t)MV_NUM * m), lb(nK), rb(nK);
     for (int k = 0; k < count; k++) {
         const size_t b = (size_t)first + k;
         for (int e = 0; e < d.nnzE; e++) ex[e] = Ax[(size_t)k * d.nnzE + h->csr2csc[e]];
         std::fill(nvb.begin(), nvb.end(), 0.0); std::fill(mvb.begin(), mvb.end(), 0.0);
         for (int i = 0; i < n; i++) { nvb[(size_t)NV_G * n + i] = g[(size_t)k * n + i]; nvb[(size_t)NV_X0 * n + i] = x0 ? x0[(size_t)k * n + i] : 0.0; }
-        double *lE = &mvb[(size_t)MV_L * m], *uE = &mvb[(size_t)MV_U * m];
-        for (int r = 0; r < nC; r++) { lE[r] = spb(lbA, (size_t)k * nC + r, -INFINITY); uE[r] = spb(ubA, (size_t)k * nC + r, INFINITY); }
-        for (int i = 0; i < nK; i++) {
-            if (lbL && lbL[(size_t)k * nK + i] <= -INFINITY) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
-            if (lbR && lbR[(size_t)k * nK + i] <= -INFINITY) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
-            lE[nC + i] = spb(lbL, (size_t)k * nK + i, 0.0); uE[nC + i] = spb(ubL, (size_t)k * nK + i, INFINITY);
-            lE[nC + nK + i] = spb(lbR, (size_t)k * nK + i, 0.0); uE[nC + nK + i] = spb(ubR, (size_t)k * nK + i, INFINITY);
-            lb[i] = spb(lbL, (size_t)k * nK + i, 0.0); rb[i] = spb(lbR, (size_t)k * nK + i, 0.0);
-        }
+        const int rc = pack_row_bounds(d, h->loaded, first, k, lbA, ubA, lbL, ubL, lbR, ubR, &mvb[(size_t)MV_L * m], &mvb[(size_t)MV_U * m], lb.data(), rb.data());
+        if (rc) return rc;
         if (y0) for (int r = 0; r < m; r++) mvb[(size_t)MV_Y0 * m + r] = y0[(size_t)k * m + r];
         SpInfo info; memset(&info, 0, sizeof(info)); info.hasY0 = y0 ? 1 : 0;
         double dmin = INFINITY, dmax = 0.0;
         for (int i = 0; i < n; i++) { const double q = h->qdiagHost[i] >= 0 ? Qx[(size_t)k * d.nnzQ + h->qdiagHost[i]] : 0.0; dmin = std::min(dmin, q); dmax = std::max(dmax, std::fabs(q)); }
         h->diagRatio[b] = (dmax > 0.0 && dmin > 0.0) ? dmin / dmax : 0.0;
-        SPCHK(hipMemcpy(d.Qx + b * d.nnzQ, Qx + (size_t)k * d.nnzQ, sizeof(double) * d.nnzQ, hipMemcpyHostToDevice));
-        SPCHK(hipMemcpy(d.Ex + b * d.nnzE, ex.data(), sizeof(double) * d.nnzE, hipMemcpyHostToDevice));
-        SPCHK(hipMemcpy(d.nv + b * NV_NUM * n, nvb.data(), sizeof(double) * nvb.size(), hipMemcpyHostToDevice));
-        SPCHK(hipMemcpy(d.mv + b * MV_NUM * m, mvb.data(), sizeof(double) * mvb.size(), hipMemcpyHostToDevice));
-        SPCHK(hipMemcpy(d.lbL + b * nK, lb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
-        SPCHK(hipMemcpy(d.lbR + b * nK, rb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
-        SPCHK(hipMemcpy(d.info + b, &info, sizeof(info), hipMemcpyHostToDevice));
+        HIPCHK(g_sp_err, hipMemcpy(d.Qx + b * d.nnzQ, Qx + (size_t)k * d.nnzQ, sizeof(double) * d.nnzQ, hipMemcpyHostToDevice));
+        HIPCHK(g_sp_err, hipMemcpy(d.Ex + b * d.nnzE, ex.data(), sizeof(double) * d.nnzE, hipMemcpyHostToDevice));
+        HIPCHK(g_sp_err, hipMemcpy(d.nv + b * NV_NUM * n, nvb.data(), sizeof(double) * nvb.size(), hipMemcpyHostToDevice));
+        HIPCHK(g_sp_err, hipMemcpy(d.mv + b * MV_NUM * m, mvb.data(), sizeof(double) * mvb.size(), hipMemcpyHostToDevice));
+        HIPCHK(g_sp_err, hipMemcpy(d.lbL + b * nK, lb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
+        HIPCHK(g_sp_err, hipMemcpy(d.lbR + b * nK, rb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
+        HIPCHK(g_sp_err, hipMemcpy(d.info + b, &info, sizeof(info), hipMemcpyHostToDevice));
     }
     h->loaded = true;
     sp_choose_ordering(h);
@@ -2450,62 +2389,50 @@ catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 /* -DLCQP_SCHED_PROFILE builds: per phase (rows 0 .. PH_NUM-1: start, round, trial, factor, correct, qp end; row PH_NUM: polls without work) the clock
  * ticks (100 MHz), wavefront steps and instances served, summed over the wavefronts of all runs since the handle was created: 3 (PH_NUM + 1) values */
 extern "C" int lcqp_hip_sparse_sched_profile(lcqp_hip_sparse_t* h, unsigned long long* out)
-{
+try {
     if (!h || !out) return LCQP_INVALID_ARGUMENT;
-    SPCHK(hipSetDevice(h->device));
-    SPCHK(hipStreamSynchronize(h->stream));
-    SPCHK(hipMemcpy(out, h->db.qprof, sizeof(unsigned long long) * 3 * (PH_NUM + 1), hipMemcpyDeviceToHost));
+    if (int rc = synchronize(g_sp_err, h)) return rc;
+    HIPCHK(g_sp_err, hipMemcpy(out, h->db.qprof, sizeof(unsigned long long) * 3 * (PH_NUM + 1), hipMemcpyDeviceToHost));
     return 0;
 }
+catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 
 extern "C" int lcqp_hip_sparse_run(lcqp_hip_sparse_t* h)
 try {
     if (!h || !h->loaded) return LCQP_LCQPOBJECT_NOT_SETUP;
-    SPCHK(hipSetDevice(h->device));
+    HIPCHK(g_sp_err, hipSetDevice(h->device));
     sp_choose_ordering(h);
-    SPCHK(hipEventRecord(h->ev0, h->stream));
+    HIPCHK(g_sp_err, hipEventRecord(h->ev0, h->stream));
     switch (h->db.G) {
         case 8: sp_launch<8>(h->db, h->stream, h->ev1); break;
         case 16: sp_launch<16>(h->db, h->stream, h->ev1); break;
         case 32: sp_launch<32>(h->db, h->stream, h->ev1); break;
         default: sp_launch<64>(h->db, h->stream, h->ev1); break;
     }
-    SPCHK(hipGetLastError());
-    SPCHK(hipEventRecord(h->ev2, h->stream));
+    HIPCHK(g_sp_err, hipGetLastError());
+    HIPCHK(g_sp_err, hipEventRecord(h->ev2, h->stream));
     h->ran = true;
     return 0;
 }
 catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 
 extern "C" int lcqp_hip_sparse_synchronize(lcqp_hip_sparse_t* h)
-{
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    SPCHK(hipSetDevice(h->device));
-    SPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+try {
+    return synchronize(g_sp_err, h);
 }
+catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 
 extern "C" int lcqp_hip_sparse_last_timing(lcqp_hip_sparse_t* h, float* setup_ms, float* solve_ms)
-{
-    if (!h || !h->ran) return LCQP_INVALID_ARGUMENT;
-    SPCHK(hipSetDevice(h->device));
-    SPCHK(hipEventSynchronize(h->ev2));
-    if (setup_ms) SPCHK(hipEventElapsedTime(setup_ms, h->ev0, h->ev1));
-    if (solve_ms) SPCHK(hipEventElapsedTime(solve_ms, h->ev1, h->ev2));
-    return 0;
+try {
+    return last_timing(g_sp_err, h, setup_ms, solve_ms);
 }
+catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 
 extern "C" int lcqp_hip_sparse_get_solution(lcqp_hip_sparse_t* h, double* x, double* y, lcqp_stats_t* stats)
-{
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    SPCHK(hipSetDevice(h->device));
-    SpBatch& d = h->db;
-    SPCHK(hipStreamSynchronize(h->stream));
-    if (x) SPCHK(hipMemcpy(x, d.xout, sizeof(double) * (size_t)d.B * d.n, hipMemcpyDeviceToHost));
-    if (y) SPCHK(hipMemcpy(y, d.yout, sizeof(double) * (size_t)d.B * d.m, hipMemcpyDeviceToHost));
-    if (stats) SPCHK(hipMemcpy(stats, d.stats, sizeof(lcqp_stats_t) * (size_t)d.B, hipMemcpyDeviceToHost));
-    return 0;
+try {
+    return get_solution(g_sp_err, h, h ? h->db.m : 0, x, y, stats);
 }
+catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 
 // -DLCQP_PROFILE builds (tools/gpu.py sparse_profile): mean clock ticks per instance and phase of the last run
 // (products, assembly, factorisation, forward sweeps, backward sweeps, vector operations, LCQP level, -)
@@ -2514,10 +2441,9 @@ try {
 #ifdef LCQP_PROFILE
     if (!h || !out) return LCQP_INVALID_ARGUMENT;
     SpBatch& d = h->db;
-    SPCHK(hipSetDevice(h->device));
-    SPCHK(hipStreamSynchronize(h->stream));
+    if (int rc = synchronize(g_sp_err, h)) return rc;
     std::vector<SpInfo> info(d.B);
-    SPCHK(hipMemcpy(info.data(), d.info, sizeof(SpInfo) * (size_t)d.B, hipMemcpyDeviceToHost));
+    HIPCHK(g_sp_err, hipMemcpy(info.data(), d.info, sizeof(SpInfo) * (size_t)d.B, hipMemcpyDeviceToHost));
     for (int k = 0; k < 8; k++) { out[k] = 0.0; for (auto& i : info) out[k] += i.prof[k] / d.B; }
     return 0;
 #else
@@ -2525,7 +2451,7 @@ try {
     return LCQP_HIP_UNSUPPORTED;
 #endif
 }
-catch (...) { return LCQP_HIP_ERROR; }
+catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 
 // algorithmic bytes of the last run (setup + homotopy), counted by the kernels: CSR values and indices of every sparse product,
 // band storage read and written by every assembly, factorisation and solve

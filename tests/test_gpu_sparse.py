@@ -444,3 +444,42 @@ def test_sparse_banded_pattern_with_coupling_rows(hip, oracle, n, nC, nK, extra)
         assert np.abs(x[b] - ro["x"]).max() < 1e-9 and np.abs(y[b] - ro["y"]).max() < 1e-7
         assert abs(st[b]["iterTotal"] - ro["stats"]["iterTotal"]) <= 4
     sb.close()
+
+
+def test_handles_return_their_device_memory(hip):
+    """Ten create / load / run / destroy cycles of a dense and a sparse batch, each with storeSteps on and two rising maxIterations, so
+    that the iterate-trace buffers grow inside every handle: the device memory they take is all given back.  Free device memory is
+    read after the first cycle (the runtime keeps some of what it has once mapped) and must not drift from it by more than 16 MiB:
+    one cycle takes about 100 MiB, the trace buffers of one handle 5 to 20 MiB."""
+    import ctypes
+    mem_get_info = hip.lib().hipMemGetInfo      # from the HIP runtime the library itself runs on (a dependency of liblcqpow_hip.so)
+
+    def free_bytes():
+        f, t = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        assert mem_get_info(ctypes.byref(f), ctypes.byref(t)) == 0
+        return f.value
+    n, nC, nK, B = 512, 256, 64, 64
+    Qp, Ap = P.sparse_pattern(n, nC, nK)
+    inst = [P.sparse_instance(i, n, nC, nK) for i in range(B)]
+    Qx, g, Ax = np.stack([d["Q"].data for d in inst]), np.stack([d["g"] for d in inst]), np.stack([d["E"].data for d in inst])
+    lbA, ubA = np.stack([d["lbA"] for d in inst]), np.stack([d["ubA"] for d in inst])
+    free = []
+    for cycle in range(10):
+        its = 40 + 10 * cycle
+        bt = hip.BatchLCQP(16, 256, 64, 32, opt=hip.default_options(perturbStep=0, storeSteps=1, maxIterations=its))
+        bt.generate_synthetic(0)
+        bt.run()
+        bt.set_options(hip.default_options(perturbStep=0, storeSteps=1, maxIterations=2 * its))
+        bt.run()
+        assert len(bt.trace(0)[0]) >= 1
+        bt.close()
+        sb = hip.SparseBatchLCQP(B, n, nC, nK, Qp, Ap, opt=hip.default_options(perturbStep=0, printLevel=0, storeSteps=1, maxIterations=its))
+        assert sb.load(0, B, Qx, g, Ax, lbA=lbA, ubA=ubA) == 0
+        sb.run()
+        sb.set_options(hip.default_options(perturbStep=0, printLevel=0, storeSteps=1, maxIterations=2 * its))
+        sb.run()
+        assert len(sb.trace(0)[0]) >= 1
+        sb.close()
+        free.append(free_bytes())
+    drift = max(abs(f - free[0]) for f in free[1:])
+    assert drift <= 16 << 20, (drift, free)
