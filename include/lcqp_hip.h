@@ -108,6 +108,11 @@ int  lcqp_hip_qp_solve(lcqp_hip_qp_t* qp, int initialSolve, int* iterations, int
  * x[nV], y[nV + nC]: box duals first, then one dual per stacked row; Qx + g - A'y_A - y_box = 0. */
 void lcqp_hip_qp_get_solution(lcqp_hip_qp_t* qp, double* x, double* y);
 void lcqp_hip_qp_get_counters(lcqp_hip_qp_t* qp, int* admm, int* trials, int* factorizations, int* corrections);
+/* test and diagnostic entry points: lcqp_hip_batch_read_setup / lcqp_hip_batch_read_working_set (below) for the batch of one this object
+ * holds; LCQP_LCQPOBJECT_NOT_SETUP before its first solve */
+int  lcqp_hip_qp_read_setup(lcqp_hip_qp_t* qp, int dims[9], double scal[2], double* C, double* F1, double* D1, double* Et, double* MM,
+                            int* Cp, int* Ci, double* Cv);
+int  lcqp_hip_qp_read_working_set(lcqp_hip_qp_t* qp, int dims[2], int* slot_row, int* crow, int* row_slot, double* Ti);
 
 /* ------------------------------------------------------------------------------------------------
  * Batch of B independent dense LCQPs of one shape (nV, nC, nComp).
@@ -132,6 +137,18 @@ int  lcqp_hip_batch_generate_synthetic(lcqp_hip_batch_t* b, uint64_t seed0, uint
 /* read one instance's problem data back (any pointer may be NULL) -- used by parity tests / cpu_baseline */
 int  lcqp_hip_batch_read_problem(lcqp_hip_batch_t* b, int instance, double* Q, double* g, double* L, double* R,
                                  double* A, double* lbA, double* ubA);
+/* Test and diagnostic entry points: the raw, padded device blocks of one instance after lcqp_hip_batch_setup / lcqp_hip_batch_run
+ * (both streams of the batch are synchronised first; any pointer may be NULL -- call once with buffers NULL to learn the sizes).
+ * dims[9] = np, nblk, mEcap, mMld, capS, capC, the instance's mE, cNnz (-1: C is not compressed), setupFail; scal[2] = spv (the shift
+ * sigma_p of L1 = chol(Q + spv I)), scale (max |Q_ii|).  C [np][np]; F1 [np][np]: the symmetric-filled factor (L1 below and L1' above
+ * outside the diagonal 64 x 64 blocks, inv(L1_JJ) symmetric-filled inside them); D1 [nblk][64][64]: inv(L1_JJ), dense lower;
+ * Et [mEcap][np] = E L1^-T; MM [mMld][mMld]: M = Et Et', lower triangle; Cp [np + 1], Ci [capC], Cv [capC]: the compressed rows of C. */
+int  lcqp_hip_batch_read_setup(lcqp_hip_batch_t* b, int instance, int dims[9], double scal[2], double* C, double* F1, double* D1,
+                               double* Et, double* MM, int* Cp, int* Ci, double* Cv);
+/* The inverse factor Ti of the working-set matrix as the last lcqp_hip_batch_run left it (Ti'Ti = inv(Et_W Et_W')):
+ * dims[2] = nT (rows of Ti), ns (slots in use, free ones inside included); slot_row [capS] (row of E held by a slot, -1: free),
+ * crow [capS] (the row of Ti appended together with the slot), row_slot [mE] (-1: not in the factor), Ti [capS][capS]. */
+int  lcqp_hip_batch_read_working_set(lcqp_hip_batch_t* b, int instance, int dims[2], int* slot_row, int* crow, int* row_slot, double* Ti);
 /* Constant-matrix setup: C = L'R + R'L (src/LCQProblem.cpp:622-623), phi expressions (:969-996) and the
  * two factorisations the subsolver reuses across every iterate (replaces qp.init's setup,
  * src/SubsolverQPOASES.cpp:152).  Asynchronous on the batch stream. */
@@ -172,7 +189,10 @@ int    lcqp_hip_batch_work_sums(lcqp_hip_batch_t* b, double out[6]);
 
 /* ------------------------------------------------------------------------------------------------
  * Building blocks exposed for parity tests and micro-benchmarks (each is one kernel launch over a
- * batch of independent instances; host pointers, synchronous).
+ * batch of independent instances; host pointers, synchronous).  Two more test and diagnostic entry points sit with the objects they
+ * read: lcqp_hip_batch_read_setup / lcqp_hip_batch_read_working_set (and lcqp_hip_qp_read_setup / lcqp_hip_qp_read_working_set) copy the
+ * constant matrices of the setup kernels and the inverse factor of the working-set matrix back as they lie on the device
+ * (tests/test_gpu_setup.py); they launch nothing.
  * ---------------------------------------------------------------------------------------------- */
 /* Utilities::AffineLinearTransformation for symmetric A, src/Utilities.cpp:176-186: d = alpha*A*b + c */
 int lcqp_hip_util_symv(int batch, int n, double alpha, const double* A, const double* b, const double* c, double* d);

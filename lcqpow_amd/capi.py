@@ -99,6 +99,11 @@ def lib():
         L.lcqp_hip_batch_algorithmic_bytes.restype = C.c_double
         L.lcqp_hip_batch_algorithmic_bytes.argtypes = [C.c_void_p]
         L.lcqp_hip_batch_work_sums.argtypes = [C.c_void_p, c_double_p]
+        c_int_p = C.POINTER(C.c_int)
+        L.lcqp_hip_batch_read_setup.argtypes = [C.c_void_p, C.c_int, c_int_p, c_double_p] + [c_double_p] * 5 + [c_int_p, c_int_p, c_double_p]
+        L.lcqp_hip_batch_read_working_set.argtypes = [C.c_void_p, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p]
+        L.lcqp_hip_qp_read_setup.argtypes = [C.c_void_p, c_int_p, c_double_p] + [c_double_p] * 5 + [c_int_p, c_int_p, c_double_p]
+        L.lcqp_hip_qp_read_working_set.argtypes = [C.c_void_p, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p]
         L.lcqp_hip_util_symv.argtypes = [C.c_int, C.c_int, C.c_double] + [c_double_p] * 4
         L.lcqp_hip_util_gemv.argtypes = [C.c_int, C.c_int, C.c_int] + [c_double_p] * 3
         L.lcqp_hip_util_gemv_t.argtypes = [C.c_int, C.c_int, C.c_int] + [c_double_p] * 3
@@ -151,6 +156,32 @@ def _sized(name, a, size):
     return a
 
 
+def _ip(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def _read_setup(call):
+    """call(dims, scal, C, F1, D1, Et, MM, Cp, Ci, Cv) -> rc: the raw padded device blocks of one instance's constant matrices as numpy
+    arrays (lcqp_hip_batch_read_setup).  A first call with no buffers asks for the dimensions."""
+    dims = np.zeros(9, dtype=np.int32); scal = np.zeros(2)
+    _check(call(_ip(dims), _p(scal), None, None, None, None, None, None, None, None), "read_setup")
+    np_, nblk, mEcap, mMld, capS, capC = (int(v) for v in dims[:6])
+    Cm = np.zeros((np_, np_)); F1 = np.zeros((np_, np_)); D1 = np.zeros((nblk, 64, 64)); Et = np.zeros((mEcap, np_))
+    MM = np.zeros((mMld, mMld)); Cp = np.zeros(np_ + 1, dtype=np.int32); Ci = np.zeros(capC, dtype=np.int32); Cv = np.zeros(capC)
+    _check(call(_ip(dims), _p(scal), _p(Cm), _p(F1), _p(D1), _p(Et), _p(MM), _ip(Cp), _ip(Ci), _p(Cv)), "read_setup")
+    return dict(np=np_, nblk=nblk, mEcap=mEcap, mMld=mMld, capS=capS, capC=capC, mE=int(dims[6]), cNnz=int(dims[7]),
+                setupFail=int(dims[8]), spv=float(scal[0]), scale=float(scal[1]), C=Cm, F1=F1, D1=D1, Et=Et, MM=MM, Cp=Cp, Ci=Ci, Cv=Cv)
+
+
+def _read_working_set(call, capS, mE):
+    """call(dims, slot_row, crow, row_slot, Ti) -> rc: the inverse factor of the working-set matrix and its maps (lcqp_hip_batch_read_working_set)"""
+    dims = np.zeros(2, dtype=np.int32)
+    slot_row = np.zeros(capS, dtype=np.int32); crow = np.zeros(capS, dtype=np.int32); row_slot = np.zeros(max(mE, 1), dtype=np.int32)
+    Ti = np.zeros((capS, capS))
+    _check(call(_ip(dims), _ip(slot_row), _ip(crow), _ip(row_slot), _p(Ti)), "read_working_set")
+    return dict(nT=int(dims[0]), ns=int(dims[1]), slot_row=slot_row, crow=crow, row_slot=row_slot[:mE], Ti=Ti)
+
+
 class SubsolverHIP:
     """Python view of the SubsolverBase-shaped QP object (include/SubsolverBase.hpp:28-58)."""
 
@@ -176,6 +207,16 @@ class SubsolverHIP:
         x = np.zeros(self.nV); y = np.zeros(self.nV + self.nC)
         lib().lcqp_hip_qp_get_solution(self.h, _p(x), _p(y))
         return x, y
+
+    def read_setup(self):
+        """the constant matrices of the last fresh solve (test and diagnostic entry point; see BatchLCQP.read_setup)"""
+        return _read_setup(lambda *a: lib().lcqp_hip_qp_read_setup(self.h, *a))
+
+    def read_working_set(self):
+        """the inverse factor the last solve left (test and diagnostic entry point; see BatchLCQP.read_working_set)"""
+        dims = np.zeros(9, dtype=np.int32)
+        _check(lib().lcqp_hip_qp_read_setup(self.h, _ip(dims), *[None] * 9), "read_setup")
+        return _read_working_set(lambda *a: lib().lcqp_hip_qp_read_working_set(self.h, *a), int(dims[4]), int(dims[6]))
 
     def counters(self):
         v = [C.c_int(0) for _ in range(4)]
@@ -338,6 +379,20 @@ class BatchLCQP:
         A = np.zeros((nC, n)); lbA = np.zeros(nC); ubA = np.zeros(nC)
         _check(lib().lcqp_hip_batch_read_problem(self.h, b, _p(Q), _p(g), _p(L), _p(R), _p(A), _p(lbA), _p(ubA)), "read_problem")
         return dict(Q=Q, g=g, L=L, R=R, A=A, lbA=lbA, ubA=ubA)
+
+    def read_setup(self, b):
+        """Test and diagnostic entry point: the raw padded device blocks of instance b after setup() or run() -- the dimensions np, nblk,
+        mEcap, mMld, capS, capC and the instance's mE, cNnz, setupFail, spv, scale; C [np][np], F1 [np][np] (the symmetric-filled factor
+        of Q + spv I), D1 [nblk][64][64] (its inverted diagonal blocks), Et [mEcap][np], MM [mMld][mMld] (lower triangle) and the
+        compressed rows Cp, Ci, Cv of C."""
+        return _read_setup(lambda *a: lib().lcqp_hip_batch_read_setup(self.h, b, *a))
+
+    def read_working_set(self, b):
+        """Test and diagnostic entry point: nT, ns, slot_row [capS], crow [capS], row_slot [mE] and Ti [capS][capS] of instance b as the
+        last run left them."""
+        dims = np.zeros(9, dtype=np.int32)
+        _check(lib().lcqp_hip_batch_read_setup(self.h, b, _ip(dims), *[None] * 9), "read_setup")
+        return _read_working_set(lambda *a: lib().lcqp_hip_batch_read_working_set(self.h, b, *a), int(dims[4]), int(dims[6]))
 
     def setup(self):
         _check(lib().lcqp_hip_batch_setup(self.h), "setup")

@@ -516,6 +516,58 @@ try {
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 
+// ---- read-back of the constant matrices and of the working-set factor (tests, diagnostics): the raw padded blocks of one instance ----
+template <class T>
+static int read_block(T* dst, const T* src, size_t count)
+{
+    if (dst) HIPCHK(g_err, hipMemcpy(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int lcqp_hip_batch_read_setup(lcqp_hip_batch_t* h, int b, int dims[9], double scal[2], double* Cm, double* F1, double* D1,
+                                         double* Et, double* MM, int* Cp, int* Ci, double* Cv)
+try {
+    if (!h || b < 0 || b >= h->db.B) return LCQP_INVALID_ARGUMENT;
+    if (int rc = synchronize(g_err, h)) return rc;
+    HIPCHK(g_err, hipStreamSynchronize(h->side));
+    const DevBatch& d = h->db;
+    const size_t ib = b, np = d.np, mE = d.mEcap, ld = d.mMld;
+    InstInfo info;
+    HIPCHK(g_err, hipMemcpy(&info, d.info + ib, sizeof(InstInfo), hipMemcpyDeviceToHost));
+    if (dims) {
+        const int v[9] = {d.np, d.nblk, d.mEcap, d.mMld, d.capS, d.capC, info.mE, info.cNnz, info.setupFail};
+        memcpy(dims, v, sizeof v);
+    }
+    if (scal) { scal[0] = info.spv; scal[1] = info.scale; }
+    int rc = read_block(Cm, d.C + ib * np * np, np * np);
+    if (!rc) rc = read_block(F1, d.F1 + ib * np * np, np * np);
+    if (!rc) rc = read_block(D1, d.D1 + ib * d.nblk * 4096, (size_t)d.nblk * 4096);
+    if (!rc) rc = read_block(Et, d.Et + ib * mE * np, mE * np);
+    if (!rc) rc = read_block(MM, d.MM + ib * ld * ld, ld * ld);
+    if (!rc) rc = read_block(Cp, d.Cp + ib * (np + 1), np + 1);
+    if (!rc) rc = read_block(Ci, d.Ci + ib * d.capC, (size_t)d.capC);
+    if (!rc) rc = read_block(Cv, d.Cv + ib * d.capC, (size_t)d.capC);
+    return rc;
+}
+catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+
+extern "C" int lcqp_hip_batch_read_working_set(lcqp_hip_batch_t* h, int b, int dims[2], int* slot_row, int* crow, int* row_slot, double* Ti)
+try {
+    if (!h || b < 0 || b >= h->db.B) return LCQP_INVALID_ARGUMENT;
+    if (int rc = synchronize(g_err, h)) return rc;
+    const DevBatch& d = h->db;
+    const size_t ib = b, capS = d.capS;
+    InstInfo info;
+    HIPCHK(g_err, hipMemcpy(&info, d.info + ib, sizeof(InstInfo), hipMemcpyDeviceToHost));
+    if (dims) { dims[0] = info.nT; dims[1] = info.ns; }
+    int rc = read_block(slot_row, d.idx + ib * capS, capS);
+    if (!rc) rc = read_block(crow, d.crow + ib * capS, capS);
+    if (!rc) rc = read_block(row_slot, d.mi + ib * I_NUM * d.mEcap + (size_t)I_SLOT * d.mEcap, (size_t)info.mE);
+    if (!rc) rc = read_block(Ti, d.S + ib * capS * capS, capS * capS);
+    return rc;
+}
+catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+
 // =================================================================================================
 // QP object (SubsolverBase semantics): a batch of one with nComp = 0 whose rows are the nC stacked rows
 // =================================================================================================
@@ -678,6 +730,22 @@ try {
     if (corrections) *corrections = q->cCorr;
 }
 catch (...) { }   // nothing throws across the C boundary
+
+// the QP object is a batch of one: the same two readers through its batch (LCQP_LCQPOBJECT_NOT_SETUP before the first solve built it)
+extern "C" int lcqp_hip_qp_read_setup(lcqp_hip_qp_t* q, int dims[9], double scal[2], double* Cm, double* F1, double* D1, double* Et,
+                                      double* MM, int* Cp, int* Ci, double* Cv)
+{
+    if (!q) return LCQP_INVALID_ARGUMENT;
+    if (!q->hb) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return lcqp_hip_batch_read_setup(q->hb, 0, dims, scal, Cm, F1, D1, Et, MM, Cp, Ci, Cv);
+}
+
+extern "C" int lcqp_hip_qp_read_working_set(lcqp_hip_qp_t* q, int dims[2], int* slot_row, int* crow, int* row_slot, double* Ti)
+{
+    if (!q) return LCQP_INVALID_ARGUMENT;
+    if (!q->hb) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return lcqp_hip_batch_read_working_set(q->hb, 0, dims, slot_row, crow, row_slot, Ti);
+}
 
 // =================================================================================================
 // building blocks (tests, micro-benchmarks)

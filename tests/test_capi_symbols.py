@@ -64,6 +64,9 @@ def test_c_abi_rejects_bad_arguments_without_a_gpu():
     assert L.lcqp_hip_qp_create(0, 0, Q.ctypes.data_as(dp), None, None, 0) is None
     assert L.lcqp_hip_qp_create(2, 1, Q.ctypes.data_as(dp), None, None, 0) is None          # nC > 0 without A
     assert L.lcqp_hip_batch_run(None) != 0 and L.lcqp_hip_batch_setup(None) != 0
+    dims = (ctypes.c_int * 9)()
+    assert L.lcqp_hip_batch_read_setup(None, 0, dims, *[None] * 9) != 0 and L.lcqp_hip_batch_read_working_set(None, 0, dims, *[None] * 4) != 0
+    assert L.lcqp_hip_qp_read_setup(None, dims, *[None] * 9) != 0 and L.lcqp_hip_qp_read_working_set(None, dims, *[None] * 4) != 0
     n = ctypes.c_int(0)
     if la.device_count() == 0:
         # no GPU here: creating a batch must fail with the HIP error, never fall back to anything
@@ -74,6 +77,11 @@ def test_c_abi_rejects_bad_arguments_without_a_gpu():
         g = np.zeros(2)
         rc = L.lcqp_hip_qp_solve(ctypes.c_void_p(q), 1, ctypes.byref(it), ctypes.byref(ef), g.ctypes.data_as(dp), None, None, None, None, None, None)
         assert rc == capi.SUBPROBLEM_SOLVER_ERROR and ef.value != 0
+        # the readers of the setup matrices and of the working set have nothing to read: an error code, no crash, the buffers untouched
+        dims[0] = -7
+        assert L.lcqp_hip_qp_read_setup(ctypes.c_void_p(q), dims, *[None] * 9) != 0
+        assert L.lcqp_hip_qp_read_working_set(ctypes.c_void_p(q), dims, *[None] * 4) != 0
+        assert dims[0] == -7
         L.lcqp_hip_qp_destroy(ctypes.c_void_p(q))
 
 
