@@ -156,6 +156,29 @@ int  lcqp_hip_batch_setup(lcqp_hip_batch_t* b);
 /* LCQProblem::runSolver for all instances, src/LCQProblem.cpp:444-560.  Asynchronous on the batch
  * stream; includes setup if it has not run since the last load. */
 int  lcqp_hip_batch_run(lcqp_hip_batch_t* b);
+/* Re-solves: the matrices stay, the vectors change (receding horizon, parameter sweeps).
+ * lcqp_hip_batch_update replaces every vector of instances [first, first+count) and nothing else: the arguments of lcqp_hip_batch_load
+ * without Q, L, R, A -- the same packing, the same meaning of NULL (g is required).  The batch must hold problems (load or
+ * generate_synthetic; else LCQP_LCQPOBJECT_NOT_SETUP).  The set of variables with a finite lb or ub must be the one the instance was
+ * loaded with (box bounds are rows of the factored matrices): otherwise LCQP_INVALID_ARGUMENT with a message, and nothing is written.
+ * Values, and finite against infinite on lbA / ubA / ubL / ubR, may change freely; lbL / lbR of -inf are refused as in load. */
+int  lcqp_hip_batch_update(lcqp_hip_batch_t* b, int first, int count, const double* g,
+                           const double* lbL, const double* ubL, const double* lbR, const double* ubR,
+                           const double* lbA, const double* ubA, const double* lb, const double* ub,
+                           const double* x0, const double* y0);
+/* Solve every instance again on the setup that is in place: ONE kernel (k_refresh) stands where the setup kernels of lcqp_hip_batch_run
+ * stand, then the homotopy launch.  Asynchronous on the batch stream.  When no setup belongs to the matrices and options in place (none
+ * yet, or a load / generate_synthetic / set_options since) this is lcqp_hip_batch_run.
+ * mode 0 (cold): every instance starts as after a fresh load -- the result is the bits of a new batch object given the same data by
+ *   lcqp_hip_batch_load and solved by lcqp_hip_batch_run.
+ * mode 1 (warm): an instance whose last run returned LCQP_SUCCESSFUL_RETURN starts at its last x with the penalty rho0[i] (host array [B],
+ *   every entry > 0) or, with rho0 == NULL, its last rhoOpt; it skips the zero-penalty QP, and its first QP is a hot start from the stored
+ *   point, working set and inverse factor.  Its x0 / y0 are not read.  In the reference's terms: runSolver with x0, y0 = the last
+ *   solution, solveZeroPenaltyFirst = false, initialPenaltyParameter = that penalty.  Every other instance runs cold as in mode 0.
+ * lcqp_hip_batch_last_timing reports k_refresh as setup_ms. */
+int  lcqp_hip_batch_resolve(lcqp_hip_batch_t* b, int mode, const double* rho0);
+/* out[0] = full setups, out[1] = homotopy launches this object has issued (host counters) */
+int  lcqp_hip_batch_launch_counts(lcqp_hip_batch_t* b, int out[2]);
 /* Hint of a caller that keeps several batch objects in flight (BatchPipeline): the setup of this object will run beside the homotopy
  * kernel of another one.  The library then launches the setup kernels that fit into the registers and LDS ONE finished instance frees on
  * a compute unit (the streamed form of Et = E L1^-T instead of the register-resident one), so that the setup starts in the gaps of the

@@ -87,6 +87,9 @@ def lib():
         L.lcqp_hip_batch_set_overlapped.argtypes = [C.c_void_p, C.c_int]
         L.lcqp_hip_batch_load.argtypes = [C.c_void_p, C.c_int, C.c_int] + [c_double_p] * 15
         L.lcqp_hip_batch_generate_synthetic.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
+        L.lcqp_hip_batch_update.argtypes = [C.c_void_p, C.c_int, C.c_int] + [c_double_p] * 11
+        L.lcqp_hip_batch_resolve.argtypes = [C.c_void_p, C.c_int, c_double_p]
+        L.lcqp_hip_batch_launch_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.lcqp_hip_batch_read_problem.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 7
         L.lcqp_hip_batch_setup.argtypes = [C.c_void_p]
         L.lcqp_hip_batch_run.argtypes = [C.c_void_p]
@@ -315,9 +318,13 @@ class BatchPipeline:
         self.state[k] = 2
         return self.slots[k], True        # (object, it carries a finished run)
 
-    def launch(self, bt):
+    def launch(self, bt, resolve=None, rho0=None):
+        """resolve: None launches bt.run(); False / True launch bt.resolve(warm=resolve, rho0=rho0) on the setup bt holds"""
         k = self.slots.index(bt)
-        bt.run()
+        if resolve is None:
+            bt.run()
+        else:
+            bt.resolve(warm=resolve, rho0=rho0)
         self.state[k] = 1
         self.order.append(k)
 
@@ -372,6 +379,30 @@ class BatchLCQP:
 
     def generate_synthetic(self, first_instance=0, seed0=SEED0):
         _check(lib().lcqp_hip_batch_generate_synthetic(self.h, seed0, first_instance), "generate_synthetic")
+
+    def update(self, first, count, g, lbL=None, ubL=None, lbR=None, ubR=None, lbA=None, ubA=None, lb=None, ub=None, x0=None, y0=None):
+        """lcqp_hip_batch_update: new vectors for instances [first, first + count), the matrices stay.  Returns the ReturnValue code like
+        load (0; 100 INVALID_ARGUMENT when the set of box-bounded variables would change -- see last_error()); a wrongly sized array
+        raises ValueError."""
+        n, nC, nK = self.nV, self.nC, self.nComp
+        if first < 0 or count <= 0 or first + count > self.B:
+            raise ValueError(f"instances [{first}, {first + count}) outside the batch of {self.B}")
+        sizes = (("g", g, n), ("lbL", lbL, nK), ("ubL", ubL, nK), ("lbR", lbR, nK), ("ubR", ubR, nK), ("lbA", lbA, nC), ("ubA", ubA, nC),
+                 ("lb", lb, n), ("ub", ub, n), ("x0", x0, n), ("y0", y0, self.nd))
+        a = [_sized(nm, _arr(v), count * sz) for nm, v, sz in sizes]
+        return lib().lcqp_hip_batch_update(self.h, first, count, *[_p(v) for v in a])
+
+    def resolve(self, warm=False, rho0=None):
+        """lcqp_hip_batch_resolve: solve again on the setup in place (asynchronous like run).  warm: instances whose last run succeeded
+        start from their last solution, working set and penalty (rho0: [B] starting penalties, each > 0, instead of the last rhoOpt)."""
+        r = _sized("rho0", _arr(rho0), self.B)
+        _check(lib().lcqp_hip_batch_resolve(self.h, 1 if warm else 0, _p(r)), "resolve")
+
+    def launch_counts(self):
+        """(full setups, homotopy launches) this object has issued"""
+        out = (C.c_int * 2)()
+        _check(lib().lcqp_hip_batch_launch_counts(self.h, out), "launch_counts")
+        return out[0], out[1]
 
     def read_problem(self, b):
         n, nC, nComp = self.nV, self.nC, self.nComp

@@ -44,6 +44,31 @@ class BatchLCQProblem {
     // the two halves of runSolver: the launches on this batch's own HIP stream (returns at once), and the wait + read-back.  Between the two
     // the host is free -- e.g. to load and launch another batch object (BatchPipeline below).
     ReturnValue runSolverAsync() { return (ReturnValue)lcqp_hip_batch_run(h); }
+    // Re-solves (lcqp_hip_batch_update / lcqp_hip_batch_resolve): new vectors for one instance, the matrices stay -- the argument list of
+    // loadLCQP without Q, L, R, A; the set of variables with a finite lb or ub must be the one the instance was loaded with.
+    ReturnValue updateLCQP(int instance, const double* g, const double* lbL = 0, const double* ubL = 0, const double* lbR = 0,
+                           const double* ubR = 0, const double* lbA = 0, const double* ubA = 0, const double* lb = 0,
+                           const double* ub = 0, const double* x0 = 0, const double* y0 = 0)
+    {
+        return (ReturnValue)lcqp_hip_batch_update(h, instance, 1, g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0);
+    }
+    // solve again on the setup in place.  warm: instances whose last run succeeded start from their last solution, working set and
+    // penalty (rho0: [batch] starting penalties, each > 0, instead of the last rhoOpt); every other instance, and every instance of a
+    // cold re-solve, starts as after a fresh load.  resolveAsync + collect are the two halves, as for runSolver.
+    ReturnValue resolve(bool warm, const double* rho0 = 0)
+    {
+        const ReturnValue rc = resolveAsync(warm, rho0);
+        return rc != SUCCESSFUL_RETURN ? rc : collect();
+    }
+    ReturnValue resolveAsync(bool warm, const double* rho0 = 0) { return (ReturnValue)lcqp_hip_batch_resolve(h, warm ? 1 : 0, rho0); }
+    // full setups and homotopy launches this object has issued
+    ReturnValue getLaunchCounts(int& setups, int& launches) const
+    {
+        int c[2] = {0, 0};
+        const ReturnValue rc = (ReturnValue)lcqp_hip_batch_launch_counts(h, c);
+        setups = c[0]; launches = c[1];
+        return rc;
+    }
     ReturnValue collect()
     {
         x.assign((size_t)B * nV_, 0.0);
@@ -114,12 +139,9 @@ class BatchPipeline {
     }
     bool hasResults() const { return cur >= 0 && state[cur] == 2; }     // the object acquire() returned carries a finished run
     ReturnValue lastCollectStatus() const { return lastRc; }
-    ReturnValue launch(BatchLCQProblem& b)
-    {
-        for (size_t k = 0; k < slots.size(); ++k)
-            if (slots[k] == &b) { const ReturnValue rc = b.runSolverAsync(); if (rc == SUCCESSFUL_RETURN) { state[k] = 1; order.push_back((int)k); } return rc; }
-        return INVALID_ARGUMENT;
-    }
+    ReturnValue launch(BatchLCQProblem& b) { return owns(b) ? launched(b, b.runSolverAsync()) : INVALID_ARGUMENT; }
+    // a re-solve of the batch object on the setup it holds (BatchLCQProblem::resolveAsync)
+    ReturnValue launchResolve(BatchLCQProblem& b, bool warm, const double* rho0 = 0) { return owns(b) ? launched(b, b.resolveAsync(warm, rho0)) : INVALID_ARGUMENT; }
     // after the last launch: the batches still in flight, oldest first (NULL when none is left)
     BatchLCQProblem* drain()
     {
@@ -131,6 +153,13 @@ class BatchPipeline {
     }
 
   private:
+    bool owns(const BatchLCQProblem& b) const { for (size_t k = 0; k < slots.size(); ++k) if (slots[k] == &b) return true; return false; }
+    ReturnValue launched(BatchLCQProblem& b, ReturnValue rc)
+    {
+        for (size_t k = 0; k < slots.size(); ++k)
+            if (slots[k] == &b && rc == SUCCESSFUL_RETURN) { state[k] = 1; order.push_back((int)k); }
+        return rc;
+    }
     std::vector<BatchLCQProblem*> slots;
     std::vector<int> state;      // 0 free, 1 in flight, 2 finished (results in the object)
     std::vector<int> order;      // launch order of the batches in flight

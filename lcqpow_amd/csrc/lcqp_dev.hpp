@@ -24,6 +24,10 @@ struct InstInfo {
     int ndep, ns;                                                         // ndep: active rows flagged dependent (I_DEP); ns: slots of Ti in use (high-water mark, free slots inside count)
     int cNnz, kReady, rnReady, nHot;                                                   // cNnz: non-zeros of C held in compressed rows (k_compress_C), -1: C is swept as a dense matrix; kReady: L_K exists (qp_build_K); rnReady: M_RN holds the row norms of E (and I_HOTC / M_HOTV the rows with a single non-zero, nHot of them)
     double scale, sigma, spv, rhoAdmm, phiConst;
+    // hand-over between two runs on the same setup (k_refresh).  haveSolution == 2: the stored point and working set are kept but the stored
+    // residual does not belong to them any more (new vectors) -- the next hot start takes the polish's cold entry and stores a fresh one.
+    int warm, pad0;      // warm: lcqp_run starts from the last solution (V_XK) at the penalty rho0, without the zero-penalty QP
+    double rho0;
     double hist[64];     // the last nDynamicPenalty complementarity values (src/LCQProblem.cpp:1344-1375; the reference's default is 3)
     double work[6];   // exact work sums for the byte accounting: [0] rows of Et read by the corrections, [1] sum(nT*ns) over corrections (pass over Ti), [2] bytes of Ti and M moved by working-set updates and predicted corrections, [3] number of updates, [4] rows of E read by the residual sweeps (both stages), [5] triangular solves with L1
 };
@@ -1195,14 +1199,15 @@ __device__ __forceinline__ int qp_solve(Ctx<NCH>& c, int initial, const double* 
     wg_map<4>(mE, [&](int r) { return yq[r]; }, [&](int r, double v) { ya[r] = v; });
     __syncthreads();
     int n_admm = initial ? o.admmFirst : o.admmHot;
-    const int use_stored = (!initial && uniform_i(c.info->haveSolution) && n_admm == 0);
+    const int haveSol = uniform_i(c.info->haveSolution);
+    const int use_stored = (!initial && haveSol && n_admm == 0);
     // Rows flagged dependent keep their multiplier while a solve runs (their equations are not in the factor).  ACROSS the solves of a
     // homotopy that let the multipliers of two parallel rows -- duplicated or redundant equalities -- drift apart without bound (1e11
     // against -1e11 after eight penalty updates: only their sum is determined), until the cancellation error of A'y exceeded the
     // stationarity tolerance at a point that IS stationary (fuzz seed 22 id 283: MAX_ITERATIONS_REACHED).  A hot start therefore hands a
     // flagged row's multiplier back: it starts at zero, the stored residual no longer belongs to the stored point, and the polish takes its
     // cold entry (the true residual, every row) on the stored working set.  (round 5; oracle: orc_qp_solve)
-    int reuse_stored = use_stored;
+    int reuse_stored = use_stored && haveSol != 2;      // 2: the vectors changed since the residual was stored (k_refresh)
     if (ROBUST && use_stored && uniform_i(c.info->ndep) > 0) {
         const int* dep = c.I(I_DEP);
         int z = 0;
@@ -1298,7 +1303,10 @@ __device__ __forceinline__ void lcqp_run(Ctx<NCH>& c)
     st.rhoOpt = 0.0;
     st.admmIter = st.trials = st.factorizations = st.corrections = st.qpSolves = st.reserved = 0;
     int rc = 0, qpIter = 0, histLen = 0, algoStat = 0, totalIter = 0;
-    double alphak = 1.0, rho = o.initialPenaltyParameter;                     // :999-1000
+    // warm (k_refresh): the pass below is still the first of the homotopy -- no step length, no perturbation, rhoOpt = rho -- but it starts at the
+    // last solution and penalty, without the zero-penalty QP, and its QP is a hot start on the stored working set
+    const int warm = uniform_i(c.info->warm);
+    double alphak = 1.0, rho = warm ? uniform_d(c.info->rho0) : o.initialPenaltyParameter;                     // :999-1000
     const double phiConst = uniform_d(c.info->phiConst);
     uint64_t perturbCounter = 0;
     double* hist = c.info->hist;
@@ -1308,7 +1316,10 @@ __device__ __forceinline__ void lcqp_run(Ctx<NCH>& c)
     }
 
     // xk = x0, g_tilde = g   (setInitialGuess .ipp:133-158, :966-967)
-    for (int i = t; i < np; i += WG) { xk[i] = c.V(V_X0)[i]; gtil[i] = g[i]; }
+    {
+        const double* xs = warm ? xk : c.V(V_X0);      // warm: xk still holds the x the last run returned
+        for (int i = t; i < np; i += WG) { xk[i] = xs[i]; gtil[i] = g[i]; }
+    }
     __syncthreads();
 
     auto updatePenalty = [&]() {      // :1199-1214 (Qk = Q + rho C is never materialised: Qk v = Qv + rho Cv; g_tilde follows in the fused pass)
@@ -1318,9 +1329,10 @@ __device__ __forceinline__ void lcqp_run(Ctx<NCH>& c)
     };
     double gmax = -1.0;      // max |gk| over the n variables, handed to the subsolver (it scales its tolerances with 1 + |g|_inf); < 0: not known
     auto solveQP = [&](int initial) -> int {   // :1115-1148 (getSolution, yk_A and pk = xnew - xk follow in the fused pass / at the exit)
-        const double* y0 = (initial && c.info->hasY0) ? db.y0 + (size_t)c.b * db.nd : nullptr;
+        const int qpInitial = initial && !uniform_i(c.info->warm);
+        const double* y0 = (qpInitial && c.info->hasY0) ? db.y0 + (size_t)c.b * db.nd : nullptr;
         PROF(c, P_LCQP);
-        const int ef = uniform_i(qp_solve<NCH, ROBUST, true, LR>(c, initial, gk, y0, &qpIter, gmax, /*checkBounds=*/initial));
+        const int ef = uniform_i(qp_solve<NCH, ROBUST, true, LR>(c, qpInitial, gk, y0, &qpIter, gmax, /*checkBounds=*/initial));
         qpIter = uniform_i(qpIter);
         PROF(c, P_MISC);
         st.subproblemIter += qpIter;
@@ -1330,7 +1342,7 @@ __device__ __forceinline__ void lcqp_run(Ctx<NCH>& c)
     };
 
     // first QP (:452-467)
-    if (o.solveZeroPenaltyFirst) {
+    if (o.solveZeroPenaltyFirst && !warm) {
         wg_copy(gk, g, np);
     } else {
         wg_symv<NCH>(c.C, nullptr, n, xk, nullptr, Cx, nullptr, nullptr, nullptr, c.lds);

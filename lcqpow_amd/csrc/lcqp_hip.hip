@@ -120,6 +120,13 @@ struct lcqp_hip_batch {
     int numCU = 256;
     bool overlapped = false;      // lcqp_hip_batch_set_overlapped
     bool ran = false, anyLoaded = false;
+    // re-solves (lcqp_hip_batch_update / lcqp_hip_batch_resolve): does the setup on the device belong to the matrices and options in place
+    // (set by run / setup / resolve, cleared by load / generate_synthetic / set_options); which instances hold a problem, and which of
+    // their variables carry a finite box bound (those are rows of E, hence of Et and M: an update must keep the set); launches issued
+    bool setupValid = false;
+    std::vector<char> filled, boxed;      // [B], [B][n]
+    double* rhoStart = nullptr;           // [B] on the device: starting penalties of a warm re-solve
+    int nSetups = 0, nLaunches = 0;
     int nch;
     explicit lcqp_hip_batch(int dev) : db(), device(dev) {}
     ~lcqp_hip_batch() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
@@ -219,7 +226,8 @@ try {
                     m.alloc(g_err, d.lbR, B * nLR) && m.alloc(g_err, d.yk, B * d.nd) && m.alloc(g_err, d.y0, B * d.nd) &&
                     m.alloc(g_err, d.xout, B * nV) && m.alloc(g_err, d.yout, B * d.nd) && m.alloc(g_err, d.stats, B) &&
                     m.alloc(g_err, d.info, B) && m.alloc(g_err, d.prof, B * 16);
-    if (!ok) return nullptr;
+    if (!ok || !m.alloc(g_err, h->rhoStart, B)) return nullptr;
+    h->filled.assign(B, 0); h->boxed.assign(B * (size_t)nV, 0);
     if (hipError_t e = hipStreamSynchronize(h->stream)) { hip_fail(g_err, "hipStreamSynchronize(h->stream)", e); return nullptr; }
     return h.release();
 }
@@ -234,6 +242,7 @@ catch (...) { }   // nothing throws across the C boundary
 // storeSteps: the first 1024 iterates
 extern "C" int lcqp_hip_batch_set_options(lcqp_hip_batch_t* h, const lcqp_options_t* opt)
 try {
+    if (h) h->setupValid = false;      // the scales of the ADMM weights and the proximal shifts of the factors come from the options
     return set_options(g_err, h, opt, 1024);
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
@@ -256,6 +265,21 @@ catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothin
 
 extern "C" void* lcqp_hip_batch_stream(lcqp_hip_batch_t* h) { return h ? (void*)h->stream.s : nullptr; }
 
+// both pinned staging slots hold at least `bytes`
+static int stage_reserve(lcqp_hip_batch* h, size_t bytes)
+{
+    if (h->stageBytes >= bytes) return 0;
+    h->stageBytes = 0;
+    for (StageSlot& st : h->stage) {
+        HIPCHK(g_err, hipEventSynchronize(st.done));
+        if (st.buf) (void)hipHostFree(st.buf);
+        st.buf = nullptr;
+        HIPCHK(g_err, hipHostMalloc(&st.buf, bytes, hipHostMallocDefault));
+    }
+    h->stageBytes = bytes;
+    return 0;
+}
+
 extern "C" int lcqp_hip_batch_load(lcqp_hip_batch_t* h, int first, int count,
                                    const double* Q, const double* g, const double* L, const double* R,
                                    const double* lbL, const double* ubL, const double* lbR, const double* ubR,
@@ -277,15 +301,8 @@ try {
     const size_t nY = (size_t)d.nd, nLR = (size_t)(nComp ? nComp : 1);
     const size_t infoDbl = (sizeof(InstInfo) + 7) / 8, bidxDbl = ((size_t)np * sizeof(int) + 7) / 8;
     const size_t slotBytes = sizeof(double) * (nQ + nE + nNV + nMV + nY + 2 * nLR + infoDbl + bidxDbl);
-    if (h->stageBytes < slotBytes) {
-        h->stageBytes = 0;
-        for (StageSlot& st : h->stage) {
-            if (st.buf) (void)hipHostFree(st.buf);
-            st.buf = nullptr;
-            HIPCHK(g_err, hipHostMalloc(&st.buf, slotBytes, hipHostMallocDefault));
-        }
-        h->stageBytes = slotBytes;
-    }
+    if (int rc = stage_reserve(h, slotBytes)) return rc;
+    h->setupValid = false;
     for (int k = 0; k < count; k++) {
         const size_t b = (size_t)first + k;
         StageSlot& slot = h->stage[k & 1];
@@ -316,8 +333,11 @@ try {
             vlb[i] = bnd(lb, (size_t)k * n + i, -INFINITY);     // setLB/setUB .ipp:54-112
             vub[i] = bnd(ub, (size_t)k * n + i, INFINITY);
             vx0[i] = x0 ? x0[(size_t)k * n + i] : 0.0;          // setInitialGuess .ipp:133-158
-            if (std::isfinite(vlb[i]) || std::isfinite(vub[i])) bidx[nfin++] = i;
+            const bool fin = std::isfinite(vlb[i]) || std::isfinite(vub[i]);
+            h->boxed[b * n + i] = fin;
+            if (fin) bidx[nfin++] = i;
         }
+        h->filled[b] = 1;
         info->nfin = nfin; info->mE = mA + nfin; info->hasY0 = y0 ? 1 : 0;
         HIPCHK(g_err, hipMemcpyAsync(d.Q + b * nQ, Qp, sizeof(double) * nQ, hipMemcpyHostToDevice, h->stream));
         HIPCHK(g_err, hipMemcpyAsync(d.E + b * nE, Ep, sizeof(double) * nE, hipMemcpyHostToDevice, h->stream));
@@ -348,6 +368,8 @@ try {
     DevBatch& d = h->db;
     if (d.nComp * 2 > d.n) { g_err = "synthetic generator needs 2*nComp <= nV"; return LCQP_INVALID_ARGUMENT; }
     d.hasLbL = d.hasLbR = 0; h->anyLoaded = true;
+    h->setupValid = false;
+    std::fill(h->filled.begin(), h->filled.end(), 1); std::fill(h->boxed.begin(), h->boxed.end(), 0);      // no box bounds
     dispatch_db(h, ID_k_synth_fill, d.B, nullptr, 0, seed0, firstInstance);
     dispatch_db(h, ID_k_synth_Q, d.B * (d.nblk * (d.nblk + 1) / 2));
     HIPCHK(g_err, hipGetLastError());
@@ -389,6 +411,8 @@ static int launch_setup(lcqp_hip_batch* h)
 {
     const DevBatch& d = h->db;
     hipStream_t on = h->stream;
+    h->setupValid = false;
+    h->nSetups++;
     const int ntile = d.nblk * (d.nblk + 1) / 2;
     const int nrb = (d.mEcap + 63) / 64, nb = (d.mMld + 127) / 128, nmt = nb * (nb + 1);      // k_build_M: 128 x 64 tiles of the lower triangle
     dispatch_db(h, ID_k_prepare, d.B);
@@ -412,6 +436,7 @@ static int launch_setup(lcqp_hip_batch* h)
     if (fork) HIPCHK(g_err, hipStreamWaitEvent(on, h->evJoin, 0));
     dispatch_db(h, ID_k_build_M, d.B * nmt);
     HIPCHK(g_err, hipGetLastError());
+    h->setupValid = true;
     return 0;
 }
 
@@ -443,12 +468,129 @@ try {
     if (rc) return rc;
     HIPCHK(g_err, hipEventRecord(h->ev1, h->stream));
     dispatch_db(h, ID_k_lcqp_run, h->db.B);
+    h->nLaunches++;
     HIPCHK(g_err, hipGetLastError());
     HIPCHK(g_err, hipEventRecord(h->ev2, h->stream));
     h->ran = true;
     return 0;
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+
+// New vectors for instances [first, first + count) of a batch that holds problems: everything lcqp_hip_batch_load takes except the
+// matrices.  The whole range is checked before anything is written.
+extern "C" int lcqp_hip_batch_update(lcqp_hip_batch_t* h, int first, int count, const double* g,
+                                     const double* lbL, const double* ubL, const double* lbR, const double* ubR,
+                                     const double* lbA, const double* ubA, const double* lb, const double* ub,
+                                     const double* x0, const double* y0)
+try {
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    DevBatch& d = h->db;
+    const int n = d.n, nComp = d.nComp, mA = d.mA, np = d.np, mE = d.mEcap;
+    if (first < 0 || count <= 0 || first > d.B - count) return LCQP_INVALID_ARGUMENT;
+    for (int k = 0; k < count; k++) if (!h->filled[(size_t)first + k]) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!g) return LCQP_INVALID_OBJECTIVE_LINEAR_TERM;
+    for (size_t j = 0; j < (size_t)count * nComp; j++)
+        if (bnd(lbL, j, 0.0) <= -INFINITY || bnd(lbR, j, 0.0) <= -INFINITY) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
+    for (int k = 0; k < count; k++)
+        for (int i = 0; i < n; i++) {
+            const size_t j = (size_t)k * n + i;
+            const bool fin = std::isfinite(bnd(lb, j, -INFINITY)) || std::isfinite(bnd(ub, j, INFINITY));
+            if (fin != (h->boxed[((size_t)first + k) * n + i] != 0)) {
+                g_err = "update: variable " + std::to_string(i) + " of instance " + std::to_string(first + k) +
+                        (fin ? " gains" : " loses") + " its box bound; the set of bounded variables is fixed by the load (they are rows of the factored matrices)";
+                return LCQP_INVALID_ARGUMENT;
+            }
+        }
+    HIPCHK(g_err, hipSetDevice(h->device));
+    // pinned staging: [g | lb | ub | x0 | lE | uE | y0 | lbuf | rbuf | hasY0]
+    const size_t nY = (size_t)d.nd, nLR = (size_t)(nComp ? nComp : 1);
+    const size_t slotBytes = sizeof(double) * (4 * (size_t)np + 2 * (size_t)mA + nY + 2 * nLR + 1);
+    if (int rc = stage_reserve(h, slotBytes)) return rc;
+    for (int k = 0; k < count; k++) {
+        const size_t b = (size_t)first + k;
+        StageSlot& slot = h->stage[k & 1];
+        HIPCHK(g_err, hipEventSynchronize(slot.done));            // the copies that last used this slot are done
+        double* vg = (double*)slot.buf;
+        double *vlb = vg + np, *vub = vlb + np, *vx0 = vub + np, *lE = vx0 + np, *uE = lE + mA, *ybuf = uE + mA, *lbuf = ybuf + nY, *rbuf = lbuf + nLR;
+        int* hasY0 = (int*)(rbuf + nLR);
+        memset(vg, 0, slotBytes);
+        fill_row_bounds(d, k, lbA, ubA, lbL, ubL, lbR, ubR, lE, uE, lbuf, rbuf);
+        d.hasLbL |= lbL ? 1 : 0; d.hasLbR |= lbR ? 1 : 0;      // switched on, never off: whatever the order of the calls (an absent vector is the zero vector)
+        for (int i = 0; i < np; i++) { vlb[i] = -INFINITY; vub[i] = INFINITY; }
+        for (int i = 0; i < n; i++) {
+            vg[i] = g[(size_t)k * n + i];
+            vlb[i] = bnd(lb, (size_t)k * n + i, -INFINITY);
+            vub[i] = bnd(ub, (size_t)k * n + i, INFINITY);
+            vx0[i] = x0 ? x0[(size_t)k * n + i] : 0.0;
+        }
+        *hasY0 = y0 ? 1 : 0;
+        double* nvb = d.nv + b * (size_t)V_NUM * np;
+        double* mvb = d.mv + b * (size_t)M_NUM * mE;
+        static_assert(V_UB == V_LB + 1 && V_X0 == V_UB + 1, "lb, ub and x0 go over in one copy");
+        HIPCHK(g_err, hipMemcpyAsync(nvb + (size_t)V_G * np, vg, sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(g_err, hipMemcpyAsync(nvb + (size_t)V_LB * np, vlb, sizeof(double) * 3 * np, hipMemcpyHostToDevice, h->stream));
+        if (mA) {      // the bounds of the box rows behind them follow from V_LB / V_UB on the device (k_prepare, k_refresh)
+            HIPCHK(g_err, hipMemcpyAsync(mvb + (size_t)M_L * mE, lE, sizeof(double) * mA, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(g_err, hipMemcpyAsync(mvb + (size_t)M_U * mE, uE, sizeof(double) * mA, hipMemcpyHostToDevice, h->stream));
+        }
+        HIPCHK(g_err, hipMemcpyAsync(&d.info[b].hasY0, hasY0, sizeof(int), hipMemcpyHostToDevice, h->stream));
+        if (nComp) {
+            HIPCHK(g_err, hipMemcpyAsync(d.lbL + b * nComp, lbuf, sizeof(double) * nComp, hipMemcpyHostToDevice, h->stream));
+            HIPCHK(g_err, hipMemcpyAsync(d.lbR + b * nComp, rbuf, sizeof(double) * nComp, hipMemcpyHostToDevice, h->stream));
+        }
+        if (y0) {
+            memcpy(ybuf, y0 + (size_t)k * d.nd, sizeof(double) * d.nd);
+            HIPCHK(g_err, hipMemcpyAsync(d.y0 + b * nY, ybuf, sizeof(double) * nY, hipMemcpyHostToDevice, h->stream));
+        }
+        HIPCHK(g_err, hipEventRecord(slot.done, h->stream));
+    }
+    HIPCHK(g_err, hipStreamSynchronize(h->stream));
+    return 0;
+}
+catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+
+// Solve again on the setup in place: k_refresh instead of the five setup kernels, then the homotopy launch.  Without a setup that belongs
+// to the matrices and options in place this is lcqp_hip_batch_run.
+extern "C" int lcqp_hip_batch_resolve(lcqp_hip_batch_t* h, int mode, const double* rho0)
+try {
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (mode != 0 && mode != 1) { g_err = "resolve: mode is 0 (cold) or 1 (warm)"; return LCQP_INVALID_ARGUMENT; }
+    const int B = h->db.B;
+    if (rho0)
+        for (int b = 0; b < B; b++)
+            if (!(rho0[b] > 0.0)) { g_err = "resolve: rho0[" + std::to_string(b) + "] is not positive"; return LCQP_INVALID_ARGUMENT; }
+    if (!h->anyLoaded) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!h->setupValid) return lcqp_hip_batch_run(h);
+    HIPCHK(g_err, hipSetDevice(h->device));
+    const bool withRho = mode == 1 && rho0;
+    if (withRho) {
+        if (int rc = stage_reserve(h, sizeof(double) * (size_t)B)) return rc;
+        HIPCHK(g_err, hipEventSynchronize(h->stage[0].done));
+        memcpy(h->stage[0].buf, rho0, sizeof(double) * (size_t)B);
+        HIPCHK(g_err, hipMemcpyAsync(h->rhoStart, h->stage[0].buf, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(g_err, hipEventRecord(h->stage[0].done, h->stream));
+    }
+    HIPCHK(g_err, hipEventRecord(h->ev0, h->stream));
+    LaunchArgs a;
+    a.db = h->db; a.mode = mode; a.rho0 = withRho ? h->rhoStart : nullptr;
+    lcqp_dispatch(h->nch, ID_k_refresh, B, h->stream, a);
+    HIPCHK(g_err, hipGetLastError());
+    HIPCHK(g_err, hipEventRecord(h->ev1, h->stream));
+    dispatch_db(h, ID_k_lcqp_run, B);
+    h->nLaunches++;
+    HIPCHK(g_err, hipGetLastError());
+    HIPCHK(g_err, hipEventRecord(h->ev2, h->stream));
+    h->ran = true;
+    return 0;
+}
+catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+
+extern "C" int lcqp_hip_batch_launch_counts(lcqp_hip_batch_t* h, int out[2])
+{
+    if (!h || !out) return LCQP_INVALID_ARGUMENT;
+    out[0] = h->nSetups; out[1] = h->nLaunches;
+    return 0;
+}
 
 extern "C" int lcqp_hip_batch_synchronize(lcqp_hip_batch_t* h)
 try {

@@ -163,15 +163,13 @@ int get_solution(std::string& err, H* h, int ndual, double* x, double* y, lcqp_s
 // A batch may mix instances with and without lbL / lbR: an absent bound vector is the zero vector, and the phi expressions of :969-996
 // with zeros are the arithmetic of an instance loaded without them, bit for bit.  The batch-wide flags only say whether ANY instance
 // carries bounds, i.e. whether the kernels read the (zero-filled) arrays at all; the first load of the handle, or a load starting at
-// instance 0, starts them over (k == 0), the other instances and loads add to them.
+// instance 0, starts them over (k == 0), the other instances and loads add to them (pack_row_bounds; fill_row_bounds leaves the flags
+// to its caller).
 template <class D>
-int pack_row_bounds(D& d, bool loaded, int first, int k, const double* lbA, const double* ubA, const double* lbL, const double* ubL,
+int fill_row_bounds(const D& d, int k, const double* lbA, const double* ubA, const double* lbL, const double* ubL,
                     const double* lbR, const double* ubR, double* lE, double* uE, double* lo, double* ro)
 {
     const int nC = d.nC, nComp = d.nComp;
-    const int hasL = lbL ? 1 : 0, hasR = lbR ? 1 : 0;
-    if (k == 0 && (!loaded || first == 0)) { d.hasLbL = hasL; d.hasLbR = hasR; }
-    else { d.hasLbL |= hasL; d.hasLbR |= hasR; }
     for (int r = 0; r < nC; r++) { lE[r] = bnd(lbA, (size_t)k * nC + r, -INFINITY); uE[r] = bnd(ubA, (size_t)k * nC + r, INFINITY); }
     for (int i = 0; i < nComp; i++) {
         const size_t j = (size_t)k * nComp + i;
@@ -182,6 +180,16 @@ int pack_row_bounds(D& d, bool loaded, int first, int k, const double* lbA, cons
         uE[nC + nComp + i] = bnd(ubR, j, INFINITY);
     }
     return 0;
+}
+
+template <class D>
+int pack_row_bounds(D& d, bool loaded, int first, int k, const double* lbA, const double* ubA, const double* lbL, const double* ubL,
+                    const double* lbR, const double* ubR, double* lE, double* uE, double* lo, double* ro)
+{
+    const int hasL = lbL ? 1 : 0, hasR = lbR ? 1 : 0;
+    if (k == 0 && (!loaded || first == 0)) { d.hasLbL = hasL; d.hasLbR = hasR; }
+    else { d.hasLbL |= hasL; d.hasLbR |= hasR; }
+    return fill_row_bounds(d, k, lbA, ubA, lbL, ubL, lbR, ubR, lE, uE, lo, ro);
 }
 
 }  // namespace lcqp_rt

@@ -16,28 +16,20 @@ using namespace lcqp;
 #define LCQP_LDS LCQP_LDS_N(4)
 
 
-// ---- k_prepare: scales, padding, box rows, ADMM rho vector, phi expressions ----------------------
+// ---- the vector half of the setup: bounds of the box rows, ADMM rho vector, phi expressions (k_prepare, k_refresh) ----------------------
+// Returns phi_const (uniform); writes M_L / M_U of the box rows, M_RHOV and V_GPHI.
 template <int NCH>
-__global__ __launch_bounds__(WG) void k_prepare(DevBatch db)
+__device__ __forceinline__ double prepare_vectors(const DevBatch& db, Ctx<NCH>& c, Lds lds, double scale)
 {
-    LCQP_LDS_N(NCH)
     constexpr int np = 128 * NCH;
-    const int b = blockIdx.x, t = threadIdx.x;
-    Ctx<NCH> c = make_ctx<NCH>(db, b, lds);
-    const int n = db.n, mA = db.mA, nC = db.nC, nComp = db.nComp;
-    double dmax = 0.0;
-    for (int i = t; i < n; i += WG) dmax = fmax(dmax, fabs(c.Q[(size_t)i * np + i]));
-    double scale = block_max(dmax, lds);
-    if (!(scale > 1e-300)) scale = 1.0;
-    for (int i = n + t; i < np; i += WG) c.Q[(size_t)i * np + i] = 1.0;
+    const int b = c.b, t = threadIdx.x;
+    const int mA = db.mA, nC = db.nC, nComp = db.nComp;
     const int nfin = c.info->nfin;
     const int mE = mA + nfin;
     double *l = c.M(M_L), *u = c.M(M_U), *rhov = c.M(M_RHOV);
-    for (int k = 0; k < nfin; k++) {
-        double* row = c.E + (size_t)(mA + k) * np;
+    for (int k = t; k < nfin; k += WG) {
         const int bi = c.boxidx[k];
-        for (int i = t; i < np; i += WG) row[i] = (i == bi) ? 1.0 : 0.0;
-        if (t == 0) { l[mA + k] = c.V(V_LB)[bi]; u[mA + k] = c.V(V_UB)[bi]; }
+        l[mA + k] = c.V(V_LB)[bi]; u[mA + k] = c.V(V_UB)[bi];
     }
     __syncthreads();
     const double rho = db.opt.admmRho * scale;
@@ -69,23 +61,108 @@ __global__ __launch_bounds__(WG) void k_prepare(DevBatch db)
     } else {
         wg_fill(gphi, 0.0, np);
     }
-    {   // no dependent-row flags or promotions survive a new setup (qp_polish<ROBUST>)
-        int *dep = c.I(I_DEP), *prio = c.I(I_PRIO), *rslot = c.I(I_SLOT);
-        for (int r = t; r < db.mEcap; r += WG) { dep[r] = 0; prio[r] = 0; rslot[r] = -1; }
-        for (int a = t; a < db.capS; a += WG) c.idx[a] = -1;      // the inverse factor of the working-set matrix starts empty
-    }
+    return phiConst;
+}
+
+// the subsolver of an instance starts cold: no dependent-row flags or promotions survive (qp_polish<ROBUST>), the inverse factor of the
+// working-set matrix is empty, no stored solution, a homotopy from x0 at the initial penalty
+template <int NCH>
+__device__ __forceinline__ void prepare_cold(const DevBatch& db, Ctx<NCH>& c)
+{
+    const int t = threadIdx.x;
+    int *dep = c.I(I_DEP), *prio = c.I(I_PRIO), *rslot = c.I(I_SLOT);
+    for (int r = t; r < db.mEcap; r += WG) { dep[r] = 0; prio[r] = 0; rslot[r] = -1; }
+    for (int a = t; a < db.capS; a += WG) c.idx[a] = -1;
     if (t == 0) {
         c.info->prioCtr = 0;
         c.info->ndep = 0;
-        c.info->mE = mE;
+        c.info->haveSolution = 0;
+        c.info->nT = 0; c.info->ns = 0;
+        c.info->warm = 0; c.info->rho0 = db.opt.initialPenaltyParameter;
+    }
+}
+
+// ---- k_prepare: scales, padding, box rows, ADMM rho vector, phi expressions ----------------------
+template <int NCH>
+__global__ __launch_bounds__(WG) void k_prepare(DevBatch db)
+{
+    LCQP_LDS_N(NCH)
+    constexpr int np = 128 * NCH;
+    const int b = blockIdx.x, t = threadIdx.x;
+    Ctx<NCH> c = make_ctx<NCH>(db, b, lds);
+    const int n = db.n, mA = db.mA;
+    double dmax = 0.0;
+    for (int i = t; i < n; i += WG) dmax = fmax(dmax, fabs(c.Q[(size_t)i * np + i]));
+    double scale = block_max(dmax, lds);
+    if (!(scale > 1e-300)) scale = 1.0;
+    for (int i = n + t; i < np; i += WG) c.Q[(size_t)i * np + i] = 1.0;
+    const int nfin = c.info->nfin;
+    for (int k = 0; k < nfin; k++) {
+        double* row = c.E + (size_t)(mA + k) * np;
+        const int bi = c.boxidx[k];
+        for (int i = t; i < np; i += WG) row[i] = (i == bi) ? 1.0 : 0.0;
+    }
+    const double phiConst = prepare_vectors<NCH>(db, c, lds, scale);
+    prepare_cold<NCH>(db, c);
+    if (t == 0) {
+        c.info->mE = mA + nfin;
         c.info->scale = scale;
         c.info->sigma = db.opt.admmSigma * scale;
-        c.info->rhoAdmm = rho;
+        c.info->rhoAdmm = db.opt.admmRho * scale;
         c.info->phiConst = phiConst;
-        c.info->haveSolution = 0;
-        c.info->nT = 0; c.info->ns = 0; c.info->cNnz = -1;
+        c.info->cNnz = -1;
         c.info->setupFail = 0;
         c.info->isSetup = 1;
+    }
+}
+
+// ---- k_refresh: new vectors on the setup in place, and the hand-over between two runs (lcqp_hip_batch_resolve) ----------------------
+// Stands where the five setup kernels stand in a run: the matrices, hence scale, sigma, spv, C and its compressed rows, L1, Et and M, are
+// the ones in HBM; what depends on g, the bounds and lbL / lbR is formed again exactly as k_prepare forms it, and L_K (which contains
+// E' diag(rho) E) is left to the rare instance that needs ADMM.  mode 0: every instance starts cold -- the bits of a run after a fresh load.
+// mode 1: an instance whose last run returned 0 starts warm (InstInfo::warm): from its last x, at rho0[b] (else its last rhoOpt), and its
+// first QP is a hot start on the stored point, working set and inverse factor.  The stored statuses are brought in line with the new bounds
+// (a row with equal bounds is an equality; an equality whose bounds differ, or a row held at a side that is infinite now, leaves with a zero
+// multiplier -- the polish rotates it out of the factor), a row flagged dependent hands its multiplier back as in qp_solve, and the stored
+// residual is marked void (haveSolution = 2): the polish takes its cold entry, which also forms E x, the margins and the status of every row
+// anew -- nothing of the last run's row state survives a moved bound.
+template <int NCH>
+__global__ __launch_bounds__(WG) void k_refresh(DevBatch db, int mode, const double* rho0)
+{
+    LCQP_LDS_N(NCH)
+    const int b = blockIdx.x, t = threadIdx.x;
+    Ctx<NCH> c = make_ctx<NCH>(db, b, lds);
+    const double scale = c.info->scale;
+    const int warm = mode == 1 && c.info->haveSolution != 0 && db.stats[b].returnValue == 0 && c.info->setupFail == 0;
+    double rhoStart = db.opt.initialPenaltyParameter;
+    if (warm) {
+        const double last = db.stats[b].rhoOpt;
+        rhoStart = rho0 ? rho0[b] : (last > 0.0 ? last : db.opt.initialPenaltyParameter);
+    }
+    __syncthreads();      // every thread has read the marks thread 0 rewrites below
+    const double phiConst = prepare_vectors<NCH>(db, c, lds, scale);
+    if (warm) {
+        const int mE = c.mE;
+        const double *l = c.M(M_L), *u = c.M(M_U);
+        double* yq = c.M(M_YQ);
+        int *st = c.I(I_ST), *dep = c.I(I_DEP), *prio = c.I(I_PRIO);
+        for (int r = t; r < mE; r += WG) {
+            const double lo = l[r], hi = u[r];
+            int s = st[r];
+            if (lo == hi) s = ST_EQ;
+            else if (s == ST_EQ || (s == ST_LOWER && isinf(lo)) || (s == ST_UPPER && isinf(hi))) s = ST_INACT;
+            if (s == ST_INACT || dep[r]) yq[r] = 0.0;
+            st[r] = s;
+            dep[r] = 0; prio[r] = 0;
+        }
+        if (t == 0) { c.info->prioCtr = 0; c.info->ndep = 0; c.info->haveSolution = 2; c.info->warm = 1; c.info->rho0 = rhoStart; }
+    } else {
+        prepare_cold<NCH>(db, c);
+    }
+    if (t == 0) {
+        c.info->rhoAdmm = db.opt.admmRho * scale;
+        c.info->phiConst = phiConst;
+        c.info->kReady = 0;
     }
 }
 
@@ -761,6 +838,7 @@ static void launch_impl(int kid, int grid, hipStream_t s, const LaunchArgs& a)
 {
     switch (kid) {
         case ID_k_prepare:    hipLaunchKernelGGL((k_prepare<NCH>), dim3(grid), dim3(WG), 0, s, a.db); break;
+        case ID_k_refresh:    hipLaunchKernelGGL((k_refresh<NCH>), dim3(grid), dim3(WG), 0, s, a.db, a.mode, a.rho0); break;
         case ID_k_build_C:    hipLaunchKernelGGL((k_build_C<NCH>), dim3(grid), dim3(WG), 0, s, a.db); break;
         case ID_k_compress_C: hipLaunchKernelGGL((k_compress_C<NCH>), dim3(grid), dim3(WG), 0, s, a.db); break;
         case ID_k_factor:     hipLaunchKernelGGL((k_factor<NCH, 1>), dim3(grid), dim3(WG), 0, s, a.db); break;

@@ -6,13 +6,15 @@
 namespace lcqp {
 
 enum KernelId { ID_k_prepare, ID_k_build_C, ID_k_compress_C, ID_k_factor, ID_k_factor_full, ID_k_trsm, ID_k_trsm_streamed, ID_k_build_M, ID_k_lcqp_run, ID_k_qp_solve,
-                ID_k_synth_fill, ID_k_synth_Q, ID_k_util_symv, ID_k_util_rows, ID_k_util_rows_list };
+                ID_k_synth_fill, ID_k_synth_Q, ID_k_util_symv, ID_k_util_rows, ID_k_util_rows_list, ID_k_refresh };
 
 struct LaunchArgs {
     DevBatch db;
     const int* list = nullptr;
     int initial = 0;
     uint64_t seed0 = 0, first = 0;
+    int mode = 0;                       // k_refresh: 0 every instance cold, 1 warm where the last run succeeded
+    const double* rho0 = nullptr;       // k_refresh: [B] starting penalties of the warm instances (device), or null
     // building-block kernels
     int n = 0, m = 0;
     double alpha = 0.0;
