@@ -1,6 +1,8 @@
 """Load once, then K steps of new vectors + warm re-solve: a batch of controllers that solve the same LCQP matrices
 again and again with a new linear term and new bounds.
-    python examples/resolve_sequence.py [B=256] [steps=5]"""
+    python examples/resolve_sequence.py [B=256] [steps=5]
+    python examples/resolve_sequence.py [B=256] [steps=5] sparse     the same on the sparse arm (lcqp_hip_sparse_update / _resolve): the banded
+                                                                     synthetic workload at n = 512, iterate counts per step"""
 import os
 import sys
 import time
@@ -11,9 +13,44 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import lcqpow_amd as la  # noqa: E402
 
 
+def sparse_leg(B, steps):
+    from lcqpow_amd import synth_sparse as S
+    n, nC, nK = 512, 256, 64
+    Qpat, Apat, qo, eo = S.sparse_pattern_arrays(n, nC, nK)
+    inst = [S.sparse_values(i, n, nC, nK, orders=(qo, eo)) for i in range(B)]
+    sb = la.SparseBatchLCQP(B, n, nC, nK, Qpat, Apat, opt=la.default_options(perturbStep=0, printLevel=0))
+    g = np.stack([d["g"] for d in inst]); lbA = np.stack([d["lbA"] for d in inst]); ubA = np.stack([d["ubA"] for d in inst])
+    rc = sb.load(0, B, np.stack([d["Qx"] for d in inst]), g, np.stack([d["Ex"] for d in inst]), lbA=lbA, ubA=ubA)     # the matrices go to the device once
+    if rc != 0:
+        raise RuntimeError(f"load failed with code {rc}")
+    sb.run()
+    _, _, st = sb.solution()
+    setup_ms, solve_ms = sb.last_timing()
+    print(f"sparse, first solve: {np.mean([s['iterTotal'] for s in st]):.1f} iterates per LCQP, setup {setup_ms:.2f} ms + homotopy {solve_ms:.2f} ms")
+    rng = np.random.default_rng(0)
+    for step in range(1, steps + 1):
+        g = g * (1.0 + 0.02 * rng.standard_normal(g.shape))
+        shift = 0.02 * (ubA - lbA) * rng.standard_normal(lbA.shape)
+        lbA, ubA = lbA + shift, ubA + shift
+        rc = sb.update(0, B, g, lbA=lbA, ubA=ubA)
+        if rc != 0:
+            raise RuntimeError(f"update failed with code {rc}")
+        sb.resolve(warm=True)
+        _, _, st = sb.solution()
+        refresh_ms, solve_ms = sb.last_timing()
+        it = [s["iterTotal"] for s in st]
+        ok = sum(s["returnValue"] == 0 for s in st)
+        print(f"sparse, step {step}: {ok}/{B} solved, iterates mean {np.mean(it):.1f} max {max(it)}, refresh {refresh_ms:.3f} ms + homotopy {solve_ms:.2f} ms")
+    print("sparse, launches (full setups, homotopy launches):", sb.launch_counts())
+    sb.close()
+
+
 def main():
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    if len(sys.argv) > 3 and sys.argv[3] == "sparse":
+        sparse_leg(B, steps)
+        return
     n, nC, nComp = 256, 512, 64
     bt = la.BatchLCQP(B, n, nC, nComp, opt=la.default_options(printLevel=0))
     bt.generate_synthetic(0)          # stands for load(): the matrices go to the device once

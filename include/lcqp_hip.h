@@ -260,6 +260,23 @@ int lcqp_hip_chol_solve(int batch, int n, const double* K, const double* b, doub
  * lcqp_sparse_general.hpp; a 2-D grid with 16 384 variables is one).  Returns NULL only when a front of that factorisation would exceed
  * 576 rows or the factor 2^28 entries (lcqp_hip_sparse_last_error() says so): the host layer runs such a problem on the dense kernels,
  * which take nV <= 4096.
+ *
+ * Re-solves on the matrices in place (the sparse twin of lcqp_hip_batch_update / _resolve / _launch_counts):
+ *   lcqp_hip_sparse_update   new g, bounds, x0, y0 for instances [first, first + count): the argument list of lcqp_hip_sparse_load without
+ *                            Qx and Ax, same packing, NULL as there.  The stored solution, working set and factors of the instances stay.
+ *                            Refused before anything is written: a range outside the batch (LCQP_INVALID_ARGUMENT), an instance never loaded
+ *                            (LCQP_LCQPOBJECT_NOT_SETUP), g == NULL (LCQP_INVALID_OBJECTIVE_LINEAR_TERM), -inf in lbL / lbR
+ *                            (LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND).
+ *   lcqp_hip_sparse_resolve  solves again (asynchronous, like run).  While the setup on the device belongs to the matrices and options in
+ *                            place (run and resolve set the mark, load and set_options clear it) ONE kernel stands where the setup kernel
+ *                            of a run stands: it forms what depends on the bounds and rebuilds the ADMM KKT factor only for instances in
+ *                            which a row changed its class (free, equality, other); last_timing reports it as setup_ms.  Otherwise the
+ *                            call is lcqp_hip_sparse_run.  mode 0 (cold): the bits of a fresh handle given the same data by load and solved
+ *                            by run.  mode 1 (warm): an instance whose last run returned 0 starts at its last solution, working set, polish
+ *                            factor and penalty -- rho0 [B] (host; every entry finite and > 0, else LCQP_INVALID_ARGUMENT) or NULL for its
+ *                            last rhoOpt -- without the zero-penalty QP: runSolver with x0, y0 = the last solution,
+ *                            solveZeroPenaltyFirst = false, initialPenaltyParameter = rho.  Every other instance runs cold.
+ *   lcqp_hip_sparse_launch_counts   out[0] full setups, out[1] homotopy launches this handle has issued.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct lcqp_hip_sparse lcqp_hip_sparse_t;
 lcqp_hip_sparse_t* lcqp_hip_sparse_create(int batch, int nV, int nC, int nComp, const int* Qp, const int* Qi,
@@ -283,6 +300,11 @@ int  lcqp_hip_sparse_load(lcqp_hip_sparse_t* s, int first, int count, const doub
                           const double* lbA, const double* ubA, const double* lbL, const double* ubL, const double* lbR,
                           const double* ubR, const double* x0, const double* y0);
 int  lcqp_hip_sparse_run(lcqp_hip_sparse_t* s);                          /* runSolver for every instance (asynchronous) */
+int  lcqp_hip_sparse_update(lcqp_hip_sparse_t* s, int first, int count, const double* g,
+                            const double* lbA, const double* ubA, const double* lbL, const double* ubL,
+                            const double* lbR, const double* ubR, const double* x0, const double* y0);
+int  lcqp_hip_sparse_resolve(lcqp_hip_sparse_t* s, int mode, const double* rho0);
+int  lcqp_hip_sparse_launch_counts(lcqp_hip_sparse_t* s, int out[2]);   /* full setups, homotopy launches */
 int  lcqp_hip_sparse_synchronize(lcqp_hip_sparse_t* s);
 int  lcqp_hip_sparse_last_timing(lcqp_hip_sparse_t* s, float* setup_ms, float* solve_ms);
 int  lcqp_hip_sparse_get_solution(lcqp_hip_sparse_t* s, double* x, double* y, lcqp_stats_t* stats);   /* y: [B][nC + 2 nComp] */

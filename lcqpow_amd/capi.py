@@ -117,6 +117,9 @@ def lib():
         L.lcqp_hip_csc_destroy.argtypes = [C.c_void_p]
         L.lcqp_hip_csc_apply.argtypes = [C.c_void_p, C.c_int, C.c_double, c_double_p, c_double_p, c_double_p, C.c_int, C.POINTER(C.c_float)]
         L.lcqp_hip_chol_solve.argtypes = [C.c_int, C.c_int] + [c_double_p] * 3 + [C.c_int, C.POINTER(C.c_float)]
+        L.lcqp_hip_sparse_update.argtypes = [C.c_void_p, C.c_int, C.c_int] + [c_double_p] * 9
+        L.lcqp_hip_sparse_resolve.argtypes = [C.c_void_p, C.c_int, c_double_p]
+        L.lcqp_hip_sparse_launch_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         _lib = L
     return _lib
 
@@ -633,6 +636,29 @@ class SparseBatchLCQP:
 
     def run(self):
         self._chk(lib().lcqp_hip_sparse_run(self.h), "run")
+
+    def update(self, first, count, g, lbA=None, ubA=None, lbL=None, ubL=None, lbR=None, ubR=None, x0=None, y0=None):
+        """lcqp_hip_sparse_update: new vectors for instances [first, first + count), the matrices stay (the argument list of load without
+        Qx and Ax).  Returns the ReturnValue code like load (0; 100 for a range outside the batch, 116 for g = None, 120 for -inf in
+        lbL / lbR); a wrongly sized array raises ValueError."""
+        n, nC, nK = self.nV, self.nC, self.nComp
+        sizes = (("g", g, n), ("lbA", lbA, nC), ("ubA", ubA, nC), ("lbL", lbL, nK), ("ubL", ubL, nK), ("lbR", lbR, nK), ("ubR", ubR, nK),
+                 ("x0", x0, n), ("y0", y0, self.m))
+        a = [_sized(nm, _arr(v), max(count, 0) * sz) for nm, v, sz in sizes]
+        return lib().lcqp_hip_sparse_update(self.h, first, count, *[_p(v) for v in a])
+
+    def resolve(self, warm=False, rho0=None):
+        """lcqp_hip_sparse_resolve: solve again on the setup in place (asynchronous like run).  warm: instances whose last run succeeded
+        start from their last solution, working set and penalty (rho0: [B] starting penalties, each finite and > 0, instead of the last
+        rhoOpt); the others, and all of them without warm, start cold -- the bits of a fresh handle."""
+        r = _sized("rho0", _arr(rho0), self.B)
+        self._chk(lib().lcqp_hip_sparse_resolve(self.h, 1 if warm else 0, _p(r)), "resolve")
+
+    def launch_counts(self):
+        """(full setups, homotopy launches) this object has issued"""
+        out = (C.c_int * 2)()
+        self._chk(lib().lcqp_hip_sparse_launch_counts(self.h, out), "launch_counts")
+        return out[0], out[1]
 
     def synchronize(self):
         self._chk(lib().lcqp_hip_sparse_synchronize(self.h), "synchronize")

@@ -45,6 +45,8 @@ enum { MI_ST, MI_STT, MI_STF, MI_NEW, MI_NUM };
 
 struct SpInfo {
     int haveSolution, stfValid, hasY0, bigReg;     // bigReg: this instance needs the safe regularisation of the polish (a Hessian that is only semidefinite)
+    int warm, pad0;                                // warm (k_sparse_refresh): sp_ph_start begins at the last solution, at the penalty rho0, without the zero-penalty QP
+    double rho0;
     double scale, sigma, delta, delta2, phiConst;
     double deltaS, delta2S;                        // the light level tried first (sp_polish)
     double e1max;                                  // largest row 1-norm of E: with |x|_inf the scale of the rounding of a computed E_r x (the active-row test of the polish)
@@ -1533,12 +1535,14 @@ __device__ __forceinline__ int sp_ph_correct(SpCtx<G>& c, SpState& S)
 
 // the subsolver call starts (oracle: sqp_solve, entry): SubsolverBase::solve on the OSQP arm.  A hot start from the stored solution goes
 // straight to the polish; everything else takes the round preamble (PH_ROUND).
+// warmFirst (sp_ph_start of a warm re-solve, k_sparse_refresh): the first QP of the homotopy is a hot start on the stored point and working
+// set -- but the stored residual and E x belong to the g and the bounds of the run before, so the polish takes its cold entry there.
 template <int G>
-__device__ __forceinline__ int sp_qp_begin(SpCtx<G>& c, SpState& S, GD g)
+__device__ __forceinline__ int sp_qp_begin(SpCtx<G>& c, SpState& S, GD g, bool warmFirst = false)
 {
     const SpBatch& db = *c.db;
     const lcqp_options_t& o = db.opt;
-    const int t = c.gl, n = db.n, m = db.m, initial = S.initial;
+    const int t = c.gl, n = db.n, m = db.m, initial = S.initial && !warmFirst;
     GD xq = c.V(NV_XQ), xa = c.V(NV_XA), xt = c.V(NV_XT);
     GD yq = c.M(MV_YQ), ya = c.M(MV_YA), yt = c.M(MV_YT);
     GD l = c.M(MV_L), u = c.M(MV_U);
@@ -1568,7 +1572,7 @@ __device__ __forceinline__ int sp_qp_begin(SpCtx<G>& c, SpState& S, GD g)
     // (xt is xq already: the stored solution is the accepted trial vector of the QP before, copied from xt in sp_ph_qpend, and nothing has
     // written xt since -- use_stored is only set behind that copy)
     g_sync();
-    return sp_polish_begin<G>(c, S, g, 1);
+    return sp_polish_begin<G>(c, S, g, warmFirst ? 0 : 1);
 }
 
 // PH_ROUND: the preamble of a round that does not start from the stored solution -- the first QP of a homotopy, and every round after a
@@ -1621,20 +1625,30 @@ __device__ __forceinline__ int sp_ph_start(SpCtx<G>& c, SpState& S)
     GD Qx = c.V(NV_QX), Cx = c.V(NV_CX), Qp = c.V(NV_QP), Cp = c.V(NV_CP);
     memset(&S.st, 0, sizeof(S.st));
     S.rc = 0; S.qpIter = 0; S.histLen = 0; S.algoStat = 0; S.totalIter = 0;
-    S.alphak = 1.0; S.rho = o.initialPenaltyParameter;
+    // warm (k_sparse_refresh): the pass that follows is still the first of the homotopy -- no step length, no perturbation, rhoOpt = rho --
+    // but it starts at the last solution (NV_XK still holds it) and at the penalty rho0, without the zero-penalty QP, and its QP is a hot
+    // start on the stored point and working set (sp_qp_begin)
+    const int warm = c.info->warm;
+    S.alphak = 1.0; S.rho = warm ? c.info->rho0 : o.initialPenaltyParameter;
     S.perturbCounter = 0;
     if (db.traceCap > 0 && t == 0) db.traceLen[c.b] = 0;     // a run that records nothing leaves an empty trace
-    { GD x0 = c.V(NV_X0);
-      g_map<G, 8>(n, t, [&](int i) { return D2{x0[i], g[i]}; }, [&](int i, D2 v) { xk[i] = v.a; gtil[i] = v.b; }); }
+    if (warm) {
+        const double rho = S.rho;
+        if (db.hasLbL || db.hasLbR) { GD gphi = c.V(NV_GPHI); g_map<G, 8>(n, t, [&](int i) { return D2{g[i], gphi[i]}; }, [&](int i, D2 v) { gtil[i] = v.a + rho * v.b; }); }
+        else g_map<G, 8>(n, t, [&](int i) { return g[i]; }, [&](int i, double v) { gtil[i] = v; });
+    } else {
+        GD x0 = c.V(NV_X0);
+        g_map<G, 8>(n, t, [&](int i) { return D2{x0[i], g[i]}; }, [&](int i, D2 v) { xk[i] = v.a; gtil[i] = v.b; });
+    }
     g_sync();
     // Q x0 and C x0 once; from here on both follow the steps (sp_ph_qpend)
     sp_Qx2<G>(c, xk, xk, Qx, Qp); sp_Cx2<G>(c, xk, xk, Cx, Cp);
     c.bytes += db.by[BY_START];
-    if (o.solveZeroPenaltyFirst) { for (int i = t; i < n; i += G) gk[i] = g[i]; g_sync(); }
+    if (o.solveZeroPenaltyFirst && !warm) { for (int i = t; i < n; i += G) gk[i] = g[i]; g_sync(); }
     else { const double rho = S.rho; for (int i = t; i < n; i += G) gk[i] = rho * Cx[i] + gtil[i]; g_sync(); }
     S.initial = 1;
     S.gmaxNext = -1.0;      // max |gk| of the next QP when this level has formed it (-1: the subsolver looks)
-    return sp_qp_begin<G>(c, S, gk);
+    return sp_qp_begin<G>(c, S, gk, warm != 0);
 }
 
 // PH_QPEND: the subsolver has a verified solution (oracle: the exit of sqp_solve), then one iterate of runSolver's loop up to the next QP
@@ -1825,27 +1839,23 @@ __device__ __forceinline__ SpCtx<G> sp_ctx(const SpBatch& db, int b, int w0, int
 }
 
 // ---- setup: scales, rho vector, phi expressions, the ONE factorisation of the ADMM KKT matrix ----------------------------------
-template <int G>
-__global__ __launch_bounds__(WGS) void k_sparse_setup(SpBatch db)
+// The vector half of the setup, shared by k_sparse_setup and k_sparse_refresh: the ADMM weights of the rows from l and u (a free row
+// 1e-6 rho, an equality rho rhoEqMult, anything else rho), g_phi and phi_const from lbL / lbR (src/LCQProblem.cpp:969-996).  Returns
+// phi_const.  DETECT: `changed` says whether a weight of this lane's rows differs from the one in place, i.e. from the one inside the ADMM
+// KKT factor.
+template <int G, bool DETECT>
+__device__ __forceinline__ double sp_prepare_vectors(SpCtx<G>& c, double scale, int& changed)
 {
-    const int b = blockIdx.x * (64 / G) + threadIdx.x / G;
-    if (b >= db.B) return;
-    SpCtx<G> c = sp_ctx<G>(db, b, blockIdx.x * (64 / G), (int)threadIdx.x);
+    const SpBatch& db = *c.db;
     const int t = c.gl, n = db.n, m = db.m, nC = db.nC, nK = db.nComp;
-#ifdef LCQP_PROFILE
-    if (t == 0) for (int k = 0; k < SP_NPHASE; k++) c.info->prof[k] = 0.0;
-#endif
-    double dmax = 0.0;
-    for (int i = t; i < n; i += G)
-        for (int k = db.Qp[i]; k < db.Qp[i + 1]; k++) if (db.Qi[k] == i) dmax = fmax(dmax, fabs(c.Qx()[k]));
-    double scale = g_max<G>(dmax);
-    if (!(scale > 1e-300)) scale = 1.0;
     const double rho = db.opt.admmRho * scale;
     GD l = c.M(MV_L), u = c.M(MV_U), rhov = c.M(MV_RHOV);
+    changed = 0;
     for (int r = t; r < m; r += G) {
         double rv = rho;
         if (isinf(l[r]) && isinf(u[r])) rv = 1e-6 * rho;
         else if (l[r] == u[r]) rv = rho * db.opt.rhoEqMult;
+        if (DETECT) changed |= (rhov[r] != rv);
         rhov[r] = rv;
     }
     // phi expressions (src/LCQProblem.cpp:969-996)
@@ -1863,6 +1873,40 @@ __global__ __launch_bounds__(WGS) void k_sparse_setup(SpBatch db)
     } else {
         for (int i = t; i < n; i += G) gphi[i] = 0.0;
     }
+    return phiConst;
+}
+
+// the ADMM KKT matrix [Q + sigma I, E'; E, -diag(1 / rhov)] factorised, with its border when the pattern has one
+template <int G>
+__device__ __forceinline__ void sp_admm_factor(SpCtx<G>& c, double scale)
+{
+    const SpBatch& db = *c.db;
+    GD rhov = c.M(MV_RHOV);
+    sp_factor_band<G>(c, c.KF(true), c.KD(true), db.opt.admmSigma * scale, [=](int r) { return 1.0 / rhov[r]; }, [](int) { return true; });
+    if (db.kb > 0) {
+        sp_border_prepare<G>(c, true, [](int) { return true; });
+        for (int jb = 0; jb < db.kb; jb++) { GD vec = sp_border_column<G>(c, true, jb); sp_solve_band<G>(c, true, vec); }
+        sp_border_schur<G>(c, true, db.opt.admmSigma * scale, [=](int r) { return 1.0 / rhov[r]; }, [](int) { return true; });
+    }
+}
+
+template <int G>
+__global__ __launch_bounds__(WGS) void k_sparse_setup(SpBatch db)
+{
+    const int b = blockIdx.x * (64 / G) + threadIdx.x / G;
+    if (b >= db.B) return;
+    SpCtx<G> c = sp_ctx<G>(db, b, blockIdx.x * (64 / G), (int)threadIdx.x);
+    const int t = c.gl, n = db.n, m = db.m;
+#ifdef LCQP_PROFILE
+    if (t == 0) for (int k = 0; k < SP_NPHASE; k++) c.info->prof[k] = 0.0;
+#endif
+    double dmax = 0.0;
+    for (int i = t; i < n; i += G)
+        for (int k = db.Qp[i]; k < db.Qp[i + 1]; k++) if (db.Qi[k] == i) dmax = fmax(dmax, fabs(c.Qx()[k]));
+    double scale = g_max<G>(dmax);
+    if (!(scale > 1e-300)) scale = 1.0;
+    int unused;
+    const double phiConst = sp_prepare_vectors<G, false>(c, scale, unused);
     double e1 = 0.0;
     {
         GD Ev = c.Ex();
@@ -1874,6 +1918,7 @@ __global__ __launch_bounds__(WGS) void k_sparse_setup(SpBatch db)
         c.info->scale = scale; c.info->sigma = db.opt.admmSigma * scale; c.info->delta = db.opt.proxBig * scale; c.info->delta2 = 1e-9 / scale;
         c.info->phiConst = phiConst; c.info->haveSolution = 0; c.info->stfValid = 0; c.info->bytes = 0.0;
         c.info->deltaS = db.opt.proxSmall * scale; c.info->delta2S = 1e-14 / scale; c.info->bigReg = 0;
+        c.info->warm = 0;
     }
     g_sync();
     if constexpr (G <= 16) {
@@ -1892,12 +1937,57 @@ __global__ __launch_bounds__(WGS) void k_sparse_setup(SpBatch db)
         }
         g_sync();
     }
-    sp_factor_band<G>(c, c.KF(true), c.KD(true), db.opt.admmSigma * scale, [=](int r) { return 1.0 / rhov[r]; }, [](int) { return true; });
-    if (db.kb > 0) {
-        sp_border_prepare<G>(c, true, [](int) { return true; });
-        for (int jb = 0; jb < db.kb; jb++) { GD vec = sp_border_column<G>(c, true, jb); sp_solve_band<G>(c, true, vec); }
-        sp_border_schur<G>(c, true, db.opt.admmSigma * scale, [=](int r) { return 1.0 / rhov[r]; }, [](int) { return true; });
+    sp_admm_factor<G>(c, scale);
+    if (t == 0) c.info->bytes = c.bytes;
+}
+
+// ---- refresh: new vectors on the setup in place, and the hand-over between two runs (lcqp_hip_sparse_resolve) ----------------------------
+// Stands where k_sparse_setup stands in a run.  The matrices, hence scale, sigma, the regularisations, e1max and K0, are the ones in memory;
+// what depends on the bounds and on lbL / lbR is formed again exactly as the setup forms it.  The ADMM KKT factor contains 1 / rhov: it is
+// rebuilt for an instance in which the class of a row changed (free, equality, other) and left in place otherwise -- the same weights give
+// the same factor bit for bit.  (Lane groups of one wavefront may part here: the factorisation and the border routines keep everything
+// per group -- collectives inside the group, the group's own piece of LDS, no workgroup barrier -- as k_sparse_sched relies on when a
+// step holds fewer instances than the wavefront has groups.)
+// mode 0: every instance starts cold, as the setup leaves it.  mode 1: an instance whose last run returned 0 starts warm (SpInfo::warm):
+// at its last x and at rho0[b] (else its last rhoOpt), its first QP a hot start on the stored point, working set and polish factor.  The
+// stored statuses are brought in line with the new bounds: equal bounds make an equality; an equality whose bounds differ, or a row held
+// at a side that is infinite now, leaves with a zero multiplier (the trial's comparison of the factor's set with the working set then
+// asks for a factorisation).
+template <int G>
+__global__ __launch_bounds__(WGS) void k_sparse_refresh(SpBatch db, int mode, const double* rho0)
+{
+    const int b = blockIdx.x * (64 / G) + threadIdx.x / G;
+    if (b >= db.B) return;
+    SpCtx<G> c = sp_ctx<G>(db, b, blockIdx.x * (64 / G), (int)threadIdx.x);
+    const int t = c.gl, m = db.m;
+    const double scale = c.info->scale;
+    const int warm = mode == 1 && c.info->haveSolution != 0 && db.stats[b].returnValue == 0;
+    double rhoStart = db.opt.initialPenaltyParameter;
+    if (warm) {
+        const double last = db.stats[b].rhoOpt;
+        rhoStart = rho0 ? rho0[b] : (last > 0.0 ? last : db.opt.initialPenaltyParameter);
     }
+    int changed;
+    const double phiConst = sp_prepare_vectors<G, true>(c, scale, changed);
+    if (warm) {
+        GD l = c.M(MV_L), u = c.M(MV_U), yq = c.M(MV_YQ);
+        GI st = c.I(MI_ST);
+        for (int r = t; r < m; r += G) {
+            const double lo = l[r], hi = u[r];
+            int s = st[r];
+            if (lo == hi) s = ST_EQ;
+            else if (s == ST_EQ || (s == ST_LOWER && isinf(lo)) || (s == ST_UPPER && isinf(hi))) s = ST_INACT;
+            if (s == ST_INACT) yq[r] = 0.0;
+            st[r] = s;
+        }
+    }
+    if (t == 0) {
+        c.info->phiConst = phiConst; c.info->bytes = 0.0;
+        c.info->warm = warm; c.info->rho0 = rhoStart;
+        if (!warm) { c.info->haveSolution = 0; c.info->stfValid = 0; c.info->bigReg = 0; }
+    }
+    g_sync();
+    if (g_any<G>(changed)) sp_admm_factor<G>(c, scale);
     if (t == 0) c.info->bytes = c.bytes;
 }
 
@@ -2122,13 +2212,15 @@ __global__ void k_sparse_sched_init(SpBatch db)
     }
 }
 
+// refresh: k_sparse_refresh<G>(mode, rho0) stands where k_sparse_setup<G> stands (lcqp_hip_sparse_resolve)
 template <int G>
-static void sp_launch(const SpBatch& db, hipStream_t stream, hipEvent_t mid)
+static void sp_launch(const SpBatch& db, hipStream_t stream, hipEvent_t mid, bool refresh = false, int mode = 0, const double* rho0 = nullptr)
 {
     const int ipw = 64 / G, grid = (db.B + ipw - 1) / ipw;
     // LDS: the working sets' bit sets of sp_ph_factor (G <= 16), the window of sp_factor_lds (per group G x G and 16 staged rows) otherwise
     const size_t ldsBytes = G <= 16 ? sizeof(unsigned) * (size_t)ipw * db.bitWords : sizeof(double) * (size_t)ipw * (G * G + 16 * G);
-    hipLaunchKernelGGL(k_sparse_setup<G>, dim3(grid), dim3(WGS), ldsBytes, stream, db);
+    if (refresh) hipLaunchKernelGGL(k_sparse_refresh<G>, dim3(grid), dim3(WGS), ldsBytes, stream, db, mode, rho0);
+    else hipLaunchKernelGGL(k_sparse_setup<G>, dim3(grid), dim3(WGS), ldsBytes, stream, db);
     (void)hipEventRecord(mid, stream);
     const int ninit = std::max(db.nPools * db.poolSize, db.nPools * (PH_NUM + 1) * QCTL);
     hipLaunchKernelGGL(k_sparse_sched_init, dim3((ninit + 255) / 256), dim3(256), 0, stream, db);
@@ -2174,6 +2266,12 @@ struct lcqp_hip_sparse {
     std::vector<int> qdiagHost;    // entry of Q_ii in the value array
     std::vector<double> diagRatio; // per instance: min_i Q_ii / max_i Q_ii of the loaded Hessian (1: not loaded yet)
     bool loaded = false, ran = false;
+    std::vector<char> filled;      // per instance: a load has given it a problem
+    // re-solves (lcqp_hip_sparse_update / lcqp_hip_sparse_resolve): does the setup on the device belong to the matrices and options in place
+    // (run and resolve set the mark; load and set_options clear it)
+    bool setupValid = false;
+    int nSetups = 0, nLaunches = 0;      // full setups (k_sparse_setup) and homotopy launches issued: lcqp_hip_sparse_launch_counts
+    double* rhoStart = nullptr;          // [B] starting penalties of a warm re-solve (allocated by the first resolve that carries them)
     explicit lcqp_hip_sparse(int dev) : db(), device(dev) {}
     ~lcqp_hip_sparse() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
 };
@@ -2209,7 +2307,7 @@ try {
     std::unique_ptr<lcqp_hip_sparse> h(new lcqp_hip_sparse(device));
     for (hipError_t e : {h->stream.status, h->ev0.status, h->ev1.status, h->ev2.status})
         if (e != hipSuccess) { hip_fail(g_sp_err, "stream/event creation", e); return nullptr; }
-    h->csr2csc = P.csr2csc; h->hasB = P.hasB; h->qdiagHost = P.qdiag; h->diagRatio.assign(batch, 1.0);
+    h->csr2csc = P.csr2csc; h->hasB = P.hasB; h->qdiagHost = P.qdiag; h->diagRatio.assign(batch, 1.0); h->filled.assign(batch, 0);
     SpBatch& d = h->db;
     d.B = batch; d.n = n; d.m = m; d.nC = nC; d.nComp = nComp; d.N = N; d.Np = ((N + 63) / 64) * 64; d.w = w; d.ld = ld; d.nnzQ = nnzQ; d.nnzE = nnzA; d.G = G; d.kb = kb; d.nU = nU; d.nCb = nCb;
     d.general = general ? 1 : 0;
@@ -2336,6 +2434,7 @@ extern "C" int lcqp_hip_sparse_get_ordering(const lcqp_hip_sparse_t* h, int* per
 // storeSteps: the first 4096 iterates
 extern "C" int lcqp_hip_sparse_set_options(lcqp_hip_sparse_t* h, const lcqp_options_t* opt)
 try {
+    if (h) h->setupValid = false;      // the ADMM weights, sigma and the regularisations of the factors come from the options
     return set_options(g_sp_err, h, opt, 4096);
 }
 catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
@@ -2359,6 +2458,7 @@ try {
     if (first < 0 || count <= 0 || first + count > d.B || !Qx || !Ax) return LCQP_INVALID_ARGUMENT;
     if (!g) return LCQP_INVALID_OBJECTIVE_LINEAR_TERM;
     HIPCHK(g_sp_err, hipSetDevice(h->device));
+    h->setupValid = false;
     std::vector<double> ex(d.nnzE), nvb((size_t)NV_NUM * n), mvb((size_t)MV_NUM * m), lb(nK), rb(nK);
     for (int k = 0; k < count; k++) {
         const size_t b = (size_t)first + k;
@@ -2379,6 +2479,7 @@ try {
         HIPCHK(g_sp_err, hipMemcpy(d.lbL + b * nK, lb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
         HIPCHK(g_sp_err, hipMemcpy(d.lbR + b * nK, rb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
         HIPCHK(g_sp_err, hipMemcpy(d.info + b, &info, sizeof(info), hipMemcpyHostToDevice));
+        h->filled[b] = 1;
     }
     h->loaded = true;
     sp_choose_ordering(h);
@@ -2397,24 +2498,102 @@ try {
 }
 catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 
+// the launches of a run or a re-solve on the handle's stream: the setup (or the refresh) from ev0 to ev1, the homotopy from ev1 to ev2
+static int sp_run(lcqp_hip_sparse* h, bool refresh, int mode, const double* rho0)
+{
+    h->setupValid = false;
+    HIPCHK(g_sp_err, hipEventRecord(h->ev0, h->stream));
+    switch (h->db.G) {
+        case 8: sp_launch<8>(h->db, h->stream, h->ev1, refresh, mode, rho0); break;
+        case 16: sp_launch<16>(h->db, h->stream, h->ev1, refresh, mode, rho0); break;
+        case 32: sp_launch<32>(h->db, h->stream, h->ev1, refresh, mode, rho0); break;
+        default: sp_launch<64>(h->db, h->stream, h->ev1, refresh, mode, rho0); break;
+    }
+    if (!refresh) h->nSetups++;
+    h->nLaunches++;
+    HIPCHK(g_sp_err, hipGetLastError());
+    HIPCHK(g_sp_err, hipEventRecord(h->ev2, h->stream));
+    h->ran = true;
+    h->setupValid = true;
+    return 0;
+}
+
 extern "C" int lcqp_hip_sparse_run(lcqp_hip_sparse_t* h)
 try {
     if (!h || !h->loaded) return LCQP_LCQPOBJECT_NOT_SETUP;
     HIPCHK(g_sp_err, hipSetDevice(h->device));
     sp_choose_ordering(h);
-    HIPCHK(g_sp_err, hipEventRecord(h->ev0, h->stream));
-    switch (h->db.G) {
-        case 8: sp_launch<8>(h->db, h->stream, h->ev1); break;
-        case 16: sp_launch<16>(h->db, h->stream, h->ev1); break;
-        case 32: sp_launch<32>(h->db, h->stream, h->ev1); break;
-        default: sp_launch<64>(h->db, h->stream, h->ev1); break;
+    return sp_run(h, false, 0, nullptr);
+}
+catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
+
+// New vectors for instances [first, first + count) of a batch that holds problems: the argument list of lcqp_hip_sparse_load without the
+// values of the matrices, the same packing, the same meaning of NULL.  The whole range is checked before anything is written, and only
+// NV_G, NV_X0, MV_L, MV_U, MV_Y0, lbL, lbR and hasY0 of those instances are written: the stored solution, the statuses and the factors stay.
+extern "C" int lcqp_hip_sparse_update(lcqp_hip_sparse_t* h, int first, int count, const double* g,
+                                      const double* lbA, const double* ubA, const double* lbL, const double* ubL,
+                                      const double* lbR, const double* ubR, const double* x0, const double* y0)
+try {
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    SpBatch& d = h->db;
+    const int n = d.n, m = d.m, nK = d.nComp;
+    if (first < 0 || count <= 0 || first > d.B - count) return LCQP_INVALID_ARGUMENT;
+    for (int k = 0; k < count; k++) if (!h->filled[(size_t)first + k]) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!g) return LCQP_INVALID_OBJECTIVE_LINEAR_TERM;
+    for (size_t j = 0; j < (size_t)count * nK; j++)
+        if (bnd(lbL, j, 0.0) <= -INFINITY || bnd(lbR, j, 0.0) <= -INFINITY) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
+    HIPCHK(g_sp_err, hipSetDevice(h->device));
+    HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));      // a run in flight reads what is written below
+    static_assert(MV_U == MV_L + 1, "l and u go over in one copy");
+    std::vector<double> lu((size_t)2 * m), lb(nK), rb(nK), x0z(x0 ? 0 : n, 0.0);
+    const int hasY0 = y0 ? 1 : 0;
+    for (int k = 0; k < count; k++) {
+        const size_t b = (size_t)first + k;
+        fill_row_bounds(d, k, lbA, ubA, lbL, ubL, lbR, ubR, lu.data(), lu.data() + m, lb.data(), rb.data());
+        d.hasLbL |= lbL ? 1 : 0; d.hasLbR |= lbR ? 1 : 0;      // switched on, never off (an absent vector is the zero vector)
+        double* nvb = d.nv + b * NV_NUM * n;
+        double* mvb = d.mv + b * MV_NUM * m;
+        HIPCHK(g_sp_err, hipMemcpy(nvb + (size_t)NV_G * n, g + (size_t)k * n, sizeof(double) * n, hipMemcpyHostToDevice));
+        HIPCHK(g_sp_err, hipMemcpy(nvb + (size_t)NV_X0 * n, x0 ? x0 + (size_t)k * n : x0z.data(), sizeof(double) * n, hipMemcpyHostToDevice));
+        HIPCHK(g_sp_err, hipMemcpy(mvb + (size_t)MV_L * m, lu.data(), sizeof(double) * 2 * m, hipMemcpyHostToDevice));
+        if (y0) HIPCHK(g_sp_err, hipMemcpy(mvb + (size_t)MV_Y0 * m, y0 + (size_t)k * m, sizeof(double) * m, hipMemcpyHostToDevice));
+        HIPCHK(g_sp_err, hipMemcpy(d.lbL + b * nK, lb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
+        HIPCHK(g_sp_err, hipMemcpy(d.lbR + b * nK, rb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
+        HIPCHK(g_sp_err, hipMemcpy(&d.info[b].hasY0, &hasY0, sizeof(int), hipMemcpyHostToDevice));
     }
-    HIPCHK(g_sp_err, hipGetLastError());
-    HIPCHK(g_sp_err, hipEventRecord(h->ev2, h->stream));
-    h->ran = true;
     return 0;
 }
 catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
+
+// Solve again on the setup in place: k_sparse_refresh where a run has k_sparse_setup, then the homotopy launch.  Without a setup that
+// belongs to the matrices and options in place this is lcqp_hip_sparse_run.
+extern "C" int lcqp_hip_sparse_resolve(lcqp_hip_sparse_t* h, int mode, const double* rho0)
+try {
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (mode != 0 && mode != 1) { g_sp_err = "resolve: mode is 0 (cold) or 1 (warm)"; return LCQP_INVALID_ARGUMENT; }
+    const int B = h->db.B;
+    if (rho0)
+        for (int b = 0; b < B; b++)
+            if (!(rho0[b] > 0.0) || !std::isfinite(rho0[b])) { g_sp_err = "resolve: rho0[" + std::to_string(b) + "] is not a finite positive number"; return LCQP_INVALID_ARGUMENT; }
+    if (!h->loaded) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!h->setupValid) return lcqp_hip_sparse_run(h);
+    HIPCHK(g_sp_err, hipSetDevice(h->device));
+    const bool withRho = mode == 1 && rho0;
+    if (withRho) {
+        if (!h->rhoStart && !h->mem.alloc(g_sp_err, h->rhoStart, (size_t)B)) { g_sp_err = "device allocation failed: " + g_sp_err; return LCQP_HIP_ERROR; }
+        HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));      // the zero-fill of a fresh buffer, a run in flight that reads an older one
+        HIPCHK(g_sp_err, hipMemcpy(h->rhoStart, rho0, sizeof(double) * (size_t)B, hipMemcpyHostToDevice));
+    }
+    return sp_run(h, true, mode, withRho ? h->rhoStart : nullptr);
+}
+catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
+
+extern "C" int lcqp_hip_sparse_launch_counts(lcqp_hip_sparse_t* h, int out[2])
+{
+    if (!h || !out) return LCQP_INVALID_ARGUMENT;
+    out[0] = h->nSetups; out[1] = h->nLaunches;
+    return 0;
+}
 
 extern "C" int lcqp_hip_sparse_synchronize(lcqp_hip_sparse_t* h)
 try {

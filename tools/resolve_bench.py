@@ -2,7 +2,11 @@
 Per step, from HIP events (last_timing) and the wall clock around update / load + launch + collect:
   (a) load + run as today, (b) update + resolve(cold), (c) update + resolve(warm), with the mean and maximum iterate count of (c).
 Warm-up steps are excluded.  Writes one JSON file.
-    python tools/resolve_bench.py [--batch 1024] [--steps 5] [--warmup 2] [--out profiles/round7/resolve/resolve_bench.json]"""
+    python tools/resolve_bench.py [--batch 1024] [--steps 5] [--warmup 2] [--out profiles/round7/resolve/resolve_bench.json]
+--sparse: the sparse arm instead (lcqpow_amd/synth_sparse.py at --n, default 4096; --batch instances): on ONE handle, per step, run on the
+data in place (the baseline: k_sparse_setup + homotopy), update + resolve(cold) and update + resolve(warm), with last_timing and the
+iterate means of each.
+    python tools/resolve_bench.py --sparse [--batch 4096] [--n 4096] [--steps 3] [--warmup 1] [--out ...]"""
 import argparse
 import json
 import os
@@ -15,13 +19,69 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import lcqpow_amd as la  # noqa: E402
 
 
+def sparse_main(a):
+    from lcqpow_amd import synth_sparse as S
+    B, n = a.batch, a.n
+    nC, nK = n // 2, n // 8
+    Qpat, Apat, qo, eo = S.sparse_pattern_arrays(n, nC, nK)
+    sb = la.SparseBatchLCQP(B, n, nC, nK, Qpat, Apat, opt=la.default_options(perturbStep=0, printLevel=0))
+    g = np.zeros((B, n)); lbA = np.zeros((B, nC)); ubA = np.zeros((B, nC))
+    for c0 in range(0, B, 1024):                              # host staging: 1024 instances are 0.4 GB of values at n = 4096
+        inst = [S.sparse_values(i, n, nC, nK, orders=(qo, eo)) for i in range(c0, min(B, c0 + 1024))]
+        c1 = c0 + len(inst)
+        g[c0:c1] = [d["g"] for d in inst]; lbA[c0:c1] = [d["lbA"] for d in inst]; ubA[c0:c1] = [d["ubA"] for d in inst]
+        assert sb.load(c0, len(inst), np.stack([d["Qx"] for d in inst]), g[c0:c1], np.stack([d["Ex"] for d in inst]), lbA=lbA[c0:c1], ubA=ubA[c0:c1]) == 0
+    rng = np.random.default_rng(0)
+    vec = dict(g=g, lbA=lbA, ubA=ubA)
+    # per step: the warm re-solve first -- it starts from the solution of the data one 2 % move back --, then the two cold solves of the same data
+    kinds = ("update_resolve_warm", "run", "update_resolve_cold")
+    rows = {k: [] for k in kinds}
+    sb.run(); sb.synchronize()
+    for k in range(a.warmup + a.steps):
+        shift = 0.02 * (vec["ubA"] - vec["lbA"]) * rng.standard_normal(vec["lbA"].shape)
+        vec = dict(g=vec["g"] * (1.0 + 0.02 * rng.standard_normal(vec["g"].shape)), lbA=vec["lbA"] + shift, ubA=vec["ubA"] + shift)
+        for kind in kinds:      # run: the same handle, the data the warm step has just put in place (a full setup + a cold homotopy)
+            t0 = time.perf_counter()
+            if kind == "run":
+                sb.run()
+            else:
+                assert sb.update(0, B, vec["g"], lbA=vec["lbA"], ubA=vec["ubA"]) == 0
+                sb.resolve(warm=(kind == "update_resolve_warm"))
+            _, _, st = sb.solution()
+            wall = (time.perf_counter() - t0) * 1e3
+            setup_ms, solve_ms = sb.last_timing()
+            it = [s["iterTotal"] for s in st]
+            if k >= a.warmup:
+                rows[kind].append(dict(wall_ms=wall, setup_ms=setup_ms, solve_ms=solve_ms, iter_mean=float(np.mean(it)), iter_max=int(max(it)),
+                                       solved=int(sum(s["returnValue"] == 0 for s in st))))
+    res = dict(arm="sparse", batch=B, shape=[n, nC, nK], lanes=sb.lanes(), steps=a.steps, warmup=a.warmup)
+    for kind in ("run", "update_resolve_cold", "update_resolve_warm"):
+        r = {key: float(np.mean([q[key] for q in rows[kind]])) for key in ("wall_ms", "setup_ms", "solve_ms", "iter_mean")}
+        r.update(iter_max=max(q["iter_max"] for q in rows[kind]), solved_min=min(q["solved"] for q in rows[kind]), steps=rows[kind])
+        res[kind] = r
+        print(f"{kind:22s} wall {r['wall_ms']:8.1f} ms   setup/refresh {r['setup_ms']:7.3f} ms   homotopy {r['solve_ms']:8.2f} ms   "
+              f"iterates mean {r['iter_mean']:.1f} max {r['iter_max']}   solved >= {r['solved_min']}/{B}")
+    res["launch_counts"] = list(sb.launch_counts())
+    sb.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--sparse", action="store_true", help="the sparse arm: run against resolve(cold) and resolve(warm) on one handle")
+    ap.add_argument("--n", type=int, default=4096, help="--sparse: variables per instance (nC = n / 2, nComp = n / 8)")
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=os.path.join("profiles", "round7", "resolve", "resolve_bench.json"))
     a = ap.parse_args()
+    if a.sparse:
+        res = sparse_main(a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+        print("written", a.out)
+        return
     B, n, nC, nComp = a.batch, 256, 512, 64
     opt = la.default_options(printLevel=0)
     bt = la.BatchLCQP(B, n, nC, nComp, opt=opt)
