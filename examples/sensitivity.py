@@ -1,0 +1,53 @@
+"""Fit the linear terms of 64 small LCQPs so that their solutions match targets: gradient steps through lcqpow_amd.diff.
+
+Each step is one batched solve (update + warm re-solve after the first) and one lcqp_hip_batch_sensitivity call; the loss per step is
+printed.  The targets are solutions of the same LCQPs for other linear terms, so a loss of zero is attainable.
+
+    python examples/sensitivity.py
+"""
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import lcqpow_amd as la  # noqa: E402
+from lcqpow_amd.diff import BatchLCQPLayer  # noqa: E402
+
+B, n, nC, nComp = 64, 24, 12, 6
+
+
+def problem(rng):
+    M = rng.uniform(-1, 1, (n, n)); Q = M.T @ M / n + np.eye(n)
+    L = np.zeros((nComp, n)); R = np.zeros((nComp, n))
+    L[np.arange(nComp), np.arange(nComp)] = 1.0; R[np.arange(nComp), nComp + np.arange(nComp)] = 1.0
+    xs = rng.uniform(0.2, 1, n); xs[nComp:2 * nComp] = 0.0
+    A = rng.uniform(-1, 1, (nC, n)) / np.sqrt(n)
+    return dict(Q=Q, L=L, R=R, A=A, lbA=A @ xs - rng.uniform(0.1, 1, nC), ubA=A @ xs + rng.uniform(0.1, 1, nC), g=rng.uniform(-1, 1, n))
+
+
+def main():
+    if la.device_count() < 1:
+        raise SystemExit("needs a GPU (the product path has no CPU fallback)")
+    rng = np.random.default_rng(0)
+    ds = [problem(rng) for _ in range(B)]
+    st = lambda k: np.stack([d[k] for d in ds])
+    bt = la.BatchLCQP(B, n, nC, nComp, opt=la.default_options(perturbStep=0))
+    assert bt.load(0, B, st("Q"), st("g"), st("L"), st("R"), A=st("A"), lbA=st("lbA"), ubA=st("ubA")) == 0
+    layer = BatchLCQPLayer(bt, bounds=dict(lbA=st("lbA"), ubA=st("ubA")))
+    with torch.no_grad():      # the targets: the solutions for a shifted linear term
+        target = layer(torch.as_tensor(st("g") + 0.3 * rng.standard_normal((B, n))))
+    g = torch.tensor(st("g"), requires_grad=True)
+    opt = torch.optim.SGD([g], lr=0.5)
+    for step in range(12):
+        opt.zero_grad()
+        loss = 0.5 * ((layer(g) - target) ** 2).sum()      # a sum over independent instances: every instance takes its own step
+        loss.backward()
+        opt.step()
+        print("step %2d  mean loss per LCQP %.6e  flagged instances %d" % (step, loss.item() / B, int(np.count_nonzero(layer.info))))
+    bt.close()
+
+
+if __name__ == "__main__":
+    main()

@@ -108,6 +108,9 @@ int  lcqp_hip_qp_solve(lcqp_hip_qp_t* qp, int initialSolve, int* iterations, int
  * x[nV], y[nV + nC]: box duals first, then one dual per stacked row; Qx + g - A'y_A - y_box = 0. */
 void lcqp_hip_qp_get_solution(lcqp_hip_qp_t* qp, double* x, double* y);
 void lcqp_hip_qp_get_counters(lcqp_hip_qp_t* qp, int* admm, int* trials, int* factorizations, int* corrections);
+/* lcqp_hip_batch_sensitivity (below) for the batch of one this object holds: the derivatives of the solution of the convex QP last solved,
+ * dg [nrhs][nV], db and side [.][nV + nC], info [1].  LCQP_LCQPOBJECT_NOT_SETUP before the first successful solve and after set_options. */
+int  lcqp_hip_qp_sensitivity(lcqp_hip_qp_t* qp, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
 /* test and diagnostic entry points: lcqp_hip_batch_read_setup / lcqp_hip_batch_read_working_set (below) for the batch of one this object
  * holds; LCQP_LCQPOBJECT_NOT_SETUP before its first solve */
 int  lcqp_hip_qp_read_setup(lcqp_hip_qp_t* qp, int dims[9], double scal[2], double* C, double* F1, double* D1, double* Et, double* MM,
@@ -177,6 +180,24 @@ int  lcqp_hip_batch_update(lcqp_hip_batch_t* b, int first, int count, const doub
  *   solution, solveZeroPenaltyFirst = false, initialPenaltyParameter = that penalty.  Every other instance runs cold as in mode 0.
  * lcqp_hip_batch_last_timing reports k_refresh as setup_ms. */
 int  lcqp_hip_batch_resolve(lcqp_hip_batch_t* b, int mode, const double* rho0);
+/* Solution sensitivities (DESIGN.md section 3a'): adjoint derivatives of the x the last run / resolve returned with respect to g and to
+ * the bounds its working set W sits on.  For instance i and right-hand side k, v[i][k] = dl/dx is an upstream gradient ([B][nrhs][nV], host);
+ *   dg[i][k]   [nV]                 = dl/dg
+ *   db[i][k]   [nV + nC + 2 nComp]  entry r = dl/d(the bound row r sits on), zero for rows outside W; the reference's dual layout
+ *                                    (box rows first, then A, L, R)
+ *   side[i]    [nV + nC + 2 nComp]  0 outside W, -1 at the lower bound, +1 at the upper bound, 2 equality (both bounds move the row)
+ *   info[i]    0 when x is locally a smooth function of (g, b_W) given by the equality-constrained QP on W; else a sum of
+ *              1  the last run did not return 0, or nothing was solved yet: the outputs of the instance are zero
+ *              2  active rows flagged linearly dependent are not in W: the derivative is the one with those rows dropped
+ *              4  an inequality-type row of W (both rows of a biactive complementarity pair included) has |y_r| <= 1e-9 (1 + |y|_inf)
+ *              8  a complementarity pair has neither side in W
+ * db, side, info may be NULL.  One launch of k_sensitivity on the batch stream behind whatever is queued there; synchronous on return.  The
+ * call reads the state of the batch and changes none of it: a warm resolve after it returns the bits it returns without it.
+ * LCQP_INVALID_ARGUMENT: NULL handle, v or dg, or nrhs < 1.  LCQP_LCQPOBJECT_NOT_SETUP: no run / resolve on this object yet, or a load /
+ * generate_synthetic / set_options since the last one.  LCQP_HIP_ERROR: a HIP call failed (no device). */
+int  lcqp_hip_batch_sensitivity(lcqp_hip_batch_t* b, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
+/* kernel time of the last lcqp_hip_batch_sensitivity launch of this object, ms (HIP events around k_sensitivity, the copies excluded) */
+int  lcqp_hip_batch_sensitivity_timing(lcqp_hip_batch_t* b, float* kernel_ms);
 /* out[0] = full setups, out[1] = homotopy launches this object has issued (host counters) */
 int  lcqp_hip_batch_launch_counts(lcqp_hip_batch_t* b, int out[2]);
 /* Hint of a caller that keeps several batch objects in flight (BatchPipeline): the setup of this object will run beside the homotopy

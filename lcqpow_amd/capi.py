@@ -107,6 +107,9 @@ def lib():
         L.lcqp_hip_batch_read_working_set.argtypes = [C.c_void_p, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p]
         L.lcqp_hip_qp_read_setup.argtypes = [C.c_void_p, c_int_p, c_double_p] + [c_double_p] * 5 + [c_int_p, c_int_p, c_double_p]
         L.lcqp_hip_qp_read_working_set.argtypes = [C.c_void_p, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p]
+        L.lcqp_hip_batch_sensitivity.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
+        L.lcqp_hip_batch_sensitivity_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.lcqp_hip_qp_sensitivity.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_util_symv.argtypes = [C.c_int, C.c_int, C.c_double] + [c_double_p] * 4
         L.lcqp_hip_util_gemv.argtypes = [C.c_int, C.c_int, C.c_int] + [c_double_p] * 3
         L.lcqp_hip_util_gemv_t.argtypes = [C.c_int, C.c_int, C.c_int] + [c_double_p] * 3
@@ -188,6 +191,34 @@ def _read_working_set(call, capS, mE):
     return dict(nT=int(dims[0]), ns=int(dims[1]), slot_row=slot_row, crow=crow, row_slot=row_slot[:mE], Ti=Ti)
 
 
+def _sensitivity(call, v, B, nV, nd):
+    """call(nrhs, v, dg, db, side, info) -> rc.  v: [B][nV] or [B][k][nV]; returns (dg, db, side, info) with dg shaped like v, db
+    [B][nd] or [B][k][nd], side [B][nd] (int32), info [B] (int32)."""
+    v = _arr(v)
+    single = v.ndim == 2
+    if v.ndim not in (2, 3) or v.shape[0] != B or v.shape[-1] != nV or v.size == 0:
+        raise ValueError(f"v: expected [{B}][{nV}] or [{B}][k][{nV}], got shape {v.shape}")
+    k = 1 if single else v.shape[1]
+    dg = np.zeros((B, k, nV)); db = np.zeros((B, k, nd)); side = np.zeros((B, nd), dtype=np.int32); info = np.zeros(B, dtype=np.int32)
+    _check(call(k, _p(v), _p(dg), _p(db), _ip(side), _ip(info)), "sensitivity")
+    return (dg[:, 0], db[:, 0], side, info) if single else (dg, db, side, info)
+
+
+def split_bound_derivatives(db, side, nV, nC, nComp):
+    """db and side of a sensitivity call (the reference's dual layout: box rows first, then A, L, R) as derivatives with respect to the
+    bound vectors of load / update: a dict with dlbA, dubA, dlbL, dubL, dlbR, dubR, dlb, dub, each shaped like its bound with the
+    leading axes of db.  A row at its lower bound (side -1) gives its value to the lower bound's derivative, a row at its upper bound
+    (+1) to the upper bound's.  An EQUALITY row (side 2, lower == upper) moves with either bound, and the ONE value db holds for it appears
+    in both derivatives: it is the derivative along moving both bounds together (the only move that keeps the row an equality), so a
+    caller who ties the two bounds to one parameter must count it once, not add the two entries."""
+    db = np.asarray(db); side = np.asarray(side)
+    sd = side if db.ndim == side.ndim else side[:, None, :]
+    lo = np.where((sd == -1) | (sd == 2), db, 0.0); hi = np.where((sd == 1) | (sd == 2), db, 0.0)
+    a, l, r = nV, nV + nC, nV + nC + nComp
+    return dict(dlb=lo[..., :a], dub=hi[..., :a], dlbA=lo[..., a:l], dubA=hi[..., a:l], dlbL=lo[..., l:r], dubL=hi[..., l:r],
+                dlbR=lo[..., r:], dubR=hi[..., r:])
+
+
 class SubsolverHIP:
     """Python view of the SubsolverBase-shaped QP object (include/SubsolverBase.hpp:28-58)."""
 
@@ -213,6 +244,14 @@ class SubsolverHIP:
         x = np.zeros(self.nV); y = np.zeros(self.nV + self.nC)
         lib().lcqp_hip_qp_get_solution(self.h, _p(x), _p(y))
         return x, y
+
+    def sensitivity(self, v):
+        """lcqp_hip_qp_sensitivity: derivatives of the solution of the QP last solved.  v: [nV] or [k][nV] upstream gradients dl/dx;
+        returns (dg, db, side, info): dl/dg shaped like v, dl/d(bound) [nV + nC] or [k][nV + nC], side [nV + nC], info (int; 0 =
+        differentiable) -- see BatchLCQP.sensitivity."""
+        v = _arr(v)
+        dg, db, side, info = _sensitivity(lambda *a: lib().lcqp_hip_qp_sensitivity(self.h, *a), v[None], 1, self.nV, self.nV + self.nC)
+        return dg[0], db[0], side[0], int(info[0])
 
     def read_setup(self):
         """the constant matrices of the last fresh solve (test and diagnostic entry point; see BatchLCQP.read_setup)"""
@@ -400,6 +439,21 @@ class BatchLCQP:
         start from their last solution, working set and penalty (rho0: [B] starting penalties, each > 0, instead of the last rhoOpt)."""
         r = _sized("rho0", _arr(rho0), self.B)
         _check(lib().lcqp_hip_batch_resolve(self.h, 1 if warm else 0, _p(r)), "resolve")
+
+    def sensitivity(self, v):
+        """lcqp_hip_batch_sensitivity: adjoint derivatives of the x the last run / resolve returned (synchronous; DESIGN.md section 3a').
+        v: upstream gradients dl/dx, [B][nV] or [B][k][nV].  Returns (dg, db, side, info): dg = dl/dg shaped like v; db [B][nd] or
+        [B][k][nd], entry r = dl/d(the bound row r sits on) in the layout of the dual vector (box rows first, then A, L, R), zero for
+        rows outside the working set; side [B][nd]: 0 outside, -1 at lower, +1 at upper, 2 equality (split_bound_derivatives turns db and
+        side into derivatives per bound vector); info [B]: 0 = differentiable, else the flag bits of include/lcqp_hip.h.  The call
+        changes nothing on the device."""
+        return _sensitivity(lambda *a: lib().lcqp_hip_batch_sensitivity(self.h, *a), v, self.B, self.nV, self.nd)
+
+    def sensitivity_kernel_ms(self):
+        """kernel time of the last sensitivity call (HIP events around k_sensitivity)"""
+        ms = C.c_float(0)
+        _check(lib().lcqp_hip_batch_sensitivity_timing(self.h, C.byref(ms)), "sensitivity_timing")
+        return ms.value
 
     def launch_counts(self):
         """(full setups, homotopy launches) this object has issued"""

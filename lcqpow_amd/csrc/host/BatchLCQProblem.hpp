@@ -61,6 +61,13 @@ class BatchLCQProblem {
         return rc != SUCCESSFUL_RETURN ? rc : collect();
     }
     ReturnValue resolveAsync(bool warm, const double* rho0 = 0) { return (ReturnValue)lcqp_hip_batch_resolve(h, warm ? 1 : 0, rho0); }
+    // Solution sensitivities (lcqp_hip_batch_sensitivity): for nrhs upstream gradients v = dl/dx per instance ([batch][nrhs][nV]) the
+    // derivatives dg = dl/dg (same shape) and db = dl/d(bound), side, info ([batch][nrhs][nDuals], [batch][nDuals], [batch]; each may be 0)
+    // of the solutions the last runSolver / resolve returned.  info[i] != 0: instance i is not differentiable by the criteria of the header.
+    ReturnValue getSensitivity(int nrhs, const double* v, double* dg, double* db = 0, int* side = 0, int* info = 0)
+    {
+        return (ReturnValue)lcqp_hip_batch_sensitivity(h, nrhs, v, dg, db, side, info);
+    }
     // full setups and homotopy launches this object has issued
     ReturnValue getLaunchCounts(int& setups, int& launches) const
     {

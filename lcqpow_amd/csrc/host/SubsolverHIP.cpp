@@ -47,4 +47,9 @@ void SubsolverHIP::getSolution(double* x, double* y)
     if (qp) lcqp_hip_qp_get_solution(qp, x, y);
 }
 
+ReturnValue SubsolverHIP::getSensitivity(int nrhs, const double* v, double* dg, double* db, int* side, int* info)
+{
+    return (ReturnValue)lcqp_hip_qp_sensitivity(qp, nrhs, v, dg, db, side, info);
+}
+
 }  // namespace LCQPow

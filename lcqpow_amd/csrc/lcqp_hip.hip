@@ -124,8 +124,17 @@ struct lcqp_hip_batch {
     // (set by run / setup / resolve, cleared by load / generate_synthetic / set_options); which instances hold a problem, and which of
     // their variables carry a finite box bound (those are rows of E, hence of Et and M: an update must keep the set); launches issued
     bool setupValid = false;
+    // the stored point, working set and inverse factor belong to a solve on the data in place (set by run / resolve, cleared with
+    // setupValid): what lcqp_hip_batch_sensitivity differentiates
+    bool solved = false;
     std::vector<char> filled, boxed;      // [B], [B][n]
     double* rhoStart = nullptr;           // [B] on the device: starting penalties of a warm re-solve
+    // lcqp_hip_batch_sensitivity: device buffers for sensRhs right-hand sides per instance (grown on demand; layouts at k_sensitivity) and
+    // the events around its last launch
+    double *sensV = nullptr, *sensDg = nullptr, *sensDb = nullptr;
+    int *sensSide = nullptr, *sensInfo = nullptr;
+    int sensRhs = 0;
+    Event evS0, evS1;
     int nSetups = 0, nLaunches = 0;
     int nch;
     explicit lcqp_hip_batch(int dev) : db(), device(dev) {}
@@ -242,7 +251,7 @@ catch (...) { }   // nothing throws across the C boundary
 // storeSteps: the first 1024 iterates
 extern "C" int lcqp_hip_batch_set_options(lcqp_hip_batch_t* h, const lcqp_options_t* opt)
 try {
-    if (h) h->setupValid = false;      // the scales of the ADMM weights and the proximal shifts of the factors come from the options
+    if (h) h->setupValid = h->solved = false;      // the scales of the ADMM weights and the proximal shifts of the factors come from the options
     return set_options(g_err, h, opt, 1024);
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
@@ -302,7 +311,7 @@ try {
     const size_t infoDbl = (sizeof(InstInfo) + 7) / 8, bidxDbl = ((size_t)np * sizeof(int) + 7) / 8;
     const size_t slotBytes = sizeof(double) * (nQ + nE + nNV + nMV + nY + 2 * nLR + infoDbl + bidxDbl);
     if (int rc = stage_reserve(h, slotBytes)) return rc;
-    h->setupValid = false;
+    h->setupValid = h->solved = false;
     for (int k = 0; k < count; k++) {
         const size_t b = (size_t)first + k;
         StageSlot& slot = h->stage[k & 1];
@@ -368,7 +377,7 @@ try {
     DevBatch& d = h->db;
     if (d.nComp * 2 > d.n) { g_err = "synthetic generator needs 2*nComp <= nV"; return LCQP_INVALID_ARGUMENT; }
     d.hasLbL = d.hasLbR = 0; h->anyLoaded = true;
-    h->setupValid = false;
+    h->setupValid = h->solved = false;
     std::fill(h->filled.begin(), h->filled.end(), 1); std::fill(h->boxed.begin(), h->boxed.end(), 0);      // no box bounds
     dispatch_db(h, ID_k_synth_fill, d.B, nullptr, 0, seed0, firstInstance);
     dispatch_db(h, ID_k_synth_Q, d.B * (d.nblk * (d.nblk + 1) / 2));
@@ -411,7 +420,7 @@ static int launch_setup(lcqp_hip_batch* h)
 {
     const DevBatch& d = h->db;
     hipStream_t on = h->stream;
-    h->setupValid = false;
+    h->setupValid = h->solved = false;
     h->nSetups++;
     const int ntile = d.nblk * (d.nblk + 1) / 2;
     const int nrb = (d.mEcap + 63) / 64, nb = (d.mMld + 127) / 128, nmt = nb * (nb + 1);      // k_build_M: 128 x 64 tiles of the lower triangle
@@ -471,7 +480,7 @@ try {
     h->nLaunches++;
     HIPCHK(g_err, hipGetLastError());
     HIPCHK(g_err, hipEventRecord(h->ev2, h->stream));
-    h->ran = true;
+    h->ran = h->solved = true;
     return 0;
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
@@ -580,7 +589,7 @@ try {
     h->nLaunches++;
     HIPCHK(g_err, hipGetLastError());
     HIPCHK(g_err, hipEventRecord(h->ev2, h->stream));
-    h->ran = true;
+    h->ran = h->solved = true;
     return 0;
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
@@ -710,6 +719,54 @@ try {
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 
+// ---- solution sensitivities (DESIGN.md section 3a'): one launch of k_sensitivity on the batch stream, host buffers in and out ----
+static int batch_sensitivity(lcqp_hip_batch* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
+{
+    DevBatch& d = h->db;
+    HIPCHK(g_err, hipSetDevice(h->device));
+    for (hipError_t e : {h->evS0.status, h->evS1.status}) if (e != hipSuccess) return hip_fail(g_err, "hipEventCreate", e);
+    const size_t B = d.B, n = d.n, np = d.np, nd = d.nd, ldb = (size_t)d.nd + d.capS, K = nrhs;
+    if (nrhs > h->sensRhs) {
+        HIPCHK(g_err, hipStreamSynchronize(h->stream));
+        for (const void* p : {(const void*)h->sensV, (const void*)h->sensDg, (const void*)h->sensDb, (const void*)h->sensSide, (const void*)h->sensInfo}) h->mem.release(p);
+        h->sensV = h->sensDg = h->sensDb = nullptr; h->sensSide = h->sensInfo = nullptr; h->sensRhs = 0;
+        if (!h->mem.alloc(g_err, h->sensV, B * K * n) || !h->mem.alloc(g_err, h->sensDg, B * K * np) || !h->mem.alloc(g_err, h->sensDb, B * K * ldb) ||
+            !h->mem.alloc(g_err, h->sensSide, B * nd) || !h->mem.alloc(g_err, h->sensInfo, B)) return LCQP_HIP_ERROR;
+        h->sensRhs = nrhs;
+    }
+    HIPCHK(g_err, hipMemcpyAsync(h->sensV, v, sizeof(double) * B * K * n, hipMemcpyHostToDevice, h->stream));
+    LaunchArgs a;
+    a.db = d; a.nrhs = nrhs; a.sensV = h->sensV; a.sensDg = h->sensDg; a.sensDb = h->sensDb; a.sensSide = h->sensSide; a.sensInfo = h->sensInfo;
+    HIPCHK(g_err, hipEventRecord(h->evS0, h->stream));
+    lcqp_dispatch(h->nch, ID_k_sensitivity, d.B, h->stream, a);
+    HIPCHK(g_err, hipGetLastError());
+    HIPCHK(g_err, hipEventRecord(h->evS1, h->stream));
+    HIPCHK(g_err, hipMemcpy2DAsync(dg, sizeof(double) * n, h->sensDg, sizeof(double) * np, sizeof(double) * n, B * K, hipMemcpyDeviceToHost, h->stream));
+    if (db) HIPCHK(g_err, hipMemcpy2DAsync(db, sizeof(double) * nd, h->sensDb, sizeof(double) * ldb, sizeof(double) * nd, B * K, hipMemcpyDeviceToHost, h->stream));
+    if (side) HIPCHK(g_err, hipMemcpyAsync(side, h->sensSide, sizeof(int) * B * nd, hipMemcpyDeviceToHost, h->stream));
+    if (info) HIPCHK(g_err, hipMemcpyAsync(info, h->sensInfo, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(g_err, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int lcqp_hip_batch_sensitivity(lcqp_hip_batch_t* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
+try {
+    if (!h || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
+    if (!h->solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return batch_sensitivity(h, nrhs, v, dg, db, side, info);
+}
+catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+
+extern "C" int lcqp_hip_batch_sensitivity_timing(lcqp_hip_batch_t* h, float* kernel_ms)
+try {
+    if (!h || !kernel_ms || !h->sensRhs) return LCQP_INVALID_ARGUMENT;
+    HIPCHK(g_err, hipSetDevice(h->device));
+    HIPCHK(g_err, hipEventSynchronize(h->evS1));
+    HIPCHK(g_err, hipEventElapsedTime(kernel_ms, h->evS0, h->evS1));
+    return 0;
+}
+catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+
 // =================================================================================================
 // QP object (SubsolverBase semantics): a batch of one with nComp = 0 whose rows are the nC stacked rows
 // =================================================================================================
@@ -723,13 +780,14 @@ struct lcqp_hip_qp {
     int device;
     std::vector<double> xsol, ysol;
     int cAdmm, cTrials, cFact, cCorr;
+    bool solved;                       // the last solve returned a solution on the options in place (lcqp_hip_qp_sensitivity)
 };
 
 extern "C" lcqp_hip_qp_t* lcqp_hip_qp_create(int nV, int nC, const double* Q, const double* A, const lcqp_options_t* opt, int device)
 try {
     if (nV <= 0 || nC < 0 || !Q || (nC > 0 && !A)) { g_err = "invalid arguments"; return nullptr; }
     lcqp_hip_qp* q = new lcqp_hip_qp();
-    q->hb = nullptr; q->nV = nV; q->nC = nC; q->device = device; q->haveBounds = false; q->withBox = false;
+    q->hb = nullptr; q->nV = nV; q->nC = nC; q->device = device; q->haveBounds = false; q->withBox = false; q->solved = false;
     q->Q.assign(Q, Q + (size_t)nV * nV);
     if (nC) q->A.assign(A, A + (size_t)nC * nV);
     if (opt) q->opt = *opt; else lcqp_hip_options_default(&q->opt);
@@ -748,6 +806,7 @@ try {
     lcqp_hip_qp* q = new lcqp_hip_qp(*s);
     q->hb = nullptr;
     q->haveBounds = false;
+    q->solved = false;
     return q;
 }
 catch (...) { g_err = "out of host memory"; return nullptr; }   // nothing throws across the C boundary
@@ -765,6 +824,7 @@ try {
     if (!q || !opt) return LCQP_INVALID_ARGUMENT;
     q->opt = *opt;
     q->haveBounds = false;   // forces a fresh setup (rho / sigma / prox weights enter the factorisations)
+    q->solved = false;
     return 0;
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
@@ -787,6 +847,7 @@ try {
     if (!q || !g || !iterations || !exit_flag) return LCQP_INVALID_ARGUMENT;
     const int n = q->nV, nC = q->nC;
     *iterations = 0; *exit_flag = 0;
+    q->solved = false;
     const bool needBox = (lb != nullptr) || (ub != nullptr);
     bool fresh = initialSolve || !q->hb || !q->haveBounds;
     if (!fresh) {
@@ -851,6 +912,7 @@ try {
         hipMemcpy(q->ysol.data(), d.yout, sizeof(double) * ((size_t)n + nC), hipMemcpyDeviceToHost) != hipSuccess) {
         *exit_flag = -1; return LCQP_SUBPROBLEM_SOLVER_ERROR;
     }
+    q->solved = true;
     return LCQP_SUCCESSFUL_RETURN;
 }
 catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
@@ -888,6 +950,15 @@ extern "C" int lcqp_hip_qp_read_working_set(lcqp_hip_qp_t* q, int dims[2], int* 
     if (!q->hb) return LCQP_LCQPOBJECT_NOT_SETUP;
     return lcqp_hip_batch_read_working_set(q->hb, 0, dims, slot_row, crow, row_slot, Ti);
 }
+
+// the derivatives of the convex QP last solved: k_sensitivity on the batch of one (dg [nrhs][nV], db / side [.][nV + nC], info [1])
+extern "C" int lcqp_hip_qp_sensitivity(lcqp_hip_qp_t* q, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
+try {
+    if (!q || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
+    if (!q->hb || !q->solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return batch_sensitivity(q->hb, nrhs, v, dg, db, side, info);
+}
+catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 
 // =================================================================================================
 // building blocks (tests, micro-benchmarks)

@@ -166,6 +166,81 @@ __global__ __launch_bounds__(WG) void k_refresh(DevBatch db, int mode, const dou
     }
 }
 
+// ---- k_sensitivity: adjoint derivatives of the returned x in g and in the bounds of the working set (DESIGN.md section 3a') -------------
+// At the point the last run (or QP solve) returned, x is the minimiser of 1/2 x'Hx + g'x on E_W x = b_W, H = Q + sigma_p I = L1 L1', W the
+// rows in the inverse factor.  For an upstream gradient v:  c = L1^-1 v;  lambda = Ti'Ti (Et_W c);  d = L1^-T (c - Et_W' lambda);
+// dl/dg = -d, dl/db_W = lambda: one full correction of qp_polish with r1 = v, r2 = 0, from the same routines with the same load policy
+// (plain first pass over Et_W, streamed second pass, the triangle of Ti).  The kernel READS the state of the instance and writes only its
+// outputs -- no vector pool, InstInfo, status or factor changes, so that a warm re-solve after it returns what it returns without it.
+//   v [B][nrhs][n];  dg [B][nrhs][np] (the work vector of the solves; -d on return, zero on the padding);
+//   dbo [B][nrhs][nd + capS]: nd derivatives in the reference's dual layout (box first), then capS slot-space scratch (lambda);
+//   side [B][nd]: 0 outside W, -1 at lower, +1 at upper, 2 equality;  sinfo [B]: flag bits (include/lcqp_hip.h), 0 = differentiable.
+template <int NCH>
+__global__ __launch_bounds__(WG) void k_sensitivity(DevBatch db, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo)
+{
+    LCQP_LDS_N(NCH)
+    constexpr int np = 128 * NCH;
+    const int b = blockIdx.x, t = threadIdx.x;
+    Ctx<NCH> c = make_ctx<NCH>(db, b, lds);
+    const int n = db.n, nC = db.nC, nComp = db.nComp, mA = db.mA, nd = db.nd, mE = c.mE;
+    const int ldb = nd + db.capS;
+    const int solved = c.info->haveSolution != 0 && c.info->setupFail == 0 && db.stats[b].returnValue == 0;
+    int* sd = side + (size_t)b * nd;
+    for (int i = t; i < nd; i += WG) sd[i] = 0;
+    if (!solved) {      // (uniform) nothing to differentiate: zero outputs
+        for (int k = 0; k < nrhs; k++) {
+            wg_fill(dg + ((size_t)b * nrhs + k) * np, 0.0, np);
+            wg_fill(dbo + ((size_t)b * nrhs + k) * ldb, 0.0, ldb);
+        }
+        if (t == 0) sinfo[b] = 1;
+        return;
+    }
+    const int nT = uniform_i(c.info->nT), ns = uniform_i(c.info->ns);
+    const int nsp = 64 * ((ns + 63) >> 6);
+    const int *st = c.I(I_ST), *rslot = c.I(I_SLOT), *idx = c.idx, *boxidx = c.boxidx;
+    const double* yq = c.M(M_YQ);
+    auto pos = [&](int r) { return r < mA ? n + r : boxidx[r - mA]; };      // row of E -> entry of the reference's dual vector
+    double ym = 0.0;
+    for (int r = t; r < mE; r += WG) ym = fmax(ym, fabs(yq[r]));
+    const double ytol = 1e-9 * (1.0 + block_max(ym, lds));      // (the barrier inside also orders the zero fill of `side` before the marks below)
+    // a row of L or R at its LOWER bound is a side of its pair; the active side of a pair that is not biactive is an equality of the branch
+    auto sideIn = [&](int r) { return rslot[r] >= 0 && st[r] != ST_UPPER; };
+    int weak = 0, open = 0;
+    for (int r = t; r < mE; r += WG) {
+        if (rslot[r] < 0) continue;
+        const int s = st[r];
+        sd[pos(r)] = (s == ST_EQ) ? 2 : (s == ST_UPPER ? 1 : -1);
+        bool ineq = s != ST_EQ;
+        if (ineq && r >= nC && r < mA && s != ST_UPPER) ineq = sideIn(r < nC + nComp ? r + nComp : r - nComp);
+        if (ineq && fabs(yq[r]) <= ytol) weak = 1;
+    }
+    for (int i = t; i < nComp; i += WG) if (!sideIn(nC + i) && !sideIn(nC + nComp + i)) open = 1;
+    weak = block_or(weak, lds);
+    open = block_or(open, lds);
+    if (t == 0) sinfo[b] = (uniform_i(c.info->ndep) > 0 ? 2 : 0) | (weak ? 4 : 0) | (open ? 8 : 0);
+    for (int k = 0; k < nrhs; k++) {
+        const double* vk = v + ((size_t)b * nrhs + k) * n;
+        double* w = dg + ((size_t)b * nrhs + k) * np;
+        double* out = dbo + ((size_t)b * nrhs + k) * ldb;
+        double* lam = out + nd;
+        for (int i = t; i < np; i += WG) w[i] = (i < n) ? vk[i] : 0.0;
+        for (int i = t; i < nd; i += WG) out[i] = 0.0;
+        __syncthreads();
+        wg_trsv<wg_ncopy(NCH) == 2>(c.F1, np, c.nblk, w, true, lds);
+        if (nT > 0) {
+            wg_rows<NCH, false, true>(c.Et, idx, ns, w, lam, nullptr, lds, [](int, double) {});
+            for (int a = t; a < nsp; a += WG) lam[a] = (a < ns && idx[a] >= 0) ? lam[a] : 0.0;
+            __syncthreads();
+            ti_apply<NCH>(c, lam, lam, nT, ns);
+            wg_rows<NCH>(c.Et, idx, ns, nullptr, nullptr, lam, lds, [&](int i, double s) { w[i] = w[i] - s; });
+        }
+        wg_trsv<wg_ncopy(NCH) == 2>(c.F1, np, c.nblk, w, false, lds);
+        for (int i = t; i < np; i += WG) w[i] = (i < n) ? -w[i] : 0.0;
+        for (int a = t; a < ns; a += WG) { const int r = idx[a]; if (r >= 0) out[pos(r)] = lam[a]; }
+        __syncthreads();
+    }
+}
+
 // ---- k_build_C: C = L'R + R'L (Utilities::MatrixSymmetrizationProduct, src/Utilities.cpp:104-116) ----
 // One 64 x 64 tile of the lower triangle per workgroup.  Both products advance in the same loop (four panels of 16 rows of L and R per step:
 // half the steps, barriers and exposed loads of two products one after the other), and the mirrored tile goes through LDS so that its rows
@@ -839,6 +914,7 @@ static void launch_impl(int kid, int grid, hipStream_t s, const LaunchArgs& a)
     switch (kid) {
         case ID_k_prepare:    hipLaunchKernelGGL((k_prepare<NCH>), dim3(grid), dim3(WG), 0, s, a.db); break;
         case ID_k_refresh:    hipLaunchKernelGGL((k_refresh<NCH>), dim3(grid), dim3(WG), 0, s, a.db, a.mode, a.rho0); break;
+        case ID_k_sensitivity: hipLaunchKernelGGL((k_sensitivity<NCH>), dim3(grid), dim3(WG), 0, s, a.db, a.nrhs, a.sensV, a.sensDg, a.sensDb, a.sensSide, a.sensInfo); break;
         case ID_k_build_C:    hipLaunchKernelGGL((k_build_C<NCH>), dim3(grid), dim3(WG), 0, s, a.db); break;
         case ID_k_compress_C: hipLaunchKernelGGL((k_compress_C<NCH>), dim3(grid), dim3(WG), 0, s, a.db); break;
         case ID_k_factor:     hipLaunchKernelGGL((k_factor<NCH, 1>), dim3(grid), dim3(WG), 0, s, a.db); break;

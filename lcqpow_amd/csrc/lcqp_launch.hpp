@@ -6,7 +6,7 @@
 namespace lcqp {
 
 enum KernelId { ID_k_prepare, ID_k_build_C, ID_k_compress_C, ID_k_factor, ID_k_factor_full, ID_k_trsm, ID_k_trsm_streamed, ID_k_build_M, ID_k_lcqp_run, ID_k_qp_solve,
-                ID_k_synth_fill, ID_k_synth_Q, ID_k_util_symv, ID_k_util_rows, ID_k_util_rows_list, ID_k_refresh };
+                ID_k_synth_fill, ID_k_synth_Q, ID_k_util_symv, ID_k_util_rows, ID_k_util_rows_list, ID_k_refresh, ID_k_sensitivity };
 
 struct LaunchArgs {
     DevBatch db;
@@ -15,6 +15,11 @@ struct LaunchArgs {
     uint64_t seed0 = 0, first = 0;
     int mode = 0;                       // k_refresh: 0 every instance cold, 1 warm where the last run succeeded
     const double* rho0 = nullptr;       // k_refresh: [B] starting penalties of the warm instances (device), or null
+    // k_sensitivity (device buffers; layouts at the kernel)
+    int nrhs = 0;
+    const double* sensV = nullptr;
+    double *sensDg = nullptr, *sensDb = nullptr;
+    int *sensSide = nullptr, *sensInfo = nullptr;
     // building-block kernels
     int n = 0, m = 0;
     double alpha = 0.0;

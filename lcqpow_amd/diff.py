@@ -1,0 +1,93 @@
+"""Differentiable batched LCQP solves for torch: x*(g, lbA, ubA) with gradients from lcqp_hip_batch_sensitivity (DESIGN.md section 3a').
+
+The solve and its derivative run on the HIP path of :mod:`lcqpow_amd.capi`; there is no CPU fallback -- without the built library, or
+without a device, using the layer raises.  Tensors are copied to the host and back around the C ABI (host pointers): plumbing, not a
+hot path.
+
+    bt = BatchLCQP(B, nV, nC, nComp, opt=...); bt.load(0, B, Q, g0, L, R, A=A, lbA=lbA, ubA=ubA)
+    layer = BatchLCQPLayer(bt, bounds=dict(lbA=lbA, ubA=ubA))
+    x = layer(g)                      # [B][nV], on g's device; update + run the first time, update + resolve(warm) afterwards
+    loss(x).backward()                # g.grad = dl/dg through the working set the solve ended on
+"""
+import warnings
+
+import numpy as np
+import torch
+
+from . import capi
+
+BOUND_KEYS = ("lbL", "ubL", "lbR", "ubR", "lbA", "ubA", "lb", "ub")
+
+
+def _host(t):
+    return None if t is None else np.ascontiguousarray(t.detach().cpu().to(torch.float64).numpy())
+
+
+class LCQPSolveFunction(torch.autograd.Function):
+    """forward(layer, g, lbA, ubA) -> x: lcqp_hip_batch_update with the layer's other vectors, then run (first call) or resolve(warm).
+    backward: one lcqp_hip_batch_sensitivity call; gradients for g and, where they were given as tensors, lbA and ubA.
+
+    The derivative is the one of the equality-constrained QP on the working set the solve ended on.  Instances the library flags
+    (info != 0: a failed solve -- zero gradient --, dropped dependent rows, a vanishing multiplier, an open complementarity pair) still get
+    what the kernel computed, together with ONE warning per backward call that counts them; nothing is zeroed silently.
+    A row with lbA == ubA has one derivative for both bounds: when both are tensor inputs each receives half of it, so that bounds tied
+    to one parameter (the only move that keeps the row an equality) sum to the value; a single tensor input receives all of it."""
+
+    @staticmethod
+    def forward(ctx, layer, g, lbA=None, ubA=None):
+        bt = layer.bt
+        kw = dict(layer.bounds)
+        if lbA is not None: kw["lbA"] = _host(lbA)
+        if ubA is not None: kw["ubA"] = _host(ubA)
+        rc = bt.update(0, bt.B, _host(g), **kw)
+        if rc != 0:
+            raise RuntimeError(f"lcqp_hip_batch_update failed with code {rc}: {capi.last_error()}")
+        if layer.solves == 0:
+            bt.run()
+        else:
+            bt.resolve(warm=layer.warm)
+        x, y, st = bt.solution()
+        layer.solves += 1
+        layer.y, layer.stats = y, st
+        ctx.layer, ctx.serial = layer, layer.solves
+        ctx.given = (lbA is not None, ubA is not None)
+        return torch.as_tensor(x, dtype=g.dtype, device=g.device)
+
+    @staticmethod
+    def backward(ctx, grad_x):
+        layer = ctx.layer
+        if ctx.serial != layer.solves:
+            raise RuntimeError("backward through a solve that is not the layer's last one: the batch object holds the state of one solve")
+        bt = layer.bt
+        dg, db, side, info = bt.sensitivity(_host(grad_x))
+        layer.info = info
+        bad = int(np.count_nonzero(info))
+        if bad:
+            warnings.warn(f"LCQPSolveFunction.backward: {bad} of {bt.B} instances are not differentiable by the library's criteria "
+                          f"(info bits present: {int(np.bitwise_or.reduce(info))}); their gradients are the kernel's output as it is",
+                          RuntimeWarning, stacklevel=2)
+        out = lambda a: torch.as_tensor(a, dtype=grad_x.dtype, device=grad_x.device)
+        parts = capi.split_bound_derivatives(db, side, bt.nV, bt.nC, bt.nComp)
+        eq = side[:, bt.nV:bt.nV + bt.nC] == 2
+        share = np.where(eq, 0.5, 1.0) if all(ctx.given) else 1.0
+        glb = out(parts["dlbA"] * share) if ctx.given[0] else None
+        gub = out(parts["dubA"] * share) if ctx.given[1] else None
+        return None, out(dg), glb, gub
+
+
+class BatchLCQPLayer:
+    """A loaded BatchLCQP as a torch layer.  bounds: the bound vectors the batch was loaded with ([B][...] arrays under the names of
+    BatchLCQP.update: lbL, ubL, lbR, ubR, lbA, ubA, lb, ub) -- an update replaces EVERY vector, so the ones that are not inputs of the
+    layer are handed over again with every solve.  warm: re-solves start from the last solution where it exists."""
+
+    def __init__(self, batch, bounds=None, warm=True):
+        capi.lib()      # raises when the HIP library is not built: no CPU fallback
+        unknown = set(bounds or ()) - set(BOUND_KEYS)
+        if unknown:
+            raise ValueError(f"bounds: unknown keys {sorted(unknown)}")
+        self.bt, self.warm, self.solves = batch, warm, 0
+        self.bounds = {k: capi._arr(v) for k, v in (bounds or {}).items() if v is not None}
+        self.y = self.stats = self.info = None
+
+    def __call__(self, g, lbA=None, ubA=None):
+        return LCQPSolveFunction.apply(self, g, lbA, ubA)
