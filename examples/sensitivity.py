@@ -4,6 +4,7 @@ Each step is one batched solve (update + warm re-solve after the first) and one 
 printed.  The targets are solutions of the same LCQPs for other linear terms, so a loss of zero is attainable.
 
     python examples/sensitivity.py
+    python examples/sensitivity.py sparse      # the same fit on the sparse arm: 16 banded LCQPs (n = 64), lcqp_hip_sparse_sensitivity
 """
 import os
 import sys
@@ -13,7 +14,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import lcqpow_amd as la  # noqa: E402
-from lcqpow_amd.diff import BatchLCQPLayer  # noqa: E402
+from lcqpow_amd.diff import BatchLCQPLayer, SparseBatchLCQPLayer  # noqa: E402
 
 B, n, nC, nComp = 64, 24, 12, 6
 
@@ -27,25 +28,42 @@ def problem(rng):
     return dict(Q=Q, L=L, R=R, A=A, lbA=A @ xs - rng.uniform(0.1, 1, nC), ubA=A @ xs + rng.uniform(0.1, 1, nC), g=rng.uniform(-1, 1, n))
 
 
-def main():
-    if la.device_count() < 1:
-        raise SystemExit("needs a GPU (the product path has no CPU fallback)")
-    rng = np.random.default_rng(0)
-    ds = [problem(rng) for _ in range(B)]
-    st = lambda k: np.stack([d[k] for d in ds])
-    bt = la.BatchLCQP(B, n, nC, nComp, opt=la.default_options(perturbStep=0))
-    assert bt.load(0, B, st("Q"), st("g"), st("L"), st("R"), A=st("A"), lbA=st("lbA"), ubA=st("ubA")) == 0
-    layer = BatchLCQPLayer(bt, bounds=dict(lbA=st("lbA"), ubA=st("ubA")))
+def fit(layer, g0, rng, batch):
     with torch.no_grad():      # the targets: the solutions for a shifted linear term
-        target = layer(torch.as_tensor(st("g") + 0.3 * rng.standard_normal((B, n))))
-    g = torch.tensor(st("g"), requires_grad=True)
+        target = layer(torch.as_tensor(g0 + 0.3 * rng.standard_normal(g0.shape)))
+    g = torch.tensor(g0, requires_grad=True)
     opt = torch.optim.SGD([g], lr=0.5)
     for step in range(12):
         opt.zero_grad()
         loss = 0.5 * ((layer(g) - target) ** 2).sum()      # a sum over independent instances: every instance takes its own step
         loss.backward()
         opt.step()
-        print("step %2d  mean loss per LCQP %.6e  flagged instances %d" % (step, loss.item() / B, int(np.count_nonzero(layer.info))))
+        print("step %2d  mean loss per LCQP %.6e  flagged instances %d" % (step, loss.item() / batch, int(np.count_nonzero(layer.info))))
+
+
+def sparse_main():
+    from lcqpow_amd import synth_sparse as S
+    Bs, ns, nCs, nKs = 16, 64, 32, 8
+    Qpat, Apat, qo, eo = S.sparse_pattern_arrays(ns, nCs, nKs)
+    inst = [S.sparse_values(i, ns, nCs, nKs, orders=(qo, eo)) for i in range(Bs)]
+    st = lambda k: np.stack([d[k] for d in inst])
+    sb = la.SparseBatchLCQP(Bs, ns, nCs, nKs, Qpat, Apat, opt=la.default_options(perturbStep=0))
+    assert sb.load(0, Bs, st("Qx"), st("g"), st("Ex"), lbA=st("lbA"), ubA=st("ubA")) == 0
+    fit(SparseBatchLCQPLayer(sb, bounds=dict(lbA=st("lbA"), ubA=st("ubA"))), st("g"), np.random.default_rng(0), Bs)
+    sb.close()
+
+
+def main():
+    if la.device_count() < 1:
+        raise SystemExit("needs a GPU (the product path has no CPU fallback)")
+    if sys.argv[1:] == ["sparse"]:
+        return sparse_main()
+    rng = np.random.default_rng(0)
+    ds = [problem(rng) for _ in range(B)]
+    st = lambda k: np.stack([d[k] for d in ds])
+    bt = la.BatchLCQP(B, n, nC, nComp, opt=la.default_options(perturbStep=0))
+    assert bt.load(0, B, st("Q"), st("g"), st("L"), st("R"), A=st("A"), lbA=st("lbA"), ubA=st("ubA")) == 0
+    fit(BatchLCQPLayer(bt, bounds=dict(lbA=st("lbA"), ubA=st("ubA"))), st("g"), rng, B)
     bt.close()
 
 

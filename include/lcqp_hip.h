@@ -326,6 +326,27 @@ int  lcqp_hip_sparse_update(lcqp_hip_sparse_t* s, int first, int count, const do
                             const double* lbR, const double* ubR, const double* x0, const double* y0);
 int  lcqp_hip_sparse_resolve(lcqp_hip_sparse_t* s, int mode, const double* rho0);
 int  lcqp_hip_sparse_launch_counts(lcqp_hip_sparse_t* s, int out[2]);   /* full setups, homotopy launches */
+/* Solution sensitivities of the sparse batch (DESIGN.md section 3a''; the twin of lcqp_hip_batch_sensitivity in this arm's conventions: no
+ * box rows, m = nC + 2 nComp rows [A; L; R]): adjoint derivatives of the x the last run / resolve returned with respect to g and to the
+ * bounds its stored working set W sits on.  For instance i and right-hand side k, v[i][k] = dl/dx is an upstream gradient
+ * ([B][nrhs][nV], host);
+ *   dg[i][k]   [nV]   = dl/dg
+ *   db[i][k]   [m]    entry r = dl/d(the bound row r sits on), zero for rows outside W -- the derivative with respect to the bound as
+ *                     the caller hands it to load / update, whatever the sign of this arm's duals
+ *   side[i]    [m]    0 outside W, -1 at the lower bound, +1 at the upper bound, 2 equality (both bounds move the row)
+ *   info[i]    0 when x is locally a smooth function of (g, b_W) given by the equality-constrained QP on W; else a sum of
+ *              1  the last run did not return 0, or nothing was solved yet: the outputs of the instance are zero
+ *              2  the refinement against [Q, E_W'; E_W, 0] did not reach its rounding floor: that matrix is singular or too ill-conditioned
+ *                 (dependent rows in W, or a semidefinite Q with a null direction on W); the outputs are those of the regularised system
+ *              4  an inequality-type row of W (both rows of a biactive complementarity pair included) has |y_r| <= 1e-9 (1 + |y|_inf)
+ *              8  a complementarity pair has neither side in W
+ * db, side, info may be NULL.  One launch of k_sparse_sensitivity on the handle's stream behind whatever is queued there; synchronous on
+ * return.  The call reads the state of the batch: a cold or warm resolve after it returns the bits it returns without it.
+ * LCQP_INVALID_ARGUMENT: NULL handle, v or dg, or nrhs < 1.  LCQP_LCQPOBJECT_NOT_SETUP: no run / resolve on this handle yet, or a load /
+ * set_options since the last one (the mark of lcqp_hip_sparse_resolve).  LCQP_HIP_ERROR: a HIP call failed. */
+int  lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* s, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
+/* kernel time of the last lcqp_hip_sparse_sensitivity launch of this handle, ms (HIP events around k_sparse_sensitivity, the copies excluded) */
+int  lcqp_hip_sparse_sensitivity_timing(lcqp_hip_sparse_t* s, float* kernel_ms);
 int  lcqp_hip_sparse_synchronize(lcqp_hip_sparse_t* s);
 int  lcqp_hip_sparse_last_timing(lcqp_hip_sparse_t* s, float* setup_ms, float* solve_ms);
 int  lcqp_hip_sparse_get_solution(lcqp_hip_sparse_t* s, double* x, double* y, lcqp_stats_t* stats);   /* y: [B][nC + 2 nComp] */

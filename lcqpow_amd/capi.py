@@ -123,6 +123,8 @@ def lib():
         L.lcqp_hip_sparse_update.argtypes = [C.c_void_p, C.c_int, C.c_int] + [c_double_p] * 9
         L.lcqp_hip_sparse_resolve.argtypes = [C.c_void_p, C.c_int, c_double_p]
         L.lcqp_hip_sparse_launch_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
+        L.lcqp_hip_sparse_sensitivity.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
+        L.lcqp_hip_sparse_sensitivity_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         _lib = L
     return _lib
 
@@ -204,8 +206,9 @@ def _sensitivity(call, v, B, nV, nd):
     return (dg[:, 0], db[:, 0], side, info) if single else (dg, db, side, info)
 
 
-def split_bound_derivatives(db, side, nV, nC, nComp):
-    """db and side of a sensitivity call (the reference's dual layout: box rows first, then A, L, R) as derivatives with respect to the
+def split_bound_derivatives(db, side, nV, nC, nComp, sparse=False):
+    """db and side of a sensitivity call (the reference's dual layout: box rows first, then A, L, R; sparse=True: the layout of
+    SparseBatchLCQP.sensitivity, which has no box rows -- dlb and dub are then empty) as derivatives with respect to the
     bound vectors of load / update: a dict with dlbA, dubA, dlbL, dubL, dlbR, dubR, dlb, dub, each shaped like its bound with the
     leading axes of db.  A row at its lower bound (side -1) gives its value to the lower bound's derivative, a row at its upper bound
     (+1) to the upper bound's.  An EQUALITY row (side 2, lower == upper) moves with either bound, and the ONE value db holds for it appears
@@ -214,7 +217,8 @@ def split_bound_derivatives(db, side, nV, nC, nComp):
     db = np.asarray(db); side = np.asarray(side)
     sd = side if db.ndim == side.ndim else side[:, None, :]
     lo = np.where((sd == -1) | (sd == 2), db, 0.0); hi = np.where((sd == 1) | (sd == 2), db, 0.0)
-    a, l, r = nV, nV + nC, nV + nC + nComp
+    a = 0 if sparse else nV
+    l, r = a + nC, a + nC + nComp
     return dict(dlb=lo[..., :a], dub=hi[..., :a], dlbA=lo[..., a:l], dubA=hi[..., a:l], dlbL=lo[..., l:r], dubL=hi[..., l:r],
                 dlbR=lo[..., r:], dubR=hi[..., r:])
 
@@ -713,6 +717,24 @@ class SparseBatchLCQP:
         out = (C.c_int * 2)()
         self._chk(lib().lcqp_hip_sparse_launch_counts(self.h, out), "launch_counts")
         return out[0], out[1]
+
+    def sensitivity(self, v):
+        """lcqp_hip_sparse_sensitivity: adjoint derivatives of the x the last run / resolve returned (synchronous; DESIGN.md section 3a'').
+        v: [B][nV] or [B][k][nV] upstream gradients dl/dx.  Returns (dg, db, side, info): dg = dl/dg shaped like v; db [B][m] or
+        [B][k][m], m = nC + 2 nComp (rows A, L, R): dl/d(the bound each row of the working set sits on), zero outside it; side [B][m]:
+        0 outside, -1 at lower, +1 at upper, 2 equality (split_bound_derivatives(..., sparse=True) turns db and side into derivatives
+        per bound vector); info [B]: 0 = differentiable, else the flag bits of include/lcqp_hip.h."""
+        def call(*a):
+            rc = lib().lcqp_hip_sparse_sensitivity(self.h, *a)
+            self._chk(rc, "sensitivity")
+            return rc
+        return _sensitivity(call, v, self.B, self.nV, self.m)
+
+    def sensitivity_kernel_ms(self):
+        """kernel time of the last sensitivity call (HIP events around k_sparse_sensitivity)"""
+        ms = C.c_float(0)
+        self._chk(lib().lcqp_hip_sparse_sensitivity_timing(self.h, C.byref(ms)), "sensitivity_timing")
+        return ms.value
 
     def synchronize(self):
         self._chk(lib().lcqp_hip_sparse_synchronize(self.h), "synchronize")

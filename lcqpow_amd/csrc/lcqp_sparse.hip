@@ -1991,6 +1991,109 @@ __global__ __launch_bounds__(WGS) void k_sparse_refresh(SpBatch db, int mode, co
     if (t == 0) c.info->bytes = c.bytes;
 }
 
+// ---- k_sparse_sensitivity: adjoint derivatives of the returned x in g and in the bounds of the stored working set (DESIGN.md 3a'') ----------
+// At the point the last run returned, x is the minimiser of 1/2 x'Qx + g'x on E_W x = b_W, W the stored working set (MI_ST).  For an upstream
+// gradient v:  K0 [d; lambda] = [v; 0],  K0 = [Q, E_W'; E_W, 0];  dl/dg = -d,  dl/db_W = lambda.  The polish factor in memory is the LDL' of
+// [Q + delta I, E_W'; E_W, -delta2 I] for exactly this set: an instance leaves its last QP through a trial that changed nothing behind a
+// correction whose factor matched MI_STT (sp_ph_trial / sp_ph_factor), sp_ph_qpend copies MI_STT to MI_ST, and nothing factorises after it.
+// Which of the two regularisation levels it holds does not matter here: it only preconditions the refinement against the UNREGULARISED
+// K0 -- residual [v - Q d - E_W'lambda; -E_W d] from the ELL products, correction through the same factor -- that runs until the residual
+// is under its own rounding floor, 64 eps max_i(sum of |terms|_i), at most SENS_REFINE_MAX times (contraction delta |K0^-1| per step).
+// G lanes per instance, as k_sparse_refresh; per instance a loop over the nrhs vectors.  The kernel READS the state of the instance; it
+// writes its outputs and four buffers that every phase of a run overwrites before it reads them: the solve vector (SpBatch::Nv), NV_PK (d),
+// NV_QP (Q d) and MV_LX (lambda).
+//   v, dg [B][nrhs][n];  dbo [B][nrhs][m];  side [B][m]: 0 outside W, -1 at lower, +1 at upper, 2 equality;  sinfo [B]: flag bits
+//   (include/lcqp_hip.h), 0 = differentiable.
+constexpr int SENS_REFINE_MAX = 4;
+template <int G>
+__global__ __launch_bounds__(WGS) void k_sparse_sensitivity(SpBatch db, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo)
+{
+    const int b = blockIdx.x * (64 / G) + threadIdx.x / G;
+    if (b >= db.B) return;
+    SpCtx<G> c = sp_ctx<G>(db, b, blockIdx.x * (64 / G), (int)threadIdx.x);
+    const int t = c.gl, n = db.n, m = db.m, nC = db.nC, nK = db.nComp;
+    int* sd = side + (size_t)b * m;
+    const int solved = c.info->haveSolution != 0 && db.stats[b].returnValue == 0;
+    if (!solved) {      // (uniform inside the group) nothing to differentiate: zero outputs
+        for (int r = t; r < m; r += G) sd[r] = 0;
+        for (int k = 0; k < nrhs; k++) {
+            double* og = dg + ((size_t)b * nrhs + k) * n;
+            double* ob = dbo + ((size_t)b * nrhs + k) * m;
+            for (int i = t; i < n; i += G) og[i] = 0.0;
+            for (int r = t; r < m; r += G) ob[r] = 0.0;
+        }
+        if (t == 0) sinfo[b] = 1;
+        return;
+    }
+    GI st = c.I(MI_ST);
+    GD yq = c.M(MV_YQ);
+    const int* iperm = db.iperm;
+    // flags, as on the dense path (k_sensitivity): a row of L or R at its lower bound is a side of its pair; the active side of a pair that
+    // is not biactive is an equality of the branch and needs no multiplier
+    double ym = 0.0;
+    for (int r = t; r < m; r += G) ym = fmax(ym, fabs(yq[r]));
+    const double ytol = 1e-9 * (1.0 + g_max<G>(ym));
+    auto sideIn = [&](int r) { const int s = st[r]; return s != ST_INACT && s != ST_UPPER; };
+    int weak = 0, open = 0;
+    for (int r = t; r < m; r += G) {
+        const int s = st[r];
+        sd[r] = (s == ST_INACT) ? 0 : ((s == ST_EQ) ? 2 : (s == ST_UPPER ? 1 : -1));
+        if (s == ST_INACT) continue;
+        bool ineq = s != ST_EQ;
+        if (ineq && r >= nC && s != ST_UPPER) ineq = sideIn(r < nC + nK ? r + nK : r - nK);
+        if (ineq && fabs(yq[r]) <= ytol) weak = 1;
+    }
+    for (int i = t; i < nK; i += G) if (!sideIn(nC + i) && !sideIn(nC + nK + i)) open = 1;
+    weak = g_any<G>(weak) ? 1 : 0;
+    open = g_any<G>(open) ? 1 : 0;
+    GD d = c.V(NV_PK), qd = c.V(NV_QP), lam = c.M(MV_LX), bv = c.Nv();
+    const double e1 = c.info->e1max;
+    int stalled = 0;
+    for (int k = 0; k < nrhs; k++) {
+        const double* vk = v + ((size_t)b * nrhs + k) * n;
+        double* og = dg + ((size_t)b * nrhs + k) * n;
+        double* ob = dbo + ((size_t)b * nrhs + k) * m;
+        g_map<G, 8>(n, t, [&](int i) { return ID{iperm[i], vk[i]}; }, [&](int i, ID w) { bv[w.i] = w.a; d[i] = 0.0; });
+        g_map<G, 8>(m, t, [&](int r) { return iperm[n + r]; }, [&](int r, int p) { bv[p] = 0.0; lam[r] = 0.0; });
+        g_sync();
+        for (int it = 0;; it++) {
+            sp_solve<G>(c, false, bv);
+            double dm = 0.0;
+            g_map<G, 8>(n, t, [&](int i) { return D2{bv[iperm[i]], d[i]}; }, [&](int i, D2 w) { const double dn = w.b + w.a; d[i] = dn; dm = fmax(dm, fabs(dn)); });
+            g_map<G, 8>(m, t, [&](int r) { return ID2{st[r], bv[iperm[n + r]], lam[r]}; }, [&](int r, ID2 w) { lam[r] = (w.s != ST_INACT) ? w.y + w.v : 0.0; });
+            g_sync();
+            if (it == 0) {      // the answer of the regularised system: what stays when the refinement does not reach its floor
+                g_map<G, 8>(n, t, [&](int i) { return (double)d[i]; }, [&](int i, double w) { og[i] = -w; });
+                g_map<G, 8>(m, t, [&](int r) { return (double)lam[r]; }, [&](int r, double w) { ob[r] = w; });
+            }
+            // the residual against K0, straight into the solve vector: [v - Q d - E_W'lambda; -E_W d]
+            SPROF(c, SP_VECTORS);
+            sp_ell<G, false>(db.ellQ, c.gl, c.Qx(), [&](int j) { return D2{d[j], 0.0}; }, [](int) { return NoPre{}; }, [&](int i, double s, double, NoPre) { qd[i] = s; });
+            g_sync();
+            double mx = 0.0, sc = 0.0;
+            sp_ell<G, true>(db.ellT, c.gl, c.Ex(), [&](int r) { return D2{(st[r] != ST_INACT) ? (double)lam[r] : 0.0, 0.0}; },
+                            [&](int i) { return ID2{iperm[i], vk[i], qd[i]}; },
+                            [&](int, double s, double, ID2 w) { const double rv = (w.v - w.y) - s; bv[w.s] = rv; mx = nmax(mx, fabs(rv)); sc = fmax(sc, fabs(w.v) + fabs(w.y) + fabs(s)); });
+            sp_ell<G, false>(db.ellE, c.gl, c.Ex(), [&](int j) { return D2{d[j], 0.0}; }, [&](int r) { return I2{st[r], iperm[n + r]}; },
+                             [&](int, double s, double, I2 w) { const double rv = (w.a != ST_INACT) ? -s : 0.0; bv[w.b] = rv; mx = nmax(mx, fabs(rv)); });
+            g_sync();
+            SPROF(c, SP_PRODUCTS);
+            const double res = g_max<G>(mx), scale = fmax(g_max<G>(sc), e1 * g_max<G>(dm));
+            const bool conv = res <= 64.0 * 2.221e-16 * scale;      // (a NaN does not pass)
+            if (conv || it == SENS_REFINE_MAX) {
+                if (!conv) stalled = 1;
+                if (conv && it > 0) {
+                    g_map<G, 8>(n, t, [&](int i) { return (double)d[i]; }, [&](int i, double w) { og[i] = -w; });
+                    g_map<G, 8>(m, t, [&](int r) { return (double)lam[r]; }, [&](int r, double w) { ob[r] = w; });
+                }
+                break;
+            }
+        }
+        g_sync();
+    }
+    if (t == 0) sinfo[b] = (stalled ? 2 : 0) | (weak ? 4 : 0) | (open ? 8 : 0);
+}
+
 // ---- the scheduler: persistent wavefronts that serve the phase queues of their pool -------------------------------------------------------
 // Queue discipline (per pool and phase): push = take a position (atomicAdd on tail), wait until its slot's sequence says "free for this
 // position" (at once, unless the ring has been lapped), store (position + 1, instance id) into it, atomicAdd on count; pop = claim entries of
@@ -2272,6 +2375,12 @@ struct lcqp_hip_sparse {
     bool setupValid = false;
     int nSetups = 0, nLaunches = 0;      // full setups (k_sparse_setup) and homotopy launches issued: lcqp_hip_sparse_launch_counts
     double* rhoStart = nullptr;          // [B] starting penalties of a warm re-solve (allocated by the first resolve that carries them)
+    // lcqp_hip_sparse_sensitivity: device buffers for sensRhs right-hand sides per instance (grown on demand; layouts at k_sparse_sensitivity)
+    // and the events around its last launch
+    double *sensV = nullptr, *sensDg = nullptr, *sensDb = nullptr;
+    int *sensSide = nullptr, *sensInfo = nullptr;
+    int sensRhs = 0;
+    Event evS0, evS1;
     explicit lcqp_hip_sparse(int dev) : db(), device(dev) {}
     ~lcqp_hip_sparse() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
 };
@@ -2594,6 +2703,61 @@ extern "C" int lcqp_hip_sparse_launch_counts(lcqp_hip_sparse_t* h, int out[2])
     out[0] = h->nSetups; out[1] = h->nLaunches;
     return 0;
 }
+
+// ---- solution sensitivities (DESIGN.md section 3a''): one launch of k_sparse_sensitivity on the handle's stream, host buffers in and out ----
+template <int G>
+static void sp_launch_sensitivity(const lcqp_hip_sparse* h, int nrhs)
+{
+    const SpBatch& db = h->db;
+    const int ipw = 64 / G, grid = (db.B + ipw - 1) / ipw;
+    const size_t ldsBytes = (G == 64 && db.general) ? sizeof(double) * (size_t)(G * G + 16 * G) : 0;      // the window of the general solve
+    hipLaunchKernelGGL(k_sparse_sensitivity<G>, dim3(grid), dim3(WGS), ldsBytes, h->stream, db, nrhs, h->sensV, h->sensDg, h->sensDb, h->sensSide, h->sensInfo);
+}
+
+extern "C" int lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
+try {
+    if (!h || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
+    if (!h->setupValid) return LCQP_LCQPOBJECT_NOT_SETUP;
+    SpBatch& d = h->db;
+    HIPCHK(g_sp_err, hipSetDevice(h->device));
+    for (hipError_t e : {h->evS0.status, h->evS1.status}) if (e != hipSuccess) return hip_fail(g_sp_err, "hipEventCreate", e);
+    const size_t B = d.B, n = d.n, m = d.m, K = nrhs;
+    if (nrhs > h->sensRhs) {
+        HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));
+        for (const void* p : {(const void*)h->sensV, (const void*)h->sensDg, (const void*)h->sensDb, (const void*)h->sensSide, (const void*)h->sensInfo}) h->mem.release(p);
+        h->sensV = h->sensDg = h->sensDb = nullptr; h->sensSide = h->sensInfo = nullptr; h->sensRhs = 0;
+        if (!h->mem.alloc(g_sp_err, h->sensV, B * K * n) || !h->mem.alloc(g_sp_err, h->sensDg, B * K * n) || !h->mem.alloc(g_sp_err, h->sensDb, B * K * m) ||
+            !h->mem.alloc(g_sp_err, h->sensSide, B * m) || !h->mem.alloc(g_sp_err, h->sensInfo, B)) return LCQP_HIP_ERROR;
+        h->sensRhs = nrhs;
+    }
+    HIPCHK(g_sp_err, hipMemcpyAsync(h->sensV, v, sizeof(double) * B * K * n, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(g_sp_err, hipEventRecord(h->evS0, h->stream));
+    switch (d.G) {
+        case 8: sp_launch_sensitivity<8>(h, nrhs); break;
+        case 16: sp_launch_sensitivity<16>(h, nrhs); break;
+        case 32: sp_launch_sensitivity<32>(h, nrhs); break;
+        default: sp_launch_sensitivity<64>(h, nrhs); break;
+    }
+    HIPCHK(g_sp_err, hipGetLastError());
+    HIPCHK(g_sp_err, hipEventRecord(h->evS1, h->stream));
+    HIPCHK(g_sp_err, hipMemcpyAsync(dg, h->sensDg, sizeof(double) * B * K * n, hipMemcpyDeviceToHost, h->stream));
+    if (db) HIPCHK(g_sp_err, hipMemcpyAsync(db, h->sensDb, sizeof(double) * B * K * m, hipMemcpyDeviceToHost, h->stream));
+    if (side) HIPCHK(g_sp_err, hipMemcpyAsync(side, h->sensSide, sizeof(int) * B * m, hipMemcpyDeviceToHost, h->stream));
+    if (info) HIPCHK(g_sp_err, hipMemcpyAsync(info, h->sensInfo, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));
+    return 0;
+}
+catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
+
+extern "C" int lcqp_hip_sparse_sensitivity_timing(lcqp_hip_sparse_t* h, float* kernel_ms)
+try {
+    if (!h || !kernel_ms || !h->sensRhs) return LCQP_INVALID_ARGUMENT;
+    HIPCHK(g_sp_err, hipSetDevice(h->device));
+    HIPCHK(g_sp_err, hipEventSynchronize(h->evS1));
+    HIPCHK(g_sp_err, hipEventElapsedTime(kernel_ms, h->evS0, h->evS1));
+    return 0;
+}
+catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 
 extern "C" int lcqp_hip_sparse_synchronize(lcqp_hip_sparse_t* h)
 try {

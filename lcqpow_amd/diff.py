@@ -1,4 +1,5 @@
-"""Differentiable batched LCQP solves for torch: x*(g, lbA, ubA) with gradients from lcqp_hip_batch_sensitivity (DESIGN.md section 3a').
+"""Differentiable batched LCQP solves for torch: x*(g, lbA, ubA) with gradients from lcqp_hip_batch_sensitivity (DESIGN.md section 3a') or,
+for a SparseBatchLCQP behind a SparseBatchLCQPLayer, lcqp_hip_sparse_sensitivity (section 3a'').
 
 The solve and its derivative run on the HIP path of :mod:`lcqpow_amd.capi`; there is no CPU fallback -- without the built library, or
 without a device, using the layer raises.  Tensors are copied to the host and back around the C ABI (host pointers): plumbing, not a
@@ -41,7 +42,7 @@ class LCQPSolveFunction(torch.autograd.Function):
         if ubA is not None: kw["ubA"] = _host(ubA)
         rc = bt.update(0, bt.B, _host(g), **kw)
         if rc != 0:
-            raise RuntimeError(f"lcqp_hip_batch_update failed with code {rc}: {capi.last_error()}")
+            raise RuntimeError(f"update failed with code {rc}: {layer.last_error()}")
         if layer.solves == 0:
             bt.run()
         else:
@@ -67,8 +68,9 @@ class LCQPSolveFunction(torch.autograd.Function):
                           f"(info bits present: {int(np.bitwise_or.reduce(info))}); their gradients are the kernel's output as it is",
                           RuntimeWarning, stacklevel=2)
         out = lambda a: torch.as_tensor(a, dtype=grad_x.dtype, device=grad_x.device)
-        parts = capi.split_bound_derivatives(db, side, bt.nV, bt.nC, bt.nComp)
-        eq = side[:, bt.nV:bt.nV + bt.nC] == 2
+        parts = capi.split_bound_derivatives(db, side, bt.nV, bt.nC, bt.nComp, sparse=layer.sparse)
+        a0 = 0 if layer.sparse else bt.nV      # first row of A in the layout of side
+        eq = side[:, a0:a0 + bt.nC] == 2
         share = np.where(eq, 0.5, 1.0) if all(ctx.given) else 1.0
         glb = out(parts["dlbA"] * share) if ctx.given[0] else None
         gub = out(parts["dubA"] * share) if ctx.given[1] else None
@@ -80,14 +82,30 @@ class BatchLCQPLayer:
     BatchLCQP.update: lbL, ubL, lbR, ubR, lbA, ubA, lb, ub) -- an update replaces EVERY vector, so the ones that are not inputs of the
     layer are handed over again with every solve.  warm: re-solves start from the last solution where it exists."""
 
+    sparse = False
+    bound_keys = BOUND_KEYS
+
     def __init__(self, batch, bounds=None, warm=True):
         capi.lib()      # raises when the HIP library is not built: no CPU fallback
-        unknown = set(bounds or ()) - set(BOUND_KEYS)
+        unknown = set(bounds or ()) - set(self.bound_keys)
         if unknown:
             raise ValueError(f"bounds: unknown keys {sorted(unknown)}")
         self.bt, self.warm, self.solves = batch, warm, 0
         self.bounds = {k: capi._arr(v) for k, v in (bounds or {}).items() if v is not None}
         self.y = self.stats = self.info = None
 
+    def last_error(self):
+        return capi.last_error()
+
     def __call__(self, g, lbA=None, ubA=None):
         return LCQPSolveFunction.apply(self, g, lbA, ubA)
+
+
+class SparseBatchLCQPLayer(BatchLCQPLayer):
+    """A loaded SparseBatchLCQP as a torch layer: the same function over lcqp_hip_sparse_update / _run / _resolve / _sensitivity.  bounds:
+    the vectors of SparseBatchLCQP.update the batch was loaded with (lbA, ubA, lbL, ubL, lbR, ubR; the sparse arm has no box)."""
+    sparse = True
+    bound_keys = tuple(k for k in BOUND_KEYS if k not in ("lb", "ub"))
+
+    def last_error(self):
+        return capi.lib().lcqp_hip_sparse_last_error().decode()

@@ -2,7 +2,13 @@
 algorithmic bytes: bytes_bs(np) + 2 * 8 * np * n_T + 8 * n_T (n_T + 1) / 2 per right-hand side, summed over the batch from the n_T of
 every instance (the rows of its working set, counted from `side`).  DESIGN.md section 7.
 
-usage: python tools/sensitivity_timing.py [--log FILE] [--reps 30]"""
+usage: python tools/sensitivity_timing.py [--log FILE] [--reps 30]
+
+--sparse: k_sparse_sensitivity (lcqp_hip_sparse_sensitivity_timing) on the sparse synthetic workload (lcqpow_amd/synth_sparse.py) after
+run, nrhs = 1: n = 4096 with B = 4096 (skipped with --quick), and (512, 256, 64) with B = 1024 on the band engine and, under
+LCQP_SPARSE_GENERAL=1, on the general LDL'.  Beside each, on the same handle in the same process, the time of a warm resolve of unchanged
+data (refresh + homotopy, last_timing) -- the unit a finite-difference gradient pays 2 nV times.
+    python tools/sensitivity_timing.py --sparse [--quick] [--log FILE] [--reps 20]"""
 import argparse
 import os
 import sys
@@ -39,13 +45,70 @@ def measure(B, nrhs, reps, n=256, nC=512, nComp=64, warmup=5):
                 peak_fraction=total / (med * 1e-3) / HBM_PEAK, us_per_rhs=1e3 * med / nrhs)
 
 
+def measure_sparse(B, n, nC, nK, general, reps, warmup=3):
+    from lcqpow_amd import synth_sparse as S
+    if general:
+        os.environ["LCQP_SPARSE_GENERAL"] = "1"      # read when the handle is created
+    else:
+        os.environ.pop("LCQP_SPARSE_GENERAL", None)
+    Qpat, Apat, qo, eo = S.sparse_pattern_arrays(n, nC, nK)
+    sb = la.SparseBatchLCQP(B, n, nC, nK, Qpat, Apat, opt=la.default_options(perturbStep=0, printLevel=0))
+    os.environ.pop("LCQP_SPARSE_GENERAL", None)
+    for c0 in range(0, B, 1024):
+        inst = [S.sparse_values(i, n, nC, nK, orders=(qo, eo)) for i in range(c0, min(B, c0 + 1024))]
+        st = lambda k: np.stack([d[k] for d in inst])
+        assert sb.load(c0, len(inst), st("Qx"), st("g"), st("Ex"), lbA=st("lbA"), ubA=st("ubA")) == 0
+    sb.run()
+    stats = sb.solution()[2]
+    v = np.random.default_rng(0).standard_normal((B, n))
+    ms, warm = [], []
+    for r in range(warmup + reps):
+        dg, db, side, info = sb.sensitivity(v)
+        if r >= warmup:
+            ms.append(sb.sensitivity_kernel_ms())
+    for r in range(warmup + reps):
+        sb.resolve(warm=True)
+        sb.synchronize()
+        if r >= warmup:
+            warm.append(sum(sb.last_timing()))
+    engine = "general LDL', %d fronts" % sb.fronts() if sb.fronts() else "band, %d lanes" % sb.lanes()
+    sb.close()
+    ms, warm = np.sort(np.array(ms)), np.sort(np.array(warm))
+    return dict(B=B, n=n, nC=nC, nK=nK, engine=engine, solved=sum(s["returnValue"] == 0 for s in stats), flagged=int(np.count_nonzero(info)),
+                W_mean=float(np.count_nonzero(side, axis=1).mean()), ms_min=float(ms[0]), ms_median=float(np.median(ms)), ms_max=float(ms[-1]),
+                warm_min=float(warm[0]), warm_median=float(np.median(warm)), warm_max=float(warm[-1]),
+                fd_ratio=2.0 * n * float(np.median(warm)) / float(np.median(ms)))
+
+
+def sparse_main(a):
+    shapes = [(1024, 512, 256, 64, False), (1024, 512, 256, 64, True)]
+    if not a.quick:
+        shapes.insert(0, (4096, 4096, 2048, 512, False))
+    lines = []
+    for B, n, nC, nK, general in shapes:
+        r = measure_sparse(B, n, nC, nK, general, a.reps)
+        lines.append("n = {n:4d} nC = {nC} nComp = {nK} B = {B:4d} ({engine}) nrhs = 1: kernel ms min / median / max = {ms_min:.4f} / {ms_median:.4f} / {ms_max:.4f}; "
+                     "warm resolve of unchanged data (refresh + homotopy) ms min / median / max = {warm_min:.3f} / {warm_median:.3f} / {warm_max:.3f}; "
+                     "2 nV warm re-solves / one call = {fd_ratio:.3g}; mean |W| {W_mean:.1f}; solved {solved}, flagged {flagged}".format(**r))
+        print(lines[-1], flush=True)
+    if a.log:
+        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
+        with open(a.log, "w") as f:
+            f.write("k_sparse_sensitivity, sparse synthetic workload after run; %d timed calls after 3 warm-up calls each\n" % a.reps)
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--log")
     ap.add_argument("--reps", type=int, default=30)
+    ap.add_argument("--sparse", action="store_true", help="the sparse arm's kernel beside a warm resolve of unchanged data")
+    ap.add_argument("--quick", action="store_true", help="--sparse: without the n = 4096, B = 4096 batch")
     a = ap.parse_args()
     if la.device_count() < 1:
         raise SystemExit("needs a GPU (no CPU fallback)")
+    if a.sparse:
+        return sparse_main(a)
     lines = []
     for B, nrhs in ((1024, 1), (1024, 8), (1, 1), (1, 8)):
         r = measure(B, nrhs, a.reps)
