@@ -175,7 +175,7 @@ int  lcqp_hip_batch_update(lcqp_hip_batch_t* b, int first, int count, const doub
  * mode 0 (cold): every instance starts as after a fresh load -- the result is the bits of a new batch object given the same data by
  *   lcqp_hip_batch_load and solved by lcqp_hip_batch_run.
  * mode 1 (warm): an instance whose last run returned LCQP_SUCCESSFUL_RETURN starts at its last x with the penalty rho0[i] (host array [B],
- *   every entry > 0) or, with rho0 == NULL, its last rhoOpt; it skips the zero-penalty QP, and its first QP is a hot start from the stored
+ *   every entry finite and > 0, else LCQP_INVALID_ARGUMENT) or, with rho0 == NULL, its last rhoOpt; it skips the zero-penalty QP, and its first QP is a hot start from the stored
  *   point, working set and inverse factor.  Its x0 / y0 are not read.  In the reference's terms: runSolver with x0, y0 = the last
  *   solution, solveZeroPenaltyFirst = false, initialPenaltyParameter = that penalty.  Every other instance runs cold as in mode 0.
  * lcqp_hip_batch_last_timing reports k_refresh as setup_ms. */

@@ -120,6 +120,24 @@ def lib():
         L.lcqp_hip_csc_destroy.argtypes = [C.c_void_p]
         L.lcqp_hip_csc_apply.argtypes = [C.c_void_p, C.c_int, C.c_double, c_double_p, c_double_p, c_double_p, C.c_int, C.POINTER(C.c_float)]
         L.lcqp_hip_chol_solve.argtypes = [C.c_int, C.c_int] + [c_double_p] * 3 + [C.c_int, C.POINTER(C.c_float)]
+        L.lcqp_hip_sparse_create.restype = C.c_void_p
+        L.lcqp_hip_sparse_create.argtypes = [C.c_int] * 4 + [c_int_p] * 4 + [C.c_int]
+        L.lcqp_hip_sparse_last_error.restype = C.c_char_p
+        L.lcqp_hip_sparse_destroy.argtypes = [C.c_void_p]
+        L.lcqp_hip_sparse_bandwidth.argtypes = [C.c_void_p]
+        L.lcqp_hip_sparse_lanes.argtypes = [C.c_void_p]
+        L.lcqp_hip_sparse_border.argtypes = [C.c_void_p]
+        L.lcqp_hip_sparse_fronts.argtypes = [C.c_void_p]
+        L.lcqp_hip_sparse_get_ordering.argtypes = [C.c_void_p, c_int_p]
+        L.lcqp_hip_sparse_set_options.argtypes = [C.c_void_p, C.POINTER(Options)]
+        L.lcqp_hip_sparse_load.argtypes = [C.c_void_p, C.c_int, C.c_int] + [c_double_p] * 11
+        L.lcqp_hip_sparse_run.argtypes = [C.c_void_p]
+        L.lcqp_hip_sparse_synchronize.argtypes = [C.c_void_p]
+        L.lcqp_hip_sparse_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+        L.lcqp_hip_sparse_get_solution.argtypes = [C.c_void_p, c_double_p, c_double_p, C.c_void_p]
+        L.lcqp_hip_sparse_get_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, C.POINTER(C.c_int)]
+        L.lcqp_hip_sparse_algorithmic_bytes.restype = C.c_double
+        L.lcqp_hip_sparse_algorithmic_bytes.argtypes = [C.c_void_p]
         L.lcqp_hip_sparse_update.argtypes = [C.c_void_p, C.c_int, C.c_int] + [c_double_p] * 9
         L.lcqp_hip_sparse_resolve.argtypes = [C.c_void_p, C.c_int, c_double_p]
         L.lcqp_hip_sparse_launch_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
@@ -193,8 +211,8 @@ def _read_working_set(call, capS, mE):
     return dict(nT=int(dims[0]), ns=int(dims[1]), slot_row=slot_row, crow=crow, row_slot=row_slot[:mE], Ti=Ti)
 
 
-def _sensitivity(call, v, B, nV, nd):
-    """call(nrhs, v, dg, db, side, info) -> rc.  v: [B][nV] or [B][k][nV]; returns (dg, db, side, info) with dg shaped like v, db
+def _sensitivity(call, v, B, nV, nd, check=None):
+    """call(nrhs, v, dg, db, side, info) -> rc; check(rc, what) raises with the error string of the caller's arm (default: the dense one).  v: [B][nV] or [B][k][nV]; returns (dg, db, side, info) with dg shaped like v, db
     [B][nd] or [B][k][nd], side [B][nd] (int32), info [B] (int32)."""
     v = _arr(v)
     single = v.ndim == 2
@@ -202,7 +220,7 @@ def _sensitivity(call, v, B, nV, nd):
         raise ValueError(f"v: expected [{B}][{nV}] or [{B}][k][{nV}], got shape {v.shape}")
     k = 1 if single else v.shape[1]
     dg = np.zeros((B, k, nV)); db = np.zeros((B, k, nd)); side = np.zeros((B, nd), dtype=np.int32); info = np.zeros(B, dtype=np.int32)
-    _check(call(k, _p(v), _p(dg), _p(db), _ip(side), _ip(info)), "sensitivity")
+    (check or _check)(call(k, _p(v), _p(dg), _p(db), _ip(side), _ip(info)), "sensitivity")
     return (dg[:, 0], db[:, 0], side, info) if single else (dg, db, side, info)
 
 
@@ -391,20 +409,104 @@ class BatchPipeline:
                 s.set_overlapped(False)      # the caller's objects run alone again
 
 
-class BatchLCQP:
+class _Batch:
+    """What BatchLCQP and SparseBatchLCQP have in common: the entry points both arms of the C ABI export under their own prefix.  A
+    subclass sets _prefix ("lcqp_hip_batch_" / "lcqp_hip_sparse_"), _ndual (entries of an instance's dual vector) and _last_error()
+    (the arm's error string), and keeps its constructor, load / update (the argument orders differ) and the arm-only methods."""
+
+    def _sym(self, name):
+        return getattr(lib(), self._prefix + name)
+
+    def _check(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f"{what} failed with code {rc}: {self._last_error()}")
+
+    def _call(self, name, *args):
+        self._check(self._sym(name)(self.h, *args), name)
+
+    def set_options(self, opt):
+        self._call("set_options", C.byref(opt))
+
+    def run(self):
+        self._call("run")
+
+    def resolve(self, warm=False, rho0=None):
+        """*_resolve: solve again on the setup in place (asynchronous like run).  warm: instances whose last run succeeded start from
+        their last solution, working set and penalty (rho0: [B] starting penalties, each finite and > 0, instead of the last rhoOpt);
+        the others, and all of them without warm, start cold -- the bits of a fresh object."""
+        r = _sized("rho0", _arr(rho0), self.B)
+        self._call("resolve", 1 if warm else 0, _p(r))
+
+    def launch_counts(self):
+        """(full setups, homotopy launches) this object has issued"""
+        out = (C.c_int * 2)()
+        self._call("launch_counts", out)
+        return out[0], out[1]
+
+    def sensitivity(self, v):
+        """*_sensitivity: adjoint derivatives of the x the last run / resolve returned (synchronous; DESIGN.md sections 3a', 3a'').
+        v: upstream gradients dl/dx, [B][nV] or [B][k][nV].  Returns (dg, db, side, info): dg = dl/dg shaped like v; db [B][nd] or
+        [B][k][nd], entry r = dl/d(the bound row r sits on) in the layout of the arm's dual vector (dense: box rows first, then A, L, R,
+        nd = nV + nC + 2 nComp; sparse: A, L, R, nd = nC + 2 nComp), zero for rows outside the working set; side [B][nd]: 0 outside,
+        -1 at lower, +1 at upper, 2 equality (split_bound_derivatives turns db and side into derivatives per bound vector; sparse=True
+        for the sparse arm); info [B]: 0 = differentiable, else the flag bits of include/lcqp_hip.h.  The call changes nothing on the
+        device."""
+        return _sensitivity(lambda *a: self._sym("sensitivity")(self.h, *a), v, self.B, self.nV, self._ndual, check=self._check)
+
+    def sensitivity_kernel_ms(self):
+        """kernel time of the last sensitivity call (HIP events around k_sensitivity / k_sparse_sensitivity)"""
+        ms = C.c_float(0)
+        self._call("sensitivity_timing", C.byref(ms))
+        return ms.value
+
+    def synchronize(self):
+        self._call("synchronize")
+
+    def last_timing(self):
+        a = C.c_float(0); b = C.c_float(0)
+        self._call("last_timing", C.byref(a), C.byref(b))
+        return a.value, b.value
+
+    def solution(self):
+        x = np.zeros((self.B, self.nV)); y = np.zeros((self.B, self._ndual))
+        st = (Stats * self.B)()
+        self._call("get_solution", _p(x), _p(y), st)
+        return x, y, [s.asdict() for s in st]
+
+    def trace(self, instance, cap=1024):
+        """per-iterate (|statk|inf, phi, rho, alphak, obj, merit, |pk|inf, QP iterations) and xk of one instance (needs options.storeSteps)"""
+        sc = np.zeros((cap, 8)); xs = np.zeros((cap, self.nV)); n = C.c_int(0)
+        self._call("get_trace", instance, cap, _p(sc), _p(xs), C.byref(n))
+        return sc[:n.value].copy(), xs[:n.value].copy()
+
+    def algorithmic_bytes(self):
+        return self._sym("algorithmic_bytes")(self.h)
+
+    def close(self):
+        if self.h:
+            self._sym("destroy")(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class BatchLCQP(_Batch):
     """B independent dense LCQPs of one shape solved on one GPU (lcqp_hip_batch_*)."""
+    _prefix = "lcqp_hip_batch_"
+    _last_error = staticmethod(last_error)
 
     def __init__(self, batch, nV, nC, nComp, with_box=False, device=0, opt=None):
         self.B, self.nV, self.nC, self.nComp = batch, nV, nC, nComp
-        self.nd = nV + nC + 2 * nComp
+        self.nd = self._ndual = nV + nC + 2 * nComp
         self.h = lib().lcqp_hip_batch_create(batch, nV, nC, nComp, int(with_box), device)
         if not self.h:
             raise RuntimeError("lcqp_hip_batch_create failed: " + last_error())
         if opt is not None:
             self.set_options(opt)
-
-    def set_options(self, opt):
-        _check(lib().lcqp_hip_batch_set_options(self.h, C.byref(opt)), "set_options")
 
     def set_overlapped(self, overlapped=True):
         """lcqp_hip_batch_set_overlapped: this object's setup runs beside another object's homotopy kernel (BatchPipeline sets it)."""
@@ -438,33 +540,6 @@ class BatchLCQP:
         a = [_sized(nm, _arr(v), count * sz) for nm, v, sz in sizes]
         return lib().lcqp_hip_batch_update(self.h, first, count, *[_p(v) for v in a])
 
-    def resolve(self, warm=False, rho0=None):
-        """lcqp_hip_batch_resolve: solve again on the setup in place (asynchronous like run).  warm: instances whose last run succeeded
-        start from their last solution, working set and penalty (rho0: [B] starting penalties, each > 0, instead of the last rhoOpt)."""
-        r = _sized("rho0", _arr(rho0), self.B)
-        _check(lib().lcqp_hip_batch_resolve(self.h, 1 if warm else 0, _p(r)), "resolve")
-
-    def sensitivity(self, v):
-        """lcqp_hip_batch_sensitivity: adjoint derivatives of the x the last run / resolve returned (synchronous; DESIGN.md section 3a').
-        v: upstream gradients dl/dx, [B][nV] or [B][k][nV].  Returns (dg, db, side, info): dg = dl/dg shaped like v; db [B][nd] or
-        [B][k][nd], entry r = dl/d(the bound row r sits on) in the layout of the dual vector (box rows first, then A, L, R), zero for
-        rows outside the working set; side [B][nd]: 0 outside, -1 at lower, +1 at upper, 2 equality (split_bound_derivatives turns db and
-        side into derivatives per bound vector); info [B]: 0 = differentiable, else the flag bits of include/lcqp_hip.h.  The call
-        changes nothing on the device."""
-        return _sensitivity(lambda *a: lib().lcqp_hip_batch_sensitivity(self.h, *a), v, self.B, self.nV, self.nd)
-
-    def sensitivity_kernel_ms(self):
-        """kernel time of the last sensitivity call (HIP events around k_sensitivity)"""
-        ms = C.c_float(0)
-        _check(lib().lcqp_hip_batch_sensitivity_timing(self.h, C.byref(ms)), "sensitivity_timing")
-        return ms.value
-
-    def launch_counts(self):
-        """(full setups, homotopy launches) this object has issued"""
-        out = (C.c_int * 2)()
-        _check(lib().lcqp_hip_batch_launch_counts(self.h, out), "launch_counts")
-        return out[0], out[1]
-
     def read_problem(self, b):
         n, nC, nComp = self.nV, self.nC, self.nComp
         Q = np.zeros((n, n)); g = np.zeros(n); L = np.zeros((nComp, n)); R = np.zeros((nComp, n))
@@ -489,32 +564,6 @@ class BatchLCQP:
     def setup(self):
         _check(lib().lcqp_hip_batch_setup(self.h), "setup")
 
-    def run(self):
-        _check(lib().lcqp_hip_batch_run(self.h), "run")
-
-    def synchronize(self):
-        _check(lib().lcqp_hip_batch_synchronize(self.h), "synchronize")
-
-    def last_timing(self):
-        a = C.c_float(0); b = C.c_float(0)
-        _check(lib().lcqp_hip_batch_last_timing(self.h, C.byref(a), C.byref(b)), "last_timing")
-        return a.value, b.value
-
-    def solution(self):
-        x = np.zeros((self.B, self.nV)); y = np.zeros((self.B, self.nd))
-        st = (Stats * self.B)()
-        _check(lib().lcqp_hip_batch_get_solution(self.h, _p(x), _p(y), st), "get_solution")
-        return x, y, [s.asdict() for s in st]
-
-    def trace(self, instance, cap=1024):
-        """per-iterate (|statk|inf, phi, rho, alphak, obj, merit, |pk|inf, QP iterations) and xk of one instance (needs options.storeSteps)"""
-        sc = np.zeros((cap, 8)); xs = np.zeros((cap, self.nV)); n = C.c_int(0)
-        _check(lib().lcqp_hip_batch_get_trace(self.h, instance, cap, _p(sc), _p(xs), C.byref(n)), "get_trace")
-        return sc[:n.value].copy(), xs[:n.value].copy()
-
-    def algorithmic_bytes(self):
-        return lib().lcqp_hip_batch_algorithmic_bytes(self.h)
-
     def work_sums(self):
         """batch totals counted by the kernel: rows of Et read by the corrections, rows x slots over the corrections, bytes and number of
         the working-set updates, rows of E read by the residual sweeps, triangular solves with L1 (include/lcqp_hip.h)"""
@@ -524,17 +573,6 @@ class BatchLCQP:
 
     def stream(self):
         return lib().lcqp_hip_batch_stream(self.h)
-
-    def close(self):
-        if self.h:
-            lib().lcqp_hip_batch_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def util_symv(alpha, A, b, c):
@@ -619,48 +657,30 @@ class CSCMatrix:
             pass
 
 
-class SparseBatchLCQP:
+class SparseBatchLCQP(_Batch):
     """B independent sparse LCQPs of one sparsity pattern on one GPU (lcqp_hip_sparse_*): the reference's OSQP_SPARSE arm.
     Qpat / Apat: scipy-like CSC pattern objects with .indptr / .indices (Q full symmetric nV x nV; A the stacked [A; L; R],
     (nC + 2 nComp) x nV).  Values are loaded per instance in the CSC order of these patterns."""
+    _prefix = "lcqp_hip_sparse_"
 
     def __init__(self, batch, nV, nC, nComp, Qpat, Apat, device=0, opt=None):
-        ip = C.POINTER(C.c_int)
-        L = lib()
-        L.lcqp_hip_sparse_create.restype = C.c_void_p
-        L.lcqp_hip_sparse_create.argtypes = [C.c_int] * 4 + [ip] * 4 + [C.c_int]
-        L.lcqp_hip_sparse_last_error.restype = C.c_char_p
-        L.lcqp_hip_sparse_destroy.argtypes = [C.c_void_p]
-        L.lcqp_hip_sparse_bandwidth.argtypes = [C.c_void_p]
-        L.lcqp_hip_sparse_lanes.argtypes = [C.c_void_p]
-        L.lcqp_hip_sparse_border.argtypes = [C.c_void_p]
-        L.lcqp_hip_sparse_fronts.argtypes = [C.c_void_p]
-        L.lcqp_hip_sparse_get_ordering.argtypes = [C.c_void_p, ip]
-        L.lcqp_hip_sparse_set_options.argtypes = [C.c_void_p, C.POINTER(Options)]
-        L.lcqp_hip_sparse_load.argtypes = [C.c_void_p, C.c_int, C.c_int] + [c_double_p] * 11
-        L.lcqp_hip_sparse_run.argtypes = [C.c_void_p]
-        L.lcqp_hip_sparse_synchronize.argtypes = [C.c_void_p]
-        L.lcqp_hip_sparse_last_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-        L.lcqp_hip_sparse_get_solution.argtypes = [C.c_void_p, c_double_p, c_double_p, C.c_void_p]
-        L.lcqp_hip_sparse_get_trace.argtypes = [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, C.POINTER(C.c_int)]
-        L.lcqp_hip_sparse_algorithmic_bytes.restype = C.c_double
-        L.lcqp_hip_sparse_algorithmic_bytes.argtypes = [C.c_void_p]
-        self.B, self.nV, self.nC, self.nComp, self.m = batch, nV, nC, nComp, nC + 2 * nComp
+        self.B, self.nV, self.nC, self.nComp = batch, nV, nC, nComp
+        self.m = self._ndual = nC + 2 * nComp
         self._pat = [np.ascontiguousarray(a, dtype=np.int32) for a in (Qpat.indptr, Qpat.indices, Apat.indptr, Apat.indices)]
         if self._pat[0].size != nV + 1 or self._pat[2].size != nV + 1:
             raise ValueError("pattern column pointers must have nV + 1 entries (CSC)")
         if self._pat[1].size != int(self._pat[0][-1]) or self._pat[3].size != int(self._pat[2][-1]):
             raise ValueError("pattern index arrays must have indptr[-1] entries")        # the C side reads exactly that many
         self.nnzQ, self.nnzA = int(self._pat[0][-1]), int(self._pat[2][-1])
-        self.h = L.lcqp_hip_sparse_create(batch, nV, nC, nComp, *[a.ctypes.data_as(ip) for a in self._pat], device)
+        self.h = lib().lcqp_hip_sparse_create(batch, nV, nC, nComp, *[_ip(a) for a in self._pat], device)
         if not self.h:
-            raise RuntimeError("lcqp_hip_sparse_create failed: " + L.lcqp_hip_sparse_last_error().decode())
+            raise RuntimeError("lcqp_hip_sparse_create failed: " + self._last_error())
         if opt is not None:
             self.set_options(opt)
 
-    def _chk(self, rc, what):
-        if rc != 0:
-            raise RuntimeError(f"{what} failed with code {rc}: {lib().lcqp_hip_sparse_last_error().decode()}")
+    @staticmethod
+    def _last_error():
+        return lib().lcqp_hip_sparse_last_error().decode()
 
     def bandwidth(self):
         return lib().lcqp_hip_sparse_bandwidth(self.h)
@@ -679,11 +699,8 @@ class SparseBatchLCQP:
 
     def ordering(self):
         perm = np.zeros(self.nV + self.m, dtype=np.int32)
-        self._chk(lib().lcqp_hip_sparse_get_ordering(self.h, perm.ctypes.data_as(C.POINTER(C.c_int))), "get_ordering")
+        self._call("get_ordering", _ip(perm))
         return perm
-
-    def set_options(self, opt):
-        self._chk(lib().lcqp_hip_sparse_set_options(self.h, C.byref(opt)), "set_options")
 
     def load(self, first, count, Qx, g, Ax, lbA=None, ubA=None, lbL=None, ubL=None, lbR=None, ubR=None, x0=None, y0=None):
         n, nC, nK = self.nV, self.nC, self.nComp
@@ -691,9 +708,6 @@ class SparseBatchLCQP:
                  ("lbR", lbR, nK), ("ubR", ubR, nK), ("x0", x0, n), ("y0", y0, self.m))
         a = [_sized(nm, _arr(v), count * sz) for nm, v, sz in sizes]
         return lib().lcqp_hip_sparse_load(self.h, first, count, *[_p(v) for v in a])
-
-    def run(self):
-        self._chk(lib().lcqp_hip_sparse_run(self.h), "run")
 
     def update(self, first, count, g, lbA=None, ubA=None, lbL=None, ubL=None, lbR=None, ubR=None, x0=None, y0=None):
         """lcqp_hip_sparse_update: new vectors for instances [first, first + count), the matrices stay (the argument list of load without
@@ -704,68 +718,3 @@ class SparseBatchLCQP:
                  ("x0", x0, n), ("y0", y0, self.m))
         a = [_sized(nm, _arr(v), max(count, 0) * sz) for nm, v, sz in sizes]
         return lib().lcqp_hip_sparse_update(self.h, first, count, *[_p(v) for v in a])
-
-    def resolve(self, warm=False, rho0=None):
-        """lcqp_hip_sparse_resolve: solve again on the setup in place (asynchronous like run).  warm: instances whose last run succeeded
-        start from their last solution, working set and penalty (rho0: [B] starting penalties, each finite and > 0, instead of the last
-        rhoOpt); the others, and all of them without warm, start cold -- the bits of a fresh handle."""
-        r = _sized("rho0", _arr(rho0), self.B)
-        self._chk(lib().lcqp_hip_sparse_resolve(self.h, 1 if warm else 0, _p(r)), "resolve")
-
-    def launch_counts(self):
-        """(full setups, homotopy launches) this object has issued"""
-        out = (C.c_int * 2)()
-        self._chk(lib().lcqp_hip_sparse_launch_counts(self.h, out), "launch_counts")
-        return out[0], out[1]
-
-    def sensitivity(self, v):
-        """lcqp_hip_sparse_sensitivity: adjoint derivatives of the x the last run / resolve returned (synchronous; DESIGN.md section 3a'').
-        v: [B][nV] or [B][k][nV] upstream gradients dl/dx.  Returns (dg, db, side, info): dg = dl/dg shaped like v; db [B][m] or
-        [B][k][m], m = nC + 2 nComp (rows A, L, R): dl/d(the bound each row of the working set sits on), zero outside it; side [B][m]:
-        0 outside, -1 at lower, +1 at upper, 2 equality (split_bound_derivatives(..., sparse=True) turns db and side into derivatives
-        per bound vector); info [B]: 0 = differentiable, else the flag bits of include/lcqp_hip.h."""
-        def call(*a):
-            rc = lib().lcqp_hip_sparse_sensitivity(self.h, *a)
-            self._chk(rc, "sensitivity")
-            return rc
-        return _sensitivity(call, v, self.B, self.nV, self.m)
-
-    def sensitivity_kernel_ms(self):
-        """kernel time of the last sensitivity call (HIP events around k_sparse_sensitivity)"""
-        ms = C.c_float(0)
-        self._chk(lib().lcqp_hip_sparse_sensitivity_timing(self.h, C.byref(ms)), "sensitivity_timing")
-        return ms.value
-
-    def synchronize(self):
-        self._chk(lib().lcqp_hip_sparse_synchronize(self.h), "synchronize")
-
-    def last_timing(self):
-        a = C.c_float(0); b = C.c_float(0)
-        self._chk(lib().lcqp_hip_sparse_last_timing(self.h, C.byref(a), C.byref(b)), "last_timing")
-        return a.value, b.value
-
-    def solution(self):
-        x = np.zeros((self.B, self.nV)); y = np.zeros((self.B, self.m))
-        st = (Stats * self.B)()
-        self._chk(lib().lcqp_hip_sparse_get_solution(self.h, _p(x), _p(y), st), "get_solution")
-        return x, y, [s.asdict() for s in st]
-
-    def trace(self, instance, cap=1024):
-        """per-iterate (|statk|inf, phi, rho, alphak, obj, merit, |pk|inf, QP iterations) and xk of one instance (needs options.storeSteps)"""
-        sc = np.zeros((cap, 8)); xs = np.zeros((cap, self.nV)); n = C.c_int(0)
-        self._chk(lib().lcqp_hip_sparse_get_trace(self.h, instance, cap, _p(sc), _p(xs), C.byref(n)), "get_trace")
-        return sc[:n.value].copy(), xs[:n.value].copy()
-
-    def algorithmic_bytes(self):
-        return lib().lcqp_hip_sparse_algorithmic_bytes(self.h)
-
-    def close(self):
-        if self.h:
-            lib().lcqp_hip_sparse_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -68,12 +68,11 @@ static thread_local std::string g_err;      // the dense, QP, util and CSC entry
 
 extern "C" const char* lcqp_hip_last_error(void) { return g_err.c_str(); }
 extern "C" int lcqp_hip_device_count(void)
-try {
+{ return guarded(g_err, [&] {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) return 0;
     return n;
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 extern "C" void lcqp_hip_options_default(lcqp_options_t* o)
 {   // src/Options.cpp:296-333
@@ -120,22 +119,11 @@ struct lcqp_hip_batch {
     int numCU = 256;
     bool overlapped = false;      // lcqp_hip_batch_set_overlapped
     bool ran = false, anyLoaded = false;
-    // re-solves (lcqp_hip_batch_update / lcqp_hip_batch_resolve): does the setup on the device belong to the matrices and options in place
-    // (set by run / setup / resolve, cleared by load / generate_synthetic / set_options); which instances hold a problem, and which of
-    // their variables carry a finite box bound (those are rows of E, hence of Et and M: an update must keep the set); launches issued
-    bool setupValid = false;
-    // the stored point, working set and inverse factor belong to a solve on the data in place (set by run / resolve, cleared with
-    // setupValid): what lcqp_hip_batch_sensitivity differentiates
-    bool solved = false;
-    std::vector<char> filled, boxed;      // [B], [B][n]
-    double* rhoStart = nullptr;           // [B] on the device: starting penalties of a warm re-solve
-    // lcqp_hip_batch_sensitivity: device buffers for sensRhs right-hand sides per instance (grown on demand; layouts at k_sensitivity) and
-    // the events around its last launch
-    double *sensV = nullptr, *sensDg = nullptr, *sensDb = nullptr;
-    int *sensSide = nullptr, *sensInfo = nullptr;
-    int sensRhs = 0;
-    Event evS0, evS1;
-    int nSetups = 0, nLaunches = 0;
+    // re-solves and sensitivities (lcqp_host_rt.hpp).  boxed: which variables of an instance carry a finite box bound -- those are rows of
+    // E, hence of Et and M: an update must keep the set
+    ResolveState rs;
+    std::vector<char> boxed;              // [B][n]
+    SensBuffers sens;
     int nch;
     explicit lcqp_hip_batch(int dev) : db(), device(dev) {}
     ~lcqp_hip_batch() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
@@ -196,7 +184,7 @@ static void dispatch_db(lcqp_hip_batch* h, int kid, int grid, const int* list = 
 }
 
 extern "C" lcqp_hip_batch_t* lcqp_hip_batch_create(int batch, int nV, int nC, int nComp, int withBox, int device)
-try {
+{ return guarded(g_err, [&]() -> lcqp_hip_batch_t* {
     if (batch <= 0 || nV <= 0 || nC < 0 || nComp < 0) { g_err = "invalid dimensions"; return nullptr; }
     if (nV > 4096) { g_err = "nV > 4096 is not supported by the dense kernels of this build (padded sizes 128 ... 4096; the sparse engine takes larger banded / bordered problems)"; return nullptr; }
     if (hipError_t e = hipSetDevice(device)) { hip_fail(g_err, "hipSetDevice(device)", e); return nullptr; }
@@ -235,42 +223,37 @@ try {
                     m.alloc(g_err, d.lbR, B * nLR) && m.alloc(g_err, d.yk, B * d.nd) && m.alloc(g_err, d.y0, B * d.nd) &&
                     m.alloc(g_err, d.xout, B * nV) && m.alloc(g_err, d.yout, B * d.nd) && m.alloc(g_err, d.stats, B) &&
                     m.alloc(g_err, d.info, B) && m.alloc(g_err, d.prof, B * 16);
-    if (!ok || !m.alloc(g_err, h->rhoStart, B)) return nullptr;
-    h->filled.assign(B, 0); h->boxed.assign(B * (size_t)nV, 0);
+    if (!ok || !m.alloc(g_err, h->rs.rhoStart, B)) return nullptr;
+    h->rs.filled.assign(B, 0); h->boxed.assign(B * (size_t)nV, 0);
     if (hipError_t e = hipStreamSynchronize(h->stream)) { hip_fail(g_err, "hipStreamSynchronize(h->stream)", e); return nullptr; }
     return h.release();
-}
-catch (...) { g_err = "out of host memory"; return nullptr; }   // nothing throws across the C boundary
+}, nullptr); }
 
 extern "C" void lcqp_hip_batch_destroy(lcqp_hip_batch_t* h)
-try {
-    delete h;      // ~lcqp_hip_batch: set the device, synchronise, then the members
+{
+    guarded(g_err, [&] { delete h; });      // ~lcqp_hip_batch: set the device, synchronise, then the members
 }
-catch (...) { }   // nothing throws across the C boundary
 
 // storeSteps: the first 1024 iterates
 extern "C" int lcqp_hip_batch_set_options(lcqp_hip_batch_t* h, const lcqp_options_t* opt)
-try {
-    if (h) h->setupValid = h->solved = false;      // the scales of the ADMM weights and the proximal shifts of the factors come from the options
+{ return guarded(g_err, [&] {
+    if (h) h->rs.invalidate();      // the scales of the ADMM weights and the proximal shifts of the factors come from the options
     return set_options(g_err, h, opt, 1024);
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 extern "C" int lcqp_hip_batch_get_trace(lcqp_hip_batch_t* h, int instance, int cap, double* scalars, double* x, int* len)
-try {
-    return get_trace(g_err, h, instance, cap, scalars, x, len);
+{
+    return guarded(g_err, [&] { return get_trace(g_err, h, instance, cap, scalars, x, len); });
 }
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 
 // diagnostic builds (-DLCQP_PROFILE): per-instance cycle counters of the megakernel's phases, [B][16]
 extern "C" int lcqp_hip_batch_read_profile(lcqp_hip_batch_t* h, unsigned long long* out)
-try {
+{ return guarded(g_err, [&] {
     if (!h || !out) return LCQP_INVALID_ARGUMENT;
     if (int rc = synchronize(g_err, h)) return rc;
     HIPCHK(g_err, hipMemcpy(out, h->db.prof, sizeof(unsigned long long) * (size_t)h->db.B * 16, hipMemcpyDeviceToHost));
     return 0;
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 extern "C" void* lcqp_hip_batch_stream(lcqp_hip_batch_t* h) { return h ? (void*)h->stream.s : nullptr; }
 
@@ -294,7 +277,7 @@ extern "C" int lcqp_hip_batch_load(lcqp_hip_batch_t* h, int first, int count,
                                    const double* lbL, const double* ubL, const double* lbR, const double* ubR,
                                    const double* A, const double* lbA, const double* ubA,
                                    const double* lb, const double* ub, const double* x0, const double* y0)
-try {
+{ return guarded(g_err, [&] {
     if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
     DevBatch& d = h->db;
     const int n = d.n, nC = d.nC, nComp = d.nComp, mA = d.mA, np = d.np, mE = d.mEcap;
@@ -311,7 +294,7 @@ try {
     const size_t infoDbl = (sizeof(InstInfo) + 7) / 8, bidxDbl = ((size_t)np * sizeof(int) + 7) / 8;
     const size_t slotBytes = sizeof(double) * (nQ + nE + nNV + nMV + nY + 2 * nLR + infoDbl + bidxDbl);
     if (int rc = stage_reserve(h, slotBytes)) return rc;
-    h->setupValid = h->solved = false;
+    h->rs.invalidate();
     for (int k = 0; k < count; k++) {
         const size_t b = (size_t)first + k;
         StageSlot& slot = h->stage[k & 1];
@@ -346,7 +329,7 @@ try {
             h->boxed[b * n + i] = fin;
             if (fin) bidx[nfin++] = i;
         }
-        h->filled[b] = 1;
+        h->rs.filled[b] = 1;
         info->nfin = nfin; info->mE = mA + nfin; info->hasY0 = y0 ? 1 : 0;
         HIPCHK(g_err, hipMemcpyAsync(d.Q + b * nQ, Qp, sizeof(double) * nQ, hipMemcpyHostToDevice, h->stream));
         HIPCHK(g_err, hipMemcpyAsync(d.E + b * nE, Ep, sizeof(double) * nE, hipMemcpyHostToDevice, h->stream));
@@ -367,28 +350,26 @@ try {
     HIPCHK(g_err, hipStreamSynchronize(h->stream));
     h->anyLoaded = true;
     return 0;
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 extern "C" int lcqp_hip_batch_generate_synthetic(lcqp_hip_batch_t* h, uint64_t seed0, uint64_t firstInstance)
-try {
+{ return guarded(g_err, [&] {
     if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
     HIPCHK(g_err, hipSetDevice(h->device));
     DevBatch& d = h->db;
     if (d.nComp * 2 > d.n) { g_err = "synthetic generator needs 2*nComp <= nV"; return LCQP_INVALID_ARGUMENT; }
     d.hasLbL = d.hasLbR = 0; h->anyLoaded = true;
-    h->setupValid = h->solved = false;
-    std::fill(h->filled.begin(), h->filled.end(), 1); std::fill(h->boxed.begin(), h->boxed.end(), 0);      // no box bounds
+    h->rs.invalidate();
+    std::fill(h->rs.filled.begin(), h->rs.filled.end(), 1); std::fill(h->boxed.begin(), h->boxed.end(), 0);      // no box bounds
     dispatch_db(h, ID_k_synth_fill, d.B, nullptr, 0, seed0, firstInstance);
     dispatch_db(h, ID_k_synth_Q, d.B * (d.nblk * (d.nblk + 1) / 2));
     HIPCHK(g_err, hipGetLastError());
     return 0;
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 extern "C" int lcqp_hip_batch_read_problem(lcqp_hip_batch_t* h, int b, double* Q, double* g, double* L, double* R,
                                            double* A, double* lbA, double* ubA)
-try {
+{ return guarded(g_err, [&] {
     if (!h || b < 0 || b >= h->db.B) return LCQP_INVALID_ARGUMENT;
     if (int rc = synchronize(g_err, h)) return rc;
     DevBatch& d = h->db;
@@ -412,16 +393,15 @@ try {
         if (R) memcpy(R + (size_t)r * n, &Ep[(size_t)(nC + nComp + r) * np], sizeof(double) * n);
     }
     return 0;
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 // the setup kernels of the batch on its stream, the C branch on the side stream
 static int launch_setup(lcqp_hip_batch* h)
 {
     const DevBatch& d = h->db;
     hipStream_t on = h->stream;
-    h->setupValid = h->solved = false;
-    h->nSetups++;
+    h->rs.invalidate();
+    h->rs.nSetups++;
     const int ntile = d.nblk * (d.nblk + 1) / 2;
     const int nrb = (d.mEcap + 63) / 64, nb = (d.mMld + 127) / 128, nmt = nb * (nb + 1);      // k_build_M: 128 x 64 tiles of the lower triangle
     dispatch_db(h, ID_k_prepare, d.B);
@@ -445,7 +425,7 @@ static int launch_setup(lcqp_hip_batch* h)
     if (fork) HIPCHK(g_err, hipStreamWaitEvent(on, h->evJoin, 0));
     dispatch_db(h, ID_k_build_M, d.B * nmt);
     HIPCHK(g_err, hipGetLastError());
-    h->setupValid = true;
+    h->rs.setupValid = true;
     return 0;
 }
 
@@ -457,19 +437,18 @@ extern "C" int lcqp_hip_batch_set_overlapped(lcqp_hip_batch_t* h, int overlapped
 }
 
 extern "C" int lcqp_hip_batch_setup(lcqp_hip_batch_t* h)
-try {
+{ return guarded(g_err, [&] {
     if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
     HIPCHK(g_err, hipSetDevice(h->device));
     return launch_setup(h);
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 // One launch for the whole batch.  (Round 5 measured the setup of one slice of the batch beside the homotopy of the slice before, as a
 // switch of this call: slower at every split -- profiles/round5/run_chunks_ab.log: 30 200 LCQPs/s in one piece, 26 800 / 27 100 / 23 100 in
 // two / three / four slices, the setup kernels crawl beside a homotopy launch that saturates HBM.  The switch is gone; overlap across
 // BATCHES is the product's BatchPipeline.)
 extern "C" int lcqp_hip_batch_run(lcqp_hip_batch_t* h)
-try {
+{ return guarded(g_err, [&] {
     if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
     HIPCHK(g_err, hipSetDevice(h->device));
     HIPCHK(g_err, hipEventRecord(h->ev0, h->stream));
@@ -477,13 +456,12 @@ try {
     if (rc) return rc;
     HIPCHK(g_err, hipEventRecord(h->ev1, h->stream));
     dispatch_db(h, ID_k_lcqp_run, h->db.B);
-    h->nLaunches++;
+    h->rs.nLaunches++;
     HIPCHK(g_err, hipGetLastError());
     HIPCHK(g_err, hipEventRecord(h->ev2, h->stream));
-    h->ran = h->solved = true;
+    h->ran = h->rs.solved = true;
     return 0;
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 // New vectors for instances [first, first + count) of a batch that holds problems: everything lcqp_hip_batch_load takes except the
 // matrices.  The whole range is checked before anything is written.
@@ -491,15 +469,10 @@ extern "C" int lcqp_hip_batch_update(lcqp_hip_batch_t* h, int first, int count, 
                                      const double* lbL, const double* ubL, const double* lbR, const double* ubR,
                                      const double* lbA, const double* ubA, const double* lb, const double* ub,
                                      const double* x0, const double* y0)
-try {
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+{ return guarded(g_err, [&] {
+    if (int rc = check_update(g_err, h, first, count, g, lbL, lbR)) return rc;
     DevBatch& d = h->db;
     const int n = d.n, nComp = d.nComp, mA = d.mA, np = d.np, mE = d.mEcap;
-    if (first < 0 || count <= 0 || first > d.B - count) return LCQP_INVALID_ARGUMENT;
-    for (int k = 0; k < count; k++) if (!h->filled[(size_t)first + k]) return LCQP_LCQPOBJECT_NOT_SETUP;
-    if (!g) return LCQP_INVALID_OBJECTIVE_LINEAR_TERM;
-    for (size_t j = 0; j < (size_t)count * nComp; j++)
-        if (bnd(lbL, j, 0.0) <= -INFINITY || bnd(lbR, j, 0.0) <= -INFINITY) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
     for (int k = 0; k < count; k++)
         for (int i = 0; i < n; i++) {
             const size_t j = (size_t)k * n + i;
@@ -555,69 +528,56 @@ try {
     }
     HIPCHK(g_err, hipStreamSynchronize(h->stream));
     return 0;
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 // Solve again on the setup in place: k_refresh instead of the five setup kernels, then the homotopy launch.  Without a setup that belongs
 // to the matrices and options in place this is lcqp_hip_batch_run.
 extern "C" int lcqp_hip_batch_resolve(lcqp_hip_batch_t* h, int mode, const double* rho0)
-try {
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    if (mode != 0 && mode != 1) { g_err = "resolve: mode is 0 (cold) or 1 (warm)"; return LCQP_INVALID_ARGUMENT; }
+{ return guarded(g_err, [&] {
+    if (int rc = check_resolve(g_err, h, mode, rho0, h && h->anyLoaded)) return rc == RESOLVE_RUNS ? lcqp_hip_batch_run(h) : rc;
     const int B = h->db.B;
-    if (rho0)
-        for (int b = 0; b < B; b++)
-            if (!(rho0[b] > 0.0)) { g_err = "resolve: rho0[" + std::to_string(b) + "] is not positive"; return LCQP_INVALID_ARGUMENT; }
-    if (!h->anyLoaded) return LCQP_LCQPOBJECT_NOT_SETUP;
-    if (!h->setupValid) return lcqp_hip_batch_run(h);
     HIPCHK(g_err, hipSetDevice(h->device));
     const bool withRho = mode == 1 && rho0;
     if (withRho) {
         if (int rc = stage_reserve(h, sizeof(double) * (size_t)B)) return rc;
         HIPCHK(g_err, hipEventSynchronize(h->stage[0].done));
         memcpy(h->stage[0].buf, rho0, sizeof(double) * (size_t)B);
-        HIPCHK(g_err, hipMemcpyAsync(h->rhoStart, h->stage[0].buf, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(g_err, hipMemcpyAsync(h->rs.rhoStart, h->stage[0].buf, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, h->stream));
         HIPCHK(g_err, hipEventRecord(h->stage[0].done, h->stream));
     }
     HIPCHK(g_err, hipEventRecord(h->ev0, h->stream));
     LaunchArgs a;
-    a.db = h->db; a.mode = mode; a.rho0 = withRho ? h->rhoStart : nullptr;
+    a.db = h->db; a.mode = mode; a.rho0 = withRho ? h->rs.rhoStart : nullptr;
     lcqp_dispatch(h->nch, ID_k_refresh, B, h->stream, a);
     HIPCHK(g_err, hipGetLastError());
     HIPCHK(g_err, hipEventRecord(h->ev1, h->stream));
     dispatch_db(h, ID_k_lcqp_run, B);
-    h->nLaunches++;
+    h->rs.nLaunches++;
     HIPCHK(g_err, hipGetLastError());
     HIPCHK(g_err, hipEventRecord(h->ev2, h->stream));
-    h->ran = h->solved = true;
+    h->ran = h->rs.solved = true;
     return 0;
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 extern "C" int lcqp_hip_batch_launch_counts(lcqp_hip_batch_t* h, int out[2])
 {
-    if (!h || !out) return LCQP_INVALID_ARGUMENT;
-    out[0] = h->nSetups; out[1] = h->nLaunches;
-    return 0;
+    return launch_counts(h, out);
 }
 
 extern "C" int lcqp_hip_batch_synchronize(lcqp_hip_batch_t* h)
-try {
-    return synchronize(g_err, h);
+{
+    return guarded(g_err, [&] { return synchronize(g_err, h); });
 }
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 
 extern "C" int lcqp_hip_batch_last_timing(lcqp_hip_batch_t* h, float* setup_ms, float* solve_ms)
-try {
-    return last_timing(g_err, h, setup_ms, solve_ms);
+{
+    return guarded(g_err, [&] { return last_timing(g_err, h, setup_ms, solve_ms); });
 }
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 
 extern "C" int lcqp_hip_batch_get_solution(lcqp_hip_batch_t* h, double* x, double* y, lcqp_stats_t* stats)
-try {
-    return get_solution(g_err, h, h ? h->db.nd : 0, x, y, stats);
+{
+    return guarded(g_err, [&] { return get_solution(g_err, h, h ? h->db.nd : 0, x, y, stats); });
 }
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 
 // Algorithmic HBM bytes of the last run, from the per-instance work counters:
 //   residual evaluation (trial with sweeps, stats.reserved): Q + E once   8*(n*n + m*n)
@@ -628,7 +588,7 @@ catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothin
 //   LCQP                        : one sweep over Q and C (Q x0, C x0); per iterate C pk from compressed rows (12 B per non-zero) or by a
 //                                 sweep over C; Q pk comes from the subsolver's verified residual
 extern "C" double lcqp_hip_batch_algorithmic_bytes(lcqp_hip_batch_t* h)
-try {
+{ return guarded(g_err, [&] {
     if (!h) return 0.0;
     DevBatch& d = h->db;
     std::vector<lcqp_stats_t> st(d.B);
@@ -651,11 +611,10 @@ try {
         total += (st[b].iterTotal + 1) * (info[b].cNnz >= 0 ? 12.0 * info[b].cNnz : 8.0 * n * n);   // C pk per LCQP iterate: compressed rows or a sweep
     }
     return total;
-}
-catch (...) { return 0.0; }   // nothing throws across the C boundary
+}, 0.0); }
 
 extern "C" int lcqp_hip_batch_work_sums(lcqp_hip_batch_t* h, double out[6])
-try {
+{ return guarded(g_err, [&] {
     if (!h || !out) return LCQP_INVALID_ARGUMENT;
     DevBatch& d = h->db;
     if (int rc = synchronize(g_err, h)) return rc;
@@ -664,8 +623,7 @@ try {
     for (int k = 0; k < 6; k++) out[k] = 0.0;
     for (int b = 0; b < d.B; b++) for (int k = 0; k < 6; k++) out[k] += info[b].work[k];
     return 0;
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 // ---- read-back of the constant matrices and of the working-set factor (tests, diagnostics): the raw padded blocks of one instance ----
 template <class T>
@@ -677,7 +635,7 @@ static int read_block(T* dst, const T* src, size_t count)
 
 extern "C" int lcqp_hip_batch_read_setup(lcqp_hip_batch_t* h, int b, int dims[9], double scal[2], double* Cm, double* F1, double* D1,
                                          double* Et, double* MM, int* Cp, int* Ci, double* Cv)
-try {
+{ return guarded(g_err, [&] {
     if (!h || b < 0 || b >= h->db.B) return LCQP_INVALID_ARGUMENT;
     if (int rc = synchronize(g_err, h)) return rc;
     HIPCHK(g_err, hipStreamSynchronize(h->side));
@@ -699,11 +657,10 @@ try {
     if (!rc) rc = read_block(Ci, d.Ci + ib * d.capC, (size_t)d.capC);
     if (!rc) rc = read_block(Cv, d.Cv + ib * d.capC, (size_t)d.capC);
     return rc;
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 extern "C" int lcqp_hip_batch_read_working_set(lcqp_hip_batch_t* h, int b, int dims[2], int* slot_row, int* crow, int* row_slot, double* Ti)
-try {
+{ return guarded(g_err, [&] {
     if (!h || b < 0 || b >= h->db.B) return LCQP_INVALID_ARGUMENT;
     if (int rc = synchronize(g_err, h)) return rc;
     const DevBatch& d = h->db;
@@ -716,56 +673,36 @@ try {
     if (!rc) rc = read_block(row_slot, d.mi + ib * I_NUM * d.mEcap + (size_t)I_SLOT * d.mEcap, (size_t)info.mE);
     if (!rc) rc = read_block(Ti, d.S + ib * capS * capS, capS * capS);
     return rc;
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 // ---- solution sensitivities (DESIGN.md section 3a'): one launch of k_sensitivity on the batch stream, host buffers in and out ----
 static int batch_sensitivity(lcqp_hip_batch* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
 {
     DevBatch& d = h->db;
+    SensBuffers& sb = h->sens;
     HIPCHK(g_err, hipSetDevice(h->device));
-    for (hipError_t e : {h->evS0.status, h->evS1.status}) if (e != hipSuccess) return hip_fail(g_err, "hipEventCreate", e);
-    const size_t B = d.B, n = d.n, np = d.np, nd = d.nd, ldb = (size_t)d.nd + d.capS, K = nrhs;
-    if (nrhs > h->sensRhs) {
-        HIPCHK(g_err, hipStreamSynchronize(h->stream));
-        for (const void* p : {(const void*)h->sensV, (const void*)h->sensDg, (const void*)h->sensDb, (const void*)h->sensSide, (const void*)h->sensInfo}) h->mem.release(p);
-        h->sensV = h->sensDg = h->sensDb = nullptr; h->sensSide = h->sensInfo = nullptr; h->sensRhs = 0;
-        if (!h->mem.alloc(g_err, h->sensV, B * K * n) || !h->mem.alloc(g_err, h->sensDg, B * K * np) || !h->mem.alloc(g_err, h->sensDb, B * K * ldb) ||
-            !h->mem.alloc(g_err, h->sensSide, B * nd) || !h->mem.alloc(g_err, h->sensInfo, B)) return LCQP_HIP_ERROR;
-        h->sensRhs = nrhs;
-    }
-    HIPCHK(g_err, hipMemcpyAsync(h->sensV, v, sizeof(double) * B * K * n, hipMemcpyHostToDevice, h->stream));
+    if (int rc = sb.reserve(g_err, h->mem, h->stream, d.B, nrhs, d.n, d.np, (size_t)d.nd + d.capS, d.nd)) return rc;
+    if (int rc = sb.upload(g_err, v)) return rc;
     LaunchArgs a;
-    a.db = d; a.nrhs = nrhs; a.sensV = h->sensV; a.sensDg = h->sensDg; a.sensDb = h->sensDb; a.sensSide = h->sensSide; a.sensInfo = h->sensInfo;
-    HIPCHK(g_err, hipEventRecord(h->evS0, h->stream));
+    a.db = d; a.nrhs = nrhs; a.sensV = sb.v; a.sensDg = sb.dg; a.sensDb = sb.db; a.sensSide = sb.side; a.sensInfo = sb.info;
+    HIPCHK(g_err, hipEventRecord(sb.ev0, h->stream));
     lcqp_dispatch(h->nch, ID_k_sensitivity, d.B, h->stream, a);
     HIPCHK(g_err, hipGetLastError());
-    HIPCHK(g_err, hipEventRecord(h->evS1, h->stream));
-    HIPCHK(g_err, hipMemcpy2DAsync(dg, sizeof(double) * n, h->sensDg, sizeof(double) * np, sizeof(double) * n, B * K, hipMemcpyDeviceToHost, h->stream));
-    if (db) HIPCHK(g_err, hipMemcpy2DAsync(db, sizeof(double) * nd, h->sensDb, sizeof(double) * ldb, sizeof(double) * nd, B * K, hipMemcpyDeviceToHost, h->stream));
-    if (side) HIPCHK(g_err, hipMemcpyAsync(side, h->sensSide, sizeof(int) * B * nd, hipMemcpyDeviceToHost, h->stream));
-    if (info) HIPCHK(g_err, hipMemcpyAsync(info, h->sensInfo, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(g_err, hipStreamSynchronize(h->stream));
-    return 0;
+    HIPCHK(g_err, hipEventRecord(sb.ev1, h->stream));
+    return sb.download(g_err, dg, db, side, info, d.n, d.nd);
 }
 
 extern "C" int lcqp_hip_batch_sensitivity(lcqp_hip_batch_t* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
-try {
+{ return guarded(g_err, [&] {
     if (!h || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
-    if (!h->solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
     return batch_sensitivity(h, nrhs, v, dg, db, side, info);
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 extern "C" int lcqp_hip_batch_sensitivity_timing(lcqp_hip_batch_t* h, float* kernel_ms)
-try {
-    if (!h || !kernel_ms || !h->sensRhs) return LCQP_INVALID_ARGUMENT;
-    HIPCHK(g_err, hipSetDevice(h->device));
-    HIPCHK(g_err, hipEventSynchronize(h->evS1));
-    HIPCHK(g_err, hipEventElapsedTime(kernel_ms, h->evS0, h->evS1));
-    return 0;
+{
+    return guarded(g_err, [&] { return sensitivity_timing(g_err, h, kernel_ms); });
 }
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 
 // =================================================================================================
 // QP object (SubsolverBase semantics): a batch of one with nComp = 0 whose rows are the nC stacked rows
@@ -784,7 +721,7 @@ struct lcqp_hip_qp {
 };
 
 extern "C" lcqp_hip_qp_t* lcqp_hip_qp_create(int nV, int nC, const double* Q, const double* A, const lcqp_options_t* opt, int device)
-try {
+{ return guarded(g_err, [&]() -> lcqp_hip_qp_t* {
     if (nV <= 0 || nC < 0 || !Q || (nC > 0 && !A)) { g_err = "invalid arguments"; return nullptr; }
     lcqp_hip_qp* q = new lcqp_hip_qp();
     q->hb = nullptr; q->nV = nV; q->nC = nC; q->device = device; q->haveBounds = false; q->withBox = false; q->solved = false;
@@ -794,11 +731,10 @@ try {
     q->xsol.assign(nV, 0.0); q->ysol.assign((size_t)nV + nC, 0.0);
     q->cAdmm = q->cTrials = q->cFact = q->cCorr = 0;
     return q;
-}
-catch (...) { g_err = "out of host memory"; return nullptr; }   // nothing throws across the C boundary
+}, nullptr); }
 
 extern "C" lcqp_hip_qp_t* lcqp_hip_qp_clone(const lcqp_hip_qp_t* s)
-try {
+{ return guarded(g_err, [&]() -> lcqp_hip_qp_t* {
     if (!s) return nullptr;
     // The reference copies subsolvers only before their first use (src/Subsolver.cpp:125-136,
     // src/LCQProblem.cpp:906-907): the clone carries the problem data and options; device state is
@@ -808,26 +744,23 @@ try {
     q->haveBounds = false;
     q->solved = false;
     return q;
-}
-catch (...) { g_err = "out of host memory"; return nullptr; }   // nothing throws across the C boundary
+}, nullptr); }
 
 extern "C" void lcqp_hip_qp_destroy(lcqp_hip_qp_t* q)
-try {
+{ guarded(g_err, [&] {
     if (!q) return;
     if (q->hb) lcqp_hip_batch_destroy(q->hb);
     delete q;
-}
-catch (...) { }   // nothing throws across the C boundary
+}); }
 
 extern "C" int lcqp_hip_qp_set_options(lcqp_hip_qp_t* q, const lcqp_options_t* opt)
-try {
+{ return guarded(g_err, [&] {
     if (!q || !opt) return LCQP_INVALID_ARGUMENT;
     q->opt = *opt;
     q->haveBounds = false;   // forces a fresh setup (rho / sigma / prox weights enter the factorisations)
     q->solved = false;
     return 0;
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 static bool same_pattern(const std::vector<double>& a0, const std::vector<double>& b0, const double* a1, const double* b1, size_t n)
 {
@@ -843,7 +776,7 @@ static bool same_pattern(const std::vector<double>& a0, const std::vector<double
 extern "C" int lcqp_hip_qp_solve(lcqp_hip_qp_t* q, int initialSolve, int* iterations, int* exit_flag,
                                  const double* g, const double* lbA, const double* ubA,
                                  const double* x0, const double* y0, const double* lb, const double* ub)
-try {
+{ return guarded(g_err, [&] {
     if (!q || !g || !iterations || !exit_flag) return LCQP_INVALID_ARGUMENT;
     const int n = q->nV, nC = q->nC;
     *iterations = 0; *exit_flag = 0;
@@ -914,26 +847,23 @@ try {
     }
     q->solved = true;
     return LCQP_SUCCESSFUL_RETURN;
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 extern "C" void lcqp_hip_qp_get_solution(lcqp_hip_qp_t* q, double* x, double* y)
-try {
+{ guarded(g_err, [&] {
     if (!q) return;
     if (x) memcpy(x, q->xsol.data(), sizeof(double) * q->nV);
     if (y) memcpy(y, q->ysol.data(), sizeof(double) * ((size_t)q->nV + q->nC));
-}
-catch (...) { }   // nothing throws across the C boundary
+}); }
 
 extern "C" void lcqp_hip_qp_get_counters(lcqp_hip_qp_t* q, int* admm, int* trials, int* factorizations, int* corrections)
-try {
+{ guarded(g_err, [&] {
     if (!q) return;
     if (admm) *admm = q->cAdmm;
     if (trials) *trials = q->cTrials;
     if (factorizations) *factorizations = q->cFact;
     if (corrections) *corrections = q->cCorr;
-}
-catch (...) { }   // nothing throws across the C boundary
+}); }
 
 // the QP object is a batch of one: the same two readers through its batch (LCQP_LCQPOBJECT_NOT_SETUP before the first solve built it)
 extern "C" int lcqp_hip_qp_read_setup(lcqp_hip_qp_t* q, int dims[9], double scal[2], double* Cm, double* F1, double* D1, double* Et,
@@ -953,12 +883,11 @@ extern "C" int lcqp_hip_qp_read_working_set(lcqp_hip_qp_t* q, int dims[2], int* 
 
 // the derivatives of the convex QP last solved: k_sensitivity on the batch of one (dg [nrhs][nV], db / side [.][nV + nC], info [1])
 extern "C" int lcqp_hip_qp_sensitivity(lcqp_hip_qp_t* q, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
-try {
+{ return guarded(g_err, [&] {
     if (!q || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
     if (!q->hb || !q->solved) return LCQP_LCQPOBJECT_NOT_SETUP;
     return batch_sensitivity(q->hb, nrhs, v, dg, db, side, info);
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 // =================================================================================================
 // building blocks (tests, micro-benchmarks)
@@ -1003,7 +932,7 @@ static int download_padded(double* dst, const double* src, int batch, int rows, 
 }
 
 extern "C" int lcqp_hip_util_symv(int batch, int n, double alpha, const double* A, const double* bv, const double* cv, double* dv)
-try {
+{ return guarded(g_err, [&] {
     if (n <= 0 || n > 4096 || batch <= 0) return LCQP_HIP_UNSUPPORTED;
     const int nch = padded_nch(n), np = 128 * nch;
     DevMem tb;
@@ -1017,8 +946,7 @@ try {
     { LaunchArgs la; la.n = n; la.alpha = alpha; la.A = dA; la.b = db_; la.c = dc; la.d = dd; lcqp_dispatch(nch, ID_k_util_symv, batch, 0, la); }
     HIPCHK(g_err, hipDeviceSynchronize());
     return download_padded(dv, dd, batch, 1, n, np, 1);
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 static int util_rows(int batch, int m, int n, const double* A, const double* x, double* dots, const double* coef, double* outT)
 {
@@ -1040,7 +968,7 @@ static int util_rows(int batch, int m, int n, const double* A, const double* x, 
 
 extern "C" int lcqp_hip_util_rows_list(int batch, int m, int n, const double* A, const int* list, int nlist, const double* x, const double* coef,
                                        double* dots, double* outT)
-try {
+{ return guarded(g_err, [&] {
     if (n <= 0 || n > 4096 || batch <= 0 || m <= 0 || nlist < 0 || nlist > m || !list) return LCQP_HIP_UNSUPPORTED;
     const int nch = padded_nch(n), np = 128 * nch;
     DevMem tb;
@@ -1058,22 +986,19 @@ try {
     if (dots) HIPCHK(g_err, hipMemcpy(dots, dd, sizeof(double) * (size_t)batch * m, hipMemcpyDeviceToHost));
     if (outT) return download_padded(outT, dout, batch, 1, n, np, 1);
     return 0;
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 extern "C" int lcqp_hip_util_gemv(int batch, int m, int n, const double* A, const double* b, double* c)
-try {
-    return util_rows(batch, m, n, A, b, c, nullptr, nullptr);
+{
+    return guarded(g_err, [&] { return util_rows(batch, m, n, A, b, c, nullptr, nullptr); });
 }
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 extern "C" int lcqp_hip_util_gemv_t(int batch, int m, int n, const double* A, const double* b, double* c)
-try {
-    return util_rows(batch, m, n, A, nullptr, nullptr, b, c);
+{
+    return guarded(g_err, [&] { return util_rows(batch, m, n, A, nullptr, nullptr, b, c); });
 }
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
 
 extern "C" int lcqp_hip_util_symm_product(int batch, int m, int n, const double* A, const double* Bm, double* C)
-try {
+{ return guarded(g_err, [&] {
     // goes through the batch object so that the production kernel k_build_C is what is tested
     lcqp_hip_batch* h = lcqp_hip_batch_create(batch, n, 0, m, 0, 0);
     if (!h) return LCQP_HIP_ERROR;
@@ -1095,8 +1020,7 @@ try {
     if (!rc) rc = download_padded(C, d.C, batch, n, n, d.np, d.np);
     lcqp_hip_batch_destroy(h);
     return rc;
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 // =================================================================================================
 // CSC utilities on the device: compressed-segment gather products.
@@ -1132,7 +1056,7 @@ struct lcqp_hip_csc {
 };
 
 extern "C" lcqp_hip_csc_t* lcqp_hip_csc_create(int m, int n, int nnz, const int* p, const int* i, const double* x, int device)
-try {
+{ return guarded(g_err, [&]() -> lcqp_hip_csc_t* {
     if (m <= 0 || n <= 0 || nnz < 0 || !p || (nnz && (!i || !x))) { g_err = "invalid CSC arguments"; return nullptr; }
     if (hipError_t e = hipSetDevice(device)) { hip_fail(g_err, "hipSetDevice(device)", e); return nullptr; }
     // transpose on the host: counting sort by row index (stable, so columns stay ascending inside a row)
@@ -1153,20 +1077,18 @@ try {
     if (!ok) return nullptr;
     if (hipError_t e = hipStreamSynchronize(nullptr)) { hip_fail(g_err, "hipStreamSynchronize(nullptr)", e); return nullptr; }      // the zero-fills
     return h.release();
-}
-catch (...) { g_err = "out of host memory"; return nullptr; }   // nothing throws across the C boundary
+}, nullptr); }
 
 extern "C" void lcqp_hip_csc_destroy(lcqp_hip_csc_t* h)
-try {
-    delete h;
+{
+    guarded(g_err, [&] { delete h; });
 }
-catch (...) { }   // nothing throws across the C boundary
 
 // d = alpha * op(A) * b + (c ? c : 0);  transposed != 0: op(A) = A' (b has m entries, d has n), else op(A) = A.
 // repeat > 1 re-launches the product for timing; *ms = time per launch.
 extern "C" int lcqp_hip_csc_apply(lcqp_hip_csc_t* h, int transposed, double alpha, const double* b, const double* c, double* d,
                                   int repeat, float* ms)
-try {
+{ return guarded(g_err, [&] {
     if (!h || !b || !d) return LCQP_INVALID_ARGUMENT;
     HIPCHK(g_err, hipSetDevice(h->device));
     const int nin = transposed ? h->m : h->n, nout = transposed ? h->n : h->m;
@@ -1182,8 +1104,7 @@ try {
     if (rc) return rc;
     HIPCHK(g_err, hipMemcpy(d, h->vout, sizeof(double) * nout, hipMemcpyDeviceToHost));
     return 0;
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 // micro-benchmark of the row sweep (wg_rows) on device-resident random data: mode 1 = dots only (A x),
 // 2 = axpy only (A'y), 3 = both in one sweep; *ms = time per launch
@@ -1194,7 +1115,7 @@ __global__ void k_fill_random(double* p, size_t n, uint64_t seed)
 }
 
 extern "C" int lcqp_hip_bench_rows(int batch, int m, int n, int mode, int repeat, float* ms)
-try {
+{ return guarded(g_err, [&] {
     if (n <= 0 || n > 4096 || batch <= 0 || m <= 0) return LCQP_HIP_UNSUPPORTED;
     const int nch = padded_nch(n), np = 128 * nch;
     DevMem tb;
@@ -1210,11 +1131,10 @@ try {
     la.x = (mode & 1) ? dx : nullptr; la.dots = (mode & 1) ? dd : nullptr;
     la.coef = (mode & 2) ? dcf : nullptr; la.outT = (mode & 2) ? dout : nullptr;
     return time_launches(repeat, ms, [&] { lcqp_dispatch(nch, ID_k_util_rows, batch, 0, la); });
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }
 
 extern "C" int lcqp_hip_chol_solve(int batch, int n, const double* K, const double* b, double* x, int repeat, float* ms)
-try {
+{ return guarded(g_err, [&] {
     if (n <= 0 || n > LCQP_MAX_ACTIVE || batch <= 0) return LCQP_HIP_UNSUPPORTED;   // k_chol / k_backsolve use the 35 KiB arena
     const int np = ((n + 63) / 64) * 64, nblk = np / 64;
     DevMem tb;
@@ -1241,5 +1161,4 @@ try {
     for (int i = 0; i < batch; i++) if (fail[i]) { g_err = "matrix not positive definite"; return LCQP_SUBPROBLEM_SOLVER_ERROR; }
     rc = time_launches(repeat, ms, [&] { hipLaunchKernelGGL(k_backsolve, dim3(batch), dim3(WG), 0, 0, np, nblk, dF, drhs, dx); });
     return rc ? rc : download_padded(x, dx, batch, 1, n, np, 1);
-}
-catch (...) { g_err = "out of host memory"; return LCQP_HIP_ERROR; }   // nothing throws across the C boundary
+}); }

@@ -24,6 +24,19 @@ inline int hip_fail(std::string& slot, const char* call, hipError_t e)
         if (e_ != hipSuccess) return lcqp_rt::hip_fail(slot, #call, e_);   \
     } while (0)
 
+// The body of an extern "C" entry point: nothing throws across the C boundary.  An exception (std::bad_alloc from a host container)
+// leaves its message in the arm's slot and returns `fallback` -- LCQP_HIP_ERROR, or nullptr / 0.0 for the entry points that return a
+// pointer / a double, nothing for the void ones.
+template <class F, class R = int>
+__attribute__((always_inline)) inline auto guarded(std::string& err, F body, R fallback = LCQP_HIP_ERROR) -> decltype(body())
+{
+    try { return body(); }
+    catch (...) {
+        err = "out of host memory";
+        if constexpr (!std::is_void_v<decltype(body())>) return fallback;
+    }
+}
+
 // a stream / an event, created by the constructor (its result in `status`) and destroyed by the destructor
 struct Stream {
     hipStream_t s = nullptr;
@@ -156,6 +169,119 @@ int get_solution(std::string& err, H* h, int ndual, double* x, double* y, lcqp_s
     if (stats) HIPCHK(err, hipMemcpy(stats, d.stats, sizeof(lcqp_stats_t) * (size_t)d.B, hipMemcpyDeviceToHost));
     return 0;
 }
+
+// ---- re-solves (*_update / *_resolve / *_launch_counts) and sensitivities: the host state of a handle (members rs and sens) and the
+// entry-point bodies of both arms.  Nothing of it is a kernel argument, and none of it enters the dynamic symbol table of the library.
+#pragma GCC visibility push(hidden)
+struct ResolveState {
+    // the setup on the device belongs to the matrices and options in place: set by run / setup / resolve, cleared by load /
+    // generate_synthetic / set_options (invalidate)
+    bool setupValid = false;
+    // the stored point, working set and factors belong to a solve on the data in place (set by run / resolve, cleared with setupValid):
+    // what *_sensitivity differentiates
+    bool solved = false;
+    std::vector<char> filled;             // [B]: the instance holds a problem
+    double* rhoStart = nullptr;           // [B] on the device: starting penalties of a warm re-solve
+    int nSetups = 0, nLaunches = 0;       // full setups and homotopy launches issued
+    void invalidate() { setupValid = solved = false; }
+};
+
+// *_update: the checks both arms make, in this order, before anything is written
+template <class H>
+int check_update(std::string&, H* h, int first, int count, const double* g, const double* lbL, const double* lbR)
+{
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    const auto& d = h->db;
+    if (first < 0 || count <= 0 || first > d.B - count) return LCQP_INVALID_ARGUMENT;
+    for (int k = 0; k < count; k++) if (!h->rs.filled[(size_t)first + k]) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!g) return LCQP_INVALID_OBJECTIVE_LINEAR_TERM;
+    for (size_t j = 0; j < (size_t)count * d.nComp; j++)
+        if (bnd(lbL, j, 0.0) <= -INFINITY || bnd(lbR, j, 0.0) <= -INFINITY) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
+    return 0;
+}
+
+// *_resolve up to the launches: an error code, RESOLVE_RUNS when no setup belongs to the matrices and options in place (the call is then
+// *_run), 0 when the refresh kernel may stand where the setup stands.  rho0 [B]: every entry finite and positive.
+enum { RESOLVE_RUNS = -1 };
+template <class H>
+int check_resolve(std::string& err, H* h, int mode, const double* rho0, bool loaded)
+{
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (mode != 0 && mode != 1) { err = "resolve: mode is 0 (cold) or 1 (warm)"; return LCQP_INVALID_ARGUMENT; }
+    if (rho0)
+        for (int b = 0; b < h->db.B; b++)
+            if (!(rho0[b] > 0.0) || !std::isfinite(rho0[b])) { err = "resolve: rho0[" + std::to_string(b) + "] is not a finite positive number"; return LCQP_INVALID_ARGUMENT; }
+    if (!loaded) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return h->rs.setupValid ? 0 : RESOLVE_RUNS;
+}
+
+template <class H>
+int launch_counts(H* h, int out[2])
+{
+    if (!h || !out) return LCQP_INVALID_ARGUMENT;
+    out[0] = h->rs.nSetups; out[1] = h->rs.nLaunches;
+    return 0;
+}
+
+// The device buffers of *_sensitivity for `rhs` right-hand sides per instance, grown on demand (layouts at k_sensitivity /
+// k_sparse_sensitivity), and the events around the last launch.  A call is reserve, upload, record(ev0), the arm's launch, record(ev1),
+// download.
+struct SensBuffers {
+    double *v = nullptr, *dg = nullptr, *db = nullptr;
+    int *side = nullptr, *info = nullptr;
+    int rhs = 0;
+    Event ev0, ev1;
+    hipStream_t stream = nullptr;         // of the call in progress, with its sizes: rows = B * nrhs; leading dimensions in elements
+    size_t B = 0, rows = 0, ldV = 0, ldDg = 0, ldDb = 0, nSide = 0;
+
+    int reserve(std::string& err, DevMem& mem, hipStream_t s, size_t nB, int nrhs, size_t ldv, size_t lddg, size_t lddb, size_t nside)
+    {
+        for (hipError_t e : {ev0.status, ev1.status}) if (e != hipSuccess) return hip_fail(err, "hipEventCreate", e);
+        stream = s; B = nB; rows = nB * nrhs; ldV = ldv; ldDg = lddg; ldDb = lddb; nSide = nside;
+        if (nrhs <= rhs) return 0;
+        HIPCHK(err, hipStreamSynchronize(s));
+        for (const void* p : {(const void*)v, (const void*)dg, (const void*)db, (const void*)side, (const void*)info}) mem.release(p);
+        v = dg = db = nullptr; side = info = nullptr; rhs = 0;
+        if (!mem.alloc(err, v, rows * ldV) || !mem.alloc(err, dg, rows * ldDg) || !mem.alloc(err, db, rows * ldDb) ||
+            !mem.alloc(err, side, B * nSide) || !mem.alloc(err, info, B)) return LCQP_HIP_ERROR;
+        rhs = nrhs;
+        return 0;
+    }
+    int upload(std::string& err, const double* hv)
+    {
+        HIPCHK(err, hipMemcpyAsync(v, hv, sizeof(double) * rows * ldV, hipMemcpyHostToDevice, stream));
+        return 0;
+    }
+    // rows of `width` doubles out of device rows of pitch `ld`: a pitched copy where the device rows are padded, a plain one otherwise
+    int rows_out(std::string& err, double* dst, const double* src, size_t width, size_t ld)
+    {
+        if (ld > width) HIPCHK(err, hipMemcpy2DAsync(dst, sizeof(double) * width, src, sizeof(double) * ld, sizeof(double) * width, rows, hipMemcpyDeviceToHost, stream));
+        else HIPCHK(err, hipMemcpyAsync(dst, src, sizeof(double) * rows * width, hipMemcpyDeviceToHost, stream));
+        return 0;
+    }
+    // the results to the host (hdb, hside, hinfo may be NULL); synchronous on return
+    int download(std::string& err, double* hdg, double* hdb, int* hside, int* hinfo, size_t wDg, size_t wDb)
+    {
+        if (int rc = rows_out(err, hdg, dg, wDg, ldDg)) return rc;
+        if (hdb) if (int rc = rows_out(err, hdb, db, wDb, ldDb)) return rc;
+        if (hside) HIPCHK(err, hipMemcpyAsync(hside, side, sizeof(int) * B * nSide, hipMemcpyDeviceToHost, stream));
+        if (hinfo) HIPCHK(err, hipMemcpyAsync(hinfo, info, sizeof(int) * B, hipMemcpyDeviceToHost, stream));
+        HIPCHK(err, hipStreamSynchronize(stream));
+        return 0;
+    }
+};
+
+// *_sensitivity_timing: the kernel time of the last sensitivity launch (ev0 -> ev1)
+template <class H>
+int sensitivity_timing(std::string& err, H* h, float* kernel_ms)
+{
+    if (!h || !kernel_ms || !h->sens.rhs) return LCQP_INVALID_ARGUMENT;
+    HIPCHK(err, hipSetDevice(h->device));
+    HIPCHK(err, hipEventSynchronize(h->sens.ev1));
+    HIPCHK(err, hipEventElapsedTime(kernel_ms, h->sens.ev0, h->sens.ev1));
+    return 0;
+}
+#pragma GCC visibility pop
 
 // Row bounds of instance k of a load (setConstraints / setComplementarityBounds, src/LCQProblem.cpp:563-626, 726-785): lE / uE rows
 // [0, nC) from lbA / ubA (default -inf / +inf), rows nC + i and nC + nComp + i from lbL / ubL and lbR / ubR (default 0 / +inf); lo / ro:

@@ -2369,18 +2369,10 @@ struct lcqp_hip_sparse {
     std::vector<int> qdiagHost;    // entry of Q_ii in the value array
     std::vector<double> diagRatio; // per instance: min_i Q_ii / max_i Q_ii of the loaded Hessian (1: not loaded yet)
     bool loaded = false, ran = false;
-    std::vector<char> filled;      // per instance: a load has given it a problem
-    // re-solves (lcqp_hip_sparse_update / lcqp_hip_sparse_resolve): does the setup on the device belong to the matrices and options in place
-    // (run and resolve set the mark; load and set_options clear it)
-    bool setupValid = false;
-    int nSetups = 0, nLaunches = 0;      // full setups (k_sparse_setup) and homotopy launches issued: lcqp_hip_sparse_launch_counts
-    double* rhoStart = nullptr;          // [B] starting penalties of a warm re-solve (allocated by the first resolve that carries them)
-    // lcqp_hip_sparse_sensitivity: device buffers for sensRhs right-hand sides per instance (grown on demand; layouts at k_sparse_sensitivity)
-    // and the events around its last launch
-    double *sensV = nullptr, *sensDg = nullptr, *sensDb = nullptr;
-    int *sensSide = nullptr, *sensInfo = nullptr;
-    int sensRhs = 0;
-    Event evS0, evS1;
+    // re-solves and sensitivities (lcqp_host_rt.hpp).  This arm has no setup without a solve: setupValid and solved go together;
+    // rhoStart is allocated by the first resolve that carries penalties
+    ResolveState rs;
+    SensBuffers sens;
     explicit lcqp_hip_sparse(int dev) : db(), device(dev) {}
     ~lcqp_hip_sparse() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
 };
@@ -2401,7 +2393,7 @@ static void sp_choose_ordering(lcqp_hip_sparse* h)
 
 // the pattern analysis (lcqp_sparse_pattern.hpp), then the device copies of its arrays and the storage of the batch
 extern "C" lcqp_hip_sparse_t* lcqp_hip_sparse_create(int batch, int nV, int nC, int nComp, const int* Qp, const int* Qi, const int* Ap, const int* Ai, int device)
-try {
+{ return guarded(g_sp_err, [&]() -> lcqp_hip_sparse_t* {
     if (batch <= 0 || nV <= 0 || nC < 0 || nComp <= 0 || !Qp || !Qi || !Ap || !Ai) { g_sp_err = "invalid arguments"; return nullptr; }
     lcqp_pattern::Hooks hooks;
     if (const char* e = std::getenv("LCQP_SPARSE_GENERAL")) hooks.general = std::atoi(e) == 1;      // test hook: the general LDL' on a pattern the band engine would take
@@ -2416,7 +2408,7 @@ try {
     std::unique_ptr<lcqp_hip_sparse> h(new lcqp_hip_sparse(device));
     for (hipError_t e : {h->stream.status, h->ev0.status, h->ev1.status, h->ev2.status})
         if (e != hipSuccess) { hip_fail(g_sp_err, "stream/event creation", e); return nullptr; }
-    h->csr2csc = P.csr2csc; h->hasB = P.hasB; h->qdiagHost = P.qdiag; h->diagRatio.assign(batch, 1.0); h->filled.assign(batch, 0);
+    h->csr2csc = P.csr2csc; h->hasB = P.hasB; h->qdiagHost = P.qdiag; h->diagRatio.assign(batch, 1.0); h->rs.filled.assign(batch, 0);
     SpBatch& d = h->db;
     d.B = batch; d.n = n; d.m = m; d.nC = nC; d.nComp = nComp; d.N = N; d.Np = ((N + 63) / 64) * 64; d.w = w; d.ld = ld; d.nnzQ = nnzQ; d.nnzE = nnzA; d.G = G; d.kb = kb; d.nU = nU; d.nCb = nCb;
     d.general = general ? 1 : 0;
@@ -2519,14 +2511,12 @@ try {
     if (!ok) { g_sp_err = "device allocation failed: " + g_sp_err; return nullptr; }
     if (hipError_t e = hipStreamSynchronize(h->stream)) { hip_fail(g_sp_err, "hipStreamSynchronize(h->stream)", e); return nullptr; }      // the zero-fills
     return h.release();
-}
-catch (...) { g_sp_err = "out of host memory"; return nullptr; }
+}, nullptr); }
 
 extern "C" void lcqp_hip_sparse_destroy(lcqp_hip_sparse_t* h)
-try {
-    delete h;      // ~lcqp_hip_sparse: set the device, synchronise, then the members
+{
+    guarded(g_sp_err, [&] { delete h; });      // ~lcqp_hip_sparse: set the device, synchronise, then the members
 }
-catch (...) { }
 
 extern "C" int lcqp_hip_sparse_bandwidth(const lcqp_hip_sparse_t* h) { return h ? h->db.w : -1; }
 extern "C" int lcqp_hip_sparse_lanes(const lcqp_hip_sparse_t* h) { return h ? h->db.G : -1; }
@@ -2542,32 +2532,30 @@ extern "C" int lcqp_hip_sparse_get_ordering(const lcqp_hip_sparse_t* h, int* per
 
 // storeSteps: the first 4096 iterates
 extern "C" int lcqp_hip_sparse_set_options(lcqp_hip_sparse_t* h, const lcqp_options_t* opt)
-try {
-    if (h) h->setupValid = false;      // the ADMM weights, sigma and the regularisations of the factors come from the options
+{ return guarded(g_sp_err, [&] {
+    if (h) h->rs.invalidate();      // the ADMM weights, sigma and the regularisations of the factors come from the options
     return set_options(g_sp_err, h, opt, 4096);
-}
-catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
+}); }
 
 /* per-iterate trace of one instance of the last run (needs options.storeSteps), as lcqp_hip_batch_get_trace */
 extern "C" int lcqp_hip_sparse_get_trace(lcqp_hip_sparse_t* h, int instance, int cap, double* scalars, double* x, int* len)
-try {
-    return get_trace(g_sp_err, h, instance, cap, scalars, x, len);
+{
+    return guarded(g_sp_err, [&] { return get_trace(g_sp_err, h, instance, cap, scalars, x, len); });
 }
-catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 
 // LCQProblem::loadLCQP (sparse overload, src/LCQProblem.cpp:390-441) for instances [first, first + count): values only -- the
 // pattern was given to lcqp_hip_sparse_create.  Qx: [count][nnzQ]; Ax: [count][nnzA] in the CSC order of the stacked [A; L; R].
 extern "C" int lcqp_hip_sparse_load(lcqp_hip_sparse_t* h, int first, int count, const double* Qx, const double* g, const double* Ax,
                                     const double* lbA, const double* ubA, const double* lbL, const double* ubL, const double* lbR,
                                     const double* ubR, const double* x0, const double* y0)
-try {
+{ return guarded(g_sp_err, [&] {
     if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
     SpBatch& d = h->db;
     const int n = d.n, m = d.m, nK = d.nComp;
     if (first < 0 || count <= 0 || first + count > d.B || !Qx || !Ax) return LCQP_INVALID_ARGUMENT;
     if (!g) return LCQP_INVALID_OBJECTIVE_LINEAR_TERM;
     HIPCHK(g_sp_err, hipSetDevice(h->device));
-    h->setupValid = false;
+    h->rs.invalidate();
     std::vector<double> ex(d.nnzE), nvb((size_t)NV_NUM * n), mvb((size_t)MV_NUM * m), lb(nK), rb(nK);
     for (int k = 0; k < count; k++) {
         const size_t b = (size_t)first + k;
@@ -2588,29 +2576,27 @@ try {
         HIPCHK(g_sp_err, hipMemcpy(d.lbL + b * nK, lb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
         HIPCHK(g_sp_err, hipMemcpy(d.lbR + b * nK, rb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
         HIPCHK(g_sp_err, hipMemcpy(d.info + b, &info, sizeof(info), hipMemcpyHostToDevice));
-        h->filled[b] = 1;
+        h->rs.filled[b] = 1;
     }
     h->loaded = true;
     sp_choose_ordering(h);
     return 0;
-}
-catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
+}); }
 
 /* -DLCQP_SCHED_PROFILE builds: per phase (rows 0 .. PH_NUM-1: start, round, trial, factor, correct, qp end; row PH_NUM: polls without work) the clock
  * ticks (100 MHz), wavefront steps and instances served, summed over the wavefronts of all runs since the handle was created: 3 (PH_NUM + 1) values */
 extern "C" int lcqp_hip_sparse_sched_profile(lcqp_hip_sparse_t* h, unsigned long long* out)
-try {
+{ return guarded(g_sp_err, [&] {
     if (!h || !out) return LCQP_INVALID_ARGUMENT;
     if (int rc = synchronize(g_sp_err, h)) return rc;
     HIPCHK(g_sp_err, hipMemcpy(out, h->db.qprof, sizeof(unsigned long long) * 3 * (PH_NUM + 1), hipMemcpyDeviceToHost));
     return 0;
-}
-catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
+}); }
 
 // the launches of a run or a re-solve on the handle's stream: the setup (or the refresh) from ev0 to ev1, the homotopy from ev1 to ev2
 static int sp_run(lcqp_hip_sparse* h, bool refresh, int mode, const double* rho0)
 {
-    h->setupValid = false;
+    h->rs.invalidate();
     HIPCHK(g_sp_err, hipEventRecord(h->ev0, h->stream));
     switch (h->db.G) {
         case 8: sp_launch<8>(h->db, h->stream, h->ev1, refresh, mode, rho0); break;
@@ -2618,23 +2604,21 @@ static int sp_run(lcqp_hip_sparse* h, bool refresh, int mode, const double* rho0
         case 32: sp_launch<32>(h->db, h->stream, h->ev1, refresh, mode, rho0); break;
         default: sp_launch<64>(h->db, h->stream, h->ev1, refresh, mode, rho0); break;
     }
-    if (!refresh) h->nSetups++;
-    h->nLaunches++;
+    if (!refresh) h->rs.nSetups++;
+    h->rs.nLaunches++;
     HIPCHK(g_sp_err, hipGetLastError());
     HIPCHK(g_sp_err, hipEventRecord(h->ev2, h->stream));
-    h->ran = true;
-    h->setupValid = true;
+    h->ran = h->rs.setupValid = h->rs.solved = true;
     return 0;
 }
 
 extern "C" int lcqp_hip_sparse_run(lcqp_hip_sparse_t* h)
-try {
+{ return guarded(g_sp_err, [&] {
     if (!h || !h->loaded) return LCQP_LCQPOBJECT_NOT_SETUP;
     HIPCHK(g_sp_err, hipSetDevice(h->device));
     sp_choose_ordering(h);
     return sp_run(h, false, 0, nullptr);
-}
-catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
+}); }
 
 // New vectors for instances [first, first + count) of a batch that holds problems: the argument list of lcqp_hip_sparse_load without the
 // values of the matrices, the same packing, the same meaning of NULL.  The whole range is checked before anything is written, and only
@@ -2642,15 +2626,10 @@ catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 extern "C" int lcqp_hip_sparse_update(lcqp_hip_sparse_t* h, int first, int count, const double* g,
                                       const double* lbA, const double* ubA, const double* lbL, const double* ubL,
                                       const double* lbR, const double* ubR, const double* x0, const double* y0)
-try {
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+{ return guarded(g_sp_err, [&] {
+    if (int rc = check_update(g_sp_err, h, first, count, g, lbL, lbR)) return rc;
     SpBatch& d = h->db;
     const int n = d.n, m = d.m, nK = d.nComp;
-    if (first < 0 || count <= 0 || first > d.B - count) return LCQP_INVALID_ARGUMENT;
-    for (int k = 0; k < count; k++) if (!h->filled[(size_t)first + k]) return LCQP_LCQPOBJECT_NOT_SETUP;
-    if (!g) return LCQP_INVALID_OBJECTIVE_LINEAR_TERM;
-    for (size_t j = 0; j < (size_t)count * nK; j++)
-        if (bnd(lbL, j, 0.0) <= -INFINITY || bnd(lbR, j, 0.0) <= -INFINITY) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
     HIPCHK(g_sp_err, hipSetDevice(h->device));
     HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));      // a run in flight reads what is written below
     static_assert(MV_U == MV_L + 1, "l and u go over in one copy");
@@ -2671,37 +2650,27 @@ try {
         HIPCHK(g_sp_err, hipMemcpy(&d.info[b].hasY0, &hasY0, sizeof(int), hipMemcpyHostToDevice));
     }
     return 0;
-}
-catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
+}); }
 
 // Solve again on the setup in place: k_sparse_refresh where a run has k_sparse_setup, then the homotopy launch.  Without a setup that
 // belongs to the matrices and options in place this is lcqp_hip_sparse_run.
 extern "C" int lcqp_hip_sparse_resolve(lcqp_hip_sparse_t* h, int mode, const double* rho0)
-try {
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    if (mode != 0 && mode != 1) { g_sp_err = "resolve: mode is 0 (cold) or 1 (warm)"; return LCQP_INVALID_ARGUMENT; }
+{ return guarded(g_sp_err, [&] {
+    if (int rc = check_resolve(g_sp_err, h, mode, rho0, h && h->loaded)) return rc == RESOLVE_RUNS ? lcqp_hip_sparse_run(h) : rc;
     const int B = h->db.B;
-    if (rho0)
-        for (int b = 0; b < B; b++)
-            if (!(rho0[b] > 0.0) || !std::isfinite(rho0[b])) { g_sp_err = "resolve: rho0[" + std::to_string(b) + "] is not a finite positive number"; return LCQP_INVALID_ARGUMENT; }
-    if (!h->loaded) return LCQP_LCQPOBJECT_NOT_SETUP;
-    if (!h->setupValid) return lcqp_hip_sparse_run(h);
     HIPCHK(g_sp_err, hipSetDevice(h->device));
     const bool withRho = mode == 1 && rho0;
     if (withRho) {
-        if (!h->rhoStart && !h->mem.alloc(g_sp_err, h->rhoStart, (size_t)B)) { g_sp_err = "device allocation failed: " + g_sp_err; return LCQP_HIP_ERROR; }
+        if (!h->rs.rhoStart && !h->mem.alloc(g_sp_err, h->rs.rhoStart, (size_t)B)) { g_sp_err = "device allocation failed: " + g_sp_err; return LCQP_HIP_ERROR; }
         HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));      // the zero-fill of a fresh buffer, a run in flight that reads an older one
-        HIPCHK(g_sp_err, hipMemcpy(h->rhoStart, rho0, sizeof(double) * (size_t)B, hipMemcpyHostToDevice));
+        HIPCHK(g_sp_err, hipMemcpy(h->rs.rhoStart, rho0, sizeof(double) * (size_t)B, hipMemcpyHostToDevice));
     }
-    return sp_run(h, true, mode, withRho ? h->rhoStart : nullptr);
-}
-catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
+    return sp_run(h, true, mode, withRho ? h->rs.rhoStart : nullptr);
+}); }
 
 extern "C" int lcqp_hip_sparse_launch_counts(lcqp_hip_sparse_t* h, int out[2])
 {
-    if (!h || !out) return LCQP_INVALID_ARGUMENT;
-    out[0] = h->nSetups; out[1] = h->nLaunches;
-    return 0;
+    return launch_counts(h, out);
 }
 
 // ---- solution sensitivities (DESIGN.md section 3a''): one launch of k_sparse_sensitivity on the handle's stream, host buffers in and out ----
@@ -2711,27 +2680,19 @@ static void sp_launch_sensitivity(const lcqp_hip_sparse* h, int nrhs)
     const SpBatch& db = h->db;
     const int ipw = 64 / G, grid = (db.B + ipw - 1) / ipw;
     const size_t ldsBytes = (G == 64 && db.general) ? sizeof(double) * (size_t)(G * G + 16 * G) : 0;      // the window of the general solve
-    hipLaunchKernelGGL(k_sparse_sensitivity<G>, dim3(grid), dim3(WGS), ldsBytes, h->stream, db, nrhs, h->sensV, h->sensDg, h->sensDb, h->sensSide, h->sensInfo);
+    hipLaunchKernelGGL(k_sparse_sensitivity<G>, dim3(grid), dim3(WGS), ldsBytes, h->stream, db, nrhs, h->sens.v, h->sens.dg, h->sens.db, h->sens.side, h->sens.info);
 }
 
 extern "C" int lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
-try {
+{ return guarded(g_sp_err, [&] {
     if (!h || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
-    if (!h->setupValid) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
     SpBatch& d = h->db;
+    SensBuffers& sb = h->sens;
     HIPCHK(g_sp_err, hipSetDevice(h->device));
-    for (hipError_t e : {h->evS0.status, h->evS1.status}) if (e != hipSuccess) return hip_fail(g_sp_err, "hipEventCreate", e);
-    const size_t B = d.B, n = d.n, m = d.m, K = nrhs;
-    if (nrhs > h->sensRhs) {
-        HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));
-        for (const void* p : {(const void*)h->sensV, (const void*)h->sensDg, (const void*)h->sensDb, (const void*)h->sensSide, (const void*)h->sensInfo}) h->mem.release(p);
-        h->sensV = h->sensDg = h->sensDb = nullptr; h->sensSide = h->sensInfo = nullptr; h->sensRhs = 0;
-        if (!h->mem.alloc(g_sp_err, h->sensV, B * K * n) || !h->mem.alloc(g_sp_err, h->sensDg, B * K * n) || !h->mem.alloc(g_sp_err, h->sensDb, B * K * m) ||
-            !h->mem.alloc(g_sp_err, h->sensSide, B * m) || !h->mem.alloc(g_sp_err, h->sensInfo, B)) return LCQP_HIP_ERROR;
-        h->sensRhs = nrhs;
-    }
-    HIPCHK(g_sp_err, hipMemcpyAsync(h->sensV, v, sizeof(double) * B * K * n, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(g_sp_err, hipEventRecord(h->evS0, h->stream));
+    if (int rc = sb.reserve(g_sp_err, h->mem, h->stream, d.B, nrhs, d.n, d.n, d.m, d.m)) return rc;
+    if (int rc = sb.upload(g_sp_err, v)) return rc;
+    HIPCHK(g_sp_err, hipEventRecord(sb.ev0, h->stream));
     switch (d.G) {
         case 8: sp_launch_sensitivity<8>(h, nrhs); break;
         case 16: sp_launch_sensitivity<16>(h, nrhs); break;
@@ -2739,48 +2700,34 @@ try {
         default: sp_launch_sensitivity<64>(h, nrhs); break;
     }
     HIPCHK(g_sp_err, hipGetLastError());
-    HIPCHK(g_sp_err, hipEventRecord(h->evS1, h->stream));
-    HIPCHK(g_sp_err, hipMemcpyAsync(dg, h->sensDg, sizeof(double) * B * K * n, hipMemcpyDeviceToHost, h->stream));
-    if (db) HIPCHK(g_sp_err, hipMemcpyAsync(db, h->sensDb, sizeof(double) * B * K * m, hipMemcpyDeviceToHost, h->stream));
-    if (side) HIPCHK(g_sp_err, hipMemcpyAsync(side, h->sensSide, sizeof(int) * B * m, hipMemcpyDeviceToHost, h->stream));
-    if (info) HIPCHK(g_sp_err, hipMemcpyAsync(info, h->sensInfo, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));
-    return 0;
-}
-catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
+    HIPCHK(g_sp_err, hipEventRecord(sb.ev1, h->stream));
+    return sb.download(g_sp_err, dg, db, side, info, d.n, d.m);
+}); }
 
 extern "C" int lcqp_hip_sparse_sensitivity_timing(lcqp_hip_sparse_t* h, float* kernel_ms)
-try {
-    if (!h || !kernel_ms || !h->sensRhs) return LCQP_INVALID_ARGUMENT;
-    HIPCHK(g_sp_err, hipSetDevice(h->device));
-    HIPCHK(g_sp_err, hipEventSynchronize(h->evS1));
-    HIPCHK(g_sp_err, hipEventElapsedTime(kernel_ms, h->evS0, h->evS1));
-    return 0;
+{
+    return guarded(g_sp_err, [&] { return sensitivity_timing(g_sp_err, h, kernel_ms); });
 }
-catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 
 extern "C" int lcqp_hip_sparse_synchronize(lcqp_hip_sparse_t* h)
-try {
-    return synchronize(g_sp_err, h);
+{
+    return guarded(g_sp_err, [&] { return synchronize(g_sp_err, h); });
 }
-catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 
 extern "C" int lcqp_hip_sparse_last_timing(lcqp_hip_sparse_t* h, float* setup_ms, float* solve_ms)
-try {
-    return last_timing(g_sp_err, h, setup_ms, solve_ms);
+{
+    return guarded(g_sp_err, [&] { return last_timing(g_sp_err, h, setup_ms, solve_ms); });
 }
-catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 
 extern "C" int lcqp_hip_sparse_get_solution(lcqp_hip_sparse_t* h, double* x, double* y, lcqp_stats_t* stats)
-try {
-    return get_solution(g_sp_err, h, h ? h->db.m : 0, x, y, stats);
+{
+    return guarded(g_sp_err, [&] { return get_solution(g_sp_err, h, h ? h->db.m : 0, x, y, stats); });
 }
-catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
 
 // -DLCQP_PROFILE builds (tools/gpu.py sparse_profile): mean clock ticks per instance and phase of the last run
 // (products, assembly, factorisation, forward sweeps, backward sweeps, vector operations, LCQP level, -)
 extern "C" int lcqp_hip_sparse_read_profile(lcqp_hip_sparse_t* h, double* out)
-try {
+{ return guarded(g_sp_err, [&] {
 #ifdef LCQP_PROFILE
     if (!h || !out) return LCQP_INVALID_ARGUMENT;
     SpBatch& d = h->db;
@@ -2793,13 +2740,12 @@ try {
     (void)h; (void)out;
     return LCQP_HIP_UNSUPPORTED;
 #endif
-}
-catch (...) { g_sp_err = "out of host memory"; return LCQP_HIP_ERROR; }
+}); }
 
 // algorithmic bytes of the last run (setup + homotopy), counted by the kernels: CSR values and indices of every sparse product,
 // band storage read and written by every assembly, factorisation and solve
 extern "C" double lcqp_hip_sparse_algorithmic_bytes(lcqp_hip_sparse_t* h)
-try {
+{ return guarded(g_sp_err, [&] {
     if (!h) return 0.0;
     SpBatch& d = h->db;
     if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return 0.0;
@@ -2808,5 +2754,4 @@ try {
     double tot = 0.0;
     for (auto& i : info) tot += i.bytes;
     return tot;
-}
-catch (...) { return 0.0; }
+}, 0.0); }

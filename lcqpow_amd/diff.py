@@ -42,7 +42,7 @@ class LCQPSolveFunction(torch.autograd.Function):
         if ubA is not None: kw["ubA"] = _host(ubA)
         rc = bt.update(0, bt.B, _host(g), **kw)
         if rc != 0:
-            raise RuntimeError(f"update failed with code {rc}: {layer.last_error()}")
+            raise RuntimeError(f"update failed with code {rc}: {bt._last_error()}")
         if layer.solves == 0:
             bt.run()
         else:
@@ -94,9 +94,6 @@ class BatchLCQPLayer:
         self.bounds = {k: capi._arr(v) for k, v in (bounds or {}).items() if v is not None}
         self.y = self.stats = self.info = None
 
-    def last_error(self):
-        return capi.last_error()
-
     def __call__(self, g, lbA=None, ubA=None):
         return LCQPSolveFunction.apply(self, g, lbA, ubA)
 
@@ -106,6 +103,3 @@ class SparseBatchLCQPLayer(BatchLCQPLayer):
     the vectors of SparseBatchLCQP.update the batch was loaded with (lbA, ubA, lbL, ubL, lbR, ubR; the sparse arm has no box)."""
     sparse = True
     bound_keys = tuple(k for k in BOUND_KEYS if k not in ("lb", "ub"))
-
-    def last_error(self):
-        return capi.lib().lcqp_hip_sparse_last_error().decode()

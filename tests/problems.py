@@ -300,3 +300,58 @@ def lcqp_kkt_residuals(d, x, y, rho):
             at_lo = np.isfinite(lo) & (v - lo <= tol); at_hi = np.isfinite(hi) & (hi - v <= tol)
         sign = max(sign, np.where(~at_lo, np.maximum(yy, 0.0), 0.0).max(initial=0.0), np.where(~at_hi, np.maximum(-yy, 0.0), 0.0).max(initial=0.0))
     return float(stat), float(feas), compl, float(sign)
+
+
+# ---- re-solves and sensitivities (tests/test_gpu_*resolve*.py, test_gpu_*sensitivity*.py) ---------------------------------------------
+VEC_KEYS = ("lbL", "ubL", "lbR", "ubR", "lbA", "ubA", "lb", "ub", "x0", "y0")      # the optional vectors of load / update (the sparse arm: without lb, ub)
+SMALL, MID = (64, 32, 8), (512, 256, 64)      # (nV, nC, nComp) of the sparse synthetic workload
+OPT = dict(perturbStep=0, printLevel=0)
+
+
+def random_lcqp(rng, n, nC, nComp, box, shifted):
+    M = rng.uniform(-1, 1, (n, n)); Q = M.T @ M / n + np.eye(n)
+    L = np.zeros((nComp, n)); R = np.zeros((nComp, n))
+    for i in range(nComp):
+        L[i, i] = 1.0; R[i, nComp + i] = 1.0
+    xs = rng.uniform(0.2, 1, n); xs[nComp:2 * nComp] = 0.0
+    A = rng.uniform(-1, 1, (nC, n)) / np.sqrt(n)
+    d = dict(Q=Q, g=rng.uniform(-1, 1, n), L=L, R=R, A=A, lbA=A @ xs - rng.uniform(0.1, 1, nC), ubA=A @ xs + rng.uniform(0.1, 1, nC),
+             nV=n, nC=nC, nComp=nComp)
+    if shifted:
+        d.update(lbL=rng.uniform(-0.2, 0.0, nComp), lbR=rng.uniform(-0.2, 0.0, nComp))
+    if box:
+        d.update(lb=xs - 2.0, ub=np.where(rng.random(n) < 0.5, xs + 2.0, np.inf))
+    return d
+
+
+def perturbed(d, seed, box_too=True):
+    """the 2 % recipe: g (1 + 0.02 z); lbA and ubA both shifted by 0.02 (ubA - lbA) z' (width 1 where infinite); z, z' from default_rng(seed)
+    in that order.  Box bounds (finite ones) move by 0.02 z'' as well: values change, the set of bounded variables does not."""
+    rng = np.random.default_rng(seed)
+    z = rng.standard_normal(d["nV"]); z2 = rng.standard_normal(d["nC"])
+    w = d["ubA"] - d["lbA"]
+    w = np.where(np.isfinite(w), w, 1.0)
+    e = dict(d, g=d["g"] * (1.0 + 0.02 * z), lbA=d["lbA"] + 0.02 * w * z2, ubA=d["ubA"] + 0.02 * w * z2)
+    if box_too and d.get("lb") is not None:
+        z3 = rng.standard_normal(d["nV"])
+        e.update(lb=d["lb"] + 0.02 * z3, ub=d["ub"] + 0.02 * z3)
+    return e
+
+
+def moved(d, seed):
+    """perturbed() for the sparse arm, which has no box: the same draws in the same order"""
+    return perturbed(d, seed, box_too=False)
+
+
+def instances(shape, B):
+    return [sparse_instance(b, *shape) for b in range(B)]
+
+
+def circle_instances(B):
+    import scipy.sparse as sp
+    d = circle(100)
+    Q = sp.csc_matrix(d["Q"]); E = sp.csc_matrix(np.vstack([d["A"], d["L"], d["R"]]))
+    Q.sort_indices(); E.sort_indices()
+    one = dict(Q=Q, E=E, g=np.asarray(d["g"], dtype=float), lbA=np.asarray(d["lbA"], dtype=float), ubA=np.asarray(d["ubA"], dtype=float),
+               x0=np.asarray(d["x0"], dtype=float), nV=d["nV"], nC=d["nC"], nComp=d["nComp"])
+    return [dict(one) for _ in range(B)]

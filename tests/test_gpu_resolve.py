@@ -13,80 +13,18 @@ import numpy as np
 import pytest
 
 import problems as P
+from batch_helpers import assert_same_bits, load_all, result, stack, update_all
+from problems import VEC_KEYS, perturbed, random_lcqp
 
 pytestmark = pytest.mark.gpu
 
 X_TOL, Y_TOL = 1e-9, 1e-7
-VEC_KEYS = ("lbL", "ubL", "lbR", "ubR", "lbA", "ubA", "lb", "ub", "x0", "y0")
 SHAPES = ((64, 128, 16, 48), (256, 512, 64, 24))      # (n, nC, nComp, instances): the 72 inputs of the warm-start checks
-
-
-def random_lcqp(rng, n, nC, nComp, box, shifted):
-    M = rng.uniform(-1, 1, (n, n)); Q = M.T @ M / n + np.eye(n)
-    L = np.zeros((nComp, n)); R = np.zeros((nComp, n))
-    for i in range(nComp):
-        L[i, i] = 1.0; R[i, nComp + i] = 1.0
-    xs = rng.uniform(0.2, 1, n); xs[nComp:2 * nComp] = 0.0
-    A = rng.uniform(-1, 1, (nC, n)) / np.sqrt(n)
-    d = dict(Q=Q, g=rng.uniform(-1, 1, n), L=L, R=R, A=A, lbA=A @ xs - rng.uniform(0.1, 1, nC), ubA=A @ xs + rng.uniform(0.1, 1, nC),
-             nV=n, nC=nC, nComp=nComp)
-    if shifted:
-        d.update(lbL=rng.uniform(-0.2, 0.0, nComp), lbR=rng.uniform(-0.2, 0.0, nComp))
-    if box:
-        d.update(lb=xs - 2.0, ub=np.where(rng.random(n) < 0.5, xs + 2.0, np.inf))
-    return d
-
-
-def perturbed(d, seed, box_too=True):
-    """the 2 % recipe: g (1 + 0.02 z); lbA and ubA both shifted by 0.02 (ubA - lbA) z' (width 1 where infinite); z, z' from default_rng(seed)
-    in that order.  Box bounds (finite ones) move by 0.02 z'' as well: values change, the set of bounded variables does not."""
-    rng = np.random.default_rng(seed)
-    z = rng.standard_normal(d["nV"]); z2 = rng.standard_normal(d["nC"])
-    w = d["ubA"] - d["lbA"]
-    w = np.where(np.isfinite(w), w, 1.0)
-    e = dict(d, g=d["g"] * (1.0 + 0.02 * z), lbA=d["lbA"] + 0.02 * w * z2, ubA=d["ubA"] + 0.02 * w * z2)
-    if box_too and d.get("lb") is not None:
-        z3 = rng.standard_normal(d["nV"])
-        e.update(lb=d["lb"] + 0.02 * z3, ub=d["ub"] + 0.02 * z3)
-    return e
-
-
-def stack(ds, key):
-    return None if ds[0].get(key) is None else np.stack([d[key] for d in ds])
-
-
-def load_all(bt, ds):
-    rc = bt.load(0, len(ds), stack(ds, "Q"), stack(ds, "g"), stack(ds, "L"), stack(ds, "R"), A=stack(ds, "A"),
-                 **{k: stack(ds, k) for k in VEC_KEYS})
-    assert rc == 0, rc
-
-
-def update_all(bt, ds, first=0):
-    rc = bt.update(first, len(ds), stack(ds, "g"), **{k: stack(ds, k) for k in VEC_KEYS})
-    assert rc == 0, (rc, bt_error())
 
 
 def bt_error():
     import lcqpow_amd
     return lcqpow_amd.capi.last_error()
-
-
-def result(bt, trace=False):
-    x, y, st = bt.solution()
-    out = dict(x=x, y=y, st=st, work=bt.work_sums())
-    if trace:
-        out["trace"] = [bt.trace(b) for b in range(bt.B)]
-    return out
-
-
-def assert_same_bits(a, b, rows=None):
-    rows = range(len(a["st"])) if rows is None else rows
-    for i in rows:
-        assert np.array_equal(a["x"][i], b["x"][i]) and np.array_equal(a["y"][i], b["y"][i]), i
-        assert a["st"][i] == b["st"][i], (i, a["st"][i], b["st"][i])
-        if "trace" in a:
-            assert np.array_equal(a["trace"][i][0], b["trace"][i][0]) and np.array_equal(a["trace"][i][1], b["trace"][i][1]), i
-            assert len(a["trace"][i][0]) == a["st"][i]["iterTotal"]
 
 
 def fresh(hip, ds, opt, B=None, trace=False):
@@ -397,7 +335,7 @@ def test_argument_checks_precede_every_device_call(hip):
         bt.update(0, 1, np.zeros(n + 1))
     with pytest.raises(ValueError):
         bt.resolve(warm=True, rho0=np.ones(B + 1))
-    for bad in ([1.0, 0.0], [-1.0, 1.0], [np.nan, 1.0]):
+    for bad in ([1.0, 0.0], [-1.0, 1.0], [np.nan, 1.0], [np.inf, 1.0]):
         with pytest.raises(RuntimeError, match="rho0"):
             bt.resolve(warm=True, rho0=bad)
     assert L.lcqp_hip_batch_resolve(bt.h, 2, None) == 100

@@ -7,7 +7,7 @@
 re-solve, bound stationarityTolerance |v|_1 / (h lambda_min(Q)) from the solver's exit test.   5  the call changes nothing.
 6  flag bits.   7  the QP twin.   8  torch.
 
-Problems: tests/test_gpu_resolve.py::random_lcqp with default_rng(1000 + instance).  Every figure is printed before it is asserted."""
+Problems: tests/problems.py::random_lcqp with default_rng(1000 + instance).  Every figure is printed before it is asserted."""
 import ctypes
 import functools
 import warnings
@@ -16,11 +16,11 @@ import numpy as np
 import pytest
 
 import problems as P
-from test_gpu_resolve import assert_same_bits, load_all, perturbed, random_lcqp, result, stack, update_all
+from batch_helpers import assert_same_bits, grown_and_fresh, kkt_reference, load_all, result, stack, update_all
+from problems import perturbed, random_lcqp
 
 pytestmark = pytest.mark.gpu
 
-LD = np.longdouble
 H_FD = 1e-6
 #          n,  nC, nComp, B, box, shifted, equalities     path
 SHAPES = {"np128": (40, 20, 8, 6, False, False, False),
@@ -63,21 +63,6 @@ def rows_and_bounds(d):
 def working_rows(ws):
     sr = ws["slot_row"][:ws["ns"]]
     return np.sort(sr[sr >= 0])
-
-
-def kkt_reference(Q, EW, V, extended):
-    """dg, mu for the columns of V: K [d; mu] = [v; 0]; float64 LU, refined with long-double residuals when `extended`.  Also cond_2(K)."""
-    n, m = Q.shape[0], EW.shape[0]
-    K = np.zeros((n + m, n + m)); K[:n, :n] = Q; K[:n, n:] = EW.T; K[n:, :n] = EW
-    rhs = np.zeros((n + m, V.shape[1])); rhs[:n] = V
-    sol = np.linalg.solve(K, rhs)
-    if extended:
-        KL, rl, sl = K.astype(LD), rhs.astype(LD), sol.astype(LD)
-        for _ in range(3):
-            sl = sl + np.linalg.solve(K, (rl - KL @ sl).astype(np.float64)).astype(LD)
-        sol = sl
-    ev = np.abs(np.linalg.eigvalsh(K))
-    return -sol[:n], sol[n:], float(ev.max() / ev.min())
 
 
 @functools.lru_cache(maxsize=None)
@@ -270,6 +255,18 @@ def test_the_call_changes_nothing(hip, n, nC, nComp, B, box):
         bt.close()
     assert_same_bits(out[0], out[1])
     assert np.array_equal(out[0]["work"], out[1]["work"])
+
+
+def test_buffers_grow_from_a_live_allocation(hip):
+    n, nC, nComp, B = 40, 20, 8, 2
+    ds = [random_lcqp(np.random.default_rng(1000 + b), n, nC, nComp, False, False) for b in range(B)]
+
+    def solved():
+        bt = hip.BatchLCQP(B, n, nC, nComp, opt=hip.default_options(perturbStep=0))
+        load_all(bt, ds)
+        bt.run()
+        return bt
+    grown_and_fresh(solved, np.random.default_rng(77).standard_normal((B, 3, n)))
 
 
 # ---- 6: flags ------------------------------------------------------------------------------------------------------------------------

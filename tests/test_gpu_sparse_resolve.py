@@ -11,65 +11,12 @@ import numpy as np
 import pytest
 
 import problems as P
+from batch_helpers import assert_same_bits, handle, result, stack, update_all
+from problems import MID, OPT, SMALL, circle_instances, instances, moved
 
 pytestmark = pytest.mark.gpu
 
 X_TOL, Y_TOL = 1e-8, 1e-6
-SMALL, MID = (64, 32, 8), (512, 256, 64)
-VEC_KEYS = ("lbA", "ubA", "lbL", "ubL", "lbR", "ubR", "x0", "y0")
-OPT = dict(perturbStep=0, printLevel=0)
-
-
-# ---- inputs ----------------------------------------------------------------------------------------------------------------------------
-def instances(shape, B):
-    return [P.sparse_instance(b, *shape) for b in range(B)]
-
-
-def moved(d, seed):
-    """the 2 % recipe of tests/test_gpu_resolve.py::perturbed without the box part: g (1 + 0.02 z); lbA and ubA both shifted by
-    0.02 (ubA - lbA) z'; z, z' from default_rng(seed) in that order"""
-    rng = np.random.default_rng(seed)
-    z = rng.standard_normal(d["nV"]); z2 = rng.standard_normal(d["nC"])
-    w = d["ubA"] - d["lbA"]
-    w = np.where(np.isfinite(w), w, 1.0)
-    return dict(d, g=d["g"] * (1.0 + 0.02 * z), lbA=d["lbA"] + 0.02 * w * z2, ubA=d["ubA"] + 0.02 * w * z2)
-
-
-def stack(ds, key):
-    return None if ds[0].get(key) is None else np.stack([d[key] for d in ds])
-
-
-def handle(hip, ds, opt, B=None):
-    """a handle for the pattern of ds[0], its instances loaded"""
-    d = ds[0]
-    sb = hip.SparseBatchLCQP(B or len(ds), d["nV"], d["nC"], d["nComp"], d["Q"], d["E"], opt=opt)
-    rc = sb.load(0, len(ds), np.stack([q["Q"].data for q in ds]), stack(ds, "g"), np.stack([q["E"].data for q in ds]),
-                 **{k: stack(ds, k) for k in VEC_KEYS})
-    assert rc == 0, rc
-    return sb
-
-
-def update_all(sb, ds, first=0):
-    rc = sb.update(first, len(ds), stack(ds, "g"), **{k: stack(ds, k) for k in VEC_KEYS})
-    assert rc == 0, rc
-
-
-def result(sb, trace=False):
-    x, y, st = sb.solution()
-    out = dict(x=x, y=y, st=st)
-    if trace:
-        out["trace"] = [sb.trace(b) for b in range(sb.B)]
-    return out
-
-
-def assert_same_bits(a, b, rows=None):
-    rows = range(len(a["st"])) if rows is None else rows
-    for i in rows:
-        assert np.array_equal(a["x"][i], b["x"][i]) and np.array_equal(a["y"][i], b["y"][i]), i
-        assert a["st"][i] == b["st"][i], (i, a["st"][i], b["st"][i])
-        if "trace" in a:
-            assert np.array_equal(a["trace"][i][0], b["trace"][i][0]) and np.array_equal(a["trace"][i][1], b["trace"][i][1]), i
-            assert len(a["trace"][i][0]) == a["st"][i]["iterTotal"]
 
 
 def fresh(hip, ds, opt, trace=False):
@@ -80,16 +27,6 @@ def fresh(hip, ds, opt, trace=False):
     assert sb.launch_counts() == (1, 1)
     sb.close()
     return out
-
-
-def circle_instances(B):
-    import scipy.sparse as sp
-    d = P.circle(100)
-    Q = sp.csc_matrix(d["Q"]); E = sp.csc_matrix(np.vstack([d["A"], d["L"], d["R"]]))
-    Q.sort_indices(); E.sort_indices()
-    one = dict(Q=Q, E=E, g=np.asarray(d["g"], dtype=float), lbA=np.asarray(d["lbA"], dtype=float), ubA=np.asarray(d["ubA"], dtype=float),
-               x0=np.asarray(d["x0"], dtype=float), nV=d["nV"], nC=d["nC"], nComp=d["nComp"])
-    return [dict(one) for _ in range(B)]
 
 
 # ---- the oracle, asked once per input ----------------------------------------------------------------------------------------------------

@@ -1,25 +1,23 @@
 """Solution sensitivities of the sparse arm (lcqp_hip_sparse_sensitivity, SparseBatchLCQPLayer; DESIGN.md section 3a'').
 
 1  dg, db against numpy on the device's own working set W (from `side`): K0 = [[Q, E_W'], [E_W, 0]] dense from the CSC data,
-   K0 [d; mu] = [v; 0], dg = -d, db_W = mu; float64 LU refined with np.longdouble residuals (kkt_reference of the dense test); bound
+   K0 [d; mu] = [v; 0], dg = -d, db_W = mu; float64 LU refined with np.longdouble residuals (kkt_reference of tests/batch_helpers.py); bound
    max|delta| <= 1e-12 (nV + |W|) cond_2(K0) |v|_inf.
 2  W is the active set by value, and info.   3  structure that needs no reference.   4  central differences through the product's own
 warm re-solves, bound stationarityTolerance |v|_1 / (h lambda_min(Q)); fixes the sign of db.   5  the call changes nothing.
 6  state errors and a failed instance.   7  torch.
 
-Shapes: the ones tests/test_gpu_sparse_resolve.py uses to reach every engine.  Every figure is printed before it is asserted."""
-import contextlib
+Shapes: the ones tests/test_gpu_sparse_resolve.py uses to reach every engine (tests/problems.py).  Every figure is printed before it is asserted."""
 import ctypes
 import functools
-import os
 import warnings
 
 import numpy as np
 import pytest
 
 import problems as P
-from test_gpu_sensitivity import kkt_reference
-from test_gpu_sparse_resolve import MID, OPT, SMALL, assert_same_bits, circle_instances, handle, instances, moved, result, update_all
+from batch_helpers import assert_same_bits, environment, grown_and_fresh, handle, kkt_reference, result, update_all
+from problems import MID, OPT, SMALL, circle_instances, instances, moved
 
 pytestmark = pytest.mark.gpu
 
@@ -34,19 +32,6 @@ CASES = {"small": (("synth", SMALL, 6), {}),
          "mid, general ldl": (("synth", MID, 2), {"LCQP_SPARSE_GENERAL": "1"}),
          "grid, general ldl": (("grid", (44, 300, 200), 2), {}),
          "bordered circle": (("circle", 100, 2), {})}
-
-
-@contextlib.contextmanager
-def environment(env):
-    """the test hooks are read when a handle is created"""
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
-        yield
-    finally:
-        for k, v in old.items():
-            if v is None: os.environ.pop(k, None)
-            else: os.environ[k] = v
 
 
 def instances_of(key):
@@ -252,6 +237,16 @@ def test_the_call_changes_nothing(hip, case, warm):
         assert sb.launch_counts() == (1, 2)
         sb.close()
     assert_same_bits(out[0], out[1])
+
+
+def test_buffers_grow_from_a_live_allocation(hip):
+    ds = instances(SMALL, 2)
+
+    def solved():
+        sb = handle(hip, ds, hip.default_options(**OPT))
+        sb.run()
+        return sb
+    grown_and_fresh(solved, np.random.default_rng(77).standard_normal((2, 3, SMALL[0])))
 
 
 # ---- 6: state errors and a failed instance -------------------------------------------------------------------------------------------
