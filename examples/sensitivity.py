@@ -5,6 +5,7 @@ printed.  The targets are solutions of the same LCQPs for other linear terms, so
 
     python examples/sensitivity.py
     python examples/sensitivity.py sparse      # the same fit on the sparse arm: 16 banded LCQPs (n = 64), lcqp_hip_sparse_sensitivity
+    python examples/sensitivity.py jacobian    # the full Jacobians dx/dg of the 64 LCQPs (lcqp_hip_batch_jacobian): |Jg - Jg'| and the kernel time
 """
 import os
 import sys
@@ -63,7 +64,15 @@ def main():
     st = lambda k: np.stack([d[k] for d in ds])
     bt = la.BatchLCQP(B, n, nC, nComp, opt=la.default_options(perturbStep=0))
     assert bt.load(0, B, st("Q"), st("g"), st("L"), st("R"), A=st("A"), lbA=st("lbA"), ubA=st("ubA")) == 0
-    fit(BatchLCQPLayer(bt, bounds=dict(lbA=st("lbA"), ubA=st("ubA"))), st("g"), rng, B)
+    layer = BatchLCQPLayer(bt, bounds=dict(lbA=st("lbA"), ubA=st("ubA")))
+    if sys.argv[1:] == ["jacobian"]:
+        with torch.no_grad():
+            layer(torch.as_tensor(st("g")))
+        Jg = layer.jacobian()
+        print("Jg %s: max |Jg - Jg'| = %.3e, kernel %.4f ms, flagged instances %d"
+              % (tuple(Jg.shape), (Jg - Jg.transpose(1, 2)).abs().max().item(), bt.sensitivity_kernel_ms(), int(np.count_nonzero(layer.info))))
+    else:
+        fit(layer, st("g"), rng, B)
     bt.close()
 
 

@@ -111,6 +111,10 @@ void lcqp_hip_qp_get_counters(lcqp_hip_qp_t* qp, int* admm, int* trials, int* fa
 /* lcqp_hip_batch_sensitivity (below) for the batch of one this object holds: the derivatives of the solution of the convex QP last solved,
  * dg [nrhs][nV], db and side [.][nV + nC], info [1].  LCQP_LCQPOBJECT_NOT_SETUP before the first successful solve and after set_options. */
 int  lcqp_hip_qp_sensitivity(lcqp_hip_qp_t* qp, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
+/* lcqp_hip_batch_sensitivity_blocked and lcqp_hip_batch_jacobian (below) for the batch of one: dg [nrhs][nV], db [nrhs][nV + nC];
+ * Jg [nV][nV], Jb [nV][nV + nC] (or NULL), side [nV + nC], info [1].  nV > 512: the vector kernel, the bits of lcqp_hip_qp_sensitivity. */
+int  lcqp_hip_qp_sensitivity_blocked(lcqp_hip_qp_t* qp, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
+int  lcqp_hip_qp_jacobian(lcqp_hip_qp_t* qp, double* Jg, double* Jb, int* side, int* info);
 /* test and diagnostic entry points: lcqp_hip_batch_read_setup / lcqp_hip_batch_read_working_set (below) for the batch of one this object
  * holds; LCQP_LCQPOBJECT_NOT_SETUP before its first solve */
 int  lcqp_hip_qp_read_setup(lcqp_hip_qp_t* qp, int dims[9], double scal[2], double* C, double* F1, double* D1, double* Et, double* MM,
@@ -196,8 +200,34 @@ int  lcqp_hip_batch_resolve(lcqp_hip_batch_t* b, int mode, const double* rho0);
  * LCQP_INVALID_ARGUMENT: NULL handle, v or dg, or nrhs < 1.  LCQP_LCQPOBJECT_NOT_SETUP: no run / resolve on this object yet, or a load /
  * generate_synthetic / set_options since the last one.  LCQP_HIP_ERROR: a HIP call failed (no device). */
 int  lcqp_hip_batch_sensitivity(lcqp_hip_batch_t* b, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
-/* kernel time of the last lcqp_hip_batch_sensitivity launch of this object, ms (HIP events around k_sensitivity, the copies excluded) */
+/* kernel time of the last lcqp_hip_batch_sensitivity / _sensitivity_blocked / _jacobian call of this object, ms (HIP events around
+ * k_sensitivity or k_sensitivity_blk, the copies excluded; a Jacobian that went in chunks: the sum over its launches) */
 int  lcqp_hip_batch_sensitivity_timing(lcqp_hip_batch_t* b, float* kernel_ms);
+/* lcqp_hip_batch_sensitivity for many vectors (DESIGN.md section 3a'''): the same arguments, layouts, flags and return codes, checked in the
+ * same order before any device call.  The vectors of an instance go through k_sensitivity_blk in panels of 16 (LCQP_SENS_PANEL; the last
+ * panel padded with zero columns): the correction as block x panel products on the fp64 matrix cores, each 64 x 64 block of the factor
+ * read once per panel instead of once per vector.  The results equal lcqp_hip_batch_sensitivity's to rounding (the bound of DESIGN.md
+ * section 2), NOT to the bit: the sums are formed in another order.  Within this entry point a vector's result does not depend on the
+ * other vectors of the call or on its place among them, bit for bit.  side and info are those of lcqp_hip_batch_sensitivity.
+ * Padded sizes above 512 (nV > 512: np = 1024 / 2048 / 4096) have no room for a panel in LDS: there this entry point launches
+ * k_sensitivity and returns the bits of lcqp_hip_batch_sensitivity.  With one or a few vectors the vector kernel is the faster one (a
+ * panel is then mostly zero columns). */
+#define LCQP_SENS_PANEL 16
+int  lcqp_hip_batch_sensitivity_blocked(lcqp_hip_batch_t* b, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
+/* The full solution Jacobians of the instances [first, first + count): the blocked kernel on the unit vectors, which it generates on the
+ * device (nothing is uploaded).
+ *   Jg[i][k][j]  [count][nV][nV]   d x*_k / d g_j of instance first + i
+ *   Jb[i][k][r]  [count][nV][nd]   d x*_k / d (the bound row r of the dual layout sits on), zero outside W; may be NULL
+ *   side [count][nd], info [count]  as lcqp_hip_batch_sensitivity; may be NULL
+ * The staging on the device is bounded: the call loops over chunks of instances whose staging stays below
+ * LCQP_JACOBIAN_STAGING_BYTES (at least one instance per chunk), one launch and one download per chunk; the results do not depend on the
+ * chunking.  nV > 512: k_sensitivity on an uploaded identity, in chunks of unit vectors under the same cap; a sub-range then costs the
+ * launches of the whole batch (the vector kernel has no instance offset).
+ * LCQP_INVALID_ARGUMENT: NULL handle or Jg, first < 0, count < 1, first + count > B.  LCQP_LCQPOBJECT_NOT_SETUP as lcqp_hip_batch_sensitivity. */
+#define LCQP_JACOBIAN_STAGING_BYTES (1ull << 30)
+int  lcqp_hip_batch_jacobian(lcqp_hip_batch_t* b, int first, int count, double* Jg, double* Jb, int* side, int* info);
+/* another staging cap for this object's Jacobian calls (0: the default); for tests of the chunking and for small devices */
+int  lcqp_hip_batch_set_jacobian_staging(lcqp_hip_batch_t* b, size_t bytes);
 /* out[0] = full setups, out[1] = homotopy launches this object has issued (host counters) */
 int  lcqp_hip_batch_launch_counts(lcqp_hip_batch_t* b, int out[2]);
 /* Hint of a caller that keeps several batch objects in flight (BatchPipeline): the setup of this object will run beside the homotopy

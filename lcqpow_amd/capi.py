@@ -110,6 +110,11 @@ def lib():
         L.lcqp_hip_batch_sensitivity.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_batch_sensitivity_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.lcqp_hip_qp_sensitivity.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
+        L.lcqp_hip_batch_sensitivity_blocked.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
+        L.lcqp_hip_qp_sensitivity_blocked.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
+        L.lcqp_hip_batch_jacobian.argtypes = [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_int_p]
+        L.lcqp_hip_qp_jacobian.argtypes = [C.c_void_p, c_double_p, c_double_p, c_int_p, c_int_p]
+        L.lcqp_hip_batch_set_jacobian_staging.argtypes = [C.c_void_p, C.c_size_t]
         L.lcqp_hip_util_symv.argtypes = [C.c_int, C.c_int, C.c_double] + [c_double_p] * 4
         L.lcqp_hip_util_gemv.argtypes = [C.c_int, C.c_int, C.c_int] + [c_double_p] * 3
         L.lcqp_hip_util_gemv_t.argtypes = [C.c_int, C.c_int, C.c_int] + [c_double_p] * 3
@@ -224,6 +229,22 @@ def _sensitivity(call, v, B, nV, nd, check=None):
     return (dg[:, 0], db[:, 0], side, info) if single else (dg, db, side, info)
 
 
+SENS_PANEL = 16      # LCQP_SENS_PANEL: vectors per panel of the blocked sensitivity kernel
+
+
+def _jacobian(call, B, nV, nd, first, count, bounds, check=None):
+    """call(first, count, Jg, Jb, side, info) -> rc on the instances [first, first + count) of B (count None: to the end).  Returns
+    (Jg [count][nV][nV], Jb [count][nV][nd] or None, side [count][nd], info [count]); raises before any call on a range outside the batch."""
+    if count is None:
+        count = B - first
+    if not (isinstance(first, (int, np.integer)) and isinstance(count, (int, np.integer))) or first < 0 or count < 1 or first + count > B:
+        raise ValueError(f"jacobian: instances [{first}, {first} + {count}) are not inside the batch of {B}")
+    Jg = np.zeros((count, nV, nV)); Jb = np.zeros((count, nV, nd)) if bounds else None
+    side = np.zeros((count, nd), dtype=np.int32); info = np.zeros(count, dtype=np.int32)
+    (check or _check)(call(int(first), int(count), _p(Jg), _p(Jb), _ip(side), _ip(info)), "jacobian")
+    return Jg, Jb, side, info
+
+
 def split_bound_derivatives(db, side, nV, nC, nComp, sparse=False):
     """db and side of a sensitivity call (the reference's dual layout: box rows first, then A, L, R; sparse=True: the layout of
     SparseBatchLCQP.sensitivity, which has no box rows -- dlb and dub are then empty) as derivatives with respect to the
@@ -267,13 +288,20 @@ class SubsolverHIP:
         lib().lcqp_hip_qp_get_solution(self.h, _p(x), _p(y))
         return x, y
 
-    def sensitivity(self, v):
+    def sensitivity(self, v, blocked=False):
         """lcqp_hip_qp_sensitivity: derivatives of the solution of the QP last solved.  v: [nV] or [k][nV] upstream gradients dl/dx;
         returns (dg, db, side, info): dl/dg shaped like v, dl/d(bound) [nV + nC] or [k][nV + nC], side [nV + nC], info (int; 0 =
-        differentiable) -- see BatchLCQP.sensitivity."""
+        differentiable) -- see BatchLCQP.sensitivity.  blocked: lcqp_hip_qp_sensitivity_blocked."""
         v = _arr(v)
-        dg, db, side, info = _sensitivity(lambda *a: lib().lcqp_hip_qp_sensitivity(self.h, *a), v[None], 1, self.nV, self.nV + self.nC)
+        f = lib().lcqp_hip_qp_sensitivity_blocked if blocked else lib().lcqp_hip_qp_sensitivity
+        dg, db, side, info = _sensitivity(lambda *a: f(self.h, *a), v[None], 1, self.nV, self.nV + self.nC)
         return dg[0], db[0], side[0], int(info[0])
+
+    def jacobian(self, bounds=True):
+        """lcqp_hip_qp_jacobian: (Jg [nV][nV] = dx/dg, Jb [nV][nV + nC] = dx/d(bound) or None, side [nV + nC], info) of the QP last
+        solved -- see BatchLCQP.jacobian."""
+        Jg, Jb, side, info = _jacobian(lambda first, count, *a: lib().lcqp_hip_qp_jacobian(self.h, *a), 1, self.nV, self.nV + self.nC, 0, 1, bounds)
+        return Jg[0], (Jb[0] if bounds else None), side[0], int(info[0])
 
     def read_setup(self):
         """the constant matrices of the last fresh solve (test and diagnostic entry point; see BatchLCQP.read_setup)"""
@@ -524,6 +552,28 @@ class BatchLCQP(_Batch):
                  ("y0", y0, self.nd))
         a = [_sized(nm, _arr(v), count * sz) for nm, v, sz in sizes]
         return lib().lcqp_hip_batch_load(self.h, first, count, *[_p(v) for v in a])
+
+    def sensitivity(self, v, blocked=False):
+        """_Batch.sensitivity; blocked: lcqp_hip_batch_sensitivity_blocked, the kernel that takes the k vectors of an instance in panels
+        of SENS_PANEL on the matrix cores (DESIGN.md section 3a''') -- the same results to rounding (not to the bit), faster from about
+        a panel of vectors on; the default stays the vector kernel."""
+        name = "sensitivity_blocked" if blocked else "sensitivity"
+        return _sensitivity(lambda *a: self._sym(name)(self.h, *a), v, self.B, self.nV, self._ndual, check=self._check)
+
+    def jacobian(self, first=0, count=None, bounds=True, _staging_bytes=None):
+        """lcqp_hip_batch_jacobian: the full solution Jacobians of the instances [first, first + count) (count None: to the end) at the
+        x the last run / resolve returned (synchronous; DESIGN.md section 3a''').  Returns (Jg, Jb, side, info): Jg [count][nV][nV],
+        Jg[i][k][j] = dx_k/dg_j; Jb [count][nV][nd], Jb[i][k][r] = dx_k/d(the bound row r sits on) in the dual layout, zero outside the
+        working set (None with bounds=False); side [count][nd] and info [count] as sensitivity.  The unit vectors are generated on the
+        device, and the call goes in chunks of instances under a staging cap (_staging_bytes: another cap for this one call, for tests).
+        The call changes nothing on the device."""
+        if _staging_bytes is not None:
+            self._call("set_jacobian_staging", int(_staging_bytes))
+        try:
+            return _jacobian(lambda *a: self._sym("jacobian")(self.h, *a), self.B, self.nV, self.nd, first, count, bounds, check=self._check)
+        finally:
+            if _staging_bytes is not None:
+                self._call("set_jacobian_staging", 0)      # back to the default cap
 
     def generate_synthetic(self, first_instance=0, seed0=SEED0):
         _check(lib().lcqp_hip_batch_generate_synthetic(self.h, seed0, first_instance), "generate_synthetic")

@@ -64,9 +64,15 @@ class BatchLCQProblem {
     // Solution sensitivities (lcqp_hip_batch_sensitivity): for nrhs upstream gradients v = dl/dx per instance ([batch][nrhs][nV]) the
     // derivatives dg = dl/dg (same shape) and db = dl/d(bound), side, info ([batch][nrhs][nDuals], [batch][nDuals], [batch]; each may be 0)
     // of the solutions the last runSolver / resolve returned.  info[i] != 0: instance i is not differentiable by the criteria of the header.
-    ReturnValue getSensitivity(int nrhs, const double* v, double* dg, double* db = 0, int* side = 0, int* info = 0)
+    // blocked: lcqp_hip_batch_sensitivity_blocked (panels of 16 vectors on the matrix cores; equal to rounding, not to the bit)
+    ReturnValue getSensitivity(int nrhs, const double* v, double* dg, double* db = 0, int* side = 0, int* info = 0, bool blocked = false)
     {
-        return (ReturnValue)lcqp_hip_batch_sensitivity(h, nrhs, v, dg, db, side, info);
+        return (ReturnValue)(blocked ? lcqp_hip_batch_sensitivity_blocked(h, nrhs, v, dg, db, side, info) : lcqp_hip_batch_sensitivity(h, nrhs, v, dg, db, side, info));
+    }
+    // lcqp_hip_batch_jacobian: Jg [count][nV][nV], Jb [count][nV][nd] (or 0), side [count][nd], info [count] of the instances [first, first + count)
+    ReturnValue getJacobian(int first, int count, double* Jg, double* Jb = 0, int* side = 0, int* info = 0)
+    {
+        return (ReturnValue)lcqp_hip_batch_jacobian(h, first, count, Jg, Jb, side, info);
     }
     // full setups and homotopy launches this object has issued
     ReturnValue getLaunchCounts(int& setups, int& launches) const

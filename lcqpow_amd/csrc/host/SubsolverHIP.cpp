@@ -47,9 +47,14 @@ void SubsolverHIP::getSolution(double* x, double* y)
     if (qp) lcqp_hip_qp_get_solution(qp, x, y);
 }
 
-ReturnValue SubsolverHIP::getSensitivity(int nrhs, const double* v, double* dg, double* db, int* side, int* info)
+ReturnValue SubsolverHIP::getSensitivity(int nrhs, const double* v, double* dg, double* db, int* side, int* info, bool blocked)
 {
-    return (ReturnValue)lcqp_hip_qp_sensitivity(qp, nrhs, v, dg, db, side, info);
+    return (ReturnValue)(blocked ? lcqp_hip_qp_sensitivity_blocked(qp, nrhs, v, dg, db, side, info) : lcqp_hip_qp_sensitivity(qp, nrhs, v, dg, db, side, info));
+}
+
+ReturnValue SubsolverHIP::getJacobian(double* Jg, double* Jb, int* side, int* info)
+{
+    return (ReturnValue)lcqp_hip_qp_jacobian(qp, Jg, Jb, side, info);
 }
 
 }  // namespace LCQPow

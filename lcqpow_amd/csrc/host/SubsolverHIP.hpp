@@ -24,7 +24,9 @@ class SubsolverHIP : public SubsolverBase {
                       const double* const y0 = 0, const double* const lb = 0, const double* const ub = 0) override;
     void getSolution(double* x, double* y) override;
     // derivatives of the solution of the QP last solved (lcqp_hip_qp_sensitivity): v, dg [nrhs][nV]; db, side [.][nV + nC], info [1] may be 0
-    ReturnValue getSensitivity(int nrhs, const double* v, double* dg, double* db = 0, int* side = 0, int* info = 0);
+    ReturnValue getSensitivity(int nrhs, const double* v, double* dg, double* db = 0, int* side = 0, int* info = 0, bool blocked = false);
+    // lcqp_hip_qp_jacobian: Jg [nV][nV], Jb [nV][nV + nC] (or 0), side [nV + nC], info [1]
+    ReturnValue getJacobian(double* Jg, double* Jb = 0, int* side = 0, int* info = 0);
 
   private:
     void clear();

@@ -124,6 +124,8 @@ struct lcqp_hip_batch {
     ResolveState rs;
     std::vector<char> boxed;              // [B][n]
     SensBuffers sens;
+    SensBuffers sensBlk;                  // of k_sensitivity_blk (other leading dimensions, a varying number of instances)
+    size_t jacStaging = LCQP_JACOBIAN_STAGING_BYTES;      // device bytes a Jacobian call may stage per chunk of instances
     int nch;
     explicit lcqp_hip_batch(int dev) : db(), device(dev) {}
     ~lcqp_hip_batch() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
@@ -699,6 +701,108 @@ extern "C" int lcqp_hip_batch_sensitivity(lcqp_hip_batch_t* h, int nrhs, const d
     return batch_sensitivity(h, nrhs, v, dg, db, side, info);
 }); }
 
+// ---- blocked sensitivities and Jacobians (DESIGN.md section 3a'''): k_sensitivity_blk for np <= 512, k_sensitivity above ----
+// one launch on instances [first, first + count) with the buffers reserved for them; v == nullptr: unit vectors, nothing uploaded
+static int blocked_launch(lcqp_hip_batch* h, int first, int count, int nrhs, const double* v, double* dg, double* db, int* side, int* info, float* ms)
+{
+    DevBatch& d = h->db;
+    SensBuffers& sb = h->sensBlk;
+    // (ldv is the same for both kinds of call so that the rows reserved by one serve the other: a Jacobian's rows carry an unused v)
+    if (int rc = sb.reserve_rows(g_err, h->mem, h->stream, count, nrhs, d.n, d.np, (size_t)d.nd + 2 * (size_t)d.capS, d.nd)) return rc;
+    if (v) if (int rc = sb.upload(g_err, v)) return rc;
+    LaunchArgs a;
+    a.db = d; a.sensFirst = first; a.nrhs = nrhs; a.sensV = v ? sb.v : nullptr; a.sensDg = sb.dg; a.sensDb = sb.db; a.sensSide = sb.side; a.sensInfo = sb.info;
+    HIPCHK(g_err, hipEventRecord(sb.ev0, h->stream));
+    lcqp_dispatch(h->nch, ID_k_sensitivity_blk, count, h->stream, a);
+    HIPCHK(g_err, hipGetLastError());
+    HIPCHK(g_err, hipEventRecord(sb.ev1, h->stream));
+    if (int rc = sb.download(g_err, dg, db, side, info, d.n, d.nd)) return rc;
+    HIPCHK(g_err, hipEventElapsedTime(ms, sb.ev0, sb.ev1));
+    return 0;
+}
+
+static int batch_sensitivity_blocked(lcqp_hip_batch* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
+{
+    if (h->nch > 4) return batch_sensitivity(h, nrhs, v, dg, db, side, info);      // a panel of np >= 1024 does not fit LDS: the vector kernel and its bits
+    HIPCHK(g_err, hipSetDevice(h->device));
+    float ms = 0.f;
+    if (int rc = blocked_launch(h, 0, h->db.B, nrhs, v, dg, db, side, info, &ms)) return rc;
+    h->sens.lastMs = ms;
+    return 0;
+}
+
+// Jg [count][n][n], Jb [count][n][nd] (or NULL), side [count][nd], info [count] of the instances [first, first + count)
+static int batch_jacobian(lcqp_hip_batch* h, int first, int count, double* Jg, double* Jb, int* side, int* info)
+{
+    DevBatch& d = h->db;
+    HIPCHK(g_err, hipSetDevice(h->device));
+    const size_t n = d.n, nd = d.nd;
+    float total = 0.f;
+    if (h->nch <= 4) {
+        // chunks of instances whose staging (n rows of v, dg and db each) stays below the cap; one launch and one download per chunk
+        const size_t perInst = sizeof(double) * n * (n + (size_t)d.np + nd + 2 * (size_t)d.capS);
+        size_t chunk = h->jacStaging / perInst;
+        if (chunk < 1) chunk = 1;
+        if (chunk > (size_t)d.B) chunk = d.B;
+        for (size_t c0 = 0; c0 < (size_t)count; c0 += chunk) {
+            const size_t cb = std::min(chunk, (size_t)count - c0);
+            float ms = 0.f;
+            if (int rc = blocked_launch(h, first + (int)c0, (int)cb, d.n, nullptr, Jg + c0 * n * n, Jb ? Jb + c0 * n * nd : nullptr,
+                                        side ? side + c0 * nd : nullptr, info ? info + c0 : nullptr, &ms)) return rc;
+            total += ms;
+        }
+        h->sens.lastMs = total;
+        return 0;
+    }
+    // np >= 1024: k_sensitivity on the whole batch with an uploaded identity, in chunks of unit vectors under the same cap.  The vector kernel
+    // has no instance offset: a sub-range costs the launches of the full batch of B (these sizes are the single-large-problem ones, B small).
+    const size_t B = d.B, perVec = sizeof(double) * B * (n + (size_t)d.np + nd + (size_t)d.capS);
+    size_t m = h->jacStaging / perVec;
+    if (m < 1) m = 1;
+    if (m > n) m = n;
+    std::vector<double> vh(B * m * n), dgh(B * m * n), dbh(Jb ? B * m * nd : 0);
+    std::vector<int> sideh(B * nd), infoh(B);
+    for (size_t k0 = 0; k0 < n; k0 += m) {
+        const size_t mk = std::min(m, n - k0);
+        std::fill(vh.begin(), vh.end(), 0.0);
+        for (size_t b = 0; b < B; b++) for (size_t j = 0; j < mk; j++) vh[(b * mk + j) * n + k0 + j] = 1.0;
+        if (int rc = batch_sensitivity(h, (int)mk, vh.data(), dgh.data(), Jb ? dbh.data() : nullptr, sideh.data(), infoh.data())) return rc;
+        float ms = 0.f;
+        HIPCHK(g_err, hipEventElapsedTime(&ms, h->sens.ev0, h->sens.ev1));
+        total += ms;
+        for (size_t i = 0; i < (size_t)count; i++) {
+            const size_t b = first + i;
+            memcpy(Jg + (i * n + k0) * n, dgh.data() + b * mk * n, sizeof(double) * mk * n);
+            if (Jb) memcpy(Jb + (i * n + k0) * nd, dbh.data() + b * mk * nd, sizeof(double) * mk * nd);
+        }
+    }
+    if (side) memcpy(side, sideh.data() + (size_t)first * nd, sizeof(int) * count * nd);
+    if (info) memcpy(info, infoh.data() + first, sizeof(int) * count);
+    h->sens.lastMs = total;
+    return 0;
+}
+
+extern "C" int lcqp_hip_batch_sensitivity_blocked(lcqp_hip_batch_t* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
+{ return guarded(g_err, [&] {
+    if (!h || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return batch_sensitivity_blocked(h, nrhs, v, dg, db, side, info);
+}); }
+
+extern "C" int lcqp_hip_batch_jacobian(lcqp_hip_batch_t* h, int first, int count, double* Jg, double* Jb, int* side, int* info)
+{ return guarded(g_err, [&] {
+    if (!h || !Jg || first < 0 || count < 1 || first > h->db.B - count) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return batch_jacobian(h, first, count, Jg, Jb, side, info);
+}); }
+
+extern "C" int lcqp_hip_batch_set_jacobian_staging(lcqp_hip_batch_t* h, size_t bytes)
+{ return guarded(g_err, [&] {
+    if (!h) return LCQP_INVALID_ARGUMENT;
+    h->jacStaging = bytes ? bytes : (size_t)LCQP_JACOBIAN_STAGING_BYTES;
+    return 0;
+}); }
+
 extern "C" int lcqp_hip_batch_sensitivity_timing(lcqp_hip_batch_t* h, float* kernel_ms)
 {
     return guarded(g_err, [&] { return sensitivity_timing(g_err, h, kernel_ms); });
@@ -887,6 +991,21 @@ extern "C" int lcqp_hip_qp_sensitivity(lcqp_hip_qp_t* q, int nrhs, const double*
     if (!q || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
     if (!q->hb || !q->solved) return LCQP_LCQPOBJECT_NOT_SETUP;
     return batch_sensitivity(q->hb, nrhs, v, dg, db, side, info);
+}); }
+
+// the blocked twins on the batch of one (lcqp_hip_batch_sensitivity_blocked, lcqp_hip_batch_jacobian)
+extern "C" int lcqp_hip_qp_sensitivity_blocked(lcqp_hip_qp_t* q, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
+{ return guarded(g_err, [&] {
+    if (!q || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
+    if (!q->hb || !q->solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return batch_sensitivity_blocked(q->hb, nrhs, v, dg, db, side, info);
+}); }
+
+extern "C" int lcqp_hip_qp_jacobian(lcqp_hip_qp_t* q, double* Jg, double* Jb, int* side, int* info)
+{ return guarded(g_err, [&] {
+    if (!q || !Jg) return LCQP_INVALID_ARGUMENT;
+    if (!q->hb || !q->solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return batch_jacobian(q->hb, 0, 1, Jg, Jb, side, info);
 }); }
 
 // =================================================================================================

@@ -230,6 +230,8 @@ struct SensBuffers {
     double *v = nullptr, *dg = nullptr, *db = nullptr;
     int *side = nullptr, *info = nullptr;
     int rhs = 0;
+    size_t capB = 0, capRows = 0;         // reserve_rows: instances and rows the buffers have room for
+    float lastMs = -1.f;                  // >= 0: the kernel time *_sensitivity_timing reports in place of ev0 -> ev1 (a launch on other buffers)
     Event ev0, ev1;
     hipStream_t stream = nullptr;         // of the call in progress, with its sizes: rows = B * nrhs; leading dimensions in elements
     size_t B = 0, rows = 0, ldV = 0, ldDg = 0, ldDb = 0, nSide = 0;
@@ -238,6 +240,7 @@ struct SensBuffers {
     {
         for (hipError_t e : {ev0.status, ev1.status}) if (e != hipSuccess) return hip_fail(err, "hipEventCreate", e);
         stream = s; B = nB; rows = nB * nrhs; ldV = ldv; ldDg = lddg; ldDb = lddb; nSide = nside;
+        lastMs = -1.f;
         if (nrhs <= rhs) return 0;
         HIPCHK(err, hipStreamSynchronize(s));
         for (const void* p : {(const void*)v, (const void*)dg, (const void*)db, (const void*)side, (const void*)info}) mem.release(p);
@@ -245,6 +248,23 @@ struct SensBuffers {
         if (!mem.alloc(err, v, rows * ldV) || !mem.alloc(err, dg, rows * ldDg) || !mem.alloc(err, db, rows * ldDb) ||
             !mem.alloc(err, side, B * nSide) || !mem.alloc(err, info, B)) return LCQP_HIP_ERROR;
         rhs = nrhs;
+        return 0;
+    }
+    // the same for calls whose number of instances varies (the blocked kernel's buffers: a Jacobian works on a chunk of the batch, with one
+    // right-hand side per variable): room for nB instances and nB * nrhs rows, grown when either is exceeded
+    int reserve_rows(std::string& err, DevMem& mem, hipStream_t s, size_t nB, size_t nrhs, size_t ldv, size_t lddg, size_t lddb, size_t nside)
+    {
+        for (hipError_t e : {ev0.status, ev1.status}) if (e != hipSuccess) return hip_fail(err, "hipEventCreate", e);
+        stream = s; B = nB; rows = nB * nrhs; ldV = ldv; ldDg = lddg; ldDb = lddb; nSide = nside;
+        if (nB <= capB && rows <= capRows) return 0;
+        HIPCHK(err, hipStreamSynchronize(s));
+        for (const void* p : {(const void*)v, (const void*)dg, (const void*)db, (const void*)side, (const void*)info}) mem.release(p);
+        v = dg = db = nullptr; side = info = nullptr;
+        const size_t nb = nB > capB ? nB : capB, nr = rows > capRows ? rows : capRows;
+        capB = capRows = 0;
+        if (!mem.alloc(err, v, nr * ldV) || !mem.alloc(err, dg, nr * ldDg) || !mem.alloc(err, db, nr * ldDb) ||
+            !mem.alloc(err, side, nb * nSide) || !mem.alloc(err, info, nb)) return LCQP_HIP_ERROR;
+        capB = nb; capRows = nr;
         return 0;
     }
     int upload(std::string& err, const double* hv)
@@ -275,7 +295,8 @@ struct SensBuffers {
 template <class H>
 int sensitivity_timing(std::string& err, H* h, float* kernel_ms)
 {
-    if (!h || !kernel_ms || !h->sens.rhs) return LCQP_INVALID_ARGUMENT;
+    if (!h || !kernel_ms || (!h->sens.rhs && h->sens.lastMs < 0.f)) return LCQP_INVALID_ARGUMENT;
+    if (h->sens.lastMs >= 0.f) { *kernel_ms = h->sens.lastMs; return 0; }      // the last launch was a blocked one, on buffers of its own
     HIPCHK(err, hipSetDevice(h->device));
     HIPCHK(err, hipEventSynchronize(h->sens.ev1));
     HIPCHK(err, hipEventElapsedTime(kernel_ms, h->sens.ev0, h->sens.ev1));

@@ -166,38 +166,15 @@ __global__ __launch_bounds__(WG) void k_refresh(DevBatch db, int mode, const dou
     }
 }
 
-// ---- k_sensitivity: adjoint derivatives of the returned x in g and in the bounds of the working set (DESIGN.md section 3a') -------------
-// At the point the last run (or QP solve) returned, x is the minimiser of 1/2 x'Hx + g'x on E_W x = b_W, H = Q + sigma_p I = L1 L1', W the
-// rows in the inverse factor.  For an upstream gradient v:  c = L1^-1 v;  lambda = Ti'Ti (Et_W c);  d = L1^-T (c - Et_W' lambda);
-// dl/dg = -d, dl/db_W = lambda: one full correction of qp_polish with r1 = v, r2 = 0, from the same routines with the same load policy
-// (plain first pass over Et_W, streamed second pass, the triangle of Ti).  The kernel READS the state of the instance and writes only its
-// outputs -- no vector pool, InstInfo, status or factor changes, so that a warm re-solve after it returns what it returns without it.
-//   v [B][nrhs][n];  dg [B][nrhs][np] (the work vector of the solves; -d on return, zero on the padding);
-//   dbo [B][nrhs][nd + capS]: nd derivatives in the reference's dual layout (box first), then capS slot-space scratch (lambda);
-//   side [B][nd]: 0 outside W, -1 at lower, +1 at upper, 2 equality;  sinfo [B]: flag bits (include/lcqp_hip.h), 0 = differentiable.
+// ---- the marks of a sensitivity call: `side` of every row in the working set and the flag bits of the instance (include/lcqp_hip.h) -----
+// One function for k_sensitivity and k_sensitivity_blk, so that the two kernels cannot disagree about a flag.  sd [nd]: zero on entry (every
+// thread's fill may still be in flight: the barrier inside block_max orders it before the marks); sflag: the instance's entry of `info`.
 template <int NCH>
-__global__ __launch_bounds__(WG) void k_sensitivity(DevBatch db, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo)
+__device__ __forceinline__ void sens_marks(const DevBatch& db, Ctx<NCH>& c, Lds lds, int* sd, int* sflag)
 {
-    LCQP_LDS_N(NCH)
-    constexpr int np = 128 * NCH;
-    const int b = blockIdx.x, t = threadIdx.x;
-    Ctx<NCH> c = make_ctx<NCH>(db, b, lds);
-    const int n = db.n, nC = db.nC, nComp = db.nComp, mA = db.mA, nd = db.nd, mE = c.mE;
-    const int ldb = nd + db.capS;
-    const int solved = c.info->haveSolution != 0 && c.info->setupFail == 0 && db.stats[b].returnValue == 0;
-    int* sd = side + (size_t)b * nd;
-    for (int i = t; i < nd; i += WG) sd[i] = 0;
-    if (!solved) {      // (uniform) nothing to differentiate: zero outputs
-        for (int k = 0; k < nrhs; k++) {
-            wg_fill(dg + ((size_t)b * nrhs + k) * np, 0.0, np);
-            wg_fill(dbo + ((size_t)b * nrhs + k) * ldb, 0.0, ldb);
-        }
-        if (t == 0) sinfo[b] = 1;
-        return;
-    }
-    const int nT = uniform_i(c.info->nT), ns = uniform_i(c.info->ns);
-    const int nsp = 64 * ((ns + 63) >> 6);
-    const int *st = c.I(I_ST), *rslot = c.I(I_SLOT), *idx = c.idx, *boxidx = c.boxidx;
+    const int t = threadIdx.x;
+    const int n = db.n, nC = db.nC, nComp = db.nComp, mA = db.mA, mE = c.mE;
+    const int *st = c.I(I_ST), *rslot = c.I(I_SLOT), *boxidx = c.boxidx;
     const double* yq = c.M(M_YQ);
     auto pos = [&](int r) { return r < mA ? n + r : boxidx[r - mA]; };      // row of E -> entry of the reference's dual vector
     double ym = 0.0;
@@ -217,7 +194,43 @@ __global__ __launch_bounds__(WG) void k_sensitivity(DevBatch db, int nrhs, const
     for (int i = t; i < nComp; i += WG) if (!sideIn(nC + i) && !sideIn(nC + nComp + i)) open = 1;
     weak = block_or(weak, lds);
     open = block_or(open, lds);
-    if (t == 0) sinfo[b] = (uniform_i(c.info->ndep) > 0 ? 2 : 0) | (weak ? 4 : 0) | (open ? 8 : 0);
+    if (t == 0) *sflag = (uniform_i(c.info->ndep) > 0 ? 2 : 0) | (weak ? 4 : 0) | (open ? 8 : 0);
+}
+
+// ---- k_sensitivity: adjoint derivatives of the returned x in g and in the bounds of the working set (DESIGN.md section 3a') -------------
+// At the point the last run (or QP solve) returned, x is the minimiser of 1/2 x'Hx + g'x on E_W x = b_W, H = Q + sigma_p I = L1 L1', W the
+// rows in the inverse factor.  For an upstream gradient v:  c = L1^-1 v;  lambda = Ti'Ti (Et_W c);  d = L1^-T (c - Et_W' lambda);
+// dl/dg = -d, dl/db_W = lambda: one full correction of qp_polish with r1 = v, r2 = 0, from the same routines with the same load policy
+// (plain first pass over Et_W, streamed second pass, the triangle of Ti).  The kernel READS the state of the instance and writes only its
+// outputs -- no vector pool, InstInfo, status or factor changes, so that a warm re-solve after it returns what it returns without it.
+//   v [B][nrhs][n];  dg [B][nrhs][np] (the work vector of the solves; -d on return, zero on the padding);
+//   dbo [B][nrhs][nd + capS]: nd derivatives in the reference's dual layout (box first), then capS slot-space scratch (lambda);
+//   side [B][nd]: 0 outside W, -1 at lower, +1 at upper, 2 equality;  sinfo [B]: flag bits (include/lcqp_hip.h), 0 = differentiable.
+template <int NCH>
+__global__ __launch_bounds__(WG) void k_sensitivity(DevBatch db, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo)
+{
+    LCQP_LDS_N(NCH)
+    constexpr int np = 128 * NCH;
+    const int b = blockIdx.x, t = threadIdx.x;
+    Ctx<NCH> c = make_ctx<NCH>(db, b, lds);
+    const int n = db.n, mA = db.mA, nd = db.nd;
+    const int ldb = nd + db.capS;
+    const int solved = c.info->haveSolution != 0 && c.info->setupFail == 0 && db.stats[b].returnValue == 0;
+    int* sd = side + (size_t)b * nd;
+    for (int i = t; i < nd; i += WG) sd[i] = 0;
+    if (!solved) {      // (uniform) nothing to differentiate: zero outputs
+        for (int k = 0; k < nrhs; k++) {
+            wg_fill(dg + ((size_t)b * nrhs + k) * np, 0.0, np);
+            wg_fill(dbo + ((size_t)b * nrhs + k) * ldb, 0.0, ldb);
+        }
+        if (t == 0) sinfo[b] = 1;
+        return;
+    }
+    const int nT = uniform_i(c.info->nT), ns = uniform_i(c.info->ns);
+    const int nsp = 64 * ((ns + 63) >> 6);
+    const int *idx = c.idx, *boxidx = c.boxidx;
+    auto pos = [&](int r) { return r < mA ? n + r : boxidx[r - mA]; };      // row of E -> entry of the reference's dual vector
+    sens_marks<NCH>(db, c, lds, sd, sinfo + b);
     for (int k = 0; k < nrhs; k++) {
         const double* vk = v + ((size_t)b * nrhs + k) * n;
         double* w = dg + ((size_t)b * nrhs + k) * np;
@@ -237,6 +250,267 @@ __global__ __launch_bounds__(WG) void k_sensitivity(DevBatch db, int nrhs, const
         wg_trsv<wg_ncopy(NCH) == 2>(c.F1, np, c.nblk, w, false, lds);
         for (int i = t; i < np; i += WG) w[i] = (i < n) ? -w[i] : 0.0;
         for (int a = t; a < ns; a += WG) { const int r = idx[a]; if (r >= 0) out[pos(r)] = lam[a]; }
+        __syncthreads();
+    }
+}
+
+// ---- k_sensitivity_blk: the correction of k_sensitivity for SENS_PANEL upstream gradients at once (DESIGN.md section 3a''') ------------
+// The vectors of an instance are taken in panels of SENS_PANEL columns (the last one padded with zero columns); the panel X (np x SENS_PANEL)
+// lives in LDS from its load to its store, and every product is a chain of v_mfma_f64_16x16x4_f64 on a 64 x 64 block of the matrix, staged in
+// LDS, times 64 rows of a panel:
+//   C = L1^-1 X        left-looking block forward substitution  C_I = D_II (X_I - sum_{J<I} L_IJ C_J): the blocks below the diagonal of F1, and
+//                      the lower triangle of the symmetric-filled inverted diagonal block;
+//   S = Et_W C         rows of Et gathered through idx (a free slot or a slot beyond ns is a zero row);
+//   U = Ti S, Lambda = Ti' U     the entries (j, s) of Ti with j < nT, s < ns, idx[s] >= 0 and j >= crow[s] -- exactly what ti_apply_fast reads,
+//                      one layout whatever ns is (ti_apply's two passes for ns > 256 read the same matrix);
+//   C <- C - Et_W' Lambda;   D = L1^-T C   block backward substitution with the blocks above the diagonal (L_JI' as stored) and the upper triangle
+//                      of the diagonal block;   dg = -D, db_W = Lambda scattered as k_sensitivity scatters them.
+// A column of the result depends on its own column of X only, through the same instructions wherever it stands in a panel: permuting the
+// vectors of a call permutes its outputs bit for bit, and a zero column returns zeros.
+// Per panel each block of F1 is read once (forward: below the diagonal, backward: above it -- the symmetric fill holds both), each entry of Ti
+// and each active row of Et twice (S and U have to be complete before Lambda and the correction can start; the second read follows the first
+// within microseconds and is expected to be served by L2 -- that has not been measured).  The slot-space panels S / Lambda and U (at most capS x SENS_PANEL each) stay out of LDS: they live in the slot-space
+// scratch behind each vector's row of dbo -- 8 KB per staged block against the 32 KB block of the matrix it multiplies.
+// SENS_PANEL = 16, the N of the fp64 MFMA: one accumulator per wave and 64-row block.  LDS: the panel 16 np doubles (64 KB at np = 512), a
+// 64 x 66 block of the matrix (33 KB; pitch 66: the plain A-operand reads of a half-wave fall into 64 distinct banks; the transposed reads of
+// Lambda = Ti' U and of the correction are 2-way conflicted at this pitch, and the panel load writes X at a stride of 16 doubles once per
+// panel -- neither has been measured) and 64 rows of a slot-space panel (8 KB): 57 / 73 / 89 / 105 KB for NCH = 1 .. 4.  174 - 184 VGPRs and 8
+// AGPRs (at most 192 unified registers: two waves per SIMD): two workgroups per CU up to np = 256, one above, where LDS is the bound.  The
+// product loop is unrolled by four, not fully: sixteen operand pairs in flight cost 278 registers and the second workgroup.  32 columns would
+// double the panel and leave np = 512 without room for the matrix block.  (The kernel never runs beside k_lcqp_run.)
+//   v [count][nrhs][n], or null: vector k of every instance is the unit vector e_k (the rows of the Jacobian; the block rows of the forward
+//   substitution above the panel's first unit entry are zero and are skipped);  dg [count][nrhs][np];  dbo [count][nrhs][nd + 2 capS]: nd
+//   derivatives, then S / Lambda and U;  side [count][nd];  sinfo [count].  Workgroup o works on instance first + o and writes row o of the outputs.
+constexpr int SENS_PANEL = 16;
+constexpr int SENS_PA = 66;
+
+template <int NCH>
+__global__ __launch_bounds__(WG) void k_sensitivity_blk(DevBatch db, int first, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo)
+{
+    constexpr int np = 128 * NCH, P = SENS_PANEL, PA = SENS_PA;
+    static_assert(P == 16, "one 16-column MFMA block per wave and row block");
+    __shared__ double Xs[np * P];
+    __shared__ double As[64 * PA];
+    __shared__ double Bs[64 * P];
+    __shared__ double sh_red[16];
+    __shared__ int sh_ired[16];
+    Lds lds{As, sh_red, sh_ired};
+    const int o = blockIdx.x, b = first + o, t = tid_here(), lane = t & 63, w = t >> 6, il = lane & 15, kl = lane >> 4;
+    Ctx<NCH> c = make_ctx<NCH>(db, b, lds);
+    const int n = db.n, mA = db.mA, nd = db.nd, capS = db.capS, nblk = c.nblk;
+    const int ldb = nd + 2 * capS;
+    const int solved = c.info->haveSolution != 0 && c.info->setupFail == 0 && db.stats[b].returnValue == 0;
+    int* sd = side + (size_t)o * nd;
+    for (int i = t; i < nd; i += WG) sd[i] = 0;
+    if (!solved) {      // (uniform) nothing to differentiate: zero outputs
+        for (int k = 0; k < nrhs; k++) {
+            wg_fill(dg + ((size_t)o * nrhs + k) * np, 0.0, np);
+            wg_fill(dbo + ((size_t)o * nrhs + k) * ldb, 0.0, ldb);
+        }
+        if (t == 0) sinfo[o] = 1;
+        return;
+    }
+    const int nT = uniform_i(c.info->nT), ns = uniform_i(c.info->ns);
+    const int nsb = (ns + 63) >> 6, njb = (nT + 63) >> 6;      // 64 nsb, 64 njb <= capS: ns, nT <= capS, a multiple of 64
+    const int *idx = c.idx, *boxidx = c.boxidx, *crow = c.crow;
+    const double *F1 = c.F1, *Et = c.Et, *Ti = c.S;
+    auto pos = [&](int r) { return r < mA ? n + r : boxidx[r - mA]; };
+    sens_marks<NCH>(db, c, lds, sd, sinfo + o);
+
+    // a 64 x 64 block of a matrix on its way into As: thread t carries the column pair 2 (t & 31) of the rows (t >> 5) + 8 i
+    const int ar = t >> 5, ac = (t & 31) * 2;
+    double2 ra[8];
+    double rb[4];
+    // rowp(r): where row r of the block starts (its 64 columns), or null for a zero row; keep(r, col): whether an entry takes part
+    auto loadA = [&](auto rowp, auto keep) {
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            const int r = ar + 8 * i;
+            const double* p = rowp(r);
+            double2 x{0.0, 0.0};
+            if (p) x = *reinterpret_cast<const double2*>(p + ac);
+            if (!keep(r, ac)) x.x = 0.0;
+            if (!keep(r, ac + 1)) x.y = 0.0;
+            ra[i] = x;
+        }
+    };
+    auto storeA = [&]() {
+#pragma unroll
+        for (int i = 0; i < 8; i++) *reinterpret_cast<double2*>(As + (ar + 8 * i) * PA + ac) = ra[i];
+    };
+    auto all = [](int, int) { return true; };
+    // acc += (As or its transpose)[rows 16 w .. 16 w + 15] * Bp (64 x P, pitch P)
+    auto mm = [&](d4_t& acc, const double* Bp, bool tr) {
+#pragma unroll 4
+        for (int k4 = 0; k4 < 16; k4++) {
+            const int k = 4 * k4 + kl;
+            const double av = tr ? As[k * PA + 16 * w + il] : As[(16 * w + il) * PA + k];
+            acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, Bp[k * P + il], acc, 0, 0, 0);
+        }
+    };
+
+    #pragma nounroll
+    for (int k0 = 0; k0 < nrhs; k0 += P) {
+        const int pv = min(P, nrhs - k0);      // columns of this panel that are vectors of the call
+        const size_t row0 = (size_t)o * nrhs + k0;
+        // entry (a, j) of the slot-space panels: S, then Lambda, at offset nd of vector j's row of dbo; U at nd + capS
+        auto slotp = [&](int which, int a, int j) -> double* { return dbo + (row0 + j) * ldb + nd + which * capS + a; };
+        // 64 rows of a slot-space panel on their way into Bs: rb[m] is entry (a0 + (e & 63), e >> 6) for e = t + 256 m; padded columns are zero
+        auto loadB = [&](int which, int a0) {
+#pragma unroll
+            for (int m = 0; m < 4; m++) { const int e = t + WG * m, j = e >> 6; rb[m] = (j < pv) ? *slotp(which, a0 + (e & 63), j) : 0.0; }
+        };
+        auto storeB = [&]() {
+#pragma unroll
+            for (int m = 0; m < 4; m++) { const int e = t + WG * m; Bs[(e & 63) * P + (e >> 6)] = rb[m]; }
+        };
+        // accumulator register q of a wave is row 16 w + kl + 4 q of the block, column il
+        auto storeSlot = [&](int which, int a0, const d4_t& acc) {
+            if (il < pv) {
+#pragma unroll
+                for (int q = 0; q < 4; q++) *slotp(which, a0 + 16 * w + kl + 4 * q, il) = acc[q];
+            }
+        };
+        const int skip = v ? 0 : (k0 >> 6);      // unit vectors: the block rows above the first unit entry stay zero in the forward substitution
+        for (int e = t; e < np * P; e += WG) {
+            const int j = e / np, i = e - j * np;
+            double x = 0.0;
+            if (i < n && j < pv) x = v ? v[(row0 + j) * n + i] : (i == k0 + j ? 1.0 : 0.0);
+            Xs[i * P + j] = x;
+        }
+        for (int j = 0; j < pv; j++) wg_fill(dbo + (row0 + j) * ldb, 0.0, nd);
+        __syncthreads();
+
+        // X <- L1^-1 X (forward) or L1^-T X (backward): block (I, J) of the symmetric-filled F1 is L_IJ below the diagonal and L_JI' above it
+        auto trisolve = [&](bool fwd) {
+            #pragma nounroll
+            for (int s = (fwd ? skip : 0); s < nblk; s++) {
+                const int I = fwd ? s : nblk - 1 - s;
+                const int J0 = fwd ? skip : I + 1, J1 = fwd ? I : nblk;
+                auto blk = [&](int J) { return [=](int r) { return F1 + (size_t)(64 * I + r) * np + 64 * J; }; };
+                d4_t acc{0.0, 0.0, 0.0, 0.0};
+                if (J1 > J0) loadA(blk(J0), all);
+                #pragma nounroll
+                for (int J = J0; J < J1; J++) {
+                    storeA();
+                    __syncthreads();
+                    if (J + 1 < J1) loadA(blk(J + 1), all);
+                    mm(acc, Xs + 64 * J * P, false);
+                    __syncthreads();
+                }
+                // the diagonal block holds D = inv(L_II) below and D' above: forward applies D (entries c <= r), backward D' (c >= r)
+                if (fwd) loadA(blk(I), [](int r, int cc) { return cc <= r; });
+                else loadA(blk(I), [](int r, int cc) { return cc >= r; });
+#pragma unroll
+                for (int q = 0; q < 4; q++) Xs[(64 * I + 16 * w + kl + 4 * q) * P + il] -= acc[q];
+                storeA();
+                __syncthreads();
+                d4_t y{0.0, 0.0, 0.0, 0.0};
+                mm(y, Xs + 64 * I * P, false);
+                __syncthreads();      // every wave has read X_I
+#pragma unroll
+                for (int q = 0; q < 4; q++) Xs[(64 * I + 16 * w + kl + 4 * q) * P + il] = y[q];
+                __syncthreads();
+            }
+        };
+        trisolve(true);
+        if (nT > 0) {
+            // rows of Et held by the slots 64 sb .. 64 sb + 63, columns 64 J .. 64 J + 63
+            auto etBlk = [&](int sb, int J) {
+                return [=](int r) -> const double* {
+                    const int a = 64 * sb + r;
+                    const int row = (a < ns) ? idx[a] : -1;
+                    return row >= 0 ? Et + (size_t)row * np + 64 * J : nullptr;
+                };
+            };
+            // rows 64 jb .. of Ti, slots 64 sb ..: column s is zero above crow[s], and everywhere on a free slot
+            auto tiBlk = [&](int jb, int sb) { return [=](int r) -> const double* { return (64 * jb + r < nT) ? Ti + (size_t)(64 * jb + r) * capS + 64 * sb : nullptr; }; };
+            auto tiKeep = [&](int jb, int sb) {
+                return [=](int r, int cc) { const int s = 64 * sb + cc; return s < ns && idx[s] >= 0 && 64 * jb + r >= crow[s]; };
+            };
+            // S = Et_W C
+            #pragma nounroll
+            for (int sb = 0; sb < nsb; sb++) {
+                d4_t acc{0.0, 0.0, 0.0, 0.0};
+                loadA(etBlk(sb, 0), all);
+                #pragma nounroll
+                for (int J = 0; J < nblk; J++) {
+                    storeA();
+                    __syncthreads();
+                    if (J + 1 < nblk) loadA(etBlk(sb, J + 1), all);
+                    mm(acc, Xs + 64 * J * P, false);
+                    __syncthreads();
+                }
+                storeSlot(0, 64 * sb, acc);
+            }
+            __syncthreads();
+            // U = Ti S
+            #pragma nounroll
+            for (int jb = 0; jb < njb; jb++) {
+                d4_t acc{0.0, 0.0, 0.0, 0.0};
+                loadA(tiBlk(jb, 0), tiKeep(jb, 0));
+                loadB(0, 0);
+                #pragma nounroll
+                for (int sb = 0; sb < nsb; sb++) {
+                    storeA();
+                    storeB();
+                    __syncthreads();
+                    if (sb + 1 < nsb) { loadA(tiBlk(jb, sb + 1), tiKeep(jb, sb + 1)); loadB(0, 64 * (sb + 1)); }
+                    mm(acc, Bs, false);
+                    __syncthreads();
+                }
+                storeSlot(1, 64 * jb, acc);
+            }
+            __syncthreads();
+            // Lambda = Ti' U, in the place of S
+            #pragma nounroll
+            for (int sb = 0; sb < nsb; sb++) {
+                d4_t acc{0.0, 0.0, 0.0, 0.0};
+                loadA(tiBlk(0, sb), tiKeep(0, sb));
+                loadB(1, 0);
+                #pragma nounroll
+                for (int jb = 0; jb < njb; jb++) {
+                    storeA();
+                    storeB();
+                    __syncthreads();
+                    if (jb + 1 < njb) { loadA(tiBlk(jb + 1, sb), tiKeep(jb + 1, sb)); loadB(1, 64 * (jb + 1)); }
+                    mm(acc, Bs, true);
+                    __syncthreads();
+                }
+                storeSlot(0, 64 * sb, acc);
+            }
+            __syncthreads();
+            // C <- C - Et_W' Lambda
+            #pragma nounroll
+            for (int J = 0; J < nblk; J++) {
+                d4_t acc{0.0, 0.0, 0.0, 0.0};
+                loadA(etBlk(0, J), all);
+                loadB(0, 0);
+                #pragma nounroll
+                for (int sb = 0; sb < nsb; sb++) {
+                    storeA();
+                    storeB();
+                    __syncthreads();
+                    if (sb + 1 < nsb) { loadA(etBlk(sb + 1, J), all); loadB(0, 64 * (sb + 1)); }
+                    mm(acc, Bs, true);
+                    __syncthreads();
+                }
+#pragma unroll
+                for (int q = 0; q < 4; q++) Xs[(64 * J + 16 * w + kl + 4 * q) * P + il] -= acc[q];
+            }
+            __syncthreads();
+        }
+        trisolve(false);
+        for (int e = t; e < np * pv; e += WG) {
+            const int j = e / np, i = e - j * np;
+            dg[(row0 + j) * np + i] = (i < n) ? -Xs[i * P + j] : 0.0;
+        }
+        if (nT > 0)
+            for (int e = t; e < ns * pv; e += WG) {
+                const int j = e / ns, a = e - j * ns;
+                const int r = idx[a];
+                if (r >= 0) dbo[(row0 + j) * ldb + pos(r)] = *slotp(0, a, j);
+            }
         __syncthreads();
     }
 }
@@ -914,6 +1188,9 @@ static void launch_impl(int kid, int grid, hipStream_t s, const LaunchArgs& a)
     switch (kid) {
         case ID_k_prepare:    hipLaunchKernelGGL((k_prepare<NCH>), dim3(grid), dim3(WG), 0, s, a.db); break;
         case ID_k_refresh:    hipLaunchKernelGGL((k_refresh<NCH>), dim3(grid), dim3(WG), 0, s, a.db, a.mode, a.rho0); break;
+        case ID_k_sensitivity_blk:      // np <= 512 only: the callers send the larger sizes to k_sensitivity
+            if constexpr (NCH <= 4) hipLaunchKernelGGL((k_sensitivity_blk<NCH>), dim3(grid), dim3(WG), 0, s, a.db, a.sensFirst, a.nrhs, a.sensV, a.sensDg, a.sensDb, a.sensSide, a.sensInfo);
+            break;
         case ID_k_sensitivity: hipLaunchKernelGGL((k_sensitivity<NCH>), dim3(grid), dim3(WG), 0, s, a.db, a.nrhs, a.sensV, a.sensDg, a.sensDb, a.sensSide, a.sensInfo); break;
         case ID_k_build_C:    hipLaunchKernelGGL((k_build_C<NCH>), dim3(grid), dim3(WG), 0, s, a.db); break;
         case ID_k_compress_C: hipLaunchKernelGGL((k_compress_C<NCH>), dim3(grid), dim3(WG), 0, s, a.db); break;

@@ -6,7 +6,7 @@
 namespace lcqp {
 
 enum KernelId { ID_k_prepare, ID_k_build_C, ID_k_compress_C, ID_k_factor, ID_k_factor_full, ID_k_trsm, ID_k_trsm_streamed, ID_k_build_M, ID_k_lcqp_run, ID_k_qp_solve,
-                ID_k_synth_fill, ID_k_synth_Q, ID_k_util_symv, ID_k_util_rows, ID_k_util_rows_list, ID_k_refresh, ID_k_sensitivity };
+                ID_k_synth_fill, ID_k_synth_Q, ID_k_util_symv, ID_k_util_rows, ID_k_util_rows_list, ID_k_refresh, ID_k_sensitivity, ID_k_sensitivity_blk };
 
 struct LaunchArgs {
     DevBatch db;
@@ -17,6 +17,7 @@ struct LaunchArgs {
     const double* rho0 = nullptr;       // k_refresh: [B] starting penalties of the warm instances (device), or null
     // k_sensitivity (device buffers; layouts at the kernel)
     int nrhs = 0;
+    int sensFirst = 0;                  // k_sensitivity_blk: workgroup o works on instance sensFirst + o; sensV null: unit vectors
     const double* sensV = nullptr;
     double *sensDg = nullptr, *sensDb = nullptr;
     int *sensSide = nullptr, *sensInfo = nullptr;

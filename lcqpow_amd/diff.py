@@ -50,6 +50,7 @@ class LCQPSolveFunction(torch.autograd.Function):
         x, y, st = bt.solution()
         layer.solves += 1
         layer.y, layer.stats = y, st
+        layer._like = (g.dtype, g.device)
         ctx.layer, ctx.serial = layer, layer.solves
         ctx.given = (lbA is not None, ubA is not None)
         return torch.as_tensor(x, dtype=g.dtype, device=g.device)
@@ -96,6 +97,18 @@ class BatchLCQPLayer:
 
     def __call__(self, g, lbA=None, ubA=None):
         return LCQPSolveFunction.apply(self, g, lbA, ubA)
+
+    def jacobian(self, serial=None):
+        """dx/dg of the layer's last solve, [B][nV][nV] ([b][k][j] = dx_k/dg_j), a tensor of the dtype and on the device of that
+        solve's g (BatchLCQP.jacobian: the blocked kernel on the unit vectors; dense arm).  serial: the value of layer.solves right
+        after the solve that is meant -- like backward, the call raises when that is not the last one.  layer.info holds the flags."""
+        if self.solves == 0 or (serial is not None and serial != self.solves):
+            raise RuntimeError("jacobian of a solve that is not the layer's last one: the batch object holds the state of one solve")
+        if self.sparse:
+            raise RuntimeError("jacobian: only the dense arm has the blocked kernel")
+        Jg, _, _, info = self.bt.jacobian(bounds=False)
+        self.info = info
+        return torch.as_tensor(Jg, dtype=self._like[0], device=self._like[1])
 
 
 class SparseBatchLCQPLayer(BatchLCQPLayer):

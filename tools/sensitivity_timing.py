@@ -8,7 +8,12 @@ usage: python tools/sensitivity_timing.py [--log FILE] [--reps 30]
 run, nrhs = 1: n = 4096 with B = 4096 (skipped with --quick), and (512, 256, 64) with B = 1024 on the band engine and, under
 LCQP_SPARSE_GENERAL=1, on the general LDL'.  Beside each, on the same handle in the same process, the time of a warm resolve of unchanged
 data (refresh + homotopy, last_timing) -- the unit a finite-difference gradient pays 2 nV times.
-    python tools/sensitivity_timing.py --sparse [--quick] [--log FILE] [--reps 20]"""
+    python tools/sensitivity_timing.py --sparse [--quick] [--log FILE] [--reps 20]
+
+--blocked: k_sensitivity_blk (lcqp_hip_batch_sensitivity_blocked) beside k_sensitivity on the same handle in the same process, the calls
+interleaved, for nrhs = 1, 16, 64, 256 on the BASELINE shape (B = 1024, n = 256, nC = 512, nComp = 64) and on (40, 20, 8) with B = 1024;
+then jacobian() beside the vector call on an uploaded identity, kernel time and wall clock.
+    python tools/sensitivity_timing.py --blocked [--quick] [--log FILE] [--reps 20]"""
 import argparse
 import os
 import sys
@@ -80,6 +85,60 @@ def measure_sparse(B, n, nC, nK, general, reps, warmup=3):
                 fd_ratio=2.0 * n * float(np.median(warm)) / float(np.median(ms)))
 
 
+def measure_blocked(B, n, nC, nComp, nrhs_list, reps, warmup=3):
+    import time
+    bt = la.BatchLCQP(B, n, nC, nComp, opt=la.default_options())
+    bt.generate_synthetic(0)
+    bt.run()
+    lines = []
+    rng = np.random.default_rng(0)
+    stat = lambda ms: (float(np.min(ms)), float(np.median(ms)), float(np.max(ms)))
+    for nrhs in nrhs_list:
+        v = rng.standard_normal((B, nrhs, n))
+        vec, blk = [], []
+        for r in range(warmup + reps):      # interleaved: one vector call, one blocked call
+            bt.sensitivity(v)
+            t0 = bt.sensitivity_kernel_ms()
+            bt.sensitivity(v, blocked=True)
+            t1 = bt.sensitivity_kernel_ms()
+            if r >= warmup:
+                vec.append(t0); blk.append(t1)
+        a, b = stat(vec), stat(blk)
+        lines.append("n = %d B = %d nrhs = %3d: vector kernel ms min / median / max = %.4f / %.4f / %.4f; blocked = %.4f / %.4f / %.4f; "
+                     "vector median / blocked median = %.2f; blocked median below vector min: %s"
+                     % (n, B, nrhs, a[0], a[1], a[2], b[0], b[1], b[2], a[1] / b[1], b[1] < a[0]))
+        print(lines[-1], flush=True)
+    # the Jacobian: the device's unit vectors against an uploaded identity through the vector kernel
+    eye = np.ascontiguousarray(np.broadcast_to(np.eye(n), (B, n, n)))
+    kj, wj, kv, wv = [], [], [], []
+    for r in range(1 + max(3, reps // 4)):
+        t = time.perf_counter(); Jg = bt.jacobian(bounds=False)[0]; w1 = time.perf_counter() - t
+        k1 = bt.sensitivity_kernel_ms()
+        t = time.perf_counter(); dg = bt.sensitivity(eye)[0]; w0 = time.perf_counter() - t
+        k0 = bt.sensitivity_kernel_ms()
+        if r >= 1:
+            kj.append(k1); wj.append(1e3 * w1); kv.append(k0); wv.append(1e3 * w0)
+    sym = float(np.abs(Jg - Jg.transpose(0, 2, 1)).max())
+    lines.append("n = %d B = %d jacobian(): kernel ms min / median / max = %.3f / %.3f / %.3f, wall ms median %.1f; vector kernel on an uploaded identity: "
+                 "%.3f / %.3f / %.3f, wall ms median %.1f; max |jacobian - vector| = %.3g, max |Jg - Jg'| = %.3g"
+                 % ((n, B) + stat(kj) + (float(np.median(wj)),) + stat(kv) + (float(np.median(wv)), float(np.abs(Jg - dg).max()), sym)))
+    print(lines[-1], flush=True)
+    bt.close()
+    return lines
+
+
+def blocked_main(a):
+    lines = []
+    nr = (1, 16, 64) if a.quick else (1, 16, 64, 256)
+    for B, n, nC, nComp in ((1024, 40, 20, 8), (256 if a.quick else 1024, 256, 512, 64)):
+        lines += measure_blocked(B, n, nC, nComp, nr, a.reps)
+    if a.log:
+        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
+        with open(a.log, "w") as f:
+            f.write("k_sensitivity_blk beside k_sensitivity, synthetic workload after run, one handle, calls interleaved; %d timed calls after 3 warm-up calls each\n" % a.reps)
+            f.write("\n".join(lines) + "\n")
+
+
 def sparse_main(a):
     shapes = [(1024, 512, 256, 64, False), (1024, 512, 256, 64, True)]
     if not a.quick:
@@ -103,12 +162,15 @@ def main():
     ap.add_argument("--log")
     ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--sparse", action="store_true", help="the sparse arm's kernel beside a warm resolve of unchanged data")
-    ap.add_argument("--quick", action="store_true", help="--sparse: without the n = 4096, B = 4096 batch")
+    ap.add_argument("--quick", action="store_true", help="--sparse: without the n = 4096, B = 4096 batch; --blocked: B = 256 at n = 256, without nrhs = 256")
+    ap.add_argument("--blocked", action="store_true", help="the blocked kernel beside the vector kernel, and the Jacobian")
     a = ap.parse_args()
     if la.device_count() < 1:
         raise SystemExit("needs a GPU (no CPU fallback)")
     if a.sparse:
         return sparse_main(a)
+    if a.blocked:
+        return blocked_main(a)
     lines = []
     for B, nrhs in ((1024, 1), (1024, 8), (1, 1), (1, 8)):
         r = measure(B, nrhs, a.reps)
