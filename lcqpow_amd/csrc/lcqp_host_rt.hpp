@@ -1,4 +1,4 @@
-// lcqp_host_rt.hpp -- host runtime shared by the C ABIs of the dense (lcqp_hip.hip) and sparse (lcqp_sparse.hip) arms: error reporting,
+// lcqp_host_rt.hpp -- host runtime shared by the C ABIs of the dense (lcqp_hip.hip) and sparse (lcqp_sparse_host.hip) arms: error reporting,
 // owners of streams, events and device memory, and the entry-point bodies both arms have in common.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,5 +1,5 @@
 // lcqp_launch.hpp -- the seam between the host translation unit (lcqp_hip.hip) and the per-size kernel translation units
-// (lcqp_nch.hip, one per NCH in {1,2,3,4,8}).
+// (lcqp_nch.hip, one per NCH in {1,2,3,4,8,16,32}).
 #pragma once
 #include "lcqp_dev.hpp"
 

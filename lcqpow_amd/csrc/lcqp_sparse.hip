@@ -18,134 +18,32 @@
 // Patterns whose KKT band is wider take a bordered band (a few dense nodes behind the band, e.g. the arrow-shaped circle example) or the
 // general sparse LDL' (lcqp_sparse_general.hpp); what neither holds is refused here, and the host layer runs it on the dense kernels behind
 // the same OSQP_SPARSE surface.
+//
+// Kernels only: the host side of lcqp_hip_sparse_* is lcqp_sparse_host.hip, and lcqp_sparse_launch.hpp is the seam between the two (the
+// batch struct the kernels take, the launch functions defined at the end of this file).  One translation unit per lane-group width:
+// compile with -DLCQP_TU_G=G.
 #include "lcqp_wg.hpp"
-#include "../../include/lcqp_hip.h"
-#include "lcqp_sparse_pattern.hpp"
-#include "lcqp_host_rt.hpp"
+#include "lcqp_sparse_launch.hpp"
+#include "lcqp_sparse_pattern.hpp"      // GEN_MAX_FRONT
 
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
-#include <memory>
-#include <string>
-#include <vector>
+
+#ifndef LCQP_TU_G
+#error "compile lcqp_sparse.hip with -DLCQP_TU_G=8|16|32|64"
+#endif
+#define LCQP_CAT2(a, b) a##b
+#define LCQP_CAT(a, b) LCQP_CAT2(a, b)
 
 using namespace lcqp;
+using namespace lcqp_sparse;
 
 namespace {
 
 constexpr int WGS = 64;      // one wavefront per workgroup; 64 / G instances in it
 constexpr int SCHED_WAVES_PER_SIMD = 2;   // register budget of k_sparse_sched at G <= 8: 512 / SCHED_WAVES_PER_SIMD per lane
-enum { NV_G, NV_GTIL, NV_GPHI, NV_XK, NV_PK, NV_XNEW, NV_GK, NV_QX, NV_CX, NV_QP, NV_CP, NV_TMP, NV_XQ, NV_XA, NV_XT, NV_R1,
-       NV_X0, NV_NUM };
-enum { MV_L, MV_U, MV_RHOV, MV_YQ, MV_YA, MV_ZA, MV_YT, MV_EX, MV_YK, MV_Y0, MV_LX, MV_LX2, MV_NUM };
-enum { MI_ST, MI_STT, MI_STF, MI_NEW, MI_NUM };
-
-struct SpInfo {
-    int haveSolution, stfValid, hasY0, bigReg;     // bigReg: this instance needs the safe regularisation of the polish (a Hessian that is only semidefinite)
-    int warm, pad0;                                // warm (k_sparse_refresh): sp_ph_start begins at the last solution, at the penalty rho0, without the zero-penalty QP
-    double rho0;
-    double scale, sigma, delta, delta2, phiConst;
-    double deltaS, delta2S;                        // the light level tried first (sp_polish)
-    double e1max;                                  // largest row 1-norm of E: with |x|_inf the scale of the rounding of a computed E_r x (the active-row test of the polish)
-    double hist[64];
-    double bytes;        // algorithmic bytes counted by the kernel
-    double prof[8];      // -DLCQP_PROFILE: clock ticks per phase (SP_* below)
-};
-enum { SP_PRODUCTS, SP_ASSEMBLE, SP_FACTOR, SP_FORWARD, SP_BACKWARD, SP_VECTORS, SP_LCQP, SP_RHS, SP_NPHASE };
-
-// ---- the homotopy as a phase machine (round 4) ----------------------------------------------------------------------------------------
-// Round 3 ran the whole homotopy of an instance inside one persistent lane group: the 64 / G instances of a wavefront moved in lock step, an
-// instance was active in 74 % of its wavefront's trials and refactorised in 26 % of them while its wavefront did in 83 %.  Now an instance is
-// a record in memory (SpState + its vectors) that moves through QUEUES, one per phase; a wavefront pops up to 64 / G instances that are in
-// the SAME phase, runs that phase for them, and pushes each to the queue of its next phase (k_sparse_sched).  A wavefront therefore only
-// ever holds instances doing the same thing; nobody waits for a neighbour's factorisation or for the slowest polish of eight.
-enum { PH_START, PH_ROUND, PH_TRIAL, PH_FACTOR, PH_CORRECT, PH_QPEND, PH_NUM };
-enum { BY_ASSEMBLE, BY_FACTOR_LDS, BY_FACTOR, BY_SOLVE, BY_BORDER_PREPARE, BY_BORDER_SOLVE, BY_EX, BY_SWEEP, BY_START, BY_E, BY_NUM };
-struct SpState {
-    // LCQProblem::runSolver (src/LCQProblem.cpp:444-560)
-    int initial, histLen, algoStat, totalIter, rc, qpIter;
-    double alphak, rho, gmaxNext;
-    unsigned long long perturbCounter;
-    lcqp_stats_t st;
-    // the subsolver call (oracle: sqp_solve)
-    int round, n_admm, use_stored, backup_pending, admm_ready, trials0, admm0;
-    // the polish (oracle: sqp_polish)
-    int trial, reuse, fact_valid, borderTodo, nrefine;      // nrefine: refinement corrections taken for the active rows alone
-    double gs, ytol, dpUsed, d2Used, xinf;                  // xinf: |x|_inf behind the last correction
-    // work counters
-    int cAdmm, cTrials, cFact, cCorr, cSweeps;
-    double bytes;
-};
-// Queues: the batch is cut into pools of `poolSize` consecutive instances (a power of two; the byte offset of an instance inside its pool fits
-// 32 bits for every per-instance array: the saddr + 32-bit offset addressing of SpCtx::arr); wavefront w serves pool w % nPools.  Per pool
-// and phase a ring of poolSize entries (an instance is in at most one queue) and three counters: tail (next position to write), head (next
-// position to read), count (entries published); every ring slot carries a SEQUENCE number beside the instance id (a bounded multi-producer /
-// multi-consumer queue after Vyukov; sequence and id share one 64-bit word, written by one store): slot p & mask is free for position p when
-// its sequence is p, holds position p's entry when it is p + 1, and is handed on to position p + poolSize by its consumer -- a producer that laps the ring onto a slot whose entry has been claimed but not
-// read yet waits instead of overwriting it.  ctl[pool][PH_NUM] = instances of the pool not finished yet.
-constexpr int QCTL = 4;      // ints per (pool, phase): tail, head, count, pad
-
-struct EllMat { const int *eidx, *epos, *ptr, *cidx, *cmap; int rows, W, tails; };   // see g_ell
-
-struct SpBatch {
-    int B, n, m, nC, nComp, N, Np, w, ld, nnzQ, nnzE, G;  // Np: N rounded up to a multiple of 64 (padding rows: zero coefficients)
-    int hasLbL, hasLbR;
-    lcqp_options_t opt;
-    const int *Qp, *Qi, *Ep, *Ei, *ETp, *ETi, *ETmap, *iperm, *bandQ, *bandE;
-    const int *bsrc, *pnode, *qdiag, *Erow;   // band entry -> value it comes from (sp_factor_reg), node of a band position, Q_ii, row of an E entry
-    const int *bgate, *bdiag;                 // band entry -> the row of E whose membership in the working set gates it (-1: none); band position -> its diagonal (sp_factor_reg)
-    EllMat ellQ, ellE, ellT; // rows of Q, rows of E, columns of E in ELL slabs
-    double *Qx, *Ex;         // [B][nnzQ], [B][nnzE] (CSR order)
-    double *Kb;              // [B][N*ld] assembled band rows (input of a factorisation): Kb[i*ld + k] = K[i][i-w+k]
-    double *KaF, *KaD;       // ADMM KKT factor in the folded layout of band_sweep [B][Np*G], 1/D [B][Np]
-    double *KpF, *KpD;       // polish KKT factor
-    double* K0;              // [Np][G] per instance: the band rows of [Q, E'; E, .] with every row of E in, diagonal slot Q_ii (variables) -- what sp_factor_reg streams
-    int bitWords;            // 32-bit words of a working set's bit set in LDS (sp_ph_factor), 0: it does not fit, the flags are read from memory
-    double *nv, *mv, *Nv;    // [B][NV_NUM][n], [B][MV_NUM][m], [B][2][Np]
-    // Bordered band (round 3): the last kb positions of the ordering are border nodes -- rows or variables too dense for any band (the
-    // coupling constraint and the two shared variables of examples/OptimizeOnCircle.cpp).  K = [Bd U'; U C]: the band engine factorises
-    // Bd with the border positions as isolated unit pivots; the border is carried by W = U inv(Bd) (kb band solves per factorisation) and
-    // the Schur complement S = C - W U' (kb x kb, dense LDL').  U: per border node the entries it shares with band nodes (Upos: band
-    // position, Usrc: entry of Q (k < nnzQ) or of E (nnzQ + k, CSR order), Ugate: the row of E whose membership in the working set gates
-    // the entry, -1 none); C: the entries among border nodes, lower triangle (Cb2: the other border node).
-    int kb, nU, nCb;
-    int lightOK;     // the ordering puts every row behind one of its variables and every Hessian of the batch is safely definite: the polish tries its light regularisation first
-    const int *bnode, *Uptr, *Upos, *Usrc, *Ugate, *Cptr, *Cb2, *Csrc, *Cgate;
-    double *bW, *bUv, *bS;   // [B][2][kb][Np] W rows, [B][2][nU] gated values of U, [B][2][kb][kb] factor of S   (index 0: polish, 1: ADMM)
-    double *lbL, *lbR;       // [B][nComp]
-    int* mi;                 // [B][MI_NUM][m]
-    SpInfo* info;
-    lcqp_stats_t* stats;
-    double *xout, *yout;     // [B][n], [B][m]
-    // per-iterate tracking (options.storeSteps, src/LCQProblem.cpp:1365-1378), as on the dense path: [B][traceCap][8] = (|statk|inf, phi, rho,
-    // alphak, obj, merit, |pk|inf, QP iterations), [B][traceCap][n] = xk, traceLen[B]; traceCap == 0: not allocated
-    double *traceS, *traceX;
-    int* traceLen;
-    int traceCap;
-    // phase machine
-    SpState* state;          // [B]
-    unsigned long long* qring;  // [nPools][PH_NUM][poolSize] ring slots: (sequence number << 32) | instance id, one 64-bit word so that a slot changes hands in one store
-    int* qctl;                  // [nPools][PH_NUM + 1][QCTL]
-    int poolSize, nPools;
-    int wideDiv;                // SIMDs of the device per pool (sp_launch): unfinished instances of the pool / wideDiv = instances of a streaming step
-    // General sparse LDL' (round 6; lcqp_sparse_general.hpp): patterns that are neither banded nor bordered -- multifrontal over a nested-
-    // dissection tree with dense fronts, one wavefront per instance (G = 64).  general != 0: KaF / KpF hold the panels of the fronts
-    // (gLsize doubles per instance instead of Np * G), KaD / KpD 1 / D per position as for the band; kb = 0, lightOK = 0.
-    int general, gnF, gMaxFront;
-    unsigned gLsize, gStackSize;
-    const int *gPiv0, *gNp, *gNb, *gRowPtr, *gRows, *gChildPtr, *gChild, *gRel, *gAsmPtr, *gAsmSrc, *gAsmGate, *gAsmPos;
-    const unsigned *gLoff, *gCBoff;
-    const int *gMeta, *gChildInfo;   // [gnF][GEN_META] np, nb, piv0, rowPtr, asmPtr, asmEnd, childPtr, childEnd, Loff, CBoff: one load per front; [children][4] nb, CBoff, rowPtr of the child
-    double *gStack, *gFront;     // [B][gStackSize] update blocks of the fronts, [B][gMaxFront^2] a front too large for LDS
-    size_t kfStride;             // doubles per instance of KaF / KpF
-    // algorithmic bytes of one event of each kind (filled by the host: formed in the kernel they are loop invariants the compiler keeps in
-    // registers across every phase)
-    double by[BY_NUM];
-    unsigned long long* qprof;   // [PH_NUM + 1][3] (-DLCQP_SCHED_PROFILE): clock ticks, wavefront steps, instances served per phase; row PH_NUM: ticks / polls without work
-};
 
 // ---- addressing: uniform base pointer + 32-bit lane offset -------------------------------------------------------------------------
 // Every per-instance array is reached as (base of the wave's first instance: uniform, SGPRs) + (byte offset of the lane's instance
@@ -709,7 +607,6 @@ constexpr int GEN_JB = 8;
 constexpr int GEN_LDS_FRONT = 64;        // fronts up to this size are factorised inside LDS
 using lcqp_pattern::GEN_MAX_FRONT;       // the panel of the largest front (lcqp_sparse_pattern.hpp refuses larger ones)
 
-constexpr int GEN_META = 12;
 constexpr int GEN_BITS_OFF = GEN_MAX_FRONT * GEN_JB + 16;        // doubles: the working set as a bit set behind the panel and 1 / D of a block
 constexpr int GEN_BITS_WORDS = (GEN_LDS_FRONT * GEN_LDS_FRONT + 16 * 64 - GEN_BITS_OFF) * 2;      // 32-bit words that fit the rest of the window
 
@@ -2317,7 +2214,7 @@ __global__ void k_sparse_sched_init(SpBatch db)
 
 // refresh: k_sparse_refresh<G>(mode, rho0) stands where k_sparse_setup<G> stands (lcqp_hip_sparse_resolve)
 template <int G>
-static void sp_launch(const SpBatch& db, hipStream_t stream, hipEvent_t mid, bool refresh = false, int mode = 0, const double* rho0 = nullptr)
+static void sp_launch(const SpBatch& db, hipStream_t stream, hipEvent_t mid, bool refresh, int mode, const double* rho0)
 {
     const int ipw = 64 / G, grid = (db.B + ipw - 1) / ipw;
     // LDS: the working sets' bit sets of sp_ph_factor (G <= 16), the window of sp_factor_lds (per group G x G and 16 staged rows) otherwise
@@ -2344,414 +2241,21 @@ static void sp_launch(const SpBatch& db, hipStream_t stream, hipEvent_t mid, boo
     hipLaunchKernelGGL(k_sparse_sched<G>, dim3(waves), dim3(WGS), ldsBytes, stream, dbs);
 }
 
-}  // namespace
-
-// =================================================================================================
-// host side
-// =================================================================================================
-using namespace lcqp_rt;
-
-static thread_local std::string g_sp_err;
-extern "C" const char* lcqp_hip_sparse_last_error(void) { return g_sp_err.c_str(); }
-
-// The members are released in reverse order after the destructor's synchronisation: device memory, events, stream.
-struct lcqp_hip_sparse {
-    SpBatch db;
-    int device;
-    Stream stream;
-    Event ev0, ev1, ev2;           // run: setup from ev0 to ev1, homotopy from ev1 to ev2
-    DevMem mem{stream};            // zero-fills on the handle's stream
-    std::vector<int> csr2csc;      // value order: E (CSR) entry k comes from entry csr2csc[k] of the caller's CSC arrays
-    // the two orderings of the band (lcqp_sparse_pattern.hpp: Pattern::ord): device copies of their maps, the permutation for get_ordering
-    struct Ord { std::vector<int> perm; int *iperm, *bandQ, *bandE, *bsrc, *bgate, *bdiag, *pnode, *Upos; bool rowsFollow; } ord[2] = {};
-    bool hasB = false;
-    int useB = 0;                  // ordering of the last sp_choose_ordering
-    std::vector<int> qdiagHost;    // entry of Q_ii in the value array
-    std::vector<double> diagRatio; // per instance: min_i Q_ii / max_i Q_ii of the loaded Hessian (1: not loaded yet)
-    bool loaded = false, ran = false;
-    // re-solves and sensitivities (lcqp_host_rt.hpp).  This arm has no setup without a solve: setupValid and solved go together;
-    // rhoStart is allocated by the first resolve that carries penalties
-    ResolveState rs;
-    SensBuffers sens;
-    explicit lcqp_hip_sparse(int dev) : db(), device(dev) {}
-    ~lcqp_hip_sparse() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
-};
-
-// Ordering [1] and the light regularisation of the polish are for batches whose Hessians are safely definite, judged by their diagonals
-// (min Q_ii >= 1e-6 max Q_ii in every loaded instance); the pivot check of sp_polish covers what the diagonals do not show.
-static void sp_choose_ordering(lcqp_hip_sparse* h)
-{
-    bool definite = h->loaded;      // nothing loaded yet: the plain ordering
-    for (double r : h->diagRatio) definite = definite && (r >= 1e-6);
-    const int k = (definite && h->hasB) ? 1 : 0;
-    const lcqp_hip_sparse::Ord& o = h->ord[k];
-    SpBatch& d = h->db;
-    d.iperm = o.iperm; d.bandQ = o.bandQ; d.bandE = o.bandE; d.bsrc = o.bsrc; d.bgate = o.bgate; d.bdiag = o.bdiag; d.pnode = o.pnode; d.Upos = o.Upos;
-    d.lightOK = (definite && o.rowsFollow) ? 1 : 0;
-    h->useB = k;
-}
-
-// the pattern analysis (lcqp_sparse_pattern.hpp), then the device copies of its arrays and the storage of the batch
-extern "C" lcqp_hip_sparse_t* lcqp_hip_sparse_create(int batch, int nV, int nC, int nComp, const int* Qp, const int* Qi, const int* Ap, const int* Ai, int device)
-{ return guarded(g_sp_err, [&]() -> lcqp_hip_sparse_t* {
-    if (batch <= 0 || nV <= 0 || nC < 0 || nComp <= 0 || !Qp || !Qi || !Ap || !Ai) { g_sp_err = "invalid arguments"; return nullptr; }
-    lcqp_pattern::Hooks hooks;
-    if (const char* e = std::getenv("LCQP_SPARSE_GENERAL")) hooks.general = std::atoi(e) == 1;      // test hook: the general LDL' on a pattern the band engine would take
-    if (const char* e = std::getenv("LCQP_SPARSE_LANES")) hooks.lanes = std::atoi(e);               // test hook: a wider lane group than the band needs
-    lcqp_pattern::Pattern P;
-    if (!lcqp_pattern::analyse_pattern(nV, nC, nComp, Qp, Qi, Ap, Ai, hooks, P, g_sp_err)) return nullptr;
-    const int n = P.n, m = P.m, N = P.N, nnzQ = P.nnzQ, nnzA = P.nnzE, w = P.w, G = P.G, ld = G, kb = P.kb;
-    const int nU = (int)P.Usrc.size(), nCb = (int)P.Csrc.size();
-    const bool general = P.general;
-    const lcqp_general::Symbolic& sym = P.sym;
-    if (hipError_t e = hipSetDevice(device)) { hip_fail(g_sp_err, "hipSetDevice failed", e); return nullptr; }
-    std::unique_ptr<lcqp_hip_sparse> h(new lcqp_hip_sparse(device));
-    for (hipError_t e : {h->stream.status, h->ev0.status, h->ev1.status, h->ev2.status})
-        if (e != hipSuccess) { hip_fail(g_sp_err, "stream/event creation", e); return nullptr; }
-    h->csr2csc = P.csr2csc; h->hasB = P.hasB; h->qdiagHost = P.qdiag; h->diagRatio.assign(batch, 1.0); h->rs.filled.assign(batch, 0);
-    SpBatch& d = h->db;
-    d.B = batch; d.n = n; d.m = m; d.nC = nC; d.nComp = nComp; d.N = N; d.Np = ((N + 63) / 64) * 64; d.w = w; d.ld = ld; d.nnzQ = nnzQ; d.nnzE = nnzA; d.G = G; d.kb = kb; d.nU = nU; d.nCb = nCb;
-    d.general = general ? 1 : 0;
-    d.kfStride = general ? (size_t)sym.Lsize : (size_t)d.Np * G;
-    if (general) { d.gnF = sym.nF; d.gMaxFront = sym.maxFront; d.gLsize = (unsigned)sym.Lsize; d.gStackSize = (unsigned)std::max<long long>(sym.stackSize, 1); d.w = 0; }
-    d.bitWords = (G <= 16 && (size_t)(64 / G) * ((m + 31) / 32) * sizeof(unsigned) <= 16384) ? (m + 31) / 32 : 0;      // at most 16 KB of LDS per wavefront
-    if (const char* e = std::getenv("LCQP_SPARSE_NOBITS")) { if (std::atoi(e) == 1) d.bitWords = 0; }                    // test hook: the path of problems with more rows than that
-    {   // algorithmic bytes per event (what each event has to read and write once: 8-byte values, 4-byte indices)
-        const double dN = N, dq = nnzQ, de = nnzA, Nb = N - kb;
-        d.by[BY_ASSEMBLE] = 8.0 * (dN * ld + dq + de) + 4.0 * (dq + de);
-        d.by[BY_FACTOR_LDS] = 8.0 * (3.0 * dN * (w + 1));
-        d.by[BY_FACTOR] = 12.0 * (dq + de) + 8.0 * dN * (w + 2);
-        d.by[BY_SOLVE] = 8.0 * (2.0 * dN * w + 4.0 * dN);
-        d.by[BY_BORDER_PREPARE] = 8.0 * (2.0 * (double)nU + (double)kb * d.Np);
-        d.by[BY_BORDER_SOLVE] = 8.0 * ((double)kb * Nb + 2.0 * Nb + nU);
-        d.by[BY_EX] = 12.0 * de + 8.0 * (n + m);
-        d.by[BY_SWEEP] = 12.0 * (dq + de) + 8.0 * (3.0 * n + m);
-        d.by[BY_START] = 12.0 * dq + 2.0 * 12.0 * de;
-        d.by[BY_E] = 12.0 * de;
-        if (general) {      // a factorisation reads every value of Q and E once and writes the panels and 1 / D; a solve reads the panels twice
-            d.by[BY_FACTOR] = 12.0 * (dq + de) + 8.0 * ((double)sym.Lsize + dN);
-            d.by[BY_SOLVE] = 8.0 * (2.0 * (double)sym.Lsize + 4.0 * dN);
-        }
-    }
-    const size_t Np = d.Np;
-    lcqp_hip_options_default(&d.opt);
-    const size_t B = batch;
-    DevMem& mm = h->mem;
-    std::string& err = g_sp_err;
-    bool ok = mm.alloc(err, d.Qp, n + 1, Qp) && mm.alloc(err, d.Qi, nnzQ, Qi) && mm.alloc(err, d.Ep, m + 1, P.Ep.data()) &&
-         mm.alloc(err, d.Ei, nnzA, P.Ei.data()) && mm.alloc(err, d.ETp, n + 1, P.ETp.data()) && mm.alloc(err, d.ETi, nnzA, P.ETi.data()) &&
-         mm.alloc(err, d.ETmap, nnzA, P.ETmap.data()) &&
-         mm.alloc(err, d.qdiag, n, P.qdiag.data()) && mm.alloc(err, d.Erow, nnzA, P.Erow.data());
-    for (int k = 0; k < (P.hasB ? 2 : 1); k++) {
-        const lcqp_pattern::Ordering& M = P.ord[k];
-        lcqp_hip_sparse::Ord& o = h->ord[k];
-        ok = ok && mm.alloc(err, o.iperm, N, M.iperm.data()) && mm.alloc(err, o.bandQ, nnzQ, M.bandQ.data()) &&
-             mm.alloc(err, o.bandE, nnzA, M.bandE.data()) && mm.alloc(err, o.bsrc, M.bsrc.size(), M.bsrc.data()) &&
-             mm.alloc(err, o.bgate, M.bgate.size(), M.bgate.data()) && mm.alloc(err, o.bdiag, M.bdiag.size(), M.bdiag.data()) &&
-             mm.alloc(err, o.pnode, N, M.perm.data()) && mm.alloc(err, o.Upos, nU, M.Upos.data());
-        o.perm = M.perm; o.rowsFollow = M.rowsFollow;
-    }
-    if (ok) sp_choose_ordering(h.get());
-    if (kb > 0)
-        ok = ok && mm.alloc(err, d.bnode, kb, P.border.data()) && mm.alloc(err, d.Uptr, kb + 1, P.Uptr.data()) &&
-             mm.alloc(err, d.Usrc, nU, P.Usrc.data()) && mm.alloc(err, d.Ugate, nU, P.Ugate.data()) && mm.alloc(err, d.Cptr, kb + 1, P.Cptr.data()) &&
-             mm.alloc(err, d.Cb2, nCb, P.Cb2.data()) && mm.alloc(err, d.Csrc, nCb, P.Csrc.data()) && mm.alloc(err, d.Cgate, nCb, P.Cgate.data()) &&
-             mm.alloc(err, d.bW, (size_t)batch * 2 * kb * d.Np) && mm.alloc(err, d.bUv, (size_t)batch * 2 * nU) &&
-             mm.alloc(err, d.bS, (size_t)batch * 2 * kb * kb);
-    // ELL slabs of the three gathers (g_ell): rows of Q, rows of E, columns of E
-    auto ell = [&](EllMat& e, const lcqp_pattern::Ell& s, int rows, const int* dptr, const int* didx, const int* dmap) {
-        e.rows = rows; e.W = s.W; e.tails = s.tails; e.ptr = dptr; e.cidx = didx; e.cmap = dmap; e.epos = nullptr;
-        return mm.alloc(err, e.eidx, s.eidx.size(), s.eidx.data()) && (s.epos.empty() || mm.alloc(err, e.epos, s.epos.size(), s.epos.data()));
-    };
-    ok = ok && ell(d.ellQ, P.ellQ, n, d.Qp, d.Qi, nullptr) && ell(d.ellE, P.ellE, m, d.Ep, d.Ei, nullptr) && ell(d.ellT, P.ellT, n, d.ETp, d.ETi, d.ETmap);
-    ok = ok && mm.alloc(err, d.Qx, B * nnzQ) && mm.alloc(err, d.Ex, B * nnzA) &&
-         mm.alloc(err, d.Kb, (G > 16 && !general) ? B * N * ld : 0) &&      // the band array is only written by the LDS-window factorisation
-         mm.alloc(err, d.KaF, B * d.kfStride) && mm.alloc(err, d.KaD, B * Np) &&
-         mm.alloc(err, d.KpF, B * d.kfStride) && mm.alloc(err, d.KpD, B * Np) &&
-         mm.alloc(err, d.K0, G <= 16 ? B * Np * G : 0) &&
-         mm.alloc(err, d.nv, B * NV_NUM * n) && mm.alloc(err, d.mv, B * MV_NUM * m) && mm.alloc(err, d.Nv, B * 2 * Np) &&
-         mm.alloc(err, d.lbL, B * nComp) && mm.alloc(err, d.lbR, B * nComp) && mm.alloc(err, d.mi, B * MI_NUM * m) &&
-         mm.alloc(err, d.info, B) && mm.alloc(err, d.stats, B) && mm.alloc(err, d.xout, B * n) &&
-         mm.alloc(err, d.yout, B * m);
-    if (general) {
-        std::vector<unsigned> lo(sym.Loff.begin(), sym.Loff.end()), co(sym.CBoff.begin(), sym.CBoff.end());
-        std::vector<int> meta((size_t)sym.nF * GEN_META, 0), cinfo(std::max<size_t>(sym.child.size(), 1) * 4, 0);
-        for (int f = 0; f < sym.nF; f++) {
-            int* mt = meta.data() + (size_t)f * GEN_META;
-            mt[0] = sym.np[f]; mt[1] = sym.nb[f]; mt[2] = sym.piv0[f]; mt[3] = sym.rowPtr[f]; mt[4] = sym.asmPtr[f]; mt[5] = sym.asmPtr[f + 1];
-            mt[6] = sym.childPtr[f]; mt[7] = sym.childPtr[f + 1]; mt[8] = (int)sym.Loff[f]; mt[9] = (int)sym.CBoff[f];
-        }
-        for (size_t ci = 0; ci < sym.child.size(); ci++) { const int ch = sym.child[ci]; cinfo[4 * ci] = sym.nb[ch]; cinfo[4 * ci + 1] = (int)sym.CBoff[ch]; cinfo[4 * ci + 2] = sym.rowPtr[ch]; }
-        ok = ok && mm.alloc(err, d.gPiv0, sym.piv0.size(), sym.piv0.data()) && mm.alloc(err, d.gNp, sym.np.size(), sym.np.data()) &&
-             mm.alloc(err, d.gNb, sym.nb.size(), sym.nb.data()) && mm.alloc(err, d.gRowPtr, sym.rowPtr.size(), sym.rowPtr.data()) &&
-             mm.alloc(err, d.gRows, std::max<size_t>(sym.rows.size(), 1), sym.rows.empty() ? nullptr : sym.rows.data()) &&
-             mm.alloc(err, d.gChildPtr, sym.childPtr.size(), sym.childPtr.data()) &&
-             mm.alloc(err, d.gChild, std::max<size_t>(sym.child.size(), 1), sym.child.empty() ? nullptr : sym.child.data()) &&
-             mm.alloc(err, d.gRel, std::max<size_t>(sym.rel.size(), 1), sym.rel.empty() ? nullptr : sym.rel.data()) &&
-             mm.alloc(err, d.gAsmPtr, sym.asmPtr.size(), sym.asmPtr.data()) && mm.alloc(err, d.gAsmSrc, sym.asmSrc.size(), sym.asmSrc.data()) &&
-             mm.alloc(err, d.gAsmGate, sym.asmGate.size(), sym.asmGate.data()) && mm.alloc(err, d.gAsmPos, sym.asmPos.size(), sym.asmPos.data()) &&
-             mm.alloc(err, d.gLoff, lo.size(), lo.data()) && mm.alloc(err, d.gCBoff, co.size(), co.data()) &&
-             mm.alloc(err, d.gMeta, meta.size(), meta.data()) && mm.alloc(err, d.gChildInfo, cinfo.size(), cinfo.data()) &&
-             mm.alloc(err, d.gStack, B * d.gStackSize) && mm.alloc(err, d.gFront, B * (size_t)d.gMaxFront * d.gMaxFront);
-    }
-    {
-        // pools of the phase machine (k_sparse_sched): the largest power of two of instances whose per-instance arrays all stay below 4 GiB
-        // (the 32-bit lane offsets of SpCtx::arr), at most the batch rounded up to a power of two
-        size_t perInst = sizeof(double) * std::max<size_t>({(size_t)nnzQ, (size_t)nnzA, 2 * Np, (size_t)((G > 16 && !general) ? (size_t)N * ld : 0), d.kfStride,
-                                                            general ? (size_t)d.gStackSize : 0, general ? (size_t)d.gMaxFront * d.gMaxFront : 0,
-                                                            2 * (size_t)kb * Np, 2 * (size_t)nU, (size_t)NV_NUM * n, (size_t)MV_NUM * m, (size_t)nComp});
-        perInst = std::max(perInst, sizeof(int) * (size_t)MI_NUM * m);
-        int pool = 1;
-        while ((size_t)(2 * pool) * perInst < ((size_t)1 << 32) && pool < batch) pool *= 2;
-        if (const char* e = std::getenv("LCQP_SPARSE_POOL")) { const int v = std::atoi(e); if (v >= 1 && v < pool && (v & (v - 1)) == 0) pool = v; }      // test hook: several small pools
-        d.poolSize = pool; d.nPools = (batch + pool - 1) / pool;
-        ok = ok && mm.alloc(err, d.state, B) && mm.alloc(err, d.qring, (size_t)d.nPools * PH_NUM * pool) &&
-             mm.alloc(err, d.qctl, (size_t)d.nPools * (PH_NUM + 1) * QCTL) && mm.alloc(err, d.qprof, (PH_NUM + 1) * 3);
-    }
-    if (!ok) { g_sp_err = "device allocation failed: " + g_sp_err; return nullptr; }
-    if (hipError_t e = hipStreamSynchronize(h->stream)) { hip_fail(g_sp_err, "hipStreamSynchronize(h->stream)", e); return nullptr; }      // the zero-fills
-    return h.release();
-}, nullptr); }
-
-extern "C" void lcqp_hip_sparse_destroy(lcqp_hip_sparse_t* h)
-{
-    guarded(g_sp_err, [&] { delete h; });      // ~lcqp_hip_sparse: set the device, synchronise, then the members
-}
-
-extern "C" int lcqp_hip_sparse_bandwidth(const lcqp_hip_sparse_t* h) { return h ? h->db.w : -1; }
-extern "C" int lcqp_hip_sparse_lanes(const lcqp_hip_sparse_t* h) { return h ? h->db.G : -1; }
-extern "C" int lcqp_hip_sparse_border(const lcqp_hip_sparse_t* h) { return h ? h->db.kb : -1; }
-extern "C" int lcqp_hip_sparse_fronts(const lcqp_hip_sparse_t* h) { return h ? (h->db.general ? h->db.gnF : 0) : -1; }
-extern "C" int lcqp_hip_sparse_get_ordering(const lcqp_hip_sparse_t* h, int* perm)
-{
-    if (!h || !perm) return LCQP_INVALID_ARGUMENT;
-    const std::vector<int>& pm = h->ord[h->useB].perm;      // the ordering the loaded Hessians select (sp_choose_ordering)
-    memcpy(perm, pm.data(), sizeof(int) * pm.size());
-    return 0;
-}
-
-// storeSteps: the first 4096 iterates
-extern "C" int lcqp_hip_sparse_set_options(lcqp_hip_sparse_t* h, const lcqp_options_t* opt)
-{ return guarded(g_sp_err, [&] {
-    if (h) h->rs.invalidate();      // the ADMM weights, sigma and the regularisations of the factors come from the options
-    return set_options(g_sp_err, h, opt, 4096);
-}); }
-
-/* per-iterate trace of one instance of the last run (needs options.storeSteps), as lcqp_hip_batch_get_trace */
-extern "C" int lcqp_hip_sparse_get_trace(lcqp_hip_sparse_t* h, int instance, int cap, double* scalars, double* x, int* len)
-{
-    return guarded(g_sp_err, [&] { return get_trace(g_sp_err, h, instance, cap, scalars, x, len); });
-}
-
-// LCQProblem::loadLCQP (sparse overload, src/LCQProblem.cpp:390-441) for instances [first, first + count): values only -- the
-// pattern was given to lcqp_hip_sparse_create.  Qx: [count][nnzQ]; Ax: [count][nnzA] in the CSC order of the stacked [A; L; R].
-extern "C" int lcqp_hip_sparse_load(lcqp_hip_sparse_t* h, int first, int count, const double* Qx, const double* g, const double* Ax,
-                                    const double* lbA, const double* ubA, const double* lbL, const double* ubL, const double* lbR,
-                                    const double* ubR, const double* x0, const double* y0)
-{ return guarded(g_sp_err, [&] {
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    SpBatch& d = h->db;
-    const int n = d.n, m = d.m, nK = d.nComp;
-    if (first < 0 || count <= 0 || first + count > d.B || !Qx || !Ax) return LCQP_INVALID_ARGUMENT;
-    if (!g) return LCQP_INVALID_OBJECTIVE_LINEAR_TERM;
-    HIPCHK(g_sp_err, hipSetDevice(h->device));
-    h->rs.invalidate();
-    std::vector<double> ex(d.nnzE), nvb((size_t)NV_NUM * n), mvb((size_t)MV_NUM * m), lb(nK), rb(nK);
-    for (int k = 0; k < count; k++) {
-        const size_t b = (size_t)first + k;
-        for (int e = 0; e < d.nnzE; e++) ex[e] = Ax[(size_t)k * d.nnzE + h->csr2csc[e]];
-        std::fill(nvb.begin(), nvb.end(), 0.0); std::fill(mvb.begin(), mvb.end(), 0.0);
-        for (int i = 0; i < n; i++) { nvb[(size_t)NV_G * n + i] = g[(size_t)k * n + i]; nvb[(size_t)NV_X0 * n + i] = x0 ? x0[(size_t)k * n + i] : 0.0; }
-        const int rc = pack_row_bounds(d, h->loaded, first, k, lbA, ubA, lbL, ubL, lbR, ubR, &mvb[(size_t)MV_L * m], &mvb[(size_t)MV_U * m], lb.data(), rb.data());
-        if (rc) return rc;
-        if (y0) for (int r = 0; r < m; r++) mvb[(size_t)MV_Y0 * m + r] = y0[(size_t)k * m + r];
-        SpInfo info; memset(&info, 0, sizeof(info)); info.hasY0 = y0 ? 1 : 0;
-        double dmin = INFINITY, dmax = 0.0;
-        for (int i = 0; i < n; i++) { const double q = h->qdiagHost[i] >= 0 ? Qx[(size_t)k * d.nnzQ + h->qdiagHost[i]] : 0.0; dmin = std::min(dmin, q); dmax = std::max(dmax, std::fabs(q)); }
-        h->diagRatio[b] = (dmax > 0.0 && dmin > 0.0) ? dmin / dmax : 0.0;
-        HIPCHK(g_sp_err, hipMemcpy(d.Qx + b * d.nnzQ, Qx + (size_t)k * d.nnzQ, sizeof(double) * d.nnzQ, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(d.Ex + b * d.nnzE, ex.data(), sizeof(double) * d.nnzE, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(d.nv + b * NV_NUM * n, nvb.data(), sizeof(double) * nvb.size(), hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(d.mv + b * MV_NUM * m, mvb.data(), sizeof(double) * mvb.size(), hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(d.lbL + b * nK, lb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(d.lbR + b * nK, rb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(d.info + b, &info, sizeof(info), hipMemcpyHostToDevice));
-        h->rs.filled[b] = 1;
-    }
-    h->loaded = true;
-    sp_choose_ordering(h);
-    return 0;
-}); }
-
-/* -DLCQP_SCHED_PROFILE builds: per phase (rows 0 .. PH_NUM-1: start, round, trial, factor, correct, qp end; row PH_NUM: polls without work) the clock
- * ticks (100 MHz), wavefront steps and instances served, summed over the wavefronts of all runs since the handle was created: 3 (PH_NUM + 1) values */
-extern "C" int lcqp_hip_sparse_sched_profile(lcqp_hip_sparse_t* h, unsigned long long* out)
-{ return guarded(g_sp_err, [&] {
-    if (!h || !out) return LCQP_INVALID_ARGUMENT;
-    if (int rc = synchronize(g_sp_err, h)) return rc;
-    HIPCHK(g_sp_err, hipMemcpy(out, h->db.qprof, sizeof(unsigned long long) * 3 * (PH_NUM + 1), hipMemcpyDeviceToHost));
-    return 0;
-}); }
-
-// the launches of a run or a re-solve on the handle's stream: the setup (or the refresh) from ev0 to ev1, the homotopy from ev1 to ev2
-static int sp_run(lcqp_hip_sparse* h, bool refresh, int mode, const double* rho0)
-{
-    h->rs.invalidate();
-    HIPCHK(g_sp_err, hipEventRecord(h->ev0, h->stream));
-    switch (h->db.G) {
-        case 8: sp_launch<8>(h->db, h->stream, h->ev1, refresh, mode, rho0); break;
-        case 16: sp_launch<16>(h->db, h->stream, h->ev1, refresh, mode, rho0); break;
-        case 32: sp_launch<32>(h->db, h->stream, h->ev1, refresh, mode, rho0); break;
-        default: sp_launch<64>(h->db, h->stream, h->ev1, refresh, mode, rho0); break;
-    }
-    if (!refresh) h->rs.nSetups++;
-    h->rs.nLaunches++;
-    HIPCHK(g_sp_err, hipGetLastError());
-    HIPCHK(g_sp_err, hipEventRecord(h->ev2, h->stream));
-    h->ran = h->rs.setupValid = h->rs.solved = true;
-    return 0;
-}
-
-extern "C" int lcqp_hip_sparse_run(lcqp_hip_sparse_t* h)
-{ return guarded(g_sp_err, [&] {
-    if (!h || !h->loaded) return LCQP_LCQPOBJECT_NOT_SETUP;
-    HIPCHK(g_sp_err, hipSetDevice(h->device));
-    sp_choose_ordering(h);
-    return sp_run(h, false, 0, nullptr);
-}); }
-
-// New vectors for instances [first, first + count) of a batch that holds problems: the argument list of lcqp_hip_sparse_load without the
-// values of the matrices, the same packing, the same meaning of NULL.  The whole range is checked before anything is written, and only
-// NV_G, NV_X0, MV_L, MV_U, MV_Y0, lbL, lbR and hasY0 of those instances are written: the stored solution, the statuses and the factors stay.
-extern "C" int lcqp_hip_sparse_update(lcqp_hip_sparse_t* h, int first, int count, const double* g,
-                                      const double* lbA, const double* ubA, const double* lbL, const double* ubL,
-                                      const double* lbR, const double* ubR, const double* x0, const double* y0)
-{ return guarded(g_sp_err, [&] {
-    if (int rc = check_update(g_sp_err, h, first, count, g, lbL, lbR)) return rc;
-    SpBatch& d = h->db;
-    const int n = d.n, m = d.m, nK = d.nComp;
-    HIPCHK(g_sp_err, hipSetDevice(h->device));
-    HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));      // a run in flight reads what is written below
-    static_assert(MV_U == MV_L + 1, "l and u go over in one copy");
-    std::vector<double> lu((size_t)2 * m), lb(nK), rb(nK), x0z(x0 ? 0 : n, 0.0);
-    const int hasY0 = y0 ? 1 : 0;
-    for (int k = 0; k < count; k++) {
-        const size_t b = (size_t)first + k;
-        fill_row_bounds(d, k, lbA, ubA, lbL, ubL, lbR, ubR, lu.data(), lu.data() + m, lb.data(), rb.data());
-        d.hasLbL |= lbL ? 1 : 0; d.hasLbR |= lbR ? 1 : 0;      // switched on, never off (an absent vector is the zero vector)
-        double* nvb = d.nv + b * NV_NUM * n;
-        double* mvb = d.mv + b * MV_NUM * m;
-        HIPCHK(g_sp_err, hipMemcpy(nvb + (size_t)NV_G * n, g + (size_t)k * n, sizeof(double) * n, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(nvb + (size_t)NV_X0 * n, x0 ? x0 + (size_t)k * n : x0z.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(mvb + (size_t)MV_L * m, lu.data(), sizeof(double) * 2 * m, hipMemcpyHostToDevice));
-        if (y0) HIPCHK(g_sp_err, hipMemcpy(mvb + (size_t)MV_Y0 * m, y0 + (size_t)k * m, sizeof(double) * m, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(d.lbL + b * nK, lb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(d.lbR + b * nK, rb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(&d.info[b].hasY0, &hasY0, sizeof(int), hipMemcpyHostToDevice));
-    }
-    return 0;
-}); }
-
-// Solve again on the setup in place: k_sparse_refresh where a run has k_sparse_setup, then the homotopy launch.  Without a setup that
-// belongs to the matrices and options in place this is lcqp_hip_sparse_run.
-extern "C" int lcqp_hip_sparse_resolve(lcqp_hip_sparse_t* h, int mode, const double* rho0)
-{ return guarded(g_sp_err, [&] {
-    if (int rc = check_resolve(g_sp_err, h, mode, rho0, h && h->loaded)) return rc == RESOLVE_RUNS ? lcqp_hip_sparse_run(h) : rc;
-    const int B = h->db.B;
-    HIPCHK(g_sp_err, hipSetDevice(h->device));
-    const bool withRho = mode == 1 && rho0;
-    if (withRho) {
-        if (!h->rs.rhoStart && !h->mem.alloc(g_sp_err, h->rs.rhoStart, (size_t)B)) { g_sp_err = "device allocation failed: " + g_sp_err; return LCQP_HIP_ERROR; }
-        HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));      // the zero-fill of a fresh buffer, a run in flight that reads an older one
-        HIPCHK(g_sp_err, hipMemcpy(h->rs.rhoStart, rho0, sizeof(double) * (size_t)B, hipMemcpyHostToDevice));
-    }
-    return sp_run(h, true, mode, withRho ? h->rs.rhoStart : nullptr);
-}); }
-
-extern "C" int lcqp_hip_sparse_launch_counts(lcqp_hip_sparse_t* h, int out[2])
-{
-    return launch_counts(h, out);
-}
-
-// ---- solution sensitivities (DESIGN.md section 3a''): one launch of k_sparse_sensitivity on the handle's stream, host buffers in and out ----
+// one launch of k_sparse_sensitivity<G> (DESIGN.md section 3a'') on device buffers
 template <int G>
-static void sp_launch_sensitivity(const lcqp_hip_sparse* h, int nrhs)
+static void sp_launch_sensitivity(const SpBatch& db, hipStream_t stream, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo)
 {
-    const SpBatch& db = h->db;
     const int ipw = 64 / G, grid = (db.B + ipw - 1) / ipw;
     const size_t ldsBytes = (G == 64 && db.general) ? sizeof(double) * (size_t)(G * G + 16 * G) : 0;      // the window of the general solve
-    hipLaunchKernelGGL(k_sparse_sensitivity<G>, dim3(grid), dim3(WGS), ldsBytes, h->stream, db, nrhs, h->sens.v, h->sens.dg, h->sens.db, h->sens.side, h->sens.info);
+    hipLaunchKernelGGL(k_sparse_sensitivity<G>, dim3(grid), dim3(WGS), ldsBytes, stream, db, nrhs, v, dg, dbo, side, sinfo);
 }
 
-extern "C" int lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
-{ return guarded(g_sp_err, [&] {
-    if (!h || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
-    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    SpBatch& d = h->db;
-    SensBuffers& sb = h->sens;
-    HIPCHK(g_sp_err, hipSetDevice(h->device));
-    if (int rc = sb.reserve(g_sp_err, h->mem, h->stream, d.B, nrhs, d.n, d.n, d.m, d.m)) return rc;
-    if (int rc = sb.upload(g_sp_err, v)) return rc;
-    HIPCHK(g_sp_err, hipEventRecord(sb.ev0, h->stream));
-    switch (d.G) {
-        case 8: sp_launch_sensitivity<8>(h, nrhs); break;
-        case 16: sp_launch_sensitivity<16>(h, nrhs); break;
-        case 32: sp_launch_sensitivity<32>(h, nrhs); break;
-        default: sp_launch_sensitivity<64>(h, nrhs); break;
-    }
-    HIPCHK(g_sp_err, hipGetLastError());
-    HIPCHK(g_sp_err, hipEventRecord(sb.ev1, h->stream));
-    return sb.download(g_sp_err, dg, db, side, info, d.n, d.m);
-}); }
+}  // namespace
 
-extern "C" int lcqp_hip_sparse_sensitivity_timing(lcqp_hip_sparse_t* h, float* kernel_ms)
-{
-    return guarded(g_sp_err, [&] { return sensitivity_timing(g_sp_err, h, kernel_ms); });
+// the two launch functions of this unit's width (lcqp_sparse_launch.hpp)
+namespace lcqp_sparse {
+void LCQP_CAT(lcqp_sparse_launch_, LCQP_TU_G)(const SpBatch& db, hipStream_t stream, hipEvent_t mid, bool refresh, int mode, const double* rho0)
+{ sp_launch<LCQP_TU_G>(db, stream, mid, refresh, mode, rho0); }
+void LCQP_CAT(lcqp_sparse_sensitivity_, LCQP_TU_G)(const SpBatch& db, hipStream_t stream, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo)
+{ sp_launch_sensitivity<LCQP_TU_G>(db, stream, nrhs, v, dg, dbo, side, sinfo); }
 }
-
-extern "C" int lcqp_hip_sparse_synchronize(lcqp_hip_sparse_t* h)
-{
-    return guarded(g_sp_err, [&] { return synchronize(g_sp_err, h); });
-}
-
-extern "C" int lcqp_hip_sparse_last_timing(lcqp_hip_sparse_t* h, float* setup_ms, float* solve_ms)
-{
-    return guarded(g_sp_err, [&] { return last_timing(g_sp_err, h, setup_ms, solve_ms); });
-}
-
-extern "C" int lcqp_hip_sparse_get_solution(lcqp_hip_sparse_t* h, double* x, double* y, lcqp_stats_t* stats)
-{
-    return guarded(g_sp_err, [&] { return get_solution(g_sp_err, h, h ? h->db.m : 0, x, y, stats); });
-}
-
-// -DLCQP_PROFILE builds (tools/gpu.py sparse_profile): mean clock ticks per instance and phase of the last run
-// (products, assembly, factorisation, forward sweeps, backward sweeps, vector operations, LCQP level, -)
-extern "C" int lcqp_hip_sparse_read_profile(lcqp_hip_sparse_t* h, double* out)
-{ return guarded(g_sp_err, [&] {
-#ifdef LCQP_PROFILE
-    if (!h || !out) return LCQP_INVALID_ARGUMENT;
-    SpBatch& d = h->db;
-    if (int rc = synchronize(g_sp_err, h)) return rc;
-    std::vector<SpInfo> info(d.B);
-    HIPCHK(g_sp_err, hipMemcpy(info.data(), d.info, sizeof(SpInfo) * (size_t)d.B, hipMemcpyDeviceToHost));
-    for (int k = 0; k < 8; k++) { out[k] = 0.0; for (auto& i : info) out[k] += i.prof[k] / d.B; }
-    return 0;
-#else
-    (void)h; (void)out;
-    return LCQP_HIP_UNSUPPORTED;
-#endif
-}); }
-
-// algorithmic bytes of the last run (setup + homotopy), counted by the kernels: CSR values and indices of every sparse product,
-// band storage read and written by every assembly, factorisation and solve
-extern "C" double lcqp_hip_sparse_algorithmic_bytes(lcqp_hip_sparse_t* h)
-{ return guarded(g_sp_err, [&] {
-    if (!h) return 0.0;
-    SpBatch& d = h->db;
-    if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return 0.0;
-    std::vector<SpInfo> info(d.B);
-    if (hipMemcpy(info.data(), d.info, sizeof(SpInfo) * (size_t)d.B, hipMemcpyDeviceToHost) != hipSuccess) return 0.0;
-    double tot = 0.0;
-    for (auto& i : info) tot += i.bytes;
-    return tot;
-}, 0.0); }

@@ -1,0 +1,134 @@
+// lcqp_sparse_launch.hpp -- the seam between the host translation unit of the sparse arm (lcqp_sparse_host.hip: the C ABI lcqp_hip_sparse_*)
+// and its kernel translation units (lcqp_sparse.hip, one per lane-group width G in {8,16,32,64}): the batch as the kernels see it, the
+// constants both sides index it with, and the launch functions.  Plain structs and declarations only: no device code lives here.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "../../include/lcqp_hip.h"
+
+namespace lcqp_sparse {
+// nothing of the seam enters the dynamic symbol table of the library: not the launch functions, and not what the host runtime's templates
+// (lcqp_host_rt.hpp) become when they are instantiated over these structs
+#pragma GCC visibility push(hidden)
+
+enum { NV_G, NV_GTIL, NV_GPHI, NV_XK, NV_PK, NV_XNEW, NV_GK, NV_QX, NV_CX, NV_QP, NV_CP, NV_TMP, NV_XQ, NV_XA, NV_XT, NV_R1,
+       NV_X0, NV_NUM };
+enum { MV_L, MV_U, MV_RHOV, MV_YQ, MV_YA, MV_ZA, MV_YT, MV_EX, MV_YK, MV_Y0, MV_LX, MV_LX2, MV_NUM };
+enum { MI_ST, MI_STT, MI_STF, MI_NEW, MI_NUM };
+
+struct SpInfo {
+    int haveSolution, stfValid, hasY0, bigReg;     // bigReg: this instance needs the safe regularisation of the polish (a Hessian that is only semidefinite)
+    int warm, pad0;                                // warm (k_sparse_refresh): sp_ph_start begins at the last solution, at the penalty rho0, without the zero-penalty QP
+    double rho0;
+    double scale, sigma, delta, delta2, phiConst;
+    double deltaS, delta2S;                        // the light level tried first (sp_polish)
+    double e1max;                                  // largest row 1-norm of E: with |x|_inf the scale of the rounding of a computed E_r x (the active-row test of the polish)
+    double hist[64];
+    double bytes;        // algorithmic bytes counted by the kernel
+    double prof[8];      // -DLCQP_PROFILE: clock ticks per phase (SP_* below)
+};
+enum { SP_PRODUCTS, SP_ASSEMBLE, SP_FACTOR, SP_FORWARD, SP_BACKWARD, SP_VECTORS, SP_LCQP, SP_RHS, SP_NPHASE };
+
+// ---- the homotopy as a phase machine (round 4) ----------------------------------------------------------------------------------------
+// Round 3 ran the whole homotopy of an instance inside one persistent lane group: the 64 / G instances of a wavefront moved in lock step, an
+// instance was active in 74 % of its wavefront's trials and refactorised in 26 % of them while its wavefront did in 83 %.  Now an instance is
+// a record in memory (SpState + its vectors) that moves through QUEUES, one per phase; a wavefront pops up to 64 / G instances that are in
+// the SAME phase, runs that phase for them, and pushes each to the queue of its next phase (k_sparse_sched).  A wavefront therefore only
+// ever holds instances doing the same thing; nobody waits for a neighbour's factorisation or for the slowest polish of eight.
+enum { PH_START, PH_ROUND, PH_TRIAL, PH_FACTOR, PH_CORRECT, PH_QPEND, PH_NUM };
+enum { BY_ASSEMBLE, BY_FACTOR_LDS, BY_FACTOR, BY_SOLVE, BY_BORDER_PREPARE, BY_BORDER_SOLVE, BY_EX, BY_SWEEP, BY_START, BY_E, BY_NUM };
+struct SpState {
+    // LCQProblem::runSolver (src/LCQProblem.cpp:444-560)
+    int initial, histLen, algoStat, totalIter, rc, qpIter;
+    double alphak, rho, gmaxNext;
+    unsigned long long perturbCounter;
+    lcqp_stats_t st;
+    // the subsolver call (oracle: sqp_solve)
+    int round, n_admm, use_stored, backup_pending, admm_ready, trials0, admm0;
+    // the polish (oracle: sqp_polish)
+    int trial, reuse, fact_valid, borderTodo, nrefine;      // nrefine: refinement corrections taken for the active rows alone
+    double gs, ytol, dpUsed, d2Used, xinf;                  // xinf: |x|_inf behind the last correction
+    // work counters
+    int cAdmm, cTrials, cFact, cCorr, cSweeps;
+    double bytes;
+};
+// Queues: the batch is cut into pools of `poolSize` consecutive instances (a power of two; the byte offset of an instance inside its pool fits
+// 32 bits for every per-instance array: the saddr + 32-bit offset addressing of SpCtx::arr); wavefront w serves pool w % nPools.  Per pool
+// and phase a ring of poolSize entries (an instance is in at most one queue) and three counters: tail (next position to write), head (next
+// position to read), count (entries published); every ring slot carries a SEQUENCE number beside the instance id (a bounded multi-producer /
+// multi-consumer queue after Vyukov; sequence and id share one 64-bit word, written by one store): slot p & mask is free for position p when
+// its sequence is p, holds position p's entry when it is p + 1, and is handed on to position p + poolSize by its consumer -- a producer that laps the ring onto a slot whose entry has been claimed but not
+// read yet waits instead of overwriting it.  ctl[pool][PH_NUM] = instances of the pool not finished yet.
+constexpr int QCTL = 4;      // ints per (pool, phase): tail, head, count, pad
+
+struct EllMat { const int *eidx, *epos, *ptr, *cidx, *cmap; int rows, W, tails; };   // see g_ell
+
+struct SpBatch {
+    int B, n, m, nC, nComp, N, Np, w, ld, nnzQ, nnzE, G;  // Np: N rounded up to a multiple of 64 (padding rows: zero coefficients)
+    int hasLbL, hasLbR;
+    lcqp_options_t opt;
+    const int *Qp, *Qi, *Ep, *Ei, *ETp, *ETi, *ETmap, *iperm, *bandQ, *bandE;
+    const int *bsrc, *pnode, *qdiag, *Erow;   // band entry -> value it comes from (sp_factor_reg), node of a band position, Q_ii, row of an E entry
+    const int *bgate, *bdiag;                 // band entry -> the row of E whose membership in the working set gates it (-1: none); band position -> its diagonal (sp_factor_reg)
+    EllMat ellQ, ellE, ellT; // rows of Q, rows of E, columns of E in ELL slabs
+    double *Qx, *Ex;         // [B][nnzQ], [B][nnzE] (CSR order)
+    double *Kb;              // [B][N*ld] assembled band rows (input of a factorisation): Kb[i*ld + k] = K[i][i-w+k]
+    double *KaF, *KaD;       // ADMM KKT factor in the folded layout of band_sweep [B][Np*G], 1/D [B][Np]
+    double *KpF, *KpD;       // polish KKT factor
+    double* K0;              // [Np][G] per instance: the band rows of [Q, E'; E, .] with every row of E in, diagonal slot Q_ii (variables) -- what sp_factor_reg streams
+    int bitWords;            // 32-bit words of a working set's bit set in LDS (sp_ph_factor), 0: it does not fit, the flags are read from memory
+    double *nv, *mv, *Nv;    // [B][NV_NUM][n], [B][MV_NUM][m], [B][2][Np]
+    // Bordered band (round 3): the last kb positions of the ordering are border nodes -- rows or variables too dense for any band (the
+    // coupling constraint and the two shared variables of examples/OptimizeOnCircle.cpp).  K = [Bd U'; U C]: the band engine factorises
+    // Bd with the border positions as isolated unit pivots; the border is carried by W = U inv(Bd) (kb band solves per factorisation) and
+    // the Schur complement S = C - W U' (kb x kb, dense LDL').  U: per border node the entries it shares with band nodes (Upos: band
+    // position, Usrc: entry of Q (k < nnzQ) or of E (nnzQ + k, CSR order), Ugate: the row of E whose membership in the working set gates
+    // the entry, -1 none); C: the entries among border nodes, lower triangle (Cb2: the other border node).
+    int kb, nU, nCb;
+    int lightOK;     // the ordering puts every row behind one of its variables and every Hessian of the batch is safely definite: the polish tries its light regularisation first
+    const int *bnode, *Uptr, *Upos, *Usrc, *Ugate, *Cptr, *Cb2, *Csrc, *Cgate;
+    double *bW, *bUv, *bS;   // [B][2][kb][Np] W rows, [B][2][nU] gated values of U, [B][2][kb][kb] factor of S   (index 0: polish, 1: ADMM)
+    double *lbL, *lbR;       // [B][nComp]
+    int* mi;                 // [B][MI_NUM][m]
+    SpInfo* info;
+    lcqp_stats_t* stats;
+    double *xout, *yout;     // [B][n], [B][m]
+    // per-iterate tracking (options.storeSteps, src/LCQProblem.cpp:1365-1378), as on the dense path: [B][traceCap][8] = (|statk|inf, phi, rho,
+    // alphak, obj, merit, |pk|inf, QP iterations), [B][traceCap][n] = xk, traceLen[B]; traceCap == 0: not allocated
+    double *traceS, *traceX;
+    int* traceLen;
+    int traceCap;
+    // phase machine
+    SpState* state;          // [B]
+    unsigned long long* qring;  // [nPools][PH_NUM][poolSize] ring slots: (sequence number << 32) | instance id, one 64-bit word so that a slot changes hands in one store
+    int* qctl;                  // [nPools][PH_NUM + 1][QCTL]
+    int poolSize, nPools;
+    int wideDiv;                // SIMDs of the device per pool (sp_launch): unfinished instances of the pool / wideDiv = instances of a streaming step
+    // General sparse LDL' (round 6; lcqp_sparse_general.hpp): patterns that are neither banded nor bordered -- multifrontal over a nested-
+    // dissection tree with dense fronts, one wavefront per instance (G = 64).  general != 0: KaF / KpF hold the panels of the fronts
+    // (gLsize doubles per instance instead of Np * G), KaD / KpD 1 / D per position as for the band; kb = 0, lightOK = 0.
+    int general, gnF, gMaxFront;
+    unsigned gLsize, gStackSize;
+    const int *gPiv0, *gNp, *gNb, *gRowPtr, *gRows, *gChildPtr, *gChild, *gRel, *gAsmPtr, *gAsmSrc, *gAsmGate, *gAsmPos;
+    const unsigned *gLoff, *gCBoff;
+    const int *gMeta, *gChildInfo;   // [gnF][GEN_META] np, nb, piv0, rowPtr, asmPtr, asmEnd, childPtr, childEnd, Loff, CBoff: one load per front; [children][4] nb, CBoff, rowPtr of the child
+    double *gStack, *gFront;     // [B][gStackSize] update blocks of the fronts, [B][gMaxFront^2] a front too large for LDS
+    size_t kfStride;             // doubles per instance of KaF / KpF
+    // algorithmic bytes of one event of each kind (filled by the host: formed in the kernel they are loop invariants the compiler keeps in
+    // registers across every phase)
+    double by[BY_NUM];
+    unsigned long long* qprof;   // [PH_NUM + 1][3] (-DLCQP_SCHED_PROFILE): clock ticks, wavefront steps, instances served per phase; row PH_NUM: ticks / polls without work
+};
+
+constexpr int GEN_META = 12;      // ints per front of SpBatch::gMeta
+
+// The launch functions, defined in lcqp_sparse.hip for G = LCQP_TU_G.
+// SpRunFn: the launches of a run on `stream` -- k_sparse_setup<G>, or with `refresh` k_sparse_refresh<G>(mode, rho0) in its place, `mid`
+// recorded behind it, then the homotopy (k_sparse_sched_init, k_sparse_sched<G>).
+// SpSensitivityFn: one launch of k_sparse_sensitivity<G> on `stream` over device buffers (layouts at the kernel).
+using SpRunFn = void(const SpBatch& db, hipStream_t stream, hipEvent_t mid, bool refresh, int mode, const double* rho0);
+using SpSensitivityFn = void(const SpBatch& db, hipStream_t stream, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo);
+SpRunFn lcqp_sparse_launch_8, lcqp_sparse_launch_16, lcqp_sparse_launch_32, lcqp_sparse_launch_64;
+SpSensitivityFn lcqp_sparse_sensitivity_8, lcqp_sparse_sensitivity_16, lcqp_sparse_sensitivity_32, lcqp_sparse_sensitivity_64;
+#pragma GCC visibility pop
+
+}  // namespace lcqp_sparse

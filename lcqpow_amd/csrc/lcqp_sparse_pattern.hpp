@@ -1,4 +1,4 @@
-// lcqp_sparse_pattern.hpp -- the pattern analysis of the sparse arm: everything lcqp_hip_sparse_create (lcqp_sparse.hip) derives from the CSC
+// lcqp_sparse_pattern.hpp -- the pattern analysis of the sparse arm: everything lcqp_hip_sparse_create (lcqp_sparse_host.hip) derives from the CSC
 // patterns of Q and of the stacked [A; L; R] before it touches a device -- checks, CSR form, the orderings of the KKT matrix and the choice
 // between band, bordered band and general LDL', the band maps of each ordering, the border lists, the ELL slabs of the gathers.  Host only,
 // once per pattern; no HIP in this file (CPU checks: tests/cpp/sparse_pattern_test.cpp).
