@@ -20,13 +20,6 @@ using namespace lcqp_rt;
 // =================================================================================================
 // device kernels: the per-size ones live in lcqp_kernels.hpp / lcqp_nch.hip; here only the two that are not templated
 // =================================================================================================
-#define LCQP_LDS_N(NCHV)                                    \
-    __shared__ double sh_arena[arena_doubles(NCHV)];        \
-    __shared__ double sh_red[16];                           \
-    __shared__ int sh_ired[16];                             \
-    Lds lds{sh_arena, sh_red, sh_ired};
-#define LCQP_LDS LCQP_LDS_N(4)
-
 __global__ __launch_bounds__(WG) void k_chol(int np, int nblk, int n, double* F, double* dscr, int* fail)
 {
     LCQP_LDS
@@ -123,72 +116,49 @@ struct lcqp_hip_batch {
     // E, hence of Et and M: an update must keep the set
     ResolveState rs;
     std::vector<char> boxed;              // [B][n]
-    SensBuffers sens;
-    SensBuffers sensBlk;                  // of k_sensitivity_blk (other leading dimensions, a varying number of instances)
+    SensBuffers sens;                     // of k_sensitivity
+    SensBuffers sensBlk;                  // of k_sensitivity_blk (another pitch of db, a varying number of instances)
     size_t jacStaging = LCQP_JACOBIAN_STAGING_BYTES;      // device bytes a Jacobian call may stage per chunk of instances
     int nch;
+    const SizeKernels* k = nullptr;       // the launch table of the padded size (dense_kernels), set by lcqp_hip_batch_create
     explicit lcqp_hip_batch(int dev) : db(), device(dev) {}
     ~lcqp_hip_batch() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
 };
 
-// -DLCQP_ONLY_NCH=k (experiment builds, tools/gpu_ab.py): link only the kernels of one padded size
 // padded size of a problem with n variables in units of 128: 1, 2, 3, 4, then 8 (np = 1024), 16 (np = 2048) and 32 (np = 4096)
 static inline int padded_nch(int n) { const int k = (n + 127) / 128; return k > 16 ? 32 : (k > 8 ? 16 : (k > 4 ? 8 : k)); }
 
-static void lcqp_dispatch(int nch, int kid, int grid, hipStream_t s, const LaunchArgs& a)
+// The launch table of a padded size (lcqp_launch.hpp), or null with a message: a size whose kernels this build does not link is an error,
+// never another size's kernels (their buffers have another pitch).  -DLCQP_ONLY_NCH=k (the profile library, experiment builds: tools/gpu_ab.py)
+// links the kernels of one padded size only.
+static const SizeKernels* dense_kernels(int nch)
 {
 #ifdef LCQP_ONLY_NCH
-    (void)nch;
-#define LCQP_CAT2(a, b) a##b
-#define LCQP_CAT(a, b) LCQP_CAT2(a, b)
-    LCQP_CAT(lcqp_launch_, LCQP_ONLY_NCH)(kid, grid, s, a);
+    static const SizeKernels* const sizes[] = {&size_kernels<LCQP_ONLY_NCH>()};
 #else
-    switch (nch) {
-        case 1: lcqp_launch_1(kid, grid, s, a); break;
-        case 2: lcqp_launch_2(kid, grid, s, a); break;
-        case 3: lcqp_launch_3(kid, grid, s, a); break;
-        case 4: lcqp_launch_4(kid, grid, s, a); break;
-        case 8: lcqp_launch_8(kid, grid, s, a); break;
-        case 16: lcqp_launch_16(kid, grid, s, a); break;
-        default: lcqp_launch_32(kid, grid, s, a); break;
-    }
+    static const SizeKernels* const sizes[] = {&size_kernels<1>(), &size_kernels<2>(), &size_kernels<3>(), &size_kernels<4>(),
+                                               &size_kernels<8>(), &size_kernels<16>(), &size_kernels<32>()};
 #endif
-}
-// the second build of the persistent kernels (256 registers): np <= 512 (36 KB of LDS per workgroup) and at most three workgroups per CU
-static bool lcqp_dispatch_few(int nch, int kid, int grid, hipStream_t s, const LaunchArgs& a)
-{
-#ifdef LCQP_ONLY_NCH
-#if LCQP_ONLY_NCH <= 4
-    (void)nch;
-    LCQP_CAT(lcqp_launch_few_, LCQP_ONLY_NCH)(kid, grid, s, a);
-    return true;
-#else
-    (void)nch; (void)kid; (void)grid; (void)s; (void)a;
-    return false;
-#endif
-#else
-    if (nch == 1) lcqp_launch_few_1(kid, grid, s, a);
-    else if (nch == 2) lcqp_launch_few_2(kid, grid, s, a);
-    else if (nch == 3) lcqp_launch_few_3(kid, grid, s, a);
-    else if (nch == 4) lcqp_launch_few_4(kid, grid, s, a);
-    else return false;
-    return true;
-#endif
+    for (const SizeKernels* k : sizes) if (k->nch == nch) return k;
+    g_err = "the dense kernels of the padded size " + std::to_string(128 * nch) + " are not part of this build of the library; it holds the padded sizes";
+    for (const SizeKernels* k : sizes) g_err += " " + std::to_string(128 * k->nch);
+    return nullptr;
 }
 
-static void dispatch_db(lcqp_hip_batch* h, int kid, int grid, const int* list = nullptr, int initial = 0, uint64_t seed0 = 0, uint64_t first = 0, hipStream_t on = nullptr)
+// The build of the two persistent kernels a launch of the batch takes: the second one (256 registers) for np <= 512 (36 KB of LDS per
+// workgroup) and at most three workgroups per CU, the standard one otherwise
+static const RunKernels& run_kernels(const lcqp_hip_batch* h)
 {
-    LaunchArgs a;
-    a.db = h->db; a.list = list; a.initial = initial; a.seed0 = seed0; a.first = first;
-    if ((kid == ID_k_lcqp_run || kid == ID_k_qp_solve) && h->nch <= 4 && h->db.B <= 3 * h->numCU && !h->overlapped
-        && lcqp_dispatch_few(h->nch, kid, grid, on ? on : h->stream, a)) return;
-    lcqp_dispatch(h->nch, kid, grid, on ? on : h->stream, a);
+    const bool few = h->nch <= 4 && h->db.B <= 3 * h->numCU && !h->overlapped && h->k->few;
+    return few ? *h->k->few : h->k->run;
 }
 
 extern "C" lcqp_hip_batch_t* lcqp_hip_batch_create(int batch, int nV, int nC, int nComp, int withBox, int device)
 { return guarded(g_err, [&]() -> lcqp_hip_batch_t* {
     if (batch <= 0 || nV <= 0 || nC < 0 || nComp < 0) { g_err = "invalid dimensions"; return nullptr; }
     if (nV > 4096) { g_err = "nV > 4096 is not supported by the dense kernels of this build (padded sizes 128 ... 4096; the sparse engine takes larger banded / bordered problems)"; return nullptr; }
+    const SizeKernels* kernels = dense_kernels(padded_nch(nV));
+    if (!kernels) return nullptr;
     if (hipError_t e = hipSetDevice(device)) { hip_fail(g_err, "hipSetDevice(device)", e); return nullptr; }
     std::unique_ptr<lcqp_hip_batch> h(new lcqp_hip_batch(device));
     for (hipError_t e : {h->stream.status, h->side.status, h->ev0.status, h->ev1.status, h->ev2.status, h->evFork.status, h->evJoin.status,
@@ -197,7 +167,8 @@ extern "C" lcqp_hip_batch_t* lcqp_hip_batch_create(int batch, int nV, int nC, in
     { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) h->numCU = cu; }
     DevBatch& d = h->db;
     d.B = batch; d.n = nV; d.nC = nC; d.nComp = nComp; d.mA = nC + 2 * nComp;
-    h->nch = padded_nch(nV);      // 512 < nV <= 1024 runs the np = 1024 instantiation; 1024 < nV <= 2048: np = 2048 (96 KiB of LDS, one workgroup per CU, one row in flight per wave)
+    h->k = kernels;
+    h->nch = kernels->nch;        // 512 < nV <= 1024 runs the np = 1024 instantiation; 1024 < nV <= 2048: np = 2048 (96 KiB of LDS, one workgroup per CU, one row in flight per wave)
     d.np = 128 * h->nch;
     d.nblk = d.np / 64;
     d.boxcap = withBox ? nV : 0;
@@ -363,8 +334,8 @@ extern "C" int lcqp_hip_batch_generate_synthetic(lcqp_hip_batch_t* h, uint64_t s
     d.hasLbL = d.hasLbR = 0; h->anyLoaded = true;
     h->rs.invalidate();
     std::fill(h->rs.filled.begin(), h->rs.filled.end(), 1); std::fill(h->boxed.begin(), h->boxed.end(), 0);      // no box bounds
-    dispatch_db(h, ID_k_synth_fill, d.B, nullptr, 0, seed0, firstInstance);
-    dispatch_db(h, ID_k_synth_Q, d.B * (d.nblk * (d.nblk + 1) / 2));
+    h->k->synth_fill(d, d.B, h->stream, seed0, firstInstance);
+    h->k->synth_Q(d, d.B * (d.nblk * (d.nblk + 1) / 2), h->stream);
     HIPCHK(g_err, hipGetLastError());
     return 0;
 }); }
@@ -401,12 +372,13 @@ extern "C" int lcqp_hip_batch_read_problem(lcqp_hip_batch_t* h, int b, double* Q
 static int launch_setup(lcqp_hip_batch* h)
 {
     const DevBatch& d = h->db;
+    const SizeKernels& k = *h->k;
     hipStream_t on = h->stream;
     h->rs.invalidate();
     h->rs.nSetups++;
     const int ntile = d.nblk * (d.nblk + 1) / 2;
     const int nrb = (d.mEcap + 63) / 64, nb = (d.mMld + 127) / 128, nmt = nb * (nb + 1);      // k_build_M: 128 x 64 tiles of the lower triangle
-    dispatch_db(h, ID_k_prepare, d.B);
+    k.prepare(d, d.B, on);
     // C and its compressed rows depend on L and R only, the chain L1 -> Et -> M on Q and E: two branches.  The short one goes to the side
     // stream and runs in the gaps of k_factor (one workgroup per instance, a life of dependent chains).  Measured alternatives, round 6
     // (profiles/round6/README.md): the side branch beside k_trsm, or beside k_trsm and k_build_M -- both 0.2 ms slower.
@@ -414,18 +386,20 @@ static int launch_setup(lcqp_hip_batch* h)
     if (fork) {
         HIPCHK(g_err, hipEventRecord(h->evFork, on));
         HIPCHK(g_err, hipStreamWaitEvent(h->side, h->evFork, 0));
-        dispatch_db(h, ID_k_build_C, d.B * ntile, nullptr, 0, 0, 0, h->side);
-        dispatch_db(h, ID_k_compress_C, d.B, nullptr, 0, 0, 0, h->side);
+        k.build_C(d, d.B * ntile, h->side);
+        k.compress_C(d, d.B, h->side);
         HIPCHK(g_err, hipEventRecord(h->evJoin, h->side));
     }
     // more than three workgroups per CU (np <= 256: 36 KB of LDS each): the instantiation held to 128 registers, so that four are resident and
     // the batch needs one round
-    dispatch_db(h, (h->nch <= 2 && d.B > 3 * h->numCU) ? ID_k_factor_full : ID_k_factor, d.B);
-    dispatch_db(h, h->overlapped ? ID_k_trsm_streamed : ID_k_trsm, d.B * nrb);
+    const BatchKernel factor = (h->nch <= 2 && d.B > 3 * h->numCU) ? k.factor_full : k.factor;
+    const BatchKernel trsm = h->overlapped ? k.trsm_streamed : k.trsm;
+    factor(d, d.B, on);
+    trsm(d, d.B * nrb, on);
     // the join sits in front of the last setup kernel, not behind it: an event recorded right after a stream wait carried a late time stamp
     // (the homotopy kernel appeared 2 ms shorter than rocprofv3 and the wall clock say), and the side branch has long finished by then
     if (fork) HIPCHK(g_err, hipStreamWaitEvent(on, h->evJoin, 0));
-    dispatch_db(h, ID_k_build_M, d.B * nmt);
+    k.build_M(d, d.B * nmt, on);
     HIPCHK(g_err, hipGetLastError());
     h->rs.setupValid = true;
     return 0;
@@ -457,7 +431,7 @@ extern "C" int lcqp_hip_batch_run(lcqp_hip_batch_t* h)
     int rc = launch_setup(h);   // the factorisations are part of runSolver's cost (initializeSolver :885)
     if (rc) return rc;
     HIPCHK(g_err, hipEventRecord(h->ev1, h->stream));
-    dispatch_db(h, ID_k_lcqp_run, h->db.B);
+    run_kernels(h).lcqp_run(h->db, h->db.B, h->stream);
     h->rs.nLaunches++;
     HIPCHK(g_err, hipGetLastError());
     HIPCHK(g_err, hipEventRecord(h->ev2, h->stream));
@@ -548,12 +522,10 @@ extern "C" int lcqp_hip_batch_resolve(lcqp_hip_batch_t* h, int mode, const doubl
         HIPCHK(g_err, hipEventRecord(h->stage[0].done, h->stream));
     }
     HIPCHK(g_err, hipEventRecord(h->ev0, h->stream));
-    LaunchArgs a;
-    a.db = h->db; a.mode = mode; a.rho0 = withRho ? h->rs.rhoStart : nullptr;
-    lcqp_dispatch(h->nch, ID_k_refresh, B, h->stream, a);
+    h->k->refresh(h->db, B, h->stream, mode, withRho ? h->rs.rhoStart : nullptr);
     HIPCHK(g_err, hipGetLastError());
     HIPCHK(g_err, hipEventRecord(h->ev1, h->stream));
-    dispatch_db(h, ID_k_lcqp_run, B);
+    run_kernels(h).lcqp_run(h->db, B, h->stream);
     h->rs.nLaunches++;
     HIPCHK(g_err, hipGetLastError());
     HIPCHK(g_err, hipEventRecord(h->ev2, h->stream));
@@ -677,68 +649,54 @@ extern "C" int lcqp_hip_batch_read_working_set(lcqp_hip_batch_t* h, int b, int d
     return rc;
 }); }
 
-// ---- solution sensitivities (DESIGN.md section 3a'): one launch of k_sensitivity on the batch stream, host buffers in and out ----
-static int batch_sensitivity(lcqp_hip_batch* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
+// ---- solution sensitivities (DESIGN.md sections 3a' and 3a'''): k_sensitivity on the whole batch, k_sensitivity_blk (np <= 512) on a range ----
+// One launch on the batch stream, host buffers in and out, its kernel time added to *ms.  blk: k_sensitivity_blk on the instances
+// [first, first + count), on buffers of its own (the two kernels fix different pitches of db); v == nullptr: unit vectors, nothing
+// uploaded.  Otherwise k_sensitivity, which has no instance offset: first = 0, count = B.
+static int sensitivity_launch(lcqp_hip_batch* h, bool blk, int first, int count, int nrhs, const double* v, double* dg, double* db, int* side, int* info, float* ms)
 {
     DevBatch& d = h->db;
-    SensBuffers& sb = h->sens;
+    SensBuffers& sb = blk ? h->sensBlk : h->sens;
     HIPCHK(g_err, hipSetDevice(h->device));
-    if (int rc = sb.reserve(g_err, h->mem, h->stream, d.B, nrhs, d.n, d.np, (size_t)d.nd + d.capS, d.nd)) return rc;
-    if (int rc = sb.upload(g_err, v)) return rc;
-    LaunchArgs a;
-    a.db = d; a.nrhs = nrhs; a.sensV = sb.v; a.sensDg = sb.dg; a.sensDb = sb.db; a.sensSide = sb.side; a.sensInfo = sb.info;
+    // (ldv is the same for a Jacobian and a blocked call so that the rows reserved by one serve the other: a Jacobian's rows carry an unused v)
+    if (int rc = sb.reserve(g_err, h->mem, h->stream, count, nrhs, d.n, d.np, (size_t)d.nd + (blk ? 2 : 1) * (size_t)d.capS, d.nd)) return rc;
+    if (v) if (int rc = sb.upload(g_err, v)) return rc;
+    const double* dv = v ? sb.v : nullptr;
     HIPCHK(g_err, hipEventRecord(sb.ev0, h->stream));
-    lcqp_dispatch(h->nch, ID_k_sensitivity, d.B, h->stream, a);
+    if (blk) h->k->sensitivity_blk(d, count, h->stream, first, nrhs, dv, sb.dg, sb.db, sb.side, sb.info);
+    else h->k->sensitivity(d, count, h->stream, nrhs, dv, sb.dg, sb.db, sb.side, sb.info);
     HIPCHK(g_err, hipGetLastError());
     HIPCHK(g_err, hipEventRecord(sb.ev1, h->stream));
-    return sb.download(g_err, dg, db, side, info, d.n, d.nd);
+    if (int rc = sb.download(g_err, dg, db, side, info, d.n, d.nd)) return rc;
+    float t = 0.f;
+    HIPCHK(g_err, hipEventElapsedTime(&t, sb.ev0, sb.ev1));
+    *ms += t;
+    return 0;
+}
+
+// blk: the blocked kernel where the padded size has one, the vector kernel and its bits above
+static int batch_sensitivity(lcqp_hip_batch* h, bool blk, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
+{
+    float ms = 0.f;
+    if (int rc = sensitivity_launch(h, blk && h->k->sensitivity_blk, 0, h->db.B, nrhs, v, dg, db, side, info, &ms)) return rc;
+    h->rs.sensMs = ms;
+    return 0;
 }
 
 extern "C" int lcqp_hip_batch_sensitivity(lcqp_hip_batch_t* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
 { return guarded(g_err, [&] {
     if (!h || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
     if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return batch_sensitivity(h, nrhs, v, dg, db, side, info);
+    return batch_sensitivity(h, false, nrhs, v, dg, db, side, info);
 }); }
-
-// ---- blocked sensitivities and Jacobians (DESIGN.md section 3a'''): k_sensitivity_blk for np <= 512, k_sensitivity above ----
-// one launch on instances [first, first + count) with the buffers reserved for them; v == nullptr: unit vectors, nothing uploaded
-static int blocked_launch(lcqp_hip_batch* h, int first, int count, int nrhs, const double* v, double* dg, double* db, int* side, int* info, float* ms)
-{
-    DevBatch& d = h->db;
-    SensBuffers& sb = h->sensBlk;
-    // (ldv is the same for both kinds of call so that the rows reserved by one serve the other: a Jacobian's rows carry an unused v)
-    if (int rc = sb.reserve_rows(g_err, h->mem, h->stream, count, nrhs, d.n, d.np, (size_t)d.nd + 2 * (size_t)d.capS, d.nd)) return rc;
-    if (v) if (int rc = sb.upload(g_err, v)) return rc;
-    LaunchArgs a;
-    a.db = d; a.sensFirst = first; a.nrhs = nrhs; a.sensV = v ? sb.v : nullptr; a.sensDg = sb.dg; a.sensDb = sb.db; a.sensSide = sb.side; a.sensInfo = sb.info;
-    HIPCHK(g_err, hipEventRecord(sb.ev0, h->stream));
-    lcqp_dispatch(h->nch, ID_k_sensitivity_blk, count, h->stream, a);
-    HIPCHK(g_err, hipGetLastError());
-    HIPCHK(g_err, hipEventRecord(sb.ev1, h->stream));
-    if (int rc = sb.download(g_err, dg, db, side, info, d.n, d.nd)) return rc;
-    HIPCHK(g_err, hipEventElapsedTime(ms, sb.ev0, sb.ev1));
-    return 0;
-}
-
-static int batch_sensitivity_blocked(lcqp_hip_batch* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
-{
-    if (h->nch > 4) return batch_sensitivity(h, nrhs, v, dg, db, side, info);      // a panel of np >= 1024 does not fit LDS: the vector kernel and its bits
-    HIPCHK(g_err, hipSetDevice(h->device));
-    float ms = 0.f;
-    if (int rc = blocked_launch(h, 0, h->db.B, nrhs, v, dg, db, side, info, &ms)) return rc;
-    h->sens.lastMs = ms;
-    return 0;
-}
 
 // Jg [count][n][n], Jb [count][n][nd] (or NULL), side [count][nd], info [count] of the instances [first, first + count)
 static int batch_jacobian(lcqp_hip_batch* h, int first, int count, double* Jg, double* Jb, int* side, int* info)
 {
     DevBatch& d = h->db;
-    HIPCHK(g_err, hipSetDevice(h->device));
     const size_t n = d.n, nd = d.nd;
     float total = 0.f;
-    if (h->nch <= 4) {
+    if (h->k->sensitivity_blk) {
         // chunks of instances whose staging (n rows of v, dg and db each) stays below the cap; one launch and one download per chunk
         const size_t perInst = sizeof(double) * n * (n + (size_t)d.np + nd + 2 * (size_t)d.capS);
         size_t chunk = h->jacStaging / perInst;
@@ -746,16 +704,14 @@ static int batch_jacobian(lcqp_hip_batch* h, int first, int count, double* Jg, d
         if (chunk > (size_t)d.B) chunk = d.B;
         for (size_t c0 = 0; c0 < (size_t)count; c0 += chunk) {
             const size_t cb = std::min(chunk, (size_t)count - c0);
-            float ms = 0.f;
-            if (int rc = blocked_launch(h, first + (int)c0, (int)cb, d.n, nullptr, Jg + c0 * n * n, Jb ? Jb + c0 * n * nd : nullptr,
-                                        side ? side + c0 * nd : nullptr, info ? info + c0 : nullptr, &ms)) return rc;
-            total += ms;
+            if (int rc = sensitivity_launch(h, true, first + (int)c0, (int)cb, d.n, nullptr, Jg + c0 * n * n, Jb ? Jb + c0 * n * nd : nullptr,
+                                            side ? side + c0 * nd : nullptr, info ? info + c0 : nullptr, &total)) return rc;
         }
-        h->sens.lastMs = total;
+        h->rs.sensMs = total;
         return 0;
     }
-    // np >= 1024: k_sensitivity on the whole batch with an uploaded identity, in chunks of unit vectors under the same cap.  The vector kernel
-    // has no instance offset: a sub-range costs the launches of the full batch of B (these sizes are the single-large-problem ones, B small).
+    // no blocked kernel (np >= 1024): k_sensitivity on the whole batch with an uploaded identity, in chunks of unit vectors under the same cap.  The
+    // vector kernel has no instance offset: a sub-range costs the launches of the full batch of B (these sizes are the single-large-problem ones, B small).
     const size_t B = d.B, perVec = sizeof(double) * B * (n + (size_t)d.np + nd + (size_t)d.capS);
     size_t m = h->jacStaging / perVec;
     if (m < 1) m = 1;
@@ -766,10 +722,7 @@ static int batch_jacobian(lcqp_hip_batch* h, int first, int count, double* Jg, d
         const size_t mk = std::min(m, n - k0);
         std::fill(vh.begin(), vh.end(), 0.0);
         for (size_t b = 0; b < B; b++) for (size_t j = 0; j < mk; j++) vh[(b * mk + j) * n + k0 + j] = 1.0;
-        if (int rc = batch_sensitivity(h, (int)mk, vh.data(), dgh.data(), Jb ? dbh.data() : nullptr, sideh.data(), infoh.data())) return rc;
-        float ms = 0.f;
-        HIPCHK(g_err, hipEventElapsedTime(&ms, h->sens.ev0, h->sens.ev1));
-        total += ms;
+        if (int rc = sensitivity_launch(h, false, 0, d.B, (int)mk, vh.data(), dgh.data(), Jb ? dbh.data() : nullptr, sideh.data(), infoh.data(), &total)) return rc;
         for (size_t i = 0; i < (size_t)count; i++) {
             const size_t b = first + i;
             memcpy(Jg + (i * n + k0) * n, dgh.data() + b * mk * n, sizeof(double) * mk * n);
@@ -778,7 +731,7 @@ static int batch_jacobian(lcqp_hip_batch* h, int first, int count, double* Jg, d
     }
     if (side) memcpy(side, sideh.data() + (size_t)first * nd, sizeof(int) * count * nd);
     if (info) memcpy(info, infoh.data() + first, sizeof(int) * count);
-    h->sens.lastMs = total;
+    h->rs.sensMs = total;
     return 0;
 }
 
@@ -786,7 +739,7 @@ extern "C" int lcqp_hip_batch_sensitivity_blocked(lcqp_hip_batch_t* h, int nrhs,
 { return guarded(g_err, [&] {
     if (!h || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
     if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return batch_sensitivity_blocked(h, nrhs, v, dg, db, side, info);
+    return batch_sensitivity(h, true, nrhs, v, dg, db, side, info);
 }); }
 
 extern "C" int lcqp_hip_batch_jacobian(lcqp_hip_batch_t* h, int first, int count, double* Jg, double* Jb, int* side, int* info)
@@ -805,7 +758,7 @@ extern "C" int lcqp_hip_batch_set_jacobian_staging(lcqp_hip_batch_t* h, size_t b
 
 extern "C" int lcqp_hip_batch_sensitivity_timing(lcqp_hip_batch_t* h, float* kernel_ms)
 {
-    return guarded(g_err, [&] { return sensitivity_timing(g_err, h, kernel_ms); });
+    return sensitivity_timing(h, kernel_ms);
 }
 
 // =================================================================================================
@@ -937,7 +890,7 @@ extern "C" int lcqp_hip_qp_solve(lcqp_hip_qp_t* q, int initialSolve, int* iterat
     if (hipMemcpyAsync(d.nv + (size_t)V_GK * d.np, gp.data(), sizeof(double) * d.np, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
         *exit_flag = -1; return LCQP_SUBPROBLEM_SOLVER_ERROR;
     }
-    dispatch_db(h, ID_k_qp_solve, 1, nullptr, initialSolve ? 1 : 0);
+    run_kernels(h).qp_solve(d, 1, h->stream, initialSolve ? 1 : 0);
     lcqp_stats_t st;
     if (hipStreamSynchronize(h->stream) != hipSuccess ||
         hipMemcpy(&st, d.stats, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) { *exit_flag = -1; return LCQP_SUBPROBLEM_SOLVER_ERROR; }
@@ -990,7 +943,7 @@ extern "C" int lcqp_hip_qp_sensitivity(lcqp_hip_qp_t* q, int nrhs, const double*
 { return guarded(g_err, [&] {
     if (!q || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
     if (!q->hb || !q->solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return batch_sensitivity(q->hb, nrhs, v, dg, db, side, info);
+    return batch_sensitivity(q->hb, false, nrhs, v, dg, db, side, info);
 }); }
 
 // the blocked twins on the batch of one (lcqp_hip_batch_sensitivity_blocked, lcqp_hip_batch_jacobian)
@@ -998,7 +951,7 @@ extern "C" int lcqp_hip_qp_sensitivity_blocked(lcqp_hip_qp_t* q, int nrhs, const
 { return guarded(g_err, [&] {
     if (!q || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
     if (!q->hb || !q->solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return batch_sensitivity_blocked(q->hb, nrhs, v, dg, db, side, info);
+    return batch_sensitivity(q->hb, true, nrhs, v, dg, db, side, info);
 }); }
 
 extern "C" int lcqp_hip_qp_jacobian(lcqp_hip_qp_t* q, double* Jg, double* Jb, int* side, int* info)
@@ -1053,7 +1006,9 @@ static int download_padded(double* dst, const double* src, int batch, int rows, 
 extern "C" int lcqp_hip_util_symv(int batch, int n, double alpha, const double* A, const double* bv, const double* cv, double* dv)
 { return guarded(g_err, [&] {
     if (n <= 0 || n > 4096 || batch <= 0) return LCQP_HIP_UNSUPPORTED;
-    const int nch = padded_nch(n), np = 128 * nch;
+    const SizeKernels* k = dense_kernels(padded_nch(n));
+    if (!k) return LCQP_HIP_UNSUPPORTED;
+    const int np = 128 * k->nch;
     DevMem tb;
     double *dA, *db_, *dc, *dd;
     if (!tb.alloc(g_err, dA, (size_t)batch * np * np) || !tb.alloc(g_err, db_, (size_t)batch * np) || !tb.alloc(g_err, dc, (size_t)batch * np) ||
@@ -1062,7 +1017,7 @@ extern "C" int lcqp_hip_util_symv(int batch, int n, double alpha, const double* 
     int rc = upload_padded(dA, A, batch, n, n, np, np); if (rc) return rc;
     rc = upload_padded(db_, bv, batch, 1, n, np, 1); if (rc) return rc;
     rc = upload_padded(dc, cv, batch, 1, n, np, 1); if (rc) return rc;
-    { LaunchArgs la; la.n = n; la.alpha = alpha; la.A = dA; la.b = db_; la.c = dc; la.d = dd; lcqp_dispatch(nch, ID_k_util_symv, batch, 0, la); }
+    k->util_symv(batch, 0, n, alpha, dA, db_, dc, dd);
     HIPCHK(g_err, hipDeviceSynchronize());
     return download_padded(dv, dd, batch, 1, n, np, 1);
 }); }
@@ -1070,7 +1025,9 @@ extern "C" int lcqp_hip_util_symv(int batch, int n, double alpha, const double* 
 static int util_rows(int batch, int m, int n, const double* A, const double* x, double* dots, const double* coef, double* outT)
 {
     if (n <= 0 || n > 4096 || batch <= 0 || m <= 0) return LCQP_HIP_UNSUPPORTED;
-    const int nch = padded_nch(n), np = 128 * nch;
+    const SizeKernels* k = dense_kernels(padded_nch(n));
+    if (!k) return LCQP_HIP_UNSUPPORTED;
+    const int np = 128 * k->nch;
     DevMem tb;
     double *dA, *dx = nullptr, *dd = nullptr, *dcf = nullptr, *dout = nullptr;
     if (!tb.alloc(g_err, dA, (size_t)batch * m * np) || (x && !tb.alloc(g_err, dx, (size_t)batch * np)) || (dots && !tb.alloc(g_err, dd, (size_t)batch * m)) ||
@@ -1078,7 +1035,7 @@ static int util_rows(int batch, int m, int n, const double* A, const double* x, 
         return LCQP_HIP_ERROR;
     int rc = upload_padded(dA, A, batch, m, n, np, m); if (rc) return rc;
     if (x) { rc = upload_padded(dx, x, batch, 1, n, np, 1); if (rc) return rc; }
-    { LaunchArgs la; la.m = m; la.A = dA; la.x = dx; la.dots = dd; la.coef = dcf; la.outT = dout; lcqp_dispatch(nch, ID_k_util_rows, batch, 0, la); }
+    k->util_rows(batch, 0, m, dA, dx, dd, dcf, dout);
     HIPCHK(g_err, hipDeviceSynchronize());
     if (dots) HIPCHK(g_err, hipMemcpy(dots, dd, sizeof(double) * (size_t)batch * m, hipMemcpyDeviceToHost));
     if (outT) return download_padded(outT, dout, batch, 1, n, np, 1);
@@ -1089,7 +1046,9 @@ extern "C" int lcqp_hip_util_rows_list(int batch, int m, int n, const double* A,
                                        double* dots, double* outT)
 { return guarded(g_err, [&] {
     if (n <= 0 || n > 4096 || batch <= 0 || m <= 0 || nlist < 0 || nlist > m || !list) return LCQP_HIP_UNSUPPORTED;
-    const int nch = padded_nch(n), np = 128 * nch;
+    const SizeKernels* k = dense_kernels(padded_nch(n));
+    if (!k) return LCQP_HIP_UNSUPPORTED;
+    const int np = 128 * k->nch;
     DevMem tb;
     double *dA, *dx = nullptr, *dd = nullptr, *dcf = nullptr, *dout = nullptr;
     int* dl;
@@ -1100,7 +1059,7 @@ extern "C" int lcqp_hip_util_rows_list(int batch, int m, int n, const double* A,
         return LCQP_HIP_ERROR;
     int rc = upload_padded(dA, A, batch, m, n, np, m); if (rc) return rc;
     if (x) { rc = upload_padded(dx, x, batch, 1, n, np, 1); if (rc) return rc; }
-    { LaunchArgs la; la.m = m; la.n = nlist; la.A = dA; la.list = dl; la.x = dx; la.dots = dd; la.coef = dcf; la.outT = dout; lcqp_dispatch(nch, ID_k_util_rows_list, batch, 0, la); }
+    k->util_rows_list(batch, 0, m, nlist, dA, dl, dx, dd, dcf, dout);
     HIPCHK(g_err, hipDeviceSynchronize());
     if (dots) HIPCHK(g_err, hipMemcpy(dots, dd, sizeof(double) * (size_t)batch * m, hipMemcpyDeviceToHost));
     if (outT) return download_padded(outT, dout, batch, 1, n, np, 1);
@@ -1133,7 +1092,7 @@ extern "C" int lcqp_hip_util_symm_product(int batch, int m, int n, const double*
         }
     }
     if (!rc) {
-        dispatch_db(h, ID_k_build_C, d.B * (d.nblk * (d.nblk + 1) / 2));
+        h->k->build_C(d, d.B * (d.nblk * (d.nblk + 1) / 2), h->stream);
         if (hipStreamSynchronize(h->stream) != hipSuccess) rc = LCQP_HIP_ERROR;
     }
     if (!rc) rc = download_padded(C, d.C, batch, n, n, d.np, d.np);
@@ -1236,7 +1195,9 @@ __global__ void k_fill_random(double* p, size_t n, uint64_t seed)
 extern "C" int lcqp_hip_bench_rows(int batch, int m, int n, int mode, int repeat, float* ms)
 { return guarded(g_err, [&] {
     if (n <= 0 || n > 4096 || batch <= 0 || m <= 0) return LCQP_HIP_UNSUPPORTED;
-    const int nch = padded_nch(n), np = 128 * nch;
+    const SizeKernels* k = dense_kernels(padded_nch(n));
+    if (!k) return LCQP_HIP_UNSUPPORTED;
+    const int np = 128 * k->nch;
     DevMem tb;
     double *dA, *dx, *dd, *dcf, *dout;
     if (!tb.alloc(g_err, dA, (size_t)batch * m * np) || !tb.alloc(g_err, dx, (size_t)batch * np) || !tb.alloc(g_err, dd, (size_t)batch * m) ||
@@ -1245,11 +1206,8 @@ extern "C" int lcqp_hip_bench_rows(int batch, int m, int n, int mode, int repeat
     hipLaunchKernelGGL(k_fill_random, dim3(2048), dim3(256), 0, 0, dA, (size_t)batch * m * np, 1ULL);
     hipLaunchKernelGGL(k_fill_random, dim3(256), dim3(256), 0, 0, dx, (size_t)batch * np, 2ULL);
     hipLaunchKernelGGL(k_fill_random, dim3(256), dim3(256), 0, 0, dcf, (size_t)batch * m, 3ULL);
-    LaunchArgs la;
-    la.m = m; la.A = dA;
-    la.x = (mode & 1) ? dx : nullptr; la.dots = (mode & 1) ? dd : nullptr;
-    la.coef = (mode & 2) ? dcf : nullptr; la.outT = (mode & 2) ? dout : nullptr;
-    return time_launches(repeat, ms, [&] { lcqp_dispatch(nch, ID_k_util_rows, batch, 0, la); });
+    const bool dots = mode & 1, axpy = mode & 2;
+    return time_launches(repeat, ms, [&] { k->util_rows(batch, 0, m, dA, dots ? dx : nullptr, dots ? dd : nullptr, axpy ? dcf : nullptr, axpy ? dout : nullptr); });
 }); }
 
 extern "C" int lcqp_hip_chol_solve(int batch, int n, const double* K, const double* b, double* x, int repeat, float* ms)

@@ -183,6 +183,9 @@ struct ResolveState {
     std::vector<char> filled;             // [B]: the instance holds a problem
     double* rhoStart = nullptr;           // [B] on the device: starting penalties of a warm re-solve
     int nSetups = 0, nLaunches = 0;       // full setups and homotopy launches issued
+    // the kernel time of the last sensitivity call that returned its results, summed over its launches (ev0 -> ev1 of the SensBuffers each
+    // ran on: a vector call is one launch, a Jacobian one per chunk); < 0 before the first
+    float sensMs = -1.f;
     void invalidate() { setupValid = solved = false; }
 };
 
@@ -223,36 +226,19 @@ int launch_counts(H* h, int out[2])
     return 0;
 }
 
-// The device buffers of *_sensitivity for `rhs` right-hand sides per instance, grown on demand (layouts at k_sensitivity /
-// k_sparse_sensitivity), and the events around the last launch.  A call is reserve, upload, record(ev0), the arm's launch, record(ev1),
-// download.
+// The device buffers of *_sensitivity (layouts at k_sensitivity / k_sensitivity_blk / k_sparse_sensitivity), grown on demand, and the
+// events around the last launch.  A call is reserve, upload, record(ev0), the arm's launch, record(ev1), download.
 struct SensBuffers {
     double *v = nullptr, *dg = nullptr, *db = nullptr;
     int *side = nullptr, *info = nullptr;
-    int rhs = 0;
-    size_t capB = 0, capRows = 0;         // reserve_rows: instances and rows the buffers have room for
-    float lastMs = -1.f;                  // >= 0: the kernel time *_sensitivity_timing reports in place of ev0 -> ev1 (a launch on other buffers)
+    size_t capB = 0, capRows = 0;         // instances and rows the buffers have room for
     Event ev0, ev1;
     hipStream_t stream = nullptr;         // of the call in progress, with its sizes: rows = B * nrhs; leading dimensions in elements
     size_t B = 0, rows = 0, ldV = 0, ldDg = 0, ldDb = 0, nSide = 0;
 
-    int reserve(std::string& err, DevMem& mem, hipStream_t s, size_t nB, int nrhs, size_t ldv, size_t lddg, size_t lddb, size_t nside)
-    {
-        for (hipError_t e : {ev0.status, ev1.status}) if (e != hipSuccess) return hip_fail(err, "hipEventCreate", e);
-        stream = s; B = nB; rows = nB * nrhs; ldV = ldv; ldDg = lddg; ldDb = lddb; nSide = nside;
-        lastMs = -1.f;
-        if (nrhs <= rhs) return 0;
-        HIPCHK(err, hipStreamSynchronize(s));
-        for (const void* p : {(const void*)v, (const void*)dg, (const void*)db, (const void*)side, (const void*)info}) mem.release(p);
-        v = dg = db = nullptr; side = info = nullptr; rhs = 0;
-        if (!mem.alloc(err, v, rows * ldV) || !mem.alloc(err, dg, rows * ldDg) || !mem.alloc(err, db, rows * ldDb) ||
-            !mem.alloc(err, side, B * nSide) || !mem.alloc(err, info, B)) return LCQP_HIP_ERROR;
-        rhs = nrhs;
-        return 0;
-    }
-    // the same for calls whose number of instances varies (the blocked kernel's buffers: a Jacobian works on a chunk of the batch, with one
-    // right-hand side per variable): room for nB instances and nB * nrhs rows, grown when either is exceeded
-    int reserve_rows(std::string& err, DevMem& mem, hipStream_t s, size_t nB, size_t nrhs, size_t ldv, size_t lddg, size_t lddb, size_t nside)
+    // room for nB instances and nB * nrhs rows, grown when either is exceeded (the blocked kernel's calls vary both: a Jacobian works on a
+    // chunk of the batch, with one right-hand side per variable)
+    int reserve(std::string& err, DevMem& mem, hipStream_t s, size_t nB, size_t nrhs, size_t ldv, size_t lddg, size_t lddb, size_t nside)
     {
         for (hipError_t e : {ev0.status, ev1.status}) if (e != hipSuccess) return hip_fail(err, "hipEventCreate", e);
         stream = s; B = nB; rows = nB * nrhs; ldV = ldv; ldDg = lddg; ldDb = lddb; nSide = nside;
@@ -291,15 +277,12 @@ struct SensBuffers {
     }
 };
 
-// *_sensitivity_timing: the kernel time of the last sensitivity launch (ev0 -> ev1)
+// *_sensitivity_timing: the kernel time of the last sensitivity call (ResolveState::sensMs)
 template <class H>
-int sensitivity_timing(std::string& err, H* h, float* kernel_ms)
+int sensitivity_timing(H* h, float* kernel_ms)
 {
-    if (!h || !kernel_ms || (!h->sens.rhs && h->sens.lastMs < 0.f)) return LCQP_INVALID_ARGUMENT;
-    if (h->sens.lastMs >= 0.f) { *kernel_ms = h->sens.lastMs; return 0; }      // the last launch was a blocked one, on buffers of its own
-    HIPCHK(err, hipSetDevice(h->device));
-    HIPCHK(err, hipEventSynchronize(h->sens.ev1));
-    HIPCHK(err, hipEventElapsedTime(kernel_ms, h->sens.ev0, h->sens.ev1));
+    if (!h || !kernel_ms || h->rs.sensMs < 0.f) return LCQP_INVALID_ARGUMENT;
+    *kernel_ms = h->rs.sensMs;
     return 0;
 }
 #pragma GCC visibility pop

@@ -1,19 +1,13 @@
-// lcqp_kernels.hpp -- the kernels that are instantiated once per padded size np = 128*NCH, and their launcher.
-// Each instantiation is its own translation unit (lcqp_nch.hip compiled with -DLCQP_TU_NCH=1,2,3,4,8): the five builds run in
-// parallel, and the register allocation of one size cannot perturb another's (cdna_hip_programming.md §5.4 rule 19).
+// lcqp_kernels.hpp -- the kernels that are instantiated once per padded size np = 128*NCH, and their launch tables (lcqp_launch.hpp).
+// Each instantiation is its own translation unit (lcqp_nch.hip compiled with -DLCQP_TU_NCH=1,2,3,4,8,16,32, and for NCH <= 4 a second
+// time with -DLCQP_TU_FEW for the two persistent kernels alone): the eleven builds run in parallel, and the register allocation of one
+// size cannot perturb another's (cdna_hip_programming.md §5.4 rule 19).
 #pragma once
 #include "lcqp_dev.hpp"
 #include "lcqp_launch.hpp"
 #include "../../include/lcqp_synth.h"
 
 using namespace lcqp;
-
-#define LCQP_LDS_N(NCHV)                                    \
-    __shared__ double sh_arena[arena_doubles(NCHV)];        \
-    __shared__ double sh_red[16];                           \
-    __shared__ int sh_ired[16];                             \
-    Lds lds{sh_arena, sh_red, sh_ired};
-#define LCQP_LDS LCQP_LDS_N(4)
 
 
 // ---- the vector half of the setup: bounds of the box rows, ADMM rho vector, phi expressions (k_prepare, k_refresh) ----------------------
@@ -1160,53 +1154,73 @@ __global__ __launch_bounds__(WG) void k_util_rows_list(int m, int nlist, const d
                        coef ? coef + (size_t)b * m : nullptr, lds, [&](int i, double s) { if (o) o[i] = s; });
 }
 
-// ---- launcher of this translation unit's instantiation (declared in lcqp_launch.hpp) -----------------------------------------
+// ---- the launch tables of this translation unit's instantiation (declared in lcqp_launch.hpp) -------------------------------------
 template <int NCH>
-static void launch_run(int grid, hipStream_t s, const LaunchArgs& a)
+static void launch_run(const DevBatch& db, int grid, hipStream_t s)
 {
     if constexpr (NCH <= 2) {
         // the row state sits behind the routines' scratch (arena[0, LDS_ROWS_OFF)): the sweeps need 6 np doubles there, the triangular solves
         // 5 np, the widest pass over the inverse factor 4 capS, the rotations 3 capS
         static_assert(6 * 128 * NCH <= LDS_ROWS_OFF, "k_lcqp_run<NCH, true>: the sweeps' scratch must end below the row state");
-        if (a.db.mEcap <= LDS_ROWS_MAX && 4 * a.db.capS <= LDS_ROWS_OFF) { hipLaunchKernelGGL((k_lcqp_run<NCH, true, LCQP_VARIANT>), dim3(grid), dim3(WG), 0, s, a.db); return; }
+        if (db.mEcap <= LDS_ROWS_MAX && 4 * db.capS <= LDS_ROWS_OFF) { hipLaunchKernelGGL((k_lcqp_run<NCH, true, LCQP_VARIANT>), dim3(grid), dim3(WG), 0, s, db); return; }
     }
-    hipLaunchKernelGGL((k_lcqp_run<NCH, false, LCQP_VARIANT>), dim3(grid), dim3(WG), 0, s, a.db);
+    hipLaunchKernelGGL((k_lcqp_run<NCH, false, LCQP_VARIANT>), dim3(grid), dim3(WG), 0, s, db);
 }
 
+template <int NCH>
+static void launch_qp_solve(const DevBatch& db, int grid, hipStream_t s, int initial)
+{
+    hipLaunchKernelGGL((k_qp_solve<NCH, LCQP_VARIANT>), dim3(grid), dim3(WG), 0, s, db, initial);
+}
+
+namespace lcqp {
 #ifdef LCQP_TU_FEW
 // the translation unit of the second build holds the two persistent kernels only
 template <int NCH>
-static void launch_impl(int kid, int grid, hipStream_t s, const LaunchArgs& a)
+const RunKernels& few_kernels()
 {
-    if (kid == ID_k_lcqp_run) launch_run<NCH>(grid, s, a);
-    else if (kid == ID_k_qp_solve) hipLaunchKernelGGL((k_qp_solve<NCH, LCQP_VARIANT>), dim3(grid), dim3(WG), 0, s, a.db, a.initial);
+    static const RunKernels k = {launch_run<NCH>, launch_qp_solve<NCH>};      // as this unit builds them: LCQP_VARIANT, LCQP_MINWAVES
+    return k;
 }
 #else
 template <int NCH>
-static void launch_impl(int kid, int grid, hipStream_t s, const LaunchArgs& a)
+const SizeKernels& size_kernels()
 {
-    switch (kid) {
-        case ID_k_prepare:    hipLaunchKernelGGL((k_prepare<NCH>), dim3(grid), dim3(WG), 0, s, a.db); break;
-        case ID_k_refresh:    hipLaunchKernelGGL((k_refresh<NCH>), dim3(grid), dim3(WG), 0, s, a.db, a.mode, a.rho0); break;
-        case ID_k_sensitivity_blk:      // np <= 512 only: the callers send the larger sizes to k_sensitivity
-            if constexpr (NCH <= 4) hipLaunchKernelGGL((k_sensitivity_blk<NCH>), dim3(grid), dim3(WG), 0, s, a.db, a.sensFirst, a.nrhs, a.sensV, a.sensDg, a.sensDb, a.sensSide, a.sensInfo);
-            break;
-        case ID_k_sensitivity: hipLaunchKernelGGL((k_sensitivity<NCH>), dim3(grid), dim3(WG), 0, s, a.db, a.nrhs, a.sensV, a.sensDg, a.sensDb, a.sensSide, a.sensInfo); break;
-        case ID_k_build_C:    hipLaunchKernelGGL((k_build_C<NCH>), dim3(grid), dim3(WG), 0, s, a.db); break;
-        case ID_k_compress_C: hipLaunchKernelGGL((k_compress_C<NCH>), dim3(grid), dim3(WG), 0, s, a.db); break;
-        case ID_k_factor:     hipLaunchKernelGGL((k_factor<NCH, 1>), dim3(grid), dim3(WG), 0, s, a.db); break;
-        case ID_k_factor_full: hipLaunchKernelGGL((k_factor<NCH, NCH <= 2 ? 4 : 1>), dim3(grid), dim3(WG), 0, s, a.db); break;
-        case ID_k_trsm:       hipLaunchKernelGGL((k_trsm<NCH>), dim3(grid), dim3(WG), 0, s, a.db); break;
-        case ID_k_trsm_streamed: hipLaunchKernelGGL((k_trsm_streamed<NCH>), dim3(grid), dim3(WG), 0, s, a.db); break;
-        case ID_k_build_M:    hipLaunchKernelGGL((k_build_M<NCH>), dim3(grid), dim3(WG), 0, s, a.db); break;
-        case ID_k_lcqp_run:   launch_run<NCH>(grid, s, a); break;
-        case ID_k_qp_solve:   hipLaunchKernelGGL((k_qp_solve<NCH, LCQP_VARIANT>), dim3(grid), dim3(WG), 0, s, a.db, a.initial); break;
-        case ID_k_synth_fill: hipLaunchKernelGGL((k_synth_fill<NCH>), dim3(grid), dim3(WG), 0, s, a.db, a.seed0, a.first); break;
-        case ID_k_synth_Q:    hipLaunchKernelGGL((k_synth_Q<NCH>), dim3(grid), dim3(WG), 0, s, a.db); break;
-        case ID_k_util_symv:  hipLaunchKernelGGL((k_util_symv<NCH>), dim3(grid), dim3(WG), 0, s, a.n, a.alpha, a.A, a.b, a.c, a.d); break;
-        case ID_k_util_rows:  hipLaunchKernelGGL((k_util_rows<NCH>), dim3(grid), dim3(WG), 0, s, a.m, a.A, a.x, a.dots, a.coef, a.outT); break;
-        case ID_k_util_rows_list: hipLaunchKernelGGL((k_util_rows_list<NCH>), dim3(grid), dim3(WG), 0, s, a.m, a.n, a.A, a.list, a.x, a.dots, a.coef, a.outT); break;
-        default: break;
-    }
+    static const SizeKernels k = [] {
+        SizeKernels t{};
+        t.nch = NCH;
+        if constexpr (NCH <= 4) t.few = &few_kernels<NCH>();
+        t.prepare = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_prepare<NCH>), dim3(grid), dim3(WG), 0, s, db); };
+        t.refresh = [](const DevBatch& db, int grid, hipStream_t s, int mode, const double* rho0) { hipLaunchKernelGGL((k_refresh<NCH>), dim3(grid), dim3(WG), 0, s, db, mode, rho0); };
+        if constexpr (NCH <= 4)      // np <= 512 only: a panel of np >= 1024 does not fit LDS
+            t.sensitivity_blk = [](const DevBatch& db, int grid, hipStream_t s, int first, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo) {
+                hipLaunchKernelGGL((k_sensitivity_blk<NCH>), dim3(grid), dim3(WG), 0, s, db, first, nrhs, v, dg, dbo, side, sinfo);
+            };
+        t.sensitivity = [](const DevBatch& db, int grid, hipStream_t s, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo) {
+            hipLaunchKernelGGL((k_sensitivity<NCH>), dim3(grid), dim3(WG), 0, s, db, nrhs, v, dg, dbo, side, sinfo);
+        };
+        t.build_C = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_build_C<NCH>), dim3(grid), dim3(WG), 0, s, db); };
+        t.compress_C = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_compress_C<NCH>), dim3(grid), dim3(WG), 0, s, db); };
+        t.factor = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_factor<NCH, 1>), dim3(grid), dim3(WG), 0, s, db); };
+        t.factor_full = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_factor<NCH, NCH <= 2 ? 4 : 1>), dim3(grid), dim3(WG), 0, s, db); };
+        t.trsm = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_trsm<NCH>), dim3(grid), dim3(WG), 0, s, db); };
+        t.trsm_streamed = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_trsm_streamed<NCH>), dim3(grid), dim3(WG), 0, s, db); };
+        t.build_M = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_build_M<NCH>), dim3(grid), dim3(WG), 0, s, db); };
+        t.run = {launch_run<NCH>, launch_qp_solve<NCH>};
+        t.synth_fill = [](const DevBatch& db, int grid, hipStream_t s, uint64_t seed0, uint64_t first) { hipLaunchKernelGGL((k_synth_fill<NCH>), dim3(grid), dim3(WG), 0, s, db, seed0, first); };
+        t.synth_Q = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_synth_Q<NCH>), dim3(grid), dim3(WG), 0, s, db); };
+        t.util_symv = [](int grid, hipStream_t s, int n, double alpha, const double* A, const double* b, const double* c, double* d) {
+            hipLaunchKernelGGL((k_util_symv<NCH>), dim3(grid), dim3(WG), 0, s, n, alpha, A, b, c, d);
+        };
+        t.util_rows = [](int grid, hipStream_t s, int m, const double* A, const double* x, double* dots, const double* coef, double* outT) {
+            hipLaunchKernelGGL((k_util_rows<NCH>), dim3(grid), dim3(WG), 0, s, m, A, x, dots, coef, outT);
+        };
+        t.util_rows_list = [](int grid, hipStream_t s, int m, int nlist, const double* A, const int* list, const double* x, double* dots, const double* coef, double* outT) {
+            hipLaunchKernelGGL((k_util_rows_list<NCH>), dim3(grid), dim3(WG), 0, s, m, nlist, A, list, x, dots, coef, outT);
+        };
+        return t;
+    }();
+    return k;
 }
 #endif
+}  // namespace lcqp

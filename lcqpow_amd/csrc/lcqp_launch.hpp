@@ -1,45 +1,48 @@
 // lcqp_launch.hpp -- the seam between the host translation unit (lcqp_hip.hip) and the per-size kernel translation units
-// (lcqp_nch.hip, one per NCH in {1,2,3,4,8,16,32}).
+// (lcqp_nch.hip, one per NCH in {1,2,3,4,8,16,32} and a second one of the two persistent kernels for NCH <= 4): per padded size one table
+// of launch functions, each with the arguments its kernel takes.  `grid` is the number of workgroups; every launch is asynchronous on
+// `s`.  Declarations only: no device code lives here.
 #pragma once
 #include "lcqp_dev.hpp"
 
 namespace lcqp {
+// nothing of the seam enters the dynamic symbol table of the library
+#pragma GCC visibility push(hidden)
 
-enum KernelId { ID_k_prepare, ID_k_build_C, ID_k_compress_C, ID_k_factor, ID_k_factor_full, ID_k_trsm, ID_k_trsm_streamed, ID_k_build_M, ID_k_lcqp_run, ID_k_qp_solve,
-                ID_k_synth_fill, ID_k_synth_Q, ID_k_util_symv, ID_k_util_rows, ID_k_util_rows_list, ID_k_refresh, ID_k_sensitivity, ID_k_sensitivity_blk };
-
-struct LaunchArgs {
-    DevBatch db;
-    const int* list = nullptr;
-    int initial = 0;
-    uint64_t seed0 = 0, first = 0;
-    int mode = 0;                       // k_refresh: 0 every instance cold, 1 warm where the last run succeeded
-    const double* rho0 = nullptr;       // k_refresh: [B] starting penalties of the warm instances (device), or null
-    // k_sensitivity (device buffers; layouts at the kernel)
-    int nrhs = 0;
-    int sensFirst = 0;                  // k_sensitivity_blk: workgroup o works on instance sensFirst + o; sensV null: unit vectors
-    const double* sensV = nullptr;
-    double *sensDg = nullptr, *sensDb = nullptr;
-    int *sensSide = nullptr, *sensInfo = nullptr;
-    // building-block kernels
-    int n = 0, m = 0;
-    double alpha = 0.0;
-    const double *A = nullptr, *b = nullptr, *c = nullptr, *x = nullptr, *coef = nullptr;
-    double *d = nullptr, *dots = nullptr, *outT = nullptr;
+// the two persistent kernels: the standard unit and the second (256-register) build each define a pair
+struct RunKernels {
+    void (*lcqp_run)(const DevBatch& db, int grid, hipStream_t s);
+    void (*qp_solve)(const DevBatch& db, int grid, hipStream_t s, int initial);
 };
 
-// defined in lcqp_nch.hip for NCH = LCQP_TU_NCH
-void lcqp_launch_1(int kid, int grid, hipStream_t s, const LaunchArgs& a);
-void lcqp_launch_2(int kid, int grid, hipStream_t s, const LaunchArgs& a);
-void lcqp_launch_3(int kid, int grid, hipStream_t s, const LaunchArgs& a);
-void lcqp_launch_4(int kid, int grid, hipStream_t s, const LaunchArgs& a);
-void lcqp_launch_8(int kid, int grid, hipStream_t s, const LaunchArgs& a);
-void lcqp_launch_16(int kid, int grid, hipStream_t s, const LaunchArgs& a);
-void lcqp_launch_32(int kid, int grid, hipStream_t s, const LaunchArgs& a);
-// k_lcqp_run and k_qp_solve for batches of at most three workgroups per CU (lcqp_nch.hip with -DLCQP_TU_FEW), np <= 512
-void lcqp_launch_few_1(int kid, int grid, hipStream_t s, const LaunchArgs& a);
-void lcqp_launch_few_2(int kid, int grid, hipStream_t s, const LaunchArgs& a);
-void lcqp_launch_few_3(int kid, int grid, hipStream_t s, const LaunchArgs& a);
-void lcqp_launch_few_4(int kid, int grid, hipStream_t s, const LaunchArgs& a);
+using BatchKernel = void (*)(const DevBatch& db, int grid, hipStream_t s);
 
+struct SizeKernels {
+    int nch;                    // np = 128 * nch
+    RunKernels run;
+    const RunKernels* few;      // the second build of the persistent kernels (np <= 512, at most three workgroups per CU), null for NCH > 4
+    BatchKernel prepare;
+    // mode 0: every instance cold, 1: warm where the last run succeeded; rho0 [B]: starting penalties of the warm instances (device), or null
+    void (*refresh)(const DevBatch& db, int grid, hipStream_t s, int mode, const double* rho0);
+    BatchKernel build_C, compress_C;
+    BatchKernel factor, factor_full;      // factor_full: held to 128 registers for np <= 256, so that four workgroups per CU are resident
+    BatchKernel trsm, trsm_streamed, build_M;
+    void (*synth_fill)(const DevBatch& db, int grid, hipStream_t s, uint64_t seed0, uint64_t first);
+    BatchKernel synth_Q;
+    // device buffers, layouts at the kernels.  sensitivity: the whole batch.  sensitivity_blk: workgroup o works on instance first + o,
+    // v null: unit vectors; null for NCH > 4 (a panel of np >= 1024 does not fit LDS)
+    void (*sensitivity)(const DevBatch& db, int grid, hipStream_t s, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo);
+    void (*sensitivity_blk)(const DevBatch& db, int grid, hipStream_t s, int first, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo);
+    // building-block kernels
+    void (*util_symv)(int grid, hipStream_t s, int n, double alpha, const double* A, const double* b, const double* c, double* d);
+    void (*util_rows)(int grid, hipStream_t s, int m, const double* A, const double* x, double* dots, const double* coef, double* outT);
+    void (*util_rows_list)(int grid, hipStream_t s, int m, int nlist, const double* A, const int* list, const double* x, double* dots, const double* coef, double* outT);
+};
+
+// defined in lcqp_kernels.hpp and instantiated by lcqp_nch.hip for NCH = LCQP_TU_NCH: size_kernels by the standard unit, few_kernels by
+// the unit compiled with -DLCQP_TU_FEW
+template <int NCH> const SizeKernels& size_kernels();
+template <int NCH> const RunKernels& few_kernels();
+
+#pragma GCC visibility pop
 }  // namespace lcqp

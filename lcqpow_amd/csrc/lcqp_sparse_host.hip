@@ -358,12 +358,14 @@ extern "C" int lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* h, int nrhs, const
     sp_launchers(d.G).sensitivity(d, h->stream, nrhs, sb.v, sb.dg, sb.db, sb.side, sb.info);
     HIPCHK(g_sp_err, hipGetLastError());
     HIPCHK(g_sp_err, hipEventRecord(sb.ev1, h->stream));
-    return sb.download(g_sp_err, dg, db, side, info, d.n, d.m);
+    if (int rc = sb.download(g_sp_err, dg, db, side, info, d.n, d.m)) return rc;
+    HIPCHK(g_sp_err, hipEventElapsedTime(&h->rs.sensMs, sb.ev0, sb.ev1));
+    return 0;
 }); }
 
 extern "C" int lcqp_hip_sparse_sensitivity_timing(lcqp_hip_sparse_t* h, float* kernel_ms)
 {
-    return guarded(g_sp_err, [&] { return sensitivity_timing(g_sp_err, h, kernel_ms); });
+    return sensitivity_timing(h, kernel_ms);
 }
 
 extern "C" int lcqp_hip_sparse_synchronize(lcqp_hip_sparse_t* h)

@@ -46,6 +46,13 @@ struct Lds {
     double* red;    // 16 doubles
     int* ired;      // 16 ints
 };
+// the LDS of a kernel, declared at the top of its body: LCQP_LDS_N(NCH) in the per-size kernels, LCQP_LDS in the ones that are not templated
+#define LCQP_LDS_N(NCHV)                                    \
+    __shared__ double sh_arena[arena_doubles(NCHV)];        \
+    __shared__ double sh_red[16];                           \
+    __shared__ int sh_ired[16];                             \
+    Lds lds{sh_arena, sh_red, sh_ired};
+#define LCQP_LDS LCQP_LDS_N(4)
 
 // Matrix streams (rows of Q, E, Et, the factor L1): every byte is used once per pass and the matrices of a batch (12 GB) never fit a
 // cache, so these loads are non-temporal and leave L2 / the Infinity Cache to what IS re-read: the vectors and the inverse factor T
