@@ -6,6 +6,7 @@ printed.  The targets are solutions of the same LCQPs for other linear terms, so
     python examples/sensitivity.py
     python examples/sensitivity.py sparse      # the same fit on the sparse arm: 16 banded LCQPs (n = 64), lcqp_hip_sparse_sensitivity
     python examples/sensitivity.py jacobian    # the full Jacobians dx/dg of the 64 LCQPs (lcqp_hip_batch_jacobian): |Jg - Jg'| and the kernel time
+    python examples/sensitivity.py adjoint     # learn ONE constraint matrix A shared by the 64 LCQPs from a loss on x and y (lcqp_hip_batch_adjoint)
 """
 import os
 import sys
@@ -54,11 +55,38 @@ def sparse_main():
     sb.close()
 
 
+def adjoint_main():
+    """the OptNet setting: the 64 LCQPs share Q and A; targets (x, y) come from the true A, the fit starts from a disturbed one"""
+    rng = np.random.default_rng(0)
+    ds = [problem(rng) for _ in range(B)]
+    st = lambda k: np.stack([d[k] for d in ds])
+    Q, A_true = ds[0]["Q"], ds[0]["A"]
+    bt = la.BatchLCQP(B, n, nC, nComp, opt=la.default_options(perturbStep=0))
+    assert bt.load(0, B, np.stack([Q] * B), st("g"), st("L"), st("R"), A=np.stack([A_true] * B), lbA=st("lbA"), ubA=st("ubA")) == 0
+    layer = BatchLCQPLayer(bt, bounds=dict(lbA=st("lbA"), ubA=st("ubA")))
+    g = torch.as_tensor(st("g"))
+    with torch.no_grad():
+        xt, yt = layer.solve(g, A=torch.as_tensor(A_true))
+    A = torch.tensor(A_true + 0.05 * rng.standard_normal(A_true.shape) / np.sqrt(n), requires_grad=True)
+    opt = torch.optim.SGD([A], lr=0.02)
+    for step in range(12):
+        opt.zero_grad()
+        x, y = layer.solve(g, A=A)      # a shared [nC][nV] tensor: load + run; A.grad is summed over the batch on the device
+        loss = 0.5 * ((x - xt) ** 2).sum() + 0.5 * ((y - yt) ** 2).sum()
+        loss.backward()
+        opt.step()
+        print("step %2d  mean loss per LCQP %.6e  |A - A_true|_max %.3e  flagged instances %d"
+              % (step, loss.item() / B, float(np.abs(A.detach().numpy() - A_true).max()), int(np.count_nonzero(layer.info))))
+    bt.close()
+
+
 def main():
     if la.device_count() < 1:
         raise SystemExit("needs a GPU (the product path has no CPU fallback)")
     if sys.argv[1:] == ["sparse"]:
         return sparse_main()
+    if sys.argv[1:] == ["adjoint"]:
+        return adjoint_main()
     rng = np.random.default_rng(0)
     ds = [problem(rng) for _ in range(B)]
     st = lambda k: np.stack([d[k] for d in ds])

@@ -115,6 +115,10 @@ int  lcqp_hip_qp_sensitivity(lcqp_hip_qp_t* qp, int nrhs, const double* v, doubl
  * Jg [nV][nV], Jb [nV][nV + nC] (or NULL), side [nV + nC], info [1].  nV > 512: the vector kernel, the bits of lcqp_hip_qp_sensitivity. */
 int  lcqp_hip_qp_sensitivity_blocked(lcqp_hip_qp_t* qp, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
 int  lcqp_hip_qp_jacobian(lcqp_hip_qp_t* qp, double* Jg, double* Jb, int* side, int* info);
+/* lcqp_hip_batch_adjoint (below) for the batch of one: vx, dg [nV]; vy (or NULL), db, side [nV + nC]; info [1]; dQ [nV][nV] and dA [nC][nV]
+ * (A = the stacked rows) may be NULL.  LCQP_INVALID_ARGUMENT: NULL object, vx or dg; LCQP_LCQPOBJECT_NOT_SETUP as lcqp_hip_qp_sensitivity. */
+int  lcqp_hip_qp_adjoint(lcqp_hip_qp_t* qp, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
+                         double* dQ, double* dA);
 /* test and diagnostic entry points: lcqp_hip_batch_read_setup / lcqp_hip_batch_read_working_set (below) for the batch of one this object
  * holds; LCQP_LCQPOBJECT_NOT_SETUP before its first solve */
 int  lcqp_hip_qp_read_setup(lcqp_hip_qp_t* qp, int dims[9], double scal[2], double* C, double* F1, double* D1, double* Et, double* MM,
@@ -228,6 +232,23 @@ int  lcqp_hip_batch_sensitivity_blocked(lcqp_hip_batch_t* b, int nrhs, const dou
 int  lcqp_hip_batch_jacobian(lcqp_hip_batch_t* b, int first, int count, double* Jg, double* Jb, int* side, int* info);
 /* another staging cap for this object's Jacobian calls (0: the default); for tests of the chunking and for small devices */
 int  lcqp_hip_batch_set_jacobian_staging(lcqp_hip_batch_t* b, size_t bytes);
+/* The full adjoint (DESIGN.md section 3a''''): lcqp_hip_batch_sensitivity with nrhs = 1, extended by upstream gradients on the returned duals
+ * and by the gradients in the matrices.  At the returned point x, y_W solve  H x + g - E_W' y_W = 0,  E_W x = b_W  (H = Q + sigma_p I; y in the
+ * reference's layout, box rows first; the returned y is the multiplier of this penalty-free system).  For a loss l with vx = dl/dx [B][nV] and
+ * vy = dl/dy [B][nd] (host; vy may be NULL = zero; its entries outside W are ignored: those duals are identically zero on the branch):
+ *   d, mu with  H d + E_W' mu = vx,  E_W d = -vy_W;     dg = dl/dg = -d,   db_W = dl/db_W = mu   (dg, db, side, info as lcqp_hip_batch_sensitivity)
+ *   dQ = 1/2 (dg x' + x dg')                             the symmetric derivative; symmetric to the bit
+ *   row r of dA / dL / dR = -(db_r x + y_r dg)           for the rows with side != 0, exactly zero elsewhere; box rows have no matrix
+ * reduce = 0: dQ [B][nV][nV], dA [B][nC][nV], dL and dR [B][nComp][nV], computed in chunks of instances whose staging stays below the cap of
+ * lcqp_hip_batch_set_jacobian_staging (the results do not depend on the chunking).  reduce = 1: [nV][nV], [nC][nV], [nComp][nV]: the sums over
+ * the batch (one matrix shared by the instances), formed on the device in the order of the batch -- the same bits on every call; an instance
+ * with info & 1 contributes zeros, every other flagged instance what the kernels computed.  Each of dQ, dA, dL, dR may be NULL.
+ * With vy == NULL and no matrix output the call is lcqp_hip_batch_sensitivity with nrhs = 1, to the bit.  It reads the batch and changes none
+ * of it.  lcqp_hip_batch_sensitivity_timing then reports the sum of its kernels.
+ * LCQP_INVALID_ARGUMENT: NULL handle, vx or dg, or reduce outside 0 / 1.  LCQP_LCQPOBJECT_NOT_SETUP as lcqp_hip_batch_sensitivity.  Both are
+ * decided before any device call. */
+int  lcqp_hip_batch_adjoint(lcqp_hip_batch_t* b, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
+                            int reduce, double* dQ, double* dA, double* dL, double* dR);
 /* out[0] = full setups, out[1] = homotopy launches this object has issued (host counters) */
 int  lcqp_hip_batch_launch_counts(lcqp_hip_batch_t* b, int out[2]);
 /* Hint of a caller that keeps several batch objects in flight (BatchPipeline): the setup of this object will run beside the homotopy

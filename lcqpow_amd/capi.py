@@ -115,6 +115,8 @@ def lib():
         L.lcqp_hip_batch_jacobian.argtypes = [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_qp_jacobian.argtypes = [C.c_void_p, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_batch_set_jacobian_staging.argtypes = [C.c_void_p, C.c_size_t]
+        L.lcqp_hip_batch_adjoint.argtypes = [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p, C.c_int] + [c_double_p] * 4
+        L.lcqp_hip_qp_adjoint.argtypes = [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p] + [c_double_p] * 2
         L.lcqp_hip_util_symv.argtypes = [C.c_int, C.c_int, C.c_double] + [c_double_p] * 4
         L.lcqp_hip_util_gemv.argtypes = [C.c_int, C.c_int, C.c_int] + [c_double_p] * 3
         L.lcqp_hip_util_gemv_t.argtypes = [C.c_int, C.c_int, C.c_int] + [c_double_p] * 3
@@ -229,6 +231,25 @@ def _sensitivity(call, v, B, nV, nd, check=None):
     return (dg[:, 0], db[:, 0], side, info) if single else (dg, db, side, info)
 
 
+def _adjoint(call, vx, vy, B, nV, nd, shapes, matrices, lead, check=None):
+    """call(vx, vy, dg, db, side, info, *matrix outputs in the order of `shapes`) -> rc.  vx [B][nV]; vy [B][nd] or None; shapes: name ->
+    (rows, nV) of every matrix the entry point has; matrices: the names asked for; lead: () for sums over the batch, (B,) otherwise.
+    Returns a dict with dg [B][nV], db [B][nd], side [B][nd], info [B] and one array per name in `matrices`."""
+    vx = _arr(vx); vy = _arr(vy)
+    if vx.shape != (B, nV):
+        raise ValueError(f"vx: expected [{B}][{nV}], got shape {vx.shape}")
+    if vy is not None and vy.shape != (B, nd):
+        raise ValueError(f"vy: expected [{B}][{nd}], got shape {vy.shape}")
+    unknown = set(matrices) - set(shapes)
+    if unknown:
+        raise ValueError(f"matrices: unknown names {sorted(unknown)} (this object has {sorted(shapes)})")
+    out = dict(dg=np.zeros((B, nV)), db=np.zeros((B, nd)), side=np.zeros((B, nd), dtype=np.int32), info=np.zeros(B, dtype=np.int32))
+    mats = {k: np.zeros(tuple(lead) + shp) for k, shp in shapes.items() if k in matrices}
+    (check or _check)(call(_p(vx), _p(vy), _p(out["dg"]), _p(out["db"]), _ip(out["side"]), _ip(out["info"]), *[_p(mats.get(k)) for k in shapes]), "adjoint")
+    out.update(mats)
+    return out
+
+
 SENS_PANEL = 16      # LCQP_SENS_PANEL: vectors per panel of the blocked sensitivity kernel
 
 
@@ -302,6 +323,15 @@ class SubsolverHIP:
         solved -- see BatchLCQP.jacobian."""
         Jg, Jb, side, info = _jacobian(lambda first, count, *a: lib().lcqp_hip_qp_jacobian(self.h, *a), 1, self.nV, self.nV + self.nC, 0, 1, bounds)
         return Jg[0], (Jb[0] if bounds else None), side[0], int(info[0])
+
+    def adjoint(self, vx, vy=None, matrices=("Q", "A")):
+        """lcqp_hip_qp_adjoint: BatchLCQP.adjoint on the QP last solved.  vx [nV], vy [nV + nC] or None; returns a dict with dg [nV], db and
+        side [nV + nC], info (int) and, as `matrices` asks, Q [nV][nV] and A [nC][nV] (the gradients in the matrices of the constructor)."""
+        n, m = self.nV, self.nC
+        vx = _arr(vx); vy = _arr(vy)
+        r = _adjoint(lambda *a: lib().lcqp_hip_qp_adjoint(self.h, *a), vx[None], None if vy is None else vy[None], 1, n, n + m,
+                     dict(Q=(n, n), A=(m, n)), matrices, ())
+        return {k: (int(v[0]) if k == "info" else v[0] if k in ("dg", "db", "side") else v) for k, v in r.items()}
 
     def read_setup(self):
         """the constant matrices of the last fresh solve (test and diagnostic entry point; see BatchLCQP.read_setup)"""
@@ -571,6 +601,26 @@ class BatchLCQP(_Batch):
             self._call("set_jacobian_staging", int(_staging_bytes))
         try:
             return _jacobian(lambda *a: self._sym("jacobian")(self.h, *a), self.B, self.nV, self.nd, first, count, bounds, check=self._check)
+        finally:
+            if _staging_bytes is not None:
+                self._call("set_jacobian_staging", 0)      # back to the default cap
+
+    def adjoint(self, vx, vy=None, matrices=("Q", "A", "L", "R"), reduce=False, _staging_bytes=None):
+        """lcqp_hip_batch_adjoint: the gradients of a loss that reads the x AND the y the last run / resolve returned (synchronous; DESIGN.md
+        section 3a'''').  vx = dl/dx [B][nV]; vy = dl/dy [B][nd] in the dual layout, or None (entries on rows outside the working set are
+        ignored).  Returns a dict: dg, db, side, info as sensitivity (one vector per instance), and under the names in `matrices` the
+        gradients in Q [B][nV][nV] (symmetric), A [B][nC][nV], L and R [B][nComp][nV] -- with reduce=True their sums over the batch, [nV][nV]
+        and so on, formed on the device (one matrix shared by all instances).  Rows outside the working set are zero; an instance with
+        info & 1 contributes zeros.  Without reduce the matrices come in chunks of instances under the staging cap of jacobian
+        (_staging_bytes: another cap for this one call, for tests).  The call changes nothing on the device."""
+        n, nC, nK = self.nV, self.nC, self.nComp
+        if _staging_bytes is not None:
+            self._call("set_jacobian_staging", int(_staging_bytes))
+        try:
+            f = self._sym("adjoint")
+            call = lambda vx, vy, dg, db, side, info, *m: f(self.h, vx, vy, dg, db, side, info, 1 if reduce else 0, *m)
+            return _adjoint(call, vx, vy, self.B, n, self.nd, dict(Q=(n, n), A=(nC, n), L=(nK, n), R=(nK, n)), matrices,
+                            () if reduce else (self.B,), check=self._check)
         finally:
             if _staging_bytes is not None:
                 self._call("set_jacobian_staging", 0)      # back to the default cap

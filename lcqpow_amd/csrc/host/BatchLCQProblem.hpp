@@ -74,6 +74,14 @@ class BatchLCQProblem {
     {
         return (ReturnValue)lcqp_hip_batch_jacobian(h, first, count, Jg, Jb, side, info);
     }
+    // lcqp_hip_batch_adjoint: upstream gradients vx [batch][nV] and vy [batch][nDuals] (or 0) on the primal and dual solutions; dg, db, side,
+    // info as getSensitivity with nrhs = 1; the gradients in the matrices dQ [batch][nV][nV], dA [batch][nC][nV], dL, dR [batch][nComp][nV]
+    // (each may be 0), or with reduce their sums over the batch ([nV][nV], ...)
+    ReturnValue getAdjoint(const double* vx, const double* vy, double* dg, double* db = 0, int* side = 0, int* info = 0, bool reduce = false,
+                           double* dQ = 0, double* dA = 0, double* dL = 0, double* dR = 0)
+    {
+        return (ReturnValue)lcqp_hip_batch_adjoint(h, vx, vy, dg, db, side, info, reduce ? 1 : 0, dQ, dA, dL, dR);
+    }
     // full setups and homotopy launches this object has issued
     ReturnValue getLaunchCounts(int& setups, int& launches) const
     {

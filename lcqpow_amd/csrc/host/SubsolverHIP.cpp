@@ -57,4 +57,9 @@ ReturnValue SubsolverHIP::getJacobian(double* Jg, double* Jb, int* side, int* in
     return (ReturnValue)lcqp_hip_qp_jacobian(qp, Jg, Jb, side, info);
 }
 
+ReturnValue SubsolverHIP::getAdjoint(const double* vx, const double* vy, double* dg, double* db, int* side, int* info, double* dQ, double* dA)
+{
+    return (ReturnValue)lcqp_hip_qp_adjoint(qp, vx, vy, dg, db, side, info, dQ, dA);
+}
+
 }  // namespace LCQPow

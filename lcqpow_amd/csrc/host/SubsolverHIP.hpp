@@ -27,6 +27,8 @@ class SubsolverHIP : public SubsolverBase {
     ReturnValue getSensitivity(int nrhs, const double* v, double* dg, double* db = 0, int* side = 0, int* info = 0, bool blocked = false);
     // lcqp_hip_qp_jacobian: Jg [nV][nV], Jb [nV][nV + nC] (or 0), side [nV + nC], info [1]
     ReturnValue getJacobian(double* Jg, double* Jb = 0, int* side = 0, int* info = 0);
+    // lcqp_hip_qp_adjoint: vx, dg [nV]; vy (or 0), db, side [nV + nC]; info [1]; dQ [nV][nV], dA [nC][nV] may be 0
+    ReturnValue getAdjoint(const double* vx, const double* vy, double* dg, double* db = 0, int* side = 0, int* info = 0, double* dQ = 0, double* dA = 0);
 
   private:
     void clear();

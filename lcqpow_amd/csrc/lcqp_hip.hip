@@ -18,7 +18,7 @@ using namespace lcqp_rt;
 
 
 // =================================================================================================
-// device kernels: the per-size ones live in lcqp_kernels.hpp / lcqp_nch.hip; here only the two that are not templated
+// device kernels: the per-size ones live in lcqp_kernels.hpp / lcqp_nch.hip; here only the ones that are not templated
 // =================================================================================================
 __global__ __launch_bounds__(WG) void k_chol(int np, int nblk, int n, double* F, double* dscr, int* fail)
 {
@@ -36,6 +36,76 @@ __global__ __launch_bounds__(WG, 4) void k_backsolve(int np, int nblk, const dou
     __syncthreads();
     wg_trsv(F + (size_t)b * np * np, np, nblk, xv, true, lds);
     wg_trsv(F + (size_t)b * np * np, np, nblk, xv, false, lds);
+}
+
+// ---- the matrix gradients of an adjoint call (DESIGN.md section 3a'''', lcqp_hip_batch_adjoint) --------------------------------------
+// With dg, db, side and info of k_sensitivity (nrhs = 1, still in its device buffers) and the returned x, y, row r of the stacked gradient
+// [dQ; dA; dL; dR] ([nd][n]: r < n a row of Q, above it the entry of the dual layout the row of E belongs to) of instance b is
+//   s_r (alpha_r x_b + beta_r dg_b),   r < n: alpha = dg_r, beta = x_r, s = 1/2 (the symmetric derivative);
+//                                      r >= n: alpha = -db_r, beta = -y_r, s = 1 where side_r != 0, a zero row elsewhere;
+// zero for an instance with info & 1.  The two products are rounded separately and then added (no contraction): entry (i, j) of dQ forms the
+// products of entry (j, i) in the other order, so dQ is symmetric to the bit.  Both kernels read x, y and the four buffers, nothing else.
+struct AdjointArgs {
+    int B, n, np, nd, ldb;                 // ldb: pitch of db
+    const double *x, *y, *dg, *db;         // xout [B][n], yout [B][nd], dg [B][np], db [B][ldb]
+    const int *side, *info;                // [B][nd], [B]
+};
+// rows [r0, r0 + rows) of the stacked gradient go to out ([count][rows][n], or [rows][n] summed over the batch); null: not asked for
+struct AdjointSeg { double* out; int r0, rows; };
+struct AdjointSegs { AdjointSeg s[4]; };
+
+__device__ __forceinline__ double adjoint_term(const AdjointArgs& a, int b, int r, int j)
+{
+#pragma clang fp contract(off)
+    if (a.info[b] & 1) return 0.0;
+    const double xj = a.x[(size_t)b * a.n + j], dj = a.dg[(size_t)b * a.np + j];
+    if (r < a.n) return 0.5 * (a.dg[(size_t)b * a.np + r] * xj + a.x[(size_t)b * a.n + r] * dj);
+    if (a.side[(size_t)b * a.nd + r] == 0) return 0.0;
+    return -(a.db[(size_t)b * a.ldb + r] * xj + a.y[(size_t)b * a.nd + r] * dj);
+}
+
+// k_adjoint_outer: the gradients of the instances [first, first + count), one matrix per instance.  blockIdx.y: the segment; the threads
+// walk its count * rows * n doubles as one array, two neighbours each (one 16-byte store; the buffers start on 16-byte boundaries).
+__global__ __launch_bounds__(WG) void k_adjoint_outer(AdjointArgs a, AdjointSegs segs, int first, int count)
+{
+    const AdjointSeg sg = segs.s[blockIdx.y];
+    if (!sg.out) return;
+    const size_t per = (size_t)sg.rows * a.n, total = per * count;
+    for (size_t p = ((size_t)blockIdx.x * WG + threadIdx.x) * 2; p < total; p += (size_t)gridDim.x * WG * 2) {
+        double v[2] = {0.0, 0.0};
+        for (int e = 0; e < 2; e++) {
+            const size_t f = p + e;
+            if (f >= total) break;
+            const size_t o = f / per, rem = f - o * per;
+            const int r = (int)(rem / a.n), j = (int)(rem - (size_t)r * a.n);
+            v[e] = adjoint_term(a, first + (int)o, sg.r0 + r, j);
+        }
+        if (p + 1 < total) *reinterpret_cast<double2*>(sg.out + p) = double2{v[0], v[1]};
+        else sg.out[p] = v[0];
+    }
+}
+
+// k_adjoint_reduce: the same gradients summed over the batch (one Q / A / L / R shared by the instances).  A thread owns two neighbouring
+// entries and adds the instances' terms -- the very values k_adjoint_outer writes -- in the order of the batch: no atomics, the same bits
+// on every call, and the rounding error of a sum of B numbers, (B - 1) eps/2 sum_b |term_b|.  (A product [alpha' beta'] [X; DG] on the fp64
+// matrix cores would round against the partial sums of alpha x and beta dg separately, which cancel inside a term: no bound in the terms.)
+__global__ __launch_bounds__(WG) void k_adjoint_reduce(AdjointArgs a, AdjointSegs segs)
+{
+    const AdjointSeg sg = segs.s[blockIdx.y];
+    if (!sg.out) return;
+    const size_t total = (size_t)sg.rows * a.n;
+    for (size_t p = ((size_t)blockIdx.x * WG + threadIdx.x) * 2; p < total; p += (size_t)gridDim.x * WG * 2) {
+        const bool two = p + 1 < total;
+        const int r0 = (int)(p / a.n), j0 = (int)(p - (size_t)r0 * a.n);
+        const int r1 = two ? (int)((p + 1) / a.n) : r0, j1 = two ? (int)(p + 1 - (size_t)r1 * a.n) : j0;
+        double s0 = 0.0, s1 = 0.0;
+        for (int b = 0; b < a.B; b++) {
+            s0 += adjoint_term(a, b, sg.r0 + r0, j0);
+            s1 += adjoint_term(a, b, sg.r0 + r1, j1);
+        }
+        if (two) *reinterpret_cast<double2*>(sg.out + p) = double2{s0, s1};
+        else sg.out[p] = s0;
+    }
 }
 
 // =================================================================================================
@@ -118,7 +188,11 @@ struct lcqp_hip_batch {
     std::vector<char> boxed;              // [B][n]
     SensBuffers sens;                     // of k_sensitivity
     SensBuffers sensBlk;                  // of k_sensitivity_blk (another pitch of db, a varying number of instances)
-    size_t jacStaging = LCQP_JACOBIAN_STAGING_BYTES;      // device bytes a Jacobian call may stage per chunk of instances
+    size_t jacStaging = LCQP_JACOBIAN_STAGING_BYTES;      // device bytes a Jacobian / adjoint call may stage per chunk of instances
+    // of lcqp_hip_batch_adjoint, grown on demand: the upstream gradients on the duals [B][nd]; the matrix gradients of one chunk
+    double *adjVy = nullptr, *adjOut = nullptr;
+    size_t adjVyCap = 0, adjOutCap = 0;
+    Event adjEv0, adjEv1;                 // around the last matrix-gradient launch
     int nch;
     const SizeKernels* k = nullptr;       // the launch table of the padded size (dense_kernels), set by lcqp_hip_batch_create
     explicit lcqp_hip_batch(int dev) : db(), device(dev) {}
@@ -653,7 +727,20 @@ extern "C" int lcqp_hip_batch_read_working_set(lcqp_hip_batch_t* h, int b, int d
 // One launch on the batch stream, host buffers in and out, its kernel time added to *ms.  blk: k_sensitivity_blk on the instances
 // [first, first + count), on buffers of its own (the two kernels fix different pitches of db); v == nullptr: unit vectors, nothing
 // uploaded.  Otherwise k_sensitivity, which has no instance offset: first = 0, count = B.
-static int sensitivity_launch(lcqp_hip_batch* h, bool blk, int first, int count, int nrhs, const double* v, double* dg, double* db, int* side, int* info, float* ms)
+// a device buffer of the handle with room for `count` doubles (the stream is drained before a smaller one is freed)
+static int grow(lcqp_hip_batch* h, double*& p, size_t& cap, size_t count)
+{
+    if (count <= cap) return 0;
+    HIPCHK(g_err, hipStreamSynchronize(h->stream));
+    h->mem.release(p);
+    p = nullptr; cap = 0;
+    if (!h->mem.alloc(g_err, p, count)) return LCQP_HIP_ERROR;
+    cap = count;
+    return 0;
+}
+
+static int sensitivity_launch(lcqp_hip_batch* h, bool blk, int first, int count, int nrhs, const double* v, double* dg, double* db, int* side, int* info, float* ms,
+                              const double* vy = nullptr)
 {
     DevBatch& d = h->db;
     SensBuffers& sb = blk ? h->sensBlk : h->sens;
@@ -662,8 +749,13 @@ static int sensitivity_launch(lcqp_hip_batch* h, bool blk, int first, int count,
     if (int rc = sb.reserve(g_err, h->mem, h->stream, count, nrhs, d.n, d.np, (size_t)d.nd + (blk ? 2 : 1) * (size_t)d.capS, d.nd)) return rc;
     if (v) if (int rc = sb.upload(g_err, v)) return rc;
     const double* dv = v ? sb.v : nullptr;
+    if (vy) {      // (k_sensitivity<NCH, true> of lcqp_hip_batch_adjoint: the whole batch, vy [B][nrhs][nd] from the host)
+        if (int rc = grow(h, h->adjVy, h->adjVyCap, sb.rows * d.nd)) return rc;
+        HIPCHK(g_err, hipMemcpyAsync(h->adjVy, vy, sizeof(double) * sb.rows * d.nd, hipMemcpyHostToDevice, h->stream));
+    }
     HIPCHK(g_err, hipEventRecord(sb.ev0, h->stream));
     if (blk) h->k->sensitivity_blk(d, count, h->stream, first, nrhs, dv, sb.dg, sb.db, sb.side, sb.info);
+    else if (vy) h->k->sensitivity_dual(d, count, h->stream, nrhs, dv, h->adjVy, sb.dg, sb.db, sb.side, sb.info);
     else h->k->sensitivity(d, count, h->stream, nrhs, dv, sb.dg, sb.db, sb.side, sb.info);
     HIPCHK(g_err, hipGetLastError());
     HIPCHK(g_err, hipEventRecord(sb.ev1, h->stream));
@@ -760,6 +852,68 @@ extern "C" int lcqp_hip_batch_sensitivity_timing(lcqp_hip_batch_t* h, float* ker
 {
     return sensitivity_timing(h, kernel_ms);
 }
+
+// ---- the full adjoint (DESIGN.md section 3a''''): upstream gradients on x and y, gradients in g, the bounds and the matrices ----
+// k_sensitivity (with vy: its DUAL instantiation) on the whole batch, its results to the host; then, on the device buffers it left, the matrix
+// gradients that were asked for: k_adjoint_reduce once, or k_adjoint_outer per chunk of instances under the Jacobian staging cap.
+static int batch_adjoint(lcqp_hip_batch* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
+                         int reduce, double* dQ, double* dA, double* dL, double* dR)
+{
+    DevBatch& d = h->db;
+    float ms = 0.f;
+    if (int rc = sensitivity_launch(h, false, 0, d.B, 1, vx, dg, db, side, info, &ms, vy)) return rc;
+    const size_t n = d.n;
+    double* host[4] = {dQ, d.nC ? dA : nullptr, d.nComp ? dL : nullptr, d.nComp ? dR : nullptr};
+    const int r0[4] = {0, d.n, d.n + d.nC, d.n + d.nC + d.nComp}, rows[4] = {d.n, d.nC, d.nComp, d.nComp};
+    size_t perInst = 0;      // doubles of one instance's gradients
+    for (int k = 0; k < 4; k++) if (host[k]) perInst += (size_t)rows[k] * n;
+    if (perInst) {
+        const SensBuffers& sb = h->sens;
+        const AdjointArgs a = {d.B, d.n, d.np, d.nd, (int)sb.ldDb, d.xout, d.yout, sb.dg, sb.db, sb.side, sb.info};
+        for (hipError_t e : {h->adjEv0.status, h->adjEv1.status}) if (e != hipSuccess) return hip_fail(g_err, "hipEventCreate", e);
+        size_t chunk = 1;
+        if (!reduce) {
+            chunk = h->jacStaging / (sizeof(double) * perInst);
+            if (chunk < 1) chunk = 1;
+            if (chunk > (size_t)d.B) chunk = d.B;
+        }
+        if (int rc = grow(h, h->adjOut, h->adjOutCap, chunk * perInst + 4)) return rc;      // (+ 4: every segment starts on an even offset)
+        for (size_t c0 = 0; c0 < (reduce ? (size_t)1 : (size_t)d.B); c0 += chunk) {
+            const size_t cb = reduce ? 1 : std::min(chunk, (size_t)d.B - c0);
+            AdjointSegs segs{};
+            size_t off = 0, most = 0;
+            for (int k = 0; k < 4; k++) {
+                if (!host[k]) continue;
+                const size_t cnt = cb * rows[k] * n;
+                segs.s[k] = {h->adjOut + off, r0[k], rows[k]};
+                off += cnt + (cnt & 1);
+                most = std::max(most, cnt);
+            }
+            const unsigned gx = (unsigned)std::min<size_t>((most + 2 * WG - 1) / (2 * WG), 65535);
+            HIPCHK(g_err, hipEventRecord(h->adjEv0, h->stream));
+            if (reduce) hipLaunchKernelGGL(k_adjoint_reduce, dim3(gx, 4), dim3(WG), 0, h->stream, a, segs);
+            else hipLaunchKernelGGL(k_adjoint_outer, dim3(gx, 4), dim3(WG), 0, h->stream, a, segs, (int)c0, (int)cb);
+            HIPCHK(g_err, hipGetLastError());
+            HIPCHK(g_err, hipEventRecord(h->adjEv1, h->stream));
+            for (int k = 0; k < 4; k++)
+                if (host[k]) HIPCHK(g_err, hipMemcpyAsync(host[k] + c0 * rows[k] * n, segs.s[k].out, sizeof(double) * cb * rows[k] * n, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(g_err, hipStreamSynchronize(h->stream));
+            float t = 0.f;
+            HIPCHK(g_err, hipEventElapsedTime(&t, h->adjEv0, h->adjEv1));
+            ms += t;
+        }
+    }
+    h->rs.sensMs = ms;
+    return 0;
+}
+
+extern "C" int lcqp_hip_batch_adjoint(lcqp_hip_batch_t* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
+                                      int reduce, double* dQ, double* dA, double* dL, double* dR)
+{ return guarded(g_err, [&] {
+    if (!h || !vx || !dg || (reduce != 0 && reduce != 1)) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return batch_adjoint(h, vx, vy, dg, db, side, info, reduce, dQ, dA, dL, dR);
+}); }
 
 // =================================================================================================
 // QP object (SubsolverBase semantics): a batch of one with nComp = 0 whose rows are the nC stacked rows
@@ -944,6 +1098,15 @@ extern "C" int lcqp_hip_qp_sensitivity(lcqp_hip_qp_t* q, int nrhs, const double*
     if (!q || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
     if (!q->hb || !q->solved) return LCQP_LCQPOBJECT_NOT_SETUP;
     return batch_sensitivity(q->hb, false, nrhs, v, dg, db, side, info);
+}); }
+
+// the full adjoint on the batch of one (lcqp_hip_batch_adjoint): vy, db, side [nV + nC]; dQ [nV][nV], dA [nC][nV] (the stacked rows) may be NULL
+extern "C" int lcqp_hip_qp_adjoint(lcqp_hip_qp_t* q, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
+                                   double* dQ, double* dA)
+{ return guarded(g_err, [&] {
+    if (!q || !vx || !dg) return LCQP_INVALID_ARGUMENT;
+    if (!q->hb || !q->solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return batch_adjoint(q->hb, vx, vy, dg, db, side, info, 0, dQ, dA, nullptr, nullptr);
 }); }
 
 // the blocked twins on the batch of one (lcqp_hip_batch_sensitivity_blocked, lcqp_hip_batch_jacobian)

@@ -200,8 +200,11 @@ __device__ __forceinline__ void sens_marks(const DevBatch& db, Ctx<NCH>& c, Lds 
 //   v [B][nrhs][n];  dg [B][nrhs][np] (the work vector of the solves; -d on return, zero on the padding);
 //   dbo [B][nrhs][nd + capS]: nd derivatives in the reference's dual layout (box first), then capS slot-space scratch (lambda);
 //   side [B][nd]: 0 outside W, -1 at lower, +1 at upper, 2 equality;  sinfo [B]: flag bits (include/lcqp_hip.h), 0 = differentiable.
-template <int NCH>
-__global__ __launch_bounds__(WG) void k_sensitivity(DevBatch db, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo)
+// DUAL (DESIGN.md section 3a'''', lcqp_hip_batch_adjoint): an upstream gradient vy [B][nrhs][nd] on the returned duals, in their layout,
+// joins the right-hand side: lambda = Ti'Ti (Et_W c + vy_W), so that E_W d = -vy_W.  Entries of vy outside W are not read.  Without DUAL vy
+// is not read at all.
+template <int NCH, bool DUAL>
+__global__ __launch_bounds__(WG) void k_sensitivity(DevBatch db, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo, const double* vy)
 {
     LCQP_LDS_N(NCH)
     constexpr int np = 128 * NCH;
@@ -236,7 +239,12 @@ __global__ __launch_bounds__(WG) void k_sensitivity(DevBatch db, int nrhs, const
         wg_trsv<wg_ncopy(NCH) == 2>(c.F1, np, c.nblk, w, true, lds);
         if (nT > 0) {
             wg_rows<NCH, false, true>(c.Et, idx, ns, w, lam, nullptr, lds, [](int, double) {});
-            for (int a = t; a < nsp; a += WG) lam[a] = (a < ns && idx[a] >= 0) ? lam[a] : 0.0;
+            if constexpr (DUAL) {
+                const double* vyk = vy + ((size_t)b * nrhs + k) * nd;
+                for (int a = t; a < nsp; a += WG) lam[a] = (a < ns && idx[a] >= 0) ? lam[a] + vyk[pos(idx[a])] : 0.0;
+            } else {
+                for (int a = t; a < nsp; a += WG) lam[a] = (a < ns && idx[a] >= 0) ? lam[a] : 0.0;
+            }
             __syncthreads();
             ti_apply<NCH>(c, lam, lam, nT, ns);
             wg_rows<NCH>(c.Et, idx, ns, nullptr, nullptr, lam, lds, [&](int i, double s) { w[i] = w[i] - s; });
@@ -1197,7 +1205,10 @@ const SizeKernels& size_kernels()
                 hipLaunchKernelGGL((k_sensitivity_blk<NCH>), dim3(grid), dim3(WG), 0, s, db, first, nrhs, v, dg, dbo, side, sinfo);
             };
         t.sensitivity = [](const DevBatch& db, int grid, hipStream_t s, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo) {
-            hipLaunchKernelGGL((k_sensitivity<NCH>), dim3(grid), dim3(WG), 0, s, db, nrhs, v, dg, dbo, side, sinfo);
+            hipLaunchKernelGGL((k_sensitivity<NCH, false>), dim3(grid), dim3(WG), 0, s, db, nrhs, v, dg, dbo, side, sinfo, nullptr);
+        };
+        t.sensitivity_dual = [](const DevBatch& db, int grid, hipStream_t s, int nrhs, const double* v, const double* vy, double* dg, double* dbo, int* side, int* sinfo) {
+            hipLaunchKernelGGL((k_sensitivity<NCH, true>), dim3(grid), dim3(WG), 0, s, db, nrhs, v, dg, dbo, side, sinfo, vy);
         };
         t.build_C = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_build_C<NCH>), dim3(grid), dim3(WG), 0, s, db); };
         t.compress_C = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_compress_C<NCH>), dim3(grid), dim3(WG), 0, s, db); };

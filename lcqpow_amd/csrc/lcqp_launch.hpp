@@ -30,8 +30,10 @@ struct SizeKernels {
     void (*synth_fill)(const DevBatch& db, int grid, hipStream_t s, uint64_t seed0, uint64_t first);
     BatchKernel synth_Q;
     // device buffers, layouts at the kernels.  sensitivity: the whole batch.  sensitivity_blk: workgroup o works on instance first + o,
-    // v null: unit vectors; null for NCH > 4 (a panel of np >= 1024 does not fit LDS)
+    // v null: unit vectors; null for NCH > 4 (a panel of np >= 1024 does not fit LDS).  sensitivity_dual: k_sensitivity<NCH, true>, which adds
+    // the upstream gradients vy [B][nrhs][nd] on the duals to the right-hand side
     void (*sensitivity)(const DevBatch& db, int grid, hipStream_t s, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo);
+    void (*sensitivity_dual)(const DevBatch& db, int grid, hipStream_t s, int nrhs, const double* v, const double* vy, double* dg, double* dbo, int* side, int* sinfo);
     void (*sensitivity_blk)(const DevBatch& db, int grid, hipStream_t s, int first, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo);
     // building-block kernels
     void (*util_symv)(int grid, hipStream_t s, int n, double alpha, const double* A, const double* b, const double* c, double* d);

@@ -9,6 +9,11 @@ hot path.
     layer = BatchLCQPLayer(bt, bounds=dict(lbA=lbA, ubA=ubA))
     x = layer(g)                      # [B][nV], on g's device; update + run the first time, update + resolve(warm) afterwards
     loss(x).backward()                # g.grad = dl/dg through the working set the solve ended on
+
+The full adjoint (lcqp_hip_batch_adjoint, DESIGN.md section 3a''''; dense arm) also returns the duals and differentiates in the matrices:
+
+    x, y = layer.solve(g, Q=Q, A=A)   # Q [nV][nV] shared by the batch (or [B][nV][nV] per instance), likewise A, L, R
+    loss(x, y).backward()             # g.grad, Q.grad, A.grad
 """
 import warnings
 
@@ -78,6 +83,90 @@ class LCQPSolveFunction(torch.autograd.Function):
         return None, out(dg), glb, gub
 
 
+MATRIX_KEYS = ("Q", "A", "L", "R")
+
+
+class LCQPFullSolveFunction(torch.autograd.Function):
+    """forward(layer, g, Q, A, L, R, lbA, ubA) -> (x, y).  Without matrix tensors: update + run / resolve(warm), as LCQPSolveFunction.  With
+    one: lcqp_hip_batch_load of the whole batch + run; a tensor of shape [B][..][nV] holds one matrix per instance, one of shape [..][nV] is
+    shared by the batch (broadcast at the load); a matrix that is not given is the one the batch holds.
+    backward: lcqp_hip_batch_adjoint with the upstream gradients on x and on y -- gradients for g, for lbA / ubA where they were tensors (the
+    rules of LCQPSolveFunction), and for the matrix tensors: per instance (reduce = 0) or, for a shared tensor, summed over the batch on the
+    device (reduce = 1).  Flagged instances: the one warning of LCQPSolveFunction."""
+
+    @staticmethod
+    def forward(ctx, layer, g, Q=None, A=None, L=None, R=None, lbA=None, ubA=None):
+        bt = layer.bt
+        kw = dict(layer.bounds)
+        if lbA is not None: kw["lbA"] = _host(lbA)
+        if ubA is not None: kw["ubA"] = _host(ubA)
+        given = dict(zip(MATRIX_KEYS, (Q, A, L, R)))
+        rows = dict(Q=bt.nV, A=bt.nC, L=bt.nComp, R=bt.nComp)
+        shared = {}
+        for k, t in given.items():
+            if t is None:
+                continue
+            if tuple(t.shape) not in ((bt.B, rows[k], bt.nV), (rows[k], bt.nV)):
+                raise ValueError(f"{k}: expected [{bt.B}][{rows[k]}][{bt.nV}] or [{rows[k]}][{bt.nV}], got {tuple(t.shape)}")
+            shared[k] = t.dim() == 2
+        if shared:
+            held = layer._matrices()
+            for k, t in given.items():
+                if t is not None:
+                    held[k] = np.ascontiguousarray(np.broadcast_to(_host(t), (bt.B, rows[k], bt.nV)))
+            rc = bt.load(0, bt.B, held["Q"], _host(g), held["L"], held["R"], A=held["A"], **kw)
+            if rc != 0:
+                raise RuntimeError(f"load failed with code {rc}: {bt._last_error()}")
+            bt.run()
+        else:
+            rc = bt.update(0, bt.B, _host(g), **kw)
+            if rc != 0:
+                raise RuntimeError(f"update failed with code {rc}: {bt._last_error()}")
+            if layer.solves == 0:
+                bt.run()
+            else:
+                bt.resolve(warm=layer.warm)
+        x, y, st = bt.solution()
+        layer.solves += 1
+        layer.y, layer.stats = y, st
+        layer._like = (g.dtype, g.device)
+        ctx.layer, ctx.serial = layer, layer.solves
+        ctx.given = (lbA is not None, ubA is not None)
+        ctx.shared = shared
+        out = lambda a: torch.as_tensor(a, dtype=g.dtype, device=g.device)
+        return out(x), out(y)
+
+    @staticmethod
+    def backward(ctx, grad_x, grad_y):
+        layer = ctx.layer
+        if ctx.serial != layer.solves:
+            raise RuntimeError("backward through a solve that is not the layer's last one: the batch object holds the state of one solve")
+        bt = layer.bt
+        vx, vy = _host(grad_x), _host(grad_y)
+        each = tuple(k for k, sh in ctx.shared.items() if not sh)
+        summed = tuple(k for k, sh in ctx.shared.items() if sh)
+        r = bt.adjoint(vx, vy, matrices=each, reduce=False)
+        mats = {k: r[k] for k in each}
+        if summed:
+            rs = bt.adjoint(vx, vy, matrices=summed, reduce=True)
+            mats.update({k: rs[k] for k in summed})
+        dg, db, side, info = r["dg"], r["db"], r["side"], r["info"]
+        layer.info = info
+        bad = int(np.count_nonzero(info))
+        if bad:
+            warnings.warn(f"LCQPFullSolveFunction.backward: {bad} of {bt.B} instances are not differentiable by the library's criteria "
+                          f"(info bits present: {int(np.bitwise_or.reduce(info))}); their gradients are the kernel's output as it is",
+                          RuntimeWarning, stacklevel=2)
+        out = lambda a: torch.as_tensor(a, dtype=grad_x.dtype, device=grad_x.device)
+        parts = capi.split_bound_derivatives(db, side, bt.nV, bt.nC, bt.nComp)
+        eq = side[:, bt.nV:bt.nV + bt.nC] == 2
+        share = np.where(eq, 0.5, 1.0) if all(ctx.given) else 1.0
+        glb = out(parts["dlbA"] * share) if ctx.given[0] else None
+        gub = out(parts["dubA"] * share) if ctx.given[1] else None
+        gm = [out(mats[k]) if k in mats else None for k in MATRIX_KEYS]
+        return (None, out(dg), *gm, glb, gub)
+
+
 class BatchLCQPLayer:
     """A loaded BatchLCQP as a torch layer.  bounds: the bound vectors the batch was loaded with ([B][...] arrays under the names of
     BatchLCQP.update: lbL, ubL, lbR, ubR, lbA, ubA, lb, ub) -- an update replaces EVERY vector, so the ones that are not inputs of the
@@ -94,9 +183,26 @@ class BatchLCQPLayer:
         self.bt, self.warm, self.solves = batch, warm, 0
         self.bounds = {k: capi._arr(v) for k, v in (bounds or {}).items() if v is not None}
         self.y = self.stats = self.info = None
+        self._held = None
 
     def __call__(self, g, lbA=None, ubA=None):
         return LCQPSolveFunction.apply(self, g, lbA, ubA)
+
+    def solve(self, g, Q=None, A=None, L=None, R=None, lbA=None, ubA=None):
+        """(x, y) of the batch for the linear terms g, both differentiable (LCQPFullSolveFunction; dense arm): y [B][nV + nC + 2 nComp] in
+        the reference's dual layout.  Q, A, L, R: tensors that replace the matrices of the batch for this and later solves -- [B][..][nV]
+        one per instance, [..][nV] one shared by all instances (its gradient is the sum over the batch).  Without any, the solve is the
+        update + resolve of __call__."""
+        if self.sparse:
+            raise RuntimeError("solve: only the dense arm has the full adjoint")
+        return LCQPFullSolveFunction.apply(self, g, Q, A, L, R, lbA, ubA)
+
+    def _matrices(self):
+        """the matrices the batch holds, [B][..][nV] each: read back once, then kept in step with the loads of solve"""
+        if self._held is None:
+            ps = [self.bt.read_problem(b) for b in range(self.bt.B)]
+            self._held = {k: np.stack([p[k] for p in ps]) for k in MATRIX_KEYS}
+        return self._held
 
     def jacobian(self, serial=None):
         """dx/dg of the layer's last solve, [B][nV][nV] ([b][k][j] = dx_k/dg_j), a tensor of the dtype and on the device of that

@@ -13,10 +13,16 @@ data (refresh + homotopy, last_timing) -- the unit a finite-difference gradient 
 --blocked: k_sensitivity_blk (lcqp_hip_batch_sensitivity_blocked) beside k_sensitivity on the same handle in the same process, the calls
 interleaved, for nrhs = 1, 16, 64, 256 on the BASELINE shape (B = 1024, n = 256, nC = 512, nComp = 64) and on (40, 20, 8) with B = 1024;
 then jacobian() beside the vector call on an uploaded identity, kernel time and wall clock.
-    python tools/sensitivity_timing.py --blocked [--quick] [--log FILE] [--reps 20]"""
+    python tools/sensitivity_timing.py --blocked [--quick] [--log FILE] [--reps 20]
+
+--adjoint: lcqp_hip_batch_adjoint with all four matrix gradients on the BASELINE shape and on (40, 20, 8), B = 1024 (256 with --quick):
+reduce = 1 (k_adjoint_reduce, (nV + mA) nV doubles to the host) beside reduce = 0 (k_adjoint_outer in chunks, B times as many) on the same
+handle in the same process, the calls interleaved; kernel time (the sum of the call's kernels, k_sensitivity included) and wall clock.
+    python tools/sensitivity_timing.py --adjoint [--quick] [--log FILE] [--reps 20]"""
 import argparse
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -127,6 +133,40 @@ def measure_blocked(B, n, nC, nComp, nrhs_list, reps, warmup=3):
     return lines
 
 
+def measure_adjoint(B, n, nC, nComp, reps, warmup=3):
+    bt = la.BatchLCQP(B, n, nC, nComp, opt=la.default_options())
+    bt.generate_synthetic(0)
+    bt.run()
+    rng = np.random.default_rng(0)
+    vx, vy = rng.standard_normal((B, n)), rng.standard_normal((B, n + nC + 2 * nComp))
+    ms = {False: [], True: []}; wall = {False: [], True: []}
+    for r in range(warmup + reps):
+        for reduce in (True, False):      # interleaved: both see the same drift of the clocks
+            t0 = time.perf_counter()
+            out = bt.adjoint(vx, vy, reduce=reduce)
+            t1 = time.perf_counter()
+            if r >= warmup:
+                ms[reduce].append(bt.sensitivity_kernel_ms()); wall[reduce].append(1e3 * (t1 - t0))
+    bt.close()
+    q = lambda a: (float(np.min(a)), float(np.median(a)), float(np.max(a)))
+    line = "n = %d nC = %d nComp = %d B = %d:" % (n, nC, nComp, B)
+    for reduce in (True, False):
+        line += " reduce = %d kernels ms min / median / max = %.4f / %.4f / %.4f, wall ms = %.2f / %.2f / %.2f;" % ((int(reduce),) + q(ms[reduce]) + q(wall[reduce]))
+    line += " flagged %d" % int(np.count_nonzero(out["info"]))
+    print(line, flush=True)
+    return line
+
+
+def adjoint_main(a):
+    B = 256 if a.quick else 1024
+    lines = [measure_adjoint(B, n, nC, nComp, a.reps) for n, nC, nComp in ((40, 20, 8), (256, 512, 64))]
+    if a.log:
+        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
+        with open(a.log, "w") as f:
+            f.write("lcqp_hip_batch_adjoint, reduce = 1 beside reduce = 0, synthetic workload after run, one handle, calls interleaved; %d timed calls after 3 warm-up calls each\n" % a.reps)
+            f.write("\n".join(lines) + "\n")
+
+
 def blocked_main(a):
     lines = []
     nr = (1, 16, 64) if a.quick else (1, 16, 64, 256)
@@ -164,6 +204,7 @@ def main():
     ap.add_argument("--sparse", action="store_true", help="the sparse arm's kernel beside a warm resolve of unchanged data")
     ap.add_argument("--quick", action="store_true", help="--sparse: without the n = 4096, B = 4096 batch; --blocked: B = 256 at n = 256, without nrhs = 256")
     ap.add_argument("--blocked", action="store_true", help="the blocked kernel beside the vector kernel, and the Jacobian")
+    ap.add_argument("--adjoint", action="store_true", help="the matrix gradients summed on the device beside the per-instance path")
     a = ap.parse_args()
     if la.device_count() < 1:
         raise SystemExit("needs a GPU (no CPU fallback)")
@@ -171,6 +212,8 @@ def main():
         return sparse_main(a)
     if a.blocked:
         return blocked_main(a)
+    if a.adjoint:
+        return adjoint_main(a)
     lines = []
     for B, nrhs in ((1024, 1), (1024, 8), (1, 1), (1, 8)):
         r = measure(B, nrhs, a.reps)
