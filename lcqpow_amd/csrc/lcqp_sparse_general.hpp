@@ -10,7 +10,7 @@
 //     are the boundary of the region it closes -- the later nodes adjacent to the region --, taken as dense (the fill of eliminating a connected
 //     region IS the clique on its boundary; a few explicit zeros stand where a separator node does not touch every boundary node).  The
 //     front tree is the dissection tree; fronts are numbered in postorder, children before parents.
-//   * Numeric (device: sp_general_factor / sp_general_solve in lcqp_sparse.hip; CPU restatement of the same loops for the tests:
+//   * Numeric (device: sp_general_factor / sp_general_solve in lcqp_sparse_factor.hpp; CPU restatement of the same loops for the tests:
 //     tests/cpp/general_ldl_test.cpp): a front F (ff x ff, ff = np + nb) is zeroed, takes the entries of K whose column is one of its pivots
 //     (asm lists below; entries of E are gated by the working set by VALUE, the pattern never changes), takes the update blocks of its
 //     children (extend-add through `rel`), eliminates its np pivots (right-looking, no pivoting: the matrix is quasi-definite for

@@ -1,7 +1,7 @@
 // lcqp_sparse_host.hip -- the host side of the sparse arm: the C ABI lcqp_hip_sparse_* (include/lcqp_hip.h).  The handle, the pattern
 // analysis (lcqp_sparse_pattern.hpp) and the storage of a batch in create, load / update / run / resolve, sensitivities, the readers,
 // and the LCQP_SPARSE_* environment test hooks.  No kernel is defined here: they are in lcqp_sparse.hip, one translation unit per lane-group
-// width G, reached through the launch functions of lcqp_sparse_launch.hpp.
+// width G, reached through the launch tables of lcqp_sparse_launch.hpp.
 #include "lcqp_sparse_launch.hpp"
 #include "lcqp_sparse_pattern.hpp"
 #include "lcqp_host_rt.hpp"
@@ -24,6 +24,7 @@ extern "C" const char* lcqp_hip_sparse_last_error(void) { return g_sp_err.c_str(
 struct lcqp_hip_sparse {
     SpBatch db;
     int device;
+    int cus = 0;                   // compute units of `device` (create): bounds the persistent wavefronts of a run
     Stream stream;
     Event ev0, ev1, ev2;           // run: setup from ev0 to ev1, homotopy from ev1 to ev2
     DevMem mem{stream};            // zero-fills on the handle's stream
@@ -57,6 +58,15 @@ static void sp_choose_ordering(lcqp_hip_sparse* h)
     h->useB = k;
 }
 
+// the launch table of a lane-group width, one per kernel translation unit; null for a width that has none (the pattern analysis gives 8,
+// 16, 32 or 64, and create refuses anything else)
+static const SpKernels* sp_kernels(int G)
+{
+    static const SpKernels* const units[] = {&sparse_kernels<8>(), &sparse_kernels<16>(), &sparse_kernels<32>(), &sparse_kernels<64>()};
+    for (const SpKernels* u : units) if (u->G == G) return u;
+    return nullptr;
+}
+
 // the pattern analysis (lcqp_sparse_pattern.hpp), then the device copies of its arrays and the storage of the batch
 extern "C" lcqp_hip_sparse_t* lcqp_hip_sparse_create(int batch, int nV, int nC, int nComp, const int* Qp, const int* Qi, const int* Ap, const int* Ai, int device)
 { return guarded(g_sp_err, [&]() -> lcqp_hip_sparse_t* {
@@ -69,11 +79,13 @@ extern "C" lcqp_hip_sparse_t* lcqp_hip_sparse_create(int batch, int nV, int nC, 
     const int n = P.n, m = P.m, N = P.N, nnzQ = P.nnzQ, nnzA = P.nnzE, w = P.w, G = P.G, ld = G, kb = P.kb;
     const int nU = (int)P.Usrc.size(), nCb = (int)P.Csrc.size();
     const bool general = P.general;
+    if (!sp_kernels(G)) { g_sp_err = "the pattern analysis chose a lane-group width that has no kernel unit"; return nullptr; }
     const lcqp_general::Symbolic& sym = P.sym;
     if (hipError_t e = hipSetDevice(device)) { hip_fail(g_sp_err, "hipSetDevice failed", e); return nullptr; }
     std::unique_ptr<lcqp_hip_sparse> h(new lcqp_hip_sparse(device));
     for (hipError_t e : {h->stream.status, h->ev0.status, h->ev1.status, h->ev2.status})
         if (e != hipSuccess) { hip_fail(g_sp_err, "stream/event creation", e); return nullptr; }
+    if (hipError_t e = hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device)) { hip_fail(g_sp_err, "hipDeviceGetAttribute(multiprocessor count)", e); return nullptr; }
     h->csr2csc = P.csr2csc; h->hasB = P.hasB; h->qdiagHost = P.qdiag; h->diagRatio.assign(batch, 1.0); h->rs.filled.assign(batch, 0);
     SpBatch& d = h->db;
     d.B = batch; d.n = n; d.m = m; d.nC = nC; d.nComp = nComp; d.N = N; d.Np = ((N + 63) / 64) * 64; d.w = w; d.ld = ld; d.nnzQ = nnzQ; d.nnzE = nnzA; d.G = G; d.kb = kb; d.nU = nU; d.nCb = nCb;
@@ -171,6 +183,7 @@ extern "C" lcqp_hip_sparse_t* lcqp_hip_sparse_create(int batch, int nV, int nC, 
         while ((size_t)(2 * pool) * perInst < ((size_t)1 << 32) && pool < batch) pool *= 2;
         if (const char* e = std::getenv("LCQP_SPARSE_POOL")) { const int v = std::atoi(e); if (v >= 1 && v < pool && (v & (v - 1)) == 0) pool = v; }      // test hook: several small pools
         d.poolSize = pool; d.nPools = (batch + pool - 1) / pool;
+        d.wideDiv = std::max(1, h->cus * 4 / std::max(1, d.nPools));      // SIMDs of the device per pool
         ok = ok && mm.alloc(err, d.state, B) && mm.alloc(err, d.qring, (size_t)d.nPools * PH_NUM * pool) &&
              mm.alloc(err, d.qctl, (size_t)d.nPools * (PH_NUM + 1) * QCTL) && mm.alloc(err, d.qprof, (PH_NUM + 1) * 3);
     }
@@ -259,22 +272,12 @@ extern "C" int lcqp_hip_sparse_sched_profile(lcqp_hip_sparse_t* h, unsigned long
     return 0;
 }); }
 
-// the kernel translation unit of a lane-group width (the pattern analysis gives 8, 16, 32 or 64)
-struct SpLaunchers { int G; SpRunFn* run; SpSensitivityFn* sensitivity; };
-static const SpLaunchers& sp_launchers(int G)
-{
-    static const SpLaunchers units[] = {{8, lcqp_sparse_launch_8, lcqp_sparse_sensitivity_8}, {16, lcqp_sparse_launch_16, lcqp_sparse_sensitivity_16},
-                                        {32, lcqp_sparse_launch_32, lcqp_sparse_sensitivity_32}, {64, lcqp_sparse_launch_64, lcqp_sparse_sensitivity_64}};
-    for (const SpLaunchers& u : units) if (u.G == G) return u;
-    return units[3];
-}
-
 // the launches of a run or a re-solve on the handle's stream: the setup (or the refresh) from ev0 to ev1, the homotopy from ev1 to ev2
 static int sp_run(lcqp_hip_sparse* h, bool refresh, int mode, const double* rho0)
 {
     h->rs.invalidate();
     HIPCHK(g_sp_err, hipEventRecord(h->ev0, h->stream));
-    sp_launchers(h->db.G).run(h->db, h->stream, h->ev1, refresh, mode, rho0);
+    sp_kernels(h->db.G)->run(h->db, h->cus, h->stream, h->ev1, refresh, mode, rho0);
     if (!refresh) h->rs.nSetups++;
     h->rs.nLaunches++;
     HIPCHK(g_sp_err, hipGetLastError());
@@ -355,7 +358,7 @@ extern "C" int lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* h, int nrhs, const
     if (int rc = sb.reserve(g_sp_err, h->mem, h->stream, d.B, nrhs, d.n, d.n, d.m, d.m)) return rc;
     if (int rc = sb.upload(g_sp_err, v)) return rc;
     HIPCHK(g_sp_err, hipEventRecord(sb.ev0, h->stream));
-    sp_launchers(d.G).sensitivity(d, h->stream, nrhs, sb.v, sb.dg, sb.db, sb.side, sb.info);
+    sp_kernels(d.G)->sensitivity(d, h->stream, nrhs, sb.v, sb.dg, sb.db, sb.side, sb.info);
     HIPCHK(g_sp_err, hipGetLastError());
     HIPCHK(g_sp_err, hipEventRecord(sb.ev1, h->stream));
     if (int rc = sb.download(g_sp_err, dg, db, side, info, d.n, d.m)) return rc;

@@ -1,6 +1,7 @@
 // lcqp_sparse_launch.hpp -- the seam between the host translation unit of the sparse arm (lcqp_sparse_host.hip: the C ABI lcqp_hip_sparse_*)
 // and its kernel translation units (lcqp_sparse.hip, one per lane-group width G in {8,16,32,64}): the batch as the kernels see it, the
-// constants both sides index it with, and the launch functions.  Plain structs and declarations only: no device code lives here.
+// constants both sides index it with, and the table of launch functions of a width.  Plain structs and declarations only: no device code
+// lives here.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/lcqp_hip.h"
@@ -102,7 +103,7 @@ struct SpBatch {
     unsigned long long* qring;  // [nPools][PH_NUM][poolSize] ring slots: (sequence number << 32) | instance id, one 64-bit word so that a slot changes hands in one store
     int* qctl;                  // [nPools][PH_NUM + 1][QCTL]
     int poolSize, nPools;
-    int wideDiv;                // SIMDs of the device per pool (sp_launch): unfinished instances of the pool / wideDiv = instances of a streaming step
+    int wideDiv;                // SIMDs of the device per pool (lcqp_hip_sparse_create): unfinished instances of the pool / wideDiv = instances of a streaming step
     // General sparse LDL' (round 6; lcqp_sparse_general.hpp): patterns that are neither banded nor bordered -- multifrontal over a nested-
     // dissection tree with dense fronts, one wavefront per instance (G = 64).  general != 0: KaF / KpF hold the panels of the fronts
     // (gLsize doubles per instance instead of Np * G), KaD / KpD 1 / D per position as for the band; kb = 0, lightOK = 0.
@@ -121,14 +122,16 @@ struct SpBatch {
 
 constexpr int GEN_META = 12;      // ints per front of SpBatch::gMeta
 
-// The launch functions, defined in lcqp_sparse.hip for G = LCQP_TU_G.
+// Per lane-group width one table of launch functions, as lcqp_launch.hpp has one per padded size.
 // SpRunFn: the launches of a run on `stream` -- k_sparse_setup<G>, or with `refresh` k_sparse_refresh<G>(mode, rho0) in its place, `mid`
-// recorded behind it, then the homotopy (k_sparse_sched_init, k_sparse_sched<G>).
+// recorded behind it, then the homotopy (k_sparse_sched_init, k_sparse_sched<G>).  cus: compute units of the device the batch lives on
+// (the persistent wavefronts of k_sparse_sched are at most what it holds at once).
 // SpSensitivityFn: one launch of k_sparse_sensitivity<G> on `stream` over device buffers (layouts at the kernel).
-using SpRunFn = void(const SpBatch& db, hipStream_t stream, hipEvent_t mid, bool refresh, int mode, const double* rho0);
+using SpRunFn = void(const SpBatch& db, int cus, hipStream_t stream, hipEvent_t mid, bool refresh, int mode, const double* rho0);
 using SpSensitivityFn = void(const SpBatch& db, hipStream_t stream, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo);
-SpRunFn lcqp_sparse_launch_8, lcqp_sparse_launch_16, lcqp_sparse_launch_32, lcqp_sparse_launch_64;
-SpSensitivityFn lcqp_sparse_sensitivity_8, lcqp_sparse_sensitivity_16, lcqp_sparse_sensitivity_32, lcqp_sparse_sensitivity_64;
+struct SpKernels { int G; SpRunFn* run; SpSensitivityFn* sensitivity; };
+// defined in lcqp_sparse.hip and instantiated there for G = LCQP_TU_G
+template <int G> const SpKernels& sparse_kernels();
 #pragma GCC visibility pop
 
 }  // namespace lcqp_sparse

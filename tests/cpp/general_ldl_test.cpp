@@ -1,5 +1,5 @@
 // CPU check of the general sparse LDL' of the sparse arm (lcqpow_amd/csrc/lcqp_sparse_general.hpp): the symbolic analysis, and a scalar restatement
-// of the numeric loops the device runs (sp_general_factor / sp_general_solve in lcqp_sparse.hip: same fronts, same order of operations), against a
+// of the numeric loops the device runs (sp_general_factor / sp_general_solve in lcqp_sparse_factor.hpp: same fronts, same order of operations), against a
 // dense LDL' solve of the same KKT matrix.  usage: general_ldl_test [grid size] [leaf]      (no GPU; run by tests/test_general_ldl.py)
 #include <cmath>
 #include <cstdio>
