@@ -398,6 +398,27 @@ int  lcqp_hip_sparse_launch_counts(lcqp_hip_sparse_t* s, int out[2]);   /* full 
 int  lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* s, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
 /* kernel time of the last lcqp_hip_sparse_sensitivity launch of this handle, ms (HIP events around k_sparse_sensitivity, the copies excluded) */
 int  lcqp_hip_sparse_sensitivity_timing(lcqp_hip_sparse_t* s, float* kernel_ms);
+/* Test and diagnostic entry point (as lcqp_hip_batch_read_setup / _read_working_set on the dense arm): the KKT factorisations and solves
+ * of the sparse arm -- the register band, the LDS-window band, the bordered band, the general LDL' -- run for every instance of the batch
+ * on matrices the caller names, one solve per right-hand side and NO refinement, so that tests/test_gpu_sparse_factor.py can hold each engine
+ * to a plain reference.  One launch of k_sparse_kkt_probe on the handle's stream; the handle is synchronised first, the call is synchronous.
+ *   rhs, sol   [B][nrhs][nV + nC + 2 nComp] (host) in NODE order: the variables, then the rows of E = [A; L; R]
+ * mode LCQP_KKT_PROBE_FACTOR: dprim [B], ddual [B][m], use [B][m] (0 / 1), m = nC + 2 nComp.  [Q + dprim I, E_use'; E_use, -diag(ddual)] is
+ *   factorised into the polish slot -- a row outside `use` gets the diagonal -1 and no entries -- by exactly the pieces a run composes, then
+ *   solved with.  `which` and the record buffers are ignored.  THE STORED POLISH FACTOR IS OVERWRITTEN: afterwards
+ *   lcqp_hip_sparse_sensitivity answers LCQP_LCQPOBJECT_NOT_SETUP and a warm lcqp_hip_sparse_resolve starts every instance cold, until the next
+ *   run / resolve.
+ * mode LCQP_KKT_PROBE_STORED: no factorisation; the solves run with the factor of slot `which` (0: the polish slot, 1: the ADMM slot) as the
+ *   last run / resolve left it, and the record of the matrix that factor is the factor of comes back in the layout of the FACTOR inputs:
+ *   rec_dprim [B], rec_ddual [B][m], rec_use [B][m] -- polish: the regularisation pair of the last factorisation and its working set; ADMM:
+ *   sigma, 1 / rho_r, all ones.  dprim, ddual, use are ignored.  Changes nothing a run reads.
+ * LCQP_INVALID_ARGUMENT: nrhs < 1, NULL rhs or sol, a mode other than the two, FACTOR with a NULL input, STORED with `which` outside 0 / 1 or a
+ * NULL record buffer.  Then LCQP_LCQPOBJECT_NOT_SETUP: NULL handle, no run / resolve on this handle yet or a load / set_options since (the band
+ * rows the register engine streams exist only behind one), STORED on the polish slot behind a FACTOR call.  LCQP_HIP_ERROR: a HIP call failed. */
+#define LCQP_KKT_PROBE_FACTOR 0
+#define LCQP_KKT_PROBE_STORED 1
+int  lcqp_hip_sparse_kkt_probe(lcqp_hip_sparse_t* s, int mode, int which, int nrhs, const double* dprim, const double* ddual, const int* use,
+                               const double* rhs, double* sol, double* rec_dprim, double* rec_ddual, int* rec_use);
 int  lcqp_hip_sparse_synchronize(lcqp_hip_sparse_t* s);
 int  lcqp_hip_sparse_last_timing(lcqp_hip_sparse_t* s, float* setup_ms, float* solve_ms);
 int  lcqp_hip_sparse_get_solution(lcqp_hip_sparse_t* s, double* x, double* y, lcqp_stats_t* stats);   /* y: [B][nC + 2 nComp] */

@@ -150,6 +150,8 @@ def lib():
         L.lcqp_hip_sparse_launch_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.lcqp_hip_sparse_sensitivity.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_sparse_sensitivity_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.lcqp_hip_sparse_kkt_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p,
+                                                c_double_p, c_double_p, c_int_p]
         _lib = L
     return _lib
 
@@ -801,6 +803,33 @@ class SparseBatchLCQP(_Batch):
         perm = np.zeros(self.nV + self.m, dtype=np.int32)
         self._call("get_ordering", _ip(perm))
         return perm
+
+    def kkt_probe(self, rhs, dprim=None, ddual=None, use=None, which=None):
+        """Test and diagnostic entry point (lcqp_hip_sparse_kkt_probe; after a completed run / resolve): solves with a KKT factorisation of
+        every instance, one solve per right-hand side, no refinement.  rhs [B][nrhs][nV + m] in node order (variables, then the rows of
+        [A; L; R]); returns the solutions in the same shape.
+        FACTOR mode (dprim [B], ddual [B][m], use [B][m] 0/1 given): factorises [Q + dprim I, E_use'; E_use, -diag(ddual)] (a row outside use:
+        diagonal -1, no entries) into the polish slot first.  That overwrites the stored polish factor: sensitivity() then answers 300 and
+        a warm resolve starts cold.  Returns sol.
+        STORED mode (which = 0: the polish slot, 1: the ADMM slot): the factor as the last run left it.  Returns (sol, record) with
+        record = dict(dprim [B], ddual [B][m], use [B][m]): the matrix that factor is the factor of."""
+        B, N, m = self.B, self.nV + self.m, self.m
+        rhs = _arr(rhs)
+        if rhs.ndim != 3 or rhs.shape[0] != B or rhs.shape[2] != N or rhs.shape[1] < 1:
+            raise ValueError(f"rhs: expected [{B}][nrhs][{N}], got shape {rhs.shape}")
+        sol = np.zeros_like(rhs)
+        if which is None:
+            dp = _sized("dprim", _arr(dprim), B); dd = _sized("ddual", _arr(ddual), B * m)
+            if dp is None or dd is None or use is None:
+                raise ValueError("FACTOR mode needs dprim, ddual and use; STORED mode needs which")
+            us = np.ascontiguousarray(use, dtype=np.int32)
+            if us.size != B * m:
+                raise ValueError(f"use: expected {B * m} values, got {us.size}")
+            self._call("kkt_probe", 0, 0, rhs.shape[1], _p(dp), _p(dd), _ip(us), _p(rhs), _p(sol), None, None, None)
+            return sol
+        rp = np.zeros(B); rd = np.zeros((B, m)); ru = np.zeros((B, m), dtype=np.int32)
+        self._call("kkt_probe", 1, int(which), rhs.shape[1], None, None, None, _p(rhs), _p(sol), _p(rp), _p(rd), _ip(ru))
+        return sol, dict(dprim=rp, ddual=rd, use=ru)
 
     def load(self, first, count, Qx, g, Ax, lbA=None, ubA=None, lbL=None, ubL=None, lbR=None, ubR=None, x0=None, y0=None):
         n, nC, nK = self.nV, self.nC, self.nComp

@@ -27,7 +27,7 @@
 //   lcqp_sparse_lane.hpp     the lane-group model: addressing, SpCtx, collectives, g_map, g_ell       (dense: lcqp_wg.hpp)
 //   lcqp_sparse_factor.hpp   assembly, the three factorisation engines, sweeps, border, sp_solve
 //   lcqp_sparse_solver.hpp   products, ADMM, polish, the phases of the homotopy, the setup's pieces  (dense: lcqp_dev.hpp)
-//   lcqp_sparse.hip          this file: the setup / refresh / sensitivity kernels, the queue scheduler, the launches and their table
+//   lcqp_sparse.hip          this file: the setup / refresh / sensitivity / probe kernels, the queue scheduler, the launches and their table
 //                                                                                                    (dense: lcqp_kernels.hpp / lcqp_nch.hip)
 #include "lcqp_sparse_solver.hpp"
 
@@ -242,6 +242,74 @@ __global__ __launch_bounds__(WGS) void k_sparse_sensitivity(SpBatch db, int nrhs
         g_sync();
     }
     if (t == 0) sinfo[b] = (stalled ? 2 : 0) | (weak ? 4 : 0) | (open ? 8 : 0);
+}
+
+// ---- k_sparse_kkt_probe: test and diagnostic kernel (lcqp_hip_sparse_kkt_probe) -- the factorisation engines and sp_solve held to a plain
+// reference, one solve per right-hand side, no refinement (tests/test_gpu_sparse_factor.py) ------------------------------------------------
+// rhs, sol [B][nrhs][N] in NODE order (variables, then the rows of E); the solve vector is filled through iperm as sp_ph_correct fills it,
+// its padding positions are zero.
+// mode 0 (FACTOR): [Q + dprim[b] I, E_use'; E_use, -diag(ddual[b])] (use [B][m], 0 / 1; a row outside: diagonal -1, no entries) is factorised
+// into the POLISH slot by the pieces sp_ph_factor / sp_ph_correct compose -- the working set as a bit set in LDS (G <= 16, bitWords > 0),
+// sp_factor_band, sp_border_prepare, the kb columns of W through sp_solve_band, sp_border_schur.  The stored polish factor is gone after it:
+// haveSolution, stfValid and fact_valid are cleared (a warm re-solve starts this instance cold; the host clears its own mark).
+// mode 1 (STORED): no factorisation; the factor of slot `which` (0 polish, 1 ADMM) as the last run left it, and the record of the matrix it
+// is the factor of: recP [B], recD [B][m], recU [B][m] -- polish: S.dpUsed, S.d2Used on every row, MI_STF != ST_INACT; ADMM: sigma,
+// 1 / rhov[r], ones.  Writes its outputs and the solve vector only.
+template <int G>
+__global__ __launch_bounds__(WGS) void k_sparse_kkt_probe(SpBatch db, int mode, int which, int nrhs, const double* dprim, const double* ddual, const int* use,
+                                                          const double* rhs, double* sol, double* recP, double* recD, int* recU)
+{
+    const int b = blockIdx.x * (64 / G) + threadIdx.x / G;
+    if (b >= db.B) return;
+    SpCtx<G> c = sp_ctx<G>(db, b, blockIdx.x * (64 / G), (int)threadIdx.x);
+    const int t = c.gl, m = db.m, N = db.N;
+    const int* iperm = db.iperm;
+    const bool admm = mode == 1 && which == 1;
+    if (mode == 0) {
+        const double dp = dprim[b];
+        const double* dd = ddual + (size_t)b * m;
+        const int* us = use + (size_t)b * m;
+        // the working set as a bit set in LDS, as sp_ph_factor builds it
+        unsigned* bits = nullptr;
+        if (G <= 16 && db.bitWords > 0) {
+            bits = reinterpret_cast<unsigned*>(sp_dyn_lds) + (size_t)((int)threadIdx.x / G) * db.bitWords;
+            for (int w = t; w < db.bitWords; w += G) {
+                unsigned word = 0u;
+#pragma unroll 8
+                for (int k = 0; k < 32; k++) { const int r = w * 32 + k; if (r < m && us[r] != 0) word |= 1u << k; }
+                bits[w] = word;
+            }
+            wave_sync();
+        }
+        if (bits) sp_factor_band<G>(c, c.KF(false), c.KD(false), dp, [=](int r) { return dd[r]; }, [=](int r) { return ((bits[r >> 5] >> (r & 31)) & 1u) != 0u; });
+        else sp_factor_band<G>(c, c.KF(false), c.KD(false), dp, [=](int r) { return dd[r]; }, [=](int r) { return us[r] != 0; });
+        if (db.kb > 0) {
+            sp_border_prepare<G>(c, false, [=](int r) { return us[r] != 0; });
+            for (int jb = 0; jb < db.kb; jb++) { GD vec = sp_border_column<G>(c, false, jb); sp_solve_band<G>(c, false, vec); }
+            sp_border_schur<G>(c, false, dp, [=](int r) { return dd[r]; }, [=](int r) { return us[r] != 0; });
+        }
+        if (t == 0) { c.info->haveSolution = 0; c.info->stfValid = 0; db.state[b].fact_valid = 0; }
+    } else if (admm) {
+        GD rhov = c.M(MV_RHOV);
+        for (int r = t; r < m; r += G) { recD[(size_t)b * m + r] = 1.0 / rhov[r]; recU[(size_t)b * m + r] = 1; }
+        if (t == 0) recP[b] = c.info->sigma;
+    } else {
+        GI stf = c.I(MI_STF);
+        const double d2 = db.state[b].d2Used;
+        for (int r = t; r < m; r += G) { recD[(size_t)b * m + r] = d2; recU[(size_t)b * m + r] = (stf[r] != ST_INACT) ? 1 : 0; }
+        if (t == 0) recP[b] = db.state[b].dpUsed;
+    }
+    GD bv = c.Nv();
+    for (int p = N + t; p < db.Np; p += G) bv[p] = 0.0;
+    for (int k = 0; k < nrhs; k++) {
+        const double* bk = rhs + ((size_t)b * nrhs + k) * N;
+        double* xk = sol + ((size_t)b * nrhs + k) * N;
+        g_map<G, 8>(N, t, [&](int i) { return ID{iperm[i], bk[i]}; }, [&](int, ID w) { bv[w.i] = w.a; });
+        g_sync();
+        sp_solve<G>(c, admm, bv);
+        g_map<G, 8>(N, t, [&](int i) { return (double)bv[iperm[i]]; }, [&](int i, double w) { xk[i] = w; });
+        g_sync();
+    }
 }
 
 // ---- the scheduler: persistent wavefronts that serve the phase queues of their pool -------------------------------------------------------
@@ -499,6 +567,16 @@ static void sp_launch_sensitivity(const SpBatch& db, hipStream_t stream, int nrh
     hipLaunchKernelGGL(k_sparse_sensitivity<G>, dim3(grid), dim3(WGS), ldsBytes, stream, db, nrhs, v, dg, dbo, side, sinfo);
 }
 
+// one launch of k_sparse_kkt_probe<G> on device buffers; the LDS of a factorisation (sp_launch), which covers the window of the general solve
+template <int G>
+static void sp_launch_kkt_probe(const SpBatch& db, hipStream_t stream, int mode, int which, int nrhs, const double* dprim, const double* ddual, const int* use,
+                                const double* rhs, double* sol, double* recP, double* recD, int* recU)
+{
+    const int ipw = 64 / G, grid = (db.B + ipw - 1) / ipw;
+    const size_t ldsBytes = G <= 16 ? sizeof(unsigned) * (size_t)ipw * db.bitWords : sizeof(double) * (size_t)ipw * group_lds_doubles(G);
+    hipLaunchKernelGGL(k_sparse_kkt_probe<G>, dim3(grid), dim3(WGS), ldsBytes, stream, db, mode, which, nrhs, dprim, ddual, use, rhs, sol, recP, recD, recU);
+}
+
 }  // namespace
 
 // the launch table of this unit's width (lcqp_sparse_launch.hpp)
@@ -506,7 +584,7 @@ namespace lcqp_sparse {
 template <int G>
 const SpKernels& sparse_kernels()
 {
-    static const SpKernels k = {G, sp_launch<G>, sp_launch_sensitivity<G>};
+    static const SpKernels k = {G, sp_launch<G>, sp_launch_sensitivity<G>, sp_launch_kkt_probe<G>};
     return k;
 }
 }

@@ -366,6 +366,44 @@ extern "C" int lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* h, int nrhs, const
     return 0;
 }); }
 
+// ---- test and diagnostic entry point: the KKT factorisations and solves of every instance held against a plain reference (k_sparse_kkt_probe) ----
+extern "C" int lcqp_hip_sparse_kkt_probe(lcqp_hip_sparse_t* h, int mode, int which, int nrhs, const double* dprim, const double* ddual, const int* use,
+                                         const double* rhs, double* sol, double* rec_dprim, double* rec_ddual, int* rec_use)
+{ return guarded(g_sp_err, [&] {
+    if (nrhs < 1 || !rhs || !sol) return LCQP_INVALID_ARGUMENT;
+    if (mode != LCQP_KKT_PROBE_FACTOR && mode != LCQP_KKT_PROBE_STORED) { g_sp_err = "kkt_probe: mode is 0 (FACTOR) or 1 (STORED)"; return LCQP_INVALID_ARGUMENT; }
+    if (mode == LCQP_KKT_PROBE_FACTOR && (!dprim || !ddual || !use)) return LCQP_INVALID_ARGUMENT;
+    if (mode == LCQP_KKT_PROBE_STORED && ((which != 0 && which != 1) || !rec_dprim || !rec_ddual || !rec_use)) {
+        g_sp_err = "kkt_probe: STORED takes which = 0 (polish slot) or 1 (ADMM slot) and the three record buffers";
+        return LCQP_INVALID_ARGUMENT;
+    }
+    // K0 of the register engine and both factors exist behind a run or a resolve on the data in place; the stored polish factor and its record
+    // only while no FACTOR probe has overwritten them
+    if (!h || !h->rs.setupValid) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (mode == LCQP_KKT_PROBE_STORED && which == 0 && !h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    SpBatch& d = h->db;
+    if (int rc = synchronize(g_sp_err, h)) return rc;
+    const size_t B = d.B, m = d.m, nvec = B * (size_t)nrhs * d.N;
+    DevMem tmp(h->stream);      // the buffers of this call; freed on every way out
+    double *dP = nullptr, *dD = nullptr, *dRhs = nullptr, *dSol = nullptr, *rP = nullptr, *rD = nullptr;
+    int *dU = nullptr, *rU = nullptr;
+    bool ok = tmp.alloc(g_sp_err, dRhs, nvec, rhs) && tmp.alloc(g_sp_err, dSol, nvec);
+    if (mode == LCQP_KKT_PROBE_FACTOR) ok = ok && tmp.alloc(g_sp_err, dP, B, dprim) && tmp.alloc(g_sp_err, dD, B * m, ddual) && tmp.alloc(g_sp_err, dU, B * m, use);
+    else ok = ok && tmp.alloc(g_sp_err, rP, B) && tmp.alloc(g_sp_err, rD, B * m) && tmp.alloc(g_sp_err, rU, B * m);
+    if (!ok) { g_sp_err = "device allocation failed: " + g_sp_err; return LCQP_HIP_ERROR; }
+    if (mode == LCQP_KKT_PROBE_FACTOR) h->rs.solved = false;      // the polish factor of the last run is about to be overwritten
+    sp_kernels(d.G)->kkt_probe(d, h->stream, mode, which, nrhs, dP, dD, dU, dRhs, dSol, rP, rD, rU);
+    HIPCHK(g_sp_err, hipGetLastError());
+    HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));
+    HIPCHK(g_sp_err, hipMemcpy(sol, dSol, sizeof(double) * nvec, hipMemcpyDeviceToHost));
+    if (mode == LCQP_KKT_PROBE_STORED) {
+        HIPCHK(g_sp_err, hipMemcpy(rec_dprim, rP, sizeof(double) * B, hipMemcpyDeviceToHost));
+        HIPCHK(g_sp_err, hipMemcpy(rec_ddual, rD, sizeof(double) * B * m, hipMemcpyDeviceToHost));
+        HIPCHK(g_sp_err, hipMemcpy(rec_use, rU, sizeof(int) * B * m, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}); }
+
 extern "C" int lcqp_hip_sparse_sensitivity_timing(lcqp_hip_sparse_t* h, float* kernel_ms)
 {
     return sensitivity_timing(h, kernel_ms);

@@ -129,7 +129,10 @@ constexpr int GEN_META = 12;      // ints per front of SpBatch::gMeta
 // SpSensitivityFn: one launch of k_sparse_sensitivity<G> on `stream` over device buffers (layouts at the kernel).
 using SpRunFn = void(const SpBatch& db, int cus, hipStream_t stream, hipEvent_t mid, bool refresh, int mode, const double* rho0);
 using SpSensitivityFn = void(const SpBatch& db, hipStream_t stream, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo);
-struct SpKernels { int G; SpRunFn* run; SpSensitivityFn* sensitivity; };
+// SpKktProbeFn: one launch of k_sparse_kkt_probe<G> on `stream` over device buffers (layouts and modes at the kernel).
+using SpKktProbeFn = void(const SpBatch& db, hipStream_t stream, int mode, int which, int nrhs, const double* dprim, const double* ddual, const int* use,
+                          const double* rhs, double* sol, double* recP, double* recD, int* recU);
+struct SpKernels { int G; SpRunFn* run; SpSensitivityFn* sensitivity; SpKktProbeFn* kkt_probe; };
 // defined in lcqp_sparse.hip and instantiated there for G = LCQP_TU_G
 template <int G> const SpKernels& sparse_kernels();
 #pragma GCC visibility pop

@@ -148,7 +148,8 @@ __device__ __forceinline__ int sp_polish_begin(SpCtx<G>& c, SpState& S, GD g, in
     S.gs = 1.0 + ((reuse && S.gmaxNext >= 0.0) ? S.gmaxNext : sp_maxabs<G>(c, g, c.db->n));      // (the LCQP level knows max|g| of the vector it has just formed)
     S.ytol = o.feasTol * S.gs;
     S.fact_valid = 0; S.borderTodo = 0;
-    S.dpUsed = c.info->delta; S.d2Used = c.info->delta2;      // regularisation of the factorisation in use
+    // (S.dpUsed / S.d2Used stay: they are the regularisation of the factorisation IN MEMORY, written by sp_ph_factor.  A hot start whose
+    // working set matches the factor's corrects with that factor, whichever of the two levels it holds.)
     S.trial = 0; S.reuse = reuse; S.nrefine = 0; S.xinf = 0.0;
     return PH_TRIAL;
 }

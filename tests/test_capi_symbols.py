@@ -85,6 +85,38 @@ def test_c_abi_rejects_bad_arguments_without_a_gpu():
         L.lcqp_hip_qp_destroy(ctypes.c_void_p(q))
 
 
+def test_sparse_kkt_probe_checks_its_arguments_without_a_gpu():
+    """lcqp_hip_sparse_kkt_probe (test and diagnostic entry point of the sparse arm): nrhs < 1, NULL vectors, a mode other than FACTOR / STORED, a
+    FACTOR call without its inputs, a STORED call with a bad slot or without its record buffers are LCQP_INVALID_ARGUMENT; with good arguments a
+    NULL handle -- the only handle there is without a device -- is LCQP_LCQPOBJECT_NOT_SETUP, as a call before the first run is on a GPU
+    (tests/test_gpu_sparse_factor.py).  All of it is decided before any device call."""
+    import numpy as np
+    import lcqpow_amd as la
+    L = la.lib()
+    assert "lcqp_hip_sparse_kkt_probe" in declared_functions()
+    dp = ctypes.POINTER(ctypes.c_double); ip = ctypes.POINTER(ctypes.c_int)
+    v = np.zeros(4); w = np.zeros(4); u = np.zeros(4, dtype=np.int32)
+    d = lambda a: a.ctypes.data_as(dp)
+    i = lambda a: a.ctypes.data_as(ip)
+    probe = L.lcqp_hip_sparse_kkt_probe
+    FACTOR, STORED = 0, 1
+    good_f = (d(v), d(v), i(u), d(v), d(w), None, None, None)
+    good_s = (None, None, None, d(v), d(w), d(v), d(v), i(u))
+    assert probe(None, FACTOR, 0, 0, *good_f) == 100 and probe(None, STORED, 0, -1, *good_s) == 100              # nrhs < 1
+    assert probe(None, FACTOR, 0, 1, d(v), d(v), i(u), None, d(w), None, None, None) == 100                        # rhs
+    assert probe(None, FACTOR, 0, 1, d(v), d(v), i(u), d(v), None, None, None, None) == 100                        # sol
+    assert probe(None, 2, 0, 1, *good_f) == 100 and probe(None, -1, 0, 1, *good_s) == 100                          # mode
+    for k in range(3):                                                                                             # FACTOR without dprim / ddual / use
+        a = list(good_f); a[k] = None
+        assert probe(None, FACTOR, 0, 1, *a) == 100
+    assert probe(None, STORED, 2, 1, *good_s) == 100 and probe(None, STORED, -1, 1, *good_s) == 100                # which
+    for k in (5, 6, 7):                                                                                            # STORED without a record buffer
+        a = list(good_s); a[k] = None
+        assert probe(None, STORED, 0, 1, *a) == 100
+    assert probe(None, FACTOR, 0, 1, *good_f) == 300 and probe(None, STORED, 0, 1, *good_s) == 300 and probe(None, STORED, 1, 1, *good_s) == 300
+    assert w.sum() == 0.0
+
+
 def test_missing_extension_fails_loudly(monkeypatch):
     """no CPU fallback: without the built HIP library the binding raises instead of computing anything"""
     import pytest

@@ -1,6 +1,7 @@
 """The compiler's register / LDS / occupancy report of the dense kernels at np = 256 (hipcc -Rpass-analysis=kernel-resource-usage with the
 flags of __graft_entry__.HIP_FLAGS), for the standard build and for the 256-register build of the persistent kernels (-DLCQP_TU_FEW).
-    python tools/kernel_resources.py > profiles/<round>/final/kernel_resource_usage.txt        (no GPU needed)"""
+    python tools/kernel_resources.py > profiles/<round>/final/kernel_resource_usage.txt        (no GPU needed)
+    python tools/kernel_resources.py sparse        the same report for the four kernel units of the sparse arm (lcqp_sparse.hip, G = 8, 16, 32, 64)"""
 import os, re, shutil, subprocess, sys, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -9,10 +10,10 @@ import __graft_entry__ as g
 KEEP = ("VGPRs:", "AGPRs:", "ScratchSize", "Occupancy", "SGPRs Spill", "VGPRs Spill", "LDS Size")
 
 
-def report(extra):
+def report(extra, unit=("lcqp_nch.hip", "-DLCQP_TU_NCH=2")):
     with tempfile.TemporaryDirectory() as tmp:
         cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")] + g.HIP_FLAGS + ["--cuda-device-only", "-c", "-o", os.path.join(tmp, "x.co"),
-               os.path.join(g.CSRC, "lcqp_nch.hip"), "-DLCQP_TU_NCH=2", "-Rpass-analysis=kernel-resource-usage"] + extra
+               os.path.join(g.CSRC, unit[0]), unit[1], "-Rpass-analysis=kernel-resource-usage"] + extra
         err = subprocess.run(cmd, capture_output=True, text=True).stderr
     filt = shutil.which("c++filt")
     out, cur = [], None
@@ -28,6 +29,13 @@ def report(extra):
             cur.append(t)
     return out
 
+
+if sys.argv[1:] == ["sparse"]:      # the four kernel units of the sparse arm, one per lane-group width
+    print("Compiler resource usage of the sparse kernel units (lcqp_sparse.hip -DLCQP_TU_G=g; tools/kernel_resources.py sparse).")
+    for G in g.SPARSE_G_LIST:
+        print("\n-- G = %d" % G)
+        for o in report([], ("lcqp_sparse.hip", "-DLCQP_TU_G=%d" % G)): print(o[0] + "\n    " + "; ".join(o[1:]))
+    sys.exit(0)
 
 print("Compiler resource usage of the np = 256 translation unit (hipcc -Rpass-analysis=kernel-resource-usage, flags of __graft_entry__.HIP_FLAGS; tools/kernel_resources.py).")
 print("Waves per SIMD = 512 / (VGPRs + AGPRs), rounded down; a 256-thread workgroup is one wave per SIMD, so this is also the workgroups per CU the registers allow.")
