@@ -298,6 +298,15 @@ class SubsolverHIP:
         if not self.h:
             raise RuntimeError("lcqp_hip_qp_create failed: " + last_error())
 
+    def clone(self):
+        """lcqp_hip_qp_clone: the problem data, options, last solution and counters; the device state is built by the clone's first solve"""
+        c = object.__new__(SubsolverHIP)
+        c.nV, c.nC, c.opt = self.nV, self.nC, type(self.opt).from_buffer_copy(self.opt)
+        c.h = lib().lcqp_hip_qp_clone(self.h)
+        if not c.h:
+            raise RuntimeError("lcqp_hip_qp_clone failed: " + last_error())
+        return c
+
     def solve(self, initialSolve, g, lbA=None, ubA=None, x0=None, y0=None, lb=None, ub=None):
         it = C.c_int(0); ef = C.c_int(0)
         n, m = self.nV, self.nC

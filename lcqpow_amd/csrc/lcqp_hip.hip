@@ -1,8 +1,7 @@
-// lcqp_hip.hip -- kernels and C-ABI of liblcqpow_hip.so (gfx950 only; see include/lcqp_hip.h).
-#include "lcqp_dev.hpp"
-#include "lcqp_launch.hpp"
-#include "lcqp_host_rt.hpp"
-#include "../../include/lcqp_synth.h"
+// lcqp_hip.hip -- the dense arm's batch: the process-wide entry points, the choice of launch table and build (dense_kernels, run_kernels)
+// and the C ABI of the batch handle, lcqp_hip_batch_* (gfx950 only; see include/lcqp_hip.h), with the two adjoint kernels that ABI
+// launches.  The QP object is lcqp_hip_qp.hip, the building blocks and CSC utilities lcqp_hip_util.hip; lcqp_hip_batch.hpp is what they share.
+#include "lcqp_hip_batch.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -18,26 +17,9 @@ using namespace lcqp_rt;
 
 
 // =================================================================================================
-// device kernels: the per-size ones live in lcqp_kernels.hpp / lcqp_nch.hip; here only the ones that are not templated
+// device kernels: the per-size ones live in lcqp_kernels.hpp / lcqp_nch.hip; here only the two that are not templated and that the batch
+// ABI launches (the other four are in lcqp_hip_util.hip)
 // =================================================================================================
-__global__ __launch_bounds__(WG) void k_chol(int np, int nblk, int n, double* F, double* dscr, int* fail)
-{
-    LCQP_LDS
-    const int b = blockIdx.x;
-    wg_chol(F + (size_t)b * np * np, np, nblk, n, 0.0, dscr + (size_t)b * 4096, nullptr, fail + b, lds, 0);
-}
-
-__global__ __launch_bounds__(WG, 4) void k_backsolve(int np, int nblk, const double* F, const double* rhs, double* x)
-{
-    LCQP_LDS
-    const int b = blockIdx.x;
-    double* xv = x + (size_t)b * np;
-    for (int i = threadIdx.x; i < np; i += WG) xv[i] = rhs[(size_t)b * np + i];
-    __syncthreads();
-    wg_trsv(F + (size_t)b * np * np, np, nblk, xv, true, lds);
-    wg_trsv(F + (size_t)b * np * np, np, nblk, xv, false, lds);
-}
-
 // ---- the matrix gradients of an adjoint call (DESIGN.md section 3a'''', lcqp_hip_batch_adjoint) --------------------------------------
 // With dg, db, side and info of k_sensitivity (nrhs = 1, still in its device buffers) and the returned x, y, row r of the stacked gradient
 // [dQ; dA; dL; dR] ([nd][n]: r < n a row of Q, above it the entry of the dual layout the row of E belongs to) of instance b is
@@ -128,6 +110,7 @@ extern "C" int lcqp_hip_request_hw_queues(int n)
 }
 
 static thread_local std::string g_err;      // the dense, QP, util and CSC entry points (lcqp_host_rt.hpp: HIPCHK(g_err, ...))
+std::string& dense_err() { return g_err; }  // the slot for lcqp_hip_qp.hip and lcqp_hip_util.hip
 
 extern "C" const char* lcqp_hip_last_error(void) { return g_err.c_str(); }
 extern "C" int lcqp_hip_device_count(void)
@@ -160,52 +143,10 @@ extern "C" void lcqp_hip_options_default(lcqp_options_t* o)
     o->admmFirst = 0; o->admmHot = 0; o->maxTrials = 16; o->maxRounds = 40;      // maxTrials: 12 until round 3 -- cold starts of the synthetic workload need up to 14 trials, and a polish that runs out of trials costs an ADMM round (the factor L_K, ten iterations, a second cold polish): those instances were the tail of the launch
 }
 
-// a pinned staging slot of loadLCQP and the event of the copies that last read it
-struct StageSlot {
-    void* buf = nullptr;
-    Event done{hipEventDisableTiming};
-    ~StageSlot() { if (buf) (void)hipHostFree(buf); }
-};
-
-// The members are released in reverse order after the destructor's synchronisation: device memory, staging slots, events, streams.
-struct lcqp_hip_batch {
-    DevBatch db;
-    int device;
-    // the setup has two independent branches (C = L'R + R'L and its compression; L1 -> Et -> M): the short one runs on `side`
-    Stream stream, side;
-    Event ev0, ev1, ev2;                  // run: setup from ev0 to ev1, homotopy from ev1 to ev2
-    Event evFork{hipEventDisableTiming}, evJoin{hipEventDisableTiming};
-    // two pinned staging slots for loadLCQP: instance k is packed into slot k&1 while slot (k-1)&1 is in flight
-    StageSlot stage[2];
-    size_t stageBytes = 0;
-    DevMem mem{stream};
-    int numCU = 256;
-    bool overlapped = false;      // lcqp_hip_batch_set_overlapped
-    bool ran = false, anyLoaded = false;
-    // re-solves and sensitivities (lcqp_host_rt.hpp).  boxed: which variables of an instance carry a finite box bound -- those are rows of
-    // E, hence of Et and M: an update must keep the set
-    ResolveState rs;
-    std::vector<char> boxed;              // [B][n]
-    SensBuffers sens;                     // of k_sensitivity
-    SensBuffers sensBlk;                  // of k_sensitivity_blk (another pitch of db, a varying number of instances)
-    size_t jacStaging = LCQP_JACOBIAN_STAGING_BYTES;      // device bytes a Jacobian / adjoint call may stage per chunk of instances
-    // of lcqp_hip_batch_adjoint, grown on demand: the upstream gradients on the duals [B][nd]; the matrix gradients of one chunk
-    double *adjVy = nullptr, *adjOut = nullptr;
-    size_t adjVyCap = 0, adjOutCap = 0;
-    Event adjEv0, adjEv1;                 // around the last matrix-gradient launch
-    int nch;
-    const SizeKernels* k = nullptr;       // the launch table of the padded size (dense_kernels), set by lcqp_hip_batch_create
-    explicit lcqp_hip_batch(int dev) : db(), device(dev) {}
-    ~lcqp_hip_batch() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
-};
-
-// padded size of a problem with n variables in units of 128: 1, 2, 3, 4, then 8 (np = 1024), 16 (np = 2048) and 32 (np = 4096)
-static inline int padded_nch(int n) { const int k = (n + 127) / 128; return k > 16 ? 32 : (k > 8 ? 16 : (k > 4 ? 8 : k)); }
-
 // The launch table of a padded size (lcqp_launch.hpp), or null with a message: a size whose kernels this build does not link is an error,
 // never another size's kernels (their buffers have another pitch).  -DLCQP_ONLY_NCH=k (the profile library, experiment builds: tools/gpu_ab.py)
 // links the kernels of one padded size only.
-static const SizeKernels* dense_kernels(int nch)
+const SizeKernels* dense_kernels(int nch)
 {
 #ifdef LCQP_ONLY_NCH
     static const SizeKernels* const sizes[] = {&size_kernels<LCQP_ONLY_NCH>()};
@@ -221,7 +162,7 @@ static const SizeKernels* dense_kernels(int nch)
 
 // The build of the two persistent kernels a launch of the batch takes: the second one (256 registers) for np <= 512 (36 KB of LDS per
 // workgroup) and at most three workgroups per CU, the standard one otherwise
-static const RunKernels& run_kernels(const lcqp_hip_batch* h)
+const RunKernels& run_kernels(const lcqp_hip_batch* h)
 {
     const bool few = h->nch <= 4 && h->db.B <= 3 * h->numCU && !h->overlapped && h->k->few;
     return few ? *h->k->few : h->k->run;
@@ -443,7 +384,7 @@ extern "C" int lcqp_hip_batch_read_problem(lcqp_hip_batch_t* h, int b, double* Q
 }); }
 
 // the setup kernels of the batch on its stream, the C branch on the side stream
-static int launch_setup(lcqp_hip_batch* h)
+int launch_setup(lcqp_hip_batch* h)
 {
     const DevBatch& d = h->db;
     const SizeKernels& k = *h->k;
@@ -767,7 +708,7 @@ static int sensitivity_launch(lcqp_hip_batch* h, bool blk, int first, int count,
 }
 
 // blk: the blocked kernel where the padded size has one, the vector kernel and its bits above
-static int batch_sensitivity(lcqp_hip_batch* h, bool blk, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
+int batch_sensitivity(lcqp_hip_batch* h, bool blk, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
 {
     float ms = 0.f;
     if (int rc = sensitivity_launch(h, blk && h->k->sensitivity_blk, 0, h->db.B, nrhs, v, dg, db, side, info, &ms)) return rc;
@@ -783,7 +724,7 @@ extern "C" int lcqp_hip_batch_sensitivity(lcqp_hip_batch_t* h, int nrhs, const d
 }); }
 
 // Jg [count][n][n], Jb [count][n][nd] (or NULL), side [count][nd], info [count] of the instances [first, first + count)
-static int batch_jacobian(lcqp_hip_batch* h, int first, int count, double* Jg, double* Jb, int* side, int* info)
+int batch_jacobian(lcqp_hip_batch* h, int first, int count, double* Jg, double* Jb, int* side, int* info)
 {
     DevBatch& d = h->db;
     const size_t n = d.n, nd = d.nd;
@@ -856,8 +797,8 @@ extern "C" int lcqp_hip_batch_sensitivity_timing(lcqp_hip_batch_t* h, float* ker
 // ---- the full adjoint (DESIGN.md section 3a''''): upstream gradients on x and y, gradients in g, the bounds and the matrices ----
 // k_sensitivity (with vy: its DUAL instantiation) on the whole batch, its results to the host; then, on the device buffers it left, the matrix
 // gradients that were asked for: k_adjoint_reduce once, or k_adjoint_outer per chunk of instances under the Jacobian staging cap.
-static int batch_adjoint(lcqp_hip_batch* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
-                         int reduce, double* dQ, double* dA, double* dL, double* dR)
+int batch_adjoint(lcqp_hip_batch* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
+                  int reduce, double* dQ, double* dA, double* dL, double* dR)
 {
     DevBatch& d = h->db;
     float ms = 0.f;
@@ -913,492 +854,4 @@ extern "C" int lcqp_hip_batch_adjoint(lcqp_hip_batch_t* h, const double* vx, con
     if (!h || !vx || !dg || (reduce != 0 && reduce != 1)) return LCQP_INVALID_ARGUMENT;
     if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
     return batch_adjoint(h, vx, vy, dg, db, side, info, reduce, dQ, dA, dL, dR);
-}); }
-
-// =================================================================================================
-// QP object (SubsolverBase semantics): a batch of one with nComp = 0 whose rows are the nC stacked rows
-// =================================================================================================
-struct lcqp_hip_qp {
-    lcqp_hip_batch* hb;
-    int nV, nC;
-    std::vector<double> Q, A;          // host copies (deep copy, src/SubsolverQPOASES.cpp:41-45)
-    std::vector<double> lbA, ubA, lb, ub;
-    bool haveBounds, withBox;
-    lcqp_options_t opt;
-    int device;
-    std::vector<double> xsol, ysol;
-    int cAdmm, cTrials, cFact, cCorr;
-    bool solved;                       // the last solve returned a solution on the options in place (lcqp_hip_qp_sensitivity)
-};
-
-extern "C" lcqp_hip_qp_t* lcqp_hip_qp_create(int nV, int nC, const double* Q, const double* A, const lcqp_options_t* opt, int device)
-{ return guarded(g_err, [&]() -> lcqp_hip_qp_t* {
-    if (nV <= 0 || nC < 0 || !Q || (nC > 0 && !A)) { g_err = "invalid arguments"; return nullptr; }
-    lcqp_hip_qp* q = new lcqp_hip_qp();
-    q->hb = nullptr; q->nV = nV; q->nC = nC; q->device = device; q->haveBounds = false; q->withBox = false; q->solved = false;
-    q->Q.assign(Q, Q + (size_t)nV * nV);
-    if (nC) q->A.assign(A, A + (size_t)nC * nV);
-    if (opt) q->opt = *opt; else lcqp_hip_options_default(&q->opt);
-    q->xsol.assign(nV, 0.0); q->ysol.assign((size_t)nV + nC, 0.0);
-    q->cAdmm = q->cTrials = q->cFact = q->cCorr = 0;
-    return q;
-}, nullptr); }
-
-extern "C" lcqp_hip_qp_t* lcqp_hip_qp_clone(const lcqp_hip_qp_t* s)
-{ return guarded(g_err, [&]() -> lcqp_hip_qp_t* {
-    if (!s) return nullptr;
-    // The reference copies subsolvers only before their first use (src/Subsolver.cpp:125-136,
-    // src/LCQProblem.cpp:906-907): the clone carries the problem data and options; device state is
-    // rebuilt by its own first solve.
-    lcqp_hip_qp* q = new lcqp_hip_qp(*s);
-    q->hb = nullptr;
-    q->haveBounds = false;
-    q->solved = false;
-    return q;
-}, nullptr); }
-
-extern "C" void lcqp_hip_qp_destroy(lcqp_hip_qp_t* q)
-{ guarded(g_err, [&] {
-    if (!q) return;
-    if (q->hb) lcqp_hip_batch_destroy(q->hb);
-    delete q;
-}); }
-
-extern "C" int lcqp_hip_qp_set_options(lcqp_hip_qp_t* q, const lcqp_options_t* opt)
-{ return guarded(g_err, [&] {
-    if (!q || !opt) return LCQP_INVALID_ARGUMENT;
-    q->opt = *opt;
-    q->haveBounds = false;   // forces a fresh setup (rho / sigma / prox weights enter the factorisations)
-    q->solved = false;
-    return 0;
-}); }
-
-static bool same_pattern(const std::vector<double>& a0, const std::vector<double>& b0, const double* a1, const double* b1, size_t n)
-{
-    for (size_t i = 0; i < n; i++) {
-        const double lo1 = a1 ? a1[i] : -INFINITY, hi1 = b1 ? b1[i] : INFINITY;
-        const bool fin0 = std::isfinite(a0[i]) || std::isfinite(b0[i]), fin1 = std::isfinite(lo1) || std::isfinite(hi1);
-        const bool eq0 = a0[i] == b0[i], eq1 = lo1 == hi1;
-        if (fin0 != fin1 || eq0 != eq1) return false;
-    }
-    return true;
-}
-
-extern "C" int lcqp_hip_qp_solve(lcqp_hip_qp_t* q, int initialSolve, int* iterations, int* exit_flag,
-                                 const double* g, const double* lbA, const double* ubA,
-                                 const double* x0, const double* y0, const double* lb, const double* ub)
-{ return guarded(g_err, [&] {
-    if (!q || !g || !iterations || !exit_flag) return LCQP_INVALID_ARGUMENT;
-    const int n = q->nV, nC = q->nC;
-    *iterations = 0; *exit_flag = 0;
-    q->solved = false;
-    const bool needBox = (lb != nullptr) || (ub != nullptr);
-    bool fresh = initialSolve || !q->hb || !q->haveBounds;
-    if (!fresh) {
-        if (needBox && !q->withBox) fresh = true;
-        else if (!same_pattern(q->lbA, q->ubA, lbA, ubA, nC) || !same_pattern(q->lb, q->ub, lb, ub, n)) fresh = true;
-    }
-    if (q->hb && (fresh && (needBox && !q->withBox))) { lcqp_hip_batch_destroy(q->hb); q->hb = nullptr; }
-    if (!q->hb) {
-        q->hb = lcqp_hip_batch_create(1, n, nC, 0, needBox ? 1 : 0, q->device);
-        if (!q->hb) { *exit_flag = -1; return LCQP_SUBPROBLEM_SOLVER_ERROR; }
-        q->withBox = needBox;
-        fresh = true;
-    }
-    lcqp_hip_batch* h = q->hb;
-    DevBatch& d = h->db;
-    if (hipSetDevice(h->device) != hipSuccess) { *exit_flag = -1; return LCQP_SUBPROBLEM_SOLVER_ERROR; }
-    q->lbA.assign(nC, -INFINITY); q->ubA.assign(nC, INFINITY); q->lb.assign(n, -INFINITY); q->ub.assign(n, INFINITY);
-    for (int i = 0; i < nC; i++) { if (lbA) q->lbA[i] = lbA[i]; if (ubA) q->ubA[i] = ubA[i]; }
-    for (int i = 0; i < n; i++) { if (lb) q->lb[i] = lb[i]; if (ub) q->ub[i] = ub[i]; }
-    q->haveBounds = true;
-    int rc;
-    if (fresh) {
-        lcqp_hip_batch_set_options(h, &q->opt);
-        // batch of one, nComp = 0: the "A" block carries all stacked rows; L/R are empty
-        double dummy = 0.0;
-        rc = lcqp_hip_batch_load(h, 0, 1, q->Q.data(), g, &dummy, &dummy, nullptr, nullptr, nullptr, nullptr,
-                                 nC ? q->A.data() : nullptr, q->lbA.data(), q->ubA.data(),
-                                 q->withBox ? q->lb.data() : nullptr, q->withBox ? q->ub.data() : nullptr, x0, y0);
-        if (rc) { *exit_flag = -1; return LCQP_SUBPROBLEM_SOLVER_ERROR; }
-        rc = launch_setup(h);
-        if (rc) { *exit_flag = -1; return LCQP_SUBPROBLEM_SOLVER_ERROR; }
-        initialSolve = 1;
-    } else {
-        // same pattern: refresh bound values (finite/equality pattern unchanged, factorisations stay valid)
-        std::vector<double> l(d.mEcap, 0.0), u(d.mEcap, 0.0);
-        for (int r = 0; r < nC; r++) { l[r] = q->lbA[r]; u[r] = q->ubA[r]; }
-        int k = 0;
-        for (int i = 0; i < n; i++)
-            if (std::isfinite(q->lb[i]) || std::isfinite(q->ub[i])) { l[nC + k] = q->lb[i]; u[nC + k] = q->ub[i]; k++; }
-        if (hipMemcpyAsync(d.mv + (size_t)M_L * d.mEcap, l.data(), sizeof(double) * d.mEcap, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-            hipMemcpyAsync(d.mv + (size_t)M_U * d.mEcap, u.data(), sizeof(double) * d.mEcap, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
-            // new bound values: the safe margins of the row screening (M_MG, relative to the old bounds) are void -- NaN margins make
-            // the next residual sweep read every row
-            hipMemsetAsync(d.mv + (size_t)M_MG * d.mEcap, 0xFF, sizeof(double) * d.mEcap, h->stream) != hipSuccess ||
-            hipStreamSynchronize(h->stream) != hipSuccess) { *exit_flag = -1; return LCQP_SUBPROBLEM_SOLVER_ERROR; }
-    }
-    // linear term of this call
-    std::vector<double> gp(d.np, 0.0);
-    memcpy(gp.data(), g, sizeof(double) * n);
-    if (hipMemcpyAsync(d.nv + (size_t)V_GK * d.np, gp.data(), sizeof(double) * d.np, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
-        *exit_flag = -1; return LCQP_SUBPROBLEM_SOLVER_ERROR;
-    }
-    run_kernels(h).qp_solve(d, 1, h->stream, initialSolve ? 1 : 0);
-    lcqp_stats_t st;
-    if (hipStreamSynchronize(h->stream) != hipSuccess ||
-        hipMemcpy(&st, d.stats, sizeof(st), hipMemcpyDeviceToHost) != hipSuccess) { *exit_flag = -1; return LCQP_SUBPROBLEM_SOLVER_ERROR; }
-    *iterations = st.subproblemIter;
-    *exit_flag = st.qpSolverExitFlag;
-    q->cAdmm += st.admmIter; q->cTrials += st.trials; q->cFact += st.factorizations; q->cCorr += st.corrections;
-    if (st.qpSolverExitFlag != 0) return LCQP_SUBPROBLEM_SOLVER_ERROR;
-    if (hipMemcpy(q->xsol.data(), d.xout, sizeof(double) * n, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(q->ysol.data(), d.yout, sizeof(double) * ((size_t)n + nC), hipMemcpyDeviceToHost) != hipSuccess) {
-        *exit_flag = -1; return LCQP_SUBPROBLEM_SOLVER_ERROR;
-    }
-    q->solved = true;
-    return LCQP_SUCCESSFUL_RETURN;
-}); }
-
-extern "C" void lcqp_hip_qp_get_solution(lcqp_hip_qp_t* q, double* x, double* y)
-{ guarded(g_err, [&] {
-    if (!q) return;
-    if (x) memcpy(x, q->xsol.data(), sizeof(double) * q->nV);
-    if (y) memcpy(y, q->ysol.data(), sizeof(double) * ((size_t)q->nV + q->nC));
-}); }
-
-extern "C" void lcqp_hip_qp_get_counters(lcqp_hip_qp_t* q, int* admm, int* trials, int* factorizations, int* corrections)
-{ guarded(g_err, [&] {
-    if (!q) return;
-    if (admm) *admm = q->cAdmm;
-    if (trials) *trials = q->cTrials;
-    if (factorizations) *factorizations = q->cFact;
-    if (corrections) *corrections = q->cCorr;
-}); }
-
-// the QP object is a batch of one: the same two readers through its batch (LCQP_LCQPOBJECT_NOT_SETUP before the first solve built it)
-extern "C" int lcqp_hip_qp_read_setup(lcqp_hip_qp_t* q, int dims[9], double scal[2], double* Cm, double* F1, double* D1, double* Et,
-                                      double* MM, int* Cp, int* Ci, double* Cv)
-{
-    if (!q) return LCQP_INVALID_ARGUMENT;
-    if (!q->hb) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return lcqp_hip_batch_read_setup(q->hb, 0, dims, scal, Cm, F1, D1, Et, MM, Cp, Ci, Cv);
-}
-
-extern "C" int lcqp_hip_qp_read_working_set(lcqp_hip_qp_t* q, int dims[2], int* slot_row, int* crow, int* row_slot, double* Ti)
-{
-    if (!q) return LCQP_INVALID_ARGUMENT;
-    if (!q->hb) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return lcqp_hip_batch_read_working_set(q->hb, 0, dims, slot_row, crow, row_slot, Ti);
-}
-
-// the derivatives of the convex QP last solved: k_sensitivity on the batch of one (dg [nrhs][nV], db / side [.][nV + nC], info [1])
-extern "C" int lcqp_hip_qp_sensitivity(lcqp_hip_qp_t* q, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
-{ return guarded(g_err, [&] {
-    if (!q || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
-    if (!q->hb || !q->solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return batch_sensitivity(q->hb, false, nrhs, v, dg, db, side, info);
-}); }
-
-// the full adjoint on the batch of one (lcqp_hip_batch_adjoint): vy, db, side [nV + nC]; dQ [nV][nV], dA [nC][nV] (the stacked rows) may be NULL
-extern "C" int lcqp_hip_qp_adjoint(lcqp_hip_qp_t* q, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
-                                   double* dQ, double* dA)
-{ return guarded(g_err, [&] {
-    if (!q || !vx || !dg) return LCQP_INVALID_ARGUMENT;
-    if (!q->hb || !q->solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return batch_adjoint(q->hb, vx, vy, dg, db, side, info, 0, dQ, dA, nullptr, nullptr);
-}); }
-
-// the blocked twins on the batch of one (lcqp_hip_batch_sensitivity_blocked, lcqp_hip_batch_jacobian)
-extern "C" int lcqp_hip_qp_sensitivity_blocked(lcqp_hip_qp_t* q, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
-{ return guarded(g_err, [&] {
-    if (!q || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
-    if (!q->hb || !q->solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return batch_sensitivity(q->hb, true, nrhs, v, dg, db, side, info);
-}); }
-
-extern "C" int lcqp_hip_qp_jacobian(lcqp_hip_qp_t* q, double* Jg, double* Jb, int* side, int* info)
-{ return guarded(g_err, [&] {
-    if (!q || !Jg) return LCQP_INVALID_ARGUMENT;
-    if (!q->hb || !q->solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return batch_jacobian(q->hb, 0, 1, Jg, Jb, side, info);
-}); }
-
-// =================================================================================================
-// building blocks (tests, micro-benchmarks)
-// =================================================================================================
-// mean time of `repeat` launches (at least one) after one warm-up launch, all on the null stream
-template <class Launch>
-static int time_launches(int repeat, float* ms, Launch launch)
-{
-    Event e0, e1;      // destroyed on every return
-    if (hipError_t e = e0.status ? e0.status : e1.status) return hip_fail(g_err, "hipEventCreate", e);
-    if (repeat < 1) repeat = 1;
-    launch();
-    HIPCHK(g_err, hipEventRecord(e0, 0));
-    for (int r = 0; r < repeat; r++) launch();
-    HIPCHK(g_err, hipEventRecord(e1, 0));
-    HIPCHK(g_err, hipEventSynchronize(e1));
-    float t = 0.f;
-    HIPCHK(g_err, hipEventElapsedTime(&t, e0, e1));
-    if (ms) *ms = t / repeat;
-    return 0;
-}
-
-static int upload_padded(double* dst, const double* src, int batch, int rows, int cols, int ld, int rowsPad)
-{
-    // src: [batch][rows][cols] -> dst: [batch][rowsPad][ld]
-    std::vector<double> buf((size_t)rowsPad * ld);
-    for (int b = 0; b < batch; b++) {
-        std::fill(buf.begin(), buf.end(), 0.0);
-        for (int r = 0; r < rows; r++) memcpy(&buf[(size_t)r * ld], src + ((size_t)b * rows + r) * cols, sizeof(double) * cols);
-        HIPCHK(g_err, hipMemcpy(dst + (size_t)b * rowsPad * ld, buf.data(), sizeof(double) * rowsPad * ld, hipMemcpyHostToDevice));
-    }
-    return 0;
-}
-static int download_padded(double* dst, const double* src, int batch, int rows, int cols, int ld, int rowsPad)
-{
-    std::vector<double> buf((size_t)rowsPad * ld);
-    for (int b = 0; b < batch; b++) {
-        HIPCHK(g_err, hipMemcpy(buf.data(), src + (size_t)b * rowsPad * ld, sizeof(double) * rowsPad * ld, hipMemcpyDeviceToHost));
-        for (int r = 0; r < rows; r++) memcpy(dst + ((size_t)b * rows + r) * cols, &buf[(size_t)r * ld], sizeof(double) * cols);
-    }
-    return 0;
-}
-
-extern "C" int lcqp_hip_util_symv(int batch, int n, double alpha, const double* A, const double* bv, const double* cv, double* dv)
-{ return guarded(g_err, [&] {
-    if (n <= 0 || n > 4096 || batch <= 0) return LCQP_HIP_UNSUPPORTED;
-    const SizeKernels* k = dense_kernels(padded_nch(n));
-    if (!k) return LCQP_HIP_UNSUPPORTED;
-    const int np = 128 * k->nch;
-    DevMem tb;
-    double *dA, *db_, *dc, *dd;
-    if (!tb.alloc(g_err, dA, (size_t)batch * np * np) || !tb.alloc(g_err, db_, (size_t)batch * np) || !tb.alloc(g_err, dc, (size_t)batch * np) ||
-        !tb.alloc(g_err, dd, (size_t)batch * np))
-        return LCQP_HIP_ERROR;
-    int rc = upload_padded(dA, A, batch, n, n, np, np); if (rc) return rc;
-    rc = upload_padded(db_, bv, batch, 1, n, np, 1); if (rc) return rc;
-    rc = upload_padded(dc, cv, batch, 1, n, np, 1); if (rc) return rc;
-    k->util_symv(batch, 0, n, alpha, dA, db_, dc, dd);
-    HIPCHK(g_err, hipDeviceSynchronize());
-    return download_padded(dv, dd, batch, 1, n, np, 1);
-}); }
-
-static int util_rows(int batch, int m, int n, const double* A, const double* x, double* dots, const double* coef, double* outT)
-{
-    if (n <= 0 || n > 4096 || batch <= 0 || m <= 0) return LCQP_HIP_UNSUPPORTED;
-    const SizeKernels* k = dense_kernels(padded_nch(n));
-    if (!k) return LCQP_HIP_UNSUPPORTED;
-    const int np = 128 * k->nch;
-    DevMem tb;
-    double *dA, *dx = nullptr, *dd = nullptr, *dcf = nullptr, *dout = nullptr;
-    if (!tb.alloc(g_err, dA, (size_t)batch * m * np) || (x && !tb.alloc(g_err, dx, (size_t)batch * np)) || (dots && !tb.alloc(g_err, dd, (size_t)batch * m)) ||
-        (coef && !tb.alloc(g_err, dcf, (size_t)batch * m, coef)) || (outT && !tb.alloc(g_err, dout, (size_t)batch * np)))
-        return LCQP_HIP_ERROR;
-    int rc = upload_padded(dA, A, batch, m, n, np, m); if (rc) return rc;
-    if (x) { rc = upload_padded(dx, x, batch, 1, n, np, 1); if (rc) return rc; }
-    k->util_rows(batch, 0, m, dA, dx, dd, dcf, dout);
-    HIPCHK(g_err, hipDeviceSynchronize());
-    if (dots) HIPCHK(g_err, hipMemcpy(dots, dd, sizeof(double) * (size_t)batch * m, hipMemcpyDeviceToHost));
-    if (outT) return download_padded(outT, dout, batch, 1, n, np, 1);
-    return 0;
-}
-
-extern "C" int lcqp_hip_util_rows_list(int batch, int m, int n, const double* A, const int* list, int nlist, const double* x, const double* coef,
-                                       double* dots, double* outT)
-{ return guarded(g_err, [&] {
-    if (n <= 0 || n > 4096 || batch <= 0 || m <= 0 || nlist < 0 || nlist > m || !list) return LCQP_HIP_UNSUPPORTED;
-    const SizeKernels* k = dense_kernels(padded_nch(n));
-    if (!k) return LCQP_HIP_UNSUPPORTED;
-    const int np = 128 * k->nch;
-    DevMem tb;
-    double *dA, *dx = nullptr, *dd = nullptr, *dcf = nullptr, *dout = nullptr;
-    int* dl;
-    if (!tb.alloc(g_err, dA, (size_t)batch * m * np) || (x && !tb.alloc(g_err, dx, (size_t)batch * np)) ||
-        (dots && !tb.alloc(g_err, dd, (size_t)batch * m, dots)) ||      // rows outside the list keep the caller's values
-        (coef && !tb.alloc(g_err, dcf, (size_t)batch * m, coef)) || (outT && !tb.alloc(g_err, dout, (size_t)batch * np)) ||
-        !tb.alloc(g_err, dl, (size_t)batch * nlist, list))
-        return LCQP_HIP_ERROR;
-    int rc = upload_padded(dA, A, batch, m, n, np, m); if (rc) return rc;
-    if (x) { rc = upload_padded(dx, x, batch, 1, n, np, 1); if (rc) return rc; }
-    k->util_rows_list(batch, 0, m, nlist, dA, dl, dx, dd, dcf, dout);
-    HIPCHK(g_err, hipDeviceSynchronize());
-    if (dots) HIPCHK(g_err, hipMemcpy(dots, dd, sizeof(double) * (size_t)batch * m, hipMemcpyDeviceToHost));
-    if (outT) return download_padded(outT, dout, batch, 1, n, np, 1);
-    return 0;
-}); }
-
-extern "C" int lcqp_hip_util_gemv(int batch, int m, int n, const double* A, const double* b, double* c)
-{
-    return guarded(g_err, [&] { return util_rows(batch, m, n, A, b, c, nullptr, nullptr); });
-}
-extern "C" int lcqp_hip_util_gemv_t(int batch, int m, int n, const double* A, const double* b, double* c)
-{
-    return guarded(g_err, [&] { return util_rows(batch, m, n, A, nullptr, nullptr, b, c); });
-}
-
-extern "C" int lcqp_hip_util_symm_product(int batch, int m, int n, const double* A, const double* Bm, double* C)
-{ return guarded(g_err, [&] {
-    // goes through the batch object so that the production kernel k_build_C is what is tested
-    lcqp_hip_batch* h = lcqp_hip_batch_create(batch, n, 0, m, 0, 0);
-    if (!h) return LCQP_HIP_ERROR;
-    DevBatch& d = h->db;
-    int rc = upload_padded(d.E, A, batch, m, n, d.np, d.mEcap);
-    if (!rc) {
-        // second block (R) starts at row m of each instance
-        std::vector<double> buf((size_t)d.mEcap * d.np);
-        for (int b = 0; b < batch && !rc; b++) {
-            if (hipMemcpy(buf.data(), d.E + (size_t)b * d.mEcap * d.np, sizeof(double) * buf.size(), hipMemcpyDeviceToHost) != hipSuccess) { rc = LCQP_HIP_ERROR; break; }
-            for (int r = 0; r < m; r++) memcpy(&buf[(size_t)(m + r) * d.np], Bm + ((size_t)b * m + r) * n, sizeof(double) * n);
-            if (hipMemcpy(d.E + (size_t)b * d.mEcap * d.np, buf.data(), sizeof(double) * buf.size(), hipMemcpyHostToDevice) != hipSuccess) rc = LCQP_HIP_ERROR;
-        }
-    }
-    if (!rc) {
-        h->k->build_C(d, d.B * (d.nblk * (d.nblk + 1) / 2), h->stream);
-        if (hipStreamSynchronize(h->stream) != hipSuccess) rc = LCQP_HIP_ERROR;
-    }
-    if (!rc) rc = download_padded(C, d.C, batch, n, n, d.np, d.np);
-    lcqp_hip_batch_destroy(h);
-    return rc;
-}); }
-
-// =================================================================================================
-// CSC utilities on the device: compressed-segment gather products.
-// A CSC matrix is uploaded together with its transpose (the CSC of A' is the CSR of A), so both
-// MatrixMultiplication (A b) and TransponsedMatrixMultiplication (A'b) are gathers over compressed segments --
-// no atomics, deterministic, the same summation order as the reference's inner loops
-// (src/Utilities.cpp:49-59,75-82,189-199,228-241).
-// =================================================================================================
-// out[s] = alpha * sum_{k in [ptr[s], ptr[s+1])} val[k] * v[idx[k]] + (add ? add[s] : 0); 16 lanes per segment
-__global__ __launch_bounds__(256) void k_seg_gather(int nseg, const int* __restrict__ ptr, const int* __restrict__ idx,
-                                                    const double* __restrict__ val, const double* __restrict__ v, double alpha,
-                                                    const double* __restrict__ add, double* __restrict__ out)
-{
-    const int sub = threadIdx.x & 15;
-    const int seg = (blockIdx.x * blockDim.x + threadIdx.x) >> 4;
-    double s = 0.0;
-    if (seg < nseg) {
-        const int k0 = ptr[seg], k1 = ptr[seg + 1];
-        for (int k = k0 + sub; k < k1; k += 16) s += val[k] * v[idx[k]];
-    }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 16);
-    if (seg < nseg && sub == 0) out[seg] = alpha * s + (add ? add[seg] : 0.0);
-}
-
-struct lcqp_hip_csc {
-    int m, n, nnz, device;
-    int *p, *i, *tp, *ti;        // CSC of A and CSC of A' (device)
-    double *x, *tx;
-    double *vin, *vout, *vadd;   // staging vectors of length max(m, n)
-    DevMem mem;
-    ~lcqp_hip_csc() { (void)hipSetDevice(device); }      // then the memory
-};
-
-extern "C" lcqp_hip_csc_t* lcqp_hip_csc_create(int m, int n, int nnz, const int* p, const int* i, const double* x, int device)
-{ return guarded(g_err, [&]() -> lcqp_hip_csc_t* {
-    if (m <= 0 || n <= 0 || nnz < 0 || !p || (nnz && (!i || !x))) { g_err = "invalid CSC arguments"; return nullptr; }
-    if (hipError_t e = hipSetDevice(device)) { hip_fail(g_err, "hipSetDevice(device)", e); return nullptr; }
-    // transpose on the host: counting sort by row index (stable, so columns stay ascending inside a row)
-    std::vector<int> tp(m + 1, 0), ti(nnz ? nnz : 1);
-    std::vector<double> tx(nnz ? nnz : 1);
-    for (int k = 0; k < nnz; k++) { if (i[k] < 0 || i[k] >= m) { g_err = "CSC row index out of bounds"; return nullptr; } tp[i[k] + 1]++; }
-    for (int r = 0; r < m; r++) tp[r + 1] += tp[r];
-    std::vector<int> cur(tp.begin(), tp.end() - 1);
-    for (int c = 0; c < n; c++)
-        for (int k = p[c]; k < p[c + 1]; k++) { const int d = cur[i[k]]++; ti[d] = c; tx[d] = x[k]; }
-    std::unique_ptr<lcqp_hip_csc> h(new lcqp_hip_csc());
-    h->m = m; h->n = n; h->nnz = nnz; h->device = device;
-    const size_t mx = (size_t)(m > n ? m : n);
-    DevMem& dm = h->mem;
-    const bool ok = dm.alloc(g_err, h->p, n + 1, p) && dm.alloc(g_err, h->i, nnz, i) && dm.alloc(g_err, h->x, nnz, x) &&
-                    dm.alloc(g_err, h->tp, m + 1, tp.data()) && dm.alloc(g_err, h->ti, nnz, ti.data()) && dm.alloc(g_err, h->tx, nnz, tx.data()) &&
-                    dm.alloc(g_err, h->vin, mx) && dm.alloc(g_err, h->vout, mx) && dm.alloc(g_err, h->vadd, mx);
-    if (!ok) return nullptr;
-    if (hipError_t e = hipStreamSynchronize(nullptr)) { hip_fail(g_err, "hipStreamSynchronize(nullptr)", e); return nullptr; }      // the zero-fills
-    return h.release();
-}, nullptr); }
-
-extern "C" void lcqp_hip_csc_destroy(lcqp_hip_csc_t* h)
-{
-    guarded(g_err, [&] { delete h; });
-}
-
-// d = alpha * op(A) * b + (c ? c : 0);  transposed != 0: op(A) = A' (b has m entries, d has n), else op(A) = A.
-// repeat > 1 re-launches the product for timing; *ms = time per launch.
-extern "C" int lcqp_hip_csc_apply(lcqp_hip_csc_t* h, int transposed, double alpha, const double* b, const double* c, double* d,
-                                  int repeat, float* ms)
-{ return guarded(g_err, [&] {
-    if (!h || !b || !d) return LCQP_INVALID_ARGUMENT;
-    HIPCHK(g_err, hipSetDevice(h->device));
-    const int nin = transposed ? h->m : h->n, nout = transposed ? h->n : h->m;
-    HIPCHK(g_err, hipMemcpy(h->vin, b, sizeof(double) * nin, hipMemcpyHostToDevice));
-    if (c) HIPCHK(g_err, hipMemcpy(h->vadd, c, sizeof(double) * nout, hipMemcpyHostToDevice));
-    const int* ptr = transposed ? h->p : h->tp;     // A'b gathers over the columns of A, A b over the columns of A'
-    const int* idx = transposed ? h->i : h->ti;
-    const double* val = transposed ? h->x : h->tx;
-    const int grid = (nout * 16 + 255) / 256;
-    const int rc = time_launches(repeat, ms, [&] {
-        hipLaunchKernelGGL(k_seg_gather, dim3(grid), dim3(256), 0, 0, nout, ptr, idx, val, h->vin, alpha, c ? h->vadd : nullptr, h->vout);
-    });
-    if (rc) return rc;
-    HIPCHK(g_err, hipMemcpy(d, h->vout, sizeof(double) * nout, hipMemcpyDeviceToHost));
-    return 0;
-}); }
-
-// micro-benchmark of the row sweep (wg_rows) on device-resident random data: mode 1 = dots only (A x),
-// 2 = axpy only (A'y), 3 = both in one sweep; *ms = time per launch
-__global__ void k_fill_random(double* p, size_t n, uint64_t seed)
-{
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
-        p[i] = 2.0 * lcqp_u01(seed, i) - 1.0;
-}
-
-extern "C" int lcqp_hip_bench_rows(int batch, int m, int n, int mode, int repeat, float* ms)
-{ return guarded(g_err, [&] {
-    if (n <= 0 || n > 4096 || batch <= 0 || m <= 0) return LCQP_HIP_UNSUPPORTED;
-    const SizeKernels* k = dense_kernels(padded_nch(n));
-    if (!k) return LCQP_HIP_UNSUPPORTED;
-    const int np = 128 * k->nch;
-    DevMem tb;
-    double *dA, *dx, *dd, *dcf, *dout;
-    if (!tb.alloc(g_err, dA, (size_t)batch * m * np) || !tb.alloc(g_err, dx, (size_t)batch * np) || !tb.alloc(g_err, dd, (size_t)batch * m) ||
-        !tb.alloc(g_err, dcf, (size_t)batch * m) || !tb.alloc(g_err, dout, (size_t)batch * np))
-        return LCQP_HIP_ERROR;
-    hipLaunchKernelGGL(k_fill_random, dim3(2048), dim3(256), 0, 0, dA, (size_t)batch * m * np, 1ULL);
-    hipLaunchKernelGGL(k_fill_random, dim3(256), dim3(256), 0, 0, dx, (size_t)batch * np, 2ULL);
-    hipLaunchKernelGGL(k_fill_random, dim3(256), dim3(256), 0, 0, dcf, (size_t)batch * m, 3ULL);
-    const bool dots = mode & 1, axpy = mode & 2;
-    return time_launches(repeat, ms, [&] { k->util_rows(batch, 0, m, dA, dots ? dx : nullptr, dots ? dd : nullptr, axpy ? dcf : nullptr, axpy ? dout : nullptr); });
-}); }
-
-extern "C" int lcqp_hip_chol_solve(int batch, int n, const double* K, const double* b, double* x, int repeat, float* ms)
-{ return guarded(g_err, [&] {
-    if (n <= 0 || n > LCQP_MAX_ACTIVE || batch <= 0) return LCQP_HIP_UNSUPPORTED;   // k_chol / k_backsolve use the 35 KiB arena
-    const int np = ((n + 63) / 64) * 64, nblk = np / 64;
-    DevMem tb;
-    double *dF, *dscr, *drhs, *dx;
-    int* dfail;
-    if (!tb.alloc(g_err, dF, (size_t)batch * np * np) || !tb.alloc(g_err, dscr, (size_t)batch * 4096) || !tb.alloc(g_err, drhs, (size_t)batch * np) ||
-        !tb.alloc(g_err, dx, (size_t)batch * np) || !tb.alloc(g_err, dfail, batch))
-        return LCQP_HIP_ERROR;
-    // pad with a unit diagonal
-    {
-        std::vector<double> buf((size_t)np * np);
-        for (int bb = 0; bb < batch; bb++) {
-            std::fill(buf.begin(), buf.end(), 0.0);
-            for (int i = 0; i < n; i++) memcpy(&buf[(size_t)i * np], K + ((size_t)bb * n + i) * n, sizeof(double) * n);
-            for (int i = n; i < np; i++) buf[(size_t)i * np + i] = 1.0;
-            HIPCHK(g_err, hipMemcpy(dF + (size_t)bb * np * np, buf.data(), sizeof(double) * np * np, hipMemcpyHostToDevice));
-        }
-    }
-    int rc = upload_padded(drhs, b, batch, 1, n, np, 1); if (rc) return rc;
-    hipLaunchKernelGGL(k_chol, dim3(batch), dim3(WG), 0, 0, np, nblk, n, dF, dscr, dfail);
-    HIPCHK(g_err, hipDeviceSynchronize());
-    std::vector<int> fail(batch);
-    HIPCHK(g_err, hipMemcpy(fail.data(), dfail, sizeof(int) * batch, hipMemcpyDeviceToHost));
-    for (int i = 0; i < batch; i++) if (fail[i]) { g_err = "matrix not positive definite"; return LCQP_SUBPROBLEM_SOLVER_ERROR; }
-    rc = time_launches(repeat, ms, [&] { hipLaunchKernelGGL(k_backsolve, dim3(batch), dim3(WG), 0, 0, np, nblk, dF, drhs, dx); });
-    return rc ? rc : download_padded(x, dx, batch, 1, n, np, 1);
 }); }

@@ -1,0 +1,67 @@
+// lcqp_hip_batch.hpp -- what the three host units of the dense arm share: the batch handle behind lcqp_hip_batch_t, the functions of
+// lcqp_hip.hip that the QP object (lcqp_hip_qp.hip) and the building blocks (lcqp_hip_util.hip) call on it, and the arm's error slot.
+// Internal: nothing of it enters the dynamic symbol table of the library.  Host code only.
+#pragma once
+#include "lcqp_launch.hpp"
+#include "lcqp_host_rt.hpp"
+
+#include <string>
+#include <vector>
+
+#pragma GCC visibility push(hidden)
+
+// the error slot of the dense arm (one thread_local string, defined in lcqp_hip.hip): what lcqp_hip_last_error returns for all three units
+std::string& dense_err();
+
+// a pinned staging slot of loadLCQP and the event of the copies that last read it
+struct StageSlot {
+    void* buf = nullptr;
+    lcqp_rt::Event done{hipEventDisableTiming};
+    ~StageSlot() { if (buf) (void)hipHostFree(buf); }
+};
+
+// The members are released in reverse order after the destructor's synchronisation: device memory, staging slots, events, streams.
+struct lcqp_hip_batch {
+    lcqp::DevBatch db;
+    int device;
+    // the setup has two independent branches (C = L'R + R'L and its compression; L1 -> Et -> M): the short one runs on `side`
+    lcqp_rt::Stream stream, side;
+    lcqp_rt::Event ev0, ev1, ev2;         // run: setup from ev0 to ev1, homotopy from ev1 to ev2
+    lcqp_rt::Event evFork{hipEventDisableTiming}, evJoin{hipEventDisableTiming};
+    // two pinned staging slots for loadLCQP: instance k is packed into slot k&1 while slot (k-1)&1 is in flight
+    StageSlot stage[2];
+    size_t stageBytes = 0;
+    lcqp_rt::DevMem mem{stream};
+    int numCU = 256;
+    bool overlapped = false;      // lcqp_hip_batch_set_overlapped
+    bool ran = false, anyLoaded = false;
+    // re-solves and sensitivities (lcqp_host_rt.hpp).  boxed: which variables of an instance carry a finite box bound -- those are rows of
+    // E, hence of Et and M: an update must keep the set
+    lcqp_rt::ResolveState rs;
+    std::vector<char> boxed;              // [B][n]
+    lcqp_rt::SensBuffers sens;            // of k_sensitivity
+    lcqp_rt::SensBuffers sensBlk;         // of k_sensitivity_blk (another pitch of db, a varying number of instances)
+    size_t jacStaging = LCQP_JACOBIAN_STAGING_BYTES;      // device bytes a Jacobian / adjoint call may stage per chunk of instances
+    // of lcqp_hip_batch_adjoint, grown on demand: the upstream gradients on the duals [B][nd]; the matrix gradients of one chunk
+    double *adjVy = nullptr, *adjOut = nullptr;
+    size_t adjVyCap = 0, adjOutCap = 0;
+    lcqp_rt::Event adjEv0, adjEv1;        // around the last matrix-gradient launch
+    int nch;
+    const lcqp::SizeKernels* k = nullptr; // the launch table of the padded size (dense_kernels), set by lcqp_hip_batch_create
+    explicit lcqp_hip_batch(int dev) : db(), device(dev) {}
+    ~lcqp_hip_batch() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
+};
+
+// padded size of a problem with n variables in units of 128: 1, 2, 3, 4, then 8 (np = 1024), 16 (np = 2048) and 32 (np = 4096)
+inline int padded_nch(int n) { const int k = (n + 127) / 128; return k > 16 ? 32 : (k > 8 ? 16 : (k > 4 ? 8 : k)); }
+
+// lcqp_hip.hip; the comments are at the definitions
+const lcqp::SizeKernels* dense_kernels(int nch);
+const lcqp::RunKernels& run_kernels(const lcqp_hip_batch* h);
+int launch_setup(lcqp_hip_batch* h);
+int batch_sensitivity(lcqp_hip_batch* h, bool blk, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
+int batch_jacobian(lcqp_hip_batch* h, int first, int count, double* Jg, double* Jb, int* side, int* info);
+int batch_adjoint(lcqp_hip_batch* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
+                  int reduce, double* dQ, double* dA, double* dL, double* dR);
+
+#pragma GCC visibility pop

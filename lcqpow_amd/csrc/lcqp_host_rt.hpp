@@ -1,4 +1,4 @@
-// lcqp_host_rt.hpp -- host runtime shared by the C ABIs of the dense (lcqp_hip.hip) and sparse (lcqp_sparse_host.hip) arms: error reporting,
+// lcqp_host_rt.hpp -- host runtime shared by the C ABIs of the dense (lcqp_hip.hip, lcqp_hip_qp.hip, lcqp_hip_util.hip) and sparse (lcqp_sparse_host.hip) arms: error reporting,
 // owners of streams, events and device memory, and the entry-point bodies both arms have in common.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -12,10 +12,13 @@
 
 namespace lcqp_rt {
 
-// "<call>: <HIP reason>" into an arm's error slot (lcqp_hip_last_error / lcqp_hip_sparse_last_error)
+// "<call>: <HIP reason>" into an arm's error slot (lcqp_hip_last_error / lcqp_hip_sparse_last_error).  The runtime also keeps the error
+// as the thread's last one until it is asked for: it is taken here, or the hipGetLastError() behind the next launch of the thread --
+// of any handle -- would report this call's failure as that launch's.
 inline int hip_fail(std::string& slot, const char* call, hipError_t e)
 {
     slot = std::string(call) + ": " + hipGetErrorString(e);
+    (void)hipGetLastError();
     return LCQP_HIP_ERROR;
 }
 #define HIPCHK(slot, call)                                                 \

@@ -1,4 +1,4 @@
-// lcqp_launch.hpp -- the seam between the host translation unit (lcqp_hip.hip) and the per-size kernel translation units
+// lcqp_launch.hpp -- the seam between the host translation units (lcqp_hip.hip, lcqp_hip_qp.hip, lcqp_hip_util.hip) and the per-size kernel translation units
 // (lcqp_nch.hip, one per NCH in {1,2,3,4,8,16,32} and a second one of the two persistent kernels for NCH <= 4): per padded size one table
 // of launch functions, each with the arguments its kernel takes.  `grid` is the number of workgroups; every launch is asynchronous on
 // `s`.  Declarations only: no device code lives here.

@@ -85,6 +85,31 @@ def test_c_abi_rejects_bad_arguments_without_a_gpu():
         L.lcqp_hip_qp_destroy(ctypes.c_void_p(q))
 
 
+def test_qp_solve_failure_leaves_a_message():
+    """A failing lcqp_hip_qp_solve sets exit_flag = -1, returns SUBPROBLEM_SOLVER_ERROR and leaves the failing HIP call in
+    lcqp_hip_last_error().  A device index far out of range is a runtime argument error with or without a GPU: lcqp_hip_qp_create touches
+    no device and succeeds, the first solve cannot build its batch.  This is the one failure a valid device-free call reaches (the message
+    is lcqp_hip_batch_create's); the HIP calls of the solve behind it fail only where a device fails.
+    The error is reported once: hip_fail takes it from the runtime, whose hipGetLastError() -- the check behind every launch of the
+    thread, of any handle -- would otherwise hand it to the next launch."""
+    import numpy as np
+    import lcqpow_amd as la
+    from lcqpow_amd import capi
+    L = la.lib()
+    Q = np.eye(2); g = np.zeros(2); dp = ctypes.POINTER(ctypes.c_double)
+    assert L.lcqp_hip_qp_create(0, 0, Q.ctypes.data_as(dp), None, None, 0) is None and capi.last_error() == "invalid arguments"
+    q = L.lcqp_hip_qp_create(2, 0, Q.ctypes.data_as(dp), None, None, 1 << 20)
+    assert q is not None
+    it, ef = ctypes.c_int(7), ctypes.c_int(7)
+    rc = L.lcqp_hip_qp_solve(ctypes.c_void_p(q), 1, ctypes.byref(it), ctypes.byref(ef), g.ctypes.data_as(dp), None, None, None, None, None, None)
+    assert rc == capi.SUBPROBLEM_SOLVER_ERROR and ef.value == -1 and it.value == 0
+    assert capi.last_error().startswith("hipSetDevice(device): "), capi.last_error()      # not the stale message of the call before
+    if la.device_count() > 0:      # (without a device every call of the runtime, hipGetLastError() included, returns hipErrorNoDevice)
+        runtime = [ln.split()[-1] for ln in open("/proc/self/maps") if "libamdhip64" in ln]       # the HIP runtime the library is linked to
+        assert runtime and ctypes.CDLL(runtime[0]).hipGetLastError() == 0                         # hipSuccess: nothing left for a later launch check
+    L.lcqp_hip_qp_destroy(ctypes.c_void_p(q))
+
+
 def test_sparse_kkt_probe_checks_its_arguments_without_a_gpu():
     """lcqp_hip_sparse_kkt_probe (test and diagnostic entry point of the sparse arm): nrhs < 1, NULL vectors, a mode other than FACTOR / STORED, a
     FACTOR call without its inputs, a STORED call with a bad slot or without its record buffers are LCQP_INVALID_ARGUMENT; with good arguments a

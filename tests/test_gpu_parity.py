@@ -167,6 +167,50 @@ def test_subsolver_warm_start_duals(hip, oracle):
     q1.close(); q2.close()
 
 
+def test_subsolver_clone_owns_its_batch(hip):
+    """lcqp_hip_qp_clone copies the problem data, the options, the last solution and the counters, never the batch: a clone builds its own
+    device state in its first solve, whether it was taken before or after the original's first solve, and outlives the original.  The same
+    QP through two objects gives the same bits (no atomics in the kernels); a hot start is held to the QP's KKT conditions at the
+    tolerances of test_subsolver_matches_oracle_and_kkt."""
+    n, m = 24, 12
+    r = np.random.default_rng(5)
+    M = r.standard_normal((n, n)); Q = M.T @ M / n + np.eye(n)
+    A = r.standard_normal((m, n)) / np.sqrt(n); xs = r.standard_normal(n)
+    lbA = A @ xs - r.uniform(0.1, 1, m); ubA = A @ xs + r.uniform(0.1, 1, m)
+    lbA[:2] = ubA[:2]                                                  # two equalities
+    lb = np.full(n, -np.inf); ub = np.full(n, np.inf)
+    lb[:4] = xs[:4] - r.uniform(0.1, 1, 4); ub[:4] = xs[:4] + r.uniform(0.1, 1, 4)      # box bounds on four variables
+    g = r.standard_normal(n)
+    # (a) clone before the first solve
+    qa = hip.SubsolverHIP(n, m, Q, A); qb = qa.clone()
+    ra = qa.solve(True, g, lbA, ubA, np.zeros(n), None, lb, ub); rb = qb.solve(True, g, lbA, ubA, np.zeros(n), None, lb, ub)
+    assert ra == rb and (ra[0], ra[2]) == (0, 0), (ra, rb)
+    (xa, ya), (xb, yb) = qa.getSolution(), qb.getSolution()
+    assert np.array_equal(xa, xb) and np.array_equal(ya, yb)
+    qa.close(); qb.close()
+    # (b) clone after a solve; the original goes first
+    qa = hip.SubsolverHIP(n, m, Q, A)
+    ra = qa.solve(True, g, lbA, ubA, np.zeros(n), None, lb, ub)
+    assert (ra[0], ra[2]) == (0, 0)
+    (xa, ya), ca = qa.getSolution(), qa.counters()
+    qb = qa.clone()
+    assert all(np.array_equal(u, v) for u, v in zip(qb.getSolution(), (xa, ya))) and qb.counters() == ca
+    qa.close()
+    rb = qb.solve(False, g, lbA, ubA, np.zeros(n), None, lb, ub)      # not an initial solve, but no batch yet: a fresh setup of its own
+    assert rb == ra, (ra, rb)
+    xb, yb = qb.getSolution()
+    assert np.array_equal(xa, xb) and np.array_equal(ya, yb)
+    assert qb.counters() == {k: 2 * v for k, v in ca.items()}          # the counters it took over plus the same work once more
+    g2 = g + 0.2 * r.standard_normal(n)
+    rb = qb.solve(False, g2, lbA, ubA, None, None, lb, ub)              # the same bound pattern: a hot start
+    assert (rb[0], rb[2]) == (0, 0), rb
+    xb, yb = qb.getSolution()
+    stat, pf, cs = P.kkt_residuals(Q, g2, A, lbA, ubA, lb, ub, xb, yb)
+    print("hot start of the clone: stat %.3g pf %.3g cs %.3g" % (stat, pf, cs))
+    assert stat < 1e-10 and pf < 1e-8 and cs < 1e-8
+    qb.close()
+
+
 @pytest.mark.parametrize("n", [100, 256, 300, 512, 700, 1024, 1500, 2048, 3000, 4096])
 def test_row_list_sweep(hip, n):
     """wg_rows through a row list with row-indexed scalars (stage 1 / stage 2 of the subsolver's trials) on its own, every padded size

@@ -2,7 +2,7 @@
 
     python tools/gpu_ab.py [--rounds R] [--batch B] name=path/to/lib.so ...
 
-Each variant is a build of lcqpow_amd/csrc/lcqp_hip.hip (e.g. with -DLCQP_ONLY_NCH=2 -DLCQP_MINWAVES=..), loaded through its own
+Each variant is a build of the library (build_hip of __graft_entry__.py with out=, defines= and only_nch=; e.g. with -DLCQP_ONLY_NCH=2 -DLCQP_MINWAVES=..), loaded through its own
 ctypes handle.  Prints per variant: median / min of the setup and homotopy kernel times (HIP events on the launch stream),
 solved count, work counters, and the largest difference of the solutions from the first variant.
 """
