@@ -7,6 +7,7 @@ printed.  The targets are solutions of the same LCQPs for other linear terms, so
     python examples/sensitivity.py sparse      # the same fit on the sparse arm: 16 banded LCQPs (n = 64), lcqp_hip_sparse_sensitivity
     python examples/sensitivity.py jacobian    # the full Jacobians dx/dg of the 64 LCQPs (lcqp_hip_batch_jacobian): |Jg - Jg'| and the kernel time
     python examples/sensitivity.py adjoint     # learn ONE constraint matrix A shared by the 64 LCQPs from a loss on x and y (lcqp_hip_batch_adjoint)
+    python examples/sensitivity.py sparse adjoint   # learn ONE value array of [A; L; R] shared by 16 banded LCQPs (lcqp_hip_sparse_adjoint)
 """
 import os
 import sys
@@ -55,6 +56,37 @@ def sparse_main():
     sb.close()
 
 
+def sparse_adjoint_main():
+    """the OptNet setting on the sparse arm: the 16 LCQPs share the values of E = [A; L; R] on the pattern; targets (x, y) come from the true
+    values, the fit starts from disturbed ones (the rows of A only: L and R stay the selectors they are)"""
+    from lcqpow_amd import synth_sparse as S
+    Bs, ns, nCs, nKs = 16, 64, 32, 8
+    rng = np.random.default_rng(0)
+    Qpat, Apat, qo, eo = S.sparse_pattern_arrays(ns, nCs, nKs)
+    inst = [S.sparse_values(i, ns, nCs, nKs, orders=(qo, eo)) for i in range(Bs)]
+    st = lambda k: np.stack([d[k] for d in inst])
+    Ex_true = inst[0]["Ex"]
+    in_A = np.asarray(Apat.indices) < nCs      # the entries of the stacked pattern that belong to rows of A
+    sb = la.SparseBatchLCQP(Bs, ns, nCs, nKs, Qpat, Apat, opt=la.default_options(perturbStep=0))
+    assert sb.load(0, Bs, st("Qx"), st("g"), np.stack([Ex_true] * Bs), lbA=st("lbA"), ubA=st("ubA")) == 0
+    layer = SparseBatchLCQPLayer(sb, bounds=dict(lbA=st("lbA"), ubA=st("ubA")), values=dict(Qx=st("Qx"), Ax=Ex_true))
+    g = torch.as_tensor(st("g"))
+    with torch.no_grad():
+        xt, yt = layer.solve(g, Ax=torch.as_tensor(Ex_true))
+    Ax = torch.tensor(Ex_true + 0.02 * in_A * rng.standard_normal(Ex_true.shape), requires_grad=True)
+    opt = torch.optim.SGD([Ax], lr=0.02)
+    for step in range(12):
+        opt.zero_grad()
+        x, y = layer.solve(g, Ax=Ax)      # a shared [nnzA] tensor: load + run; Ax.grad is summed over the batch on the device
+        loss = 0.5 * ((x - xt) ** 2).sum() + 0.5 * ((y - yt) ** 2).sum()
+        loss.backward()
+        Ax.grad *= torch.as_tensor(in_A, dtype=Ax.dtype)
+        opt.step()
+        print("step %2d  mean loss per LCQP %.6e  |Ax - Ax_true|_max %.3e  flagged instances %d"
+              % (step, loss.item() / Bs, float(np.abs(Ax.detach().numpy() - Ex_true).max()), int(np.count_nonzero(layer.info))))
+    sb.close()
+
+
 def adjoint_main():
     """the OptNet setting: the 64 LCQPs share Q and A; targets (x, y) come from the true A, the fit starts from a disturbed one"""
     rng = np.random.default_rng(0)
@@ -85,6 +117,8 @@ def main():
         raise SystemExit("needs a GPU (the product path has no CPU fallback)")
     if sys.argv[1:] == ["sparse"]:
         return sparse_main()
+    if sys.argv[1:] == ["sparse", "adjoint"]:
+        return sparse_adjoint_main()
     if sys.argv[1:] == ["adjoint"]:
         return adjoint_main()
     rng = np.random.default_rng(0)

@@ -398,6 +398,30 @@ int  lcqp_hip_sparse_launch_counts(lcqp_hip_sparse_t* s, int out[2]);   /* full 
 int  lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* s, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
 /* kernel time of the last lcqp_hip_sparse_sensitivity launch of this handle, ms (HIP events around k_sparse_sensitivity, the copies excluded) */
 int  lcqp_hip_sparse_sensitivity_timing(lcqp_hip_sparse_t* s, float* kernel_ms);
+/* The full adjoint of the sparse batch (DESIGN.md section 3a''''; the twin of lcqp_hip_batch_adjoint): lcqp_hip_sparse_sensitivity with
+ * nrhs = 1, extended by upstream gradients on the returned duals and by the gradients on the stored entries of Q and of E = [A; L; R].  At the
+ * returned point x, y_W solve  Q x + g - E_W' y_W = 0,  E_W x = b_W  (y as lcqp_hip_sparse_get_solution returns it, [m], m = nC + 2 nComp, rows
+ * A, L, R: the multiplier of this penalty-free system).  For a loss l with vx = dl/dx [B][nV] and vy = dl/dy [B][m] (host; vy may be NULL =
+ * zero; its entries outside W are ignored: those duals are identically zero on the branch):
+ *   d, mu with  Q d + E_W' mu = vx,  E_W d = -vy_W;     dg = dl/dg = -d,   db_W = dl/db_W = mu   (dg, db, side, info as lcqp_hip_sparse_sensitivity)
+ *   dQx[k] = 1/2 (dg_i x_j + x_i dg_j)                   stored entry k = (i, j) of Q: the symmetric derivative.  Q is given as the full
+ *                                                        symmetric pattern; entries (i, j) and (j, i) are equal to the bit, and for a
+ *                                                        symmetric perturbation Z on the pattern  dl = sum_k dQx[k] Z[k]
+ *   dAx[k] = -(db_r x_j + y_r dg_j)                      stored entry k = (r, j) of the stacked pattern given to lcqp_hip_sparse_create, for
+ *                                                        the rows with side != 0; exactly zero elsewhere
+ * Both are in the order of Qx / Ax of lcqp_hip_sparse_load (the caller's CSC order).  reduce = 0: dQx [B][nnzQ], dAx [B][nnzA], computed in
+ * chunks of instances whose staging stays below the cap of lcqp_hip_sparse_set_adjoint_staging (the results do not depend on the chunking).
+ * reduce = 1: [nnzQ], [nnzA]: the sums over the batch (one value array shared by the instances), formed on the device in the order of the
+ * batch -- the same bits on every call; an instance with info & 1 contributes zeros, every other flagged instance what the kernels computed.
+ * db, side, info, dQx, dAx may be NULL.
+ * With vy == NULL and no matrix output the call is lcqp_hip_sparse_sensitivity with nrhs = 1, to the bit.  It reads the batch and changes none
+ * of it.  lcqp_hip_sparse_sensitivity_timing then reports the sum of its kernels.
+ * LCQP_INVALID_ARGUMENT: NULL handle, vx or dg, or reduce outside 0 / 1.  Then LCQP_LCQPOBJECT_NOT_SETUP as lcqp_hip_sparse_sensitivity.  Both
+ * are decided before any device call. */
+int  lcqp_hip_sparse_adjoint(lcqp_hip_sparse_t* s, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
+                             int reduce, double* dQx, double* dAx);
+/* another staging cap for this handle's adjoint calls (0: the default, LCQP_JACOBIAN_STAGING_BYTES); for tests of the chunking and for small devices */
+int  lcqp_hip_sparse_set_adjoint_staging(lcqp_hip_sparse_t* s, size_t bytes);
 /* Test and diagnostic entry point (as lcqp_hip_batch_read_setup / _read_working_set on the dense arm): the KKT factorisations and solves
  * of the sparse arm -- the register band, the LDS-window band, the bordered band, the general LDL' -- run for every instance of the batch
  * on matrices the caller names, one solve per right-hand side and NO refinement, so that tests/test_gpu_sparse_factor.py can hold each engine

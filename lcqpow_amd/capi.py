@@ -150,6 +150,8 @@ def lib():
         L.lcqp_hip_sparse_launch_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.lcqp_hip_sparse_sensitivity.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_sparse_sensitivity_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.lcqp_hip_sparse_adjoint.argtypes = [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p, C.c_int] + [c_double_p] * 2
+        L.lcqp_hip_sparse_set_adjoint_staging.argtypes = [C.c_void_p, C.c_size_t]
         L.lcqp_hip_sparse_kkt_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p,
                                                 c_double_p, c_double_p, c_int_p]
         _lib = L
@@ -839,6 +841,24 @@ class SparseBatchLCQP(_Batch):
         rp = np.zeros(B); rd = np.zeros((B, m)); ru = np.zeros((B, m), dtype=np.int32)
         self._call("kkt_probe", 1, int(which), rhs.shape[1], None, None, None, _p(rhs), _p(sol), _p(rp), _p(rd), _ip(ru))
         return sol, dict(dprim=rp, ddual=rd, use=ru)
+
+    def adjoint(self, vx, vy=None, matrices=("Q", "A"), reduce=False, _staging_bytes=None):
+        """lcqp_hip_sparse_adjoint: the gradients of a loss that reads the x AND the y the last run / resolve returned (synchronous; DESIGN.md
+        section 3a'''').  vx = dl/dx [B][nV]; vy = dl/dy [B][m] in the layout of solution()'s y (rows A, L, R), or None for zero.  Returns a dict:
+        dg, db, side, info as sensitivity(vx) returns them, and under "Q" / "A" the gradients on the stored entries of Q and of the stacked
+        [A; L; R], in the order of load's Qx / Ax -- [B][nnz], or [nnz] summed over the batch on the device with reduce=True (one value array
+        shared by the instances).  "Q" holds the symmetric derivative: entries (i, j) and (j, i) are equal.  reduce=False goes in chunks of
+        instances under the staging cap (_staging_bytes: another cap for this one call, for tests).  The call changes nothing on the device."""
+        if _staging_bytes is not None:
+            self._call("set_adjoint_staging", int(_staging_bytes))
+        try:
+            f = self._sym("adjoint")
+            call = lambda vx, vy, dg, db, side, info, *m: f(self.h, vx, vy, dg, db, side, info, 1 if reduce else 0, *m)
+            return _adjoint(call, vx, vy, self.B, self.nV, self.m, dict(Q=(self.nnzQ,), A=(self.nnzA,)), matrices,
+                            () if reduce else (self.B,), check=self._check)
+        finally:
+            if _staging_bytes is not None:
+                self._call("set_adjoint_staging", 0)      # back to the default cap
 
     def load(self, first, count, Qx, g, Ax, lbA=None, ubA=None, lbL=None, ubL=None, lbR=None, ubR=None, x0=None, y0=None):
         n, nC, nK = self.nV, self.nC, self.nComp

@@ -156,9 +156,13 @@ __global__ __launch_bounds__(WGS) void k_sparse_refresh(SpBatch db, int mode, co
 // NV_QP (Q d) and MV_LX (lambda).
 //   v, dg [B][nrhs][n];  dbo [B][nrhs][m];  side [B][m]: 0 outside W, -1 at lower, +1 at upper, 2 equality;  sinfo [B]: flag bits
 //   (include/lcqp_hip.h), 0 = differentiable.
+// DUAL (DESIGN.md section 3a'''', lcqp_hip_sparse_adjoint): an upstream gradient vy [B][nrhs][m] on the returned duals joins the right-hand
+// side, K0 [d; lambda] = [v; -vy_W], so that E_W d = -vy_W.  The refinement carries it in its second block -- residual
+// [v - Q d - E_W'lambda; -vy_W - E_W d] -- and in the scale of the rounding floor (|vy_r| on the rows of W).  Entries of vy outside W are
+// loaded and dropped: whatever they hold, the bits are the same.  Without DUAL vy is not read at all, and the code is the one above.
 constexpr int SENS_REFINE_MAX = 4;
-template <int G>
-__global__ __launch_bounds__(WGS) void k_sparse_sensitivity(SpBatch db, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo)
+template <int G, bool DUAL>
+__global__ __launch_bounds__(WGS) void k_sparse_sensitivity(SpBatch db, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo, const double* vy)
 {
     const int b = blockIdx.x * (64 / G) + threadIdx.x / G;
     if (b >= db.B) return;
@@ -210,7 +214,11 @@ __global__ __launch_bounds__(WGS) void k_sparse_sensitivity(SpBatch db, int nrhs
             g_map<G, 8>(m, t, [&](int r) { return (double)lam[r]; }, [&](int r, double w) { ob[r] = w; });
         };
         g_map<G, 8>(n, t, [&](int i) { return ID{iperm[i], vk[i]}; }, [&](int i, ID w) { bv[w.i] = w.a; d[i] = 0.0; });
-        g_map<G, 8>(m, t, [&](int r) { return iperm[n + r]; }, [&](int r, int p) { bv[p] = 0.0; lam[r] = 0.0; });
+        const double* vyk = DUAL ? vy + ((size_t)b * nrhs + k) * m : nullptr;
+        if constexpr (DUAL)
+            g_map<G, 8>(m, t, [&](int r) { return I2D{st[r], iperm[n + r], vyk[r]}; }, [&](int r, I2D w) { bv[w.b] = (w.a != ST_INACT) ? -w.y : 0.0; lam[r] = 0.0; });
+        else
+            g_map<G, 8>(m, t, [&](int r) { return iperm[n + r]; }, [&](int r, int p) { bv[p] = 0.0; lam[r] = 0.0; });
         g_sync();
         for (int it = 0;; it++) {
             sp_solve<G>(c, false, bv);
@@ -227,8 +235,17 @@ __global__ __launch_bounds__(WGS) void k_sparse_sensitivity(SpBatch db, int nrhs
             sp_ell<G, true>(db.ellT, c.gl, c.Ex(), [&](int r) { return D2{(st[r] != ST_INACT) ? (double)lam[r] : 0.0, 0.0}; },
                             [&](int i) { return ID2{iperm[i], vk[i], qd[i]}; },
                             [&](int, double s, double, ID2 w) { const double rv = (w.v - w.y) - s; bv[w.s] = rv; mx = nmax(mx, fabs(rv)); sc = fmax(sc, fabs(w.v) + fabs(w.y) + fabs(s)); });
-            sp_ell<G, false>(db.ellE, c.gl, c.Ex(), [&](int j) { return D2{d[j], 0.0}; }, [&](int r) { return I2{st[r], iperm[n + r]}; },
-                             [&](int, double s, double, I2 w) { const double rv = (w.a != ST_INACT) ? -s : 0.0; bv[w.b] = rv; mx = nmax(mx, fabs(rv)); });
+            if constexpr (DUAL)
+                sp_ell<G, false>(db.ellE, c.gl, c.Ex(), [&](int j) { return D2{d[j], 0.0}; }, [&](int r) { return I2D{st[r], iperm[n + r], vyk[r]}; },
+                                 [&](int, double s, double, I2D w) {
+                                     const bool in = w.a != ST_INACT;
+                                     const double rv = in ? -w.y - s : 0.0;
+                                     bv[w.b] = rv; mx = nmax(mx, fabs(rv));
+                                     if (in) sc = fmax(sc, fabs(w.y) + fabs(s));
+                                 });
+            else
+                sp_ell<G, false>(db.ellE, c.gl, c.Ex(), [&](int j) { return D2{d[j], 0.0}; }, [&](int r) { return I2{st[r], iperm[n + r]}; },
+                                 [&](int, double s, double, I2 w) { const double rv = (w.a != ST_INACT) ? -s : 0.0; bv[w.b] = rv; mx = nmax(mx, fabs(rv)); });
             g_sync();
             SPROF(c, SP_PRODUCTS);
             const double res = g_max<G>(mx), scale = fmax(g_max<G>(sc), e1 * g_max<G>(dm));
@@ -558,13 +575,23 @@ static void sp_launch(const SpBatch& db, int cus, hipStream_t stream, hipEvent_t
     hipLaunchKernelGGL(k_sparse_sched<G>, dim3(waves), dim3(WGS), ldsBytes, stream, db);
 }
 
-// one launch of k_sparse_sensitivity<G> (DESIGN.md section 3a'') on device buffers
-template <int G>
-static void sp_launch_sensitivity(const SpBatch& db, hipStream_t stream, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo)
+// one launch of k_sparse_sensitivity<G, DUAL> (DESIGN.md sections 3a'', 3a'''') on device buffers
+template <int G, bool DUAL>
+static void sp_launch_sens(const SpBatch& db, hipStream_t stream, int nrhs, const double* v, const double* vy, double* dg, double* dbo, int* side, int* sinfo)
 {
     const int ipw = 64 / G, grid = (db.B + ipw - 1) / ipw;
     const size_t ldsBytes = (G == 64 && db.general) ? sizeof(double) * (size_t)ipw * group_lds_doubles(G) : 0;      // the window of the general solve
-    hipLaunchKernelGGL(k_sparse_sensitivity<G>, dim3(grid), dim3(WGS), ldsBytes, stream, db, nrhs, v, dg, dbo, side, sinfo);
+    hipLaunchKernelGGL((k_sparse_sensitivity<G, DUAL>), dim3(grid), dim3(WGS), ldsBytes, stream, db, nrhs, v, dg, dbo, side, sinfo, vy);
+}
+template <int G>
+static void sp_launch_sensitivity(const SpBatch& db, hipStream_t stream, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo)
+{
+    sp_launch_sens<G, false>(db, stream, nrhs, v, nullptr, dg, dbo, side, sinfo);
+}
+template <int G>
+static void sp_launch_sensitivity_dual(const SpBatch& db, hipStream_t stream, int nrhs, const double* v, const double* vy, double* dg, double* dbo, int* side, int* sinfo)
+{
+    sp_launch_sens<G, true>(db, stream, nrhs, v, vy, dg, dbo, side, sinfo);
 }
 
 // one launch of k_sparse_kkt_probe<G> on device buffers; the LDS of a factorisation (sp_launch), which covers the window of the general solve
@@ -584,7 +611,7 @@ namespace lcqp_sparse {
 template <int G>
 const SpKernels& sparse_kernels()
 {
-    static const SpKernels k = {G, sp_launch<G>, sp_launch_sensitivity<G>, sp_launch_kkt_probe<G>};
+    static const SpKernels k = {G, sp_launch<G>, sp_launch_sensitivity<G>, sp_launch_sensitivity_dual<G>, sp_launch_kkt_probe<G>};
     return k;
 }
 }

@@ -1,7 +1,9 @@
 // lcqp_sparse_host.hip -- the host side of the sparse arm: the C ABI lcqp_hip_sparse_* (include/lcqp_hip.h).  The handle, the pattern
-// analysis (lcqp_sparse_pattern.hpp) and the storage of a batch in create, load / update / run / resolve, sensitivities, the readers,
-// and the LCQP_SPARSE_* environment test hooks.  No kernel is defined here: they are in lcqp_sparse.hip, one translation unit per lane-group
-// width G, reached through the launch tables of lcqp_sparse_launch.hpp.
+// analysis (lcqp_sparse_pattern.hpp) and the storage of a batch in create, load / update / run / resolve, sensitivities, the full adjoint,
+// the readers, and the LCQP_SPARSE_* environment test hooks.  The kernels of the solver are not defined here: they are in lcqp_sparse.hip,
+// one translation unit per lane-group width G, reached through the launch tables of lcqp_sparse_launch.hpp.  The two kernels that do not
+// depend on the width -- the matrix gradients of lcqp_hip_sparse_adjoint -- sit beside the entry point that launches them, as
+// k_adjoint_outer / k_adjoint_reduce do in lcqp_hip.hip.
 #include "lcqp_sparse_launch.hpp"
 #include "lcqp_sparse_pattern.hpp"
 #include "lcqp_host_rt.hpp"
@@ -40,9 +42,122 @@ struct lcqp_hip_sparse {
     // rhoStart is allocated by the first resolve that carries penalties
     ResolveState rs;
     SensBuffers sens;
+    // of lcqp_hip_sparse_adjoint, grown on demand: the upstream gradients on the duals [B][m]; the gradients on the non-zeros of one chunk of
+    // instances; the device copy of csr2csc (one per pattern, uploaded by the first call that asks for dAx); the events around its kernels
+    size_t adjStaging = LCQP_JACOBIAN_STAGING_BYTES;
+    double *adjVy = nullptr, *adjOut = nullptr;
+    size_t adjVyCap = 0, adjOutCap = 0;
+    int* adjMap = nullptr;
+    Event adjEv0, adjEv1;
     explicit lcqp_hip_sparse(int dev) : db(), device(dev) {}
     ~lcqp_hip_sparse() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
 };
+
+// ---- the gradients on the non-zeros of an adjoint call (DESIGN.md section 3a'''', lcqp_hip_sparse_adjoint) ----------------------------------
+// With dg, db, side and info of k_sparse_sensitivity (nrhs = 1, still in its device buffers) and the returned x, y of instance b:
+//   stored entry k = (i, j) of Q:                 1/2 (dg_i x_j + x_i dg_j)     (the symmetric derivative);
+//   stored entry k = (r, j) of E = [A; L; R]:     -(db_r x_j + y_r dg_j)  where side_r != 0, exactly 0.0 elsewhere;
+// zero for an instance with info & 1.  The two products are rounded separately and then added (contraction is switched off in the two term
+// functions: __dmul_rn / __dadd_rn are plain operators to this compiler and would be fused): entry (j, i) of Q forms the products of entry
+// (i, j) in the other order, so the two are equal to the bit.  k runs over the CSR arrays of the
+// device (SpBatch::Qp / Qi, Erow / Ei); the outputs are in the caller's CSC order: for the symmetric pattern of Q that is the CSR order, for E
+// entry k goes to position emap[k] (the device copy of csr2csc).  Both kernels read x, y, the four buffers and the index arrays, nothing else.
+constexpr int SP_ADJ_WG = 256;
+struct SpAdjointArgs {
+    int B, n, m, nnzQ, nnzE;
+    const double *x, *y, *dg, *db;         // xout [B][n], yout [B][m], dg [B][n], db [B][m]
+    const int *side, *info;                // [B][m], [B]
+    const int *Qp, *Qi, *Erow, *Ei;        // row pointers and columns of Q; row and column of every entry of E
+    const int* emap;                       // [nnzE], null when outE is
+    double *outQ, *outE;                   // [count][nnzQ], [count][nnzE], or [nnzQ], [nnzE] summed over the batch; null: not asked for
+};
+
+// the row of entry k of a CSR pattern: the largest i with ptr[i] <= k
+__device__ __forceinline__ int sp_adjoint_row(const int* ptr, int rows, int k)
+{
+    int lo = 0, hi = rows;
+    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (ptr[mid] <= k) lo = mid; else hi = mid; }
+    return lo;
+}
+__device__ __forceinline__ double sp_adjoint_q(const SpAdjointArgs& a, int b, int i, int j)
+{
+#pragma clang fp contract(off)
+    if (a.info[b] & 1) return 0.0;
+    const double *x = a.x + (size_t)b * a.n, *g = a.dg + (size_t)b * a.n;
+    const double p0 = g[i] * x[j], p1 = x[i] * g[j];
+    return 0.5 * (p0 + p1);
+}
+__device__ __forceinline__ double sp_adjoint_e(const SpAdjointArgs& a, int b, int r, int j)
+{
+#pragma clang fp contract(off)
+    if ((a.info[b] & 1) || a.side[(size_t)b * a.m + r] == 0) return 0.0;
+    const double p0 = a.db[(size_t)b * a.m + r] * a.x[(size_t)b * a.n + j], p1 = a.y[(size_t)b * a.m + r] * a.dg[(size_t)b * a.n + j];
+    return -(p0 + p1);
+}
+
+// k_sparse_adjoint_nnz: the gradients of the instances [first, first + count), one value array per instance.  blockIdx.y 0: Q -- the threads
+// walk its count * nnzQ doubles as one array, two neighbours each (one 16-byte store; the segment starts on a 16-byte boundary); 1: E -- one
+// entry per thread, read in CSR order (coalesced gathers of the indices) and stored through the map.
+__global__ __launch_bounds__(SP_ADJ_WG) void k_sparse_adjoint_nnz(SpAdjointArgs a, int first, int count)
+{
+    const size_t tid = (size_t)blockIdx.x * SP_ADJ_WG + threadIdx.x, nth = (size_t)gridDim.x * SP_ADJ_WG;
+    if (blockIdx.y == 0) {
+        if (!a.outQ) return;
+        const size_t per = a.nnzQ, total = per * count;
+        for (size_t p = tid * 2; p < total; p += nth * 2) {
+            double v[2] = {0.0, 0.0};
+            for (int e = 0; e < 2; e++) {
+                const size_t f = p + e;
+                if (f >= total) break;
+                const size_t o = f / per;
+                const int k = (int)(f - o * per);
+                v[e] = sp_adjoint_q(a, first + (int)o, sp_adjoint_row(a.Qp, a.n, k), a.Qi[k]);
+            }
+            if (p + 1 < total) *reinterpret_cast<double2*>(a.outQ + p) = double2{v[0], v[1]};
+            else a.outQ[p] = v[0];
+        }
+    } else {
+        if (!a.outE) return;
+        const size_t per = a.nnzE, total = per * count;
+        for (size_t f = tid; f < total; f += nth) {
+            const size_t o = f / per;
+            const int k = (int)(f - o * per);
+            a.outE[o * per + a.emap[k]] = sp_adjoint_e(a, first + (int)o, a.Erow[k], a.Ei[k]);
+        }
+    }
+}
+
+// k_sparse_adjoint_reduce: the same terms summed over the batch (one Qx / Ax shared by the instances).  A thread owns its entries (two
+// neighbours of Q, one of E) and adds the instances' terms -- the very values k_sparse_adjoint_nnz writes -- in the order of the batch: no
+// atomics, the same bits on every call, and the rounding error of a sum of B numbers, (B - 1) eps/2 sum_b |term_b|.
+__global__ __launch_bounds__(SP_ADJ_WG) void k_sparse_adjoint_reduce(SpAdjointArgs a)
+{
+    const size_t tid = (size_t)blockIdx.x * SP_ADJ_WG + threadIdx.x, nth = (size_t)gridDim.x * SP_ADJ_WG;
+    if (blockIdx.y == 0) {
+        if (!a.outQ) return;
+        const size_t total = a.nnzQ;
+        for (size_t p = tid * 2; p < total; p += nth * 2) {
+            const bool two = p + 1 < total;
+            const int k0 = (int)p, k1 = two ? k0 + 1 : k0;
+            const int i0 = sp_adjoint_row(a.Qp, a.n, k0), j0 = a.Qi[k0], i1 = sp_adjoint_row(a.Qp, a.n, k1), j1 = a.Qi[k1];
+            double s0 = 0.0, s1 = 0.0;
+            for (int b = 0; b < a.B; b++) {
+                s0 += sp_adjoint_q(a, b, i0, j0);
+                s1 += sp_adjoint_q(a, b, i1, j1);
+            }
+            if (two) *reinterpret_cast<double2*>(a.outQ + p) = double2{s0, s1};
+            else a.outQ[p] = s0;
+        }
+    } else {
+        if (!a.outE) return;
+        for (size_t f = tid; f < (size_t)a.nnzE; f += nth) {
+            const int k = (int)f, r = a.Erow[k], j = a.Ei[k];
+            double s = 0.0;
+            for (int b = 0; b < a.B; b++) s += sp_adjoint_e(a, b, r, j);
+            a.outE[a.emap[k]] = s;
+        }
+    }
+}
 
 // Ordering [1] and the light regularisation of the polish are for batches whose Hessians are safely definite, judged by their diagonals
 // (min Q_ii >= 1e-6 max Q_ii in every loaded instance); the pivot check of sp_polish covers what the diagonals do not show.
@@ -347,22 +462,109 @@ extern "C" int lcqp_hip_sparse_launch_counts(lcqp_hip_sparse_t* h, int out[2])
     return launch_counts(h, out);
 }
 
-// ---- solution sensitivities (DESIGN.md section 3a''): one launch of k_sparse_sensitivity on the handle's stream, host buffers in and out ----
-extern "C" int lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
-{ return guarded(g_sp_err, [&] {
-    if (!h || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
-    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+// a device buffer of the handle with room for `count` doubles (the stream is drained before a smaller one is freed)
+static int sp_grow(lcqp_hip_sparse* h, double*& p, size_t& cap, size_t count)
+{
+    if (count <= cap) return 0;
+    HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));
+    h->mem.release(p);
+    p = nullptr; cap = 0;
+    if (!h->mem.alloc(g_sp_err, p, count)) return LCQP_HIP_ERROR;
+    cap = count;
+    return 0;
+}
+
+// ---- solution sensitivities (DESIGN.md section 3a''): one launch of k_sparse_sensitivity on the handle's stream, host buffers in and out,
+// its kernel time in *ms.  vy ([B][nrhs][m], host): the DUAL instantiation of lcqp_hip_sparse_adjoint ----
+static int sp_sensitivity_launch(lcqp_hip_sparse* h, int nrhs, const double* v, const double* vy, double* dg, double* db, int* side, int* info, float* ms)
+{
     SpBatch& d = h->db;
     SensBuffers& sb = h->sens;
     HIPCHK(g_sp_err, hipSetDevice(h->device));
     if (int rc = sb.reserve(g_sp_err, h->mem, h->stream, d.B, nrhs, d.n, d.n, d.m, d.m)) return rc;
     if (int rc = sb.upload(g_sp_err, v)) return rc;
+    if (vy) {
+        if (int rc = sp_grow(h, h->adjVy, h->adjVyCap, sb.rows * d.m)) return rc;
+        HIPCHK(g_sp_err, hipMemcpyAsync(h->adjVy, vy, sizeof(double) * sb.rows * d.m, hipMemcpyHostToDevice, h->stream));
+    }
     HIPCHK(g_sp_err, hipEventRecord(sb.ev0, h->stream));
-    sp_kernels(d.G)->sensitivity(d, h->stream, nrhs, sb.v, sb.dg, sb.db, sb.side, sb.info);
+    if (vy) sp_kernels(d.G)->sensitivity_dual(d, h->stream, nrhs, sb.v, h->adjVy, sb.dg, sb.db, sb.side, sb.info);
+    else sp_kernels(d.G)->sensitivity(d, h->stream, nrhs, sb.v, sb.dg, sb.db, sb.side, sb.info);
     HIPCHK(g_sp_err, hipGetLastError());
     HIPCHK(g_sp_err, hipEventRecord(sb.ev1, h->stream));
     if (int rc = sb.download(g_sp_err, dg, db, side, info, d.n, d.m)) return rc;
-    HIPCHK(g_sp_err, hipEventElapsedTime(&h->rs.sensMs, sb.ev0, sb.ev1));
+    HIPCHK(g_sp_err, hipEventElapsedTime(ms, sb.ev0, sb.ev1));
+    return 0;
+}
+
+extern "C" int lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
+{ return guarded(g_sp_err, [&] {
+    if (!h || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return sp_sensitivity_launch(h, nrhs, v, nullptr, dg, db, side, info, &h->rs.sensMs);
+}); }
+
+// ---- the full adjoint (DESIGN.md section 3a''''): k_sparse_sensitivity (with vy: its DUAL instantiation) on the whole batch, its results to
+// the host; then, on the device buffers it left, the gradients on the non-zeros that were asked for: k_sparse_adjoint_reduce once, or
+// k_sparse_adjoint_nnz per chunk of instances under the staging cap ----
+static int sp_adjoint(lcqp_hip_sparse* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info, int reduce, double* dQx, double* dAx)
+{
+    SpBatch& d = h->db;
+    float ms = 0.f;
+    if (int rc = sp_sensitivity_launch(h, 1, vx, vy, dg, db, side, info, &ms)) return rc;
+    const size_t nq = dQx ? (size_t)d.nnzQ : 0, ne = dAx ? (size_t)d.nnzE : 0, perInst = nq + ne;
+    if (perInst) {
+        for (hipError_t e : {h->adjEv0.status, h->adjEv1.status}) if (e != hipSuccess) return hip_fail(g_sp_err, "hipEventCreate", e);
+        if (dAx && !h->adjMap) {      // the one map of the pattern; a permutation of the positions of the caller's value array
+            for (int k : h->csr2csc) if (k < 0 || k >= d.nnzE) { g_sp_err = "adjoint: the value map of the pattern is out of range"; return LCQP_HIP_ERROR; }
+            if ((int)h->csr2csc.size() != d.nnzE) { g_sp_err = "adjoint: the value map of the pattern has the wrong length"; return LCQP_HIP_ERROR; }
+            if (!h->mem.alloc(g_sp_err, h->adjMap, h->csr2csc.size(), h->csr2csc.data())) return LCQP_HIP_ERROR;
+        }
+        const SensBuffers& sb = h->sens;
+        size_t chunk = 1;
+        if (!reduce) {
+            chunk = h->adjStaging / (sizeof(double) * perInst);
+            if (chunk < 1) chunk = 1;
+            if (chunk > (size_t)d.B) chunk = d.B;
+        }
+        if (int rc = sp_grow(h, h->adjOut, h->adjOutCap, chunk * perInst + 2)) return rc;      // (+ 2: both segments start on an even offset)
+        SpAdjointArgs a = {d.B, d.n, d.m, d.nnzQ, d.nnzE, d.xout, d.yout, sb.dg, sb.db, sb.side, sb.info, d.Qp, d.Qi, d.Erow, d.Ei, h->adjMap, nullptr, nullptr};
+        for (size_t c0 = 0; c0 < (reduce ? (size_t)1 : (size_t)d.B); c0 += chunk) {
+            const size_t cb = reduce ? 1 : std::min(chunk, (size_t)d.B - c0);
+            const size_t cq = cb * nq, ce = cb * ne;
+            a.outQ = dQx ? h->adjOut : nullptr;
+            a.outE = dAx ? h->adjOut + cq + (cq & 1) : nullptr;
+            // a thread of the Q segment owns two neighbouring entries, one of the E segment one entry
+            const unsigned gx = (unsigned)std::min<size_t>((std::max((cq + 1) / 2, ce) + SP_ADJ_WG - 1) / SP_ADJ_WG, 65535);
+            HIPCHK(g_sp_err, hipEventRecord(h->adjEv0, h->stream));
+            if (reduce) hipLaunchKernelGGL(k_sparse_adjoint_reduce, dim3(gx, 2), dim3(SP_ADJ_WG), 0, h->stream, a);
+            else hipLaunchKernelGGL(k_sparse_adjoint_nnz, dim3(gx, 2), dim3(SP_ADJ_WG), 0, h->stream, a, (int)c0, (int)cb);
+            HIPCHK(g_sp_err, hipGetLastError());
+            HIPCHK(g_sp_err, hipEventRecord(h->adjEv1, h->stream));
+            if (dQx) HIPCHK(g_sp_err, hipMemcpyAsync(dQx + c0 * nq, a.outQ, sizeof(double) * cq, hipMemcpyDeviceToHost, h->stream));
+            if (dAx) HIPCHK(g_sp_err, hipMemcpyAsync(dAx + c0 * ne, a.outE, sizeof(double) * ce, hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));
+            float t = 0.f;
+            HIPCHK(g_sp_err, hipEventElapsedTime(&t, h->adjEv0, h->adjEv1));
+            ms += t;
+        }
+    }
+    h->rs.sensMs = ms;
+    return 0;
+}
+
+extern "C" int lcqp_hip_sparse_adjoint(lcqp_hip_sparse_t* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
+                                       int reduce, double* dQx, double* dAx)
+{ return guarded(g_sp_err, [&] {
+    if (!h || !vx || !dg || (reduce != 0 && reduce != 1)) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return sp_adjoint(h, vx, vy, dg, db, side, info, reduce, dQx, dAx);
+}); }
+
+extern "C" int lcqp_hip_sparse_set_adjoint_staging(lcqp_hip_sparse_t* h, size_t bytes)
+{ return guarded(g_sp_err, [&] {
+    if (!h) return LCQP_INVALID_ARGUMENT;
+    h->adjStaging = bytes ? bytes : (size_t)LCQP_JACOBIAN_STAGING_BYTES;
     return 0;
 }); }
 

@@ -126,13 +126,15 @@ constexpr int GEN_META = 12;      // ints per front of SpBatch::gMeta
 // SpRunFn: the launches of a run on `stream` -- k_sparse_setup<G>, or with `refresh` k_sparse_refresh<G>(mode, rho0) in its place, `mid`
 // recorded behind it, then the homotopy (k_sparse_sched_init, k_sparse_sched<G>).  cus: compute units of the device the batch lives on
 // (the persistent wavefronts of k_sparse_sched are at most what it holds at once).
-// SpSensitivityFn: one launch of k_sparse_sensitivity<G> on `stream` over device buffers (layouts at the kernel).
+// SpSensitivityFn: one launch of k_sparse_sensitivity<G, false> on `stream` over device buffers (layouts at the kernel).
+// SpSensitivityDualFn: k_sparse_sensitivity<G, true>, which adds the upstream gradients on the duals vy [B][nrhs][m] (lcqp_hip_sparse_adjoint).
 using SpRunFn = void(const SpBatch& db, int cus, hipStream_t stream, hipEvent_t mid, bool refresh, int mode, const double* rho0);
 using SpSensitivityFn = void(const SpBatch& db, hipStream_t stream, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo);
+using SpSensitivityDualFn = void(const SpBatch& db, hipStream_t stream, int nrhs, const double* v, const double* vy, double* dg, double* dbo, int* side, int* sinfo);
 // SpKktProbeFn: one launch of k_sparse_kkt_probe<G> on `stream` over device buffers (layouts and modes at the kernel).
 using SpKktProbeFn = void(const SpBatch& db, hipStream_t stream, int mode, int which, int nrhs, const double* dprim, const double* ddual, const int* use,
                           const double* rhs, double* sol, double* recP, double* recD, int* recU);
-struct SpKernels { int G; SpRunFn* run; SpSensitivityFn* sensitivity; SpKktProbeFn* kkt_probe; };
+struct SpKernels { int G; SpRunFn* run; SpSensitivityFn* sensitivity; SpSensitivityDualFn* sensitivity_dual; SpKktProbeFn* kkt_probe; };
 // defined in lcqp_sparse.hip and instantiated there for G = LCQP_TU_G
 template <int G> const SpKernels& sparse_kernels();
 #pragma GCC visibility pop

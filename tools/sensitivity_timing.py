@@ -18,7 +18,13 @@ then jacobian() beside the vector call on an uploaded identity, kernel time and 
 --adjoint: lcqp_hip_batch_adjoint with all four matrix gradients on the BASELINE shape and on (40, 20, 8), B = 1024 (256 with --quick):
 reduce = 1 (k_adjoint_reduce, (nV + mA) nV doubles to the host) beside reduce = 0 (k_adjoint_outer in chunks, B times as many) on the same
 handle in the same process, the calls interleaved; kernel time (the sum of the call's kernels, k_sensitivity included) and wall clock.
-    python tools/sensitivity_timing.py --adjoint [--quick] [--log FILE] [--reps 20]"""
+    python tools/sensitivity_timing.py --adjoint [--quick] [--log FILE] [--reps 20]
+
+--sparse --adjoint: lcqp_hip_sparse_adjoint with both value-array gradients on the sparse synthetic workload, (512, 256, 64) with B = 1024
+(256 with --quick) on the band engine: reduce = 1 (k_sparse_adjoint_reduce, nnzQ + nnzA doubles to the host) beside reduce = 0
+(k_sparse_adjoint_nnz in chunks, B times as many) on the same handle in the same process, the calls interleaved; kernel time (the sum of the
+call's kernels, k_sparse_sensitivity<G, true> included) and wall clock.
+    python tools/sensitivity_timing.py --sparse --adjoint [--quick] [--log FILE] [--reps 20]"""
 import argparse
 import os
 import sys
@@ -157,6 +163,44 @@ def measure_adjoint(B, n, nC, nComp, reps, warmup=3):
     return line
 
 
+def measure_sparse_adjoint(B, n, nC, nK, reps, warmup=3):
+    from lcqpow_amd import synth_sparse as S
+    Qpat, Apat, qo, eo = S.sparse_pattern_arrays(n, nC, nK)
+    sb = la.SparseBatchLCQP(B, n, nC, nK, Qpat, Apat, opt=la.default_options(perturbStep=0, printLevel=0))
+    inst = [S.sparse_values(i, n, nC, nK, orders=(qo, eo)) for i in range(B)]
+    st = lambda k: np.stack([d[k] for d in inst])
+    assert sb.load(0, B, st("Qx"), st("g"), st("Ex"), lbA=st("lbA"), ubA=st("ubA")) == 0
+    sb.run()
+    rng = np.random.default_rng(0)
+    vx, vy = rng.standard_normal((B, n)), rng.standard_normal((B, nC + 2 * nK))
+    ms = {False: [], True: []}; wall = {False: [], True: []}
+    for r in range(warmup + reps):
+        for reduce in (True, False):      # interleaved: both see the same drift of the clocks
+            t0 = time.perf_counter()
+            out = sb.adjoint(vx, vy, reduce=reduce)
+            t1 = time.perf_counter()
+            if r >= warmup:
+                ms[reduce].append(sb.sensitivity_kernel_ms()); wall[reduce].append(1e3 * (t1 - t0))
+    engine = "band, %d lanes" % sb.lanes()
+    sb.close()
+    q = lambda a: (float(np.min(a)), float(np.median(a)), float(np.max(a)))
+    line = "n = %d nC = %d nComp = %d B = %d (%s; nnzQ %d, nnzA %d):" % (n, nC, nK, B, engine, sb.nnzQ, sb.nnzA)
+    for reduce in (True, False):
+        line += " reduce = %d kernels ms min / median / max = %.4f / %.4f / %.4f, wall ms = %.2f / %.2f / %.2f;" % ((int(reduce),) + q(ms[reduce]) + q(wall[reduce]))
+    line += " flagged %d" % int(np.count_nonzero(out["info"]))
+    print(line, flush=True)
+    return line
+
+
+def sparse_adjoint_main(a):
+    lines = [measure_sparse_adjoint(256 if a.quick else 1024, 512, 256, 64, a.reps)]
+    if a.log:
+        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
+        with open(a.log, "w") as f:
+            f.write("lcqp_hip_sparse_adjoint, reduce = 1 beside reduce = 0, sparse synthetic workload after run, one handle, calls interleaved; %d timed calls after 3 warm-up calls each\n" % a.reps)
+            f.write("\n".join(lines) + "\n")
+
+
 def adjoint_main(a):
     B = 256 if a.quick else 1024
     lines = [measure_adjoint(B, n, nC, nComp, a.reps) for n, nC, nComp in ((40, 20, 8), (256, 512, 64))]
@@ -208,6 +252,8 @@ def main():
     a = ap.parse_args()
     if la.device_count() < 1:
         raise SystemExit("needs a GPU (no CPU fallback)")
+    if a.sparse and a.adjoint:
+        return sparse_adjoint_main(a)
     if a.sparse:
         return sparse_main(a)
     if a.blocked:
