@@ -263,6 +263,44 @@ int  lcqp_hip_batch_last_timing(lcqp_hip_batch_t* b, float* setup_ms, float* sol
 /* getPrimalSolution / getDualSolution / getOutputStatistics, src/LCQProblem.cpp:1485-1504,1519:
  * x[B][nV], y[B][nV+nC+2nComp], stats[B]; returnValue of runSolver is stats[i].returnValue. */
 int  lcqp_hip_batch_get_solution(lcqp_hip_batch_t* b, double* x, double* y, lcqp_stats_t* stats);
+
+/* ---- Device-pointer entry points of the dense batch (DESIGN.md section 3a'''''): the twins of lcqp_hip_batch_load / _update / _get_solution /
+ * _sensitivity(_blocked) / _adjoint whose data pointers are DEVICE pointers.  Layouts, defaults for absent vectors, return codes and the order
+ * of the checks are the host twins'; the pools, the solution and every gradient hold the bits the host twins leave.  The differences:
+ *   pointers  every non-NULL data pointer is plain device memory (hipMalloc) of the handle's device that holds the bytes the call moves; pinned or
+ *             managed host memory, another device's memory and pageable memory are refused with LCQP_INVALID_ARGUMENT and a message, before
+ *             anything is enqueued.  dQ, dA, dL, dR must be 16-byte aligned (the adjoint kernels store pairs of doubles).
+ *   stream    the caller's hipStream_t (NULL: the legacy default stream).  The handle's stream waits for an event recorded on it, the work is
+ *             enqueued on the handle's stream, and the caller's stream waits for an event recorded behind it: inputs are read after their
+ *             producers, outputs are visible to what the caller enqueues next, and no call waits on the host -- except load_device and
+ *             update_device, which read one status word (and, for a load with box bounds, the flags of the bounded variables) back.
+ *   shared    (load) bits 1, 2, 4, 8 for Q, A, L, R: the pointer holds ONE matrix for all `count` instances (broadcast by the pack kernel).
+ *   NULL matrix (load) leaves that block of each instance as the pool holds it; every instance of the range must then already hold a problem,
+ *             else the host twin's code for the missing matrix is returned.  g stays mandatory.
+ *   validation the value checks (-inf in lbL / lbR: LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND; update: the set of box-bounded variables stays,
+ *             LCQP_INVALID_ARGUMENT) run in one kernel over the whole range before anything is written; on a failure nothing is written, and
+ *             the message names the lowest (instance, variable), as the host twin's does.
+ *   NULL handle: LCQP_LCQPOBJECT_NOT_SETUP from all five.
+ * The two paths mix on one handle: the host state (which instances hold problems, the box flags, the lbL / lbR flags) is kept in step.
+ * sensitivity_device: blocked != 0 is lcqp_hip_batch_sensitivity_blocked.  v [B][nrhs][nV], vx [B][nV], vy [B][nd] are read where they lie;
+ * stats of get_solution_device is a device array of B lcqp_stats_t.  The kernel time of sensitivity_device / adjoint_device is formed when
+ * lcqp_hip_batch_sensitivity_timing asks for it (that call then waits for the kernels). */
+int  lcqp_hip_batch_load_device(lcqp_hip_batch_t* b, int first, int count, int shared,
+                                const double* Q, const double* g, const double* L, const double* R,
+                                const double* lbL, const double* ubL, const double* lbR, const double* ubR,
+                                const double* A, const double* lbA, const double* ubA,
+                                const double* lb, const double* ub, const double* x0, const double* y0, void* stream);
+int  lcqp_hip_batch_update_device(lcqp_hip_batch_t* b, int first, int count, const double* g,
+                                  const double* lbL, const double* ubL, const double* lbR, const double* ubR,
+                                  const double* lbA, const double* ubA, const double* lb, const double* ub,
+                                  const double* x0, const double* y0, void* stream);
+int  lcqp_hip_batch_get_solution_device(lcqp_hip_batch_t* b, double* x, double* y, lcqp_stats_t* stats, void* stream);
+int  lcqp_hip_batch_sensitivity_device(lcqp_hip_batch_t* b, int blocked, int nrhs, const double* v,
+                                       double* dg, double* db, int* side, int* info, void* stream);
+int  lcqp_hip_batch_adjoint_device(lcqp_hip_batch_t* b, const double* vx, const double* vy,
+                                   double* dg, double* db, int* side, int* info,
+                                   int reduce, double* dQ, double* dA, double* dL, double* dR, void* stream);
+
 /* per-iterate tracking of one instance when options.storeSteps != 0 (LCQProblem::storeSteps,
  * src/LCQProblem.cpp:1365-1378; OutputStatistics tracking vectors, src/OutputStatistics.cpp:131-164): scalars[len][8] =
  * (|statk|_inf, phi, rho, alphak, objective, merit, |pk|_inf, iterations of the last QP), x[len][nV] = xk at the top of

@@ -1,6 +1,7 @@
 """ctypes binding of the C ABI in include/lcqp_hip.h (liblcqpow_hip.so).  No CPU fallback."""
 import ctypes as C
 import os
+import sys
 
 import numpy as np
 
@@ -45,6 +46,17 @@ class Stats(C.Structure):
 
 
 _lib = None
+_runtime = None      # "torch": the library was bound to the HIP runtime a torch of this process bundles; "system": to the one it was linked against
+
+
+def _torch_hip_runtime():
+    """the libamdhip64.so a torch that this process has IMPORTED ships in its own lib directory, or None (no torch imported, a torch
+    without ROCm, or one that uses the system's runtime)"""
+    t = sys.modules.get("torch")
+    if t is None or not getattr(getattr(t, "version", None), "hip", None):
+        return None
+    p = os.path.join(os.path.dirname(t.__file__), "lib", "libamdhip64.so")
+    return p if os.path.exists(p) else None
 
 
 def library_path():
@@ -69,6 +81,15 @@ def lib():
         if not os.path.exists(_SO):
             raise RuntimeError(f"{_SO} is missing: the HIP extension must be built (see __graft_entry__.build); "
                                "there is no CPU fallback for the product path")
+        # Two HIP runtimes cannot drive one GPU from one process (the second one finds the device's address space taken and reports no
+        # GPU), and a pointer is a device pointer only to the runtime that allocated it.  In a process that has imported a torch with a
+        # runtime of its own, the library is therefore bound to THAT runtime: it goes into the global symbol scope first, where the
+        # library's HIP calls are then resolved.  A process without torch binds to the runtime the library was linked against, as ever.
+        global _runtime
+        rt = _torch_hip_runtime()
+        if rt:
+            C.CDLL(rt, mode=C.RTLD_GLOBAL)
+        _runtime = "torch" if rt else "system"
         L = C.CDLL(_SO)
         L.lcqp_hip_last_error.restype = C.c_char_p
         L.lcqp_hip_options_default.argtypes = [C.POINTER(Options)]
@@ -116,6 +137,11 @@ def lib():
         L.lcqp_hip_qp_jacobian.argtypes = [C.c_void_p, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_batch_set_jacobian_staging.argtypes = [C.c_void_p, C.c_size_t]
         L.lcqp_hip_batch_adjoint.argtypes = [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p, C.c_int] + [c_double_p] * 4
+        L.lcqp_hip_batch_load_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 15 + [C.c_void_p]
+        L.lcqp_hip_batch_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 11 + [C.c_void_p]
+        L.lcqp_hip_batch_get_solution_device.argtypes = [C.c_void_p] * 5
+        L.lcqp_hip_batch_sensitivity_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
+        L.lcqp_hip_batch_adjoint_device.argtypes = [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 5
         L.lcqp_hip_qp_adjoint.argtypes = [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p] + [c_double_p] * 2
         L.lcqp_hip_util_symv.argtypes = [C.c_int, C.c_int, C.c_double] + [c_double_p] * 4
         L.lcqp_hip_util_gemv.argtypes = [C.c_int, C.c_int, C.c_int] + [c_double_p] * 3
@@ -283,6 +309,16 @@ def split_bound_derivatives(db, side, nV, nC, nComp, sparse=False):
     lo = np.where((sd == -1) | (sd == 2), db, 0.0); hi = np.where((sd == 1) | (sd == 2), db, 0.0)
     a = 0 if sparse else nV
     l, r = a + nC, a + nC + nComp
+    return dict(dlb=lo[..., :a], dub=hi[..., :a], dlbA=lo[..., a:l], dubA=hi[..., a:l], dlbL=lo[..., l:r], dubL=hi[..., l:r],
+                dlbR=lo[..., r:], dubR=hi[..., r:])
+
+
+def split_bound_derivatives_torch(db, side, nV, nC, nComp):
+    """split_bound_derivatives (dense layout) on torch tensors, where they lie: the same selections, nothing through the host"""
+    sd = side if db.dim() == side.dim() else side[:, None, :]
+    zero = db.new_zeros(())
+    lo = db.where((sd == -1) | (sd == 2), zero); hi = db.where((sd == 1) | (sd == 2), zero)
+    a, l, r = nV, nV + nC, nV + nC + nComp
     return dict(dlb=lo[..., :a], dub=hi[..., :a], dlbA=lo[..., a:l], dubA=hi[..., a:l], dlbL=lo[..., l:r], dubL=hi[..., l:r],
                 dlbR=lo[..., r:], dubR=hi[..., r:])
 
@@ -573,6 +609,7 @@ class BatchLCQP(_Batch):
     def __init__(self, batch, nV, nC, nComp, with_box=False, device=0, opt=None):
         self.B, self.nV, self.nC, self.nComp = batch, nV, nC, nComp
         self.nd = self._ndual = nV + nC + 2 * nComp
+        self.device = device
         self.h = lib().lcqp_hip_batch_create(batch, nV, nC, nComp, int(with_box), device)
         if not self.h:
             raise RuntimeError("lcqp_hip_batch_create failed: " + last_error())
@@ -637,6 +674,126 @@ class BatchLCQP(_Batch):
         finally:
             if _staging_bytes is not None:
                 self._call("set_jacobian_staging", 0)      # back to the default cap
+
+    # ---- the device-pointer entry points (DESIGN.md section 3a'''''): torch tensors on the handle's device in, torch tensors out; the work is
+    # ordered behind torch.cuda.current_stream(), and what the caller enqueues there next sees the results.  No copy through the host.
+    def _dev(self, name, t, shapes, optional=True):
+        """the device address of a tensor argument (None: NULL) after the checks the C side cannot make: a float64, contiguous torch tensor
+        on the handle's device of one of `shapes`; anything else raises ValueError"""
+        import torch
+        if t is None:
+            if optional:
+                return None
+            raise ValueError(f"{name}: must be given")
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: expected a torch tensor on the device of the batch, got {type(t).__name__}")
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous float64 tensor, got {t.dtype}{'' if t.is_contiguous() else ', not contiguous'}")
+        if t.device.type != "cuda" or t.device.index != self.device:
+            raise ValueError(f"{name}: expected a tensor on cuda:{self.device}, got one on {t.device}")
+        if tuple(t.shape) not in shapes:
+            raise ValueError(f"{name}: expected shape {' or '.join(str(list(s)) for s in shapes)}, got {list(t.shape)}")
+        return t.data_ptr() if t.numel() else None
+
+    def _stream(self):
+        """the current torch stream of the handle's device.  Raises when the library and torch do not share one HIP runtime (lib())."""
+        import torch
+        lib()
+        if _runtime != "torch" and _torch_hip_runtime():
+            raise RuntimeError("the device-pointer entry points need the library and torch on ONE HIP runtime: import torch before the first "
+                               "use of lcqpow_amd (the library was loaded first and is bound to the system's runtime)")
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _range(self, first, count):
+        if not (isinstance(first, int) and isinstance(count, int)) or first < 0 or count <= 0 or first + count > self.B:
+            raise ValueError(f"instances [{first}, {first} + {count}) outside the batch of {self.B}")
+
+    def _device_vectors(self, count, g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0):
+        n, nC, nK = self.nV, self.nC, self.nComp
+        if g is None:
+            return [None] * 11
+        args = (("g", g, n), ("lbL", lbL, nK), ("ubL", ubL, nK), ("lbR", lbR, nK), ("ubR", ubR, nK), ("lbA", lbA, nC), ("ubA", ubA, nC),
+                ("lb", lb, n), ("ub", ub, n), ("x0", x0, n), ("y0", y0, self.nd))
+        return [self._dev(nm, v, ((count, sz),)) for nm, v, sz in args]
+
+    def load_device(self, first, count, Q, g, L, R, lbL=None, ubL=None, lbR=None, ubR=None, A=None, lbA=None, ubA=None,
+                    lb=None, ub=None, x0=None, y0=None):
+        """lcqp_hip_batch_load_device: load() from float64 torch tensors on the handle's device, packed into the pools by kernels.  A
+        matrix of shape [rows][nV] is ONE matrix for all `count` instances (broadcast by the pack kernel), one of shape
+        [count][rows][nV] holds one per instance; a matrix that is None stays as the batch holds it (every instance of the range must
+        hold a problem then).  Returns the ReturnValue code like load; the pools hold the bytes load leaves."""
+        n, nC, nK = self.nV, self.nC, self.nComp
+        self._range(first, count)
+        shared, ptr = 0, {}
+        for bit, (nm, t, rows) in enumerate((("Q", Q, n), ("A", A, nC), ("L", L, nK), ("R", R, nK))):
+            ptr[nm] = self._dev(nm, t, ((rows, n), (count, rows, n)))
+            if t is not None and t.dim() == 2:
+                shared |= 1 << bit
+        v = self._device_vectors(count, g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0)
+        return lib().lcqp_hip_batch_load_device(self.h, first, count, shared, ptr["Q"], v[0], ptr["L"], ptr["R"], v[1], v[2], v[3], v[4],
+                                                ptr["A"], v[5], v[6], v[7], v[8], v[9], v[10], self._stream())
+
+    def update_device(self, first, count, g, lbL=None, ubL=None, lbR=None, ubR=None, lbA=None, ubA=None, lb=None, ub=None, x0=None, y0=None):
+        """lcqp_hip_batch_update_device: update() from float64 torch tensors on the handle's device.  Returns the ReturnValue code."""
+        self._range(first, count)
+        v = self._device_vectors(count, g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0)
+        return lib().lcqp_hip_batch_update_device(self.h, first, count, *v, self._stream())
+
+    def solution_device(self, stats=False):
+        """lcqp_hip_batch_get_solution_device: (x [B][nV], y [B][nd]) as float64 tensors on the handle's device, ordered behind the run on
+        the current torch stream; nothing waits on the host.  stats=True: a third tensor, [B][sizeof(lcqp_stats_t)] bytes
+        (Stats.from_buffer_copy reads an entry once it is on the host)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        x = torch.empty((self.B, self.nV), dtype=torch.float64, device=dev); y = torch.empty((self.B, self.nd), dtype=torch.float64, device=dev)
+        st = torch.empty((self.B, C.sizeof(Stats)), dtype=torch.uint8, device=dev) if stats else None
+        self._call("get_solution_device", x.data_ptr(), y.data_ptr(), st.data_ptr() if stats else None, self._stream())
+        return (x, y, st) if stats else (x, y)
+
+    def sensitivity_device(self, v, blocked=False):
+        """lcqp_hip_batch_sensitivity_device: sensitivity(v, blocked) with v a float64 tensor on the handle's device, [B][nV] or
+        [B][k][nV], read where it lies; returns (dg, db, side, info) as tensors on that device (side, info: int32)."""
+        import torch
+        B, n, nd = self.B, self.nV, self.nd
+        if isinstance(v, torch.Tensor) and v.dim() == 3 and v.shape[1] < 1:
+            raise ValueError("v: no vectors")
+        k = v.shape[1] if isinstance(v, torch.Tensor) and v.dim() == 3 else 1
+        pv = self._dev("v", v, ((B, n), (B, k, n)), optional=False)
+        dev = torch.device("cuda", self.device)
+        lead = (B,) if v.dim() == 2 else (B, k)
+        dg = torch.empty(lead + (n,), dtype=torch.float64, device=dev); db = torch.empty(lead + (nd,), dtype=torch.float64, device=dev)
+        side = torch.empty((B, nd), dtype=torch.int32, device=dev); info = torch.empty(B, dtype=torch.int32, device=dev)
+        self._call("sensitivity_device", 1 if blocked else 0, k, pv, dg.data_ptr(), db.data_ptr(), side.data_ptr(), info.data_ptr(), self._stream())
+        return dg, db, side, info
+
+    def adjoint_device(self, vx, vy=None, matrices=("Q", "A", "L", "R"), reduce=False, out=None):
+        """lcqp_hip_batch_adjoint_device: adjoint(vx, vy, matrices, reduce) with float64 tensors on the handle's device in and out -- the
+        matrix gradients are written by ONE launch straight into their tensors, whatever their size (no staging, no chunks).  out: tensors
+        to write the matrix gradients into, by name (16-byte aligned; default: fresh ones).  Returns the dict of adjoint, of tensors."""
+        import torch
+        B, n, nC, nK, nd = self.B, self.nV, self.nC, self.nComp, self.nd
+        shapes = dict(Q=(n, n), A=(nC, n), L=(nK, n), R=(nK, n))
+        unknown = set(matrices) - set(shapes)
+        if unknown:
+            raise ValueError(f"matrices: unknown names {sorted(unknown)} (this object has {sorted(shapes)})")
+        pvx = self._dev("vx", vx, ((B, n),), optional=False); pvy = self._dev("vy", vy, ((B, nd),))
+        dev = torch.device("cuda", self.device)
+        r = dict(dg=torch.empty((B, n), dtype=torch.float64, device=dev), db=torch.empty((B, nd), dtype=torch.float64, device=dev),
+                 side=torch.empty((B, nd), dtype=torch.int32, device=dev), info=torch.empty(B, dtype=torch.int32, device=dev))
+        lead = () if reduce else (B,)
+        mats = {}
+        for k in shapes:
+            if k in matrices:
+                t = (out or {}).get(k)
+                if t is None:      # the kernels write every entry except those of a matrix without rows
+                    t = torch.empty(lead + shapes[k], dtype=torch.float64, device=dev)
+                self._dev(k, t, (lead + shapes[k],))
+                mats[k] = t
+        ptrs = [mats[k].data_ptr() if k in mats and mats[k].numel() else None for k in shapes]
+        self._call("adjoint_device", pvx, pvy, r["dg"].data_ptr(), r["db"].data_ptr(), r["side"].data_ptr(), r["info"].data_ptr(),
+                   1 if reduce else 0, *ptrs, self._stream())
+        r.update(mats)
+        return r
 
     def generate_synthetic(self, first_instance=0, seed0=SEED0):
         _check(lib().lcqp_hip_batch_generate_synthetic(self.h, seed0, first_instance), "generate_synthetic")

@@ -176,7 +176,7 @@ extern "C" lcqp_hip_batch_t* lcqp_hip_batch_create(int batch, int nV, int nC, in
     if (!kernels) return nullptr;
     if (hipError_t e = hipSetDevice(device)) { hip_fail(g_err, "hipSetDevice(device)", e); return nullptr; }
     std::unique_ptr<lcqp_hip_batch> h(new lcqp_hip_batch(device));
-    for (hipError_t e : {h->stream.status, h->side.status, h->ev0.status, h->ev1.status, h->ev2.status, h->evFork.status, h->evJoin.status,
+    for (hipError_t e : {h->stream.status, h->side.status, h->ev0.status, h->ev1.status, h->ev2.status, h->evFork.status, h->evJoin.status, h->evIn.status, h->evOut.status,
                          h->stage[0].done.status, h->stage[1].done.status})
         if (e != hipSuccess) { hip_fail(g_err, "stream/event creation", e); return nullptr; }
     { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) h->numCU = cu; }
@@ -469,8 +469,7 @@ extern "C" int lcqp_hip_batch_update(lcqp_hip_batch_t* h, int first, int count, 
             const size_t j = (size_t)k * n + i;
             const bool fin = std::isfinite(bnd(lb, j, -INFINITY)) || std::isfinite(bnd(ub, j, INFINITY));
             if (fin != (h->boxed[((size_t)first + k) * n + i] != 0)) {
-                g_err = "update: variable " + std::to_string(i) + " of instance " + std::to_string(first + k) +
-                        (fin ? " gains" : " loses") + " its box bound; the set of bounded variables is fixed by the load (they are rows of the factored matrices)";
+                g_err = box_change_message(i, first + k, fin);
                 return LCQP_INVALID_ARGUMENT;
             }
         }
@@ -680,26 +679,37 @@ static int grow(lcqp_hip_batch* h, double*& p, size_t& cap, size_t count)
     return 0;
 }
 
+// dev (the device-pointer twins): v and vy are device arrays, read where they lie (they have the pitch the kernels expect); the results go to
+// the caller's device arrays with copies on the batch stream, nothing waits on the host, and the kernel time stays in the events until
+// lcqp_hip_batch_sensitivity_timing asks for it (sensPending).
 static int sensitivity_launch(lcqp_hip_batch* h, bool blk, int first, int count, int nrhs, const double* v, double* dg, double* db, int* side, int* info, float* ms,
-                              const double* vy = nullptr)
+                              const double* vy = nullptr, bool dev = false)
 {
     DevBatch& d = h->db;
     SensBuffers& sb = blk ? h->sensBlk : h->sens;
     HIPCHK(g_err, hipSetDevice(h->device));
     // (ldv is the same for a Jacobian and a blocked call so that the rows reserved by one serve the other: a Jacobian's rows carry an unused v)
     if (int rc = sb.reserve(g_err, h->mem, h->stream, count, nrhs, d.n, d.np, (size_t)d.nd + (blk ? 2 : 1) * (size_t)d.capS, d.nd)) return rc;
-    if (v) if (int rc = sb.upload(g_err, v)) return rc;
-    const double* dv = v ? sb.v : nullptr;
-    if (vy) {      // (k_sensitivity<NCH, true> of lcqp_hip_batch_adjoint: the whole batch, vy [B][nrhs][nd] from the host)
+    h->sensPending = 0;
+    if (v && !dev) if (int rc = sb.upload(g_err, v)) return rc;
+    const double* dv = dev ? v : (v ? sb.v : nullptr);
+    const double* dvy = vy;
+    if (vy && !dev) {      // (k_sensitivity<NCH, true> of lcqp_hip_batch_adjoint: the whole batch, vy [B][nrhs][nd] from the host)
         if (int rc = grow(h, h->adjVy, h->adjVyCap, sb.rows * d.nd)) return rc;
         HIPCHK(g_err, hipMemcpyAsync(h->adjVy, vy, sizeof(double) * sb.rows * d.nd, hipMemcpyHostToDevice, h->stream));
+        dvy = h->adjVy;
     }
     HIPCHK(g_err, hipEventRecord(sb.ev0, h->stream));
     if (blk) h->k->sensitivity_blk(d, count, h->stream, first, nrhs, dv, sb.dg, sb.db, sb.side, sb.info);
-    else if (vy) h->k->sensitivity_dual(d, count, h->stream, nrhs, dv, h->adjVy, sb.dg, sb.db, sb.side, sb.info);
+    else if (vy) h->k->sensitivity_dual(d, count, h->stream, nrhs, dv, dvy, sb.dg, sb.db, sb.side, sb.info);
     else h->k->sensitivity(d, count, h->stream, nrhs, dv, sb.dg, sb.db, sb.side, sb.info);
     HIPCHK(g_err, hipGetLastError());
     HIPCHK(g_err, hipEventRecord(sb.ev1, h->stream));
+    if (dev) {
+        if (int rc = sb.download_device(g_err, dg, db, side, info, d.n, d.nd)) return rc;
+        h->sensPending = blk ? 2 : 1;
+        return 0;
+    }
     if (int rc = sb.download(g_err, dg, db, side, info, d.n, d.nd)) return rc;
     float t = 0.f;
     HIPCHK(g_err, hipEventElapsedTime(&t, sb.ev0, sb.ev1));
@@ -789,10 +799,24 @@ extern "C" int lcqp_hip_batch_set_jacobian_staging(lcqp_hip_batch_t* h, size_t b
     return 0;
 }); }
 
+// (after a device-pointer call the time is still in the events: wait for them and form it)
 extern "C" int lcqp_hip_batch_sensitivity_timing(lcqp_hip_batch_t* h, float* kernel_ms)
-{
+{ return guarded(g_err, [&] {
+    if (h && h->sensPending) {
+        HIPCHK(g_err, hipSetDevice(h->device));
+        const SensBuffers& sb = (h->sensPending & 3) == 2 ? h->sensBlk : h->sens;
+        float t = 0.f, ta = 0.f;
+        HIPCHK(g_err, hipEventSynchronize(sb.ev1));
+        HIPCHK(g_err, hipEventElapsedTime(&t, sb.ev0, sb.ev1));
+        if (h->sensPending & 4) {
+            HIPCHK(g_err, hipEventSynchronize(h->adjEv1));
+            HIPCHK(g_err, hipEventElapsedTime(&ta, h->adjEv0, h->adjEv1));
+        }
+        h->rs.sensMs = t + ta;
+        h->sensPending = 0;
+    }
     return sensitivity_timing(h, kernel_ms);
-}
+}); }
 
 // ---- the full adjoint (DESIGN.md section 3a''''): upstream gradients on x and y, gradients in g, the bounds and the matrices ----
 // k_sensitivity (with vy: its DUAL instantiation) on the whole batch, its results to the host; then, on the device buffers it left, the matrix
@@ -854,4 +878,85 @@ extern "C" int lcqp_hip_batch_adjoint(lcqp_hip_batch_t* h, const double* vx, con
     if (!h || !vx || !dg || (reduce != 0 && reduce != 1)) return LCQP_INVALID_ARGUMENT;
     if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
     return batch_adjoint(h, vx, vy, dg, db, side, info, reduce, dQ, dA, dL, dR);
+}); }
+
+// ---- the device-pointer twins of the three calls above (include/lcqp_hip.h; load, update and get_solution are in lcqp_hip_device.hip) ----
+int batch_sensitivity_device(lcqp_hip_batch* h, bool blk, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
+{
+    float ms = 0.f;
+    return sensitivity_launch(h, blk && h->k->sensitivity_blk, 0, h->db.B, nrhs, v, dg, db, side, info, &ms, nullptr, true);
+}
+
+// k_sensitivity as batch_adjoint launches it, then ONE launch of k_adjoint_outer / k_adjoint_reduce that writes the caller's arrays: no
+// staging buffer, no chunks
+int batch_adjoint_device(lcqp_hip_batch* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
+                         int reduce, double* dQ, double* dA, double* dL, double* dR)
+{
+    DevBatch& d = h->db;
+    float ms = 0.f;
+    if (int rc = sensitivity_launch(h, false, 0, d.B, 1, vx, dg, db, side, info, &ms, vy, true)) return rc;
+    double* out[4] = {dQ, d.nC ? dA : nullptr, d.nComp ? dL : nullptr, d.nComp ? dR : nullptr};
+    const int r0[4] = {0, d.n, d.n + d.nC, d.n + d.nC + d.nComp}, rows[4] = {d.n, d.nC, d.nComp, d.nComp};
+    AdjointSegs segs{};
+    size_t most = 0;
+    for (int k = 0; k < 4; k++) {
+        if (!out[k]) continue;
+        segs.s[k] = {out[k], r0[k], rows[k]};
+        most = std::max(most, (reduce ? (size_t)1 : (size_t)d.B) * rows[k] * d.n);
+    }
+    if (!most) return 0;
+    const SensBuffers& sb = h->sens;
+    const AdjointArgs a = {d.B, d.n, d.np, d.nd, (int)sb.ldDb, d.xout, d.yout, sb.dg, sb.db, sb.side, sb.info};
+    for (hipError_t e : {h->adjEv0.status, h->adjEv1.status}) if (e != hipSuccess) return hip_fail(g_err, "hipEventCreate", e);
+    const unsigned gx = (unsigned)std::min<size_t>((most + 2 * WG - 1) / (2 * WG), 65535);
+    HIPCHK(g_err, hipEventRecord(h->adjEv0, h->stream));
+    if (reduce) hipLaunchKernelGGL(k_adjoint_reduce, dim3(gx, 4), dim3(WG), 0, h->stream, a, segs);
+    else hipLaunchKernelGGL(k_adjoint_outer, dim3(gx, 4), dim3(WG), 0, h->stream, a, segs, 0, d.B);
+    HIPCHK(g_err, hipGetLastError());
+    HIPCHK(g_err, hipEventRecord(h->adjEv1, h->stream));
+    h->sensPending |= 4;
+    return 0;
+}
+
+// the pointer checks of the two calls: every array with the bytes the call moves
+static bool sens_pointers_ok(lcqp_hip_batch* h, size_t rows, const double* v, const char* vname, const double* vy, double* dg, double* db, int* side, int* info)
+{
+    const DevBatch& d = h->db;
+    return device_pointer_ok(g_err, h, vname, v, sizeof(double) * rows * d.n) && device_pointer_ok(g_err, h, "vy", vy, sizeof(double) * rows * d.nd) &&
+           device_pointer_ok(g_err, h, "dg", dg, sizeof(double) * rows * d.n) && device_pointer_ok(g_err, h, "db", db, sizeof(double) * rows * d.nd) &&
+           device_pointer_ok(g_err, h, "side", side, sizeof(int) * (size_t)d.B * d.nd, 4) && device_pointer_ok(g_err, h, "info", info, sizeof(int) * (size_t)d.B, 4);
+}
+
+extern "C" int lcqp_hip_batch_sensitivity_device(lcqp_hip_batch_t* h, int blocked, int nrhs, const double* v, double* dg, double* db,
+                                                 int* side, int* info, void* stream)
+{ return guarded(g_err, [&] {
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    HIPCHK(g_err, hipSetDevice(h->device));
+    if (!sens_pointers_ok(h, (size_t)h->db.B * nrhs, v, "v", nullptr, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
+    StreamHandOver over(h, stream);
+    HIPCHK(g_err, over.status);
+    const int rc = batch_sensitivity_device(h, blocked != 0, nrhs, v, dg, db, side, info);
+    HIPCHK(g_err, over.done());
+    return rc;
+}); }
+
+extern "C" int lcqp_hip_batch_adjoint_device(lcqp_hip_batch_t* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
+                                             int reduce, double* dQ, double* dA, double* dL, double* dR, void* stream)
+{ return guarded(g_err, [&] {
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!vx || !dg || (reduce != 0 && reduce != 1)) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    HIPCHK(g_err, hipSetDevice(h->device));
+    const DevBatch& d = h->db;
+    if (!sens_pointers_ok(h, d.B, vx, "vx", vy, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
+    const size_t lead = sizeof(double) * (reduce ? (size_t)1 : (size_t)d.B) * d.n;
+    if (!device_pointer_ok(g_err, h, "dQ", dQ, lead * d.n, 16) || !device_pointer_ok(g_err, h, "dA", dA, lead * d.nC, 16) ||
+        !device_pointer_ok(g_err, h, "dL", dL, lead * d.nComp, 16) || !device_pointer_ok(g_err, h, "dR", dR, lead * d.nComp, 16)) return LCQP_INVALID_ARGUMENT;
+    StreamHandOver over(h, stream);
+    HIPCHK(g_err, over.status);
+    const int rc = batch_adjoint_device(h, vx, vy, dg, db, side, info, reduce, dQ, dA, dL, dR);
+    HIPCHK(g_err, over.done());
+    return rc;
 }); }

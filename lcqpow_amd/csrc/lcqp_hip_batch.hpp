@@ -5,6 +5,7 @@
 #include "lcqp_launch.hpp"
 #include "lcqp_host_rt.hpp"
 
+#include <cstdint>
 #include <string>
 #include <vector>
 
@@ -46,6 +47,12 @@ struct lcqp_hip_batch {
     double *adjVy = nullptr, *adjOut = nullptr;
     size_t adjVyCap = 0, adjOutCap = 0;
     lcqp_rt::Event adjEv0, adjEv1;        // around the last matrix-gradient launch
+    // of the device-pointer entry points (lcqp_hip_device.hip): the events of the hand-over between the caller's stream and `stream`; the
+    // status words of k_check_vectors followed by the box flags of a load ([2] x 8 bytes, then [B][n] bytes); and which events still hold
+    // the kernel time of the last sensitivity_device / adjoint_device call (0: none, 1: sens, 2: sensBlk; + 4: adjEv0 / adjEv1 as well)
+    lcqp_rt::Event evIn{hipEventDisableTiming}, evOut{hipEventDisableTiming};
+    unsigned long long* devChk = nullptr;
+    int sensPending = 0;
     int nch;
     const lcqp::SizeKernels* k = nullptr; // the launch table of the padded size (dense_kernels), set by lcqp_hip_batch_create
     explicit lcqp_hip_batch(int dev) : db(), device(dev) {}
@@ -63,5 +70,66 @@ int batch_sensitivity(lcqp_hip_batch* h, bool blk, int nrhs, const double* v, do
 int batch_jacobian(lcqp_hip_batch* h, int first, int count, double* Jg, double* Jb, int* side, int* info);
 int batch_adjoint(lcqp_hip_batch* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
                   int reduce, double* dQ, double* dA, double* dL, double* dR);
+
+int batch_sensitivity_device(lcqp_hip_batch* h, bool blk, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
+int batch_adjoint_device(lcqp_hip_batch* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
+                         int reduce, double* dQ, double* dA, double* dL, double* dR);
+
+// the message of lcqp_hip_batch_update and its device twin for a variable whose box bound appears or disappears
+inline std::string box_change_message(int variable, int instance, bool gains)
+{
+    return "update: variable " + std::to_string(variable) + " of instance " + std::to_string(instance) + (gains ? " gains" : " loses") +
+           " its box bound; the set of bounded variables is fixed by the load (they are rows of the factored matrices)";
+}
+
+// ---- the device-pointer entry points: what lcqp_hip.hip (sensitivity, adjoint) and lcqp_hip_device.hip (load, update, solution) share ----
+// A data pointer of such a call: NULL, or plain device memory of the handle's device with `bytes` behind it (align: 8, or 16 for dQ ... dR).
+// Anything else -- pageable, pinned or managed host memory, another device -- leaves a message and returns false; nothing is dereferenced.
+inline bool device_pointer_ok(std::string& err, const lcqp_hip_batch* h, const char* name, const void* p, size_t bytes, size_t align = 8)
+{
+    if (!p) return true;
+    hipPointerAttribute_t at{};
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) (void)hipGetLastError();
+    if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.isManaged) {
+        err = std::string(name) + ": not a device pointer (the *_device entry points take plain device memory; host, pinned and managed memory go through the host entry points)";
+        return false;
+    }
+    if (at.device != h->device) {
+        err = std::string(name) + ": memory of device " + std::to_string(at.device) + ", the batch lives on device " + std::to_string(h->device);
+        return false;
+    }
+    if ((size_t)(uintptr_t)p % align) {
+        err = std::string(name) + ": not aligned to " + std::to_string(align) + " bytes";
+        return false;
+    }
+    void* base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return true; }
+    if ((const char*)p + bytes > (const char*)base + size) {
+        err = std::string(name) + ": the allocation ends before the " + std::to_string(bytes) + " bytes the call moves";
+        return false;
+    }
+    return true;
+}
+
+// The hand-over of a device-pointer call: the handle's stream waits for what the caller's stream holds so far (the constructor), the
+// caller's stream for what the call enqueued on the handle's stream (done()).  Nothing waits on the host.
+struct StreamHandOver {
+    lcqp_hip_batch* h;
+    hipStream_t caller;
+    hipError_t status = hipSuccess;
+    StreamHandOver(lcqp_hip_batch* h_, void* stream) : h(h_), caller((hipStream_t)stream)
+    {
+        if (caller == h->stream.s) return;
+        status = hipEventRecord(h->evIn, caller);
+        if (status == hipSuccess) status = hipStreamWaitEvent(h->stream, h->evIn, 0);
+    }
+    hipError_t done()
+    {
+        if (caller == h->stream.s) return hipSuccess;
+        const hipError_t e = hipEventRecord(h->evOut, h->stream);
+        return e != hipSuccess ? e : hipStreamWaitEvent(caller, h->evOut, 0);
+    }
+};
 
 #pragma GCC visibility pop

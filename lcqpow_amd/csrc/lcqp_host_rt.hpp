@@ -268,6 +268,15 @@ struct SensBuffers {
         else HIPCHK(err, hipMemcpyAsync(dst, src, sizeof(double) * rows * width, hipMemcpyDeviceToHost, stream));
         return 0;
     }
+    // the results to device arrays of the caller (ddb, dside, dinfo may be NULL), on the stream; nothing waits
+    int download_device(std::string& err, double* ddg, double* ddb, int* dside, int* dinfo, size_t wDg, size_t wDb)
+    {
+        HIPCHK(err, hipMemcpy2DAsync(ddg, sizeof(double) * wDg, dg, sizeof(double) * ldDg, sizeof(double) * wDg, rows, hipMemcpyDeviceToDevice, stream));
+        if (ddb) HIPCHK(err, hipMemcpy2DAsync(ddb, sizeof(double) * wDb, db, sizeof(double) * ldDb, sizeof(double) * wDb, rows, hipMemcpyDeviceToDevice, stream));
+        if (dside) HIPCHK(err, hipMemcpyAsync(dside, side, sizeof(int) * B * nSide, hipMemcpyDeviceToDevice, stream));
+        if (dinfo) HIPCHK(err, hipMemcpyAsync(dinfo, info, sizeof(int) * B, hipMemcpyDeviceToDevice, stream));
+        return 0;
+    }
     // the results to the host (hdb, hside, hinfo may be NULL); synchronous on return
     int download(std::string& err, double* hdg, double* hdb, int* hside, int* hinfo, size_t wDg, size_t wDb)
     {

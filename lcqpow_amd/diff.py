@@ -2,8 +2,11 @@
 for a SparseBatchLCQP behind a SparseBatchLCQPLayer, lcqp_hip_sparse_sensitivity (section 3a'').
 
 The solve and its derivative run on the HIP path of :mod:`lcqpow_amd.capi`; there is no CPU fallback -- without the built library, or
-without a device, using the layer raises.  Tensors are copied to the host and back around the C ABI (host pointers): plumbing, not a
-hot path.
+without a device, using the layer raises.  The dense layer has two paths, chosen per call by where g lives (layer.last_path):
+"device" when g is a tensor on the batch's GPU -- the device-pointer entry points (DESIGN.md section 3a'''''): tensors are packed into the
+pools by kernels, x, y and every gradient are produced on the device, and nothing goes through the host but a status word and the count
+of flagged instances -- and "host" otherwise: tensors are copied to the host and back around the host-pointer C ABI, exactly as a CPU
+tensor always was.  The sparse layer has the host path only.
 
     bt = BatchLCQP(B, nV, nC, nComp, opt=...); bt.load(0, B, Q, g0, L, R, A=A, lbA=lbA, ubA=ubA)
     layer = BatchLCQPLayer(bt, bounds=dict(lbA=lbA, ubA=ubA))
@@ -35,6 +38,31 @@ def _host(t):
     return None if t is None else np.ascontiguousarray(t.detach().cpu().to(torch.float64).numpy())
 
 
+def _dev(t, device):
+    """a tensor argument as the device-pointer entry points take it: float64, contiguous, on `device`, detached"""
+    return None if t is None else t.detach().to(device=device, dtype=torch.float64).contiguous()
+
+
+def _warn_flagged(who, info, B):
+    """the one warning of a backward call on the device path: the count is the one scalar read of that call"""
+    bad = int(torch.count_nonzero(info))
+    if bad:
+        bits = int(np.bitwise_or.reduce(info.cpu().numpy()))
+        warnings.warn(f"{who}.backward: {bad} of {B} instances are not differentiable by the library's criteria "
+                      f"(info bits present: {bits}); their gradients are the kernel's output as it is", RuntimeWarning, stacklevel=3)
+
+
+def _bound_grads_device(bt, db, side, given, like):
+    """the gradients of lbA / ubA on the device path: split_bound_derivatives and the equality rule of LCQPSolveFunction, on tensors"""
+    parts = capi.split_bound_derivatives_torch(db, side, bt.nV, bt.nC, bt.nComp)
+    eq = side[:, bt.nV:bt.nV + bt.nC] == 2
+    one = db.new_ones(())
+    share = torch.where(eq, 0.5 * one, one) if all(given) else one
+    glb = (parts["dlbA"] * share).to(like) if given[0] else None
+    gub = (parts["dubA"] * share).to(like) if given[1] else None
+    return glb, gub
+
+
 class LCQPSolveFunction(torch.autograd.Function):
     """forward(layer, g, lbA, ubA) -> x: lcqp_hip_batch_update with the layer's other vectors, then run (first call) or resolve(warm).
     backward: one lcqp_hip_batch_sensitivity call; gradients for g and, where they were given as tensors, lbA and ubA.
@@ -48,6 +76,26 @@ class LCQPSolveFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, layer, g, lbA=None, ubA=None):
         bt = layer.bt
+        ctx.device_path = layer._on_device(g)
+        layer.last_path = "device" if ctx.device_path else "host"
+        if ctx.device_path:
+            kw = dict(layer._device_bounds(g.device))
+            if lbA is not None: kw["lbA"] = _dev(lbA, g.device)
+            if ubA is not None: kw["ubA"] = _dev(ubA, g.device)
+            rc = bt.update_device(0, bt.B, _dev(g, g.device), **kw)
+            if rc != 0:
+                raise RuntimeError(f"update failed with code {rc}: {bt._last_error()}")
+            if layer.solves == 0:
+                bt.run()
+            else:
+                bt.resolve(warm=layer.warm)
+            x, y = bt.solution_device()
+            layer.solves += 1
+            layer.y, layer.stats = y, None      # (the statistics: through the host call, when layer.stats is read)
+            layer._like = (g.dtype, g.device)
+            ctx.layer, ctx.serial = layer, layer.solves
+            ctx.given = (lbA is not None, ubA is not None)
+            return x.to(g.dtype)
         kw = dict(layer.bounds)
         if lbA is not None: kw["lbA"] = _host(lbA)
         if ubA is not None: kw["ubA"] = _host(ubA)
@@ -72,6 +120,12 @@ class LCQPSolveFunction(torch.autograd.Function):
         if ctx.serial != layer.solves:
             raise RuntimeError("backward through a solve that is not the layer's last one: the batch object holds the state of one solve")
         bt = layer.bt
+        if ctx.device_path:
+            dg, db, side, info = bt.sensitivity_device(_dev(grad_x, grad_x.device))
+            layer.info = info
+            _warn_flagged("LCQPSolveFunction", info, bt.B)
+            glb, gub = _bound_grads_device(bt, db, side, ctx.given, grad_x.dtype)
+            return None, dg.to(grad_x.dtype), glb, gub
         dg, db, side, info = bt.sensitivity(_host(grad_x))
         layer.info = info
         bad = int(np.count_nonzero(info))
@@ -103,9 +157,6 @@ class LCQPFullSolveFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, layer, g, Q=None, A=None, L=None, R=None, lbA=None, ubA=None):
         bt = layer.bt
-        kw = dict(layer.bounds)
-        if lbA is not None: kw["lbA"] = _host(lbA)
-        if ubA is not None: kw["ubA"] = _host(ubA)
         given = dict(zip(MATRIX_KEYS, (Q, A, L, R)))
         rows = dict(Q=bt.nV, A=bt.nC, L=bt.nComp, R=bt.nComp)
         shared = {}
@@ -115,6 +166,39 @@ class LCQPFullSolveFunction(torch.autograd.Function):
             if tuple(t.shape) not in ((bt.B, rows[k], bt.nV), (rows[k], bt.nV)):
                 raise ValueError(f"{k}: expected [{bt.B}][{rows[k]}][{bt.nV}] or [{rows[k]}][{bt.nV}], got {tuple(t.shape)}")
             shared[k] = t.dim() == 2
+        ctx.device_path = layer._on_device(g)
+        layer.last_path = "device" if ctx.device_path else "host"
+        if ctx.device_path:
+            kw = dict(layer._device_bounds(g.device))
+            if lbA is not None: kw["lbA"] = _dev(lbA, g.device)
+            if ubA is not None: kw["ubA"] = _dev(ubA, g.device)
+            if shared:
+                # a matrix that is not an input is not handed over: the batch keeps it (NULL), a shared one is broadcast by the pack kernel
+                m = {k: _dev(t, g.device) for k, t in given.items()}
+                rc = bt.load_device(0, bt.B, m["Q"], _dev(g, g.device), m["L"], m["R"], A=m["A"], **kw)
+                if rc != 0:
+                    raise RuntimeError(f"load failed with code {rc}: {bt._last_error()}")
+                layer._held = None      # (the host path reads the matrices back again when it next needs them)
+                bt.run()
+            else:
+                rc = bt.update_device(0, bt.B, _dev(g, g.device), **kw)
+                if rc != 0:
+                    raise RuntimeError(f"update failed with code {rc}: {bt._last_error()}")
+                if layer.solves == 0:
+                    bt.run()
+                else:
+                    bt.resolve(warm=layer.warm)
+            x, y = bt.solution_device()
+            layer.solves += 1
+            layer.y, layer.stats = y, None
+            layer._like = (g.dtype, g.device)
+            ctx.layer, ctx.serial = layer, layer.solves
+            ctx.given = (lbA is not None, ubA is not None)
+            ctx.shared = shared
+            return x.to(g.dtype), y.to(g.dtype)
+        kw = dict(layer.bounds)
+        if lbA is not None: kw["lbA"] = _host(lbA)
+        if ubA is not None: kw["ubA"] = _host(ubA)
         if shared:
             held = layer._matrices()
             for k, t in given.items():
@@ -148,9 +232,21 @@ class LCQPFullSolveFunction(torch.autograd.Function):
         if ctx.serial != layer.solves:
             raise RuntimeError("backward through a solve that is not the layer's last one: the batch object holds the state of one solve")
         bt = layer.bt
-        vx, vy = _host(grad_x), _host(grad_y)
         each = tuple(k for k, sh in ctx.shared.items() if not sh)
         summed = tuple(k for k, sh in ctx.shared.items() if sh)
+        if ctx.device_path:
+            vx, vy = _dev(grad_x, grad_x.device), _dev(grad_y, grad_x.device)
+            r = bt.adjoint_device(vx, vy, matrices=each, reduce=False)
+            mats = {k: r[k] for k in each}
+            if summed:
+                rs = bt.adjoint_device(vx, vy, matrices=summed, reduce=True)
+                mats.update({k: rs[k] for k in summed})
+            layer.info = r["info"]
+            _warn_flagged("LCQPFullSolveFunction", r["info"], bt.B)
+            glb, gub = _bound_grads_device(bt, r["db"], r["side"], ctx.given, grad_x.dtype)
+            gm = [mats[k].to(grad_x.dtype) if k in mats else None for k in MATRIX_KEYS]
+            return (None, r["dg"].to(grad_x.dtype), *gm, glb, gub)
+        vx, vy = _host(grad_x), _host(grad_y)
         r = bt.adjoint(vx, vy, matrices=each, reduce=False)
         mats = {k: r[k] for k in each}
         if summed:
@@ -274,9 +370,33 @@ class BatchLCQPLayer:
         self.bounds = {k: capi._arr(v) for k, v in (bounds or {}).items() if v is not None}
         self.y = self.stats = self.info = None
         self._held = None
+        self.last_path = None      # "device" or "host": the path of the last solve
+        self._bounds_dev = None
 
     def __call__(self, g, lbA=None, ubA=None):
         return LCQPSolveFunction.apply(self, g, lbA, ubA)
+
+    @property
+    def stats(self):
+        """the statistics of the last solve, a list of dicts; after a solve on the device path they are fetched through the host call
+        (BatchLCQP.solution) when first asked for"""
+        if self._stats is None and self.solves and self.last_path == "device":
+            self._stats = self.bt.solution()[2]
+        return self._stats
+
+    @stats.setter
+    def stats(self, st):
+        self._stats = st
+
+    def _on_device(self, g):
+        """the device path: the dense arm, and g a tensor on the GPU of the batch"""
+        return (not self.sparse) and g.is_cuda and g.device.index == getattr(self.bt, "device", None)
+
+    def _device_bounds(self, device):
+        """the layer's bound vectors as float64 tensors on the device, uploaded once"""
+        if self._bounds_dev is None:
+            self._bounds_dev = {k: torch.as_tensor(v, dtype=torch.float64, device=device).contiguous() for k, v in self.bounds.items()}
+        return self._bounds_dev
 
     def solve(self, g, Q=None, A=None, L=None, R=None, lbA=None, ubA=None):
         """(x, y) of the batch for the linear terms g, both differentiable (LCQPFullSolveFunction): y [B][nV + nC + 2 nComp] in
