@@ -119,11 +119,13 @@ int  lcqp_hip_qp_jacobian(lcqp_hip_qp_t* qp, double* Jg, double* Jb, int* side, 
  * (A = the stacked rows) may be NULL.  LCQP_INVALID_ARGUMENT: NULL object, vx or dg; LCQP_LCQPOBJECT_NOT_SETUP as lcqp_hip_qp_sensitivity. */
 int  lcqp_hip_qp_adjoint(lcqp_hip_qp_t* qp, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
                          double* dQ, double* dA);
-/* test and diagnostic entry points: lcqp_hip_batch_read_setup / lcqp_hip_batch_read_working_set (below) for the batch of one this object
- * holds; LCQP_LCQPOBJECT_NOT_SETUP before its first solve */
+/* test and diagnostic entry points: lcqp_hip_batch_read_setup / lcqp_hip_batch_read_working_set / lcqp_hip_batch_read_admm (below) for the
+ * batch of one this object holds; LCQP_LCQPOBJECT_NOT_SETUP before its first solve */
 int  lcqp_hip_qp_read_setup(lcqp_hip_qp_t* qp, int dims[9], double scal[2], double* C, double* F1, double* D1, double* Et, double* MM,
                             int* Cp, int* Ci, double* Cv);
 int  lcqp_hip_qp_read_working_set(lcqp_hip_qp_t* qp, int dims[2], int* slot_row, int* crow, int* row_slot, double* Ti);
+int  lcqp_hip_qp_read_admm(lcqp_hip_qp_t* qp, int dims[6], double scal[3], double* FK, double* rhov, double* l, double* u,
+                           double* xa, double* ya, double* za, double* dy, double* dx);
 
 /* ------------------------------------------------------------------------------------------------
  * Batch of B independent dense LCQPs of one shape (nV, nC, nComp).
@@ -160,6 +162,15 @@ int  lcqp_hip_batch_read_setup(lcqp_hip_batch_t* b, int instance, int dims[9], d
  * dims[2] = nT (rows of Ti), ns (slots in use, free ones inside included); slot_row [capS] (row of E held by a slot, -1: free),
  * crow [capS] (the row of Ti appended together with the slot), row_slot [mE] (-1: not in the factor), Ti [capS][capS]. */
 int  lcqp_hip_batch_read_working_set(lcqp_hip_batch_t* b, int instance, int dims[2], int* slot_row, int* crow, int* row_slot, double* Ti);
+/* The state of the ADMM fallback of the dense subsolver (qp_build_K, qp_admm, qp_adapt_rho) as the last QP that ran it left it; the polish
+ * writes none of it.  Both streams are synchronised, nothing is launched, any pointer may be NULL (buffers NULL: the sizes).
+ * dims[6] = np, nblk, mEcap, the instance's mE, kReady (FK holds the factor of the rho vector in place), setupFail; scal[3] = sigma,
+ * rhoAdmm, scale.  FK [np][np]: L_K, the factor of K = Q + sigma I + E' diag(rhov) E, symmetric-filled, its diagonal 64 x 64 blocks
+ * holding their inverses (as F1).  rhov, l, u (the bounds of the stacked rows), ya, za, dy (the change of ya in the last iteration)
+ * [mEcap]; xa, dx (the change of xa in the last iteration) [np].  LCQP_INVALID_ARGUMENT: NULL handle, instance out of range;
+ * LCQP_LCQPOBJECT_NOT_SETUP: no setup belongs to the data in place (before lcqp_hip_batch_setup / lcqp_hip_batch_run). */
+int  lcqp_hip_batch_read_admm(lcqp_hip_batch_t* b, int instance, int dims[6], double scal[3], double* FK, double* rhov, double* l, double* u,
+                              double* xa, double* ya, double* za, double* dy, double* dx);
 /* Constant-matrix setup: C = L'R + R'L (src/LCQProblem.cpp:622-623), phi expressions (:969-996) and the
  * two factorisations the subsolver reuses across every iterate (replaces qp.init's setup,
  * src/SubsolverQPOASES.cpp:152).  Asynchronous on the batch stream. */
@@ -322,10 +333,11 @@ int    lcqp_hip_batch_work_sums(lcqp_hip_batch_t* b, double out[6]);
 
 /* ------------------------------------------------------------------------------------------------
  * Building blocks exposed for parity tests and micro-benchmarks (each is one kernel launch over a
- * batch of independent instances; host pointers, synchronous).  Two more test and diagnostic entry points sit with the objects they
+ * batch of independent instances; host pointers, synchronous).  Three more test and diagnostic entry points sit with the objects they
  * read: lcqp_hip_batch_read_setup / lcqp_hip_batch_read_working_set (and lcqp_hip_qp_read_setup / lcqp_hip_qp_read_working_set) copy the
  * constant matrices of the setup kernels and the inverse factor of the working-set matrix back as they lie on the device
- * (tests/test_gpu_setup.py); they launch nothing.
+ * (tests/test_gpu_setup.py); lcqp_hip_batch_read_admm (and lcqp_hip_qp_read_admm) does the same for the factor L_K, the rho vector and
+ * the iterates of the ADMM fallback (tests/test_gpu_admm.py).  They launch nothing.
  * ---------------------------------------------------------------------------------------------- */
 /* Utilities::AffineLinearTransformation for symmetric A, src/Utilities.cpp:176-186: d = alpha*A*b + c */
 int lcqp_hip_util_symv(int batch, int n, double alpha, const double* A, const double* b, const double* c, double* d);

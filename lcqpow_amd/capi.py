@@ -128,6 +128,8 @@ def lib():
         L.lcqp_hip_batch_read_working_set.argtypes = [C.c_void_p, C.c_int, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p]
         L.lcqp_hip_qp_read_setup.argtypes = [C.c_void_p, c_int_p, c_double_p] + [c_double_p] * 5 + [c_int_p, c_int_p, c_double_p]
         L.lcqp_hip_qp_read_working_set.argtypes = [C.c_void_p, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p]
+        L.lcqp_hip_batch_read_admm.argtypes = [C.c_void_p, C.c_int, c_int_p, c_double_p] + [c_double_p] * 9
+        L.lcqp_hip_qp_read_admm.argtypes = [C.c_void_p, c_int_p, c_double_p] + [c_double_p] * 9
         L.lcqp_hip_batch_sensitivity.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_batch_sensitivity_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.lcqp_hip_qp_sensitivity.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
@@ -246,6 +248,20 @@ def _read_working_set(call, capS, mE):
     Ti = np.zeros((capS, capS))
     _check(call(_ip(dims), _ip(slot_row), _ip(crow), _ip(row_slot), _p(Ti)), "read_working_set")
     return dict(nT=int(dims[0]), ns=int(dims[1]), slot_row=slot_row, crow=crow, row_slot=row_slot[:mE], Ti=Ti)
+
+
+def _read_admm(call):
+    """call(dims, scal, FK, rhov, l, u, xa, ya, za, dy, dx) -> rc: the state of the ADMM fallback of one instance as it lies on the device
+    (lcqp_hip_batch_read_admm).  A first call with no buffers asks for the dimensions."""
+    dims = np.zeros(6, dtype=np.int32); scal = np.zeros(3)
+    _check(call(_ip(dims), _p(scal), *[None] * 9), "read_admm")
+    np_, nblk, mEcap = (int(v) for v in dims[:3])
+    FK = np.zeros((np_, np_))
+    rhov, l, u, ya, za, dy = (np.zeros(mEcap) for _ in range(6))
+    xa = np.zeros(np_); dx = np.zeros(np_)
+    _check(call(_ip(dims), _p(scal), _p(FK), _p(rhov), _p(l), _p(u), _p(xa), _p(ya), _p(za), _p(dy), _p(dx)), "read_admm")
+    return dict(np=np_, nblk=nblk, mEcap=mEcap, mE=int(dims[3]), kReady=int(dims[4]), setupFail=int(dims[5]), sigma=float(scal[0]),
+                rhoAdmm=float(scal[1]), scale=float(scal[2]), FK=FK, rhov=rhov, l=l, u=u, xa=xa, ya=ya, za=za, dy=dy, dx=dx)
 
 
 def _sensitivity(call, v, B, nV, nd, check=None):
@@ -385,6 +401,10 @@ class SubsolverHIP:
     def read_setup(self):
         """the constant matrices of the last fresh solve (test and diagnostic entry point; see BatchLCQP.read_setup)"""
         return _read_setup(lambda *a: lib().lcqp_hip_qp_read_setup(self.h, *a))
+
+    def read_admm(self):
+        """the state of the ADMM fallback as the last solve that ran it left it (test and diagnostic entry point; see BatchLCQP.read_admm)"""
+        return _read_admm(lambda *a: lib().lcqp_hip_qp_read_admm(self.h, *a))
 
     def read_working_set(self):
         """the inverse factor the last solve left (test and diagnostic entry point; see BatchLCQP.read_working_set)"""
@@ -830,6 +850,12 @@ class BatchLCQP(_Batch):
         dims = np.zeros(9, dtype=np.int32)
         _check(lib().lcqp_hip_batch_read_setup(self.h, b, _ip(dims), *[None] * 9), "read_setup")
         return _read_working_set(lambda *a: lib().lcqp_hip_batch_read_working_set(self.h, b, *a), int(dims[4]), int(dims[6]))
+
+    def read_admm(self, b):
+        """Test and diagnostic entry point: the ADMM fallback of instance b as the last QP that ran it left it -- np, nblk, mEcap, mE,
+        kReady, setupFail, sigma, rhoAdmm, scale; FK [np][np] (the symmetric-filled factor of Q + sigma I + E' diag(rhov) E, inverted
+        diagonal blocks), rhov, l, u, ya, za, dy [mEcap] and xa, dx [np]."""
+        return _read_admm(lambda *a: lib().lcqp_hip_batch_read_admm(self.h, b, *a))
 
     def setup(self):
         _check(lib().lcqp_hip_batch_setup(self.h), "setup")

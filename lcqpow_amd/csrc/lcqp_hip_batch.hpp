@@ -75,6 +75,14 @@ int batch_sensitivity_device(lcqp_hip_batch* h, bool blk, int nrhs, const double
 int batch_adjoint_device(lcqp_hip_batch* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
                          int reduce, double* dQ, double* dA, double* dL, double* dR);
 
+// one block of a read-back entry point (tests, diagnostics): `count` values from the device to dst, or nothing when the caller passed NULL
+template <class T>
+inline int read_back(T* dst, const T* src, size_t count)
+{
+    if (dst) HIPCHK(dense_err(), hipMemcpy(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 // the message of lcqp_hip_batch_update and its device twin for a variable whose box bound appears or disappears
 inline std::string box_change_message(int variable, int instance, bool gains)
 {

@@ -182,7 +182,7 @@ extern "C" void lcqp_hip_qp_get_counters(lcqp_hip_qp_t* q, int* admm, int* trial
     if (corrections) *corrections = q->cCorr;
 }); }
 
-// the QP object is a batch of one: the same two readers through its batch (LCQP_LCQPOBJECT_NOT_SETUP before the first solve built it)
+// the QP object is a batch of one: the same three readers through its batch (LCQP_LCQPOBJECT_NOT_SETUP before the first solve built it)
 extern "C" int lcqp_hip_qp_read_setup(lcqp_hip_qp_t* q, int dims[9], double scal[2], double* Cm, double* F1, double* D1, double* Et,
                                       double* MM, int* Cp, int* Ci, double* Cv)
 {
@@ -196,6 +196,14 @@ extern "C" int lcqp_hip_qp_read_working_set(lcqp_hip_qp_t* q, int dims[2], int* 
     if (!q) return LCQP_INVALID_ARGUMENT;
     if (!q->hb) return LCQP_LCQPOBJECT_NOT_SETUP;
     return lcqp_hip_batch_read_working_set(q->hb.get(), 0, dims, slot_row, crow, row_slot, Ti);
+}
+
+extern "C" int lcqp_hip_qp_read_admm(lcqp_hip_qp_t* q, int dims[6], double scal[3], double* FK, double* rhov, double* l, double* u,
+                                     double* xa, double* ya, double* za, double* dy, double* dx)
+{
+    if (!q) return LCQP_INVALID_ARGUMENT;
+    if (!q->hb) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return lcqp_hip_batch_read_admm(q->hb.get(), 0, dims, scal, FK, rhov, l, u, xa, ya, za, dy, dx);
 }
 
 // the derivatives of the convex QP last solved: k_sensitivity on the batch of one (dg [nrhs][nV], db / side [.][nV + nC], info [1])

@@ -307,3 +307,39 @@ extern "C" int lcqp_hip_chol_solve(int batch, int n, const double* K, const doub
     rc = time_launches(repeat, ms, [&] { hipLaunchKernelGGL(k_backsolve, dim3(batch), dim3(WG), 0, 0, np, nblk, dF, drhs, dx); });
     return rc ? rc : download_padded(x, dx, batch, 1, n, np, 1);
 }); }
+
+// =================================================================================================
+// read-back of the ADMM fallback (tests, diagnostics): the raw padded blocks of one instance, nothing is launched
+// =================================================================================================
+// L_K as it lies in FK, the rho vector, the bounds of the stacked rows and the iterates with their last change (qp_build_K, qp_admm,
+// qp_adapt_rho in lcqp_dev.hpp).  The polish writes none of them, so they are those of the last QP that ran ADMM.  (The readers of the
+// setup matrices and of the working set are in lcqp_hip.hip; this one stands here because that unit is one of the kernel sources the
+// committed profiles are keyed to, and a reader is no reason to void them.)
+extern "C" int lcqp_hip_batch_read_admm(lcqp_hip_batch_t* h, int b, int dims[6], double scal[3], double* FK, double* rhov, double* l, double* u,
+                                        double* xa, double* ya, double* za, double* dy, double* dx)
+{ return guarded(dense_err(), [&] {
+    if (!h || b < 0 || b >= h->db.B) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.setupValid) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (int rc = synchronize(dense_err(), h)) return rc;
+    HIPCHK(dense_err(), hipStreamSynchronize(h->side));
+    const DevBatch& d = h->db;
+    const size_t ib = b, np = d.np, mE = d.mEcap;
+    InstInfo info;
+    HIPCHK(dense_err(), hipMemcpy(&info, d.info + ib, sizeof(InstInfo), hipMemcpyDeviceToHost));
+    if (dims) {
+        const int v[6] = {d.np, d.nblk, d.mEcap, info.mE, info.kReady, info.setupFail};
+        memcpy(dims, v, sizeof v);
+    }
+    if (scal) { scal[0] = info.sigma; scal[1] = info.rhoAdmm; scal[2] = info.scale; }
+    const double *nv = d.nv + ib * V_NUM * np, *mv = d.mv + ib * M_NUM * mE;
+    int rc = read_back(FK, d.FK + ib * np * np, np * np);
+    if (!rc) rc = read_back(rhov, mv + (size_t)M_RHOV * mE, mE);
+    if (!rc) rc = read_back(l, mv + (size_t)M_L * mE, mE);
+    if (!rc) rc = read_back(u, mv + (size_t)M_U * mE, mE);
+    if (!rc) rc = read_back(xa, nv + (size_t)V_XA * np, np);
+    if (!rc) rc = read_back(ya, mv + (size_t)M_YA * mE, mE);
+    if (!rc) rc = read_back(za, mv + (size_t)M_ZA * mE, mE);
+    if (!rc) rc = read_back(dy, mv + (size_t)M_DY * mE, mE);
+    if (!rc) rc = read_back(dx, nv + (size_t)V_W * np, np);
+    return rc;
+}); }

@@ -111,10 +111,11 @@ def kkt_residuals(Q, g, A, lbA, ubA, lb, ub, x, y):
     return stat, pf, cs
 
 
-def certificate_qps(seed=3, n=24, m=30):
+def certificate_qps(seed=3, n=24, m=30, box=False):
     """two QPs for the certificates of the subsolver: (infeasible) a feasible polytope plus two rows that contradict each
     other, x_0 + x_1 >= 1 and x_0 + x_1 <= -1, on different rows so that no bound pair is inconsistent by itself;
-    (unbounded) a singular Hessian whose null space holds a descent direction that no constraint blocks."""
+    (unbounded) a singular Hessian whose null space holds a descent direction that no constraint blocks.
+    box: a box around the feasible point on the upper half of the variables (lb, ub in both dicts; x_0 stays free)."""
     r = np.random.default_rng(seed)
     M = r.standard_normal((n, n)); Q = M.T @ M / n + np.eye(n)
     A = r.standard_normal((m, n)) / np.sqrt(n); xs = r.standard_normal(n)
@@ -126,6 +127,10 @@ def certificate_qps(seed=3, n=24, m=30):
     A2 = r.standard_normal((m, n)) / np.sqrt(n); A2[:, 0] = 0        # ... nor any constraint
     g2 = r.standard_normal(n); g2[0] = 1.0                          # ... and decreasing it lowers the objective without bound
     unbounded = dict(Q=Q2, A=A2, g=g2, lbA=A2 @ xs - 1.0, ubA=A2 @ xs + 1.0)
+    if box:
+        lb = np.full(n, -np.inf); ub = np.full(n, np.inf)
+        lb[n // 2:] = xs[n // 2:] - r.uniform(0.5, 1.5, n - n // 2); ub[n // 2:] = xs[n // 2:] + r.uniform(0.5, 1.5, n - n // 2)
+        infeasible.update(lb=lb, ub=ub); unbounded.update(lb=lb.copy(), ub=ub.copy())
     return infeasible, unbounded
 
 

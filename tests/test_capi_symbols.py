@@ -67,6 +67,7 @@ def test_c_abi_rejects_bad_arguments_without_a_gpu():
     dims = (ctypes.c_int * 9)()
     assert L.lcqp_hip_batch_read_setup(None, 0, dims, *[None] * 9) != 0 and L.lcqp_hip_batch_read_working_set(None, 0, dims, *[None] * 4) != 0
     assert L.lcqp_hip_qp_read_setup(None, dims, *[None] * 9) != 0 and L.lcqp_hip_qp_read_working_set(None, dims, *[None] * 4) != 0
+    assert L.lcqp_hip_batch_read_admm(None, 0, dims, *[None] * 10) != 0 and L.lcqp_hip_qp_read_admm(None, dims, *[None] * 10) != 0
     n = ctypes.c_int(0)
     if la.device_count() == 0:
         # no GPU here: creating a batch must fail with the HIP error, never fall back to anything
@@ -81,6 +82,7 @@ def test_c_abi_rejects_bad_arguments_without_a_gpu():
         dims[0] = -7
         assert L.lcqp_hip_qp_read_setup(ctypes.c_void_p(q), dims, *[None] * 9) != 0
         assert L.lcqp_hip_qp_read_working_set(ctypes.c_void_p(q), dims, *[None] * 4) != 0
+        assert L.lcqp_hip_qp_read_admm(ctypes.c_void_p(q), dims, *[None] * 10) != 0
         assert dims[0] == -7
         L.lcqp_hip_qp_destroy(ctypes.c_void_p(q))
 
