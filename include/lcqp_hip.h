@@ -472,6 +472,51 @@ int  lcqp_hip_sparse_adjoint(lcqp_hip_sparse_t* s, const double* vx, const doubl
                              int reduce, double* dQx, double* dAx);
 /* another staging cap for this handle's adjoint calls (0: the default, LCQP_JACOBIAN_STAGING_BYTES); for tests of the chunking and for small devices */
 int  lcqp_hip_sparse_set_adjoint_staging(lcqp_hip_sparse_t* s, size_t bytes);
+/* ---- Device-pointer entry points of the sparse batch (DESIGN.md section 3a''''', "The sparse arm"): the twins of lcqp_hip_sparse_load / _update /
+ * _get_solution / _sensitivity / _adjoint whose data pointers are DEVICE pointers, under the rules of the dense device calls above.  Layouts,
+ * defaults for absent vectors and return codes are the host twins'; the pools, the solution and every gradient hold the bits the host twins
+ * leave, and the handle chooses the ordering and the light regularisation a host load of the same data chooses.  The differences:
+ *   pointers  every non-NULL data pointer is plain device memory (hipMalloc) of the handle's device that holds the bytes the call moves; host,
+ *             pinned and managed memory and another device's memory are refused with LCQP_INVALID_ARGUMENT and a message, on the host, before
+ *             anything is enqueued.  dQx must be 16-byte aligned (the Q segment of the gradient kernels stores pairs of doubles), dAx 8-byte.
+ *   stream    the caller's hipStream_t (NULL: the legacy default stream).  The handle's stream waits for an event recorded on it, the work is
+ *             enqueued on the handle's stream, and the caller's stream waits for an event recorded behind it.  run and resolve stay on the
+ *             handle's stream: update_device -> resolve -> get_solution_device needs no host wait, and update_device does not drain the
+ *             stream the way lcqp_hip_sparse_update does -- stream order replaces that.  load_device and update_device wait for ONE status
+ *             read each (the check below; for a load with Qx also two numbers per instance from the diagonal of its Hessian, from which the
+ *             host forms the ratio that selects the ordering); a call also waits when a buffer of the handle grows.  Nothing else waits.
+ *   shared    (load) bit 1: Qx is ONE [nnzQ] array for all `count` instances, bit 2: the same for Ax (broadcast by the pack kernel; the
+ *             setting reduce = 1 of the adjoint is meant for).  Other bits: LCQP_INVALID_ARGUMENT.
+ *   NULL Qx / Ax (load) leaves those values as the batch holds them; every instance of the range must then already hold a problem, else
+ *             LCQP_INVALID_ARGUMENT (the host twin's code for a missing matrix).  g stays mandatory: LCQP_INVALID_OBJECTIVE_LINEAR_TERM.
+ *   validation -inf in lbL / lbR is looked for by one kernel over the whole range before anything is written; on a failure nothing is
+ *             written, NO host state changes, and the code is LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND.  This is deliberately stricter than
+ *             lcqp_hip_sparse_load, which clears the setup mark first and may have written the instances in front of the offending one.
+ *   NULL handle: LCQP_LCQPOBJECT_NOT_SETUP from all five.
+ * The two paths mix on one handle: the host state (which instances hold problems, the lbL / lbR flags, the diagonal ratios, the setup mark)
+ * is kept in step.  sensitivity_device / adjoint_device make the state checks of their host twins (LCQP_INVALID_ARGUMENT for NULL v / vx / dg,
+ * nrhs < 1, reduce outside 0 / 1; then LCQP_LCQPOBJECT_NOT_SETUP without a finished solve); v [B][nrhs][nV], vx [B][nV], vy [B][m] are read
+ * where they lie; dQx / dAx ([B][nnz], or [nnz] with reduce = 1) are written by ONE launch, without staging or chunks, with the terms -- hence
+ * the bits -- of the host call.  stats of get_solution_device is a device array of B lcqp_stats_t.  The kernel time of the two is formed when
+ * lcqp_hip_sparse_sensitivity_timing asks for it (that call then waits for the kernels). */
+int  lcqp_hip_sparse_load_device(lcqp_hip_sparse_t* s, int first, int count, int shared,
+                                 const double* Qx, const double* g, const double* Ax,
+                                 const double* lbA, const double* ubA, const double* lbL, const double* ubL,
+                                 const double* lbR, const double* ubR, const double* x0, const double* y0, void* stream);
+int  lcqp_hip_sparse_update_device(lcqp_hip_sparse_t* s, int first, int count, const double* g,
+                                   const double* lbA, const double* ubA, const double* lbL, const double* ubL,
+                                   const double* lbR, const double* ubR, const double* x0, const double* y0, void* stream);
+int  lcqp_hip_sparse_get_solution_device(lcqp_hip_sparse_t* s, double* x, double* y, lcqp_stats_t* stats, void* stream);
+int  lcqp_hip_sparse_sensitivity_device(lcqp_hip_sparse_t* s, int nrhs, const double* v,
+                                        double* dg, double* db, int* side, int* info, void* stream);
+int  lcqp_hip_sparse_adjoint_device(lcqp_hip_sparse_t* s, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
+                                    int reduce, double* dQx, double* dAx, void* stream);
+/* Test and diagnostic entry point: the problem of one instance as the pools hold it, so that a load or an update can be held bit for bit and
+ * not only through solutions.  Host buffers, synchronous, launches nothing; any output may be NULL.  Qx [nnzQ]; Ax [nnzA] in the caller's CSC
+ * order (through the inverse of the value map); g, x0 [nV]; lE, uE [m]: the stacked row bounds as stored, m = nC + 2 nComp; lbL, lbR [nComp];
+ * y0 [m]; hasY0 [1].  LCQP_INVALID_ARGUMENT: NULL handle, or an instance outside the batch. */
+int  lcqp_hip_sparse_read_problem(lcqp_hip_sparse_t* s, int instance, double* Qx, double* Ax, double* g,
+                                  double* lE, double* uE, double* lbL, double* lbR, double* x0, double* y0, int* hasY0);
 /* Test and diagnostic entry point (as lcqp_hip_batch_read_setup / _read_working_set on the dense arm): the KKT factorisations and solves
  * of the sparse arm -- the register band, the LDS-window band, the bordered band, the general LDL' -- run for every instance of the batch
  * on matrices the caller names, one solve per right-hand side and NO refinement, so that tests/test_gpu_sparse_factor.py can hold each engine

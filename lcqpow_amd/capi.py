@@ -180,6 +180,12 @@ def lib():
         L.lcqp_hip_sparse_sensitivity_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.lcqp_hip_sparse_adjoint.argtypes = [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p, C.c_int] + [c_double_p] * 2
         L.lcqp_hip_sparse_set_adjoint_staging.argtypes = [C.c_void_p, C.c_size_t]
+        L.lcqp_hip_sparse_load_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11 + [C.c_void_p]
+        L.lcqp_hip_sparse_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_void_p]
+        L.lcqp_hip_sparse_get_solution_device.argtypes = [C.c_void_p] * 5
+        L.lcqp_hip_sparse_sensitivity_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        L.lcqp_hip_sparse_adjoint_device.argtypes = [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 3
+        L.lcqp_hip_sparse_read_problem.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 9 + [c_int_p]
         L.lcqp_hip_sparse_kkt_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p,
                                                 c_double_p, c_double_p, c_int_p]
         _lib = L
@@ -329,12 +335,13 @@ def split_bound_derivatives(db, side, nV, nC, nComp, sparse=False):
                 dlbR=lo[..., r:], dubR=hi[..., r:])
 
 
-def split_bound_derivatives_torch(db, side, nV, nC, nComp):
-    """split_bound_derivatives (dense layout) on torch tensors, where they lie: the same selections, nothing through the host"""
+def split_bound_derivatives_torch(db, side, nV, nC, nComp, sparse=False):
+    """split_bound_derivatives on torch tensors, where they lie: the same selections, nothing through the host"""
     sd = side if db.dim() == side.dim() else side[:, None, :]
     zero = db.new_zeros(())
     lo = db.where((sd == -1) | (sd == 2), zero); hi = db.where((sd == 1) | (sd == 2), zero)
-    a, l, r = nV, nV + nC, nV + nC + nComp
+    a = 0 if sparse else nV
+    l, r = a + nC, a + nC + nComp
     return dict(dlb=lo[..., :a], dub=hi[..., :a], dlbA=lo[..., a:l], dubA=hi[..., a:l], dlbL=lo[..., l:r], dubL=hi[..., l:r],
                 dlbR=lo[..., r:], dubR=hi[..., r:])
 
@@ -609,6 +616,39 @@ class _Batch:
     def algorithmic_bytes(self):
         return self._sym("algorithmic_bytes")(self.h)
 
+    # ---- what the device-pointer entry points of both arms share (DESIGN.md section 3a'''''): the checks of a tensor argument, the
+    # stream the call is ordered behind, the range of instances.  A subclass sets self.device.
+    def _dev(self, name, t, shapes, optional=True):
+        """the device address of a tensor argument (None: NULL) after the checks the C side cannot make: a float64, contiguous torch tensor
+        on the handle's device of one of `shapes`; anything else raises ValueError"""
+        import torch
+        if t is None:
+            if optional:
+                return None
+            raise ValueError(f"{name}: must be given")
+        if not isinstance(t, torch.Tensor):
+            raise ValueError(f"{name}: expected a torch tensor on the device of the batch, got {type(t).__name__}")
+        if t.dtype != torch.float64 or not t.is_contiguous():
+            raise ValueError(f"{name}: expected a contiguous float64 tensor, got {t.dtype}{'' if t.is_contiguous() else ', not contiguous'}")
+        if t.device.type != "cuda" or t.device.index != self.device:
+            raise ValueError(f"{name}: expected a tensor on cuda:{self.device}, got one on {t.device}")
+        if tuple(t.shape) not in shapes:
+            raise ValueError(f"{name}: expected shape {' or '.join(str(list(s)) for s in shapes)}, got {list(t.shape)}")
+        return t.data_ptr() if t.numel() else None
+
+    def _stream(self):
+        """the current torch stream of the handle's device.  Raises when the library and torch do not share one HIP runtime (lib())."""
+        import torch
+        lib()
+        if _runtime != "torch" and _torch_hip_runtime():
+            raise RuntimeError("the device-pointer entry points need the library and torch on ONE HIP runtime: import torch before the first "
+                               "use of lcqpow_amd (the library was loaded first and is bound to the system's runtime)")
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _range(self, first, count):
+        if not (isinstance(first, int) and isinstance(count, int)) or first < 0 or count <= 0 or first + count > self.B:
+            raise ValueError(f"instances [{first}, {first} + {count}) outside the batch of {self.B}")
+
     def close(self):
         if self.h:
             self._sym("destroy")(self.h)
@@ -697,37 +737,6 @@ class BatchLCQP(_Batch):
 
     # ---- the device-pointer entry points (DESIGN.md section 3a'''''): torch tensors on the handle's device in, torch tensors out; the work is
     # ordered behind torch.cuda.current_stream(), and what the caller enqueues there next sees the results.  No copy through the host.
-    def _dev(self, name, t, shapes, optional=True):
-        """the device address of a tensor argument (None: NULL) after the checks the C side cannot make: a float64, contiguous torch tensor
-        on the handle's device of one of `shapes`; anything else raises ValueError"""
-        import torch
-        if t is None:
-            if optional:
-                return None
-            raise ValueError(f"{name}: must be given")
-        if not isinstance(t, torch.Tensor):
-            raise ValueError(f"{name}: expected a torch tensor on the device of the batch, got {type(t).__name__}")
-        if t.dtype != torch.float64 or not t.is_contiguous():
-            raise ValueError(f"{name}: expected a contiguous float64 tensor, got {t.dtype}{'' if t.is_contiguous() else ', not contiguous'}")
-        if t.device.type != "cuda" or t.device.index != self.device:
-            raise ValueError(f"{name}: expected a tensor on cuda:{self.device}, got one on {t.device}")
-        if tuple(t.shape) not in shapes:
-            raise ValueError(f"{name}: expected shape {' or '.join(str(list(s)) for s in shapes)}, got {list(t.shape)}")
-        return t.data_ptr() if t.numel() else None
-
-    def _stream(self):
-        """the current torch stream of the handle's device.  Raises when the library and torch do not share one HIP runtime (lib())."""
-        import torch
-        lib()
-        if _runtime != "torch" and _torch_hip_runtime():
-            raise RuntimeError("the device-pointer entry points need the library and torch on ONE HIP runtime: import torch before the first "
-                               "use of lcqpow_amd (the library was loaded first and is bound to the system's runtime)")
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def _range(self, first, count):
-        if not (isinstance(first, int) and isinstance(count, int)) or first < 0 or count <= 0 or first + count > self.B:
-            raise ValueError(f"instances [{first}, {first} + {count}) outside the batch of {self.B}")
-
     def _device_vectors(self, count, g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0):
         n, nC, nK = self.nV, self.nC, self.nComp
         if g is None:
@@ -962,6 +971,7 @@ class SparseBatchLCQP(_Batch):
     def __init__(self, batch, nV, nC, nComp, Qpat, Apat, device=0, opt=None):
         self.B, self.nV, self.nC, self.nComp = batch, nV, nC, nComp
         self.m = self._ndual = nC + 2 * nComp
+        self.device = device
         self._pat = [np.ascontiguousarray(a, dtype=np.int32) for a in (Qpat.indptr, Qpat.indices, Apat.indptr, Apat.indices)]
         if self._pat[0].size != nV + 1 or self._pat[2].size != nV + 1:
             raise ValueError("pattern column pointers must have nV + 1 entries (CSC)")
@@ -1059,3 +1069,100 @@ class SparseBatchLCQP(_Batch):
                  ("x0", x0, n), ("y0", y0, self.m))
         a = [_sized(nm, _arr(v), max(count, 0) * sz) for nm, v, sz in sizes]
         return lib().lcqp_hip_sparse_update(self.h, first, count, *[_p(v) for v in a])
+
+    # ---- the device-pointer entry points (DESIGN.md section 3a''''', "The sparse arm"): torch tensors on the handle's device in, torch tensors
+    # out; the work is ordered behind torch.cuda.current_stream(), and what the caller enqueues there next sees the results.
+    def _device_vectors(self, count, g, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0):
+        n, nC, nK = self.nV, self.nC, self.nComp
+        if g is None:
+            return [None] * 9
+        args = (("g", g, n), ("lbA", lbA, nC), ("ubA", ubA, nC), ("lbL", lbL, nK), ("ubL", ubL, nK), ("lbR", lbR, nK), ("ubR", ubR, nK),
+                ("x0", x0, n), ("y0", y0, self.m))
+        return [self._dev(nm, v, ((count, sz),)) for nm, v, sz in args]
+
+    def load_device(self, first, count, Qx, g, Ax, lbA=None, ubA=None, lbL=None, ubL=None, lbR=None, ubR=None, x0=None, y0=None):
+        """lcqp_hip_sparse_load_device: load() from float64 torch tensors on the handle's device, packed into the pools by kernels.  A
+        value tensor of shape [nnz] is ONE array for all `count` instances (broadcast by the pack kernel), one of shape [count][nnz]
+        holds one per instance; one that is None stays as the batch holds it (every instance of the range must hold a problem then).
+        Returns the ReturnValue code like load; the pools hold the bytes load leaves."""
+        self._range(first, count)
+        shared, ptr = 0, {}
+        for bit, (nm, t, nnz) in enumerate((("Qx", Qx, self.nnzQ), ("Ax", Ax, self.nnzA))):
+            ptr[nm] = self._dev(nm, t, ((nnz,), (count, nnz)))
+            if t is not None and t.dim() == 1:
+                shared |= 1 << bit
+        v = self._device_vectors(count, g, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0)
+        return lib().lcqp_hip_sparse_load_device(self.h, first, count, shared, ptr["Qx"], v[0], ptr["Ax"], *v[1:], self._stream())
+
+    def update_device(self, first, count, g, lbA=None, ubA=None, lbL=None, ubL=None, lbR=None, ubR=None, x0=None, y0=None):
+        """lcqp_hip_sparse_update_device: update() from float64 torch tensors on the handle's device; the call does not drain the handle's
+        stream, it is ordered behind it.  Returns the ReturnValue code."""
+        self._range(first, count)
+        v = self._device_vectors(count, g, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0)
+        return lib().lcqp_hip_sparse_update_device(self.h, first, count, *v, self._stream())
+
+    def solution_device(self, stats=False):
+        """lcqp_hip_sparse_get_solution_device: (x [B][nV], y [B][m]) as float64 tensors on the handle's device, ordered behind the run on
+        the current torch stream; nothing waits on the host.  stats=True: a third tensor, [B][sizeof(lcqp_stats_t)] bytes."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        x = torch.empty((self.B, self.nV), dtype=torch.float64, device=dev); y = torch.empty((self.B, self.m), dtype=torch.float64, device=dev)
+        st = torch.empty((self.B, C.sizeof(Stats)), dtype=torch.uint8, device=dev) if stats else None
+        self._call("get_solution_device", x.data_ptr(), y.data_ptr(), st.data_ptr() if stats else None, self._stream())
+        return (x, y, st) if stats else (x, y)
+
+    def sensitivity_device(self, v):
+        """lcqp_hip_sparse_sensitivity_device: sensitivity(v) with v a float64 tensor on the handle's device, [B][nV] or [B][k][nV], read
+        where it lies; returns (dg, db, side, info) as tensors on that device (side, info: int32)."""
+        import torch
+        B, n, m = self.B, self.nV, self.m
+        if isinstance(v, torch.Tensor) and v.dim() == 3 and v.shape[1] < 1:
+            raise ValueError("v: no vectors")
+        k = v.shape[1] if isinstance(v, torch.Tensor) and v.dim() == 3 else 1
+        pv = self._dev("v", v, ((B, n), (B, k, n)), optional=False)
+        dev = torch.device("cuda", self.device)
+        lead = (B,) if v.dim() == 2 else (B, k)
+        dg = torch.empty(lead + (n,), dtype=torch.float64, device=dev); db = torch.empty(lead + (m,), dtype=torch.float64, device=dev)
+        side = torch.empty((B, m), dtype=torch.int32, device=dev); info = torch.empty(B, dtype=torch.int32, device=dev)
+        self._call("sensitivity_device", k, pv, dg.data_ptr(), db.data_ptr(), side.data_ptr(), info.data_ptr(), self._stream())
+        return dg, db, side, info
+
+    def adjoint_device(self, vx, vy=None, matrices=("Q", "A"), reduce=False, out=None):
+        """lcqp_hip_sparse_adjoint_device: adjoint(vx, vy, matrices, reduce) with float64 tensors on the handle's device in and out -- the
+        gradients on the non-zeros are written by ONE launch straight into their tensors, whatever their size (no staging, no chunks).
+        out: tensors to write them into, by name ("Q": 16-byte aligned; default: fresh ones).  Returns the dict of adjoint, of tensors."""
+        import torch
+        B, n, m = self.B, self.nV, self.m
+        shapes = dict(Q=(self.nnzQ,), A=(self.nnzA,))
+        unknown = set(matrices) - set(shapes)
+        if unknown:
+            raise ValueError(f"matrices: unknown names {sorted(unknown)} (this object has {sorted(shapes)})")
+        pvx = self._dev("vx", vx, ((B, n),), optional=False); pvy = self._dev("vy", vy, ((B, m),))
+        dev = torch.device("cuda", self.device)
+        r = dict(dg=torch.empty((B, n), dtype=torch.float64, device=dev), db=torch.empty((B, m), dtype=torch.float64, device=dev),
+                 side=torch.empty((B, m), dtype=torch.int32, device=dev), info=torch.empty(B, dtype=torch.int32, device=dev))
+        lead = () if reduce else (B,)
+        mats = {}
+        for k in shapes:
+            if k in matrices:
+                t = (out or {}).get(k)
+                if t is None:      # the kernels write every entry
+                    t = torch.empty(lead + shapes[k], dtype=torch.float64, device=dev)
+                self._dev(k, t, (lead + shapes[k],))
+                mats[k] = t
+        ptrs = [mats[k].data_ptr() if k in mats and mats[k].numel() else None for k in shapes]
+        self._call("adjoint_device", pvx, pvy, r["dg"].data_ptr(), r["db"].data_ptr(), r["side"].data_ptr(), r["info"].data_ptr(),
+                   1 if reduce else 0, *ptrs, self._stream())
+        r.update(mats)
+        return r
+
+    def read_problem(self, b):
+        """Test and diagnostic entry point (lcqp_hip_sparse_read_problem): instance b as the pools hold it -- Qx [nnzQ], Ax [nnzA] in the
+        order of load, g, x0 [nV], lE, uE [m] (the stacked row bounds), lbL, lbR [nComp], y0 [m], hasY0 (int)."""
+        n, m, nK = self.nV, self.m, self.nComp
+        d = dict(Qx=np.zeros(self.nnzQ), Ax=np.zeros(self.nnzA), g=np.zeros(n), lE=np.zeros(m), uE=np.zeros(m), lbL=np.zeros(nK), lbR=np.zeros(nK),
+                 x0=np.zeros(n), y0=np.zeros(m))
+        has = C.c_int(0)
+        self._call("read_problem", int(b), *[_p(d[k]) for k in ("Qx", "Ax", "g", "lE", "uE", "lbL", "lbR", "x0", "y0")], C.byref(has))
+        d["hasY0"] = has.value
+        return d

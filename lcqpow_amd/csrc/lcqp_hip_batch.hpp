@@ -5,7 +5,6 @@
 #include "lcqp_launch.hpp"
 #include "lcqp_host_rt.hpp"
 
-#include <cstdint>
 #include <string>
 #include <vector>
 
@@ -90,54 +89,7 @@ inline std::string box_change_message(int variable, int instance, bool gains)
            " its box bound; the set of bounded variables is fixed by the load (they are rows of the factored matrices)";
 }
 
-// ---- the device-pointer entry points: what lcqp_hip.hip (sensitivity, adjoint) and lcqp_hip_device.hip (load, update, solution) share ----
-// A data pointer of such a call: NULL, or plain device memory of the handle's device with `bytes` behind it (align: 8, or 16 for dQ ... dR).
-// Anything else -- pageable, pinned or managed host memory, another device -- leaves a message and returns false; nothing is dereferenced.
-inline bool device_pointer_ok(std::string& err, const lcqp_hip_batch* h, const char* name, const void* p, size_t bytes, size_t align = 8)
-{
-    if (!p) return true;
-    hipPointerAttribute_t at{};
-    const hipError_t e = hipPointerGetAttributes(&at, p);
-    if (e != hipSuccess) (void)hipGetLastError();
-    if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.isManaged) {
-        err = std::string(name) + ": not a device pointer (the *_device entry points take plain device memory; host, pinned and managed memory go through the host entry points)";
-        return false;
-    }
-    if (at.device != h->device) {
-        err = std::string(name) + ": memory of device " + std::to_string(at.device) + ", the batch lives on device " + std::to_string(h->device);
-        return false;
-    }
-    if ((size_t)(uintptr_t)p % align) {
-        err = std::string(name) + ": not aligned to " + std::to_string(align) + " bytes";
-        return false;
-    }
-    void* base = nullptr; size_t size = 0;
-    if (hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return true; }
-    if ((const char*)p + bytes > (const char*)base + size) {
-        err = std::string(name) + ": the allocation ends before the " + std::to_string(bytes) + " bytes the call moves";
-        return false;
-    }
-    return true;
-}
-
-// The hand-over of a device-pointer call: the handle's stream waits for what the caller's stream holds so far (the constructor), the
-// caller's stream for what the call enqueued on the handle's stream (done()).  Nothing waits on the host.
-struct StreamHandOver {
-    lcqp_hip_batch* h;
-    hipStream_t caller;
-    hipError_t status = hipSuccess;
-    StreamHandOver(lcqp_hip_batch* h_, void* stream) : h(h_), caller((hipStream_t)stream)
-    {
-        if (caller == h->stream.s) return;
-        status = hipEventRecord(h->evIn, caller);
-        if (status == hipSuccess) status = hipStreamWaitEvent(h->stream, h->evIn, 0);
-    }
-    hipError_t done()
-    {
-        if (caller == h->stream.s) return hipSuccess;
-        const hipError_t e = hipEventRecord(h->evOut, h->stream);
-        return e != hipSuccess ? e : hipStreamWaitEvent(caller, h->evOut, 0);
-    }
-};
+// (device_pointer_ok and StreamHandOver, which the device-pointer entry points of lcqp_hip.hip and lcqp_hip_device.hip are built on, are
+// templates on the handle in lcqp_host_rt.hpp: the sparse arm shares them)
 
 #pragma GCC visibility pop

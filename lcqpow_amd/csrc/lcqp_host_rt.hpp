@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -297,6 +298,59 @@ int sensitivity_timing(H* h, float* kernel_ms)
     *kernel_ms = h->rs.sensMs;
     return 0;
 }
+// ---- the device-pointer entry points of both arms (lcqp_hip.hip, lcqp_hip_device.hip; lcqp_sparse_host.hip, lcqp_sparse_device.hip): H has
+// device, stream and the two events evIn / evOut (hipEventDisableTiming) ----
+// A data pointer of such a call: NULL, or plain device memory of the handle's device with `bytes` behind it (align: 8, or 16 where a kernel stores pairs of doubles).
+// Anything else -- pageable, pinned or managed host memory, another device -- leaves a message and returns false; nothing is dereferenced.
+template <class H>
+bool device_pointer_ok(std::string& err, const H* h, const char* name, const void* p, size_t bytes, size_t align = 8)
+{
+    if (!p) return true;
+    hipPointerAttribute_t at{};
+    const hipError_t e = hipPointerGetAttributes(&at, p);
+    if (e != hipSuccess) (void)hipGetLastError();
+    if (e != hipSuccess || at.type != hipMemoryTypeDevice || at.isManaged) {
+        err = std::string(name) + ": not a device pointer (the *_device entry points take plain device memory; host, pinned and managed memory go through the host entry points)";
+        return false;
+    }
+    if (at.device != h->device) {
+        err = std::string(name) + ": memory of device " + std::to_string(at.device) + ", the batch lives on device " + std::to_string(h->device);
+        return false;
+    }
+    if ((size_t)(uintptr_t)p % align) {
+        err = std::string(name) + ": not aligned to " + std::to_string(align) + " bytes";
+        return false;
+    }
+    void* base = nullptr; size_t size = 0;
+    if (hipMemGetAddressRange((hipDeviceptr_t*)&base, &size, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); return true; }
+    if ((const char*)p + bytes > (const char*)base + size) {
+        err = std::string(name) + ": the allocation ends before the " + std::to_string(bytes) + " bytes the call moves";
+        return false;
+    }
+    return true;
+}
+
+// The hand-over of a device-pointer call: the handle's stream waits for what the caller's stream holds so far (the constructor), the
+// caller's stream for what the call enqueued on the handle's stream (done()).  Nothing waits on the host.
+template <class H>
+struct StreamHandOver {
+    H* h;
+    hipStream_t caller;
+    hipError_t status = hipSuccess;
+    StreamHandOver(H* h_, void* stream) : h(h_), caller((hipStream_t)stream)
+    {
+        if (caller == h->stream.s) return;
+        status = hipEventRecord(h->evIn, caller);
+        if (status == hipSuccess) status = hipStreamWaitEvent(h->stream, h->evIn, 0);
+    }
+    hipError_t done()
+    {
+        if (caller == h->stream.s) return hipSuccess;
+        const hipError_t e = hipEventRecord(h->evOut, h->stream);
+        return e != hipSuccess ? e : hipStreamWaitEvent(caller, h->evOut, 0);
+    }
+};
+
 #pragma GCC visibility pop
 
 // Row bounds of instance k of a load (setConstraints / setComplementarityBounds, src/LCQProblem.cpp:563-626, 726-785): lE / uE rows

@@ -1,12 +1,12 @@
 // lcqp_sparse_host.hip -- the host side of the sparse arm: the C ABI lcqp_hip_sparse_* (include/lcqp_hip.h).  The handle, the pattern
 // analysis (lcqp_sparse_pattern.hpp) and the storage of a batch in create, load / update / run / resolve, sensitivities, the full adjoint,
-// the readers, and the LCQP_SPARSE_* environment test hooks.  The kernels of the solver are not defined here: they are in lcqp_sparse.hip,
+// the device-pointer twins of the last two, the readers, and the LCQP_SPARSE_* environment test hooks (the device-pointer load / update /
+// solution and their kernels: lcqp_sparse_device.hip; lcqp_sparse_batch.hpp holds what the two units share).  The kernels of the solver are not defined here: they are in lcqp_sparse.hip,
 // one translation unit per lane-group width G, reached through the launch tables of lcqp_sparse_launch.hpp.  The two kernels that do not
 // depend on the width -- the matrix gradients of lcqp_hip_sparse_adjoint -- sit beside the entry point that launches them, as
 // k_adjoint_outer / k_adjoint_reduce do in lcqp_hip.hip.
-#include "lcqp_sparse_launch.hpp"
+#include "lcqp_sparse_batch.hpp"
 #include "lcqp_sparse_pattern.hpp"
-#include "lcqp_host_rt.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -20,38 +20,8 @@ using namespace lcqp_rt;
 using namespace lcqp_sparse;
 
 static thread_local std::string g_sp_err;
+std::string& sparse_err() { return g_sp_err; }
 extern "C" const char* lcqp_hip_sparse_last_error(void) { return g_sp_err.c_str(); }
-
-// The members are released in reverse order after the destructor's synchronisation: device memory, events, stream.
-struct lcqp_hip_sparse {
-    SpBatch db;
-    int device;
-    int cus = 0;                   // compute units of `device` (create): bounds the persistent wavefronts of a run
-    Stream stream;
-    Event ev0, ev1, ev2;           // run: setup from ev0 to ev1, homotopy from ev1 to ev2
-    DevMem mem{stream};            // zero-fills on the handle's stream
-    std::vector<int> csr2csc;      // value order: E (CSR) entry k comes from entry csr2csc[k] of the caller's CSC arrays
-    // the two orderings of the band (lcqp_sparse_pattern.hpp: Pattern::ord): device copies of their maps, the permutation for get_ordering
-    struct Ord { std::vector<int> perm; int *iperm, *bandQ, *bandE, *bsrc, *bgate, *bdiag, *pnode, *Upos; bool rowsFollow; } ord[2] = {};
-    bool hasB = false;
-    int useB = 0;                  // ordering of the last sp_choose_ordering
-    std::vector<int> qdiagHost;    // entry of Q_ii in the value array
-    std::vector<double> diagRatio; // per instance: min_i Q_ii / max_i Q_ii of the loaded Hessian (1: not loaded yet)
-    bool loaded = false, ran = false;
-    // re-solves and sensitivities (lcqp_host_rt.hpp).  This arm has no setup without a solve: setupValid and solved go together;
-    // rhoStart is allocated by the first resolve that carries penalties
-    ResolveState rs;
-    SensBuffers sens;
-    // of lcqp_hip_sparse_adjoint, grown on demand: the upstream gradients on the duals [B][m]; the gradients on the non-zeros of one chunk of
-    // instances; the device copy of csr2csc (one per pattern, uploaded by the first call that asks for dAx); the events around its kernels
-    size_t adjStaging = LCQP_JACOBIAN_STAGING_BYTES;
-    double *adjVy = nullptr, *adjOut = nullptr;
-    size_t adjVyCap = 0, adjOutCap = 0;
-    int* adjMap = nullptr;
-    Event adjEv0, adjEv1;
-    explicit lcqp_hip_sparse(int dev) : db(), device(dev) {}
-    ~lcqp_hip_sparse() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
-};
 
 // ---- the gradients on the non-zeros of an adjoint call (DESIGN.md section 3a'''', lcqp_hip_sparse_adjoint) ----------------------------------
 // With dg, db, side and info of k_sparse_sensitivity (nrhs = 1, still in its device buffers) and the returned x, y of instance b:
@@ -161,7 +131,7 @@ __global__ __launch_bounds__(SP_ADJ_WG) void k_sparse_adjoint_reduce(SpAdjointAr
 
 // Ordering [1] and the light regularisation of the polish are for batches whose Hessians are safely definite, judged by their diagonals
 // (min Q_ii >= 1e-6 max Q_ii in every loaded instance); the pivot check of sp_polish covers what the diagonals do not show.
-static void sp_choose_ordering(lcqp_hip_sparse* h)
+void sp_choose_ordering(lcqp_hip_sparse* h)
 {
     bool definite = h->loaded;      // nothing loaded yet: the plain ordering
     for (double r : h->diagRatio) definite = definite && (r >= 1e-6);
@@ -198,7 +168,7 @@ extern "C" lcqp_hip_sparse_t* lcqp_hip_sparse_create(int batch, int nV, int nC, 
     const lcqp_general::Symbolic& sym = P.sym;
     if (hipError_t e = hipSetDevice(device)) { hip_fail(g_sp_err, "hipSetDevice failed", e); return nullptr; }
     std::unique_ptr<lcqp_hip_sparse> h(new lcqp_hip_sparse(device));
-    for (hipError_t e : {h->stream.status, h->ev0.status, h->ev1.status, h->ev2.status})
+    for (hipError_t e : {h->stream.status, h->ev0.status, h->ev1.status, h->ev2.status, h->evIn.status, h->evOut.status})
         if (e != hipSuccess) { hip_fail(g_sp_err, "stream/event creation", e); return nullptr; }
     if (hipError_t e = hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device)) { hip_fail(g_sp_err, "hipDeviceGetAttribute(multiprocessor count)", e); return nullptr; }
     h->csr2csc = P.csr2csc; h->hasB = P.hasB; h->qdiagHost = P.qdiag; h->diagRatio.assign(batch, 1.0); h->rs.filled.assign(batch, 0);
@@ -474,24 +444,50 @@ static int sp_grow(lcqp_hip_sparse* h, double*& p, size_t& cap, size_t count)
     return 0;
 }
 
+// the device copy of the one value map of the pattern (a permutation of the positions of the caller's Ax), uploaded once: entry k of the CSR
+// arrays of E is entry valMap[k] of the caller's CSC array.  The adjoint scatters through it, a device load gathers through it.
+int sp_value_map(lcqp_hip_sparse* h)
+{
+    if (h->valMap) return 0;
+    const SpBatch& d = h->db;
+    for (int k : h->csr2csc) if (k < 0 || k >= d.nnzE) { g_sp_err = "the value map of the pattern is out of range"; return LCQP_HIP_ERROR; }
+    if ((int)h->csr2csc.size() != d.nnzE) { g_sp_err = "the value map of the pattern has the wrong length"; return LCQP_HIP_ERROR; }
+    if (!h->mem.alloc(g_sp_err, h->valMap, h->csr2csc.size(), h->csr2csc.data())) return LCQP_HIP_ERROR;
+    return 0;
+}
+
 // ---- solution sensitivities (DESIGN.md section 3a''): one launch of k_sparse_sensitivity on the handle's stream, host buffers in and out,
-// its kernel time in *ms.  vy ([B][nrhs][m], host): the DUAL instantiation of lcqp_hip_sparse_adjoint ----
-static int sp_sensitivity_launch(lcqp_hip_sparse* h, int nrhs, const double* v, const double* vy, double* dg, double* db, int* side, int* info, float* ms)
+// its kernel time in *ms.  vy ([B][nrhs][m]): the DUAL instantiation of lcqp_hip_sparse_adjoint.  dev (the device-pointer twins): v and vy are
+// device arrays, read where they lie; the results go to the caller's device arrays with copies on the handle's stream, nothing waits on the
+// host, and the kernel time stays in the events until lcqp_hip_sparse_sensitivity_timing asks for it (sensPending) ----
+static int sp_sensitivity_launch(lcqp_hip_sparse* h, int nrhs, const double* v, const double* vy, double* dg, double* db, int* side, int* info, float* ms,
+                                 bool dev = false)
 {
     SpBatch& d = h->db;
     SensBuffers& sb = h->sens;
     HIPCHK(g_sp_err, hipSetDevice(h->device));
     if (int rc = sb.reserve(g_sp_err, h->mem, h->stream, d.B, nrhs, d.n, d.n, d.m, d.m)) return rc;
-    if (int rc = sb.upload(g_sp_err, v)) return rc;
-    if (vy) {
-        if (int rc = sp_grow(h, h->adjVy, h->adjVyCap, sb.rows * d.m)) return rc;
-        HIPCHK(g_sp_err, hipMemcpyAsync(h->adjVy, vy, sizeof(double) * sb.rows * d.m, hipMemcpyHostToDevice, h->stream));
+    h->sensPending = 0;
+    const double *dv = v, *dvy = vy;
+    if (!dev) {
+        if (int rc = sb.upload(g_sp_err, v)) return rc;
+        dv = sb.v;
+        if (vy) {
+            if (int rc = sp_grow(h, h->adjVy, h->adjVyCap, sb.rows * d.m)) return rc;
+            HIPCHK(g_sp_err, hipMemcpyAsync(h->adjVy, vy, sizeof(double) * sb.rows * d.m, hipMemcpyHostToDevice, h->stream));
+            dvy = h->adjVy;
+        }
     }
     HIPCHK(g_sp_err, hipEventRecord(sb.ev0, h->stream));
-    if (vy) sp_kernels(d.G)->sensitivity_dual(d, h->stream, nrhs, sb.v, h->adjVy, sb.dg, sb.db, sb.side, sb.info);
-    else sp_kernels(d.G)->sensitivity(d, h->stream, nrhs, sb.v, sb.dg, sb.db, sb.side, sb.info);
+    if (vy) sp_kernels(d.G)->sensitivity_dual(d, h->stream, nrhs, dv, dvy, sb.dg, sb.db, sb.side, sb.info);
+    else sp_kernels(d.G)->sensitivity(d, h->stream, nrhs, dv, sb.dg, sb.db, sb.side, sb.info);
     HIPCHK(g_sp_err, hipGetLastError());
     HIPCHK(g_sp_err, hipEventRecord(sb.ev1, h->stream));
+    if (dev) {
+        if (int rc = sb.download_device(g_sp_err, dg, db, side, info, d.n, d.m)) return rc;
+        h->sensPending = 1;
+        return 0;
+    }
     if (int rc = sb.download(g_sp_err, dg, db, side, info, d.n, d.m)) return rc;
     HIPCHK(g_sp_err, hipEventElapsedTime(ms, sb.ev0, sb.ev1));
     return 0;
@@ -515,11 +511,7 @@ static int sp_adjoint(lcqp_hip_sparse* h, const double* vx, const double* vy, do
     const size_t nq = dQx ? (size_t)d.nnzQ : 0, ne = dAx ? (size_t)d.nnzE : 0, perInst = nq + ne;
     if (perInst) {
         for (hipError_t e : {h->adjEv0.status, h->adjEv1.status}) if (e != hipSuccess) return hip_fail(g_sp_err, "hipEventCreate", e);
-        if (dAx && !h->adjMap) {      // the one map of the pattern; a permutation of the positions of the caller's value array
-            for (int k : h->csr2csc) if (k < 0 || k >= d.nnzE) { g_sp_err = "adjoint: the value map of the pattern is out of range"; return LCQP_HIP_ERROR; }
-            if ((int)h->csr2csc.size() != d.nnzE) { g_sp_err = "adjoint: the value map of the pattern has the wrong length"; return LCQP_HIP_ERROR; }
-            if (!h->mem.alloc(g_sp_err, h->adjMap, h->csr2csc.size(), h->csr2csc.data())) return LCQP_HIP_ERROR;
-        }
+        if (dAx) if (int rc = sp_value_map(h)) return rc;
         const SensBuffers& sb = h->sens;
         size_t chunk = 1;
         if (!reduce) {
@@ -528,7 +520,7 @@ static int sp_adjoint(lcqp_hip_sparse* h, const double* vx, const double* vy, do
             if (chunk > (size_t)d.B) chunk = d.B;
         }
         if (int rc = sp_grow(h, h->adjOut, h->adjOutCap, chunk * perInst + 2)) return rc;      // (+ 2: both segments start on an even offset)
-        SpAdjointArgs a = {d.B, d.n, d.m, d.nnzQ, d.nnzE, d.xout, d.yout, sb.dg, sb.db, sb.side, sb.info, d.Qp, d.Qi, d.Erow, d.Ei, h->adjMap, nullptr, nullptr};
+        SpAdjointArgs a = {d.B, d.n, d.m, d.nnzQ, d.nnzE, d.xout, d.yout, sb.dg, sb.db, sb.side, sb.info, d.Qp, d.Qi, d.Erow, d.Ei, h->valMap, nullptr, nullptr};
         for (size_t c0 = 0; c0 < (reduce ? (size_t)1 : (size_t)d.B); c0 += chunk) {
             const size_t cb = reduce ? 1 : std::min(chunk, (size_t)d.B - c0);
             const size_t cq = cb * nq, ce = cb * ne;
@@ -565,6 +557,66 @@ extern "C" int lcqp_hip_sparse_set_adjoint_staging(lcqp_hip_sparse_t* h, size_t 
 { return guarded(g_sp_err, [&] {
     if (!h) return LCQP_INVALID_ARGUMENT;
     h->adjStaging = bytes ? bytes : (size_t)LCQP_JACOBIAN_STAGING_BYTES;
+    return 0;
+}); }
+
+// ---- the device-pointer twins of lcqp_hip_sparse_sensitivity / _adjoint (include/lcqp_hip.h, DESIGN.md section 3a'''''; load, update and
+// get_solution are in lcqp_sparse_device.hip) ----
+// the pointer checks of the two calls: every array with the bytes the call moves
+static bool sp_sens_pointers_ok(lcqp_hip_sparse* h, size_t rows, const double* v, const char* vname, const double* vy, double* dg, double* db, int* side, int* info)
+{
+    const SpBatch& d = h->db;
+    return device_pointer_ok(g_sp_err, h, vname, v, sizeof(double) * rows * d.n) && device_pointer_ok(g_sp_err, h, "vy", vy, sizeof(double) * rows * d.m) &&
+           device_pointer_ok(g_sp_err, h, "dg", dg, sizeof(double) * rows * d.n) && device_pointer_ok(g_sp_err, h, "db", db, sizeof(double) * rows * d.m) &&
+           device_pointer_ok(g_sp_err, h, "side", side, sizeof(int) * (size_t)d.B * d.m, 4) && device_pointer_ok(g_sp_err, h, "info", info, sizeof(int) * (size_t)d.B, 4);
+}
+
+extern "C" int lcqp_hip_sparse_sensitivity_device(lcqp_hip_sparse_t* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info, void* stream)
+{ return guarded(g_sp_err, [&] {
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    HIPCHK(g_sp_err, hipSetDevice(h->device));
+    if (!sp_sens_pointers_ok(h, (size_t)h->db.B * nrhs, v, "v", nullptr, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
+    StreamHandOver over(h, stream);
+    HIPCHK(g_sp_err, over.status);
+    float ms = 0.f;
+    const int rc = sp_sensitivity_launch(h, nrhs, v, nullptr, dg, db, side, info, &ms, true);
+    HIPCHK(g_sp_err, over.done());
+    return rc;
+}); }
+
+// k_sparse_sensitivity as sp_adjoint launches it, then ONE launch of k_sparse_adjoint_nnz over the whole batch (or k_sparse_adjoint_reduce) that
+// writes the caller's arrays: no staging buffer, no chunks.  The terms are those of sp_adjoint_q / sp_adjoint_e: the host call's bits.
+extern "C" int lcqp_hip_sparse_adjoint_device(lcqp_hip_sparse_t* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
+                                              int reduce, double* dQx, double* dAx, void* stream)
+{ return guarded(g_sp_err, [&] {
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!vx || !dg || (reduce != 0 && reduce != 1)) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    HIPCHK(g_sp_err, hipSetDevice(h->device));
+    SpBatch& d = h->db;
+    if (!sp_sens_pointers_ok(h, d.B, vx, "vx", vy, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
+    const size_t lead = reduce ? (size_t)1 : (size_t)d.B, cq = dQx ? lead * d.nnzQ : 0, ce = dAx ? lead * d.nnzE : 0;
+    if (!device_pointer_ok(g_sp_err, h, "dQx", dQx, sizeof(double) * cq, 16) || !device_pointer_ok(g_sp_err, h, "dAx", dAx, sizeof(double) * ce)) return LCQP_INVALID_ARGUMENT;
+    if (dAx) if (int rc = sp_value_map(h)) return rc;
+    if (cq + ce) for (hipError_t e : {h->adjEv0.status, h->adjEv1.status}) if (e != hipSuccess) return hip_fail(g_sp_err, "hipEventCreate", e);
+    StreamHandOver over(h, stream);
+    HIPCHK(g_sp_err, over.status);
+    float ms = 0.f;
+    if (int rc = sp_sensitivity_launch(h, 1, vx, vy, dg, db, side, info, &ms, true)) { (void)over.done(); return rc; }
+    if (cq + ce) {
+        const SensBuffers& sb = h->sens;
+        const SpAdjointArgs a = {d.B, d.n, d.m, d.nnzQ, d.nnzE, d.xout, d.yout, sb.dg, sb.db, sb.side, sb.info, d.Qp, d.Qi, d.Erow, d.Ei, h->valMap, dQx, dAx};
+        const unsigned gx = (unsigned)std::min<size_t>((std::max((cq + 1) / 2, ce) + SP_ADJ_WG - 1) / SP_ADJ_WG, 65535);
+        HIPCHK(g_sp_err, hipEventRecord(h->adjEv0, h->stream));
+        if (reduce) hipLaunchKernelGGL(k_sparse_adjoint_reduce, dim3(gx, 2), dim3(SP_ADJ_WG), 0, h->stream, a);
+        else hipLaunchKernelGGL(k_sparse_adjoint_nnz, dim3(gx, 2), dim3(SP_ADJ_WG), 0, h->stream, a, 0, d.B);
+        HIPCHK(g_sp_err, hipGetLastError());
+        HIPCHK(g_sp_err, hipEventRecord(h->adjEv1, h->stream));
+        h->sensPending |= 4;
+    }
+    HIPCHK(g_sp_err, over.done());
     return 0;
 }); }
 
@@ -606,10 +658,23 @@ extern "C" int lcqp_hip_sparse_kkt_probe(lcqp_hip_sparse_t* h, int mode, int whi
     return 0;
 }); }
 
+// (after a device-pointer call the time is still in the events: wait for them and form it)
 extern "C" int lcqp_hip_sparse_sensitivity_timing(lcqp_hip_sparse_t* h, float* kernel_ms)
-{
+{ return guarded(g_sp_err, [&] {
+    if (h && h->sensPending) {
+        HIPCHK(g_sp_err, hipSetDevice(h->device));
+        float t = 0.f, ta = 0.f;
+        HIPCHK(g_sp_err, hipEventSynchronize(h->sens.ev1));
+        HIPCHK(g_sp_err, hipEventElapsedTime(&t, h->sens.ev0, h->sens.ev1));
+        if (h->sensPending & 4) {
+            HIPCHK(g_sp_err, hipEventSynchronize(h->adjEv1));
+            HIPCHK(g_sp_err, hipEventElapsedTime(&ta, h->adjEv0, h->adjEv1));
+        }
+        h->rs.sensMs = t + ta;
+        h->sensPending = 0;
+    }
     return sensitivity_timing(h, kernel_ms);
-}
+}); }
 
 extern "C" int lcqp_hip_sparse_synchronize(lcqp_hip_sparse_t* h)
 {

@@ -1,9 +1,9 @@
 #!/bin/bash
-# prints VGPR / scratch / occupancy per kernel of one padded size and of the sparse arm, one unit per lane-group width (hipcc -Rpass-analysis=kernel-resource-usage); writes nothing into the tree
+# prints VGPR / scratch / occupancy per kernel of one padded size, of the sparse arm, one unit per lane-group width, and of the sparse arm's device-pointer unit (hipcc -Rpass-analysis=kernel-resource-usage); writes nothing into the tree
 # usage: lcqpow_amd/csrc/resusage.sh [NCH=2] [-DFLAGS...]
 cd "$(dirname "$0")"
 NCH=${1:-2}; shift
-for f in "lcqp_nch.hip -DLCQP_TU_NCH=$NCH" "lcqp_sparse.hip -DLCQP_TU_G="{8,16,32,64}; do
+for f in "lcqp_nch.hip -DLCQP_TU_NCH=$NCH" "lcqp_sparse.hip -DLCQP_TU_G="{8,16,32,64} "lcqp_sparse_device.hip"; do
 hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -mllvm -disable-machine-licm -c -o /tmp/resusage_$$.o $f -Rpass-analysis=kernel-resource-usage "$@" 2>&1 | python3 -c "
 import sys,re,subprocess
 cur=None;rows={}

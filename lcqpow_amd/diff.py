@@ -2,11 +2,11 @@
 for a SparseBatchLCQP behind a SparseBatchLCQPLayer, lcqp_hip_sparse_sensitivity (section 3a'').
 
 The solve and its derivative run on the HIP path of :mod:`lcqpow_amd.capi`; there is no CPU fallback -- without the built library, or
-without a device, using the layer raises.  The dense layer has two paths, chosen per call by where g lives (layer.last_path):
+without a device, using the layer raises.  Both layers have two paths, chosen per call by where g lives (layer.last_path):
 "device" when g is a tensor on the batch's GPU -- the device-pointer entry points (DESIGN.md section 3a'''''): tensors are packed into the
 pools by kernels, x, y and every gradient are produced on the device, and nothing goes through the host but a status word and the count
 of flagged instances -- and "host" otherwise: tensors are copied to the host and back around the host-pointer C ABI, exactly as a CPU
-tensor always was.  The sparse layer has the host path only.
+tensor always was.  Both paths return the same bits.
 
     bt = BatchLCQP(B, nV, nC, nComp, opt=...); bt.load(0, B, Q, g0, L, R, A=A, lbA=lbA, ubA=ubA)
     layer = BatchLCQPLayer(bt, bounds=dict(lbA=lbA, ubA=ubA))
@@ -52,10 +52,11 @@ def _warn_flagged(who, info, B):
                       f"(info bits present: {bits}); their gradients are the kernel's output as it is", RuntimeWarning, stacklevel=3)
 
 
-def _bound_grads_device(bt, db, side, given, like):
+def _bound_grads_device(bt, db, side, given, like, sparse=False):
     """the gradients of lbA / ubA on the device path: split_bound_derivatives and the equality rule of LCQPSolveFunction, on tensors"""
-    parts = capi.split_bound_derivatives_torch(db, side, bt.nV, bt.nC, bt.nComp)
-    eq = side[:, bt.nV:bt.nV + bt.nC] == 2
+    parts = capi.split_bound_derivatives_torch(db, side, bt.nV, bt.nC, bt.nComp, sparse=sparse)
+    a0 = 0 if sparse else bt.nV      # first row of A in the layout of side
+    eq = side[:, a0:a0 + bt.nC] == 2
     one = db.new_ones(())
     share = torch.where(eq, 0.5 * one, one) if all(given) else one
     glb = (parts["dlbA"] * share).to(like) if given[0] else None
@@ -124,7 +125,7 @@ class LCQPSolveFunction(torch.autograd.Function):
             dg, db, side, info = bt.sensitivity_device(_dev(grad_x, grad_x.device))
             layer.info = info
             _warn_flagged("LCQPSolveFunction", info, bt.B)
-            glb, gub = _bound_grads_device(bt, db, side, ctx.given, grad_x.dtype)
+            glb, gub = _bound_grads_device(bt, db, side, ctx.given, grad_x.dtype, sparse=layer.sparse)
             return None, dg.to(grad_x.dtype), glb, gub
         dg, db, side, info = bt.sensitivity(_host(grad_x))
         layer.info = info
@@ -277,14 +278,13 @@ class LCQPSparseFullSolveFunction(torch.autograd.Function):
     resolve(warm).  With one: lcqp_hip_sparse_load of the whole batch + run; a tensor [B][nnz] holds one value array per instance, one of
     shape [nnz] is shared by the batch (broadcast at the load); an array that is not given is the one the layer holds (its `values`).
     backward: lcqp_hip_sparse_adjoint with the upstream gradients on x and on y -- one call for the per-instance tensors (reduce = 0), one
-    for the shared ones (reduce = 1, the sum over the batch formed on the device).  Flagged instances: the one warning of LCQPSolveFunction."""
+    for the shared ones (reduce = 1, the sum over the batch formed on the device).  Flagged instances: the one warning of LCQPSolveFunction.
+    With g on the GPU of the batch the calls are the device-pointer twins (lcqp_hip_sparse_load_device and so on): an array that is not given
+    is not handed over, the batch keeps it; a shared one is broadcast by the pack kernel."""
 
     @staticmethod
     def forward(ctx, layer, g, Qx=None, Ax=None, lbA=None, ubA=None):
         bt = layer.bt
-        kw = dict(layer.bounds)
-        if lbA is not None: kw["lbA"] = _host(lbA)
-        if ubA is not None: kw["ubA"] = _host(ubA)
         given = dict(zip(SPARSE_VALUE_KEYS, (Qx, Ax)))
         nnz = dict(Qx=bt.nnzQ, Ax=bt.nnzA)
         shared = {}
@@ -294,8 +294,39 @@ class LCQPSparseFullSolveFunction(torch.autograd.Function):
             if tuple(t.shape) not in ((bt.B, nnz[k]), (nnz[k],)):
                 raise ValueError(f"{k}: expected [{bt.B}][{nnz[k]}] or [{nnz[k]}], got {tuple(t.shape)}")
             shared[k] = t.dim() == 1
+        ctx.device_path = layer._on_device(g)
+        layer.last_path = "device" if ctx.device_path else "host"
+        if ctx.device_path:
+            kw = dict(layer._device_bounds(g.device))
+            if lbA is not None: kw["lbA"] = _dev(lbA, g.device)
+            if ubA is not None: kw["ubA"] = _dev(ubA, g.device)
+            if shared:
+                rc = bt.load_device(0, bt.B, _dev(Qx, g.device), _dev(g, g.device), _dev(Ax, g.device), **kw)
+                if rc != 0:
+                    raise RuntimeError(f"load failed with code {rc}: {bt._last_error()}")
+                layer._values_stale = True      # (the host path reads the value arrays back when it next needs them)
+                bt.run()
+            else:
+                rc = bt.update_device(0, bt.B, _dev(g, g.device), **kw)
+                if rc != 0:
+                    raise RuntimeError(f"update failed with code {rc}: {bt._last_error()}")
+                if layer.solves == 0:
+                    bt.run()
+                else:
+                    bt.resolve(warm=layer.warm)
+            x, y = bt.solution_device()
+            layer.solves += 1
+            layer.y, layer.stats = y, None
+            layer._like = (g.dtype, g.device)
+            ctx.layer, ctx.serial = layer, layer.solves
+            ctx.given = (lbA is not None, ubA is not None)
+            ctx.shared = shared
+            return x.to(g.dtype), y.to(g.dtype)
+        kw = dict(layer.bounds)
+        if lbA is not None: kw["lbA"] = _host(lbA)
+        if ubA is not None: kw["ubA"] = _host(ubA)
         if shared:
-            held = layer.values
+            held = layer._values()
             for k, t in given.items():
                 if t is not None:
                     held[k] = np.ascontiguousarray(np.broadcast_to(_host(t), (bt.B, nnz[k])))
@@ -327,10 +358,22 @@ class LCQPSparseFullSolveFunction(torch.autograd.Function):
         if ctx.serial != layer.solves:
             raise RuntimeError("backward through a solve that is not the layer's last one: the batch object holds the state of one solve")
         bt = layer.bt
-        vx, vy = _host(grad_x), _host(grad_y)
         name = dict(Qx="Q", Ax="A")      # the names of SparseBatchLCQP.adjoint
         each = tuple(name[k] for k, sh in ctx.shared.items() if not sh)
         summed = tuple(name[k] for k, sh in ctx.shared.items() if sh)
+        if ctx.device_path:
+            vx, vy = _dev(grad_x, grad_x.device), _dev(grad_y, grad_x.device)
+            r = bt.adjoint_device(vx, vy, matrices=each, reduce=False)
+            mats = {k: r[k] for k in each}
+            if summed:
+                rs = bt.adjoint_device(vx, vy, matrices=summed, reduce=True)
+                mats.update({k: rs[k] for k in summed})
+            layer.info = r["info"]
+            _warn_flagged("LCQPSparseFullSolveFunction", r["info"], bt.B)
+            glb, gub = _bound_grads_device(bt, r["db"], r["side"], ctx.given, grad_x.dtype, sparse=True)
+            gm = [mats[name[k]].to(grad_x.dtype) if name[k] in mats else None for k in SPARSE_VALUE_KEYS]
+            return (None, r["dg"].to(grad_x.dtype), *gm, glb, gub)
+        vx, vy = _host(grad_x), _host(grad_y)
         r = bt.adjoint(vx, vy, matrices=each, reduce=False)
         mats = {k: r[k] for k in each}
         if summed:
@@ -389,8 +432,8 @@ class BatchLCQPLayer:
         self._stats = st
 
     def _on_device(self, g):
-        """the device path: the dense arm, and g a tensor on the GPU of the batch"""
-        return (not self.sparse) and g.is_cuda and g.device.index == getattr(self.bt, "device", None)
+        """the device path: g a tensor on the GPU of the batch"""
+        return g.is_cuda and g.device.index == getattr(self.bt, "device", None)
 
     def _device_bounds(self, device):
         """the layer's bound vectors as float64 tensors on the device, uploaded once"""
@@ -426,17 +469,20 @@ class BatchLCQPLayer:
 
 
 class SparseBatchLCQPLayer(BatchLCQPLayer):
-    """A loaded SparseBatchLCQP as a torch layer: the same function over lcqp_hip_sparse_update / _run / _resolve / _sensitivity.  bounds:
+    """A loaded SparseBatchLCQP as a torch layer: the same function over lcqp_hip_sparse_update / _run / _resolve / _sensitivity (with g on the
+    GPU of the batch: over their device-pointer twins; layer.last_path says which path ran).  bounds:
     the vectors of SparseBatchLCQP.update the batch was loaded with (lbA, ubA, lbL, ubL, lbR, ubR; the sparse arm has no box)."""
     sparse = True
     bound_keys = tuple(k for k in BOUND_KEYS if k not in ("lb", "ub"))
 
     def __init__(self, batch, bounds=None, warm=True, values=None):
-        """values: dict(Qx=[B][nnzQ], Ax=[B][nnzA]) (or [nnz], shared) -- the value arrays the batch was loaded with.  The sparse handle cannot
-        read its matrices back, so a layer whose solve() takes Qx or Ax needs them, the way it needs `bounds`: a load replaces BOTH arrays, and
-        the one that is not an input of the solve is handed over again.  The layer keeps them in step with its own loads."""
+        """values: dict(Qx=[B][nnzQ], Ax=[B][nnzA]) (or [nnz], shared) -- the value arrays the batch was loaded with.  A layer whose solve()
+        takes Qx or Ax needs them, the way it needs `bounds`: a host load replaces BOTH arrays, and the one that is not an input of the solve
+        is handed over again.  The layer keeps them in step with its own loads (after a load on the device path: read back through
+        SparseBatchLCQP.read_problem when the host path next needs them)."""
         super().__init__(batch, bounds=bounds, warm=warm)
         self.values = None
+        self._values_stale = False
         if values is not None:
             if set(values) != set(SPARSE_VALUE_KEYS):
                 raise ValueError(f"values: expected the keys {list(SPARSE_VALUE_KEYS)}, got {sorted(values)}")
@@ -447,6 +493,14 @@ class SparseBatchLCQPLayer(BatchLCQPLayer):
                 if v.shape not in ((batch.B, nnz[k]), (nnz[k],)):
                     raise ValueError(f"values[{k!r}]: expected [{batch.B}][{nnz[k]}] or [{nnz[k]}], got {v.shape}")
                 self.values[k] = np.ascontiguousarray(np.broadcast_to(v, (batch.B, nnz[k])))
+
+    def _values(self):
+        """the value arrays the batch holds, [B][nnz] each, for a load on the host path"""
+        if self._values_stale:
+            ps = [self.bt.read_problem(b) for b in range(self.bt.B)]
+            self.values = {k: np.stack([p[k] for p in ps]) for k in SPARSE_VALUE_KEYS}
+            self._values_stale = False
+        return self.values
 
     def solve(self, g, Qx=None, Ax=None, lbA=None, ubA=None):
         """(x, y) of the batch for the linear terms g, both differentiable (LCQPSparseFullSolveFunction): y [B][nC + 2 nComp], rows A, L, R.

@@ -8,7 +8,12 @@ handle in one process, at the BASELINE shape (B = 1024, nV = 256, nC = 512, nCom
 Every figure is the wall clock of the calls including what makes their results usable: the host calls return finished results, the device
 calls are followed by a synchronisation of the torch stream.  min / median / max over --reps calls after --warmup calls.
 
-usage: python tools/device_io_timing.py [--quick] [--log FILE] [--reps 10] [--warmup 2]"""
+--sparse: the same three rows for the sparse arm (lcqp_hip_sparse_*), with per-instance value arrays, on the banded synthetic workload of
+lcqpow_amd/synth_sparse.py at two shapes -- n = 4096, nC = 2048, nComp = 512 with B = 4096 and n = 512, nC = 256, nComp = 64 with B = 1024
+(--quick: B = 64 each) --, followed by the kernel times of the three pack kernels (HIP events on the torch stream around load_device and
+update_device; the check kernel and its status read are inside) and the bytes per second of k_sparse_pack_values.
+
+usage: python tools/device_io_timing.py [--sparse] [--quick] [--log FILE] [--reps 10] [--warmup 2]"""
 import argparse
 import os
 import sys
@@ -33,9 +38,87 @@ def timed(call, reps, warmup):
     return t.min(), float(np.median(t)), t.max()
 
 
+HBM_PEAK = 8.0e12      # bytes per second of one MI355X
+
+
+def sparse_rows(say, args, shape, B):
+    from lcqpow_amd import synth_sparse as S
+    n, nC, nK = shape
+    m = nC + 2 * nK
+    Qpat, Apat, qo, eo = S.sparse_pattern_arrays(n, nC, nK)
+    sb = la.SparseBatchLCQP(B, n, nC, nK, Qpat, Apat, opt=la.default_options(perturbStep=0, printLevel=0))
+    inst = [S.sparse_values(i, n, nC, nK, orders=(qo, eo)) for i in range(B)]
+    h = {k: np.stack([d[k] for d in inst]) for k in ("Qx", "g", "Ex", "lbA", "ubA")}
+    del inst
+    dev = lambda a: torch.as_tensor(a, dtype=torch.float64, device="cuda:0")
+    d = {k: dev(v) for k, v in h.items()}
+    say(f"sparse, banded workload: B = {B}, nV = {n}, nC = {nC}, nComp = {nK}, nnzQ = {sb.nnzQ}, nnzA = {sb.nnzA}, lanes = {sb.lanes()}; "
+        f"{args.reps} calls after {args.warmup}; wall clock, ms: min / median / max")
+
+    def row(name, host, device):
+        th, td = timed(host, args.reps, args.warmup), timed(device, args.reps, args.warmup)
+        verdict = "" if td[1] < th[1] else "    DEVICE MEDIAN NOT BELOW HOST"
+        say(f"  {name:<44s} host {th[0]:9.2f} / {th[1]:9.2f} / {th[2]:9.2f}    device {td[0]:9.2f} / {td[1]:9.2f} / {td[2]:9.2f}    median ratio {th[1] / td[1]:7.1f}{verdict}")
+
+    def load_host():
+        assert sb.load(0, B, h["Qx"], h["g"], h["Ex"], lbA=h["lbA"], ubA=h["ubA"]) == 0
+
+    def load_device():
+        assert sb.load_device(0, B, d["Qx"], d["g"], d["Ex"], lbA=d["lbA"], ubA=d["ubA"]) == 0
+
+    row("load", load_host, load_device)
+    sb.run()
+    sb.synchronize()
+    say("  (run on the loaded data: setup %.2f ms + homotopy %.2f ms of kernel time)" % sb.last_timing())
+
+    def resolve_host():
+        assert sb.update(0, B, h["g"], lbA=h["lbA"], ubA=h["ubA"]) == 0
+        sb.resolve(warm=True)
+        sb.solution()
+
+    def resolve_device():
+        assert sb.update_device(0, B, d["g"], lbA=d["lbA"], ubA=d["ubA"]) == 0
+        sb.resolve(warm=True)
+        sb.solution_device()
+
+    row("update + resolve(warm) + solution", resolve_host, resolve_device)
+    sb.synchronize()
+    say("  (the warm re-solve alone: setup %.2f ms + homotopy %.2f ms of kernel time)" % sb.last_timing())
+
+    rng = np.random.default_rng(0)
+    vx, vy = rng.standard_normal((B, n)), rng.standard_normal((B, m))
+    dvx, dvy = dev(vx), dev(vy)
+    out = dict(Q=torch.empty((B, sb.nnzQ), dtype=torch.float64, device="cuda:0"), A=torch.empty((B, sb.nnzA), dtype=torch.float64, device="cuda:0"))
+    row("adjoint, per-instance dQx and dAx", lambda: sb.adjoint(vx, vy), lambda: sb.adjoint_device(dvx, dvy, out=out))
+    say("  (kernel time of the last adjoint_device: %.3f ms)" % sb.sensitivity_kernel_ms())
+
+    # the pack kernels by HIP events on the torch stream: the whole call (check kernel, its status read, the pack kernels), and from the
+    # difference of a load with and without value arrays the time of k_sparse_pack_values
+    def events(call):
+        ts = []
+        for _ in range(args.warmup + args.reps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            e0.record(); call(); e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+        return float(np.median(ts[args.warmup:]))
+    t_load = events(load_device)
+    t_vec = events(lambda: sb.load_device(0, B, None, d["g"], None, lbA=d["lbA"], ubA=d["ubA"]))
+    t_upd = events(lambda: sb.update_device(0, B, d["g"], lbA=d["lbA"], ubA=d["ubA"]))
+    moved = 8.0 * B * (2 * sb.nnzQ + 2 * sb.nnzA) + 4.0 * sb.nnzA      # values read and written once, the map (it stays in cache)
+    t_val = max(t_load - t_vec, 1e-6)
+    say(f"  event time on the stream, median, ms: load_device {t_load:.3f} (k_sparse_check_vectors with the diagonal pairs + status read + k_sparse_pack_values + "
+        f"k_sparse_pack_vectors), load_device without value arrays {t_vec:.3f} (check + status read + k_sparse_pack_vectors), update_device {t_upd:.3f}")
+    say(f"  k_sparse_pack_values (the difference; it includes the diagonal pairs of the check kernel): {t_val:.3f} ms for {moved / 1e9:.3f} GB = "
+        f"{moved / (t_val * 1e-3) / 1e9:.0f} GB/s = {100.0 * moved / (t_val * 1e-3) / HBM_PEAK:.1f} % of the HBM peak of {HBM_PEAK / 1e12:.1f} TB/s")
+    sb.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--sparse", action="store_true")
     ap.add_argument("--log")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -47,6 +130,19 @@ def main():
     def say(s):
         print(s, flush=True)
         lines.append(s)
+
+    def write_log():
+        if args.log:
+            os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
+            with open(args.log, "w") as f:
+                f.write("\n".join(lines) + "\n")
+
+    if args.sparse:
+        say("device_io_timing --sparse: host entry points of the sparse batch against their device-pointer twins, one handle per shape, one process")
+        for shape, Bs in (((4096, 2048, 512), 4096), ((512, 256, 64), 1024)):
+            sparse_rows(say, args, shape, 64 if args.quick else Bs)
+            write_log()
+        return
 
     bt = la.BatchLCQP(B, n, nC, nK, opt=la.default_options(perturbStep=0, printLevel=0))
     bt.generate_synthetic(0)
@@ -99,10 +195,7 @@ def main():
     row("adjoint, per-instance Q", lambda: bt.adjoint(vx, vy, matrices=("Q",)), lambda: bt.adjoint_device(dvx, dvy, matrices=("Q",), out=out))
     say("  (kernel time of the last adjoint_device: %.3f ms)" % bt.sensitivity_kernel_ms())
     bt.close()
-    if args.log:
-        os.makedirs(os.path.dirname(os.path.abspath(args.log)), exist_ok=True)
-        with open(args.log, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    write_log()
 
 
 if __name__ == "__main__":
