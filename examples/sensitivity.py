@@ -6,6 +6,7 @@ printed.  The targets are solutions of the same LCQPs for other linear terms, so
     python examples/sensitivity.py
     python examples/sensitivity.py sparse      # the same fit on the sparse arm: 16 banded LCQPs (n = 64), lcqp_hip_sparse_sensitivity
     python examples/sensitivity.py jacobian    # the full Jacobians dx/dg of the 64 LCQPs (lcqp_hip_batch_jacobian): |Jg - Jg'| and the kernel time
+    python examples/sensitivity.py sparse jacobian   # the full Jacobians of the 16 banded LCQPs (lcqp_hip_sparse_jacobian), panel kernel
     python examples/sensitivity.py adjoint     # learn ONE constraint matrix A shared by the 64 LCQPs from a loss on x and y (lcqp_hip_batch_adjoint)
     python examples/sensitivity.py sparse adjoint   # learn ONE value array of [A; L; R] shared by 16 banded LCQPs (lcqp_hip_sparse_adjoint)
 """
@@ -44,7 +45,7 @@ def fit(layer, g0, rng, batch):
         print("step %2d  mean loss per LCQP %.6e  flagged instances %d" % (step, loss.item() / batch, int(np.count_nonzero(layer.info))))
 
 
-def sparse_main():
+def sparse_main(jacobian=False):
     from lcqpow_amd import synth_sparse as S
     Bs, ns, nCs, nKs = 16, 64, 32, 8
     Qpat, Apat, qo, eo = S.sparse_pattern_arrays(ns, nCs, nKs)
@@ -52,7 +53,15 @@ def sparse_main():
     st = lambda k: np.stack([d[k] for d in inst])
     sb = la.SparseBatchLCQP(Bs, ns, nCs, nKs, Qpat, Apat, opt=la.default_options(perturbStep=0))
     assert sb.load(0, Bs, st("Qx"), st("g"), st("Ex"), lbA=st("lbA"), ubA=st("ubA")) == 0
-    fit(SparseBatchLCQPLayer(sb, bounds=dict(lbA=st("lbA"), ubA=st("ubA"))), st("g"), np.random.default_rng(0), Bs)
+    layer = SparseBatchLCQPLayer(sb, bounds=dict(lbA=st("lbA"), ubA=st("ubA")))
+    if jacobian:
+        with torch.no_grad():
+            layer(torch.as_tensor(st("g")))
+        Jg = layer.jacobian()
+        print("Jg %s (panels of %d columns): max |Jg - Jg'| = %.3e, kernel %.4f ms, flagged instances %d"
+              % (tuple(Jg.shape), sb.sens_panel(), (Jg - Jg.transpose(1, 2)).abs().max().item(), sb.sensitivity_kernel_ms(), int(np.count_nonzero(layer.info))))
+    else:
+        fit(layer, st("g"), np.random.default_rng(0), Bs)
     sb.close()
 
 
@@ -117,6 +126,8 @@ def main():
         raise SystemExit("needs a GPU (the product path has no CPU fallback)")
     if sys.argv[1:] == ["sparse"]:
         return sparse_main()
+    if sys.argv[1:] == ["sparse", "jacobian"]:
+        return sparse_main(jacobian=True)
     if sys.argv[1:] == ["sparse", "adjoint"]:
         return sparse_adjoint_main()
     if sys.argv[1:] == ["adjoint"]:

@@ -446,8 +446,39 @@ int  lcqp_hip_sparse_launch_counts(lcqp_hip_sparse_t* s, int out[2]);   /* full 
  * LCQP_INVALID_ARGUMENT: NULL handle, v or dg, or nrhs < 1.  LCQP_LCQPOBJECT_NOT_SETUP: no run / resolve on this handle yet, or a load /
  * set_options since the last one (the mark of lcqp_hip_sparse_resolve).  LCQP_HIP_ERROR: a HIP call failed. */
 int  lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* s, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
-/* kernel time of the last lcqp_hip_sparse_sensitivity launch of this handle, ms (HIP events around k_sparse_sensitivity, the copies excluded) */
+/* kernel time of the last lcqp_hip_sparse_sensitivity / _sensitivity_blocked / _jacobian call of this handle, ms (HIP events around
+ * k_sparse_sensitivity or k_sparse_sensitivity_blk, the copies excluded; a call that went in chunks: the sum over its launches) */
 int  lcqp_hip_sparse_sensitivity_timing(lcqp_hip_sparse_t* s, float* kernel_ms);
+/* lcqp_hip_sparse_sensitivity for many vectors (DESIGN.md section 3a''', "The sparse arm"): the same arguments, layouts, flags and return
+ * codes, checked in the same order before any device call.  The vectors of an instance go through k_sparse_sensitivity_blk in panels of
+ * lcqp_hip_sparse_sens_panel(s) columns (LCQP_SPARSE_SENS_PANEL by default; the last panel padded with zero columns): one lane group per
+ * (instance, panel) pair, the band factor streamed once per panel instead of once per vector, the panel's columns as independent chains
+ * of one sweep.  Per column the arithmetic is the sequence of k_sparse_sensitivity, so the results equal lcqp_hip_sparse_sensitivity's to
+ * rounding (the bound of DESIGN.md section 2), NOT to the bit (the two kernels are compiled apart and contract differently; measured: the
+ * last bits differ); within this entry point a vector's result does not depend on the other vectors of the call or on its place among
+ * them, bit for bit.  side and info are those of lcqp_hip_sparse_sensitivity.  The staging
+ * on the device is bounded as for lcqp_hip_sparse_jacobian.
+ * The general sparse LDL' (lcqp_hip_sparse_fronts(s) > 0) has no panel kernel: there lcqp_hip_sparse_sens_panel returns 0, and this entry
+ * point launches k_sparse_sensitivity and returns the bits of lcqp_hip_sparse_sensitivity. */
+#define LCQP_SPARSE_SENS_PANEL 8
+/* the panel width this handle's engine uses; 0 where the two entry points fall back to the vector kernel (NULL handle: 0) */
+int  lcqp_hip_sparse_sens_panel(const lcqp_hip_sparse_t* s);
+int  lcqp_hip_sparse_sensitivity_blocked(lcqp_hip_sparse_t* s, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
+/* The full solution Jacobians of the instances [first, first + count): the panel kernel on the unit vectors, which it writes into its solve
+ * panels on the device (nothing is uploaded).
+ *   Jg[i][k][j]  [count][nV][nV]   d x*_k / d g_j of instance first + i
+ *   Jb[i][k][r]  [count][nV][m]    d x*_k / d (the bound row r sits on), m = nC + 2 nComp, rows A, L, R; zero outside W; may be NULL
+ *   side [count][m], info [count]  as lcqp_hip_sparse_sensitivity; may be NULL
+ * Row k of Jg[i] and of Jb[i] is what lcqp_hip_sparse_sensitivity_blocked returns for v = e_k, to the bit.
+ * The staging on the device (outputs and workspaces of the work items in flight) is bounded by the cap of
+ * lcqp_hip_sparse_set_adjoint_staging, which governs the adjoint's chunks and these: the call loops over chunks of whole (instance, panel)
+ * items, at least one per chunk -- a chunk may split an instance by columns --, one launch and one download per chunk; the results do not
+ * depend on the chunking, bit for bit.  General sparse LDL': k_sparse_sensitivity on uploaded unit vectors, in chunks of columns under the
+ * same cap; a sub-range then costs the launches of the whole batch (the vector kernel has no instance offset).
+ * Both calls are synchronous on return, change nothing a run / resolve reads and leave lcqp_hip_sparse_launch_counts alone.
+ * LCQP_INVALID_ARGUMENT: NULL handle or Jg, first < 0, count < 1, first + count > B.  Then LCQP_LCQPOBJECT_NOT_SETUP as
+ * lcqp_hip_sparse_sensitivity.  Both are decided before any device call. */
+int  lcqp_hip_sparse_jacobian(lcqp_hip_sparse_t* s, int first, int count, double* Jg, double* Jb, int* side, int* info);
 /* The full adjoint of the sparse batch (DESIGN.md section 3a''''; the twin of lcqp_hip_batch_adjoint): lcqp_hip_sparse_sensitivity with
  * nrhs = 1, extended by upstream gradients on the returned duals and by the gradients on the stored entries of Q and of E = [A; L; R].  At the
  * returned point x, y_W solve  Q x + g - E_W' y_W = 0,  E_W x = b_W  (y as lcqp_hip_sparse_get_solution returns it, [m], m = nC + 2 nComp, rows
@@ -470,7 +501,8 @@ int  lcqp_hip_sparse_sensitivity_timing(lcqp_hip_sparse_t* s, float* kernel_ms);
  * are decided before any device call. */
 int  lcqp_hip_sparse_adjoint(lcqp_hip_sparse_t* s, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
                              int reduce, double* dQx, double* dAx);
-/* another staging cap for this handle's adjoint calls (0: the default, LCQP_JACOBIAN_STAGING_BYTES); for tests of the chunking and for small devices */
+/* another staging cap for this handle's adjoint, blocked-sensitivity and Jacobian calls (0: the default, LCQP_JACOBIAN_STAGING_BYTES); for
+ * tests of the chunking and for small devices */
 int  lcqp_hip_sparse_set_adjoint_staging(lcqp_hip_sparse_t* s, size_t bytes);
 /* ---- Device-pointer entry points of the sparse batch (DESIGN.md section 3a''''', "The sparse arm"): the twins of lcqp_hip_sparse_load / _update /
  * _get_solution / _sensitivity / _adjoint whose data pointers are DEVICE pointers, under the rules of the dense device calls above.  Layouts,

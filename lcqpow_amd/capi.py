@@ -178,6 +178,9 @@ def lib():
         L.lcqp_hip_sparse_launch_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.lcqp_hip_sparse_sensitivity.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_sparse_sensitivity_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
+        L.lcqp_hip_sparse_sens_panel.argtypes = [C.c_void_p]
+        L.lcqp_hip_sparse_sensitivity_blocked.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
+        L.lcqp_hip_sparse_jacobian.argtypes = [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_sparse_adjoint.argtypes = [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p, C.c_int] + [c_double_p] * 2
         L.lcqp_hip_sparse_set_adjoint_staging.argtypes = [C.c_void_p, C.c_size_t]
         L.lcqp_hip_sparse_load_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11 + [C.c_void_p]
@@ -1034,6 +1037,34 @@ class SparseBatchLCQP(_Batch):
         rp = np.zeros(B); rd = np.zeros((B, m)); ru = np.zeros((B, m), dtype=np.int32)
         self._call("kkt_probe", 1, int(which), rhs.shape[1], None, None, None, _p(rhs), _p(sol), _p(rp), _p(rd), _ip(ru))
         return sol, dict(dprim=rp, ddual=rd, use=ru)
+
+    def sens_panel(self):
+        """lcqp_hip_sparse_sens_panel: columns per panel of k_sparse_sensitivity_blk on this handle's engine; 0 where sensitivity_blocked()
+        and jacobian() run the vector kernel (the general sparse LDL')"""
+        return lib().lcqp_hip_sparse_sens_panel(self.h)
+
+    def sensitivity_blocked(self, v):
+        """lcqp_hip_sparse_sensitivity_blocked: sensitivity(v) -- the same arguments and results -- through the kernel that takes the k vectors
+        of an instance in panels of sens_panel() columns, one lane group per (instance, panel) pair, the band factor streamed once per
+        panel (DESIGN.md section 3a''', "The sparse arm"): per column the arithmetic of the vector kernel (the same results to rounding); a
+        column's result does not depend on the other columns of the call, bit for bit.  (A method of its own rather than a keyword of
+        sensitivity, whose signature (v) is part of this class's tested surface.)"""
+        return _sensitivity(lambda *a: self._sym("sensitivity_blocked")(self.h, *a), v, self.B, self.nV, self._ndual, check=self._check)
+
+    def jacobian(self, first=0, count=None, bounds=True, _staging_bytes=None):
+        """lcqp_hip_sparse_jacobian: the full solution Jacobians of the instances [first, first + count) (count None: to the end) at the x the
+        last run / resolve returned (synchronous; DESIGN.md section 3a''', "The sparse arm").  Returns (Jg, Jb, side, info): Jg
+        [count][nV][nV], Jg[i][k][j] = dx_k/dg_j; Jb [count][nV][m], Jb[i][k][r] = dx_k/d(the bound row r of [A; L; R] sits on), zero outside
+        the working set (None with bounds=False); side [count][m] and info [count] as sensitivity.  The unit vectors are generated on the
+        device, and the call goes in chunks of (instance, panel) work items under the staging cap of adjoint (_staging_bytes: another cap
+        for this one call, for tests).  The call changes nothing on the device."""
+        if _staging_bytes is not None:
+            self._call("set_adjoint_staging", int(_staging_bytes))
+        try:
+            return _jacobian(lambda *a: self._sym("jacobian")(self.h, *a), self.B, self.nV, self.m, first, count, bounds, check=self._check)
+        finally:
+            if _staging_bytes is not None:
+                self._call("set_adjoint_staging", 0)      # back to the default cap
 
     def adjoint(self, vx, vy=None, matrices=("Q", "A"), reduce=False, _staging_bytes=None):
         """lcqp_hip_sparse_adjoint: the gradients of a loss that reads the x AND the y the last run / resolve returned (synchronous; DESIGN.md

@@ -230,12 +230,14 @@ int launch_counts(H* h, int out[2])
     return 0;
 }
 
-// The device buffers of *_sensitivity (layouts at k_sensitivity / k_sensitivity_blk / k_sparse_sensitivity), grown on demand, and the
+// The device buffers of *_sensitivity (layouts at k_sensitivity / k_sensitivity_blk / k_sparse_sensitivity / k_sparse_sensitivity_blk), grown on demand, and the
 // events around the last launch.  A call is reserve, upload, record(ev0), the arm's launch, record(ev1), download.
 struct SensBuffers {
     double *v = nullptr, *dg = nullptr, *db = nullptr;
     int *side = nullptr, *info = nullptr;
     size_t capB = 0, capRows = 0;         // instances and rows the buffers have room for
+    double* ws = nullptr;                 // k_sparse_sensitivity_blk: the workspaces of the work items of one chunk (reserve_ws)
+    size_t capWs = 0;
     Event ev0, ev1;
     hipStream_t stream = nullptr;         // of the call in progress, with its sizes: rows = B * nrhs; leading dimensions in elements
     size_t B = 0, rows = 0, ldV = 0, ldDg = 0, ldDb = 0, nSide = 0;
@@ -244,8 +246,13 @@ struct SensBuffers {
     // chunk of the batch, with one right-hand side per variable)
     int reserve(std::string& err, DevMem& mem, hipStream_t s, size_t nB, size_t nrhs, size_t ldv, size_t lddg, size_t lddb, size_t nside)
     {
+        return reserve_rows(err, mem, s, nB, nB * nrhs, ldv, lddg, lddb, nside);
+    }
+    // the same with the rows given as such (the sparse panel kernel stages the rows of a chunk of work items, not of whole instances)
+    int reserve_rows(std::string& err, DevMem& mem, hipStream_t s, size_t nB, size_t nRows, size_t ldv, size_t lddg, size_t lddb, size_t nside)
+    {
         for (hipError_t e : {ev0.status, ev1.status}) if (e != hipSuccess) return hip_fail(err, "hipEventCreate", e);
-        stream = s; B = nB; rows = nB * nrhs; ldV = ldv; ldDg = lddg; ldDb = lddb; nSide = nside;
+        stream = s; B = nB; rows = nRows; ldV = ldv; ldDg = lddg; ldDb = lddb; nSide = nside;
         if (nB <= capB && rows <= capRows) return 0;
         HIPCHK(err, hipStreamSynchronize(s));
         for (const void* p : {(const void*)v, (const void*)dg, (const void*)db, (const void*)side, (const void*)info}) mem.release(p);
@@ -255,6 +262,16 @@ struct SensBuffers {
         if (!mem.alloc(err, v, nr * ldV) || !mem.alloc(err, dg, nr * ldDg) || !mem.alloc(err, db, nr * ldDb) ||
             !mem.alloc(err, side, nb * nSide) || !mem.alloc(err, info, nb)) return LCQP_HIP_ERROR;
         capB = nb; capRows = nr;
+        return 0;
+    }
+    int reserve_ws(std::string& err, DevMem& mem, hipStream_t s, size_t doubles)
+    {
+        if (doubles <= capWs) return 0;
+        HIPCHK(err, hipStreamSynchronize(s));
+        mem.release(ws);
+        ws = nullptr; capWs = 0;
+        if (!mem.alloc(err, ws, doubles)) return LCQP_HIP_ERROR;
+        capWs = doubles;
         return 0;
     }
     int upload(std::string& err, const double* hv)

@@ -27,7 +27,7 @@
 //   lcqp_sparse_lane.hpp     the lane-group model: addressing, SpCtx, collectives, g_map, g_ell       (dense: lcqp_wg.hpp)
 //   lcqp_sparse_factor.hpp   assembly, the three factorisation engines, sweeps, border, sp_solve
 //   lcqp_sparse_solver.hpp   products, ADMM, polish, the phases of the homotopy, the setup's pieces  (dense: lcqp_dev.hpp)
-//   lcqp_sparse.hip          this file: the setup / refresh / sensitivity / probe kernels, the queue scheduler, the launches and their table
+//   lcqp_sparse.hip          this file: the setup / refresh / sensitivity (vector and panel) / probe kernels, the queue scheduler, the launches and their table
 //                                                                                                    (dense: lcqp_kernels.hpp / lcqp_nch.hip)
 #include "lcqp_sparse_solver.hpp"
 
@@ -143,6 +143,33 @@ __global__ __launch_bounds__(WGS) void k_sparse_refresh(SpBatch db, int mode, co
     if (t == 0) c.info->bytes = c.bytes;
 }
 
+// the side codes of an instance's rows (0 outside W, -1 at lower, +1 at upper, 2 equality) into sd [m], and its flags 4 and 8 as the return
+// value (include/lcqp_hip.h) -- shared by k_sparse_sensitivity and k_sparse_sensitivity_blk, as sens_marks is on the dense side.
+// Flags, as on the dense path (k_sensitivity): a row of L or R at its lower bound is a side of its pair; the active side of a pair that
+// is not biactive is an equality of the branch and needs no multiplier.
+template <int G>
+__device__ __forceinline__ int sp_sens_marks(const SpBatch& db, GI st, GD yq, int t, int* sd)
+{
+    const int m = db.m, nC = db.nC, nK = db.nComp;
+    double ym = 0.0;
+    for (int r = t; r < m; r += G) ym = fmax(ym, fabs(yq[r]));
+    const double ytol = 1e-9 * (1.0 + g_max<G>(ym));
+    auto sideIn = [&](int r) { const int s = st[r]; return s != ST_INACT && s != ST_UPPER; };
+    int weak = 0, open = 0;
+    for (int r = t; r < m; r += G) {
+        const int s = st[r];
+        sd[r] = (s == ST_INACT) ? 0 : ((s == ST_EQ) ? 2 : (s == ST_UPPER ? 1 : -1));
+        if (s == ST_INACT) continue;
+        bool ineq = s != ST_EQ;
+        if (ineq && r >= nC && s != ST_UPPER) ineq = sideIn(r < nC + nK ? r + nK : r - nK);
+        if (ineq && fabs(yq[r]) <= ytol) weak = 1;
+    }
+    for (int i = t; i < nK; i += G) if (!sideIn(nC + i) && !sideIn(nC + nK + i)) open = 1;
+    weak = g_any<G>(weak) ? 1 : 0;
+    open = g_any<G>(open) ? 1 : 0;
+    return (weak ? 4 : 0) | (open ? 8 : 0);
+}
+
 // ---- k_sparse_sensitivity: adjoint derivatives of the returned x in g and in the bounds of the stored working set (DESIGN.md 3a'') ----------
 // At the point the last run returned, x is the minimiser of 1/2 x'Qx + g'x on E_W x = b_W, W the stored working set (MI_ST).  For an upstream
 // gradient v:  K0 [d; lambda] = [v; 0],  K0 = [Q, E_W'; E_W, 0];  dl/dg = -d,  dl/db_W = lambda.  The polish factor in memory is the LDL' of
@@ -184,24 +211,7 @@ __global__ __launch_bounds__(WGS) void k_sparse_sensitivity(SpBatch db, int nrhs
     GI st = c.I(MI_ST);
     GD yq = c.M(MV_YQ);
     const int* iperm = db.iperm;
-    // flags, as on the dense path (k_sensitivity): a row of L or R at its lower bound is a side of its pair; the active side of a pair that
-    // is not biactive is an equality of the branch and needs no multiplier
-    double ym = 0.0;
-    for (int r = t; r < m; r += G) ym = fmax(ym, fabs(yq[r]));
-    const double ytol = 1e-9 * (1.0 + g_max<G>(ym));
-    auto sideIn = [&](int r) { const int s = st[r]; return s != ST_INACT && s != ST_UPPER; };
-    int weak = 0, open = 0;
-    for (int r = t; r < m; r += G) {
-        const int s = st[r];
-        sd[r] = (s == ST_INACT) ? 0 : ((s == ST_EQ) ? 2 : (s == ST_UPPER ? 1 : -1));
-        if (s == ST_INACT) continue;
-        bool ineq = s != ST_EQ;
-        if (ineq && r >= nC && s != ST_UPPER) ineq = sideIn(r < nC + nK ? r + nK : r - nK);
-        if (ineq && fabs(yq[r]) <= ytol) weak = 1;
-    }
-    for (int i = t; i < nK; i += G) if (!sideIn(nC + i) && !sideIn(nC + nK + i)) open = 1;
-    weak = g_any<G>(weak) ? 1 : 0;
-    open = g_any<G>(open) ? 1 : 0;
+    const int marks = sp_sens_marks<G>(db, st, yq, t, sd);
     GD d = c.V(NV_PK), qd = c.V(NV_QP), lam = c.M(MV_LX), bv = c.Nv();
     const double e1 = c.info->e1max;
     int stalled = 0;
@@ -258,7 +268,186 @@ __global__ __launch_bounds__(WGS) void k_sparse_sensitivity(SpBatch db, int nrhs
         }
         g_sync();
     }
-    if (t == 0) sinfo[b] = (stalled ? 2 : 0) | (weak ? 4 : 0) | (open ? 8 : 0);
+    if (t == 0) sinfo[b] = (stalled ? 2 : 0) | marks;
+}
+
+// ---- k_sparse_sensitivity_blk: k_sparse_sensitivity for many vectors, in panels of P columns (DESIGN.md section 3a''', "The sparse arm") ------
+// One lane group per (instance, panel) WORK ITEM, not per instance: a Jacobian of one instance fills the device.  Per item the loop of
+// k_sparse_sensitivity on P columns at once: scatter [v; 0] through iperm, panel solve (sp_solve_panel: the factor is streamed once per
+// panel, P independent chains per lane), accumulate into [d; lambda], residual against the unregularised K0 by the ELL products with P
+// vectors per pass over the matrix values, per column the stopping rule of the vector kernel with the same per-column scale, at most
+// SENS_REFINE_MAX corrections.
+// Column independence: every quantity is formed per column by the sequence of operations the vector kernel applies to that vector.  A column
+// that has converged is written out at that iteration and FROZEN: its slice of the panel is zeroed (the solves then carry exact zeros
+// there) and its d, lambda are not touched again.  The padding columns of a ragged last panel are zero columns, frozen from the start.  So
+// the result of a column depends on nothing but that column -- not on its place in the panel, not on its neighbours -- bit for bit.
+// The kernel READS the batch (pools, MI_ST, MV_YQ, SpInfo, the polish factor, the border) and WRITES only its own buffers: the staged
+// outputs, side, info and the item's workspace (SpSensBlkArgs).  It uses none of SpBatch::Nv, NV_PK, NV_QP, MV_LX: two items of one
+// instance run at the same time and would collide there.
+// side is written by the item of panel 0; the flags are OR-ed into info (integer atomicOr: the order does not matter) -- 2 by any item with
+// a stalled column, 4 and 8 by the item of panel 0, 1 by every item of an unsolved instance, whose outputs are zero.
+// unit: column j of the call is e_j, written into the solve panel by the kernel itself; v is not read.
+// Band engines only (plain and bordered): the host never launches it on the general LDL' (lcqp_sparse_host.hip).
+constexpr int sens_panel_width(int G) { return LCQP_SPARSE_SENS_PANEL; }      // per lane width; 4 where 8 would need scratch
+
+// g_ell's sums for the P columns of a panel behind one pass over the matrix values: per column the W slab entries in order (an absent one
+// adds 0 * 0), then the tail of a long row.  xv(j, k): entry j of column k of the gathered panel; out(i, s): the P sums of row i.
+template <int G, int P, bool MAP, class Xv, class Out>
+__device__ __forceinline__ void sp_ell_panel(const EllMat& E, int gl, GD vals, Xv xv, Out out)
+{
+    const int rows = E.rows, W = E.W;
+    gl = here(gl);
+    for (int i = gl; i < rows; i += G) {
+        double s[P];
+#pragma unroll
+        for (int k = 0; k < P; k++) s[k] = 0.0;
+        const int p0 = E.ptr[i], p1 = E.ptr[i + 1];
+#pragma unroll 4
+        for (int q = 0; q < W; q++) {
+            const int pos = MAP ? E.epos[q * rows + i] : ((p0 + q < p1) ? p0 + q : -1);
+            const bool ok = pos >= 0;
+            const int j = ok ? E.eidx[q * rows + i] : 0;
+            const double av = vals[ok ? pos : 0];
+            const double a = ok ? av : 0.0;
+#pragma unroll
+            for (int k = 0; k < P; k++) { const double x = xv(j, k); s[k] += a * (ok ? x : 0.0); }
+        }
+        if (E.tails)
+            for (int e = p0 + W; e < p1; e++) {
+                const double av = vals[E.cmap ? E.cmap[e] : e]; const int j = E.cidx[e];
+#pragma unroll
+                for (int k = 0; k < P; k++) s[k] += av * xv(j, k);
+            }
+        out(i, s);
+    }
+}
+
+template <int G>
+__global__ __launch_bounds__(WGS) void k_sparse_sensitivity_blk(SpBatch db, SpSensBlkArgs a)
+{
+    constexpr int P = sens_panel_width(G), IPW = 64 / G;
+    const int li = blockIdx.x * IPW + threadIdx.x / G;      // item of this launch
+    if (li >= a.nItems) return;
+    const int item = a.item0 + li, ir = item / a.npan, pan = item - ir * a.npan, b = a.first + ir;
+    const int w0 = a.first + (a.item0 + (int)blockIdx.x * IPW) / a.npan;      // the instance of the wave's first item (uniform): b >= w0
+    SpCtx<G> c = sp_ctx<G>(db, b, w0, (int)threadIdx.x);
+    const int t = c.gl, n = db.n, m = db.m, Np = db.Np;
+    const int c0 = pan * P, nc = min(P, a.ncols - c0);
+    double* og = a.dg + (size_t)li * P * n;
+    double* ob = a.dbo + (size_t)li * P * m;
+    int* sd = a.side + (size_t)ir * m;
+    const int solved = c.info->haveSolution != 0 && db.stats[b].returnValue == 0;
+    if (!solved) {      // (uniform inside the group) nothing to differentiate: zero outputs
+        if (pan == 0) for (int r = t; r < m; r += G) sd[r] = 0;
+        for (int i = t; i < nc * n; i += G) og[i] = 0.0;
+        for (int r = t; r < nc * m; r += G) ob[r] = 0.0;
+        if (t == 0) atomicOr(a.info + ir, 1);
+        return;
+    }
+    GI st = c.I(MI_ST);
+    const int* iperm = db.iperm;
+    if (pan == 0) {
+        const int marks = sp_sens_marks<G>(db, st, c.M(MV_YQ), t, sd);
+        if (t == 0 && marks) atomicOr(a.info + ir, marks);
+    }
+    // the item's workspace: the base of the wave's first item (uniform) + this group's offset
+    const size_t wsItem = sens_blk_ws_doubles(db, P);
+    double* wbase = a.ws + (size_t)blockIdx.x * IPW * wsItem;
+    const unsigned woff = (unsigned)(threadIdx.x / G) * (unsigned)wsItem * 8u;
+    GD bv{wbase, woff}, d{wbase + (size_t)P * Np, woff}, qd{wbase + (size_t)P * (Np + n), woff}, lam{wbase + (size_t)P * (Np + 2 * n), woff};
+    const double* vi = a.unit ? nullptr : a.v + ((size_t)ir * a.ncols + c0) * n;
+    auto vin = [&](int i, int k) -> double {      // entry i of column k of the panel (a padding column: zero)
+        if (k >= nc) return 0.0;
+        return a.unit ? ((i == c0 + k) ? 1.0 : 0.0) : vi[(size_t)k * n + i];
+    };
+    for (int p = t; p < Np * P; p += G) bv[p] = 0.0;
+    g_sync();
+    for (int i = t; i < n; i += G) {
+        const int pi = iperm[i];
+#pragma unroll
+        for (int k = 0; k < P; k++) { bv[pi * P + k] = vin(i, k); d[i * P + k] = 0.0; }
+    }
+    for (int r = t; r < m * P; r += G) lam[r] = 0.0;
+    g_sync();
+    const double e1 = c.info->e1max;
+    unsigned act = (1u << nc) - 1u;      // columns still refined (uniform inside the group)
+    int stalled = 0;
+    auto write_out = [&](unsigned cols) {      // dl/dg = -d, dl/db_W = lambda
+#pragma unroll
+        for (int k = 0; k < P; k++)
+            if ((cols >> k) & 1u) {
+                for (int i = t; i < n; i += G) og[(size_t)k * n + i] = -(double)d[i * P + k];
+                for (int r = t; r < m; r += G) ob[(size_t)k * m + r] = (double)lam[r * P + k];
+            }
+    };
+    for (int it = 0; act; it++) {
+        sp_solve_panel<G, P>(c, bv);
+        double dm[P], mx[P], sc[P];
+#pragma unroll
+        for (int k = 0; k < P; k++) dm[k] = mx[k] = sc[k] = 0.0;
+        for (int i = t; i < n; i += G) {
+            const int pi = iperm[i];
+#pragma unroll
+            for (int k = 0; k < P; k++)
+                if ((act >> k) & 1u) { const double dn = (double)d[i * P + k] + (double)bv[pi * P + k]; d[i * P + k] = dn; dm[k] = fmax(dm[k], fabs(dn)); }
+        }
+        for (int r = t; r < m; r += G) {
+            const int pr = iperm[n + r]; const bool in = st[r] != ST_INACT;
+#pragma unroll
+            for (int k = 0; k < P; k++)
+                if ((act >> k) & 1u) lam[r * P + k] = in ? (double)lam[r * P + k] + (double)bv[pr * P + k] : 0.0;
+        }
+        g_sync();
+        if (it == 0) write_out(act);      // the answer of the regularised system: what stays when the refinement does not reach its floor
+        // the residual against K0, straight into the solve panel: [v - Q d - E_W'lambda; -E_W d]; a frozen column keeps its zeros
+        sp_ell_panel<G, P, false>(db.ellQ, t, c.Qx(), [&](int j, int k) { return (double)d[j * P + k]; },
+                                  [&](int i, double (&s)[P]) {
+#pragma unroll
+                                      for (int k = 0; k < P; k++) qd[i * P + k] = s[k];
+                                  });
+        g_sync();
+        sp_ell_panel<G, P, true>(db.ellT, t, c.Ex(), [&](int r, int k) { return (st[r] != ST_INACT) ? (double)lam[r * P + k] : 0.0; },
+                                 [&](int i, double (&s)[P]) {
+                                     const int pi = iperm[i];
+#pragma unroll
+                                     for (int k = 0; k < P; k++) {
+                                         if (!((act >> k) & 1u)) continue;
+                                         const double vv = vin(i, k), y = qd[i * P + k];
+                                         const double rv = (vv - y) - s[k];
+                                         bv[pi * P + k] = rv; mx[k] = nmax(mx[k], fabs(rv)); sc[k] = fmax(sc[k], fabs(vv) + fabs(y) + fabs(s[k]));
+                                     }
+                                 });
+        sp_ell_panel<G, P, false>(db.ellE, t, c.Ex(), [&](int j, int k) { return (double)d[j * P + k]; },
+                                  [&](int r, double (&s)[P]) {
+                                      const int pr = iperm[n + r]; const bool in = st[r] != ST_INACT;
+#pragma unroll
+                                      for (int k = 0; k < P; k++) {
+                                          if (!((act >> k) & 1u)) continue;
+                                          const double rv = in ? -s[k] : 0.0;
+                                          bv[pr * P + k] = rv; mx[k] = nmax(mx[k], fabs(rv));
+                                      }
+                                  });
+        g_sync();
+        unsigned done = 0u, conv = 0u;
+#pragma unroll
+        for (int k = 0; k < P; k++) {
+            const double res = g_max<G>(mx[k]), scale = fmax(g_max<G>(sc[k]), e1 * g_max<G>(dm[k]));
+            const bool cv = res <= 64.0 * 2.221e-16 * scale;      // (a NaN does not pass)
+            if (((act >> k) & 1u) && (cv || it == SENS_REFINE_MAX)) { done |= 1u << k; if (cv) conv |= 1u << k; else stalled = 1; }
+        }
+        if (done) {
+            if (it > 0 && conv) write_out(conv);
+            act &= ~done;
+            if (act) {      // freeze: the finished columns leave the panel
+                for (int p = t; p < Np; p += G) {
+#pragma unroll
+                    for (int k = 0; k < P; k++) if ((done >> k) & 1u) bv[p * P + k] = 0.0;
+                }
+                g_sync();
+            }
+        }
+    }
+    if (t == 0 && stalled) atomicOr(a.info + ir, 2);
 }
 
 // ---- k_sparse_kkt_probe: test and diagnostic kernel (lcqp_hip_sparse_kkt_probe) -- the factorisation engines and sp_solve held to a plain
@@ -594,6 +783,14 @@ static void sp_launch_sensitivity_dual(const SpBatch& db, hipStream_t stream, in
     sp_launch_sens<G, true>(db, stream, nrhs, v, vy, dg, dbo, side, sinfo);
 }
 
+// one launch of k_sparse_sensitivity_blk<G> (lcqp_sparse_launch.hpp: SpSensBlkArgs): a lane group per work item, no LDS (band engines only)
+template <int G>
+static void sp_launch_sensitivity_blk(const SpBatch& db, hipStream_t stream, const SpSensBlkArgs& a)
+{
+    const int ipw = 64 / G, grid = (a.nItems + ipw - 1) / ipw;
+    hipLaunchKernelGGL(k_sparse_sensitivity_blk<G>, dim3(grid), dim3(WGS), 0, stream, db, a);
+}
+
 // one launch of k_sparse_kkt_probe<G> on device buffers; the LDS of a factorisation (sp_launch), which covers the window of the general solve
 template <int G>
 static void sp_launch_kkt_probe(const SpBatch& db, hipStream_t stream, int mode, int which, int nrhs, const double* dprim, const double* ddual, const int* use,
@@ -611,7 +808,8 @@ namespace lcqp_sparse {
 template <int G>
 const SpKernels& sparse_kernels()
 {
-    static const SpKernels k = {G, sp_launch<G>, sp_launch_sensitivity<G>, sp_launch_sensitivity_dual<G>, sp_launch_kkt_probe<G>};
+    static const SpKernels k = {G, sp_launch<G>, sp_launch_sensitivity<G>, sp_launch_sensitivity_dual<G>, sp_launch_kkt_probe<G>,
+                                sp_launch_sensitivity_blk<G>, sens_panel_width(G)};
     return k;
 }
 }

@@ -767,4 +767,142 @@ __device__ __forceinline__ void sp_solve(SpCtx<G>& c, bool admm, GD b)
     if (c.db->kb > 0) sp_border_solve<G>(c, admm, b);
 }
 
+// ---- the panel forms: P right-hand sides behind one pass over the factor (k_sparse_sensitivity_blk, DESIGN.md section 3a''') --------------
+// The P vectors of a panel are stored INTERLEAVED: position p of column k is b[p * P + k], so that a lane fetches the P values of its position
+// with wide loads and the store of a finished block is contiguous.  Per step one coefficient is loaded exactly as band_sweep loads it (the
+// ring, the chunking and the folded layout are its own), P values are broadcast and P multiply-subtracts follow: P independent chains per
+// lane for the coefficient traffic of one.  Per column the sequence of operations is the one of band_sweep, so a column's result depends on
+// nothing but that column.  The scalar routines above are untouched: every kernel that had them keeps its code.
+template <int G, int P, bool FWD>
+__device__ __forceinline__ void band_sweep_panel(GD K, GD Kd, GD b, int Np, int gl)
+{
+    static_assert(P % 2 == 0, "the panel is moved in pairs of doubles");
+    constexpr int CH = G < 16 ? G : 16, NCHUNK = 64 / CH, BPS = 64 / G, RING = (G == 8) ? 8 : 2;
+    static_assert(RING >= 2 && NCHUNK % RING == 0, "RING has to divide 64 / CH (band_sweep)");
+    gl = here(gl);
+    auto at = [&](int p) -> int { return FWD ? p : Np - 1 - p; };
+    double cf[RING][CH];
+    auto load_chunk = [&](double* dst, int sb, int ck) {      // band_sweep's
+        const int s0 = ck * CH, bi = s0 / G, so = s0 % G;
+        if (sb < Np) {
+            if (FWD) {
+                const int e0 = (sb + bi * G + gl) * G + so;
+#pragma unroll
+                for (int q = 0; q < CH / 2; q++) { const dv2 v = K.ld2(e0 + 2 * q); dst[2 * q] = v.x; dst[2 * q + 1] = v.y; }
+            } else {
+                const int pb = sb + bi * G;
+#pragma unroll
+                for (int q = 0; q < CH; q++) {
+                    const int k = so + q;
+                    const int iblk = Np - G - pb - (gl < k ? G : 0);
+                    dst[q] = (iblk >= 0) ? K.ld((iblk + (G - 1 - k)) * G + (G - 1 - gl)) : 0.0;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < CH; q++) dst[q] = 0.0;
+        }
+    };
+    auto load_pos = [&](double* dst, int p) {
+#pragma unroll
+        for (int k = 0; k < P / 2; k++) { const dv2 v = b.ld2(p * P + 2 * k); dst[2 * k] = v.x; dst[2 * k + 1] = v.y; }
+    };
+    double rh[BPS][P], dl[BPS], cur[P], res[P];
+#pragma unroll
+    for (int q = 0; q < BPS; q++) { load_pos(rh[q], at(q * G + gl)); dl[q] = FWD ? Kd.ld(q * G + gl) : 1.0; }
+#pragma unroll
+    for (int ck = 0; ck < RING - 1; ck++) load_chunk(cf[ck], 0, ck);
+#pragma unroll
+    for (int c = 0; c < P; c++) { cur[c] = rh[0][c]; res[c] = 0.0; }
+    if (64 < Np) load_pos(rh[0], at(64 + gl));
+    for (int sb = 0; sb < Np; sb += 64) {
+        const bool more = sb + 64 < Np, more2 = sb + 128 < Np;
+#pragma unroll
+        for (int ck = 0; ck < NCHUNK; ck++) {
+            { const int nck = ck + RING - 1; load_chunk(cf[nck % RING], sb + 64 * (nck / NCHUNK), nck % NCHUNK); }
+#pragma unroll
+            for (int q = 0; q < CH; q++) {
+                const int s = ck * CH + q, k = s % G, bi = s / G;
+                double yj[P];
+#pragma unroll
+                for (int c = 0; c < P; c++) yj[c] = g_bcast<G>(cur[c], k);
+#pragma unroll
+                for (int c = 0; c < P; c++) cur[c] -= cf[ck % RING][q] * yj[c];
+                if (gl == k) {
+#pragma unroll
+                    for (int c = 0; c < P; c++) { res[c] = yj[c]; cur[c] = rh[(bi + 1) % BPS][c]; }
+                }
+                if (k == G - 1) {                                          // block bi is complete: store it, refill its slots
+                    const int p = at(sb + bi * G + gl);
+#pragma unroll
+                    for (int c = 0; c < P; c++) b[p * P + c] = FWD ? res[c] * dl[bi] : res[c];
+                    if (bi + 1 < BPS) { if (more) load_pos(rh[bi + 1], at(sb + 64 + (bi + 1) * G + gl)); }
+                    else if (more2) load_pos(rh[0], at(sb + 128 + gl));
+                    if (FWD && more) dl[bi] = Kd.ld(sb + 64 + bi * G + gl);
+                }
+            }
+        }
+    }
+}
+
+// the polish factor on a panel (the band engines only: the general LDL' has no panel form).  Reads the factor and the
+// border; writes the panel alone -- no counter of the context, nothing of the instance.
+template <int G, int P>
+__device__ __forceinline__ void sp_solve_band_panel(SpCtx<G>& c, GD b)
+{
+    const int Np = c.db->Np;
+    band_sweep_panel<G, P, true>(c.KF(false), c.KD(false), b, Np, c.gl);
+    g_sync();
+    band_sweep_panel<G, P, false>(c.KF(false), c.KD(false), b, Np, c.gl);
+    g_sync();
+}
+// sp_border_solve per column: the kb border dot products and the W correction for the P columns; lane 0 solves with S once per column
+template <int G, int P>
+__device__ __forceinline__ void sp_border_solve_panel(SpCtx<G>& c, GD b)
+{
+    const SpBatch& db = *c.db;
+    const int t = here(c.gl), kb = db.kb, Np = db.Np, Nb = db.N - db.kb;
+    GD W = c.BW(false), Uv = c.BUv(false), S = c.BS(false);
+    for (int a = 0; a < kb; a++) {
+        double sacc[P];
+#pragma unroll
+        for (int k = 0; k < P; k++) sacc[k] = 0.0;
+        for (int e = db.Uptr[a] + t; e < db.Uptr[a + 1]; e += G) {
+            const double u = Uv[e]; const int pos = db.Upos[e];
+#pragma unroll
+            for (int k = 0; k < P; k++) sacc[k] += u * b[pos * P + k];
+        }
+#pragma unroll
+        for (int k = 0; k < P; k++) { const double sa = g_sum<G>(sacc[k]); if (t == 0) b[(Nb + a) * P + k] -= sa; }
+    }
+    g_sync();
+    if (t == 0) {
+        for (int k = 0; k < P; k++) {
+            for (int i = 0; i < kb; i++) { double v = b[(Nb + i) * P + k]; for (int j = 0; j < i; j++) v -= S[i * kb + j] * b[(Nb + j) * P + k]; b[(Nb + i) * P + k] = v; }
+            for (int i = 0; i < kb; i++) b[(Nb + i) * P + k] = b[(Nb + i) * P + k] / S[i * kb + i];
+            for (int i = kb - 1; i >= 0; i--) { double v = b[(Nb + i) * P + k]; for (int j = i + 1; j < kb; j++) v -= S[j * kb + i] * b[(Nb + j) * P + k]; b[(Nb + i) * P + k] = v; }
+        }
+    }
+    g_sync();
+    for (int p = t; p < Nb; p += G) {
+        double acc[P];
+#pragma unroll
+        for (int k = 0; k < P; k++) acc[k] = 0.0;
+        for (int a = 0; a < kb; a++) {
+            const double w = W[a * Np + p];
+#pragma unroll
+            for (int k = 0; k < P; k++) acc[k] += w * b[(Nb + a) * P + k];
+        }
+#pragma unroll
+        for (int k = 0; k < P; k++) b[p * P + k] -= acc[k];
+    }
+    g_sync();
+}
+template <int G, int P>
+__device__ __forceinline__ void sp_solve_panel(SpCtx<G>& c, GD b)
+{
+    sp_solve_band_panel<G, P>(c, b);
+    if (c.db->kb > 0) sp_border_solve_panel<G, P>(c, b);
+}
+
 }  // namespace

@@ -500,6 +500,110 @@ extern "C" int lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* h, int nrhs, const
     return sp_sensitivity_launch(h, nrhs, v, nullptr, dg, db, side, info, &h->rs.sensMs);
 }); }
 
+// ---- panels of vectors and full Jacobians (DESIGN.md section 3a''', "The sparse arm"): k_sparse_sensitivity_blk on the work items
+// (instance, panel) of the call, in chunks under the staging cap ----
+// the panel width of the handle's engine; 0: the general LDL', which both entry points run on the vector kernel
+static int sp_panel(const lcqp_hip_sparse* h) { return h->db.general ? 0 : sp_kernels(h->db.G)->panel; }
+extern "C" int lcqp_hip_sparse_sens_panel(const lcqp_hip_sparse_t* h) { return h ? sp_panel(h) : 0; }
+
+// The chunks of a call with nItems work items of itemBytes of staging each under the cap: whole items, at least one per chunk.
+static size_t sp_panel_chunk(size_t cap, size_t itemBytes, size_t nItems)
+{
+    size_t chunk = itemBytes ? cap / itemBytes : nItems;
+    if (chunk < 1) chunk = 1;
+    return chunk < nItems ? chunk : nItems;
+}
+
+// Instances [first, first + count), ncols columns each: v [count][ncols][n] on the host, or NULL = the unit vectors (ncols = n).  dg
+// [count][ncols][n], db [count][ncols][m], side [count][m], info [count] on the host.  One launch and one download per chunk of items; an item's
+// columns are contiguous in the caller's arrays, so a chunk lands there with one copy per item.  The kernel time of the call is the sum over
+// its launches.
+static int sp_panel_run(lcqp_hip_sparse* h, int first, int count, int ncols, const double* v, double* dg, double* db, int* side, int* info)
+{
+    SpBatch& d = h->db;
+    SensBuffers& sb = h->sens;
+    const size_t P = sp_panel(h), n = d.n, m = d.m, npan = ((size_t)ncols + P - 1) / P, nItems = (size_t)count * npan;
+    const size_t wsItem = sens_blk_ws_doubles(d, (int)P);
+    const size_t chunk = sp_panel_chunk(h->adjStaging, sizeof(double) * (P * (n + m) + wsItem), nItems);
+    HIPCHK(g_sp_err, hipSetDevice(h->device));
+    const size_t vrows = v ? (size_t)count * ncols : 0;
+    if (int rc = sb.reserve_rows(g_sp_err, h->mem, h->stream, count, std::max(vrows, chunk * P), n, n, m, m)) return rc;
+    if (int rc = sb.reserve_ws(g_sp_err, h->mem, h->stream, chunk * wsItem)) return rc;
+    h->sensPending = 0;
+    if (v) HIPCHK(g_sp_err, hipMemcpyAsync(sb.v, v, sizeof(double) * vrows * n, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(g_sp_err, hipMemsetAsync(sb.info, 0, sizeof(int) * (size_t)count, h->stream));
+    std::vector<double> hg(chunk * P * n), hb(db ? chunk * P * m : 0);
+    float ms = 0.f;
+    for (size_t i0 = 0; i0 < nItems; i0 += chunk) {
+        const size_t ni = std::min(chunk, nItems - i0);
+        const SpSensBlkArgs a = {first, (int)npan, ncols, v ? 0 : 1, (int)i0, (int)ni, sb.v, sb.dg, sb.db, sb.side, sb.info, sb.ws};
+        HIPCHK(g_sp_err, hipEventRecord(sb.ev0, h->stream));
+        sp_kernels(d.G)->sensitivity_blk(d, h->stream, a);
+        HIPCHK(g_sp_err, hipGetLastError());
+        HIPCHK(g_sp_err, hipEventRecord(sb.ev1, h->stream));
+        HIPCHK(g_sp_err, hipMemcpyAsync(hg.data(), sb.dg, sizeof(double) * ni * P * n, hipMemcpyDeviceToHost, h->stream));
+        if (db) HIPCHK(g_sp_err, hipMemcpyAsync(hb.data(), sb.db, sizeof(double) * ni * P * m, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));
+        float t = 0.f;
+        HIPCHK(g_sp_err, hipEventElapsedTime(&t, sb.ev0, sb.ev1));
+        ms += t;
+        for (size_t i = 0; i < ni; i++) {
+            const size_t item = i0 + i, ir = item / npan, c0 = (item % npan) * P, nc = std::min(P, (size_t)ncols - c0);
+            std::memcpy(dg + (ir * ncols + c0) * n, hg.data() + i * P * n, sizeof(double) * nc * n);
+            if (db) std::memcpy(db + (ir * ncols + c0) * m, hb.data() + i * P * m, sizeof(double) * nc * m);
+        }
+    }
+    if (side) HIPCHK(g_sp_err, hipMemcpyAsync(side, sb.side, sizeof(int) * (size_t)count * m, hipMemcpyDeviceToHost, h->stream));
+    if (info) HIPCHK(g_sp_err, hipMemcpyAsync(info, sb.info, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));
+    h->rs.sensMs = ms;
+    return 0;
+}
+
+extern "C" int lcqp_hip_sparse_sensitivity_blocked(lcqp_hip_sparse_t* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
+{ return guarded(g_sp_err, [&] {
+    if (!h || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!sp_panel(h)) return sp_sensitivity_launch(h, nrhs, v, nullptr, dg, db, side, info, &h->rs.sensMs);
+    return sp_panel_run(h, 0, h->db.B, nrhs, v, dg, db, side, info);
+}); }
+
+// the general LDL': k_sparse_sensitivity on uploaded unit vectors, in chunks of columns whose staging (v, dg, db of the whole batch) stays
+// under the cap; the vector kernel has no instance offset, so the batch runs and the range is copied out
+static int sp_jacobian_vector(lcqp_hip_sparse* h, int first, int count, double* Jg, double* Jb, int* side, int* info)
+{
+    const SpBatch& d = h->db;
+    const size_t B = d.B, n = d.n, m = d.m;
+    const size_t cc = sp_panel_chunk(h->adjStaging, sizeof(double) * B * (2 * n + m), n);
+    std::vector<double> V(B * cc * n), G(B * cc * n), Bd(Jb ? B * cc * m : 0);
+    std::vector<int> sd(B * m), in(B);
+    float ms = 0.f;
+    for (size_t c0 = 0; c0 < n; c0 += cc) {
+        const size_t nc = std::min(cc, n - c0);
+        std::fill(V.begin(), V.end(), 0.0);
+        for (size_t b = 0; b < B; b++) for (size_t k = 0; k < nc; k++) V[(b * nc + k) * n + c0 + k] = 1.0;
+        float t = 0.f;
+        if (int rc = sp_sensitivity_launch(h, (int)nc, V.data(), nullptr, G.data(), Jb ? Bd.data() : nullptr, sd.data(), in.data(), &t)) return rc;
+        ms += t;
+        for (size_t i = 0; i < (size_t)count; i++) {
+            std::memcpy(Jg + (i * n + c0) * n, G.data() + (first + i) * nc * n, sizeof(double) * nc * n);
+            if (Jb) std::memcpy(Jb + (i * n + c0) * m, Bd.data() + (first + i) * nc * m, sizeof(double) * nc * m);
+        }
+    }
+    if (side) std::memcpy(side, sd.data() + (size_t)first * m, sizeof(int) * (size_t)count * m);
+    if (info) std::memcpy(info, in.data() + first, sizeof(int) * (size_t)count);
+    h->rs.sensMs = ms;
+    return 0;
+}
+
+extern "C" int lcqp_hip_sparse_jacobian(lcqp_hip_sparse_t* h, int first, int count, double* Jg, double* Jb, int* side, int* info)
+{ return guarded(g_sp_err, [&] {
+    if (!h || !Jg || first < 0 || count < 1 || (long long)first + count > h->db.B) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!sp_panel(h)) return sp_jacobian_vector(h, first, count, Jg, Jb, side, info);
+    return sp_panel_run(h, first, count, h->db.n, nullptr, Jg, Jb, side, info);
+}); }
+
 // ---- the full adjoint (DESIGN.md section 3a''''): k_sparse_sensitivity (with vy: its DUAL instantiation) on the whole batch, its results to
 // the host; then, on the device buffers it left, the gradients on the non-zeros that were asked for: k_sparse_adjoint_reduce once, or
 // k_sparse_adjoint_nnz per chunk of instances under the staging cap ----

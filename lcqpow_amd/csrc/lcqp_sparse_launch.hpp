@@ -134,7 +134,25 @@ using SpSensitivityDualFn = void(const SpBatch& db, hipStream_t stream, int nrhs
 // SpKktProbeFn: one launch of k_sparse_kkt_probe<G> on `stream` over device buffers (layouts and modes at the kernel).
 using SpKktProbeFn = void(const SpBatch& db, hipStream_t stream, int mode, int which, int nrhs, const double* dprim, const double* ddual, const int* use,
                           const double* rhs, double* sol, double* recP, double* recD, int* recU);
-struct SpKernels { int G; SpRunFn* run; SpSensitivityFn* sensitivity; SpSensitivityDualFn* sensitivity_dual; SpKktProbeFn* kkt_probe; };
+// SpSensitivityBlkFn: one launch of k_sparse_sensitivity_blk<G> on `stream` (DESIGN.md section 3a''', "The sparse arm"): the work items
+// [item0, item0 + nItems) of a call whose items are numbered (instance - first) * npan + panel; column c of panel q is column q * panel + c of
+// the call, ncols columns per instance.  unit != 0: column j is the unit vector e_j and v is not read; else v [count][ncols][n].  The outputs
+// of item item0 + i are staged at dg + i * panel * n and dbo + i * panel * m, one contiguous vector per column; side [count][m] (written by
+// the item of panel 0), info [count] (OR-ed into: zeroed by the host in front of the call's first launch); ws: the items' workspaces,
+// sens_blk_ws_doubles(db, panel) doubles each.
+struct SpSensBlkArgs {
+    int first, npan, ncols, unit, item0, nItems;
+    const double* v;
+    double *dg, *dbo;
+    int *side, *info;
+    double* ws;
+};
+using SpSensitivityBlkFn = void(const SpBatch& db, hipStream_t stream, const SpSensBlkArgs& a);
+// doubles of workspace per work item: the solve panel [Np], d and Q d [n], lambda [m], interleaved by column
+__host__ __device__ inline size_t sens_blk_ws_doubles(const SpBatch& db, int panel) { return (size_t)panel * ((size_t)db.Np + 2 * (size_t)db.n + db.m); }
+// panel: the panel width of this lane width's k_sparse_sensitivity_blk (0: the width is routed to the vector kernel)
+struct SpKernels { int G; SpRunFn* run; SpSensitivityFn* sensitivity; SpSensitivityDualFn* sensitivity_dual; SpKktProbeFn* kkt_probe;
+                   SpSensitivityBlkFn* sensitivity_blk; int panel; };
 // defined in lcqp_sparse.hip and instantiated there for G = LCQP_TU_G
 template <int G> const SpKernels& sparse_kernels();
 #pragma GCC visibility pop

@@ -457,12 +457,10 @@ class BatchLCQPLayer:
 
     def jacobian(self, serial=None):
         """dx/dg of the layer's last solve, [B][nV][nV] ([b][k][j] = dx_k/dg_j), a tensor of the dtype and on the device of that
-        solve's g (BatchLCQP.jacobian: the blocked kernel on the unit vectors; dense arm).  serial: the value of layer.solves right
+        solve's g (BatchLCQP.jacobian / SparseBatchLCQP.jacobian: the arm's blocked kernel on the unit vectors).  serial: the value of layer.solves right
         after the solve that is meant -- like backward, the call raises when that is not the last one.  layer.info holds the flags."""
         if self.solves == 0 or (serial is not None and serial != self.solves):
             raise RuntimeError("jacobian of a solve that is not the layer's last one: the batch object holds the state of one solve")
-        if self.sparse:
-            raise RuntimeError("jacobian: only the dense arm has the blocked kernel")
         Jg, _, _, info = self.bt.jacobian(bounds=False)
         self.info = info
         return torch.as_tensor(Jg, dtype=self._like[0], device=self._like[1])

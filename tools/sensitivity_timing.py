@@ -24,7 +24,12 @@ handle in the same process, the calls interleaved; kernel time (the sum of the c
 (256 with --quick) on the band engine: reduce = 1 (k_sparse_adjoint_reduce, nnzQ + nnzA doubles to the host) beside reduce = 0
 (k_sparse_adjoint_nnz in chunks, B times as many) on the same handle in the same process, the calls interleaved; kernel time (the sum of the
 call's kernels, k_sparse_sensitivity<G, true> included) and wall clock.
-    python tools/sensitivity_timing.py --sparse --adjoint [--quick] [--log FILE] [--reps 20]"""
+    python tools/sensitivity_timing.py --sparse --adjoint [--quick] [--log FILE] [--reps 20]
+
+--sparse --blocked: k_sparse_sensitivity_blk (sb.sensitivity_blocked(V)) beside k_sparse_sensitivity (sb.sensitivity(V)) at nrhs = 64,
+interleaved, and sb.jacobian(), on the sparse synthetic workload (512, 256, 64) on the band engine with B = 1024 (256 with --quick) and
+with B = 4, the few-instances case the (instance, panel) mapping is for.
+    python tools/sensitivity_timing.py --sparse --blocked [--quick] [--log FILE] [--reps 20]"""
 import argparse
 import os
 import sys
@@ -192,6 +197,51 @@ def measure_sparse_adjoint(B, n, nC, nK, reps, warmup=3):
     return line
 
 
+def measure_sparse_blocked(B, n, nC, nK, nrhs, reps, warmup=3):
+    """sb.sensitivity_blocked(V) (k_sparse_sensitivity, unchanged) beside sb.sensitivity(V) (k_sparse_sensitivity_blk) at nrhs vectors,
+    interleaved, and sb.jacobian(), on one handle in one process; kernel time from HIP events (sensitivity_kernel_ms)"""
+    from lcqpow_amd import synth_sparse as S
+    Qpat, Apat, qo, eo = S.sparse_pattern_arrays(n, nC, nK)
+    sb = la.SparseBatchLCQP(B, n, nC, nK, Qpat, Apat, opt=la.default_options(perturbStep=0, printLevel=0))
+    inst = [S.sparse_values(i, n, nC, nK, orders=(qo, eo)) for i in range(B)]
+    st = lambda k: np.stack([d[k] for d in inst])
+    assert sb.load(0, B, st("Qx"), st("g"), st("Ex"), lbA=st("lbA"), ubA=st("ubA")) == 0
+    sb.run()
+    stats = sb.solution()[2]
+    v = np.random.default_rng(0).standard_normal((B, nrhs, n))
+    vec, blk, jac = [], [], []
+    for r in range(warmup + reps):      # interleaved: one vector call, one blocked call
+        a = sb.sensitivity(v)
+        t0 = sb.sensitivity_kernel_ms()
+        b = sb.sensitivity_blocked(v)
+        t1 = sb.sensitivity_kernel_ms()
+        if r >= warmup:
+            vec.append(t0); blk.append(t1)
+    for r in range(warmup + reps):
+        info = sb.jacobian(bounds=False)[3]
+        if r >= warmup:
+            jac.append(sb.sensitivity_kernel_ms())
+    q = lambda ms: (float(np.min(ms)), float(np.median(ms)), float(np.max(ms)))
+    line = ("n = %d nC = %d nComp = %d B = %d (band, %d lanes, panel %d) nrhs = %d: vector kernel ms min / median / max = %.4f / %.4f / %.4f; "
+            "blocked = %.4f / %.4f / %.4f; vector / blocked (medians) = %.2f; us per vector and instance %.3f -> %.3f; bits equal %s; "
+            "jacobian (nrhs = %d) = %.4f / %.4f / %.4f, us per column and instance %.3f; solved %d, flagged %d"
+            % ((n, nC, nK, B, sb.lanes(), sb.sens_panel(), nrhs) + q(vec) + q(blk) + (np.median(vec) / np.median(blk),
+               1e3 * np.median(vec) / (B * nrhs), 1e3 * np.median(blk) / (B * nrhs), bool(np.array_equal(a[0], b[0]) and np.array_equal(a[1], b[1])), n)
+               + q(jac) + (1e3 * np.median(jac) / (B * n), sum(s["returnValue"] == 0 for s in stats), int(np.count_nonzero(info)))))
+    sb.close()
+    print(line, flush=True)
+    return line
+
+
+def sparse_blocked_main(a):
+    lines = [measure_sparse_blocked(B, 512, 256, 64, 64, a.reps) for B in ((256, 4) if a.quick else (1024, 4))]
+    if a.log:
+        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
+        with open(a.log, "w") as f:
+            f.write("k_sparse_sensitivity_blk beside k_sparse_sensitivity, sparse synthetic workload after run, one handle, calls interleaved; %d timed calls after 3 warm-up calls each\n" % a.reps)
+            f.write("\n".join(lines) + "\n")
+
+
 def sparse_adjoint_main(a):
     lines = [measure_sparse_adjoint(256 if a.quick else 1024, 512, 256, 64, a.reps)]
     if a.log:
@@ -254,6 +304,8 @@ def main():
         raise SystemExit("needs a GPU (no CPU fallback)")
     if a.sparse and a.adjoint:
         return sparse_adjoint_main(a)
+    if a.sparse and a.blocked:
+        return sparse_blocked_main(a)
     if a.sparse:
         return sparse_main(a)
     if a.blocked:
