@@ -1,6 +1,7 @@
 // lcqp_hip.hip -- the dense arm's batch: the process-wide entry points, the choice of launch table and build (dense_kernels, run_kernels)
 // and the C ABI of the batch handle, lcqp_hip_batch_* (gfx950 only; see include/lcqp_hip.h), with the two adjoint kernels that ABI
 // launches.  The QP object is lcqp_hip_qp.hip, the building blocks and CSC utilities lcqp_hip_util.hip; lcqp_hip_batch.hpp is what they share.
+// The sensitivity, Jacobian and adjoint entry points hand their kernels to the drivers of lcqp_sens_rt.hpp, which the sparse arm uses too.
 #include "lcqp_hip_batch.hpp"
 
 #include <algorithm>
@@ -614,13 +615,6 @@ extern "C" int lcqp_hip_batch_work_sums(lcqp_hip_batch_t* h, double out[6])
 }); }
 
 // ---- read-back of the constant matrices and of the working-set factor (tests, diagnostics): the raw padded blocks of one instance ----
-template <class T>
-static int read_block(T* dst, const T* src, size_t count)
-{
-    if (dst) HIPCHK(g_err, hipMemcpy(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost));
-    return 0;
-}
-
 extern "C" int lcqp_hip_batch_read_setup(lcqp_hip_batch_t* h, int b, int dims[9], double scal[2], double* Cm, double* F1, double* D1,
                                          double* Et, double* MM, int* Cp, int* Ci, double* Cv)
 { return guarded(g_err, [&] {
@@ -636,14 +630,14 @@ extern "C" int lcqp_hip_batch_read_setup(lcqp_hip_batch_t* h, int b, int dims[9]
         memcpy(dims, v, sizeof v);
     }
     if (scal) { scal[0] = info.spv; scal[1] = info.scale; }
-    int rc = read_block(Cm, d.C + ib * np * np, np * np);
-    if (!rc) rc = read_block(F1, d.F1 + ib * np * np, np * np);
-    if (!rc) rc = read_block(D1, d.D1 + ib * d.nblk * 4096, (size_t)d.nblk * 4096);
-    if (!rc) rc = read_block(Et, d.Et + ib * mE * np, mE * np);
-    if (!rc) rc = read_block(MM, d.MM + ib * ld * ld, ld * ld);
-    if (!rc) rc = read_block(Cp, d.Cp + ib * (np + 1), np + 1);
-    if (!rc) rc = read_block(Ci, d.Ci + ib * d.capC, (size_t)d.capC);
-    if (!rc) rc = read_block(Cv, d.Cv + ib * d.capC, (size_t)d.capC);
+    int rc = read_back(g_err, Cm, d.C + ib * np * np, np * np);
+    if (!rc) rc = read_back(g_err, F1, d.F1 + ib * np * np, np * np);
+    if (!rc) rc = read_back(g_err, D1, d.D1 + ib * d.nblk * 4096, (size_t)d.nblk * 4096);
+    if (!rc) rc = read_back(g_err, Et, d.Et + ib * mE * np, mE * np);
+    if (!rc) rc = read_back(g_err, MM, d.MM + ib * ld * ld, ld * ld);
+    if (!rc) rc = read_back(g_err, Cp, d.Cp + ib * (np + 1), np + 1);
+    if (!rc) rc = read_back(g_err, Ci, d.Ci + ib * d.capC, (size_t)d.capC);
+    if (!rc) rc = read_back(g_err, Cv, d.Cv + ib * d.capC, (size_t)d.capC);
     return rc;
 }); }
 
@@ -656,72 +650,37 @@ extern "C" int lcqp_hip_batch_read_working_set(lcqp_hip_batch_t* h, int b, int d
     InstInfo info;
     HIPCHK(g_err, hipMemcpy(&info, d.info + ib, sizeof(InstInfo), hipMemcpyDeviceToHost));
     if (dims) { dims[0] = info.nT; dims[1] = info.ns; }
-    int rc = read_block(slot_row, d.idx + ib * capS, capS);
-    if (!rc) rc = read_block(crow, d.crow + ib * capS, capS);
-    if (!rc) rc = read_block(row_slot, d.mi + ib * I_NUM * d.mEcap + (size_t)I_SLOT * d.mEcap, (size_t)info.mE);
-    if (!rc) rc = read_block(Ti, d.S + ib * capS * capS, capS * capS);
+    int rc = read_back(g_err, slot_row, d.idx + ib * capS, capS);
+    if (!rc) rc = read_back(g_err, crow, d.crow + ib * capS, capS);
+    if (!rc) rc = read_back(g_err, row_slot, d.mi + ib * I_NUM * d.mEcap + (size_t)I_SLOT * d.mEcap, (size_t)info.mE);
+    if (!rc) rc = read_back(g_err, Ti, d.S + ib * capS * capS, capS * capS);
     return rc;
 }); }
 
 // ---- solution sensitivities (DESIGN.md sections 3a' and 3a'''): k_sensitivity on the whole batch, k_sensitivity_blk (np <= 512) on a range ----
-// One launch on the batch stream, host buffers in and out, its kernel time added to *ms.  blk: k_sensitivity_blk on the instances
-// [first, first + count), on buffers of its own (the two kernels fix different pitches of db); v == nullptr: unit vectors, nothing
-// uploaded.  Otherwise k_sensitivity, which has no instance offset: first = 0, count = B.
-// a device buffer of the handle with room for `count` doubles (the stream is drained before a smaller one is freed)
-static int grow(lcqp_hip_batch* h, double*& p, size_t& cap, size_t count)
-{
-    if (count <= cap) return 0;
-    HIPCHK(g_err, hipStreamSynchronize(h->stream));
-    h->mem.release(p);
-    p = nullptr; cap = 0;
-    if (!h->mem.alloc(g_err, p, count)) return LCQP_HIP_ERROR;
-    cap = count;
-    return 0;
-}
-
-// dev (the device-pointer twins): v and vy are device arrays, read where they lie (they have the pitch the kernels expect); the results go to
-// the caller's device arrays with copies on the batch stream, nothing waits on the host, and the kernel time stays in the events until
-// lcqp_hip_batch_sensitivity_timing asks for it (sensPending).
-static int sensitivity_launch(lcqp_hip_batch* h, bool blk, int first, int count, int nrhs, const double* v, double* dg, double* db, int* side, int* info, float* ms,
-                              const double* vy = nullptr, bool dev = false)
+// One launch through sensitivity_call (lcqp_sens_rt.hpp: host or device arrays in and out, the kernel time added to ms or left in the
+// events).  blk: k_sensitivity_blk on the instances [first, first + count), on buffers of its own (the two kernels fix different pitches of
+// db); v == nullptr: unit vectors, nothing uploaded.  Otherwise k_sensitivity -- with vy its DUAL instantiation --, which has no instance
+// offset: first = 0, count = B.
+static int dense_sensitivity(lcqp_hip_batch* h, bool blk, int first, int count, int nrhs, const double* v, const double* vy, bool dev,
+                             double* dg, double* db, int* side, int* info, float& ms)
 {
     DevBatch& d = h->db;
-    SensBuffers& sb = blk ? h->sensBlk : h->sens;
-    HIPCHK(g_err, hipSetDevice(h->device));
-    // (ldv is the same for a Jacobian and a blocked call so that the rows reserved by one serve the other: a Jacobian's rows carry an unused v)
-    if (int rc = sb.reserve(g_err, h->mem, h->stream, count, nrhs, d.n, d.np, (size_t)d.nd + (blk ? 2 : 1) * (size_t)d.capS, d.nd)) return rc;
-    h->sensPending = 0;
-    if (v && !dev) if (int rc = sb.upload(g_err, v)) return rc;
-    const double* dv = dev ? v : (v ? sb.v : nullptr);
-    const double* dvy = vy;
-    if (vy && !dev) {      // (k_sensitivity<NCH, true> of lcqp_hip_batch_adjoint: the whole batch, vy [B][nrhs][nd] from the host)
-        if (int rc = grow(h, h->adjVy, h->adjVyCap, sb.rows * d.nd)) return rc;
-        HIPCHK(g_err, hipMemcpyAsync(h->adjVy, vy, sizeof(double) * sb.rows * d.nd, hipMemcpyHostToDevice, h->stream));
-        dvy = h->adjVy;
-    }
-    HIPCHK(g_err, hipEventRecord(sb.ev0, h->stream));
-    if (blk) h->k->sensitivity_blk(d, count, h->stream, first, nrhs, dv, sb.dg, sb.db, sb.side, sb.info);
-    else if (vy) h->k->sensitivity_dual(d, count, h->stream, nrhs, dv, dvy, sb.dg, sb.db, sb.side, sb.info);
-    else h->k->sensitivity(d, count, h->stream, nrhs, dv, sb.dg, sb.db, sb.side, sb.info);
-    HIPCHK(g_err, hipGetLastError());
-    HIPCHK(g_err, hipEventRecord(sb.ev1, h->stream));
-    if (dev) {
-        if (int rc = sb.download_device(g_err, dg, db, side, info, d.n, d.nd)) return rc;
-        h->sensPending = blk ? 2 : 1;
-        return 0;
-    }
-    if (int rc = sb.download(g_err, dg, db, side, info, d.n, d.nd)) return rc;
-    float t = 0.f;
-    HIPCHK(g_err, hipEventElapsedTime(&t, sb.ev0, sb.ev1));
-    *ms += t;
-    return 0;
+    // (ldV is the same for a Jacobian and a blocked call so that the rows reserved by one serve the other: a Jacobian's rows carry an unused v)
+    const SensPitch p = {(size_t)d.n, (size_t)d.np, (size_t)d.nd + (blk ? 2 : 1) * (size_t)d.capS, (size_t)d.nd};
+    return sensitivity_call(g_err, h, blk ? h->sensBlk : h->sn.sens, p, count, nrhs, v, vy, dev, blk ? 2 : 1, dg, db, side, info, ms,
+                            [&](const double* dv, const double* dvy, SensBuffers& sb) {
+        if (blk) h->k->sensitivity_blk(d, count, h->stream, first, nrhs, dv, sb.dg, sb.db, sb.side, sb.info);
+        else if (vy) h->k->sensitivity_dual(d, count, h->stream, nrhs, dv, dvy, sb.dg, sb.db, sb.side, sb.info);
+        else h->k->sensitivity(d, count, h->stream, nrhs, dv, sb.dg, sb.db, sb.side, sb.info);
+    });
 }
 
 // blk: the blocked kernel where the padded size has one, the vector kernel and its bits above
 int batch_sensitivity(lcqp_hip_batch* h, bool blk, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
 {
     float ms = 0.f;
-    if (int rc = sensitivity_launch(h, blk && h->k->sensitivity_blk, 0, h->db.B, nrhs, v, dg, db, side, info, &ms)) return rc;
+    if (int rc = dense_sensitivity(h, blk && h->k->sensitivity_blk, 0, h->db.B, nrhs, v, nullptr, false, dg, db, side, info, ms)) return rc;
     h->rs.sensMs = ms;
     return 0;
 }
@@ -738,42 +697,20 @@ int batch_jacobian(lcqp_hip_batch* h, int first, int count, double* Jg, double* 
 {
     DevBatch& d = h->db;
     const size_t n = d.n, nd = d.nd;
+    // no blocked kernel (np >= 1024): k_sensitivity on an uploaded identity (these sizes are the single-large-problem ones, B small)
+    if (!h->k->sensitivity_blk)
+        return jacobian_by_vectors(h, sizeof(double) * (size_t)d.B * (n + (size_t)d.np + nd + (size_t)d.capS), nd, first, count, Jg, Jb, side, info,
+                                   [&](int nc, const double* v, double* dg, double* db, int* sd, int* in, float& ms) {
+            return dense_sensitivity(h, false, 0, d.B, nc, v, nullptr, false, dg, db, sd, in, ms);
+        });
+    // chunks of instances whose staging (n rows of v, dg and db each) stays below the cap; one launch and one download per chunk
+    const size_t chunk = staging_chunk(h->sn.staging, sizeof(double) * n * (n + (size_t)d.np + nd + 2 * (size_t)d.capS), count);
     float total = 0.f;
-    if (h->k->sensitivity_blk) {
-        // chunks of instances whose staging (n rows of v, dg and db each) stays below the cap; one launch and one download per chunk
-        const size_t perInst = sizeof(double) * n * (n + (size_t)d.np + nd + 2 * (size_t)d.capS);
-        size_t chunk = h->jacStaging / perInst;
-        if (chunk < 1) chunk = 1;
-        if (chunk > (size_t)d.B) chunk = d.B;
-        for (size_t c0 = 0; c0 < (size_t)count; c0 += chunk) {
-            const size_t cb = std::min(chunk, (size_t)count - c0);
-            if (int rc = sensitivity_launch(h, true, first + (int)c0, (int)cb, d.n, nullptr, Jg + c0 * n * n, Jb ? Jb + c0 * n * nd : nullptr,
-                                            side ? side + c0 * nd : nullptr, info ? info + c0 : nullptr, &total)) return rc;
-        }
-        h->rs.sensMs = total;
-        return 0;
+    for (size_t c0 = 0; c0 < (size_t)count; c0 += chunk) {
+        const size_t cb = std::min(chunk, (size_t)count - c0);
+        if (int rc = dense_sensitivity(h, true, first + (int)c0, (int)cb, d.n, nullptr, nullptr, false, Jg + c0 * n * n, Jb ? Jb + c0 * n * nd : nullptr,
+                                       side ? side + c0 * nd : nullptr, info ? info + c0 : nullptr, total)) return rc;
     }
-    // no blocked kernel (np >= 1024): k_sensitivity on the whole batch with an uploaded identity, in chunks of unit vectors under the same cap.  The
-    // vector kernel has no instance offset: a sub-range costs the launches of the full batch of B (these sizes are the single-large-problem ones, B small).
-    const size_t B = d.B, perVec = sizeof(double) * B * (n + (size_t)d.np + nd + (size_t)d.capS);
-    size_t m = h->jacStaging / perVec;
-    if (m < 1) m = 1;
-    if (m > n) m = n;
-    std::vector<double> vh(B * m * n), dgh(B * m * n), dbh(Jb ? B * m * nd : 0);
-    std::vector<int> sideh(B * nd), infoh(B);
-    for (size_t k0 = 0; k0 < n; k0 += m) {
-        const size_t mk = std::min(m, n - k0);
-        std::fill(vh.begin(), vh.end(), 0.0);
-        for (size_t b = 0; b < B; b++) for (size_t j = 0; j < mk; j++) vh[(b * mk + j) * n + k0 + j] = 1.0;
-        if (int rc = sensitivity_launch(h, false, 0, d.B, (int)mk, vh.data(), dgh.data(), Jb ? dbh.data() : nullptr, sideh.data(), infoh.data(), &total)) return rc;
-        for (size_t i = 0; i < (size_t)count; i++) {
-            const size_t b = first + i;
-            memcpy(Jg + (i * n + k0) * n, dgh.data() + b * mk * n, sizeof(double) * mk * n);
-            if (Jb) memcpy(Jb + (i * n + k0) * nd, dbh.data() + b * mk * nd, sizeof(double) * mk * nd);
-        }
-    }
-    if (side) memcpy(side, sideh.data() + (size_t)first * nd, sizeof(int) * count * nd);
-    if (info) memcpy(info, infoh.data() + first, sizeof(int) * count);
     h->rs.sensMs = total;
     return 0;
 }
@@ -793,81 +730,62 @@ extern "C" int lcqp_hip_batch_jacobian(lcqp_hip_batch_t* h, int first, int count
 }); }
 
 extern "C" int lcqp_hip_batch_set_jacobian_staging(lcqp_hip_batch_t* h, size_t bytes)
-{ return guarded(g_err, [&] {
-    if (!h) return LCQP_INVALID_ARGUMENT;
-    h->jacStaging = bytes ? bytes : (size_t)LCQP_JACOBIAN_STAGING_BYTES;
-    return 0;
-}); }
+{
+    return guarded(g_err, [&] { return set_staging(h, bytes); });
+}
 
-// (after a device-pointer call the time is still in the events: wait for them and form it)
 extern "C" int lcqp_hip_batch_sensitivity_timing(lcqp_hip_batch_t* h, float* kernel_ms)
-{ return guarded(g_err, [&] {
-    if (h && h->sensPending) {
-        HIPCHK(g_err, hipSetDevice(h->device));
-        const SensBuffers& sb = (h->sensPending & 3) == 2 ? h->sensBlk : h->sens;
-        float t = 0.f, ta = 0.f;
-        HIPCHK(g_err, hipEventSynchronize(sb.ev1));
-        HIPCHK(g_err, hipEventElapsedTime(&t, sb.ev0, sb.ev1));
-        if (h->sensPending & 4) {
-            HIPCHK(g_err, hipEventSynchronize(h->adjEv1));
-            HIPCHK(g_err, hipEventElapsedTime(&ta, h->adjEv0, h->adjEv1));
-        }
-        h->rs.sensMs = t + ta;
-        h->sensPending = 0;
-    }
-    return sensitivity_timing(h, kernel_ms);
-}); }
+{
+    return guarded(g_err, [&] { return sensitivity_timing(g_err, h, kernel_ms, h ? &h->sensBlk : nullptr); });
+}
 
 // ---- the full adjoint (DESIGN.md section 3a''''): upstream gradients on x and y, gradients in g, the bounds and the matrices ----
-// k_sensitivity (with vy: its DUAL instantiation) on the whole batch, its results to the host; then, on the device buffers it left, the matrix
-// gradients that were asked for: k_adjoint_reduce once, or k_adjoint_outer per chunk of instances under the Jacobian staging cap.
+// k_sensitivity (with vy: its DUAL instantiation) on the whole batch, its results to the host (the device twin: to the caller's device
+// arrays); then, on the device buffers it left, the matrix gradients that were asked for.
+// the four segments of the stacked gradient as the caller asked for them (a segment without rows is not asked for)
+struct AdjointWanted { double* out[4]; int r0[4], rows[4]; };
+static AdjointWanted adjoint_wanted(const DevBatch& d, double* dQ, double* dA, double* dL, double* dR)
+{
+    return {{dQ, d.nC ? dA : nullptr, d.nComp ? dL : nullptr, d.nComp ? dR : nullptr}, {0, d.n, d.n + d.nC, d.n + d.nC + d.nComp}, {d.n, d.nC, d.nComp, d.nComp}};
+}
+// k_adjoint_reduce, or k_adjoint_outer on the instances [first, first + count); most: the doubles of the largest segment
+static void launch_adjoint(lcqp_hip_batch* h, const AdjointSegs& segs, size_t most, int reduce, int first, int count)
+{
+    const DevBatch& d = h->db;
+    const SensBuffers& sb = h->sn.sens;
+    const AdjointArgs a = {d.B, d.n, d.np, d.nd, (int)sb.ldDb, d.xout, d.yout, sb.dg, sb.db, sb.side, sb.info};
+    const unsigned gx = (unsigned)std::min<size_t>((most + 2 * WG - 1) / (2 * WG), 65535);
+    if (reduce) hipLaunchKernelGGL(k_adjoint_reduce, dim3(gx, 4), dim3(WG), 0, h->stream, a, segs);
+    else hipLaunchKernelGGL(k_adjoint_outer, dim3(gx, 4), dim3(WG), 0, h->stream, a, segs, first, count);
+}
+
+// the host call: k_adjoint_reduce once, or k_adjoint_outer per chunk of instances under the Jacobian staging cap (adjoint_chunks)
 int batch_adjoint(lcqp_hip_batch* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
                   int reduce, double* dQ, double* dA, double* dL, double* dR)
 {
     DevBatch& d = h->db;
     float ms = 0.f;
-    if (int rc = sensitivity_launch(h, false, 0, d.B, 1, vx, dg, db, side, info, &ms, vy)) return rc;
+    if (int rc = dense_sensitivity(h, false, 0, d.B, 1, vx, vy, false, dg, db, side, info, ms)) return rc;
     const size_t n = d.n;
-    double* host[4] = {dQ, d.nC ? dA : nullptr, d.nComp ? dL : nullptr, d.nComp ? dR : nullptr};
-    const int r0[4] = {0, d.n, d.n + d.nC, d.n + d.nC + d.nComp}, rows[4] = {d.n, d.nC, d.nComp, d.nComp};
+    const AdjointWanted w = adjoint_wanted(d, dQ, dA, dL, dR);
     size_t perInst = 0;      // doubles of one instance's gradients
-    for (int k = 0; k < 4; k++) if (host[k]) perInst += (size_t)rows[k] * n;
-    if (perInst) {
-        const SensBuffers& sb = h->sens;
-        const AdjointArgs a = {d.B, d.n, d.np, d.nd, (int)sb.ldDb, d.xout, d.yout, sb.dg, sb.db, sb.side, sb.info};
-        for (hipError_t e : {h->adjEv0.status, h->adjEv1.status}) if (e != hipSuccess) return hip_fail(g_err, "hipEventCreate", e);
-        size_t chunk = 1;
-        if (!reduce) {
-            chunk = h->jacStaging / (sizeof(double) * perInst);
-            if (chunk < 1) chunk = 1;
-            if (chunk > (size_t)d.B) chunk = d.B;
-        }
-        if (int rc = grow(h, h->adjOut, h->adjOutCap, chunk * perInst + 4)) return rc;      // (+ 4: every segment starts on an even offset)
-        for (size_t c0 = 0; c0 < (reduce ? (size_t)1 : (size_t)d.B); c0 += chunk) {
-            const size_t cb = reduce ? 1 : std::min(chunk, (size_t)d.B - c0);
+    for (int k = 0; k < 4; k++) if (w.out[k]) perInst += (size_t)w.rows[k] * n;
+    if (perInst)      // (+ 4: every segment starts on an even offset)
+        if (int rc = adjoint_chunks(g_err, h, perInst, 4, reduce, ms, [&](size_t c0, size_t cb, AdjCopy* cp) {
             AdjointSegs segs{};
             size_t off = 0, most = 0;
+            int ncp = 0;
             for (int k = 0; k < 4; k++) {
-                if (!host[k]) continue;
-                const size_t cnt = cb * rows[k] * n;
-                segs.s[k] = {h->adjOut + off, r0[k], rows[k]};
+                if (!w.out[k]) continue;
+                const size_t cnt = cb * w.rows[k] * n;
+                segs.s[k] = {h->sn.adjOut + off, w.r0[k], w.rows[k]};
+                cp[ncp++] = {w.out[k] + c0 * w.rows[k] * n, segs.s[k].out, cnt};
                 off += cnt + (cnt & 1);
                 most = std::max(most, cnt);
             }
-            const unsigned gx = (unsigned)std::min<size_t>((most + 2 * WG - 1) / (2 * WG), 65535);
-            HIPCHK(g_err, hipEventRecord(h->adjEv0, h->stream));
-            if (reduce) hipLaunchKernelGGL(k_adjoint_reduce, dim3(gx, 4), dim3(WG), 0, h->stream, a, segs);
-            else hipLaunchKernelGGL(k_adjoint_outer, dim3(gx, 4), dim3(WG), 0, h->stream, a, segs, (int)c0, (int)cb);
-            HIPCHK(g_err, hipGetLastError());
-            HIPCHK(g_err, hipEventRecord(h->adjEv1, h->stream));
-            for (int k = 0; k < 4; k++)
-                if (host[k]) HIPCHK(g_err, hipMemcpyAsync(host[k] + c0 * rows[k] * n, segs.s[k].out, sizeof(double) * cb * rows[k] * n, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(g_err, hipStreamSynchronize(h->stream));
-            float t = 0.f;
-            HIPCHK(g_err, hipEventElapsedTime(&t, h->adjEv0, h->adjEv1));
-            ms += t;
-        }
-    }
+            launch_adjoint(h, segs, most, reduce, (int)c0, (int)cb);
+            return ncp;
+        })) return rc;
     h->rs.sensMs = ms;
     return 0;
 }
@@ -881,52 +799,6 @@ extern "C" int lcqp_hip_batch_adjoint(lcqp_hip_batch_t* h, const double* vx, con
 }); }
 
 // ---- the device-pointer twins of the three calls above (include/lcqp_hip.h; load, update and get_solution are in lcqp_hip_device.hip) ----
-int batch_sensitivity_device(lcqp_hip_batch* h, bool blk, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
-{
-    float ms = 0.f;
-    return sensitivity_launch(h, blk && h->k->sensitivity_blk, 0, h->db.B, nrhs, v, dg, db, side, info, &ms, nullptr, true);
-}
-
-// k_sensitivity as batch_adjoint launches it, then ONE launch of k_adjoint_outer / k_adjoint_reduce that writes the caller's arrays: no
-// staging buffer, no chunks
-int batch_adjoint_device(lcqp_hip_batch* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
-                         int reduce, double* dQ, double* dA, double* dL, double* dR)
-{
-    DevBatch& d = h->db;
-    float ms = 0.f;
-    if (int rc = sensitivity_launch(h, false, 0, d.B, 1, vx, dg, db, side, info, &ms, vy, true)) return rc;
-    double* out[4] = {dQ, d.nC ? dA : nullptr, d.nComp ? dL : nullptr, d.nComp ? dR : nullptr};
-    const int r0[4] = {0, d.n, d.n + d.nC, d.n + d.nC + d.nComp}, rows[4] = {d.n, d.nC, d.nComp, d.nComp};
-    AdjointSegs segs{};
-    size_t most = 0;
-    for (int k = 0; k < 4; k++) {
-        if (!out[k]) continue;
-        segs.s[k] = {out[k], r0[k], rows[k]};
-        most = std::max(most, (reduce ? (size_t)1 : (size_t)d.B) * rows[k] * d.n);
-    }
-    if (!most) return 0;
-    const SensBuffers& sb = h->sens;
-    const AdjointArgs a = {d.B, d.n, d.np, d.nd, (int)sb.ldDb, d.xout, d.yout, sb.dg, sb.db, sb.side, sb.info};
-    for (hipError_t e : {h->adjEv0.status, h->adjEv1.status}) if (e != hipSuccess) return hip_fail(g_err, "hipEventCreate", e);
-    const unsigned gx = (unsigned)std::min<size_t>((most + 2 * WG - 1) / (2 * WG), 65535);
-    HIPCHK(g_err, hipEventRecord(h->adjEv0, h->stream));
-    if (reduce) hipLaunchKernelGGL(k_adjoint_reduce, dim3(gx, 4), dim3(WG), 0, h->stream, a, segs);
-    else hipLaunchKernelGGL(k_adjoint_outer, dim3(gx, 4), dim3(WG), 0, h->stream, a, segs, 0, d.B);
-    HIPCHK(g_err, hipGetLastError());
-    HIPCHK(g_err, hipEventRecord(h->adjEv1, h->stream));
-    h->sensPending |= 4;
-    return 0;
-}
-
-// the pointer checks of the two calls: every array with the bytes the call moves
-static bool sens_pointers_ok(lcqp_hip_batch* h, size_t rows, const double* v, const char* vname, const double* vy, double* dg, double* db, int* side, int* info)
-{
-    const DevBatch& d = h->db;
-    return device_pointer_ok(g_err, h, vname, v, sizeof(double) * rows * d.n) && device_pointer_ok(g_err, h, "vy", vy, sizeof(double) * rows * d.nd) &&
-           device_pointer_ok(g_err, h, "dg", dg, sizeof(double) * rows * d.n) && device_pointer_ok(g_err, h, "db", db, sizeof(double) * rows * d.nd) &&
-           device_pointer_ok(g_err, h, "side", side, sizeof(int) * (size_t)d.B * d.nd, 4) && device_pointer_ok(g_err, h, "info", info, sizeof(int) * (size_t)d.B, 4);
-}
-
 extern "C" int lcqp_hip_batch_sensitivity_device(lcqp_hip_batch_t* h, int blocked, int nrhs, const double* v, double* dg, double* db,
                                                  int* side, int* info, void* stream)
 { return guarded(g_err, [&] {
@@ -934,14 +806,15 @@ extern "C" int lcqp_hip_batch_sensitivity_device(lcqp_hip_batch_t* h, int blocke
     if (nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
     if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
     HIPCHK(g_err, hipSetDevice(h->device));
-    if (!sens_pointers_ok(h, (size_t)h->db.B * nrhs, v, "v", nullptr, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
-    StreamHandOver over(h, stream);
-    HIPCHK(g_err, over.status);
-    const int rc = batch_sensitivity_device(h, blocked != 0, nrhs, v, dg, db, side, info);
-    HIPCHK(g_err, over.done());
-    return rc;
+    if (!sens_pointers_ok(g_err, h, h->db.nd, (size_t)h->db.B * nrhs, v, "v", nullptr, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
+    return device_call(g_err, h, stream, [&] {
+        float ms = 0.f;
+        return dense_sensitivity(h, blocked && h->k->sensitivity_blk, 0, h->db.B, nrhs, v, nullptr, true, dg, db, side, info, ms);
+    });
 }); }
 
+// k_sensitivity as batch_adjoint launches it, then ONE launch of k_adjoint_outer / k_adjoint_reduce that writes the caller's arrays: no
+// staging buffer, no chunks
 extern "C" int lcqp_hip_batch_adjoint_device(lcqp_hip_batch_t* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
                                              int reduce, double* dQ, double* dA, double* dL, double* dR, void* stream)
 { return guarded(g_err, [&] {
@@ -950,13 +823,22 @@ extern "C" int lcqp_hip_batch_adjoint_device(lcqp_hip_batch_t* h, const double* 
     if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
     HIPCHK(g_err, hipSetDevice(h->device));
     const DevBatch& d = h->db;
-    if (!sens_pointers_ok(h, d.B, vx, "vx", vy, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
+    if (!sens_pointers_ok(g_err, h, d.nd, d.B, vx, "vx", vy, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
     const size_t lead = sizeof(double) * (reduce ? (size_t)1 : (size_t)d.B) * d.n;
     if (!device_pointer_ok(g_err, h, "dQ", dQ, lead * d.n, 16) || !device_pointer_ok(g_err, h, "dA", dA, lead * d.nC, 16) ||
         !device_pointer_ok(g_err, h, "dL", dL, lead * d.nComp, 16) || !device_pointer_ok(g_err, h, "dR", dR, lead * d.nComp, 16)) return LCQP_INVALID_ARGUMENT;
-    StreamHandOver over(h, stream);
-    HIPCHK(g_err, over.status);
-    const int rc = batch_adjoint_device(h, vx, vy, dg, db, side, info, reduce, dQ, dA, dL, dR);
-    HIPCHK(g_err, over.done());
-    return rc;
+    return device_call(g_err, h, stream, [&] {
+        float ms = 0.f;
+        if (int rc = dense_sensitivity(h, false, 0, d.B, 1, vx, vy, true, dg, db, side, info, ms)) return rc;
+        const AdjointWanted w = adjoint_wanted(d, dQ, dA, dL, dR);
+        AdjointSegs segs{};
+        size_t most = 0;
+        for (int k = 0; k < 4; k++) {
+            if (!w.out[k]) continue;
+            segs.s[k] = {w.out[k], w.r0[k], w.rows[k]};
+            most = std::max(most, (reduce ? (size_t)1 : (size_t)d.B) * w.rows[k] * d.n);
+        }
+        if (!most) return 0;
+        return adjoint_device(g_err, h, [&] { launch_adjoint(h, segs, most, reduce, 0, d.B); });
+    });
 }); }

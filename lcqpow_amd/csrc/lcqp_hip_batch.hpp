@@ -1,9 +1,10 @@
 // lcqp_hip_batch.hpp -- what the three host units of the dense arm share: the batch handle behind lcqp_hip_batch_t, the functions of
-// lcqp_hip.hip that the QP object (lcqp_hip_qp.hip) and the building blocks (lcqp_hip_util.hip) call on it, and the arm's error slot.
+// lcqp_hip.hip that the QP object (lcqp_hip_qp.hip) and the building blocks (lcqp_hip_util.hip) call on it, and the arm's error slot.  The
+// host code the handle shares with the sparse arm's comes in with lcqp_host_rt.hpp and lcqp_sens_rt.hpp.
 // Internal: nothing of it enters the dynamic symbol table of the library.  Host code only.
 #pragma once
 #include "lcqp_launch.hpp"
-#include "lcqp_host_rt.hpp"
+#include "lcqp_sens_rt.hpp"
 
 #include <string>
 #include <vector>
@@ -35,23 +36,16 @@ struct lcqp_hip_batch {
     int numCU = 256;
     bool overlapped = false;      // lcqp_hip_batch_set_overlapped
     bool ran = false, anyLoaded = false;
-    // re-solves and sensitivities (lcqp_host_rt.hpp).  boxed: which variables of an instance carry a finite box bound -- those are rows of
-    // E, hence of Et and M: an update must keep the set
+    // re-solves (lcqp_host_rt.hpp) and sensitivities (lcqp_sens_rt.hpp).  boxed: which variables of an instance carry a finite box bound --
+    // those are rows of E, hence of Et and M: an update must keep the set
     lcqp_rt::ResolveState rs;
     std::vector<char> boxed;              // [B][n]
-    lcqp_rt::SensBuffers sens;            // of k_sensitivity
+    lcqp_rt::SensState sn;                // sn.sens: of k_sensitivity
     lcqp_rt::SensBuffers sensBlk;         // of k_sensitivity_blk (another pitch of db, a varying number of instances)
-    size_t jacStaging = LCQP_JACOBIAN_STAGING_BYTES;      // device bytes a Jacobian / adjoint call may stage per chunk of instances
-    // of lcqp_hip_batch_adjoint, grown on demand: the upstream gradients on the duals [B][nd]; the matrix gradients of one chunk
-    double *adjVy = nullptr, *adjOut = nullptr;
-    size_t adjVyCap = 0, adjOutCap = 0;
-    lcqp_rt::Event adjEv0, adjEv1;        // around the last matrix-gradient launch
     // of the device-pointer entry points (lcqp_hip_device.hip): the events of the hand-over between the caller's stream and `stream`; the
-    // status words of k_check_vectors followed by the box flags of a load ([2] x 8 bytes, then [B][n] bytes); and which events still hold
-    // the kernel time of the last sensitivity_device / adjoint_device call (0: none, 1: sens, 2: sensBlk; + 4: adjEv0 / adjEv1 as well)
+    // status words of k_check_vectors followed by the box flags of a load ([2] x 8 bytes, then [B][n] bytes)
     lcqp_rt::Event evIn{hipEventDisableTiming}, evOut{hipEventDisableTiming};
     unsigned long long* devChk = nullptr;
-    int sensPending = 0;
     int nch;
     const lcqp::SizeKernels* k = nullptr; // the launch table of the padded size (dense_kernels), set by lcqp_hip_batch_create
     explicit lcqp_hip_batch(int dev) : db(), device(dev) {}
@@ -70,18 +64,6 @@ int batch_jacobian(lcqp_hip_batch* h, int first, int count, double* Jg, double* 
 int batch_adjoint(lcqp_hip_batch* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
                   int reduce, double* dQ, double* dA, double* dL, double* dR);
 
-int batch_sensitivity_device(lcqp_hip_batch* h, bool blk, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
-int batch_adjoint_device(lcqp_hip_batch* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
-                         int reduce, double* dQ, double* dA, double* dL, double* dR);
-
-// one block of a read-back entry point (tests, diagnostics): `count` values from the device to dst, or nothing when the caller passed NULL
-template <class T>
-inline int read_back(T* dst, const T* src, size_t count)
-{
-    if (dst) HIPCHK(dense_err(), hipMemcpy(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost));
-    return 0;
-}
-
 // the message of lcqp_hip_batch_update and its device twin for a variable whose box bound appears or disappears
 inline std::string box_change_message(int variable, int instance, bool gains)
 {
@@ -89,7 +71,7 @@ inline std::string box_change_message(int variable, int instance, bool gains)
            " its box bound; the set of bounded variables is fixed by the load (they are rows of the factored matrices)";
 }
 
-// (device_pointer_ok and StreamHandOver, which the device-pointer entry points of lcqp_hip.hip and lcqp_hip_device.hip are built on, are
-// templates on the handle in lcqp_host_rt.hpp: the sparse arm shares them)
+// (device_pointer_ok, device_call and read_back, which the device-pointer entry points and the readers of the three units are built on, are
+// templates in lcqp_host_rt.hpp: the sparse arm shares them)
 
 #pragma GCC visibility pop

@@ -1,6 +1,7 @@
 // lcqp_hip_device.hip -- the dense batch's device-pointer entry points that fill and read the pools: lcqp_hip_batch_load_device,
 // _update_device and _get_solution_device (include/lcqp_hip.h, DESIGN.md section 3a'''''), with their three kernels.  The twins of
-// _sensitivity and _adjoint sit beside the kernels they launch, in lcqp_hip.hip; lcqp_hip_batch.hpp holds what the two units share.
+// _sensitivity and _adjoint sit beside the kernels they launch, in lcqp_hip.hip; lcqp_hip_batch.hpp holds what the two units share, lcqp_host_rt.hpp the hand-over
+// around every such call (device_call) and _get_solution_device, which are the sparse arm's too.
 #include "lcqp_hip_batch.hpp"
 
 #include <algorithm>
@@ -230,31 +231,27 @@ extern "C" int lcqp_hip_batch_load_device(lcqp_hip_batch_t* h, int first, int co
         if (!device_pointer_ok(g_err, h, names[k], mats[k], sizeof(double) * (one ? 1 : (size_t)count) * rows[k] * n)) return LCQP_INVALID_ARGUMENT;
     }
     if (!vectors_ok(h, count, pv)) return LCQP_INVALID_ARGUMENT;
-    StreamHandOver over(h, stream);
-    HIPCHK(g_err, over.status);
-    unsigned long long words[2];
     std::vector<char> flags((size_t)count * n);
-    if (int rc = check_vectors(h, first, count, pv, false, words, (lb || ub) ? flags.data() : nullptr)) return rc;
-    if (words[0] != ~0ull) {
-        HIPCHK(g_err, over.done());
-        return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
-    }
-    // the host state of lcqp_hip_batch_load: the setup mark, the lbL / lbR flags by the rule of pack_row_bounds, the box flags
-    h->rs.invalidate();
-    const int hasL = lbL ? 1 : 0, hasR = lbR ? 1 : 0;
-    if (!h->anyLoaded || first == 0) { d.hasLbL = hasL; d.hasLbR = hasR; }
-    else { d.hasLbL |= hasL; d.hasLbR |= hasR; }
-    for (int k = 0; k < count; k++) h->rs.filled[(size_t)first + k] = 1;
-    memcpy(h->boxed.data() + (size_t)first * n, flags.data(), flags.size());
-    h->anyLoaded = true;
-    const int half = d.np / 2, mostRows = std::max(d.np, std::max(nC, std::max(nComp, d.mEcap - d.mA)));
-    const unsigned gx = (unsigned)std::min<size_t>(((size_t)mostRows * half + 4 * WG - 1) / (4 * WG), 4096);      // four pieces per thread
-    hipLaunchKernelGGL(k_pack_matrices, dim3(gx, std::min(count, 65535), 5), dim3(WG), 0, h->stream, d, first, count, pm);
-    HIPCHK(g_err, hipGetLastError());
-    hipLaunchKernelGGL(k_pack_vectors, dim3(count), dim3(WG), 0, h->stream, d, first, count, pv, 0);
-    HIPCHK(g_err, hipGetLastError());
-    HIPCHK(g_err, over.done());
-    return 0;
+    return device_call(g_err, h, stream, [&] {
+        unsigned long long words[2];
+        if (int rc = check_vectors(h, first, count, pv, false, words, (lb || ub) ? flags.data() : nullptr)) return rc;
+        if (words[0] != ~0ull) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
+        // the host state of lcqp_hip_batch_load: the setup mark, the lbL / lbR flags by the rule of pack_row_bounds, the box flags
+        h->rs.invalidate();
+        const int hasL = lbL ? 1 : 0, hasR = lbR ? 1 : 0;
+        if (!h->anyLoaded || first == 0) { d.hasLbL = hasL; d.hasLbR = hasR; }
+        else { d.hasLbL |= hasL; d.hasLbR |= hasR; }
+        for (int k = 0; k < count; k++) h->rs.filled[(size_t)first + k] = 1;
+        memcpy(h->boxed.data() + (size_t)first * n, flags.data(), flags.size());
+        h->anyLoaded = true;
+        const int half = d.np / 2, mostRows = std::max(d.np, std::max(nC, std::max(nComp, d.mEcap - d.mA)));
+        const unsigned gx = (unsigned)std::min<size_t>(((size_t)mostRows * half + 4 * WG - 1) / (4 * WG), 4096);      // four pieces per thread
+        hipLaunchKernelGGL(k_pack_matrices, dim3(gx, std::min(count, 65535), 5), dim3(WG), 0, h->stream, d, first, count, pm);
+        HIPCHK(g_err, hipGetLastError());
+        hipLaunchKernelGGL(k_pack_vectors, dim3(count), dim3(WG), 0, h->stream, d, first, count, pv, 0);
+        HIPCHK(g_err, hipGetLastError());
+        return 0;
+    });
 }); }
 
 extern "C" int lcqp_hip_batch_update_device(lcqp_hip_batch_t* h, int first, int count, const double* g,
@@ -268,37 +265,23 @@ extern "C" int lcqp_hip_batch_update_device(lcqp_hip_batch_t* h, int first, int 
     HIPCHK(g_err, hipSetDevice(h->device));
     const PackVectors pv = {g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0};
     if (!vectors_ok(h, count, pv)) return LCQP_INVALID_ARGUMENT;
-    StreamHandOver over(h, stream);
-    HIPCHK(g_err, over.status);
-    unsigned long long words[2];
-    if (int rc = check_vectors(h, first, count, pv, true, words, nullptr)) return rc;
-    if (words[0] != ~0ull || words[1] != ~0ull) {
-        HIPCHK(g_err, over.done());
+    return device_call(g_err, h, stream, [&] {
+        unsigned long long words[2];
+        if (int rc = check_vectors(h, first, count, pv, true, words, nullptr)) return rc;
         if (words[0] != ~0ull) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
-        const unsigned long long j = words[1] >> 1;
-        g_err = box_change_message((int)(j % d.n), first + (int)(j / d.n), words[1] & 1);
-        return LCQP_INVALID_ARGUMENT;
-    }
-    d.hasLbL |= lbL ? 1 : 0; d.hasLbR |= lbR ? 1 : 0;
-    hipLaunchKernelGGL(k_pack_vectors, dim3(count), dim3(WG), 0, h->stream, d, first, count, pv, 1);
-    HIPCHK(g_err, hipGetLastError());
-    HIPCHK(g_err, over.done());
-    return 0;
+        if (words[1] != ~0ull) {
+            const unsigned long long j = words[1] >> 1;
+            g_err = box_change_message((int)(j % d.n), first + (int)(j / d.n), words[1] & 1);
+            return LCQP_INVALID_ARGUMENT;
+        }
+        d.hasLbL |= lbL ? 1 : 0; d.hasLbR |= lbR ? 1 : 0;
+        hipLaunchKernelGGL(k_pack_vectors, dim3(count), dim3(WG), 0, h->stream, d, first, count, pv, 1);
+        HIPCHK(g_err, hipGetLastError());
+        return 0;
+    });
 }); }
 
 extern "C" int lcqp_hip_batch_get_solution_device(lcqp_hip_batch_t* h, double* x, double* y, lcqp_stats_t* stats, void* stream)
-{ return guarded(g_err, [&] {
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    const DevBatch& d = h->db;
-    HIPCHK(g_err, hipSetDevice(h->device));
-    const size_t B = d.B;
-    if (!device_pointer_ok(g_err, h, "x", x, sizeof(double) * B * d.n) || !device_pointer_ok(g_err, h, "y", y, sizeof(double) * B * d.nd) ||
-        !device_pointer_ok(g_err, h, "stats", stats, sizeof(lcqp_stats_t) * B, 4)) return LCQP_INVALID_ARGUMENT;
-    StreamHandOver over(h, stream);
-    HIPCHK(g_err, over.status);
-    if (x) HIPCHK(g_err, hipMemcpyAsync(x, d.xout, sizeof(double) * B * d.n, hipMemcpyDeviceToDevice, h->stream));
-    if (y) HIPCHK(g_err, hipMemcpyAsync(y, d.yout, sizeof(double) * B * d.nd, hipMemcpyDeviceToDevice, h->stream));
-    if (stats) HIPCHK(g_err, hipMemcpyAsync(stats, d.stats, sizeof(lcqp_stats_t) * B, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(g_err, over.done());
-    return 0;
-}); }
+{
+    return guarded(g_err, [&] { return get_solution_device(g_err, h, h ? h->db.nd : 0, x, y, stats, stream); });
+}

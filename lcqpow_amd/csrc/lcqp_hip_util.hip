@@ -332,14 +332,14 @@ extern "C" int lcqp_hip_batch_read_admm(lcqp_hip_batch_t* h, int b, int dims[6],
     }
     if (scal) { scal[0] = info.sigma; scal[1] = info.rhoAdmm; scal[2] = info.scale; }
     const double *nv = d.nv + ib * V_NUM * np, *mv = d.mv + ib * M_NUM * mE;
-    int rc = read_back(FK, d.FK + ib * np * np, np * np);
-    if (!rc) rc = read_back(rhov, mv + (size_t)M_RHOV * mE, mE);
-    if (!rc) rc = read_back(l, mv + (size_t)M_L * mE, mE);
-    if (!rc) rc = read_back(u, mv + (size_t)M_U * mE, mE);
-    if (!rc) rc = read_back(xa, nv + (size_t)V_XA * np, np);
-    if (!rc) rc = read_back(ya, mv + (size_t)M_YA * mE, mE);
-    if (!rc) rc = read_back(za, mv + (size_t)M_ZA * mE, mE);
-    if (!rc) rc = read_back(dy, mv + (size_t)M_DY * mE, mE);
-    if (!rc) rc = read_back(dx, nv + (size_t)V_W * np, np);
+    int rc = read_back(dense_err(), FK, d.FK + ib * np * np, np * np);
+    if (!rc) rc = read_back(dense_err(), rhov, mv + (size_t)M_RHOV * mE, mE);
+    if (!rc) rc = read_back(dense_err(), l, mv + (size_t)M_L * mE, mE);
+    if (!rc) rc = read_back(dense_err(), u, mv + (size_t)M_U * mE, mE);
+    if (!rc) rc = read_back(dense_err(), xa, nv + (size_t)V_XA * np, np);
+    if (!rc) rc = read_back(dense_err(), ya, mv + (size_t)M_YA * mE, mE);
+    if (!rc) rc = read_back(dense_err(), za, mv + (size_t)M_ZA * mE, mE);
+    if (!rc) rc = read_back(dense_err(), dy, mv + (size_t)M_DY * mE, mE);
+    if (!rc) rc = read_back(dense_err(), dx, nv + (size_t)V_W * np, np);
     return rc;
 }); }

@@ -1,5 +1,7 @@
-// lcqp_host_rt.hpp -- host runtime shared by the C ABIs of the dense (lcqp_hip.hip, lcqp_hip_qp.hip, lcqp_hip_util.hip) and sparse (lcqp_sparse_host.hip) arms: error reporting,
-// owners of streams, events and device memory, and the entry-point bodies both arms have in common.  Host code only.
+// lcqp_host_rt.hpp -- host runtime shared by the C ABIs of the dense (lcqp_hip.hip, lcqp_hip_device.hip, lcqp_hip_qp.hip, lcqp_hip_util.hip) and sparse
+// (lcqp_sparse_host.hip, lcqp_sparse_device.hip) arms: error reporting, owners of streams, events and device memory, and the entry-point bodies both arms have
+// in common -- solution, options, trace, re-solves, the buffers of a sensitivity launch, the hand-over of a device-pointer call.  What drives the sensitivity,
+// Jacobian and adjoint kernels on top of these is lcqp_sens_rt.hpp.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "../../include/lcqp_hip.h"
@@ -174,7 +176,7 @@ int get_solution(std::string& err, H* h, int ndual, double* x, double* y, lcqp_s
     return 0;
 }
 
-// ---- re-solves (*_update / *_resolve / *_launch_counts) and sensitivities: the host state of a handle (members rs and sens) and the
+// ---- re-solves (*_update / *_resolve / *_launch_counts) and sensitivities: the host state of a handle (member rs; lcqp_sens_rt.hpp: sn) and the
 // entry-point bodies of both arms.  Nothing of it is a kernel argument, and none of it enters the dynamic symbol table of the library.
 #pragma GCC visibility push(hidden)
 struct ResolveState {
@@ -227,6 +229,14 @@ int launch_counts(H* h, int out[2])
 {
     if (!h || !out) return LCQP_INVALID_ARGUMENT;
     out[0] = h->rs.nSetups; out[1] = h->rs.nLaunches;
+    return 0;
+}
+
+// one block of a read-back entry point (tests, diagnostics): `count` values from the device to dst, or nothing when the caller passed NULL
+template <class T>
+int read_back(std::string& err, T* dst, const T* src, size_t count)
+{
+    if (dst) HIPCHK(err, hipMemcpy(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -307,14 +317,6 @@ struct SensBuffers {
     }
 };
 
-// *_sensitivity_timing: the kernel time of the last sensitivity call (ResolveState::sensMs)
-template <class H>
-int sensitivity_timing(H* h, float* kernel_ms)
-{
-    if (!h || !kernel_ms || h->rs.sensMs < 0.f) return LCQP_INVALID_ARGUMENT;
-    *kernel_ms = h->rs.sensMs;
-    return 0;
-}
 // ---- the device-pointer entry points of both arms (lcqp_hip.hip, lcqp_hip_device.hip; lcqp_sparse_host.hip, lcqp_sparse_device.hip): H has
 // device, stream and the two events evIn / evOut (hipEventDisableTiming) ----
 // A data pointer of such a call: NULL, or plain device memory of the handle's device with `bytes` behind it (align: 8, or 16 where a kernel stores pairs of doubles).
@@ -367,6 +369,39 @@ struct StreamHandOver {
         return e != hipSuccess ? e : hipStreamWaitEvent(caller, h->evOut, 0);
     }
 };
+
+// What such a call enqueues, between the two halves of the hand-over: body() runs behind the caller's stream, and done() follows on every way
+// out of it.  The code of the body where it fails (a failing done() behind it is not reported), else the status of done().
+template <class H, class F>
+int device_call(std::string& err, H* h, void* stream, F body)
+{
+    StreamHandOver<H> over(h, stream);
+    HIPCHK(err, over.status);
+    if (int rc = body()) {
+        if (over.done() != hipSuccess) (void)hipGetLastError();
+        return rc;
+    }
+    HIPCHK(err, over.done());
+    return 0;
+}
+
+// *_get_solution_device: get_solution into device arrays of the caller, with copies on the handle's stream; nothing waits on the host
+template <class H>
+int get_solution_device(std::string& err, H* h, size_t ndual, double* x, double* y, lcqp_stats_t* stats, void* stream)
+{
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    const auto& d = h->db;
+    HIPCHK(err, hipSetDevice(h->device));
+    const size_t B = d.B;
+    if (!device_pointer_ok(err, h, "x", x, sizeof(double) * B * d.n) || !device_pointer_ok(err, h, "y", y, sizeof(double) * B * ndual) ||
+        !device_pointer_ok(err, h, "stats", stats, sizeof(lcqp_stats_t) * B, 4)) return LCQP_INVALID_ARGUMENT;
+    return device_call(err, h, stream, [&] {
+        if (x) HIPCHK(err, hipMemcpyAsync(x, d.xout, sizeof(double) * B * d.n, hipMemcpyDeviceToDevice, h->stream));
+        if (y) HIPCHK(err, hipMemcpyAsync(y, d.yout, sizeof(double) * B * ndual, hipMemcpyDeviceToDevice, h->stream));
+        if (stats) HIPCHK(err, hipMemcpyAsync(stats, d.stats, sizeof(lcqp_stats_t) * B, hipMemcpyDeviceToDevice, h->stream));
+        return 0;
+    });
+}
 
 #pragma GCC visibility pop
 

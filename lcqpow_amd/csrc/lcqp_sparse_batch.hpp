@@ -1,9 +1,10 @@
 // lcqp_sparse_batch.hpp -- what the two host units of the sparse arm share: the handle behind lcqp_hip_sparse_t, the functions of
-// lcqp_sparse_host.hip that the device-pointer unit (lcqp_sparse_device.hip) calls on it, and the arm's error slot.  Internal: nothing of it
-// enters the dynamic symbol table of the library.  Host code only.
+// lcqp_sparse_host.hip that the device-pointer unit (lcqp_sparse_device.hip) calls on it, and the arm's error slot.  The host code the handle
+// shares with the dense arm's comes in with lcqp_host_rt.hpp and lcqp_sens_rt.hpp.  Internal: nothing of it enters the dynamic symbol table
+// of the library.  Host code only.
 #pragma once
 #include "lcqp_sparse_launch.hpp"
-#include "lcqp_host_rt.hpp"
+#include "lcqp_sens_rt.hpp"
 
 #include <string>
 #include <vector>
@@ -29,26 +30,18 @@ struct lcqp_hip_sparse {
     std::vector<int> qdiagHost;    // entry of Q_ii in the value array
     std::vector<double> diagRatio; // per instance: min_i Q_ii / max_i Q_ii of the loaded Hessian (1: not loaded yet)
     bool loaded = false, ran = false;
-    // re-solves and sensitivities (lcqp_host_rt.hpp).  This arm has no setup without a solve: setupValid and solved go together;
-    // rhoStart is allocated by the first resolve that carries penalties
+    // re-solves (lcqp_host_rt.hpp) and sensitivities (lcqp_sens_rt.hpp).  This arm has no setup without a solve: setupValid and solved go
+    // together; rhoStart is allocated by the first resolve that carries penalties
     lcqp_rt::ResolveState rs;
-    lcqp_rt::SensBuffers sens;
-    // of lcqp_hip_sparse_adjoint, grown on demand: the upstream gradients on the duals [B][m]; the gradients on the non-zeros of one chunk of
-    // instances; the events around its kernels
-    size_t adjStaging = LCQP_JACOBIAN_STAGING_BYTES;
-    double *adjVy = nullptr, *adjOut = nullptr;
-    size_t adjVyCap = 0, adjOutCap = 0;
-    lcqp_rt::Event adjEv0, adjEv1;
+    lcqp_rt::SensState sn;
     // the device copy of csr2csc (one per pattern, uploaded by sp_value_map for the first call that needs it): the adjoint stores dAx through
     // it, k_sparse_pack_values of a device load gathers Ax through it
     int* valMap = nullptr;
     // of the device-pointer entry points (lcqp_sparse_device.hip; sensitivity_device and adjoint_device beside their host twins): the events of
     // the hand-over between the caller's stream and `stream`; the status word of k_sparse_check_vectors followed by the diagonal pairs of a
-    // load ([2] x 8 bytes, then [B][2] doubles); and which events still hold the kernel time of the last sensitivity_device / adjoint_device
-    // call (0: none, 1: sens; + 4: adjEv0 / adjEv1 as well)
+    // load ([2] x 8 bytes, then [B][2] doubles)
     lcqp_rt::Event evIn{hipEventDisableTiming}, evOut{hipEventDisableTiming};
     unsigned long long* devChk = nullptr;
-    int sensPending = 0;
     explicit lcqp_hip_sparse(int dev) : db(), device(dev) {}
     ~lcqp_hip_sparse() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
 };

@@ -1,7 +1,8 @@
 // lcqp_sparse_device.hip -- the sparse batch's device-pointer entry points that fill and read the pools: lcqp_hip_sparse_load_device,
 // _update_device and _get_solution_device (include/lcqp_hip.h, DESIGN.md section 3a'''''), with their three kernels, and the diagnostic
 // reader lcqp_hip_sparse_read_problem.  The twins of _sensitivity and _adjoint sit beside the kernels they launch, in lcqp_sparse_host.hip;
-// lcqp_sparse_batch.hpp holds what the two units share.  The model is lcqp_hip_device.hip of the dense arm.
+// lcqp_sparse_batch.hpp holds what the two units share, lcqp_host_rt.hpp the hand-over around every such call (device_call) and
+// _get_solution_device, which are the dense arm's too.  The model is lcqp_hip_device.hip of the dense arm.
 #include "lcqp_sparse_batch.hpp"
 
 #include <algorithm>
@@ -196,41 +197,37 @@ extern "C" int lcqp_hip_sparse_load_device(lcqp_hip_sparse_t* h, int first, int 
     if (!device_pointer_ok(g_sp_err, h, "Qx", Qx, sizeof(double) * (oneQ ? 1 : (size_t)count) * d.nnzQ) ||
         !device_pointer_ok(g_sp_err, h, "Ax", Ax, sizeof(double) * (oneA ? 1 : (size_t)count) * d.nnzE) || !sp_vectors_ok(h, count, pv)) return LCQP_INVALID_ARGUMENT;
     if (Ax) if (int rc = sp_value_map(h)) return rc;
-    StreamHandOver over(h, stream);
-    HIPCHK(g_sp_err, over.status);
-    const int nq = oneQ ? 1 : count;
-    std::vector<unsigned long long> chk;
-    if (int rc = sp_check_vectors(h, count, pv, Qx, pm.qStride, nq, chk)) return rc;
-    if (chk[0] != ~0ull) {
-        HIPCHK(g_sp_err, over.done());
-        return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
-    }
-    // the host state of lcqp_hip_sparse_load: the setup mark, the lbL / lbR flags by the rule of pack_row_bounds, the diagonal ratios, the ordering
-    h->rs.invalidate();
-    const int hasL = lbL ? 1 : 0, hasR = lbR ? 1 : 0;
-    if (!h->loaded || first == 0) { d.hasLbL = hasL; d.hasLbR = hasR; }
-    else { d.hasLbL |= hasL; d.hasLbR |= hasR; }
-    for (int k = 0; k < count; k++) {
-        h->rs.filled[(size_t)first + k] = 1;
-        if (!Qx) continue;
-        double pair[2];
-        memcpy(pair, chk.data() + 2 + 2 * (size_t)(oneQ ? 0 : k), sizeof(pair));
-        const double dmin = pair[0], dmax = pair[1];
-        h->diagRatio[(size_t)first + k] = (dmax > 0.0 && dmin > 0.0) ? dmin / dmax : 0.0;
-    }
-    h->loaded = true;
-    sp_choose_ordering(h);
-    if (Qx || Ax) {
-        const int most = std::max(Qx ? d.nnzQ : 0, Ax ? d.nnzE : 0);
-        const unsigned gx = (unsigned)std::min<size_t>(((size_t)most + 4 * SP_DEV_WG - 1) / (4 * SP_DEV_WG), 4096);      // four entries per thread
-        hipLaunchKernelGGL(k_sparse_pack_values, dim3(std::max(gx, 1u), std::min(count, 65535), 2), dim3(SP_DEV_WG), 0, h->stream, d, first, count, pm,
-                           (const int*)h->valMap);
+    return device_call(g_sp_err, h, stream, [&] {
+        const int nq = oneQ ? 1 : count;
+        std::vector<unsigned long long> chk;
+        if (int rc = sp_check_vectors(h, count, pv, Qx, pm.qStride, nq, chk)) return rc;
+        if (chk[0] != ~0ull) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
+        // the host state of lcqp_hip_sparse_load: the setup mark, the lbL / lbR flags by the rule of pack_row_bounds, the diagonal ratios, the ordering
+        h->rs.invalidate();
+        const int hasL = lbL ? 1 : 0, hasR = lbR ? 1 : 0;
+        if (!h->loaded || first == 0) { d.hasLbL = hasL; d.hasLbR = hasR; }
+        else { d.hasLbL |= hasL; d.hasLbR |= hasR; }
+        for (int k = 0; k < count; k++) {
+            h->rs.filled[(size_t)first + k] = 1;
+            if (!Qx) continue;
+            double pair[2];
+            memcpy(pair, chk.data() + 2 + 2 * (size_t)(oneQ ? 0 : k), sizeof(pair));
+            const double dmin = pair[0], dmax = pair[1];
+            h->diagRatio[(size_t)first + k] = (dmax > 0.0 && dmin > 0.0) ? dmin / dmax : 0.0;
+        }
+        h->loaded = true;
+        sp_choose_ordering(h);
+        if (Qx || Ax) {
+            const int most = std::max(Qx ? d.nnzQ : 0, Ax ? d.nnzE : 0);
+            const unsigned gx = (unsigned)std::min<size_t>(((size_t)most + 4 * SP_DEV_WG - 1) / (4 * SP_DEV_WG), 4096);      // four entries per thread
+            hipLaunchKernelGGL(k_sparse_pack_values, dim3(std::max(gx, 1u), std::min(count, 65535), 2), dim3(SP_DEV_WG), 0, h->stream, d, first, count, pm,
+                               (const int*)h->valMap);
+            HIPCHK(g_sp_err, hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_sparse_pack_vectors, dim3(count), dim3(SP_DEV_WG), 0, h->stream, d, first, pv, 0);
         HIPCHK(g_sp_err, hipGetLastError());
-    }
-    hipLaunchKernelGGL(k_sparse_pack_vectors, dim3(count), dim3(SP_DEV_WG), 0, h->stream, d, first, pv, 0);
-    HIPCHK(g_sp_err, hipGetLastError());
-    HIPCHK(g_sp_err, over.done());
-    return 0;
+        return 0;
+    });
 }); }
 
 extern "C" int lcqp_hip_sparse_update_device(lcqp_hip_sparse_t* h, int first, int count, const double* g,
@@ -244,46 +241,23 @@ extern "C" int lcqp_hip_sparse_update_device(lcqp_hip_sparse_t* h, int first, in
     const SpPackVectors pv = {g, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0};
     if (!sp_vectors_ok(h, count, pv)) return LCQP_INVALID_ARGUMENT;
     // no drain of the handle's stream as in lcqp_hip_sparse_update: the kernels below are behind a run in flight on the same stream
-    StreamHandOver over(h, stream);
-    HIPCHK(g_sp_err, over.status);
-    std::vector<unsigned long long> chk;
-    if (int rc = sp_check_vectors(h, count, pv, nullptr, 0, 0, chk)) return rc;
-    if (chk[0] != ~0ull) {
-        HIPCHK(g_sp_err, over.done());
-        return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
-    }
-    d.hasLbL |= lbL ? 1 : 0; d.hasLbR |= lbR ? 1 : 0;
-    hipLaunchKernelGGL(k_sparse_pack_vectors, dim3(count), dim3(SP_DEV_WG), 0, h->stream, d, first, pv, 1);
-    HIPCHK(g_sp_err, hipGetLastError());
-    HIPCHK(g_sp_err, over.done());
-    return 0;
+    return device_call(g_sp_err, h, stream, [&] {
+        std::vector<unsigned long long> chk;
+        if (int rc = sp_check_vectors(h, count, pv, nullptr, 0, 0, chk)) return rc;
+        if (chk[0] != ~0ull) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
+        d.hasLbL |= lbL ? 1 : 0; d.hasLbR |= lbR ? 1 : 0;
+        hipLaunchKernelGGL(k_sparse_pack_vectors, dim3(count), dim3(SP_DEV_WG), 0, h->stream, d, first, pv, 1);
+        HIPCHK(g_sp_err, hipGetLastError());
+        return 0;
+    });
 }); }
 
 extern "C" int lcqp_hip_sparse_get_solution_device(lcqp_hip_sparse_t* h, double* x, double* y, lcqp_stats_t* stats, void* stream)
-{ return guarded(g_sp_err, [&] {
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    const SpBatch& d = h->db;
-    HIPCHK(g_sp_err, hipSetDevice(h->device));
-    const size_t B = d.B;
-    if (!device_pointer_ok(g_sp_err, h, "x", x, sizeof(double) * B * d.n) || !device_pointer_ok(g_sp_err, h, "y", y, sizeof(double) * B * d.m) ||
-        !device_pointer_ok(g_sp_err, h, "stats", stats, sizeof(lcqp_stats_t) * B, 4)) return LCQP_INVALID_ARGUMENT;
-    StreamHandOver over(h, stream);
-    HIPCHK(g_sp_err, over.status);
-    if (x) HIPCHK(g_sp_err, hipMemcpyAsync(x, d.xout, sizeof(double) * B * d.n, hipMemcpyDeviceToDevice, h->stream));
-    if (y) HIPCHK(g_sp_err, hipMemcpyAsync(y, d.yout, sizeof(double) * B * d.m, hipMemcpyDeviceToDevice, h->stream));
-    if (stats) HIPCHK(g_sp_err, hipMemcpyAsync(stats, d.stats, sizeof(lcqp_stats_t) * B, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(g_sp_err, over.done());
-    return 0;
-}); }
-
-// ---- test and diagnostic entry point: the problem of one instance as the pools hold it (host buffers, synchronous, launches nothing) ----
-template <class T>
-static int sp_read_back(T* dst, const T* src, size_t count)
 {
-    if (dst) HIPCHK(g_sp_err, hipMemcpy(dst, src, sizeof(T) * count, hipMemcpyDeviceToHost));
-    return 0;
+    return guarded(g_sp_err, [&] { return get_solution_device(g_sp_err, h, h ? h->db.m : 0, x, y, stats, stream); });
 }
 
+// ---- test and diagnostic entry point: the problem of one instance as the pools hold it (host buffers, synchronous, launches nothing) ----
 extern "C" int lcqp_hip_sparse_read_problem(lcqp_hip_sparse_t* h, int instance, double* Qx, double* Ax, double* g,
                                             double* lE, double* uE, double* lbL, double* lbR, double* x0, double* y0, int* hasY0)
 { return guarded(g_sp_err, [&] {
@@ -292,19 +266,19 @@ extern "C" int lcqp_hip_sparse_read_problem(lcqp_hip_sparse_t* h, int instance, 
     if (int rc = synchronize(g_sp_err, h)) return rc;
     const size_t b = instance, n = d.n, m = d.m, nK = d.nComp;
     const double *nv = d.nv + b * NV_NUM * n, *mv = d.mv + b * MV_NUM * m;
-    if (int rc = sp_read_back(Qx, d.Qx + b * d.nnzQ, d.nnzQ)) return rc;
+    if (int rc = read_back(g_sp_err, Qx, d.Qx + b * d.nnzQ, d.nnzQ)) return rc;
     if (Ax) {      // Ex is in the CSR order of the device: entry e is entry csr2csc[e] of the caller's CSC array
         std::vector<double> ex(d.nnzE);
-        if (int rc = sp_read_back(ex.data(), d.Ex + b * d.nnzE, d.nnzE)) return rc;
+        if (int rc = read_back(g_sp_err, ex.data(), d.Ex + b * d.nnzE, d.nnzE)) return rc;
         for (int e = 0; e < d.nnzE; e++) Ax[h->csr2csc[e]] = ex[e];
     }
-    if (int rc = sp_read_back(g, nv + (size_t)NV_G * n, n)) return rc;
-    if (int rc = sp_read_back(x0, nv + (size_t)NV_X0 * n, n)) return rc;
-    if (int rc = sp_read_back(lE, mv + (size_t)MV_L * m, m)) return rc;
-    if (int rc = sp_read_back(uE, mv + (size_t)MV_U * m, m)) return rc;
-    if (int rc = sp_read_back(y0, mv + (size_t)MV_Y0 * m, m)) return rc;
-    if (int rc = sp_read_back(lbL, d.lbL + b * nK, nK)) return rc;
-    if (int rc = sp_read_back(lbR, d.lbR + b * nK, nK)) return rc;
-    if (int rc = sp_read_back(hasY0, &d.info[b].hasY0, 1)) return rc;
+    if (int rc = read_back(g_sp_err, g, nv + (size_t)NV_G * n, n)) return rc;
+    if (int rc = read_back(g_sp_err, x0, nv + (size_t)NV_X0 * n, n)) return rc;
+    if (int rc = read_back(g_sp_err, lE, mv + (size_t)MV_L * m, m)) return rc;
+    if (int rc = read_back(g_sp_err, uE, mv + (size_t)MV_U * m, m)) return rc;
+    if (int rc = read_back(g_sp_err, y0, mv + (size_t)MV_Y0 * m, m)) return rc;
+    if (int rc = read_back(g_sp_err, lbL, d.lbL + b * nK, nK)) return rc;
+    if (int rc = read_back(g_sp_err, lbR, d.lbR + b * nK, nK)) return rc;
+    if (int rc = read_back(g_sp_err, hasY0, &d.info[b].hasY0, 1)) return rc;
     return 0;
 }); }

@@ -1,7 +1,7 @@
 // lcqp_sparse_host.hip -- the host side of the sparse arm: the C ABI lcqp_hip_sparse_* (include/lcqp_hip.h).  The handle, the pattern
 // analysis (lcqp_sparse_pattern.hpp) and the storage of a batch in create, load / update / run / resolve, sensitivities, the full adjoint,
 // the device-pointer twins of the last two, the readers, and the LCQP_SPARSE_* environment test hooks (the device-pointer load / update /
-// solution and their kernels: lcqp_sparse_device.hip; lcqp_sparse_batch.hpp holds what the two units share).  The kernels of the solver are not defined here: they are in lcqp_sparse.hip,
+// solution and their kernels: lcqp_sparse_device.hip; lcqp_sparse_batch.hpp holds what the two units share; the drivers of the sensitivity, Jacobian and adjoint kernels are those of the dense arm, lcqp_sens_rt.hpp).  The kernels of the solver are not defined here: they are in lcqp_sparse.hip,
 // one translation unit per lane-group width G, reached through the launch tables of lcqp_sparse_launch.hpp.  The two kernels that do not
 // depend on the width -- the matrix gradients of lcqp_hip_sparse_adjoint -- sit beside the entry point that launches them, as
 // k_adjoint_outer / k_adjoint_reduce do in lcqp_hip.hip.
@@ -432,18 +432,6 @@ extern "C" int lcqp_hip_sparse_launch_counts(lcqp_hip_sparse_t* h, int out[2])
     return launch_counts(h, out);
 }
 
-// a device buffer of the handle with room for `count` doubles (the stream is drained before a smaller one is freed)
-static int sp_grow(lcqp_hip_sparse* h, double*& p, size_t& cap, size_t count)
-{
-    if (count <= cap) return 0;
-    HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));
-    h->mem.release(p);
-    p = nullptr; cap = 0;
-    if (!h->mem.alloc(g_sp_err, p, count)) return LCQP_HIP_ERROR;
-    cap = count;
-    return 0;
-}
-
 // the device copy of the one value map of the pattern (a permutation of the positions of the caller's Ax), uploaded once: entry k of the CSR
 // arrays of E is entry valMap[k] of the caller's CSC array.  The adjoint scatters through it, a device load gathers through it.
 int sp_value_map(lcqp_hip_sparse* h)
@@ -456,40 +444,25 @@ int sp_value_map(lcqp_hip_sparse* h)
     return 0;
 }
 
-// ---- solution sensitivities (DESIGN.md section 3a''): one launch of k_sparse_sensitivity on the handle's stream, host buffers in and out,
-// its kernel time in *ms.  vy ([B][nrhs][m]): the DUAL instantiation of lcqp_hip_sparse_adjoint.  dev (the device-pointer twins): v and vy are
-// device arrays, read where they lie; the results go to the caller's device arrays with copies on the handle's stream, nothing waits on the
-// host, and the kernel time stays in the events until lcqp_hip_sparse_sensitivity_timing asks for it (sensPending) ----
-static int sp_sensitivity_launch(lcqp_hip_sparse* h, int nrhs, const double* v, const double* vy, double* dg, double* db, int* side, int* info, float* ms,
-                                 bool dev = false)
+// ---- solution sensitivities (DESIGN.md section 3a''): one launch of k_sparse_sensitivity -- with vy ([B][nrhs][m]) the DUAL instantiation of
+// lcqp_hip_sparse_adjoint -- on the whole batch through sensitivity_call (lcqp_sens_rt.hpp: host or device arrays in and out, the kernel time
+// added to ms or left in the events) ----
+static int sp_sensitivity(lcqp_hip_sparse* h, int nrhs, const double* v, const double* vy, bool dev, double* dg, double* db, int* side, int* info, float& ms)
 {
     SpBatch& d = h->db;
-    SensBuffers& sb = h->sens;
-    HIPCHK(g_sp_err, hipSetDevice(h->device));
-    if (int rc = sb.reserve(g_sp_err, h->mem, h->stream, d.B, nrhs, d.n, d.n, d.m, d.m)) return rc;
-    h->sensPending = 0;
-    const double *dv = v, *dvy = vy;
-    if (!dev) {
-        if (int rc = sb.upload(g_sp_err, v)) return rc;
-        dv = sb.v;
-        if (vy) {
-            if (int rc = sp_grow(h, h->adjVy, h->adjVyCap, sb.rows * d.m)) return rc;
-            HIPCHK(g_sp_err, hipMemcpyAsync(h->adjVy, vy, sizeof(double) * sb.rows * d.m, hipMemcpyHostToDevice, h->stream));
-            dvy = h->adjVy;
-        }
-    }
-    HIPCHK(g_sp_err, hipEventRecord(sb.ev0, h->stream));
-    if (vy) sp_kernels(d.G)->sensitivity_dual(d, h->stream, nrhs, dv, dvy, sb.dg, sb.db, sb.side, sb.info);
-    else sp_kernels(d.G)->sensitivity(d, h->stream, nrhs, dv, sb.dg, sb.db, sb.side, sb.info);
-    HIPCHK(g_sp_err, hipGetLastError());
-    HIPCHK(g_sp_err, hipEventRecord(sb.ev1, h->stream));
-    if (dev) {
-        if (int rc = sb.download_device(g_sp_err, dg, db, side, info, d.n, d.m)) return rc;
-        h->sensPending = 1;
-        return 0;
-    }
-    if (int rc = sb.download(g_sp_err, dg, db, side, info, d.n, d.m)) return rc;
-    HIPCHK(g_sp_err, hipEventElapsedTime(ms, sb.ev0, sb.ev1));
+    const SensPitch p = {(size_t)d.n, (size_t)d.n, (size_t)d.m, (size_t)d.m};
+    return sensitivity_call(g_sp_err, h, h->sn.sens, p, d.B, nrhs, v, vy, dev, 1, dg, db, side, info, ms, [&](const double* dv, const double* dvy, SensBuffers& sb) {
+        if (vy) sp_kernels(d.G)->sensitivity_dual(d, h->stream, nrhs, dv, dvy, sb.dg, sb.db, sb.side, sb.info);
+        else sp_kernels(d.G)->sensitivity(d, h->stream, nrhs, dv, sb.dg, sb.db, sb.side, sb.info);
+    });
+}
+
+// the host call on the vector kernel
+static int sp_sensitivity_host(lcqp_hip_sparse* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
+{
+    float ms = 0.f;
+    if (int rc = sp_sensitivity(h, nrhs, v, nullptr, false, dg, db, side, info, ms)) return rc;
+    h->rs.sensMs = ms;
     return 0;
 }
 
@@ -497,7 +470,7 @@ extern "C" int lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* h, int nrhs, const
 { return guarded(g_sp_err, [&] {
     if (!h || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
     if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return sp_sensitivity_launch(h, nrhs, v, nullptr, dg, db, side, info, &h->rs.sensMs);
+    return sp_sensitivity_host(h, nrhs, v, dg, db, side, info);
 }); }
 
 // ---- panels of vectors and full Jacobians (DESIGN.md section 3a''', "The sparse arm"): k_sparse_sensitivity_blk on the work items
@@ -506,14 +479,6 @@ extern "C" int lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* h, int nrhs, const
 static int sp_panel(const lcqp_hip_sparse* h) { return h->db.general ? 0 : sp_kernels(h->db.G)->panel; }
 extern "C" int lcqp_hip_sparse_sens_panel(const lcqp_hip_sparse_t* h) { return h ? sp_panel(h) : 0; }
 
-// The chunks of a call with nItems work items of itemBytes of staging each under the cap: whole items, at least one per chunk.
-static size_t sp_panel_chunk(size_t cap, size_t itemBytes, size_t nItems)
-{
-    size_t chunk = itemBytes ? cap / itemBytes : nItems;
-    if (chunk < 1) chunk = 1;
-    return chunk < nItems ? chunk : nItems;
-}
-
 // Instances [first, first + count), ncols columns each: v [count][ncols][n] on the host, or NULL = the unit vectors (ncols = n).  dg
 // [count][ncols][n], db [count][ncols][m], side [count][m], info [count] on the host.  One launch and one download per chunk of items; an item's
 // columns are contiguous in the caller's arrays, so a chunk lands there with one copy per item.  The kernel time of the call is the sum over
@@ -521,15 +486,15 @@ static size_t sp_panel_chunk(size_t cap, size_t itemBytes, size_t nItems)
 static int sp_panel_run(lcqp_hip_sparse* h, int first, int count, int ncols, const double* v, double* dg, double* db, int* side, int* info)
 {
     SpBatch& d = h->db;
-    SensBuffers& sb = h->sens;
+    SensBuffers& sb = h->sn.sens;
     const size_t P = sp_panel(h), n = d.n, m = d.m, npan = ((size_t)ncols + P - 1) / P, nItems = (size_t)count * npan;
     const size_t wsItem = sens_blk_ws_doubles(d, (int)P);
-    const size_t chunk = sp_panel_chunk(h->adjStaging, sizeof(double) * (P * (n + m) + wsItem), nItems);
+    const size_t chunk = staging_chunk(h->sn.staging, sizeof(double) * (P * (n + m) + wsItem), nItems);
     HIPCHK(g_sp_err, hipSetDevice(h->device));
     const size_t vrows = v ? (size_t)count * ncols : 0;
     if (int rc = sb.reserve_rows(g_sp_err, h->mem, h->stream, count, std::max(vrows, chunk * P), n, n, m, m)) return rc;
     if (int rc = sb.reserve_ws(g_sp_err, h->mem, h->stream, chunk * wsItem)) return rc;
-    h->sensPending = 0;
+    h->sn.sensPending = 0;
     if (v) HIPCHK(g_sp_err, hipMemcpyAsync(sb.v, v, sizeof(double) * vrows * n, hipMemcpyHostToDevice, h->stream));
     HIPCHK(g_sp_err, hipMemsetAsync(sb.info, 0, sizeof(int) * (size_t)count, h->stream));
     std::vector<double> hg(chunk * P * n), hb(db ? chunk * P * m : 0);
@@ -537,10 +502,7 @@ static int sp_panel_run(lcqp_hip_sparse* h, int first, int count, int ncols, con
     for (size_t i0 = 0; i0 < nItems; i0 += chunk) {
         const size_t ni = std::min(chunk, nItems - i0);
         const SpSensBlkArgs a = {first, (int)npan, ncols, v ? 0 : 1, (int)i0, (int)ni, sb.v, sb.dg, sb.db, sb.side, sb.info, sb.ws};
-        HIPCHK(g_sp_err, hipEventRecord(sb.ev0, h->stream));
-        sp_kernels(d.G)->sensitivity_blk(d, h->stream, a);
-        HIPCHK(g_sp_err, hipGetLastError());
-        HIPCHK(g_sp_err, hipEventRecord(sb.ev1, h->stream));
+        if (int rc = timed_launch(g_sp_err, h->stream, sb.ev0, sb.ev1, [&] { sp_kernels(d.G)->sensitivity_blk(d, h->stream, a); })) return rc;
         HIPCHK(g_sp_err, hipMemcpyAsync(hg.data(), sb.dg, sizeof(double) * ni * P * n, hipMemcpyDeviceToHost, h->stream));
         if (db) HIPCHK(g_sp_err, hipMemcpyAsync(hb.data(), sb.db, sizeof(double) * ni * P * m, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));
@@ -564,134 +526,87 @@ extern "C" int lcqp_hip_sparse_sensitivity_blocked(lcqp_hip_sparse_t* h, int nrh
 { return guarded(g_sp_err, [&] {
     if (!h || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
     if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    if (!sp_panel(h)) return sp_sensitivity_launch(h, nrhs, v, nullptr, dg, db, side, info, &h->rs.sensMs);
+    if (!sp_panel(h)) return sp_sensitivity_host(h, nrhs, v, dg, db, side, info);
     return sp_panel_run(h, 0, h->db.B, nrhs, v, dg, db, side, info);
 }); }
-
-// the general LDL': k_sparse_sensitivity on uploaded unit vectors, in chunks of columns whose staging (v, dg, db of the whole batch) stays
-// under the cap; the vector kernel has no instance offset, so the batch runs and the range is copied out
-static int sp_jacobian_vector(lcqp_hip_sparse* h, int first, int count, double* Jg, double* Jb, int* side, int* info)
-{
-    const SpBatch& d = h->db;
-    const size_t B = d.B, n = d.n, m = d.m;
-    const size_t cc = sp_panel_chunk(h->adjStaging, sizeof(double) * B * (2 * n + m), n);
-    std::vector<double> V(B * cc * n), G(B * cc * n), Bd(Jb ? B * cc * m : 0);
-    std::vector<int> sd(B * m), in(B);
-    float ms = 0.f;
-    for (size_t c0 = 0; c0 < n; c0 += cc) {
-        const size_t nc = std::min(cc, n - c0);
-        std::fill(V.begin(), V.end(), 0.0);
-        for (size_t b = 0; b < B; b++) for (size_t k = 0; k < nc; k++) V[(b * nc + k) * n + c0 + k] = 1.0;
-        float t = 0.f;
-        if (int rc = sp_sensitivity_launch(h, (int)nc, V.data(), nullptr, G.data(), Jb ? Bd.data() : nullptr, sd.data(), in.data(), &t)) return rc;
-        ms += t;
-        for (size_t i = 0; i < (size_t)count; i++) {
-            std::memcpy(Jg + (i * n + c0) * n, G.data() + (first + i) * nc * n, sizeof(double) * nc * n);
-            if (Jb) std::memcpy(Jb + (i * n + c0) * m, Bd.data() + (first + i) * nc * m, sizeof(double) * nc * m);
-        }
-    }
-    if (side) std::memcpy(side, sd.data() + (size_t)first * m, sizeof(int) * (size_t)count * m);
-    if (info) std::memcpy(info, in.data() + first, sizeof(int) * (size_t)count);
-    h->rs.sensMs = ms;
-    return 0;
-}
 
 extern "C" int lcqp_hip_sparse_jacobian(lcqp_hip_sparse_t* h, int first, int count, double* Jg, double* Jb, int* side, int* info)
 { return guarded(g_sp_err, [&] {
     if (!h || !Jg || first < 0 || count < 1 || (long long)first + count > h->db.B) return LCQP_INVALID_ARGUMENT;
     if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    if (!sp_panel(h)) return sp_jacobian_vector(h, first, count, Jg, Jb, side, info);
-    return sp_panel_run(h, first, count, h->db.n, nullptr, Jg, Jb, side, info);
+    if (sp_panel(h)) return sp_panel_run(h, first, count, h->db.n, nullptr, Jg, Jb, side, info);
+    // the general LDL': k_sparse_sensitivity on uploaded unit vectors; the staging of a column is v, dg and db of the whole batch
+    const size_t B = h->db.B, n = h->db.n, m = h->db.m;
+    return jacobian_by_vectors(h, sizeof(double) * B * (2 * n + m), m, first, count, Jg, Jb, side, info,
+                               [&](int nc, const double* v, double* dg, double* db, int* sd, int* in, float& ms) {
+        return sp_sensitivity(h, nc, v, nullptr, false, dg, db, sd, in, ms);
+    });
 }); }
 
 // ---- the full adjoint (DESIGN.md section 3a''''): k_sparse_sensitivity (with vy: its DUAL instantiation) on the whole batch, its results to
-// the host; then, on the device buffers it left, the gradients on the non-zeros that were asked for: k_sparse_adjoint_reduce once, or
-// k_sparse_adjoint_nnz per chunk of instances under the staging cap ----
-static int sp_adjoint(lcqp_hip_sparse* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info, int reduce, double* dQx, double* dAx)
+// the host (the device twin: to the caller's device arrays); then, on the device buffers it left, the gradients on the non-zeros that were
+// asked for ----
+// k_sparse_adjoint_reduce, or k_sparse_adjoint_nnz on the instances [first, first + count), into outQ (cq doubles) and outE (ce doubles)
+static void sp_launch_adjoint(lcqp_hip_sparse* h, double* outQ, size_t cq, double* outE, size_t ce, int reduce, int first, int count)
 {
-    SpBatch& d = h->db;
-    float ms = 0.f;
-    if (int rc = sp_sensitivity_launch(h, 1, vx, vy, dg, db, side, info, &ms)) return rc;
-    const size_t nq = dQx ? (size_t)d.nnzQ : 0, ne = dAx ? (size_t)d.nnzE : 0, perInst = nq + ne;
-    if (perInst) {
-        for (hipError_t e : {h->adjEv0.status, h->adjEv1.status}) if (e != hipSuccess) return hip_fail(g_sp_err, "hipEventCreate", e);
-        if (dAx) if (int rc = sp_value_map(h)) return rc;
-        const SensBuffers& sb = h->sens;
-        size_t chunk = 1;
-        if (!reduce) {
-            chunk = h->adjStaging / (sizeof(double) * perInst);
-            if (chunk < 1) chunk = 1;
-            if (chunk > (size_t)d.B) chunk = d.B;
-        }
-        if (int rc = sp_grow(h, h->adjOut, h->adjOutCap, chunk * perInst + 2)) return rc;      // (+ 2: both segments start on an even offset)
-        SpAdjointArgs a = {d.B, d.n, d.m, d.nnzQ, d.nnzE, d.xout, d.yout, sb.dg, sb.db, sb.side, sb.info, d.Qp, d.Qi, d.Erow, d.Ei, h->valMap, nullptr, nullptr};
-        for (size_t c0 = 0; c0 < (reduce ? (size_t)1 : (size_t)d.B); c0 += chunk) {
-            const size_t cb = reduce ? 1 : std::min(chunk, (size_t)d.B - c0);
-            const size_t cq = cb * nq, ce = cb * ne;
-            a.outQ = dQx ? h->adjOut : nullptr;
-            a.outE = dAx ? h->adjOut + cq + (cq & 1) : nullptr;
-            // a thread of the Q segment owns two neighbouring entries, one of the E segment one entry
-            const unsigned gx = (unsigned)std::min<size_t>((std::max((cq + 1) / 2, ce) + SP_ADJ_WG - 1) / SP_ADJ_WG, 65535);
-            HIPCHK(g_sp_err, hipEventRecord(h->adjEv0, h->stream));
-            if (reduce) hipLaunchKernelGGL(k_sparse_adjoint_reduce, dim3(gx, 2), dim3(SP_ADJ_WG), 0, h->stream, a);
-            else hipLaunchKernelGGL(k_sparse_adjoint_nnz, dim3(gx, 2), dim3(SP_ADJ_WG), 0, h->stream, a, (int)c0, (int)cb);
-            HIPCHK(g_sp_err, hipGetLastError());
-            HIPCHK(g_sp_err, hipEventRecord(h->adjEv1, h->stream));
-            if (dQx) HIPCHK(g_sp_err, hipMemcpyAsync(dQx + c0 * nq, a.outQ, sizeof(double) * cq, hipMemcpyDeviceToHost, h->stream));
-            if (dAx) HIPCHK(g_sp_err, hipMemcpyAsync(dAx + c0 * ne, a.outE, sizeof(double) * ce, hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));
-            float t = 0.f;
-            HIPCHK(g_sp_err, hipEventElapsedTime(&t, h->adjEv0, h->adjEv1));
-            ms += t;
-        }
-    }
-    h->rs.sensMs = ms;
-    return 0;
+    const SpBatch& d = h->db;
+    const SensBuffers& sb = h->sn.sens;
+    const SpAdjointArgs a = {d.B, d.n, d.m, d.nnzQ, d.nnzE, d.xout, d.yout, sb.dg, sb.db, sb.side, sb.info, d.Qp, d.Qi, d.Erow, d.Ei, h->valMap, outQ, outE};
+    // a thread of the Q segment owns two neighbouring entries, one of the E segment one entry
+    const unsigned gx = (unsigned)std::min<size_t>((std::max((cq + 1) / 2, ce) + SP_ADJ_WG - 1) / SP_ADJ_WG, 65535);
+    if (reduce) hipLaunchKernelGGL(k_sparse_adjoint_reduce, dim3(gx, 2), dim3(SP_ADJ_WG), 0, h->stream, a);
+    else hipLaunchKernelGGL(k_sparse_adjoint_nnz, dim3(gx, 2), dim3(SP_ADJ_WG), 0, h->stream, a, first, count);
 }
 
+// the host call: k_sparse_adjoint_reduce once, or k_sparse_adjoint_nnz per chunk of instances under the staging cap (adjoint_chunks)
 extern "C" int lcqp_hip_sparse_adjoint(lcqp_hip_sparse_t* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
                                        int reduce, double* dQx, double* dAx)
 { return guarded(g_sp_err, [&] {
     if (!h || !vx || !dg || (reduce != 0 && reduce != 1)) return LCQP_INVALID_ARGUMENT;
     if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return sp_adjoint(h, vx, vy, dg, db, side, info, reduce, dQx, dAx);
-}); }
-
-extern "C" int lcqp_hip_sparse_set_adjoint_staging(lcqp_hip_sparse_t* h, size_t bytes)
-{ return guarded(g_sp_err, [&] {
-    if (!h) return LCQP_INVALID_ARGUMENT;
-    h->adjStaging = bytes ? bytes : (size_t)LCQP_JACOBIAN_STAGING_BYTES;
+    SpBatch& d = h->db;
+    float ms = 0.f;
+    if (int rc = sp_sensitivity(h, 1, vx, vy, false, dg, db, side, info, ms)) return rc;
+    const size_t nq = dQx ? (size_t)d.nnzQ : 0, ne = dAx ? (size_t)d.nnzE : 0;
+    if (nq + ne) {
+        if (dAx) if (int rc = sp_value_map(h)) return rc;
+        // (+ 2: both segments start on an even offset)
+        if (int rc = adjoint_chunks(g_sp_err, h, nq + ne, 2, reduce, ms, [&](size_t c0, size_t cb, AdjCopy* cp) {
+            const size_t cq = cb * nq, ce = cb * ne;
+            double *outQ = dQx ? h->sn.adjOut : nullptr, *outE = dAx ? h->sn.adjOut + cq + (cq & 1) : nullptr;
+            int ncp = 0;
+            if (dQx) cp[ncp++] = {dQx + c0 * nq, outQ, cq};
+            if (dAx) cp[ncp++] = {dAx + c0 * ne, outE, ce};
+            sp_launch_adjoint(h, outQ, cq, outE, ce, reduce, (int)c0, (int)cb);
+            return ncp;
+        })) return rc;
+    }
+    h->rs.sensMs = ms;
     return 0;
 }); }
 
-// ---- the device-pointer twins of lcqp_hip_sparse_sensitivity / _adjoint (include/lcqp_hip.h, DESIGN.md section 3a'''''; load, update and
-// get_solution are in lcqp_sparse_device.hip) ----
-// the pointer checks of the two calls: every array with the bytes the call moves
-static bool sp_sens_pointers_ok(lcqp_hip_sparse* h, size_t rows, const double* v, const char* vname, const double* vy, double* dg, double* db, int* side, int* info)
+extern "C" int lcqp_hip_sparse_set_adjoint_staging(lcqp_hip_sparse_t* h, size_t bytes)
 {
-    const SpBatch& d = h->db;
-    return device_pointer_ok(g_sp_err, h, vname, v, sizeof(double) * rows * d.n) && device_pointer_ok(g_sp_err, h, "vy", vy, sizeof(double) * rows * d.m) &&
-           device_pointer_ok(g_sp_err, h, "dg", dg, sizeof(double) * rows * d.n) && device_pointer_ok(g_sp_err, h, "db", db, sizeof(double) * rows * d.m) &&
-           device_pointer_ok(g_sp_err, h, "side", side, sizeof(int) * (size_t)d.B * d.m, 4) && device_pointer_ok(g_sp_err, h, "info", info, sizeof(int) * (size_t)d.B, 4);
+    return guarded(g_sp_err, [&] { return set_staging(h, bytes); });
 }
 
+// ---- the device-pointer twins of lcqp_hip_sparse_sensitivity / _adjoint (include/lcqp_hip.h, DESIGN.md section 3a'''''; load, update and
+// get_solution are in lcqp_sparse_device.hip) ----
 extern "C" int lcqp_hip_sparse_sensitivity_device(lcqp_hip_sparse_t* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info, void* stream)
 { return guarded(g_sp_err, [&] {
     if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
     if (nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
     if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
     HIPCHK(g_sp_err, hipSetDevice(h->device));
-    if (!sp_sens_pointers_ok(h, (size_t)h->db.B * nrhs, v, "v", nullptr, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
-    StreamHandOver over(h, stream);
-    HIPCHK(g_sp_err, over.status);
-    float ms = 0.f;
-    const int rc = sp_sensitivity_launch(h, nrhs, v, nullptr, dg, db, side, info, &ms, true);
-    HIPCHK(g_sp_err, over.done());
-    return rc;
+    if (!sens_pointers_ok(g_sp_err, h, h->db.m, (size_t)h->db.B * nrhs, v, "v", nullptr, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
+    return device_call(g_sp_err, h, stream, [&] {
+        float ms = 0.f;
+        return sp_sensitivity(h, nrhs, v, nullptr, true, dg, db, side, info, ms);
+    });
 }); }
 
-// k_sparse_sensitivity as sp_adjoint launches it, then ONE launch of k_sparse_adjoint_nnz over the whole batch (or k_sparse_adjoint_reduce) that
-// writes the caller's arrays: no staging buffer, no chunks.  The terms are those of sp_adjoint_q / sp_adjoint_e: the host call's bits.
+// k_sparse_sensitivity as the host call launches it, then ONE launch of k_sparse_adjoint_nnz over the whole batch (or k_sparse_adjoint_reduce)
+// that writes the caller's arrays: no staging buffer, no chunks.  The terms are those of sp_adjoint_q / sp_adjoint_e: the host call's bits.
 extern "C" int lcqp_hip_sparse_adjoint_device(lcqp_hip_sparse_t* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
                                               int reduce, double* dQx, double* dAx, void* stream)
 { return guarded(g_sp_err, [&] {
@@ -700,28 +615,16 @@ extern "C" int lcqp_hip_sparse_adjoint_device(lcqp_hip_sparse_t* h, const double
     if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
     HIPCHK(g_sp_err, hipSetDevice(h->device));
     SpBatch& d = h->db;
-    if (!sp_sens_pointers_ok(h, d.B, vx, "vx", vy, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
+    if (!sens_pointers_ok(g_sp_err, h, d.m, d.B, vx, "vx", vy, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
     const size_t lead = reduce ? (size_t)1 : (size_t)d.B, cq = dQx ? lead * d.nnzQ : 0, ce = dAx ? lead * d.nnzE : 0;
     if (!device_pointer_ok(g_sp_err, h, "dQx", dQx, sizeof(double) * cq, 16) || !device_pointer_ok(g_sp_err, h, "dAx", dAx, sizeof(double) * ce)) return LCQP_INVALID_ARGUMENT;
     if (dAx) if (int rc = sp_value_map(h)) return rc;
-    if (cq + ce) for (hipError_t e : {h->adjEv0.status, h->adjEv1.status}) if (e != hipSuccess) return hip_fail(g_sp_err, "hipEventCreate", e);
-    StreamHandOver over(h, stream);
-    HIPCHK(g_sp_err, over.status);
-    float ms = 0.f;
-    if (int rc = sp_sensitivity_launch(h, 1, vx, vy, dg, db, side, info, &ms, true)) { (void)over.done(); return rc; }
-    if (cq + ce) {
-        const SensBuffers& sb = h->sens;
-        const SpAdjointArgs a = {d.B, d.n, d.m, d.nnzQ, d.nnzE, d.xout, d.yout, sb.dg, sb.db, sb.side, sb.info, d.Qp, d.Qi, d.Erow, d.Ei, h->valMap, dQx, dAx};
-        const unsigned gx = (unsigned)std::min<size_t>((std::max((cq + 1) / 2, ce) + SP_ADJ_WG - 1) / SP_ADJ_WG, 65535);
-        HIPCHK(g_sp_err, hipEventRecord(h->adjEv0, h->stream));
-        if (reduce) hipLaunchKernelGGL(k_sparse_adjoint_reduce, dim3(gx, 2), dim3(SP_ADJ_WG), 0, h->stream, a);
-        else hipLaunchKernelGGL(k_sparse_adjoint_nnz, dim3(gx, 2), dim3(SP_ADJ_WG), 0, h->stream, a, 0, d.B);
-        HIPCHK(g_sp_err, hipGetLastError());
-        HIPCHK(g_sp_err, hipEventRecord(h->adjEv1, h->stream));
-        h->sensPending |= 4;
-    }
-    HIPCHK(g_sp_err, over.done());
-    return 0;
+    return device_call(g_sp_err, h, stream, [&] {
+        float ms = 0.f;
+        if (int rc = sp_sensitivity(h, 1, vx, vy, true, dg, db, side, info, ms)) return rc;
+        if (!(cq + ce)) return 0;
+        return adjoint_device(g_sp_err, h, [&] { sp_launch_adjoint(h, dQx, cq, dAx, ce, reduce, 0, d.B); });
+    });
 }); }
 
 // ---- test and diagnostic entry point: the KKT factorisations and solves of every instance held against a plain reference (k_sparse_kkt_probe) ----
@@ -762,23 +665,10 @@ extern "C" int lcqp_hip_sparse_kkt_probe(lcqp_hip_sparse_t* h, int mode, int whi
     return 0;
 }); }
 
-// (after a device-pointer call the time is still in the events: wait for them and form it)
 extern "C" int lcqp_hip_sparse_sensitivity_timing(lcqp_hip_sparse_t* h, float* kernel_ms)
-{ return guarded(g_sp_err, [&] {
-    if (h && h->sensPending) {
-        HIPCHK(g_sp_err, hipSetDevice(h->device));
-        float t = 0.f, ta = 0.f;
-        HIPCHK(g_sp_err, hipEventSynchronize(h->sens.ev1));
-        HIPCHK(g_sp_err, hipEventElapsedTime(&t, h->sens.ev0, h->sens.ev1));
-        if (h->sensPending & 4) {
-            HIPCHK(g_sp_err, hipEventSynchronize(h->adjEv1));
-            HIPCHK(g_sp_err, hipEventElapsedTime(&ta, h->adjEv0, h->adjEv1));
-        }
-        h->rs.sensMs = t + ta;
-        h->sensPending = 0;
-    }
-    return sensitivity_timing(h, kernel_ms);
-}); }
+{
+    return guarded(g_sp_err, [&] { return sensitivity_timing(g_sp_err, h, kernel_ms); });
+}
 
 extern "C" int lcqp_hip_sparse_synchronize(lcqp_hip_sparse_t* h)
 {

@@ -206,6 +206,38 @@ def test_jacobian(hip, key):
             assert np.array_equal(part, full[:c["nj"]])
 
 
+def test_jacobian_fallback_sub_range_and_column_chunks(hip):
+    """np = 1024 has no blocked kernel: the Jacobian is the vector kernel on uploaded unit vectors, in chunks of columns under the staging
+    cap, on the whole batch, with the range copied out.  The smallest shape that takes this route, held to the cases the sparse arm's general
+    LDL' is held to: a sub-range, several column chunks with a partial last one, and the bits of sensitivity(identity).  The vector kernel
+    treats the columns of a call independently, so every comparison is bit for bit: the host code from before the two arms shared it gave equal
+    bits at np = 1024 in all four comparisons, so np.array_equal is asserted and not the bound of test_jacobian."""
+    n, nC, nComp, B = 520, 40, 10, 3
+    nd = n + nC + 2 * nComp
+    ds = [random_lcqp(np.random.default_rng(1000 + b), n, nC, nComp, False, False) for b in range(B)]
+    bt = hip.BatchLCQP(B, n, nC, nComp, opt=hip.default_options(perturbStep=0))
+    load_all(bt, ds)
+    bt.run()
+    st = bt.solution()[2]
+    su = bt.read_setup(0)
+    assert su["np"] == 1024 and all(s["returnValue"] == 0 for s in st)
+    counts = bt.launch_counts()
+    full = bt.jacobian()
+    part = bt.jacobian(first=1, count=2)
+    cap = 200 * 8 * B * (n + su["np"] + nd + su["capS"])      # 200 unit vectors per launch: column chunks of 200, 200 and 120
+    chunked = bt.jacobian(_staging_bytes=cap)
+    one = bt.jacobian(first=2, count=1, _staging_bytes=cap + 8)      # (a cap between two multiples rounds down to the same chunks)
+    eye = bt.sensitivity(np.ascontiguousarray(np.broadcast_to(np.eye(n), (B, n, n))))
+    assert bt.launch_counts() == counts
+    bt.close()
+    assert full[0].shape == (B, n, n) and full[1].shape == (B, n, nd) and not np.any(full[3] & 1)
+    for name, f, p, c, o, e in zip(("Jg", "Jb", "side", "info"), full, part, chunked, one, eye):
+        differ = [int(np.sum(f[1:3] != p)), int(np.sum(f != c)), int(np.sum(f[2:3] != o)), int(np.sum(f != e))]
+        print(f"  {name}: entries that differ from jacobian(): sub-range {differ[0]}, column chunks {differ[1]}, both {differ[2]}, sensitivity(identity) {differ[3]}")
+        assert np.array_equal(p, f[1:3]) and np.array_equal(c, f) and np.array_equal(o, f[2:3]) and np.array_equal(e, f)
+    assert all(np.any(full[0][b] != 0.0) for b in range(B))
+
+
 def test_jacobian_in_chunks_over_a_large_batch(hip):
     c = solved_case("many")
     import lcqpow_amd as hip_
