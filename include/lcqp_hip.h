@@ -458,11 +458,25 @@ int  lcqp_hip_sparse_sensitivity_timing(lcqp_hip_sparse_t* s, float* kernel_ms);
  * last bits differ); within this entry point a vector's result does not depend on the other vectors of the call or on its place among
  * them, bit for bit.  side and info are those of lcqp_hip_sparse_sensitivity.  The staging
  * on the device is bounded as for lcqp_hip_sparse_jacobian.
- * The general sparse LDL' (lcqp_hip_sparse_fronts(s) > 0) has no panel kernel: there lcqp_hip_sparse_sens_panel returns 0, and this entry
- * point launches k_sparse_sensitivity and returns the bits of lcqp_hip_sparse_sensitivity. */
+ * The general sparse LDL' (lcqp_hip_sparse_fronts(s) > 0) has a panel kernel of its own, k_sparse_sensitivity_blk_general, behind a switch
+ * of the handle that is OFF by default (lcqp_hip_sparse_set_general_panel): without it lcqp_hip_sparse_sens_panel returns 0 there, and this
+ * entry point launches k_sparse_sensitivity and returns the bits of lcqp_hip_sparse_sensitivity. */
 #define LCQP_SPARSE_SENS_PANEL 8
-/* the panel width this handle's engine uses; 0 where the two entry points fall back to the vector kernel (NULL handle: 0) */
+/* the panel width this handle's engine uses; 0 where the two entry points fall back to the vector kernel -- the general sparse LDL' of a
+ * handle that has not switched its panel form on (NULL handle: 0) */
 int  lcqp_hip_sparse_sens_panel(const lcqp_hip_sparse_t* s);
+/* The panel form of the general sparse LDL' (DESIGN.md section 3a''', "The general engine"), per handle, off by default.  on = 1: on a
+ * handle of the general engine lcqp_hip_sparse_sens_panel returns the panel width, and lcqp_hip_sparse_sensitivity_blocked and
+ * lcqp_hip_sparse_jacobian go through the (instance, panel) work items of the band engines -- chunks under the staging cap, unit vectors
+ * generated on the device, a sub-range at the cost of its own items -- with a panel sweep over the fronts as the solve.  Per column the
+ * results equal the vector kernel's to rounding, not to the bit; within the panel form a column's result depends on nothing but that
+ * column, bit for bit.  on = 0: the vector kernel again, and its bits.  A handle of a band engine accepts the call, and nothing changes.
+ * The call makes no device call and touches neither the setup, nor the mark of the last solve, nor the stored solution.
+ * LCQP_INVALID_ARGUMENT: NULL handle, or on outside 0 / 1. */
+int  lcqp_hip_sparse_set_general_panel(lcqp_hip_sparse_t* s, int on);
+/* the largest front (pivots + update rows) of the handle's general sparse LDL': which classes of the sweeps run (<= 64, <= 256, larger);
+ * 0: a band engine (NULL handle: -1) */
+int  lcqp_hip_sparse_max_front(const lcqp_hip_sparse_t* s);
 int  lcqp_hip_sparse_sensitivity_blocked(lcqp_hip_sparse_t* s, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
 /* The full solution Jacobians of the instances [first, first + count): the panel kernel on the unit vectors, which it writes into its solve
  * panels on the device (nothing is uploaded).
@@ -473,7 +487,7 @@ int  lcqp_hip_sparse_sensitivity_blocked(lcqp_hip_sparse_t* s, int nrhs, const d
  * The staging on the device (outputs and workspaces of the work items in flight) is bounded by the cap of
  * lcqp_hip_sparse_set_adjoint_staging, which governs the adjoint's chunks and these: the call loops over chunks of whole (instance, panel)
  * items, at least one per chunk -- a chunk may split an instance by columns --, one launch and one download per chunk; the results do not
- * depend on the chunking, bit for bit.  General sparse LDL': k_sparse_sensitivity on uploaded unit vectors, in chunks of columns under the
+ * depend on the chunking, bit for bit.  General sparse LDL' without lcqp_hip_sparse_set_general_panel: k_sparse_sensitivity on uploaded unit vectors, in chunks of columns under the
  * same cap; a sub-range then costs the launches of the whole batch (the vector kernel has no instance offset).
  * Both calls are synchronous on return, change nothing a run / resolve reads and leave lcqp_hip_sparse_launch_counts alone.
  * LCQP_INVALID_ARGUMENT: NULL handle or Jg, first < 0, count < 1, first + count > B.  Then LCQP_LCQPOBJECT_NOT_SETUP as

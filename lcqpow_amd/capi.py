@@ -179,6 +179,8 @@ def lib():
         L.lcqp_hip_sparse_sensitivity.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_sparse_sensitivity_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.lcqp_hip_sparse_sens_panel.argtypes = [C.c_void_p]
+        L.lcqp_hip_sparse_set_general_panel.argtypes = [C.c_void_p, C.c_int]
+        L.lcqp_hip_sparse_max_front.argtypes = [C.c_void_p]
         L.lcqp_hip_sparse_sensitivity_blocked.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_sparse_jacobian.argtypes = [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_sparse_adjoint.argtypes = [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p, C.c_int] + [c_double_p] * 2
@@ -1040,8 +1042,21 @@ class SparseBatchLCQP(_Batch):
 
     def sens_panel(self):
         """lcqp_hip_sparse_sens_panel: columns per panel of k_sparse_sensitivity_blk on this handle's engine; 0 where sensitivity_blocked()
-        and jacobian() run the vector kernel (the general sparse LDL')"""
+        and jacobian() run the vector kernel (the general sparse LDL' before set_general_panel())"""
         return lib().lcqp_hip_sparse_sens_panel(self.h)
+
+    def set_general_panel(self, on=True):
+        """lcqp_hip_sparse_set_general_panel: on a handle of the general sparse LDL', sensitivity_blocked() and jacobian() through the panel
+        kernel of that engine (off by default: the vector kernel and its bits).  No effect on a band engine.  Costs nothing and changes
+        nothing on the device."""
+        rc = lib().lcqp_hip_sparse_set_general_panel(self.h, int(on))
+        if rc:
+            raise ValueError(f"lcqp_hip_sparse_set_general_panel({on!r}) returned {rc}")
+        return self
+
+    def max_front(self):
+        """lcqp_hip_sparse_max_front: the largest front of the general sparse LDL' (0: a band engine)"""
+        return lib().lcqp_hip_sparse_max_front(self.h)
 
     def sensitivity_blocked(self, v):
         """lcqp_hip_sparse_sensitivity_blocked: sensitivity(v) -- the same arguments and results -- through the kernel that takes the k vectors

@@ -287,8 +287,9 @@ __global__ __launch_bounds__(WGS) void k_sparse_sensitivity(SpBatch db, int nrhs
 // side is written by the item of panel 0; the flags are OR-ed into info (integer atomicOr: the order does not matter) -- 2 by any item with
 // a stalled column, 4 and 8 by the item of panel 0, 1 by every item of an unsolved instance, whose outputs are zero.
 // unit: column j of the call is e_j, written into the solve panel by the kernel itself; v is not read.
-// Band engines only (plain and bordered): the host never launches it on the general LDL' (lcqp_sparse_host.hip).
+// Band engines (plain and bordered); the general LDL' has the same body under k_sparse_sensitivity_blk_general below.
 constexpr int sens_panel_width(int G) { return LCQP_SPARSE_SENS_PANEL; }      // per lane width; 4 where 8 would need scratch
+constexpr int general_panel_width() { return LCQP_SPARSE_SENS_PANEL; }        // the general LDL' (sp_general_front_panel): all three front classes
 
 // g_ell's sums for the P columns of a panel behind one pass over the matrix values: per column the W slab entries in order (an absent one
 // adds 0 * 0), then the tail of a long row.  xv(j, k): entry j of column k of the gathered panel; out(i, s): the P sums of row i.
@@ -322,10 +323,12 @@ __device__ __forceinline__ void sp_ell_panel(const EllMat& E, int gl, GD vals, X
     }
 }
 
-template <int G>
-__global__ __launch_bounds__(WGS) void k_sparse_sensitivity_blk(SpBatch db, SpSensBlkArgs a)
+// GENERAL (G = 64 only): the solve is the general LDL's panel form, sp_general_solve_panel; everything else is the same code.
+template <int G, bool GENERAL>
+__device__ __forceinline__ void sp_sensitivity_blk(const SpBatch& db, const SpSensBlkArgs& a)
 {
-    constexpr int P = sens_panel_width(G), IPW = 64 / G;
+    static_assert(!GENERAL || G == 64, "the general LDL' runs one wavefront per instance");
+    constexpr int P = GENERAL ? general_panel_width() : sens_panel_width(G), IPW = 64 / G;
     const int li = blockIdx.x * IPW + threadIdx.x / G;      // item of this launch
     if (li >= a.nItems) return;
     const int item = a.item0 + li, ir = item / a.npan, pan = item - ir * a.npan, b = a.first + ir;
@@ -381,7 +384,8 @@ __global__ __launch_bounds__(WGS) void k_sparse_sensitivity_blk(SpBatch db, SpSe
             }
     };
     for (int it = 0; act; it++) {
-        sp_solve_panel<G, P>(c, bv);
+        if constexpr (GENERAL) sp_general_solve_panel<P>(c, bv);
+        else sp_solve_panel<G, P>(c, bv);
         double dm[P], mx[P], sc[P];
 #pragma unroll
         for (int k = 0; k < P; k++) dm[k] = mx[k] = sc[k] = 0.0;
@@ -449,6 +453,22 @@ __global__ __launch_bounds__(WGS) void k_sparse_sensitivity_blk(SpBatch db, SpSe
     }
     if (t == 0 && stalled) atomicOr(a.info + ir, 2);
 }
+
+template <int G>
+__global__ __launch_bounds__(WGS) void k_sparse_sensitivity_blk(SpBatch db, SpSensBlkArgs a)
+{
+    sp_sensitivity_blk<G, false>(db, a);
+}
+
+// k_sparse_sensitivity_blk on the general LDL' (DESIGN.md section 3a''', "The general engine"): one wavefront per (instance, panel) work
+// item, the same body with sp_general_solve_panel as its solve.  The panel sweeps hold their right-hand sides in registers: no LDS.
+// Launched only for a handle that switched the panel form on (lcqp_hip_sparse_set_general_panel).  Compiled into the unit of G = 64 alone.
+#if LCQP_TU_G == 64
+__global__ __launch_bounds__(WGS) void k_sparse_sensitivity_blk_general(SpBatch db, SpSensBlkArgs a)
+{
+    sp_sensitivity_blk<64, true>(db, a);
+}
+#endif
 
 // ---- k_sparse_kkt_probe: test and diagnostic kernel (lcqp_hip_sparse_kkt_probe) -- the factorisation engines and sp_solve held to a plain
 // reference, one solve per right-hand side, no refinement (tests/test_gpu_sparse_factor.py) ------------------------------------------------
@@ -791,6 +811,14 @@ static void sp_launch_sensitivity_blk(const SpBatch& db, hipStream_t stream, con
     hipLaunchKernelGGL(k_sparse_sensitivity_blk<G>, dim3(grid), dim3(WGS), 0, stream, db, a);
 }
 
+// one launch of k_sparse_sensitivity_blk_general: a wavefront per work item, no LDS
+static void sp_launch_sensitivity_blk_general(const SpBatch& db, hipStream_t stream, const SpSensBlkArgs& a)
+{
+#if LCQP_TU_G == 64
+    hipLaunchKernelGGL(k_sparse_sensitivity_blk_general, dim3(a.nItems), dim3(WGS), 0, stream, db, a);
+#endif
+}
+
 // one launch of k_sparse_kkt_probe<G> on device buffers; the LDS of a factorisation (sp_launch), which covers the window of the general solve
 template <int G>
 static void sp_launch_kkt_probe(const SpBatch& db, hipStream_t stream, int mode, int which, int nrhs, const double* dprim, const double* ddual, const int* use,
@@ -809,7 +837,8 @@ template <int G>
 const SpKernels& sparse_kernels()
 {
     static const SpKernels k = {G, sp_launch<G>, sp_launch_sensitivity<G>, sp_launch_sensitivity_dual<G>, sp_launch_kkt_probe<G>,
-                                sp_launch_sensitivity_blk<G>, sens_panel_width(G)};
+                                sp_launch_sensitivity_blk<G>, sens_panel_width(G),
+                                G == 64 ? sp_launch_sensitivity_blk_general : nullptr, G == 64 ? general_panel_width() : 0};
     return k;
 }
 }

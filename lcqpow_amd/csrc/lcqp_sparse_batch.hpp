@@ -30,6 +30,7 @@ struct lcqp_hip_sparse {
     std::vector<int> qdiagHost;    // entry of Q_ii in the value array
     std::vector<double> diagRatio; // per instance: min_i Q_ii / max_i Q_ii of the loaded Hessian (1: not loaded yet)
     bool loaded = false, ran = false;
+    bool generalPanel = false;     // lcqp_hip_sparse_set_general_panel: many-vector derivatives of the general LDL' through its panel kernel
     // re-solves (lcqp_host_rt.hpp) and sensitivities (lcqp_sens_rt.hpp).  This arm has no setup without a solve: setupValid and solved go
     // together; rhoStart is allocated by the first resolve that carries penalties
     lcqp_rt::ResolveState rs;

@@ -845,8 +845,8 @@ __device__ __forceinline__ void band_sweep_panel(GD K, GD Kd, GD b, int Np, int 
     }
 }
 
-// the polish factor on a panel (the band engines only: the general LDL' has no panel form).  Reads the factor and the
-// border; writes the panel alone -- no counter of the context, nothing of the instance.
+// the polish factor on a panel, band engines (the general LDL' has its own panel form: sp_general_solve_panel below).  Reads the factor and
+// the border; writes the panel alone -- no counter of the context, nothing of the instance.
 template <int G, int P>
 __device__ __forceinline__ void sp_solve_band_panel(SpCtx<G>& c, GD b)
 {
@@ -903,6 +903,143 @@ __device__ __forceinline__ void sp_solve_panel(SpCtx<G>& c, GD b)
 {
     sp_solve_band_panel<G, P>(c, b);
     if (c.db->kb > 0) sp_border_solve_panel<G, P>(c, b);
+}
+
+// ---- the general LDL' on a panel (k_sparse_sensitivity_blk_general, DESIGN.md section 3a''', "The general engine") ------------------------
+// One front of sp_general_sweep for P right-hand sides, interleaved as above.  Lane t holds rows t, t + 64, ... of the front, QR of them, the
+// P values of a row in P registers: a pivot step is one coefficient per held row (read from the factor exactly as the vector sweep reads it,
+// U pivots' worth in flight), P broadcasts and P fused multiply-adds per held row -- P independent chains behind every coefficient.  The
+// front is walked by chunks of 64 rows with the chunk number a compile-time constant, so the register a pivot is broadcast from is fixed by
+// the code, and the rows of the chunks a pivot cannot reach (above it forward, below it backward) are not touched.  All three front classes
+// are this one routine: QR = 1 (ff <= 64), 4 (ff <= 256), 9 (ff <= GEN_MAX_FRONT); the right-hand sides of the largest class live in
+// registers too (72 doubles per lane), so the routine uses no LDS.  Axpy form both ways, as the vector sweep.
+// Per column the operations are: x_i -= l_ij y_j for the pivots j in ascending (forward) or the rows i in descending (backward) order --
+// whatever the column's place in the panel, whatever its neighbours hold.  A zero column stays zero.
+template <int P, int QR, int U, bool FWD>
+__device__ __forceinline__ void sp_general_front_panel(GD Lp, GD b, const int* rows, int np, int ff, int piv0, int t)
+{
+    static_assert(P % 2 == 0, "the panel is moved in pairs of doubles");
+    double x[QR][P];
+#pragma unroll
+    for (int q = 0; q < QR; q++) {
+        const int i = t + 64 * q;
+        if (i < ff) {
+            const int pos = i < np ? piv0 + i : rows[i - np];
+#pragma unroll
+            for (int k = 0; k < P / 2; k++) { const dv2 v = b.ld2(pos * P + 2 * k); x[q][2 * k] = v.x; x[q][2 * k + 1] = v.y; }
+        } else {
+#pragma unroll
+            for (int k = 0; k < P; k++) x[q][k] = 0.0;
+        }
+    }
+    if (FWD) {
+#pragma unroll
+        for (int qp = 0; qp < QR; qp++) {      // the pivots of chunk qp: they live in x[qp], and reach the rows of the chunks qp .. QR-1
+            const int je = min(np, 64 * qp + 64);
+            for (int j0 = 64 * qp; j0 < je; j0 += U) {
+                double lv[U][QR];
+#pragma unroll
+                for (int u = 0; u < U; u++)
+#pragma unroll
+                    for (int q = 0; q < QR; q++)
+                        if (q >= qp) { const int j = j0 + u, i = t + 64 * q; lv[u][q] = (j < je && i > j && i < ff) ? (double)Lp[i + ff * j] : 0.0; }
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const int j = j0 + u;
+                    if (j < je) {
+                        double y[P];
+#pragma unroll
+                        for (int k = 0; k < P; k++) y[k] = wave_bcast(x[qp][k], j - 64 * qp);
+#pragma unroll
+                        for (int q = 0; q < QR; q++)
+                            if (q >= qp) {
+#pragma unroll
+                                for (int k = 0; k < P; k++) x[q][k] -= lv[u][q] * y[k];
+                            }
+                    }
+                }
+            }
+        }
+    } else {
+#pragma unroll
+        for (int qq = 0; qq < QR; qq++) {      // the rows of chunk qi, last chunk first: they live in x[qi], and reach the pivots of the chunks 0 .. qi
+            const int qi = QR - 1 - qq;
+            const int ihi = min(ff - 1, 64 * qi + 63), ilo = max(1, 64 * qi);
+            for (int i0 = ihi; i0 >= ilo; i0 -= U) {
+                double lv[U][QR];
+#pragma unroll
+                for (int u = 0; u < U; u++)
+#pragma unroll
+                    for (int q = 0; q < QR; q++)
+                        if (q <= qi) { const int i = i0 - u, j = t + 64 * q; lv[u][q] = (i >= ilo && j < i && j < np) ? (double)Lp[i + ff * j] : 0.0; }
+#pragma unroll
+                for (int u = 0; u < U; u++) {
+                    const int i = i0 - u;
+                    if (i >= ilo) {
+                        double y[P];
+#pragma unroll
+                        for (int k = 0; k < P; k++) y[k] = wave_bcast(x[qi][k], i - 64 * qi);
+#pragma unroll
+                        for (int q = 0; q < QR; q++)
+                            if (q <= qi) {
+#pragma unroll
+                                for (int k = 0; k < P; k++) x[q][k] -= lv[u][q] * y[k];
+                            }
+                    }
+                }
+            }
+        }
+    }
+    // forward: the pivots and the update rows go back; backward: the pivots alone (the rows behind them belong to the ancestors)
+#pragma unroll
+    for (int q = 0; q < QR; q++) {
+        const int i = t + 64 * q;
+        if (i < (FWD ? ff : np)) {
+            const int pos = i < np ? piv0 + i : rows[i - np];
+#pragma unroll
+            for (int k = 0; k < P; k++) b[pos * P + k] = x[q][k];
+        }
+    }
+}
+
+// sp_general_sweep for a panel: the fronts in postorder (forward) or in reverse (backward), each by the class of its size
+template <int P, bool FWD>
+__device__ __forceinline__ void sp_general_sweep_panel(SpCtx<64>& c, GD Lst, GD b)
+{
+    const SpBatch& db = *c.db;
+    const int t = here(c.gl);
+    static_assert(GEN_MAX_FRONT <= 9 * 64, "the largest class holds nine rows per lane");
+    for (int q = 0; q < db.gnF; q++) {
+        const int f = FWD ? q : db.gnF - 1 - q;
+        const int* mt = db.gMeta + (size_t)f * GEN_META;
+        const int np = mt[0], nb = mt[1], ff = np + nb, piv0 = mt[2];
+        const int* rows = db.gRows + mt[3];
+        GD Lp = Lst + mt[8];
+        if (ff <= 64) sp_general_front_panel<P, 1, 8, FWD>(Lp, b, rows, np, ff, piv0, t);
+        else if (ff <= 256) sp_general_front_panel<P, 4, 4, FWD>(Lp, b, rows, np, ff, piv0, t);
+        else sp_general_front_panel<P, 9, 2, FWD>(Lp, b, rows, np, ff, piv0, t);
+        g_sync();      // the update rows a front wrote are read by other lanes in its parent
+    }
+}
+
+// sp_general_solve on a panel, for the polish factor: forward, 1 / D per position for all P columns, backward.  Reads the factor, 1 / D,
+// gMeta and gRows; writes the panel alone -- no counter of the context, nothing of the instance (no gStack, no gFront, no LDS).
+template <int P>
+__device__ __forceinline__ void sp_general_solve_panel(SpCtx<64>& c, GD b)
+{
+    const SpBatch& db = *c.db;
+    sp_general_sweep_panel<P, true>(c, c.KF(false), b);
+    {
+        GD Kd = c.KD(false);
+        const int t = here(c.gl);
+        for (int p = t; p < db.N; p += 64) {
+            const double dinv = Kd[p];
+#pragma unroll
+            for (int k = 0; k < P / 2; k++) { const dv2 v = b.ld2(p * P + 2 * k); b[p * P + 2 * k] = v.x * dinv; b[p * P + 2 * k + 1] = v.y * dinv; }
+        }
+        g_sync();
+    }
+    sp_general_sweep_panel<P, false>(c, c.KF(false), b);
 }
 
 }  // namespace

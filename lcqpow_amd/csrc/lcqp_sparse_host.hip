@@ -475,9 +475,22 @@ extern "C" int lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* h, int nrhs, const
 
 // ---- panels of vectors and full Jacobians (DESIGN.md section 3a''', "The sparse arm"): k_sparse_sensitivity_blk on the work items
 // (instance, panel) of the call, in chunks under the staging cap ----
-// the panel width of the handle's engine; 0: the general LDL', which both entry points run on the vector kernel
-static int sp_panel(const lcqp_hip_sparse* h) { return h->db.general ? 0 : sp_kernels(h->db.G)->panel; }
+// the panel width of the handle's engine; 0: the general LDL' without its switch (lcqp_hip_sparse_set_general_panel), which both entry
+// points then run on the vector kernel
+static int sp_panel(const lcqp_hip_sparse* h)
+{
+    const SpKernels* k = sp_kernels(h->db.G);
+    return h->db.general ? (h->generalPanel ? k->panel_general : 0) : k->panel;
+}
 extern "C" int lcqp_hip_sparse_sens_panel(const lcqp_hip_sparse_t* h) { return h ? sp_panel(h) : 0; }
+// the switch is a member of the handle and nothing else: no device call, no mark of the setup or the solution is touched
+extern "C" int lcqp_hip_sparse_set_general_panel(lcqp_hip_sparse_t* h, int on)
+{
+    if (!h || (on != 0 && on != 1)) return LCQP_INVALID_ARGUMENT;
+    h->generalPanel = on == 1;
+    return 0;
+}
+extern "C" int lcqp_hip_sparse_max_front(const lcqp_hip_sparse_t* h) { return h ? (h->db.general ? h->db.gMaxFront : 0) : -1; }
 
 // Instances [first, first + count), ncols columns each: v [count][ncols][n] on the host, or NULL = the unit vectors (ncols = n).  dg
 // [count][ncols][n], db [count][ncols][m], side [count][m], info [count] on the host.  One launch and one download per chunk of items; an item's
@@ -488,7 +501,8 @@ static int sp_panel_run(lcqp_hip_sparse* h, int first, int count, int ncols, con
     SpBatch& d = h->db;
     SensBuffers& sb = h->sn.sens;
     const size_t P = sp_panel(h), n = d.n, m = d.m, npan = ((size_t)ncols + P - 1) / P, nItems = (size_t)count * npan;
-    const size_t wsItem = sens_blk_ws_doubles(d, (int)P);
+    const size_t wsItem = sens_blk_ws_doubles(d, (int)P);      // (the general LDL': Np >= N = n + m positions in the ordering of the fronts)
+    SpSensitivityBlkFn* const launch = d.general ? sp_kernels(d.G)->sensitivity_blk_general : sp_kernels(d.G)->sensitivity_blk;
     const size_t chunk = staging_chunk(h->sn.staging, sizeof(double) * (P * (n + m) + wsItem), nItems);
     HIPCHK(g_sp_err, hipSetDevice(h->device));
     const size_t vrows = v ? (size_t)count * ncols : 0;
@@ -502,7 +516,7 @@ static int sp_panel_run(lcqp_hip_sparse* h, int first, int count, int ncols, con
     for (size_t i0 = 0; i0 < nItems; i0 += chunk) {
         const size_t ni = std::min(chunk, nItems - i0);
         const SpSensBlkArgs a = {first, (int)npan, ncols, v ? 0 : 1, (int)i0, (int)ni, sb.v, sb.dg, sb.db, sb.side, sb.info, sb.ws};
-        if (int rc = timed_launch(g_sp_err, h->stream, sb.ev0, sb.ev1, [&] { sp_kernels(d.G)->sensitivity_blk(d, h->stream, a); })) return rc;
+        if (int rc = timed_launch(g_sp_err, h->stream, sb.ev0, sb.ev1, [&] { launch(d, h->stream, a); })) return rc;
         HIPCHK(g_sp_err, hipMemcpyAsync(hg.data(), sb.dg, sizeof(double) * ni * P * n, hipMemcpyDeviceToHost, h->stream));
         if (db) HIPCHK(g_sp_err, hipMemcpyAsync(hb.data(), sb.db, sizeof(double) * ni * P * m, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));
@@ -535,7 +549,7 @@ extern "C" int lcqp_hip_sparse_jacobian(lcqp_hip_sparse_t* h, int first, int cou
     if (!h || !Jg || first < 0 || count < 1 || (long long)first + count > h->db.B) return LCQP_INVALID_ARGUMENT;
     if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
     if (sp_panel(h)) return sp_panel_run(h, first, count, h->db.n, nullptr, Jg, Jb, side, info);
-    // the general LDL': k_sparse_sensitivity on uploaded unit vectors; the staging of a column is v, dg and db of the whole batch
+    // the general LDL' without its panel form: k_sparse_sensitivity on uploaded unit vectors; the staging of a column is v, dg and db of the whole batch
     const size_t B = h->db.B, n = h->db.n, m = h->db.m;
     return jacobian_by_vectors(h, sizeof(double) * B * (2 * n + m), m, first, count, Jg, Jb, side, info,
                                [&](int nc, const double* v, double* dg, double* db, int* sd, int* in, float& ms) {

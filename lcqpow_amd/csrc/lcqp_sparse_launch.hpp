@@ -151,8 +151,9 @@ using SpSensitivityBlkFn = void(const SpBatch& db, hipStream_t stream, const SpS
 // doubles of workspace per work item: the solve panel [Np], d and Q d [n], lambda [m], interleaved by column
 __host__ __device__ inline size_t sens_blk_ws_doubles(const SpBatch& db, int panel) { return (size_t)panel * ((size_t)db.Np + 2 * (size_t)db.n + db.m); }
 // panel: the panel width of this lane width's k_sparse_sensitivity_blk (0: the width is routed to the vector kernel)
+// sensitivity_blk_general, panel_general: k_sparse_sensitivity_blk_general and its panel width -- the unit of G = 64 alone, null / 0 elsewhere
 struct SpKernels { int G; SpRunFn* run; SpSensitivityFn* sensitivity; SpSensitivityDualFn* sensitivity_dual; SpKktProbeFn* kkt_probe;
-                   SpSensitivityBlkFn* sensitivity_blk; int panel; };
+                   SpSensitivityBlkFn* sensitivity_blk; int panel; SpSensitivityBlkFn* sensitivity_blk_general; int panel_general; };
 // defined in lcqp_sparse.hip and instantiated there for G = LCQP_TU_G
 template <int G> const SpKernels& sparse_kernels();
 #pragma GCC visibility pop

@@ -473,12 +473,16 @@ class SparseBatchLCQPLayer(BatchLCQPLayer):
     sparse = True
     bound_keys = tuple(k for k in BOUND_KEYS if k not in ("lb", "ub"))
 
-    def __init__(self, batch, bounds=None, warm=True, values=None):
-        """values: dict(Qx=[B][nnzQ], Ax=[B][nnzA]) (or [nnz], shared) -- the value arrays the batch was loaded with.  A layer whose solve()
+    def __init__(self, batch, bounds=None, warm=True, values=None, general_panel=None):
+        """general_panel: True / False is handed to batch.set_general_panel -- jacobian() of a batch on the general sparse LDL' through that
+        engine's panel kernel (None: the handle's setting stays).
+        values: dict(Qx=[B][nnzQ], Ax=[B][nnzA]) (or [nnz], shared) -- the value arrays the batch was loaded with.  A layer whose solve()
         takes Qx or Ax needs them, the way it needs `bounds`: a host load replaces BOTH arrays, and the one that is not an input of the solve
         is handed over again.  The layer keeps them in step with its own loads (after a load on the device path: read back through
         SparseBatchLCQP.read_problem when the host path next needs them)."""
         super().__init__(batch, bounds=bounds, warm=warm)
+        if general_panel is not None:
+            batch.set_general_panel(bool(general_panel))
         self.values = None
         self._values_stale = False
         if values is not None:

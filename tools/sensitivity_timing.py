@@ -29,7 +29,14 @@ call's kernels, k_sparse_sensitivity<G, true> included) and wall clock.
 --sparse --blocked: k_sparse_sensitivity_blk (sb.sensitivity_blocked(V)) beside k_sparse_sensitivity (sb.sensitivity(V)) at nrhs = 64,
 interleaved, and sb.jacobian(), on the sparse synthetic workload (512, 256, 64) on the band engine with B = 1024 (256 with --quick) and
 with B = 4, the few-instances case the (instance, panel) mapping is for.
-    python tools/sensitivity_timing.py --sparse --blocked [--quick] [--log FILE] [--reps 20]"""
+    python tools/sensitivity_timing.py --sparse --blocked [--quick] [--log FILE] [--reps 20]
+
+--sparse --blocked --general-panel: the general LDL' with its panel form off and on (SparseBatchLCQP.set_general_panel) on the SAME handle in
+the same process, the calls interleaved: sensitivity_blocked at nrhs = 64 and jacobian(first=0, count=1) on the grid workload
+(lcqpow_amd/synth_sparse.py::grid_pattern_arrays) at g = 44 (nC = 200, nComp = 300) and g = 128 (bench.py's grid_128), B = 1 and B = 64.
+Off is the vector kernel.  --jac-reps: timed Jacobian calls (default: --reps; after the same 3 warm-up calls; 0 skips them: with the switch
+off a Jacobian is nV launches of the vector kernel over the whole batch -- 16 384 per call at g = 128); --grids, --batches: other sizes.
+    python tools/sensitivity_timing.py --sparse --blocked --general-panel [--grids 44,128] [--batches 1,64] [--jac-reps N] [--log FILE] [--reps 20]"""
 import argparse
 import os
 import sys
@@ -233,6 +240,64 @@ def measure_sparse_blocked(B, n, nC, nK, nrhs, reps, warmup=3):
     return line
 
 
+def measure_general_panel(g, nC, nK, B, nrhs, reps, jac_reps, warmup=3):
+    """the general LDL' on a g x g grid: sensitivity_blocked(V) and jacobian(0, 1) with the panel form off (k_sparse_sensitivity) and on
+    (k_sparse_sensitivity_blk_general), interleaved on one handle; kernel time from HIP events (sensitivity_kernel_ms)"""
+    from lcqpow_amd import synth_sparse as S
+    Qpat, Apat, qo, eo, info = S.grid_pattern_arrays(g, nC, nK)
+    n = g * g
+    sb = la.SparseBatchLCQP(B, n, nC, nK, Qpat, Apat, opt=la.default_options(perturbStep=0, printLevel=0))
+    inst = [S.grid_values(i, info, (qo, eo)) for i in range(B)]
+    st = lambda k: np.stack([d[k] for d in inst])
+    assert sb.load(0, B, st("Qx"), st("g"), st("Ex"), lbA=st("lbA"), ubA=st("ubA")) == 0
+    sb.run()
+    stats = sb.solution()[2]
+    v = np.random.default_rng(0).standard_normal((B, nrhs, n))
+    t = {False: [], True: []}; tj = {False: [], True: []}
+    out = {}
+    for r in range(warmup + reps):
+        for on in (False, True):
+            sb.set_general_panel(on)
+            out[on] = sb.sensitivity_blocked(v)
+            if r >= warmup:
+                t[on].append(sb.sensitivity_kernel_ms())
+    for r in range((warmup + jac_reps) if jac_reps > 0 else 0):
+        for on in (False, True):
+            sb.set_general_panel(on)
+            sb.jacobian(first=0, count=1, bounds=False)
+            if r >= warmup:
+                tj[on].append(sb.sensitivity_kernel_ms())
+    q = lambda ms: (float(np.min(ms)), float(np.median(ms)), float(np.max(ms)))
+    err = float(max(np.abs(out[True][0] - out[False][0]).max(), np.abs(out[True][1] - out[False][1]).max()))
+    line = ("grid %d x %d (n = %d nC = %d nComp = %d) B = %d (general LDL', %d fronts, largest %d, panel %d) nrhs = %d: off (vector kernel) ms min / median / max = "
+            "%.4f / %.4f / %.4f; on (panel kernel) = %.4f / %.4f / %.4f; off / on (medians) = %.2f; us per vector and instance %.3f -> %.3f; "
+            "max |on - off| = %.3g; solved %d, flagged %d"
+            % ((g, g, n, nC, nK, B, sb.fronts(), sb.max_front(), sb.sens_panel(), nrhs) + q(t[False]) + q(t[True])
+               + (np.median(t[False]) / np.median(t[True]), 1e3 * np.median(t[False]) / (B * nrhs), 1e3 * np.median(t[True]) / (B * nrhs), err,
+                  sum(s["returnValue"] == 0 for s in stats), int(np.count_nonzero(out[True][3])))))
+    if jac_reps > 0:
+        line += ("; jacobian(0, 1) (%d columns, %d timed calls): off = %.3f / %.3f / %.3f; on = %.3f / %.3f / %.3f; off / on = %.2f; us per column %.3f -> %.3f"
+                 % ((n, jac_reps) + q(tj[False]) + q(tj[True]) + (np.median(tj[False]) / np.median(tj[True]), 1e3 * np.median(tj[False]) / n, 1e3 * np.median(tj[True]) / n)))
+    sb.close()
+    print(line, flush=True)
+    return line
+
+
+def general_panel_main(a):
+    shape = {44: (200, 300), 128: (800, 1200)}
+    lines = []
+    for g in [int(x) for x in a.grids.split(",")]:
+        nC, nK = shape.get(g, (g * g // 10, g * g // 7))
+        for B in [int(x) for x in a.batches.split(",")]:
+            lines.append(measure_general_panel(g, nC, nK, B, 64, a.reps, a.jac_reps))
+    if a.log:
+        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
+        with open(a.log, "w") as f:
+            f.write("the general LDL' with its panel form off (k_sparse_sensitivity) and on (k_sparse_sensitivity_blk_general), grid workload after run, one handle, "
+                    "calls interleaved; %d timed calls after 3 warm-up calls each\n" % a.reps)
+            f.write("\n".join(lines) + "\n")
+
+
 def sparse_blocked_main(a):
     lines = [measure_sparse_blocked(B, 512, 256, 64, 64, a.reps) for B in ((256, 4) if a.quick else (1024, 4))]
     if a.log:
@@ -299,11 +364,19 @@ def main():
     ap.add_argument("--quick", action="store_true", help="--sparse: without the n = 4096, B = 4096 batch; --blocked: B = 256 at n = 256, without nrhs = 256")
     ap.add_argument("--blocked", action="store_true", help="the blocked kernel beside the vector kernel, and the Jacobian")
     ap.add_argument("--adjoint", action="store_true", help="the matrix gradients summed on the device beside the per-instance path")
+    ap.add_argument("--general-panel", action="store_true", help="--sparse --blocked: the general LDL' with its panel form off and on, on one handle")
+    ap.add_argument("--grids", default="44,128", help="--general-panel: grid sizes")
+    ap.add_argument("--batches", default="1,64", help="--general-panel: batch sizes")
+    ap.add_argument("--jac-reps", type=int, default=None, help="--general-panel: timed jacobian(0, 1) calls per setting (default: --reps; 0: none)")
     a = ap.parse_args()
+    if a.jac_reps is None:
+        a.jac_reps = a.reps
     if la.device_count() < 1:
         raise SystemExit("needs a GPU (no CPU fallback)")
     if a.sparse and a.adjoint:
         return sparse_adjoint_main(a)
+    if a.sparse and a.blocked and a.general_panel:
+        return general_panel_main(a)
     if a.sparse and a.blocked:
         return sparse_blocked_main(a)
     if a.sparse:
