@@ -563,6 +563,29 @@ int  lcqp_hip_sparse_adjoint_device(lcqp_hip_sparse_t* s, const double* vx, cons
  * y0 [m]; hasY0 [1].  LCQP_INVALID_ARGUMENT: NULL handle, or an instance outside the batch. */
 int  lcqp_hip_sparse_read_problem(lcqp_hip_sparse_t* s, int instance, double* Qx, double* Ax, double* g,
                                   double* lE, double* uE, double* lbL, double* lbR, double* x0, double* y0, int* hasY0);
+/* Test and diagnostic entry point (as lcqp_hip_batch_read_admm on the dense arm): the state of the ADMM rounds of one instance as it lies on
+ * the device, so that tests/test_gpu_sparse_admm.py can hold the weights and the iterates to a plain reference.  Host buffers, synchronous,
+ * launches nothing and changes nothing; any output may be NULL.  dims [2]: nV, m = nC + 2 nComp; scal [3]: sigma = admmSigma scale, rho =
+ * admmRho scale, scale = max |Q_ii|; rhov, l, u, ya, za [m] in the row order of [A; L; R]; xa [nV].  The polish writes none of xa, ya, za:
+ * they are those of the last QP that ran ADMM iterations (ya = -y0 at the start of a solve that is given y0).
+ * LCQP_INVALID_ARGUMENT: NULL handle, or an instance outside the batch.  LCQP_LCQPOBJECT_NOT_SETUP: no run / resolve on this handle yet, or a
+ * load / set_options since. */
+int  lcqp_hip_sparse_read_admm(lcqp_hip_sparse_t* s, int instance, int dims[2], double scal[3], double* rhov, double* l, double* u,
+                               double* xa, double* ya, double* za);
+/* Test and diagnostic entry point: the sparse products of the solver (sp_Ex, sp_Qx2, sp_ETy, sp_residual, sp_Cx2, sp_C_from_Ex in
+ * lcqp_sparse_solver.hpp) themselves, applied for every instance of a loaded batch to vectors the caller supplies, so that
+ * tests/test_gpu_sparse_products.py can hold every branch of the ELL-slab gather to a plain reference.  One launch of k_sparse_product_probe
+ * on the handle's stream; the handle is synchronised first, the call is synchronous.  Writes only scratch a run rewrites before it reads it.
+ *   wide  0: the lane group of the handle per instance (lcqp_hip_sparse_lanes); 1: a wavefront per instance, as the streaming phases of a run
+ *   vn    [B][8][nV]  inputs: x of E x | x0, x1 of Q x0, Q x1 | base of base - E'y | g, x of the residual | v0, v1 of C v0, C v1
+ *   vm    [B][4][m]   inputs: y of base - E'y | y of the residual | lx0, lx1 of the two C-from-E-x forms (entries of E v; rows of A unused)
+ *   on    [B][11][nV] outputs: Q x0, Q x1 | base - E'y | r1 = -g - Q x - E'y, Q x | C v0, C v1 | L'R + R'L gathers of (lx0, lx1) |
+ *                     the one-vector form of lx0 and its second sum (zeros)
+ *   om    [B][m]      E x
+ *   os    [B][3]      max |base - E'y|, max |r1|, max_i (|g_i| + |Q x|_i + |E'y|_i) as the routines return them
+ *   ell   [6] or NULL slab width (4 / 8) and tail flag of the row slab of Q, the row slab of E and the column slab of E
+ * LCQP_INVALID_ARGUMENT: NULL handle or buffer, wide outside 0 / 1.  LCQP_LCQPOBJECT_NOT_SETUP: nothing loaded yet. */
+int  lcqp_hip_sparse_product_probe(lcqp_hip_sparse_t* s, int wide, const double* vn, const double* vm, double* on, double* om, double* os, int ell[6]);
 /* Test and diagnostic entry point (as lcqp_hip_batch_read_setup / _read_working_set on the dense arm): the KKT factorisations and solves
  * of the sparse arm -- the register band, the LDS-window band, the bordered band, the general LDL' -- run for every instance of the batch
  * on matrices the caller names, one solve per right-hand side and NO refinement, so that tests/test_gpu_sparse_factor.py can hold each engine

@@ -191,6 +191,8 @@ def lib():
         L.lcqp_hip_sparse_sensitivity_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
         L.lcqp_hip_sparse_adjoint_device.argtypes = [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 3
         L.lcqp_hip_sparse_read_problem.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 9 + [c_int_p]
+        L.lcqp_hip_sparse_read_admm.argtypes = [C.c_void_p, C.c_int, c_int_p, c_double_p] + [c_double_p] * 6
+        L.lcqp_hip_sparse_product_probe.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 5 + [c_int_p]
         L.lcqp_hip_sparse_kkt_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p,
                                                 c_double_p, c_double_p, c_int_p]
         _lib = L
@@ -1212,3 +1214,32 @@ class SparseBatchLCQP(_Batch):
         self._call("read_problem", int(b), *[_p(d[k]) for k in ("Qx", "Ax", "g", "lE", "uE", "lbL", "lbR", "x0", "y0")], C.byref(has))
         d["hasY0"] = has.value
         return d
+
+    def read_admm(self, b):
+        """Test and diagnostic entry point (lcqp_hip_sparse_read_admm; after a run / resolve; launches nothing): the state of the ADMM rounds
+        of instance b as it lies on the device -- sigma, rho (= admmRho scale), scale; rhov, l, u, ya, za [m] in the row order of
+        [A; L; R]; xa [nV].  The polish writes none of xa, ya, za: they are those of the last QP that ran ADMM iterations."""
+        n, m = self.nV, self.m
+        dims = np.zeros(2, dtype=np.int32); scal = np.zeros(3)
+        d = dict(rhov=np.zeros(m), l=np.zeros(m), u=np.zeros(m), xa=np.zeros(n), ya=np.zeros(m), za=np.zeros(m))
+        self._call("read_admm", int(b), _ip(dims), _p(scal), *[_p(d[k]) for k in ("rhov", "l", "u", "xa", "ya", "za")])
+        d.update(n=int(dims[0]), m=int(dims[1]), sigma=float(scal[0]), rho=float(scal[1]), scale=float(scal[2]))
+        return d
+
+    PRODUCT_INPUTS_N = ("x", "q0", "q1", "base", "g", "xr", "c0", "c1")
+    PRODUCT_INPUTS_M = ("y", "yr", "lx0", "lx1")
+    PRODUCT_OUTPUTS_N = ("Qx0", "Qx1", "ETy", "r1", "Qxr", "Cx0", "Cx1", "CE0", "CE1", "CE", "CEzero")
+
+    def product_probe(self, vn, vm, wide=False):
+        """Test and diagnostic entry point (lcqp_hip_sparse_product_probe; needs only a loaded batch): the sparse products of the solver
+        applied to the caller's vectors.  vn [B][8][nV] in the order of PRODUCT_INPUTS_N, vm [B][4][m] in the order of PRODUCT_INPUTS_M.
+        Returns a dict: one [B][nV] array per name of PRODUCT_OUTPUTS_N (Q x0, Q x1 | base - E'y | r1 = -g - Q xr - E'yr, Q xr | C c0, C c1 |
+        the swapped column gathers of lx0, lx1 | that of lx0 alone and its second sum), Ex [B][m], ETy_max, r1_max, r1_scale [B], and ell =
+        (W, tails) of the row slab of Q, the row slab of E and the column slab of E.  wide: a wavefront per instance instead of lanes()."""
+        B, n, m = self.B, self.nV, self.m
+        vn = _sized("vn", _arr(vn), B * 8 * n); vm = _sized("vm", _arr(vm), B * 4 * m)
+        on = np.zeros((B, 11, n)); om = np.zeros((B, m)); os_ = np.zeros((B, 3)); ell = np.zeros(6, dtype=np.int32)
+        self._call("product_probe", 1 if wide else 0, _p(vn), _p(vm), _p(on), _p(om), _p(os_), _ip(ell))
+        r = {k: on[:, i] for i, k in enumerate(self.PRODUCT_OUTPUTS_N)}
+        r.update(Ex=om, ETy_max=os_[:, 0], r1_max=os_[:, 1], r1_scale=os_[:, 2], ell=dict(Q=(int(ell[0]), int(ell[1])), E=(int(ell[2]), int(ell[3])), T=(int(ell[4]), int(ell[5]))))
+        return r

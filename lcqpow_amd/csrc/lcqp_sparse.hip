@@ -538,6 +538,52 @@ __global__ __launch_bounds__(WGS) void k_sparse_kkt_probe(SpBatch db, int mode, 
     }
 }
 
+// ---- k_sparse_product_probe: test and diagnostic kernel (lcqp_hip_sparse_product_probe) -- the sparse products of lcqp_sparse_solver.hpp
+// themselves applied to vectors the caller supplies, so that every branch of g_ell (slab width 4 / 8, scalar tail, position map, ragged last
+// tile) can be held to a plain reference (tests/test_gpu_sparse_products.py) ---------------------------------------------------------------
+// Layouts: lcqp_sparse_launch.hpp (PPN_*, PPM_*, PPO_*, PPS_*).  Reads the values of Q and E and the caller's inputs; writes the caller's
+// outputs and MV_LX / MV_LX2 (sp_Cx2's own scratch, which every phase of a run writes before it reads).  GL lanes per instance.
+// The kernel is launched WITHOUT dynamic LDS (the products use none): c.win of the context below points at nothing and must not be touched.
+template <int GL>
+__device__ __forceinline__ void sp_product_probe(const SpBatch& db, const SpProductProbeArgs& a, int b, int w0, int lane)
+{
+    SpCtx<GL> c = sp_ctx<GL>(db, b, w0, lane);
+    const int t = c.gl, n = db.n, m = db.m;
+    auto vn = [&](int k) { return c.arr(a.vn, (size_t)PPN_NUM * n, (unsigned)k * n); };
+    auto vm = [&](int k) { return c.arr(a.vm, (size_t)PPM_NUM * m, (unsigned)k * m); };
+    auto on = [&](int k) { return c.arr(a.on, (size_t)PPO_NUM * n, (unsigned)k * n); };
+    double* os = a.os + (size_t)b * PPS_NUM;
+    sp_Ex<GL>(c, vn(PPN_X), c.arr(a.om, (size_t)m));
+    sp_Qx2<GL>(c, vn(PPN_Q0), vn(PPN_Q1), on(PPO_QX0), on(PPO_QX1));
+    {
+        GD base = vn(PPN_BASE);
+        const double mx = sp_ETy<GL>(c, vm(PPM_Y), on(PPO_ETY), [&](int i) { return base[i]; }, [](double v) { return v; });
+        if (t == 0) os[PPS_ETY_MAX] = mx;
+    }
+    {
+        double scale = 0.0;
+        const double mx = sp_residual<GL>(c, vn(PPN_G), vn(PPN_XR), vm(PPM_YR), on(PPO_R1), on(PPO_QXR), scale);
+        if (t == 0) { os[PPS_RES_MAX] = mx; os[PPS_RES_SCALE] = scale; }
+    }
+    sp_Cx2<GL>(c, vn(PPN_C0), vn(PPN_C1), on(PPO_CX0), on(PPO_CX1));
+    {
+        GD o0 = on(PPO_CE0), o1 = on(PPO_CE1);
+        sp_C_from_Ex<GL, true>(c, vm(PPM_LX0), vm(PPM_LX1), [](int) { return NoPre{}; }, [&](int i, double s0, double s1, NoPre) { o0[i] = s0; o1[i] = s1; });
+    }
+    {
+        GD o0 = on(PPO_CE), o1 = on(PPO_CEZ);
+        sp_C_from_Ex<GL, false>(c, vm(PPM_LX0), vm(PPM_LX1), [](int) { return NoPre{}; }, [&](int i, double s0, double s1, NoPre) { o0[i] = s0; o1[i] = s1; });
+    }
+}
+template <int G>
+__global__ __launch_bounds__(WGS) void k_sparse_product_probe(SpBatch db, int wide, SpProductProbeArgs a)
+{
+    if (wide) { sp_product_probe<64>(db, a, blockIdx.x, blockIdx.x, (int)threadIdx.x); return; }      // grid = B
+    const int b = blockIdx.x * (64 / G) + threadIdx.x / G;
+    if (b >= db.B) return;
+    sp_product_probe<G>(db, a, b, blockIdx.x * (64 / G), (int)threadIdx.x);
+}
+
 // ---- the scheduler: persistent wavefronts that serve the phase queues of their pool -------------------------------------------------------
 // Queue discipline (per pool and phase): push = take a position (atomicAdd on tail), wait until its slot's sequence says "free for this
 // position" (at once, unless the ring has been lapped), store (position + 1, instance id) into it, atomicAdd on count; pop = claim entries of
@@ -829,6 +875,14 @@ static void sp_launch_kkt_probe(const SpBatch& db, hipStream_t stream, int mode,
     hipLaunchKernelGGL(k_sparse_kkt_probe<G>, dim3(grid), dim3(WGS), ldsBytes, stream, db, mode, which, nrhs, dprim, ddual, use, rhs, sol, recP, recD, recU);
 }
 
+// one launch of k_sparse_product_probe<G> on device buffers: a lane group per instance, or with `wide` a wavefront; the products use no LDS
+template <int G>
+static void sp_launch_product_probe(const SpBatch& db, hipStream_t stream, int wide, const SpProductProbeArgs& a)
+{
+    const int ipw = 64 / G, grid = wide ? db.B : (db.B + ipw - 1) / ipw;
+    hipLaunchKernelGGL(k_sparse_product_probe<G>, dim3(grid), dim3(WGS), 0, stream, db, wide, a);
+}
+
 }  // namespace
 
 // the launch table of this unit's width (lcqp_sparse_launch.hpp)
@@ -838,7 +892,8 @@ const SpKernels& sparse_kernels()
 {
     static const SpKernels k = {G, sp_launch<G>, sp_launch_sensitivity<G>, sp_launch_sensitivity_dual<G>, sp_launch_kkt_probe<G>,
                                 sp_launch_sensitivity_blk<G>, sens_panel_width(G),
-                                G == 64 ? sp_launch_sensitivity_blk_general : nullptr, G == 64 ? general_panel_width() : 0};
+                                G == 64 ? sp_launch_sensitivity_blk_general : nullptr, G == 64 ? general_panel_width() : 0,
+                                sp_launch_product_probe<G>};
     return k;
 }
 }

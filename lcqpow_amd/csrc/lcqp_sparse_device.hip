@@ -282,3 +282,28 @@ extern "C" int lcqp_hip_sparse_read_problem(lcqp_hip_sparse_t* h, int instance, 
     if (int rc = read_back(g_sp_err, hasY0, &d.info[b].hasY0, 1)) return rc;
     return 0;
 }); }
+
+// ---- test and diagnostic entry point: the ADMM state of one instance as the pools hold it (host buffers, synchronous, launches nothing) ----
+// The weights, the stacked bounds and the iterates (sp_prepare_vectors, sp_qp_begin, sp_ph_round, sp_admm in lcqp_sparse_solver.hpp).  The polish
+// writes none of xa, ya, za, so they are those of the last QP that ran ADMM.
+extern "C" int lcqp_hip_sparse_read_admm(lcqp_hip_sparse_t* h, int instance, int dims[2], double scal[3], double* rhov, double* l, double* u,
+                                         double* xa, double* ya, double* za)
+{ return guarded(g_sp_err, [&] {
+    if (!h || instance < 0 || instance >= h->db.B) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.setupValid) return LCQP_LCQPOBJECT_NOT_SETUP;
+    const SpBatch& d = h->db;
+    if (int rc = synchronize(g_sp_err, h)) return rc;
+    const size_t b = instance, n = d.n, m = d.m;
+    SpInfo info;
+    HIPCHK(g_sp_err, hipMemcpy(&info, d.info + b, sizeof(SpInfo), hipMemcpyDeviceToHost));
+    if (dims) { dims[0] = d.n; dims[1] = d.m; }
+    if (scal) { scal[0] = info.sigma; scal[1] = d.opt.admmRho * info.scale; scal[2] = info.scale; }
+    const double *nv = d.nv + b * NV_NUM * n, *mv = d.mv + b * MV_NUM * m;
+    if (int rc = read_back(g_sp_err, rhov, mv + (size_t)MV_RHOV * m, m)) return rc;
+    if (int rc = read_back(g_sp_err, l, mv + (size_t)MV_L * m, m)) return rc;
+    if (int rc = read_back(g_sp_err, u, mv + (size_t)MV_U * m, m)) return rc;
+    if (int rc = read_back(g_sp_err, xa, nv + (size_t)NV_XA * n, n)) return rc;
+    if (int rc = read_back(g_sp_err, ya, mv + (size_t)MV_YA * m, m)) return rc;
+    if (int rc = read_back(g_sp_err, za, mv + (size_t)MV_ZA * m, m)) return rc;
+    return 0;
+}); }

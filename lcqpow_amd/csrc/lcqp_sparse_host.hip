@@ -679,6 +679,29 @@ extern "C" int lcqp_hip_sparse_kkt_probe(lcqp_hip_sparse_t* h, int mode, int whi
     return 0;
 }); }
 
+// ---- test and diagnostic entry point: the sparse products of every instance applied to the caller's vectors (k_sparse_product_probe) ----
+extern "C" int lcqp_hip_sparse_product_probe(lcqp_hip_sparse_t* h, int wide, const double* vn, const double* vm, double* on, double* om, double* os, int ell[6])
+{ return guarded(g_sp_err, [&] {
+    if (!h || !vn || !vm || !on || !om || !os || (wide != 0 && wide != 1)) return LCQP_INVALID_ARGUMENT;
+    if (!h->loaded) return LCQP_LCQPOBJECT_NOT_SETUP;
+    HIPCHK(g_sp_err, hipSetDevice(h->device));
+    SpBatch& d = h->db;
+    if (int rc = synchronize(g_sp_err, h)) return rc;
+    if (ell) { const int v[6] = {d.ellQ.W, d.ellQ.tails, d.ellE.W, d.ellE.tails, d.ellT.W, d.ellT.tails}; memcpy(ell, v, sizeof v); }
+    const size_t B = d.B, n = d.n, m = d.m;
+    DevMem tmp(h->stream);      // the buffers of this call; freed on every way out
+    SpProductProbeArgs a = {};
+    if (!(tmp.alloc(g_sp_err, a.vn, B * PPN_NUM * n, vn) && tmp.alloc(g_sp_err, a.vm, B * PPM_NUM * m, vm) && tmp.alloc(g_sp_err, a.on, B * PPO_NUM * n) &&
+          tmp.alloc(g_sp_err, a.om, B * m) && tmp.alloc(g_sp_err, a.os, B * PPS_NUM))) { g_sp_err = "device allocation failed: " + g_sp_err; return LCQP_HIP_ERROR; }
+    sp_kernels(d.G)->product_probe(d, h->stream, wide, a);
+    HIPCHK(g_sp_err, hipGetLastError());
+    HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));
+    HIPCHK(g_sp_err, hipMemcpy(on, a.on, sizeof(double) * B * PPO_NUM * n, hipMemcpyDeviceToHost));
+    HIPCHK(g_sp_err, hipMemcpy(om, a.om, sizeof(double) * B * m, hipMemcpyDeviceToHost));
+    HIPCHK(g_sp_err, hipMemcpy(os, a.os, sizeof(double) * B * PPS_NUM, hipMemcpyDeviceToHost));
+    return 0;
+}); }
+
 extern "C" int lcqp_hip_sparse_sensitivity_timing(lcqp_hip_sparse_t* h, float* kernel_ms)
 {
     return guarded(g_sp_err, [&] { return sensitivity_timing(g_sp_err, h, kernel_ms); });

@@ -134,6 +134,15 @@ using SpSensitivityDualFn = void(const SpBatch& db, hipStream_t stream, int nrhs
 // SpKktProbeFn: one launch of k_sparse_kkt_probe<G> on `stream` over device buffers (layouts and modes at the kernel).
 using SpKktProbeFn = void(const SpBatch& db, hipStream_t stream, int mode, int which, int nrhs, const double* dprim, const double* ddual, const int* use,
                           const double* rhs, double* sol, double* recP, double* recD, int* recU);
+// SpProductProbeFn: one launch of k_sparse_product_probe<G> on `stream` over device buffers: the sparse products of lcqp_sparse_solver.hpp
+// applied to the caller's vectors.  vn [B][PPN_NUM][n] and vm [B][PPM_NUM][m] are the inputs, on [B][PPO_NUM][n], om [B][m] (E x) and os
+// [B][PPS_NUM] the outputs.  wide: one instance per wavefront with all 64 lanes, as the streaming phases of k_sparse_sched run the products.
+enum { PPN_X, PPN_Q0, PPN_Q1, PPN_BASE, PPN_G, PPN_XR, PPN_C0, PPN_C1, PPN_NUM };      // sp_Ex | sp_Qx2 | base of sp_ETy | g, x of sp_residual | sp_Cx2
+enum { PPM_Y, PPM_YR, PPM_LX0, PPM_LX1, PPM_NUM };                                     // y of sp_ETy | y of sp_residual | lx0, lx1 of sp_C_from_Ex
+enum { PPO_QX0, PPO_QX1, PPO_ETY, PPO_R1, PPO_QXR, PPO_CX0, PPO_CX1, PPO_CE0, PPO_CE1, PPO_CE, PPO_CEZ, PPO_NUM };   // CE0, CE1: TWO; CE, CEZ (zeros): one vector
+enum { PPS_ETY_MAX, PPS_RES_MAX, PPS_RES_SCALE, PPS_NUM };
+struct SpProductProbeArgs { double *vn, *vm, *on, *om, *os; };
+using SpProductProbeFn = void(const SpBatch& db, hipStream_t stream, int wide, const SpProductProbeArgs& a);
 // SpSensitivityBlkFn: one launch of k_sparse_sensitivity_blk<G> on `stream` (DESIGN.md section 3a''', "The sparse arm"): the work items
 // [item0, item0 + nItems) of a call whose items are numbered (instance - first) * npan + panel; column c of panel q is column q * panel + c of
 // the call, ncols columns per instance.  unit != 0: column j is the unit vector e_j and v is not read; else v [count][ncols][n].  The outputs
@@ -153,7 +162,8 @@ __host__ __device__ inline size_t sens_blk_ws_doubles(const SpBatch& db, int pan
 // panel: the panel width of this lane width's k_sparse_sensitivity_blk (0: the width is routed to the vector kernel)
 // sensitivity_blk_general, panel_general: k_sparse_sensitivity_blk_general and its panel width -- the unit of G = 64 alone, null / 0 elsewhere
 struct SpKernels { int G; SpRunFn* run; SpSensitivityFn* sensitivity; SpSensitivityDualFn* sensitivity_dual; SpKktProbeFn* kkt_probe;
-                   SpSensitivityBlkFn* sensitivity_blk; int panel; SpSensitivityBlkFn* sensitivity_blk_general; int panel_general; };
+                   SpSensitivityBlkFn* sensitivity_blk; int panel; SpSensitivityBlkFn* sensitivity_blk_general; int panel_general;
+                   SpProductProbeFn* product_probe; };
 // defined in lcqp_sparse.hip and instantiated there for G = LCQP_TU_G
 template <int G> const SpKernels& sparse_kernels();
 #pragma GCC visibility pop

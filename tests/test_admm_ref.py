@@ -196,3 +196,74 @@ def test_float64_stays_two_orders_below_the_bounds_of_the_rho_update(case):
         worst = max(_float64_ratio_rho("batch", key + (j,), rho, False) for j in range(min(key[0], 3)))
     print(f"    admmRho = {rho}: float64 against long double: worst error / bound = {worst:.3e}")
     assert worst < 1e-2
+
+
+# ---- the sparse arm's conventions (tests/sparse_admm_ref.py; tests/test_gpu_sparse_admm.py holds the device to it) ---------------------------
+import sparse_admm_ref as SR
+
+
+def test_sparse_reference_fixed_point_is_a_kkt_point():
+    """with a free row at the weight 1e-6 rho: the iteration converges to the KKT point of the QP, the free row carries no multiplier and its
+    z follows E x"""
+    Q, E, g, l, u = list(_small_qps())[1]
+    rng = np.random.default_rng(3)
+    E = np.vstack([E, rng.standard_normal((1, E.shape[1]))]); l = np.append(l, -np.inf); u = np.append(u, np.inf)
+    n = len(g)
+    scale = np.abs(np.diag(Q)).max()
+    rhov = SR.rho_vector(Opt, scale, l, u)
+    assert rhov[-1] == 1e-6 * (Opt.admmRho * scale) and (rhov[:-1] >= Opt.admmRho * scale).all()
+    x, y, z = (v.astype(np.float64) for v in SR.admm(Q, E, g, l, u, rhov, Opt.admmSigma * scale, Opt.admmAlpha, np.zeros(n), np.ones(len(l)), 3000))
+    assert y[-1] == 0.0
+    assert np.abs(Q @ x + g + E.T @ y).max() < 1e-9
+    ex = E @ x
+    assert (ex >= l - 1e-9).all() and (ex <= u + 1e-9).all() and np.abs(ex - z).max() < 1e-9
+    at_l, at_u = np.abs(ex - l) < 1e-8, np.abs(ex - u) < 1e-8
+    assert (y[~at_u] <= 1e-9).all() and (y[~at_l] >= -1e-9).all()
+
+
+@functools.lru_cache(maxsize=None)
+def _sparse_case(name):
+    return SR.CASES[name][0]()
+
+
+def _sparse_ratio(d, perm, dt):
+    """worst error / bound of the device-form iteration in dtype dt (ordering perm) against the long-double reduced form, per quantity"""
+    Q, E = SR.dense(d)
+    l, u = SR.stacked(d)
+    n = d["nV"]
+    scale = np.abs(np.diag(Q)).max(); sigma = Opt.admmSigma * scale
+    rhov = SR.rho_vector(Opt, scale, l, u)
+    condK = R.cond2(R.K(Q, E, sigma, rhov, np.float64))
+    worst = dict(xa=0.0, ya=0.0, za=0.0)
+    for x0, y0 in ((np.zeros(n), np.zeros(len(l))), (d["x0"], -d["y0"])):
+        ref = SR.admm(Q, E, d["g"], l, u, rhov, sigma, Opt.admmAlpha, x0, y0, max(SR.KS), LD, SR.KS)
+        got = SR.admm_kkt(Q, E, d["g"], l, u, rhov, sigma, Opt.admmAlpha, x0, y0, max(SR.KS), dt, perm, SR.KS)
+        for k in SR.KS:
+            b, by = SR.iterate_bounds(n, condK, k, *ref[k], rhov, l, u)
+            for name, err, bd in SR.iterate_errors(got[k], ref[k], b, by):
+                with np.errstate(divide="ignore", invalid="ignore"):
+                    worst[name] = max(worst[name], float(np.where(err > 0, err / bd, 0.0).max()))
+    return worst
+
+
+def test_sparse_kkt_form_and_reduced_form_agree_in_long_double():
+    d = _sparse_case("small")[0]
+    worst = _sparse_ratio(d, np.arange(d["nV"] + d["E"].shape[0]), LD)
+    print(f"    KKT form against reduced form, both long double: worst error / bound = {worst}")
+    assert max(worst.values()) < 1e-5       # eps of long double / eps of float64 = 5e-4 of what test_sparse_float64_... allows
+
+
+@pytest.mark.parametrize("name", list(SR.CASES))
+def test_sparse_float64_stays_two_orders_below_the_gpu_bounds(oracle, name):
+    """a float64 run of the device's form -- the KKT matrix, an LDL' without pivoting in a fill-reducing ordering of the pattern, one solve
+    per iteration, no refinement -- against the long-double reduced form: 1e-2 of the bounds of tests/test_gpu_sparse_admm.py at the most,
+    for every instance, start and iteration count used there"""
+    from test_sparse_kkt_ref import _ordering
+    inst = _sparse_case(name)
+    perm, _ = _ordering(oracle, inst[0], "general" in name)
+    worst = dict(xa=0.0, ya=0.0, za=0.0)
+    for d in inst:
+        w = _sparse_ratio(d, perm, np.float64)
+        worst = {k: max(worst[k], w[k]) for k in worst}
+    print(f"    {name}: float64 KKT form against long double: worst error / bound = " + "  ".join(f"{k} {v:.2e}" for k, v in worst.items()))
+    assert max(worst.values()) < 1e-2
