@@ -6,6 +6,7 @@ printed.  The targets are solutions of the same LCQPs for other linear terms, so
     python examples/sensitivity.py
     python examples/sensitivity.py sparse      # the same fit on the sparse arm: 16 banded LCQPs (n = 64), lcqp_hip_sparse_sensitivity
     python examples/sensitivity.py jacobian    # the full Jacobians dx/dg of the 64 LCQPs (lcqp_hip_batch_jacobian): |Jg - Jg'| and the kernel time
+    python examples/sensitivity.py duals       # the four blocks of D(x, y) / D(g, bounds) of one LCQP (lcqp_hip_batch_jacobian and _jacobian_duals)
     python examples/sensitivity.py sparse jacobian   # the full Jacobians of the 16 banded LCQPs (lcqp_hip_sparse_jacobian), panel kernel
     python examples/sensitivity.py adjoint     # learn ONE constraint matrix A shared by the 64 LCQPs from a loss on x and y (lcqp_hip_batch_adjoint)
     python examples/sensitivity.py sparse adjoint   # learn ONE value array of [A; L; R] shared by 16 banded LCQPs (lcqp_hip_sparse_adjoint)
@@ -144,6 +145,20 @@ def main():
         Jg = layer.jacobian()
         print("Jg %s: max |Jg - Jg'| = %.3e, kernel %.4f ms, flagged instances %d"
               % (tuple(Jg.shape), (Jg - Jg.transpose(1, 2)).abs().max().item(), bt.sensitivity_kernel_ms(), int(np.count_nonzero(layer.info))))
+    elif sys.argv[1:] == ["duals"]:
+        with torch.no_grad():
+            layer.solve(torch.as_tensor(st("g")))
+        J = layer.jacobian(duals=True)      # the whole solution map D(x, y) / D(g, b_W): BatchLCQP.jacobian and .jacobian_duals
+        W = torch.flatnonzero(J["side"][0])
+        print("instance 0: %d rows in the working set, dual positions %s" % (len(W), W.tolist()))
+        torch.set_printoptions(precision=4, linewidth=160)
+        print("dx/dg  %s, first 4 x 4:\n%s" % (tuple(J["xg"].shape), J["xg"][0, :4, :4]))
+        print("dx/db  %s, x rows 0 .. 3, columns of W:\n%s" % (tuple(J["xb"].shape), J["xb"][0, :4][:, W]))
+        print("dy/dg  %s, rows of W, g columns 0 .. 3:\n%s" % (tuple(J["yg"].shape), J["yg"][0, W][:, :4]))
+        print("dy/db  %s, W x W:\n%s" % (tuple(J["yb"].shape), J["yb"][0, W][:, W]))
+        print("max |dy/dg - (dx/db)'| = %.3e, max |dy/db - (dy/db)'| = %.3e, flagged instances %d"
+              % ((J["yg"] - J["xb"].transpose(1, 2)).abs().max().item(), (J["yb"] - J["yb"].transpose(1, 2)).abs().max().item(),
+                 int(np.count_nonzero(layer.info))))
     else:
         fit(layer, st("g"), rng, B)
     bt.close()

@@ -215,8 +215,8 @@ int  lcqp_hip_batch_resolve(lcqp_hip_batch_t* b, int mode, const double* rho0);
  * LCQP_INVALID_ARGUMENT: NULL handle, v or dg, or nrhs < 1.  LCQP_LCQPOBJECT_NOT_SETUP: no run / resolve on this object yet, or a load /
  * generate_synthetic / set_options since the last one.  LCQP_HIP_ERROR: a HIP call failed (no device). */
 int  lcqp_hip_batch_sensitivity(lcqp_hip_batch_t* b, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
-/* kernel time of the last lcqp_hip_batch_sensitivity / _sensitivity_blocked / _jacobian call of this object, ms (HIP events around
- * k_sensitivity or k_sensitivity_blk, the copies excluded; a Jacobian that went in chunks: the sum over its launches) */
+/* kernel time of the last lcqp_hip_batch_sensitivity / _sensitivity_blocked / _jacobian / _adjoint_blocked / _jacobian_duals call of this
+ * object or of their device twins, ms (HIP events around k_sensitivity, k_sensitivity_blk or k_sensitivity_blk_dual, the copies excluded; a Jacobian that went in chunks: the sum over its launches) */
 int  lcqp_hip_batch_sensitivity_timing(lcqp_hip_batch_t* b, float* kernel_ms);
 /* lcqp_hip_batch_sensitivity for many vectors (DESIGN.md section 3a'''): the same arguments, layouts, flags and return codes, checked in the
  * same order before any device call.  The vectors of an instance go through k_sensitivity_blk in panels of 16 (LCQP_SENS_PANEL; the last
@@ -260,6 +260,25 @@ int  lcqp_hip_batch_set_jacobian_staging(lcqp_hip_batch_t* b, size_t bytes);
  * decided before any device call. */
 int  lcqp_hip_batch_adjoint(lcqp_hip_batch_t* b, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
                             int reduce, double* dQ, double* dA, double* dL, double* dR);
+/* The blocked adjoint (DESIGN.md section 3a'''', "Panels with gradients on y"): lcqp_hip_batch_sensitivity_blocked with upstream gradients on
+ * the duals.  vx [B][nrhs][nV], vy [B][nrhs][nd] (host; either may be NULL = zero, not both; entries of vy outside W are not read);
+ * dg [B][nrhs][nV], db [B][nrhs][nd], side [B][nd], info [B] as lcqp_hip_batch_adjoint gives them for one pair.  The pairs of an instance
+ * go through k_sensitivity_blk_dual in panels of LCQP_SENS_PANEL; with vx == NULL the forward substitution is not run.  A pair's
+ * result does not depend on the other pairs of the call or on its place among them, bit for bit.  With vy == NULL the call is
+ * lcqp_hip_batch_sensitivity_blocked, to the bit.  nV > 512: k_sensitivity<NCH, true> and its bits (a NULL vx is a zero panel there).
+ * LCQP_INVALID_ARGUMENT: NULL handle or dg, vx and vy both NULL, nrhs < 1.  LCQP_LCQPOBJECT_NOT_SETUP as lcqp_hip_batch_sensitivity. */
+int  lcqp_hip_batch_adjoint_blocked(lcqp_hip_batch_t* b, int nrhs, const double* vx, const double* vy, double* dg, double* db, int* side, int* info);
+/* The dual rows of the solution Jacobian for the instances [first, first + count): D y* / D (g, b_W), the blocked kernel on the unit
+ * vectors of the slot space, which it generates on the device (nothing is uploaded, no forward substitution).
+ *   Jyg[i][r][j]  [count][nd][nV]   d y*_r / d g_j of instance first + i
+ *   Jyb[i][r][s]  [count][nd][nd]   d y*_r / d (the bound row s of the dual layout sits on); may be NULL
+ *   side [count][nd], info [count]  as lcqp_hip_batch_sensitivity; may be NULL
+ * Rows (and, in Jyb, columns) outside W are zero.  Jyg[i][r][j] is Jb[i][j][r] of lcqp_hip_batch_jacobian to rounding: both are the block
+ * (K^-1)_{x lambda}.  The staging on the device holds one row per slot of the working set (at most capS per instance, not nd) and is
+ * chunked over instances under the cap of lcqp_hip_batch_set_jacobian_staging; the results do not depend on the chunking.  nV > 512:
+ * k_sensitivity<NCH, true> on uploaded unit vectors of the rows in W, in chunks of vectors under the same cap, on the whole batch.
+ * LCQP_INVALID_ARGUMENT: NULL handle or Jyg, first < 0, count < 1, first + count > B.  LCQP_LCQPOBJECT_NOT_SETUP as lcqp_hip_batch_sensitivity. */
+int  lcqp_hip_batch_jacobian_duals(lcqp_hip_batch_t* b, int first, int count, double* Jyg, double* Jyb, int* side, int* info);
 /* out[0] = full setups, out[1] = homotopy launches this object has issued (host counters) */
 int  lcqp_hip_batch_launch_counts(lcqp_hip_batch_t* b, int out[2]);
 /* Hint of a caller that keeps several batch objects in flight (BatchPipeline): the setup of this object will run beside the homotopy
@@ -311,6 +330,16 @@ int  lcqp_hip_batch_sensitivity_device(lcqp_hip_batch_t* b, int blocked, int nrh
 int  lcqp_hip_batch_adjoint_device(lcqp_hip_batch_t* b, const double* vx, const double* vy,
                                    double* dg, double* db, int* side, int* info,
                                    int reduce, double* dQ, double* dA, double* dL, double* dR, void* stream);
+/* The twins of lcqp_hip_batch_adjoint_blocked, _jacobian and _jacobian_duals under the same rules: device arrays in and out, the bits of the
+ * host twins, NULL handle: LCQP_LCQPOBJECT_NOT_SETUP.  The Jacobians go in the host twins' chunks of instances; a small kernel
+ * (k_pack_dual_rows) moves the staged rows of the dual Jacobian to their rows of Jyg / Jyb, which are zero-filled on the device before it.
+ * lcqp_hip_batch_sensitivity_timing reports the sum over the chunks' kernels, as after the host twins (a call with more than one chunk
+ * waits on the host for each chunk's kernel but the last: the next chunk reuses the staging and the events).  nV > 512 (no blocked kernel): the Jacobians are formed by the host
+ * twins and copied to the device; those two calls then wait on the host. */
+int  lcqp_hip_batch_adjoint_blocked_device(lcqp_hip_batch_t* b, int nrhs, const double* vx, const double* vy,
+                                           double* dg, double* db, int* side, int* info, void* stream);
+int  lcqp_hip_batch_jacobian_device(lcqp_hip_batch_t* b, int first, int count, double* Jg, double* Jb, int* side, int* info, void* stream);
+int  lcqp_hip_batch_jacobian_duals_device(lcqp_hip_batch_t* b, int first, int count, double* Jyg, double* Jyb, int* side, int* info, void* stream);
 
 /* per-iterate tracking of one instance when options.storeSteps != 0 (LCQProblem::storeSteps,
  * src/LCQProblem.cpp:1365-1378; OutputStatistics tracking vectors, src/OutputStatistics.cpp:131-164): scalars[len][8] =

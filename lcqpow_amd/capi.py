@@ -144,6 +144,11 @@ def lib():
         L.lcqp_hip_batch_get_solution_device.argtypes = [C.c_void_p] * 5
         L.lcqp_hip_batch_sensitivity_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
         L.lcqp_hip_batch_adjoint_device.argtypes = [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 5
+        L.lcqp_hip_batch_adjoint_blocked.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
+        L.lcqp_hip_batch_jacobian_duals.argtypes = [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_int_p]
+        L.lcqp_hip_batch_adjoint_blocked_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        L.lcqp_hip_batch_jacobian_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
+        L.lcqp_hip_batch_jacobian_duals_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
         L.lcqp_hip_qp_adjoint.argtypes = [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p] + [c_double_p] * 2
         L.lcqp_hip_util_symv.argtypes = [C.c_int, C.c_int, C.c_double] + [c_double_p] * 4
         L.lcqp_hip_util_gemv.argtypes = [C.c_int, C.c_int, C.c_int] + [c_double_p] * 3
@@ -312,14 +317,16 @@ def _adjoint(call, vx, vy, B, nV, nd, shapes, matrices, lead, check=None):
 SENS_PANEL = 16      # LCQP_SENS_PANEL: vectors per panel of the blocked sensitivity kernel
 
 
-def _jacobian(call, B, nV, nd, first, count, bounds, check=None):
+def _jacobian(call, B, nV, nd, first, count, bounds, check=None, rows=None):
     """call(first, count, Jg, Jb, side, info) -> rc on the instances [first, first + count) of B (count None: to the end).  Returns
-    (Jg [count][nV][nV], Jb [count][nV][nd] or None, side [count][nd], info [count]); raises before any call on a range outside the batch."""
+    (Jg [count][nV][nV], Jb [count][nV][nd] or None, side [count][nd], info [count]); raises before any call on a range outside the batch.
+    rows: the rows of the two blocks when they are not nV (the dual Jacobian: nd)."""
     if count is None:
         count = B - first
     if not (isinstance(first, (int, np.integer)) and isinstance(count, (int, np.integer))) or first < 0 or count < 1 or first + count > B:
         raise ValueError(f"jacobian: instances [{first}, {first} + {count}) are not inside the batch of {B}")
-    Jg = np.zeros((count, nV, nV)); Jb = np.zeros((count, nV, nd)) if bounds else None
+    rows = nV if rows is None else rows
+    Jg = np.zeros((count, rows, nV)); Jb = np.zeros((count, rows, nd)) if bounds else None
     side = np.zeros((count, nd), dtype=np.int32); info = np.zeros(count, dtype=np.int32)
     (check or _check)(call(int(first), int(count), _p(Jg), _p(Jb), _ip(side), _ip(info)), "jacobian")
     return Jg, Jb, side, info
@@ -742,8 +749,81 @@ class BatchLCQP(_Batch):
             if _staging_bytes is not None:
                 self._call("set_jacobian_staging", 0)      # back to the default cap
 
+    def _pairs(self, VX, VY, conv):
+        """the shapes of a blocked adjoint call: VX [B][k][nV] or None, VY [B][k][nd] or None, not both None; returns (VX, VY, k)"""
+        VX, VY = conv(VX), conv(VY)
+        if VX is None and VY is None:
+            raise ValueError("adjoint_blocked: VX and VY are both None")
+        k = (VX if VX is not None else VY).shape[1] if (VX if VX is not None else VY).ndim == 3 else 0
+        for name, a, width in (("VX", VX, self.nV), ("VY", VY, self.nd)):
+            if a is not None and (a.ndim != 3 or k < 1 or tuple(a.shape) != (self.B, k, width)):
+                raise ValueError(f"{name}: expected [{self.B}][k][{width}] with k >= 1, got shape {tuple(a.shape)}")
+        return VX, VY, k
+
+    def adjoint_blocked(self, VX, VY=None):
+        """lcqp_hip_batch_adjoint_blocked: adjoint() without matrices for k pairs per instance, in panels of SENS_PANEL on the matrix cores
+        (DESIGN.md section 3a'''').  VX [B][k][nV] = dl/dx or None, VY [B][k][nd] = dl/dy or None (not both; entries of VY outside the working
+        set are not read).  Returns (dg [B][k][nV], db [B][k][nd], side [B][nd], info [B]).  With VY None the call is
+        sensitivity(VX, blocked=True), to the bit; with VX None the forward substitution is not run."""
+        VX, VY, k = self._pairs(VX, VY, _arr)
+        B, n, nd = self.B, self.nV, self.nd
+        dg = np.zeros((B, k, n)); db = np.zeros((B, k, nd)); side = np.zeros((B, nd), dtype=np.int32); info = np.zeros(B, dtype=np.int32)
+        self._call("adjoint_blocked", k, _p(VX), _p(VY), _p(dg), _p(db), _ip(side), _ip(info))
+        return dg, db, side, info
+
+    def jacobian_duals(self, first=0, count=None, bounds=True, _staging_bytes=None):
+        """lcqp_hip_batch_jacobian_duals: the dual rows of the solution Jacobian of the instances [first, first + count) (count None: to the
+        end).  Returns (Jyg, Jyb, side, info): Jyg [count][nd][nV], Jyg[i][r][j] = dy_r/dg_j; Jyb [count][nd][nd], Jyb[i][r][s] =
+        dy_r/d(the bound row s sits on) (None with bounds=False); rows and columns outside the working set are zero.  The unit vectors of
+        the working set are generated on the device; the call goes in chunks of instances under the staging cap of jacobian."""
+        if _staging_bytes is not None:
+            self._call("set_jacobian_staging", int(_staging_bytes))
+        try:
+            return _jacobian(lambda *a: self._sym("jacobian_duals")(self.h, *a), self.B, self.nV, self.nd, first, count, bounds, check=self._check,
+                             rows=self.nd)
+        finally:
+            if _staging_bytes is not None:
+                self._call("set_jacobian_staging", 0)      # back to the default cap
+
     # ---- the device-pointer entry points (DESIGN.md section 3a'''''): torch tensors on the handle's device in, torch tensors out; the work is
     # ordered behind torch.cuda.current_stream(), and what the caller enqueues there next sees the results.  No copy through the host.
+    def adjoint_blocked_device(self, VX, VY=None):
+        """lcqp_hip_batch_adjoint_blocked_device: adjoint_blocked on float64 tensors of the handle's device, read where they lie; returns
+        (dg, db, side, info) as tensors on that device"""
+        import torch
+        for name, t in (("VX", VX), ("VY", VY)):
+            if t is not None and not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name}: expected a torch tensor on the device of the batch, got {type(t).__name__}")
+        VX, VY, k = self._pairs(VX, VY, lambda t: t)
+        B, n, nd = self.B, self.nV, self.nd
+        pvx = self._dev("VX", VX, ((B, k, n),)); pvy = self._dev("VY", VY, ((B, k, nd),))
+        dev = torch.device("cuda", self.device)
+        dg = torch.empty((B, k, n), dtype=torch.float64, device=dev); db = torch.empty((B, k, nd), dtype=torch.float64, device=dev)
+        side = torch.empty((B, nd), dtype=torch.int32, device=dev); info = torch.empty(B, dtype=torch.int32, device=dev)
+        self._call("adjoint_blocked_device", k, pvx, pvy, dg.data_ptr(), db.data_ptr(), side.data_ptr(), info.data_ptr(), self._stream())
+        return dg, db, side, info
+
+    def _jacobian_device(self, name, rows, first, count, bounds):
+        import torch
+        if count is None:
+            count = self.B - first
+        self._range(first, count)
+        n, nd = self.nV, self.nd
+        dev = torch.device("cuda", self.device)
+        Jg = torch.empty((count, rows, n), dtype=torch.float64, device=dev)
+        Jb = torch.empty((count, rows, nd), dtype=torch.float64, device=dev) if bounds else None
+        side = torch.empty((count, nd), dtype=torch.int32, device=dev); info = torch.empty(count, dtype=torch.int32, device=dev)
+        self._call(name, first, count, Jg.data_ptr(), Jb.data_ptr() if bounds else None, side.data_ptr(), info.data_ptr(), self._stream())
+        return Jg, Jb, side, info
+
+    def jacobian_device(self, first=0, count=None, bounds=True):
+        """lcqp_hip_batch_jacobian_device: jacobian() written into tensors on the handle's device, (Jg, Jb, side, info)"""
+        return self._jacobian_device("jacobian_device", self.nV, first, count, bounds)
+
+    def jacobian_duals_device(self, first=0, count=None, bounds=True):
+        """lcqp_hip_batch_jacobian_duals_device: jacobian_duals() written into tensors on the handle's device, (Jyg, Jyb, side, info)"""
+        return self._jacobian_device("jacobian_duals_device", self.nd, first, count, bounds)
+
     def _device_vectors(self, count, g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0):
         n, nC, nK = self.nV, self.nC, self.nComp
         if g is None:

@@ -82,6 +82,18 @@ class BatchLCQProblem {
     {
         return (ReturnValue)lcqp_hip_batch_adjoint(h, vx, vy, dg, db, side, info, reduce ? 1 : 0, dQ, dA, dL, dR);
     }
+    // lcqp_hip_batch_adjoint_blocked: nrhs pairs per instance, vx [batch][nrhs][nV] and vy [batch][nrhs][nDuals] (either may be 0, not both),
+    // in panels of 16 on the matrix cores; dg [batch][nrhs][nV], db [batch][nrhs][nDuals], side, info as getSensitivity
+    ReturnValue getAdjointBlocked(int nrhs, const double* vx, const double* vy, double* dg, double* db = 0, int* side = 0, int* info = 0)
+    {
+        return (ReturnValue)lcqp_hip_batch_adjoint_blocked(h, nrhs, vx, vy, dg, db, side, info);
+    }
+    // lcqp_hip_batch_jacobian_duals: Jyg [count][nDuals][nV] = dy/dg, Jyb [count][nDuals][nDuals] = dy/d(bounds) (or 0), zero outside the
+    // working set; side [count][nDuals], info [count] of the instances [first, first + count)
+    ReturnValue getDualJacobian(int first, int count, double* Jyg, double* Jyb = 0, int* side = 0, int* info = 0)
+    {
+        return (ReturnValue)lcqp_hip_batch_jacobian_duals(h, first, count, Jyg, Jyb, side, info);
+    }
     // full setups and homotopy launches this object has issued
     ReturnValue getLaunchCounts(int& setups, int& launches) const
     {

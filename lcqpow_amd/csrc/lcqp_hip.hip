@@ -736,7 +736,7 @@ extern "C" int lcqp_hip_batch_set_jacobian_staging(lcqp_hip_batch_t* h, size_t b
 
 extern "C" int lcqp_hip_batch_sensitivity_timing(lcqp_hip_batch_t* h, float* kernel_ms)
 {
-    return guarded(g_err, [&] { return sensitivity_timing(g_err, h, kernel_ms, h ? &h->sensBlk : nullptr); });
+    return guarded(g_err, [&] { return sensitivity_timing(g_err, h, kernel_ms, h ? &h->sensBlk : nullptr, h ? &h->sensDual : nullptr); });
 }
 
 // ---- the full adjoint (DESIGN.md section 3a''''): upstream gradients on x and y, gradients in g, the bounds and the matrices ----
@@ -840,5 +840,244 @@ extern "C" int lcqp_hip_batch_adjoint_device(lcqp_hip_batch_t* h, const double* 
         }
         if (!most) return 0;
         return adjoint_device(g_err, h, [&] { launch_adjoint(h, segs, most, reduce, 0, d.B); });
+    });
+}); }
+
+// ---- panels with gradients on y, the dual rows of the Jacobian (DESIGN.md section 3a'''', "Panels with gradients on y") ----
+// k_sensitivity_blk_dual on the whole batch through sensitivity_call, on the buffers and pitches of the blocked kernel.  vy == nullptr:
+// the blocked sensitivity call itself.  No blocked kernel (np >= 1024): k_sensitivity<NCH, true>, an absent vx as a zero panel.
+static int dense_adjoint_blocked(lcqp_hip_batch* h, int nrhs, const double* vx, const double* vy, bool dev,
+                                 double* dg, double* db, int* side, int* info, float& ms)
+{
+    DevBatch& d = h->db;
+    if (!vy) return dense_sensitivity(h, h->k->sensitivity_blk != nullptr, 0, d.B, nrhs, vx, nullptr, dev, dg, db, side, info, ms);
+    const bool blk = h->k->sensitivity_blk_dual != nullptr;
+    const SensPitch p = {(size_t)d.n, (size_t)d.np, (size_t)d.nd + (blk ? 2 : 1) * (size_t)d.capS, (size_t)d.nd};
+    std::vector<double> zeros;
+    if (!blk && !vx && !dev) { zeros.assign((size_t)d.B * nrhs * d.n, 0.0); vx = zeros.data(); }
+    hipError_t filled = hipSuccess;
+    if (int rc = sensitivity_call(g_err, h, blk ? h->sensBlk : h->sn.sens, p, d.B, nrhs, vx, vy, dev, blk ? 2 : 1, dg, db, side, info, ms,
+                                  [&](const double* dv, const double* dvy, SensBuffers& sb) {
+        if (blk) { h->k->sensitivity_blk_dual(d, d.B, h->stream, 0, nrhs, dv, dvy, 0, sb.dg, sb.db, sb.side, sb.info, nullptr); return; }
+        if (!dv) { filled = hipMemsetAsync(sb.v, 0, sizeof(double) * sb.rows * d.n, h->stream); dv = sb.v; }      // (the device twin without vx)
+        h->k->sensitivity_dual(d, d.B, h->stream, nrhs, dv, dvy, sb.dg, sb.db, sb.side, sb.info);
+    })) return rc;
+    HIPCHK(g_err, filled);
+    return 0;
+}
+
+int batch_adjoint_blocked(lcqp_hip_batch* h, int nrhs, const double* vx, const double* vy, double* dg, double* db, int* side, int* info)
+{
+    float ms = 0.f;
+    if (int rc = dense_adjoint_blocked(h, nrhs, vx, vy, false, dg, db, side, info, ms)) return rc;
+    h->rs.sensMs = ms;
+    return 0;
+}
+
+extern "C" int lcqp_hip_batch_adjoint_blocked(lcqp_hip_batch_t* h, int nrhs, const double* vx, const double* vy, double* dg, double* db, int* side, int* info)
+{ return guarded(g_err, [&] {
+    if (!h || nrhs < 1 || (!vx && !vy) || !dg) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return batch_adjoint_blocked(h, nrhs, vx, vy, dg, db, side, info);
+}); }
+
+// One launch of k_sensitivity_blk_dual on the unit vectors of the slot space of the instances [first, first + count), on sensDual:
+// capS staged rows per instance (row j: the j-th occupied slot), no v, and behind the `count` rows of `side` the map [count][capS] from
+// staged row to dual position (-1: no such slot).  dual_rowpos: where that map lies.
+static int* dual_rowpos(lcqp_hip_batch* h, int count) { return h->sensDual.side + (size_t)count * h->db.nd; }
+static int dual_jacobian_launch(lcqp_hip_batch* h, int first, int count)
+{
+    DevBatch& d = h->db;
+    SensBuffers& sb = h->sensDual;
+    HIPCHK(g_err, hipSetDevice(h->device));
+    if (int rc = sb.reserve(g_err, h->mem, h->stream, count, d.capS, 0, d.np, (size_t)d.nd + 2 * (size_t)d.capS, (size_t)d.nd + d.capS)) return rc;
+    h->sn.sensPending = 0;
+    h->sn.pendingMs = 0.f;
+    return timed_launch(g_err, h->stream, sb.ev0, sb.ev1, [&] {
+        h->k->sensitivity_blk_dual(d, count, h->stream, first, d.capS, nullptr, nullptr, 1, sb.dg, sb.db, sb.side, sb.info, dual_rowpos(h, count));
+    });
+}
+// the staging of one instance of such a launch, in bytes
+static size_t dual_jacobian_staging(const DevBatch& d)
+{
+    return sizeof(double) * (size_t)d.capS * ((size_t)d.np + d.nd + 2 * (size_t)d.capS) + sizeof(int) * (size_t)d.capS;
+}
+
+// np >= 1024: k_sensitivity<NCH, true> with vx = 0 and vy = the unit vectors of the dual positions that are in W for some instance of the
+// range, uploaded in chunks of vectors under the cap, on the whole batch (the vector kernel has no instance offset)
+static int jacobian_duals_by_vectors(lcqp_hip_batch* h, int first, int count, double* Jyg, double* Jyb, int* side, int* info)
+{
+    DevBatch& d = h->db;
+    const size_t B = d.B, n = d.n, nd = d.nd;
+    float ms = 0.f;
+    std::vector<double> zero(B * n, 0.0), G(B * n);
+    std::vector<int> sd(B * nd), in(B);
+    if (int rc = dense_sensitivity(h, false, 0, d.B, 1, zero.data(), nullptr, false, G.data(), nullptr, sd.data(), in.data(), ms)) return rc;
+    std::vector<size_t> rows;
+    for (size_t r = 0; r < nd; r++) {
+        bool any = false;
+        for (size_t i = 0; i < (size_t)count; i++) any = any || sd[(first + i) * nd + r] != 0;
+        if (any) rows.push_back(r);
+    }
+    const size_t cc = staging_chunk(h->sn.staging, sizeof(double) * B * (n + (size_t)d.np + 2 * nd + (size_t)d.capS), rows.size());
+    std::vector<double> VY(B * cc * nd), Bd(B * cc * nd);
+    G.resize(B * cc * n);
+    for (size_t c0 = 0; c0 < rows.size(); c0 += cc) {
+        const size_t nc = std::min(cc, rows.size() - c0);
+        std::fill(VY.begin(), VY.end(), 0.0);
+        for (size_t b = 0; b < B; b++) for (size_t k = 0; k < nc; k++) VY[(b * nc + k) * nd + rows[c0 + k]] = 1.0;
+        if (int rc = dense_adjoint_blocked(h, (int)nc, nullptr, VY.data(), false, G.data(), Bd.data(), nullptr, nullptr, ms)) return rc;
+        for (size_t i = 0; i < (size_t)count; i++)
+            for (size_t k = 0; k < nc; k++) {
+                const size_t r = rows[c0 + k], src = (first + i) * nc + k;
+                if (sd[(first + i) * nd + r] == 0) continue;      // not in this instance's W: the row stays zero
+                std::memcpy(Jyg + (i * nd + r) * n, G.data() + src * n, sizeof(double) * n);
+                if (Jyb) std::memcpy(Jyb + (i * nd + r) * nd, Bd.data() + src * nd, sizeof(double) * nd);
+            }
+    }
+    if (side) std::memcpy(side, sd.data() + (size_t)first * nd, sizeof(int) * (size_t)count * nd);
+    if (info) std::memcpy(info, in.data() + first, sizeof(int) * (size_t)count);
+    h->rs.sensMs = ms;
+    return 0;
+}
+
+// Jyg [count][nd][n], Jyb [count][nd][nd] (or NULL), side [count][nd], info [count] of the instances [first, first + count)
+int batch_jacobian_duals(lcqp_hip_batch* h, int first, int count, double* Jyg, double* Jyb, int* side, int* info)
+{
+    DevBatch& d = h->db;
+    const size_t n = d.n, nd = d.nd, capS = d.capS;
+    std::memset(Jyg, 0, sizeof(double) * (size_t)count * nd * n);
+    if (Jyb) std::memset(Jyb, 0, sizeof(double) * (size_t)count * nd * nd);
+    if (!h->k->sensitivity_blk_dual) return jacobian_duals_by_vectors(h, first, count, Jyg, Jyb, side, info);
+    // chunks of instances whose staging stays below the cap; one launch and one download per chunk, the rows scattered on the host
+    const size_t chunk = staging_chunk(h->sn.staging, dual_jacobian_staging(d), count);
+    std::vector<double> G(chunk * capS * n), Bd(Jyb ? chunk * capS * nd : 0);
+    std::vector<int> rp(chunk * capS);
+    float total = 0.f;
+    for (size_t c0 = 0; c0 < (size_t)count; c0 += chunk) {
+        const size_t cb = std::min(chunk, (size_t)count - c0);
+        if (int rc = dual_jacobian_launch(h, first + (int)c0, (int)cb)) return rc;
+        SensBuffers& sb = h->sensDual;
+        HIPCHK(g_err, hipMemcpyAsync(rp.data(), dual_rowpos(h, (int)cb), sizeof(int) * cb * capS, hipMemcpyDeviceToHost, h->stream));
+        if (int rc = sb.rows_out(g_err, G.data(), sb.dg, n, sb.ldDg)) return rc;
+        if (Jyb) if (int rc = sb.rows_out(g_err, Bd.data(), sb.db, nd, sb.ldDb)) return rc;
+        if (side) HIPCHK(g_err, hipMemcpyAsync(side + c0 * nd, sb.side, sizeof(int) * cb * nd, hipMemcpyDeviceToHost, h->stream));
+        if (info) HIPCHK(g_err, hipMemcpyAsync(info + c0, sb.info, sizeof(int) * cb, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(g_err, hipStreamSynchronize(h->stream));
+        float t = 0.f;
+        HIPCHK(g_err, hipEventElapsedTime(&t, sb.ev0, sb.ev1));
+        total += t;
+        for (size_t o = 0; o < cb; o++)
+            for (size_t j = 0; j < capS; j++) {
+                const int r = rp[o * capS + j];
+                if (r < 0 || (size_t)r >= nd) continue;
+                std::memcpy(Jyg + ((c0 + o) * nd + r) * n, G.data() + (o * capS + j) * n, sizeof(double) * n);
+                if (Jyb) std::memcpy(Jyb + ((c0 + o) * nd + r) * nd, Bd.data() + (o * capS + j) * nd, sizeof(double) * nd);
+            }
+    }
+    h->rs.sensMs = total;
+    return 0;
+}
+
+extern "C" int lcqp_hip_batch_jacobian_duals(lcqp_hip_batch_t* h, int first, int count, double* Jyg, double* Jyb, int* side, int* info)
+{ return guarded(g_err, [&] {
+    if (!h || !Jyg || first < 0 || count < 1 || first > h->db.B - count) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return batch_jacobian_duals(h, first, count, Jyg, Jyb, side, info);
+}); }
+
+// ---- their device-pointer twins, and lcqp_hip_batch_jacobian's ----
+extern "C" int lcqp_hip_batch_adjoint_blocked_device(lcqp_hip_batch_t* h, int nrhs, const double* vx, const double* vy,
+                                                     double* dg, double* db, int* side, int* info, void* stream)
+{ return guarded(g_err, [&] {
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (nrhs < 1 || (!vx && !vy) || !dg) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    HIPCHK(g_err, hipSetDevice(h->device));
+    if (!sens_pointers_ok(g_err, h, h->db.nd, (size_t)h->db.B * nrhs, vx, "vx", vy, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
+    return device_call(g_err, h, stream, [&] {
+        float ms = 0.f;
+        return dense_adjoint_blocked(h, nrhs, vx, vy, true, dg, db, side, info, ms);
+    });
+}); }
+
+// the checks both Jacobian twins make: the range, then the four arrays with the bytes the call moves (rows: of one instance's two blocks)
+static int jacobian_device_checks(lcqp_hip_batch* h, int first, int count, size_t rows, const char* gname, double* Jg, const char* bname, double* Jb,
+                                  int* side, int* info)
+{
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!Jg || first < 0 || count < 1 || first > h->db.B - count) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    HIPCHK(g_err, hipSetDevice(h->device));
+    const size_t n = h->db.n, nd = h->db.nd, c = count;
+    if (!device_pointer_ok(g_err, h, gname, Jg, sizeof(double) * c * rows * n) || !device_pointer_ok(g_err, h, bname, Jb, sizeof(double) * c * rows * nd) ||
+        !device_pointer_ok(g_err, h, "side", side, sizeof(int) * c * nd, 4) || !device_pointer_ok(g_err, h, "info", info, sizeof(int) * c, 4)) return LCQP_INVALID_ARGUMENT;
+    return 0;
+}
+
+// np >= 1024: a Jacobian formed by the host twin (run) and copied to the caller's device arrays; waits on the host
+template <class R>
+static int jacobian_through_host(lcqp_hip_batch* h, size_t count, size_t rows, double* Jg, double* Jb, int* side, int* info, R run)
+{
+    const size_t n = h->db.n, nd = h->db.nd;
+    std::vector<double> G(count * rows * n), Bd(Jb ? count * rows * nd : 0);
+    std::vector<int> sd(count * nd), in(count);
+    if (int rc = run(G.data(), Jb ? Bd.data() : nullptr, sd.data(), in.data())) return rc;
+    HIPCHK(g_err, hipMemcpyAsync(Jg, G.data(), sizeof(double) * G.size(), hipMemcpyHostToDevice, h->stream));
+    if (Jb) HIPCHK(g_err, hipMemcpyAsync(Jb, Bd.data(), sizeof(double) * Bd.size(), hipMemcpyHostToDevice, h->stream));
+    if (side) HIPCHK(g_err, hipMemcpyAsync(side, sd.data(), sizeof(int) * sd.size(), hipMemcpyHostToDevice, h->stream));
+    if (info) HIPCHK(g_err, hipMemcpyAsync(info, in.data(), sizeof(int) * in.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(g_err, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+extern "C" int lcqp_hip_batch_jacobian_device(lcqp_hip_batch_t* h, int first, int count, double* Jg, double* Jb, int* side, int* info, void* stream)
+{ return guarded(g_err, [&] {
+    if (int rc = jacobian_device_checks(h, first, count, h ? h->db.n : 0, "Jg", Jg, "Jb", Jb, side, info)) return rc;
+    DevBatch& d = h->db;
+    const size_t n = d.n, nd = d.nd;
+    return device_call(g_err, h, stream, [&] {
+        if (!h->k->sensitivity_blk)
+            return jacobian_through_host(h, count, n, Jg, Jb, side, info, [&](double* G, double* Bd, int* sd, int* in) { return batch_jacobian(h, first, count, G, Bd, sd, in); });
+        // the chunks of batch_jacobian; every chunk's results go from the staging to their place with copies on the handle's stream
+        const size_t chunk = staging_chunk(h->sn.staging, sizeof(double) * n * (n + (size_t)d.np + nd + 2 * (size_t)d.capS), count);
+        float ms = 0.f, before = 0.f;      // before: the kernel time of the chunks in front of the last one (chunk_time)
+        for (size_t c0 = 0; c0 < (size_t)count; c0 += chunk) {
+            const size_t cb = std::min(chunk, (size_t)count - c0);
+            if (c0) if (int rc = chunk_time(g_err, h->sensBlk, before)) return rc;
+            if (int rc = dense_sensitivity(h, true, first + (int)c0, (int)cb, d.n, nullptr, nullptr, true, Jg + c0 * n * n, Jb ? Jb + c0 * n * nd : nullptr,
+                                           side ? side + c0 * nd : nullptr, info ? info + c0 : nullptr, ms)) return rc;
+        }
+        h->sn.pendingMs = before;
+        return 0;
+    });
+}); }
+
+extern "C" int lcqp_hip_batch_jacobian_duals_device(lcqp_hip_batch_t* h, int first, int count, double* Jyg, double* Jyb, int* side, int* info, void* stream)
+{ return guarded(g_err, [&] {
+    if (int rc = jacobian_device_checks(h, first, count, h ? h->db.nd : 0, "Jyg", Jyg, "Jyb", Jyb, side, info)) return rc;
+    DevBatch& d = h->db;
+    const size_t n = d.n, nd = d.nd;
+    return device_call(g_err, h, stream, [&] {
+        if (!h->k->sensitivity_blk_dual)
+            return jacobian_through_host(h, count, nd, Jyg, Jyb, side, info, [&](double* G, double* Bd, int* sd, int* in) { return batch_jacobian_duals(h, first, count, G, Bd, sd, in); });
+        // the rows k_pack_dual_rows does not write (outside W) are zero
+        HIPCHK(g_err, hipMemsetAsync(Jyg, 0, sizeof(double) * (size_t)count * nd * n, h->stream));
+        if (Jyb) HIPCHK(g_err, hipMemsetAsync(Jyb, 0, sizeof(double) * (size_t)count * nd * nd, h->stream));
+        const size_t chunk = staging_chunk(h->sn.staging, dual_jacobian_staging(d), count);
+        float before = 0.f;      // the kernel time of the chunks in front of the last one (chunk_time)
+        for (size_t c0 = 0; c0 < (size_t)count; c0 += chunk) {
+            const size_t cb = std::min(chunk, (size_t)count - c0);
+            if (c0) if (int rc = chunk_time(g_err, h->sensDual, before)) return rc;
+            if (int rc = dual_jacobian_launch(h, first + (int)c0, (int)cb)) return rc;
+            const SensBuffers& sb = h->sensDual;
+            launch_pack_dual_rows(d, h->stream, (int)cb, (int)sb.ldDb, sb.dg, sb.db, dual_rowpos(h, (int)cb), Jyg + c0 * nd * n, Jyb ? Jyb + c0 * nd * nd : nullptr);
+            HIPCHK(g_err, hipGetLastError());
+            if (side) HIPCHK(g_err, hipMemcpyAsync(side + c0 * nd, sb.side, sizeof(int) * cb * nd, hipMemcpyDeviceToDevice, h->stream));
+            if (info) HIPCHK(g_err, hipMemcpyAsync(info + c0, sb.info, sizeof(int) * cb, hipMemcpyDeviceToDevice, h->stream));
+        }
+        h->sn.sensPending = 3;
+        h->sn.pendingMs = before;
+        return 0;
     });
 }); }

@@ -42,6 +42,7 @@ struct lcqp_hip_batch {
     std::vector<char> boxed;              // [B][n]
     lcqp_rt::SensState sn;                // sn.sens: of k_sensitivity
     lcqp_rt::SensBuffers sensBlk;         // of k_sensitivity_blk (another pitch of db, a varying number of instances)
+    lcqp_rt::SensBuffers sensDual;        // of the dual Jacobian: capS staged rows per instance, no v, the row map behind `side`
     // of the device-pointer entry points (lcqp_hip_device.hip): the events of the hand-over between the caller's stream and `stream`; the
     // status words of k_check_vectors followed by the box flags of a load ([2] x 8 bytes, then [B][n] bytes)
     lcqp_rt::Event evIn{hipEventDisableTiming}, evOut{hipEventDisableTiming};
@@ -63,6 +64,13 @@ int batch_sensitivity(lcqp_hip_batch* h, bool blk, int nrhs, const double* v, do
 int batch_jacobian(lcqp_hip_batch* h, int first, int count, double* Jg, double* Jb, int* side, int* info);
 int batch_adjoint(lcqp_hip_batch* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
                   int reduce, double* dQ, double* dA, double* dL, double* dR);
+
+int batch_adjoint_blocked(lcqp_hip_batch* h, int nrhs, const double* vx, const double* vy, double* dg, double* db, int* side, int* info);
+int batch_jacobian_duals(lcqp_hip_batch* h, int first, int count, double* Jyg, double* Jyb, int* side, int* info);
+// lcqp_hip_device.hip: k_pack_dual_rows on `count` instances -- staged row j of instance o (dg pitch np, db pitch ldb) goes to row
+// rowpos[o][j] of Jyg [count][nd][n] and Jyb [count][nd][nd] (or null); rowpos < 0: the row is not part of the result
+void launch_pack_dual_rows(const lcqp::DevBatch& d, hipStream_t s, int count, int ldb, const double* dg, const double* db, const int* rowpos,
+                           double* Jyg, double* Jyb);
 
 // the message of lcqp_hip_batch_update and its device twin for a variable whose box bound appears or disappears
 inline std::string box_change_message(int variable, int instance, bool gains)

@@ -159,9 +159,35 @@ __global__ __launch_bounds__(WG) void k_pack_matrices(DevBatch db, int first, in
     }
 }
 
+// ---- k_pack_dual_rows: the staged rows of a dual Jacobian to their rows of the caller's arrays (lcqp_hip_batch_jacobian_duals_device) ----
+// blockIdx.x: the staged row j < capS, blockIdx.y (strided): the instance o of the chunk.  rowpos [count][capS]: the dual position r < nd of
+// staged row j, or -1 -- no two staged rows of an instance share a position, so no element is written twice.  dg [count][capS][np] and
+// db [count][capS][ldb] as k_sensitivity_blk left them; Jyg [count][nd][n], Jyb [count][nd][nd] or null.
+__global__ __launch_bounds__(WG) void k_pack_dual_rows(int count, int capS, int n, int np, int nd, int ldb, const double* dg, const double* dbs,
+                                                       const int* rowpos, double* Jyg, double* Jyb)
+{
+    const int j = blockIdx.x, t = threadIdx.x;
+    for (int o = blockIdx.y; o < count; o += gridDim.y) {
+        const size_t row = (size_t)o * capS + j;
+        const int r = rowpos[row];
+        if (r < 0 || r >= nd) continue;
+        double* og = Jyg + ((size_t)o * nd + r) * n;
+        for (int i = t; i < n; i += WG) og[i] = dg[row * np + i];
+        if (!Jyb) continue;
+        double* ob = Jyb + ((size_t)o * nd + r) * nd;
+        for (int i = t; i < nd; i += WG) ob[i] = dbs[row * ldb + i];
+    }
+}
+
 // =================================================================================================
 // host side
 // =================================================================================================
+void launch_pack_dual_rows(const DevBatch& d, hipStream_t s, int count, int ldb, const double* dg, const double* db, const int* rowpos,
+                           double* Jyg, double* Jyb)
+{
+    hipLaunchKernelGGL(k_pack_dual_rows, dim3(d.capS, std::min(count, 65535)), dim3(WG), 0, s, count, d.capS, d.n, d.np, d.nd, ldb, dg, db, rowpos, Jyg, Jyb);
+}
+
 #define g_err dense_err()      // the error slot of the dense arm (thread_local, lcqp_hip.hip)
 
 // the status words (and, for a load, the box flags behind them) of k_check_vectors: [2] words, then [B][n] bytes

@@ -286,8 +286,27 @@ __global__ __launch_bounds__(WG) void k_sensitivity(DevBatch db, int nrhs, const
 constexpr int SENS_PANEL = 16;
 constexpr int SENS_PA = 66;
 
-template <int NCH>
-__global__ __launch_bounds__(WG) void k_sensitivity_blk(DevBatch db, int first, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo)
+//
+// DUAL (DESIGN.md section 3a'''', "Panels with gradients on y"; lcqp_hip_batch_adjoint_blocked / _jacobian_duals): the slot-space right-hand
+// side of k_sensitivity<NCH, true> for a panel.  Without DUAL vy, unit and rowpos are not read, and the code is the one above.
+//   unit == 0: S <- Et_W C + V_y,W with V_y,W(a, j) = vy[j][pos(idx[a])] on the occupied slots a < ns and zero elsewhere, added where S is
+//     stored to the slot-space scratch, before U = Ti S.  vy [count][nrhs][nd] or null.  v == null is a ZERO panel here (not unit vectors):
+//     the forward substitution and S = Et_W C are not run at all, S = V_y,W.
+//   unit == 1: column j of the call is the unit vector of the j-th occupied slot (idx[s] >= 0, s < ns, in slot order), written straight into
+//     S; v and vy are not read, nothing is substituted forward.  The call has min(nrhs, occupied slots) columns (nrhs <= capS staged rows per
+//     instance); rowpos [count][capS] receives pos(idx[s(j)]) for every staged row j and -1 behind them: where the row belongs in y.  An
+//     instance without a solution gets -1 throughout and no rows.
+// A column depends on its own columns of X and V_y only, through the same instructions wherever it stands (the sums over slots and rows run
+// in the order of the kernel above whatever the other columns hold).
+// Registers: the figures above (174 - 184 VGPRs + 8 AGPRs, at most 192 unified) are those of DUAL = false.  The DUAL build takes 188 / 189 /
+// 178 / 185 VGPRs + 8 AGPRs for NCH = 1 .. 4, i.e. 196 / 197 / 186 / 193 unified registers: above 192 at three sizes, without scratch.  That
+// costs nothing at run time -- a workgroup is one wave per SIMD, the occupancy steps of two and one workgroups per CU lie at 256 and 512
+// registers, and LDS bounds np >= 384 to one workgroup anyway -- but it leaves no headroom: a change that adds registers here should be
+// looked at with csrc/resusage.sh.  (The V_y,W pass is a loop of its own and the ranks come from mbcnt for this reason.)
+// The body of both kernels (k_sensitivity_blk: DUAL = false; k_sensitivity_blk_dual: DUAL = true, below it).
+template <int NCH, bool DUAL>
+__device__ __forceinline__ void sensitivity_blk(const DevBatch& db, int first, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo,
+                                                const double* vy, int unit, int* rowpos)
 {
     constexpr int np = 128 * NCH, P = SENS_PANEL, PA = SENS_PA;
     static_assert(P == 16, "one 16-column MFMA block per wave and row block");
@@ -305,10 +324,12 @@ __global__ __launch_bounds__(WG) void k_sensitivity_blk(DevBatch db, int first, 
     int* sd = side + (size_t)o * nd;
     for (int i = t; i < nd; i += WG) sd[i] = 0;
     if (!solved) {      // (uniform) nothing to differentiate: zero outputs
-        for (int k = 0; k < nrhs; k++) {
+        const bool rowsOnly = DUAL && unit;      // (the staged rows of a dual Jacobian are read through rowpos only)
+        for (int k = 0; k < nrhs && !rowsOnly; k++) {
             wg_fill(dg + ((size_t)o * nrhs + k) * np, 0.0, np);
             wg_fill(dbo + ((size_t)o * nrhs + k) * ldb, 0.0, ldb);
         }
+        if constexpr (DUAL) { if (unit) for (int j = t; j < capS; j += WG) rowpos[(size_t)o * capS + j] = -1; }
         if (t == 0) sinfo[o] = 1;
         return;
     }
@@ -318,6 +339,28 @@ __global__ __launch_bounds__(WG) void k_sensitivity_blk(DevBatch db, int first, 
     const double *F1 = c.F1, *Et = c.Et, *Ti = c.S;
     auto pos = [&](int r) { return r < mA ? n + r : boxidx[r - mA]; };
     sens_marks<NCH>(db, c, lds, sd, sinfo + o);
+    // (DUAL, unit) the occupied slots in slot order: wave 0 calls f(a, rank) for the rank-th occupied slot a; every wave returns their number
+    auto occupied = [&](auto f) {
+        int cnt = 0;
+        for (int a0 = 0; a0 < ns; a0 += 64) {
+            const int a = a0 + lane;
+            const bool occ = a < ns && idx[a] >= 0;
+            const unsigned long long m = __ballot(occ);
+            // (mbcnt: the occupied lanes below this one, without a lane mask that would stay in registers over the product loops)
+            if (occ && w == 0) f(a, cnt + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u)));
+            cnt += __popcll(m);
+        }
+        return cnt;
+    };
+    int ncols = nrhs;
+    if constexpr (DUAL) {
+        if (unit) {
+            int* rp = rowpos + (size_t)o * capS;
+            const int nocc = occupied([&](int a, int rank) { rp[rank] = rank < nrhs ? pos(idx[a]) : -1; });
+            ncols = min(nrhs, nocc);
+            for (int j = nocc + t; j < capS; j += WG) rp[j] = -1;
+        }
+    }
 
     // a 64 x 64 block of a matrix on its way into As: thread t carries the column pair 2 (t & 31) of the rows (t >> 5) + 8 i
     const int ar = t >> 5, ac = (t & 31) * 2;
@@ -352,8 +395,8 @@ __global__ __launch_bounds__(WG) void k_sensitivity_blk(DevBatch db, int first, 
     };
 
     #pragma nounroll
-    for (int k0 = 0; k0 < nrhs; k0 += P) {
-        const int pv = min(P, nrhs - k0);      // columns of this panel that are vectors of the call
+    for (int k0 = 0; k0 < ncols; k0 += P) {
+        const int pv = min(P, ncols - k0);      // columns of this panel that are vectors of the call
         const size_t row0 = (size_t)o * nrhs + k0;
         // entry (a, j) of the slot-space panels: S, then Lambda, at offset nd of vector j's row of dbo; U at nd + capS
         auto slotp = [&](int which, int a, int j) -> double* { return dbo + (row0 + j) * ldb + nd + which * capS + a; };
@@ -373,11 +416,12 @@ __global__ __launch_bounds__(WG) void k_sensitivity_blk(DevBatch db, int first, 
                 for (int q = 0; q < 4; q++) *slotp(which, a0 + 16 * w + kl + 4 * q, il) = acc[q];
             }
         };
-        const int skip = v ? 0 : (k0 >> 6);      // unit vectors: the block rows above the first unit entry stay zero in the forward substitution
+        const int skip = (DUAL || v) ? 0 : (k0 >> 6);      // unit vectors: the block rows above the first unit entry stay zero in the forward substitution
         for (int e = t; e < np * P; e += WG) {
             const int j = e / np, i = e - j * np;
             double x = 0.0;
-            if (i < n && j < pv) x = v ? v[(row0 + j) * n + i] : (i == k0 + j ? 1.0 : 0.0);
+            if constexpr (DUAL) { if (v && i < n && j < pv) x = v[(row0 + j) * n + i]; }
+            else if (i < n && j < pv) x = v ? v[(row0 + j) * n + i] : (i == k0 + j ? 1.0 : 0.0);
             Xs[i * P + j] = x;
         }
         for (int j = 0; j < pv; j++) wg_fill(dbo + (row0 + j) * ldb, 0.0, nd);
@@ -415,7 +459,7 @@ __global__ __launch_bounds__(WG) void k_sensitivity_blk(DevBatch db, int first, 
                 __syncthreads();
             }
         };
-        trisolve(true);
+        if (!DUAL || v) trisolve(true);      // (DUAL without X: C = 0, nothing to substitute)
         if (nT > 0) {
             // rows of Et held by the slots 64 sb .. 64 sb + 63, columns 64 J .. 64 J + 63
             auto etBlk = [&](int sb, int J) {
@@ -432,7 +476,7 @@ __global__ __launch_bounds__(WG) void k_sensitivity_blk(DevBatch db, int first, 
             };
             // S = Et_W C
             #pragma nounroll
-            for (int sb = 0; sb < nsb; sb++) {
+            for (int sb = 0; sb < ((!DUAL || v) ? nsb : 0); sb++) {
                 d4_t acc{0.0, 0.0, 0.0, 0.0};
                 loadA(etBlk(sb, 0), all);
                 #pragma nounroll
@@ -444,6 +488,25 @@ __global__ __launch_bounds__(WG) void k_sensitivity_blk(DevBatch db, int first, 
                     __syncthreads();
                 }
                 storeSlot(0, 64 * sb, acc);
+            }
+            if constexpr (DUAL) {
+                // S <- S + V_y,W in the scratch, before U = Ti S reads it (a pass of its own over at most capS x 16 entries: the addresses of vy
+                // stay out of the product loops' registers).  No X: S is V_y,W itself, or the unit vectors of the occupied slots k0 .. k0 + pv - 1.
+                if (!v || vy) {
+                    if (v) __syncthreads();
+                    const int rows = 64 * nsb;
+                    for (int e = t; e < rows * pv; e += WG) {
+                        const int j = e / rows, a = e - j * rows;
+                        const int r = (!unit && vy && a < ns) ? idx[a] : -1;
+                        double s = v ? *slotp(0, a, j) : 0.0;
+                        if (r >= 0) s += vy[(row0 + j) * nd + pos(r)];
+                        *slotp(0, a, j) = s;
+                    }
+                    if (unit) {
+                        __syncthreads();
+                        occupied([&](int a, int rank) { if (rank >= k0 && rank < k0 + pv) *slotp(0, a, rank - k0) = 1.0; });
+                    }
+                }
             }
             __syncthreads();
             // U = Ti S
@@ -515,6 +578,19 @@ __global__ __launch_bounds__(WG) void k_sensitivity_blk(DevBatch db, int first, 
             }
         __syncthreads();
     }
+}
+
+template <int NCH>
+__global__ __launch_bounds__(WG) void k_sensitivity_blk(DevBatch db, int first, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo)
+{
+    sensitivity_blk<NCH, false>(db, first, nrhs, v, dg, dbo, side, sinfo, nullptr, 0, nullptr);
+}
+
+template <int NCH>
+__global__ __launch_bounds__(WG) void k_sensitivity_blk_dual(DevBatch db, int first, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo,
+                            const double* vy, int unit, int* rowpos)
+{
+    sensitivity_blk<NCH, true>(db, first, nrhs, v, dg, dbo, side, sinfo, vy, unit, rowpos);
 }
 
 // ---- k_build_C: C = L'R + R'L (Utilities::MatrixSymmetrizationProduct, src/Utilities.cpp:104-116) ----
@@ -1201,9 +1277,15 @@ const SizeKernels& size_kernels()
         t.prepare = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_prepare<NCH>), dim3(grid), dim3(WG), 0, s, db); };
         t.refresh = [](const DevBatch& db, int grid, hipStream_t s, int mode, const double* rho0) { hipLaunchKernelGGL((k_refresh<NCH>), dim3(grid), dim3(WG), 0, s, db, mode, rho0); };
         if constexpr (NCH <= 4)      // np <= 512 only: a panel of np >= 1024 does not fit LDS
+        {
             t.sensitivity_blk = [](const DevBatch& db, int grid, hipStream_t s, int first, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo) {
                 hipLaunchKernelGGL((k_sensitivity_blk<NCH>), dim3(grid), dim3(WG), 0, s, db, first, nrhs, v, dg, dbo, side, sinfo);
             };
+            t.sensitivity_blk_dual = [](const DevBatch& db, int grid, hipStream_t s, int first, int nrhs, const double* v, const double* vy, int unit,
+                                        double* dg, double* dbo, int* side, int* sinfo, int* rowpos) {
+                hipLaunchKernelGGL((k_sensitivity_blk_dual<NCH>), dim3(grid), dim3(WG), 0, s, db, first, nrhs, v, dg, dbo, side, sinfo, vy, unit, rowpos);
+            };
+        }
         t.sensitivity = [](const DevBatch& db, int grid, hipStream_t s, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo) {
             hipLaunchKernelGGL((k_sensitivity<NCH, false>), dim3(grid), dim3(WG), 0, s, db, nrhs, v, dg, dbo, side, sinfo, nullptr);
         };

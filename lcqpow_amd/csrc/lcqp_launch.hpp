@@ -35,6 +35,11 @@ struct SizeKernels {
     void (*sensitivity)(const DevBatch& db, int grid, hipStream_t s, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo);
     void (*sensitivity_dual)(const DevBatch& db, int grid, hipStream_t s, int nrhs, const double* v, const double* vy, double* dg, double* dbo, int* side, int* sinfo);
     void (*sensitivity_blk)(const DevBatch& db, int grid, hipStream_t s, int first, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo);
+    // k_sensitivity_blk_dual<NCH> (null for NCH > 4).  unit 0: panels of pairs, v [count][nrhs][n] or null (a zero panel: no forward
+    // substitution), vy [count][nrhs][nd] or null.  unit 1: the unit vectors of the slot space, nrhs <= capS staged rows per instance, and
+    // rowpos [count][capS]: the dual position of every staged row, -1 behind the last occupied slot
+    void (*sensitivity_blk_dual)(const DevBatch& db, int grid, hipStream_t s, int first, int nrhs, const double* v, const double* vy, int unit,
+                                 double* dg, double* dbo, int* side, int* sinfo, int* rowpos);
     // building-block kernels
     void (*util_symv)(int grid, hipStream_t s, int n, double alpha, const double* A, const double* b, const double* c, double* d);
     void (*util_rows)(int grid, hipStream_t s, int m, const double* A, const double* x, double* dots, const double* coef, double* outT);

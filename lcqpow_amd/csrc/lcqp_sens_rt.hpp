@@ -19,8 +19,11 @@ struct SensState {
     size_t adjVyCap = 0, adjOutCap = 0;
     Event adjEv0, adjEv1;                 // around the last matrix-gradient launch
     // which events still hold the kernel time of the last sensitivity_device / adjoint_device call: 0: none, 1: sens, 2: the arm's second
-    // SensBuffers (dense: sensBlk); + 4: adjEv0 / adjEv1 as well
+    // SensBuffers (dense: sensBlk), 3: its third (dense: sensDual); + 4: adjEv0 / adjEv1 as well
     int sensPending = 0;
+    // a device-pointer call that went in chunks: the kernel time of the chunks before the last one (their events are reused), added to
+    // what the pending events hold
+    float pendingMs = 0.f;
 };
 
 // a device buffer of the handle with room for `count` doubles (the stream is drained before a smaller one is freed)
@@ -81,6 +84,7 @@ int sensitivity_call(std::string& err, H* h, SensBuffers& sb, const SensPitch& p
     HIPCHK(err, hipSetDevice(h->device));
     if (int rc = sb.reserve(err, h->mem, h->stream, count, nrhs, p.ldV, p.ldDg, p.ldDb, p.nd)) return rc;
     sn.sensPending = 0;
+    sn.pendingMs = 0.f;
     if (v && !dev) if (int rc = sb.upload(err, v)) return rc;
     const double *dv = dev ? v : (v ? sb.v : nullptr), *dvy = vy;
     if (vy && !dev) {      // (the DUAL instantiation of *_adjoint: vy [count][nrhs][nd] from the host)
@@ -171,15 +175,26 @@ int adjoint_chunks(std::string& err, H* h, size_t perInst, size_t pad, int reduc
     return 0;
 }
 
+// Between two chunks of a device-pointer call: wait for the chunk's kernel and add its time to acc -- the next chunk reuses the events and
+// the staging.  (Only a call whose staging exceeds the cap has more than one chunk; the last chunk's time stays in the events.)
+inline int chunk_time(std::string& err, const SensBuffers& sb, float& acc)
+{
+    float t = 0.f;
+    HIPCHK(err, hipEventSynchronize(sb.ev1));
+    HIPCHK(err, hipEventElapsedTime(&t, sb.ev0, sb.ev1));
+    acc += t;
+    return 0;
+}
+
 // *_sensitivity_timing: the kernel time of the last sensitivity call (ResolveState::sensMs).  After a device-pointer call the time is still in
-// the events: wait for them and form it.  second: the SensBuffers behind sensPending = 2 (the dense arm's sensBlk).
+// the events: wait for them and form it.  second, third: the SensBuffers behind sensPending = 2 and 3 (the dense arm's sensBlk and sensDual).
 template <class H>
-int sensitivity_timing(std::string& err, H* h, float* kernel_ms, const SensBuffers* second = nullptr)
+int sensitivity_timing(std::string& err, H* h, float* kernel_ms, const SensBuffers* second = nullptr, const SensBuffers* third = nullptr)
 {
     if (h && h->sn.sensPending) {
         SensState& sn = h->sn;
         HIPCHK(err, hipSetDevice(h->device));
-        const SensBuffers& sb = (sn.sensPending & 3) == 2 ? *second : sn.sens;
+        const SensBuffers& sb = (sn.sensPending & 3) == 3 ? *third : ((sn.sensPending & 3) == 2 ? *second : sn.sens);
         float t = 0.f, ta = 0.f;
         HIPCHK(err, hipEventSynchronize(sb.ev1));
         HIPCHK(err, hipEventElapsedTime(&t, sb.ev0, sb.ev1));
@@ -187,8 +202,9 @@ int sensitivity_timing(std::string& err, H* h, float* kernel_ms, const SensBuffe
             HIPCHK(err, hipEventSynchronize(sn.adjEv1));
             HIPCHK(err, hipEventElapsedTime(&ta, sn.adjEv0, sn.adjEv1));
         }
-        h->rs.sensMs = t + ta;
+        h->rs.sensMs = t + ta + sn.pendingMs;
         sn.sensPending = 0;
+        sn.pendingMs = 0.f;
     }
     if (!h || !kernel_ms || h->rs.sensMs < 0.f) return LCQP_INVALID_ARGUMENT;
     *kernel_ms = h->rs.sensMs;

@@ -455,12 +455,29 @@ class BatchLCQPLayer:
             self._held = {k: np.stack([p[k] for p in ps]) for k in MATRIX_KEYS}
         return self._held
 
-    def jacobian(self, serial=None):
+    def jacobian(self, serial=None, duals=False):
         """dx/dg of the layer's last solve, [B][nV][nV] ([b][k][j] = dx_k/dg_j), a tensor of the dtype and on the device of that
         solve's g (BatchLCQP.jacobian / SparseBatchLCQP.jacobian: the arm's blocked kernel on the unit vectors).  serial: the value of layer.solves right
-        after the solve that is meant -- like backward, the call raises when that is not the last one.  layer.info holds the flags."""
+        after the solve that is meant -- like backward, the call raises when that is not the last one.  layer.info holds the flags.
+        duals=True (dense batch): the whole solution map D(x, y) / D(g, b_W) as a dict of the four blocks -- xg [B][nV][nV], xb [B][nV][nd],
+        yg [B][nd][nV], yb [B][nd][nd] (BatchLCQP.jacobian and .jacobian_duals) -- and side [B][nd]; with the last solve's g on the GPU of the
+        batch the device-pointer twins write device tensors (layer.last_path = "device"), else the host calls run ("host")."""
         if self.solves == 0 or (serial is not None and serial != self.solves):
             raise RuntimeError("jacobian of a solve that is not the layer's last one: the batch object holds the state of one solve")
+        if duals:
+            dtype, device = self._like
+            on_device = device.type == "cuda" and device.index == getattr(self.bt, "device", None)
+            self.last_path = "device" if on_device else "host"
+            if on_device:
+                xg, xb, side, info = self.bt.jacobian_device()
+                yg, yb, _, _ = self.bt.jacobian_duals_device()
+            else:
+                xg, xb, side, info = self.bt.jacobian()
+                yg, yb, _, _ = self.bt.jacobian_duals()
+            self.info = info if not on_device else info.cpu().numpy()
+            out = {k: torch.as_tensor(v, device=device).to(dtype) for k, v in dict(xg=xg, xb=xb, yg=yg, yb=yb).items()}
+            out["side"] = torch.as_tensor(side, device=device)
+            return out
         Jg, _, _, info = self.bt.jacobian(bounds=False)
         self.info = info
         return torch.as_tensor(Jg, dtype=self._like[0], device=self._like[1])
@@ -495,6 +512,10 @@ class SparseBatchLCQPLayer(BatchLCQPLayer):
                 if v.shape not in ((batch.B, nnz[k]), (nnz[k],)):
                     raise ValueError(f"values[{k!r}]: expected [{batch.B}][{nnz[k]}] or [{nnz[k]}], got {v.shape}")
                 self.values[k] = np.ascontiguousarray(np.broadcast_to(v, (batch.B, nnz[k])))
+
+    def jacobian(self, serial=None):
+        """BatchLCQPLayer.jacobian without the dual blocks: the sparse arm has no panel call for them"""
+        return super().jacobian(serial)
 
     def _values(self):
         """the value arrays the batch holds, [B][nnz] each, for a load on the host path"""

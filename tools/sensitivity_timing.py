@@ -15,6 +15,11 @@ interleaved, for nrhs = 1, 16, 64, 256 on the BASELINE shape (B = 1024, n = 256,
 then jacobian() beside the vector call on an uploaded identity, kernel time and wall clock.
     python tools/sensitivity_timing.py --blocked [--quick] [--log FILE] [--reps 20]
 
+--blocked --duals: jacobian_duals() (k_sensitivity_blk_dual on the unit vectors of the slot space) beside the loop of vector adjoint calls it
+replaces -- one lcqp_hip_batch_adjoint call per dual position in some instance's working set -- on the BASELINE shape with B = 4 and
+B = 1024 (256 with --quick), one handle, interleaved; kernel time summed over the launches, and wall clock.
+    python tools/sensitivity_timing.py --blocked --duals [--quick] [--log FILE] [--reps 20]
+
 --adjoint: lcqp_hip_batch_adjoint with all four matrix gradients on the BASELINE shape and on (40, 20, 8), B = 1024 (256 with --quick):
 reduce = 1 (k_adjoint_reduce, (nV + mA) nV doubles to the host) beside reduce = 0 (k_adjoint_outer in chunks, B times as many) on the same
 handle in the same process, the calls interleaved; kernel time (the sum of the call's kernels, k_sensitivity included) and wall clock.
@@ -149,6 +154,60 @@ def measure_blocked(B, n, nC, nComp, nrhs_list, reps, warmup=3):
     print(lines[-1], flush=True)
     bt.close()
     return lines
+
+
+def measure_duals(B, n, nC, nComp, reps, warmup=1):
+    """jacobian_duals() beside the loop of vector adjoint calls it replaces -- one call with vx = 0, vy = e_r per dual position r that is in
+    the working set of some instance -- on one handle, interleaved: kernel time (summed over the launches) and wall clock"""
+    bt = la.BatchLCQP(B, n, nC, nComp, opt=la.default_options())
+    bt.generate_synthetic(0)
+    bt.run()
+    nd = n + nC + 2 * nComp
+    side = bt.sensitivity(np.zeros((B, n)))[2]
+    rows = np.flatnonzero(np.any(side != 0, axis=0))
+    nW = np.count_nonzero(side, axis=1)
+    zero = np.zeros((B, n))
+    stat = lambda ms: (float(np.min(ms)), float(np.median(ms)), float(np.max(ms)))
+    kj, wj, kv, wv = [], [], [], []
+    worst = 0.0
+    for rep in range(warmup + reps):
+        # (the bound block is [B][nd][nd] on the host: asked for with a few instances only; the kernel is the same either way)
+        t = time.perf_counter(); Jyg, Jyb = bt.jacobian_duals(bounds=B <= 64)[:2]; w1 = time.perf_counter() - t
+        k1 = bt.sensitivity_kernel_ms()
+        k0 = 0.0
+        t = time.perf_counter()
+        for r in rows:
+            vy = np.zeros((B, nd)); vy[:, r] = 1.0
+            out = bt.adjoint(zero, vy, matrices=())
+            k0 += bt.sensitivity_kernel_ms()
+            if rep == 0:
+                inW = side[:, r] != 0
+                worst = max(worst, float(np.abs(out["dg"][inW] - Jyg[inW, r]).max(initial=0.0)))
+                if Jyb is not None:
+                    worst = max(worst, float(np.abs(out["db"][inW] - Jyb[inW, r]).max(initial=0.0)))
+        w0 = time.perf_counter() - t
+        if rep >= warmup:
+            kj.append(k1); wj.append(1e3 * w1); kv.append(k0); wv.append(1e3 * w0)
+    a, b = stat(kv), stat(kj)
+    line = ("n = %d nC = %d nComp = %d B = %d: rows of W per instance min / mean / max = %d / %.1f / %d, %d vector calls per loop; loop of vector adjoint calls: "
+            "kernel ms min / median / max = %.3f / %.3f / %.3f, wall ms median %.1f; jacobian_duals(): kernel ms = %.3f / %.3f / %.3f, wall ms median %.1f; "
+            "vector median / blocked median = %.2f (kernels), %.2f (wall); max |loop - jacobian_duals| = %.3g"
+            % ((n, nC, nComp, B, nW.min(), nW.mean(), nW.max(), len(rows)) + a + (float(np.median(wv)),) + b + (float(np.median(wj)),)
+               + (a[1] / b[1], float(np.median(wv)) / float(np.median(wj)), worst)))
+    print(line, flush=True)
+    bt.close()
+    return line
+
+
+def duals_main(a):
+    reps = a.reps
+    lines = [measure_duals(B, 256, 512, 64, reps) for B in ((4, 256) if a.quick else (4, 1024))]
+    if a.log:
+        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
+        with open(a.log, "w") as f:
+            f.write("lcqp_hip_batch_jacobian_duals beside the loop of lcqp_hip_batch_adjoint calls it replaces, synthetic workload after run, one handle, "
+                    "calls interleaved; %d timed repetitions after 1 warm-up repetition each\n" % reps)
+            f.write("\n".join(lines) + "\n")
 
 
 def measure_adjoint(B, n, nC, nComp, reps, warmup=3):
@@ -363,6 +422,7 @@ def main():
     ap.add_argument("--sparse", action="store_true", help="the sparse arm's kernel beside a warm resolve of unchanged data")
     ap.add_argument("--quick", action="store_true", help="--sparse: without the n = 4096, B = 4096 batch; --blocked: B = 256 at n = 256, without nrhs = 256")
     ap.add_argument("--blocked", action="store_true", help="the blocked kernel beside the vector kernel, and the Jacobian")
+    ap.add_argument("--duals", action="store_true", help="--blocked: the dual Jacobian beside the loop of vector adjoint calls it replaces (B = 4 and B = 1024; --quick: 256)")
     ap.add_argument("--adjoint", action="store_true", help="the matrix gradients summed on the device beside the per-instance path")
     ap.add_argument("--general-panel", action="store_true", help="--sparse --blocked: the general LDL' with its panel form off and on, on one handle")
     ap.add_argument("--grids", default="44,128", help="--general-panel: grid sizes")
@@ -381,6 +441,8 @@ def main():
         return sparse_blocked_main(a)
     if a.sparse:
         return sparse_main(a)
+    if a.blocked and a.duals:
+        return duals_main(a)
     if a.blocked:
         return blocked_main(a)
     if a.adjoint:
