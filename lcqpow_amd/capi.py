@@ -1,4 +1,5 @@
 """ctypes binding of the C ABI in include/lcqp_hip.h (liblcqpow_hip.so).  No CPU fallback."""
+import contextlib
 import ctypes as C
 import os
 import sys
@@ -332,6 +333,14 @@ def _jacobian(call, B, nV, nd, first, count, bounds, check=None, rows=None):
     return Jg, Jb, side, info
 
 
+def _bound_slices(lo, hi, nV, nC, nComp, sparse):
+    """lo / hi: db where the row sits on its lower / upper bound, zero elsewhere (numpy or torch), cut into the bound vectors"""
+    a = 0 if sparse else nV
+    l, r = a + nC, a + nC + nComp
+    return dict(dlb=lo[..., :a], dub=hi[..., :a], dlbA=lo[..., a:l], dubA=hi[..., a:l], dlbL=lo[..., l:r], dubL=hi[..., l:r],
+                dlbR=lo[..., r:], dubR=hi[..., r:])
+
+
 def split_bound_derivatives(db, side, nV, nC, nComp, sparse=False):
     """db and side of a sensitivity call (the reference's dual layout: box rows first, then A, L, R; sparse=True: the layout of
     SparseBatchLCQP.sensitivity, which has no box rows -- dlb and dub are then empty) as derivatives with respect to the
@@ -343,10 +352,7 @@ def split_bound_derivatives(db, side, nV, nC, nComp, sparse=False):
     db = np.asarray(db); side = np.asarray(side)
     sd = side if db.ndim == side.ndim else side[:, None, :]
     lo = np.where((sd == -1) | (sd == 2), db, 0.0); hi = np.where((sd == 1) | (sd == 2), db, 0.0)
-    a = 0 if sparse else nV
-    l, r = a + nC, a + nC + nComp
-    return dict(dlb=lo[..., :a], dub=hi[..., :a], dlbA=lo[..., a:l], dubA=hi[..., a:l], dlbL=lo[..., l:r], dubL=hi[..., l:r],
-                dlbR=lo[..., r:], dubR=hi[..., r:])
+    return _bound_slices(lo, hi, nV, nC, nComp, sparse)
 
 
 def split_bound_derivatives_torch(db, side, nV, nC, nComp, sparse=False):
@@ -354,10 +360,7 @@ def split_bound_derivatives_torch(db, side, nV, nC, nComp, sparse=False):
     sd = side if db.dim() == side.dim() else side[:, None, :]
     zero = db.new_zeros(())
     lo = db.where((sd == -1) | (sd == 2), zero); hi = db.where((sd == 1) | (sd == 2), zero)
-    a = 0 if sparse else nV
-    l, r = a + nC, a + nC + nComp
-    return dict(dlb=lo[..., :a], dub=hi[..., :a], dlbA=lo[..., a:l], dubA=hi[..., a:l], dlbL=lo[..., l:r], dubL=hi[..., l:r],
-                dlbR=lo[..., r:], dubR=hi[..., r:])
+    return _bound_slices(lo, hi, nV, nC, nComp, sparse)
 
 
 class SubsolverHIP:
@@ -559,8 +562,11 @@ class BatchPipeline:
 
 class _Batch:
     """What BatchLCQP and SparseBatchLCQP have in common: the entry points both arms of the C ABI export under their own prefix.  A
-    subclass sets _prefix ("lcqp_hip_batch_" / "lcqp_hip_sparse_"), _ndual (entries of an instance's dual vector) and _last_error()
-    (the arm's error string), and keeps its constructor, load / update (the argument orders differ) and the arm-only methods."""
+    subclass sets _prefix ("lcqp_hip_batch_" / "lcqp_hip_sparse_"), _ndual (entries of an instance's dual vector), _last_error()
+    (the arm's error string), _vectors (the vectors of a load / update in the C argument order, each with the attribute that holds its
+    length), _shapes (the matrices of adjoint by name, each with the shape of one instance's gradient) and _staging_setter (the entry
+    point that sets the staging cap of jacobian and adjoint).  It keeps its constructor, load / update (the argument orders differ),
+    the calls whose defaults differ (adjoint, adjoint_device, sensitivity_device: their bodies are here) and the arm-only methods."""
 
     def _sym(self, name):
         return getattr(lib(), self._prefix + name)
@@ -630,8 +636,49 @@ class _Batch:
     def algorithmic_bytes(self):
         return self._sym("algorithmic_bytes")(self.h)
 
+    def _vector_sizes(self):
+        """[(name, doubles per instance)] of the vectors of a load / update, in the C argument order"""
+        return [(nm, getattr(self, attr)) for nm, attr in self._vectors]
+
+    @staticmethod
+    def _host_args(table, count, values):
+        """`values` in the order of `table` [(name, doubles per instance)] as the contiguous float64 arrays of a host load / update"""
+        return [_sized(nm, _arr(v), count * sz) for (nm, sz), v in zip(table, values)]
+
+    @contextlib.contextmanager
+    def _staging(self, nbytes):
+        """another staging cap for the calls inside (None: the cap stays as it is), the default cap again afterwards"""
+        if nbytes is not None:
+            self._call(self._staging_setter, int(nbytes))
+        try:
+            yield
+        finally:
+            if nbytes is not None:
+                self._call(self._staging_setter, 0)      # back to the default cap
+
+    def jacobian(self, first=0, count=None, bounds=True, _staging_bytes=None):
+        """*_jacobian: the full solution Jacobians of the instances [first, first + count) (count None: to the end) at the x the last
+        run / resolve returned (synchronous; DESIGN.md section 3a''', for the sparse arm "The sparse arm" there).  Returns (Jg, Jb, side,
+        info): Jg [count][nV][nV], Jg[i][k][j] = dx_k/dg_j; Jb [count][nV][nd], Jb[i][k][r] = dx_k/d(the bound row r sits on) in the
+        layout of the arm's dual vector (dense: box rows first, then A, L, R, nd = nV + nC + 2 nComp; sparse: the rows of [A; L; R],
+        nd = m = nC + 2 nComp), zero outside the working set (None with bounds=False); side [count][nd] and info [count] as sensitivity.
+        The unit vectors are generated on the device, and the call goes in chunks under the arm's staging cap, the one adjoint uses
+        (dense: chunks of instances; sparse: chunks of (instance, panel) work items; _staging_bytes: another cap for this one call,
+        for tests).  The call changes nothing on the device."""
+        with self._staging(_staging_bytes):
+            return _jacobian(lambda *a: self._sym("jacobian")(self.h, *a), self.B, self.nV, self._ndual, first, count, bounds, check=self._check)
+
+    def _adjoint_host(self, vx, vy, matrices, reduce, _staging_bytes):
+        """the body of adjoint (a subclass's own: the default of `matrices` differs)"""
+        with self._staging(_staging_bytes):
+            f = self._sym("adjoint")
+            call = lambda vx, vy, dg, db, side, info, *m: f(self.h, vx, vy, dg, db, side, info, 1 if reduce else 0, *m)
+            return _adjoint(call, vx, vy, self.B, self.nV, self._ndual, self._shapes, matrices, () if reduce else (self.B,), check=self._check)
+
     # ---- what the device-pointer entry points of both arms share (DESIGN.md section 3a'''''): the checks of a tensor argument, the
-    # stream the call is ordered behind, the range of instances.  A subclass sets self.device.
+    # stream the call is ordered behind, the range of instances, and the calls that differ in nothing but _ndual and _shapes: torch tensors
+    # on the handle's device in, torch tensors out; the work is ordered behind torch.cuda.current_stream(), and what the caller enqueues
+    # there next sees the results.  No copy through the host.  A subclass sets self.device.
     def _dev(self, name, t, shapes, optional=True):
         """the device address of a tensor argument (None: NULL) after the checks the C side cannot make: a float64, contiguous torch tensor
         on the handle's device of one of `shapes`; anything else raises ValueError"""
@@ -663,6 +710,77 @@ class _Batch:
         if not (isinstance(first, int) and isinstance(count, int)) or first < 0 or count <= 0 or first + count > self.B:
             raise ValueError(f"instances [{first}, {first} + {count}) outside the batch of {self.B}")
 
+    def _device_vectors(self, count, values):
+        """the device addresses of the vectors of a load_device / update_device, `values` in the order of _vectors; without g: all NULL"""
+        if values[0] is None:
+            return [None] * len(values)
+        return [self._dev(nm, v, ((count, sz),)) for (nm, sz), v in zip(self._vector_sizes(), values)]
+
+    def _device_matrices(self, count, named):
+        """named: (name, tensor, shape of one instance's) of the matrix arguments of a load_device, in the bit order of its `shared` word.
+        Returns (shared, {name: device address}): a tensor of one instance's shape is ONE for all `count` instances, its bit is set."""
+        shared, ptr = 0, {}
+        for bit, (nm, t, shp) in enumerate(named):
+            ptr[nm] = self._dev(nm, t, (shp, (count,) + shp))
+            if t is not None and t.dim() == len(shp):
+                shared |= 1 << bit
+        return shared, ptr
+
+    def _results(self, lead):
+        """fresh tensors for (dg, db, side, info) of a derivative call: dg lead + [nV], db lead + [nd]"""
+        import torch
+        dev = torch.device("cuda", self.device)
+        return (torch.empty(lead + (self.nV,), dtype=torch.float64, device=dev), torch.empty(lead + (self._ndual,), dtype=torch.float64, device=dev),
+                torch.empty((self.B, self._ndual), dtype=torch.int32, device=dev), torch.empty(self.B, dtype=torch.int32, device=dev))
+
+    def solution_device(self, stats=False):
+        """*_get_solution_device: (x [B][nV], y [B][nd]) as float64 tensors on the handle's device (y as solution() returns it: dense in
+        the reference's dual layout, nd = nV + nC + 2 nComp; sparse nd = m, rows A, L, R), ordered behind the run on the current torch
+        stream; nothing waits on the host.  stats=True: a third tensor, [B][sizeof(lcqp_stats_t)] bytes (Stats.from_buffer_copy reads
+        an entry once it is on the host)."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        x = torch.empty((self.B, self.nV), dtype=torch.float64, device=dev); y = torch.empty((self.B, self._ndual), dtype=torch.float64, device=dev)
+        st = torch.empty((self.B, C.sizeof(Stats)), dtype=torch.uint8, device=dev) if stats else None
+        self._call("get_solution_device", x.data_ptr(), y.data_ptr(), st.data_ptr() if stats else None, self._stream())
+        return (x, y, st) if stats else (x, y)
+
+    def _sensitivity_device(self, v, *flags):
+        """the body of sensitivity_device; flags: what the arm's entry point takes in front of the number of vectors"""
+        import torch
+        B, n = self.B, self.nV
+        if isinstance(v, torch.Tensor) and v.dim() == 3 and v.shape[1] < 1:
+            raise ValueError("v: no vectors")
+        k = v.shape[1] if isinstance(v, torch.Tensor) and v.dim() == 3 else 1
+        pv = self._dev("v", v, ((B, n), (B, k, n)), optional=False)
+        dg, db, side, info = self._results((B,) if v.dim() == 2 else (B, k))
+        self._call("sensitivity_device", *flags, k, pv, dg.data_ptr(), db.data_ptr(), side.data_ptr(), info.data_ptr(), self._stream())
+        return dg, db, side, info
+
+    def _adjoint_device(self, vx, vy, matrices, reduce, out):
+        """the body of adjoint_device (a subclass's own: the default of `matrices` differs)"""
+        import torch
+        B, shapes = self.B, self._shapes
+        unknown = set(matrices) - set(shapes)
+        if unknown:
+            raise ValueError(f"matrices: unknown names {sorted(unknown)} (this object has {sorted(shapes)})")
+        pvx = self._dev("vx", vx, ((B, self.nV),), optional=False); pvy = self._dev("vy", vy, ((B, self._ndual),))
+        r = dict(zip(("dg", "db", "side", "info"), self._results((B,))))
+        lead = () if reduce else (B,)
+        mats = {}
+        for k in shapes:
+            if k in matrices:
+                t = (out or {}).get(k)
+                if t is None:      # the kernels write every entry except those of a matrix without rows
+                    t = torch.empty(lead + shapes[k], dtype=torch.float64, device=r["dg"].device)
+                self._dev(k, t, (lead + shapes[k],))
+                mats[k] = t
+        ptrs = [mats[k].data_ptr() if k in mats and mats[k].numel() else None for k in shapes]
+        self._call("adjoint_device", pvx, pvy, r["dg"].data_ptr(), r["db"].data_ptr(), r["side"].data_ptr(), r["info"].data_ptr(),
+                   1 if reduce else 0, *ptrs, self._stream())
+        r.update(mats)
+        return r
+
     def close(self):
         if self.h:
             self._sym("destroy")(self.h)
@@ -679,6 +797,9 @@ class BatchLCQP(_Batch):
     """B independent dense LCQPs of one shape solved on one GPU (lcqp_hip_batch_*)."""
     _prefix = "lcqp_hip_batch_"
     _last_error = staticmethod(last_error)
+    _staging_setter = "set_jacobian_staging"
+    _vectors = (("g", "nV"), ("lbL", "nComp"), ("ubL", "nComp"), ("lbR", "nComp"), ("ubR", "nComp"), ("lbA", "nC"), ("ubA", "nC"),
+                ("lb", "nV"), ("ub", "nV"), ("x0", "nV"), ("y0", "_ndual"))
 
     def __init__(self, batch, nV, nC, nComp, with_box=False, device=0, opt=None):
         self.B, self.nV, self.nC, self.nComp = batch, nV, nC, nComp
@@ -701,10 +822,9 @@ class BatchLCQP(_Batch):
         n, nC, nK = self.nV, self.nC, self.nComp
         if first < 0 or count <= 0 or first + count > self.B:
             raise ValueError(f"instances [{first}, {first + count}) outside the batch of {self.B}")
-        sizes = (("Q", Q, n * n), ("g", g, n), ("L", L, nK * n), ("R", R, nK * n), ("lbL", lbL, nK), ("ubL", ubL, nK), ("lbR", lbR, nK),
-                 ("ubR", ubR, nK), ("A", A, nC * n), ("lbA", lbA, nC), ("ubA", ubA, nC), ("lb", lb, n), ("ub", ub, n), ("x0", x0, n),
-                 ("y0", y0, self.nd))
-        a = [_sized(nm, _arr(v), count * sz) for nm, v, sz in sizes]
+        vec = self._vector_sizes()      # the C order: Q, g, L, R, the bounds of L and R, A, the rest
+        table = (("Q", n * n), vec[0], ("L", nK * n), ("R", nK * n), *vec[1:5], ("A", nC * n), *vec[5:])
+        a = self._host_args(table, count, (Q, g, L, R, lbL, ubL, lbR, ubR, A, lbA, ubA, lb, ub, x0, y0))
         return lib().lcqp_hip_batch_load(self.h, first, count, *[_p(v) for v in a])
 
     def sensitivity(self, v, blocked=False):
@@ -714,20 +834,10 @@ class BatchLCQP(_Batch):
         name = "sensitivity_blocked" if blocked else "sensitivity"
         return _sensitivity(lambda *a: self._sym(name)(self.h, *a), v, self.B, self.nV, self._ndual, check=self._check)
 
-    def jacobian(self, first=0, count=None, bounds=True, _staging_bytes=None):
-        """lcqp_hip_batch_jacobian: the full solution Jacobians of the instances [first, first + count) (count None: to the end) at the
-        x the last run / resolve returned (synchronous; DESIGN.md section 3a''').  Returns (Jg, Jb, side, info): Jg [count][nV][nV],
-        Jg[i][k][j] = dx_k/dg_j; Jb [count][nV][nd], Jb[i][k][r] = dx_k/d(the bound row r sits on) in the dual layout, zero outside the
-        working set (None with bounds=False); side [count][nd] and info [count] as sensitivity.  The unit vectors are generated on the
-        device, and the call goes in chunks of instances under a staging cap (_staging_bytes: another cap for this one call, for tests).
-        The call changes nothing on the device."""
-        if _staging_bytes is not None:
-            self._call("set_jacobian_staging", int(_staging_bytes))
-        try:
-            return _jacobian(lambda *a: self._sym("jacobian")(self.h, *a), self.B, self.nV, self.nd, first, count, bounds, check=self._check)
-        finally:
-            if _staging_bytes is not None:
-                self._call("set_jacobian_staging", 0)      # back to the default cap
+    @property
+    def _shapes(self):
+        n, nC, nK = self.nV, self.nC, self.nComp
+        return dict(Q=(n, n), A=(nC, n), L=(nK, n), R=(nK, n))
 
     def adjoint(self, vx, vy=None, matrices=("Q", "A", "L", "R"), reduce=False, _staging_bytes=None):
         """lcqp_hip_batch_adjoint: the gradients of a loss that reads the x AND the y the last run / resolve returned (synchronous; DESIGN.md
@@ -737,17 +847,7 @@ class BatchLCQP(_Batch):
         and so on, formed on the device (one matrix shared by all instances).  Rows outside the working set are zero; an instance with
         info & 1 contributes zeros.  Without reduce the matrices come in chunks of instances under the staging cap of jacobian
         (_staging_bytes: another cap for this one call, for tests).  The call changes nothing on the device."""
-        n, nC, nK = self.nV, self.nC, self.nComp
-        if _staging_bytes is not None:
-            self._call("set_jacobian_staging", int(_staging_bytes))
-        try:
-            f = self._sym("adjoint")
-            call = lambda vx, vy, dg, db, side, info, *m: f(self.h, vx, vy, dg, db, side, info, 1 if reduce else 0, *m)
-            return _adjoint(call, vx, vy, self.B, n, self.nd, dict(Q=(n, n), A=(nC, n), L=(nK, n), R=(nK, n)), matrices,
-                            () if reduce else (self.B,), check=self._check)
-        finally:
-            if _staging_bytes is not None:
-                self._call("set_jacobian_staging", 0)      # back to the default cap
+        return self._adjoint_host(vx, vy, matrices, reduce, _staging_bytes)
 
     def _pairs(self, VX, VY, conv):
         """the shapes of a blocked adjoint call: VX [B][k][nV] or None, VY [B][k][nd] or None, not both None; returns (VX, VY, k)"""
@@ -776,14 +876,9 @@ class BatchLCQP(_Batch):
         end).  Returns (Jyg, Jyb, side, info): Jyg [count][nd][nV], Jyg[i][r][j] = dy_r/dg_j; Jyb [count][nd][nd], Jyb[i][r][s] =
         dy_r/d(the bound row s sits on) (None with bounds=False); rows and columns outside the working set are zero.  The unit vectors of
         the working set are generated on the device; the call goes in chunks of instances under the staging cap of jacobian."""
-        if _staging_bytes is not None:
-            self._call("set_jacobian_staging", int(_staging_bytes))
-        try:
+        with self._staging(_staging_bytes):
             return _jacobian(lambda *a: self._sym("jacobian_duals")(self.h, *a), self.B, self.nV, self.nd, first, count, bounds, check=self._check,
                              rows=self.nd)
-        finally:
-            if _staging_bytes is not None:
-                self._call("set_jacobian_staging", 0)      # back to the default cap
 
     # ---- the device-pointer entry points (DESIGN.md section 3a'''''): torch tensors on the handle's device in, torch tensors out; the work is
     # ordered behind torch.cuda.current_stream(), and what the caller enqueues there next sees the results.  No copy through the host.
@@ -797,9 +892,7 @@ class BatchLCQP(_Batch):
         VX, VY, k = self._pairs(VX, VY, lambda t: t)
         B, n, nd = self.B, self.nV, self.nd
         pvx = self._dev("VX", VX, ((B, k, n),)); pvy = self._dev("VY", VY, ((B, k, nd),))
-        dev = torch.device("cuda", self.device)
-        dg = torch.empty((B, k, n), dtype=torch.float64, device=dev); db = torch.empty((B, k, nd), dtype=torch.float64, device=dev)
-        side = torch.empty((B, nd), dtype=torch.int32, device=dev); info = torch.empty(B, dtype=torch.int32, device=dev)
+        dg, db, side, info = self._results((B, k))
         self._call("adjoint_blocked_device", k, pvx, pvy, dg.data_ptr(), db.data_ptr(), side.data_ptr(), info.data_ptr(), self._stream())
         return dg, db, side, info
 
@@ -824,14 +917,6 @@ class BatchLCQP(_Batch):
         """lcqp_hip_batch_jacobian_duals_device: jacobian_duals() written into tensors on the handle's device, (Jyg, Jyb, side, info)"""
         return self._jacobian_device("jacobian_duals_device", self.nd, first, count, bounds)
 
-    def _device_vectors(self, count, g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0):
-        n, nC, nK = self.nV, self.nC, self.nComp
-        if g is None:
-            return [None] * 11
-        args = (("g", g, n), ("lbL", lbL, nK), ("ubL", ubL, nK), ("lbR", lbR, nK), ("ubR", ubR, nK), ("lbA", lbA, nC), ("ubA", ubA, nC),
-                ("lb", lb, n), ("ub", ub, n), ("x0", x0, n), ("y0", y0, self.nd))
-        return [self._dev(nm, v, ((count, sz),)) for nm, v, sz in args]
-
     def load_device(self, first, count, Q, g, L, R, lbL=None, ubL=None, lbR=None, ubR=None, A=None, lbA=None, ubA=None,
                     lb=None, ub=None, x0=None, y0=None):
         """lcqp_hip_batch_load_device: load() from float64 torch tensors on the handle's device, packed into the pools by kernels.  A
@@ -840,76 +925,27 @@ class BatchLCQP(_Batch):
         hold a problem then).  Returns the ReturnValue code like load; the pools hold the bytes load leaves."""
         n, nC, nK = self.nV, self.nC, self.nComp
         self._range(first, count)
-        shared, ptr = 0, {}
-        for bit, (nm, t, rows) in enumerate((("Q", Q, n), ("A", A, nC), ("L", L, nK), ("R", R, nK))):
-            ptr[nm] = self._dev(nm, t, ((rows, n), (count, rows, n)))
-            if t is not None and t.dim() == 2:
-                shared |= 1 << bit
-        v = self._device_vectors(count, g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0)
-        return lib().lcqp_hip_batch_load_device(self.h, first, count, shared, ptr["Q"], v[0], ptr["L"], ptr["R"], v[1], v[2], v[3], v[4],
-                                                ptr["A"], v[5], v[6], v[7], v[8], v[9], v[10], self._stream())
+        shared, ptr = self._device_matrices(count, (("Q", Q, (n, n)), ("A", A, (nC, n)), ("L", L, (nK, n)), ("R", R, (nK, n))))
+        v = self._device_vectors(count, (g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0))
+        return lib().lcqp_hip_batch_load_device(self.h, first, count, shared, ptr["Q"], v[0], ptr["L"], ptr["R"], *v[1:5], ptr["A"], *v[5:],
+                                                self._stream())
 
     def update_device(self, first, count, g, lbL=None, ubL=None, lbR=None, ubR=None, lbA=None, ubA=None, lb=None, ub=None, x0=None, y0=None):
         """lcqp_hip_batch_update_device: update() from float64 torch tensors on the handle's device.  Returns the ReturnValue code."""
         self._range(first, count)
-        v = self._device_vectors(count, g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0)
+        v = self._device_vectors(count, (g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0))
         return lib().lcqp_hip_batch_update_device(self.h, first, count, *v, self._stream())
-
-    def solution_device(self, stats=False):
-        """lcqp_hip_batch_get_solution_device: (x [B][nV], y [B][nd]) as float64 tensors on the handle's device, ordered behind the run on
-        the current torch stream; nothing waits on the host.  stats=True: a third tensor, [B][sizeof(lcqp_stats_t)] bytes
-        (Stats.from_buffer_copy reads an entry once it is on the host)."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        x = torch.empty((self.B, self.nV), dtype=torch.float64, device=dev); y = torch.empty((self.B, self.nd), dtype=torch.float64, device=dev)
-        st = torch.empty((self.B, C.sizeof(Stats)), dtype=torch.uint8, device=dev) if stats else None
-        self._call("get_solution_device", x.data_ptr(), y.data_ptr(), st.data_ptr() if stats else None, self._stream())
-        return (x, y, st) if stats else (x, y)
 
     def sensitivity_device(self, v, blocked=False):
         """lcqp_hip_batch_sensitivity_device: sensitivity(v, blocked) with v a float64 tensor on the handle's device, [B][nV] or
         [B][k][nV], read where it lies; returns (dg, db, side, info) as tensors on that device (side, info: int32)."""
-        import torch
-        B, n, nd = self.B, self.nV, self.nd
-        if isinstance(v, torch.Tensor) and v.dim() == 3 and v.shape[1] < 1:
-            raise ValueError("v: no vectors")
-        k = v.shape[1] if isinstance(v, torch.Tensor) and v.dim() == 3 else 1
-        pv = self._dev("v", v, ((B, n), (B, k, n)), optional=False)
-        dev = torch.device("cuda", self.device)
-        lead = (B,) if v.dim() == 2 else (B, k)
-        dg = torch.empty(lead + (n,), dtype=torch.float64, device=dev); db = torch.empty(lead + (nd,), dtype=torch.float64, device=dev)
-        side = torch.empty((B, nd), dtype=torch.int32, device=dev); info = torch.empty(B, dtype=torch.int32, device=dev)
-        self._call("sensitivity_device", 1 if blocked else 0, k, pv, dg.data_ptr(), db.data_ptr(), side.data_ptr(), info.data_ptr(), self._stream())
-        return dg, db, side, info
+        return self._sensitivity_device(v, 1 if blocked else 0)
 
     def adjoint_device(self, vx, vy=None, matrices=("Q", "A", "L", "R"), reduce=False, out=None):
         """lcqp_hip_batch_adjoint_device: adjoint(vx, vy, matrices, reduce) with float64 tensors on the handle's device in and out -- the
         matrix gradients are written by ONE launch straight into their tensors, whatever their size (no staging, no chunks).  out: tensors
         to write the matrix gradients into, by name (16-byte aligned; default: fresh ones).  Returns the dict of adjoint, of tensors."""
-        import torch
-        B, n, nC, nK, nd = self.B, self.nV, self.nC, self.nComp, self.nd
-        shapes = dict(Q=(n, n), A=(nC, n), L=(nK, n), R=(nK, n))
-        unknown = set(matrices) - set(shapes)
-        if unknown:
-            raise ValueError(f"matrices: unknown names {sorted(unknown)} (this object has {sorted(shapes)})")
-        pvx = self._dev("vx", vx, ((B, n),), optional=False); pvy = self._dev("vy", vy, ((B, nd),))
-        dev = torch.device("cuda", self.device)
-        r = dict(dg=torch.empty((B, n), dtype=torch.float64, device=dev), db=torch.empty((B, nd), dtype=torch.float64, device=dev),
-                 side=torch.empty((B, nd), dtype=torch.int32, device=dev), info=torch.empty(B, dtype=torch.int32, device=dev))
-        lead = () if reduce else (B,)
-        mats = {}
-        for k in shapes:
-            if k in matrices:
-                t = (out or {}).get(k)
-                if t is None:      # the kernels write every entry except those of a matrix without rows
-                    t = torch.empty(lead + shapes[k], dtype=torch.float64, device=dev)
-                self._dev(k, t, (lead + shapes[k],))
-                mats[k] = t
-        ptrs = [mats[k].data_ptr() if k in mats and mats[k].numel() else None for k in shapes]
-        self._call("adjoint_device", pvx, pvy, r["dg"].data_ptr(), r["db"].data_ptr(), r["side"].data_ptr(), r["info"].data_ptr(),
-                   1 if reduce else 0, *ptrs, self._stream())
-        r.update(mats)
-        return r
+        return self._adjoint_device(vx, vy, matrices, reduce, out)
 
     def generate_synthetic(self, first_instance=0, seed0=SEED0):
         _check(lib().lcqp_hip_batch_generate_synthetic(self.h, seed0, first_instance), "generate_synthetic")
@@ -918,12 +954,9 @@ class BatchLCQP(_Batch):
         """lcqp_hip_batch_update: new vectors for instances [first, first + count), the matrices stay.  Returns the ReturnValue code like
         load (0; 100 INVALID_ARGUMENT when the set of box-bounded variables would change -- see last_error()); a wrongly sized array
         raises ValueError."""
-        n, nC, nK = self.nV, self.nC, self.nComp
         if first < 0 or count <= 0 or first + count > self.B:
             raise ValueError(f"instances [{first}, {first + count}) outside the batch of {self.B}")
-        sizes = (("g", g, n), ("lbL", lbL, nK), ("ubL", ubL, nK), ("lbR", lbR, nK), ("ubR", ubR, nK), ("lbA", lbA, nC), ("ubA", ubA, nC),
-                 ("lb", lb, n), ("ub", ub, n), ("x0", x0, n), ("y0", y0, self.nd))
-        a = [_sized(nm, _arr(v), count * sz) for nm, v, sz in sizes]
+        a = self._host_args(self._vector_sizes(), count, (g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0))
         return lib().lcqp_hip_batch_update(self.h, first, count, *[_p(v) for v in a])
 
     def read_problem(self, b):
@@ -1054,6 +1087,9 @@ class SparseBatchLCQP(_Batch):
     Qpat / Apat: scipy-like CSC pattern objects with .indptr / .indices (Q full symmetric nV x nV; A the stacked [A; L; R],
     (nC + 2 nComp) x nV).  Values are loaded per instance in the CSC order of these patterns."""
     _prefix = "lcqp_hip_sparse_"
+    _staging_setter = "set_adjoint_staging"
+    _vectors = (("g", "nV"), ("lbA", "nC"), ("ubA", "nC"), ("lbL", "nComp"), ("ubL", "nComp"), ("lbR", "nComp"), ("ubR", "nComp"),
+                ("x0", "nV"), ("y0", "_ndual"))
 
     def __init__(self, batch, nV, nC, nComp, Qpat, Apat, device=0, opt=None):
         self.B, self.nV, self.nC, self.nComp = batch, nV, nC, nComp
@@ -1148,20 +1184,9 @@ class SparseBatchLCQP(_Batch):
         sensitivity, whose signature (v) is part of this class's tested surface.)"""
         return _sensitivity(lambda *a: self._sym("sensitivity_blocked")(self.h, *a), v, self.B, self.nV, self._ndual, check=self._check)
 
-    def jacobian(self, first=0, count=None, bounds=True, _staging_bytes=None):
-        """lcqp_hip_sparse_jacobian: the full solution Jacobians of the instances [first, first + count) (count None: to the end) at the x the
-        last run / resolve returned (synchronous; DESIGN.md section 3a''', "The sparse arm").  Returns (Jg, Jb, side, info): Jg
-        [count][nV][nV], Jg[i][k][j] = dx_k/dg_j; Jb [count][nV][m], Jb[i][k][r] = dx_k/d(the bound row r of [A; L; R] sits on), zero outside
-        the working set (None with bounds=False); side [count][m] and info [count] as sensitivity.  The unit vectors are generated on the
-        device, and the call goes in chunks of (instance, panel) work items under the staging cap of adjoint (_staging_bytes: another cap
-        for this one call, for tests).  The call changes nothing on the device."""
-        if _staging_bytes is not None:
-            self._call("set_adjoint_staging", int(_staging_bytes))
-        try:
-            return _jacobian(lambda *a: self._sym("jacobian")(self.h, *a), self.B, self.nV, self.m, first, count, bounds, check=self._check)
-        finally:
-            if _staging_bytes is not None:
-                self._call("set_adjoint_staging", 0)      # back to the default cap
+    @property
+    def _shapes(self):
+        return dict(Q=(self.nnzQ,), A=(self.nnzA,))
 
     def adjoint(self, vx, vy=None, matrices=("Q", "A"), reduce=False, _staging_bytes=None):
         """lcqp_hip_sparse_adjoint: the gradients of a loss that reads the x AND the y the last run / resolve returned (synchronous; DESIGN.md
@@ -1170,119 +1195,49 @@ class SparseBatchLCQP(_Batch):
         [A; L; R], in the order of load's Qx / Ax -- [B][nnz], or [nnz] summed over the batch on the device with reduce=True (one value array
         shared by the instances).  "Q" holds the symmetric derivative: entries (i, j) and (j, i) are equal.  reduce=False goes in chunks of
         instances under the staging cap (_staging_bytes: another cap for this one call, for tests).  The call changes nothing on the device."""
-        if _staging_bytes is not None:
-            self._call("set_adjoint_staging", int(_staging_bytes))
-        try:
-            f = self._sym("adjoint")
-            call = lambda vx, vy, dg, db, side, info, *m: f(self.h, vx, vy, dg, db, side, info, 1 if reduce else 0, *m)
-            return _adjoint(call, vx, vy, self.B, self.nV, self.m, dict(Q=(self.nnzQ,), A=(self.nnzA,)), matrices,
-                            () if reduce else (self.B,), check=self._check)
-        finally:
-            if _staging_bytes is not None:
-                self._call("set_adjoint_staging", 0)      # back to the default cap
+        return self._adjoint_host(vx, vy, matrices, reduce, _staging_bytes)
 
     def load(self, first, count, Qx, g, Ax, lbA=None, ubA=None, lbL=None, ubL=None, lbR=None, ubR=None, x0=None, y0=None):
-        n, nC, nK = self.nV, self.nC, self.nComp
-        sizes = (("Qx", Qx, self.nnzQ), ("g", g, n), ("Ax", Ax, self.nnzA), ("lbA", lbA, nC), ("ubA", ubA, nC), ("lbL", lbL, nK), ("ubL", ubL, nK),
-                 ("lbR", lbR, nK), ("ubR", ubR, nK), ("x0", x0, n), ("y0", y0, self.m))
-        a = [_sized(nm, _arr(v), count * sz) for nm, v, sz in sizes]
+        vec = self._vector_sizes()
+        a = self._host_args((("Qx", self.nnzQ), vec[0], ("Ax", self.nnzA), *vec[1:]), count, (Qx, g, Ax, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0))
         return lib().lcqp_hip_sparse_load(self.h, first, count, *[_p(v) for v in a])
 
     def update(self, first, count, g, lbA=None, ubA=None, lbL=None, ubL=None, lbR=None, ubR=None, x0=None, y0=None):
         """lcqp_hip_sparse_update: new vectors for instances [first, first + count), the matrices stay (the argument list of load without
         Qx and Ax).  Returns the ReturnValue code like load (0; 100 for a range outside the batch, 116 for g = None, 120 for -inf in
         lbL / lbR); a wrongly sized array raises ValueError."""
-        n, nC, nK = self.nV, self.nC, self.nComp
-        sizes = (("g", g, n), ("lbA", lbA, nC), ("ubA", ubA, nC), ("lbL", lbL, nK), ("ubL", ubL, nK), ("lbR", lbR, nK), ("ubR", ubR, nK),
-                 ("x0", x0, n), ("y0", y0, self.m))
-        a = [_sized(nm, _arr(v), max(count, 0) * sz) for nm, v, sz in sizes]
+        a = self._host_args(self._vector_sizes(), max(count, 0), (g, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0))
         return lib().lcqp_hip_sparse_update(self.h, first, count, *[_p(v) for v in a])
 
     # ---- the device-pointer entry points (DESIGN.md section 3a''''', "The sparse arm"): torch tensors on the handle's device in, torch tensors
     # out; the work is ordered behind torch.cuda.current_stream(), and what the caller enqueues there next sees the results.
-    def _device_vectors(self, count, g, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0):
-        n, nC, nK = self.nV, self.nC, self.nComp
-        if g is None:
-            return [None] * 9
-        args = (("g", g, n), ("lbA", lbA, nC), ("ubA", ubA, nC), ("lbL", lbL, nK), ("ubL", ubL, nK), ("lbR", lbR, nK), ("ubR", ubR, nK),
-                ("x0", x0, n), ("y0", y0, self.m))
-        return [self._dev(nm, v, ((count, sz),)) for nm, v, sz in args]
-
     def load_device(self, first, count, Qx, g, Ax, lbA=None, ubA=None, lbL=None, ubL=None, lbR=None, ubR=None, x0=None, y0=None):
         """lcqp_hip_sparse_load_device: load() from float64 torch tensors on the handle's device, packed into the pools by kernels.  A
         value tensor of shape [nnz] is ONE array for all `count` instances (broadcast by the pack kernel), one of shape [count][nnz]
         holds one per instance; one that is None stays as the batch holds it (every instance of the range must hold a problem then).
         Returns the ReturnValue code like load; the pools hold the bytes load leaves."""
         self._range(first, count)
-        shared, ptr = 0, {}
-        for bit, (nm, t, nnz) in enumerate((("Qx", Qx, self.nnzQ), ("Ax", Ax, self.nnzA))):
-            ptr[nm] = self._dev(nm, t, ((nnz,), (count, nnz)))
-            if t is not None and t.dim() == 1:
-                shared |= 1 << bit
-        v = self._device_vectors(count, g, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0)
+        shared, ptr = self._device_matrices(count, (("Qx", Qx, (self.nnzQ,)), ("Ax", Ax, (self.nnzA,))))
+        v = self._device_vectors(count, (g, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0))
         return lib().lcqp_hip_sparse_load_device(self.h, first, count, shared, ptr["Qx"], v[0], ptr["Ax"], *v[1:], self._stream())
 
     def update_device(self, first, count, g, lbA=None, ubA=None, lbL=None, ubL=None, lbR=None, ubR=None, x0=None, y0=None):
         """lcqp_hip_sparse_update_device: update() from float64 torch tensors on the handle's device; the call does not drain the handle's
         stream, it is ordered behind it.  Returns the ReturnValue code."""
         self._range(first, count)
-        v = self._device_vectors(count, g, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0)
+        v = self._device_vectors(count, (g, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0))
         return lib().lcqp_hip_sparse_update_device(self.h, first, count, *v, self._stream())
-
-    def solution_device(self, stats=False):
-        """lcqp_hip_sparse_get_solution_device: (x [B][nV], y [B][m]) as float64 tensors on the handle's device, ordered behind the run on
-        the current torch stream; nothing waits on the host.  stats=True: a third tensor, [B][sizeof(lcqp_stats_t)] bytes."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        x = torch.empty((self.B, self.nV), dtype=torch.float64, device=dev); y = torch.empty((self.B, self.m), dtype=torch.float64, device=dev)
-        st = torch.empty((self.B, C.sizeof(Stats)), dtype=torch.uint8, device=dev) if stats else None
-        self._call("get_solution_device", x.data_ptr(), y.data_ptr(), st.data_ptr() if stats else None, self._stream())
-        return (x, y, st) if stats else (x, y)
 
     def sensitivity_device(self, v):
         """lcqp_hip_sparse_sensitivity_device: sensitivity(v) with v a float64 tensor on the handle's device, [B][nV] or [B][k][nV], read
         where it lies; returns (dg, db, side, info) as tensors on that device (side, info: int32)."""
-        import torch
-        B, n, m = self.B, self.nV, self.m
-        if isinstance(v, torch.Tensor) and v.dim() == 3 and v.shape[1] < 1:
-            raise ValueError("v: no vectors")
-        k = v.shape[1] if isinstance(v, torch.Tensor) and v.dim() == 3 else 1
-        pv = self._dev("v", v, ((B, n), (B, k, n)), optional=False)
-        dev = torch.device("cuda", self.device)
-        lead = (B,) if v.dim() == 2 else (B, k)
-        dg = torch.empty(lead + (n,), dtype=torch.float64, device=dev); db = torch.empty(lead + (m,), dtype=torch.float64, device=dev)
-        side = torch.empty((B, m), dtype=torch.int32, device=dev); info = torch.empty(B, dtype=torch.int32, device=dev)
-        self._call("sensitivity_device", k, pv, dg.data_ptr(), db.data_ptr(), side.data_ptr(), info.data_ptr(), self._stream())
-        return dg, db, side, info
+        return self._sensitivity_device(v)
 
     def adjoint_device(self, vx, vy=None, matrices=("Q", "A"), reduce=False, out=None):
         """lcqp_hip_sparse_adjoint_device: adjoint(vx, vy, matrices, reduce) with float64 tensors on the handle's device in and out -- the
         gradients on the non-zeros are written by ONE launch straight into their tensors, whatever their size (no staging, no chunks).
         out: tensors to write them into, by name ("Q": 16-byte aligned; default: fresh ones).  Returns the dict of adjoint, of tensors."""
-        import torch
-        B, n, m = self.B, self.nV, self.m
-        shapes = dict(Q=(self.nnzQ,), A=(self.nnzA,))
-        unknown = set(matrices) - set(shapes)
-        if unknown:
-            raise ValueError(f"matrices: unknown names {sorted(unknown)} (this object has {sorted(shapes)})")
-        pvx = self._dev("vx", vx, ((B, n),), optional=False); pvy = self._dev("vy", vy, ((B, m),))
-        dev = torch.device("cuda", self.device)
-        r = dict(dg=torch.empty((B, n), dtype=torch.float64, device=dev), db=torch.empty((B, m), dtype=torch.float64, device=dev),
-                 side=torch.empty((B, m), dtype=torch.int32, device=dev), info=torch.empty(B, dtype=torch.int32, device=dev))
-        lead = () if reduce else (B,)
-        mats = {}
-        for k in shapes:
-            if k in matrices:
-                t = (out or {}).get(k)
-                if t is None:      # the kernels write every entry
-                    t = torch.empty(lead + shapes[k], dtype=torch.float64, device=dev)
-                self._dev(k, t, (lead + shapes[k],))
-                mats[k] = t
-        ptrs = [mats[k].data_ptr() if k in mats and mats[k].numel() else None for k in shapes]
-        self._call("adjoint_device", pvx, pvy, r["dg"].data_ptr(), r["db"].data_ptr(), r["side"].data_ptr(), r["info"].data_ptr(),
-                   1 if reduce else 0, *ptrs, self._stream())
-        r.update(mats)
-        return r
+        return self._adjoint_device(vx, vy, matrices, reduce, out)
 
     def read_problem(self, b):
         """Test and diagnostic entry point (lcqp_hip_sparse_read_problem): instance b as the pools hold it -- Qx [nnzQ], Ax [nnzA] in the

@@ -23,6 +23,9 @@ and on the sparse arm (lcqp_hip_sparse_adjoint) in the value arrays of the share
     layer = SparseBatchLCQPLayer(sb, bounds=..., values=dict(Qx=Qx0, Ax=Ax0))      # the values the batch was loaded with
     x, y = layer.solve(g, Qx=Qx, Ax=Ax)   # Qx [nnzQ] shared by the batch (or [B][nnzQ] per instance), likewise Ax over [A; L; R]
     loss(x, y).backward()                 # g.grad, Qx.grad, Ax.grad
+
+The three autograd functions share one solve and one backward routine (_solve, _backward).  What the two paths do differently is in
+_HostPath / _DevicePath, what the two arms do differently is on the layer classes.
 """
 import warnings
 
@@ -32,6 +35,8 @@ import torch
 from . import capi
 
 BOUND_KEYS = ("lbL", "ubL", "lbR", "ubR", "lbA", "ubA", "lb", "ub")
+MATRIX_KEYS = ("Q", "A", "L", "R")
+SPARSE_VALUE_KEYS = ("Qx", "Ax")
 
 
 def _host(t):
@@ -43,25 +48,163 @@ def _dev(t, device):
     return None if t is None else t.detach().to(device=device, dtype=torch.float64).contiguous()
 
 
+class _HostPath:
+    """the host-pointer calls around a solve: tensors become numpy arrays, results become tensors like `ref` (the g or the upstream
+    gradient of the call)"""
+    name, suffix = "host", ""
+
+    @staticmethod
+    def conv(t, ref):
+        return _host(t)
+
+    @staticmethod
+    def out(a, ref):
+        return torch.as_tensor(a, dtype=ref.dtype, device=ref.device)
+
+    @staticmethod
+    def bounds(layer, ref):
+        return layer.bounds
+
+    @staticmethod
+    def load_arrays(layer, replaced, ref):
+        """a host load replaces every array: the ones the layer holds, with the inputs broadcast over the batch in their place (and kept)"""
+        held = layer._held_arrays()
+        for k, t in replaced.items():
+            if t is not None:
+                held[k] = np.ascontiguousarray(np.broadcast_to(_host(t), (layer.bt.B,) + layer._trailing(k)))
+        return held
+
+    @staticmethod
+    def loaded(layer):
+        pass
+
+
+class _DevicePath:
+    """the device-pointer twins (capi: *_device): tensors stay where they are, float64; results are converted to ref's dtype"""
+    name, suffix = "device", "_device"
+
+    @staticmethod
+    def conv(t, ref):
+        return _dev(t, ref.device)
+
+    @staticmethod
+    def out(a, ref):
+        return a.to(ref.dtype)
+
+    @staticmethod
+    def bounds(layer, ref):
+        return layer._device_bounds(ref.device)
+
+    @staticmethod
+    def load_arrays(layer, replaced, ref):
+        """an array that is not an input is not handed over: the batch keeps it (NULL), a shared one is broadcast by the pack kernel"""
+        return {k: _dev(t, ref.device) for k, t in replaced.items()}
+
+    @staticmethod
+    def loaded(layer):
+        layer._mark_stale()      # (the host path reads the arrays back again when it next needs them)
+
+
+def _solve(ctx, layer, g, lbA, ubA, replaced):
+    """The forward of all three functions, on either path.  replaced: the matrix or value tensors of the call by name (None: not given).
+    Without one: update + run (first solve) / resolve(warm); with one: a load of the whole batch + run.  Returns (path, x, y), x and y
+    as the batch object returned them."""
+    bt = layer.bt
+    shared = {}
+    for k, t in replaced.items():
+        if t is None:
+            continue
+        trail = layer._trailing(k)
+        if tuple(t.shape) not in ((bt.B,) + trail, trail):
+            dims = "".join(f"[{d}]" for d in trail)
+            raise ValueError(f"{k}: expected [{bt.B}]{dims} or {dims}, got {tuple(t.shape)}")
+        shared[k] = t.dim() == len(trail)
+    path = ctx.path = _DevicePath if layer._on_device(g) else _HostPath
+    layer.last_path = path.name
+    kw = dict(path.bounds(layer, g))
+    if lbA is not None: kw["lbA"] = path.conv(lbA, g)
+    if ubA is not None: kw["ubA"] = path.conv(ubA, g)
+    if shared:
+        rc = layer._load(getattr(bt, "load" + path.suffix), path.load_arrays(layer, replaced, g), path.conv(g, g), kw)
+        if rc != 0:
+            raise RuntimeError(f"load failed with code {rc}: {bt._last_error()}")
+        path.loaded(layer)
+        bt.run()
+    else:
+        rc = getattr(bt, "update" + path.suffix)(0, bt.B, path.conv(g, g), **kw)
+        if rc != 0:
+            raise RuntimeError(f"update failed with code {rc}: {bt._last_error()}")
+        if layer.solves == 0:
+            bt.run()
+        else:
+            bt.resolve(warm=layer.warm)
+    x, y, *st = getattr(bt, "solution" + path.suffix)()
+    layer.solves += 1
+    layer.y, layer.stats = y, (st[0] if st else None)      # (device path: the statistics through the host call, when layer.stats is read)
+    layer._like = (g.dtype, g.device)
+    ctx.layer, ctx.serial = layer, layer.solves
+    ctx.given = (lbA is not None, ubA is not None)
+    ctx.shared = shared
+    return path, x, y
+
+
 def _warn_flagged(who, info, B):
-    """the one warning of a backward call on the device path: the count is the one scalar read of that call"""
-    bad = int(torch.count_nonzero(info))
+    """the one warning of a backward call; info: numpy or a tensor on the device, where the count is the one scalar read of that call"""
+    bad = int(torch.count_nonzero(info)) if torch.is_tensor(info) else int(np.count_nonzero(info))
     if bad:
-        bits = int(np.bitwise_or.reduce(info.cpu().numpy()))
+        bits = int(np.bitwise_or.reduce(info.cpu().numpy() if torch.is_tensor(info) else info))
         warnings.warn(f"{who}.backward: {bad} of {B} instances are not differentiable by the library's criteria "
-                      f"(info bits present: {bits}); their gradients are the kernel's output as it is", RuntimeWarning, stacklevel=3)
+                      f"(info bits present: {bits}); their gradients are the kernel's output as it is", RuntimeWarning, stacklevel=4)
 
 
-def _bound_grads_device(bt, db, side, given, like, sparse=False):
-    """the gradients of lbA / ubA on the device path: split_bound_derivatives and the equality rule of LCQPSolveFunction, on tensors"""
-    parts = capi.split_bound_derivatives_torch(db, side, bt.nV, bt.nC, bt.nComp, sparse=sparse)
-    a0 = 0 if sparse else bt.nV      # first row of A in the layout of side
+def _bound_grads(layer, db, side, given, out):
+    """the gradients of lbA / ubA, db and side numpy or tensors: split_bound_derivatives and the equality rule of LCQPSolveFunction"""
+    bt = layer.bt
+    on_device = torch.is_tensor(db)
+    split = capi.split_bound_derivatives_torch if on_device else capi.split_bound_derivatives
+    parts = split(db, side, bt.nV, bt.nC, bt.nComp, sparse=layer.sparse)
+    a0 = 0 if layer.sparse else bt.nV      # first row of A in the layout of side
     eq = side[:, a0:a0 + bt.nC] == 2
-    one = db.new_ones(())
-    share = torch.where(eq, 0.5 * one, one) if all(given) else one
-    glb = (parts["dlbA"] * share).to(like) if given[0] else None
-    gub = (parts["dubA"] * share).to(like) if given[1] else None
+    if on_device:
+        one = db.new_ones(())
+        share = torch.where(eq, 0.5 * one, one) if all(given) else one
+    else:
+        share = np.where(eq, 0.5, 1.0) if all(given) else 1.0
+    glb = out(parts["dlbA"] * share) if given[0] else None
+    gub = out(parts["dubA"] * share) if given[1] else None
     return glb, gub
+
+
+def _backward(who, ctx, grad_x, grad_y=None, adjoint=False):
+    """The backward of all three functions, on the path of the solve.  adjoint=False: one sensitivity call; True: the adjoint call for
+    the per-instance inputs (reduce = 0) and, where there are shared ones, a second for those (reduce = 1).  Returns the gradients of
+    (layer, g, *the layer's input keys when adjoint, lbA, ubA)."""
+    layer = ctx.layer
+    if ctx.serial != layer.solves:
+        raise RuntimeError("backward through a solve that is not the layer's last one: the batch object holds the state of one solve")
+    bt, path = layer.bt, ctx.path
+    out = lambda a: path.out(a, grad_x)
+    mats = {}
+    if adjoint:
+        name = layer.adjoint_names
+        each = tuple(name[k] for k, sh in ctx.shared.items() if not sh)
+        summed = tuple(name[k] for k, sh in ctx.shared.items() if sh)
+        call = getattr(bt, "adjoint" + path.suffix)
+        vx, vy = path.conv(grad_x, grad_x), path.conv(grad_y, grad_x)
+        r = call(vx, vy, matrices=each, reduce=False)
+        mats.update({k: r[k] for k in each})
+        if summed:
+            rs = call(vx, vy, matrices=summed, reduce=True)
+            mats.update({k: rs[k] for k in summed})
+        dg, db, side, info = r["dg"], r["db"], r["side"], r["info"]
+        gm = [out(mats[name[k]]) if name[k] in mats else None for k in layer.input_keys]
+    else:
+        dg, db, side, info = getattr(bt, "sensitivity" + path.suffix)(path.conv(grad_x, grad_x))
+        gm = []
+    layer.info = info
+    _warn_flagged(who, info, bt.B)
+    glb, gub = _bound_grads(layer, db, side, ctx.given, out)
+    return (None, out(dg), *gm, glb, gub)
 
 
 class LCQPSolveFunction(torch.autograd.Function):
@@ -76,75 +219,12 @@ class LCQPSolveFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, layer, g, lbA=None, ubA=None):
-        bt = layer.bt
-        ctx.device_path = layer._on_device(g)
-        layer.last_path = "device" if ctx.device_path else "host"
-        if ctx.device_path:
-            kw = dict(layer._device_bounds(g.device))
-            if lbA is not None: kw["lbA"] = _dev(lbA, g.device)
-            if ubA is not None: kw["ubA"] = _dev(ubA, g.device)
-            rc = bt.update_device(0, bt.B, _dev(g, g.device), **kw)
-            if rc != 0:
-                raise RuntimeError(f"update failed with code {rc}: {bt._last_error()}")
-            if layer.solves == 0:
-                bt.run()
-            else:
-                bt.resolve(warm=layer.warm)
-            x, y = bt.solution_device()
-            layer.solves += 1
-            layer.y, layer.stats = y, None      # (the statistics: through the host call, when layer.stats is read)
-            layer._like = (g.dtype, g.device)
-            ctx.layer, ctx.serial = layer, layer.solves
-            ctx.given = (lbA is not None, ubA is not None)
-            return x.to(g.dtype)
-        kw = dict(layer.bounds)
-        if lbA is not None: kw["lbA"] = _host(lbA)
-        if ubA is not None: kw["ubA"] = _host(ubA)
-        rc = bt.update(0, bt.B, _host(g), **kw)
-        if rc != 0:
-            raise RuntimeError(f"update failed with code {rc}: {bt._last_error()}")
-        if layer.solves == 0:
-            bt.run()
-        else:
-            bt.resolve(warm=layer.warm)
-        x, y, st = bt.solution()
-        layer.solves += 1
-        layer.y, layer.stats = y, st
-        layer._like = (g.dtype, g.device)
-        ctx.layer, ctx.serial = layer, layer.solves
-        ctx.given = (lbA is not None, ubA is not None)
-        return torch.as_tensor(x, dtype=g.dtype, device=g.device)
+        path, x, _ = _solve(ctx, layer, g, lbA, ubA, {})
+        return path.out(x, g)
 
     @staticmethod
     def backward(ctx, grad_x):
-        layer = ctx.layer
-        if ctx.serial != layer.solves:
-            raise RuntimeError("backward through a solve that is not the layer's last one: the batch object holds the state of one solve")
-        bt = layer.bt
-        if ctx.device_path:
-            dg, db, side, info = bt.sensitivity_device(_dev(grad_x, grad_x.device))
-            layer.info = info
-            _warn_flagged("LCQPSolveFunction", info, bt.B)
-            glb, gub = _bound_grads_device(bt, db, side, ctx.given, grad_x.dtype, sparse=layer.sparse)
-            return None, dg.to(grad_x.dtype), glb, gub
-        dg, db, side, info = bt.sensitivity(_host(grad_x))
-        layer.info = info
-        bad = int(np.count_nonzero(info))
-        if bad:
-            warnings.warn(f"LCQPSolveFunction.backward: {bad} of {bt.B} instances are not differentiable by the library's criteria "
-                          f"(info bits present: {int(np.bitwise_or.reduce(info))}); their gradients are the kernel's output as it is",
-                          RuntimeWarning, stacklevel=2)
-        out = lambda a: torch.as_tensor(a, dtype=grad_x.dtype, device=grad_x.device)
-        parts = capi.split_bound_derivatives(db, side, bt.nV, bt.nC, bt.nComp, sparse=layer.sparse)
-        a0 = 0 if layer.sparse else bt.nV      # first row of A in the layout of side
-        eq = side[:, a0:a0 + bt.nC] == 2
-        share = np.where(eq, 0.5, 1.0) if all(ctx.given) else 1.0
-        glb = out(parts["dlbA"] * share) if ctx.given[0] else None
-        gub = out(parts["dubA"] * share) if ctx.given[1] else None
-        return None, out(dg), glb, gub
-
-
-MATRIX_KEYS = ("Q", "A", "L", "R")
+        return _backward("LCQPSolveFunction", ctx, grad_x)
 
 
 class LCQPFullSolveFunction(torch.autograd.Function):
@@ -157,120 +237,12 @@ class LCQPFullSolveFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, layer, g, Q=None, A=None, L=None, R=None, lbA=None, ubA=None):
-        bt = layer.bt
-        given = dict(zip(MATRIX_KEYS, (Q, A, L, R)))
-        rows = dict(Q=bt.nV, A=bt.nC, L=bt.nComp, R=bt.nComp)
-        shared = {}
-        for k, t in given.items():
-            if t is None:
-                continue
-            if tuple(t.shape) not in ((bt.B, rows[k], bt.nV), (rows[k], bt.nV)):
-                raise ValueError(f"{k}: expected [{bt.B}][{rows[k]}][{bt.nV}] or [{rows[k]}][{bt.nV}], got {tuple(t.shape)}")
-            shared[k] = t.dim() == 2
-        ctx.device_path = layer._on_device(g)
-        layer.last_path = "device" if ctx.device_path else "host"
-        if ctx.device_path:
-            kw = dict(layer._device_bounds(g.device))
-            if lbA is not None: kw["lbA"] = _dev(lbA, g.device)
-            if ubA is not None: kw["ubA"] = _dev(ubA, g.device)
-            if shared:
-                # a matrix that is not an input is not handed over: the batch keeps it (NULL), a shared one is broadcast by the pack kernel
-                m = {k: _dev(t, g.device) for k, t in given.items()}
-                rc = bt.load_device(0, bt.B, m["Q"], _dev(g, g.device), m["L"], m["R"], A=m["A"], **kw)
-                if rc != 0:
-                    raise RuntimeError(f"load failed with code {rc}: {bt._last_error()}")
-                layer._held = None      # (the host path reads the matrices back again when it next needs them)
-                bt.run()
-            else:
-                rc = bt.update_device(0, bt.B, _dev(g, g.device), **kw)
-                if rc != 0:
-                    raise RuntimeError(f"update failed with code {rc}: {bt._last_error()}")
-                if layer.solves == 0:
-                    bt.run()
-                else:
-                    bt.resolve(warm=layer.warm)
-            x, y = bt.solution_device()
-            layer.solves += 1
-            layer.y, layer.stats = y, None
-            layer._like = (g.dtype, g.device)
-            ctx.layer, ctx.serial = layer, layer.solves
-            ctx.given = (lbA is not None, ubA is not None)
-            ctx.shared = shared
-            return x.to(g.dtype), y.to(g.dtype)
-        kw = dict(layer.bounds)
-        if lbA is not None: kw["lbA"] = _host(lbA)
-        if ubA is not None: kw["ubA"] = _host(ubA)
-        if shared:
-            held = layer._matrices()
-            for k, t in given.items():
-                if t is not None:
-                    held[k] = np.ascontiguousarray(np.broadcast_to(_host(t), (bt.B, rows[k], bt.nV)))
-            rc = bt.load(0, bt.B, held["Q"], _host(g), held["L"], held["R"], A=held["A"], **kw)
-            if rc != 0:
-                raise RuntimeError(f"load failed with code {rc}: {bt._last_error()}")
-            bt.run()
-        else:
-            rc = bt.update(0, bt.B, _host(g), **kw)
-            if rc != 0:
-                raise RuntimeError(f"update failed with code {rc}: {bt._last_error()}")
-            if layer.solves == 0:
-                bt.run()
-            else:
-                bt.resolve(warm=layer.warm)
-        x, y, st = bt.solution()
-        layer.solves += 1
-        layer.y, layer.stats = y, st
-        layer._like = (g.dtype, g.device)
-        ctx.layer, ctx.serial = layer, layer.solves
-        ctx.given = (lbA is not None, ubA is not None)
-        ctx.shared = shared
-        out = lambda a: torch.as_tensor(a, dtype=g.dtype, device=g.device)
-        return out(x), out(y)
+        path, x, y = _solve(ctx, layer, g, lbA, ubA, dict(zip(MATRIX_KEYS, (Q, A, L, R))))
+        return path.out(x, g), path.out(y, g)
 
     @staticmethod
     def backward(ctx, grad_x, grad_y):
-        layer = ctx.layer
-        if ctx.serial != layer.solves:
-            raise RuntimeError("backward through a solve that is not the layer's last one: the batch object holds the state of one solve")
-        bt = layer.bt
-        each = tuple(k for k, sh in ctx.shared.items() if not sh)
-        summed = tuple(k for k, sh in ctx.shared.items() if sh)
-        if ctx.device_path:
-            vx, vy = _dev(grad_x, grad_x.device), _dev(grad_y, grad_x.device)
-            r = bt.adjoint_device(vx, vy, matrices=each, reduce=False)
-            mats = {k: r[k] for k in each}
-            if summed:
-                rs = bt.adjoint_device(vx, vy, matrices=summed, reduce=True)
-                mats.update({k: rs[k] for k in summed})
-            layer.info = r["info"]
-            _warn_flagged("LCQPFullSolveFunction", r["info"], bt.B)
-            glb, gub = _bound_grads_device(bt, r["db"], r["side"], ctx.given, grad_x.dtype)
-            gm = [mats[k].to(grad_x.dtype) if k in mats else None for k in MATRIX_KEYS]
-            return (None, r["dg"].to(grad_x.dtype), *gm, glb, gub)
-        vx, vy = _host(grad_x), _host(grad_y)
-        r = bt.adjoint(vx, vy, matrices=each, reduce=False)
-        mats = {k: r[k] for k in each}
-        if summed:
-            rs = bt.adjoint(vx, vy, matrices=summed, reduce=True)
-            mats.update({k: rs[k] for k in summed})
-        dg, db, side, info = r["dg"], r["db"], r["side"], r["info"]
-        layer.info = info
-        bad = int(np.count_nonzero(info))
-        if bad:
-            warnings.warn(f"LCQPFullSolveFunction.backward: {bad} of {bt.B} instances are not differentiable by the library's criteria "
-                          f"(info bits present: {int(np.bitwise_or.reduce(info))}); their gradients are the kernel's output as it is",
-                          RuntimeWarning, stacklevel=2)
-        out = lambda a: torch.as_tensor(a, dtype=grad_x.dtype, device=grad_x.device)
-        parts = capi.split_bound_derivatives(db, side, bt.nV, bt.nC, bt.nComp)
-        eq = side[:, bt.nV:bt.nV + bt.nC] == 2
-        share = np.where(eq, 0.5, 1.0) if all(ctx.given) else 1.0
-        glb = out(parts["dlbA"] * share) if ctx.given[0] else None
-        gub = out(parts["dubA"] * share) if ctx.given[1] else None
-        gm = [out(mats[k]) if k in mats else None for k in MATRIX_KEYS]
-        return (None, out(dg), *gm, glb, gub)
-
-
-SPARSE_VALUE_KEYS = ("Qx", "Ax")
+        return _backward("LCQPFullSolveFunction", ctx, grad_x, grad_y, adjoint=True)
 
 
 class LCQPSparseFullSolveFunction(torch.autograd.Function):
@@ -284,116 +256,12 @@ class LCQPSparseFullSolveFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, layer, g, Qx=None, Ax=None, lbA=None, ubA=None):
-        bt = layer.bt
-        given = dict(zip(SPARSE_VALUE_KEYS, (Qx, Ax)))
-        nnz = dict(Qx=bt.nnzQ, Ax=bt.nnzA)
-        shared = {}
-        for k, t in given.items():
-            if t is None:
-                continue
-            if tuple(t.shape) not in ((bt.B, nnz[k]), (nnz[k],)):
-                raise ValueError(f"{k}: expected [{bt.B}][{nnz[k]}] or [{nnz[k]}], got {tuple(t.shape)}")
-            shared[k] = t.dim() == 1
-        ctx.device_path = layer._on_device(g)
-        layer.last_path = "device" if ctx.device_path else "host"
-        if ctx.device_path:
-            kw = dict(layer._device_bounds(g.device))
-            if lbA is not None: kw["lbA"] = _dev(lbA, g.device)
-            if ubA is not None: kw["ubA"] = _dev(ubA, g.device)
-            if shared:
-                rc = bt.load_device(0, bt.B, _dev(Qx, g.device), _dev(g, g.device), _dev(Ax, g.device), **kw)
-                if rc != 0:
-                    raise RuntimeError(f"load failed with code {rc}: {bt._last_error()}")
-                layer._values_stale = True      # (the host path reads the value arrays back when it next needs them)
-                bt.run()
-            else:
-                rc = bt.update_device(0, bt.B, _dev(g, g.device), **kw)
-                if rc != 0:
-                    raise RuntimeError(f"update failed with code {rc}: {bt._last_error()}")
-                if layer.solves == 0:
-                    bt.run()
-                else:
-                    bt.resolve(warm=layer.warm)
-            x, y = bt.solution_device()
-            layer.solves += 1
-            layer.y, layer.stats = y, None
-            layer._like = (g.dtype, g.device)
-            ctx.layer, ctx.serial = layer, layer.solves
-            ctx.given = (lbA is not None, ubA is not None)
-            ctx.shared = shared
-            return x.to(g.dtype), y.to(g.dtype)
-        kw = dict(layer.bounds)
-        if lbA is not None: kw["lbA"] = _host(lbA)
-        if ubA is not None: kw["ubA"] = _host(ubA)
-        if shared:
-            held = layer._values()
-            for k, t in given.items():
-                if t is not None:
-                    held[k] = np.ascontiguousarray(np.broadcast_to(_host(t), (bt.B, nnz[k])))
-            rc = bt.load(0, bt.B, held["Qx"], _host(g), held["Ax"], **kw)
-            if rc != 0:
-                raise RuntimeError(f"load failed with code {rc}: {bt._last_error()}")
-            bt.run()
-        else:
-            rc = bt.update(0, bt.B, _host(g), **kw)
-            if rc != 0:
-                raise RuntimeError(f"update failed with code {rc}: {bt._last_error()}")
-            if layer.solves == 0:
-                bt.run()
-            else:
-                bt.resolve(warm=layer.warm)
-        x, y, st = bt.solution()
-        layer.solves += 1
-        layer.y, layer.stats = y, st
-        layer._like = (g.dtype, g.device)
-        ctx.layer, ctx.serial = layer, layer.solves
-        ctx.given = (lbA is not None, ubA is not None)
-        ctx.shared = shared
-        out = lambda a: torch.as_tensor(a, dtype=g.dtype, device=g.device)
-        return out(x), out(y)
+        path, x, y = _solve(ctx, layer, g, lbA, ubA, dict(zip(SPARSE_VALUE_KEYS, (Qx, Ax))))
+        return path.out(x, g), path.out(y, g)
 
     @staticmethod
     def backward(ctx, grad_x, grad_y):
-        layer = ctx.layer
-        if ctx.serial != layer.solves:
-            raise RuntimeError("backward through a solve that is not the layer's last one: the batch object holds the state of one solve")
-        bt = layer.bt
-        name = dict(Qx="Q", Ax="A")      # the names of SparseBatchLCQP.adjoint
-        each = tuple(name[k] for k, sh in ctx.shared.items() if not sh)
-        summed = tuple(name[k] for k, sh in ctx.shared.items() if sh)
-        if ctx.device_path:
-            vx, vy = _dev(grad_x, grad_x.device), _dev(grad_y, grad_x.device)
-            r = bt.adjoint_device(vx, vy, matrices=each, reduce=False)
-            mats = {k: r[k] for k in each}
-            if summed:
-                rs = bt.adjoint_device(vx, vy, matrices=summed, reduce=True)
-                mats.update({k: rs[k] for k in summed})
-            layer.info = r["info"]
-            _warn_flagged("LCQPSparseFullSolveFunction", r["info"], bt.B)
-            glb, gub = _bound_grads_device(bt, r["db"], r["side"], ctx.given, grad_x.dtype, sparse=True)
-            gm = [mats[name[k]].to(grad_x.dtype) if name[k] in mats else None for k in SPARSE_VALUE_KEYS]
-            return (None, r["dg"].to(grad_x.dtype), *gm, glb, gub)
-        vx, vy = _host(grad_x), _host(grad_y)
-        r = bt.adjoint(vx, vy, matrices=each, reduce=False)
-        mats = {k: r[k] for k in each}
-        if summed:
-            rs = bt.adjoint(vx, vy, matrices=summed, reduce=True)
-            mats.update({k: rs[k] for k in summed})
-        dg, db, side, info = r["dg"], r["db"], r["side"], r["info"]
-        layer.info = info
-        bad = int(np.count_nonzero(info))
-        if bad:
-            warnings.warn(f"LCQPSparseFullSolveFunction.backward: {bad} of {bt.B} instances are not differentiable by the library's criteria "
-                          f"(info bits present: {int(np.bitwise_or.reduce(info))}); their gradients are the kernel's output as it is",
-                          RuntimeWarning, stacklevel=2)
-        out = lambda a: torch.as_tensor(a, dtype=grad_x.dtype, device=grad_x.device)
-        parts = capi.split_bound_derivatives(db, side, bt.nV, bt.nC, bt.nComp, sparse=True)
-        eq = side[:, :bt.nC] == 2
-        share = np.where(eq, 0.5, 1.0) if all(ctx.given) else 1.0
-        glb = out(parts["dlbA"] * share) if ctx.given[0] else None
-        gub = out(parts["dubA"] * share) if ctx.given[1] else None
-        gm = [out(mats[name[k]]) if name[k] in mats else None for k in SPARSE_VALUE_KEYS]
-        return (None, out(dg), *gm, glb, gub)
+        return _backward("LCQPSparseFullSolveFunction", ctx, grad_x, grad_y, adjoint=True)
 
 
 class BatchLCQPLayer:
@@ -401,8 +269,12 @@ class BatchLCQPLayer:
     BatchLCQP.update: lbL, ubL, lbR, ubR, lbA, ubA, lb, ub) -- an update replaces EVERY vector, so the ones that are not inputs of the
     layer are handed over again with every solve.  warm: re-solves start from the last solution where it exists."""
 
+    # what the arms differ in (_solve and _backward read these): the layout of side, the bound vectors, the matrix inputs of solve in
+    # their order and the name each has in adjoint(matrices=...) -- and _trailing, _held_arrays, _mark_stale, _load below
     sparse = False
     bound_keys = BOUND_KEYS
+    input_keys = MATRIX_KEYS
+    adjoint_names = dict(zip(MATRIX_KEYS, MATRIX_KEYS))
 
     def __init__(self, batch, bounds=None, warm=True):
         capi.lib()      # raises when the HIP library is not built: no CPU fallback
@@ -448,12 +320,25 @@ class BatchLCQPLayer:
         update + resolve of __call__."""
         return LCQPFullSolveFunction.apply(self, g, Q, A, L, R, lbA, ubA)
 
-    def _matrices(self):
+    def _trailing(self, k):
+        """the shape of one instance's matrix k"""
+        bt = self.bt
+        return (dict(Q=bt.nV, A=bt.nC, L=bt.nComp, R=bt.nComp)[k], bt.nV)
+
+    def _held_arrays(self):
         """the matrices the batch holds, [B][..][nV] each: read back once, then kept in step with the loads of solve"""
         if self._held is None:
             ps = [self.bt.read_problem(b) for b in range(self.bt.B)]
             self._held = {k: np.stack([p[k] for p in ps]) for k in MATRIX_KEYS}
         return self._held
+
+    def _mark_stale(self):
+        """after a load on the device path: the host copies of the matrices are read back when they are next needed"""
+        self._held = None
+
+    def _load(self, load, m, g, kw):
+        """load: BatchLCQP.load or .load_device; m: the four matrices by name"""
+        return load(0, self.bt.B, m["Q"], g, m["L"], m["R"], A=m["A"], **kw)
 
     def jacobian(self, serial=None, duals=False):
         """dx/dg of the layer's last solve, [B][nV][nV] ([b][k][j] = dx_k/dg_j), a tensor of the dtype and on the device of that
@@ -489,6 +374,8 @@ class SparseBatchLCQPLayer(BatchLCQPLayer):
     the vectors of SparseBatchLCQP.update the batch was loaded with (lbA, ubA, lbL, ubL, lbR, ubR; the sparse arm has no box)."""
     sparse = True
     bound_keys = tuple(k for k in BOUND_KEYS if k not in ("lb", "ub"))
+    input_keys = SPARSE_VALUE_KEYS
+    adjoint_names = dict(Qx="Q", Ax="A")      # the names of SparseBatchLCQP.adjoint
 
     def __init__(self, batch, bounds=None, warm=True, values=None, general_panel=None):
         """general_panel: True / False is handed to batch.set_general_panel -- jacobian() of a batch on the general sparse LDL' through that
@@ -505,25 +392,36 @@ class SparseBatchLCQPLayer(BatchLCQPLayer):
         if values is not None:
             if set(values) != set(SPARSE_VALUE_KEYS):
                 raise ValueError(f"values: expected the keys {list(SPARSE_VALUE_KEYS)}, got {sorted(values)}")
-            nnz = dict(Qx=batch.nnzQ, Ax=batch.nnzA)
             self.values = {}
             for k in SPARSE_VALUE_KEYS:
                 v = capi._arr(values[k])
-                if v.shape not in ((batch.B, nnz[k]), (nnz[k],)):
-                    raise ValueError(f"values[{k!r}]: expected [{batch.B}][{nnz[k]}] or [{nnz[k]}], got {v.shape}")
-                self.values[k] = np.ascontiguousarray(np.broadcast_to(v, (batch.B, nnz[k])))
+                nnz, = self._trailing(k)
+                if v.shape not in ((batch.B, nnz), (nnz,)):
+                    raise ValueError(f"values[{k!r}]: expected [{batch.B}][{nnz}] or [{nnz}], got {v.shape}")
+                self.values[k] = np.ascontiguousarray(np.broadcast_to(v, (batch.B, nnz)))
 
     def jacobian(self, serial=None):
         """BatchLCQPLayer.jacobian without the dual blocks: the sparse arm has no panel call for them"""
         return super().jacobian(serial)
 
-    def _values(self):
+    def _trailing(self, k):
+        """the shape of one instance's value array k"""
+        return (dict(Qx=self.bt.nnzQ, Ax=self.bt.nnzA)[k],)
+
+    def _held_arrays(self):
         """the value arrays the batch holds, [B][nnz] each, for a load on the host path"""
         if self._values_stale:
             ps = [self.bt.read_problem(b) for b in range(self.bt.B)]
             self.values = {k: np.stack([p[k] for p in ps]) for k in SPARSE_VALUE_KEYS}
             self._values_stale = False
         return self.values
+
+    def _mark_stale(self):
+        self._values_stale = True
+
+    def _load(self, load, m, g, kw):
+        """load: SparseBatchLCQP.load or .load_device; m: the two value arrays by name"""
+        return load(0, self.bt.B, m["Qx"], g, m["Ax"], **kw)
 
     def solve(self, g, Qx=None, Ax=None, lbA=None, ubA=None):
         """(x, y) of the batch for the linear terms g, both differentiable (LCQPSparseFullSolveFunction): y [B][nC + 2 nComp], rows A, L, R.

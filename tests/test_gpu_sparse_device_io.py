@@ -515,3 +515,53 @@ def test_layer_device_path(hip):
     for h, d in zip(*outs):
         assert bits(d.detach().numpy(), h.detach().numpy())
     a.close(); b.close()
+
+
+def test_layer_device_path_equality_rows_and_flagged_instances(hip):
+    """both bounds of an equality row as inputs (each gets half of the row's derivative) and the one warning about flagged instances,
+    through layer(g, lbA, ubA) and through layer.solve(g, lbA=, ubA=): the same bits and the same warning from both paths"""
+    from lcqpow_amd.diff import SparseBatchLCQPLayer
+    key = "small"
+    ds, _ = instances_of(key)
+    B, n, nC, nK = len(ds), ds[0]["nV"], ds[0]["nC"], ds[0]["nComp"]
+    a, b = make(hip, key), make(hip, key)
+    load_host(a, ds); load_host(b, ds)
+    lo, hi = stack(ds, "lbA").copy(), stack(ds, "ubA").copy()
+    lo[:, 0] = hi[:, 0] = 0.5 * (lo[:, 0] + hi[:, 0])      # row 0 of every instance: an equality inside the old range
+    gs = stack(ds, "g").copy(); gs[1, 0] = np.nan           # instance 1: no trial of its polish is accepted, the solve fails
+    la, lb_ = SparseBatchLCQPLayer(a), SparseBatchLCQPLayer(b)
+    rng = np.random.default_rng(4)
+    wx, wy = rng.standard_normal((B, n)), rng.standard_normal((B, nC + 2 * nK))
+
+    def run(layer, where):
+        out, messages = [], []
+        for full in (False, True):
+            t = {k: torch.tensor(v, dtype=torch.float64, device=where, requires_grad=True) for k, v in dict(g=gs, lbA=lo, ubA=hi).items()}
+            if full:
+                x, y = layer.solve(t["g"], lbA=t["lbA"], ubA=t["ubA"])
+                loss = (x * torch.as_tensor(wx, device=where)).sum() + (y * torch.as_tensor(wy, device=where)).sum()
+            else:
+                x = y = layer(t["g"], t["lbA"], t["ubA"])
+                loss = (x * torch.as_tensor(wx, device=where)).sum()
+            with warnings.catch_warnings(record=True) as rec:
+                warnings.simplefilter("always")
+                loss.backward()
+            messages += [(w.category, str(w.message)) for w in rec]
+            out += [x, y, t["g"].grad, t["lbA"].grad, t["ubA"].grad, torch.as_tensor(layer.info)]
+        return out, messages
+
+    host, said = run(la, "cpu")
+    device, said_d = run(lb_, "cuda:0")
+    assert la.last_path == "host" and lb_.last_path == "device"
+    assert len(host) == len(device) == 12
+    for i, (h, d) in enumerate(zip(host, device)):      # (bits, not torch.equal: what the failed instance returns may hold NaNs)
+        assert d.is_cuda and bits(d.detach().cpu().numpy(), h.detach().numpy()), i
+    assert said == said_d and len(said) == 2 and all(c is RuntimeWarning for c, _ in said)      # one per backward
+    assert said[0][1].startswith(f"LCQPSolveFunction.backward: 1 of {B} instances")
+    assert said[1][1].startswith(f"LCQPSparseFullSolveFunction.backward: 1 of {B} instances")
+    for x, y, dg, dlo, dhi, info in (host[:6], host[6:]):
+        ok = info == 0
+        assert ok.tolist() == [i != 1 for i in range(B)] and info[1] & 1
+        assert torch.equal(dlo[:, 0], dhi[:, 0]) and torch.all(dlo[ok, 0] != 0)      # the equality row: half to each bound
+        assert not torch.any((dlo[:, 1:] != 0) & (dhi[:, 1:] != 0))                # every other row sits on one bound at the most
+    a.close(); b.close()
