@@ -138,7 +138,13 @@ void lcqp_hip_batch_destroy(lcqp_hip_batch_t* b);
 /* LCQProblem::setOptions, include/LCQProblem.ipp:160-163 */
 int  lcqp_hip_batch_set_options(lcqp_hip_batch_t* b, const lcqp_options_t* opt);
 /* LCQProblem::loadLCQP (dense), src/LCQProblem.cpp:87-144, for instances [first, first+count):
- * arrays are host pointers, packed instance after instance ([count][...]); NULL as in the reference. */
+ * arrays are host pointers, packed instance after instance ([count][...]); NULL as in the reference.
+ * The host load and update are the device path (lcqp_hip_batch_load_device / _update_device below) behind an upload: after the argument
+ * and value checks, which run on the host over the whole range, the arrays go to the device as they are, in chunks of whole instances
+ * through two pinned slots into a device staging of two chunks, and the pack kernels of the device path build the pools from each chunk.
+ * A chunk holds at most 16 MiB and at most half the staging cap of lcqp_hip_batch_set_jacobian_staging (one instance always fits); the
+ * pools do not depend on the chunking.  Synchronous: the arrays are free on return.  A failing load, like a failing update, leaves the
+ * range untouched: nothing is written, and no host state changes. */
 int  lcqp_hip_batch_load(lcqp_hip_batch_t* b, int first, int count,
                          const double* Q, const double* g, const double* L, const double* R,
                          const double* lbL, const double* ubL, const double* lbR, const double* ubR,
@@ -241,7 +247,8 @@ int  lcqp_hip_batch_sensitivity_blocked(lcqp_hip_batch_t* b, int nrhs, const dou
  * LCQP_INVALID_ARGUMENT: NULL handle or Jg, first < 0, count < 1, first + count > B.  LCQP_LCQPOBJECT_NOT_SETUP as lcqp_hip_batch_sensitivity. */
 #define LCQP_JACOBIAN_STAGING_BYTES (1ull << 30)
 int  lcqp_hip_batch_jacobian(lcqp_hip_batch_t* b, int first, int count, double* Jg, double* Jb, int* side, int* info);
-/* another staging cap for this object's Jacobian calls (0: the default); for tests of the chunking and for small devices */
+/* another staging cap for this object's Jacobian and adjoint calls and for the two chunks of staging of a host load / update (0: the
+ * default); for tests of the chunking and for small devices */
 int  lcqp_hip_batch_set_jacobian_staging(lcqp_hip_batch_t* b, size_t bytes);
 /* The full adjoint (DESIGN.md section 3a''''): lcqp_hip_batch_sensitivity with nrhs = 1, extended by upstream gradients on the returned duals
  * and by the gradients in the matrices.  At the returned point x, y_W solve  H x + g - E_W' y_W = 0,  E_W x = b_W  (H = Q + sigma_p I; y in the
@@ -446,7 +453,10 @@ int  lcqp_hip_sparse_border(const lcqp_hip_sparse_t* s);                 /* bord
 int  lcqp_hip_sparse_get_ordering(const lcqp_hip_sparse_t* s, int* perm);
 int  lcqp_hip_sparse_set_options(lcqp_hip_sparse_t* s, const lcqp_options_t* opt);
 /* loadLCQP, sparse overload (src/LCQProblem.cpp:390-441), values only: Qx [count][nnzQ], Ax [count][nnzA] in the CSC order of
- * the pattern; y0 [count][nC + 2 nComp]; NULL as in the reference */
+ * the pattern; y0 [count][nC + 2 nComp]; NULL as in the reference.  load and update are the device path (lcqp_hip_sparse_load_device /
+ * _update_device below) behind an upload, as lcqp_hip_batch_load: checks on the host over the whole range, then chunks of instances
+ * (at most 16 MiB, at most half the cap of lcqp_hip_sparse_set_adjoint_staging) through two pinned slots to the pack kernels, in stream
+ * order behind a run in flight, one synchronisation at the end.  A failing load or update leaves the range and the host state untouched. */
 int  lcqp_hip_sparse_load(lcqp_hip_sparse_t* s, int first, int count, const double* Qx, const double* g, const double* Ax,
                           const double* lbA, const double* ubA, const double* lbL, const double* ubL, const double* lbR,
                           const double* ubR, const double* x0, const double* y0);
@@ -544,8 +554,8 @@ int  lcqp_hip_sparse_jacobian(lcqp_hip_sparse_t* s, int first, int count, double
  * are decided before any device call. */
 int  lcqp_hip_sparse_adjoint(lcqp_hip_sparse_t* s, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
                              int reduce, double* dQx, double* dAx);
-/* another staging cap for this handle's adjoint, blocked-sensitivity and Jacobian calls (0: the default, LCQP_JACOBIAN_STAGING_BYTES); for
- * tests of the chunking and for small devices */
+/* another staging cap for this handle's adjoint, blocked-sensitivity and Jacobian calls and for the two chunks of staging of a host load /
+ * update (0: the default, LCQP_JACOBIAN_STAGING_BYTES); for tests of the chunking and for small devices */
 int  lcqp_hip_sparse_set_adjoint_staging(lcqp_hip_sparse_t* s, size_t bytes);
 /* ---- Device-pointer entry points of the sparse batch (DESIGN.md section 3a''''', "The sparse arm"): the twins of lcqp_hip_sparse_load / _update /
  * _get_solution / _sensitivity / _adjoint whose data pointers are DEVICE pointers, under the rules of the dense device calls above.  Layouts,
@@ -557,7 +567,7 @@ int  lcqp_hip_sparse_set_adjoint_staging(lcqp_hip_sparse_t* s, size_t bytes);
  *   stream    the caller's hipStream_t (NULL: the legacy default stream).  The handle's stream waits for an event recorded on it, the work is
  *             enqueued on the handle's stream, and the caller's stream waits for an event recorded behind it.  run and resolve stay on the
  *             handle's stream: update_device -> resolve -> get_solution_device needs no host wait, and update_device does not drain the
- *             stream the way lcqp_hip_sparse_update does -- stream order replaces that.  load_device and update_device wait for ONE status
+ *             stream first -- stream order replaces that.  load_device and update_device wait for ONE status
  *             read each (the check below; for a load with Qx also two numbers per instance from the diagonal of its Hessian, from which the
  *             host forms the ratio that selects the ordering); a call also waits when a buffer of the handle grows.  Nothing else waits.
  *   shared    (load) bit 1: Qx is ONE [nnzQ] array for all `count` instances, bit 2: the same for Ax (broadcast by the pack kernel; the
@@ -565,8 +575,7 @@ int  lcqp_hip_sparse_set_adjoint_staging(lcqp_hip_sparse_t* s, size_t bytes);
  *   NULL Qx / Ax (load) leaves those values as the batch holds them; every instance of the range must then already hold a problem, else
  *             LCQP_INVALID_ARGUMENT (the host twin's code for a missing matrix).  g stays mandatory: LCQP_INVALID_OBJECTIVE_LINEAR_TERM.
  *   validation -inf in lbL / lbR is looked for by one kernel over the whole range before anything is written; on a failure nothing is
- *             written, NO host state changes, and the code is LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND.  This is deliberately stricter than
- *             lcqp_hip_sparse_load, which clears the setup mark first and may have written the instances in front of the offending one.
+ *             written, NO host state changes, and the code is LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND, as with lcqp_hip_sparse_load.
  *   NULL handle: LCQP_LCQPOBJECT_NOT_SETUP from all five.
  * The two paths mix on one handle: the host state (which instances hold problems, the lbL / lbR flags, the diagonal ratios, the setup mark)
  * is kept in step.  sensitivity_device / adjoint_device make the state checks of their host twins (LCQP_INVALID_ARGUMENT for NULL v / vx / dg,

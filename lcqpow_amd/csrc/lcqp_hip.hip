@@ -177,8 +177,7 @@ extern "C" lcqp_hip_batch_t* lcqp_hip_batch_create(int batch, int nV, int nC, in
     if (!kernels) return nullptr;
     if (hipError_t e = hipSetDevice(device)) { hip_fail(g_err, "hipSetDevice(device)", e); return nullptr; }
     std::unique_ptr<lcqp_hip_batch> h(new lcqp_hip_batch(device));
-    for (hipError_t e : {h->stream.status, h->side.status, h->ev0.status, h->ev1.status, h->ev2.status, h->evFork.status, h->evJoin.status, h->evIn.status, h->evOut.status,
-                         h->stage[0].done.status, h->stage[1].done.status})
+    for (hipError_t e : {h->stream.status, h->side.status, h->ev0.status, h->ev1.status, h->ev2.status, h->evFork.status, h->evJoin.status, h->evIn.status, h->evOut.status})
         if (e != hipSuccess) { hip_fail(g_err, "stream/event creation", e); return nullptr; }
     { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) h->numCU = cu; }
     DevBatch& d = h->db;
@@ -246,19 +245,20 @@ extern "C" int lcqp_hip_batch_read_profile(lcqp_hip_batch_t* h, unsigned long lo
 
 extern "C" void* lcqp_hip_batch_stream(lcqp_hip_batch_t* h) { return h ? (void*)h->stream.s : nullptr; }
 
-// both pinned staging slots hold at least `bytes`
-static int stage_reserve(lcqp_hip_batch* h, size_t bytes)
+// The host load and update are the device path behind an upload: the caller's arrays (v, and for a load Q, A, L, R: host memory, [count][..]
+// each, null: absent) go to the device in chunks of instances, and dense_pack -- the kernels of lcqp_hip_batch_load_device / _update_device --
+// builds the pools of [first, first + count) from them.  Synchronous: the arrays are free on return.
+static int dense_upload(lcqp_hip_batch* h, int first, int count, const PackVectors& v, const double* Q, const double* A, const double* L,
+                        const double* R, bool update)
 {
-    if (h->stageBytes >= bytes) return 0;
-    h->stageBytes = 0;
-    for (StageSlot& st : h->stage) {
-        HIPCHK(g_err, hipEventSynchronize(st.done));
-        if (st.buf) (void)hipHostFree(st.buf);
-        st.buf = nullptr;
-        HIPCHK(g_err, hipHostMalloc(&st.buf, bytes, hipHostMallocDefault));
-    }
-    h->stageBytes = bytes;
-    return 0;
+    const DevBatch& d = h->db;
+    const size_t n = d.n, nC = d.nC, nComp = d.nComp, nd = d.nd;
+    const RawArray raw[] = {{v.g, n}, {v.lbL, nComp}, {v.ubL, nComp}, {v.lbR, nComp}, {v.ubR, nComp}, {v.lbA, nC}, {v.ubA, nC}, {v.lb, n}, {v.ub, n},
+                            {v.x0, n}, {v.y0, nd}, {Q, n * n}, {A, nC * n}, {L, nComp * n}, {R, nComp * n}};
+    return upload_packed(g_err, h, count, raw, [&](int c0, int cb, const double* const* p) {
+        return dense_pack(h, first + c0, cb, PackVectors{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8], p[9], p[10]},
+                          PackMatrices{{p[11], p[12], p[13], p[14]}, {n * n, nC * n, nComp * n, nComp * n}}, update);
+    });
 }
 
 extern "C" int lcqp_hip_batch_load(lcqp_hip_batch_t* h, int first, int count,
@@ -269,74 +269,21 @@ extern "C" int lcqp_hip_batch_load(lcqp_hip_batch_t* h, int first, int count,
 { return guarded(g_err, [&] {
     if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
     DevBatch& d = h->db;
-    const int n = d.n, nC = d.nC, nComp = d.nComp, mA = d.mA, np = d.np, mE = d.mEcap;
-    if (first < 0 || count <= 0 || first + count > d.B) return LCQP_INVALID_ARGUMENT;
+    const size_t n = d.n, nC = d.nC, nComp = d.nComp;
+    if (first < 0 || count <= 0 || first > d.B - count) return LCQP_INVALID_ARGUMENT;
     if (!Q) return LCQP_INVALID_ARGUMENT;
     if (!g) return LCQP_INVALID_OBJECTIVE_LINEAR_TERM;               // include/LCQProblem.ipp:44-45
     if (!A && nC > 0) return LCQP_INVALID_CONSTRAINT_MATRIX;         // src/LCQProblem.cpp:569-570
     if (!L || !R) return LCQP_INVALID_COMPLEMENTARITY_MATRIX;        // :611-612
     if ((lb || ub) && d.boxcap == 0) { g_err = "batch was created without box-bound capacity"; return LCQP_INVALID_ARGUMENT; }
+    if (int rc = check_lower_bounds((size_t)count * nComp, lbL, lbR)) return rc;      // the last check: from here on the range is written
     HIPCHK(g_err, hipSetDevice(h->device));
-    // pinned staging: [Qp | Ep | nvb | mvb | ybuf | lbuf | rbuf | info | bidx]
-    const size_t nQ = (size_t)np * np, nE = (size_t)mE * np, nNV = (size_t)V_NUM * np, nMV = (size_t)M_NUM * mE;
-    const size_t nY = (size_t)d.nd, nLR = (size_t)(nComp ? nComp : 1);
-    const size_t infoDbl = (sizeof(InstInfo) + 7) / 8, bidxDbl = ((size_t)np * sizeof(int) + 7) / 8;
-    const size_t slotBytes = sizeof(double) * (nQ + nE + nNV + nMV + nY + 2 * nLR + infoDbl + bidxDbl);
-    if (int rc = stage_reserve(h, slotBytes)) return rc;
     h->rs.invalidate();
-    for (int k = 0; k < count; k++) {
-        const size_t b = (size_t)first + k;
-        StageSlot& slot = h->stage[k & 1];
-        HIPCHK(g_err, hipEventSynchronize(slot.done));            // the copies that last used this slot are done
-        double* Qp = (double*)slot.buf;
-        double* Ep = Qp + nQ; double* nvb = Ep + nE; double* mvb = nvb + nNV; double* ybuf = mvb + nMV;
-        double* lbuf = ybuf + nY; double* rbuf = lbuf + nLR;
-        InstInfo* info = (InstInfo*)(rbuf + nLR);
-        int* bidx = (int*)((double*)info + infoDbl);
-        memset(Qp, 0, slotBytes);
-        for (int i = 0; i < n; i++) memcpy(&Qp[(size_t)i * np], Q + ((size_t)k * n + i) * n, sizeof(double) * n);       // setQ .ipp:27-36
-        // setConstraints :563-626: stack [A; L; R]
-        for (int r = 0; r < nC; r++) memcpy(&Ep[(size_t)r * np], A + ((size_t)k * nC + r) * n, sizeof(double) * n);
-        for (int r = 0; r < nComp; r++) {
-            memcpy(&Ep[(size_t)(nC + r) * np], L + ((size_t)k * nComp + r) * n, sizeof(double) * n);
-            memcpy(&Ep[(size_t)(nC + nComp + r) * np], R + ((size_t)k * nComp + r) * n, sizeof(double) * n);
-        }
-        int rc = pack_row_bounds(d, h->anyLoaded, first, k, lbA, ubA, lbL, ubL, lbR, ubR, &mvb[(size_t)M_L * mE], &mvb[(size_t)M_U * mE], lbuf, rbuf);
-        if (rc) return rc;
-        double* vg = &nvb[(size_t)V_G * np];
-        double* vlb = &nvb[(size_t)V_LB * np];
-        double* vub = &nvb[(size_t)V_UB * np];
-        double* vx0 = &nvb[(size_t)V_X0 * np];
-        int nfin = 0;
-        for (int i = 0; i < np; i++) { vlb[i] = -INFINITY; vub[i] = INFINITY; }
-        for (int i = 0; i < n; i++) {
-            vg[i] = g[(size_t)k * n + i];
-            vlb[i] = bnd(lb, (size_t)k * n + i, -INFINITY);     // setLB/setUB .ipp:54-112
-            vub[i] = bnd(ub, (size_t)k * n + i, INFINITY);
-            vx0[i] = x0 ? x0[(size_t)k * n + i] : 0.0;          // setInitialGuess .ipp:133-158
-            const bool fin = std::isfinite(vlb[i]) || std::isfinite(vub[i]);
-            h->boxed[b * n + i] = fin;
-            if (fin) bidx[nfin++] = i;
-        }
-        h->rs.filled[b] = 1;
-        info->nfin = nfin; info->mE = mA + nfin; info->hasY0 = y0 ? 1 : 0;
-        HIPCHK(g_err, hipMemcpyAsync(d.Q + b * nQ, Qp, sizeof(double) * nQ, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(g_err, hipMemcpyAsync(d.E + b * nE, Ep, sizeof(double) * nE, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(g_err, hipMemcpyAsync(d.nv + b * nNV, nvb, sizeof(double) * nNV, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(g_err, hipMemcpyAsync(d.mv + b * nMV, mvb, sizeof(double) * nMV, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(g_err, hipMemcpyAsync(d.boxidx + b * np, bidx, sizeof(int) * np, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(g_err, hipMemcpyAsync(d.info + b, info, sizeof(InstInfo), hipMemcpyHostToDevice, h->stream));
-        if (nComp) {
-            HIPCHK(g_err, hipMemcpyAsync(d.lbL + b * nComp, lbuf, sizeof(double) * nComp, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(g_err, hipMemcpyAsync(d.lbR + b * nComp, rbuf, sizeof(double) * nComp, hipMemcpyHostToDevice, h->stream));
-        }
-        if (y0) {
-            memcpy(ybuf, y0 + (size_t)k * d.nd, sizeof(double) * d.nd);
-            HIPCHK(g_err, hipMemcpyAsync(d.y0 + b * nY, ybuf, sizeof(double) * nY, hipMemcpyHostToDevice, h->stream));
-        }
-        HIPCHK(g_err, hipEventRecord(slot.done, h->stream));
-    }
-    HIPCHK(g_err, hipStreamSynchronize(h->stream));
+    load_bound_flags(d, h->anyLoaded, first, lbL, lbR);
+    for (size_t j = 0; j < (size_t)count * n; j++)      // setLB / setUB, include/LCQProblem.ipp:54-112
+        h->boxed[(size_t)first * n + j] = std::isfinite(bnd(lb, j, -INFINITY)) || std::isfinite(bnd(ub, j, INFINITY));
+    std::fill_n(h->rs.filled.begin() + first, count, 1);
+    if (int rc = dense_upload(h, first, count, PackVectors{g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0}, Q, A, L, R, false)) return rc;
     h->anyLoaded = true;
     return 0;
 }); }
@@ -464,7 +411,7 @@ extern "C" int lcqp_hip_batch_update(lcqp_hip_batch_t* h, int first, int count, 
 { return guarded(g_err, [&] {
     if (int rc = check_update(g_err, h, first, count, g, lbL, lbR)) return rc;
     DevBatch& d = h->db;
-    const int n = d.n, nComp = d.nComp, mA = d.mA, np = d.np, mE = d.mEcap;
+    const int n = d.n;
     for (int k = 0; k < count; k++)
         for (int i = 0; i < n; i++) {
             const size_t j = (size_t)k * n + i;
@@ -475,50 +422,8 @@ extern "C" int lcqp_hip_batch_update(lcqp_hip_batch_t* h, int first, int count, 
             }
         }
     HIPCHK(g_err, hipSetDevice(h->device));
-    // pinned staging: [g | lb | ub | x0 | lE | uE | y0 | lbuf | rbuf | hasY0]
-    const size_t nY = (size_t)d.nd, nLR = (size_t)(nComp ? nComp : 1);
-    const size_t slotBytes = sizeof(double) * (4 * (size_t)np + 2 * (size_t)mA + nY + 2 * nLR + 1);
-    if (int rc = stage_reserve(h, slotBytes)) return rc;
-    for (int k = 0; k < count; k++) {
-        const size_t b = (size_t)first + k;
-        StageSlot& slot = h->stage[k & 1];
-        HIPCHK(g_err, hipEventSynchronize(slot.done));            // the copies that last used this slot are done
-        double* vg = (double*)slot.buf;
-        double *vlb = vg + np, *vub = vlb + np, *vx0 = vub + np, *lE = vx0 + np, *uE = lE + mA, *ybuf = uE + mA, *lbuf = ybuf + nY, *rbuf = lbuf + nLR;
-        int* hasY0 = (int*)(rbuf + nLR);
-        memset(vg, 0, slotBytes);
-        fill_row_bounds(d, k, lbA, ubA, lbL, ubL, lbR, ubR, lE, uE, lbuf, rbuf);
-        d.hasLbL |= lbL ? 1 : 0; d.hasLbR |= lbR ? 1 : 0;      // switched on, never off: whatever the order of the calls (an absent vector is the zero vector)
-        for (int i = 0; i < np; i++) { vlb[i] = -INFINITY; vub[i] = INFINITY; }
-        for (int i = 0; i < n; i++) {
-            vg[i] = g[(size_t)k * n + i];
-            vlb[i] = bnd(lb, (size_t)k * n + i, -INFINITY);
-            vub[i] = bnd(ub, (size_t)k * n + i, INFINITY);
-            vx0[i] = x0 ? x0[(size_t)k * n + i] : 0.0;
-        }
-        *hasY0 = y0 ? 1 : 0;
-        double* nvb = d.nv + b * (size_t)V_NUM * np;
-        double* mvb = d.mv + b * (size_t)M_NUM * mE;
-        static_assert(V_UB == V_LB + 1 && V_X0 == V_UB + 1, "lb, ub and x0 go over in one copy");
-        HIPCHK(g_err, hipMemcpyAsync(nvb + (size_t)V_G * np, vg, sizeof(double) * np, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(g_err, hipMemcpyAsync(nvb + (size_t)V_LB * np, vlb, sizeof(double) * 3 * np, hipMemcpyHostToDevice, h->stream));
-        if (mA) {      // the bounds of the box rows behind them follow from V_LB / V_UB on the device (k_prepare, k_refresh)
-            HIPCHK(g_err, hipMemcpyAsync(mvb + (size_t)M_L * mE, lE, sizeof(double) * mA, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(g_err, hipMemcpyAsync(mvb + (size_t)M_U * mE, uE, sizeof(double) * mA, hipMemcpyHostToDevice, h->stream));
-        }
-        HIPCHK(g_err, hipMemcpyAsync(&d.info[b].hasY0, hasY0, sizeof(int), hipMemcpyHostToDevice, h->stream));
-        if (nComp) {
-            HIPCHK(g_err, hipMemcpyAsync(d.lbL + b * nComp, lbuf, sizeof(double) * nComp, hipMemcpyHostToDevice, h->stream));
-            HIPCHK(g_err, hipMemcpyAsync(d.lbR + b * nComp, rbuf, sizeof(double) * nComp, hipMemcpyHostToDevice, h->stream));
-        }
-        if (y0) {
-            memcpy(ybuf, y0 + (size_t)k * d.nd, sizeof(double) * d.nd);
-            HIPCHK(g_err, hipMemcpyAsync(d.y0 + b * nY, ybuf, sizeof(double) * nY, hipMemcpyHostToDevice, h->stream));
-        }
-        HIPCHK(g_err, hipEventRecord(slot.done, h->stream));
-    }
-    HIPCHK(g_err, hipStreamSynchronize(h->stream));
-    return 0;
+    d.hasLbL |= lbL ? 1 : 0; d.hasLbR |= lbR ? 1 : 0;      // switched on, never off: whatever the order of the calls (an absent vector is the zero vector)
+    return dense_upload(h, first, count, PackVectors{g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0}, nullptr, nullptr, nullptr, nullptr, true);
 }); }
 
 // Solve again on the setup in place: k_refresh instead of the five setup kernels, then the homotopy launch.  Without a setup that belongs
@@ -530,11 +435,11 @@ extern "C" int lcqp_hip_batch_resolve(lcqp_hip_batch_t* h, int mode, const doubl
     HIPCHK(g_err, hipSetDevice(h->device));
     const bool withRho = mode == 1 && rho0;
     if (withRho) {
-        if (int rc = stage_reserve(h, sizeof(double) * (size_t)B)) return rc;
-        HIPCHK(g_err, hipEventSynchronize(h->stage[0].done));
-        memcpy(h->stage[0].buf, rho0, sizeof(double) * (size_t)B);
-        HIPCHK(g_err, hipMemcpyAsync(h->rs.rhoStart, h->stage[0].buf, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(g_err, hipEventRecord(h->stage[0].done, h->stream));
+        if (int rc = h->up.reserve(g_err, sizeof(double) * (size_t)B)) return rc;
+        HIPCHK(g_err, hipEventSynchronize(h->up.slot[0].done));
+        memcpy(h->up.slot[0].buf, rho0, sizeof(double) * (size_t)B);
+        HIPCHK(g_err, hipMemcpyAsync(h->rs.rhoStart, h->up.slot[0].buf, sizeof(double) * (size_t)B, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(g_err, hipEventRecord(h->up.slot[0].done, h->stream));
     }
     HIPCHK(g_err, hipEventRecord(h->ev0, h->stream));
     h->k->refresh(h->db, B, h->stream, mode, withRho ? h->rs.rhoStart : nullptr);

@@ -14,13 +14,6 @@
 // the error slot of the dense arm (one thread_local string, defined in lcqp_hip.hip): what lcqp_hip_last_error returns for all three units
 std::string& dense_err();
 
-// a pinned staging slot of loadLCQP and the event of the copies that last read it
-struct StageSlot {
-    void* buf = nullptr;
-    lcqp_rt::Event done{hipEventDisableTiming};
-    ~StageSlot() { if (buf) (void)hipHostFree(buf); }
-};
-
 // The members are released in reverse order after the destructor's synchronisation: device memory, staging slots, events, streams.
 struct lcqp_hip_batch {
     lcqp::DevBatch db;
@@ -29,9 +22,7 @@ struct lcqp_hip_batch {
     lcqp_rt::Stream stream, side;
     lcqp_rt::Event ev0, ev1, ev2;         // run: setup from ev0 to ev1, homotopy from ev1 to ev2
     lcqp_rt::Event evFork{hipEventDisableTiming}, evJoin{hipEventDisableTiming};
-    // two pinned staging slots for loadLCQP: instance k is packed into slot k&1 while slot (k-1)&1 is in flight
-    StageSlot stage[2];
-    size_t stageBytes = 0;
+    lcqp_rt::UploadStage up;              // the staging of the host load / update (upload_packed); resolve sends rho0 through its first slot
     lcqp_rt::DevMem mem{stream};
     int numCU = 256;
     bool overlapped = false;      // lcqp_hip_batch_set_overlapped
@@ -71,6 +62,16 @@ int batch_jacobian_duals(lcqp_hip_batch* h, int first, int count, double* Jyg, d
 // rowpos[o][j] of Jyg [count][nd][n] and Jyb [count][nd][nd] (or null); rowpos < 0: the row is not part of the result
 void launch_pack_dual_rows(const lcqp::DevBatch& d, hipStream_t s, int count, int ldb, const double* dg, const double* db, const int* rowpos,
                            double* Jyg, double* Jyb);
+
+// lcqp_hip_device.hip: the pack step of a load / an update, the one definition of the pool layout.  Device pointers to the arrays as the caller
+// holds them, of the `count` instances that go to [first, first + count):
+// the vectors, [count][..] each, null = absent (the defaults of lcqp_hip_batch_load)
+struct PackVectors { const double *g, *lbL, *ubL, *lbR, *ubR, *lbA, *ubA, *lb, *ub, *x0, *y0; };
+// the matrices of a load: [count][rows][n], or [rows][n] with stride 0 (shared); null: the block of the pool stays
+struct PackMatrices { const double* src[4]; size_t stride[4]; };      // Q, A, L, R
+// k_pack_matrices and k_pack_vectors (update: k_pack_vectors alone, m is not read) on h->stream; nothing waits.  The checks and the host
+// state are the caller's.
+int dense_pack(lcqp_hip_batch* h, int first, int count, const PackVectors& v, const PackMatrices& m, bool update);
 
 // the message of lcqp_hip_batch_update and its device twin for a variable whose box bound appears or disappears
 inline std::string box_change_message(int variable, int instance, bool gains)

@@ -1,5 +1,6 @@
 // lcqp_hip_device.hip -- the dense batch's device-pointer entry points that fill and read the pools: lcqp_hip_batch_load_device,
-// _update_device and _get_solution_device (include/lcqp_hip.h, DESIGN.md section 3a'''''), with their three kernels.  The twins of
+// _update_device and _get_solution_device (include/lcqp_hip.h, DESIGN.md section 3a'''''), with their three kernels, and dense_pack, the pack step
+// the host load / update of lcqp_hip.hip run behind their upload: the pack kernels are the one definition of the pool layout.  The twins of
 // _sensitivity and _adjoint sit beside the kernels they launch, in lcqp_hip.hip; lcqp_hip_batch.hpp holds what the two units share, lcqp_host_rt.hpp the hand-over
 // around every such call (device_call) and _get_solution_device, which are the sparse arm's too.
 #include "lcqp_hip_batch.hpp"
@@ -17,11 +18,7 @@ using namespace lcqp_rt;
 // =================================================================================================
 // device kernels: size-independent streaming kernels, no LDS tiles
 // =================================================================================================
-// the vectors of a load / an update as the caller holds them: [count][..] each, null = absent (the defaults of lcqp_hip_batch_load)
-struct PackVectors { const double *g, *lbL, *ubL, *lbR, *ubR, *lbA, *ubA, *lb, *ub, *x0, *y0; };
-// the matrices of a load: [count][rows][n], or [rows][n] with stride 0 (shared); null: the block of the pool stays
-struct PackMatrices { const double* src[4]; size_t stride[4]; };      // Q, A, L, R
-
+// (PackVectors, PackMatrices: the arrays of a load / an update as the caller holds them, lcqp_hip_batch.hpp)
 __device__ __forceinline__ double vec_or(const double* p, size_t i, double dflt) { return p ? p[i] : dflt; }
 
 // ---- k_check_vectors: the value checks of lcqp_hip_batch_load / _update over the whole range, before anything is written ----
@@ -190,6 +187,20 @@ void launch_pack_dual_rows(const DevBatch& d, hipStream_t s, int count, int ldb,
 
 #define g_err dense_err()      // the error slot of the dense arm (thread_local, lcqp_hip.hip)
 
+int dense_pack(lcqp_hip_batch* h, int first, int count, const PackVectors& v, const PackMatrices& m, bool update)
+{
+    const DevBatch& d = h->db;
+    if (!update) {
+        const int half = d.np / 2, mostRows = std::max(d.np, std::max(d.nC, std::max(d.nComp, d.mEcap - d.mA)));
+        const unsigned gx = (unsigned)std::min<size_t>(((size_t)mostRows * half + 4 * WG - 1) / (4 * WG), 4096);      // four pieces per thread
+        hipLaunchKernelGGL(k_pack_matrices, dim3(gx, std::min(count, 65535), 5), dim3(WG), 0, h->stream, d, first, count, m);
+        HIPCHK(g_err, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_pack_vectors, dim3(count), dim3(WG), 0, h->stream, d, first, count, v, update ? 1 : 0);
+    HIPCHK(g_err, hipGetLastError());
+    return 0;
+}
+
 // the status words (and, for a load, the box flags behind them) of k_check_vectors: [2] words, then [B][n] bytes
 static int check_buffer(lcqp_hip_batch* h)
 {
@@ -262,21 +273,13 @@ extern "C" int lcqp_hip_batch_load_device(lcqp_hip_batch_t* h, int first, int co
         unsigned long long words[2];
         if (int rc = check_vectors(h, first, count, pv, false, words, (lb || ub) ? flags.data() : nullptr)) return rc;
         if (words[0] != ~0ull) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
-        // the host state of lcqp_hip_batch_load: the setup mark, the lbL / lbR flags by the rule of pack_row_bounds, the box flags
+        // the host state of lcqp_hip_batch_load: the setup mark, the lbL / lbR flags, the box flags
         h->rs.invalidate();
-        const int hasL = lbL ? 1 : 0, hasR = lbR ? 1 : 0;
-        if (!h->anyLoaded || first == 0) { d.hasLbL = hasL; d.hasLbR = hasR; }
-        else { d.hasLbL |= hasL; d.hasLbR |= hasR; }
+        load_bound_flags(d, h->anyLoaded, first, lbL, lbR);
         for (int k = 0; k < count; k++) h->rs.filled[(size_t)first + k] = 1;
         memcpy(h->boxed.data() + (size_t)first * n, flags.data(), flags.size());
         h->anyLoaded = true;
-        const int half = d.np / 2, mostRows = std::max(d.np, std::max(nC, std::max(nComp, d.mEcap - d.mA)));
-        const unsigned gx = (unsigned)std::min<size_t>(((size_t)mostRows * half + 4 * WG - 1) / (4 * WG), 4096);      // four pieces per thread
-        hipLaunchKernelGGL(k_pack_matrices, dim3(gx, std::min(count, 65535), 5), dim3(WG), 0, h->stream, d, first, count, pm);
-        HIPCHK(g_err, hipGetLastError());
-        hipLaunchKernelGGL(k_pack_vectors, dim3(count), dim3(WG), 0, h->stream, d, first, count, pv, 0);
-        HIPCHK(g_err, hipGetLastError());
-        return 0;
+        return dense_pack(h, first, count, pv, pm, false);
     });
 }); }
 
@@ -285,8 +288,7 @@ extern "C" int lcqp_hip_batch_update_device(lcqp_hip_batch_t* h, int first, int 
                                             const double* lbA, const double* ubA, const double* lb, const double* ub,
                                             const double* x0, const double* y0, void* stream)
 { return guarded(g_err, [&] {
-    // (the checks of check_update that need no values, in its order; the values are checked on the device)
-    if (int rc = check_update(g_err, h, first, count, g, (const double*)nullptr, (const double*)nullptr)) return rc;
+    if (int rc = check_update(g_err, h, first, count, g)) return rc;      // (the values are checked on the device)
     DevBatch& d = h->db;
     HIPCHK(g_err, hipSetDevice(h->device));
     const PackVectors pv = {g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0};
@@ -301,9 +303,7 @@ extern "C" int lcqp_hip_batch_update_device(lcqp_hip_batch_t* h, int first, int 
             return LCQP_INVALID_ARGUMENT;
         }
         d.hasLbL |= lbL ? 1 : 0; d.hasLbR |= lbR ? 1 : 0;
-        hipLaunchKernelGGL(k_pack_vectors, dim3(count), dim3(WG), 0, h->stream, d, first, count, pv, 1);
-        HIPCHK(g_err, hipGetLastError());
-        return 0;
+        return dense_pack(h, first, count, pv, PackMatrices{}, true);
     });
 }); }
 

@@ -1,6 +1,7 @@
 // lcqp_host_rt.hpp -- host runtime shared by the C ABIs of the dense (lcqp_hip.hip, lcqp_hip_device.hip, lcqp_hip_qp.hip, lcqp_hip_util.hip) and sparse
 // (lcqp_sparse_host.hip, lcqp_sparse_device.hip) arms: error reporting, owners of streams, events and device memory, and the entry-point bodies both arms have
-// in common -- solution, options, trace, re-solves, the buffers of a sensitivity launch, the hand-over of a device-pointer call.  What drives the sensitivity,
+// in common -- solution, options, trace, re-solves, the buffers of a sensitivity launch, the hand-over of a device-pointer call, the upload of a host
+// load / update.  What drives the sensitivity,
 // Jacobian and adjoint kernels on top of these is lcqp_sens_rt.hpp.  Host code only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -9,6 +10,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
+#include <cstring>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -195,18 +197,44 @@ struct ResolveState {
     void invalidate() { setupValid = solved = false; }
 };
 
-// *_update: the checks both arms make, in this order, before anything is written
-template <class H>
-int check_update(std::string&, H* h, int first, int count, const double* g, const double* lbL, const double* lbR)
+// the value check of a host load / update over its whole range ([count * nComp] each, null: absent): a lower complementarity bound of
+// -inf is refused (the device-pointer twins make the same test in their check kernel)
+inline int check_lower_bounds(size_t entries, const double* lbL, const double* lbR)
 {
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    const auto& d = h->db;
-    if (first < 0 || count <= 0 || first > d.B - count) return LCQP_INVALID_ARGUMENT;
-    for (int k = 0; k < count; k++) if (!h->rs.filled[(size_t)first + k]) return LCQP_LCQPOBJECT_NOT_SETUP;
-    if (!g) return LCQP_INVALID_OBJECTIVE_LINEAR_TERM;
-    for (size_t j = 0; j < (size_t)count * d.nComp; j++)
+    for (size_t j = 0; j < entries; j++)
         if (bnd(lbL, j, 0.0) <= -INFINITY || bnd(lbR, j, 0.0) <= -INFINITY) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
     return 0;
+}
+
+// *_update and *_update_device: the checks both arms make that need no values, in this order; the host calls add the values' (lbL, lbR
+// on the host).  Nothing has been written when one of them fails.
+template <class H>
+int check_update(std::string&, H* h, int first, int count, const double* g)
+{
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (first < 0 || count <= 0 || first > h->db.B - count) return LCQP_INVALID_ARGUMENT;
+    for (int k = 0; k < count; k++) if (!h->rs.filled[(size_t)first + k]) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!g) return LCQP_INVALID_OBJECTIVE_LINEAR_TERM;
+    return 0;
+}
+template <class H>
+int check_update(std::string& err, H* h, int first, int count, const double* g, const double* lbL, const double* lbR)
+{
+    if (int rc = check_update(err, h, first, count, g)) return rc;
+    return check_lower_bounds((size_t)count * h->db.nComp, lbL, lbR);
+}
+
+// The lbL / lbR flags of a batch at a load (host or device) of a range that starts at `first`.  A batch may mix instances with and without
+// lbL / lbR: an absent bound vector is the zero vector, and the phi expressions of src/LCQProblem.cpp:969-996 with zeros are the arithmetic
+// of an instance loaded without them, bit for bit.  The batch-wide flags only say whether ANY instance carries bounds, i.e. whether the
+// kernels read the (zero-filled) arrays at all: the first load of the handle, or a load starting at instance 0, starts them over, every
+// other load -- and every update -- adds to them.
+template <class D>
+void load_bound_flags(D& d, bool loaded, int first, const double* lbL, const double* lbR)
+{
+    const int hasL = lbL ? 1 : 0, hasR = lbR ? 1 : 0;
+    if (!loaded || first == 0) { d.hasLbL = hasL; d.hasLbR = hasR; }
+    else { d.hasLbL |= hasL; d.hasLbR |= hasR; }
 }
 
 // *_resolve up to the launches: an error code, RESOLVE_RUNS when no setup belongs to the matrices and options in place (the call is then
@@ -403,41 +431,101 @@ int get_solution_device(std::string& err, H* h, size_t ndual, double* x, double*
     });
 }
 
-#pragma GCC visibility pop
-
-// Row bounds of instance k of a load (setConstraints / setComplementarityBounds, src/LCQProblem.cpp:563-626, 726-785): lE / uE rows
-// [0, nC) from lbA / ubA (default -inf / +inf), rows nC + i and nC + nComp + i from lbL / ubL and lbR / ubR (default 0 / +inf); lo / ro:
-// the lower bounds the phi terms read.  A lower complementarity bound of -inf is refused.
-// A batch may mix instances with and without lbL / lbR: an absent bound vector is the zero vector, and the phi expressions of :969-996
-// with zeros are the arithmetic of an instance loaded without them, bit for bit.  The batch-wide flags only say whether ANY instance
-// carries bounds, i.e. whether the kernels read the (zero-filled) arrays at all; the first load of the handle, or a load starting at
-// instance 0, starts them over (k == 0), the other instances and loads add to them (pack_row_bounds; fill_row_bounds leaves the flags
-// to its caller).
-template <class D>
-int fill_row_bounds(const D& d, int k, const double* lbA, const double* ubA, const double* lbL, const double* ubL,
-                    const double* lbR, const double* ubR, double* lE, double* uE, double* lo, double* ro)
+// a device buffer of the handle with room for `count` doubles (the stream is drained before a smaller one is freed)
+template <class H>
+int grow(std::string& err, H* h, double*& p, size_t& cap, size_t count)
 {
-    const int nC = d.nC, nComp = d.nComp;
-    for (int r = 0; r < nC; r++) { lE[r] = bnd(lbA, (size_t)k * nC + r, -INFINITY); uE[r] = bnd(ubA, (size_t)k * nC + r, INFINITY); }
-    for (int i = 0; i < nComp; i++) {
-        const size_t j = (size_t)k * nComp + i;
-        if (bnd(lbL, j, 0.0) <= -INFINITY || bnd(lbR, j, 0.0) <= -INFINITY) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
-        lE[nC + i] = lo[i] = bnd(lbL, j, 0.0);
-        uE[nC + i] = bnd(ubL, j, INFINITY);
-        lE[nC + nComp + i] = ro[i] = bnd(lbR, j, 0.0);
-        uE[nC + nComp + i] = bnd(ubR, j, INFINITY);
-    }
+    if (count <= cap) return 0;
+    HIPCHK(err, hipStreamSynchronize(h->stream));
+    h->mem.release(p);
+    p = nullptr; cap = 0;
+    if (!h->mem.alloc(err, p, count)) return LCQP_HIP_ERROR;
+    cap = count;
     return 0;
 }
 
-template <class D>
-int pack_row_bounds(D& d, bool loaded, int first, int k, const double* lbA, const double* ubA, const double* lbL, const double* ubL,
-                    const double* lbR, const double* ubR, double* lE, double* uE, double* lo, double* ro)
+// The chunks of a call with nItems work items of itemBytes of staging each under the cap: whole items, at least one per chunk.
+inline size_t staging_chunk(size_t cap, size_t itemBytes, size_t nItems)
 {
-    const int hasL = lbL ? 1 : 0, hasR = lbR ? 1 : 0;
-    if (k == 0 && (!loaded || first == 0)) { d.hasLbL = hasL; d.hasLbR = hasR; }
-    else { d.hasLbL |= hasL; d.hasLbR |= hasR; }
-    return fill_row_bounds(d, k, lbA, ubA, lbL, ubL, lbR, ubR, lE, uE, lo, ro);
+    size_t chunk = itemBytes ? cap / itemBytes : nItems;
+    if (chunk < 1) chunk = 1;
+    return chunk < nItems ? chunk : nItems;
 }
+
+// ---- the host load / update of both arms (lcqp_hip.hip, lcqp_sparse_host.hip) are transport only: the caller's raw arrays go to the device
+// in chunks of instances, and the arm's pack step -- the kernels of its device-pointer load / update -- builds the pools from them.  H has
+// stream, mem, the staging cap sn.staging and the member `up` ----
+// a pinned staging slot and the event of the copy that last read it
+struct StageSlot {
+    void* buf = nullptr;
+    Event done{hipEventDisableTiming};
+    ~StageSlot() { if (buf) (void)hipHostFree(buf); }
+};
+// two pinned slots -- chunk k is gathered into slot k & 1 while the copy out of slot (k - 1) & 1 is in flight -- and the device staging
+// of two chunks behind them (owned by the handle's DevMem)
+struct UploadStage {
+    StageSlot slot[2];
+    size_t slotBytes = 0;
+    double* dev = nullptr;
+    size_t devCap = 0;
+    // both pinned slots hold at least `bytes`
+    int reserve(std::string& err, size_t bytes)
+    {
+        for (const StageSlot& st : slot) if (st.done.status != hipSuccess) return hip_fail(err, "hipEventCreate", st.done.status);
+        if (slotBytes >= bytes) return 0;
+        slotBytes = 0;
+        for (StageSlot& st : slot) {
+            HIPCHK(err, hipEventSynchronize(st.done));
+            if (st.buf) (void)hipHostFree(st.buf);
+            st.buf = nullptr;
+            HIPCHK(err, hipHostMalloc(&st.buf, bytes, hipHostMallocDefault));
+        }
+        slotBytes = bytes;
+        return 0;
+    }
+};
+
+// one raw array of a host load / update: [count][per] doubles on the host; null or per = 0: absent
+struct RawArray { const double* src; size_t per; };
+// A chunk is whole instances, at least one, of at most UPLOAD_CHUNK_BYTES and at most half the handle's staging cap (the device staging
+// holds two chunks).  Small chunks keep the pinned memory small and let the gather of one chunk hide behind the copy of the one before.
+constexpr size_t UPLOAD_CHUNK_BYTES = (size_t)16 << 20;
+
+// The arrays of `count` instances to the device and through pack(c0, cb, dev): for the chunk [c0, c0 + cb) of the range, dev[a] is array a
+// of the chunk on the device ([cb][per]; null where the array is absent), and pack enqueues the pack step on h->stream.  Stream order
+// keeps a chunk's staging until its pack kernels have read it; the one synchronisation is at the end, so the caller's arrays are free on
+// return.  The value checks come before the call: nothing here depends on the values.
+template <class H, size_t N, class P>
+int upload_packed(std::string& err, H* h, int count, const RawArray (&arr)[N], P pack)
+{
+    size_t per = 0;
+    for (const RawArray& a : arr) if (a.src) per += a.per;
+    const size_t chunk = staging_chunk(std::min(h->sn.staging / 2, UPLOAD_CHUNK_BYTES), sizeof(double) * per, count);
+    UploadStage& up = h->up;
+    if (int rc = up.reserve(err, sizeof(double) * chunk * per)) return rc;
+    if (int rc = grow(err, h, up.dev, up.devCap, 2 * chunk * per)) return rc;
+    for (size_t c0 = 0, turn = 0; c0 < (size_t)count; c0 += chunk, turn ^= 1) {
+        const size_t cb = std::min(chunk, (size_t)count - c0);
+        StageSlot& slot = up.slot[turn];
+        HIPCHK(err, hipEventSynchronize(slot.done));      // the copy that last read this slot is done
+        double *pinned = static_cast<double*>(slot.buf), *staged = up.dev + turn * chunk * per;
+        const double* dev[N];
+        size_t at = 0;
+        for (size_t a = 0; a < N; a++) {
+            const bool there = arr[a].src && arr[a].per;
+            dev[a] = there ? staged + at : nullptr;
+            if (!there) continue;
+            std::memcpy(pinned + at, arr[a].src + c0 * arr[a].per, sizeof(double) * cb * arr[a].per);
+            at += cb * arr[a].per;
+        }
+        HIPCHK(err, hipMemcpyAsync(staged, pinned, sizeof(double) * at, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(err, hipEventRecord(slot.done, h->stream));
+        if (int rc = pack((int)c0, (int)cb, dev)) return rc;
+    }
+    HIPCHK(err, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+#pragma GCC visibility pop
 
 }  // namespace lcqp_rt

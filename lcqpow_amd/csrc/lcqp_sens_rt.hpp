@@ -1,6 +1,6 @@
 // lcqp_sens_rt.hpp -- the host code behind the sensitivity, Jacobian and adjoint entry points of both arms (lcqp_hip.hip, lcqp_sparse_host.hip):
-// the state a handle keeps for them (member sn) and the one copy of what drives their kernels -- buffer growth, the staging cap, the timed
-// launch, the call around a sensitivity kernel, the Jacobian through a vector kernel, the chunks of a host adjoint.  Templates on the handle H
+// the state a handle keeps for them (member sn) and the one copy of what drives their kernels -- the staging cap (grow and staging_chunk
+// are lcqp_host_rt.hpp's: the host load / update use them too), the timed launch, the call around a sensitivity kernel, the Jacobian through a vector kernel, the chunks of a host adjoint.  Templates on the handle H
 // (lcqp_hip_batch / lcqp_hip_sparse: device, stream, mem, db, rs, sn) like those of lcqp_host_rt.hpp; what differs between the arms -- the
 // kernels, their pitches, the width of the dual vector -- comes in as arguments and callables.  Host code only.
 #pragma once
@@ -26,19 +26,6 @@ struct SensState {
     float pendingMs = 0.f;
 };
 
-// a device buffer of the handle with room for `count` doubles (the stream is drained before a smaller one is freed)
-template <class H>
-int grow(std::string& err, H* h, double*& p, size_t& cap, size_t count)
-{
-    if (count <= cap) return 0;
-    HIPCHK(err, hipStreamSynchronize(h->stream));
-    h->mem.release(p);
-    p = nullptr; cap = 0;
-    if (!h->mem.alloc(err, p, count)) return LCQP_HIP_ERROR;
-    cap = count;
-    return 0;
-}
-
 // *_set_jacobian_staging / *_set_adjoint_staging; 0: back to the default
 template <class H>
 int set_staging(H* h, size_t bytes)
@@ -46,14 +33,6 @@ int set_staging(H* h, size_t bytes)
     if (!h) return LCQP_INVALID_ARGUMENT;
     h->sn.staging = bytes ? bytes : (size_t)LCQP_JACOBIAN_STAGING_BYTES;
     return 0;
-}
-
-// The chunks of a call with nItems work items of itemBytes of staging each under the cap: whole items, at least one per chunk.
-inline size_t staging_chunk(size_t cap, size_t itemBytes, size_t nItems)
-{
-    size_t chunk = itemBytes ? cap / itemBytes : nItems;
-    if (chunk < 1) chunk = 1;
-    return chunk < nItems ? chunk : nItems;
 }
 
 // one launch on stream s between two events, checked

@@ -21,6 +21,7 @@ struct lcqp_hip_sparse {
     int cus = 0;                   // compute units of `device` (create): bounds the persistent wavefronts of a run
     lcqp_rt::Stream stream;
     lcqp_rt::Event ev0, ev1, ev2;           // run: setup from ev0 to ev1, homotopy from ev1 to ev2
+    lcqp_rt::UploadStage up;                // the staging of the host load / update (upload_packed)
     lcqp_rt::DevMem mem{stream};            // zero-fills on the handle's stream
     std::vector<int> csr2csc;      // value order: E (CSR) entry k comes from entry csr2csc[k] of the caller's CSC arrays
     // the two orderings of the band (lcqp_sparse_pattern.hpp: Pattern::ord): device copies of their maps, the permutation for get_ordering
@@ -50,5 +51,15 @@ struct lcqp_hip_sparse {
 // lcqp_sparse_host.hip; the comments are at the definitions
 void sp_choose_ordering(lcqp_hip_sparse* h);
 int sp_value_map(lcqp_hip_sparse* h);
+
+// lcqp_sparse_device.hip: the pack step of a load / an update, the one definition of the pool layout.  Device pointers to the arrays as the
+// caller holds them, of the `count` instances that go to [first, first + count):
+// the vectors, [count][..] each, null = absent (the defaults of lcqp_hip_sparse_load)
+struct SpPackVectors { const double *g, *lbA, *ubA, *lbL, *ubL, *lbR, *ubR, *x0, *y0; };
+// the value arrays of a load: [count][nnz], or [nnz] with stride 0 (shared); null: the values of the pool stay
+struct SpPackValues { const double *Qx, *Ax; size_t qStride, aStride; };
+// k_sparse_pack_values (Ax needs sp_value_map first) and k_sparse_pack_vectors (update: k_sparse_pack_vectors alone, m is not read) on
+// h->stream; nothing waits.  The checks and the host state are the caller's.
+int sparse_pack(lcqp_hip_sparse* h, int first, int count, const SpPackVectors& v, const SpPackValues& m, bool update);
 
 #pragma GCC visibility pop

@@ -1,5 +1,6 @@
 // lcqp_sparse_device.hip -- the sparse batch's device-pointer entry points that fill and read the pools: lcqp_hip_sparse_load_device,
-// _update_device and _get_solution_device (include/lcqp_hip.h, DESIGN.md section 3a'''''), with their three kernels, and the diagnostic
+// _update_device and _get_solution_device (include/lcqp_hip.h, DESIGN.md section 3a'''''), with their three kernels, sparse_pack -- the pack step
+// the host load / update of lcqp_sparse_host.hip run behind their upload: the pack kernels are the one definition of the pool layout -- and the diagnostic
 // reader lcqp_hip_sparse_read_problem.  The twins of _sensitivity and _adjoint sit beside the kernels they launch, in lcqp_sparse_host.hip;
 // lcqp_sparse_batch.hpp holds what the two units share, lcqp_host_rt.hpp the hand-over around every such call (device_call) and
 // _get_solution_device, which are the dense arm's too.  The model is lcqp_hip_device.hip of the dense arm.
@@ -19,11 +20,7 @@ using namespace lcqp_sparse;
 // device kernels: size-independent streaming kernels, no LDS tiles
 // =================================================================================================
 constexpr int SP_DEV_WG = 256;
-// the vectors of a load / an update as the caller holds them: [count][..] each, null = absent (the defaults of lcqp_hip_sparse_load)
-struct SpPackVectors { const double *g, *lbA, *ubA, *lbL, *ubL, *lbR, *ubR, *x0, *y0; };
-// the value arrays of a load: [count][nnz], or [nnz] with stride 0 (shared); null: the values of the pool stay
-struct SpPackValues { const double *Qx, *Ax; size_t qStride, aStride; };
-
+// (SpPackVectors, SpPackValues: the arrays of a load / an update as the caller holds them, lcqp_sparse_batch.hpp)
 __device__ __forceinline__ double sp_vec_or(const double* p, size_t i, double dflt) { return p ? p[i] : dflt; }
 
 // ---- k_sparse_check_vectors: the value checks of lcqp_hip_sparse_load / _update over the whole range, before anything is written ----
@@ -143,6 +140,21 @@ __global__ __launch_bounds__(SP_DEV_WG) void k_sparse_pack_vectors(SpBatch db, i
 // =================================================================================================
 #define g_sp_err sparse_err()      // the error slot of the sparse arm (thread_local, lcqp_sparse_host.hip)
 
+int sparse_pack(lcqp_hip_sparse* h, int first, int count, const SpPackVectors& v, const SpPackValues& m, bool update)
+{
+    const SpBatch& d = h->db;
+    if (!update && (m.Qx || m.Ax)) {
+        const int most = std::max(m.Qx ? d.nnzQ : 0, m.Ax ? d.nnzE : 0);
+        const unsigned gx = (unsigned)std::min<size_t>(((size_t)most + 4 * SP_DEV_WG - 1) / (4 * SP_DEV_WG), 4096);      // four entries per thread
+        hipLaunchKernelGGL(k_sparse_pack_values, dim3(std::max(gx, 1u), std::min(count, 65535), 2), dim3(SP_DEV_WG), 0, h->stream, d, first, count, m,
+                           (const int*)h->valMap);
+        HIPCHK(g_sp_err, hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_sparse_pack_vectors, dim3(count), dim3(SP_DEV_WG), 0, h->stream, d, first, v, update ? 1 : 0);
+    HIPCHK(g_sp_err, hipGetLastError());
+    return 0;
+}
+
 // the status word of k_sparse_check_vectors and the diagonal pairs of a load behind it: [2] words, then [B][2] doubles
 static int sp_check_buffer(lcqp_hip_sparse* h)
 {
@@ -202,11 +214,9 @@ extern "C" int lcqp_hip_sparse_load_device(lcqp_hip_sparse_t* h, int first, int 
         std::vector<unsigned long long> chk;
         if (int rc = sp_check_vectors(h, count, pv, Qx, pm.qStride, nq, chk)) return rc;
         if (chk[0] != ~0ull) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
-        // the host state of lcqp_hip_sparse_load: the setup mark, the lbL / lbR flags by the rule of pack_row_bounds, the diagonal ratios, the ordering
+        // the host state of lcqp_hip_sparse_load: the setup mark, the lbL / lbR flags, the diagonal ratios, the ordering
         h->rs.invalidate();
-        const int hasL = lbL ? 1 : 0, hasR = lbR ? 1 : 0;
-        if (!h->loaded || first == 0) { d.hasLbL = hasL; d.hasLbR = hasR; }
-        else { d.hasLbL |= hasL; d.hasLbR |= hasR; }
+        load_bound_flags(d, h->loaded, first, lbL, lbR);
         for (int k = 0; k < count; k++) {
             h->rs.filled[(size_t)first + k] = 1;
             if (!Qx) continue;
@@ -217,16 +227,7 @@ extern "C" int lcqp_hip_sparse_load_device(lcqp_hip_sparse_t* h, int first, int 
         }
         h->loaded = true;
         sp_choose_ordering(h);
-        if (Qx || Ax) {
-            const int most = std::max(Qx ? d.nnzQ : 0, Ax ? d.nnzE : 0);
-            const unsigned gx = (unsigned)std::min<size_t>(((size_t)most + 4 * SP_DEV_WG - 1) / (4 * SP_DEV_WG), 4096);      // four entries per thread
-            hipLaunchKernelGGL(k_sparse_pack_values, dim3(std::max(gx, 1u), std::min(count, 65535), 2), dim3(SP_DEV_WG), 0, h->stream, d, first, count, pm,
-                               (const int*)h->valMap);
-            HIPCHK(g_sp_err, hipGetLastError());
-        }
-        hipLaunchKernelGGL(k_sparse_pack_vectors, dim3(count), dim3(SP_DEV_WG), 0, h->stream, d, first, pv, 0);
-        HIPCHK(g_sp_err, hipGetLastError());
-        return 0;
+        return sparse_pack(h, first, count, pv, pm, false);
     });
 }); }
 
@@ -234,21 +235,18 @@ extern "C" int lcqp_hip_sparse_update_device(lcqp_hip_sparse_t* h, int first, in
                                              const double* lbA, const double* ubA, const double* lbL, const double* ubL,
                                              const double* lbR, const double* ubR, const double* x0, const double* y0, void* stream)
 { return guarded(g_sp_err, [&] {
-    // (the checks of check_update that need no values, in its order; the values are checked on the device)
-    if (int rc = check_update(g_sp_err, h, first, count, g, (const double*)nullptr, (const double*)nullptr)) return rc;
+    if (int rc = check_update(g_sp_err, h, first, count, g)) return rc;      // (the values are checked on the device)
     SpBatch& d = h->db;
     HIPCHK(g_sp_err, hipSetDevice(h->device));
     const SpPackVectors pv = {g, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0};
     if (!sp_vectors_ok(h, count, pv)) return LCQP_INVALID_ARGUMENT;
-    // no drain of the handle's stream as in lcqp_hip_sparse_update: the kernels below are behind a run in flight on the same stream
+    // no drain of the handle's stream: the kernels below are behind a run in flight on the same stream
     return device_call(g_sp_err, h, stream, [&] {
         std::vector<unsigned long long> chk;
         if (int rc = sp_check_vectors(h, count, pv, nullptr, 0, 0, chk)) return rc;
         if (chk[0] != ~0ull) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
         d.hasLbL |= lbL ? 1 : 0; d.hasLbR |= lbR ? 1 : 0;
-        hipLaunchKernelGGL(k_sparse_pack_vectors, dim3(count), dim3(SP_DEV_WG), 0, h->stream, d, first, pv, 1);
-        HIPCHK(g_sp_err, hipGetLastError());
-        return 0;
+        return sparse_pack(h, first, count, pv, SpPackValues{}, true);
     });
 }); }
 

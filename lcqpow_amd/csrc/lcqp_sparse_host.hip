@@ -307,6 +307,19 @@ extern "C" int lcqp_hip_sparse_get_trace(lcqp_hip_sparse_t* h, int instance, int
     return guarded(g_sp_err, [&] { return get_trace(g_sp_err, h, instance, cap, scalars, x, len); });
 }
 
+// The host load and update are the device path behind an upload: the caller's arrays (v, and for a load Qx and Ax: host memory, [count][..]
+// each, null: absent) go to the device in chunks of instances, and sparse_pack -- the kernels of lcqp_hip_sparse_load_device /
+// _update_device -- builds the pools of [first, first + count) from them.  Synchronous: the arrays are free on return.
+static int sparse_upload(lcqp_hip_sparse* h, int first, int count, const SpPackVectors& v, const double* Qx, const double* Ax, bool update)
+{
+    const SpBatch& d = h->db;
+    const size_t n = d.n, m = d.m, nC = d.nC, nK = d.nComp, nnzQ = d.nnzQ, nnzE = d.nnzE;
+    const RawArray raw[] = {{v.g, n}, {v.lbA, nC}, {v.ubA, nC}, {v.lbL, nK}, {v.ubL, nK}, {v.lbR, nK}, {v.ubR, nK}, {v.x0, n}, {v.y0, m}, {Qx, nnzQ}, {Ax, nnzE}};
+    return upload_packed(g_sp_err, h, count, raw, [&](int c0, int cb, const double* const* p) {
+        return sparse_pack(h, first + c0, cb, SpPackVectors{p[0], p[1], p[2], p[3], p[4], p[5], p[6], p[7], p[8]}, SpPackValues{p[9], p[10], nnzQ, nnzE}, update);
+    });
+}
+
 // LCQProblem::loadLCQP (sparse overload, src/LCQProblem.cpp:390-441) for instances [first, first + count): values only -- the
 // pattern was given to lcqp_hip_sparse_create.  Qx: [count][nnzQ]; Ax: [count][nnzA] in the CSC order of the stacked [A; L; R].
 extern "C" int lcqp_hip_sparse_load(lcqp_hip_sparse_t* h, int first, int count, const double* Qx, const double* g, const double* Ax,
@@ -315,36 +328,23 @@ extern "C" int lcqp_hip_sparse_load(lcqp_hip_sparse_t* h, int first, int count, 
 { return guarded(g_sp_err, [&] {
     if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
     SpBatch& d = h->db;
-    const int n = d.n, m = d.m, nK = d.nComp;
-    if (first < 0 || count <= 0 || first + count > d.B || !Qx || !Ax) return LCQP_INVALID_ARGUMENT;
+    const int n = d.n, nK = d.nComp;
+    if (first < 0 || count <= 0 || first > d.B - count || !Qx || !Ax) return LCQP_INVALID_ARGUMENT;
     if (!g) return LCQP_INVALID_OBJECTIVE_LINEAR_TERM;
+    if (int rc = check_lower_bounds((size_t)count * nK, lbL, lbR)) return rc;      // the last check: from here on the range is written
     HIPCHK(g_sp_err, hipSetDevice(h->device));
+    if (int rc = sp_value_map(h)) return rc;
     h->rs.invalidate();
-    std::vector<double> ex(d.nnzE), nvb((size_t)NV_NUM * n), mvb((size_t)MV_NUM * m), lb(nK), rb(nK);
+    load_bound_flags(d, h->loaded, first, lbL, lbR);
     for (int k = 0; k < count; k++) {
-        const size_t b = (size_t)first + k;
-        for (int e = 0; e < d.nnzE; e++) ex[e] = Ax[(size_t)k * d.nnzE + h->csr2csc[e]];
-        std::fill(nvb.begin(), nvb.end(), 0.0); std::fill(mvb.begin(), mvb.end(), 0.0);
-        for (int i = 0; i < n; i++) { nvb[(size_t)NV_G * n + i] = g[(size_t)k * n + i]; nvb[(size_t)NV_X0 * n + i] = x0 ? x0[(size_t)k * n + i] : 0.0; }
-        const int rc = pack_row_bounds(d, h->loaded, first, k, lbA, ubA, lbL, ubL, lbR, ubR, &mvb[(size_t)MV_L * m], &mvb[(size_t)MV_U * m], lb.data(), rb.data());
-        if (rc) return rc;
-        if (y0) for (int r = 0; r < m; r++) mvb[(size_t)MV_Y0 * m + r] = y0[(size_t)k * m + r];
-        SpInfo info; memset(&info, 0, sizeof(info)); info.hasY0 = y0 ? 1 : 0;
         double dmin = INFINITY, dmax = 0.0;
         for (int i = 0; i < n; i++) { const double q = h->qdiagHost[i] >= 0 ? Qx[(size_t)k * d.nnzQ + h->qdiagHost[i]] : 0.0; dmin = std::min(dmin, q); dmax = std::max(dmax, std::fabs(q)); }
-        h->diagRatio[b] = (dmax > 0.0 && dmin > 0.0) ? dmin / dmax : 0.0;
-        HIPCHK(g_sp_err, hipMemcpy(d.Qx + b * d.nnzQ, Qx + (size_t)k * d.nnzQ, sizeof(double) * d.nnzQ, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(d.Ex + b * d.nnzE, ex.data(), sizeof(double) * d.nnzE, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(d.nv + b * NV_NUM * n, nvb.data(), sizeof(double) * nvb.size(), hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(d.mv + b * MV_NUM * m, mvb.data(), sizeof(double) * mvb.size(), hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(d.lbL + b * nK, lb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(d.lbR + b * nK, rb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(d.info + b, &info, sizeof(info), hipMemcpyHostToDevice));
-        h->rs.filled[b] = 1;
+        h->diagRatio[(size_t)first + k] = (dmax > 0.0 && dmin > 0.0) ? dmin / dmax : 0.0;
+        h->rs.filled[(size_t)first + k] = 1;
     }
     h->loaded = true;
     sp_choose_ordering(h);
-    return 0;
+    return sparse_upload(h, first, count, SpPackVectors{g, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0}, Qx, Ax, false);
 }); }
 
 /* -DLCQP_SCHED_PROFILE builds: per phase (rows 0 .. PH_NUM-1: start, round, trial, factor, correct, qp end; row PH_NUM: polls without work) the clock
@@ -388,27 +388,10 @@ extern "C" int lcqp_hip_sparse_update(lcqp_hip_sparse_t* h, int first, int count
 { return guarded(g_sp_err, [&] {
     if (int rc = check_update(g_sp_err, h, first, count, g, lbL, lbR)) return rc;
     SpBatch& d = h->db;
-    const int n = d.n, m = d.m, nK = d.nComp;
     HIPCHK(g_sp_err, hipSetDevice(h->device));
-    HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));      // a run in flight reads what is written below
-    static_assert(MV_U == MV_L + 1, "l and u go over in one copy");
-    std::vector<double> lu((size_t)2 * m), lb(nK), rb(nK), x0z(x0 ? 0 : n, 0.0);
-    const int hasY0 = y0 ? 1 : 0;
-    for (int k = 0; k < count; k++) {
-        const size_t b = (size_t)first + k;
-        fill_row_bounds(d, k, lbA, ubA, lbL, ubL, lbR, ubR, lu.data(), lu.data() + m, lb.data(), rb.data());
-        d.hasLbL |= lbL ? 1 : 0; d.hasLbR |= lbR ? 1 : 0;      // switched on, never off (an absent vector is the zero vector)
-        double* nvb = d.nv + b * NV_NUM * n;
-        double* mvb = d.mv + b * MV_NUM * m;
-        HIPCHK(g_sp_err, hipMemcpy(nvb + (size_t)NV_G * n, g + (size_t)k * n, sizeof(double) * n, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(nvb + (size_t)NV_X0 * n, x0 ? x0 + (size_t)k * n : x0z.data(), sizeof(double) * n, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(mvb + (size_t)MV_L * m, lu.data(), sizeof(double) * 2 * m, hipMemcpyHostToDevice));
-        if (y0) HIPCHK(g_sp_err, hipMemcpy(mvb + (size_t)MV_Y0 * m, y0 + (size_t)k * m, sizeof(double) * m, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(d.lbL + b * nK, lb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(d.lbR + b * nK, rb.data(), sizeof(double) * nK, hipMemcpyHostToDevice));
-        HIPCHK(g_sp_err, hipMemcpy(&d.info[b].hasY0, &hasY0, sizeof(int), hipMemcpyHostToDevice));
-    }
-    return 0;
+    d.hasLbL |= lbL ? 1 : 0; d.hasLbR |= lbR ? 1 : 0;      // switched on, never off (an absent vector is the zero vector)
+    // (no drain of the stream: the copies and the pack kernel are behind a run in flight on it)
+    return sparse_upload(h, first, count, SpPackVectors{g, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0}, nullptr, nullptr, true);
 }); }
 
 // Solve again on the setup in place: k_sparse_refresh where a run has k_sparse_setup, then the homotopy launch.  Without a setup that
