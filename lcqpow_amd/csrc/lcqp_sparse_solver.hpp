@@ -557,10 +557,10 @@ __device__ __forceinline__ int sp_ph_qpend(SpCtx<G>& c, SpState& S)
     double sq = 0.0, sl = 0.0;      // pk'(Q + rho C) pk and pk'((Q + rho C) xk + g~)
     if (perturbed) {
         // the perturbation has to reach the penalty gradient rho C xk -- it is there to break the symmetry of problems like warm_up
-        // (perturbStep :1353-1362) -- so C xk is taken from the perturbed xk: one more pass over E, the column gather carries two
-        // vectors.  (Q xk is not: 2.2e-16 per component is below its rounding; the dense kernel does the same.)
-        sp_Ex<G>(c, xk, lx);
-        sp_C_from_Ex<G, true>(c, exs, lx, [](int) { return NoPre{}; }, [&](int i, double cxq, double cxk, NoPre) { Cx[i] = cxk; Cp[i] = cxq - cxk; });
+        // (perturbStep :1353-1362) -- so C xk is formed from the perturbed xk and C pk from pk itself (pk = xq - xk is the unperturbed
+        // difference: C xq - C xk would not be C pk), both in one pass over E and one column gather, as the dense kernel does.
+        // (Q xk is not re-formed: 2.2e-16 per component is below its rounding; the dense kernel does the same.)
+        sp_Cx2<G>(c, pk, xk, Cp, Cx);
         c.bytes += 3.0 * db.by[BY_E];
     } else {
         // C pk and, in the same pass, the two sums of the step length (round 5: they were a pass of their own over pk, Qp, Cp, Qx, Cx, gtil)
