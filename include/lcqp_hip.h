@@ -126,6 +126,9 @@ int  lcqp_hip_qp_read_setup(lcqp_hip_qp_t* qp, int dims[9], double scal[2], doub
 int  lcqp_hip_qp_read_working_set(lcqp_hip_qp_t* qp, int dims[2], int* slot_row, int* crow, int* row_slot, double* Ti);
 int  lcqp_hip_qp_read_admm(lcqp_hip_qp_t* qp, int dims[6], double scal[3], double* FK, double* rhov, double* l, double* u,
                            double* xa, double* ya, double* za, double* dy, double* dx);
+/* lcqp_hip_batch_read_polish (below) for the batch of one; k_qp_solve keeps the row state in its global arrays (dims[9] says what the
+ * homotopy kernel of that shape would do and does not concern this object) */
+int  lcqp_hip_qp_read_polish(lcqp_hip_qp_t* qp, int dims[12], double scal[7], double* V, double* M, int* I);
 
 /* ------------------------------------------------------------------------------------------------
  * Batch of B independent dense LCQPs of one shape (nV, nC, nComp).
@@ -177,6 +180,17 @@ int  lcqp_hip_batch_read_working_set(lcqp_hip_batch_t* b, int instance, int dims
  * LCQP_LCQPOBJECT_NOT_SETUP: no setup belongs to the data in place (before lcqp_hip_batch_setup / lcqp_hip_batch_run). */
 int  lcqp_hip_batch_read_admm(lcqp_hip_batch_t* b, int instance, int dims[6], double scal[3], double* FK, double* rhov, double* l, double* u,
                               double* xa, double* ya, double* za, double* dy, double* dx);
+/* The state of the active-set polish (qp_polish / qp_solve in lcqp_dev.hpp) as the last solve left it, accepted or given up.  Both streams
+ * are synchronised, nothing is launched, any pointer may be NULL (buffers NULL: the sizes).
+ * dims[12] = np, mEcap, the instance's mE, nT, ns, ndep, rnReady, nHot, haveSolution, rowsInLds, nV, capS; scal[7] = spv (sigma_p), then the six work sums of the instance
+ * (lcqp_hip_batch_work_sums; [4]: rows of E read by the residual sweeps).
+ * V [8][np]: V_XT (the polish's x), V_XS (x of the last residual sweep: the margins belong to it), V_XREF, V_R1S, V_GS, V_ATY, V_QXN, V_XQ.
+ * M [10][mEcap]: M_YT, M_EX, M_EXS, M_MG (screening margins), M_RN, M_HOTV, M_YLV, M_L, M_U, M_YQ.  I [5][mEcap]: I_STT, I_ST, I_DEP,
+ * I_SLOT, I_HOTC.  rowsInLds = 1: the homotopy kernel of this shape (np <= 256, mEcap <= 640, 4 capS <= 2048) keeps yt, ex, mg and st
+ * in LDS for the whole launch, and M_YT, M_EX, M_MG, I_STT are STALE after lcqp_hip_batch_run / _resolve (they hold what the last
+ * one-piece rebuild of a factor saved); every other array is current.  LCQP_INVALID_ARGUMENT / LCQP_LCQPOBJECT_NOT_SETUP as
+ * lcqp_hip_batch_read_admm. */
+int  lcqp_hip_batch_read_polish(lcqp_hip_batch_t* b, int instance, int dims[12], double scal[7], double* V, double* M, int* I);
 /* Constant-matrix setup: C = L'R + R'L (src/LCQProblem.cpp:622-623), phi expressions (:969-996) and the
  * two factorisations the subsolver reuses across every iterate (replaces qp.init's setup,
  * src/SubsolverQPOASES.cpp:152).  Asynchronous on the batch stream. */

@@ -131,6 +131,8 @@ def lib():
         L.lcqp_hip_qp_read_working_set.argtypes = [C.c_void_p, c_int_p, c_int_p, c_int_p, c_int_p, c_double_p]
         L.lcqp_hip_batch_read_admm.argtypes = [C.c_void_p, C.c_int, c_int_p, c_double_p] + [c_double_p] * 9
         L.lcqp_hip_qp_read_admm.argtypes = [C.c_void_p, c_int_p, c_double_p] + [c_double_p] * 9
+        L.lcqp_hip_batch_read_polish.argtypes = [C.c_void_p, C.c_int, c_int_p, c_double_p, c_double_p, c_double_p, c_int_p]
+        L.lcqp_hip_qp_read_polish.argtypes = [C.c_void_p, c_int_p, c_double_p, c_double_p, c_double_p, c_int_p]
         L.lcqp_hip_batch_sensitivity.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_batch_sensitivity_timing.argtypes = [C.c_void_p, C.POINTER(C.c_float)]
         L.lcqp_hip_qp_sensitivity.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
@@ -283,6 +285,33 @@ def _read_admm(call):
                 rhoAdmm=float(scal[1]), scale=float(scal[2]), FK=FK, rhov=rhov, l=l, u=u, xa=xa, ya=ya, za=za, dy=dy, dx=dx)
 
 
+POLISH_V = ("xt", "xs", "xref", "r1s", "gs", "aty", "qxn", "xq")
+POLISH_M = ("yt", "ex", "exs", "mg", "rn", "hotv", "ylv", "l", "u", "yq")
+POLISH_I = ("stt", "st", "dep", "row_slot", "hotc")
+POLISH_LDS_ROWS = ("yt", "ex", "mg", "stt")
+
+
+def _read_polish(call, homotopy):
+    """call(dims, scal, V, M, I) -> rc: the state of the active-set polish of one instance as it lies on the device
+    (lcqp_hip_batch_read_polish).  The vectors are cut to the n variables and the mE rows.  homotopy: the handle runs k_lcqp_run, whose
+    small shapes keep yt, ex, mg and stt in LDS -- those four come back as None there (rowsInLds), never as stale numbers."""
+    dims = np.zeros(12, dtype=np.int32); scal = np.zeros(7)
+    _check(call(_ip(dims), _p(scal), None, None, None), "read_polish")
+    np_, mEcap, mE = (int(v) for v in dims[:3])
+    n = int(dims[10])
+    V = np.zeros((len(POLISH_V), np_)); M = np.zeros((len(POLISH_M), mEcap)); I = np.zeros((len(POLISH_I), mEcap), dtype=np.int32)
+    _check(call(_ip(dims), _p(scal), _p(V), _p(M), _ip(I)), "read_polish")
+    out = dict(np=np_, mEcap=mEcap, mE=mE, nT=int(dims[3]), ns=int(dims[4]), ndep=int(dims[5]), rnReady=int(dims[6]), nHot=int(dims[7]),
+               haveSolution=int(dims[8]), rowsInLds=int(dims[9]), n=n, capS=int(dims[11]), spv=float(scal[0]), work=scal[1:].copy())
+    out.update({k: V[i, :n].copy() for i, k in enumerate(POLISH_V)})
+    out.update({k: M[i, :mE].copy() for i, k in enumerate(POLISH_M)})
+    out.update({k: I[i, :mE].copy() for i, k in enumerate(POLISH_I)})
+    if homotopy and out["rowsInLds"]:
+        for k in POLISH_LDS_ROWS:
+            out[k] = None
+    return out
+
+
 def _sensitivity(call, v, B, nV, nd, check=None):
     """call(nrhs, v, dg, db, side, info) -> rc; check(rc, what) raises with the error string of the caller's arm (default: the dense one).  v: [B][nV] or [B][k][nV]; returns (dg, db, side, info) with dg shaped like v, db
     [B][nd] or [B][k][nd], side [B][nd] (int32), info [B] (int32)."""
@@ -429,6 +458,11 @@ class SubsolverHIP:
     def read_admm(self):
         """the state of the ADMM fallback as the last solve that ran it left it (test and diagnostic entry point; see BatchLCQP.read_admm)"""
         return _read_admm(lambda *a: lib().lcqp_hip_qp_read_admm(self.h, *a))
+
+    def read_polish(self):
+        """the state of the active-set polish as the last solve left it, accepted or given up (test and diagnostic entry point; see
+        BatchLCQP.read_polish).  k_qp_solve works on the global row arrays: every vector is current."""
+        return _read_polish(lambda *a: lib().lcqp_hip_qp_read_polish(self.h, *a), homotopy=False)
 
     def read_working_set(self):
         """the inverse factor the last solve left (test and diagnostic entry point; see BatchLCQP.read_working_set)"""
@@ -985,6 +1019,14 @@ class BatchLCQP(_Batch):
         kReady, setupFail, sigma, rhoAdmm, scale; FK [np][np] (the symmetric-filled factor of Q + sigma I + E' diag(rhov) E, inverted
         diagonal blocks), rhov, l, u, ya, za, dy [mEcap] and xa, dx [np]."""
         return _read_admm(lambda *a: lib().lcqp_hip_batch_read_admm(self.h, b, *a))
+
+    def read_polish(self, b):
+        """Test and diagnostic entry point (launches nothing): the active-set polish of instance b as the last QP left it -- the dimensions
+        np, mEcap, mE, n, capS, nT, ns, ndep, rnReady, nHot, haveSolution, rowsInLds, spv (sigma_p), work (the six work sums); xt, xs, xref,
+        r1s, gs, aty, qxn, xq [n]; yt, ex, exs, mg, rn, hotv, ylv, l, u, yq [mE]; stt, st, dep, row_slot, hotc [mE].  Where the homotopy
+        kernel keeps the row state in LDS (rowsInLds: np <= 256, mEcap <= 640) yt, ex, mg and stt are None: they never reach their
+        global arrays when a launch ends."""
+        return _read_polish(lambda *a: lib().lcqp_hip_batch_read_polish(self.h, b, *a), homotopy=True)
 
     def setup(self):
         _check(lib().lcqp_hip_batch_setup(self.h), "setup")

@@ -206,6 +206,13 @@ extern "C" int lcqp_hip_qp_read_admm(lcqp_hip_qp_t* q, int dims[6], double scal[
     return lcqp_hip_batch_read_admm(q->hb.get(), 0, dims, scal, FK, rhov, l, u, xa, ya, za, dy, dx);
 }
 
+extern "C" int lcqp_hip_qp_read_polish(lcqp_hip_qp_t* q, int dims[12], double scal[7], double* V, double* M, int* I)
+{
+    if (!q) return LCQP_INVALID_ARGUMENT;
+    if (!q->hb) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return lcqp_hip_batch_read_polish(q->hb.get(), 0, dims, scal, V, M, I);
+}
+
 // the derivatives of the convex QP last solved: k_sensitivity on the batch of one (dg [nrhs][nV], db / side [.][nV + nC], info [1])
 extern "C" int lcqp_hip_qp_sensitivity(lcqp_hip_qp_t* q, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
 { return guarded(dense_err(), [&] {

@@ -343,3 +343,40 @@ extern "C" int lcqp_hip_batch_read_admm(lcqp_hip_batch_t* h, int b, int dims[6],
     if (!rc) rc = read_back(dense_err(), dx, nv + (size_t)V_W * np, np);
     return rc;
 }); }
+
+// =================================================================================================
+// read-back of the active-set polish (tests, diagnostics): the vectors qp_polish / qp_solve leave in the pools of one instance, nothing is launched
+// =================================================================================================
+// V [8][np]: V_XT, V_XS, V_XREF, V_R1S, V_GS, V_ATY, V_QXN, V_XQ;  M [10][mEcap]: M_YT, M_EX, M_EXS, M_MG, M_RN, M_HOTV, M_YLV, M_L, M_U, M_YQ;
+// I [5][mEcap]: I_STT, I_ST, I_DEP, I_SLOT, I_HOTC -- in this order, as they lie on the device.  dims[9] (rowsInLds) is 1 when the
+// homotopy kernel of this handle keeps the row state in LDS (launch_run in lcqp_kernels.hpp: np <= 256, mEcap <= LDS_ROWS_MAX,
+// 4 capS <= LDS_ROWS_OFF): qp_polish then copies yt, ex, mg, st to their global arrays only around a one-piece rebuild of the factor, so
+// M_YT, M_EX, M_MG and I_STT are STALE after lcqp_hip_batch_run / _resolve on such a handle (whatever the last rebuild left).  k_qp_solve
+// (the QP object) always works on the global arrays.
+extern "C" int lcqp_hip_batch_read_polish(lcqp_hip_batch_t* h, int b, int dims[12], double scal[7], double* V, double* M, int* I)
+{ return guarded(dense_err(), [&] {
+    if (!h || b < 0 || b >= h->db.B) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.setupValid) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (int rc = synchronize(dense_err(), h)) return rc;
+    HIPCHK(dense_err(), hipStreamSynchronize(h->side));
+    const DevBatch& d = h->db;
+    const size_t ib = b, np = d.np, mE = d.mEcap;
+    InstInfo info;
+    HIPCHK(dense_err(), hipMemcpy(&info, d.info + ib, sizeof(InstInfo), hipMemcpyDeviceToHost));
+    if (dims) {
+        const int lr = d.np <= 256 && d.mEcap <= LDS_ROWS_MAX && 4 * d.capS <= LDS_ROWS_OFF;
+        const int v[12] = {d.np, d.mEcap, info.mE, info.nT, info.ns, info.ndep, info.rnReady, info.nHot, info.haveSolution, lr, d.n, d.capS};
+        memcpy(dims, v, sizeof v);
+    }
+    if (scal) { scal[0] = info.spv; for (int k = 0; k < 6; k++) scal[1 + k] = info.work[k]; }      // work: the exact work sums of InstInfo
+    const double *nv = d.nv + ib * V_NUM * np, *mv = d.mv + ib * M_NUM * mE;
+    const int* mi = d.mi + ib * I_NUM * mE;
+    static const int vk[8] = {V_XT, V_XS, V_XREF, V_R1S, V_GS, V_ATY, V_QXN, V_XQ};
+    static const int mk[10] = {M_YT, M_EX, M_EXS, M_MG, M_RN, M_HOTV, M_YLV, M_L, M_U, M_YQ};
+    static const int ik[5] = {I_STT, I_ST, I_DEP, I_SLOT, I_HOTC};
+    int rc = 0;
+    for (int k = 0; k < 8 && !rc && V; k++) rc = read_back(dense_err(), V + k * np, nv + (size_t)vk[k] * np, np);
+    for (int k = 0; k < 10 && !rc && M; k++) rc = read_back(dense_err(), M + k * mE, mv + (size_t)mk[k] * mE, mE);
+    for (int k = 0; k < 5 && !rc && I; k++) rc = read_back(dense_err(), I + k * mE, mi + (size_t)ik[k] * mE, mE);
+    return rc;
+}); }

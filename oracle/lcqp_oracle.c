@@ -241,6 +241,9 @@ struct orc_qp {
     int c_admm, c_trials, c_fact, c_corr, c_sweeps;
     int c_pred, c_trsv;            /* predicted corrections; triangular solves with L1 */
     double rows_swept, rows_corr;  /* rows of E read by the residual sweeps; rows of Et read by the corrections */
+    /* the polish's own (x, y, working set) as the last solve left them, solved or given up (orc_qp_read_polish) */
+    double *pol_x, *pol_y;
+    int *pol_st, pol_valid;
 };
 
 orc_qp_t* orc_qp_create(int nV, int nC, const double* Q, const double* A, const orc_options_t* opt)
@@ -266,6 +269,7 @@ static void qp_free_setup(orc_qp_t* q)
     free(q->Ti); free(q->slot_row); free(q->row_slot); free(q->crow);
     q->Ti = NULL; q->slot_row = q->row_slot = q->crow = NULL;
     free(q->dy_last); free(q->dx_last); q->dy_last = q->dx_last = NULL;
+    free(q->pol_x); free(q->pol_y); free(q->pol_st); q->pol_x = q->pol_y = NULL; q->pol_st = NULL; q->pol_valid = 0;
     free(q->newst); free(q->dep); free(q->prio); q->dep = q->prio = NULL; free(q->r1_last); free(q->ex_last); free(q->g_last);
     q->r1_last = q->ex_last = q->g_last = NULL;
     q->boxidx = NULL; q->E = q->Et = q->l = q->u = q->rhov = q->L1 = q->LK = q->x = q->y = NULL;
@@ -1167,6 +1171,9 @@ int orc_qp_solve(orc_qp_t* q, int initialSolve, int* iterations, int* exit_flag,
         if (n_admm > 400) n_admm = 400;
     }
     *iterations = (q->c_trials - trials0) + (q->c_admm - admm0);
+    if (!q->pol_x) { q->pol_x = dalloc(n ? n : 1); q->pol_y = dalloc(mE ? mE : 1); q->pol_st = (int*)malloc(sizeof(int) * (mE ? mE : 1)); }
+    memcpy(q->pol_x, xt, sizeof(double) * n); memcpy(q->pol_y, yt, sizeof(double) * mE); memcpy(q->pol_st, stt, sizeof(int) * mE);
+    q->pol_valid = 1;
     if (!solved) { free(xt); free(yt); free(stt); *exit_flag = certificate ? certificate : 1; return ORC_SUBPROBLEM_SOLVER_ERROR; }
     memcpy(q->x, xt, sizeof(double) * n);
     memcpy(q->y, yt, sizeof(double) * mE);
@@ -1179,6 +1186,21 @@ int orc_qp_solve(orc_qp_t* q, int initialSolve, int* iterations, int* exit_flag,
     for (int r = 0; r < nC; r++) q->ysol[n + r] = -q->y[r];
     for (int k = 0; k < q->nfin; k++) q->ysol[q->boxidx[k]] = -q->y[nC + k];
     return ORC_SUCCESSFUL_RETURN;
+}
+
+/* the polish's x [nV], y [mE] (OSQP sign), working set [mE] (0 inactive, else lower / upper / equality as ST_*) and the anchor xref [nV] of the
+ * last solve, also when it gave up; the bounds l, u [mE] of the stacked rows.  Returns mE, or -1 before the first solve.  Any pointer may be NULL. */
+int orc_qp_read_polish(orc_qp_t* q, double* x, double* y, int* st, double* xref, double* l, double* u, double* spv)
+{
+    if (!q || !q->is_setup || !q->pol_valid) return -1;
+    if (x) memcpy(x, q->pol_x, sizeof(double) * q->nV);
+    if (y) memcpy(y, q->pol_y, sizeof(double) * q->mE);
+    if (st) memcpy(st, q->pol_st, sizeof(int) * q->mE);
+    if (xref) memcpy(xref, q->xref, sizeof(double) * q->nV);
+    if (l) memcpy(l, q->l, sizeof(double) * q->mE);
+    if (u) memcpy(u, q->u, sizeof(double) * q->mE);
+    if (spv) *spv = q->spv;      /* sigma_p, the weight of the proximal term */
+    return q->mE;
 }
 
 void orc_qp_get_solution(orc_qp_t* q, double* x, double* y)

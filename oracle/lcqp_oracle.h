@@ -110,6 +110,7 @@ int       orc_qp_solve(orc_qp_t* q, int initialSolve, int* iterations, int* exit
                        const double* lb, const double* ub);                                          /* :134-169 */
 void      orc_qp_get_solution(orc_qp_t* q, double* x, double* y);                                    /* :172-181 */
 void      orc_qp_get_counters(orc_qp_t* q, int* admm, int* trials, int* facts, int* corrections);
+int       orc_qp_read_polish(orc_qp_t* q, double* x, double* y, int* st, double* xref, double* l, double* u, double* spv);   /* the polish's state after the last solve, given up or not; returns mE */
 int       orc_qp_get_sweeps(orc_qp_t* q);   /* trials that swept Q and E (stats.reserved) */
 
 /* ---- LCQP solve (LCQProblem::loadLCQP dense + runSolver) ----

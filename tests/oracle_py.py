@@ -89,6 +89,7 @@ def lib():
         L.orc_qp_solve.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)] + [c_double_p] * 7
         L.orc_qp_get_solution.argtypes = [C.c_void_p, c_double_p, c_double_p]
         L.orc_qp_get_counters.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
+        L.orc_qp_read_polish.argtypes = [C.c_void_p, c_double_p, c_double_p, C.POINTER(C.c_int), c_double_p, c_double_p, c_double_p, c_double_p]
         L.orc_lcqp_solve.argtypes = ([C.c_int] * 3 + [c_double_p] * 15 + [C.POINTER(Options), c_double_p, c_double_p,
                                      C.POINTER(Stats), C.c_int, c_double_p, c_double_p, C.POINTER(C.c_int)])
         L.orc_synth_generate.argtypes = [C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_int] + [c_double_p] * 7
@@ -198,6 +199,17 @@ class QP:
         x = np.zeros(self.nV); y = np.zeros(self.nV + self.nC)
         lib().orc_qp_get_solution(self.h, _p(x), _p(y))
         return x, y
+
+    def read_polish(self):
+        """the polish's x, y (OSQP sign, per stacked row), working set and anchor xref as the last solve left them -- also one that gave up --
+        and the bounds l, u of the stacked rows (orc_qp_read_polish)"""
+        mE = lib().orc_qp_read_polish(self.h, None, None, None, None, None, None, None)
+        if mE < 0:
+            raise RuntimeError("orc_qp_read_polish: no solve yet")
+        x = np.zeros(self.nV); xref = np.zeros(self.nV); y = np.zeros(max(mE, 1)); l = np.zeros(max(mE, 1)); u = np.zeros(max(mE, 1))
+        st = np.zeros(max(mE, 1), dtype=np.int32); spv = np.zeros(1)
+        lib().orc_qp_read_polish(self.h, _p(x), _p(y), st.ctypes.data_as(C.POINTER(C.c_int)), _p(xref), _p(l), _p(u), _p(spv))
+        return dict(mE=mE, spv=float(spv[0]), xt=x, yt=y[:mE], stt=st[:mE], xref=xref, l=l[:mE], u=u[:mE])
 
     def counters(self):
         v = [C.c_int(0) for _ in range(4)]

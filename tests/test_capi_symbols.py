@@ -68,6 +68,8 @@ def test_c_abi_rejects_bad_arguments_without_a_gpu():
     assert L.lcqp_hip_batch_read_setup(None, 0, dims, *[None] * 9) != 0 and L.lcqp_hip_batch_read_working_set(None, 0, dims, *[None] * 4) != 0
     assert L.lcqp_hip_qp_read_setup(None, dims, *[None] * 9) != 0 and L.lcqp_hip_qp_read_working_set(None, dims, *[None] * 4) != 0
     assert L.lcqp_hip_batch_read_admm(None, 0, dims, *[None] * 10) != 0 and L.lcqp_hip_qp_read_admm(None, dims, *[None] * 10) != 0
+    assert L.lcqp_hip_batch_read_polish(None, 0, None, *[None] * 4) == 100 and L.lcqp_hip_qp_read_polish(None, None, *[None] * 4) == 100
+    assert callable(capi.BatchLCQP.read_polish) and callable(capi.SubsolverHIP.read_polish)
     n = ctypes.c_int(0)
     if la.device_count() == 0:
         # no GPU here: creating a batch must fail with the HIP error, never fall back to anything
@@ -83,6 +85,7 @@ def test_c_abi_rejects_bad_arguments_without_a_gpu():
         assert L.lcqp_hip_qp_read_setup(ctypes.c_void_p(q), dims, *[None] * 9) != 0
         assert L.lcqp_hip_qp_read_working_set(ctypes.c_void_p(q), dims, *[None] * 4) != 0
         assert L.lcqp_hip_qp_read_admm(ctypes.c_void_p(q), dims, *[None] * 10) != 0
+        assert L.lcqp_hip_qp_read_polish(ctypes.c_void_p(q), ctypes.cast(dims, ctypes.POINTER(ctypes.c_int)), *[None] * 4) == 300
         assert dims[0] == -7
         L.lcqp_hip_qp_destroy(ctypes.c_void_p(q))
 
