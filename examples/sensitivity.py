@@ -8,6 +8,7 @@ printed.  The targets are solutions of the same LCQPs for other linear terms, so
     python examples/sensitivity.py jacobian    # the full Jacobians dx/dg of the 64 LCQPs (lcqp_hip_batch_jacobian): |Jg - Jg'| and the kernel time
     python examples/sensitivity.py duals       # the four blocks of D(x, y) / D(g, bounds) of one LCQP (lcqp_hip_batch_jacobian and _jacobian_duals)
     python examples/sensitivity.py sparse jacobian   # the full Jacobians of the 16 banded LCQPs (lcqp_hip_sparse_jacobian), panel kernel
+    python examples/sensitivity.py sparse duals      # the four blocks of D(x, y) / D(g, bounds) of the 16 banded LCQPs (lcqp_hip_sparse_jacobian and _jacobian_duals)
     python examples/sensitivity.py adjoint     # learn ONE constraint matrix A shared by the 64 LCQPs from a loss on x and y (lcqp_hip_batch_adjoint)
     python examples/sensitivity.py sparse adjoint   # learn ONE value array of [A; L; R] shared by 16 banded LCQPs (lcqp_hip_sparse_adjoint)
 """
@@ -46,7 +47,7 @@ def fit(layer, g0, rng, batch):
         print("step %2d  mean loss per LCQP %.6e  flagged instances %d" % (step, loss.item() / batch, int(np.count_nonzero(layer.info))))
 
 
-def sparse_main(jacobian=False):
+def sparse_main(jacobian=False, duals=False):
     from lcqpow_amd import synth_sparse as S
     Bs, ns, nCs, nKs = 16, 64, 32, 8
     Qpat, Apat, qo, eo = S.sparse_pattern_arrays(ns, nCs, nKs)
@@ -55,7 +56,16 @@ def sparse_main(jacobian=False):
     sb = la.SparseBatchLCQP(Bs, ns, nCs, nKs, Qpat, Apat, opt=la.default_options(perturbStep=0))
     assert sb.load(0, Bs, st("Qx"), st("g"), st("Ex"), lbA=st("lbA"), ubA=st("ubA")) == 0
     layer = SparseBatchLCQPLayer(sb, bounds=dict(lbA=st("lbA"), ubA=st("ubA")))
-    if jacobian:
+    if duals:
+        with torch.no_grad():
+            layer(torch.as_tensor(st("g")))
+        J = layer.jacobian_full()      # the whole solution map D(x, y) / D(g, b_W): SparseBatchLCQP.jacobian and .jacobian_duals
+        nW = np.count_nonzero(J["side"].numpy(), axis=1)
+        print("xg %s xb %s yg %s yb %s; rows of W per instance %d to %d; max |xb - yg'| = %.3e, max |yb - yb'| = %.3e, kernel of the dual rows %.4f ms, "
+              "flagged instances %d" % (tuple(J["xg"].shape), tuple(J["xb"].shape), tuple(J["yg"].shape), tuple(J["yb"].shape), nW.min(), nW.max(),
+                                        (J["xb"] - J["yg"].transpose(1, 2)).abs().max().item(), (J["yb"] - J["yb"].transpose(1, 2)).abs().max().item(),
+                                        sb.sensitivity_kernel_ms(), int(np.count_nonzero(layer.info))))
+    elif jacobian:
         with torch.no_grad():
             layer(torch.as_tensor(st("g")))
         Jg = layer.jacobian()
@@ -129,6 +139,8 @@ def main():
         return sparse_main()
     if sys.argv[1:] == ["sparse", "jacobian"]:
         return sparse_main(jacobian=True)
+    if sys.argv[1:] == ["sparse", "duals"]:
+        return sparse_main(duals=True)
     if sys.argv[1:] == ["sparse", "adjoint"]:
         return sparse_adjoint_main()
     if sys.argv[1:] == ["adjoint"]:

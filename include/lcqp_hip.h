@@ -499,7 +499,7 @@ int  lcqp_hip_sparse_launch_counts(lcqp_hip_sparse_t* s, int out[2]);   /* full 
  * LCQP_INVALID_ARGUMENT: NULL handle, v or dg, or nrhs < 1.  LCQP_LCQPOBJECT_NOT_SETUP: no run / resolve on this handle yet, or a load /
  * set_options since the last one (the mark of lcqp_hip_sparse_resolve).  LCQP_HIP_ERROR: a HIP call failed. */
 int  lcqp_hip_sparse_sensitivity(lcqp_hip_sparse_t* s, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
-/* kernel time of the last lcqp_hip_sparse_sensitivity / _sensitivity_blocked / _jacobian call of this handle, ms (HIP events around
+/* kernel time of the last lcqp_hip_sparse_sensitivity / _sensitivity_blocked / _jacobian / _adjoint_blocked / _jacobian_duals call of this handle, ms (HIP events around
  * k_sparse_sensitivity or k_sparse_sensitivity_blk, the copies excluded; a call that went in chunks: the sum over its launches) */
 int  lcqp_hip_sparse_sensitivity_timing(lcqp_hip_sparse_t* s, float* kernel_ms);
 /* lcqp_hip_sparse_sensitivity for many vectors (DESIGN.md section 3a''', "The sparse arm"): the same arguments, layouts, flags and return
@@ -568,6 +568,36 @@ int  lcqp_hip_sparse_jacobian(lcqp_hip_sparse_t* s, int first, int count, double
  * are decided before any device call. */
 int  lcqp_hip_sparse_adjoint(lcqp_hip_sparse_t* s, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
                              int reduce, double* dQx, double* dAx);
+/* lcqp_hip_sparse_adjoint without matrices for many pairs per instance, and the dual rows of the solution Jacobian (DESIGN.md section 3a'''',
+ * "The sparse arm: panels with gradients on y"; the twins of lcqp_hip_batch_adjoint_blocked / _jacobian_duals in this arm's conventions: no box
+ * rows, m = nC + 2 nComp rows [A; L; R], y as lcqp_hip_sparse_get_solution returns it).
+ * adjoint_blocked: vx [B][nrhs][nV] or NULL (zero), vy [B][nrhs][m] or NULL (zero), not both NULL; per pair
+ *     Q d + E_W' mu = vx,  E_W d = -vy_W;     dg = -d [B][nrhs][nV],   db_W = mu [B][nrhs][m] (exactly 0.0 outside W);
+ * side, info and the layouts are those of lcqp_hip_sparse_sensitivity_blocked.  Entries of vy outside W are dropped: whatever they hold (a NaN
+ * included), the bits are the same.  The pairs go through k_sparse_sensitivity_blk_dual (the general LDL' with its panel form on:
+ * k_sparse_sensitivity_blk_general_dual) in panels of lcqp_hip_sparse_sens_panel(s) columns, as work items in chunks under the staging cap; the
+ * refinement carries the second block, residual [vx - Q d - E_W' mu; -vy_W - E_W d].  A pair's result depends on nothing but that pair -- not
+ * on its place in the call, its neighbours or the chunking --, bit for bit, and equals lcqp_hip_sparse_adjoint's to rounding.  vy == NULL: the
+ * call is lcqp_hip_sparse_sensitivity_blocked, to the bit; vx == NULL: the bits of an explicit zero vx.
+ * jacobian_duals, for the instances [first, first + count):
+ *   Jyg[i][r][j]  [count][m][nV]   d y*_r / d g_j of instance first + i
+ *   Jyb[i][r][s]  [count][m][m]    d y*_r / d (the bound row s sits on); may be NULL
+ *   side [count][m], info [count]  as lcqp_hip_sparse_sensitivity; may be NULL
+ * Rows (and columns of Jyb) outside W are exactly 0.0.  Row r of W is what adjoint_blocked returns for vx = 0, vy = e_r (band engines: to the
+ * bit).  The unit columns of W are written by the kernel, nothing is uploaded; the call is sized for m columns per instance, goes in chunks of
+ * (instance, panel) work items under the cap of lcqp_hip_sparse_set_adjoint_staging, and an instance's rows do not depend on the chunking.
+ * With lcqp_hip_sparse_jacobian the two give the whole map D(x*, y*) / D(g, b_W).
+ * On a handle whose lcqp_hip_sparse_sens_panel is 0 (the general LDL' without lcqp_hip_sparse_set_general_panel) both run the vector kernel
+ * k_sparse_sensitivity with vy and return its bits -- adjoint_blocked on the nrhs pairs, jacobian_duals on uploaded unit vy in chunks of
+ * columns under the same cap (a sub-range then costs the launches of the whole batch).
+ * Both are synchronous on return, change nothing a run / resolve reads and leave lcqp_hip_sparse_launch_counts alone;
+ * lcqp_hip_sparse_sensitivity_timing reports the sum of their launches.
+ * LCQP_INVALID_ARGUMENT: NULL handle; adjoint_blocked: nrhs < 1, vx and vy both NULL, NULL dg; jacobian_duals: NULL Jyg, first < 0, count < 1,
+ * first + count > B.  Then LCQP_LCQPOBJECT_NOT_SETUP as lcqp_hip_sparse_sensitivity.  Both are decided before any device call. */
+int  lcqp_hip_sparse_adjoint_blocked(lcqp_hip_sparse_t* s, int nrhs, const double* vx, const double* vy,
+                                     double* dg, double* db, int* side, int* info);
+int  lcqp_hip_sparse_jacobian_duals(lcqp_hip_sparse_t* s, int first, int count,
+                                    double* Jyg, double* Jyb, int* side, int* info);
 /* another staging cap for this handle's adjoint, blocked-sensitivity and Jacobian calls and for the two chunks of staging of a host load /
  * update (0: the default, LCQP_JACOBIAN_STAGING_BYTES); for tests of the chunking and for small devices */
 int  lcqp_hip_sparse_set_adjoint_staging(lcqp_hip_sparse_t* s, size_t bytes);

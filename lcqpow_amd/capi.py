@@ -192,6 +192,8 @@ def lib():
         L.lcqp_hip_sparse_sensitivity_blocked.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_sparse_jacobian.argtypes = [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_sparse_adjoint.argtypes = [C.c_void_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p, C.c_int] + [c_double_p] * 2
+        L.lcqp_hip_sparse_adjoint_blocked.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
+        L.lcqp_hip_sparse_jacobian_duals.argtypes = [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_int_p]
         L.lcqp_hip_sparse_set_adjoint_staging.argtypes = [C.c_void_p, C.c_size_t]
         L.lcqp_hip_sparse_load_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 11 + [C.c_void_p]
         L.lcqp_hip_sparse_update_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 9 + [C.c_void_p]
@@ -702,6 +704,39 @@ class _Batch:
         with self._staging(_staging_bytes):
             return _jacobian(lambda *a: self._sym("jacobian")(self.h, *a), self.B, self.nV, self._ndual, first, count, bounds, check=self._check)
 
+    def _pairs(self, VX, VY, conv):
+        """the shapes of a blocked adjoint call: VX [B][k][nV] or None, VY [B][k][nd] or None, not both None; returns (VX, VY, k)"""
+        VX, VY = conv(VX), conv(VY)
+        if VX is None and VY is None:
+            raise ValueError("adjoint_blocked: VX and VY are both None")
+        k = (VX if VX is not None else VY).shape[1] if (VX if VX is not None else VY).ndim == 3 else 0
+        for name, a, width in (("VX", VX, self.nV), ("VY", VY, self.nd)):
+            if a is not None and (a.ndim != 3 or k < 1 or tuple(a.shape) != (self.B, k, width)):
+                raise ValueError(f"{name}: expected [{self.B}][k][{width}] with k >= 1, got shape {tuple(a.shape)}")
+        return VX, VY, k
+
+    def adjoint_blocked(self, VX, VY=None):
+        """*_adjoint_blocked: adjoint() without matrices for k pairs per instance, in panels on the arm's blocked kernel (DESIGN.md section
+        3a''''; dense: panels of SENS_PANEL on the matrix cores, sparse: panels of sens_panel() columns per lane group).  VX [B][k][nV] = dl/dx
+        or None, VY [B][k][nd] = dl/dy in the layout of solution()'s y or None (not both; entries of VY outside the working set are dropped).
+        Returns (dg [B][k][nV], db [B][k][nd], side [B][nd], info [B]).  With VY None the call is the arm's blocked sensitivity call, to the
+        bit; with VX None the first block is a zero panel (dense: the forward substitution is not run)."""
+        VX, VY, k = self._pairs(VX, VY, _arr)
+        B, n, nd = self.B, self.nV, self.nd
+        dg = np.zeros((B, k, n)); db = np.zeros((B, k, nd)); side = np.zeros((B, nd), dtype=np.int32); info = np.zeros(B, dtype=np.int32)
+        self._call("adjoint_blocked", k, _p(VX), _p(VY), _p(dg), _p(db), _ip(side), _ip(info))
+        return dg, db, side, info
+
+    def jacobian_duals(self, first=0, count=None, bounds=True, _staging_bytes=None):
+        """*_jacobian_duals: the dual rows of the solution Jacobian of the instances [first, first + count) (count None: to the
+        end).  Returns (Jyg, Jyb, side, info): Jyg [count][nd][nV], Jyg[i][r][j] = dy_r/dg_j; Jyb [count][nd][nd], Jyb[i][r][s] =
+        dy_r/d(the bound row s sits on) (None with bounds=False); rows and columns outside the working set are zero.  The unit vectors of
+        the working set are generated on the device; the call goes in chunks under the staging cap of jacobian (dense: chunks of instances; sparse: chunks of
+        (instance, panel) work items; _staging_bytes: another cap for this one call, for tests)."""
+        with self._staging(_staging_bytes):
+            return _jacobian(lambda *a: self._sym("jacobian_duals")(self.h, *a), self.B, self.nV, self.nd, first, count, bounds, check=self._check,
+                             rows=self.nd)
+
     def _adjoint_host(self, vx, vy, matrices, reduce, _staging_bytes):
         """the body of adjoint (a subclass's own: the default of `matrices` differs)"""
         with self._staging(_staging_bytes):
@@ -882,37 +917,6 @@ class BatchLCQP(_Batch):
         info & 1 contributes zeros.  Without reduce the matrices come in chunks of instances under the staging cap of jacobian
         (_staging_bytes: another cap for this one call, for tests).  The call changes nothing on the device."""
         return self._adjoint_host(vx, vy, matrices, reduce, _staging_bytes)
-
-    def _pairs(self, VX, VY, conv):
-        """the shapes of a blocked adjoint call: VX [B][k][nV] or None, VY [B][k][nd] or None, not both None; returns (VX, VY, k)"""
-        VX, VY = conv(VX), conv(VY)
-        if VX is None and VY is None:
-            raise ValueError("adjoint_blocked: VX and VY are both None")
-        k = (VX if VX is not None else VY).shape[1] if (VX if VX is not None else VY).ndim == 3 else 0
-        for name, a, width in (("VX", VX, self.nV), ("VY", VY, self.nd)):
-            if a is not None and (a.ndim != 3 or k < 1 or tuple(a.shape) != (self.B, k, width)):
-                raise ValueError(f"{name}: expected [{self.B}][k][{width}] with k >= 1, got shape {tuple(a.shape)}")
-        return VX, VY, k
-
-    def adjoint_blocked(self, VX, VY=None):
-        """lcqp_hip_batch_adjoint_blocked: adjoint() without matrices for k pairs per instance, in panels of SENS_PANEL on the matrix cores
-        (DESIGN.md section 3a'''').  VX [B][k][nV] = dl/dx or None, VY [B][k][nd] = dl/dy or None (not both; entries of VY outside the working
-        set are not read).  Returns (dg [B][k][nV], db [B][k][nd], side [B][nd], info [B]).  With VY None the call is
-        sensitivity(VX, blocked=True), to the bit; with VX None the forward substitution is not run."""
-        VX, VY, k = self._pairs(VX, VY, _arr)
-        B, n, nd = self.B, self.nV, self.nd
-        dg = np.zeros((B, k, n)); db = np.zeros((B, k, nd)); side = np.zeros((B, nd), dtype=np.int32); info = np.zeros(B, dtype=np.int32)
-        self._call("adjoint_blocked", k, _p(VX), _p(VY), _p(dg), _p(db), _ip(side), _ip(info))
-        return dg, db, side, info
-
-    def jacobian_duals(self, first=0, count=None, bounds=True, _staging_bytes=None):
-        """lcqp_hip_batch_jacobian_duals: the dual rows of the solution Jacobian of the instances [first, first + count) (count None: to the
-        end).  Returns (Jyg, Jyb, side, info): Jyg [count][nd][nV], Jyg[i][r][j] = dy_r/dg_j; Jyb [count][nd][nd], Jyb[i][r][s] =
-        dy_r/d(the bound row s sits on) (None with bounds=False); rows and columns outside the working set are zero.  The unit vectors of
-        the working set are generated on the device; the call goes in chunks of instances under the staging cap of jacobian."""
-        with self._staging(_staging_bytes):
-            return _jacobian(lambda *a: self._sym("jacobian_duals")(self.h, *a), self.B, self.nV, self.nd, first, count, bounds, check=self._check,
-                             rows=self.nd)
 
     # ---- the device-pointer entry points (DESIGN.md section 3a'''''): torch tensors on the handle's device in, torch tensors out; the work is
     # ordered behind torch.cuda.current_stream(), and what the caller enqueues there next sees the results.  No copy through the host.
@@ -1135,7 +1139,7 @@ class SparseBatchLCQP(_Batch):
 
     def __init__(self, batch, nV, nC, nComp, Qpat, Apat, device=0, opt=None):
         self.B, self.nV, self.nC, self.nComp = batch, nV, nC, nComp
-        self.m = self._ndual = nC + 2 * nComp
+        self.m = self.nd = self._ndual = nC + 2 * nComp
         self.device = device
         self._pat = [np.ascontiguousarray(a, dtype=np.int32) for a in (Qpat.indptr, Qpat.indices, Apat.indptr, Apat.indices)]
         if self._pat[0].size != nV + 1 or self._pat[2].size != nV + 1:

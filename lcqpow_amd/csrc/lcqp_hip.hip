@@ -814,36 +814,12 @@ static int jacobian_duals_by_vectors(lcqp_hip_batch* h, int first, int count, do
 {
     DevBatch& d = h->db;
     const size_t B = d.B, n = d.n, nd = d.nd;
-    float ms = 0.f;
-    std::vector<double> zero(B * n, 0.0), G(B * n);
-    std::vector<int> sd(B * nd), in(B);
-    if (int rc = dense_sensitivity(h, false, 0, d.B, 1, zero.data(), nullptr, false, G.data(), nullptr, sd.data(), in.data(), ms)) return rc;
-    std::vector<size_t> rows;
-    for (size_t r = 0; r < nd; r++) {
-        bool any = false;
-        for (size_t i = 0; i < (size_t)count; i++) any = any || sd[(first + i) * nd + r] != 0;
-        if (any) rows.push_back(r);
-    }
-    const size_t cc = staging_chunk(h->sn.staging, sizeof(double) * B * (n + (size_t)d.np + 2 * nd + (size_t)d.capS), rows.size());
-    std::vector<double> VY(B * cc * nd), Bd(B * cc * nd);
-    G.resize(B * cc * n);
-    for (size_t c0 = 0; c0 < rows.size(); c0 += cc) {
-        const size_t nc = std::min(cc, rows.size() - c0);
-        std::fill(VY.begin(), VY.end(), 0.0);
-        for (size_t b = 0; b < B; b++) for (size_t k = 0; k < nc; k++) VY[(b * nc + k) * nd + rows[c0 + k]] = 1.0;
-        if (int rc = dense_adjoint_blocked(h, (int)nc, nullptr, VY.data(), false, G.data(), Bd.data(), nullptr, nullptr, ms)) return rc;
-        for (size_t i = 0; i < (size_t)count; i++)
-            for (size_t k = 0; k < nc; k++) {
-                const size_t r = rows[c0 + k], src = (first + i) * nc + k;
-                if (sd[(first + i) * nd + r] == 0) continue;      // not in this instance's W: the row stays zero
-                std::memcpy(Jyg + (i * nd + r) * n, G.data() + src * n, sizeof(double) * n);
-                if (Jyb) std::memcpy(Jyb + (i * nd + r) * nd, Bd.data() + src * nd, sizeof(double) * nd);
-            }
-    }
-    if (side) std::memcpy(side, sd.data() + (size_t)first * nd, sizeof(int) * (size_t)count * nd);
-    if (info) std::memcpy(info, in.data() + first, sizeof(int) * (size_t)count);
-    h->rs.sensMs = ms;
-    return 0;
+    std::vector<double> zero(B * n, 0.0);
+    return lcqp_rt::jacobian_duals_by_vectors(h, sizeof(double) * B * (n + (size_t)d.np + 2 * nd + (size_t)d.capS), nd, first, count, Jyg, Jyb, side, info,
+                                              [&](int nc, const double* VY, double* G, double* Bd, int* sd, int* in, float& ms) {
+        if (!VY) return dense_sensitivity(h, false, 0, d.B, 1, zero.data(), nullptr, false, G, nullptr, sd, in, ms);
+        return dense_adjoint_blocked(h, nc, nullptr, VY, false, G, Bd, sd, in, ms);
+    });
 }
 
 // Jyg [count][nd][n], Jyb [count][nd][nd] (or NULL), side [count][nd], info [count] of the instances [first, first + count)

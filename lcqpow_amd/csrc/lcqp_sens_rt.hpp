@@ -1,6 +1,6 @@
 // lcqp_sens_rt.hpp -- the host code behind the sensitivity, Jacobian and adjoint entry points of both arms (lcqp_hip.hip, lcqp_sparse_host.hip):
 // the state a handle keeps for them (member sn) and the one copy of what drives their kernels -- the staging cap (grow and staging_chunk
-// are lcqp_host_rt.hpp's: the host load / update use them too), the timed launch, the call around a sensitivity kernel, the Jacobian through a vector kernel, the chunks of a host adjoint.  Templates on the handle H
+// are lcqp_host_rt.hpp's: the host load / update use them too), the timed launch, the call around a sensitivity kernel, the Jacobians through a vector kernel, the chunks of a host adjoint.  Templates on the handle H
 // (lcqp_hip_batch / lcqp_hip_sparse: device, stream, mem, db, rs, sn) like those of lcqp_host_rt.hpp; what differs between the arms -- the
 // kernels, their pitches, the width of the dual vector -- comes in as arguments and callables.  Host code only.
 #pragma once
@@ -104,6 +104,50 @@ int jacobian_by_vectors(H* h, size_t vecBytes, size_t nd, int first, int count, 
             std::memcpy(Jg + (i * n + c0) * n, G.data() + (first + i) * nc * n, sizeof(double) * nc * n);
             if (Jb) std::memcpy(Jb + (i * n + c0) * nd, Bd.data() + (first + i) * nc * nd, sizeof(double) * nc * nd);
         }
+    }
+    if (side) std::memcpy(side, sd.data() + (size_t)first * nd, sizeof(int) * (size_t)count * nd);
+    if (info) std::memcpy(info, in.data() + first, sizeof(int) * (size_t)count);
+    h->rs.sensMs = ms;
+    return 0;
+}
+
+// The dual rows of the Jacobians of the instances [first, first + count) where the arm has only its vector kernel: vx = 0 and vy = the unit
+// vectors of the dual positions that are in W for some instance of the range, uploaded in chunks of columns whose staging -- vecBytes per
+// column, over the whole batch -- stays under the cap, on the whole batch (the vector kernel has no instance offset).
+// run(nc, VY, G, Bd, sd, in, ms) takes nc pairs (0, VY [B][nc][nd]) through the batch (host arrays; sd, in may be NULL; ms: as
+// sensitivity_call); its first call, with VY = NULL and nc = 1, is the plain sensitivity of a zero vector, for side and info.
+// Jyg [count][nd][n], Jyb [count][nd][nd] or NULL, both zero-filled here: a row outside an instance's W stays exactly zero.
+template <class H, class R>
+int jacobian_duals_by_vectors(H* h, size_t vecBytes, size_t nd, int first, int count, double* Jyg, double* Jyb, int* side, int* info, R run)
+{
+    const size_t B = h->db.B, n = h->db.n;
+    std::memset(Jyg, 0, sizeof(double) * (size_t)count * nd * n);
+    if (Jyb) std::memset(Jyb, 0, sizeof(double) * (size_t)count * nd * nd);
+    float ms = 0.f;
+    std::vector<double> G(B * n);
+    std::vector<int> sd(B * nd), in(B);
+    if (int rc = run(1, nullptr, G.data(), nullptr, sd.data(), in.data(), ms)) return rc;
+    std::vector<size_t> rows;
+    for (size_t r = 0; r < nd; r++) {
+        bool any = false;
+        for (size_t i = 0; i < (size_t)count; i++) any = any || sd[(first + i) * nd + r] != 0;
+        if (any) rows.push_back(r);
+    }
+    const size_t cc = staging_chunk(h->sn.staging, vecBytes, rows.size());
+    std::vector<double> VY(B * cc * nd), Bd(B * cc * nd);
+    G.resize(B * cc * n);
+    for (size_t c0 = 0; c0 < rows.size(); c0 += cc) {
+        const size_t nc = std::min(cc, rows.size() - c0);
+        std::fill(VY.begin(), VY.end(), 0.0);
+        for (size_t b = 0; b < B; b++) for (size_t k = 0; k < nc; k++) VY[(b * nc + k) * nd + rows[c0 + k]] = 1.0;
+        if (int rc = run((int)nc, VY.data(), G.data(), Bd.data(), nullptr, nullptr, ms)) return rc;
+        for (size_t i = 0; i < (size_t)count; i++)
+            for (size_t k = 0; k < nc; k++) {
+                const size_t r = rows[c0 + k], src = (first + i) * nc + k;
+                if (sd[(first + i) * nd + r] == 0) continue;      // not in this instance's W: the row stays zero
+                std::memcpy(Jyg + (i * nd + r) * n, G.data() + src * n, sizeof(double) * n);
+                if (Jyb) std::memcpy(Jyb + (i * nd + r) * nd, Bd.data() + src * nd, sizeof(double) * nd);
+            }
     }
     if (side) std::memcpy(side, sd.data() + (size_t)first * nd, sizeof(int) * (size_t)count * nd);
     if (info) std::memcpy(info, in.data() + first, sizeof(int) * (size_t)count);

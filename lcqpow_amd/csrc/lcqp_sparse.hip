@@ -324,7 +324,17 @@ __device__ __forceinline__ void sp_ell_panel(const EllMat& E, int gl, GD vals, X
 }
 
 // GENERAL (G = 64 only): the solve is the general LDL's panel form, sp_general_solve_panel; everything else is the same code.
-template <int G, bool GENERAL>
+// DUAL (DESIGN.md section 3a'''', "The sparse arm: panels with gradients on y"; lcqp_hip_sparse_adjoint_blocked / _jacobian_duals): the
+// right-hand side of k_sparse_sensitivity<G, true> for a panel, K0 [d; lambda] = [v; -vy_W] per column.  Position iperm[n + r] of column k
+// holds -vy[k][r] on the rows of W and 0 elsewhere; a.v == NULL: the first block is a zero panel.  The refinement carries the second block
+// -- residual [v - Q d - E_W'lambda; -vy_W - E_W d], |vy_r| + |E_r d| in the column's scale on the rows of W -- per column as the vector
+// kernel does per vector.  vy is read from memory where it is used, under a select on the row's status: entries outside W never reach the
+// arithmetic, whatever they hold.  Stopping, freezing and padding are those above, so a column's result depends on that column alone.
+// a.dunit (the dual rows of the Jacobian): ncols = m, column j of an instance is [0; -e_r(j)], r(j) the j-th row of W in row order, found by
+// a prefix count over MI_ST inside the lane group and written to rowpos[item][k] (-1: a column past |W|); nothing is uploaded.  The columns
+// past |W| are padding columns; an item whose first column lies past |W| writes its -1s and returns without a solve.
+// Without DUAL vy, dunit and rowpos are not read, and the code is the one above.
+template <int G, bool GENERAL, bool DUAL>
 __device__ __forceinline__ void sp_sensitivity_blk(const SpBatch& db, const SpSensBlkArgs& a)
 {
     static_assert(!GENERAL || G == 64, "the general LDL' runs one wavefront per instance");
@@ -335,7 +345,8 @@ __device__ __forceinline__ void sp_sensitivity_blk(const SpBatch& db, const SpSe
     const int w0 = a.first + (a.item0 + (int)blockIdx.x * IPW) / a.npan;      // the instance of the wave's first item (uniform): b >= w0
     SpCtx<G> c = sp_ctx<G>(db, b, w0, (int)threadIdx.x);
     const int t = c.gl, n = db.n, m = db.m, Np = db.Np;
-    const int c0 = pan * P, nc = min(P, a.ncols - c0);
+    const int c0 = pan * P;
+    int nc = min(P, a.ncols - c0);
     double* og = a.dg + (size_t)li * P * n;
     double* ob = a.dbo + (size_t)li * P * m;
     int* sd = a.side + (size_t)ir * m;
@@ -345,6 +356,7 @@ __device__ __forceinline__ void sp_sensitivity_blk(const SpBatch& db, const SpSe
         for (int i = t; i < nc * n; i += G) og[i] = 0.0;
         for (int r = t; r < nc * m; r += G) ob[r] = 0.0;
         if (t == 0) atomicOr(a.info + ir, 1);
+        if constexpr (DUAL) { if (a.dunit) for (int k = t; k < P; k += G) a.rowpos[(size_t)li * P + k] = -1; }
         return;
     }
     GI st = c.I(MI_ST);
@@ -353,15 +365,43 @@ __device__ __forceinline__ void sp_sensitivity_blk(const SpBatch& db, const SpSe
         const int marks = sp_sens_marks<G>(db, st, c.M(MV_YQ), t, sd);
         if (t == 0 && marks) atomicOr(a.info + ir, marks);
     }
+    int rk[DUAL ? P : 1];      // (DUAL, dunit) the row of W behind column k of this panel, -1 past |W|
+    if constexpr (DUAL) {
+        if (a.dunit) {
+            int* rp = a.rowpos + (size_t)li * P;
+            for (int k = t; k < P; k += G) rp[k] = -1;
+            g_sync();
+            int before = 0;      // rows of W in front of this tile of G rows (uniform inside the group)
+            for (int r0 = 0; r0 < m; r0 += G) {
+                const int r = r0 + t;
+                const int in = (r < m && (int)st[r < m ? r : 0] != ST_INACT) ? 1 : 0;
+                const unsigned long long mk = (__ballot(in) >> (threadIdx.x & ~(G - 1) & 63)) & (G == 64 ? ~0ull : ((1ull << (G & 63)) - 1ull));
+                const int rank = before + __popcll(mk & ((1ull << t) - 1ull));
+                if (in && rank >= c0 && rank < c0 + nc) rp[rank - c0] = r;
+                before += __popcll(mk);
+            }
+            g_sync();
+#pragma unroll
+            for (int k = 0; k < P; k++) rk[k] = rp[k];
+            nc = max(0, min(nc, before - c0));      // the columns past |W| are padding columns
+            if (nc == 0) return;
+        }
+    }
     // the item's workspace: the base of the wave's first item (uniform) + this group's offset
     const size_t wsItem = sens_blk_ws_doubles(db, P);
     double* wbase = a.ws + (size_t)blockIdx.x * IPW * wsItem;
     const unsigned woff = (unsigned)(threadIdx.x / G) * (unsigned)wsItem * 8u;
     GD bv{wbase, woff}, d{wbase + (size_t)P * Np, woff}, qd{wbase + (size_t)P * (Np + n), woff}, lam{wbase + (size_t)P * (Np + 2 * n), woff};
-    const double* vi = a.unit ? nullptr : a.v + ((size_t)ir * a.ncols + c0) * n;
+    const double* vi = (DUAL ? a.v == nullptr : a.unit != 0) ? nullptr : a.v + ((size_t)ir * a.ncols + c0) * n;
     auto vin = [&](int i, int k) -> double {      // entry i of column k of the panel (a padding column: zero)
         if (k >= nc) return 0.0;
-        return a.unit ? ((i == c0 + k) ? 1.0 : 0.0) : vi[(size_t)k * n + i];
+        if constexpr (DUAL) return vi ? vi[(size_t)k * n + i] : 0.0;
+        else return a.unit ? ((i == c0 + k) ? 1.0 : 0.0) : vi[(size_t)k * n + i];
+    };
+    const double* vyi = (DUAL && !a.dunit) ? a.vy + ((size_t)ir * a.ncols + c0) * m : nullptr;
+    auto vyin = [&](int r, int k) -> double {      // (DUAL) entry r of column k's upstream gradient on y (a padding column: zero)
+        if (k >= nc) return 0.0;
+        return vyi ? vyi[(size_t)k * m + r] : ((r == rk[k]) ? 1.0 : 0.0);
     };
     for (int p = t; p < Np * P; p += G) bv[p] = 0.0;
     g_sync();
@@ -370,6 +410,12 @@ __device__ __forceinline__ void sp_sensitivity_blk(const SpBatch& db, const SpSe
 #pragma unroll
         for (int k = 0; k < P; k++) { bv[pi * P + k] = vin(i, k); d[i * P + k] = 0.0; }
     }
+    if constexpr (DUAL)
+        for (int r = t; r < m; r += G) {
+            const int pr = iperm[n + r]; const bool in = st[r] != ST_INACT;
+#pragma unroll
+            for (int k = 0; k < P; k++) { const double y = vyin(r, k); bv[pr * P + k] = (in && k < nc) ? -y : 0.0; }
+        }
     for (int r = t; r < m * P; r += G) lam[r] = 0.0;
     g_sync();
     const double e1 = c.info->e1max;
@@ -427,8 +473,15 @@ __device__ __forceinline__ void sp_sensitivity_blk(const SpBatch& db, const SpSe
 #pragma unroll
                                       for (int k = 0; k < P; k++) {
                                           if (!((act >> k) & 1u)) continue;
-                                          const double rv = in ? -s[k] : 0.0;
-                                          bv[pr * P + k] = rv; mx[k] = nmax(mx[k], fabs(rv));
+                                          if constexpr (DUAL) {      // the second block carries -vy_W, and |vy_r| + |E_r d| joins the column's scale
+                                              const double y = vyin(r, k);
+                                              const double rv = in ? -y - s[k] : 0.0;
+                                              bv[pr * P + k] = rv; mx[k] = nmax(mx[k], fabs(rv));
+                                              if (in) sc[k] = fmax(sc[k], fabs(y) + fabs(s[k]));
+                                          } else {
+                                              const double rv = in ? -s[k] : 0.0;
+                                              bv[pr * P + k] = rv; mx[k] = nmax(mx[k], fabs(rv));
+                                          }
                                       }
                                   });
         g_sync();
@@ -457,7 +510,14 @@ __device__ __forceinline__ void sp_sensitivity_blk(const SpBatch& db, const SpSe
 template <int G>
 __global__ __launch_bounds__(WGS) void k_sparse_sensitivity_blk(SpBatch db, SpSensBlkArgs a)
 {
-    sp_sensitivity_blk<G, false>(db, a);
+    sp_sensitivity_blk<G, false, false>(db, a);
+}
+
+// k_sparse_sensitivity_blk with upstream gradients on y, or on the unit columns of the working set: the DUAL body above
+template <int G>
+__global__ __launch_bounds__(WGS) void k_sparse_sensitivity_blk_dual(SpBatch db, SpSensBlkArgs a)
+{
+    sp_sensitivity_blk<G, false, true>(db, a);
 }
 
 // k_sparse_sensitivity_blk on the general LDL' (DESIGN.md section 3a''', "The general engine"): one wavefront per (instance, panel) work
@@ -466,7 +526,11 @@ __global__ __launch_bounds__(WGS) void k_sparse_sensitivity_blk(SpBatch db, SpSe
 #if LCQP_TU_G == 64
 __global__ __launch_bounds__(WGS) void k_sparse_sensitivity_blk_general(SpBatch db, SpSensBlkArgs a)
 {
-    sp_sensitivity_blk<64, true>(db, a);
+    sp_sensitivity_blk<64, true, false>(db, a);
+}
+__global__ __launch_bounds__(WGS) void k_sparse_sensitivity_blk_general_dual(SpBatch db, SpSensBlkArgs a)
+{
+    sp_sensitivity_blk<64, true, true>(db, a);
 }
 #endif
 
@@ -865,6 +929,20 @@ static void sp_launch_sensitivity_blk_general(const SpBatch& db, hipStream_t str
 #endif
 }
 
+// the same two launches on the DUAL kernels (k_sparse_sensitivity_blk_dual<G>, k_sparse_sensitivity_blk_general_dual)
+template <int G>
+static void sp_launch_sensitivity_blk_dual(const SpBatch& db, hipStream_t stream, const SpSensBlkArgs& a)
+{
+    const int ipw = 64 / G, grid = (a.nItems + ipw - 1) / ipw;
+    hipLaunchKernelGGL(k_sparse_sensitivity_blk_dual<G>, dim3(grid), dim3(WGS), 0, stream, db, a);
+}
+static void sp_launch_sensitivity_blk_general_dual(const SpBatch& db, hipStream_t stream, const SpSensBlkArgs& a)
+{
+#if LCQP_TU_G == 64
+    hipLaunchKernelGGL(k_sparse_sensitivity_blk_general_dual, dim3(a.nItems), dim3(WGS), 0, stream, db, a);
+#endif
+}
+
 // one launch of k_sparse_kkt_probe<G> on device buffers; the LDS of a factorisation (sp_launch), which covers the window of the general solve
 template <int G>
 static void sp_launch_kkt_probe(const SpBatch& db, hipStream_t stream, int mode, int which, int nrhs, const double* dprim, const double* ddual, const int* use,
@@ -893,7 +971,8 @@ const SpKernels& sparse_kernels()
     static const SpKernels k = {G, sp_launch<G>, sp_launch_sensitivity<G>, sp_launch_sensitivity_dual<G>, sp_launch_kkt_probe<G>,
                                 sp_launch_sensitivity_blk<G>, sens_panel_width(G),
                                 G == 64 ? sp_launch_sensitivity_blk_general : nullptr, G == 64 ? general_panel_width() : 0,
-                                sp_launch_product_probe<G>};
+                                sp_launch_product_probe<G>,
+                                sp_launch_sensitivity_blk_dual<G>, G == 64 ? sp_launch_sensitivity_blk_general_dual : nullptr};
     return k;
 }
 }

@@ -479,27 +479,48 @@ extern "C" int lcqp_hip_sparse_max_front(const lcqp_hip_sparse_t* h) { return h 
 // [count][ncols][n], db [count][ncols][m], side [count][m], info [count] on the host.  One launch and one download per chunk of items; an item's
 // columns are contiguous in the caller's arrays, so a chunk lands there with one copy per item.  The kernel time of the call is the sum over
 // its launches.
-static int sp_panel_run(lcqp_hip_sparse* h, int first, int count, int ncols, const double* v, double* dg, double* db, int* side, int* info)
+// vy [count][ncols][m] (host) or dunit: the DUAL kernels (DESIGN.md section 3a'''', "The sparse arm: panels with gradients on y").  vy is staged
+// in sn.adjVy, as the vector adjoint stages its vy, and v may then be NULL (a zero panel).  dunit: ncols = m, the unit columns of the working
+// set, written by the kernel; dg [count][m][n] and db [count][m][m] are zero-filled here and receive staged column k of an item at row
+// rowpos[item][k] (the map lies behind the workspaces in sb.ws); rows outside W stay exactly zero.
+static int sp_panel_run(lcqp_hip_sparse* h, int first, int count, int ncols, const double* v, double* dg, double* db, int* side, int* info,
+                        const double* vy = nullptr, bool dunit = false)
 {
     SpBatch& d = h->db;
     SensBuffers& sb = h->sn.sens;
     const size_t P = sp_panel(h), n = d.n, m = d.m, npan = ((size_t)ncols + P - 1) / P, nItems = (size_t)count * npan;
     const size_t wsItem = sens_blk_ws_doubles(d, (int)P);      // (the general LDL': Np >= N = n + m positions in the ordering of the fronts)
-    SpSensitivityBlkFn* const launch = d.general ? sp_kernels(d.G)->sensitivity_blk_general : sp_kernels(d.G)->sensitivity_blk;
-    const size_t chunk = staging_chunk(h->sn.staging, sizeof(double) * (P * (n + m) + wsItem), nItems);
+    const bool dual = vy || dunit;
+    const SpKernels* const k = sp_kernels(d.G);
+    SpSensitivityBlkFn* const launch = dual ? (d.general ? k->sensitivity_blk_general_dual : k->sensitivity_blk_dual)
+                                            : (d.general ? k->sensitivity_blk_general : k->sensitivity_blk);
+    const size_t chunk = staging_chunk(h->sn.staging, sizeof(double) * (P * (n + m) + wsItem) + (dunit ? sizeof(int) * P : 0), nItems);
     HIPCHK(g_sp_err, hipSetDevice(h->device));
     const size_t vrows = v ? (size_t)count * ncols : 0;
     if (int rc = sb.reserve_rows(g_sp_err, h->mem, h->stream, count, std::max(vrows, chunk * P), n, n, m, m)) return rc;
-    if (int rc = sb.reserve_ws(g_sp_err, h->mem, h->stream, chunk * wsItem)) return rc;
+    if (int rc = sb.reserve_ws(g_sp_err, h->mem, h->stream, chunk * wsItem + (dunit ? (chunk * P + 1) / 2 : 0))) return rc;
+    int* const rowpos = dunit ? reinterpret_cast<int*>(sb.ws + chunk * wsItem) : nullptr;
     h->sn.sensPending = 0;
     if (v) HIPCHK(g_sp_err, hipMemcpyAsync(sb.v, v, sizeof(double) * vrows * n, hipMemcpyHostToDevice, h->stream));
+    if (vy) {
+        const size_t nvy = (size_t)count * ncols * m;
+        if (int rc = grow(g_sp_err, h, h->sn.adjVy, h->sn.adjVyCap, nvy)) return rc;
+        HIPCHK(g_sp_err, hipMemcpyAsync(h->sn.adjVy, vy, sizeof(double) * nvy, hipMemcpyHostToDevice, h->stream));
+    }
+    if (dunit) {
+        std::memset(dg, 0, sizeof(double) * (size_t)count * m * n);
+        if (db) std::memset(db, 0, sizeof(double) * (size_t)count * m * m);
+    }
+    std::vector<int> rp(dunit ? chunk * P : 0);
     HIPCHK(g_sp_err, hipMemsetAsync(sb.info, 0, sizeof(int) * (size_t)count, h->stream));
     std::vector<double> hg(chunk * P * n), hb(db ? chunk * P * m : 0);
     float ms = 0.f;
     for (size_t i0 = 0; i0 < nItems; i0 += chunk) {
         const size_t ni = std::min(chunk, nItems - i0);
-        const SpSensBlkArgs a = {first, (int)npan, ncols, v ? 0 : 1, (int)i0, (int)ni, sb.v, sb.dg, sb.db, sb.side, sb.info, sb.ws};
+        const SpSensBlkArgs a = {first, (int)npan, ncols, (v || dual) ? 0 : 1, (int)i0, (int)ni, v ? sb.v : nullptr, sb.dg, sb.db, sb.side, sb.info, sb.ws,
+                                 vy ? h->sn.adjVy : nullptr, dunit ? 1 : 0, rowpos};
         if (int rc = timed_launch(g_sp_err, h->stream, sb.ev0, sb.ev1, [&] { launch(d, h->stream, a); })) return rc;
+        if (dunit) HIPCHK(g_sp_err, hipMemcpyAsync(rp.data(), rowpos, sizeof(int) * ni * P, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(g_sp_err, hipMemcpyAsync(hg.data(), sb.dg, sizeof(double) * ni * P * n, hipMemcpyDeviceToHost, h->stream));
         if (db) HIPCHK(g_sp_err, hipMemcpyAsync(hb.data(), sb.db, sizeof(double) * ni * P * m, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));
@@ -508,6 +529,15 @@ static int sp_panel_run(lcqp_hip_sparse* h, int first, int count, int ncols, con
         ms += t;
         for (size_t i = 0; i < ni; i++) {
             const size_t item = i0 + i, ir = item / npan, c0 = (item % npan) * P, nc = std::min(P, (size_t)ncols - c0);
+            if (dunit) {      // staged column k is row rowpos[k] of the instance's blocks
+                for (size_t kk = 0; kk < P; kk++) {
+                    const int r = rp[i * P + kk];
+                    if (r < 0 || (size_t)r >= m) continue;
+                    std::memcpy(dg + (ir * m + r) * n, hg.data() + (i * P + kk) * n, sizeof(double) * n);
+                    if (db) std::memcpy(db + (ir * m + r) * m, hb.data() + (i * P + kk) * m, sizeof(double) * m);
+                }
+                continue;
+            }
             std::memcpy(dg + (ir * ncols + c0) * n, hg.data() + i * P * n, sizeof(double) * nc * n);
             if (db) std::memcpy(db + (ir * ncols + c0) * m, hb.data() + i * P * m, sizeof(double) * nc * m);
         }
@@ -537,6 +567,40 @@ extern "C" int lcqp_hip_sparse_jacobian(lcqp_hip_sparse_t* h, int first, int cou
     return jacobian_by_vectors(h, sizeof(double) * B * (2 * n + m), m, first, count, Jg, Jb, side, info,
                                [&](int nc, const double* v, double* dg, double* db, int* sd, int* in, float& ms) {
         return sp_sensitivity(h, nc, v, nullptr, false, dg, db, sd, in, ms);
+    });
+}); }
+
+// ---- panels with gradients on y, the dual rows of the Jacobian (DESIGN.md section 3a'''', "The sparse arm: panels with gradients on y") ----
+// vy == NULL: the blocked sensitivity call itself, and its bits.  Without a panel form (the general LDL' before lcqp_hip_sparse_set_general_panel):
+// k_sparse_sensitivity<G, true> on the nrhs vectors, an absent vx as a zero array, and that kernel's bits.
+extern "C" int lcqp_hip_sparse_adjoint_blocked(lcqp_hip_sparse_t* h, int nrhs, const double* vx, const double* vy, double* dg, double* db, int* side, int* info)
+{ return guarded(g_sp_err, [&] {
+    if (!h || nrhs < 1 || (!vx && !vy) || !dg) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!vy) return lcqp_hip_sparse_sensitivity_blocked(h, nrhs, vx, dg, db, side, info);
+    if (sp_panel(h)) return sp_panel_run(h, 0, h->db.B, nrhs, vx, dg, db, side, info, vy);
+    std::vector<double> zeros;
+    if (!vx) { zeros.assign((size_t)h->db.B * nrhs * h->db.n, 0.0); vx = zeros.data(); }
+    float ms = 0.f;
+    if (int rc = sp_sensitivity(h, nrhs, vx, vy, false, dg, db, side, info, ms)) return rc;
+    h->rs.sensMs = ms;
+    return 0;
+}); }
+
+// Jyg [count][m][n], Jyb [count][m][m] (or NULL), side [count][m], info [count] of the instances [first, first + count): the DUAL panel kernel
+// on the unit columns of the working set, in chunks of work items under the staging cap; without a panel form the vector kernel on uploaded
+// unit vy in chunks of columns (jacobian_duals_by_vectors: the staging of a column is v, vy, dg and db of the whole batch)
+extern "C" int lcqp_hip_sparse_jacobian_duals(lcqp_hip_sparse_t* h, int first, int count, double* Jyg, double* Jyb, int* side, int* info)
+{ return guarded(g_sp_err, [&] {
+    if (!h || !Jyg || first < 0 || count < 1 || (long long)first + count > h->db.B) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (sp_panel(h)) return sp_panel_run(h, first, count, h->db.m, nullptr, Jyg, Jyb, side, info, nullptr, true);
+    const size_t B = h->db.B, n = h->db.n, m = h->db.m;
+    std::vector<double> zeros;
+    return jacobian_duals_by_vectors(h, sizeof(double) * B * 2 * (n + m), m, first, count, Jyg, Jyb, side, info,
+                                     [&](int nc, const double* VY, double* G, double* Bd, int* sd, int* in, float& ms) {
+        zeros.assign(B * nc * n, 0.0);
+        return sp_sensitivity(h, nc, zeros.data(), VY, false, G, Bd, sd, in, ms);
     });
 }); }
 

@@ -149,21 +149,30 @@ using SpProductProbeFn = void(const SpBatch& db, hipStream_t stream, int wide, c
 // of item item0 + i are staged at dg + i * panel * n and dbo + i * panel * m, one contiguous vector per column; side [count][m] (written by
 // the item of panel 0), info [count] (OR-ed into: zeroed by the host in front of the call's first launch); ws: the items' workspaces,
 // sens_blk_ws_doubles(db, panel) doubles each.
+// The DUAL kernels (k_sparse_sensitivity_blk_dual<G>, k_sparse_sensitivity_blk_general_dual; DESIGN.md section 3a'''', "The sparse arm: panels with
+// gradients on y") read three more members, which the kernels above ignore: vy [count][ncols][m], the upstream gradients on the duals (v may
+// then be NULL: a zero panel; unit is 0); dunit != 0: ncols = m, column j is [0; -e_r(j)] on the j-th row of W, v and vy are not read, and
+// rowpos [nItems][panel] receives r(j) per staged column (-1: a column past |W|, whose staged outputs are not written).
 struct SpSensBlkArgs {
     int first, npan, ncols, unit, item0, nItems;
     const double* v;
     double *dg, *dbo;
     int *side, *info;
     double* ws;
+    const double* vy;
+    int dunit;
+    int* rowpos;
 };
 using SpSensitivityBlkFn = void(const SpBatch& db, hipStream_t stream, const SpSensBlkArgs& a);
 // doubles of workspace per work item: the solve panel [Np], d and Q d [n], lambda [m], interleaved by column
 __host__ __device__ inline size_t sens_blk_ws_doubles(const SpBatch& db, int panel) { return (size_t)panel * ((size_t)db.Np + 2 * (size_t)db.n + db.m); }
 // panel: the panel width of this lane width's k_sparse_sensitivity_blk (0: the width is routed to the vector kernel)
 // sensitivity_blk_general, panel_general: k_sparse_sensitivity_blk_general and its panel width -- the unit of G = 64 alone, null / 0 elsewhere
+// sensitivity_blk_dual, sensitivity_blk_general_dual: the DUAL kernels of the two, with the same panel widths
 struct SpKernels { int G; SpRunFn* run; SpSensitivityFn* sensitivity; SpSensitivityDualFn* sensitivity_dual; SpKktProbeFn* kkt_probe;
                    SpSensitivityBlkFn* sensitivity_blk; int panel; SpSensitivityBlkFn* sensitivity_blk_general; int panel_general;
-                   SpProductProbeFn* product_probe; };
+                   SpProductProbeFn* product_probe;
+                   SpSensitivityBlkFn* sensitivity_blk_dual; SpSensitivityBlkFn* sensitivity_blk_general_dual; };
 // defined in lcqp_sparse.hip and instantiated there for G = LCQP_TU_G
 template <int G> const SpKernels& sparse_kernels();
 #pragma GCC visibility pop

@@ -340,6 +340,27 @@ class BatchLCQPLayer:
         """load: BatchLCQP.load or .load_device; m: the four matrices by name"""
         return load(0, self.bt.B, m["Q"], g, m["L"], m["R"], A=m["A"], **kw)
 
+    def _last_solve(self, serial):
+        if self.solves == 0 or (serial is not None and serial != self.solves):
+            raise RuntimeError("jacobian of a solve that is not the layer's last one: the batch object holds the state of one solve")
+
+    def _jacobian_blocks(self, device_twins):
+        """the four blocks of D(x, y) / D(g, b_W) of the last solve and side as tensors of the dtype and on the device of that solve's g: jacobian + jacobian_duals of the batch, or -- device_twins, with that g on the GPU of
+        the batch -- their device-pointer twins"""
+        dtype, device = self._like
+        on_device = device_twins and device.type == "cuda" and device.index == getattr(self.bt, "device", None)
+        self.last_path = "device" if on_device else "host"
+        if on_device:
+            xg, xb, side, info = self.bt.jacobian_device()
+            yg, yb, _, _ = self.bt.jacobian_duals_device()
+        else:
+            xg, xb, side, info = self.bt.jacobian()
+            yg, yb, _, _ = self.bt.jacobian_duals()
+        self.info = info if not on_device else info.cpu().numpy()
+        out = {k: torch.as_tensor(v, device=device).to(dtype) for k, v in dict(xg=xg, xb=xb, yg=yg, yb=yb).items()}
+        out["side"] = torch.as_tensor(side, device=device)
+        return out
+
     def jacobian(self, serial=None, duals=False):
         """dx/dg of the layer's last solve, [B][nV][nV] ([b][k][j] = dx_k/dg_j), a tensor of the dtype and on the device of that
         solve's g (BatchLCQP.jacobian / SparseBatchLCQP.jacobian: the arm's blocked kernel on the unit vectors).  serial: the value of layer.solves right
@@ -347,22 +368,9 @@ class BatchLCQPLayer:
         duals=True (dense batch): the whole solution map D(x, y) / D(g, b_W) as a dict of the four blocks -- xg [B][nV][nV], xb [B][nV][nd],
         yg [B][nd][nV], yb [B][nd][nd] (BatchLCQP.jacobian and .jacobian_duals) -- and side [B][nd]; with the last solve's g on the GPU of the
         batch the device-pointer twins write device tensors (layer.last_path = "device"), else the host calls run ("host")."""
-        if self.solves == 0 or (serial is not None and serial != self.solves):
-            raise RuntimeError("jacobian of a solve that is not the layer's last one: the batch object holds the state of one solve")
+        self._last_solve(serial)
         if duals:
-            dtype, device = self._like
-            on_device = device.type == "cuda" and device.index == getattr(self.bt, "device", None)
-            self.last_path = "device" if on_device else "host"
-            if on_device:
-                xg, xb, side, info = self.bt.jacobian_device()
-                yg, yb, _, _ = self.bt.jacobian_duals_device()
-            else:
-                xg, xb, side, info = self.bt.jacobian()
-                yg, yb, _, _ = self.bt.jacobian_duals()
-            self.info = info if not on_device else info.cpu().numpy()
-            out = {k: torch.as_tensor(v, device=device).to(dtype) for k, v in dict(xg=xg, xb=xb, yg=yg, yb=yb).items()}
-            out["side"] = torch.as_tensor(side, device=device)
-            return out
+            return self._jacobian_blocks(device_twins=True)
         Jg, _, _, info = self.bt.jacobian(bounds=False)
         self.info = info
         return torch.as_tensor(Jg, dtype=self._like[0], device=self._like[1])
@@ -401,8 +409,18 @@ class SparseBatchLCQPLayer(BatchLCQPLayer):
                 self.values[k] = np.ascontiguousarray(np.broadcast_to(v, (batch.B, nnz)))
 
     def jacobian(self, serial=None):
-        """BatchLCQPLayer.jacobian without the dual blocks: the sparse arm has no panel call for them"""
+        """BatchLCQPLayer.jacobian without the dual blocks (its signature is part of this class's tested surface): jacobian_full has them"""
         return super().jacobian(serial)
+
+    def jacobian_full(self, serial=None):
+        """The whole solution map D(x, y) / D(g, b_W) of the layer's last solve, the dict BatchLCQPLayer.jacobian(duals=True) returns: xg
+        [B][nV][nV], xb [B][nV][m], yg [B][m][nV], yb [B][m][m] (SparseBatchLCQP.jacobian and .jacobian_duals: the arm's panel kernels on the
+        unit vectors, DESIGN.md section 3a''''), side [B][m], and info [B], as tensors of the dtype and on the device of that solve's g.  The
+        sparse arm has no device-pointer twins of the two calls: the host calls run (layer.last_path = "host").  serial: as jacobian."""
+        self._last_solve(serial)
+        out = self._jacobian_blocks(device_twins=False)
+        out["info"] = torch.as_tensor(self.info, device=self._like[1])
+        return out
 
     def _trailing(self, k):
         """the shape of one instance's value array k"""

@@ -41,7 +41,13 @@ the same process, the calls interleaved: sensitivity_blocked at nrhs = 64 and ja
 (lcqpow_amd/synth_sparse.py::grid_pattern_arrays) at g = 44 (nC = 200, nComp = 300) and g = 128 (bench.py's grid_128), B = 1 and B = 64.
 Off is the vector kernel.  --jac-reps: timed Jacobian calls (default: --reps; after the same 3 warm-up calls; 0 skips them: with the switch
 off a Jacobian is nV launches of the vector kernel over the whole batch -- 16 384 per call at g = 128); --grids, --batches: other sizes.
-    python tools/sensitivity_timing.py --sparse --blocked --general-panel [--grids 44,128] [--batches 1,64] [--jac-reps N] [--log FILE] [--reps 20]"""
+    python tools/sensitivity_timing.py --sparse --blocked --general-panel [--grids 44,128] [--batches 1,64] [--jac-reps N] [--log FILE] [--reps 20]
+
+--sparse --blocked --duals: sb.jacobian_duals(bounds=False) (k_sparse_sensitivity_blk_dual on the unit columns of the working set) beside the loop
+of vector calls it replaces -- one sb.adjoint(0, e_r) per row r in the working set of some instance -- on one handle, interleaved; kernel time
+summed over the launches.  (512, 256, 64) on the band engine with B = 4 and B = 1024 (256 with --quick), then the 44 x 44 grid on the general LDL'
+with its panel form on (k_sparse_sensitivity_blk_general_dual), B = 1 and B = 64 (--batches).
+    python tools/sensitivity_timing.py --sparse --blocked --duals [--quick] [--batches 1,64] [--log FILE] [--reps 20]"""
 import argparse
 import os
 import sys
@@ -342,6 +348,72 @@ def measure_general_panel(g, nC, nK, B, nrhs, reps, jac_reps, warmup=3):
     return line
 
 
+def measure_sparse_duals(sb, label, reps, warmup=1):
+    """jacobian_duals(bounds=False) beside the loop of adjoint(0, e_r) calls over the union of the working sets, interleaved on the solved
+    handle sb; kernel time from HIP events (sensitivity_kernel_ms)"""
+    B, n, m = sb.B, sb.nV, sb.m
+    zero = np.zeros((B, n))
+    side = sb.sensitivity(zero)[2]
+    rows = np.flatnonzero(np.any(side != 0, axis=0))
+    nW = np.count_nonzero(side, axis=1)
+    kj, kv = [], []
+    worst = 0.0
+    for r in range(warmup + reps):
+        Jyg = sb.jacobian_duals(bounds=False)[0]
+        k1 = sb.sensitivity_kernel_ms()
+        k0 = 0.0
+        for row in rows:
+            vy = np.zeros((B, m)); vy[:, row] = 1.0
+            out = sb.adjoint(zero, vy, matrices=())
+            k0 += sb.sensitivity_kernel_ms()
+            if r == 0:
+                inW = side[:, row] != 0
+                worst = max(worst, float(np.abs(out["dg"][inW] - Jyg[inW, row]).max(initial=0.0)))
+        if r >= warmup:
+            kj.append(k1); kv.append(k0)
+    q = lambda ms: (float(np.min(ms)), float(np.median(ms)), float(np.max(ms)))
+    tot = float(nW.sum())
+    line = ("%s B = %d (panel %d): rows of W per instance min / mean / max = %d / %.1f / %d, %d vector calls per loop; loop of adjoint(0, e_r): kernel ms min / "
+            "median / max = %.3f / %.3f / %.3f; jacobian_duals() = %.3f / %.3f / %.3f; loop / jacobian_duals (medians) = %.2f; us per row of W "
+            "%.3f -> %.3f; max |loop - jacobian_duals| = %.3g"
+            % ((label, B, sb.sens_panel(), nW.min(), nW.mean(), nW.max(), len(rows)) + q(kv) + q(kj)
+               + (np.median(kv) / np.median(kj), 1e3 * np.median(kv) / tot, 1e3 * np.median(kj) / tot, worst)))
+    print(line, flush=True)
+    return line
+
+
+def sparse_duals_main(a):
+    from lcqpow_amd import synth_sparse as S
+    lines = []
+    n, nC, nK = 512, 256, 64
+    Qpat, Apat, qo, eo = S.sparse_pattern_arrays(n, nC, nK)
+    for B in ((4, 256) if a.quick else (4, 1024)):
+        sb = la.SparseBatchLCQP(B, n, nC, nK, Qpat, Apat, opt=la.default_options(perturbStep=0, printLevel=0))
+        inst = [S.sparse_values(i, n, nC, nK, orders=(qo, eo)) for i in range(B)]
+        st = lambda k: np.stack([d[k] for d in inst])
+        assert sb.load(0, B, st("Qx"), st("g"), st("Ex"), lbA=st("lbA"), ubA=st("ubA")) == 0
+        sb.run()
+        lines.append(measure_sparse_duals(sb, "n = %d nC = %d nComp = %d (band, %d lanes)" % (n, nC, nK, sb.lanes()), a.reps))
+        sb.close()
+    g, nC, nK = 44, 200, 300
+    Qpat, Apat, qo, eo, info = S.grid_pattern_arrays(g, nC, nK)
+    for B in [int(x) for x in a.batches.split(",")]:
+        sb = la.SparseBatchLCQP(B, g * g, nC, nK, Qpat, Apat, opt=la.default_options(perturbStep=0, printLevel=0))
+        inst = [S.grid_values(i, info, (qo, eo)) for i in range(B)]
+        st = lambda k: np.stack([d[k] for d in inst])
+        assert sb.load(0, B, st("Qx"), st("g"), st("Ex"), lbA=st("lbA"), ubA=st("ubA")) == 0
+        sb.run()
+        sb.set_general_panel(True)
+        lines.append(measure_sparse_duals(sb, "grid %d x %d (n = %d nC = %d nComp = %d; general LDL', %d fronts, panel form on)" % (g, g, g * g, nC, nK, sb.fronts()), a.reps))
+        sb.close()
+    if a.log:
+        os.makedirs(os.path.dirname(os.path.abspath(a.log)), exist_ok=True)
+        with open(a.log, "w") as f:
+            f.write("lcqp_hip_sparse_jacobian_duals beside the loop of lcqp_hip_sparse_adjoint calls it replaces, sparse synthetic workloads after run, one handle, "
+                    "calls interleaved; %d timed repetitions after 1 warm-up repetition each\n" % a.reps)
+            f.write("\n".join(lines) + "\n")
+
+
 def general_panel_main(a):
     shape = {44: (200, 300), 128: (800, 1200)}
     lines = []
@@ -422,7 +494,7 @@ def main():
     ap.add_argument("--sparse", action="store_true", help="the sparse arm's kernel beside a warm resolve of unchanged data")
     ap.add_argument("--quick", action="store_true", help="--sparse: without the n = 4096, B = 4096 batch; --blocked: B = 256 at n = 256, without nrhs = 256")
     ap.add_argument("--blocked", action="store_true", help="the blocked kernel beside the vector kernel, and the Jacobian")
-    ap.add_argument("--duals", action="store_true", help="--blocked: the dual Jacobian beside the loop of vector adjoint calls it replaces (B = 4 and B = 1024; --quick: 256)")
+    ap.add_argument("--duals", action="store_true", help="--blocked: the dual Jacobian beside the loop of vector adjoint calls it replaces (B = 4 and B = 1024; --quick: 256); with --sparse: on the sparse arm")
     ap.add_argument("--adjoint", action="store_true", help="the matrix gradients summed on the device beside the per-instance path")
     ap.add_argument("--general-panel", action="store_true", help="--sparse --blocked: the general LDL' with its panel form off and on, on one handle")
     ap.add_argument("--grids", default="44,128", help="--general-panel: grid sizes")
@@ -435,6 +507,8 @@ def main():
         raise SystemExit("needs a GPU (no CPU fallback)")
     if a.sparse and a.adjoint:
         return sparse_adjoint_main(a)
+    if a.sparse and a.blocked and a.duals:
+        return sparse_duals_main(a)
     if a.sparse and a.blocked and a.general_panel:
         return general_panel_main(a)
     if a.sparse and a.blocked:
