@@ -654,6 +654,21 @@ int  lcqp_hip_sparse_read_problem(lcqp_hip_sparse_t* s, int instance, double* Qx
  * load / set_options since. */
 int  lcqp_hip_sparse_read_admm(lcqp_hip_sparse_t* s, int instance, int dims[2], double scal[3], double* rhov, double* l, double* u,
                                double* xa, double* ya, double* za);
+/* Test and diagnostic entry point (as lcqp_hip_batch_read_polish on the dense arm): the state of the active-set polish of one instance as
+ * the last run / resolve left it on the device, so that tests/test_gpu_sparse_polish_audit.py can hold every trial to a plain reference.  Host
+ * buffers, synchronous, launches nothing and changes nothing; any of dims, scal, V, M, I may be NULL.
+ *   dims [15]  0 nV, 1 m = nC + 2 nComp | the polish record: 2 trial, 3 reuse, 4 fact_valid, 5 nrefine, 6 round, 7 rc | the instance:
+ *              8 stfValid, 9 bigReg, 10 haveSolution | the handle: 11 lightOK, 12 border nodes, 13 general LDL', 14 lanes per instance
+ *   scal [11]  0 gs = 1 + |g|_inf, 1 ytol, 2 dpUsed, 3 d2Used (the regularisation pair of the factor in memory), 4 xinf = |x|_inf behind the
+ *              last correction | 5 delta, 6 deltaS, 7 delta2, 8 delta2S (the safe pair delta / delta2, the light pair deltaS / delta2S),
+ *              9 e1max = the largest row 1-norm of E, 10 scale = max |Q_ii|
+ *   V [5][nV]  the trial point xt, the right-hand side / residual r1, Q x of the last sweep, the linear term gk of the QP, the stored xq
+ *   M [5][m]   the trial multipliers yt, E x of the last trial, the stacked bounds l, u, the stored yq     (row order of [A; L; R])
+ *   I [4][m]   row states (0 inactive, 1 lower, 2 upper, 3 equality): the stored set st, the trial's set stt, the set of the factor in memory
+ *              stf, the set the last status test proposed
+ * LCQP_INVALID_ARGUMENT: NULL handle, or an instance outside the batch.  LCQP_LCQPOBJECT_NOT_SETUP: no run / resolve on this handle yet, or a
+ * load / set_options since. */
+int  lcqp_hip_sparse_read_polish(lcqp_hip_sparse_t* s, int instance, int dims[15], double scal[11], double* V, double* M, int* I);
 /* Test and diagnostic entry point: the sparse products of the solver (sp_Ex, sp_Qx2, sp_ETy, sp_residual, sp_Cx2, sp_C_from_Ex in
  * lcqp_sparse_solver.hpp) themselves, applied for every instance of a loaded batch to vectors the caller supplies, so that
  * tests/test_gpu_sparse_products.py can hold every branch of the ELL-slab gather to a plain reference.  One launch of k_sparse_product_probe

@@ -202,6 +202,7 @@ def lib():
         L.lcqp_hip_sparse_adjoint_device.argtypes = [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 3
         L.lcqp_hip_sparse_read_problem.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 9 + [c_int_p]
         L.lcqp_hip_sparse_read_admm.argtypes = [C.c_void_p, C.c_int, c_int_p, c_double_p] + [c_double_p] * 6
+        L.lcqp_hip_sparse_read_polish.argtypes = [C.c_void_p, C.c_int, c_int_p, c_double_p, c_double_p, c_double_p, c_int_p]
         L.lcqp_hip_sparse_product_probe.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 5 + [c_int_p]
         L.lcqp_hip_sparse_kkt_probe.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, c_double_p, c_double_p, c_int_p, c_double_p, c_double_p,
                                                 c_double_p, c_double_p, c_int_p]
@@ -1305,6 +1306,27 @@ class SparseBatchLCQP(_Batch):
         d = dict(rhov=np.zeros(m), l=np.zeros(m), u=np.zeros(m), xa=np.zeros(n), ya=np.zeros(m), za=np.zeros(m))
         self._call("read_admm", int(b), _ip(dims), _p(scal), *[_p(d[k]) for k in ("rhov", "l", "u", "xa", "ya", "za")])
         d.update(n=int(dims[0]), m=int(dims[1]), sigma=float(scal[0]), rho=float(scal[1]), scale=float(scal[2]))
+        return d
+
+    POLISH_DIMS = ("n", "m", "trial", "reuse", "fact_valid", "nrefine", "round", "rc", "stfValid", "bigReg", "haveSolution", "lightOK", "kb", "general", "G")
+    POLISH_SCALARS = ("gs", "ytol", "dpUsed", "d2Used", "xinf", "delta", "deltaS", "delta2", "delta2S", "e1max", "scale")
+    POLISH_V = ("xt", "r1", "qx", "gk", "xq")
+    POLISH_M = ("yt", "ex", "l", "u", "yq")
+    POLISH_I = ("st", "stt", "stf", "new")
+
+    def read_polish(self, b):
+        """Test and diagnostic entry point (lcqp_hip_sparse_read_polish; after a run / resolve; launches nothing): the state of the
+        active-set polish of instance b as it lies on the device, under the kernel's names -- the integers of POLISH_DIMS, the doubles of
+        POLISH_SCALARS, xt, r1, qx (NV_TMP), gk, xq [nV], yt, ex, l, u, yq [m] in the row order of [A; L; R], and the row states st, stt,
+        stf, new [m] (0 inactive, 1 lower, 2 upper, 3 equality)."""
+        n, m = self.nV, self.m
+        dims = np.zeros(len(self.POLISH_DIMS), dtype=np.int32); scal = np.zeros(len(self.POLISH_SCALARS))
+        V = np.zeros((len(self.POLISH_V), n)); M = np.zeros((len(self.POLISH_M), m)); I = np.zeros((len(self.POLISH_I), m), dtype=np.int32)
+        self._call("read_polish", int(b), _ip(dims), _p(scal), _p(V), _p(M), _ip(I))
+        d = {k: int(v) for k, v in zip(self.POLISH_DIMS, dims)}
+        d.update({k: float(v) for k, v in zip(self.POLISH_SCALARS, scal)})
+        for names, arr in ((self.POLISH_V, V), (self.POLISH_M, M), (self.POLISH_I, I)):
+            d.update({k: arr[i].copy() for i, k in enumerate(names)})
         return d
 
     PRODUCT_INPUTS_N = ("x", "q0", "q1", "base", "g", "xr", "c0", "c1")

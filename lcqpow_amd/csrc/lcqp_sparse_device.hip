@@ -305,3 +305,35 @@ extern "C" int lcqp_hip_sparse_read_admm(lcqp_hip_sparse_t* h, int instance, int
     if (int rc = read_back(g_sp_err, za, mv + (size_t)MV_ZA * m, m)) return rc;
     return 0;
 }); }
+
+// ---- test and diagnostic entry point: the polish state of one instance as the pools hold it (host buffers, synchronous, launches nothing) ----
+// The record of the phase machine (SpState), the instance's SpInfo and the vectors the trials of the polish read and write (sp_polish_begin,
+// sp_ph_trial, sp_ph_factor, sp_ph_correct, sp_ph_qpend in lcqp_sparse_solver.hpp), as the last run / resolve left them.
+extern "C" int lcqp_hip_sparse_read_polish(lcqp_hip_sparse_t* h, int instance, int dims[15], double scal[11], double* V, double* M, int* I)
+{ return guarded(g_sp_err, [&] {
+    if (!h || instance < 0 || instance >= h->db.B) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.setupValid) return LCQP_LCQPOBJECT_NOT_SETUP;
+    const SpBatch& d = h->db;
+    if (int rc = synchronize(g_sp_err, h)) return rc;
+    const size_t b = instance, n = d.n, m = d.m;
+    SpInfo info;
+    SpState S;
+    HIPCHK(g_sp_err, hipMemcpy(&info, d.info + b, sizeof(SpInfo), hipMemcpyDeviceToHost));
+    HIPCHK(g_sp_err, hipMemcpy(&S, d.state + b, sizeof(SpState), hipMemcpyDeviceToHost));
+    if (dims) {
+        const int v[15] = {d.n, d.m, S.trial, S.reuse, S.fact_valid, S.nrefine, S.round, S.rc, info.stfValid, info.bigReg, info.haveSolution,
+                           d.lightOK, d.kb, d.general, d.G};
+        memcpy(dims, v, sizeof(v));
+    }
+    if (scal) {
+        const double v[11] = {S.gs, S.ytol, S.dpUsed, S.d2Used, S.xinf, info.delta, info.deltaS, info.delta2, info.delta2S, info.e1max, info.scale};
+        memcpy(scal, v, sizeof(v));
+    }
+    const double *nv = d.nv + b * NV_NUM * n, *mv = d.mv + b * MV_NUM * m;
+    const int* mi = d.mi + b * MI_NUM * m;
+    static const int vsel[5] = {NV_XT, NV_R1, NV_TMP, NV_GK, NV_XQ}, msel[5] = {MV_YT, MV_EX, MV_L, MV_U, MV_YQ}, isel[4] = {MI_ST, MI_STT, MI_STF, MI_NEW};
+    for (int k = 0; k < 5; k++) if (int rc = read_back(g_sp_err, V ? V + (size_t)k * n : nullptr, nv + (size_t)vsel[k] * n, n)) return rc;
+    for (int k = 0; k < 5; k++) if (int rc = read_back(g_sp_err, M ? M + (size_t)k * m : nullptr, mv + (size_t)msel[k] * m, m)) return rc;
+    for (int k = 0; k < 4; k++) if (int rc = read_back(g_sp_err, I ? I + (size_t)k * m : nullptr, mi + (size_t)isel[k] * m, m)) return rc;
+    return 0;
+}); }

@@ -70,6 +70,8 @@ def test_c_abi_rejects_bad_arguments_without_a_gpu():
     assert L.lcqp_hip_batch_read_admm(None, 0, dims, *[None] * 10) != 0 and L.lcqp_hip_qp_read_admm(None, dims, *[None] * 10) != 0
     assert L.lcqp_hip_batch_read_polish(None, 0, None, *[None] * 4) == 100 and L.lcqp_hip_qp_read_polish(None, None, *[None] * 4) == 100
     assert callable(capi.BatchLCQP.read_polish) and callable(capi.SubsolverHIP.read_polish)
+    assert "lcqp_hip_sparse_read_polish" in declared_functions() and L.lcqp_hip_sparse_read_polish(None, 0, None, *[None] * 4) == 100
+    assert callable(capi.SparseBatchLCQP.read_polish)
     n = ctypes.c_int(0)
     if la.device_count() == 0:
         # no GPU here: creating a batch must fail with the HIP error, never fall back to anything
