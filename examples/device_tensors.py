@@ -38,6 +38,11 @@ def sparse():
     (x.square().sum() + y.sum()).backward()
     print("path:", layer.last_path, " |dl/dg| %.3e  |dl/dQx| %.3e  |dl/dAx| %.3e" % (g.grad.norm(), Qx.grad.norm(), Ax.grad.norm()), " on", Qx.grad.device)
     print("solved:", sum(s["returnValue"] == 0 for s in layer.stats), "of", B)
+    # the whole solution map D(x, y) / D(g, b_W) of that solve: with g on the device the panel kernels' staging goes to six device tensors
+    # through k_sparse_scatter_panels (jacobian_device + jacobian_duals_device)
+    J = layer.jacobian_full()
+    print("jacobian_full path:", layer.last_path, " on", J["xg"].device, " blocks:", {k: tuple(v.shape) for k, v in J.items()},
+          " |dx/dg| %.3e  |dy/dg| %.3e" % (J["xg"].norm(), J["yg"].norm()))
     sb.close()
 
 

@@ -639,6 +639,35 @@ int  lcqp_hip_sparse_sensitivity_device(lcqp_hip_sparse_t* s, int nrhs, const do
                                         double* dg, double* db, int* side, int* info, void* stream);
 int  lcqp_hip_sparse_adjoint_device(lcqp_hip_sparse_t* s, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
                                     int reduce, double* dQx, double* dAx, void* stream);
+/* The device-pointer twins of the four panel calls -- lcqp_hip_sparse_sensitivity_blocked, _adjoint_blocked, _jacobian and _jacobian_duals --
+ * under the rules above (DESIGN.md section 3a''''', "The sparse arm: panels and Jacobians into device arrays"): layouts, results and codes are
+ * the host twins', every array is a device array, and the results hold the host twins' bits, whatever the chunking.
+ *   checks    NULL handle: LCQP_LCQPOBJECT_NOT_SETUP.  Then the host twin's argument checks in its order (LCQP_INVALID_ARGUMENT), then
+ *             LCQP_LCQPOBJECT_NOT_SETUP without a finished solve, then the pointers: every non-NULL data pointer plain device memory of the
+ *             handle's device, 8-byte aligned (side, info: 4), with the bytes the call moves behind it -- else LCQP_INVALID_ARGUMENT and a
+ *             message that names the argument.  All of it on the host, before anything is enqueued.
+ *   inputs    v, vx [B][nrhs][nV] and vy [B][nrhs][m] are read where they lie.
+ *   work      on the handle's stream between the two events of the hand-over: the host twin's chunks of (instance, panel) work items under
+ *             the cap of lcqp_hip_sparse_set_adjoint_staging, each chunk's panel launch followed by ONE launch of k_sparse_scatter_panels,
+ *             which takes the staged columns to the rows of the caller's arrays the host twin's copies take them to (the padding columns of
+ *             a ragged last panel nowhere; jacobian_duals: column k to the row the panel kernel recorded for it, and Jyg / Jyb are
+ *             zero-filled on the stream first: rows outside W are exact zeros); side and info go device to device.
+ *   waits     none on the host, but for a buffer of the handle that grows, and for a call of more than one chunk: it waits for the kernel
+ *             of every chunk but the last, whose events it is about to reuse.  lcqp_hip_sparse_sensitivity_timing reports the sum over the
+ *             chunks' panel kernels, as after the host twins (and waits for the last one).
+ *   no panel form (lcqp_hip_sparse_sens_panel(s) == 0): the two blocked calls run the vector kernel on the caller's arrays, as
+ *             lcqp_hip_sparse_sensitivity_device does (an absent vx: a zero array on the device) -- the host twins' bits.  The two Jacobian
+ *             calls form their result through the host twins and copy it to the device: THOSE TWO THEN WAIT ON THE HOST.
+ * The calls change nothing a run / resolve reads, leave lcqp_hip_sparse_launch_counts alone and share the handle's staging with the host
+ * twins: host and device calls may alternate on one handle. */
+int  lcqp_hip_sparse_sensitivity_blocked_device(lcqp_hip_sparse_t* s, int nrhs, const double* v,
+                                                double* dg, double* db, int* side, int* info, void* stream);
+int  lcqp_hip_sparse_adjoint_blocked_device(lcqp_hip_sparse_t* s, int nrhs, const double* vx, const double* vy,
+                                            double* dg, double* db, int* side, int* info, void* stream);
+int  lcqp_hip_sparse_jacobian_device(lcqp_hip_sparse_t* s, int first, int count,
+                                     double* Jg, double* Jb, int* side, int* info, void* stream);
+int  lcqp_hip_sparse_jacobian_duals_device(lcqp_hip_sparse_t* s, int first, int count,
+                                           double* Jyg, double* Jyb, int* side, int* info, void* stream);
 /* Test and diagnostic entry point: the problem of one instance as the pools hold it, so that a load or an update can be held bit for bit and
  * not only through solutions.  Host buffers, synchronous, launches nothing; any output may be NULL.  Qx [nnzQ]; Ax [nnzA] in the caller's CSC
  * order (through the inverse of the value map); g, x0 [nV]; lE, uE [m]: the stacked row bounds as stored, m = nC + 2 nComp; lbL, lbR [nComp];

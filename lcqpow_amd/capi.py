@@ -200,6 +200,10 @@ def lib():
         L.lcqp_hip_sparse_get_solution_device.argtypes = [C.c_void_p] * 5
         L.lcqp_hip_sparse_sensitivity_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
         L.lcqp_hip_sparse_adjoint_device.argtypes = [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 3
+        L.lcqp_hip_sparse_sensitivity_blocked_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 6
+        L.lcqp_hip_sparse_adjoint_blocked_device.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 7
+        L.lcqp_hip_sparse_jacobian_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
+        L.lcqp_hip_sparse_jacobian_duals_device.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
         L.lcqp_hip_sparse_read_problem.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 9 + [c_int_p]
         L.lcqp_hip_sparse_read_admm.argtypes = [C.c_void_p, C.c_int, c_int_p, c_double_p] + [c_double_p] * 6
         L.lcqp_hip_sparse_read_polish.argtypes = [C.c_void_p, C.c_int, c_int_p, c_double_p, c_double_p, c_double_p, c_int_p]
@@ -851,6 +855,41 @@ class _Batch:
         r.update(mats)
         return r
 
+    def adjoint_blocked_device(self, VX, VY=None):
+        """*_adjoint_blocked_device: adjoint_blocked on float64 tensors of the handle's device, read where they lie; returns
+        (dg, db, side, info) as tensors on that device"""
+        import torch
+        for name, t in (("VX", VX), ("VY", VY)):
+            if t is not None and not isinstance(t, torch.Tensor):
+                raise ValueError(f"{name}: expected a torch tensor on the device of the batch, got {type(t).__name__}")
+        VX, VY, k = self._pairs(VX, VY, lambda t: t)
+        B, n, nd = self.B, self.nV, self.nd
+        pvx = self._dev("VX", VX, ((B, k, n),)); pvy = self._dev("VY", VY, ((B, k, nd),))
+        dg, db, side, info = self._results((B, k))
+        self._call("adjoint_blocked_device", k, pvx, pvy, dg.data_ptr(), db.data_ptr(), side.data_ptr(), info.data_ptr(), self._stream())
+        return dg, db, side, info
+
+    def _jacobian_device(self, name, rows, first, count, bounds):
+        import torch
+        if count is None:
+            count = self.B - first
+        self._range(first, count)
+        n, nd = self.nV, self.nd
+        dev = torch.device("cuda", self.device)
+        Jg = torch.empty((count, rows, n), dtype=torch.float64, device=dev)
+        Jb = torch.empty((count, rows, nd), dtype=torch.float64, device=dev) if bounds else None
+        side = torch.empty((count, nd), dtype=torch.int32, device=dev); info = torch.empty(count, dtype=torch.int32, device=dev)
+        self._call(name, first, count, Jg.data_ptr(), Jb.data_ptr() if bounds else None, side.data_ptr(), info.data_ptr(), self._stream())
+        return Jg, Jb, side, info
+
+    def jacobian_device(self, first=0, count=None, bounds=True):
+        """*_jacobian_device: jacobian() written into tensors on the handle's device, (Jg, Jb, side, info)"""
+        return self._jacobian_device("jacobian_device", self.nV, first, count, bounds)
+
+    def jacobian_duals_device(self, first=0, count=None, bounds=True):
+        """*_jacobian_duals_device: jacobian_duals() written into tensors on the handle's device, (Jyg, Jyb, side, info)"""
+        return self._jacobian_device("jacobian_duals_device", self.nd, first, count, bounds)
+
     def close(self):
         if self.h:
             self._sym("destroy")(self.h)
@@ -921,41 +960,6 @@ class BatchLCQP(_Batch):
 
     # ---- the device-pointer entry points (DESIGN.md section 3a'''''): torch tensors on the handle's device in, torch tensors out; the work is
     # ordered behind torch.cuda.current_stream(), and what the caller enqueues there next sees the results.  No copy through the host.
-    def adjoint_blocked_device(self, VX, VY=None):
-        """lcqp_hip_batch_adjoint_blocked_device: adjoint_blocked on float64 tensors of the handle's device, read where they lie; returns
-        (dg, db, side, info) as tensors on that device"""
-        import torch
-        for name, t in (("VX", VX), ("VY", VY)):
-            if t is not None and not isinstance(t, torch.Tensor):
-                raise ValueError(f"{name}: expected a torch tensor on the device of the batch, got {type(t).__name__}")
-        VX, VY, k = self._pairs(VX, VY, lambda t: t)
-        B, n, nd = self.B, self.nV, self.nd
-        pvx = self._dev("VX", VX, ((B, k, n),)); pvy = self._dev("VY", VY, ((B, k, nd),))
-        dg, db, side, info = self._results((B, k))
-        self._call("adjoint_blocked_device", k, pvx, pvy, dg.data_ptr(), db.data_ptr(), side.data_ptr(), info.data_ptr(), self._stream())
-        return dg, db, side, info
-
-    def _jacobian_device(self, name, rows, first, count, bounds):
-        import torch
-        if count is None:
-            count = self.B - first
-        self._range(first, count)
-        n, nd = self.nV, self.nd
-        dev = torch.device("cuda", self.device)
-        Jg = torch.empty((count, rows, n), dtype=torch.float64, device=dev)
-        Jb = torch.empty((count, rows, nd), dtype=torch.float64, device=dev) if bounds else None
-        side = torch.empty((count, nd), dtype=torch.int32, device=dev); info = torch.empty(count, dtype=torch.int32, device=dev)
-        self._call(name, first, count, Jg.data_ptr(), Jb.data_ptr() if bounds else None, side.data_ptr(), info.data_ptr(), self._stream())
-        return Jg, Jb, side, info
-
-    def jacobian_device(self, first=0, count=None, bounds=True):
-        """lcqp_hip_batch_jacobian_device: jacobian() written into tensors on the handle's device, (Jg, Jb, side, info)"""
-        return self._jacobian_device("jacobian_device", self.nV, first, count, bounds)
-
-    def jacobian_duals_device(self, first=0, count=None, bounds=True):
-        """lcqp_hip_batch_jacobian_duals_device: jacobian_duals() written into tensors on the handle's device, (Jyg, Jyb, side, info)"""
-        return self._jacobian_device("jacobian_duals_device", self.nd, first, count, bounds)
-
     def load_device(self, first, count, Q, g, L, R, lbL=None, ubL=None, lbR=None, ubR=None, A=None, lbA=None, ubA=None,
                     lb=None, ub=None, x0=None, y0=None):
         """lcqp_hip_batch_load_device: load() from float64 torch tensors on the handle's device, packed into the pools by kernels.  A
@@ -1279,6 +1283,23 @@ class SparseBatchLCQP(_Batch):
         """lcqp_hip_sparse_sensitivity_device: sensitivity(v) with v a float64 tensor on the handle's device, [B][nV] or [B][k][nV], read
         where it lies; returns (dg, db, side, info) as tensors on that device (side, info: int32)."""
         return self._sensitivity_device(v)
+
+    def sensitivity_blocked_device(self, V):
+        """lcqp_hip_sparse_sensitivity_blocked_device: sensitivity_blocked(V) with V a float64 tensor on the handle's device, [B][k][nV], read
+        where it lies; returns (dg [B][k][nV], db [B][k][m], side, info) as tensors on that device with the bits of the host call.  The
+        panel kernel's staging goes to the tensors through k_sparse_scatter_panels on the device; adjoint_blocked_device, jacobian_device
+        and jacobian_duals_device (_Batch) are the twins of the other three panel calls (DESIGN.md section 3a''''', "The sparse arm: panels
+        and Jacobians into device arrays")."""
+        import torch
+        if not isinstance(V, torch.Tensor):
+            raise ValueError(f"V: expected a torch tensor on the device of the batch, got {type(V).__name__}")
+        if V.dim() != 3 or V.shape[1] < 1:
+            raise ValueError(f"V: expected [{self.B}][k][{self.nV}] with k >= 1, got shape {tuple(V.shape)}")
+        k = V.shape[1]
+        pv = self._dev("V", V, ((self.B, k, self.nV),))
+        dg, db, side, info = self._results((self.B, k))
+        self._call("sensitivity_blocked_device", k, pv, dg.data_ptr(), db.data_ptr(), side.data_ptr(), info.data_ptr(), self._stream())
+        return dg, db, side, info
 
     def adjoint_device(self, vx, vy=None, matrices=("Q", "A"), reduce=False, out=None):
         """lcqp_hip_sparse_adjoint_device: adjoint(vx, vy, matrices, reduce) with float64 tensors on the handle's device in and out -- the

@@ -882,44 +882,14 @@ extern "C" int lcqp_hip_batch_adjoint_blocked_device(lcqp_hip_batch_t* h, int nr
     });
 }); }
 
-// the checks both Jacobian twins make: the range, then the four arrays with the bytes the call moves (rows: of one instance's two blocks)
-static int jacobian_device_checks(lcqp_hip_batch* h, int first, int count, size_t rows, const char* gname, double* Jg, const char* bname, double* Jb,
-                                  int* side, int* info)
-{
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    if (!Jg || first < 0 || count < 1 || first > h->db.B - count) return LCQP_INVALID_ARGUMENT;
-    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    HIPCHK(g_err, hipSetDevice(h->device));
-    const size_t n = h->db.n, nd = h->db.nd, c = count;
-    if (!device_pointer_ok(g_err, h, gname, Jg, sizeof(double) * c * rows * n) || !device_pointer_ok(g_err, h, bname, Jb, sizeof(double) * c * rows * nd) ||
-        !device_pointer_ok(g_err, h, "side", side, sizeof(int) * c * nd, 4) || !device_pointer_ok(g_err, h, "info", info, sizeof(int) * c, 4)) return LCQP_INVALID_ARGUMENT;
-    return 0;
-}
-
-// np >= 1024: a Jacobian formed by the host twin (run) and copied to the caller's device arrays; waits on the host
-template <class R>
-static int jacobian_through_host(lcqp_hip_batch* h, size_t count, size_t rows, double* Jg, double* Jb, int* side, int* info, R run)
-{
-    const size_t n = h->db.n, nd = h->db.nd;
-    std::vector<double> G(count * rows * n), Bd(Jb ? count * rows * nd : 0);
-    std::vector<int> sd(count * nd), in(count);
-    if (int rc = run(G.data(), Jb ? Bd.data() : nullptr, sd.data(), in.data())) return rc;
-    HIPCHK(g_err, hipMemcpyAsync(Jg, G.data(), sizeof(double) * G.size(), hipMemcpyHostToDevice, h->stream));
-    if (Jb) HIPCHK(g_err, hipMemcpyAsync(Jb, Bd.data(), sizeof(double) * Bd.size(), hipMemcpyHostToDevice, h->stream));
-    if (side) HIPCHK(g_err, hipMemcpyAsync(side, sd.data(), sizeof(int) * sd.size(), hipMemcpyHostToDevice, h->stream));
-    if (info) HIPCHK(g_err, hipMemcpyAsync(info, in.data(), sizeof(int) * in.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(g_err, hipStreamSynchronize(h->stream));
-    return 0;
-}
-
 extern "C" int lcqp_hip_batch_jacobian_device(lcqp_hip_batch_t* h, int first, int count, double* Jg, double* Jb, int* side, int* info, void* stream)
 { return guarded(g_err, [&] {
-    if (int rc = jacobian_device_checks(h, first, count, h ? h->db.n : 0, "Jg", Jg, "Jb", Jb, side, info)) return rc;
+    if (int rc = jacobian_device_checks(g_err, h, h ? h->db.nd : 0, first, count, h ? h->db.n : 0, "Jg", Jg, "Jb", Jb, side, info)) return rc;
     DevBatch& d = h->db;
     const size_t n = d.n, nd = d.nd;
     return device_call(g_err, h, stream, [&] {
         if (!h->k->sensitivity_blk)
-            return jacobian_through_host(h, count, n, Jg, Jb, side, info, [&](double* G, double* Bd, int* sd, int* in) { return batch_jacobian(h, first, count, G, Bd, sd, in); });
+            return jacobian_through_host(g_err, h, nd, count, n, Jg, Jb, side, info, [&](double* G, double* Bd, int* sd, int* in) { return batch_jacobian(h, first, count, G, Bd, sd, in); });
         // the chunks of batch_jacobian; every chunk's results go from the staging to their place with copies on the handle's stream
         const size_t chunk = staging_chunk(h->sn.staging, sizeof(double) * n * (n + (size_t)d.np + nd + 2 * (size_t)d.capS), count);
         float ms = 0.f, before = 0.f;      // before: the kernel time of the chunks in front of the last one (chunk_time)
@@ -936,12 +906,12 @@ extern "C" int lcqp_hip_batch_jacobian_device(lcqp_hip_batch_t* h, int first, in
 
 extern "C" int lcqp_hip_batch_jacobian_duals_device(lcqp_hip_batch_t* h, int first, int count, double* Jyg, double* Jyb, int* side, int* info, void* stream)
 { return guarded(g_err, [&] {
-    if (int rc = jacobian_device_checks(h, first, count, h ? h->db.nd : 0, "Jyg", Jyg, "Jyb", Jyb, side, info)) return rc;
+    if (int rc = jacobian_device_checks(g_err, h, h ? h->db.nd : 0, first, count, h ? h->db.nd : 0, "Jyg", Jyg, "Jyb", Jyb, side, info)) return rc;
     DevBatch& d = h->db;
     const size_t n = d.n, nd = d.nd;
     return device_call(g_err, h, stream, [&] {
         if (!h->k->sensitivity_blk_dual)
-            return jacobian_through_host(h, count, nd, Jyg, Jyb, side, info, [&](double* G, double* Bd, int* sd, int* in) { return batch_jacobian_duals(h, first, count, G, Bd, sd, in); });
+            return jacobian_through_host(g_err, h, nd, count, nd, Jyg, Jyb, side, info, [&](double* G, double* Bd, int* sd, int* in) { return batch_jacobian_duals(h, first, count, G, Bd, sd, in); });
         // the rows k_pack_dual_rows does not write (outside W) are zero
         HIPCHK(g_err, hipMemsetAsync(Jyg, 0, sizeof(double) * (size_t)count * nd * n, h->stream));
         if (Jyb) HIPCHK(g_err, hipMemsetAsync(Jyb, 0, sizeof(double) * (size_t)count * nd * nd, h->stream));

@@ -244,5 +244,39 @@ bool sens_pointers_ok(std::string& err, const H* h, size_t nd, size_t rows, cons
            device_pointer_ok(err, h, "side", side, sizeof(int) * B * nd, 4) && device_pointer_ok(err, h, "info", info, sizeof(int) * B, 4);
 }
 
+// the checks the Jacobian twins of both arms make (*_jacobian_device, *_jacobian_duals_device), in the host twins' order: the handle, the
+// range, a finished solve, then the four arrays with the bytes the call moves (rows: of one instance's two blocks; nd: the width of the dual
+// vector)
+template <class H>
+int jacobian_device_checks(std::string& err, H* h, size_t nd, int first, int count, size_t rows, const char* gname, double* Jg, const char* bname, double* Jb,
+                           int* side, int* info)
+{
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!Jg || first < 0 || count < 1 || first > h->db.B - count) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    HIPCHK(err, hipSetDevice(h->device));
+    const size_t n = h->db.n, c = count;
+    if (!device_pointer_ok(err, h, gname, Jg, sizeof(double) * c * rows * n) || !device_pointer_ok(err, h, bname, Jb, sizeof(double) * c * rows * nd) ||
+        !device_pointer_ok(err, h, "side", side, sizeof(int) * c * nd, 4) || !device_pointer_ok(err, h, "info", info, sizeof(int) * c, 4)) return LCQP_INVALID_ARGUMENT;
+    return 0;
+}
+
+// Where an arm has only its vector kernel for a Jacobian (dense: np >= 1024; sparse: the general LDL' without its panel form): the Jacobian
+// formed by the host twin (run) and copied to the caller's device arrays; waits on the host
+template <class H, class R>
+int jacobian_through_host(std::string& err, H* h, size_t nd, size_t count, size_t rows, double* Jg, double* Jb, int* side, int* info, R run)
+{
+    const size_t n = h->db.n;
+    std::vector<double> G(count * rows * n), Bd(Jb ? count * rows * nd : 0);
+    std::vector<int> sd(count * nd), in(count);
+    if (int rc = run(G.data(), Jb ? Bd.data() : nullptr, sd.data(), in.data())) return rc;
+    HIPCHK(err, hipMemcpyAsync(Jg, G.data(), sizeof(double) * G.size(), hipMemcpyHostToDevice, h->stream));
+    if (Jb) HIPCHK(err, hipMemcpyAsync(Jb, Bd.data(), sizeof(double) * Bd.size(), hipMemcpyHostToDevice, h->stream));
+    if (side) HIPCHK(err, hipMemcpyAsync(side, sd.data(), sizeof(int) * sd.size(), hipMemcpyHostToDevice, h->stream));
+    if (info) HIPCHK(err, hipMemcpyAsync(info, in.data(), sizeof(int) * in.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(err, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
 #pragma GCC visibility pop
 }  // namespace lcqp_rt

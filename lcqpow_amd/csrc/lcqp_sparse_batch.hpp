@@ -62,4 +62,28 @@ struct SpPackValues { const double *Qx, *Ax; size_t qStride, aStride; };
 // h->stream; nothing waits.  The checks and the host state are the caller's.
 int sparse_pack(lcqp_hip_sparse* h, int first, int count, const SpPackVectors& v, const SpPackValues& m, bool update);
 
+// ---- from the staging of the panel kernels (lcqp_sparse_launch.hpp: SpSensBlkArgs) to the caller's arrays.  The one definition of where a
+// staged column goes: the host loop of sp_panel_run (lcqp_sparse_host.hip) and k_sparse_scatter_panels (lcqp_sparse_device.hip) both call it.
+// Staged column k of work item `item` = (instance - first) * npan + panel of a call with ncols columns per instance in panels of P: the row
+// of the caller's [count][ncols][..] arrays it is, or -1: nowhere.  Plain calls: column panel * P + k of its instance; the padding columns
+// of a ragged last panel go nowhere.  dunit (the dual Jacobian, ncols = m): row rowpos -- what the kernel wrote for this column -- of its
+// instance, nowhere when that is no row (-1: a column past |W|).
+__host__ __device__ inline long long sp_panel_dest_row(unsigned item, unsigned k, unsigned npan, unsigned P, unsigned ncols, int dunit, int rowpos)
+{
+    const unsigned ir = item / npan;
+    if (dunit) return (rowpos < 0 || (unsigned)rowpos >= ncols) ? -1 : (long long)ir * ncols + rowpos;
+    const unsigned c = (item % npan) * P + k;
+    return c >= ncols ? -1 : (long long)ir * ncols + c;
+}
+// one chunk of a call: the work items [item0, item0 + nItems), staged at sg [nItems][P][n] and sb [nItems][P][m] with rowpos [nItems][P]
+// (dunit), to dg [count][ncols][n] and db [count][ncols][m] (null: not asked for) on the device
+struct SpScatterArgs {
+    int npan, ncols, dunit, P, n, m, item0, nItems;
+    const double *sg, *sb;
+    const int* rowpos;
+    double *dg, *db;
+};
+// k_sparse_scatter_panels on h->stream; nothing waits
+int sparse_scatter_panels(lcqp_hip_sparse* h, const SpScatterArgs& a);
+
 #pragma GCC visibility pop

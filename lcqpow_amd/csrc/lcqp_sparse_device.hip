@@ -1,7 +1,8 @@
 // lcqp_sparse_device.hip -- the sparse batch's device-pointer entry points that fill and read the pools: lcqp_hip_sparse_load_device,
 // _update_device and _get_solution_device (include/lcqp_hip.h, DESIGN.md section 3a'''''), with their three kernels, sparse_pack -- the pack step
-// the host load / update of lcqp_sparse_host.hip run behind their upload: the pack kernels are the one definition of the pool layout -- and the diagnostic
-// reader lcqp_hip_sparse_read_problem.  The twins of _sensitivity and _adjoint sit beside the kernels they launch, in lcqp_sparse_host.hip;
+// the host load / update of lcqp_sparse_host.hip run behind their upload: the pack kernels are the one definition of the pool layout --, the
+// scatter kernel of the device-pointer panel calls (k_sparse_scatter_panels, launched by sp_panel_run of lcqp_sparse_host.hip) and the diagnostic
+// reader lcqp_hip_sparse_read_problem.  The twins of _sensitivity, _adjoint and the panel calls sit beside their host twins, in lcqp_sparse_host.hip;
 // lcqp_sparse_batch.hpp holds what the two units share, lcqp_host_rt.hpp the hand-over around every such call (device_call) and
 // _get_solution_device, which are the dense arm's too.  The model is lcqp_hip_device.hip of the dense arm.
 #include "lcqp_sparse_batch.hpp"
@@ -135,10 +136,49 @@ __global__ __launch_bounds__(SP_DEV_WG) void k_sparse_pack_vectors(SpBatch db, i
     for (int e = t; e < (int)(sizeof(SpInfo) / 4); e += SP_DEV_WG) info[e] = e == 2 ? (p.y0 ? 1 : 0) : 0;
 }
 
+// ---- k_sparse_scatter_panels: one chunk of staged work items of a panel call to the caller's device arrays (the device-pointer twins of
+// lcqp_hip_sparse_sensitivity_blocked / _adjoint_blocked / _jacobian / _jacobian_duals; lcqp_sparse_batch.hpp: SpScatterArgs) ----
+// What the host loop of sp_panel_run does with memcpy: staged column c = i * P + k goes to row sp_panel_dest_row(..) of dg and db, or nowhere.
+// 1 << shift threads (16 .. SP_DEV_WG, chosen by the host from the longer row) take one staged column: its row of dg, then its row of db,
+// each lane element t, t + 2^shift, ... -- neighbouring lanes load and store neighbouring doubles.  The workgroups stride over the columns.
+// No two columns of a call have one destination row, so no element is written twice and the kernel needs no order among its stores.
+__global__ __launch_bounds__(SP_DEV_WG) void k_sparse_scatter_panels(SpScatterArgs a, int shift)
+{
+    const unsigned tpc = 1u << shift, t = threadIdx.x & (tpc - 1), cpw = SP_DEV_WG >> shift;
+    const unsigned total = (unsigned)a.nItems * a.P, P = a.P;
+    const size_t n = a.n, m = a.m;
+    for (unsigned c = blockIdx.x * cpw + (threadIdx.x >> shift); c < total; c += gridDim.x * cpw) {
+        const unsigned i = c / P, k = c - i * P;
+        const long long row = sp_panel_dest_row((unsigned)a.item0 + i, k, a.npan, P, a.ncols, a.dunit, a.dunit ? a.rowpos[c] : 0);
+        if (row < 0) continue;
+        const double* sg = a.sg + (size_t)c * n;
+        double* dg = a.dg + (size_t)row * n;
+        for (size_t e = t; e < n; e += tpc) dg[e] = sg[e];
+        if (!a.db) continue;
+        const double* sb = a.sb + (size_t)c * m;
+        double* db = a.db + (size_t)row * m;
+        for (size_t e = t; e < m; e += tpc) db[e] = sb[e];
+    }
+}
+
 // =================================================================================================
 // host side
 // =================================================================================================
 #define g_sp_err sparse_err()      // the error slot of the sparse arm (thread_local, lcqp_sparse_host.hip)
+
+int sparse_scatter_panels(lcqp_hip_sparse* h, const SpScatterArgs& a)
+{
+    const size_t total = (size_t)a.nItems * a.P, longer = std::max(a.n, a.db ? a.m : 0);
+    if (!total) return 0;
+    if (total > 0xFFFFFFFFull) { g_sp_err = "scatter: more staged columns in one chunk than the kernel counts"; return LCQP_HIP_UNSUPPORTED; }
+    int shift = 4;
+    while ((1 << shift) < SP_DEV_WG && ((size_t)1 << shift) < longer) shift++;
+    const size_t cpw = SP_DEV_WG >> shift;      // staged columns per workgroup and turn
+    const unsigned gx = (unsigned)std::min<size_t>((total + cpw - 1) / cpw, (size_t)std::max(h->cus, 1) * 16);
+    hipLaunchKernelGGL(k_sparse_scatter_panels, dim3(gx), dim3(SP_DEV_WG), 0, h->stream, a, shift);
+    HIPCHK(g_sp_err, hipGetLastError());
+    return 0;
+}
 
 int sparse_pack(lcqp_hip_sparse* h, int first, int count, const SpPackVectors& v, const SpPackValues& m, bool update)
 {

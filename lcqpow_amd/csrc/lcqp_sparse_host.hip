@@ -434,10 +434,14 @@ static int sp_sensitivity(lcqp_hip_sparse* h, int nrhs, const double* v, const d
 {
     SpBatch& d = h->db;
     const SensPitch p = {(size_t)d.n, (size_t)d.n, (size_t)d.m, (size_t)d.m};
-    return sensitivity_call(g_sp_err, h, h->sn.sens, p, d.B, nrhs, v, vy, dev, 1, dg, db, side, info, ms, [&](const double* dv, const double* dvy, SensBuffers& sb) {
+    hipError_t filled = hipSuccess;
+    if (int rc = sensitivity_call(g_sp_err, h, h->sn.sens, p, d.B, nrhs, v, vy, dev, 1, dg, db, side, info, ms, [&](const double* dv, const double* dvy, SensBuffers& sb) {
+        if (vy && !dv) { filled = hipMemsetAsync(sb.v, 0, sizeof(double) * sb.rows * d.n, h->stream); dv = sb.v; }      // (a device twin without vx)
         if (vy) sp_kernels(d.G)->sensitivity_dual(d, h->stream, nrhs, dv, dvy, sb.dg, sb.db, sb.side, sb.info);
         else sp_kernels(d.G)->sensitivity(d, h->stream, nrhs, dv, sb.dg, sb.db, sb.side, sb.info);
-    });
+    })) return rc;
+    HIPCHK(g_sp_err, filled);
+    return 0;
 }
 
 // the host call on the vector kernel
@@ -476,15 +480,20 @@ extern "C" int lcqp_hip_sparse_set_general_panel(lcqp_hip_sparse_t* h, int on)
 extern "C" int lcqp_hip_sparse_max_front(const lcqp_hip_sparse_t* h) { return h ? (h->db.general ? h->db.gMaxFront : 0) : -1; }
 
 // Instances [first, first + count), ncols columns each: v [count][ncols][n] on the host, or NULL = the unit vectors (ncols = n).  dg
-// [count][ncols][n], db [count][ncols][m], side [count][m], info [count] on the host.  One launch and one download per chunk of items; an item's
-// columns are contiguous in the caller's arrays, so a chunk lands there with one copy per item.  The kernel time of the call is the sum over
+// [count][ncols][n], db [count][ncols][m], side [count][m], info [count] on the host.  One launch and one download per chunk of items; staged
+// column k of an item goes to the row sp_panel_dest_row gives it, with one copy per column.  The kernel time of the call is the sum over
 // its launches.
 // vy [count][ncols][m] (host) or dunit: the DUAL kernels (DESIGN.md section 3a'''', "The sparse arm: panels with gradients on y").  vy is staged
 // in sn.adjVy, as the vector adjoint stages its vy, and v may then be NULL (a zero panel).  dunit: ncols = m, the unit columns of the working
 // set, written by the kernel; dg [count][m][n] and db [count][m][m] are zero-filled here and receive staged column k of an item at row
 // rowpos[item][k] (the map lies behind the workspaces in sb.ws); rows outside W stay exactly zero.
+// dev (the device-pointer twins, DESIGN.md section 3a''''', "The sparse arm: panels and Jacobians into device arrays"): every array is the
+// caller's device array.  v and vy are read where they lie; behind each chunk's launch k_sparse_scatter_panels takes the staged columns to the
+// rows the host loop takes them to (rowpos stays on the device); dg and db of dunit are zero-filled on the stream, side and info go device to
+// device.  Nothing waits on the host but a call of several chunks, for the kernel time of each chunk but the last (chunk_time); the last
+// one's stays in the events (sensPending).
 static int sp_panel_run(lcqp_hip_sparse* h, int first, int count, int ncols, const double* v, double* dg, double* db, int* side, int* info,
-                        const double* vy = nullptr, bool dunit = false)
+                        const double* vy = nullptr, bool dunit = false, bool dev = false)
 {
     SpBatch& d = h->db;
     SensBuffers& sb = h->sn.sens;
@@ -496,30 +505,44 @@ static int sp_panel_run(lcqp_hip_sparse* h, int first, int count, int ncols, con
                                             : (d.general ? k->sensitivity_blk_general : k->sensitivity_blk);
     const size_t chunk = staging_chunk(h->sn.staging, sizeof(double) * (P * (n + m) + wsItem) + (dunit ? sizeof(int) * P : 0), nItems);
     HIPCHK(g_sp_err, hipSetDevice(h->device));
-    const size_t vrows = v ? (size_t)count * ncols : 0;
+    const size_t vrows = (v && !dev) ? (size_t)count * ncols : 0;
     if (int rc = sb.reserve_rows(g_sp_err, h->mem, h->stream, count, std::max(vrows, chunk * P), n, n, m, m)) return rc;
     if (int rc = sb.reserve_ws(g_sp_err, h->mem, h->stream, chunk * wsItem + (dunit ? (chunk * P + 1) / 2 : 0))) return rc;
     int* const rowpos = dunit ? reinterpret_cast<int*>(sb.ws + chunk * wsItem) : nullptr;
     h->sn.sensPending = 0;
-    if (v) HIPCHK(g_sp_err, hipMemcpyAsync(sb.v, v, sizeof(double) * vrows * n, hipMemcpyHostToDevice, h->stream));
-    if (vy) {
+    h->sn.pendingMs = 0.f;
+    const double *dv = v, *dvy = vy;
+    if (v && !dev) {
+        HIPCHK(g_sp_err, hipMemcpyAsync(sb.v, v, sizeof(double) * vrows * n, hipMemcpyHostToDevice, h->stream));
+        dv = sb.v;
+    }
+    if (vy && !dev) {
         const size_t nvy = (size_t)count * ncols * m;
         if (int rc = grow(g_sp_err, h, h->sn.adjVy, h->sn.adjVyCap, nvy)) return rc;
         HIPCHK(g_sp_err, hipMemcpyAsync(h->sn.adjVy, vy, sizeof(double) * nvy, hipMemcpyHostToDevice, h->stream));
+        dvy = h->sn.adjVy;
     }
-    if (dunit) {
+    if (dunit && dev) {
+        HIPCHK(g_sp_err, hipMemsetAsync(dg, 0, sizeof(double) * (size_t)count * m * n, h->stream));
+        if (db) HIPCHK(g_sp_err, hipMemsetAsync(db, 0, sizeof(double) * (size_t)count * m * m, h->stream));
+    } else if (dunit) {
         std::memset(dg, 0, sizeof(double) * (size_t)count * m * n);
         if (db) std::memset(db, 0, sizeof(double) * (size_t)count * m * m);
     }
-    std::vector<int> rp(dunit ? chunk * P : 0);
+    std::vector<int> rp(dunit && !dev ? chunk * P : 0);
     HIPCHK(g_sp_err, hipMemsetAsync(sb.info, 0, sizeof(int) * (size_t)count, h->stream));
-    std::vector<double> hg(chunk * P * n), hb(db ? chunk * P * m : 0);
+    std::vector<double> hg(dev ? 0 : chunk * P * n), hb(db && !dev ? chunk * P * m : 0);
     float ms = 0.f;
     for (size_t i0 = 0; i0 < nItems; i0 += chunk) {
         const size_t ni = std::min(chunk, nItems - i0);
-        const SpSensBlkArgs a = {first, (int)npan, ncols, (v || dual) ? 0 : 1, (int)i0, (int)ni, v ? sb.v : nullptr, sb.dg, sb.db, sb.side, sb.info, sb.ws,
-                                 vy ? h->sn.adjVy : nullptr, dunit ? 1 : 0, rowpos};
+        const SpSensBlkArgs a = {first, (int)npan, ncols, (v || dual) ? 0 : 1, (int)i0, (int)ni, dv, sb.dg, sb.db, sb.side, sb.info, sb.ws,
+                                 dvy, dunit ? 1 : 0, rowpos};
+        if (dev && i0) if (int rc = chunk_time(g_sp_err, sb, ms)) return rc;      // (the events are about to be recorded again)
         if (int rc = timed_launch(g_sp_err, h->stream, sb.ev0, sb.ev1, [&] { launch(d, h->stream, a); })) return rc;
+        if (dev) {
+            if (int rc = sparse_scatter_panels(h, SpScatterArgs{(int)npan, ncols, dunit ? 1 : 0, (int)P, d.n, d.m, (int)i0, (int)ni, sb.dg, sb.db, rowpos, dg, db})) return rc;
+            continue;
+        }
         if (dunit) HIPCHK(g_sp_err, hipMemcpyAsync(rp.data(), rowpos, sizeof(int) * ni * P, hipMemcpyDeviceToHost, h->stream));
         HIPCHK(g_sp_err, hipMemcpyAsync(hg.data(), sb.dg, sizeof(double) * ni * P * n, hipMemcpyDeviceToHost, h->stream));
         if (db) HIPCHK(g_sp_err, hipMemcpyAsync(hb.data(), sb.db, sizeof(double) * ni * P * m, hipMemcpyDeviceToHost, h->stream));
@@ -527,23 +550,21 @@ static int sp_panel_run(lcqp_hip_sparse* h, int first, int count, int ncols, con
         float t = 0.f;
         HIPCHK(g_sp_err, hipEventElapsedTime(&t, sb.ev0, sb.ev1));
         ms += t;
-        for (size_t i = 0; i < ni; i++) {
-            const size_t item = i0 + i, ir = item / npan, c0 = (item % npan) * P, nc = std::min(P, (size_t)ncols - c0);
-            if (dunit) {      // staged column k is row rowpos[k] of the instance's blocks
-                for (size_t kk = 0; kk < P; kk++) {
-                    const int r = rp[i * P + kk];
-                    if (r < 0 || (size_t)r >= m) continue;
-                    std::memcpy(dg + (ir * m + r) * n, hg.data() + (i * P + kk) * n, sizeof(double) * n);
-                    if (db) std::memcpy(db + (ir * m + r) * m, hb.data() + (i * P + kk) * m, sizeof(double) * m);
-                }
-                continue;
-            }
-            std::memcpy(dg + (ir * ncols + c0) * n, hg.data() + i * P * n, sizeof(double) * nc * n);
-            if (db) std::memcpy(db + (ir * ncols + c0) * m, hb.data() + i * P * m, sizeof(double) * nc * m);
+        for (size_t c = 0; c < ni * P; c++) {
+            const long long row = sp_panel_dest_row((unsigned)(i0 + c / P), (unsigned)(c % P), (unsigned)npan, (unsigned)P, (unsigned)ncols, dunit ? 1 : 0, dunit ? rp[c] : 0);
+            if (row < 0) continue;
+            std::memcpy(dg + (size_t)row * n, hg.data() + c * n, sizeof(double) * n);
+            if (db) std::memcpy(db + (size_t)row * m, hb.data() + c * m, sizeof(double) * m);
         }
     }
-    if (side) HIPCHK(g_sp_err, hipMemcpyAsync(side, sb.side, sizeof(int) * (size_t)count * m, hipMemcpyDeviceToHost, h->stream));
-    if (info) HIPCHK(g_sp_err, hipMemcpyAsync(info, sb.info, sizeof(int) * (size_t)count, hipMemcpyDeviceToHost, h->stream));
+    const hipMemcpyKind out = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    if (side) HIPCHK(g_sp_err, hipMemcpyAsync(side, sb.side, sizeof(int) * (size_t)count * m, out, h->stream));
+    if (info) HIPCHK(g_sp_err, hipMemcpyAsync(info, sb.info, sizeof(int) * (size_t)count, out, h->stream));
+    if (dev) {
+        h->sn.sensPending = 1;
+        h->sn.pendingMs = ms;
+        return 0;
+    }
     HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));
     h->rs.sensMs = ms;
     return 0;
@@ -685,6 +706,63 @@ extern "C" int lcqp_hip_sparse_adjoint_device(lcqp_hip_sparse_t* h, const double
         if (int rc = sp_sensitivity(h, 1, vx, vy, true, dg, db, side, info, ms)) return rc;
         if (!(cq + ce)) return 0;
         return adjoint_device(g_sp_err, h, [&] { sp_launch_adjoint(h, dQx, cq, dAx, ce, reduce, 0, d.B); });
+    });
+}); }
+
+// ---- the device-pointer twins of the four panel calls (DESIGN.md section 3a''''', "The sparse arm: panels and Jacobians into device arrays"):
+// the host twins' checks in the host twins' order, the pointer checks, then sp_panel_run with dev between the two halves of the hand-over.
+// Without a panel form (the general LDL' before lcqp_hip_sparse_set_general_panel) the blocked calls are the vector kernel on the caller's
+// arrays (sp_sensitivity with dev), the Jacobians the host twins' results copied to the device (jacobian_through_host: these wait) ----
+extern "C" int lcqp_hip_sparse_sensitivity_blocked_device(lcqp_hip_sparse_t* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info, void* stream)
+{ return guarded(g_sp_err, [&] {
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    HIPCHK(g_sp_err, hipSetDevice(h->device));
+    if (!sens_pointers_ok(g_sp_err, h, h->db.m, (size_t)h->db.B * nrhs, v, "v", nullptr, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
+    return device_call(g_sp_err, h, stream, [&] {
+        float ms = 0.f;
+        if (!sp_panel(h)) return sp_sensitivity(h, nrhs, v, nullptr, true, dg, db, side, info, ms);
+        return sp_panel_run(h, 0, h->db.B, nrhs, v, dg, db, side, info, nullptr, false, true);
+    });
+}); }
+
+extern "C" int lcqp_hip_sparse_adjoint_blocked_device(lcqp_hip_sparse_t* h, int nrhs, const double* vx, const double* vy, double* dg, double* db,
+                                                      int* side, int* info, void* stream)
+{ return guarded(g_sp_err, [&] {
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (nrhs < 1 || (!vx && !vy) || !dg) return LCQP_INVALID_ARGUMENT;
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    HIPCHK(g_sp_err, hipSetDevice(h->device));
+    if (!sens_pointers_ok(g_sp_err, h, h->db.m, (size_t)h->db.B * nrhs, vx, "vx", vy, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
+    return device_call(g_sp_err, h, stream, [&] {
+        float ms = 0.f;
+        if (!sp_panel(h)) return sp_sensitivity(h, nrhs, vx, vy, true, dg, db, side, info, ms);      // (vy == NULL: the vector kernel of the blocked twin)
+        return sp_panel_run(h, 0, h->db.B, nrhs, vx, dg, db, side, info, vy, false, true);
+    });
+}); }
+
+extern "C" int lcqp_hip_sparse_jacobian_device(lcqp_hip_sparse_t* h, int first, int count, double* Jg, double* Jb, int* side, int* info, void* stream)
+{ return guarded(g_sp_err, [&] {
+    const size_t n = h ? h->db.n : 0, m = h ? h->db.m : 0;
+    if (int rc = jacobian_device_checks(g_sp_err, h, m, first, count, n, "Jg", Jg, "Jb", Jb, side, info)) return rc;
+    return device_call(g_sp_err, h, stream, [&] {
+        if (sp_panel(h)) return sp_panel_run(h, first, count, h->db.n, nullptr, Jg, Jb, side, info, nullptr, false, true);
+        return jacobian_through_host(g_sp_err, h, m, count, n, Jg, Jb, side, info, [&](double* G, double* Bd, int* sd, int* in) {
+            return lcqp_hip_sparse_jacobian(h, first, count, G, Bd, sd, in);
+        });
+    });
+}); }
+
+extern "C" int lcqp_hip_sparse_jacobian_duals_device(lcqp_hip_sparse_t* h, int first, int count, double* Jyg, double* Jyb, int* side, int* info, void* stream)
+{ return guarded(g_sp_err, [&] {
+    const size_t m = h ? h->db.m : 0;
+    if (int rc = jacobian_device_checks(g_sp_err, h, m, first, count, m, "Jyg", Jyg, "Jyb", Jyb, side, info)) return rc;
+    return device_call(g_sp_err, h, stream, [&] {
+        if (sp_panel(h)) return sp_panel_run(h, first, count, h->db.m, nullptr, Jyg, Jyb, side, info, nullptr, true, true);
+        return jacobian_through_host(g_sp_err, h, m, count, m, Jyg, Jyb, side, info, [&](double* G, double* Bd, int* sd, int* in) {
+            return lcqp_hip_sparse_jacobian_duals(h, first, count, G, Bd, sd, in);
+        });
     });
 }); }
 

@@ -357,6 +357,7 @@ class BatchLCQPLayer:
             xg, xb, side, info = self.bt.jacobian()
             yg, yb, _, _ = self.bt.jacobian_duals()
         self.info = info if not on_device else info.cpu().numpy()
+        self._info_as_returned = info      # (on the device path: the tensor, for a caller that wants it there)
         out = {k: torch.as_tensor(v, device=device).to(dtype) for k, v in dict(xg=xg, xb=xb, yg=yg, yb=yb).items()}
         out["side"] = torch.as_tensor(side, device=device)
         return out
@@ -415,11 +416,13 @@ class SparseBatchLCQPLayer(BatchLCQPLayer):
     def jacobian_full(self, serial=None):
         """The whole solution map D(x, y) / D(g, b_W) of the layer's last solve, the dict BatchLCQPLayer.jacobian(duals=True) returns: xg
         [B][nV][nV], xb [B][nV][m], yg [B][m][nV], yb [B][m][m] (SparseBatchLCQP.jacobian and .jacobian_duals: the arm's panel kernels on the
-        unit vectors, DESIGN.md section 3a''''), side [B][m], and info [B], as tensors of the dtype and on the device of that solve's g.  The
-        sparse arm has no device-pointer twins of the two calls: the host calls run (layer.last_path = "host").  serial: as jacobian."""
+        unit vectors, DESIGN.md section 3a''''), side [B][m], and info [B], as tensors of the dtype and on the device of that solve's g.  With
+        that g on the GPU of the batch the device-pointer twins run (SparseBatchLCQP.jacobian_device and .jacobian_duals_device: the staged
+        panels go to the six device tensors on the device, nothing passes through the host; layer.last_path = "device"), else the host calls
+        ("host").  serial: as jacobian."""
         self._last_solve(serial)
-        out = self._jacobian_blocks(device_twins=False)
-        out["info"] = torch.as_tensor(self.info, device=self._like[1])
+        out = self._jacobian_blocks(device_twins=True)
+        out["info"] = torch.as_tensor(self._info_as_returned, device=self._like[1])
         return out
 
     def _trailing(self, k):

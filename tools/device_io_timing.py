@@ -13,7 +13,13 @@ lcqpow_amd/synth_sparse.py at two shapes -- n = 4096, nC = 2048, nComp = 512 wit
 (--quick: B = 64 each) --, followed by the kernel times of the three pack kernels (HIP events on the torch stream around load_device and
 update_device; the check kernel and its status read are inside) and the bytes per second of k_sparse_pack_values.
 
-usage: python tools/device_io_timing.py [--sparse] [--quick] [--log FILE] [--reps 10] [--warmup 2]"""
+--sparse --blocked: the full solution map of the sparse arm instead -- jacobian() + jacobian_duals() (host arrays out) against jacobian_device()
++ jacobian_duals_device() (device tensors out, DESIGN.md section 3a''''', "The sparse arm: panels and Jacobians into device arrays") on one
+handle, the two pairs alternating call by call, at (512, 256, 64) with B = 64 and (64, 32, 8) with B = 1024 (--quick: B = 8 and 64) --, then
+the device pair's time on the stream by HIP events beside the kernel time of its panel launches: the difference is k_sparse_scatter_panels
+with the zero-fill of the dual blocks and the copies of side and info, given as a share of the pair and as bytes per second.
+
+usage: python tools/device_io_timing.py [--sparse [--blocked]] [--quick] [--log FILE] [--reps 10] [--warmup 2]"""
 import argparse
 import os
 import sys
@@ -115,10 +121,65 @@ def sparse_rows(say, args, shape, B):
     sb.close()
 
 
+def blocked_rows(say, args, shape, B):
+    from lcqpow_amd import synth_sparse as S
+    n, nC, nK = shape
+    m = nC + 2 * nK
+    Qpat, Apat, qo, eo = S.sparse_pattern_arrays(n, nC, nK)
+    sb = la.SparseBatchLCQP(B, n, nC, nK, Qpat, Apat, opt=la.default_options(perturbStep=0, printLevel=0))
+    inst = [S.sparse_values(i, n, nC, nK, orders=(qo, eo)) for i in range(B)]
+    h = {k: np.stack([d[k] for d in inst]) for k in ("Qx", "g", "Ex", "lbA", "ubA")}
+    del inst
+    assert sb.load(0, B, h["Qx"], h["g"], h["Ex"], lbA=h["lbA"], ubA=h["ubA"]) == 0
+    sb.run()
+    sb.synchronize()
+    say(f"sparse, banded workload: B = {B}, nV = {n}, nC = {nC}, nComp = {nK}, m = {m}, lanes = {sb.lanes()}, panel = {sb.sens_panel()}; the solution map is "
+        f"B (n + m)^2 = {8.0 * B * (n + m) ** 2 / 1e6:.0f} MB; {args.reps} alternating calls of each pair after {args.warmup}; wall clock, ms: min / median / max")
+    host_pair = lambda: (sb.jacobian(), sb.jacobian_duals())
+    device_pair = lambda: (sb.jacobian_device(), sb.jacobian_duals_device())
+    th, td = [], []
+    for k in range(args.warmup + args.reps):      # host, device, host, device, ...: what the machine does meanwhile hits both
+        for pair, ts in ((host_pair, th), (device_pair, td)):
+            th_, _, _ = timed(pair, 1, 0)
+            ts.append(th_)
+    th, td = np.array(th[args.warmup:]), np.array(td[args.warmup:])
+    verdict = "" if np.median(td) < np.median(th) else "    DEVICE MEDIAN NOT BELOW HOST"
+    say(f"  {'jacobian + jacobian_duals':<44s} host {th.min():9.2f} / {np.median(th):9.2f} / {th.max():9.2f}    device {td.min():9.2f} / {np.median(td):9.2f} / {td.max():9.2f}"
+        f"    median ratio {np.median(th) / np.median(td):7.1f}{verdict}")
+    # the same bits from both pairs
+    (hg, hb, hs, hi), (hyg, hyb, _, _) = host_pair()
+    (dg, db, ds, di), (dyg, dyb, _, _) = device_pair()
+    torch.cuda.synchronize()
+    for want, got in ((hg, dg), (hb, db), (hs, ds), (hi, di), (hyg, dyg), (hyb, dyb)):
+        assert want.tobytes() == got.cpu().numpy().tobytes()
+    rowsW = int(np.count_nonzero(hs))
+    del hg, hb, hyg, hyb, dg, db, dyg, dyb
+    # the device pair on the stream: HIP events around it; the panel kernels by the library's own events
+    ev, ker = [], []
+    for k in range(args.warmup + args.reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        e0.record(); device_pair(); e1.record()
+        torch.cuda.synchronize()
+        ev.append(e0.elapsed_time(e1))
+        sb.jacobian_device(); k1 = sb.sensitivity_kernel_ms()
+        sb.jacobian_duals_device(); ker.append(k1 + sb.sensitivity_kernel_ms())
+    ev, ker = np.array(ev[args.warmup:]), np.array(ker[args.warmup:])
+    rest = max(float(np.median(ev) - np.median(ker)), 1e-6)
+    copied = 8.0 * (n + m) * (B * n + rowsW)                 # doubles the scatter kernel reads once and writes once
+    filled = 8.0 * (n + m) * B * m                           # the zero-fill of Jyg and Jyb
+    say(f"  device pair on the stream, ms: HIP events {ev.min():.3f} / {np.median(ev):.3f} / {ev.max():.3f}; its panel kernels {ker.min():.3f} / {np.median(ker):.3f} / {ker.max():.3f}")
+    say(f"  the rest (k_sparse_scatter_panels + zero-fill of the dual blocks + side / info + launch gaps): {rest:.3f} ms = {100.0 * rest / np.median(ev):.1f} % of the pair; "
+        f"it reads {copied / 1e6:.0f} MB and writes {(copied + filled) / 1e6:.0f} MB: {(2 * copied + filled) / (rest * 1e-3) / 1e9:.0f} GB/s = "
+        f"{100.0 * (2 * copied + filled) / (rest * 1e-3) / HBM_PEAK:.1f} % of the HBM peak of {HBM_PEAK / 1e12:.1f} TB/s")
+    sb.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--sparse", action="store_true")
+    ap.add_argument("--blocked", action="store_true", help="with --sparse: jacobian() + jacobian_duals() against their device twins")
     ap.add_argument("--log")
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
@@ -137,6 +198,12 @@ def main():
             with open(args.log, "w") as f:
                 f.write("\n".join(lines) + "\n")
 
+    if args.sparse and args.blocked:
+        say("device_io_timing --sparse --blocked: the solution map of the sparse batch into host arrays and into device tensors, one handle per shape, one process")
+        for shape, Bs, Bq in (((512, 256, 64), 64, 8), ((64, 32, 8), 1024, 64)):
+            blocked_rows(say, args, shape, Bq if args.quick else Bs)
+            write_log()
+        return
     if args.sparse:
         say("device_io_timing --sparse: host entry points of the sparse batch against their device-pointer twins, one handle per shape, one process")
         for shape, Bs in (((4096, 2048, 512), 4096), ((512, 256, 64), 1024)):
