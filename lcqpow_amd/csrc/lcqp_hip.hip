@@ -1,7 +1,8 @@
 // lcqp_hip.hip -- the dense arm's batch: the process-wide entry points, the choice of launch table and build (dense_kernels, run_kernels)
-// and the C ABI of the batch handle, lcqp_hip_batch_* (gfx950 only; see include/lcqp_hip.h), with the two adjoint kernels that ABI
-// launches.  The QP object is lcqp_hip_qp.hip, the building blocks and CSC utilities lcqp_hip_util.hip; lcqp_hip_batch.hpp is what they share.
-// The sensitivity, Jacobian and adjoint entry points hand their kernels to the drivers of lcqp_sens_rt.hpp, which the sparse arm uses too.
+// and the life cycle of the batch handle in the C ABI lcqp_hip_batch_* (gfx950 only; see include/lcqp_hip.h): create, load, setup, run,
+// update, resolve and the readers.  Host code only, no kernel.  Differentiation -- the sensitivity, Jacobian and adjoint entry points, their
+// device-pointer twins and the two adjoint kernels -- is lcqp_hip_diff.hip; the QP object is lcqp_hip_qp.hip, the building blocks and CSC
+// utilities lcqp_hip_util.hip; lcqp_hip_batch.hpp is what the units share.
 #include "lcqp_hip_batch.hpp"
 
 #include <algorithm>
@@ -16,84 +17,6 @@
 using namespace lcqp;
 using namespace lcqp_rt;
 
-
-// =================================================================================================
-// device kernels: the per-size ones live in lcqp_kernels.hpp / lcqp_nch.hip; here only the two that are not templated and that the batch
-// ABI launches (the other four are in lcqp_hip_util.hip)
-// =================================================================================================
-// ---- the matrix gradients of an adjoint call (DESIGN.md section 3a'''', lcqp_hip_batch_adjoint) --------------------------------------
-// With dg, db, side and info of k_sensitivity (nrhs = 1, still in its device buffers) and the returned x, y, row r of the stacked gradient
-// [dQ; dA; dL; dR] ([nd][n]: r < n a row of Q, above it the entry of the dual layout the row of E belongs to) of instance b is
-//   s_r (alpha_r x_b + beta_r dg_b),   r < n: alpha = dg_r, beta = x_r, s = 1/2 (the symmetric derivative);
-//                                      r >= n: alpha = -db_r, beta = -y_r, s = 1 where side_r != 0, a zero row elsewhere;
-// zero for an instance with info & 1.  The two products are rounded separately and then added (no contraction): entry (i, j) of dQ forms the
-// products of entry (j, i) in the other order, so dQ is symmetric to the bit.  Both kernels read x, y and the four buffers, nothing else.
-struct AdjointArgs {
-    int B, n, np, nd, ldb;                 // ldb: pitch of db
-    const double *x, *y, *dg, *db;         // xout [B][n], yout [B][nd], dg [B][np], db [B][ldb]
-    const int *side, *info;                // [B][nd], [B]
-};
-// rows [r0, r0 + rows) of the stacked gradient go to out ([count][rows][n], or [rows][n] summed over the batch); null: not asked for
-struct AdjointSeg { double* out; int r0, rows; };
-struct AdjointSegs { AdjointSeg s[4]; };
-
-__device__ __forceinline__ double adjoint_term(const AdjointArgs& a, int b, int r, int j)
-{
-#pragma clang fp contract(off)
-    if (a.info[b] & 1) return 0.0;
-    const double xj = a.x[(size_t)b * a.n + j], dj = a.dg[(size_t)b * a.np + j];
-    if (r < a.n) return 0.5 * (a.dg[(size_t)b * a.np + r] * xj + a.x[(size_t)b * a.n + r] * dj);
-    if (a.side[(size_t)b * a.nd + r] == 0) return 0.0;
-    return -(a.db[(size_t)b * a.ldb + r] * xj + a.y[(size_t)b * a.nd + r] * dj);
-}
-
-// k_adjoint_outer: the gradients of the instances [first, first + count), one matrix per instance.  blockIdx.y: the segment; the threads
-// walk its count * rows * n doubles as one array, two neighbours each (one 16-byte store; the buffers start on 16-byte boundaries).
-__global__ __launch_bounds__(WG) void k_adjoint_outer(AdjointArgs a, AdjointSegs segs, int first, int count)
-{
-    const AdjointSeg sg = segs.s[blockIdx.y];
-    if (!sg.out) return;
-    const size_t per = (size_t)sg.rows * a.n, total = per * count;
-    for (size_t p = ((size_t)blockIdx.x * WG + threadIdx.x) * 2; p < total; p += (size_t)gridDim.x * WG * 2) {
-        double v[2] = {0.0, 0.0};
-        for (int e = 0; e < 2; e++) {
-            const size_t f = p + e;
-            if (f >= total) break;
-            const size_t o = f / per, rem = f - o * per;
-            const int r = (int)(rem / a.n), j = (int)(rem - (size_t)r * a.n);
-            v[e] = adjoint_term(a, first + (int)o, sg.r0 + r, j);
-        }
-        if (p + 1 < total) *reinterpret_cast<double2*>(sg.out + p) = double2{v[0], v[1]};
-        else sg.out[p] = v[0];
-    }
-}
-
-// k_adjoint_reduce: the same gradients summed over the batch (one Q / A / L / R shared by the instances).  A thread owns two neighbouring
-// entries and adds the instances' terms -- the very values k_adjoint_outer writes -- in the order of the batch: no atomics, the same bits
-// on every call, and the rounding error of a sum of B numbers, (B - 1) eps/2 sum_b |term_b|.  (A product [alpha' beta'] [X; DG] on the fp64
-// matrix cores would round against the partial sums of alpha x and beta dg separately, which cancel inside a term: no bound in the terms.)
-__global__ __launch_bounds__(WG) void k_adjoint_reduce(AdjointArgs a, AdjointSegs segs)
-{
-    const AdjointSeg sg = segs.s[blockIdx.y];
-    if (!sg.out) return;
-    const size_t total = (size_t)sg.rows * a.n;
-    for (size_t p = ((size_t)blockIdx.x * WG + threadIdx.x) * 2; p < total; p += (size_t)gridDim.x * WG * 2) {
-        const bool two = p + 1 < total;
-        const int r0 = (int)(p / a.n), j0 = (int)(p - (size_t)r0 * a.n);
-        const int r1 = two ? (int)((p + 1) / a.n) : r0, j1 = two ? (int)(p + 1 - (size_t)r1 * a.n) : j0;
-        double s0 = 0.0, s1 = 0.0;
-        for (int b = 0; b < a.B; b++) {
-            s0 += adjoint_term(a, b, sg.r0 + r0, j0);
-            s1 += adjoint_term(a, b, sg.r0 + r1, j1);
-        }
-        if (two) *reinterpret_cast<double2*>(sg.out + p) = double2{s0, s1};
-        else sg.out[p] = s0;
-    }
-}
-
-// =================================================================================================
-// host side
-// =================================================================================================
 // HIP maps the streams of a process onto a few hardware queues -- 4 unless GPU_MAX_HW_QUEUES says otherwise -- and every batch object has
 // two streams: a process that keeps three batch objects alive can find both slots of a BatchPipeline on ONE queue, and its batches then
 // run one after the other (tools/micro/pipeline_check.py: 35 200 LCQPs/s with two objects alive, 30 750 with an idle third one, 34 800
@@ -111,7 +34,7 @@ extern "C" int lcqp_hip_request_hw_queues(int n)
 }
 
 static thread_local std::string g_err;      // the dense, QP, util and CSC entry points (lcqp_host_rt.hpp: HIPCHK(g_err, ...))
-std::string& dense_err() { return g_err; }  // the slot for lcqp_hip_qp.hip and lcqp_hip_util.hip
+std::string& dense_err() { return g_err; }  // the slot for the other units of the arm
 
 extern "C" const char* lcqp_hip_last_error(void) { return g_err.c_str(); }
 extern "C" int lcqp_hip_device_count(void)
@@ -560,375 +483,4 @@ extern "C" int lcqp_hip_batch_read_working_set(lcqp_hip_batch_t* h, int b, int d
     if (!rc) rc = read_back(g_err, row_slot, d.mi + ib * I_NUM * d.mEcap + (size_t)I_SLOT * d.mEcap, (size_t)info.mE);
     if (!rc) rc = read_back(g_err, Ti, d.S + ib * capS * capS, capS * capS);
     return rc;
-}); }
-
-// ---- solution sensitivities (DESIGN.md sections 3a' and 3a'''): k_sensitivity on the whole batch, k_sensitivity_blk (np <= 512) on a range ----
-// One launch through sensitivity_call (lcqp_sens_rt.hpp: host or device arrays in and out, the kernel time added to ms or left in the
-// events).  blk: k_sensitivity_blk on the instances [first, first + count), on buffers of its own (the two kernels fix different pitches of
-// db); v == nullptr: unit vectors, nothing uploaded.  Otherwise k_sensitivity -- with vy its DUAL instantiation --, which has no instance
-// offset: first = 0, count = B.
-static int dense_sensitivity(lcqp_hip_batch* h, bool blk, int first, int count, int nrhs, const double* v, const double* vy, bool dev,
-                             double* dg, double* db, int* side, int* info, float& ms)
-{
-    DevBatch& d = h->db;
-    // (ldV is the same for a Jacobian and a blocked call so that the rows reserved by one serve the other: a Jacobian's rows carry an unused v)
-    const SensPitch p = {(size_t)d.n, (size_t)d.np, (size_t)d.nd + (blk ? 2 : 1) * (size_t)d.capS, (size_t)d.nd};
-    return sensitivity_call(g_err, h, blk ? h->sensBlk : h->sn.sens, p, count, nrhs, v, vy, dev, blk ? 2 : 1, dg, db, side, info, ms,
-                            [&](const double* dv, const double* dvy, SensBuffers& sb) {
-        if (blk) h->k->sensitivity_blk(d, count, h->stream, first, nrhs, dv, sb.dg, sb.db, sb.side, sb.info);
-        else if (vy) h->k->sensitivity_dual(d, count, h->stream, nrhs, dv, dvy, sb.dg, sb.db, sb.side, sb.info);
-        else h->k->sensitivity(d, count, h->stream, nrhs, dv, sb.dg, sb.db, sb.side, sb.info);
-    });
-}
-
-// blk: the blocked kernel where the padded size has one, the vector kernel and its bits above
-int batch_sensitivity(lcqp_hip_batch* h, bool blk, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
-{
-    float ms = 0.f;
-    if (int rc = dense_sensitivity(h, blk && h->k->sensitivity_blk, 0, h->db.B, nrhs, v, nullptr, false, dg, db, side, info, ms)) return rc;
-    h->rs.sensMs = ms;
-    return 0;
-}
-
-extern "C" int lcqp_hip_batch_sensitivity(lcqp_hip_batch_t* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
-{ return guarded(g_err, [&] {
-    if (!h || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
-    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return batch_sensitivity(h, false, nrhs, v, dg, db, side, info);
-}); }
-
-// Jg [count][n][n], Jb [count][n][nd] (or NULL), side [count][nd], info [count] of the instances [first, first + count)
-int batch_jacobian(lcqp_hip_batch* h, int first, int count, double* Jg, double* Jb, int* side, int* info)
-{
-    DevBatch& d = h->db;
-    const size_t n = d.n, nd = d.nd;
-    // no blocked kernel (np >= 1024): k_sensitivity on an uploaded identity (these sizes are the single-large-problem ones, B small)
-    if (!h->k->sensitivity_blk)
-        return jacobian_by_vectors(h, sizeof(double) * (size_t)d.B * (n + (size_t)d.np + nd + (size_t)d.capS), nd, first, count, Jg, Jb, side, info,
-                                   [&](int nc, const double* v, double* dg, double* db, int* sd, int* in, float& ms) {
-            return dense_sensitivity(h, false, 0, d.B, nc, v, nullptr, false, dg, db, sd, in, ms);
-        });
-    // chunks of instances whose staging (n rows of v, dg and db each) stays below the cap; one launch and one download per chunk
-    const size_t chunk = staging_chunk(h->sn.staging, sizeof(double) * n * (n + (size_t)d.np + nd + 2 * (size_t)d.capS), count);
-    float total = 0.f;
-    for (size_t c0 = 0; c0 < (size_t)count; c0 += chunk) {
-        const size_t cb = std::min(chunk, (size_t)count - c0);
-        if (int rc = dense_sensitivity(h, true, first + (int)c0, (int)cb, d.n, nullptr, nullptr, false, Jg + c0 * n * n, Jb ? Jb + c0 * n * nd : nullptr,
-                                       side ? side + c0 * nd : nullptr, info ? info + c0 : nullptr, total)) return rc;
-    }
-    h->rs.sensMs = total;
-    return 0;
-}
-
-extern "C" int lcqp_hip_batch_sensitivity_blocked(lcqp_hip_batch_t* h, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
-{ return guarded(g_err, [&] {
-    if (!h || nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
-    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return batch_sensitivity(h, true, nrhs, v, dg, db, side, info);
-}); }
-
-extern "C" int lcqp_hip_batch_jacobian(lcqp_hip_batch_t* h, int first, int count, double* Jg, double* Jb, int* side, int* info)
-{ return guarded(g_err, [&] {
-    if (!h || !Jg || first < 0 || count < 1 || first > h->db.B - count) return LCQP_INVALID_ARGUMENT;
-    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return batch_jacobian(h, first, count, Jg, Jb, side, info);
-}); }
-
-extern "C" int lcqp_hip_batch_set_jacobian_staging(lcqp_hip_batch_t* h, size_t bytes)
-{
-    return guarded(g_err, [&] { return set_staging(h, bytes); });
-}
-
-extern "C" int lcqp_hip_batch_sensitivity_timing(lcqp_hip_batch_t* h, float* kernel_ms)
-{
-    return guarded(g_err, [&] { return sensitivity_timing(g_err, h, kernel_ms, h ? &h->sensBlk : nullptr, h ? &h->sensDual : nullptr); });
-}
-
-// ---- the full adjoint (DESIGN.md section 3a''''): upstream gradients on x and y, gradients in g, the bounds and the matrices ----
-// k_sensitivity (with vy: its DUAL instantiation) on the whole batch, its results to the host (the device twin: to the caller's device
-// arrays); then, on the device buffers it left, the matrix gradients that were asked for.
-// the four segments of the stacked gradient as the caller asked for them (a segment without rows is not asked for)
-struct AdjointWanted { double* out[4]; int r0[4], rows[4]; };
-static AdjointWanted adjoint_wanted(const DevBatch& d, double* dQ, double* dA, double* dL, double* dR)
-{
-    return {{dQ, d.nC ? dA : nullptr, d.nComp ? dL : nullptr, d.nComp ? dR : nullptr}, {0, d.n, d.n + d.nC, d.n + d.nC + d.nComp}, {d.n, d.nC, d.nComp, d.nComp}};
-}
-// k_adjoint_reduce, or k_adjoint_outer on the instances [first, first + count); most: the doubles of the largest segment
-static void launch_adjoint(lcqp_hip_batch* h, const AdjointSegs& segs, size_t most, int reduce, int first, int count)
-{
-    const DevBatch& d = h->db;
-    const SensBuffers& sb = h->sn.sens;
-    const AdjointArgs a = {d.B, d.n, d.np, d.nd, (int)sb.ldDb, d.xout, d.yout, sb.dg, sb.db, sb.side, sb.info};
-    const unsigned gx = (unsigned)std::min<size_t>((most + 2 * WG - 1) / (2 * WG), 65535);
-    if (reduce) hipLaunchKernelGGL(k_adjoint_reduce, dim3(gx, 4), dim3(WG), 0, h->stream, a, segs);
-    else hipLaunchKernelGGL(k_adjoint_outer, dim3(gx, 4), dim3(WG), 0, h->stream, a, segs, first, count);
-}
-
-// the host call: k_adjoint_reduce once, or k_adjoint_outer per chunk of instances under the Jacobian staging cap (adjoint_chunks)
-int batch_adjoint(lcqp_hip_batch* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
-                  int reduce, double* dQ, double* dA, double* dL, double* dR)
-{
-    DevBatch& d = h->db;
-    float ms = 0.f;
-    if (int rc = dense_sensitivity(h, false, 0, d.B, 1, vx, vy, false, dg, db, side, info, ms)) return rc;
-    const size_t n = d.n;
-    const AdjointWanted w = adjoint_wanted(d, dQ, dA, dL, dR);
-    size_t perInst = 0;      // doubles of one instance's gradients
-    for (int k = 0; k < 4; k++) if (w.out[k]) perInst += (size_t)w.rows[k] * n;
-    if (perInst)      // (+ 4: every segment starts on an even offset)
-        if (int rc = adjoint_chunks(g_err, h, perInst, 4, reduce, ms, [&](size_t c0, size_t cb, AdjCopy* cp) {
-            AdjointSegs segs{};
-            size_t off = 0, most = 0;
-            int ncp = 0;
-            for (int k = 0; k < 4; k++) {
-                if (!w.out[k]) continue;
-                const size_t cnt = cb * w.rows[k] * n;
-                segs.s[k] = {h->sn.adjOut + off, w.r0[k], w.rows[k]};
-                cp[ncp++] = {w.out[k] + c0 * w.rows[k] * n, segs.s[k].out, cnt};
-                off += cnt + (cnt & 1);
-                most = std::max(most, cnt);
-            }
-            launch_adjoint(h, segs, most, reduce, (int)c0, (int)cb);
-            return ncp;
-        })) return rc;
-    h->rs.sensMs = ms;
-    return 0;
-}
-
-extern "C" int lcqp_hip_batch_adjoint(lcqp_hip_batch_t* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
-                                      int reduce, double* dQ, double* dA, double* dL, double* dR)
-{ return guarded(g_err, [&] {
-    if (!h || !vx || !dg || (reduce != 0 && reduce != 1)) return LCQP_INVALID_ARGUMENT;
-    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return batch_adjoint(h, vx, vy, dg, db, side, info, reduce, dQ, dA, dL, dR);
-}); }
-
-// ---- the device-pointer twins of the three calls above (include/lcqp_hip.h; load, update and get_solution are in lcqp_hip_device.hip) ----
-extern "C" int lcqp_hip_batch_sensitivity_device(lcqp_hip_batch_t* h, int blocked, int nrhs, const double* v, double* dg, double* db,
-                                                 int* side, int* info, void* stream)
-{ return guarded(g_err, [&] {
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    if (nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
-    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    HIPCHK(g_err, hipSetDevice(h->device));
-    if (!sens_pointers_ok(g_err, h, h->db.nd, (size_t)h->db.B * nrhs, v, "v", nullptr, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
-    return device_call(g_err, h, stream, [&] {
-        float ms = 0.f;
-        return dense_sensitivity(h, blocked && h->k->sensitivity_blk, 0, h->db.B, nrhs, v, nullptr, true, dg, db, side, info, ms);
-    });
-}); }
-
-// k_sensitivity as batch_adjoint launches it, then ONE launch of k_adjoint_outer / k_adjoint_reduce that writes the caller's arrays: no
-// staging buffer, no chunks
-extern "C" int lcqp_hip_batch_adjoint_device(lcqp_hip_batch_t* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
-                                             int reduce, double* dQ, double* dA, double* dL, double* dR, void* stream)
-{ return guarded(g_err, [&] {
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    if (!vx || !dg || (reduce != 0 && reduce != 1)) return LCQP_INVALID_ARGUMENT;
-    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    HIPCHK(g_err, hipSetDevice(h->device));
-    const DevBatch& d = h->db;
-    if (!sens_pointers_ok(g_err, h, d.nd, d.B, vx, "vx", vy, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
-    const size_t lead = sizeof(double) * (reduce ? (size_t)1 : (size_t)d.B) * d.n;
-    if (!device_pointer_ok(g_err, h, "dQ", dQ, lead * d.n, 16) || !device_pointer_ok(g_err, h, "dA", dA, lead * d.nC, 16) ||
-        !device_pointer_ok(g_err, h, "dL", dL, lead * d.nComp, 16) || !device_pointer_ok(g_err, h, "dR", dR, lead * d.nComp, 16)) return LCQP_INVALID_ARGUMENT;
-    return device_call(g_err, h, stream, [&] {
-        float ms = 0.f;
-        if (int rc = dense_sensitivity(h, false, 0, d.B, 1, vx, vy, true, dg, db, side, info, ms)) return rc;
-        const AdjointWanted w = adjoint_wanted(d, dQ, dA, dL, dR);
-        AdjointSegs segs{};
-        size_t most = 0;
-        for (int k = 0; k < 4; k++) {
-            if (!w.out[k]) continue;
-            segs.s[k] = {w.out[k], w.r0[k], w.rows[k]};
-            most = std::max(most, (reduce ? (size_t)1 : (size_t)d.B) * w.rows[k] * d.n);
-        }
-        if (!most) return 0;
-        return adjoint_device(g_err, h, [&] { launch_adjoint(h, segs, most, reduce, 0, d.B); });
-    });
-}); }
-
-// ---- panels with gradients on y, the dual rows of the Jacobian (DESIGN.md section 3a'''', "Panels with gradients on y") ----
-// k_sensitivity_blk_dual on the whole batch through sensitivity_call, on the buffers and pitches of the blocked kernel.  vy == nullptr:
-// the blocked sensitivity call itself.  No blocked kernel (np >= 1024): k_sensitivity<NCH, true>, an absent vx as a zero panel.
-static int dense_adjoint_blocked(lcqp_hip_batch* h, int nrhs, const double* vx, const double* vy, bool dev,
-                                 double* dg, double* db, int* side, int* info, float& ms)
-{
-    DevBatch& d = h->db;
-    if (!vy) return dense_sensitivity(h, h->k->sensitivity_blk != nullptr, 0, d.B, nrhs, vx, nullptr, dev, dg, db, side, info, ms);
-    const bool blk = h->k->sensitivity_blk_dual != nullptr;
-    const SensPitch p = {(size_t)d.n, (size_t)d.np, (size_t)d.nd + (blk ? 2 : 1) * (size_t)d.capS, (size_t)d.nd};
-    std::vector<double> zeros;
-    if (!blk && !vx && !dev) { zeros.assign((size_t)d.B * nrhs * d.n, 0.0); vx = zeros.data(); }
-    hipError_t filled = hipSuccess;
-    if (int rc = sensitivity_call(g_err, h, blk ? h->sensBlk : h->sn.sens, p, d.B, nrhs, vx, vy, dev, blk ? 2 : 1, dg, db, side, info, ms,
-                                  [&](const double* dv, const double* dvy, SensBuffers& sb) {
-        if (blk) { h->k->sensitivity_blk_dual(d, d.B, h->stream, 0, nrhs, dv, dvy, 0, sb.dg, sb.db, sb.side, sb.info, nullptr); return; }
-        if (!dv) { filled = hipMemsetAsync(sb.v, 0, sizeof(double) * sb.rows * d.n, h->stream); dv = sb.v; }      // (the device twin without vx)
-        h->k->sensitivity_dual(d, d.B, h->stream, nrhs, dv, dvy, sb.dg, sb.db, sb.side, sb.info);
-    })) return rc;
-    HIPCHK(g_err, filled);
-    return 0;
-}
-
-int batch_adjoint_blocked(lcqp_hip_batch* h, int nrhs, const double* vx, const double* vy, double* dg, double* db, int* side, int* info)
-{
-    float ms = 0.f;
-    if (int rc = dense_adjoint_blocked(h, nrhs, vx, vy, false, dg, db, side, info, ms)) return rc;
-    h->rs.sensMs = ms;
-    return 0;
-}
-
-extern "C" int lcqp_hip_batch_adjoint_blocked(lcqp_hip_batch_t* h, int nrhs, const double* vx, const double* vy, double* dg, double* db, int* side, int* info)
-{ return guarded(g_err, [&] {
-    if (!h || nrhs < 1 || (!vx && !vy) || !dg) return LCQP_INVALID_ARGUMENT;
-    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return batch_adjoint_blocked(h, nrhs, vx, vy, dg, db, side, info);
-}); }
-
-// One launch of k_sensitivity_blk_dual on the unit vectors of the slot space of the instances [first, first + count), on sensDual:
-// capS staged rows per instance (row j: the j-th occupied slot), no v, and behind the `count` rows of `side` the map [count][capS] from
-// staged row to dual position (-1: no such slot).  dual_rowpos: where that map lies.
-static int* dual_rowpos(lcqp_hip_batch* h, int count) { return h->sensDual.side + (size_t)count * h->db.nd; }
-static int dual_jacobian_launch(lcqp_hip_batch* h, int first, int count)
-{
-    DevBatch& d = h->db;
-    SensBuffers& sb = h->sensDual;
-    HIPCHK(g_err, hipSetDevice(h->device));
-    if (int rc = sb.reserve(g_err, h->mem, h->stream, count, d.capS, 0, d.np, (size_t)d.nd + 2 * (size_t)d.capS, (size_t)d.nd + d.capS)) return rc;
-    h->sn.sensPending = 0;
-    h->sn.pendingMs = 0.f;
-    return timed_launch(g_err, h->stream, sb.ev0, sb.ev1, [&] {
-        h->k->sensitivity_blk_dual(d, count, h->stream, first, d.capS, nullptr, nullptr, 1, sb.dg, sb.db, sb.side, sb.info, dual_rowpos(h, count));
-    });
-}
-// the staging of one instance of such a launch, in bytes
-static size_t dual_jacobian_staging(const DevBatch& d)
-{
-    return sizeof(double) * (size_t)d.capS * ((size_t)d.np + d.nd + 2 * (size_t)d.capS) + sizeof(int) * (size_t)d.capS;
-}
-
-// np >= 1024: k_sensitivity<NCH, true> with vx = 0 and vy = the unit vectors of the dual positions that are in W for some instance of the
-// range, uploaded in chunks of vectors under the cap, on the whole batch (the vector kernel has no instance offset)
-static int jacobian_duals_by_vectors(lcqp_hip_batch* h, int first, int count, double* Jyg, double* Jyb, int* side, int* info)
-{
-    DevBatch& d = h->db;
-    const size_t B = d.B, n = d.n, nd = d.nd;
-    std::vector<double> zero(B * n, 0.0);
-    return lcqp_rt::jacobian_duals_by_vectors(h, sizeof(double) * B * (n + (size_t)d.np + 2 * nd + (size_t)d.capS), nd, first, count, Jyg, Jyb, side, info,
-                                              [&](int nc, const double* VY, double* G, double* Bd, int* sd, int* in, float& ms) {
-        if (!VY) return dense_sensitivity(h, false, 0, d.B, 1, zero.data(), nullptr, false, G, nullptr, sd, in, ms);
-        return dense_adjoint_blocked(h, nc, nullptr, VY, false, G, Bd, sd, in, ms);
-    });
-}
-
-// Jyg [count][nd][n], Jyb [count][nd][nd] (or NULL), side [count][nd], info [count] of the instances [first, first + count)
-int batch_jacobian_duals(lcqp_hip_batch* h, int first, int count, double* Jyg, double* Jyb, int* side, int* info)
-{
-    DevBatch& d = h->db;
-    const size_t n = d.n, nd = d.nd, capS = d.capS;
-    std::memset(Jyg, 0, sizeof(double) * (size_t)count * nd * n);
-    if (Jyb) std::memset(Jyb, 0, sizeof(double) * (size_t)count * nd * nd);
-    if (!h->k->sensitivity_blk_dual) return jacobian_duals_by_vectors(h, first, count, Jyg, Jyb, side, info);
-    // chunks of instances whose staging stays below the cap; one launch and one download per chunk, the rows scattered on the host
-    const size_t chunk = staging_chunk(h->sn.staging, dual_jacobian_staging(d), count);
-    std::vector<double> G(chunk * capS * n), Bd(Jyb ? chunk * capS * nd : 0);
-    std::vector<int> rp(chunk * capS);
-    float total = 0.f;
-    for (size_t c0 = 0; c0 < (size_t)count; c0 += chunk) {
-        const size_t cb = std::min(chunk, (size_t)count - c0);
-        if (int rc = dual_jacobian_launch(h, first + (int)c0, (int)cb)) return rc;
-        SensBuffers& sb = h->sensDual;
-        HIPCHK(g_err, hipMemcpyAsync(rp.data(), dual_rowpos(h, (int)cb), sizeof(int) * cb * capS, hipMemcpyDeviceToHost, h->stream));
-        if (int rc = sb.rows_out(g_err, G.data(), sb.dg, n, sb.ldDg)) return rc;
-        if (Jyb) if (int rc = sb.rows_out(g_err, Bd.data(), sb.db, nd, sb.ldDb)) return rc;
-        if (side) HIPCHK(g_err, hipMemcpyAsync(side + c0 * nd, sb.side, sizeof(int) * cb * nd, hipMemcpyDeviceToHost, h->stream));
-        if (info) HIPCHK(g_err, hipMemcpyAsync(info + c0, sb.info, sizeof(int) * cb, hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(g_err, hipStreamSynchronize(h->stream));
-        float t = 0.f;
-        HIPCHK(g_err, hipEventElapsedTime(&t, sb.ev0, sb.ev1));
-        total += t;
-        for (size_t o = 0; o < cb; o++)
-            for (size_t j = 0; j < capS; j++) {
-                const int r = rp[o * capS + j];
-                if (r < 0 || (size_t)r >= nd) continue;
-                std::memcpy(Jyg + ((c0 + o) * nd + r) * n, G.data() + (o * capS + j) * n, sizeof(double) * n);
-                if (Jyb) std::memcpy(Jyb + ((c0 + o) * nd + r) * nd, Bd.data() + (o * capS + j) * nd, sizeof(double) * nd);
-            }
-    }
-    h->rs.sensMs = total;
-    return 0;
-}
-
-extern "C" int lcqp_hip_batch_jacobian_duals(lcqp_hip_batch_t* h, int first, int count, double* Jyg, double* Jyb, int* side, int* info)
-{ return guarded(g_err, [&] {
-    if (!h || !Jyg || first < 0 || count < 1 || first > h->db.B - count) return LCQP_INVALID_ARGUMENT;
-    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return batch_jacobian_duals(h, first, count, Jyg, Jyb, side, info);
-}); }
-
-// ---- their device-pointer twins, and lcqp_hip_batch_jacobian's ----
-extern "C" int lcqp_hip_batch_adjoint_blocked_device(lcqp_hip_batch_t* h, int nrhs, const double* vx, const double* vy,
-                                                     double* dg, double* db, int* side, int* info, void* stream)
-{ return guarded(g_err, [&] {
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
-    if (nrhs < 1 || (!vx && !vy) || !dg) return LCQP_INVALID_ARGUMENT;
-    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    HIPCHK(g_err, hipSetDevice(h->device));
-    if (!sens_pointers_ok(g_err, h, h->db.nd, (size_t)h->db.B * nrhs, vx, "vx", vy, dg, db, side, info)) return LCQP_INVALID_ARGUMENT;
-    return device_call(g_err, h, stream, [&] {
-        float ms = 0.f;
-        return dense_adjoint_blocked(h, nrhs, vx, vy, true, dg, db, side, info, ms);
-    });
-}); }
-
-extern "C" int lcqp_hip_batch_jacobian_device(lcqp_hip_batch_t* h, int first, int count, double* Jg, double* Jb, int* side, int* info, void* stream)
-{ return guarded(g_err, [&] {
-    if (int rc = jacobian_device_checks(g_err, h, h ? h->db.nd : 0, first, count, h ? h->db.n : 0, "Jg", Jg, "Jb", Jb, side, info)) return rc;
-    DevBatch& d = h->db;
-    const size_t n = d.n, nd = d.nd;
-    return device_call(g_err, h, stream, [&] {
-        if (!h->k->sensitivity_blk)
-            return jacobian_through_host(g_err, h, nd, count, n, Jg, Jb, side, info, [&](double* G, double* Bd, int* sd, int* in) { return batch_jacobian(h, first, count, G, Bd, sd, in); });
-        // the chunks of batch_jacobian; every chunk's results go from the staging to their place with copies on the handle's stream
-        const size_t chunk = staging_chunk(h->sn.staging, sizeof(double) * n * (n + (size_t)d.np + nd + 2 * (size_t)d.capS), count);
-        float ms = 0.f, before = 0.f;      // before: the kernel time of the chunks in front of the last one (chunk_time)
-        for (size_t c0 = 0; c0 < (size_t)count; c0 += chunk) {
-            const size_t cb = std::min(chunk, (size_t)count - c0);
-            if (c0) if (int rc = chunk_time(g_err, h->sensBlk, before)) return rc;
-            if (int rc = dense_sensitivity(h, true, first + (int)c0, (int)cb, d.n, nullptr, nullptr, true, Jg + c0 * n * n, Jb ? Jb + c0 * n * nd : nullptr,
-                                           side ? side + c0 * nd : nullptr, info ? info + c0 : nullptr, ms)) return rc;
-        }
-        h->sn.pendingMs = before;
-        return 0;
-    });
-}); }
-
-extern "C" int lcqp_hip_batch_jacobian_duals_device(lcqp_hip_batch_t* h, int first, int count, double* Jyg, double* Jyb, int* side, int* info, void* stream)
-{ return guarded(g_err, [&] {
-    if (int rc = jacobian_device_checks(g_err, h, h ? h->db.nd : 0, first, count, h ? h->db.nd : 0, "Jyg", Jyg, "Jyb", Jyb, side, info)) return rc;
-    DevBatch& d = h->db;
-    const size_t n = d.n, nd = d.nd;
-    return device_call(g_err, h, stream, [&] {
-        if (!h->k->sensitivity_blk_dual)
-            return jacobian_through_host(g_err, h, nd, count, nd, Jyg, Jyb, side, info, [&](double* G, double* Bd, int* sd, int* in) { return batch_jacobian_duals(h, first, count, G, Bd, sd, in); });
-        // the rows k_pack_dual_rows does not write (outside W) are zero
-        HIPCHK(g_err, hipMemsetAsync(Jyg, 0, sizeof(double) * (size_t)count * nd * n, h->stream));
-        if (Jyb) HIPCHK(g_err, hipMemsetAsync(Jyb, 0, sizeof(double) * (size_t)count * nd * nd, h->stream));
-        const size_t chunk = staging_chunk(h->sn.staging, dual_jacobian_staging(d), count);
-        float before = 0.f;      // the kernel time of the chunks in front of the last one (chunk_time)
-        for (size_t c0 = 0; c0 < (size_t)count; c0 += chunk) {
-            const size_t cb = std::min(chunk, (size_t)count - c0);
-            if (c0) if (int rc = chunk_time(g_err, h->sensDual, before)) return rc;
-            if (int rc = dual_jacobian_launch(h, first + (int)c0, (int)cb)) return rc;
-            const SensBuffers& sb = h->sensDual;
-            launch_pack_dual_rows(d, h->stream, (int)cb, (int)sb.ldDb, sb.dg, sb.db, dual_rowpos(h, (int)cb), Jyg + c0 * nd * n, Jyb ? Jyb + c0 * nd * nd : nullptr);
-            HIPCHK(g_err, hipGetLastError());
-            if (side) HIPCHK(g_err, hipMemcpyAsync(side + c0 * nd, sb.side, sizeof(int) * cb * nd, hipMemcpyDeviceToDevice, h->stream));
-            if (info) HIPCHK(g_err, hipMemcpyAsync(info + c0, sb.info, sizeof(int) * cb, hipMemcpyDeviceToDevice, h->stream));
-        }
-        h->sn.sensPending = 3;
-        h->sn.pendingMs = before;
-        return 0;
-    });
 }); }

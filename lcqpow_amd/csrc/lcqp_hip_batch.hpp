@@ -1,5 +1,6 @@
-// lcqp_hip_batch.hpp -- what the three host units of the dense arm share: the batch handle behind lcqp_hip_batch_t, the functions of
-// lcqp_hip.hip that the QP object (lcqp_hip_qp.hip) and the building blocks (lcqp_hip_util.hip) call on it, and the arm's error slot.  The
+// lcqp_hip_batch.hpp -- what the five host units of the dense arm share: the batch handle behind lcqp_hip_batch_t, the functions of
+// lcqp_hip.hip (the batch's life cycle) and lcqp_hip_diff.hip (differentiation) that the QP object (lcqp_hip_qp.hip) and the building
+// blocks (lcqp_hip_util.hip) call on it, what lcqp_hip_device.hip gives them, and the arm's error slot.  The
 // host code the handle shares with the sparse arm's comes in with lcqp_host_rt.hpp and lcqp_sens_rt.hpp.
 // Internal: nothing of it enters the dynamic symbol table of the library.  Host code only.
 #pragma once
@@ -11,7 +12,7 @@
 
 #pragma GCC visibility push(hidden)
 
-// the error slot of the dense arm (one thread_local string, defined in lcqp_hip.hip): what lcqp_hip_last_error returns for all three units
+// the error slot of the dense arm (one thread_local string, defined in lcqp_hip.hip): what lcqp_hip_last_error returns for all five units
 std::string& dense_err();
 
 // The members are released in reverse order after the destructor's synchronisation: device memory, staging slots, events, streams.
@@ -41,6 +42,7 @@ struct lcqp_hip_batch {
     int nch;
     const lcqp::SizeKernels* k = nullptr; // the launch table of the padded size (dense_kernels), set by lcqp_hip_batch_create
     explicit lcqp_hip_batch(int dev) : db(), device(dev) {}
+    size_t ndual() const { return (size_t)db.nd; }      // the width of the dual vector (lcqp_sens_rt.hpp)
     ~lcqp_hip_batch() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
 };
 
@@ -51,13 +53,13 @@ inline int padded_nch(int n) { const int k = (n + 127) / 128; return k > 16 ? 32
 const lcqp::SizeKernels* dense_kernels(int nch);
 const lcqp::RunKernels& run_kernels(const lcqp_hip_batch* h);
 int launch_setup(lcqp_hip_batch* h);
-int batch_sensitivity(lcqp_hip_batch* h, bool blk, int nrhs, const double* v, double* dg, double* db, int* side, int* info);
-int batch_jacobian(lcqp_hip_batch* h, int first, int count, double* Jg, double* Jb, int* side, int* info);
+// lcqp_hip_diff.hip: the bodies of the batch's sensitivity, Jacobian and adjoint entry points behind their guards, which the QP object
+// calls on its batch of one (dev: the device-pointer twin, with the caller's stream)
+int batch_sensitivity(lcqp_hip_batch* h, bool blk, int nrhs, const double* v, double* dg, double* db, int* side, int* info, bool dev = false, void* stream = nullptr);
+int dense_jacobian(lcqp_hip_batch* h, int first, int count, double* Jg, double* Jb, int* side, int* info, bool dev);
 int batch_adjoint(lcqp_hip_batch* h, const double* vx, const double* vy, double* dg, double* db, int* side, int* info,
-                  int reduce, double* dQ, double* dA, double* dL, double* dR);
+                  int reduce, double* dQ, double* dA, double* dL, double* dR, bool dev = false, void* stream = nullptr);
 
-int batch_adjoint_blocked(lcqp_hip_batch* h, int nrhs, const double* vx, const double* vy, double* dg, double* db, int* side, int* info);
-int batch_jacobian_duals(lcqp_hip_batch* h, int first, int count, double* Jyg, double* Jyb, int* side, int* info);
 // lcqp_hip_device.hip: k_pack_dual_rows on `count` instances -- staged row j of instance o (dg pitch np, db pitch ldb) goes to row
 // rowpos[o][j] of Jyg [count][nd][n] and Jyb [count][nd][nd] (or null); rowpos < 0: the row is not part of the result
 void launch_pack_dual_rows(const lcqp::DevBatch& d, hipStream_t s, int count, int ldb, const double* dg, const double* db, const int* rowpos,

@@ -1,7 +1,7 @@
 // lcqp_hip_device.hip -- the dense batch's device-pointer entry points that fill and read the pools: lcqp_hip_batch_load_device,
 // _update_device and _get_solution_device (include/lcqp_hip.h, DESIGN.md section 3a'''''), with their three kernels, and dense_pack, the pack step
 // the host load / update of lcqp_hip.hip run behind their upload: the pack kernels are the one definition of the pool layout.  The twins of
-// _sensitivity and _adjoint sit beside the kernels they launch, in lcqp_hip.hip; lcqp_hip_batch.hpp holds what the two units share, lcqp_host_rt.hpp the hand-over
+// the sensitivity, Jacobian and adjoint calls are one body with their host calls, in lcqp_hip_diff.hip (k_pack_dual_rows here is theirs); lcqp_hip_batch.hpp holds what the two units share, lcqp_host_rt.hpp the hand-over
 // around every such call (device_call) and _get_solution_device, which are the sparse arm's too.
 #include "lcqp_hip_batch.hpp"
 

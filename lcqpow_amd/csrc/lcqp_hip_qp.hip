@@ -242,5 +242,5 @@ extern "C" int lcqp_hip_qp_jacobian(lcqp_hip_qp_t* q, double* Jg, double* Jb, in
 { return guarded(dense_err(), [&] {
     if (!q || !Jg) return LCQP_INVALID_ARGUMENT;
     if (!q->hb || !q->solved) return LCQP_LCQPOBJECT_NOT_SETUP;
-    return batch_jacobian(q->hb.get(), 0, 1, Jg, Jb, side, info);
+    return dense_jacobian(q->hb.get(), 0, 1, Jg, Jb, side, info, false);
 }); }

@@ -1,5 +1,5 @@
-// lcqp_host_rt.hpp -- host runtime shared by the C ABIs of the dense (lcqp_hip.hip, lcqp_hip_device.hip, lcqp_hip_qp.hip, lcqp_hip_util.hip) and sparse
-// (lcqp_sparse_host.hip, lcqp_sparse_device.hip) arms: error reporting, owners of streams, events and device memory, and the entry-point bodies both arms have
+// lcqp_host_rt.hpp -- host runtime shared by the C ABIs of the dense (lcqp_hip.hip, lcqp_hip_diff.hip, lcqp_hip_device.hip, lcqp_hip_qp.hip, lcqp_hip_util.hip) and sparse
+// (lcqp_sparse_host.hip, lcqp_sparse_diff.hip, lcqp_sparse_device.hip) arms: error reporting, owners of streams, events and device memory, and the entry-point bodies both arms have
 // in common -- solution, options, trace, re-solves, the buffers of a sensitivity launch, the hand-over of a device-pointer call, the upload of a host
 // load / update.  What drives the sensitivity,
 // Jacobian and adjoint kernels on top of these is lcqp_sens_rt.hpp.  Host code only.
@@ -345,7 +345,7 @@ struct SensBuffers {
     }
 };
 
-// ---- the device-pointer entry points of both arms (lcqp_hip.hip, lcqp_hip_device.hip; lcqp_sparse_host.hip, lcqp_sparse_device.hip): H has
+// ---- the device-pointer entry points of both arms (lcqp_hip_diff.hip, lcqp_hip_device.hip; lcqp_sparse_diff.hip, lcqp_sparse_device.hip): H has
 // device, stream and the two events evIn / evOut (hipEventDisableTiming) ----
 // A data pointer of such a call: NULL, or plain device memory of the handle's device with `bytes` behind it (align: 8, or 16 where a kernel stores pairs of doubles).
 // Anything else -- pageable, pinned or managed host memory, another device -- leaves a message and returns false; nothing is dereferenced.

@@ -1,7 +1,9 @@
-// lcqp_sens_rt.hpp -- the host code behind the sensitivity, Jacobian and adjoint entry points of both arms (lcqp_hip.hip, lcqp_sparse_host.hip):
+// lcqp_sens_rt.hpp -- the host code behind the sensitivity, Jacobian and adjoint entry points of both arms (lcqp_hip_diff.hip, lcqp_sparse_diff.hip):
 // the state a handle keeps for them (member sn) and the one copy of what drives their kernels -- the staging cap (grow and staging_chunk
-// are lcqp_host_rt.hpp's: the host load / update use them too), the timed launch, the call around a sensitivity kernel, the Jacobians through a vector kernel, the chunks of a host adjoint.  Templates on the handle H
-// (lcqp_hip_batch / lcqp_hip_sparse: device, stream, mem, db, rs, sn) like those of lcqp_host_rt.hpp; what differs between the arms -- the
+// are lcqp_host_rt.hpp's: the host load / update use them too), the timed launch, the call around a sensitivity kernel, the Jacobians through
+// a vector kernel, the chunks of a host adjoint -- and of what every entry point opens and closes with: one guard per call shape (guard_vectors,
+// guard_pairs, guard_range) and the body around a host call or its device-pointer twin (sens_body).  Templates on the handle H
+// (lcqp_hip_batch / lcqp_hip_sparse: device, stream, mem, db, rs, sn, ndual()) like those of lcqp_host_rt.hpp; what differs between the arms -- the
 // kernels, their pitches, the width of the dual vector -- comes in as arguments and callables.  Host code only.
 #pragma once
 #include "lcqp_host_rt.hpp"
@@ -234,30 +236,68 @@ int sensitivity_timing(std::string& err, H* h, float* kernel_ms, const SensBuffe
     return 0;
 }
 
-// the pointer checks of *_sensitivity_device / *_adjoint_device: every array with the bytes the call moves (nd: the width of the dual vector)
+// ---- the guards of the entry points, one per call shape, for both arms and both twins of a pair (dev: the device-pointer twin).  A null
+// handle is an invalid argument to a host call and an object that is not set up to its twin; then the arguments, then a finished solve; with
+// dev the device is set and every array checked with the bytes the call moves.  H::ndual() is the width of the arm's dual vector. ----
+inline int null_handle(bool dev) { return dev ? LCQP_LCQPOBJECT_NOT_SETUP : LCQP_INVALID_ARGUMENT; }
+
+// what follows the argument checks of the vector and the pair shape, on `rows` vectors v (vname) and vy
 template <class H>
-bool sens_pointers_ok(std::string& err, const H* h, size_t nd, size_t rows, const double* v, const char* vname, const double* vy, double* dg, double* db, int* side, int* info)
+int guard_rows(std::string& err, H* h, bool dev, size_t rows, const double* v, const char* vname, const double* vy, double* dg, double* db, int* side, int* info)
 {
-    const size_t B = h->db.B, n = h->db.n;
-    return device_pointer_ok(err, h, vname, v, sizeof(double) * rows * n) && device_pointer_ok(err, h, "vy", vy, sizeof(double) * rows * nd) &&
-           device_pointer_ok(err, h, "dg", dg, sizeof(double) * rows * n) && device_pointer_ok(err, h, "db", db, sizeof(double) * rows * nd) &&
-           device_pointer_ok(err, h, "side", side, sizeof(int) * B * nd, 4) && device_pointer_ok(err, h, "info", info, sizeof(int) * B, 4);
+    if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!dev) return 0;
+    HIPCHK(err, hipSetDevice(h->device));
+    const size_t B = h->db.B, n = h->db.n, nd = h->ndual();
+    const bool ok = device_pointer_ok(err, h, vname, v, sizeof(double) * rows * n) && device_pointer_ok(err, h, "vy", vy, sizeof(double) * rows * nd) &&
+                    device_pointer_ok(err, h, "dg", dg, sizeof(double) * rows * n) && device_pointer_ok(err, h, "db", db, sizeof(double) * rows * nd) &&
+                    device_pointer_ok(err, h, "side", side, sizeof(int) * B * nd, 4) && device_pointer_ok(err, h, "info", info, sizeof(int) * B, 4);
+    return ok ? 0 : LCQP_INVALID_ARGUMENT;
 }
 
-// the checks the Jacobian twins of both arms make (*_jacobian_device, *_jacobian_duals_device), in the host twins' order: the handle, the
-// range, a finished solve, then the four arrays with the bytes the call moves (rows: of one instance's two blocks; nd: the width of the dual
-// vector)
+// the vector shape (*_sensitivity, *_sensitivity_blocked): nrhs vectors v per instance
 template <class H>
-int jacobian_device_checks(std::string& err, H* h, size_t nd, int first, int count, size_t rows, const char* gname, double* Jg, const char* bname, double* Jb,
-                           int* side, int* info)
+int guard_vectors(std::string& err, H* h, bool dev, int nrhs, const double* v, double* dg, double* db, int* side, int* info)
 {
-    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!h) return null_handle(dev);
+    if (nrhs < 1 || !v || !dg) return LCQP_INVALID_ARGUMENT;
+    return guard_rows(err, h, dev, (size_t)h->db.B * nrhs, v, "v", nullptr, dg, db, side, info);
+}
+
+// the pair shape: nrhs pairs (vx, vy) per instance, either of them (*_adjoint_blocked) or, with needVx, vx (*_adjoint: nrhs = 1, reduce 0 or 1)
+template <class H>
+int guard_pairs(std::string& err, H* h, bool dev, int nrhs, const double* vx, const double* vy, bool needVx, int reduce, double* dg, double* db, int* side, int* info)
+{
+    if (!h) return null_handle(dev);
+    if (nrhs < 1 || !(vx || (vy && !needVx)) || !dg || (reduce != 0 && reduce != 1)) return LCQP_INVALID_ARGUMENT;
+    return guard_rows(err, h, dev, (size_t)h->db.B * nrhs, vx, "vx", vy, dg, db, side, info);
+}
+
+// the range shape (*_jacobian; duals: *_jacobian_duals, whose blocks have ndual() rows per instance and are called Jyg, Jyb)
+template <class H>
+int guard_range(std::string& err, H* h, bool dev, bool duals, int first, int count, double* Jg, double* Jb, int* side, int* info)
+{
+    if (!h) return null_handle(dev);
     if (!Jg || first < 0 || count < 1 || first > h->db.B - count) return LCQP_INVALID_ARGUMENT;
     if (!h->rs.solved) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!dev) return 0;
     HIPCHK(err, hipSetDevice(h->device));
-    const size_t n = h->db.n, c = count;
-    if (!device_pointer_ok(err, h, gname, Jg, sizeof(double) * c * rows * n) || !device_pointer_ok(err, h, bname, Jb, sizeof(double) * c * rows * nd) ||
+    const size_t n = h->db.n, nd = h->ndual(), c = count, rows = duals ? nd : n;
+    if (!device_pointer_ok(err, h, duals ? "Jyg" : "Jg", Jg, sizeof(double) * c * rows * n) || !device_pointer_ok(err, h, duals ? "Jyb" : "Jb", Jb, sizeof(double) * c * rows * nd) ||
         !device_pointer_ok(err, h, "side", side, sizeof(int) * c * nd, 4) || !device_pointer_ok(err, h, "info", info, sizeof(int) * c, 4)) return LCQP_INVALID_ARGUMENT;
+    return 0;
+}
+
+// The body of a sensitivity entry point behind its guard.  A host call's body adds the kernel time of its launches to ms, and the sum becomes
+// rs.sensMs.  The device-pointer twin runs the same body between the two halves of the hand-over (device_call); there the times stay in the
+// events (sensPending, pendingMs) and ms is not read.
+template <class H, class F>
+int sens_body(std::string& err, H* h, bool dev, void* stream, F body)
+{
+    float ms = 0.f;
+    if (dev) return device_call(err, h, stream, [&] { return body(ms); });
+    if (int rc = body(ms)) return rc;
+    h->rs.sensMs = ms;
     return 0;
 }
 

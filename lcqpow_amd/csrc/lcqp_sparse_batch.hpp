@@ -1,5 +1,6 @@
-// lcqp_sparse_batch.hpp -- what the two host units of the sparse arm share: the handle behind lcqp_hip_sparse_t, the functions of
-// lcqp_sparse_host.hip that the device-pointer unit (lcqp_sparse_device.hip) calls on it, and the arm's error slot.  The host code the handle
+// lcqp_sparse_batch.hpp -- what the three host units of the sparse arm share: the handle behind lcqp_hip_sparse_t, the functions of
+// lcqp_sparse_host.hip (the life cycle) that the differentiation unit (lcqp_sparse_diff.hip) and the device-pointer unit
+// (lcqp_sparse_device.hip) call on it, what the latter gives the other two, and the arm's error slot.  The host code the handle
 // shares with the dense arm's comes in with lcqp_host_rt.hpp and lcqp_sens_rt.hpp.  Internal: nothing of it enters the dynamic symbol table
 // of the library.  Host code only.
 #pragma once
@@ -39,18 +40,20 @@ struct lcqp_hip_sparse {
     // the device copy of csr2csc (one per pattern, uploaded by sp_value_map for the first call that needs it): the adjoint stores dAx through
     // it, k_sparse_pack_values of a device load gathers Ax through it
     int* valMap = nullptr;
-    // of the device-pointer entry points (lcqp_sparse_device.hip; sensitivity_device and adjoint_device beside their host twins): the events of
+    // of the device-pointer entry points (lcqp_sparse_device.hip; the twins of the differentiation calls in lcqp_sparse_diff.hip): the events of
     // the hand-over between the caller's stream and `stream`; the status word of k_sparse_check_vectors followed by the diagonal pairs of a
     // load ([2] x 8 bytes, then [B][2] doubles)
     lcqp_rt::Event evIn{hipEventDisableTiming}, evOut{hipEventDisableTiming};
     unsigned long long* devChk = nullptr;
     explicit lcqp_hip_sparse(int dev) : db(), device(dev) {}
+    size_t ndual() const { return (size_t)db.m; }      // the width of the dual vector (lcqp_sens_rt.hpp)
     ~lcqp_hip_sparse() { (void)hipSetDevice(device); (void)hipStreamSynchronize(stream); }
 };
 
 // lcqp_sparse_host.hip; the comments are at the definitions
 void sp_choose_ordering(lcqp_hip_sparse* h);
 int sp_value_map(lcqp_hip_sparse* h);
+const lcqp_sparse::SpKernels* sp_kernels(int G);
 
 // lcqp_sparse_device.hip: the pack step of a load / an update, the one definition of the pool layout.  Device pointers to the arrays as the
 // caller holds them, of the `count` instances that go to [first, first + count):
@@ -63,7 +66,7 @@ struct SpPackValues { const double *Qx, *Ax; size_t qStride, aStride; };
 int sparse_pack(lcqp_hip_sparse* h, int first, int count, const SpPackVectors& v, const SpPackValues& m, bool update);
 
 // ---- from the staging of the panel kernels (lcqp_sparse_launch.hpp: SpSensBlkArgs) to the caller's arrays.  The one definition of where a
-// staged column goes: the host loop of sp_panel_run (lcqp_sparse_host.hip) and k_sparse_scatter_panels (lcqp_sparse_device.hip) both call it.
+// staged column goes: the host loop of sp_panel_run (lcqp_sparse_diff.hip) and k_sparse_scatter_panels (lcqp_sparse_device.hip) both call it.
 // Staged column k of work item `item` = (instance - first) * npan + panel of a call with ncols columns per instance in panels of P: the row
 // of the caller's [count][ncols][..] arrays it is, or -1: nowhere.  Plain calls: column panel * P + k of its instance; the padding columns
 // of a ragged last panel go nowhere.  dunit (the dual Jacobian, ncols = m): row rowpos -- what the kernel wrote for this column -- of its

@@ -1,9 +1,9 @@
 // lcqp_sparse_device.hip -- the sparse batch's device-pointer entry points that fill and read the pools: lcqp_hip_sparse_load_device,
 // _update_device and _get_solution_device (include/lcqp_hip.h, DESIGN.md section 3a'''''), with their three kernels, sparse_pack -- the pack step
 // the host load / update of lcqp_sparse_host.hip run behind their upload: the pack kernels are the one definition of the pool layout --, the
-// scatter kernel of the device-pointer panel calls (k_sparse_scatter_panels, launched by sp_panel_run of lcqp_sparse_host.hip) and the diagnostic
-// reader lcqp_hip_sparse_read_problem.  The twins of _sensitivity, _adjoint and the panel calls sit beside their host twins, in lcqp_sparse_host.hip;
-// lcqp_sparse_batch.hpp holds what the two units share, lcqp_host_rt.hpp the hand-over around every such call (device_call) and
+// scatter kernel of the device-pointer panel calls (k_sparse_scatter_panels, launched by sp_panel_run of lcqp_sparse_diff.hip) and the diagnostic
+// reader lcqp_hip_sparse_read_problem.  The twins of _sensitivity, _adjoint and the panel calls are one body with their host calls, in lcqp_sparse_diff.hip;
+// lcqp_sparse_batch.hpp holds what the three units share, lcqp_host_rt.hpp the hand-over around every such call (device_call) and
 // _get_solution_device, which are the dense arm's too.  The model is lcqp_hip_device.hip of the dense arm.
 #include "lcqp_sparse_batch.hpp"
 

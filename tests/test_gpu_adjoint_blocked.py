@@ -502,6 +502,54 @@ def test_device_twins_return_the_bits_of_the_host_calls(hip, key):
     bt.close()
 
 
+def test_device_jacobians_of_a_sub_range_in_uneven_chunks(hip):
+    """instances 1 .. 3 of five under a staging cap that holds two: a chunk of two, then a partial one, from a start that is not zero.  The
+    device twins return the host calls' bits under that cap and rows 1 .. 3 of the host calls under the default cap, write nothing in front
+    of or behind their range, and report the kernel time of both chunks (test_device_twins_return_the_bits_of_the_host_calls argues the half)."""
+    import torch
+    n, nC, nComp = SHAPES["np128"][:3]
+    B, first, count = 5, 1, 3
+    nd = n + nC + 2 * nComp
+    ds = [random_lcqp(np.random.default_rng(1000 + b), n, nC, nComp, False, False) for b in range(B)]
+    bt = hip.BatchLCQP(B, n, nC, nComp, opt=hip.default_options(perturbStep=0))
+    load_all(bt, ds)
+    bt.run()
+    su = bt.read_setup(0)
+    caps = {"jacobian": 8 * n * (n + su["np"] + nd + 2 * su["capS"]) * 2, "jacobian_duals": dual_staging_bytes(su, nd, 2)}
+    rows = {"jacobian": n, "jacobian_duals": nd}
+    GUARD_F, GUARD_I = -7.25, 77
+    dev = torch.device("cuda", 0)
+    try:
+        for name in ("jacobian", "jacobian_duals"):
+            for bounds in (True, False):
+                bt._call("set_jacobian_staging", 0)
+                whole = getattr(bt, name)(bounds=bounds)
+                bt._call("set_jacobian_staging", caps[name])
+                want = getattr(bt, name)(first=first, count=count, bounds=bounds)
+                ms_host = bt.sensitivity_kernel_ms()
+                Jg = torch.full((count + 2, rows[name], n), GUARD_F, dtype=torch.float64, device=dev)
+                Jb = torch.full((count + 2, rows[name], nd), GUARD_F, dtype=torch.float64, device=dev) if bounds else None
+                side = torch.full((count + 2, nd), GUARD_I, dtype=torch.int32, device=dev)
+                info = torch.full((count + 2,), GUARD_I, dtype=torch.int32, device=dev)
+                bt._call(name + "_device", first, count, Jg[1:].data_ptr(), Jb[1:].data_ptr() if bounds else None, side[1:].data_ptr(),
+                         info[1:].data_ptr(), bt._stream())
+                ms_dev = bt.sensitivity_kernel_ms()
+                print(f"  {name} bounds={bounds}, chunks of 2 and 1: kernels {ms_host:.4f} ms (host call), {ms_dev:.4f} ms (device call)")
+                for t, w, full, guard in ((Jg, want[0], whole[0], GUARD_F), (Jb, want[1], whole[1], GUARD_F), (side, want[2], whole[2], GUARD_I),
+                                          (info, want[3], whole[3], GUARD_I)):
+                    if t is None:
+                        assert w is None and full is None
+                        continue
+                    got = t.cpu().numpy()
+                    assert np.array_equal(got[1:-1], w), (name, bounds)
+                    assert np.array_equal(got[1:-1], full[first:first + count]), (name, bounds)
+                    assert np.all(got[0] == guard) and np.all(got[-1] == guard), (name, bounds)
+                assert ms_dev > 0.5 * ms_host
+    finally:
+        bt._call("set_jacobian_staging", 0)
+    bt.close()
+
+
 def test_layer_jacobian_with_duals(hip):
     import torch
     from lcqpow_amd.diff import BatchLCQPLayer
