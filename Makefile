@@ -17,6 +17,6 @@ bench: build
 	$(PY) bench.py
 
 clean:
-	rm -f lcqpow_amd/*.so oracle/*.so tests/cpp/host_tests examples/bin/*
+	rm -f lcqpow_amd/*.so oracle/*.so tests/cpp/host_tests tests/cpp/host_owner_test examples/bin/*
 
 .PHONY: build test-cpu test-gpu smoke bench clean

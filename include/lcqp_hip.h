@@ -20,6 +20,7 @@
 #ifndef LCQP_HIP_H
 #define LCQP_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus

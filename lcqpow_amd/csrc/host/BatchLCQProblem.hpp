@@ -4,8 +4,10 @@
 #ifndef LCQPOW_AMD_BATCHLCQPROBLEM_HPP
 #define LCQPOW_AMD_BATCHLCQPROBLEM_HPP
 
+#include <memory>
 #include <vector>
 
+#include "HipHandles.hpp"
 #include "Options.hpp"
 #include "OutputStatistics.hpp"
 
@@ -15,25 +17,23 @@ class BatchLCQProblem {
   public:
     BatchLCQProblem(int batch, int nV, int nC, int nComp, bool withBoxBounds = false, int device = 0)
         : B(batch), nV_(nV), nC_(nC), nComp_(nComp), h(lcqp_hip_batch_create(batch, nV, nC, nComp, withBoxBounds ? 1 : 0, device)) {}
-    ~BatchLCQProblem() { if (h) lcqp_hip_batch_destroy(h); }
-    BatchLCQProblem(const BatchLCQProblem&) = delete;
-    BatchLCQProblem& operator=(const BatchLCQProblem&) = delete;
+    // (the handle has one owner: the class moves and does not copy; so do the two classes below, which own batch objects)
 
     bool ok() const { return h != nullptr; }
-    ReturnValue setOptions(const Options& o) { return (ReturnValue)lcqp_hip_batch_set_options(h, &o.getHIPOptions()); }
+    ReturnValue setOptions(const Options& o) { return (ReturnValue)lcqp_hip_batch_set_options(h.get(), &o.getHIPOptions()); }
     // the setup of this object runs beside another object's homotopy kernel (BatchPipeline sets it): see lcqp_hip_batch_set_overlapped
-    ReturnValue setOverlapped(bool overlapped) { return (ReturnValue)lcqp_hip_batch_set_overlapped(h, overlapped ? 1 : 0); }
+    ReturnValue setOverlapped(bool overlapped) { return (ReturnValue)lcqp_hip_batch_set_overlapped(h.get(), overlapped ? 1 : 0); }
     // instance-by-instance load with the argument list of LCQProblem::loadLCQP
     ReturnValue loadLCQP(int instance, const double* Q, const double* g, const double* L, const double* R,
                          const double* lbL = 0, const double* ubL = 0, const double* lbR = 0, const double* ubR = 0,
                          const double* A = 0, const double* lbA = 0, const double* ubA = 0, const double* lb = 0,
                          const double* ub = 0, const double* x0 = 0, const double* y0 = 0)
     {
-        return (ReturnValue)lcqp_hip_batch_load(h, instance, 1, Q, g, L, R, lbL, ubL, lbR, ubR, A, lbA, ubA, lb, ub, x0, y0);
+        return (ReturnValue)lcqp_hip_batch_load(h.get(), instance, 1, Q, g, L, R, lbL, ubL, lbR, ubR, A, lbA, ubA, lb, ub, x0, y0);
     }
     ReturnValue generateSynthetic(unsigned long long seed0, unsigned long long firstInstance)
     {
-        return (ReturnValue)lcqp_hip_batch_generate_synthetic(h, seed0, firstInstance);
+        return (ReturnValue)lcqp_hip_batch_generate_synthetic(h.get(), seed0, firstInstance);
     }
     // runSolver for every instance; per-instance return values are in getReturnValue(i)
     ReturnValue runSolver()
@@ -43,14 +43,14 @@ class BatchLCQProblem {
     }
     // the two halves of runSolver: the launches on this batch's own HIP stream (returns at once), and the wait + read-back.  Between the two
     // the host is free -- e.g. to load and launch another batch object (BatchPipeline below).
-    ReturnValue runSolverAsync() { return (ReturnValue)lcqp_hip_batch_run(h); }
-    // Re-solves (lcqp_hip_batch_update / lcqp_hip_batch_resolve): new vectors for one instance, the matrices stay -- the argument list of
+    ReturnValue runSolverAsync() { return (ReturnValue)lcqp_hip_batch_run(h.get()); }
+    // Re-solves (lcqp_hip_batch_update / lcqp_hip_batch_resolve): other vectors for one instance, the matrices stay -- the argument list of
     // loadLCQP without Q, L, R, A; the set of variables with a finite lb or ub must be the one the instance was loaded with.
     ReturnValue updateLCQP(int instance, const double* g, const double* lbL = 0, const double* ubL = 0, const double* lbR = 0,
                            const double* ubR = 0, const double* lbA = 0, const double* ubA = 0, const double* lb = 0,
                            const double* ub = 0, const double* x0 = 0, const double* y0 = 0)
     {
-        return (ReturnValue)lcqp_hip_batch_update(h, instance, 1, g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0);
+        return (ReturnValue)lcqp_hip_batch_update(h.get(), instance, 1, g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0);
     }
     // solve again on the setup in place.  warm: instances whose last run succeeded start from their last solution, working set and
     // penalty (rho0: [batch] starting penalties, each > 0, instead of the last rhoOpt); every other instance, and every instance of a
@@ -60,19 +60,19 @@ class BatchLCQProblem {
         const ReturnValue rc = resolveAsync(warm, rho0);
         return rc != SUCCESSFUL_RETURN ? rc : collect();
     }
-    ReturnValue resolveAsync(bool warm, const double* rho0 = 0) { return (ReturnValue)lcqp_hip_batch_resolve(h, warm ? 1 : 0, rho0); }
+    ReturnValue resolveAsync(bool warm, const double* rho0 = 0) { return (ReturnValue)lcqp_hip_batch_resolve(h.get(), warm ? 1 : 0, rho0); }
     // Solution sensitivities (lcqp_hip_batch_sensitivity): for nrhs upstream gradients v = dl/dx per instance ([batch][nrhs][nV]) the
     // derivatives dg = dl/dg (same shape) and db = dl/d(bound), side, info ([batch][nrhs][nDuals], [batch][nDuals], [batch]; each may be 0)
     // of the solutions the last runSolver / resolve returned.  info[i] != 0: instance i is not differentiable by the criteria of the header.
     // blocked: lcqp_hip_batch_sensitivity_blocked (panels of 16 vectors on the matrix cores; equal to rounding, not to the bit)
     ReturnValue getSensitivity(int nrhs, const double* v, double* dg, double* db = 0, int* side = 0, int* info = 0, bool blocked = false)
     {
-        return (ReturnValue)(blocked ? lcqp_hip_batch_sensitivity_blocked(h, nrhs, v, dg, db, side, info) : lcqp_hip_batch_sensitivity(h, nrhs, v, dg, db, side, info));
+        return (ReturnValue)(blocked ? lcqp_hip_batch_sensitivity_blocked(h.get(), nrhs, v, dg, db, side, info) : lcqp_hip_batch_sensitivity(h.get(), nrhs, v, dg, db, side, info));
     }
     // lcqp_hip_batch_jacobian: Jg [count][nV][nV], Jb [count][nV][nd] (or 0), side [count][nd], info [count] of the instances [first, first + count)
     ReturnValue getJacobian(int first, int count, double* Jg, double* Jb = 0, int* side = 0, int* info = 0)
     {
-        return (ReturnValue)lcqp_hip_batch_jacobian(h, first, count, Jg, Jb, side, info);
+        return (ReturnValue)lcqp_hip_batch_jacobian(h.get(), first, count, Jg, Jb, side, info);
     }
     // lcqp_hip_batch_adjoint: upstream gradients vx [batch][nV] and vy [batch][nDuals] (or 0) on the primal and dual solutions; dg, db, side,
     // info as getSensitivity with nrhs = 1; the gradients in the matrices dQ [batch][nV][nV], dA [batch][nC][nV], dL, dR [batch][nComp][nV]
@@ -80,25 +80,25 @@ class BatchLCQProblem {
     ReturnValue getAdjoint(const double* vx, const double* vy, double* dg, double* db = 0, int* side = 0, int* info = 0, bool reduce = false,
                            double* dQ = 0, double* dA = 0, double* dL = 0, double* dR = 0)
     {
-        return (ReturnValue)lcqp_hip_batch_adjoint(h, vx, vy, dg, db, side, info, reduce ? 1 : 0, dQ, dA, dL, dR);
+        return (ReturnValue)lcqp_hip_batch_adjoint(h.get(), vx, vy, dg, db, side, info, reduce ? 1 : 0, dQ, dA, dL, dR);
     }
     // lcqp_hip_batch_adjoint_blocked: nrhs pairs per instance, vx [batch][nrhs][nV] and vy [batch][nrhs][nDuals] (either may be 0, not both),
     // in panels of 16 on the matrix cores; dg [batch][nrhs][nV], db [batch][nrhs][nDuals], side, info as getSensitivity
     ReturnValue getAdjointBlocked(int nrhs, const double* vx, const double* vy, double* dg, double* db = 0, int* side = 0, int* info = 0)
     {
-        return (ReturnValue)lcqp_hip_batch_adjoint_blocked(h, nrhs, vx, vy, dg, db, side, info);
+        return (ReturnValue)lcqp_hip_batch_adjoint_blocked(h.get(), nrhs, vx, vy, dg, db, side, info);
     }
     // lcqp_hip_batch_jacobian_duals: Jyg [count][nDuals][nV] = dy/dg, Jyb [count][nDuals][nDuals] = dy/d(bounds) (or 0), zero outside the
     // working set; side [count][nDuals], info [count] of the instances [first, first + count)
     ReturnValue getDualJacobian(int first, int count, double* Jyg, double* Jyb = 0, int* side = 0, int* info = 0)
     {
-        return (ReturnValue)lcqp_hip_batch_jacobian_duals(h, first, count, Jyg, Jyb, side, info);
+        return (ReturnValue)lcqp_hip_batch_jacobian_duals(h.get(), first, count, Jyg, Jyb, side, info);
     }
     // full setups and homotopy launches this object has issued
     ReturnValue getLaunchCounts(int& setups, int& launches) const
     {
         int c[2] = {0, 0};
-        const ReturnValue rc = (ReturnValue)lcqp_hip_batch_launch_counts(h, c);
+        const ReturnValue rc = (ReturnValue)lcqp_hip_batch_launch_counts(h.get(), c);
         setups = c[0]; launches = c[1];
         return rc;
     }
@@ -107,7 +107,7 @@ class BatchLCQProblem {
         x.assign((size_t)B * nV_, 0.0);
         y.assign((size_t)B * (nV_ + nC_ + 2 * nComp_), 0.0);
         st.assign(B, lcqp_stats_t());
-        return (ReturnValue)lcqp_hip_batch_get_solution(h, x.data(), y.data(), st.data());
+        return (ReturnValue)lcqp_hip_batch_get_solution(h.get(), x.data(), y.data(), st.data());
     }
     ReturnValue getReturnValue(int i) const { return (ReturnValue)st[i].returnValue; }
     AlgorithmStatus getPrimalSolution(int i, double* xOpt) const
@@ -124,11 +124,11 @@ class BatchLCQProblem {
     const lcqp_stats_t& getStats(int i) const { return st[i]; }
     int getNumberOfPrimals() const { return nV_; }
     int getNumberOfDuals() const { return nV_ + nC_ + 2 * nComp_; }
-    lcqp_hip_batch_t* handle() { return h; }
+    lcqp_hip_batch_t* handle() { return h.get(); }
 
   private:
     int B, nV_, nC_, nComp_;
-    lcqp_hip_batch_t* h;
+    BatchHandle h;
     std::vector<double> x, y;
     std::vector<lcqp_stats_t> st;
 };
@@ -149,13 +149,10 @@ class BatchPipeline {
     BatchPipeline(int depth, int batch, int nV, int nC, int nComp, bool withBoxBounds = false, int device = 0)
     {
         for (int k = 0; k < depth; ++k) {
-            slots.push_back(new BatchLCQProblem(batch, nV, nC, nComp, withBoxBounds, device)); state.push_back(0);
+            slots.push_back(std::make_unique<BatchLCQProblem>(batch, nV, nC, nComp, withBoxBounds, device)); state.push_back(0);
             if (depth > 1 && slots.back()->ok()) slots.back()->setOverlapped(true);
         }
     }
-    ~BatchPipeline() { for (size_t k = 0; k < slots.size(); ++k) delete slots[k]; }
-    BatchPipeline(const BatchPipeline&) = delete;
-    BatchPipeline& operator=(const BatchPipeline&) = delete;
     bool ok() const { for (size_t k = 0; k < slots.size(); ++k) if (!slots[k]->ok()) return false; return !slots.empty(); }
     int depth() const { return (int)slots.size(); }
     BatchLCQProblem& slot(int k) { return *slots[k]; }
@@ -182,18 +179,18 @@ class BatchPipeline {
         const int k = order.front(); order.erase(order.begin());
         lastRc = slots[k]->collect(); state[k] = 0;
         if (order.empty()) for (size_t q = 0; q < slots.size(); ++q) state[q] = 0;      // drained: a pipeline that is used again starts with every slot free
-        return slots[k];
+        return slots[k].get();
     }
 
   private:
-    bool owns(const BatchLCQProblem& b) const { for (size_t k = 0; k < slots.size(); ++k) if (slots[k] == &b) return true; return false; }
+    bool owns(const BatchLCQProblem& b) const { for (size_t k = 0; k < slots.size(); ++k) if (slots[k].get() == &b) return true; return false; }
     ReturnValue launched(BatchLCQProblem& b, ReturnValue rc)
     {
         for (size_t k = 0; k < slots.size(); ++k)
-            if (slots[k] == &b && rc == SUCCESSFUL_RETURN) { state[k] = 1; order.push_back((int)k); }
+            if (slots[k].get() == &b && rc == SUCCESSFUL_RETURN) { state[k] = 1; order.push_back((int)k); }
         return rc;
     }
-    std::vector<BatchLCQProblem*> slots;
+    std::vector<std::unique_ptr<BatchLCQProblem> > slots;
     std::vector<int> state;      // 0 free, 1 in flight, 2 finished (results in the object)
     std::vector<int> order;      // launch order of the batches in flight
     int cur = -1;
@@ -227,14 +224,13 @@ class MixedBatchLCQProblem {
     // runSolver for every problem; the return value is that of the first call that failed to LOAD or LAUNCH (per-problem results: getReturnValue)
     ReturnValue runSolver()
     {
-        for (size_t k = 0; k < buckets.size(); ++k) delete buckets[k].batch;
         buckets.clear();
         for (size_t i = 0; i < problems.size(); ++i) {
             Problem& p = problems[i];
             const bool box = p.lb || p.ub;
             size_t k = 0;
             for (; k < buckets.size(); ++k) if (buckets[k].nV == p.nV && buckets[k].nC == p.nC && buckets[k].nComp == p.nComp && buckets[k].box == box) break;
-            if (k == buckets.size()) { Bucket b = {p.nV, p.nC, p.nComp, box, std::vector<int>(), 0}; buckets.push_back(b); }
+            if (k == buckets.size()) { Bucket b = {p.nV, p.nC, p.nComp, box, std::vector<int>(), nullptr}; buckets.push_back(std::move(b)); }
             p.bucket = (int)k; p.slot = (int)buckets[k].members.size();
             buckets[k].members.push_back((int)i);
         }
@@ -242,7 +238,7 @@ class MixedBatchLCQProblem {
         int inFlight = -1;
         for (size_t k = 0; k < buckets.size(); ++k) {
             Bucket& b = buckets[k];
-            b.batch = new BatchLCQProblem((int)b.members.size(), b.nV, b.nC, b.nComp, b.box, device_);
+            b.batch = std::make_unique<BatchLCQProblem>((int)b.members.size(), b.nV, b.nC, b.nComp, b.box, device_);
             ReturnValue rc = b.batch->ok() ? SUCCESSFUL_RETURN : LCQPOBJECT_NOT_SETUP;
             if (rc == SUCCESSFUL_RETURN && haveOptions) rc = b.batch->setOptions(options);
             if (rc == SUCCESSFUL_RETURN && buckets.size() > 1) rc = b.batch->setOverlapped(true);      // beside the bucket launched before it
@@ -251,7 +247,7 @@ class MixedBatchLCQProblem {
                 rc = b.batch->loadLCQP((int)s, p.Q, p.g, p.L, p.R, p.lbL, p.ubL, p.lbR, p.ubR, p.A, p.lbA, p.ubA, p.lb, p.ub, p.x0, p.y0);
             }
             if (rc == SUCCESSFUL_RETURN) rc = b.batch->runSolverAsync();
-            if (rc != SUCCESSFUL_RETURN) { if (first == SUCCESSFUL_RETURN) first = rc; delete b.batch; b.batch = 0; }
+            if (rc != SUCCESSFUL_RETURN) { if (first == SUCCESSFUL_RETURN) first = rc; b.batch.reset(); }
             // the bucket launched before this one is collected now: its kernels ran while this one was created and loaded
             if (inFlight >= 0) { const ReturnValue rcC = buckets[inFlight].batch->collect(); if (rcC != SUCCESSFUL_RETURN && first == SUCCESSFUL_RETURN) first = rcC; }
             inFlight = b.batch ? (int)k : -1;
@@ -259,14 +255,13 @@ class MixedBatchLCQProblem {
         if (inFlight >= 0) { const ReturnValue rcC = buckets[inFlight].batch->collect(); if (rcC != SUCCESSFUL_RETURN && first == SUCCESSFUL_RETURN) first = rcC; }
         return first;
     }
-    ~MixedBatchLCQProblem() { for (size_t k = 0; k < buckets.size(); ++k) delete buckets[k].batch; }
-    MixedBatchLCQProblem(const MixedBatchLCQProblem&) = delete;
-    MixedBatchLCQProblem& operator=(const MixedBatchLCQProblem&) = delete;
 
+    // a problem without a batch object -- before runSolver, an index out of range, a member of a bucket whose create, load or launch
+    // failed -- is not solved: LCQPOBJECT_NOT_SETUP, PROBLEM_NOT_SOLVED with the output untouched, zeroed statistics
     ReturnValue getReturnValue(int i) const { const BatchLCQProblem* b = batchOf(i); return b ? b->getReturnValue(problems[i].slot) : LCQPOBJECT_NOT_SETUP; }
-    AlgorithmStatus getPrimalSolution(int i, double* xOpt) const { return batchOf(i)->getPrimalSolution(problems[i].slot, xOpt); }
-    AlgorithmStatus getDualSolution(int i, double* yOpt) const { return batchOf(i)->getDualSolution(problems[i].slot, yOpt); }
-    const lcqp_stats_t& getStats(int i) const { return batchOf(i)->getStats(problems[i].slot); }
+    AlgorithmStatus getPrimalSolution(int i, double* xOpt) const { const BatchLCQProblem* b = batchOf(i); return b ? b->getPrimalSolution(problems[i].slot, xOpt) : PROBLEM_NOT_SOLVED; }
+    AlgorithmStatus getDualSolution(int i, double* yOpt) const { const BatchLCQProblem* b = batchOf(i); return b ? b->getDualSolution(problems[i].slot, yOpt) : PROBLEM_NOT_SOLVED; }
+    const lcqp_stats_t& getStats(int i) const { static const lcqp_stats_t none = lcqp_stats_t(); const BatchLCQProblem* b = batchOf(i); return b ? b->getStats(problems[i].slot) : none; }
     int getNumberOfPrimals(int i) const { return problems[i].nV; }
     int getNumberOfDuals(int i) const { return problems[i].nV + problems[i].nC + 2 * problems[i].nComp; }
 
@@ -276,11 +271,11 @@ class MixedBatchLCQProblem {
         const double *Q, *g, *L, *R, *lbL, *ubL, *lbR, *ubR, *A, *lbA, *ubA, *lb, *ub, *x0, *y0;
         int bucket, slot;
     };
-    struct Bucket { int nV, nC, nComp; bool box; std::vector<int> members; BatchLCQProblem* batch; };
+    struct Bucket { int nV, nC, nComp; bool box; std::vector<int> members; std::unique_ptr<BatchLCQProblem> batch; };
     const BatchLCQProblem* batchOf(int i) const
     {
         if (i < 0 || i >= (int)problems.size() || problems[i].bucket < 0 || problems[i].bucket >= (int)buckets.size()) return 0;
-        return buckets[problems[i].bucket].batch;
+        return buckets[problems[i].bucket].batch.get();
     }
     int device_;
     bool haveOptions;

@@ -6,13 +6,7 @@
 
 namespace LCQPow {
 
-LCQProblem::LCQProblem()
-    : nV(0), nC(0), nComp(0), nDuals(0), boxDualOffset(0), device(0), loaded(false), haveBox(false), sparseSolver(false), hostLoop(false),
-      Q_sparse(0), A_sparse(0), L_sparse(0), R_sparse(0), C_sparse(0) {}
-
 LCQProblem::LCQProblem(int _nV, int _nC, int _nComp)
-    : nV(0), nC(0), nComp(0), nDuals(0), boxDualOffset(0), device(0), loaded(false), haveBox(false), sparseSolver(false), hostLoop(false),
-      Q_sparse(0), A_sparse(0), L_sparse(0), R_sparse(0), C_sparse(0)
 {
     // consistency checks of the reference constructor (src/LCQProblem.cpp:43-67)
     if (_nV <= 0 || _nComp <= 0 || _nC < 0) return;
@@ -31,7 +25,6 @@ ReturnValue LCQProblem::loadLCQP(const double* const _Q, const double* const _g,
     if (!_A && nC > 0) return INVALID_CONSTRAINT_MATRIX;
     if (!_L || !_R) return INVALID_COMPLEMENTARITY_MATRIX;
     const int m = nC + 2 * nComp;
-    const double inf = INFINITY;
     clearSparse();
     sparseSolver = false;
     Q.assign(_Q, _Q + (size_t)nV * nV);
@@ -123,14 +116,6 @@ ReturnValue LCQProblem::loadLCQP(const char* const Q_file, const char* const g_f
                     p(a, b[4]), p(vlbA, b[5]), p(vubA, b[6]), p(vlb, b[7]), p(vub, b[8]), p(vx0, b[9]), p(vy0, b[10]));
 }
 
-LCQProblem::~LCQProblem() { clearSparse(); }
-
-void LCQProblem::clearSparse()
-{
-    Utilities::ClearSparseMat(&Q_sparse); Utilities::ClearSparseMat(&A_sparse); Utilities::ClearSparseMat(&L_sparse);
-    Utilities::ClearSparseMat(&R_sparse); Utilities::ClearSparseMat(&C_sparse);
-}
-
 ReturnValue LCQProblem::loadLCQP(const csc* const _Q, const double* const _g, const csc* const _L, const csc* const _R,
                                  const double* const _lbL, const double* const _ubL, const double* const _lbR,
                                  const double* const _ubR, const csc* const _A, const double* const _lbA,
@@ -154,7 +139,7 @@ ReturnValue LCQProblem::loadLCQP(const csc* const _Q, const double* const _g, co
     const ReturnValue rv = loadVectors(_g, _lbL, _ubL, _lbR, _ubR, _lbA, _ubA, _lb, _ub, _x0, _y0);
     if (rv != SUCCESSFUL_RETURN) return rv;
     loaded = false;
-    Q_sparse = Utilities::copyCSC(_Q); L_sparse = Utilities::copyCSC(_L); R_sparse = Utilities::copyCSC(_R);
+    Q_sparse.reset(Utilities::copyCSC(_Q)); L_sparse.reset(Utilities::copyCSC(_L)); R_sparse.reset(Utilities::copyCSC(_R));
     {   // A_sparse = [A; L; R] column by column (setConstraints, :629-723)
         const int m = nC + 2 * nComp;
         const bool hasA = (_A && nC > 0);
@@ -168,10 +153,10 @@ ReturnValue LCQProblem::loadLCQP(const csc* const _Q, const double* const _g, co
             for (int k = _R->p[j]; k < _R->p[j + 1]; ++k) { ai.push_back(nC + nComp + _R->i[k]); ax.push_back(_R->x[k]); }
             ap[j + 1] = (int)ai.size();
         }
-        A_sparse = Utilities::copyCSC(m, nV, (int)ai.size(), ax.data(), ai.data(), ap.data());
+        A_sparse.reset(Utilities::copyCSC(m, nV, (int)ai.size(), ax.data(), ai.data(), ap.data()));
     }
-    C_sparse = (L_sparse && R_sparse) ? Utilities::MatrixSymmetrizationProduct(L_sparse, R_sparse) : 0;
-    if (!C_sparse) { int* p0 = new int[nV + 1](); C_sparse = Utilities::createCSC(nV, nV, 0, new double[1](), new int[1](), p0); }      // L'R + R'L = 0: an empty matrix, not a failure
+    C_sparse.reset((L_sparse && R_sparse) ? Utilities::MatrixSymmetrizationProduct(L_sparse.get(), R_sparse.get()) : 0);
+    if (!C_sparse) { const std::vector<int> p0(nV + 1, 0); C_sparse.reset(Utilities::copyCSC(nV, nV, 0, 0, 0, p0.data())); }      // L'R + R'L = 0: an empty matrix, not a failure
     if (!Q_sparse || !A_sparse || !L_sparse || !R_sparse || !C_sparse) { clearSparse(); return FAILED_SWITCH_TO_SPARSE; }
     sparseSolver = true;
     loaded = true;
@@ -183,11 +168,11 @@ ReturnValue LCQProblem::switchToSparseMode()
     if (!loaded) return LCQPOBJECT_NOT_SETUP;
     if (sparseSolver) return SUCCESSFUL_RETURN;
     const int m = nC + 2 * nComp;
-    Q_sparse = Utilities::dns_to_csc(Q.data(), nV, nV);
-    A_sparse = Utilities::dns_to_csc(A.data(), m, nV);
-    L_sparse = Utilities::dns_to_csc(L.data(), nComp, nV);
-    R_sparse = Utilities::dns_to_csc(R.data(), nComp, nV);
-    C_sparse = Utilities::dns_to_csc(C.data(), nV, nV);
+    Q_sparse.reset(Utilities::dns_to_csc(Q.data(), nV, nV));
+    A_sparse.reset(Utilities::dns_to_csc(A.data(), m, nV));
+    L_sparse.reset(Utilities::dns_to_csc(L.data(), nComp, nV));
+    R_sparse.reset(Utilities::dns_to_csc(R.data(), nComp, nV));
+    C_sparse.reset(Utilities::dns_to_csc(C.data(), nV, nV));
     if (!Q_sparse || !A_sparse || !L_sparse || !R_sparse || !C_sparse) { clearSparse(); return FAILED_SWITCH_TO_SPARSE; }
     std::vector<double>().swap(Q); std::vector<double>().swap(A); std::vector<double>().swap(L);
     std::vector<double>().swap(R); std::vector<double>().swap(C);
@@ -199,53 +184,48 @@ ReturnValue LCQProblem::switchToDenseMode()
 {
     if (!loaded) return LCQPOBJECT_NOT_SETUP;
     if (!sparseSolver) return SUCCESSFUL_RETURN;
-    double *q = Utilities::csc_to_dns(Q_sparse), *a = Utilities::csc_to_dns(A_sparse), *l = Utilities::csc_to_dns(L_sparse);
-    double *r = Utilities::csc_to_dns(R_sparse), *c = Utilities::csc_to_dns(C_sparse);
-    const bool ok = q && a && l && r && c;
-    if (ok) {
-        const int m = nC + 2 * nComp;
-        Q.assign(q, q + (size_t)nV * nV); A.assign(a, a + (size_t)m * nV); L.assign(l, l + (size_t)nComp * nV);
-        R.assign(r, r + (size_t)nComp * nV); C.assign(c, c + (size_t)nV * nV);
-        clearSparse();
-        sparseSolver = false;
-    }
-    delete[] q; delete[] a; delete[] l; delete[] r; delete[] c;
-    return ok ? SUCCESSFUL_RETURN : FAILED_SWITCH_TO_DENSE;
+    std::vector<double> q, a, l, r, c;
+    if (!(Utilities::csc_to_dns(Q_sparse.get(), q) && Utilities::csc_to_dns(A_sparse.get(), a) && Utilities::csc_to_dns(L_sparse.get(), l) &&
+          Utilities::csc_to_dns(R_sparse.get(), r) && Utilities::csc_to_dns(C_sparse.get(), c))) return FAILED_SWITCH_TO_DENSE;
+    Q.swap(q); A.swap(a); L.swap(l); R.swap(r); C.swap(c);
+    clearSparse();
+    sparseSolver = false;
+    return SUCCESSFUL_RETURN;
 }
 
 void LCQProblem::mulQ(const double* v, double* out) const
 {
-    if (sparseSolver) { std::vector<double> z(nV, 0.0); Utilities::AffineLinearTransformation(1.0, Q_sparse, v, z.data(), out, nV); }
+    if (sparseSolver) { std::vector<double> z(nV, 0.0); Utilities::AffineLinearTransformation(1.0, Q_sparse.get(), v, z.data(), out, nV); }
     else Utilities::MatrixMultiplication(Q.data(), v, out, nV, nV, 1);
 }
 void LCQProblem::mulC(const double* v, double* out) const
 {
-    if (sparseSolver) { std::vector<double> z(nV, 0.0); Utilities::AffineLinearTransformation(1.0, C_sparse, v, z.data(), out, nV); }
+    if (sparseSolver) { std::vector<double> z(nV, 0.0); Utilities::AffineLinearTransformation(1.0, C_sparse.get(), v, z.data(), out, nV); }
     else Utilities::MatrixMultiplication(C.data(), v, out, nV, nV, 1);
 }
 void LCQProblem::mulAT(const double* y, double* out) const
 {
-    if (sparseSolver) Utilities::TransponsedMatrixMultiplication(A_sparse, y, out);
+    if (sparseSolver) Utilities::TransponsedMatrixMultiplication(A_sparse.get(), y, out);
     else Utilities::TransponsedMatrixMultiplication(A.data(), y, out, nC + 2 * nComp, nV, 1);
 }
 void LCQProblem::mulL(const double* v, double* out) const
 {
-    if (sparseSolver) Utilities::MatrixMultiplication(L_sparse, v, out);
+    if (sparseSolver) Utilities::MatrixMultiplication(L_sparse.get(), v, out);
     else Utilities::MatrixMultiplication(L.data(), v, out, nComp, nV, 1);
 }
 void LCQProblem::mulR(const double* v, double* out) const
 {
-    if (sparseSolver) Utilities::MatrixMultiplication(R_sparse, v, out);
+    if (sparseSolver) Utilities::MatrixMultiplication(R_sparse.get(), v, out);
     else Utilities::MatrixMultiplication(R.data(), v, out, nComp, nV, 1);
 }
 void LCQProblem::addLT(const double* y, double* out) const
 {
-    if (sparseSolver) Utilities::AddTransponsedMatrixMultiplication(L_sparse, y, out);
+    if (sparseSolver) Utilities::AddTransponsedMatrixMultiplication(L_sparse.get(), y, out);
     else Utilities::AddTransponsedMatrixMultiplication(L.data(), y, out, nComp, nV, 1);
 }
 void LCQProblem::addRT(const double* y, double* out) const
 {
-    if (sparseSolver) Utilities::AddTransponsedMatrixMultiplication(R_sparse, y, out);
+    if (sparseSolver) Utilities::AddTransponsedMatrixMultiplication(R_sparse.get(), y, out);
     else Utilities::AddTransponsedMatrixMultiplication(R.data(), y, out, nComp, nV, 1);
 }
 
@@ -268,7 +248,7 @@ ReturnValue LCQProblem::initializeSolver(bool needSubsolver)
         if (!sparseSolver) return DENSE_SPARSE_MISSMATCH;                              // :952-954
         nDuals = m; boxDualOffset = 0;                                                 // :934-935
     } else if (arm == HIP_DENSE) {
-        nDuals = nV + m; boxDualOffset = nV;     // new arm: dense kernels, problem held in either mode
+        nDuals = nV + m; boxDualOffset = nV;     // this backend's own arm: dense kernels, problem held in either mode
     } else {
         return NOT_YET_IMPLEMENTED;
     }
@@ -283,14 +263,11 @@ ReturnValue LCQProblem::initializeSolver(bool needSubsolver)
         // CSC problem data: the loop below runs on the CSC Utilities; the device subsolver of this arm is dense,
         // so it receives dense copies of Q and [A;L;R] (the reference hands the CSC arrays to qpOASES / OSQP instead,
         // src/LCQProblem.cpp:908-927,960)
-        double *q = Utilities::csc_to_dns(Q_sparse), *a = Utilities::csc_to_dns(A_sparse);
-        if (!q || !a) { delete[] q; delete[] a; return FAILED_SWITCH_TO_DENSE; }
-        Subsolver tmp(nV, m, q, a, HIP_DENSE, device);
-        subsolver = tmp;
-        delete[] q; delete[] a;
+        std::vector<double> q, a;
+        if (!(Utilities::csc_to_dns(Q_sparse.get(), q) && Utilities::csc_to_dns(A_sparse.get(), a))) return FAILED_SWITCH_TO_DENSE;
+        subsolver = Subsolver(nV, m, q.data(), a.data(), HIP_DENSE, device);
     } else {
-        Subsolver tmp(nV, m, Q.data(), A.data(), HIP_DENSE, device);
-        subsolver = tmp;
+        subsolver = Subsolver(nV, m, Q.data(), A.data(), HIP_DENSE, device);
     }
     if (needSubsolver) subsolver.setOptions(options.getHIPOptions());
     gTilde = g;
@@ -323,70 +300,64 @@ ReturnValue LCQProblem::initializeSolver(bool needSubsolver)
 // (scalars: |statk|inf, phi, rho, alphak, objective, merit, |pk|inf, QP iterations)
 void LCQProblem::finishFromTrace(const std::vector<double>& sc, const std::vector<double>& xs, int len)
 {
-    const PrintLevel pl = options.getPrintLevel();
     int outer = 0, inner = 0;
     for (int k = 0; k < len; ++k) {
         const double* s = &sc[(size_t)k * 8];
         if (k > 0 && s[2] != sc[(size_t)(k - 1) * 8 + 2]) { outer++; inner = 0; }      // a penalty update in the previous pass
         if (options.getStoreSteps())
             stats.updateTrackingVectors(&xs[(size_t)k * nV], inner, (int)s[7], s[3], s[6], s[0], s[4], s[1], s[5], nV);
-        if (pl != NONE && !(pl == OUTER_LOOP_ITERATES && inner > 0)) {
-            const bool in = pl >= INNER_LOOP_ITERATES;
-            if ((in && inner % 10 == 0) || (!in && outer % 10 == 0))
-                std::printf(in ? " outer |  inner |   station  |   complem  |     rho    |   norm p   |    alpha   | sub it\n"
-                               : " outer |   station  |   complem  |     rho    |   norm p\n");
-            std::printf("%6d", outer);
-            if (in) std::printf(" | %6d", inner);
-            std::printf(" | %10.3g | %10.3g | %10.3g | %10.3g", s[0], s[1], s[2], s[6]);
-            if (in) std::printf(" | %10.3g | %6d", s[3], (int)s[7]);
-            std::printf(" \n");
-        }
+        if (printsRow(inner)) printRow(outer, inner, s[0], s[1], s[2], s[6], s[3], (int)s[7]);
         inner++;
     }
-    if (pl != NONE) std::fflush(stdout);
+    if (options.getPrintLevel() != NONE) std::fflush(stdout);
+}
+
+lcqp_options_t LCQProblem::deviceOptions(bool& wantTrace) const
+{
+    lcqp_options_t o = options.getHIPOptions();
+    wantTrace = o.storeSteps != 0 || o.printLevel != 0;
+    o.storeSteps = wantTrace ? 1 : 0;
+    return o;
+}
+
+template <typename GetTrace>
+ReturnValue LCQProblem::finishDeviceRun(const lcqp_stats_t& st, bool wantTrace, int traceCap, GetTrace getTrace)
+{
+    stats.updateIterTotal(st.iterTotal); stats.updateIterOuter(st.iterOuter); stats.updateSubproblemIter(st.subproblemIter);
+    stats.updateRhoOpt(st.rhoOpt); stats.updateQPSolverExitFlag(st.qpSolverExitFlag);
+    algoStat = (AlgorithmStatus)st.status;
+    stats.updateSolutionStatus(algoStat);
+    if (wantTrace) {
+        const int cap = std::min(st.iterTotal + 1, traceCap);
+        std::vector<double> sc((size_t)cap * 8), xs((size_t)cap * nV);
+        int len = 0;
+        if (!getTrace(cap, sc.data(), xs.data(), &len)) finishFromTrace(sc, xs, len);
+    }
+    return (ReturnValue)st.returnValue;
 }
 
 ReturnValue LCQProblem::runOnDevice()
 {
     const int m = nC + 2 * nComp;
-    double *q = 0, *a = 0, *l = 0, *r = 0;
-    if (sparseSolver) {
-        q = Utilities::csc_to_dns(Q_sparse); a = Utilities::csc_to_dns(A_sparse); l = Utilities::csc_to_dns(L_sparse); r = Utilities::csc_to_dns(R_sparse);
-        if (!q || !a || !l || !r) { delete[] q; delete[] a; delete[] l; delete[] r; return FAILED_SWITCH_TO_DENSE; }
-    }
-    const double *Qd = sparseSolver ? q : Q.data(), *Ad = sparseSolver ? a : A.data(), *Ld = sparseSolver ? l : L.data(), *Rd = sparseSolver ? r : R.data();
-    lcqp_hip_batch_t* bt = lcqp_hip_batch_create(1, nV, nC, nComp, haveBox ? 1 : 0, device);
-    ReturnValue ret = SUBPROBLEM_SOLVER_ERROR;
-    if (bt) {
-        lcqp_options_t o = options.getHIPOptions();
-        const bool wantTrace = o.storeSteps != 0 || o.printLevel != 0;
-        o.storeSteps = wantTrace ? 1 : 0;
-        int rc = lcqp_hip_batch_set_options(bt, &o);
-        if (!rc) rc = lcqp_hip_batch_load(bt, 0, 1, Qd, g.data(), Ld, Rd, haveLbL ? lbL.data() : 0, &ubA[nC], haveLbR ? lbR.data() : 0, &ubA[nC + nComp],
-                                          nC > 0 ? Ad : 0, lbA.data(), ubA.data(), haveBox ? lb.data() : 0, haveBox ? ub.data() : 0, xk.data(),
-                                          haveYk ? y0Full.data() : 0);
-        if (!rc) rc = lcqp_hip_batch_run(bt);
-        lcqp_stats_t st;
-        std::memset(&st, 0, sizeof(st));
-        yk.assign(nV + m, 0.0);
-        if (!rc) rc = lcqp_hip_batch_get_solution(bt, xk.data(), yk.data(), &st);
-        if (!rc) {
-            stats.updateIterTotal(st.iterTotal); stats.updateIterOuter(st.iterOuter); stats.updateSubproblemIter(st.subproblemIter);
-            stats.updateRhoOpt(st.rhoOpt); stats.updateQPSolverExitFlag(st.qpSolverExitFlag);
-            algoStat = (AlgorithmStatus)st.status;
-            stats.updateSolutionStatus(algoStat);
-            if (wantTrace) {
-                const int cap = std::min(st.iterTotal + 1, 1024);
-                std::vector<double> sc((size_t)cap * 8), xs((size_t)cap * nV);
-                int len = 0;
-                if (!lcqp_hip_batch_get_trace(bt, 0, cap, sc.data(), xs.data(), &len)) finishFromTrace(sc, xs, len);
-            }
-            ret = (ReturnValue)st.returnValue;
-        }
-        lcqp_hip_batch_destroy(bt);
-    }
-    delete[] q; delete[] a; delete[] l; delete[] r;
-    return ret;
+    std::vector<double> q, a, l, r;
+    if (sparseSolver && !(Utilities::csc_to_dns(Q_sparse.get(), q) && Utilities::csc_to_dns(A_sparse.get(), a) &&
+                          Utilities::csc_to_dns(L_sparse.get(), l) && Utilities::csc_to_dns(R_sparse.get(), r))) return FAILED_SWITCH_TO_DENSE;
+    const double *Qd = sparseSolver ? q.data() : Q.data(), *Ad = sparseSolver ? a.data() : A.data(), *Ld = sparseSolver ? l.data() : L.data(), *Rd = sparseSolver ? r.data() : R.data();
+    const BatchHandle bt(lcqp_hip_batch_create(1, nV, nC, nComp, haveBox ? 1 : 0, device));
+    if (!bt) return SUBPROBLEM_SOLVER_ERROR;
+    bool wantTrace;
+    const lcqp_options_t o = deviceOptions(wantTrace);
+    int rc = lcqp_hip_batch_set_options(bt.get(), &o);
+    if (!rc) rc = lcqp_hip_batch_load(bt.get(), 0, 1, Qd, g.data(), Ld, Rd, haveLbL ? lbL.data() : 0, &ubA[nC], haveLbR ? lbR.data() : 0, &ubA[nC + nComp],
+                                      nC > 0 ? Ad : 0, lbA.data(), ubA.data(), haveBox ? lb.data() : 0, haveBox ? ub.data() : 0, xk.data(),
+                                      haveYk ? y0Full.data() : 0);
+    if (!rc) rc = lcqp_hip_batch_run(bt.get());
+    lcqp_stats_t st;
+    std::memset(&st, 0, sizeof(st));
+    yk.assign(nV + m, 0.0);
+    if (!rc) rc = lcqp_hip_batch_get_solution(bt.get(), xk.data(), yk.data(), &st);
+    if (rc) return SUBPROBLEM_SOLVER_ERROR;
+    return finishDeviceRun(st, wantTrace, 1024, [&](int cap, double* sc, double* xs, int* len) { return lcqp_hip_batch_get_trace(bt.get(), 0, cap, sc, xs, len); });
 }
 
 // OSQP_SPARSE arm with CSC data: the sparse engine (lcqp_hip_sparse_*, band LDL' of the KKT matrix) when the pattern is banded; the
@@ -395,39 +366,22 @@ ReturnValue LCQProblem::runOnDevice()
 bool LCQProblem::runSparseOnDevice(ReturnValue& ret)
 {
     if (!sparseSolver) return false;
-    lcqp_hip_sparse_t* sb = lcqp_hip_sparse_create(1, nV, nC, nComp, Q_sparse->p, Q_sparse->i, A_sparse->p, A_sparse->i, device);
+    const SparseHandle sb(lcqp_hip_sparse_create(1, nV, nC, nComp, Q_sparse->p, Q_sparse->i, A_sparse->p, A_sparse->i, device));
     if (!sb) return false;                        // not a banded pattern (lcqp_hip_sparse_last_error says so)
-    const int m = nC + 2 * nComp;
-    lcqp_options_t o = options.getHIPOptions();
-    const bool wantTrace = o.storeSteps != 0 || o.printLevel != 0;
-    o.storeSteps = wantTrace ? 1 : 0;
-    int rc = lcqp_hip_sparse_set_options(sb, &o);
-    if (rc) { lcqp_hip_sparse_destroy(sb); return false; }      // e.g. nDynamicPenalty > 64: the host loop takes it
-    rc = lcqp_hip_sparse_load(sb, 0, 1, Q_sparse->x, g.data(), A_sparse->x, lbA.data(), ubA.data(), haveLbL ? lbL.data() : 0, &ubA[nC],
-                              haveLbR ? lbR.data() : 0, &ubA[nC + nComp], xk.data(), haveYk ? yk.data() : 0);
-    if (rc > 0 && rc < LCQP_HIP_ERROR) { lcqp_hip_sparse_destroy(sb); ret = (ReturnValue)rc; lastEngine = ENGINE_SPARSE_DEVICE; return true; }      // the reference's own code for bad problem data
-    if (!rc) rc = lcqp_hip_sparse_run(sb);
+    bool wantTrace;
+    const lcqp_options_t o = deviceOptions(wantTrace);
+    if (lcqp_hip_sparse_set_options(sb.get(), &o)) return false;      // e.g. nDynamicPenalty > 64: the host loop takes it
+    lastEngine = ENGINE_SPARSE_DEVICE;
+    int rc = lcqp_hip_sparse_load(sb.get(), 0, 1, Q_sparse->x, g.data(), A_sparse->x, lbA.data(), ubA.data(), haveLbL ? lbL.data() : 0, &ubA[nC],
+                                  haveLbR ? lbR.data() : 0, &ubA[nC + nComp], xk.data(), haveYk ? yk.data() : 0);
+    if (rc > 0 && rc < LCQP_HIP_ERROR) { ret = (ReturnValue)rc; return true; }      // the reference's own code for bad problem data
+    if (!rc) rc = lcqp_hip_sparse_run(sb.get());
     lcqp_stats_t st;
     std::memset(&st, 0, sizeof(st));
-    yk.assign(m, 0.0);
-    if (!rc) rc = lcqp_hip_sparse_get_solution(sb, xk.data(), yk.data(), &st);
-    if (!rc) {
-        stats.updateIterTotal(st.iterTotal); stats.updateIterOuter(st.iterOuter); stats.updateSubproblemIter(st.subproblemIter);
-        stats.updateRhoOpt(st.rhoOpt); stats.updateQPSolverExitFlag(st.qpSolverExitFlag);
-        algoStat = (AlgorithmStatus)st.status;
-        stats.updateSolutionStatus(algoStat);
-        if (wantTrace) {
-            const int cap = std::min(st.iterTotal + 1, 4096);
-            std::vector<double> sc((size_t)cap * 8), xs((size_t)cap * nV);
-            int len = 0;
-            if (!lcqp_hip_sparse_get_trace(sb, 0, cap, sc.data(), xs.data(), &len)) finishFromTrace(sc, xs, len);
-        }
-        ret = (ReturnValue)st.returnValue;
-    } else {
-        ret = SUBPROBLEM_SOLVER_ERROR;
-    }
-    lcqp_hip_sparse_destroy(sb);
-    lastEngine = ENGINE_SPARSE_DEVICE;
+    yk.assign(nC + 2 * nComp, 0.0);
+    if (!rc) rc = lcqp_hip_sparse_get_solution(sb.get(), xk.data(), yk.data(), &st);
+    ret = rc ? SUBPROBLEM_SOLVER_ERROR
+             : finishDeviceRun(st, wantTrace, 4096, [&](int cap, double* sc, double* xs, int* len) { return lcqp_hip_sparse_get_trace(sb.get(), 0, cap, sc, xs, len); });
     return true;
 }
 
@@ -631,18 +585,26 @@ void LCQProblem::storeSteps()
 
 void LCQProblem::printIteration()
 {
+    if (printsRow(innerIter)) printRow(outerIter, innerIter, Utilities::MaxAbs(statk.data(), nV), getPhi(), rho, Utilities::MaxAbs(pk.data(), nV), alphak, qpIterk);
+}
+
+bool LCQProblem::printsRow(int inner) const
+{
     const PrintLevel pl = options.getPrintLevel();
-    if (pl == NONE) return;
-    if (pl == OUTER_LOOP_ITERATES && innerIter > 0) return;
-    const bool inner = pl >= INNER_LOOP_ITERATES;
-    if ((inner && innerIter % 10 == 0) || (!inner && outerIter % 10 == 0)) {
-        std::printf(inner ? " outer |  inner |   station  |   complem  |     rho    |   norm p   |    alpha   | sub it\n"
-                          : " outer |   station  |   complem  |     rho    |   norm p\n");
-    }
-    std::printf("%6d", outerIter);
-    if (inner) std::printf(" | %6d", innerIter);
-    std::printf(" | %10.3g | %10.3g | %10.3g | %10.3g", Utilities::MaxAbs(statk.data(), nV), getPhi(), rho, Utilities::MaxAbs(pk.data(), nV));
-    if (inner) std::printf(" | %10.3g | %6d", alphak, qpIterk);
+    return pl != NONE && !(pl == OUTER_LOOP_ITERATES && inner > 0);
+}
+
+// one row of the iteration table (src/LCQProblem.cpp:1528-1576), under its header every ten rows: the host loop and the device trace print here
+void LCQProblem::printRow(int outer, int inner, double stat, double phi, double rho_, double normP, double alpha, int qpIter) const
+{
+    const bool in = options.getPrintLevel() >= INNER_LOOP_ITERATES;
+    if ((in && inner % 10 == 0) || (!in && outer % 10 == 0))
+        std::printf(in ? " outer |  inner |   station  |   complem  |     rho    |   norm p   |    alpha   | sub it\n"
+                       : " outer |   station  |   complem  |     rho    |   norm p\n");
+    std::printf("%6d", outer);
+    if (in) std::printf(" | %6d", inner);
+    std::printf(" | %10.3g | %10.3g | %10.3g | %10.3g", stat, phi, rho_, normP);
+    if (in) std::printf(" | %10.3g | %6d", alpha, qpIter);
     std::printf(" \n");
 }
 

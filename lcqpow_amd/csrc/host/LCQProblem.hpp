@@ -19,7 +19,7 @@ namespace LCQPow {
 
 class LCQProblem {
   public:
-    LCQProblem();
+    LCQProblem() = default;
     LCQProblem(int nV, int nC, int nComp);
 
     ReturnValue loadLCQP(const double* const Q, const double* const g, const double* const L, const double* const R,
@@ -41,9 +41,6 @@ class LCQProblem {
     // src/LCQProblem.cpp:1037-1102: convert the stored problem between dense arrays and CSC
     ReturnValue switchToSparseMode();
     ReturnValue switchToDenseMode();
-    ~LCQProblem();
-    LCQProblem(const LCQProblem&) = delete;
-    LCQProblem& operator=(const LCQProblem&) = delete;
     ReturnValue runSolver();
     AlgorithmStatus getPrimalSolution(double* const xOpt) const;
     AlgorithmStatus getDualSolution(double* const yOpt) const;
@@ -66,6 +63,10 @@ class LCQProblem {
                             const double* ubA, const double* lb, const double* ub, const double* x0, const double* y0);      // bounds, guess: shared by the dense and the CSC loader
     ReturnValue runOnDevice();                 // HIP_DENSE: LCQProblem::runSolver as one batch-of-one launch of k_lcqp_run
     bool runSparseOnDevice(ReturnValue& ret);  // OSQP_SPARSE with a banded or bordered pattern: k_sparse_sched; false when the pattern is not banded
+    // what the two device arms share: the options of a device run (storeSteps set when a trace is wanted), and the way from its lcqp_stats_t
+    // and its trace -- getTrace(cap, scalars, x, &len), at most traceCap iterates -- to stats, algoStat, the printed table and the ReturnValue
+    lcqp_options_t deviceOptions(bool& wantTrace) const;
+    template <typename GetTrace> ReturnValue finishDeviceRun(const lcqp_stats_t& st, bool wantTrace, int traceCap, GetTrace getTrace);
     void finishFromTrace(const std::vector<double>& sc, const std::vector<double>& xs, int len);
     ReturnValue solveQPSubproblem(bool initialSolve);
     void updateLinearization();
@@ -78,6 +79,8 @@ class LCQProblem {
     void determineStationarityType();
     void storeSteps();
     void printIteration();
+    bool printsRow(int inner) const;          // the print level asks for a row at this inner iterate
+    void printRow(int outer, int inner, double stat, double phi, double rho, double normP, double alpha, int qpIter) const;
     double getPhi();
     double getObj();
     double getMerit();
@@ -90,19 +93,19 @@ class LCQProblem {
     void mulR(const double* v, double* out) const;      // out = R v
     void addLT(const double* y, double* out) const;     // out += L' y
     void addRT(const double* y, double* out) const;     // out += R' y
-    void clearSparse();
+    void clearSparse() { Q_sparse.reset(); A_sparse.reset(); L_sparse.reset(); R_sparse.reset(); C_sparse.reset(); }
 
-    int nV, nC, nComp, nDuals, boxDualOffset, device;
-    bool loaded, haveYk, haveLbL, haveLbR, haveBox, sparseSolver, hostLoop;
+    int nV = 0, nC = 0, nComp = 0, nDuals = 0, boxDualOffset = 0, device = 0;
+    bool loaded = false, haveYk = false, haveLbL = false, haveLbR = false, haveBox = false, sparseSolver = false, hostLoop = false;
     int lastEngine = ENGINE_NONE;
     std::vector<double> y0Full, ysub;   // y0 as loaded (reference layout nV + nC + 2 nComp); subsolver dual vector (box duals first)
-    csc *Q_sparse, *A_sparse, *L_sparse, *R_sparse, *C_sparse;
-    std::vector<double> Q, g, L, R, A, lbA, ubA, lb, ub, lbL, lbR, C, Qk;
+    CscPtr Q_sparse, A_sparse, L_sparse, R_sparse, C_sparse;      // the problem in CSC mode; the owners make the class move-only
+    std::vector<double> Q, g, L, R, A, lbA, ubA, lb, ub, lbL, lbR, C;
     std::vector<double> gTilde, gPhi, xk, yk, ykA, gk, xnew, pk, statk, constrStatk, lkTmp, Qx, Cx, Qp, Cp;
-    double phiConst, alphak, rho;
-    int outerIter, innerIter, totalIter, qpIterk, qpSolverExitFlag;
-    unsigned long long perturbCounter;
-    AlgorithmStatus algoStat;
+    double phiConst = 0.0, alphak = 1.0, rho = 0.0;
+    int outerIter = 0, innerIter = 0, totalIter = 0, qpIterk = 0, qpSolverExitFlag = 0;
+    unsigned long long perturbCounter = 0;
+    AlgorithmStatus algoStat = PROBLEM_NOT_SOLVED;
     std::deque<double> complHistory;
     Options options;
     OutputStatistics stats;

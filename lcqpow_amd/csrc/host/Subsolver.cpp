@@ -2,28 +2,9 @@
 
 namespace LCQPow {
 
-Subsolver::Subsolver() : qpSolver(HIP_DENSE) {}
-
 Subsolver::Subsolver(int nV, int nC, const double* Q, const double* A, QPSolver _qpSolver, int device) : qpSolver(_qpSolver)
 {
-    if (qpSolver == HIP_DENSE) {
-        SubsolverHIP tmp(nV, nC, Q, A, device);
-        solverHIP = tmp;
-    }
-}
-
-Subsolver::Subsolver(const Subsolver& rhs) { copy(rhs); }
-
-Subsolver& Subsolver::operator=(const Subsolver& rhs)
-{
-    if (this != &rhs) copy(rhs);
-    return *this;
-}
-
-void Subsolver::copy(const Subsolver& rhs)
-{
-    qpSolver = rhs.qpSolver;
-    if (qpSolver == HIP_DENSE) solverHIP = rhs.solverHIP;
+    if (qpSolver == HIP_DENSE) solverHIP = SubsolverHIP(nV, nC, Q, A, device);
 }
 
 void Subsolver::getSolution(double* x, double* y)

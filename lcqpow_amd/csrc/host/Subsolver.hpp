@@ -10,10 +10,9 @@ namespace LCQPow {
 
 class Subsolver {
   public:
-    Subsolver();
+    // copy and move are the members': a copy clones the QP object (SubsolverHIP), a move hands it on
+    Subsolver() = default;
     Subsolver(int nV, int nC, const double* Q, const double* A, QPSolver qpSolver = HIP_DENSE, int device = 0);
-    Subsolver(const Subsolver& rhs);
-    Subsolver& operator=(const Subsolver& rhs);
 
     void getSolution(double* x, double* y);
     ReturnValue solve(bool initialSolve, int& iterations, int& exit_flag, const double* g, const double* lbA,
@@ -22,8 +21,7 @@ class Subsolver {
     void setOptions(const lcqp_options_t& options);
 
   private:
-    void copy(const Subsolver& rhs);
-    QPSolver qpSolver;
+    QPSolver qpSolver = HIP_DENSE;
     SubsolverHIP solverHIP;
 };
 

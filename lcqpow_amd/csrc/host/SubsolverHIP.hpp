@@ -4,19 +4,21 @@
 #ifndef LCQPOW_AMD_SUBSOLVERHIP_HPP
 #define LCQPOW_AMD_SUBSOLVERHIP_HPP
 
+#include "HipHandles.hpp"
 #include "SubsolverBase.hpp"
-#include "lcqp_hip.h"
 
 namespace LCQPow {
 
 class SubsolverHIP : public SubsolverBase {
   public:
-    SubsolverHIP();
+    SubsolverHIP() = default;
     // nC = number of stacked rows nC + 2*nComp, Q (nV x nV) and A (nC x nV) row-major; deep copies
     SubsolverHIP(int nV, int nC, const double* Q, const double* A, int device = 0);
+    // copies clone the QP object (the reference's surface, lcqp_hip_qp_clone); moves hand the one object on
     SubsolverHIP(const SubsolverHIP& rhs);
-    virtual ~SubsolverHIP();
     SubsolverHIP& operator=(const SubsolverHIP& rhs);
+    SubsolverHIP(SubsolverHIP&&) = default;
+    SubsolverHIP& operator=(SubsolverHIP&&) = default;
 
     void setOptions(const lcqp_options_t& options);
     ReturnValue solve(bool initialSolve, int& iterations, int& exit_flag, const double* const g,
@@ -31,8 +33,7 @@ class SubsolverHIP : public SubsolverBase {
     ReturnValue getAdjoint(const double* vx, const double* vy, double* dg, double* db = 0, int* side = 0, int* info = 0, double* dQ = 0, double* dA = 0);
 
   private:
-    void clear();
-    lcqp_hip_qp_t* qp;
+    QpHandle qp;
 };
 
 }  // namespace LCQPow

@@ -158,16 +158,25 @@ void Utilities::ClearSparseMat(csc** M)
     *M = 0;
 }
 
-double* Utilities::csc_to_dns(const csc* S)
+bool Utilities::csc_to_dns(const csc* S, std::vector<double>& full)
 {
     const int m = S->m, n = S->n;
-    double* full = new double[(size_t)m * n]();
+    full.assign((size_t)m * n, 0.0);
     for (int c = 0; c < n; ++c)
         for (int k = S->p[c]; k < S->p[c + 1]; ++k) {
-            if (k == S->nzmax) return full;
-            if (S->i[k] < 0 || S->i[k] >= m) { delete[] full; return 0; }   // INDEX_OUT_OF_BOUNDS
+            if (k == S->nzmax) return true;
+            if (S->i[k] < 0 || S->i[k] >= m) return false;   // INDEX_OUT_OF_BOUNDS
             full[(size_t)S->i[k] * n + c] = S->x[k];
         }
+    return true;
+}
+
+double* Utilities::csc_to_dns(const csc* S)
+{
+    std::vector<double> v;
+    if (!csc_to_dns(S, v)) return 0;
+    double* full = new double[v.size()];
+    std::copy(v.begin(), v.end(), full);
     return full;
 }
 

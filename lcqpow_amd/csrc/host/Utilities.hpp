@@ -1,12 +1,15 @@
 // Host-side enums, constants and dense helpers with the names and argument meaning of the reference's
 // Utilities (include/Utilities.hpp:37-129,140-328,350-362; src/Utilities.cpp:38-265).  Written from
-// scratch for this backend: std::vector-free, row-major, no qpOASES/OSQP types.  The sparse (csc) half of the
-// reference's Utilities (src/Utilities.cpp:49-59,75-82,118-173,189-199,228-241,593-650) is declared below as well.
+// scratch for this backend: row-major, no qpOASES/OSQP types.  The sparse (csc) half of the
+// reference's Utilities (src/Utilities.cpp:49-59,75-82,118-173,189-199,228-241,593-650) is declared below as well,
+// with the reference's raw-pointer contracts; CscPtr at the end is the owner the host classes hold a csc through.
 #ifndef LCQPOW_AMD_UTILITIES_HPP
 #define LCQPOW_AMD_UTILITIES_HPP
 
 #include <cmath>
 #include <cstddef>
+#include <memory>
+#include <vector>
 
 namespace LCQPow {
 
@@ -102,7 +105,8 @@ class Utilities {
     static csc* copyCSC(int m, int n, int nnx, const double* x, const int* i, const int* p);
     static csc* copyCSC(const csc* M, bool toUpperTriangular = false);
     static void ClearSparseMat(csc** M);
-    static double* csc_to_dns(const csc* sparse);                                      // new[]; caller delete[]s
+    static double* csc_to_dns(const csc* sparse);                                      // new[]; caller delete[]s; 0 for a row index out of range
+    static bool csc_to_dns(const csc* sparse, std::vector<double>& full);              // the same into a vector; false for a row index out of range
     static csc* dns_to_csc(const double* full, int m, int n);
     static void MatrixMultiplication(const csc* A, const double* b, double* c);       // c = A b
     static void TransponsedMatrixMultiplication(const csc* A, const double* b, double* c);      // c = A' b
@@ -111,6 +115,10 @@ class Utilities {
     static void AffineLinearTransformation(double alpha, const csc* S, const double* b, const double* c, double* d, int m);
     static double QuadraticFormProduct(const csc* S, const double* p, int m);
 };
+
+// owner of a csc whose storage ClearSparseMat may release (createCSC, copyCSC, dns_to_csc, MatrixSymmetrizationProduct)
+struct CscDeleter { void operator()(csc* M) const { Utilities::ClearSparseMat(&M); } };
+using CscPtr = std::unique_ptr<csc, CscDeleter>;
 
 }  // namespace LCQPow
 #endif

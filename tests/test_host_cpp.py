@@ -1,5 +1,6 @@
 """The C++ host layer (lcqpow_amd/csrc/host: LCQProblem, Subsolver, SubsolverHIP, Options, OutputStatistics,
-Utilities, BatchLCQProblem) through its own C++ test driver tests/cpp/host_tests.cpp."""
+Utilities, BatchLCQProblem) through its own C++ test driver tests/cpp/host_tests.cpp, and its ownership of CSC matrices, handles and
+batch objects through tests/cpp/host_owner_test.cpp."""
 import os
 import subprocess
 
@@ -7,6 +8,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EXE = os.path.join(ROOT, "tests", "cpp", "host_tests")
+OWNER_EXE = os.path.join(ROOT, "tests", "cpp", "host_owner_test")
 
 
 def _exe():
@@ -19,6 +21,17 @@ def _exe():
 def test_host_layer_cpu():
     """Utilities known answers (test/RunUnitTests.cpp:33-246), Options validation, OutputStatistics"""
     r = subprocess.run([_exe(), "cpu"], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout + r.stderr
+
+
+def test_host_layer_ownership():
+    """tests/cpp/host_owner_test.cpp: the host sources under AddressSanitizer and UBSan against a fake C ABI that counts handles -- a CSC load
+    with an empty C, mode switches, every exit of the two device arms, one QP object and no clone per initializeSolver, a mixed batch with
+    a bucket that could not be created, a pipeline destroyed in flight; no handle outlives its scenario.  A stand-alone program: no GPU."""
+    if not os.path.exists(OWNER_EXE):
+        import __graft_entry__ as g
+        g.build_host_tests()
+    r = subprocess.run([OWNER_EXE], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and "ALL PASSED" in r.stdout, r.stdout + r.stderr
 
 
