@@ -18,13 +18,21 @@ one makes it infeasible.
 Mutations: a corrupted phi, objective, merit, stationarity norm, step norm (scalars[k][6]) or QP iteration count fails exactly its
 quantity at exactly its row.  A moved x_k, alpha_k or rho_k is read by other quantities as well (x_k by everything in rows k and k + 1,
 alpha_k by the step norm and the stationarity norm, rho_k by merit, stationarity and the decisions): there the test asserts that the
-quantity fails and that nothing fails outside the rows and quantities that read the corrupted value."""
+quantity fails and that nothing fails outside the rows and quantities that read the corrupted value.
+
+The option sets (tests/test_gpu_trace_audit_options.py, tests/test_gpu_sparse_trace_audit_options.py: the problems and options the
+device tests run, chosen here): every case passes the audit on the oracle, reaches its branch (TGO.assert_branch on the audit's counters)
+and stays under the cap on every instance.  What had to be chosen for the cap, and the two cases of the circle that no input brings under
+it (they run for their decisions and are exempt from it), is written where the instances are made (the two files).  The oracle's window
+of 64 fills on one problem, the mid-shape instance of the general LDL' engine, and on no other."""
 import numpy as np
 import pytest
 
 import problems as P
 import test_gpu_sparse_trace_audit as TS
+import test_gpu_sparse_trace_audit_options as TSO
 import test_gpu_trace_audit as TG
+import test_gpu_trace_audit_options as TGO
 import trace_audit_ref as TA
 
 RES_TOL = 1e-12      # oracle/lcqp_oracle.c, orc_options_default: resTol; qp_polish accepts at max(resTol (1 + |g|_inf), 64 eps scale)
@@ -228,3 +236,110 @@ def test_the_gtil_rule_is_visible_to_the_step_length(oracle):
         assert set(r.failed()) <= {"alpha"}
         hit += bool(r.failures)
     assert hit > 0
+
+
+# ---- the option sets of tests/test_gpu_trace_audit_options.py and test_gpu_sparse_trace_audit_options.py, on the oracle ----------------------
+OPTION_CASES = [("dense " + shape, oset) for shape, oset in TGO.CASES] + [("sparse " + engine, oset) for engine, oset in TSO.CASES if engine != "lanes 32"]
+_OPTION_RUNS = {}
+
+
+def option_runs(oracle, group, oset):
+    """[(d, opt, result, x_start, rho_start, False, instance)] of an option case: the problems the device tests load (the sparse ones
+    densified, "lanes 32" being the problems of "lanes 8"), solved once by the dense oracle under the set's options"""
+    if (group, oset) not in _OPTION_RUNS:
+        arm, name = group.split(" ", 1)
+        ds = TGO.option_instances(name, oset) if arm == "dense" else [TSO.densified(d) for d in TSO.option_instances(name, oset)]
+        opt = TGO.options(oracle, oset) if arm == "dense" else TSO.options(oracle, name, oset)
+        if arm == "sparse" and name == "general ldl" and oset in TSO.LONG_SETS:
+            ds = ds[:1]      # (the one the device test audits)
+        _OPTION_RUNS[group, oset] = [(d, opt, P.oracle_solve(oracle, d, opt, trace=400), d.get("x0"), opt.initialPenaltyParameter, False, b) for b, d in enumerate(ds)]
+    return _OPTION_RUNS[group, oset]
+
+
+@pytest.mark.parametrize("group,oset", OPTION_CASES, ids=["%s-%s" % c for c in OPTION_CASES])
+def test_oracle_traces_pass_the_audit_under_the_options(oracle, group, oset):
+    """every quantity of every row under the option set, the branch the set is there for, and the cap of undecidable rows per instance"""
+    results, rets = [], []
+    for run in option_runs(oracle, group, oset):
+        r = audit_run(run)
+        rows = len(run[2]["trace_scalars"]) - 1
+        print(f"    {group}, {oset}, instance {run[6]}: ret {run[2]['ret']} rows {rows + 1} rho -> {run[2]['stats']['rhoOpt']:g} step length decided {r.decided} "
+              f"undecidable {r.undecidable} Leyffer updates {r.leyffer_fired} full-window rows {r.window_shifts} penalty updates {r.updates} double {r.double_updates}")
+        assert not r.failures, (group, oset, run[6], r.failures)
+        assert r.decided + r.undecidable == rows
+        if not (group.startswith("sparse") and (group.split(" ", 1)[1], oset) in TSO.CAP_EXEMPT):      # (the circle cut at 8 rows: TSO.CAP_EXEMPT says why)
+            assert r.undecidable <= CAP_SHARE * rows and r.decided >= MIN_DECIDED, (group, oset, run[6], rows, r.decided, r.undecidable)
+        results.append(r); rets.append(run[2]["ret"])
+    case = (group.split(" ", 1)[1], oset)
+    TGO.assert_branch(oset, results, rets, double=group.startswith("sparse") and case in TSO.DOUBLE_UPDATE, fills=group.startswith("sparse") and case in TSO.FILLS_64)
+
+
+@pytest.mark.parametrize("group", ["dense nch1", "sparse lanes 8"])
+@pytest.mark.parametrize("oset", list(TGO.EXPECT_RET))
+def test_a_run_that_did_not_converge_returns_the_duals_of_its_last_qp(oracle, group, oset):
+    """the check the device tests make on the runs that end with 200 and 201 (TA.last_qp_duals), on the oracle; and it bites: the duals in
+    the stationarity of the QP before are outside the bound"""
+    for run in option_runs(oracle, group, oset):
+        d, opt, ro = run[:3]
+        r, bound, r_before = TA.last_qp_duals(d, ro["trace_scalars"], ro["trace_x"], run[3], run[4], ro["y"], "dense", RES_TOL)
+        assert r <= bound < r_before, (group, oset, run[6], r, bound, r_before)
+
+
+def test_the_double_update_is_formed_one_factor_at_a_time(oracle):
+    """f = 10 from rho = 0.01: rho f formed in long double is no float64 at all (the comparison the audit used to make refused every
+    update of this sequence); the audit forms rho f and (rho f) f in float64 as the loops do, and refuses a rho that is one ulp off"""
+    assert TA.LD(0.01) * TA.LD(10.0) != TA.LD(0.01 * 10.0)
+    run = next(r for r in option_runs(oracle, "dense nch1", "6 rho 1 factor 10") if r[2]["stats"]["iterOuter"] > 0 and r[2]["trace_scalars"][-1, 2] > 1.0)
+    sc = run[2]["trace_scalars"].copy()
+    k = int(np.nonzero(np.diff(sc[:, 2]) > 0)[0][0]) + 1
+    sc[k:, 2] = np.nextafter(sc[k:, 2], np.inf)
+    assert ("rho", k) in {f[:2] for f in audit_run(run, scalars=sc).failures}
+
+
+def _as_dict(opt, **kw):
+    return dict({name: getattr(opt, name) for name, _ in opt._fields_}, **kw)
+
+
+def test_a_corrupted_rho_after_a_leyffer_update_fails_the_decisions(oracle):
+    """window of 1 (set 3).  Inside a trace rho_k is read by merit, stationarity and step length as well, so the rho that only the
+    decisions read is the one behind the last row: the trace is cut behind a row whose Leyffer test fired -- the rows, statistics and
+    options of the same run under maxIterations = that row, which ends there with 200 and rhoOpt = rho f -- and audits clean; with rhoOpt
+    left at the rho before the update, or one factor too far, it fails `decisions` and nothing else"""
+    hit = 0
+    for run in option_runs(oracle, "dense nch1", "3 window of 1"):
+        d, opt, ro, x_start, rho_start, warm = run[:6]
+        sc, xs, f = ro["trace_scalars"], ro["trace_x"], opt.penaltyUpdateFactor
+        full = audit_run(run)
+        assert not full.failures
+        for k in range(2, len(sc) - 1):
+            cut = lambda **kw: TA.audit(d, _as_dict(opt, maxIterations=k), sc[:k + 1], xs[:k + 1], x_start, rho_start, warm, "after_first_update", RES_TOL,
+                                        stats=dict(ro["stats"], iterTotal=k + 1, subproblemIter=int(sc[:k + 1, 7].sum()), returnValue=200,
+                                                   iterOuter=int(round(np.log(sc[k + 1, 2] / sc[0, 2]) / np.log(f))), **kw), x_ret=xs[k], check=False)
+            r = cut(rhoOpt=float(sc[k + 1, 2]))
+            if r.leyffer_fired == 0 or sc[k + 1, 2] != sc[k, 2] * f or TA._cmp_lt(sc[k, 0], opt.stationarityTolerance, full.records[k]["stat"][2]) is not False:
+                continue      # rows whose one update is the Leyffer update of row k itself
+            assert not r.failures, r.failures
+            for wrong in (float(sc[k, 2]), float(sc[k + 1, 2] * f)):
+                r = cut(rhoOpt=wrong)
+                assert r.failed() == ["decisions"] and {x[1] for x in r.failures} <= {k, None}, r.failures      # (None: iterOuter against the sequence)
+            hit += 1
+    assert hit > 0
+
+
+def test_a_corrupted_last_row_of_a_run_that_hit_max_iterations_fails_the_decisions(oracle):
+    """set 7, return value 200: the returned x one ulp off the last row; the last row missing from the trace; the last row recorded
+    twice.  Each fails `decisions` and nothing else"""
+    for run in option_runs(oracle, "dense nch1", "7 maxIterations") + option_runs(oracle, "sparse lanes 8", "7 maxIterations"):
+        d, opt, ro, x_start, rho_start, warm = run[:6]
+        sc, xs = ro["trace_scalars"], ro["trace_x"]
+        assert ro["ret"] == 200 and len(sc) == opt.maxIterations + 1 and not audit_run(run).failures
+        go = lambda sc, xs, x: TA.audit(d, opt, sc, xs, x_start, rho_start, warm, "after_first_update", RES_TOL, stats=ro["stats"], x_ret=x, check=False)
+        x = ro["x"].copy()
+        i = int(np.argmax(np.abs(x)))
+        x[i] = np.nextafter(x[i], np.inf)
+        r = go(sc, xs, x)
+        assert r.failed() == ["decisions"] and {f[1] for f in r.failures} == {len(sc) - 1}, r.failures
+        r = go(sc[:-1], xs[:-1], ro["x"])
+        assert r.failed() == ["decisions"], r.failures
+        r = go(sc[:-1], xs[:-1], xs[-2])      # ... even when the returned x is that row: 200 after maxIterations rows is one row early
+        assert r.failed() == ["decisions"], r.failures

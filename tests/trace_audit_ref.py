@@ -8,8 +8,11 @@ Notation: x_k row k of the trace, x_{-1} = x_start, d_k = x_k - x_{k-1}, rho_k =
 C = L'R + R'L and g_phi = -(L'lbR + R'lbL) formed here in long double, eps = 2^-53.
 
 Quantities (the names used in records and failures):
-  rho      rho_0 == rho_start and rho_{k+1} / rho_k in {1, f, f^2} exactly (f = penaltyUpdateFactor; a Leyffer update and a stationarity
-           update can fall in one pass)
+  rho      rho_0 == rho_start and rho_{k+1} in {rho_k, rho_k f, (rho_k f) f} exactly (f = penaltyUpdateFactor; a Leyffer update and a
+           stationarity update can fall in one pass).  The products are formed in float64 and one factor at a time, as updatePenalty forms
+           them in every loop (rho *= f, twice for a double update).  A product formed in long double and compared unrounded, as this audit
+           did at first, is the same number for f = 2 but not for f = 10 from rho = 0.01 (0.01 * 10 in long double is not the float64 0.1):
+           it refused every update of a correct trace; and rho_k f^2 with f^2 formed first is one rounding where the loops make two.
   obj      g'x_k + x_k'Q x_k / 2
   phi      (L x_k - lbL)'(R x_k - lbR), the direct form (the loops use the expanded one: phi_const + g_phi'x + x'Cx / 2)
   merit    obj + rho_k (L x_k)'(R x_k)
@@ -24,7 +27,15 @@ Quantities (the names used in records and failures):
            |rho_0 C x_0|_inf; row 0 otherwise: |rho_0 C d_0|_inf -- up to the residual the subsolver verified its QP to, res_tol (1 + |g_k|_inf).
   decisions  the Leyffer history, the penalty updates, iterOuter, iterTotal, the sum of the QP iterations, rhoOpt, the return value and the
            returned x, replayed from the RECORDED stat, phi and rho (which `phi` and `stat` have held to the reference).  A comparison whose
-           two sides lie within their audit bound of each other may go either way.
+           two sides lie within their audit bound of each other may go either way.  A run that ended with MAX_ITERATIONS_REACHED or
+           MAX_PENALTY_REACHED is replayed to its last row like any other: the row must not converge, its penalty updates (a stationarity
+           update included: the limits are tested behind it) must be allowed by its stat and phi, the limit named by the return value must
+           be exceeded, none may have been exceeded at an earlier row, and iterations go before the penalty when both are.
+  counters (AuditResult; what a test asserts to know its option set reached its branch): leyffer_fired, rows whose replayed Leyffer outcome
+           is {True}; window_shifts, rows that found the Leyffer window full (it is shifted by one and the new phi appended);
+           updates and double_updates, penalty updates in all and rows followed by two; row0_penalty, whether row 0 was audited as the
+           solution of a QP that carries the penalty (no zero-penalty QP: solveZeroPenaltyFirst = 0 or a warm run), and cx0 = |rho_0 C x_start|inf,
+           the term that QP's linear part has beyond g~.
 
 Bounds: no free constants.  Every sum of m products gets the standard a priori bound gamma_m sum|terms|, gamma_m = m eps / (1 - m eps), evaluated in
 long double from the absolute values of the same operands; m is the length of the longest chain, n + the most non-zeros of a row of C or Q + 8.
@@ -60,6 +71,12 @@ class AuditResult:
         self.failures = []       # (quantity, row or None, text)
         self.undecidable = 0     # rows k >= 1 whose step length the intervals do not decide
         self.decided = 0
+        self.leyffer_fired = 0   # the counters: see the module docstring
+        self.window_shifts = 0
+        self.updates = 0
+        self.double_updates = 0
+        self.row0_penalty = False
+        self.cx0 = 0.0
 
     def failed(self):
         return sorted({f[0] for f in self.failures})
@@ -70,6 +87,12 @@ class AuditResult:
 
 def _o(opt, name):
     return opt[name] if isinstance(opt, dict) else getattr(opt, name)
+
+
+def _steps(rho, f):
+    """rho, rho f, (rho f) f in float64, one factor at a time (updatePenalty: rho *= f)"""
+    rho, f = float(rho), float(f)
+    return (rho, rho * f, (rho * f) * f)
 
 
 def _gamma(m):
@@ -141,7 +164,7 @@ def audit(d, opt, scalars, xs, x_start, rho_start, warm, gtil_rule, res_tol, sta
                 res.fail("rho", 0, "rho_0 = %r, started at %r" % (float(rho), float(rho_start)))
         else:
             r0 = LD(sc[k - 1, 2])
-            if not any(rho == r0 * f ** j for j in (0, 1, 2)):
+            if float(rho) not in _steps(r0, f):
                 res.fail("rho", k, "rho_k / rho_{k-1} = %r not in {1, f, f^2}" % float(rho / r0))
         rec["rho"] = (float(rho), float(rho_start if k == 0 else sc[k - 1, 2]), 0.0)
         # ---- sum|terms| of this row's products, and with the row before for the carried ones
@@ -173,6 +196,9 @@ def audit(d, opt, scalars, xs, x_start, rho_start, warm, gtil_rule, res_tol, sta
         if k == 0 and not warm:
             gt = g      # a cold run starts with gtil = g (initializeSolver :966-967)
         gk = g if (k == 0 and zero_first) else rho * (C @ x_prev) + gt
+        if k == 0:
+            res.row0_penalty = not zero_first
+            res.cx0 = float(np.abs(rho * (C @ x_prev)).max())
         # ---- step length
         if k >= 1:
             Kd = Q @ dk + rho * (C @ dk)
@@ -268,6 +294,7 @@ def _replay(res, opt, sc, phi_b, stat_b, rho_start, stats, X, x_ret):
             if len(hist) < nd:
                 pass
             else:
+                res.window_shifts += 1
                 small = _cmp_lt(phi, ctol, phi_b[k])
                 below = [_cmp_lt(phi, eta * h, phi_b[k] + eta * hb) for h, hb in hist]
                 if small is True or any(b is True for b in below):
@@ -282,7 +309,7 @@ def _replay(res, opt, sc, phi_b, stat_b, rho_start, stats, X, x_ret):
         stat_upd = {True} if (st_small is True and ph_small is False) else ({False} if (st_small is False or ph_small is True) else {False, True})
         allowed = {int(a) + int(b) for a in ley for b in stat_upd}
         rho_next = float(stats["rhoOpt"]) if last else sc[k + 1, 2]
-        u = [j for j in (0, 1, 2) if rho_next == rho * f ** j]
+        u = [j for j, r in enumerate(_steps(rho, f)) if rho_next == r]
         u = u[0] if u else None
         if last:
             if (ret == 0) not in conv:
@@ -296,6 +323,9 @@ def _replay(res, opt, sc, phi_b, stat_b, rho_start, stats, X, x_ret):
                      % (-1 if u is None else u, rho, rho_next, stat, phi, sorted(allowed)))
             u = 0 if u is None else u
         outer += u
+        res.leyffer_fired += ley == {True}
+        res.updates += u
+        res.double_updates += u == 2
         if u > 0 and nd > 0:
             hist = []
         elif nd > 0:
@@ -307,17 +337,58 @@ def _replay(res, opt, sc, phi_b, stat_b, rho_start, stats, X, x_ret):
             res.fail("decisions", k, "MAX_ITERATIONS_REACHED after %d iterates" % K)
         if last and ret == 201 and not rho_next > max_rho:
             res.fail("decisions", k, "MAX_PENALTY_REACHED at rho %r" % rho_next)
+        if last and ret == 201 and K > max_it:
+            res.fail("decisions", k, "MAX_PENALTY_REACHED after %d iterates: maxIterations is tested first" % K)
     if outer != int(stats["iterOuter"]):
         res.fail("decisions", None, "iterOuter %d, the rho sequence has %d updates" % (stats["iterOuter"], outer))
     if x_ret is not None and not np.array_equal(np.asarray(x_ret, dtype=np.float64), np.asarray(X[-1], dtype=np.float64)):
         res.fail("decisions", K - 1, "the last row is not the returned x bit for bit")
 
 
-def audit_batch(bt, ds, which, opt, x_start, rho_start, warm, gtil_rule, res_tol, label, carried_C=False, densify=None):
+def last_qp_duals(d, scalars, xs, x_start, rho_start, y, layout, res_tol):
+    """Are the returned duals y those of the last QP solved?  For a cold run without perturbStep that ended at row K - 1 (K >= 2) without
+    converging, so that y is untransformed.  QP k has the linear term g_k = rho_k C x_{k-1} + gtil_k (rule "after_first_update") and the
+    solution xnew_k = x_{k-1} + d_k / alpha_k; its multipliers satisfy Q xnew_k + g_k - E'y_E - y_box = 0 up to the subsolver's
+    res_tol (1 + |g_k|inf).  layout "dense": y = [box (nV), A, L, R]; "sparse": y = [A, L, R].  Returns (residual of QP K - 1, its bound,
+    residual of QP K - 2): the bound is res_tol (1 + |g_k|inf) plus MARGIN gamma_m sum|terms| of the residual's own sums plus what xnew_k
+    cannot be known to from the trace, eps (|x_k| + |x_{k-1}|) / alpha_k per component, through |Q|."""
+    n, nC, nK = int(d["nV"]), int(d["nC"]), int(d["nComp"])
+    Q = np.asarray(d["Q"], dtype=np.float64).astype(LD)
+    L = np.asarray(d["L"], dtype=np.float64).astype(LD); R = np.asarray(d["R"], dtype=np.float64).astype(LD)
+    A = np.asarray(d["A"], dtype=np.float64).reshape(nC, n).astype(LD) if nC else np.zeros((0, n), dtype=LD)
+    E = np.vstack([A, L, R])
+    g, lbL, lbR = _vec(d, "g", n), _vec(d, "lbL", nK), _vec(d, "lbR", nK)
+    C = complementarity_matrix(L, R)
+    gphi = -(L.T @ lbR + R.T @ lbL)
+    y = np.asarray(y, dtype=np.float64).astype(LD)
+    ybox, yE = (y[:n], y[n:]) if layout == "dense" else (np.zeros(n, dtype=LD), y)
+    sc = np.asarray(scalars, dtype=np.float64)
+    X = np.asarray(xs, dtype=np.float64).astype(LD)
+    K = len(sc)
+    assert K >= 2 and yE.size == nC + 2 * nK
+    start = np.zeros(n, dtype=LD) if x_start is None else np.asarray(x_start, dtype=np.float64).astype(LD)
+    G = MARGIN * _gamma(n + E.shape[0] + int((C != 0).sum(axis=1).max()) + 8)
+
+    def residual(k):
+        xp = X[k - 1] if k >= 1 else start
+        rho, alpha = LD(sc[k, 2]), LD(sc[k, 3])
+        xn = xp + (X[k] - xp) / alpha
+        gt = g + rho * gphi if rho != LD(rho_start) else g
+        gk = rho * (C @ xp) + gt
+        r = Q @ xn + gk - E.T @ yE - ybox
+        terms = np.abs(Q) @ np.abs(xn) + rho * (np.abs(C) @ np.abs(xp)) + np.abs(gt) + np.abs(E).T @ np.abs(yE) + np.abs(ybox)
+        unknown = np.abs(Q) @ (EPS * (np.abs(X[k]) + np.abs(xp)) / alpha)
+        return float(np.abs(r).max()), float((G * terms + unknown).max() + LD(res_tol) * (1 + np.abs(gk).max()))
+
+    r, bound = residual(K - 1)
+    return r, bound, residual(K - 2)[0]
+
+
+def audit_batch(bt, ds, which, opt, x_start, rho_start, warm, gtil_rule, res_tol, label, carried_C=False, densify=None, expect_ret=0):
     """audit() on the instances `which` of a solved batch handle bt (BatchLCQP or SparseBatchLCQP; the traces and statistics come through its
     solution() and trace()): ds the problem dicts (densify: dict -> dense layout, for the sparse arm), x_start None or one start per
     instance, rho_start a number or one per instance.  Prints one line per instance and the worst |recorded - reference| / bound per
-    quantity; asserts that every instance converged and passed.  Returns {instance: AuditResult}."""
+    quantity; asserts that every instance passed and returned expect_ret (0: converged).  Returns {instance: AuditResult}."""
     x, _, st = bt.solution()
     worst, out = {}, {}
     for b in which:
@@ -332,7 +403,7 @@ def audit_batch(bt, ds, which, opt, x_start, rho_start, warm, gtil_rule, res_tol
         print(f"    {label} instance {b}: ret {st[b]['returnValue']} rows {len(sc)} rho -> {st[b]['rhoOpt']:g} step length decided {r.decided} undecidable {r.undecidable}"
               + "".join(f"\n      FAIL {f}" for f in r.failures))
         assert not r.failures, (label, b, r.failures)
-        assert st[b]["returnValue"] == 0, (label, b, st[b])
+        assert st[b]["returnValue"] == expect_ret, (label, b, st[b])
         out[b] = r
     print(f"    {label}: worst |recorded - reference| / bound  " + "  ".join(f"{k} {v:.3f}" for k, v in worst.items()))
     return out
