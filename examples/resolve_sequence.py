@@ -2,7 +2,10 @@
 again and again with a new linear term and new bounds.
     python examples/resolve_sequence.py [B=256] [steps=5]
     python examples/resolve_sequence.py [B=256] [steps=5] sparse     the same on the sparse arm (lcqp_hip_sparse_update / _resolve): the banded
-                                                                     synthetic workload at n = 512, iterate counts per step"""
+                                                                     synthetic workload at n = 512, iterate counts per step
+    python examples/resolve_sequence.py [B=256] [steps=5] matrices   the matrices move too, 2 % per step (an outer loop that re-linearises):
+                                                                     update_matrices + update, then the warm re-solve sets up again
+                                                                     around the last solution and working set"""
 import os
 import sys
 import time
@@ -51,6 +54,7 @@ def main():
     if len(sys.argv) > 3 and sys.argv[3] == "sparse":
         sparse_leg(B, steps)
         return
+    matrices = len(sys.argv) > 3 and sys.argv[3] == "matrices"
     n, nC, nComp = 256, 512, 64
     bt = la.BatchLCQP(B, n, nC, nComp, opt=la.default_options(printLevel=0))
     bt.generate_synthetic(0)          # stands for load(): the matrices go to the device once
@@ -60,12 +64,21 @@ def main():
     print(f"first solve: {np.mean([s['iterTotal'] for s in st]):.1f} iterates per LCQP, setup {setup_ms:.2f} ms + homotopy {solve_ms:.2f} ms")
     probs = [bt.read_problem(b) for b in range(B)]
     g = np.stack([p["g"] for p in probs]); lbA = np.stack([p["lbA"] for p in probs]); ubA = np.stack([p["ubA"] for p in probs])
+    mats = {k: np.stack([p[k] for p in probs]) for k in ("Q", "L", "R", "A")} if matrices else None
     rng = np.random.default_rng(0)
     for step in range(1, steps + 1):
         g = g * (1.0 + 0.02 * rng.standard_normal(g.shape))
         shift = 0.02 * (ubA - lbA) * rng.standard_normal(lbA.shape)
         lbA, ubA = lbA + shift, ubA + shift
+        if matrices:
+            s = 1.0 + 0.02 * rng.standard_normal((B, n))
+            mats = dict(Q=mats["Q"] * s[:, :, None] * s[:, None, :], A=mats["A"] * (1.0 + 0.02 * rng.standard_normal(mats["A"].shape)),
+                        L=mats["L"] * (1.0 + 0.02 * rng.standard_normal((B, nComp, 1))), R=mats["R"] * (1.0 + 0.02 * rng.standard_normal((B, nComp, 1))))
         t0 = time.perf_counter()
+        if matrices:
+            rc = bt.update_matrices(0, B, **mats)      # (a matrix that is left out stays as the batch holds it)
+            if rc != 0:
+                raise RuntimeError(f"update_matrices failed with code {rc}: {la.capi.last_error()}")
         rc = bt.update(0, B, g, lbA=lbA, ubA=ubA)
         if rc != 0:
             raise RuntimeError(f"update failed with code {rc}: {la.capi.last_error()}")
@@ -75,7 +88,7 @@ def main():
         refresh_ms, solve_ms = bt.last_timing()
         it = [s["iterTotal"] for s in st]
         ok = sum(s["returnValue"] == 0 for s in st)
-        print(f"step {step}: {ok}/{B} solved, iterates mean {np.mean(it):.1f} max {max(it)}, refresh {refresh_ms:.3f} ms + homotopy {solve_ms:.2f} ms, "
+        print(f"step {step}: {ok}/{B} solved, iterates mean {np.mean(it):.1f} max {max(it)}, {'setup' if matrices else 'refresh'} {refresh_ms:.3f} ms + homotopy {solve_ms:.2f} ms, "
               f"{wall:.1f} ms with update and read-back")
     print("launches (full setups, homotopy launches):", bt.launch_counts())
     bt.close()

@@ -218,8 +218,26 @@ int  lcqp_hip_batch_update(lcqp_hip_batch_t* b, int first, int count, const doub
  *   every entry finite and > 0, else LCQP_INVALID_ARGUMENT) or, with rho0 == NULL, its last rhoOpt; it skips the zero-penalty QP, and its first QP is a hot start from the stored
  *   point, working set and inverse factor.  Its x0 / y0 are not read.  In the reference's terms: runSolver with x0, y0 = the last
  *   solution, solveZeroPenaltyFirst = false, initialPenaltyParameter = that penalty.  Every other instance runs cold as in mode 0.
- * lcqp_hip_batch_last_timing reports k_refresh as setup_ms. */
+ * lcqp_hip_batch_last_timing reports k_refresh as setup_ms.
+ * After lcqp_hip_batch_update_matrices (below), mode 1 is the same warm start around new matrices: the five setup kernels run, with
+ * k_prepare_warm in front, and lcqp_hip_batch_last_timing reports them as setup_ms. */
 int  lcqp_hip_batch_resolve(lcqp_hip_batch_t* b, int mode, const double* rho0);
+/* Re-solves after a change of the matrices (an outer SQP loop that re-linearises, a layer whose Q / A are trained).
+ * lcqp_hip_batch_update_matrices replaces the named matrices of instances [first, first+count) and nothing else: Q, L, R, A as
+ * lcqp_hip_batch_load takes them (host arrays [count][rows][nV]), NULL: the matrix stays.  No vector, status, multiplier, stored point or
+ * statistic is touched.  Checked before any device call, in this order, and nothing is written when a check fails: every matrix NULL
+ * (LCQP_INVALID_ARGUMENT), NULL handle (LCQP_LCQPOBJECT_NOT_SETUP), a range outside the batch (LCQP_INVALID_ARGUMENT), an instance of the
+ * range that holds no problem (LCQP_LCQPOBJECT_NOT_SETUP), only matrices the batch has no rows of (LCQP_INVALID_ARGUMENT).
+ * Afterwards no setup and no solve belong to the data in place: the sensitivity, Jacobian and adjoint calls answer
+ * LCQP_LCQPOBJECT_NOT_SETUP until the next solve.  What the last solve stored on the device is kept, and the next
+ * lcqp_hip_batch_resolve(mode 1) starts from it: a full setup on the new matrices in which an instance whose last run returned
+ * LCQP_SUCCESSFUL_RETURN keeps its x, multipliers, statuses and penalty (rho0 as above), with an EMPTY inverse factor -- its first QP
+ * rebuilds the factor in one piece from the stored working set and the new matrices.  In the reference's terms: runSolver on the new data
+ * with x0, y0 = the last solution, solveZeroPenaltyFirst = false, initialPenaltyParameter = that penalty.  Every other instance, and every
+ * instance of a mode 0 resolve or a run, starts cold: the bits of a new batch object given the same data by lcqp_hip_batch_load.
+ * lcqp_hip_batch_update and lcqp_hip_batch_update_matrices may precede the resolve in either order; a load, generate_synthetic or
+ * set_options in between makes it a cold run. */
+int  lcqp_hip_batch_update_matrices(lcqp_hip_batch_t* b, int first, int count, const double* Q, const double* L, const double* R, const double* A);
 /* Solution sensitivities (DESIGN.md section 3a'): adjoint derivatives of the x the last run / resolve returned with respect to g and to
  * the bounds its working set W sits on.  For instance i and right-hand side k, v[i][k] = dl/dx is an upstream gradient ([B][nrhs][nV], host);
  *   dg[i][k]   [nV]                 = dl/dg
@@ -346,6 +364,10 @@ int  lcqp_hip_batch_update_device(lcqp_hip_batch_t* b, int first, int count, con
                                   const double* lbL, const double* ubL, const double* lbR, const double* ubR,
                                   const double* lbA, const double* ubA, const double* lb, const double* ub,
                                   const double* x0, const double* y0, void* stream);
+/* lcqp_hip_batch_update_matrices on device arrays, under the rules above: shared as in load_device, a NULL matrix stays, the checks and
+ * their order are the host twin's (a bit of shared outside 1 | 2 | 4 | 8: LCQP_INVALID_ARGUMENT), nothing waits on the host. */
+int  lcqp_hip_batch_update_matrices_device(lcqp_hip_batch_t* b, int first, int count, int shared, const double* Q, const double* L,
+                                           const double* R, const double* A, void* stream);
 int  lcqp_hip_batch_get_solution_device(lcqp_hip_batch_t* b, double* x, double* y, lcqp_stats_t* stats, void* stream);
 int  lcqp_hip_batch_sensitivity_device(lcqp_hip_batch_t* b, int blocked, int nrhs, const double* v,
                                        double* dg, double* db, int* side, int* info, void* stream);

@@ -111,6 +111,8 @@ def lib():
         L.lcqp_hip_batch_generate_synthetic.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64]
         L.lcqp_hip_batch_update.argtypes = [C.c_void_p, C.c_int, C.c_int] + [c_double_p] * 11
         L.lcqp_hip_batch_resolve.argtypes = [C.c_void_p, C.c_int, c_double_p]
+        L.lcqp_hip_batch_update_matrices.argtypes = [C.c_void_p, C.c_int, C.c_int] + [c_double_p] * 4
+        L.lcqp_hip_batch_update_matrices_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_void_p]
         L.lcqp_hip_batch_launch_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.lcqp_hip_batch_read_problem.argtypes = [C.c_void_p, C.c_int] + [c_double_p] * 7
         L.lcqp_hip_batch_setup.argtypes = [C.c_void_p]
@@ -979,6 +981,17 @@ class BatchLCQP(_Batch):
         v = self._device_vectors(count, (g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0))
         return lib().lcqp_hip_batch_update_device(self.h, first, count, *v, self._stream())
 
+    def update_matrices_device(self, first, count, Q=None, L=None, R=None, A=None, shared=0):
+        """lcqp_hip_batch_update_matrices_device: update_matrices() from float64 torch tensors on the handle's device.  As in
+        load_device a matrix of shape [rows][nV] is ONE matrix for all `count` instances; shared (bits 1, 2, 4, 8 for Q, A, L, R) may
+        say so too, and must then agree with the shapes.  Returns the ReturnValue code."""
+        n, nC, nK = self.nV, self.nC, self.nComp
+        self._range(first, count)
+        found, ptr = self._device_matrices(count, (("Q", Q, (n, n)), ("A", A, (nC, n)), ("L", L, (nK, n)), ("R", R, (nK, n))))
+        if count > 1 and shared & ~found:
+            raise ValueError(f"shared = {shared}: a matrix marked as shared has the shape of one per instance")
+        return lib().lcqp_hip_batch_update_matrices_device(self.h, first, count, found, ptr["Q"], ptr["L"], ptr["R"], ptr["A"], self._stream())
+
     def sensitivity_device(self, v, blocked=False):
         """lcqp_hip_batch_sensitivity_device: sensitivity(v, blocked) with v a float64 tensor on the handle's device, [B][nV] or
         [B][k][nV], read where it lies; returns (dg, db, side, info) as tensors on that device (side, info: int32)."""
@@ -1001,6 +1014,18 @@ class BatchLCQP(_Batch):
             raise ValueError(f"instances [{first}, {first + count}) outside the batch of {self.B}")
         a = self._host_args(self._vector_sizes(), count, (g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0))
         return lib().lcqp_hip_batch_update(self.h, first, count, *[_p(v) for v in a])
+
+    def update_matrices(self, first, count, Q=None, L=None, R=None, A=None):
+        """lcqp_hip_batch_update_matrices: new matrices for instances [first, first + count), None: the matrix stays; the vectors, the
+        stored point, the statuses and the penalties stay.  The next resolve(warm=True) sets up again on the new matrices and starts
+        every instance whose last run succeeded from its last solution and working set, with an empty inverse factor; resolve() and run()
+        solve the new data cold.  Returns the ReturnValue code (0; 100 INVALID_ARGUMENT without any matrix, 300 for an instance that
+        holds no problem); a wrongly sized array raises ValueError."""
+        n, nC, nK = self.nV, self.nC, self.nComp
+        if first < 0 or count <= 0 or first + count > self.B:
+            raise ValueError(f"instances [{first}, {first + count}) outside the batch of {self.B}")
+        a = self._host_args((("Q", n * n), ("L", nK * n), ("R", nK * n), ("A", nC * n)), count, (Q, L, R, A))
+        return lib().lcqp_hip_batch_update_matrices(self.h, first, count, *[_p(v) for v in a])
 
     def read_problem(self, b):
         n, nC, nComp = self.nV, self.nC, self.nComp

@@ -52,6 +52,13 @@ class BatchLCQProblem {
     {
         return (ReturnValue)lcqp_hip_batch_update(h.get(), instance, 1, g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0);
     }
+    // Other matrices for one instance (lcqp_hip_batch_update_matrices), 0: the matrix stays; the vectors, the stored solution and the
+    // penalties stay.  The next resolve(true) sets up again and starts the instances whose last run succeeded from their last solution and
+    // working set; resolve(false) and runSolver solve the new data cold.  Sensitivities are refused until then.
+    ReturnValue updateMatrices(int instance, const double* Q, const double* L = 0, const double* R = 0, const double* A = 0)
+    {
+        return (ReturnValue)lcqp_hip_batch_update_matrices(h.get(), instance, 1, Q, L, R, A);
+    }
     // solve again on the setup in place.  warm: instances whose last run succeeded start from their last solution, working set and
     // penalty (rho0: [batch] starting penalties, each > 0, instead of the last rhoOpt); every other instance, and every instance of a
     // cold re-solve, starts as after a fresh load.  resolveAsync + collect are the two halves, as for runSolver.

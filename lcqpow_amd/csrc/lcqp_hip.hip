@@ -1,6 +1,6 @@
 // lcqp_hip.hip -- the dense arm's batch: the process-wide entry points, the choice of launch table and build (dense_kernels, run_kernels)
 // and the life cycle of the batch handle in the C ABI lcqp_hip_batch_* (gfx950 only; see include/lcqp_hip.h): create, load, setup, run,
-// update, resolve and the readers.  Host code only, no kernel.  Differentiation -- the sensitivity, Jacobian and adjoint entry points, their
+// update, update_matrices, resolve and the readers.  Host code only, no kernel.  Differentiation -- the sensitivity, Jacobian and adjoint entry points, their
 // device-pointer twins and the two adjoint kernels -- is lcqp_hip_diff.hip; the QP object is lcqp_hip_qp.hip, the building blocks and CSC
 // utilities lcqp_hip_util.hip; lcqp_hip_batch.hpp is what the units share.
 #include "lcqp_hip_batch.hpp"
@@ -254,8 +254,9 @@ extern "C" int lcqp_hip_batch_read_problem(lcqp_hip_batch_t* h, int b, double* Q
     return 0;
 }); }
 
-// the setup kernels of the batch on its stream, the C branch on the side stream
-int launch_setup(lcqp_hip_batch* h)
+// the setup kernels of the batch on its stream, the C branch on the side stream.  warm: k_prepare_warm stands where k_prepare stands --
+// the matrices changed under a stored point (lcqp_hip_batch_update_matrices); rho0 [B] on the device, or null
+int launch_setup(lcqp_hip_batch* h, bool warm, const double* rho0)
 {
     const DevBatch& d = h->db;
     const SizeKernels& k = *h->k;
@@ -264,7 +265,8 @@ int launch_setup(lcqp_hip_batch* h)
     h->rs.nSetups++;
     const int ntile = d.nblk * (d.nblk + 1) / 2;
     const int nrb = (d.mEcap + 63) / 64, nb = (d.mMld + 127) / 128, nmt = nb * (nb + 1);      // k_build_M: 128 x 64 tiles of the lower triangle
-    k.prepare(d, d.B, on);
+    if (warm) k.prepare_warm(d, d.B, on, rho0);
+    else k.prepare(d, d.B, on);
     // C and its compressed rows depend on L and R only, the chain L1 -> Et -> M on Q and E: two branches.  The short one goes to the side
     // stream and runs in the gaps of k_factor (one workgroup per instance, a life of dependent chains).  Measured alternatives, round 6
     // (profiles/round6/README.md): the side branch beside k_trsm, or beside k_trsm and k_build_M -- both 0.2 ms slower.
@@ -349,11 +351,31 @@ extern "C" int lcqp_hip_batch_update(lcqp_hip_batch_t* h, int first, int count, 
     return dense_upload(h, first, count, PackVectors{g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0}, nullptr, nullptr, nullptr, nullptr, true);
 }); }
 
+// New matrices for instances [first, first + count) of a batch that holds problems: Q, L, R, A as lcqp_hip_batch_load takes them, NULL:
+// the matrix stays.  Only their blocks of the pools are written (k_pack_matrices behind the chunked upload): no vector, no InstInfo, no
+// status, multiplier, point or statistic.  The whole call is checked before anything is written.
+extern "C" int lcqp_hip_batch_update_matrices(lcqp_hip_batch_t* h, int first, int count, const double* Q, const double* L, const double* R,
+                                              const double* A)
+{ return guarded(g_err, [&] {
+    if (int rc = check_update_matrices(h, first, count, Q, L, R, A)) return rc;
+    const DevBatch& d = h->db;
+    const size_t n = d.n, nC = d.nC, nComp = d.nComp;
+    HIPCHK(g_err, hipSetDevice(h->device));
+    matrices_changed(h);
+    const RawArray raw[] = {{Q, n * n}, {A, nC * n}, {L, nComp * n}, {R, nComp * n}};
+    return upload_packed(g_err, h, count, raw, [&](int c0, int cb, const double* const* p) {
+        return dense_pack_matrices(h, first + c0, cb, PackMatrices{{p[0], p[1], p[2], p[3]}, {n * n, nC * n, nComp * n, nComp * n}}, false);
+    });
+}); }
+
 // Solve again on the setup in place: k_refresh instead of the five setup kernels, then the homotopy launch.  Without a setup that belongs
-// to the matrices and options in place this is lcqp_hip_batch_run.
+// to the matrices and options in place this is lcqp_hip_batch_run -- unless the call is warm and only the matrices changed since the last
+// solve (lcqp_hip_batch_update_matrices): then the five setup kernels run with k_prepare_warm in front, which keeps the stored point.
 extern "C" int lcqp_hip_batch_resolve(lcqp_hip_batch_t* h, int mode, const double* rho0)
 { return guarded(g_err, [&] {
-    if (int rc = check_resolve(g_err, h, mode, rho0, h && h->anyLoaded)) return rc == RESOLVE_RUNS ? lcqp_hip_batch_run(h) : rc;
+    const int chk = check_resolve(g_err, h, mode, rho0, h && h->anyLoaded);
+    const bool newMatrices = chk == RESOLVE_RUNS && mode == 1 && h->rs.pointKept;
+    if (chk && !newMatrices) return chk == RESOLVE_RUNS ? lcqp_hip_batch_run(h) : chk;
     const int B = h->db.B;
     HIPCHK(g_err, hipSetDevice(h->device));
     const bool withRho = mode == 1 && rho0;
@@ -365,8 +387,12 @@ extern "C" int lcqp_hip_batch_resolve(lcqp_hip_batch_t* h, int mode, const doubl
         HIPCHK(g_err, hipEventRecord(h->up.slot[0].done, h->stream));
     }
     HIPCHK(g_err, hipEventRecord(h->ev0, h->stream));
-    h->k->refresh(h->db, B, h->stream, mode, withRho ? h->rs.rhoStart : nullptr);
-    HIPCHK(g_err, hipGetLastError());
+    if (newMatrices) {
+        if (int rc = launch_setup(h, true, withRho ? h->rs.rhoStart : nullptr)) return rc;
+    } else {
+        h->k->refresh(h->db, B, h->stream, mode, withRho ? h->rs.rhoStart : nullptr);
+        HIPCHK(g_err, hipGetLastError());
+    }
     HIPCHK(g_err, hipEventRecord(h->ev1, h->stream));
     run_kernels(h).lcqp_run(h->db, B, h->stream);
     h->rs.nLaunches++;

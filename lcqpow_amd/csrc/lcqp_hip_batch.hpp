@@ -52,7 +52,7 @@ inline int padded_nch(int n) { const int k = (n + 127) / 128; return k > 16 ? 32
 // lcqp_hip.hip; the comments are at the definitions
 const lcqp::SizeKernels* dense_kernels(int nch);
 const lcqp::RunKernels& run_kernels(const lcqp_hip_batch* h);
-int launch_setup(lcqp_hip_batch* h);
+int launch_setup(lcqp_hip_batch* h, bool warm = false, const double* rho0 = nullptr);
 // lcqp_hip_diff.hip: the bodies of the batch's sensitivity, Jacobian and adjoint entry points behind their guards, which the QP object
 // calls on its batch of one (dev: the device-pointer twin, with the caller's stream)
 int batch_sensitivity(lcqp_hip_batch* h, bool blk, int nrhs, const double* v, double* dg, double* db, int* side, int* info, bool dev = false, void* stream = nullptr);
@@ -74,6 +74,11 @@ struct PackMatrices { const double* src[4]; size_t stride[4]; };      // Q, A, L
 // k_pack_matrices and k_pack_vectors (update: k_pack_vectors alone, m is not read) on h->stream; nothing waits.  The checks and the host
 // state are the caller's.
 int dense_pack(lcqp_hip_batch* h, int first, int count, const PackVectors& v, const PackMatrices& m, bool update);
+// lcqp_hip_batch_update_matrices and its device twin: the checks in front of every device call, the host state of a range that is about to
+// be written (ResolveState::pointKept), and k_pack_matrices alone (boxRows: with the zero fill of the box rows of E, as a load)
+int check_update_matrices(lcqp_hip_batch* h, int first, int count, const double* Q, const double* L, const double* R, const double* A);
+void matrices_changed(lcqp_hip_batch* h);
+int dense_pack_matrices(lcqp_hip_batch* h, int first, int count, const PackMatrices& m, bool boxRows);
 
 // the message of lcqp_hip_batch_update and its device twin for a variable whose box bound appears or disappears
 inline std::string box_change_message(int variable, int instance, bool gains)

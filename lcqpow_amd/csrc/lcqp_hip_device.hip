@@ -1,5 +1,5 @@
 // lcqp_hip_device.hip -- the dense batch's device-pointer entry points that fill and read the pools: lcqp_hip_batch_load_device,
-// _update_device and _get_solution_device (include/lcqp_hip.h, DESIGN.md section 3a'''''), with their three kernels, and dense_pack, the pack step
+// _update_device, _update_matrices_device and _get_solution_device (include/lcqp_hip.h, DESIGN.md section 3a'''''), with their three kernels, and dense_pack, the pack step
 // the host load / update of lcqp_hip.hip run behind their upload: the pack kernels are the one definition of the pool layout.  The twins of
 // the sensitivity, Jacobian and adjoint calls are one body with their host calls, in lcqp_hip_diff.hip (k_pack_dual_rows here is theirs); lcqp_hip_batch.hpp holds what the two units share, lcqp_host_rt.hpp the hand-over
 // around every such call (device_call) and _get_solution_device, which are the sparse arm's too.
@@ -187,18 +187,47 @@ void launch_pack_dual_rows(const DevBatch& d, hipStream_t s, int count, int ldb,
 
 #define g_err dense_err()      // the error slot of the dense arm (thread_local, lcqp_hip.hip)
 
+// k_pack_matrices on the range.  boxRows: with the segment that zeroes the box rows of E, as a load leaves them before k_prepare writes
+// them; a matrix-only update leaves that segment alone -- the rows k_prepare rewrites are rewritten anyway, the ones behind them are
+// still the zeros of the load
+int dense_pack_matrices(lcqp_hip_batch* h, int first, int count, const PackMatrices& m, bool boxRows)
+{
+    const DevBatch& d = h->db;
+    const int half = d.np / 2, mostRows = std::max(d.np, std::max(d.nC, std::max(d.nComp, d.mEcap - d.mA)));
+    const unsigned gx = (unsigned)std::min<size_t>(((size_t)mostRows * half + 4 * WG - 1) / (4 * WG), 4096);      // four pieces per thread
+    hipLaunchKernelGGL(k_pack_matrices, dim3(gx, std::min(count, 65535), boxRows ? 5 : 4), dim3(WG), 0, h->stream, d, first, count, m);
+    HIPCHK(g_err, hipGetLastError());
+    return 0;
+}
+
 int dense_pack(lcqp_hip_batch* h, int first, int count, const PackVectors& v, const PackMatrices& m, bool update)
 {
     const DevBatch& d = h->db;
-    if (!update) {
-        const int half = d.np / 2, mostRows = std::max(d.np, std::max(d.nC, std::max(d.nComp, d.mEcap - d.mA)));
-        const unsigned gx = (unsigned)std::min<size_t>(((size_t)mostRows * half + 4 * WG - 1) / (4 * WG), 4096);      // four pieces per thread
-        hipLaunchKernelGGL(k_pack_matrices, dim3(gx, std::min(count, 65535), 5), dim3(WG), 0, h->stream, d, first, count, m);
-        HIPCHK(g_err, hipGetLastError());
-    }
+    if (!update) if (int rc = dense_pack_matrices(h, first, count, m, true)) return rc;
     hipLaunchKernelGGL(k_pack_vectors, dim3(count), dim3(WG), 0, h->stream, d, first, count, v, update ? 1 : 0);
     HIPCHK(g_err, hipGetLastError());
     return 0;
+}
+
+// lcqp_hip_batch_update_matrices and its device twin up to the first device call: the checks, in this order.  Nothing is written when
+// one of them fails.
+int check_update_matrices(lcqp_hip_batch* h, int first, int count, const double* Q, const double* L, const double* R, const double* A)
+{
+    if (!Q && !L && !R && !A) return LCQP_INVALID_ARGUMENT;
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (first < 0 || count <= 0 || first > h->db.B - count) return LCQP_INVALID_ARGUMENT;
+    for (int k = 0; k < count; k++) if (!h->rs.filled[(size_t)first + k]) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!Q && !(A && h->db.nC) && !((L || R) && h->db.nComp)) return LCQP_INVALID_ARGUMENT;      // only matrices this batch has no rows of
+    return 0;
+}
+
+// ... and their host state once the range is about to be written: no setup and no solve belong to the matrices in place any more, but
+// what the last solve stored on the device -- the point, the statuses, the penalties -- is still there (ResolveState::pointKept)
+void matrices_changed(lcqp_hip_batch* h)
+{
+    const bool kept = h->rs.solved || h->rs.pointKept;
+    h->rs.invalidate();
+    h->rs.pointKept = kept;
 }
 
 // the status words (and, for a load, the box flags behind them) of k_check_vectors: [2] words, then [B][n] bytes
@@ -311,3 +340,28 @@ extern "C" int lcqp_hip_batch_get_solution_device(lcqp_hip_batch_t* h, double* x
 {
     return guarded(g_err, [&] { return get_solution_device(g_err, h, h ? h->db.nd : 0, x, y, stats, stream); });
 }
+
+// New matrices for instances [first, first + count) from device arrays of the caller: lcqp_hip_batch_update_matrices behind the hand-over
+// of the streams.  shared: bit k set -- matrix k of (Q, A, L, R) is one [rows][nV] array for the whole range.
+extern "C" int lcqp_hip_batch_update_matrices_device(lcqp_hip_batch_t* h, int first, int count, int shared, const double* Q, const double* L,
+                                                     const double* R, const double* A, void* stream)
+{ return guarded(g_err, [&] {
+    if (int rc = check_update_matrices(h, first, count, Q, L, R, A)) return rc;
+    if (shared & ~15) return LCQP_INVALID_ARGUMENT;
+    const DevBatch& d = h->db;
+    HIPCHK(g_err, hipSetDevice(h->device));
+    PackMatrices pm{};
+    const double* mats[4] = {Q, d.nC ? A : nullptr, d.nComp ? L : nullptr, d.nComp ? R : nullptr};
+    const char* names[4] = {"Q", "A", "L", "R"};
+    const size_t rows[4] = {(size_t)d.n, (size_t)d.nC, (size_t)d.nComp, (size_t)d.nComp};
+    for (int k = 0; k < 4; k++) {
+        const bool one = (shared >> k) & 1;
+        pm.src[k] = mats[k];
+        pm.stride[k] = one ? 0 : rows[k] * d.n;
+        if (!device_pointer_ok(g_err, h, names[k], mats[k], sizeof(double) * (one ? 1 : (size_t)count) * rows[k] * d.n)) return LCQP_INVALID_ARGUMENT;
+    }
+    return device_call(g_err, h, stream, [&] {
+        matrices_changed(h);
+        return dense_pack_matrices(h, first, count, pm, false);
+    });
+}); }

@@ -188,13 +188,16 @@ struct ResolveState {
     // the stored point, working set and factors belong to a solve on the data in place (set by run / resolve, cleared with setupValid):
     // what *_sensitivity differentiates
     bool solved = false;
-    std::vector<char> filled;             // [B]: the instance holds a problem
+    // the matrices changed since the last solve (dense arm: *_update_matrices), but its point, statuses and penalties are still on the
+    // device: a warm *_resolve sets up again around them.  Cleared with setupValid by everything else that clears it
+    bool pointKept = false;
+    std::vector<char> filled;            // [B]: the instance holds a problem
     double* rhoStart = nullptr;           // [B] on the device: starting penalties of a warm re-solve
     int nSetups = 0, nLaunches = 0;       // full setups and homotopy launches issued
     // the kernel time of the last sensitivity call that returned its results, summed over its launches (ev0 -> ev1 of the SensBuffers each
     // ran on: a vector call is one launch, a Jacobian one per chunk); < 0 before the first
     float sensMs = -1.f;
-    void invalidate() { setupValid = solved = false; }
+    void invalidate() { setupValid = solved = pointKept = false; }
 };
 
 // the value check of a host load / update over its whole range ([count * nComp] each, null: absent): a lower complementarity bound of

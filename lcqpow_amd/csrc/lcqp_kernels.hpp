@@ -10,7 +10,7 @@
 using namespace lcqp;
 
 
-// ---- the vector half of the setup: bounds of the box rows, ADMM rho vector, phi expressions (k_prepare, k_refresh) ----------------------
+// ---- the vector half of the setup: bounds of the box rows, ADMM rho vector, phi expressions (k_prepare, k_refresh, k_prepare_warm) ------
 // Returns phi_const (uniform); writes M_L / M_U of the box rows, M_RHOV and V_GPHI.
 template <int NCH>
 __device__ __forceinline__ double prepare_vectors(const DevBatch& db, Ctx<NCH>& c, Lds lds, double scale)
@@ -76,14 +76,12 @@ __device__ __forceinline__ void prepare_cold(const DevBatch& db, Ctx<NCH>& c)
     }
 }
 
-// ---- k_prepare: scales, padding, box rows, ADMM rho vector, phi expressions ----------------------
+// the matrix half of k_prepare / k_prepare_warm: the scale of Q (returned, uniform), the unit diagonal of its padding, the box rows of E
 template <int NCH>
-__global__ __launch_bounds__(WG) void k_prepare(DevBatch db)
+__device__ __forceinline__ double prepare_matrices(const DevBatch& db, Ctx<NCH>& c, Lds lds)
 {
-    LCQP_LDS_N(NCH)
     constexpr int np = 128 * NCH;
-    const int b = blockIdx.x, t = threadIdx.x;
-    Ctx<NCH> c = make_ctx<NCH>(db, b, lds);
+    const int t = threadIdx.x;
     const int n = db.n, mA = db.mA;
     double dmax = 0.0;
     for (int i = t; i < n; i += WG) dmax = fmax(dmax, fabs(c.Q[(size_t)i * np + i]));
@@ -96,18 +94,34 @@ __global__ __launch_bounds__(WG) void k_prepare(DevBatch db)
         const int bi = c.boxidx[k];
         for (int i = t; i < np; i += WG) row[i] = (i == bi) ? 1.0 : 0.0;
     }
+    return scale;
+}
+
+// the marks of a fresh setup (thread 0 of k_prepare / k_prepare_warm)
+template <int NCH>
+__device__ __forceinline__ void prepare_marks(const DevBatch& db, Ctx<NCH>& c, double scale, double phiConst)
+{
+    c.info->mE = db.mA + c.info->nfin;
+    c.info->scale = scale;
+    c.info->sigma = db.opt.admmSigma * scale;
+    c.info->rhoAdmm = db.opt.admmRho * scale;
+    c.info->phiConst = phiConst;
+    c.info->cNnz = -1;
+    c.info->setupFail = 0;
+    c.info->isSetup = 1;
+}
+
+// ---- k_prepare: scales, padding, box rows, ADMM rho vector, phi expressions ----------------------
+template <int NCH>
+__global__ __launch_bounds__(WG) void k_prepare(DevBatch db)
+{
+    LCQP_LDS_N(NCH)
+    const int b = blockIdx.x, t = threadIdx.x;
+    Ctx<NCH> c = make_ctx<NCH>(db, b, lds);
+    const double scale = prepare_matrices<NCH>(db, c, lds);
     const double phiConst = prepare_vectors<NCH>(db, c, lds, scale);
     prepare_cold<NCH>(db, c);
-    if (t == 0) {
-        c.info->mE = mA + nfin;
-        c.info->scale = scale;
-        c.info->sigma = db.opt.admmSigma * scale;
-        c.info->rhoAdmm = db.opt.admmRho * scale;
-        c.info->phiConst = phiConst;
-        c.info->cNnz = -1;
-        c.info->setupFail = 0;
-        c.info->isSetup = 1;
-    }
+    if (t == 0) prepare_marks<NCH>(db, c, scale, phiConst);
 }
 
 // ---- k_refresh: new vectors on the setup in place, and the hand-over between two runs (lcqp_hip_batch_resolve) ----------------------
@@ -120,6 +134,53 @@ __global__ __launch_bounds__(WG) void k_prepare(DevBatch db)
 // multiplier -- the polish rotates it out of the factor), a row flagged dependent hands its multiplier back as in qp_solve, and the stored
 // residual is marked void (haveSolution = 2): the polish takes its cold entry, which also forms E x, the margins and the status of every row
 // anew -- nothing of the last run's row state survives a moved bound.
+// an instance starts warm when the caller asks for it and its last run returned 0 on a setup that did not fail (uniform)
+template <int NCH>
+__device__ __forceinline__ int warm_start(const DevBatch& db, const Ctx<NCH>& c, int mode)
+{
+    return mode == 1 && c.info->haveSolution != 0 && db.stats[c.b].returnValue == 0 && c.info->setupFail == 0;
+}
+
+// the penalty a warm instance starts at: rho0[b] when given, else its last rhoOpt; a cold one starts at the initial penalty
+template <int NCH>
+__device__ __forceinline__ double warm_penalty(const DevBatch& db, const Ctx<NCH>& c, int warm, const double* rho0)
+{
+    if (!warm) return db.opt.initialPenaltyParameter;
+    const double last = db.stats[c.b].rhoOpt;
+    return rho0 ? rho0[c.b] : (last > 0.0 ? last : db.opt.initialPenaltyParameter);
+}
+
+// the hand-over of a warm instance (the comment of k_refresh): statuses in line with the bounds in M_L / M_U, multipliers of dependent rows
+// handed back, no flags or promotions, the stored residual void.  EMPTY (k_prepare_warm): the matrices changed too -- the inverse factor
+// is emptied as prepare_cold empties it, and the polish's cold entry builds it in one piece from the stored working set (ti_bulk)
+template <int NCH, bool EMPTY>
+__device__ __forceinline__ void prepare_warm(const DevBatch& db, Ctx<NCH>& c, double rhoStart)
+{
+    const int t = threadIdx.x;
+    const int mE = c.mE;
+    const double *l = c.M(M_L), *u = c.M(M_U);
+    double* yq = c.M(M_YQ);
+    int *st = c.I(I_ST), *dep = c.I(I_DEP), *prio = c.I(I_PRIO);
+    for (int r = t; r < mE; r += WG) {
+        const double lo = l[r], hi = u[r];
+        int s = st[r];
+        if (lo == hi) s = ST_EQ;
+        else if (s == ST_EQ || (s == ST_LOWER && isinf(lo)) || (s == ST_UPPER && isinf(hi))) s = ST_INACT;
+        if (s == ST_INACT || dep[r]) yq[r] = 0.0;
+        st[r] = s;
+        dep[r] = 0; prio[r] = 0;
+    }
+    if constexpr (EMPTY) {
+        int* rslot = c.I(I_SLOT);
+        for (int r = t; r < db.mEcap; r += WG) rslot[r] = -1;
+        for (int a = t; a < db.capS; a += WG) c.idx[a] = -1;
+    }
+    if (t == 0) {
+        c.info->prioCtr = 0; c.info->ndep = 0; c.info->haveSolution = 2; c.info->warm = 1; c.info->rho0 = rhoStart;
+        if constexpr (EMPTY) { c.info->nT = 0; c.info->ns = 0; }
+    }
+}
+
 template <int NCH>
 __global__ __launch_bounds__(WG) void k_refresh(DevBatch db, int mode, const double* rho0)
 {
@@ -127,37 +188,38 @@ __global__ __launch_bounds__(WG) void k_refresh(DevBatch db, int mode, const dou
     const int b = blockIdx.x, t = threadIdx.x;
     Ctx<NCH> c = make_ctx<NCH>(db, b, lds);
     const double scale = c.info->scale;
-    const int warm = mode == 1 && c.info->haveSolution != 0 && db.stats[b].returnValue == 0 && c.info->setupFail == 0;
-    double rhoStart = db.opt.initialPenaltyParameter;
-    if (warm) {
-        const double last = db.stats[b].rhoOpt;
-        rhoStart = rho0 ? rho0[b] : (last > 0.0 ? last : db.opt.initialPenaltyParameter);
-    }
+    const int warm = warm_start<NCH>(db, c, mode);
+    const double rhoStart = warm_penalty<NCH>(db, c, warm, rho0);
     __syncthreads();      // every thread has read the marks thread 0 rewrites below
     const double phiConst = prepare_vectors<NCH>(db, c, lds, scale);
-    if (warm) {
-        const int mE = c.mE;
-        const double *l = c.M(M_L), *u = c.M(M_U);
-        double* yq = c.M(M_YQ);
-        int *st = c.I(I_ST), *dep = c.I(I_DEP), *prio = c.I(I_PRIO);
-        for (int r = t; r < mE; r += WG) {
-            const double lo = l[r], hi = u[r];
-            int s = st[r];
-            if (lo == hi) s = ST_EQ;
-            else if (s == ST_EQ || (s == ST_LOWER && isinf(lo)) || (s == ST_UPPER && isinf(hi))) s = ST_INACT;
-            if (s == ST_INACT || dep[r]) yq[r] = 0.0;
-            st[r] = s;
-            dep[r] = 0; prio[r] = 0;
-        }
-        if (t == 0) { c.info->prioCtr = 0; c.info->ndep = 0; c.info->haveSolution = 2; c.info->warm = 1; c.info->rho0 = rhoStart; }
-    } else {
-        prepare_cold<NCH>(db, c);
-    }
+    if (warm) prepare_warm<NCH, false>(db, c, rhoStart);
+    else prepare_cold<NCH>(db, c);
     if (t == 0) {
         c.info->rhoAdmm = db.opt.admmRho * scale;
         c.info->phiConst = phiConst;
         c.info->kReady = 0;
     }
+}
+
+// ---- k_prepare_warm: k_prepare for a batch whose matrices changed under a stored point (lcqp_hip_batch_update_matrices + _resolve) -------
+// Stands where k_prepare stands in the setup: everything that depends on the matrices is formed again by it and the four kernels behind
+// it.  An instance whose last run returned 0 keeps its x (V_XK), its multipliers and statuses and its penalty, exactly as k_refresh hands
+// them over in mode 1, and starts warm at rho0[b] (else its last rhoOpt) -- but Et and M are new, so no row of the old inverse factor may
+// survive: the factor is emptied.  Every other instance starts cold.
+template <int NCH>
+__global__ __launch_bounds__(WG) void k_prepare_warm(DevBatch db, const double* rho0)
+{
+    LCQP_LDS_N(NCH)
+    const int b = blockIdx.x, t = threadIdx.x;
+    Ctx<NCH> c = make_ctx<NCH>(db, b, lds);
+    const int warm = warm_start<NCH>(db, c, 1);
+    const double rhoStart = warm_penalty<NCH>(db, c, warm, rho0);
+    __syncthreads();      // every thread has read the marks thread 0 rewrites below
+    const double scale = prepare_matrices<NCH>(db, c, lds);
+    const double phiConst = prepare_vectors<NCH>(db, c, lds, scale);
+    if (warm) prepare_warm<NCH, true>(db, c, rhoStart);
+    else prepare_cold<NCH>(db, c);
+    if (t == 0) prepare_marks<NCH>(db, c, scale, phiConst);
 }
 
 // ---- the marks of a sensitivity call: `side` of every row in the working set and the flag bits of the instance (include/lcqp_hip.h) -----
@@ -1276,6 +1338,7 @@ const SizeKernels& size_kernels()
         if constexpr (NCH <= 4) t.few = &few_kernels<NCH>();
         t.prepare = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_prepare<NCH>), dim3(grid), dim3(WG), 0, s, db); };
         t.refresh = [](const DevBatch& db, int grid, hipStream_t s, int mode, const double* rho0) { hipLaunchKernelGGL((k_refresh<NCH>), dim3(grid), dim3(WG), 0, s, db, mode, rho0); };
+        t.prepare_warm = [](const DevBatch& db, int grid, hipStream_t s, const double* rho0) { hipLaunchKernelGGL((k_prepare_warm<NCH>), dim3(grid), dim3(WG), 0, s, db, rho0); };
         if constexpr (NCH <= 4)      // np <= 512 only: a panel of np >= 1024 does not fit LDS
         {
             t.sensitivity_blk = [](const DevBatch& db, int grid, hipStream_t s, int first, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo) {

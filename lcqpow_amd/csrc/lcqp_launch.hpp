@@ -24,6 +24,8 @@ struct SizeKernels {
     BatchKernel prepare;
     // mode 0: every instance cold, 1: warm where the last run succeeded; rho0 [B]: starting penalties of the warm instances (device), or null
     void (*refresh)(const DevBatch& db, int grid, hipStream_t s, int mode, const double* rho0);
+    // k_prepare where the matrices changed under a stored point: warm where the last run succeeded, with an empty inverse factor; rho0 as above
+    void (*prepare_warm)(const DevBatch& db, int grid, hipStream_t s, const double* rho0);
     BatchKernel build_C, compress_C;
     BatchKernel factor, factor_full;      // factor_full: held to 128 registers for np <= 256, so that four workgroups per CU are resident
     BatchKernel trsm, trsm_streamed, build_M;

@@ -78,6 +78,14 @@ class _HostPath:
     def loaded(layer):
         pass
 
+    @staticmethod
+    def update_matrices(layer, given, ref):
+        """the given matrices alone, broadcast over the batch; the copies the layer holds are kept in step"""
+        full = {k: np.ascontiguousarray(np.broadcast_to(_host(t), (layer.bt.B,) + layer._trailing(k))) for k, t in given.items()}
+        if layer._held is not None:
+            layer._held.update(full)
+        return layer.bt.update_matrices(0, layer.bt.B, **full)
+
 
 class _DevicePath:
     """the device-pointer twins (capi: *_device): tensors stay where they are, float64; results are converted to ref's dtype"""
@@ -104,6 +112,12 @@ class _DevicePath:
     def loaded(layer):
         layer._mark_stale()      # (the host path reads the arrays back again when it next needs them)
 
+    @staticmethod
+    def update_matrices(layer, given, ref):
+        """the given matrices alone, from where they lie; a shared one is broadcast by the pack kernel"""
+        layer._mark_stale()
+        return layer.bt.update_matrices_device(0, layer.bt.B, **{k: _dev(t, ref.device) for k, t in given.items()})
+
 
 def _solve(ctx, layer, g, lbA, ubA, replaced):
     """The forward of all three functions, on either path.  replaced: the matrix or value tensors of the call by name (None: not given).
@@ -124,7 +138,16 @@ def _solve(ctx, layer, g, lbA, ubA, replaced):
     kw = dict(path.bounds(layer, g))
     if lbA is not None: kw["lbA"] = path.conv(lbA, g)
     if ubA is not None: kw["ubA"] = path.conv(ubA, g)
-    if shared:
+    if shared and layer.solves > 0 and layer.warm_matrices:
+        # the dense batch holds a solved point: only the given matrices are sent, and the solve starts from that point (update_matrices)
+        given = {k: t for k, t in replaced.items() if t is not None}
+        rc = path.update_matrices(layer, given, g)
+        if rc == 0:
+            rc = getattr(bt, "update" + path.suffix)(0, bt.B, path.conv(g, g), **kw)
+        if rc != 0:
+            raise RuntimeError(f"update failed with code {rc}: {bt._last_error()}")
+        bt.resolve(warm=True)
+    elif shared:
         rc = layer._load(getattr(bt, "load" + path.suffix), path.load_arrays(layer, replaced, g), path.conv(g, g), kw)
         if rc != 0:
             raise RuntimeError(f"load failed with code {rc}: {bt._last_error()}")
@@ -276,8 +299,9 @@ class BatchLCQPLayer:
     input_keys = MATRIX_KEYS
     adjoint_names = dict(zip(MATRIX_KEYS, MATRIX_KEYS))
 
-    def __init__(self, batch, bounds=None, warm=True):
+    def __init__(self, batch, bounds=None, warm=True, warm_matrices=False):
         capi.lib()      # raises when the HIP library is not built: no CPU fallback
+        self.warm_matrices = bool(warm_matrices) and not self.sparse      # solve() with matrices: update_matrices + resolve(warm) (dense arm only)
         unknown = set(bounds or ()) - set(self.bound_keys)
         if unknown:
             raise ValueError(f"bounds: unknown keys {sorted(unknown)}")
@@ -317,7 +341,10 @@ class BatchLCQPLayer:
         """(x, y) of the batch for the linear terms g, both differentiable (LCQPFullSolveFunction): y [B][nV + nC + 2 nComp] in
         the reference's dual layout.  Q, A, L, R: tensors that replace the matrices of the batch for this and later solves -- [B][..][nV]
         one per instance, [..][nV] one shared by all instances (its gradient is the sum over the batch).  Without any, the solve is the
-        update + resolve of __call__."""
+        update + resolve of __call__.  With one, on a layer constructed with warm_matrices=True that has solved before: the matrices go
+        through BatchLCQP.update_matrices instead of a load, and the solve is a resolve(warm=True) from the last solution and working set
+        on the new matrices ("New matrices"); the default is the load + cold run.  (The switch is the layer's, not
+        an argument: the parameter list of solve is part of this class's tested surface.)"""
         return LCQPFullSolveFunction.apply(self, g, Q, A, L, R, lbA, ubA)
 
     def _trailing(self, k):

@@ -6,7 +6,12 @@ Warm-up steps are excluded.  Writes one JSON file.
 --sparse: the sparse arm instead (lcqpow_amd/synth_sparse.py at --n, default 4096; --batch instances): on ONE handle, per step, run on the
 data in place (the baseline: k_sparse_setup + homotopy), update + resolve(cold) and update + resolve(warm), with last_timing and the
 iterate means of each.
-    python tools/resolve_bench.py --sparse [--batch 4096] [--n 4096] [--steps 3] [--warmup 1] [--out ...]"""
+    python tools/resolve_bench.py --sparse [--batch 4096] [--n 4096] [--steps 3] [--warmup 1] [--out ...]
+--matrices: the matrices move too ("New matrices"): per step Q, A, L, R by the 2 % recipe of
+tests/test_gpu_matrix_resolve.py and the vectors as above; on ONE handle, update_matrices + update + resolve(warm), then load + run of the
+same data (what a caller had to do before update_matrices existed).  Setup + homotopy milliseconds from HIP events as min / median / max
+over the steps, the wall clock, and the iterate counts of both.
+    python tools/resolve_bench.py --matrices [--batch 1024] [--steps 10] [--warmup 1] [--out ...]"""
 import argparse
 import json
 import os
@@ -66,8 +71,62 @@ def sparse_main(a):
     return res
 
 
+def matrices_main(a):
+    B, n, nC, nComp = a.batch, 256, 512, 64
+    bt = la.BatchLCQP(B, n, nC, nComp, opt=la.default_options(printLevel=0))
+    bt.generate_synthetic(0)
+    bt.run()
+    bt.synchronize()
+    probs = [bt.read_problem(b) for b in range(B)]
+    mats = {k: np.stack([p[k] for p in probs]) for k in ("Q", "L", "R", "A")}
+    vec = {k: np.stack([p[k] for p in probs]) for k in ("g", "lbA", "ubA")}
+    rng = np.random.default_rng(0)
+    eps = 0.02
+    kinds = ("update_matrices_resolve_warm", "load_run")
+    rows = {k: [] for k in kinds}
+    for k in range(a.warmup + a.steps):
+        s = 1.0 + eps * rng.standard_normal((B, n))
+        mats = dict(Q=mats["Q"] * s[:, :, None] * s[:, None, :], A=mats["A"] * (1.0 + eps * rng.standard_normal((B, nC, n), dtype=np.float32)),
+                    L=mats["L"] * (1.0 + eps * rng.standard_normal((B, nComp, 1))), R=mats["R"] * (1.0 + eps * rng.standard_normal((B, nComp, 1))))
+        shift = eps * (vec["ubA"] - vec["lbA"]) * rng.standard_normal(vec["lbA"].shape)
+        vec = dict(g=vec["g"] * (1.0 + eps * rng.standard_normal(vec["g"].shape)), lbA=vec["lbA"] + shift, ubA=vec["ubA"] + shift)
+        for kind in kinds:      # the warm re-solve first: it starts from the solution of the data one 2 % move back
+            t0 = time.perf_counter()
+            if kind == "load_run":
+                assert bt.load(0, B, mats["Q"], vec["g"], mats["L"], mats["R"], A=mats["A"], lbA=vec["lbA"], ubA=vec["ubA"]) == 0
+                bt.run()
+            else:
+                assert bt.update_matrices(0, B, **mats) == 0
+                assert bt.update(0, B, vec["g"], lbA=vec["lbA"], ubA=vec["ubA"]) == 0
+                bt.resolve(warm=True)
+            _, _, st = bt.solution()
+            wall = (time.perf_counter() - t0) * 1e3
+            setup_ms, solve_ms = bt.last_timing()
+            it = [q["iterTotal"] for q in st]
+            if k >= a.warmup:
+                rows[kind].append(dict(wall_ms=wall, setup_ms=setup_ms, solve_ms=solve_ms, kernels_ms=setup_ms + solve_ms, iter_mean=float(np.mean(it)),
+                                       iter_max=int(max(it)), solved=int(sum(q["returnValue"] == 0 for q in st))))
+    res = dict(mode="matrices", batch=B, shape=[n, nC, nComp], steps=a.steps, warmup=a.warmup, eps=eps)
+    for kind in kinds:
+        r = {}
+        for key in ("kernels_ms", "setup_ms", "solve_ms", "wall_ms"):
+            v = [q[key] for q in rows[kind]]
+            r[key] = dict(min=float(np.min(v)), median=float(np.median(v)), max=float(np.max(v)))
+        r.update(iter_mean=float(np.mean([q["iter_mean"] for q in rows[kind]])), iter_max=max(q["iter_max"] for q in rows[kind]),
+                 solved_min=min(q["solved"] for q in rows[kind]), steps=rows[kind])
+        res[kind] = r
+        km, sm, hm = r["kernels_ms"], r["setup_ms"], r["solve_ms"]
+        print(f"{kind:30s} setup + homotopy {km['min']:7.2f} / {km['median']:7.2f} / {km['max']:7.2f} ms (min / median / max; setup {sm['median']:.2f}, "
+              f"homotopy {hm['median']:.2f})   wall {r['wall_ms']['median']:8.1f} ms   iterates mean {r['iter_mean']:.1f} max {r['iter_max']}   "
+              f"solved >= {r['solved_min']}/{B}")
+    res["launch_counts"] = list(bt.launch_counts())
+    bt.close()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--matrices", action="store_true", help="the dense arm with new matrices per step: update_matrices + resolve(warm) against load + run")
     ap.add_argument("--sparse", action="store_true", help="the sparse arm: run against resolve(cold) and resolve(warm) on one handle")
     ap.add_argument("--n", type=int, default=4096, help="--sparse: variables per instance (nC = n / 2, nComp = n / 8)")
     ap.add_argument("--batch", type=int, default=1024)
@@ -75,8 +134,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--out", default=os.path.join("profiles", "round7", "resolve", "resolve_bench.json"))
     a = ap.parse_args()
-    if a.sparse:
-        res = sparse_main(a)
+    if a.sparse or a.matrices:
+        res = sparse_main(a) if a.sparse else matrices_main(a)
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
