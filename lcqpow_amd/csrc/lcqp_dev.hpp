@@ -315,7 +315,7 @@ __device__ __forceinline__ int qp_adapt_rho(Ctx<NCH>& c, const double* g)
 }
 
 // ---------------------------------------------------------------------------------------------
-// Dependent-row rules of the subsolver (ROBUST = true in every kernel since round 2: k_lcqp_run, k_qp_solve; oracle: q->robust).
+// Dependent-row rules of the subsolver (in every kernel since round 2: k_lcqp_run, k_qp_solve; oracle: q->robust).
 // (1) Rows the last factorisation of S flagged as linearly dependent on the rows before them: the correction neither
 //     moved their multipliers nor enforced their equations.  Strictly inside its bound: the row is not active.
 //     Violated: it must be active, so it is promoted to the front of the list and another row becomes the dependent
@@ -731,7 +731,71 @@ __device__ __forceinline__ void ti_delete(Ctx<NCH>& c, int p, int& nT, int& ns)
 //     wrong-signed multiplier leaves, else the most violated row enters -- and 4 n + 32 more trials: the full primal-dual update
 //     thrashes on LP-like QPs (singular Hessian, |g| ~ 1e7 at the end of a penalty homotopy).
 constexpr int DAMP_ROUND = 3;
-template <int NCH, bool ROBUST, bool LR>
+// PolishView: the rows and vectors of one polish and the constants of the call, built once in qp_polish and handed to its phases
+// (all of them inlined into the one call site).  What a phase reads or changes of the loop's state is in its parameter list.
+struct PolishView {
+    double *x, *r1, *cv, *du, *qx, *xs, *xref;      // V_XT, V_R1, V_C, V_DU, V_TMP, V_XS, V_XREF
+    double *yt, *ex, *mg;                           // multipliers, E x, margins of the rows (LDS with LR)
+    int* st;                                        // working set (LDS with LR)
+    double *ylv, *rn;
+    int* hotc;
+    const double* hotv;
+    const double *l, *u;
+    int *dep, *prio, *list, *rslot;
+    double *r2, *dy;
+    int* idx;
+    const double* g;                                // the arguments of the call
+    double ytol, rtolG;
+    int reuse, damp;
+    double spv, shrinkF;
+    int capNa, maxTrials;
+};
+
+// damped: the one row that may leave (largest wrong-signed multiplier, lowest index among equals); 1 << 30 when there is none
+__device__ __forceinline__ int polish_damped_leave_row(const int* st, const double* yt, int mE, double ytol, const int t, Lds lds)
+{
+    double vb = 0.0;
+    for (int r = t; r < mE; r += WG) { const int s = st[r]; const double yv = yt[r]; if ((s == ST_LOWER && yv > ytol) || (s == ST_UPPER && yv < -ytol)) vb = fmax(vb, fabs(yv)); }
+    const double ylvmax = block_max(vb, lds);
+    int rb = 1 << 30;
+    for (int r = t; r < mE; r += WG) { const int s = st[r]; const double yv = yt[r]; if (((s == ST_LOWER && yv > ytol) || (s == ST_UPPER && yv < -ytol)) && fabs(yv) >= ylvmax) rb = min(rb, r); }
+    return (int)(-block_max((double)(-rb), lds) + 0.5);
+}
+
+// |x - x_last sweep| for the margins; x becomes the x of the last sweep.  Returns the shrink of the margins per unit row norm.
+template <int NCH>
+__device__ __forceinline__ double polish_sweep_distance(Ctx<NCH>& c, const PolishView& v, double& xnrm)
+{
+    double d2 = 0.0, x2 = 0.0;
+    for (int i = tid_here(); i < c.n; i += WG) { const double xv = v.x[i], dd = xv - v.xs[i]; d2 += dd * dd; x2 += xv * xv; v.xs[i] = xv; }     // the n variables, not the padding
+    // |E_r (x - x_last)| <= |E_r| |x - x_last|; the factor covers the tolerance that moves with E_r x (feasTol (1 + |E_r x|)),
+    // the second term the rounding of a computed E_r x (~ eps |E_r| |x|)
+    double sd2, sx2;
+    block_sum2(d2, x2, sd2, sx2, c.lds);
+    xnrm = uniform_d(sqrt(sx2));
+    return uniform_d(sqrt(sd2) * v.shrinkF + 1e-13 * xnrm);
+}
+
+// a polish that gives up leaves no multipliers of leaving rows behind (M_YLV is zero between trials)
+template <int NCH>
+__device__ __forceinline__ void polish_give_up(Ctx<NCH>& c, const PolishView& v)
+{
+    for (int r = tid_here(); r < c.mE; r += WG) v.ylv[r] = 0.0;
+    __syncthreads();
+}
+
+// how far an inactive row lies outside its (tolerance-widened) bounds; 0 for an active row
+__device__ __forceinline__ double polish_violation(const PolishView& v, const lcqp_options_t& o, int r)
+{
+    if (v.st[r] != ST_INACT) return 0.0;
+    const double e = v.ex[r], ftol = o.feasTol * (1.0 + fabs(e));
+    return (e < v.l[r] - ftol) ? v.l[r] - e : ((e > v.u[r] + ftol) ? e - v.u[r] : 0.0);
+}
+
+// Steps (a) to (d) of the trial are still inline.  Tried one at a time as an inlined function over PolishView at NCH = 2 (k_lcqp_run<2,true,0>,
+// 52557 instructions): the correction kept the count but changed four places; the leaving rows kept the opcodes with 23 other lines; stage 1
+// gave 52563, the entry 52693, stage 2 52494, the factor update 52726.  Each changes how the persistent kernels spill, so none is cut out yet.
+template <int NCH, bool LR>
 __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse, double ytol, double rtolG, int damp)
 {
     constexpr int np = 128 * NCH;
@@ -758,37 +822,15 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
     // ytol = feasTol (1 + |g|_inf), rtolG = resTol (1 + |g|_inf): formed by the caller, once per QP (long-lived uniform doubles are held in scalar registers: uniform_d)
     const double shrinkF = uniform_d(1.0 + 1e-6 + o.feasTol);
     int na = 0, nsl = 0, fact_valid = 0;
-    int prioCtr = ROBUST ? uniform_i(c.info->prioCtr) : 0;
+    int prioCtr = uniform_i(c.info->prioCtr);
     const int capNa = min(min(min(max(2 * c.n, 64), mE), capS), max_active(NCH));   // room for the degenerate vertices of small problems
 
-    // |x - x_last sweep| for the margins; x becomes the x of the last sweep.  Returns the shrink of the margins per unit row norm.
     double xnrm = 0.0;      // |x|_2 at the top of the current trial (scale of the rounding floor of E_r x)
-    auto sweep_distance = [&]() -> double {
-        double d2 = 0.0, x2 = 0.0;
-        for (int i = tid_here(); i < c.n; i += WG) { const double xv = x[i], dd = xv - xs[i]; d2 += dd * dd; x2 += xv * xv; xs[i] = xv; }     // the n variables, not the padding
-        // |E_r (x - x_last)| <= |E_r| |x - x_last|; the factor covers the tolerance that moves with E_r x (feasTol (1 + |E_r x|)),
-        // the second term the rounding of a computed E_r x (~ eps |E_r| |x|)
-        double sd2, sx2;
-        block_sum2(d2, x2, sd2, sx2, c.lds);
-        xnrm = uniform_d(sqrt(sx2));
-        return uniform_d(sqrt(sd2) * shrinkF + 1e-13 * xnrm);
-    };
-
-    // a polish that gives up leaves no multipliers of leaving rows behind (M_YLV is zero between trials)
-    auto give_up = [&]() -> int {
-        for (int r = tid_here(); r < mE; r += WG) ylv[r] = 0.0;
-        __syncthreads();
-        return 0;
-    };
-
     int capOn = 0;      // the cap on entering rows applies to polishes that start from an empty working set (oracle: cap_on)
     int nrefine = 0;    // refinement corrections taken for the active rows alone
     const int maxTrials = damp ? o.maxTrials + 4 * c.n + 32 : o.maxTrials;
-    auto violation = [&](int r) -> double {
-        if (st[r] != ST_INACT) return 0.0;
-        const double e = ex[r], ftol = o.feasTol * (1.0 + fabs(e));
-        return (e < l[r] - ftol) ? l[r] - e : ((e > u[r] + ftol) ? e - u[r] : 0.0);
-    };
+    const PolishView v = {x, r1, cv, du, qx, xs, xref, yt, ex, mg, st, ylv, rn, hotc, hotv, l, u, dep, prio, list, rslot, r2, dy, idx,
+                          g, ytol, rtolG, reuse, damp, spv, shrinkF, capNa, maxTrials};
     for (int trial = 0; trial < maxTrials; trial++) {
         const int t = tid_here();      // per trial: nothing derived from the thread number is carried around the loop (it would be hoisted and spilled)
         c.cTrials++;
@@ -814,24 +856,17 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
                 }
                 int cntA = 0;
                 wg_map<4>(mE, [&](int r) { return MapID{st[r], yt[r]}; },
-                          [&](int r, MapID v) { if (ROBUST && v.s == ST_INACT && v.a != 0.0) yt[r] = 0.0; ylv[r] = 0.0; cntA += (v.s != ST_INACT); });
+                          [&](int r, MapID v) { if (v.s == ST_INACT && v.a != 0.0) yt[r] = 0.0; ylv[r] = 0.0; cntA += (v.s != ST_INACT); });
                 capOn = (block_sum_i(cntA, c.lds) == 0);
-                (void)sweep_distance();
+                (void)polish_sweep_distance<NCH>(c, v, xnrm);
                 need_true = 1;
             }
         } else {
             // (a) leaving rows; margins of the inactive rows shrink by |E_r| * |x - x_last sweep|
-            const double dl = sweep_distance();
+            const double dl = polish_sweep_distance<NCH>(c, v, xnrm);
             int cntLv = 0;
             int rLeave = -1;      // damped: the one row that may leave (largest wrong-signed multiplier, lowest index among equals)
-            if (damp) {
-                double vb = 0.0;
-                for (int r = t; r < mE; r += WG) { const int s = st[r]; const double yv = yt[r]; if ((s == ST_LOWER && yv > ytol) || (s == ST_UPPER && yv < -ytol)) vb = fmax(vb, fabs(yv)); }
-                const double ylvmax = block_max(vb, c.lds);
-                int rb = 1 << 30;
-                for (int r = t; r < mE; r += WG) { const int s = st[r]; const double yv = yt[r]; if (((s == ST_LOWER && yv > ytol) || (s == ST_UPPER && yv < -ytol)) && fabs(yv) >= ylvmax) rb = min(rb, r); }
-                rLeave = (int)(-block_max((double)(-rb), c.lds) + 0.5);
-            }
+            if (damp) rLeave = polish_damped_leave_row(st, yt, mE, ytol, t, c.lds);
             wg_map<4>(mE, [&](int r) { return MapID3{st[r], yt[r], mg[r], rn[r]}; },
                       [&](int r, MapID3 v) {
                           int s = v.s;
@@ -841,7 +876,7 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
             nlv = block_sum_i(cntLv, c.lds);
             changed = nlv > 0;
             // (b) stage 1: E_r x of the inactive rows the margins cannot rule out, and of the active rows flagged dependent
-            const bool depRows = ROBUST && uniform_i(c.info->ndep) > 0;
+            const bool depRows = uniform_i(c.info->ndep) > 0;
             const int nread = wg_compact(mE, [&](int r) { return (st[r] == ST_INACT) ? !(mg[r] > 1e-10) : (depRows && dep[r] != 0); }, list, c.lds);
             wg_rows<NCH, true>(c.E, list, nread, x, ex, nullptr, c.lds, [](int, double) {}, hotc, hotv);
             // Entering rows are capped (oracle: qp_polish, same arithmetic): when more than max(n/8, 16) inactive rows are violated -- a cold
@@ -854,11 +889,11 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
                 vcut = INFINITY;
                 if (!changed) {
                     double vm = 0.0;
-                    for (int a = t; a < nread; a += WG) vm = fmax(vm, violation(list[a]));
+                    for (int a = t; a < nread; a += WG) vm = fmax(vm, polish_violation(v, o, list[a]));
                     vm = block_max(vm, c.lds);
                     if (vm > 0.0) {
                         int rb = 1 << 30;
-                        for (int a = t; a < nread; a += WG) { const int r = list[a]; if (violation(r) >= vm) rb = min(rb, r); }
+                        for (int a = t; a < nread; a += WG) { const int r = list[a]; if (polish_violation(v, o, r) >= vm) rb = min(rb, r); }
                         rEnter = (int)(-block_max((double)(-rb), c.lds) + 0.5);
                         vcut = vm;
                     }
@@ -866,7 +901,7 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
             } else
             if (capOn) {
                 double vm = 0.0, cv = 0.0, vmax, nviol;
-                for (int a = t; a < nread; a += WG) { const double v = violation(list[a]); if (v > 0.0) { cv += 1.0; vm = fmax(vm, v); } }
+                for (int a = t; a < nread; a += WG) { const double vi = polish_violation(v, o, list[a]); if (vi > 0.0) { cv += 1.0; vm = fmax(vm, vi); } }
                 block_max_sum(vm, cv, vmax, nviol, c.lds);
                 const int cap = max(c.n / 8, 16);      // (the oracle uses 8)
                 if (nviol > (double)cap) {
@@ -874,7 +909,7 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
                     for (int it = 0; it < 12; it++) {
                         const double mid = 0.5 * (lo + hi);
                         int cnt = 0;
-                        for (int a = t; a < nread; a += WG) cnt += (violation(list[a]) >= mid);
+                        for (int a = t; a < nread; a += WG) cnt += (polish_violation(v, o, list[a]) >= mid);
                         if (block_sum_i(cnt, c.lds) > cap) lo = mid; else hi = mid;
                     }
                     vcut = uniform_d(lo);      // the lower end: a few more than cap rows (with the upper end a tie of many equally violated rows would never enter)
@@ -908,7 +943,7 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
             const unsigned packed = (unsigned)block_sum_i((chg & 1) | (((chg >> 1) & 1) << 10) | ((countDense ? nDense : 0) << 20), c.lds);
             const int chgBits = ((packed & 1023u) ? 1 : 0) | (((packed >> 10) & 1023u) ? 2 : 0);
             if (t == 0) c.info->work[4] += countDense ? (double)(packed >> 20) : (double)nread;
-            if (ROBUST && (chgBits & 2)) { prioCtr++; if (t == 0) c.info->prioCtr = prioCtr; }
+            if (chgBits & 2) { prioCtr++; if (t == 0) c.info->prioCtr = prioCtr; }
             changed |= (chgBits != 0);
             need_true = !changed;
         }
@@ -995,13 +1030,13 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
             // more active rows than variables while the set still changes by more than max(n/2, 32) rows per trial: the primal-dual update has
             // overshot (a cold start far from the solution, where every violated row enters at once) and more trials only thrash with
             // factors at full rank -- give up and let ADMM produce a working set (oracle: the same rule)
-            if (trial >= 2 && nT - ndel + nadd > c.n && ndel + nadd > max(c.n / 2, 32)) return give_up();
+            if (trial >= 2 && nT - ndel + nadd > c.n && ndel + nadd > max(c.n / 2, 32)) { polish_give_up<NCH>(c, v); return 0; }
             // in one piece when the factor is empty, when most of it would change, or when promotions dictate the order
             // (oracle: the same rule; there "in one piece" is a reset followed by appends in list order)
             PROF(c, P_UPD_PRE);
             // ... or when the row-by-row updates would cost more than the rebuild (measured: a rotation ~ 3, an append ~ 7, a rebuild ~ 96 units of
             // 7 us under load; same-box A/B 35.1 -> 34.5 ms)
-            const bool bulk = (ROBUST && prioCtr > 0) || (nT == 0 && nadd > 0) || (ndel > 0 && ndel >= max(nT / 2, 8)) || nadd >= 16 || (3 * ndel + 7 * nadd >= 96);
+            const bool bulk = prioCtr > 0 || (nT == 0 && nadd > 0) || (ndel > 0 && ndel >= max(nT / 2, 8)) || nadd >= 16 || (3 * ndel + 7 * nadd >= 96);
             int naAll = 0;
             if (bulk) {
                 int cntAct = 0;
@@ -1011,10 +1046,10 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
             }
             if (bulk && naAll <= capNa) {
                 int na2 = 0;
-                if (ROBUST)      // latest promotion first (ascending row index within one), then the rest
-                    for (int stamp = prioCtr; stamp >= 1; stamp--)
-                        na2 += wg_compact(mE, [&](int r) { return st[r] != ST_INACT && prio[r] == stamp; }, idx + na2, c.lds);
-                na2 += wg_compact(mE, [&](int r) { return st[r] != ST_INACT && (!ROBUST || prioCtr == 0 || prio[r] == 0); }, idx + na2, c.lds);
+                // latest promotion first (ascending row index within one), then the rest
+                for (int stamp = prioCtr; stamp >= 1; stamp--)
+                    na2 += wg_compact(mE, [&](int r) { return st[r] != ST_INACT && prio[r] == stamp; }, idx + na2, c.lds);
+                na2 += wg_compact(mE, [&](int r) { return st[r] != ST_INACT && (prioCtr == 0 || prio[r] == 0); }, idx + na2, c.lds);
                 if (LR) {      // the Cholesky tile of the one-piece rebuild takes the whole arena: the row state waits in its global arrays
                     double *gyt = c.M(M_YT), *gex = c.M(M_EX), *gmg = c.M(M_MG); int* gst = c.I(I_STT);
                     for (int r = t; r < mE; r += WG) { gyt[r] = yt[r]; gex[r] = ex[r]; gmg[r] = mg[r]; gst[r] = st[r]; }
@@ -1045,14 +1080,14 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
 #ifdef LCQP_PROFILE
                 if (!bulk) c.prof[13] += (unsigned long long)ndel;
 #endif
-                for (int stamp = (ROBUST && bulk) ? prioCtr : 0; stamp >= 0; stamp--) {
+                for (int stamp = bulk ? prioCtr : 0; stamp >= 0; stamp--) {
                     // stamp > 0: the rows of one promotion; stamp == 0: every active row that is not in the factor yet
                     const int cnt = wg_compact(mE, [&](int r) { return st[r] != ST_INACT && rslot[r] < 0 && (stamp == 0 || prio[r] == stamp); }, list, c.lds);
                     for (int k = 0; k < cnt; k++) {
                         const int r = uniform_i(list[k]);
                         const int rc = ti_append<NCH>(c, r, o.depTau, capNa, nT, ns);
-                        if (rc < 0) { if (t == 0) { c.info->nT = nT; c.info->ns = ns; } __syncthreads(); return give_up(); }
-                        if (ROBUST && t == 0) dep[r] = (rc == 0);
+                        if (rc < 0) { if (t == 0) { c.info->nT = nT; c.info->ns = ns; } __syncthreads(); { polish_give_up<NCH>(c, v); return 0; } }
+                        if (t == 0) dep[r] = (rc == 0);
                         ndepNow += (rc == 0);
                         touched = 1;
 #ifdef LCQP_PROFILE
@@ -1061,13 +1096,11 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
                     }
                 }
             }
-            if (ROBUST) {
-                if (ndepNow > 0 || uniform_i(c.info->ndep) > 0) {
-                    __syncthreads();
-                    for (int r = t; r < mE; r += WG) if (st[r] == ST_INACT || rslot[r] >= 0) dep[r] = 0;
-                }
-                if (t == 0) c.info->ndep = ndepNow;
+            if (ndepNow > 0 || uniform_i(c.info->ndep) > 0) {
+                __syncthreads();
+                for (int r = t; r < mE; r += WG) if (st[r] == ST_INACT || rslot[r] >= 0) dep[r] = 0;
             }
+            if (t == 0) c.info->ndep = ndepNow;
             PROF(c, P_CHOL);
             na = nT; nsl = ns;
             if (touched) { c.cFact++; if (t == 0) c.info->work[3] += 1.0; }
@@ -1077,7 +1110,7 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
         }
         const int nsp = 64 * ((nsl + 63) >> 6);
 #ifdef LCQP_TRACE_QP      // diagnostic build (tools/fuzz_case.py --trace): one line per trial, the oracle prints the same lines when its trace switch is on
-        if (tid_here() == 0) printf("  hip trial %d damp %d: left %d changed %d true %d na %d ns %d dep %d\n", trial, damp, nlv, changed, have_true, na, nsl, ROBUST ? c.info->ndep : 0);
+        if (tid_here() == 0) printf("  hip trial %d damp %d: left %d changed %d true %d na %d ns %d dep %d\n", trial, damp, nlv, changed, have_true, na, nsl, c.info->ndep);
 #endif
         if (have_true) {
             // full correction:  c = L1^-1 r1 ;  S dy = T c - r2 ;  dx = L1^-T (c - T' dy)      (T: the rows of Et in the slots of the factor)
@@ -1144,7 +1177,7 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
         __syncthreads();
         c.cCorr++;
     }
-    return give_up();
+    { polish_give_up<NCH>(c, v); return 0; }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1154,8 +1187,7 @@ __device__ __forceinline__ int qp_polish(Ctx<NCH>& c, const double* g, int reuse
 // qp.hotstart (:158).  On success the solution is left in V_XQ / M_YQ / I_ST.
 // Returns 0, or the exit flag (1 max rounds, 2 infeasible bounds, 3 setup failure).
 // ---------------------------------------------------------------------------------------------
-// ADAPT: rho adaptation between fallback rounds (qp_adapt_rho); on in every kernel (the switch stays for A/B builds).
-template <int NCH, bool ROBUST, bool ADAPT, bool LR = false>
+template <int NCH, bool LR = false>
 __device__ __forceinline__ int qp_solve(Ctx<NCH>& c, int initial, const double* g, const double* y0ref, int* iterations, double gmaxHint = -1.0, int checkBounds = 1)
 {
     constexpr int np = 128 * NCH;
@@ -1178,7 +1210,7 @@ __device__ __forceinline__ int qp_solve(Ctx<NCH>& c, int initial, const double* 
     // the tolerances scale with 1 + |g|_inf: handed over by a caller that has just formed g, else one pass
     const double gsc = uniform_d(1.0 + (gmaxHint >= 0.0 ? gmaxHint : wg_maxabs(g, c.n, c.lds)));
     const double ytolQ = uniform_d(o.feasTol * gsc), rtolQ = uniform_d(o.resTol * gsc);
-    if (ROBUST && uniform_i(c.info->prioCtr) != 0) {     // promotions of dependent rows last for one solve
+    if (uniform_i(c.info->prioCtr) != 0) {     // promotions of dependent rows last for one solve
         int* prio = c.I(I_PRIO);
         for (int r = t; r < mE; r += WG) prio[r] = 0;
         __syncthreads();
@@ -1208,7 +1240,7 @@ __device__ __forceinline__ int qp_solve(Ctx<NCH>& c, int initial, const double* 
     // flagged row's multiplier back: it starts at zero, the stored residual no longer belongs to the stored point, and the polish takes its
     // cold entry (the true residual, every row) on the stored working set.  (round 5; oracle: orc_qp_solve)
     int reuse_stored = use_stored && haveSol != 2;      // 2: the vectors changed since the residual was stored (k_refresh)
-    if (ROBUST && use_stored && uniform_i(c.info->ndep) > 0) {
+    if (use_stored && uniform_i(c.info->ndep) > 0) {
         const int* dep = c.I(I_DEP);
         int z = 0;
         for (int r = t; r < mE; r += WG) if (dep[r] && st[r] != ST_INACT && yq[r] != 0.0) { yq[r] = 0.0; ya[r] = 0.0; z = 1; }
@@ -1250,8 +1282,8 @@ __device__ __forceinline__ int qp_solve(Ctx<NCH>& c, int initial, const double* 
 #ifdef LCQP_TRACE_QP
         if (tid_here() == 0) printf(" hip round %d: admm %d stored %d reuse %d trials so far %d\n", round, n_admm, use_stored, round == 0 && reuse_stored, c.cTrials - trials0);
 #endif
-        if (qp_polish<NCH, ROBUST, LR>(c, g, round == 0 && reuse_stored, ytolQ, rtolQ, round >= DAMP_ROUND)) { solved = 1; break; }
-        if (ADAPT && round >= 1 && n_admm > 0 && qp_adapt_rho<NCH>(c, g) < 0) return 3;      // no usable ADMM factor left
+        if (qp_polish<NCH, LR>(c, g, round == 0 && reuse_stored, ytolQ, rtolQ, round >= DAMP_ROUND)) { solved = 1; break; }
+        if (round >= 1 && n_admm > 0 && qp_adapt_rho<NCH>(c, g) < 0) return 3;      // no usable ADMM factor left
         if (round >= 2) {    // at least 20 ADMM iterations behind us: is the QP infeasible or unbounded?
             certificate = qp_certificate<NCH>(c, g);
             if (certificate) break;
@@ -1285,9 +1317,8 @@ __device__ __forceinline__ void qp_export(Ctx<NCH>& c, double* xdst /*np or n*/,
 // ---------------------------------------------------------------------------------------------
 // LCQProblem::runSolver for one instance (oracle: orc_lcqp_solve).  src/LCQProblem.cpp:444-560.
 // ---------------------------------------------------------------------------------------------
-// ROBUST: the dependent-row rules of the subsolver (polish_dependent_rows); on in every kernel since round 2 (the switch stays for A/B builds).
 // LR: the row state of the subsolver lives in LDS (k_lcqp_run at np <= 256).
-template <int NCH, bool ROBUST, bool LR = false>
+template <int NCH, bool LR = false>
 __device__ __forceinline__ void lcqp_run(Ctx<NCH>& c)
 {
     constexpr int np = 128 * NCH;
@@ -1332,7 +1363,7 @@ __device__ __forceinline__ void lcqp_run(Ctx<NCH>& c)
         const int qpInitial = initial && !uniform_i(c.info->warm);
         const double* y0 = (qpInitial && c.info->hasY0) ? db.y0 + (size_t)c.b * db.nd : nullptr;
         PROF(c, P_LCQP);
-        const int ef = uniform_i(qp_solve<NCH, ROBUST, true, LR>(c, qpInitial, gk, y0, &qpIter, gmax, /*checkBounds=*/initial));
+        const int ef = uniform_i(qp_solve<NCH, LR>(c, qpInitial, gk, y0, &qpIter, gmax, /*checkBounds=*/initial));
         qpIter = uniform_i(qpIter);
         PROF(c, P_MISC);
         st.subproblemIter += qpIter;

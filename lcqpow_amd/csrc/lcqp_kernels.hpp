@@ -58,7 +58,7 @@ __device__ __forceinline__ double prepare_vectors(const DevBatch& db, Ctx<NCH>& 
     return phiConst;
 }
 
-// the subsolver of an instance starts cold: no dependent-row flags or promotions survive (qp_polish<ROBUST>), the inverse factor of the
+// the subsolver of an instance starts cold: no dependent-row flags or promotions survive (qp_polish), the inverse factor of the
 // working-set matrix is empty, no stored solution, a homotopy from x0 at the initial penalty
 template <int NCH>
 __device__ __forceinline__ void prepare_cold(const DevBatch& db, Ctx<NCH>& c)
@@ -1142,8 +1142,9 @@ __global__ __launch_bounds__(WG, LCQP_MINWAVES) void k_lcqp_run(DevBatch db)
 {
     LCQP_LDS_N(NCH)
     Ctx<NCH> c = make_ctx<NCH>(db, blockIdx.x, lds);
-    lcqp_run<NCH, true, LR>(c);      // with the dependent-row rules: since the factor is updated instead of rebuilt they cost nothing here
-                                     // (A/B 73.0 vs 72.0 ms, profiles/round2), so the batched loop and the per-QP path are ONE algorithm
+    // the dependent-row rules are part of the subsolver here too (round 2 measured them behind a switch at 73.0 vs 72.0 ms, profiles/round2:
+    // since the factor is updated instead of rebuilt they cost nothing), so the batched loop and the per-QP path are ONE algorithm
+    lcqp_run<NCH, LR>(c);
 }
 
 // ---- one QP per workgroup with the SubsolverBase semantics ----------------------------------------
@@ -1154,7 +1155,7 @@ __global__ __launch_bounds__(WG, LCQP_MINWAVES) void k_qp_solve(DevBatch db, int
     Ctx<NCH> c = make_ctx<NCH>(db, blockIdx.x, lds);
     const double* y0 = (initial && c.info->hasY0) ? db.y0 + (size_t)c.b * db.nd : nullptr;
     int iters = 0;
-    const int ef = qp_solve<NCH, true, true>(c, initial, c.V(V_GK), y0, &iters);   // single-QP path: dependent-row rules and rho adaptation
+    const int ef = qp_solve<NCH>(c, initial, c.V(V_GK), y0, &iters);   // single-QP path: dependent-row rules and rho adaptation
     if (ef == 0) qp_export<NCH>(c, db.xout + (size_t)c.b * db.n, db.n, db.yout + (size_t)c.b * db.nd);
     if (threadIdx.x == 0) {
         lcqp_stats_t s;

@@ -1,6 +1,6 @@
 """Reference for the dense subsolver's active-set polish, trial by trial, in np.longdouble, with no solver in the loop.
 
-qp_polish (lcqpow_amd/csrc/lcqp_dev.hpp:734-1148; the oracle's twin: oracle/lcqp_oracle.c, qp_polish) is audited from recorded STATES.  A state
+qp_polish (lcqpow_amd/csrc/lcqp_dev.hpp; the oracle's twin: oracle/lcqp_oracle.c, qp_polish) is audited from recorded STATES.  A state
 S_k is what a solve that was allowed exactly k trials left behind (maxRounds = 1, no ADMM, maxTrials = k: the polish gives up after its k-th
 correction, or returns at the stage-2 test of its k-th trial), read back without a launch (lcqp_hip_batch_read_polish / _read_working_set; the
 oracle: orc_qp_read_polish).  A state is a dict with the names of capi._read_polish: xt, xs, xref, yt, stt, l, u, spv and -- the device only --
@@ -8,7 +8,7 @@ ex, mg, rn, hotc, hotv, nHot, row_slot, slot_row, nT, ndep, r1s, gs, aty, qxn, e
 nothing and stores no row norms).  This module imports neither the library nor the oracle.
 
 The problem: min x'Qx/2 + g'x  s.t.  l <= E x <= u over the stacked rows E (k_qp_solve: [A; box rows], k_lcqp_run: [A; L; R; box rows]).
-Signs are the code's (OSQP's): stationarity is -g - Qx - E'y = 0 (lcqp_dev.hpp:922), a row on its lower bound has y <= 0, on its upper y >= 0.
+Signs are the code's (OSQP's): stationarity is -g - Qx - E'y = 0 (qp_polish, stage 2), a row on its lower bound has y <= 0, on its upper y >= 0.
 
 check_state -- invariants of any state:
   rn       |rn_r - |E_r|_2| <= MARGIN gamma_n |E_r|_2 and rn_r >= |E_r|_2 (1 - MARGIN gamma_n)          (wg_row_norms, lcqp_wg.hpp:379-413)
@@ -497,7 +497,7 @@ def polish_case(n, m, box, seed, equalities=True, violated=0.5):
 
 
 # (name, n, m, box, seed, equalities, share of the tight rows violated at x*).  The first case has no equality rows: an equality is active from the
-# start (qp_solve, lcqp_dev.hpp:1243), and the cap on entering rows is for polishes that start from an EMPTY set (:818).
+# start (qp_solve in lcqp_dev.hpp), and the cap on entering rows is for polishes that start from an EMPTY set (qp_polish, cold entry: capOn).
 QP_CASES = (("40x96-cap", 40, 96, False, 2, False, 0.7),
             ("40x96", 40, 96, False, 2, True, 0.5),
             ("200x330-box", 200, 330, True, 1, True, 0.5),

@@ -42,7 +42,7 @@ def qp_solve_k(d, k, keep=False):
 
 
 def paths(states):
-    """what the factor update of each transition had to do, by the kernel's own rule (lcqp_dev.hpp:1004)"""
+    """what the factor update of each transition had to do, by the kernel's own rule (qp_polish in lcqp_dev.hpp, the `bulk` rule of the factor update)"""
     got = set()
     for a, b in zip(states, states[1:]):
         A, B = a["stt"] != 0, b["stt"] != 0
