@@ -5,7 +5,9 @@ again and again with a new linear term and new bounds.
                                                                      synthetic workload at n = 512, iterate counts per step
     python examples/resolve_sequence.py [B=256] [steps=5] matrices   the matrices move too, 2 % per step (an outer loop that re-linearises):
                                                                      update_matrices + update, then the warm re-solve sets up again
-                                                                     around the last solution and working set"""
+                                                                     around the last solution and working set
+    python examples/resolve_sequence.py [B=256] [steps=5] sparse matrices   the value arrays Qx, Ax of the sparse arm move too, 2 % per step:
+                                                                     update_values + update, then the warm re-solve (k_sparse_setup_warm)"""
 import os
 import sys
 import time
@@ -16,14 +18,16 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import lcqpow_amd as la  # noqa: E402
 
 
-def sparse_leg(B, steps):
+def sparse_leg(B, steps, matrices=False):
     from lcqpow_amd import synth_sparse as S
     n, nC, nK = 512, 256, 64
     Qpat, Apat, qo, eo = S.sparse_pattern_arrays(n, nC, nK)
     inst = [S.sparse_values(i, n, nC, nK, orders=(qo, eo)) for i in range(B)]
     sb = la.SparseBatchLCQP(B, n, nC, nK, Qpat, Apat, opt=la.default_options(perturbStep=0, printLevel=0))
     g = np.stack([d["g"] for d in inst]); lbA = np.stack([d["lbA"] for d in inst]); ubA = np.stack([d["ubA"] for d in inst])
-    rc = sb.load(0, B, np.stack([d["Qx"] for d in inst]), g, np.stack([d["Ex"] for d in inst]), lbA=lbA, ubA=ubA)     # the matrices go to the device once
+    Qx, Ax = np.stack([d["Qx"] for d in inst]), np.stack([d["Ex"] for d in inst])
+    qrow, qcol = Qpat.indices, np.repeat(np.arange(n), np.diff(Qpat.indptr))      # CSC: row and column of every stored entry of Q
+    rc = sb.load(0, B, Qx, g, Ax, lbA=lbA, ubA=ubA)     # the matrices go to the device once
     if rc != 0:
         raise RuntimeError(f"load failed with code {rc}")
     sb.run()
@@ -35,6 +39,13 @@ def sparse_leg(B, steps):
         g = g * (1.0 + 0.02 * rng.standard_normal(g.shape))
         shift = 0.02 * (ubA - lbA) * rng.standard_normal(lbA.shape)
         lbA, ubA = lbA + shift, ubA + shift
+        if matrices:      # Q o s s' keeps symmetry and definiteness; every stored entry of [A; L; R] moves on its own
+            s = 1.0 + 0.02 * rng.standard_normal((B, n))
+            Qx = Qx * s[:, qrow] * s[:, qcol]
+            Ax = Ax * (1.0 + 0.02 * rng.standard_normal(Ax.shape))
+            rc = sb.update_values(0, B, Qx=Qx, Ax=Ax)      # (an array that is left out stays as the batch holds it)
+            if rc != 0:
+                raise RuntimeError(f"update_values failed with code {rc}: {la.capi.last_error()}")
         rc = sb.update(0, B, g, lbA=lbA, ubA=ubA)
         if rc != 0:
             raise RuntimeError(f"update failed with code {rc}")
@@ -52,7 +63,7 @@ def main():
     B = int(sys.argv[1]) if len(sys.argv) > 1 else 256
     steps = int(sys.argv[2]) if len(sys.argv) > 2 else 5
     if len(sys.argv) > 3 and sys.argv[3] == "sparse":
-        sparse_leg(B, steps)
+        sparse_leg(B, steps, matrices=len(sys.argv) > 4 and sys.argv[4] == "matrices")
         return
     matrices = len(sys.argv) > 3 and sys.argv[3] == "matrices"
     n, nC, nComp = 256, 512, 64

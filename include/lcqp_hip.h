@@ -471,6 +471,21 @@ int lcqp_hip_chol_solve(int batch, int n, const double* K, const double* b, doub
  *                            factor and penalty -- rho0 [B] (host; every entry finite and > 0, else LCQP_INVALID_ARGUMENT) or NULL for its
  *                            last rhoOpt -- without the zero-penalty QP: runSolver with x0, y0 = the last solution,
  *                            solveZeroPenaltyFirst = false, initialPenaltyParameter = rho.  Every other instance runs cold.
+ *   lcqp_hip_sparse_update_values   new values of the matrices on the pattern of the handle, for instances [first, first + count) of a batch
+ *                            that holds problems (the sparse twin of lcqp_hip_batch_update_matrices): Qx [count][nnzQ], Ax [count][nnzA]
+ *                            as lcqp_hip_sparse_load takes them, NULL: the array stays.  Only those values are written: no vector, no
+ *                            status, multiplier, point, statistic or factor.  Checked before any device call, in this order: neither array
+ *                            (LCQP_INVALID_ARGUMENT), NULL handle (LCQP_LCQPOBJECT_NOT_SETUP), the range (LCQP_INVALID_ARGUMENT), an instance
+ *                            never loaded (LCQP_LCQPOBJECT_NOT_SETUP); a refused call changes nothing.  The setup and the solve no longer
+ *                            belong to the data in place: the sensitivity, panel, Jacobian, adjoint and probe calls answer
+ *                            LCQP_LCQPOBJECT_NOT_SETUP until the next solve.  With Qx the ordering is chosen again from the new diagonals.
+ *                            A cold lcqp_hip_sparse_resolve behind it is lcqp_hip_sparse_run.  A WARM one (mode 1) launches ONE kernel where
+ *                            the setup kernel of a run stands (one setup and one launch in launch_counts, setup_ms in last_timing): the
+ *                            whole setup on the new values -- scales, regularisations, the ADMM KKT factor of every instance -- around the
+ *                            stored point: an instance whose last run returned 0 keeps its x, multipliers, working set and penalty (rho0 as
+ *                            above) but not its polish factor, which belongs to the old values; every other instance runs cold.
+ *                            lcqp_hip_sparse_update and _update_values may precede the resolve in either order; a load or set_options in
+ *                            between makes the resolve a run.
  *   lcqp_hip_sparse_launch_counts   out[0] full setups, out[1] homotopy launches this handle has issued.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct lcqp_hip_sparse lcqp_hip_sparse_t;
@@ -501,6 +516,7 @@ int  lcqp_hip_sparse_run(lcqp_hip_sparse_t* s);                          /* runS
 int  lcqp_hip_sparse_update(lcqp_hip_sparse_t* s, int first, int count, const double* g,
                             const double* lbA, const double* ubA, const double* lbL, const double* ubL,
                             const double* lbR, const double* ubR, const double* x0, const double* y0);
+int  lcqp_hip_sparse_update_values(lcqp_hip_sparse_t* s, int first, int count, const double* Qx, const double* Ax);
 int  lcqp_hip_sparse_resolve(lcqp_hip_sparse_t* s, int mode, const double* rho0);
 int  lcqp_hip_sparse_launch_counts(lcqp_hip_sparse_t* s, int out[2]);   /* full setups, homotopy launches */
 /* Solution sensitivities of the sparse batch (DESIGN.md section 3a''; the twin of lcqp_hip_batch_sensitivity in this arm's conventions: no
@@ -657,6 +673,11 @@ int  lcqp_hip_sparse_load_device(lcqp_hip_sparse_t* s, int first, int count, int
 int  lcqp_hip_sparse_update_device(lcqp_hip_sparse_t* s, int first, int count, const double* g,
                                    const double* lbA, const double* ubA, const double* lbL, const double* ubL,
                                    const double* lbR, const double* ubR, const double* x0, const double* y0, void* stream);
+/* lcqp_hip_sparse_update_values on device arrays, under the rules above: shared as in load_device, a NULL array stays; the checks of the
+ * host twin in its order, then shared & ~3 (LCQP_INVALID_ARGUMENT), then the pointers.  With Qx one small kernel forms the diagonal pairs
+ * of the new Hessians and the call waits for them (the one host synchronisation, as in load_device). */
+int  lcqp_hip_sparse_update_values_device(lcqp_hip_sparse_t* s, int first, int count, int shared,
+                                          const double* Qx, const double* Ax, void* stream);
 int  lcqp_hip_sparse_get_solution_device(lcqp_hip_sparse_t* s, double* x, double* y, lcqp_stats_t* stats, void* stream);
 int  lcqp_hip_sparse_sensitivity_device(lcqp_hip_sparse_t* s, int nrhs, const double* v,
                                         double* dg, double* db, int* side, int* info, void* stream);

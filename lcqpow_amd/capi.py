@@ -184,6 +184,8 @@ def lib():
         L.lcqp_hip_sparse_algorithmic_bytes.restype = C.c_double
         L.lcqp_hip_sparse_algorithmic_bytes.argtypes = [C.c_void_p]
         L.lcqp_hip_sparse_update.argtypes = [C.c_void_p, C.c_int, C.c_int] + [c_double_p] * 9
+        L.lcqp_hip_sparse_update_values.argtypes = [C.c_void_p, C.c_int, C.c_int] + [c_double_p] * 2
+        L.lcqp_hip_sparse_update_values_device.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 2 + [C.c_void_p]
         L.lcqp_hip_sparse_resolve.argtypes = [C.c_void_p, C.c_int, c_double_p]
         L.lcqp_hip_sparse_launch_counts.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
         L.lcqp_hip_sparse_sensitivity.argtypes = [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_int_p, c_int_p]
@@ -1285,6 +1287,18 @@ class SparseBatchLCQP(_Batch):
         a = self._host_args(self._vector_sizes(), max(count, 0), (g, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0))
         return lib().lcqp_hip_sparse_update(self.h, first, count, *[_p(v) for v in a])
 
+    def update_values(self, first, count, Qx=None, Ax=None):
+        """lcqp_hip_sparse_update_values: new values of the matrices for instances [first, first + count) on the pattern of the handle,
+        Qx [count][nnzQ] and Ax [count][nnzA] as load takes them, None: the array stays; the vectors, the stored point, the statuses and
+        the penalties stay.  The next resolve(warm=True) sets up again on the new values and starts every instance whose last run
+        succeeded from its last solution and working set, without its polish factor; resolve() and run() solve the new data cold.
+        Returns the ReturnValue code (0; 100 INVALID_ARGUMENT without any array, 300 for an instance that holds no problem); a wrongly
+        sized array raises ValueError."""
+        if first < 0 or count <= 0 or first + count > self.B:
+            raise ValueError(f"instances [{first}, {first + count}) outside the batch of {self.B}")
+        a = self._host_args((("Qx", self.nnzQ), ("Ax", self.nnzA)), count, (Qx, Ax))
+        return lib().lcqp_hip_sparse_update_values(self.h, first, count, *[_p(v) for v in a])
+
     # ---- the device-pointer entry points (DESIGN.md section 3a''''', "The sparse arm"): torch tensors on the handle's device in, torch tensors
     # out; the work is ordered behind torch.cuda.current_stream(), and what the caller enqueues there next sees the results.
     def load_device(self, first, count, Qx, g, Ax, lbA=None, ubA=None, lbL=None, ubL=None, lbR=None, ubR=None, x0=None, y0=None):
@@ -1303,6 +1317,16 @@ class SparseBatchLCQP(_Batch):
         self._range(first, count)
         v = self._device_vectors(count, (g, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0))
         return lib().lcqp_hip_sparse_update_device(self.h, first, count, *v, self._stream())
+
+    def update_values_device(self, first, count, Qx=None, Ax=None, shared=0):
+        """lcqp_hip_sparse_update_values_device: update_values() from float64 torch tensors on the handle's device.  As in load_device a
+        value tensor of shape [nnz] is ONE array for all `count` instances; shared (bits 1, 2 for Qx, Ax) may say so too, and must then
+        agree with the shapes.  Returns the ReturnValue code."""
+        self._range(first, count)
+        found, ptr = self._device_matrices(count, (("Qx", Qx, (self.nnzQ,)), ("Ax", Ax, (self.nnzA,))))
+        if count > 1 and shared & ~found:
+            raise ValueError(f"shared = {shared}: a value array marked as shared has the shape of one per instance")
+        return lib().lcqp_hip_sparse_update_values_device(self.h, first, count, found, ptr["Qx"], ptr["Ax"], self._stream())
 
     def sensitivity_device(self, v):
         """lcqp_hip_sparse_sensitivity_device: sensitivity(v) with v a float64 tensor on the handle's device, [B][nV] or [B][k][nV], read

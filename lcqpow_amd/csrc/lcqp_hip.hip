@@ -361,7 +361,7 @@ extern "C" int lcqp_hip_batch_update_matrices(lcqp_hip_batch_t* h, int first, in
     const DevBatch& d = h->db;
     const size_t n = d.n, nC = d.nC, nComp = d.nComp;
     HIPCHK(g_err, hipSetDevice(h->device));
-    matrices_changed(h);
+    h->rs.matrices_changed();
     const RawArray raw[] = {{Q, n * n}, {A, nC * n}, {L, nComp * n}, {R, nComp * n}};
     return upload_packed(g_err, h, count, raw, [&](int c0, int cb, const double* const* p) {
         return dense_pack_matrices(h, first + c0, cb, PackMatrices{{p[0], p[1], p[2], p[3]}, {n * n, nC * n, nComp * n, nComp * n}}, false);

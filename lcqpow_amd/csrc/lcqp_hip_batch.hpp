@@ -74,10 +74,9 @@ struct PackMatrices { const double* src[4]; size_t stride[4]; };      // Q, A, L
 // k_pack_matrices and k_pack_vectors (update: k_pack_vectors alone, m is not read) on h->stream; nothing waits.  The checks and the host
 // state are the caller's.
 int dense_pack(lcqp_hip_batch* h, int first, int count, const PackVectors& v, const PackMatrices& m, bool update);
-// lcqp_hip_batch_update_matrices and its device twin: the checks in front of every device call, the host state of a range that is about to
-// be written (ResolveState::pointKept), and k_pack_matrices alone (boxRows: with the zero fill of the box rows of E, as a load)
+// lcqp_hip_batch_update_matrices and its device twin: the checks in front of every device call (the host state of a range that is about to
+// be written is ResolveState::matrices_changed), and k_pack_matrices alone (boxRows: with the zero fill of the box rows of E, as a load)
 int check_update_matrices(lcqp_hip_batch* h, int first, int count, const double* Q, const double* L, const double* R, const double* A);
-void matrices_changed(lcqp_hip_batch* h);
 int dense_pack_matrices(lcqp_hip_batch* h, int first, int count, const PackMatrices& m, bool boxRows);
 
 // the message of lcqp_hip_batch_update and its device twin for a variable whose box bound appears or disappears

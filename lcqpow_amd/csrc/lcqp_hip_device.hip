@@ -221,15 +221,6 @@ int check_update_matrices(lcqp_hip_batch* h, int first, int count, const double*
     return 0;
 }
 
-// ... and their host state once the range is about to be written: no setup and no solve belong to the matrices in place any more, but
-// what the last solve stored on the device -- the point, the statuses, the penalties -- is still there (ResolveState::pointKept)
-void matrices_changed(lcqp_hip_batch* h)
-{
-    const bool kept = h->rs.solved || h->rs.pointKept;
-    h->rs.invalidate();
-    h->rs.pointKept = kept;
-}
-
 // the status words (and, for a load, the box flags behind them) of k_check_vectors: [2] words, then [B][n] bytes
 static int check_buffer(lcqp_hip_batch* h)
 {
@@ -361,7 +352,7 @@ extern "C" int lcqp_hip_batch_update_matrices_device(lcqp_hip_batch_t* h, int fi
         if (!device_pointer_ok(g_err, h, names[k], mats[k], sizeof(double) * (one ? 1 : (size_t)count) * rows[k] * d.n)) return LCQP_INVALID_ARGUMENT;
     }
     return device_call(g_err, h, stream, [&] {
-        matrices_changed(h);
+        h->rs.matrices_changed();
         return dense_pack_matrices(h, first, count, pm, false);
     });
 }); }

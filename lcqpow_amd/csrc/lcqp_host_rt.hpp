@@ -188,8 +188,8 @@ struct ResolveState {
     // the stored point, working set and factors belong to a solve on the data in place (set by run / resolve, cleared with setupValid):
     // what *_sensitivity differentiates
     bool solved = false;
-    // the matrices changed since the last solve (dense arm: *_update_matrices), but its point, statuses and penalties are still on the
-    // device: a warm *_resolve sets up again around them.  Cleared with setupValid by everything else that clears it
+    // the matrices changed since the last solve (*_update_matrices, sparse arm: *_update_values), but its point, statuses and penalties
+    // are still on the device: a warm *_resolve sets up again around them.  Cleared with setupValid by everything else that clears it
     bool pointKept = false;
     std::vector<char> filled;            // [B]: the instance holds a problem
     double* rhoStart = nullptr;           // [B] on the device: starting penalties of a warm re-solve
@@ -198,6 +198,14 @@ struct ResolveState {
     // ran on: a vector call is one launch, a Jacobian one per chunk); < 0 before the first
     float sensMs = -1.f;
     void invalidate() { setupValid = solved = pointKept = false; }
+    // the host state of *_update_matrices / *_update_values once the range is about to be written: no setup and no solve belong to the
+    // matrices in place any more, but what the last solve stored on the device is still there
+    void matrices_changed()
+    {
+        const bool kept = solved || pointKept;
+        invalidate();
+        pointKept = kept;
+    }
 };
 
 // the value check of a host load / update over its whole range ([count * nComp] each, null: absent): a lower complementarity bound of

@@ -41,24 +41,19 @@ namespace {
 
 constexpr int SCHED_WAVES_PER_SIMD = 2;   // register budget of k_sparse_sched at G <= 8: 512 / SCHED_WAVES_PER_SIMD per lane
 
-// ---- setup: scales, rho vector, phi expressions, the ONE factorisation of the ADMM KKT matrix ----------------------------------
+// ---- the pieces of the three setup kernels (k_sparse_setup, k_sparse_refresh, k_sparse_setup_warm) -------------------------------------
+// The matrix half: everything a setup derives from the values of Q and E alone -- scale from the diagonal of Q, e1max, sigma and the four
+// regularisations, and at G <= 16 the assembled band rows K0 through the bsrc / bdiag of the ordering in place.  Returns scale.
 template <int G>
-__global__ __launch_bounds__(WGS) void k_sparse_setup(SpBatch db)
+__device__ __forceinline__ double sp_setup_matrices(SpCtx<G>& c)
 {
-    const int b = blockIdx.x * (64 / G) + threadIdx.x / G;
-    if (b >= db.B) return;
-    SpCtx<G> c = sp_ctx<G>(db, b, blockIdx.x * (64 / G), (int)threadIdx.x);
+    const SpBatch& db = *c.db;
     const int t = c.gl, n = db.n, m = db.m;
-#ifdef LCQP_PROFILE
-    if (t == 0) for (int k = 0; k < SP_NPHASE; k++) c.info->prof[k] = 0.0;
-#endif
     double dmax = 0.0;
     for (int i = t; i < n; i += G)
         for (int k = db.Qp[i]; k < db.Qp[i + 1]; k++) if (db.Qi[k] == i) dmax = fmax(dmax, fabs(c.Qx()[k]));
     double scale = g_max<G>(dmax);
     if (!(scale > 1e-300)) scale = 1.0;
-    int unused;
-    const double phiConst = sp_prepare_vectors<G, false>(c, scale, unused);
     double e1 = 0.0;
     {
         GD Ev = c.Ex();
@@ -68,11 +63,8 @@ __global__ __launch_bounds__(WGS) void k_sparse_setup(SpBatch db)
     if (t == 0) {
         c.info->e1max = e1;
         c.info->scale = scale; c.info->sigma = db.opt.admmSigma * scale; c.info->delta = db.opt.proxBig * scale; c.info->delta2 = 1e-9 / scale;
-        c.info->phiConst = phiConst; c.info->haveSolution = 0; c.info->stfValid = 0; c.info->bytes = 0.0;
-        c.info->deltaS = db.opt.proxSmall * scale; c.info->delta2S = 1e-14 / scale; c.info->bigReg = 0;
-        c.info->warm = 0;
+        c.info->deltaS = db.opt.proxSmall * scale; c.info->delta2S = 1e-14 / scale;
     }
-    g_sync();
     if constexpr (G <= 16) {
         // the assembled band rows every factorisation of this instance streams (sp_factor_reg): the one gather from the values of Q and E
         GD K0 = c.K0(), Qv = c.Qx(), Ev = c.Ex();
@@ -87,8 +79,90 @@ __global__ __launch_bounds__(WGS) void k_sparse_setup(SpBatch db)
             const int bd = db.bdiag[r];
             K0[r * G] = (bd >= 0) ? (double)Qv[bd] : 0.0;
         }
-        g_sync();
     }
+    return scale;
+}
+
+// what an instance that starts cold reports when its first QP fails: sp_finish hands out MV_YK, which the first QP end writes -- zeros, as
+// on a fresh handle, not the duals of the run before
+template <int G>
+__device__ __forceinline__ void sp_cold_duals(SpCtx<G>& c)
+{
+    GD yk = c.M(MV_YK);
+    for (int r = c.gl; r < c.db->m; r += G) yk[r] = 0.0;
+}
+
+// the SpInfo fields of a fresh setup that do not come from the values: no solution, no polish factor, no verdict on the pivots, a cold start
+template <int G>
+__device__ __forceinline__ void sp_setup_marks(SpCtx<G>& c, double phiConst)
+{
+    sp_cold_duals<G>(c);
+    if (c.gl != 0) return;
+    c.info->phiConst = phiConst; c.info->haveSolution = 0; c.info->stfValid = 0; c.info->bytes = 0.0;
+    c.info->bigReg = 0; c.info->warm = 0;
+}
+
+// mode 1 and a last run that returned 0: the instance starts warm (read before anything of the hand-over is written)
+template <int G>
+__device__ __forceinline__ int sp_warm_condition(const SpCtx<G>& c, int mode)
+{
+    return mode == 1 && c.info->haveSolution != 0 && c.db->stats[c.b].returnValue == 0;
+}
+// ... at rho0[b], else at its last rhoOpt, else at the option; a cold instance at the option
+template <int G>
+__device__ __forceinline__ double sp_warm_penalty(const SpCtx<G>& c, int warm, const double* rho0)
+{
+    const SpBatch& db = *c.db;
+    if (!warm) return db.opt.initialPenaltyParameter;
+    const double last = db.stats[c.b].rhoOpt;
+    return rho0 ? rho0[c.b] : (last > 0.0 ? last : db.opt.initialPenaltyParameter);
+}
+
+// The hand-over between two runs.  A warm instance: the stored statuses in line with the new bounds -- equal bounds make an equality; an
+// equality whose bounds differ, or a row held at a side that is infinite now, leaves with a zero multiplier (the trial's comparison of the
+// factor's set with the working set then asks for a factorisation) --, SpInfo::warm and the starting penalty.  KEEP_FACTOR: the polish
+// factor in memory and the verdict on its pivots (bigReg) belong to the matrices in place and stay; without it both go, as in a cold
+// instance, and the first trial asks for a factorisation (sp_ph_trial: stfValid == 0).  A cold instance gets the marks of a setup.
+template <int G, bool KEEP_FACTOR>
+__device__ __forceinline__ void sp_warm_handover(SpCtx<G>& c, int warm, double rhoStart, double phiConst)
+{
+    const int t = c.gl, m = c.db->m;
+    if (warm) {
+        GD l = c.M(MV_L), u = c.M(MV_U), yq = c.M(MV_YQ);
+        GI st = c.I(MI_ST);
+        for (int r = t; r < m; r += G) {
+            const double lo = l[r], hi = u[r];
+            int s = st[r];
+            if (lo == hi) s = ST_EQ;
+            else if (s == ST_EQ || (s == ST_LOWER && isinf(lo)) || (s == ST_UPPER && isinf(hi))) s = ST_INACT;
+            if (s == ST_INACT) yq[r] = 0.0;
+            st[r] = s;
+        }
+    } else sp_cold_duals<G>(c);
+    if (t == 0) {
+        c.info->phiConst = phiConst; c.info->bytes = 0.0;
+        c.info->warm = warm; c.info->rho0 = rhoStart;
+        if (!warm) c.info->haveSolution = 0;
+        if (!warm || !KEEP_FACTOR) { c.info->stfValid = 0; c.info->bigReg = 0; }
+    }
+}
+
+// ---- setup: scales, rho vector, phi expressions, the ONE factorisation of the ADMM KKT matrix ----------------------------------
+template <int G>
+__global__ __launch_bounds__(WGS) void k_sparse_setup(SpBatch db)
+{
+    const int b = blockIdx.x * (64 / G) + threadIdx.x / G;
+    if (b >= db.B) return;
+    SpCtx<G> c = sp_ctx<G>(db, b, blockIdx.x * (64 / G), (int)threadIdx.x);
+    const int t = c.gl;
+#ifdef LCQP_PROFILE
+    if (t == 0) for (int k = 0; k < SP_NPHASE; k++) c.info->prof[k] = 0.0;
+#endif
+    const double scale = sp_setup_matrices<G>(c);
+    int unused;
+    const double phiConst = sp_prepare_vectors<G, false>(c, scale, unused);
+    sp_setup_marks<G>(c, phiConst);
+    g_sync();
     sp_admm_factor<G>(c, scale);
     if (t == 0) c.info->bytes = c.bytes;
 }
@@ -101,45 +175,54 @@ __global__ __launch_bounds__(WGS) void k_sparse_setup(SpBatch db)
 // per group -- collectives inside the group, the group's own piece of LDS, no workgroup barrier -- as k_sparse_sched relies on when a
 // step holds fewer instances than the wavefront has groups.)
 // mode 0: every instance starts cold, as the setup leaves it.  mode 1: an instance whose last run returned 0 starts warm (SpInfo::warm):
-// at its last x and at rho0[b] (else its last rhoOpt), its first QP a hot start on the stored point, working set and polish factor.  The
-// stored statuses are brought in line with the new bounds: equal bounds make an equality; an equality whose bounds differ, or a row held
-// at a side that is infinite now, leaves with a zero multiplier (the trial's comparison of the factor's set with the working set then
-// asks for a factorisation).
+// at its last x and at rho0[b] (else its last rhoOpt), its first QP a hot start on the stored point, working set and polish factor
+// (sp_warm_handover).
 template <int G>
 __global__ __launch_bounds__(WGS) void k_sparse_refresh(SpBatch db, int mode, const double* rho0)
 {
     const int b = blockIdx.x * (64 / G) + threadIdx.x / G;
     if (b >= db.B) return;
     SpCtx<G> c = sp_ctx<G>(db, b, blockIdx.x * (64 / G), (int)threadIdx.x);
-    const int t = c.gl, m = db.m;
+    const int t = c.gl;
     const double scale = c.info->scale;
-    const int warm = mode == 1 && c.info->haveSolution != 0 && db.stats[b].returnValue == 0;
-    double rhoStart = db.opt.initialPenaltyParameter;
-    if (warm) {
-        const double last = db.stats[b].rhoOpt;
-        rhoStart = rho0 ? rho0[b] : (last > 0.0 ? last : db.opt.initialPenaltyParameter);
-    }
+    const int warm = sp_warm_condition<G>(c, mode);
+    const double rhoStart = sp_warm_penalty<G>(c, warm, rho0);
     int changed;
     const double phiConst = sp_prepare_vectors<G, true>(c, scale, changed);
-    if (warm) {
-        GD l = c.M(MV_L), u = c.M(MV_U), yq = c.M(MV_YQ);
-        GI st = c.I(MI_ST);
-        for (int r = t; r < m; r += G) {
-            const double lo = l[r], hi = u[r];
-            int s = st[r];
-            if (lo == hi) s = ST_EQ;
-            else if (s == ST_EQ || (s == ST_LOWER && isinf(lo)) || (s == ST_UPPER && isinf(hi))) s = ST_INACT;
-            if (s == ST_INACT) yq[r] = 0.0;
-            st[r] = s;
-        }
-    }
-    if (t == 0) {
-        c.info->phiConst = phiConst; c.info->bytes = 0.0;
-        c.info->warm = warm; c.info->rho0 = rhoStart;
-        if (!warm) { c.info->haveSolution = 0; c.info->stfValid = 0; c.info->bigReg = 0; }
-    }
+    sp_warm_handover<G, true>(c, warm, rhoStart, phiConst);
     g_sync();
     if (g_any<G>(changed)) sp_admm_factor<G>(c, scale);
+    if (t == 0) c.info->bytes = c.bytes;
+}
+
+// ---- setup around a kept point: new VALUES of Q and E under the point of the last run (lcqp_hip_sparse_update_values, then a warm
+// lcqp_hip_sparse_resolve) ----------------------------------------------------------------------------------------------------------------
+// Stands where k_sparse_setup stands in a run, and is that kernel's matrix half -- scale, e1max, sigma, the regularisations, K0 in the
+// ordering the host has just chosen, the vector half, the ADMM factor of EVERY instance: the one in memory holds the old Q, E and sigma --
+// followed by the warm hand-over of k_sparse_refresh.  Nothing stored in permuted order outlives it unread: both factors, the border
+// arrays and K0 are rebuilt before their first use, and NV_XK, NV_XQ, MV_YQ, MI_ST are in natural order, so the host may have changed the
+// ordering in between.  The polish factor belongs to the old matrices: a warm instance keeps its point, statuses, multipliers and penalty
+// but neither stfValid nor bigReg (sp_warm_handover<G, false>), and its first trial asks for a factorisation.  An instance that is not
+// warm (no solve, or a last return value other than 0) gets exactly the marks of k_sparse_setup.  Lane groups of a wavefront part on
+// `warm` as in k_sparse_refresh.
+template <int G>
+__global__ __launch_bounds__(WGS) void k_sparse_setup_warm(SpBatch db, const double* rho0)
+{
+    const int b = blockIdx.x * (64 / G) + threadIdx.x / G;
+    if (b >= db.B) return;
+    SpCtx<G> c = sp_ctx<G>(db, b, blockIdx.x * (64 / G), (int)threadIdx.x);
+    const int t = c.gl;
+#ifdef LCQP_PROFILE
+    if (t == 0) for (int k = 0; k < SP_NPHASE; k++) c.info->prof[k] = 0.0;
+#endif
+    const int warm = sp_warm_condition<G>(c, 1);
+    const double rhoStart = sp_warm_penalty<G>(c, warm, rho0);
+    const double scale = sp_setup_matrices<G>(c);
+    int unused;
+    const double phiConst = sp_prepare_vectors<G, false>(c, scale, unused);
+    sp_warm_handover<G, false>(c, warm, rhoStart, phiConst);
+    g_sync();
+    sp_admm_factor<G>(c, scale);
     if (t == 0) c.info->bytes = c.bytes;
 }
 
@@ -870,15 +953,18 @@ __global__ void k_sparse_sched_init(SpBatch db)
     }
 }
 
-// refresh: k_sparse_refresh<G>(mode, rho0) stands where k_sparse_setup<G> stands (lcqp_hip_sparse_resolve)
+// first: the kernel in front of the homotopy -- k_sparse_setup<G>, k_sparse_refresh<G>(mode, rho0) or k_sparse_setup_warm<G>(rho0) (lcqp_hip_sparse_resolve)
 template <int G>
-static void sp_launch(const SpBatch& db, int cus, hipStream_t stream, hipEvent_t mid, bool refresh, int mode, const double* rho0)
+static void sp_launch(const SpBatch& db, int cus, hipStream_t stream, hipEvent_t mid, SpFirst first, int mode, const double* rho0)
 {
     const int ipw = 64 / G, grid = (db.B + ipw - 1) / ipw;
     // LDS: the working sets' bit sets of sp_ph_factor (G <= 16), the window of sp_factor_lds (per group G x G and 16 staged rows) otherwise
     const size_t ldsBytes = G <= 16 ? sizeof(unsigned) * (size_t)ipw * db.bitWords : sizeof(double) * (size_t)ipw * group_lds_doubles(G);
-    if (refresh) hipLaunchKernelGGL(k_sparse_refresh<G>, dim3(grid), dim3(WGS), ldsBytes, stream, db, mode, rho0);
-    else hipLaunchKernelGGL(k_sparse_setup<G>, dim3(grid), dim3(WGS), ldsBytes, stream, db);
+    switch (first) {
+    case SpFirst::REFRESH: hipLaunchKernelGGL(k_sparse_refresh<G>, dim3(grid), dim3(WGS), ldsBytes, stream, db, mode, rho0); break;
+    case SpFirst::SETUP_WARM: hipLaunchKernelGGL(k_sparse_setup_warm<G>, dim3(grid), dim3(WGS), ldsBytes, stream, db, rho0); break;
+    case SpFirst::SETUP: hipLaunchKernelGGL(k_sparse_setup<G>, dim3(grid), dim3(WGS), ldsBytes, stream, db); break;
+    }
     (void)hipEventRecord(mid, stream);
     const int ninit = std::max(db.nPools * db.poolSize, db.nPools * (PH_NUM + 1) * QCTL);
     hipLaunchKernelGGL(k_sparse_sched_init, dim3((ninit + 255) / 256), dim3(256), 0, stream, db);

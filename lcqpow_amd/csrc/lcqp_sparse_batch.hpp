@@ -64,6 +64,10 @@ struct SpPackValues { const double *Qx, *Ax; size_t qStride, aStride; };
 // k_sparse_pack_values (Ax needs sp_value_map first) and k_sparse_pack_vectors (update: k_sparse_pack_vectors alone, m is not read) on
 // h->stream; nothing waits.  The checks and the host state are the caller's.
 int sparse_pack(lcqp_hip_sparse* h, int first, int count, const SpPackVectors& v, const SpPackValues& m, bool update);
+// lcqp_hip_sparse_update_values and its device twin: the checks in front of every device call (lcqp_sparse_host.hip; the host state of a
+// range that is about to be written is ResolveState::matrices_changed), and k_sparse_pack_values alone
+int check_update_values(lcqp_hip_sparse* h, int first, int count, const double* Qx, const double* Ax);
+int sparse_pack_values(lcqp_hip_sparse* h, int first, int count, const SpPackValues& m);
 
 // ---- from the staging of the panel kernels (lcqp_sparse_launch.hpp: SpSensBlkArgs) to the caller's arrays.  The one definition of where a
 // staged column goes: the host loop of sp_panel_run (lcqp_sparse_diff.hip) and k_sparse_scatter_panels (lcqp_sparse_device.hip) both call it.

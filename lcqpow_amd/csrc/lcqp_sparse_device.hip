@@ -180,16 +180,22 @@ int sparse_scatter_panels(lcqp_hip_sparse* h, const SpScatterArgs& a)
     return 0;
 }
 
+int sparse_pack_values(lcqp_hip_sparse* h, int first, int count, const SpPackValues& m)
+{
+    const SpBatch& d = h->db;
+    if (!m.Qx && !m.Ax) return 0;
+    const int most = std::max(m.Qx ? d.nnzQ : 0, m.Ax ? d.nnzE : 0);
+    const unsigned gx = (unsigned)std::min<size_t>(((size_t)most + 4 * SP_DEV_WG - 1) / (4 * SP_DEV_WG), 4096);      // four entries per thread
+    hipLaunchKernelGGL(k_sparse_pack_values, dim3(std::max(gx, 1u), std::min(count, 65535), 2), dim3(SP_DEV_WG), 0, h->stream, d, first, count, m,
+                       (const int*)h->valMap);
+    HIPCHK(g_sp_err, hipGetLastError());
+    return 0;
+}
+
 int sparse_pack(lcqp_hip_sparse* h, int first, int count, const SpPackVectors& v, const SpPackValues& m, bool update)
 {
     const SpBatch& d = h->db;
-    if (!update && (m.Qx || m.Ax)) {
-        const int most = std::max(m.Qx ? d.nnzQ : 0, m.Ax ? d.nnzE : 0);
-        const unsigned gx = (unsigned)std::min<size_t>(((size_t)most + 4 * SP_DEV_WG - 1) / (4 * SP_DEV_WG), 4096);      // four entries per thread
-        hipLaunchKernelGGL(k_sparse_pack_values, dim3(std::max(gx, 1u), std::min(count, 65535), 2), dim3(SP_DEV_WG), 0, h->stream, d, first, count, m,
-                           (const int*)h->valMap);
-        HIPCHK(g_sp_err, hipGetLastError());
-    }
+    if (!update) if (int rc = sparse_pack_values(h, first, count, m)) return rc;
     hipLaunchKernelGGL(k_sparse_pack_vectors, dim3(count), dim3(SP_DEV_WG), 0, h->stream, d, first, v, update ? 1 : 0);
     HIPCHK(g_sp_err, hipGetLastError());
     return 0;
@@ -287,6 +293,38 @@ extern "C" int lcqp_hip_sparse_update_device(lcqp_hip_sparse_t* h, int first, in
         if (chk[0] != ~0ull) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
         d.hasLbL |= lbL ? 1 : 0; d.hasLbR |= lbR ? 1 : 0;
         return sparse_pack(h, first, count, pv, SpPackValues{}, true);
+    });
+}); }
+
+// New values of the matrices for instances [first, first + count) from device arrays of the caller: lcqp_hip_sparse_update_values behind
+// the hand-over of the streams.  shared: the bits of lcqp_hip_sparse_load_device -- 1: one Qx for the range, 2: one Ax.  With Qx the
+// diagonal pairs come from k_sparse_check_vectors over an empty set of vectors (its lbL / lbR half reads the zero default): the one host
+// synchronisation of the call.
+extern "C" int lcqp_hip_sparse_update_values_device(lcqp_hip_sparse_t* h, int first, int count, int shared, const double* Qx, const double* Ax,
+                                                    void* stream)
+{ return guarded(g_sp_err, [&] {
+    if (int rc = check_update_values(h, first, count, Qx, Ax)) return rc;
+    if (shared & ~3) return LCQP_INVALID_ARGUMENT;
+    const SpBatch& d = h->db;
+    HIPCHK(g_sp_err, hipSetDevice(h->device));
+    const bool oneQ = shared & 1, oneA = shared & 2;
+    const SpPackValues pm = {Qx, Ax, oneQ ? 0 : (size_t)d.nnzQ, oneA ? 0 : (size_t)d.nnzE};
+    if (!device_pointer_ok(g_sp_err, h, "Qx", Qx, sizeof(double) * (oneQ ? 1 : (size_t)count) * d.nnzQ) ||
+        !device_pointer_ok(g_sp_err, h, "Ax", Ax, sizeof(double) * (oneA ? 1 : (size_t)count) * d.nnzE)) return LCQP_INVALID_ARGUMENT;
+    if (Ax) if (int rc = sp_value_map(h)) return rc;
+    return device_call(g_sp_err, h, stream, [&] {
+        std::vector<unsigned long long> chk;
+        if (Qx) if (int rc = sp_check_vectors(h, count, SpPackVectors{}, Qx, pm.qStride, oneQ ? 1 : count, chk)) return rc;
+        h->rs.matrices_changed();
+        if (Qx)
+            for (int k = 0; k < count; k++) {
+                double pair[2];
+                memcpy(pair, chk.data() + 2 + 2 * (size_t)(oneQ ? 0 : k), sizeof(pair));
+                const double dmin = pair[0], dmax = pair[1];
+                h->diagRatio[(size_t)first + k] = (dmax > 0.0 && dmin > 0.0) ? dmin / dmax : 0.0;
+            }
+        sp_choose_ordering(h);
+        return sparse_pack_values(h, first, count, pm);
     });
 }); }
 

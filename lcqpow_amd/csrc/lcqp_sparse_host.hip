@@ -250,13 +250,14 @@ extern "C" int lcqp_hip_sparse_sched_profile(lcqp_hip_sparse_t* h, unsigned long
     return 0;
 }); }
 
-// the launches of a run or a re-solve on the handle's stream: the setup (or the refresh) from ev0 to ev1, the homotopy from ev1 to ev2
-static int sp_run(lcqp_hip_sparse* h, bool refresh, int mode, const double* rho0)
+// the launches of a run or a re-solve on the handle's stream: the setup (or the refresh, or the setup around the kept point) from ev0 to
+// ev1, the homotopy from ev1 to ev2
+static int sp_run(lcqp_hip_sparse* h, SpFirst first, int mode, const double* rho0)
 {
     h->rs.invalidate();
     HIPCHK(g_sp_err, hipEventRecord(h->ev0, h->stream));
-    sp_kernels(h->db.G)->run(h->db, h->cus, h->stream, h->ev1, refresh, mode, rho0);
-    if (!refresh) h->rs.nSetups++;
+    sp_kernels(h->db.G)->run(h->db, h->cus, h->stream, h->ev1, first, mode, rho0);
+    if (first != SpFirst::REFRESH) h->rs.nSetups++;
     h->rs.nLaunches++;
     HIPCHK(g_sp_err, hipGetLastError());
     HIPCHK(g_sp_err, hipEventRecord(h->ev2, h->stream));
@@ -269,7 +270,7 @@ extern "C" int lcqp_hip_sparse_run(lcqp_hip_sparse_t* h)
     if (!h || !h->loaded) return LCQP_LCQPOBJECT_NOT_SETUP;
     HIPCHK(g_sp_err, hipSetDevice(h->device));
     sp_choose_ordering(h);
-    return sp_run(h, false, 0, nullptr);
+    return sp_run(h, SpFirst::SETUP, 0, nullptr);
 }); }
 
 // New vectors for instances [first, first + count) of a batch that holds problems: the argument list of lcqp_hip_sparse_load without the
@@ -287,11 +288,52 @@ extern "C" int lcqp_hip_sparse_update(lcqp_hip_sparse_t* h, int first, int count
     return sparse_upload(h, first, count, SpPackVectors{g, lbA, ubA, lbL, ubL, lbR, ubR, x0, y0}, nullptr, nullptr, true);
 }); }
 
+// the range and value checks of lcqp_hip_sparse_update_values and its device twin up to the first device call, in the order of the dense
+// check_update_matrices.  Nothing is written when one of them fails.
+int check_update_values(lcqp_hip_sparse* h, int first, int count, const double* Qx, const double* Ax)
+{
+    if (!Qx && !Ax) return LCQP_INVALID_ARGUMENT;
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (first < 0 || count <= 0 || first > h->db.B - count) return LCQP_INVALID_ARGUMENT;
+    for (int k = 0; k < count; k++) if (!h->rs.filled[(size_t)first + k]) return LCQP_LCQPOBJECT_NOT_SETUP;
+    return 0;
+}
+
+// New values of the matrices for instances [first, first + count) of a batch that holds problems, on the pattern of the handle: Qx, Ax as
+// lcqp_hip_sparse_load takes them, NULL: the array stays.  Only their segments of the value pools are written (k_sparse_pack_values behind
+// the chunked upload): no vector, no SpInfo, no status, multiplier, point, statistic or factor.  The whole call is checked before anything
+// is written.  New Hessians may move the batch across the definiteness line of sp_choose_ordering in either direction.
+extern "C" int lcqp_hip_sparse_update_values(lcqp_hip_sparse_t* h, int first, int count, const double* Qx, const double* Ax)
+{ return guarded(g_sp_err, [&] {
+    if (int rc = check_update_values(h, first, count, Qx, Ax)) return rc;
+    const SpBatch& d = h->db;
+    const size_t nnzQ = d.nnzQ, nnzE = d.nnzE;
+    HIPCHK(g_sp_err, hipSetDevice(h->device));
+    if (Ax) if (int rc = sp_value_map(h)) return rc;
+    h->rs.matrices_changed();
+    if (Qx)
+        for (int k = 0; k < count; k++) {
+            double dmin = INFINITY, dmax = 0.0;
+            for (int i = 0; i < d.n; i++) { const double q = h->qdiagHost[i] >= 0 ? Qx[(size_t)k * nnzQ + h->qdiagHost[i]] : 0.0; dmin = std::min(dmin, q); dmax = std::max(dmax, std::fabs(q)); }
+            h->diagRatio[(size_t)first + k] = (dmax > 0.0 && dmin > 0.0) ? dmin / dmax : 0.0;
+        }
+    sp_choose_ordering(h);
+    // (no drain of the stream: the copies and the pack kernel are behind a run in flight on it)
+    const RawArray raw[] = {{Qx, nnzQ}, {Ax, nnzE}};
+    return upload_packed(g_sp_err, h, count, raw, [&](int c0, int cb, const double* const* p) {
+        return sparse_pack_values(h, first + c0, cb, SpPackValues{p[0], p[1], nnzQ, nnzE});
+    });
+}); }
+
 // Solve again on the setup in place: k_sparse_refresh where a run has k_sparse_setup, then the homotopy launch.  Without a setup that
-// belongs to the matrices and options in place this is lcqp_hip_sparse_run.
+// belongs to the matrices and options in place this is lcqp_hip_sparse_run -- unless the call is warm and only the values of the matrices
+// changed since the last solve (lcqp_hip_sparse_update_values): then k_sparse_setup_warm stands there, in the ordering the Hessians in
+// place select, and keeps the stored point.
 extern "C" int lcqp_hip_sparse_resolve(lcqp_hip_sparse_t* h, int mode, const double* rho0)
 { return guarded(g_sp_err, [&] {
-    if (int rc = check_resolve(g_sp_err, h, mode, rho0, h && h->loaded)) return rc == RESOLVE_RUNS ? lcqp_hip_sparse_run(h) : rc;
+    const int chk = check_resolve(g_sp_err, h, mode, rho0, h && h->loaded);
+    const bool newValues = chk == RESOLVE_RUNS && mode == 1 && h->rs.pointKept;
+    if (chk && !newValues) return chk == RESOLVE_RUNS ? lcqp_hip_sparse_run(h) : chk;
     const int B = h->db.B;
     HIPCHK(g_sp_err, hipSetDevice(h->device));
     const bool withRho = mode == 1 && rho0;
@@ -300,7 +342,8 @@ extern "C" int lcqp_hip_sparse_resolve(lcqp_hip_sparse_t* h, int mode, const dou
         HIPCHK(g_sp_err, hipStreamSynchronize(h->stream));      // the zero-fill of a fresh buffer, a run in flight that reads an older one
         HIPCHK(g_sp_err, hipMemcpy(h->rs.rhoStart, rho0, sizeof(double) * (size_t)B, hipMemcpyHostToDevice));
     }
-    return sp_run(h, true, mode, withRho ? h->rs.rhoStart : nullptr);
+    if (newValues) sp_choose_ordering(h);
+    return sp_run(h, newValues ? SpFirst::SETUP_WARM : SpFirst::REFRESH, mode, withRho ? h->rs.rhoStart : nullptr);
 }); }
 
 extern "C" int lcqp_hip_sparse_launch_counts(lcqp_hip_sparse_t* h, int out[2])

@@ -18,7 +18,7 @@ enum { MI_ST, MI_STT, MI_STF, MI_NEW, MI_NUM };
 
 struct SpInfo {
     int haveSolution, stfValid, hasY0, bigReg;     // bigReg: this instance needs the safe regularisation of the polish (a Hessian that is only semidefinite)
-    int warm, pad0;                                // warm (k_sparse_refresh): sp_ph_start begins at the last solution, at the penalty rho0, without the zero-penalty QP
+    int warm, pad0;                                // warm (k_sparse_refresh, k_sparse_setup_warm): sp_ph_start begins at the last solution, at the penalty rho0, without the zero-penalty QP
     double rho0;
     double scale, sigma, delta, delta2, phiConst;
     double deltaS, delta2S;                        // the light level tried first (sp_polish)
@@ -123,12 +123,15 @@ struct SpBatch {
 constexpr int GEN_META = 12;      // ints per front of SpBatch::gMeta
 
 // Per lane-group width one table of launch functions, as lcqp_launch.hpp has one per padded size.
-// SpRunFn: the launches of a run on `stream` -- k_sparse_setup<G>, or with `refresh` k_sparse_refresh<G>(mode, rho0) in its place, `mid`
-// recorded behind it, then the homotopy (k_sparse_sched_init, k_sparse_sched<G>).  cus: compute units of the device the batch lives on
-// (the persistent wavefronts of k_sparse_sched are at most what it holds at once).
+// SpFirst: the kernel in front of the homotopy -- SETUP: k_sparse_setup<G> (a run); REFRESH: k_sparse_refresh<G>(mode, rho0), new vectors on
+// the setup in place; SETUP_WARM: k_sparse_setup_warm<G>(rho0), new values of the matrices under the point of the last run.
+// SpRunFn: the launches of a run on `stream` -- the kernel `first` names, `mid` recorded behind it, then the homotopy (k_sparse_sched_init,
+// k_sparse_sched<G>).  cus: compute units of the device the batch lives on (the persistent wavefronts of k_sparse_sched are at most what
+// it holds at once).
 // SpSensitivityFn: one launch of k_sparse_sensitivity<G, false> on `stream` over device buffers (layouts at the kernel).
 // SpSensitivityDualFn: k_sparse_sensitivity<G, true>, which adds the upstream gradients on the duals vy [B][nrhs][m] (lcqp_hip_sparse_adjoint).
-using SpRunFn = void(const SpBatch& db, int cus, hipStream_t stream, hipEvent_t mid, bool refresh, int mode, const double* rho0);
+enum class SpFirst { SETUP, REFRESH, SETUP_WARM };
+using SpRunFn = void(const SpBatch& db, int cus, hipStream_t stream, hipEvent_t mid, SpFirst first, int mode, const double* rho0);
 using SpSensitivityFn = void(const SpBatch& db, hipStream_t stream, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo);
 using SpSensitivityDualFn = void(const SpBatch& db, hipStream_t stream, int nrhs, const double* v, const double* vy, double* dg, double* dbo, int* side, int* sinfo);
 // SpKktProbeFn: one launch of k_sparse_kkt_probe<G> on `stream` over device buffers (layouts and modes at the kernel).

@@ -82,9 +82,8 @@ class _HostPath:
     def update_matrices(layer, given, ref):
         """the given matrices alone, broadcast over the batch; the copies the layer holds are kept in step"""
         full = {k: np.ascontiguousarray(np.broadcast_to(_host(t), (layer.bt.B,) + layer._trailing(k))) for k, t in given.items()}
-        if layer._held is not None:
-            layer._held.update(full)
-        return layer.bt.update_matrices(0, layer.bt.B, **full)
+        layer._keep_sent(full)
+        return layer._update_matrices("", full)
 
 
 class _DevicePath:
@@ -116,7 +115,7 @@ class _DevicePath:
     def update_matrices(layer, given, ref):
         """the given matrices alone, from where they lie; a shared one is broadcast by the pack kernel"""
         layer._mark_stale()
-        return layer.bt.update_matrices_device(0, layer.bt.B, **{k: _dev(t, ref.device) for k, t in given.items()})
+        return layer._update_matrices("_device", {k: _dev(t, ref.device) for k, t in given.items()})
 
 
 def _solve(ctx, layer, g, lbA, ubA, replaced):
@@ -139,7 +138,7 @@ def _solve(ctx, layer, g, lbA, ubA, replaced):
     if lbA is not None: kw["lbA"] = path.conv(lbA, g)
     if ubA is not None: kw["ubA"] = path.conv(ubA, g)
     if shared and layer.solves > 0 and layer.warm_matrices:
-        # the dense batch holds a solved point: only the given matrices are sent, and the solve starts from that point (update_matrices)
+        # the batch holds a solved point: only the given matrices are sent, and the solve starts from that point (update_matrices / update_values)
         given = {k: t for k, t in replaced.items() if t is not None}
         rc = path.update_matrices(layer, given, g)
         if rc == 0:
@@ -301,7 +300,7 @@ class BatchLCQPLayer:
 
     def __init__(self, batch, bounds=None, warm=True, warm_matrices=False):
         capi.lib()      # raises when the HIP library is not built: no CPU fallback
-        self.warm_matrices = bool(warm_matrices) and not self.sparse      # solve() with matrices: update_matrices + resolve(warm) (dense arm only)
+        self.warm_matrices = bool(warm_matrices)      # solve() with matrices: update_matrices (sparse: update_values) + resolve(warm)
         unknown = set(bounds or ()) - set(self.bound_keys)
         if unknown:
             raise ValueError(f"bounds: unknown keys {sorted(unknown)}")
@@ -367,6 +366,15 @@ class BatchLCQPLayer:
         """load: BatchLCQP.load or .load_device; m: the four matrices by name"""
         return load(0, self.bt.B, m["Q"], g, m["L"], m["R"], A=m["A"], **kw)
 
+    def _keep_sent(self, full):
+        """after update_matrices on the host path: the copies the layer holds take the arrays that were sent"""
+        if self._held is not None:
+            self._held.update(full)
+
+    def _update_matrices(self, suffix, arrays):
+        """the given matrices alone to the whole batch: BatchLCQP.update_matrices or (suffix "_device") its device-pointer twin"""
+        return getattr(self.bt, "update_matrices" + suffix)(0, self.bt.B, **arrays)
+
     def _last_solve(self, serial):
         if self.solves == 0 or (serial is not None and serial != self.solves):
             raise RuntimeError("jacobian of a solve that is not the layer's last one: the batch object holds the state of one solve")
@@ -413,14 +421,17 @@ class SparseBatchLCQPLayer(BatchLCQPLayer):
     input_keys = SPARSE_VALUE_KEYS
     adjoint_names = dict(Qx="Q", Ax="A")      # the names of SparseBatchLCQP.adjoint
 
-    def __init__(self, batch, bounds=None, warm=True, values=None, general_panel=None):
-        """general_panel: True / False is handed to batch.set_general_panel -- jacobian() of a batch on the general sparse LDL' through that
+    def __init__(self, batch, bounds=None, warm=True, values=None, general_panel=None, warm_matrices=False):
+        """warm_matrices: solve() with Qx or Ax on a layer that has solved before sends the given arrays alone through
+        SparseBatchLCQP.update_values and solves by resolve(warm=True) from the last solution and working set ("New
+        matrices: the sparse arm"); such a solve needs no `values`.  The default is the load + cold run.
+        general_panel: True / False is handed to batch.set_general_panel -- jacobian() of a batch on the general sparse LDL' through that
         engine's panel kernel (None: the handle's setting stays).
         values: dict(Qx=[B][nnzQ], Ax=[B][nnzA]) (or [nnz], shared) -- the value arrays the batch was loaded with.  A layer whose solve()
         takes Qx or Ax needs them, the way it needs `bounds`: a host load replaces BOTH arrays, and the one that is not an input of the solve
         is handed over again.  The layer keeps them in step with its own loads (after a load on the device path: read back through
         SparseBatchLCQP.read_problem when the host path next needs them)."""
-        super().__init__(batch, bounds=bounds, warm=warm)
+        super().__init__(batch, bounds=bounds, warm=warm, warm_matrices=warm_matrices)
         if general_panel is not None:
             batch.set_general_panel(bool(general_panel))
         self.values = None
@@ -471,12 +482,21 @@ class SparseBatchLCQPLayer(BatchLCQPLayer):
         """load: SparseBatchLCQP.load or .load_device; m: the two value arrays by name"""
         return load(0, self.bt.B, m["Qx"], g, m["Ax"], **kw)
 
+    def _keep_sent(self, full):
+        """after update_values on the host path: the layer's `values` take the arrays that were sent (a stale copy is read back whole)"""
+        if self.values is not None and not self._values_stale:
+            self.values.update(full)
+
+    def _update_matrices(self, suffix, arrays):
+        """the given value arrays alone to the whole batch: SparseBatchLCQP.update_values or (suffix "_device") its device-pointer twin"""
+        return getattr(self.bt, "update_values" + suffix)(0, self.bt.B, **arrays)
+
     def solve(self, g, Qx=None, Ax=None, lbA=None, ubA=None):
         """(x, y) of the batch for the linear terms g, both differentiable (LCQPSparseFullSolveFunction): y [B][nC + 2 nComp], rows A, L, R.
         Qx, Ax: tensors that replace the value arrays of the batch for this and later solves, in the order of SparseBatchLCQP.load --
         [B][nnz] one per instance, [nnz] one shared by all instances (its gradient is the sum over the batch).  Qx.grad is the symmetric
         derivative on the full pattern.  Without any, the solve is the update + resolve of __call__."""
-        if (Qx is not None or Ax is not None) and self.values is None:
+        if (Qx is not None or Ax is not None) and self.values is None and not (self.warm_matrices and self.solves > 0):
             raise ValueError("solve: a layer that takes Qx or Ax needs the value arrays the batch holds -- construct it with "
                              "values=dict(Qx=..., Ax=...) (the sparse handle cannot read its matrices back)")
         return LCQPSparseFullSolveFunction.apply(self, g, Qx, Ax, lbA, ubA)

@@ -11,7 +11,11 @@ iterate means of each.
 tests/test_gpu_matrix_resolve.py and the vectors as above; on ONE handle, update_matrices + update + resolve(warm), then load + run of the
 same data (what a caller had to do before update_matrices existed).  Setup + homotopy milliseconds from HIP events as min / median / max
 over the steps, the wall clock, and the iterate counts of both.
-    python tools/resolve_bench.py --matrices [--batch 1024] [--steps 10] [--warmup 1] [--out ...]"""
+    python tools/resolve_bench.py --matrices [--batch 1024] [--steps 10] [--warmup 1] [--out ...]
+--sparse --matrices: the same on the sparse arm ("New matrices: the sparse arm"): per step the value arrays Qx, Ax by
+the 2 % recipe of tests/test_gpu_sparse_value_resolve.py and the vectors as above; on ONE handle, update_values + update + resolve(warm),
+then load + run of the same data.
+    python tools/resolve_bench.py --sparse --matrices [--batch 1024] [--n 4096] [--steps 5] [--warmup 1] [--out ...]"""
 import argparse
 import json
 import os
@@ -71,6 +75,67 @@ def sparse_main(a):
     return res
 
 
+def sparse_matrices_main(a):
+    from lcqpow_amd import synth_sparse as S
+    B, n = a.batch, a.n
+    nC, nK = n // 2, n // 8
+    Qpat, Apat, qo, eo = S.sparse_pattern_arrays(n, nC, nK)
+    sb = la.SparseBatchLCQP(B, n, nC, nK, Qpat, Apat, opt=la.default_options(perturbStep=0, printLevel=0))
+    inst = [S.sparse_values(i, n, nC, nK, orders=(qo, eo)) for i in range(B)]
+    val = dict(Qx=np.stack([d["Qx"] for d in inst]), Ax=np.stack([d["Ex"] for d in inst]))
+    vec = {k: np.stack([d[k] for d in inst]) for k in ("g", "lbA", "ubA")}
+    del inst
+    assert sb.load(0, B, val["Qx"], vec["g"], val["Ax"], lbA=vec["lbA"], ubA=vec["ubA"]) == 0
+    sb.run(); sb.synchronize()
+    qrow, qcol = Qpat.indices, np.repeat(np.arange(n), np.diff(Qpat.indptr))      # CSC: row and column of every stored entry of Q
+    rng = np.random.default_rng(0)
+    eps = 0.02
+    kinds = ("update_values_resolve_warm", "load_run")
+    rows = {k: [] for k in kinds}
+    for k in range(a.warmup + a.steps):
+        s = 1.0 + eps * rng.standard_normal((B, n))
+        val = dict(Qx=val["Qx"] * s[:, qrow] * s[:, qcol], Ax=val["Ax"] * (1.0 + eps * rng.standard_normal(val["Ax"].shape)))
+        shift = eps * (vec["ubA"] - vec["lbA"]) * rng.standard_normal(vec["lbA"].shape)
+        vec = dict(g=vec["g"] * (1.0 + eps * rng.standard_normal(vec["g"].shape)), lbA=vec["lbA"] + shift, ubA=vec["ubA"] + shift)
+        for kind in kinds:      # the warm re-solve first: it starts from the solution of the data one 2 % move back
+            t0 = time.perf_counter()
+            if kind == "load_run":
+                assert sb.load(0, B, val["Qx"], vec["g"], val["Ax"], lbA=vec["lbA"], ubA=vec["ubA"]) == 0
+                sb.run()
+            else:
+                assert sb.update_values(0, B, **val) == 0
+                assert sb.update(0, B, vec["g"], lbA=vec["lbA"], ubA=vec["ubA"]) == 0
+                sb.resolve(warm=True)
+            _, _, st = sb.solution()
+            wall = (time.perf_counter() - t0) * 1e3
+            setup_ms, solve_ms = sb.last_timing()
+            it = [q["iterTotal"] for q in st]
+            if k >= a.warmup:
+                rows[kind].append(dict(wall_ms=wall, setup_ms=setup_ms, solve_ms=solve_ms, kernels_ms=setup_ms + solve_ms, iter_mean=float(np.mean(it)),
+                                       iter_max=int(max(it)), solved=int(sum(q["returnValue"] == 0 for q in st))))
+    res = dict(mode="sparse matrices", batch=B, shape=[n, nC, nK], lanes=sb.lanes(), steps=a.steps, warmup=a.warmup, eps=eps)
+    summarise(res, rows, kinds, B)
+    res["launch_counts"] = list(sb.launch_counts())
+    sb.close()
+    return res
+
+
+def summarise(res, rows, kinds, B):
+    """min / median / max of the HIP-event milliseconds and the iterate counts of every kind into res, and one printed line each"""
+    for kind in kinds:
+        r = {}
+        for key in ("kernels_ms", "setup_ms", "solve_ms", "wall_ms"):
+            v = [q[key] for q in rows[kind]]
+            r[key] = dict(min=float(np.min(v)), median=float(np.median(v)), max=float(np.max(v)))
+        r.update(iter_mean=float(np.mean([q["iter_mean"] for q in rows[kind]])), iter_max=max(q["iter_max"] for q in rows[kind]),
+                 solved_min=min(q["solved"] for q in rows[kind]), steps=rows[kind])
+        res[kind] = r
+        km, sm, hm = r["kernels_ms"], r["setup_ms"], r["solve_ms"]
+        print(f"{kind:30s} setup + homotopy {km['min']:7.2f} / {km['median']:7.2f} / {km['max']:7.2f} ms (min / median / max; setup {sm['median']:.2f}, "
+              f"homotopy {hm['median']:.2f})   wall {r['wall_ms']['median']:8.1f} ms   iterates mean {r['iter_mean']:.1f} max {r['iter_max']}   "
+              f"solved >= {r['solved_min']}/{B}")
+
+
 def matrices_main(a):
     B, n, nC, nComp = a.batch, 256, 512, 64
     bt = la.BatchLCQP(B, n, nC, nComp, opt=la.default_options(printLevel=0))
@@ -107,18 +172,7 @@ def matrices_main(a):
                 rows[kind].append(dict(wall_ms=wall, setup_ms=setup_ms, solve_ms=solve_ms, kernels_ms=setup_ms + solve_ms, iter_mean=float(np.mean(it)),
                                        iter_max=int(max(it)), solved=int(sum(q["returnValue"] == 0 for q in st))))
     res = dict(mode="matrices", batch=B, shape=[n, nC, nComp], steps=a.steps, warmup=a.warmup, eps=eps)
-    for kind in kinds:
-        r = {}
-        for key in ("kernels_ms", "setup_ms", "solve_ms", "wall_ms"):
-            v = [q[key] for q in rows[kind]]
-            r[key] = dict(min=float(np.min(v)), median=float(np.median(v)), max=float(np.max(v)))
-        r.update(iter_mean=float(np.mean([q["iter_mean"] for q in rows[kind]])), iter_max=max(q["iter_max"] for q in rows[kind]),
-                 solved_min=min(q["solved"] for q in rows[kind]), steps=rows[kind])
-        res[kind] = r
-        km, sm, hm = r["kernels_ms"], r["setup_ms"], r["solve_ms"]
-        print(f"{kind:30s} setup + homotopy {km['min']:7.2f} / {km['median']:7.2f} / {km['max']:7.2f} ms (min / median / max; setup {sm['median']:.2f}, "
-              f"homotopy {hm['median']:.2f})   wall {r['wall_ms']['median']:8.1f} ms   iterates mean {r['iter_mean']:.1f} max {r['iter_max']}   "
-              f"solved >= {r['solved_min']}/{B}")
+    summarise(res, rows, kinds, B)
     res["launch_counts"] = list(bt.launch_counts())
     bt.close()
     return res
@@ -126,7 +180,7 @@ def matrices_main(a):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--matrices", action="store_true", help="the dense arm with new matrices per step: update_matrices + resolve(warm) against load + run")
+    ap.add_argument("--matrices", action="store_true", help="new matrices per step: update_matrices (with --sparse: update_values) + resolve(warm) against load + run")
     ap.add_argument("--sparse", action="store_true", help="the sparse arm: run against resolve(cold) and resolve(warm) on one handle")
     ap.add_argument("--n", type=int, default=4096, help="--sparse: variables per instance (nC = n / 2, nComp = n / 8)")
     ap.add_argument("--batch", type=int, default=1024)
@@ -135,7 +189,7 @@ def main():
     ap.add_argument("--out", default=os.path.join("profiles", "round7", "resolve", "resolve_bench.json"))
     a = ap.parse_args()
     if a.sparse or a.matrices:
-        res = sparse_main(a) if a.sparse else matrices_main(a)
+        res = sparse_matrices_main(a) if (a.sparse and a.matrices) else (sparse_main(a) if a.sparse else matrices_main(a))
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
