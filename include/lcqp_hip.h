@@ -451,10 +451,13 @@ int lcqp_hip_chol_solve(int batch, int n, const double* K, const double* b, doub
  * (Q_sparse and the stacked A_sparse = [A; L; R], src/LCQProblem.cpp:629-723; Q full symmetric).  Three factorisation engines, chosen
  * here per pattern: a band of half width <= 63; such a band plus at most 16 dense border nodes (rows or variables that touch many
  * others: the arrow of examples/OptimizeOnCircle.cpp); and, for any other pattern -- as the reference's OSQP arm takes any
- * (src/SubsolverOSQP.cpp:136-152) --, a general sparse LDL' (nested dissection with dense fronts, one wavefront per instance:
- * lcqp_sparse_general.hpp; a 2-D grid with 16 384 variables is one).  Returns NULL only when a front of that factorisation would exceed
- * 576 rows or the factor 2^28 entries (lcqp_hip_sparse_last_error() says so): the host layer runs such a problem on the dense kernels,
- * which take nV <= 4096.
+ * (src/SubsolverOSQP.cpp:136-152) --, a general sparse LDL' (dense fronts, one wavefront per instance: lcqp_sparse_general.hpp; a 2-D
+ * grid with 16 384 variables is one).  Its ordering is nested dissection; where that would need a front of more than 576 rows or a factor
+ * of 2^28 entries -- KKT graphs of small diameter: hundreds of small blocks coupled through a few dozen shared variables --, or where it
+ * lowers the largest front by a size class of the kernels and the flops with it, a minimum-degree ordering takes its place, provided it
+ * needs no more fronts (lcqp_hip_sparse_general_ordering says which one runs).  Returns NULL only when the ordering left by these rules
+ * still exceeds 576 rows in a front or 2^28 entries in the factor or the stack of update blocks -- many dense rows over many variables --
+ * (lcqp_hip_sparse_last_error() says so): the host layer runs such a problem on the dense kernels, which take nV <= 4096.
  *
  * Re-solves on the matrices in place (the sparse twin of lcqp_hip_batch_update / _resolve / _launch_counts):
  *   lcqp_hip_sparse_update   new g, bounds, x0, y0 for instances [first, first + count): the argument list of lcqp_hip_sparse_load without
@@ -499,6 +502,10 @@ int  lcqp_hip_sparse_sched_profile(lcqp_hip_sparse_t* s, unsigned long long* out
 int  lcqp_hip_sparse_bandwidth(const lcqp_hip_sparse_t* s);              /* half bandwidth of the KKT band */
 int  lcqp_hip_sparse_lanes(const lcqp_hip_sparse_t* s);                  /* lanes of a wavefront per instance: 8, 16, 32 or 64 */
 int  lcqp_hip_sparse_fronts(const lcqp_hip_sparse_t* s);                 /* fronts of the general sparse LDL' (a pattern that is neither banded nor bordered: nested dissection, dense fronts, a wavefront per instance); 0: a band engine */
+/* the ordering of the general sparse LDL' of this handle: 0 a band engine (no general LDL'), 1 nested dissection, 2 minimum degree (the rule:
+ * lcqp_hip_sparse_create above; the test hook LCQP_SPARSE_ORDERING=nd|md, read by create, forces one of the two on a pattern the general
+ * engine takes and sends no band pattern there); -1: NULL handle */
+int  lcqp_hip_sparse_general_ordering(const lcqp_hip_sparse_t* s);
 int  lcqp_hip_sparse_border(const lcqp_hip_sparse_t* s);                 /* border nodes of the bordered band: the last positions of the ordering (0: plain band) */
 /* perm[nV + nC + 2 nComp]: position -> node.  Two orderings of the band are prepared (the second, for Hessians that are safely definite by
  * their diagonals, puts every row behind one of its variables); this is the one the instances loaded so far select (before any load: the first) */

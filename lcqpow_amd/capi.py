@@ -173,6 +173,7 @@ def lib():
         L.lcqp_hip_sparse_lanes.argtypes = [C.c_void_p]
         L.lcqp_hip_sparse_border.argtypes = [C.c_void_p]
         L.lcqp_hip_sparse_fronts.argtypes = [C.c_void_p]
+        L.lcqp_hip_sparse_general_ordering.argtypes = [C.c_void_p]
         L.lcqp_hip_sparse_get_ordering.argtypes = [C.c_void_p, c_int_p]
         L.lcqp_hip_sparse_set_options.argtypes = [C.c_void_p, C.POINTER(Options)]
         L.lcqp_hip_sparse_load.argtypes = [C.c_void_p, C.c_int, C.c_int] + [c_double_p] * 11
@@ -1203,6 +1204,10 @@ class SparseBatchLCQP(_Batch):
     def fronts(self):
         """fronts of the general sparse LDL' (0: one of the band engines runs this pattern)"""
         return lib().lcqp_hip_sparse_fronts(self.h)
+
+    def general_ordering(self):
+        """lcqp_hip_sparse_general_ordering: 0 a band engine, 1 nested dissection, 2 minimum degree"""
+        return lib().lcqp_hip_sparse_general_ordering(self.h)
 
     def ordering(self):
         perm = np.zeros(self.nV + self.m, dtype=np.int32)

@@ -28,6 +28,7 @@ struct lcqp_hip_sparse {
     // the two orderings of the band (lcqp_sparse_pattern.hpp: Pattern::ord): device copies of their maps, the permutation for get_ordering
     struct Ord { std::vector<int> perm; int *iperm, *bandQ, *bandE, *bsrc, *bgate, *bdiag, *pnode, *Upos; bool rowsFollow; } ord[2] = {};
     bool hasB = false;
+    int generalOrdering = 0;       // lcqp_hip_sparse_general_ordering: 0 a band engine, 1 nested dissection, 2 minimum degree
     int useB = 0;                  // ordering of the last sp_choose_ordering
     std::vector<int> qdiagHost;    // entry of Q_ii in the value array
     std::vector<double> diagRatio; // per instance: min_i Q_ii / max_i Q_ii of the loaded Hessian (1: not loaded yet)

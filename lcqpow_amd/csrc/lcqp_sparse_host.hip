@@ -52,8 +52,10 @@ extern "C" lcqp_hip_sparse_t* lcqp_hip_sparse_create(int batch, int nV, int nC, 
     lcqp_pattern::Hooks hooks;
     if (const char* e = std::getenv("LCQP_SPARSE_GENERAL")) hooks.general = std::atoi(e) == 1;      // test hook: the general LDL' on a pattern the band engine would take
     if (const char* e = std::getenv("LCQP_SPARSE_LANES")) hooks.lanes = std::atoi(e);               // test hook: a wider lane group than the band needs
+    if (const char* e = std::getenv("LCQP_SPARSE_ORDERING"))                                          // test hook: the ordering of the general LDL' (nd | md)
+        hooks.ordering = !std::strcmp(e, "nd") ? lcqp_pattern::ORDER_ND : (!std::strcmp(e, "md") ? lcqp_pattern::ORDER_MD : 0);
     lcqp_pattern::Pattern P;
-    if (!lcqp_pattern::analyse_pattern(nV, nC, nComp, Qp, Qi, Ap, Ai, hooks, P, g_sp_err)) return nullptr;
+    if (!lcqp_pattern::analyse_pattern(nV, nC, nComp, Qp, Qi, Ap, Ai, hooks, P, g_sp_err)) { g_sp_err += P.note; return nullptr; }
     const int n = P.n, m = P.m, N = P.N, nnzQ = P.nnzQ, nnzA = P.nnzE, w = P.w, G = P.G, ld = G, kb = P.kb;
     const int nU = (int)P.Usrc.size(), nCb = (int)P.Csrc.size();
     const bool general = P.general;
@@ -64,7 +66,7 @@ extern "C" lcqp_hip_sparse_t* lcqp_hip_sparse_create(int batch, int nV, int nC, 
     for (hipError_t e : {h->stream.status, h->ev0.status, h->ev1.status, h->ev2.status, h->evIn.status, h->evOut.status})
         if (e != hipSuccess) { hip_fail(g_sp_err, "stream/event creation", e); return nullptr; }
     if (hipError_t e = hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device)) { hip_fail(g_sp_err, "hipDeviceGetAttribute(multiprocessor count)", e); return nullptr; }
-    h->csr2csc = P.csr2csc; h->hasB = P.hasB; h->qdiagHost = P.qdiag; h->diagRatio.assign(batch, 1.0); h->rs.filled.assign(batch, 0);
+    h->csr2csc = P.csr2csc; h->hasB = P.hasB; h->generalOrdering = general ? P.ordering : 0; h->qdiagHost = P.qdiag; h->diagRatio.assign(batch, 1.0); h->rs.filled.assign(batch, 0);
     SpBatch& d = h->db;
     d.B = batch; d.n = n; d.m = m; d.nC = nC; d.nComp = nComp; d.N = N; d.Np = ((N + 63) / 64) * 64; d.w = w; d.ld = ld; d.nnzQ = nnzQ; d.nnzE = nnzA; d.G = G; d.kb = kb; d.nU = nU; d.nCb = nCb;
     d.general = general ? 1 : 0;
@@ -179,6 +181,7 @@ extern "C" int lcqp_hip_sparse_bandwidth(const lcqp_hip_sparse_t* h) { return h 
 extern "C" int lcqp_hip_sparse_lanes(const lcqp_hip_sparse_t* h) { return h ? h->db.G : -1; }
 extern "C" int lcqp_hip_sparse_border(const lcqp_hip_sparse_t* h) { return h ? h->db.kb : -1; }
 extern "C" int lcqp_hip_sparse_fronts(const lcqp_hip_sparse_t* h) { return h ? (h->db.general ? h->db.gnF : 0) : -1; }
+extern "C" int lcqp_hip_sparse_general_ordering(const lcqp_hip_sparse_t* h) { return h ? h->generalOrdering : -1; }
 extern "C" int lcqp_hip_sparse_get_ordering(const lcqp_hip_sparse_t* h, int* perm)
 {
     if (!h || !perm) return LCQP_INVALID_ARGUMENT;

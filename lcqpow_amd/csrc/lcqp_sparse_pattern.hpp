@@ -20,8 +20,13 @@ constexpr int SP_KBMAX = 16;             // border nodes of the bordered band (r
 constexpr int GEN_MAX_FRONT = 576;       // panel of the largest front: 576 x 8 doubles beside nothing else in the 40 KB of a wavefront
 
 // runtime test hooks that change the analysis, read from the environment by lcqp_hip_sparse_create: LCQP_SPARSE_GENERAL=1 (the general LDL'
-// on a pattern the band engine would take), LCQP_SPARSE_LANES (16, 32 or 64 lanes per instance when that is more than the band needs)
-struct Hooks { bool general = false; int lanes = 0; };
+// on a pattern the band engine would take), LCQP_SPARSE_LANES (16, 32 or 64 lanes per instance when that is more than the band needs),
+// LCQP_SPARSE_ORDERING=nd|md (the ordering of the general LDL' whatever the choice rule says; it sends no band pattern to the general engine)
+enum { ORDER_BAND = 0, ORDER_ND = 1, ORDER_MD = 2 };      // Pattern::ordering, lcqp_hip_sparse_general_ordering
+struct Hooks { bool general = false; int lanes = 0; int ordering = 0; };
+
+// the size class of a front in the kernels (the QR = 1, 4, 9 rows per lane of lcqp_sparse_factor.hpp); 3: beyond what they take
+inline int front_class(int ff) { return ff <= 64 ? 0 : (ff <= 256 ? 1 : (ff <= GEN_MAX_FRONT ? 2 : 3)); }
 
 // what depends on the ordering: perm[position] = node and its inverse, band slot of every entry of Q and E (-1: not in the band -- an
 // upper-triangle entry of Q, or an entry of the border), where every off-diagonal band entry comes from (assembly inside the factorisation:
@@ -36,12 +41,14 @@ struct Pattern {
     int n = 0, m = 0, N = 0, nnzQ = 0, nnzE = 0;
     int w = 0, G = 0, kb = 0;     // half bandwidth (at least 1; the general LDL' has no band), lanes per instance, border nodes
     bool general = false, hasB = false;
+    int ordering = ORDER_BAND;    // of the general LDL': ORDER_ND or ORDER_MD
     std::vector<int> Ep, Ei, csr2csc, ETp, ETi, ETmap;      // E in CSR (csr2csc: its value order in the caller's CSC) and in CSC (ETmap: CSC -> CSR)
     std::vector<int> qdiag, Erow;                           // entry of Q_ii (-1: none), row of every CSR entry of E
     Ordering ord[2];                                        // [0] reverse Cuthill-McKee, [1] its rows-follow variant (hasB)
     std::vector<int> border, Uptr, Usrc, Ugate, Cptr, Cb2, Csrc, Cgate;
     Ell ellQ, ellE, ellT;                                   // rows of Q, rows of E, columns of E
     lcqp_general::Symbolic sym;                             // the general LDL' (general only)
+    std::string note;                                       // of a refused pattern: what the message does not say (a minimum-degree ordering that fits but is not taken)
 };
 
 // The pattern is taken at its word below, so it is checked first: column pointers start at 0 and never decrease; row indices inside a
@@ -137,11 +144,21 @@ inline int half_bandwidth(const std::vector<int>& pm, const std::vector<std::vec
 // Ordering: reverse Cuthill-McKee; while the half bandwidth exceeds what a lane group covers, the node of highest degree moves to the
 // border (at most SP_KBMAX nodes), the positions behind the band.  Arrow-shaped KKT matrices (a coupling row, a shared variable:
 // examples/OptimizeOnCircle.cpp:44) become a narrow band plus a few border nodes.  Neither a banded nor a bordered problem: the general sparse
-// LDL' (round 6; until then such a pattern was refused here and ran densified).  Sets P.ord[0].perm, P.border, P.general, P.sym; sub = the
-// graph of the band nodes, wA = the half bandwidth of the ordering.
-inline bool order_kkt(const int* Qp, const int* Qi, const std::vector<std::vector<int>>& adj, bool forceGeneral, Pattern& P,
+// LDL' (round 6; until then such a pattern was refused here and ran densified).  Sets P.ord[0].perm, P.border, P.general, P.ordering, P.sym;
+// sub = the graph of the band nodes, wA = the half bandwidth of the ordering.
+// The ordering of the general LDL': nested dissection, as before there was a choice.  Minimum degree (lcqp_sparse_general.hpp) takes its
+// place ONLY where nested dissection is refused -- a front beyond GEN_MAX_FRONT rows or storage beyond the 32-bit offsets --, or where the
+// largest front of minimum degree lies in a strictly lower size class of the kernels (front_class) AND its flops are lower; a tie keeps
+// nested dissection.  In both cases minimum degree must not need MORE FRONTS than nested dissection: a front costs its fixed time whatever
+// its size (lcqp_sparse_general.hpp), and the patterns on which minimum degree pays with fronts are those with dense rows -- forty or sixty
+// rows over every variable: each variable becomes a front of its own under all of those rows, its update block on the stack beside
+// those of the others -- which are dense in earnest: they keep the single large front of nested dissection, or stay refused and run on
+// the dense kernels.  No tuned threshold: the class boundaries are where the kernels change their code.  What neither ordering fits is
+// refused; where both exceed the limits the message names both largest fronts.
+inline bool order_kkt(const int* Qp, const int* Qi, const std::vector<std::vector<int>>& adj, const Hooks& hooks, Pattern& P,
                       std::vector<std::vector<int>>& sub, int& wA, std::string& err)
 {
+    const bool forceGeneral = hooks.general;
     const int n = P.n, m = P.m, N = P.N;
     std::vector<int>& permA = P.ord[0].perm;
     std::vector<int>& border = P.border;
@@ -165,12 +182,34 @@ inline bool order_kkt(const int* Qp, const int* Qi, const std::vector<std::vecto
         isBorder[best] = 1; border.push_back(best);
     }
     if (general) {
-        const lcqp_general::Symbolic& sym = P.sym = lcqp_general::analyze(n, m, adj, Qp, Qi, P.Ep.data(), P.Ei.data(), 32);
-        if (sym.maxFront > GEN_MAX_FRONT || sym.Lsize >= (1LL << 28) || sym.stackSize >= (1LL << 28)) {
-            err = "general sparse LDL' of this pattern: largest front " + std::to_string(sym.maxFront) + " (limit " + std::to_string(GEN_MAX_FRONT) + "), " +
-                  std::to_string((long long)sym.Lsize) + " factor entries: too dense for the sparse engine (use the dense kernels)";
+        using lcqp_general::Symbolic;
+        auto refused = [](const Symbolic& s) { return s.maxFront > GEN_MAX_FRONT || s.Lsize >= (1LL << 28) || s.stackSize >= (1LL << 28); };
+        Symbolic nd, md;
+        if (hooks.ordering != ORDER_MD) nd = lcqp_general::analyze(n, m, adj, Qp, Qi, P.Ep.data(), P.Ei.data(), 32);
+        // (minimum degree cannot win the class rule against a nested dissection whose fronts are all of the lowest class: not computed then)
+        const bool tryMd = hooks.ordering == ORDER_MD || (hooks.ordering != ORDER_ND && (refused(nd) || front_class(nd.maxFront) > 0));
+        if (tryMd) {
+            md = lcqp_general::analyze_md(n, m, adj, Qp, Qi, P.Ep.data(), P.Ei.data());
+            const std::string bad = lcqp_general::symbolic_violation(md);
+            if (!bad.empty()) { err = "minimum-degree analysis: " + bad; return false; }
+        }
+        const bool takeMd = hooks.ordering == ORDER_MD ||
+                            (tryMd && !refused(md) && md.nF <= nd.nF && (refused(nd) || (front_class(md.maxFront) < front_class(nd.maxFront) && md.flops < nd.flops)));
+        P.ordering = takeMd ? ORDER_MD : ORDER_ND;
+        if (refused(takeMd ? md : nd)) {
+            const Symbolic& s = takeMd ? md : nd;
+            const bool both = hooks.ordering == 0 && tryMd && refused(md);
+            err = "general sparse LDL' of this pattern: largest front " + std::to_string(s.maxFront) +
+                  (both ? " (nested dissection), " + std::to_string(md.maxFront) + " (minimum degree)" : std::string()) + " (limit " + std::to_string(GEN_MAX_FRONT) + "), " +
+                  std::to_string((long long)s.Lsize) + " factor entries: too dense for the sparse engine (use the dense kernels)";
+            // (the message of a pattern that nested dissection alone decides stays what it was; what follows goes beside it)
+            if (hooks.ordering == 0 && tryMd && !refused(md) && md.nF > nd.nF)
+                P.note = "; a minimum-degree ordering fits (largest front " + std::to_string(md.maxFront) + ") but needs " + std::to_string(md.nF) +
+                         " fronts against " + std::to_string(nd.nF) + " and is not taken (LCQP_SPARSE_ORDERING=md runs it)";
             return false;
         }
+        P.sym = takeMd ? std::move(md) : std::move(nd);
+        const Symbolic& sym = P.sym;
         border.clear();
         permA = sym.perm; wA = 0;
         sub = adj;
@@ -316,7 +355,7 @@ inline bool analyse_pattern(int nV, int nC, int nComp, const int* Qp, const int*
     for (int i = 0; i < n; i++) for (int k = Qp[i]; k < Qp[i + 1]; k++) if (Qi[k] == i) P.qdiag[i] = k;
     std::vector<std::vector<int>> sub;
     int wA = 0;
-    if (!order_kkt(Qp, Qi, kkt_graph(n, m, Qp, Qi, P.Ep, P.Ei), hooks.general, P, sub, wA, err)) return false;
+    if (!order_kkt(Qp, Qi, kkt_graph(n, m, Qp, Qi, P.Ep, P.Ei), hooks, P, sub, wA, err)) return false;
     P.kb = (int)P.border.size();
     std::vector<int> permB;
     int wB = 0;
