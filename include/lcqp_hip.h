@@ -138,6 +138,26 @@ typedef struct lcqp_hip_batch lcqp_hip_batch_t;
 
 /* LCQProblem(nV,nC,nComp) x B: src/LCQProblem.cpp:43-79.  withBox != 0 reserves rows for lb/ub. */
 lcqp_hip_batch_t* lcqp_hip_batch_create(int batch, int nV, int nC, int nComp, int withBox, int device);
+/* A batch that holds ONE Q, A, L, R for all its instances (parametric MPC, parameter sweeps, multi-start; DESIGN.md section 3a, "One set
+ * of matrices"): the blocks that depend on the matrices, the box pattern and the options alone -- Q, C, E, Et, L1, its inverted diagonal
+ * blocks, M and the compressed rows of C -- are stored once and set up once, on a grid of one matrix instance; what an instance writes
+ * during a solve stays per instance.  The handle is an lcqp_hip_batch_t that every lcqp_hip_batch_* call accepts, and an instance returns
+ * the same BITS (x, y, statistics, trace, every derivative) as the same problem in an ordinary batch of the same shape.  What differs:
+ *   lcqp_hip_batch_load / _load_device   Q, L, R, A are ONE [rows][nV] array each.  A non-NULL matrix replaces the batch's matrix whatever
+ *       the range; NULL keeps the one in place (the host call too), and before a matrix is in place its missing-matrix code is returned.
+ *       The device twin wants the `shared` bit of every matrix it is given, else LCQP_INVALID_ARGUMENT, nothing written.  Vectors are
+ *       [count][..] as ever.  The set of variables with a finite lb or ub is ONE for the batch (they are rows of the one E): the first
+ *       load defines it, from its first instance, and so does a load that brings a matrix while no instance outside its range holds a
+ *       problem; any other load whose set differs gets LCQP_INVALID_ARGUMENT, the lowest (instance, variable) in lcqp_hip_last_error(),
+ *       nothing written -- the rule lcqp_hip_batch_update has on every batch.
+ *   lcqp_hip_batch_update_matrices / _device   first == 0 and count == batch, arrays [rows][nV], the `shared` bits as above; anything else
+ *       LCQP_INVALID_ARGUMENT, nothing written.
+ *   lcqp_hip_batch_generate_synthetic   LCQP_INVALID_ARGUMENT: the generator draws matrices per instance.
+ * A factorisation that fails, fails every instance (setupFail on all of them, LCQP_SUBPROBLEM_SOLVER_ERROR from the run). */
+lcqp_hip_batch_t* lcqp_hip_batch_create_shared(int batch, int nV, int nC, int nComp, int withBox, int device);
+/* out[0]: bytes of device memory in the pools lcqp_hip_batch_create(_shared) allocated; out[1]: the part of them held once for the batch
+ * (0 on an ordinary batch).  Host arithmetic; NULL handle: LCQP_LCQPOBJECT_NOT_SETUP, NULL out: LCQP_INVALID_ARGUMENT. */
+int  lcqp_hip_batch_device_bytes(lcqp_hip_batch_t* b, size_t out[2]);
 void lcqp_hip_batch_destroy(lcqp_hip_batch_t* b);
 /* LCQProblem::setOptions, include/LCQProblem.ipp:160-163 */
 int  lcqp_hip_batch_set_options(lcqp_hip_batch_t* b, const lcqp_options_t* opt);

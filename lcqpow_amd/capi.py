@@ -104,6 +104,9 @@ def lib():
         L.lcqp_hip_qp_get_counters.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
         L.lcqp_hip_batch_create.restype = C.c_void_p
         L.lcqp_hip_batch_create.argtypes = [C.c_int] * 6
+        L.lcqp_hip_batch_create_shared.restype = C.c_void_p
+        L.lcqp_hip_batch_create_shared.argtypes = [C.c_int] * 6
+        L.lcqp_hip_batch_device_bytes.argtypes = [C.c_void_p, C.POINTER(C.c_size_t)]
         L.lcqp_hip_batch_destroy.argtypes = [C.c_void_p]
         L.lcqp_hip_batch_set_options.argtypes = [C.c_void_p, C.POINTER(Options)]
         L.lcqp_hip_batch_set_overlapped.argtypes = [C.c_void_p, C.c_int]
@@ -912,18 +915,43 @@ class BatchLCQP(_Batch):
     _prefix = "lcqp_hip_batch_"
     _last_error = staticmethod(last_error)
     _staging_setter = "set_jacobian_staging"
+    shared_matrices = False      # True: the batch holds one set of matrices (__init__)
     _vectors = (("g", "nV"), ("lbL", "nComp"), ("ubL", "nComp"), ("lbR", "nComp"), ("ubR", "nComp"), ("lbA", "nC"), ("ubA", "nC"),
                 ("lb", "nV"), ("ub", "nV"), ("x0", "nV"), ("y0", "_ndual"))
 
-    def __init__(self, batch, nV, nC, nComp, with_box=False, device=0, opt=None):
+    def __init__(self, batch, nV, nC, nComp, with_box=False, device=0, opt=None, shared_matrices=False):
+        """shared_matrices: lcqp_hip_batch_create_shared -- the batch holds ONE Q, A, L, R, stored and set up once (DESIGN.md section 3a,
+        "One set of matrices").  load / load_device / update_matrices(_device) then take 2-D matrices [rows][nV] and refuse 3-D ones; the
+        set of box-bounded variables is one for the batch; everything else is as on an ordinary batch, to the bit."""
         self.B, self.nV, self.nC, self.nComp = batch, nV, nC, nComp
         self.nd = self._ndual = nV + nC + 2 * nComp
         self.device = device
-        self.h = lib().lcqp_hip_batch_create(batch, nV, nC, nComp, int(with_box), device)
+        self.shared_matrices = bool(shared_matrices)
+        create = lib().lcqp_hip_batch_create_shared if self.shared_matrices else lib().lcqp_hip_batch_create
+        self.h = create(batch, nV, nC, nComp, int(with_box), device)
         if not self.h:
             raise RuntimeError("lcqp_hip_batch_create failed: " + last_error())
         if opt is not None:
             self.set_options(opt)
+
+    def device_bytes(self):
+        """lcqp_hip_batch_device_bytes: (bytes of device memory the handle's pools hold, the part of them held once for the batch --
+        0 on an ordinary batch)."""
+        out = (C.c_size_t * 2)()
+        _check(lib().lcqp_hip_batch_device_bytes(self.h, out), "device_bytes")
+        return int(out[0]), int(out[1])
+
+    def _one_set(self, what, first, count, matrices, whole):
+        """the refusals of a batch that holds one set of matrices, made before the C call: a matrix per instance, and (whole) a range
+        that is not the batch; returns the instances the matrix arrays are sized for"""
+        if not self.shared_matrices:
+            return count
+        for nm, m in matrices:
+            if m is not None and (m.dim() if hasattr(m, "dim") else np.ndim(m)) != 2:
+                raise ValueError(f"{what}: {nm} must be ONE matrix [rows][nV] -- this batch holds one set of matrices (shared_matrices=True)")
+        if whole and (first != 0 or count != self.B):
+            raise ValueError(f"{what}: this batch holds one set of matrices; they change for the whole batch (first=0, count={self.B})")
+        return 1
 
     def set_overlapped(self, overlapped=True):
         """lcqp_hip_batch_set_overlapped: this object's setup runs beside another object's homotopy kernel (BatchPipeline sets it)."""
@@ -937,8 +965,11 @@ class BatchLCQP(_Batch):
         if first < 0 or count <= 0 or first + count > self.B:
             raise ValueError(f"instances [{first}, {first + count}) outside the batch of {self.B}")
         vec = self._vector_sizes()      # the C order: Q, g, L, R, the bounds of L and R, A, the rest
-        table = (("Q", n * n), vec[0], ("L", nK * n), ("R", nK * n), *vec[1:5], ("A", nC * n), *vec[5:])
-        a = self._host_args(table, count, (Q, g, L, R, lbL, ubL, lbR, ubR, A, lbA, ubA, lb, ub, x0, y0))
+        # (a batch that holds one set of matrices takes one matrix each, or None: the one in place stays)
+        nmat = self._one_set("load", first, count, (("Q", Q), ("L", L), ("R", R), ("A", A)), False)
+        m = self._host_args((("Q", n * n), ("L", nK * n), ("R", nK * n), ("A", nC * n)), nmat, (Q, L, R, A))
+        v = self._host_args(vec, count, (g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0))
+        a = [m[0], v[0], m[1], m[2], *v[1:5], m[3], *v[5:]]
         return lib().lcqp_hip_batch_load(self.h, first, count, *[_p(v) for v in a])
 
     def sensitivity(self, v, blocked=False):
@@ -973,6 +1004,7 @@ class BatchLCQP(_Batch):
         hold a problem then).  Returns the ReturnValue code like load; the pools hold the bytes load leaves."""
         n, nC, nK = self.nV, self.nC, self.nComp
         self._range(first, count)
+        self._one_set("load_device", first, count, (("Q", Q), ("A", A), ("L", L), ("R", R)), False)
         shared, ptr = self._device_matrices(count, (("Q", Q, (n, n)), ("A", A, (nC, n)), ("L", L, (nK, n)), ("R", R, (nK, n))))
         v = self._device_vectors(count, (g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0))
         return lib().lcqp_hip_batch_load_device(self.h, first, count, shared, ptr["Q"], v[0], ptr["L"], ptr["R"], *v[1:5], ptr["A"], *v[5:],
@@ -990,6 +1022,7 @@ class BatchLCQP(_Batch):
         say so too, and must then agree with the shapes.  Returns the ReturnValue code."""
         n, nC, nK = self.nV, self.nC, self.nComp
         self._range(first, count)
+        self._one_set("update_matrices_device", first, count, (("Q", Q), ("A", A), ("L", L), ("R", R)), True)
         found, ptr = self._device_matrices(count, (("Q", Q, (n, n)), ("A", A, (nC, n)), ("L", L, (nK, n)), ("R", R, (nK, n))))
         if count > 1 and shared & ~found:
             raise ValueError(f"shared = {shared}: a matrix marked as shared has the shape of one per instance")
@@ -1027,7 +1060,8 @@ class BatchLCQP(_Batch):
         n, nC, nK = self.nV, self.nC, self.nComp
         if first < 0 or count <= 0 or first + count > self.B:
             raise ValueError(f"instances [{first}, {first + count}) outside the batch of {self.B}")
-        a = self._host_args((("Q", n * n), ("L", nK * n), ("R", nK * n), ("A", nC * n)), count, (Q, L, R, A))
+        nmat = self._one_set("update_matrices", first, count, (("Q", Q), ("L", L), ("R", R), ("A", A)), True)
+        a = self._host_args((("Q", n * n), ("L", nK * n), ("R", nK * n), ("A", nC * n)), nmat, (Q, L, R, A))
         return lib().lcqp_hip_batch_update_matrices(self.h, first, count, *[_p(v) for v in a])
 
     def read_problem(self, b):

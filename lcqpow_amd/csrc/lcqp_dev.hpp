@@ -6,6 +6,7 @@
 //   * LCQProblem::runSolver and its helpers (src/LCQProblem.cpp:444-560, 1105-1326, 1353-1482).
 // The CPU oracle (oracle/lcqp_oracle.c) is the same algorithm in scalar C; tests compare the two.
 #pragma once
+#include <cstddef>
 #include "lcqp_wg.hpp"
 #include "../../include/lcqp_hip.h"
 
@@ -26,7 +27,7 @@ struct InstInfo {
     double scale, sigma, spv, rhoAdmm, phiConst;
     // hand-over between two runs on the same setup (k_refresh).  haveSolution == 2: the stored point and working set are kept but the stored
     // residual does not belong to them any more (new vectors) -- the next hot start takes the polish's cold entry and stores a fresh one.
-    int warm, pad0;      // warm: lcqp_run starts from the last solution (V_XK) at the penalty rho0, without the zero-penalty QP
+    int warm, prevFail;  // warm: lcqp_run starts from the last solution (V_XK) at the penalty rho0, without the zero-penalty QP; prevFail: setupFail of the setup before the one in place (k_prepare_shared, for the warm hand-over of k_share_setup)
     double rho0;
     double hist[64];     // the last nDynamicPenalty complementarity values (src/LCQProblem.cpp:1344-1375; the reference's default is 3)
     double work[6];   // exact work sums for the byte accounting: [0] rows of Et read by the corrections, [1] sum(nT*ns) over corrections (pass over Ti), [2] bytes of Ti and M moved by working-set updates and predicted corrections, [3] number of updates, [4] rows of E read by the residual sweeps (both stages), [5] triangular solves with L1
@@ -35,6 +36,10 @@ struct InstInfo {
 struct DevBatch {
     int B, n, np, nC, nComp, mA, boxcap, mEcap, capS, nblk, nd;   // nd = n + mA (dual vector, reference layout)
     int hasLbL, hasLbR;
+    // 1: the batch holds ONE Q, A, L, R (lcqp_hip_batch_create_shared): Q, C, E, Et, F1, D1, MM and Cp / Ci / Cv are one block each,
+    // the block of instance 0; everything else is [B] as below.  (The field sits in what was padding in front of `opt`: the layout of
+    // the kernel argument, and with it the code of the kernels that do not read the field, is what it was without it.)
+    int shared;
     lcqp_options_t opt;
     double *Q, *C, *E, *Et, *F1, *FK, *S, *D1, *dscr;   // per-instance matrix blocks (S holds the inverse factor Ti, capS x capS)
     double *S2, *DS;                                     // [B][capS][capS], [B][capS/64][4096]: Cholesky factor of a working-set matrix built in one piece, its inverted diagonal blocks
@@ -56,6 +61,22 @@ struct DevBatch {
     int* traceLen;
     int traceCap;
 };
+
+// The instance whose block of a matrix pool (Q, C, E, Et, F1, D1, MM, Cp, Ci, Cv) instance b reads: itself, or 0 in a batch that holds
+// one set of matrices.  Every `pool + instance * size` of those pools outside the setup chain goes through this.  MI_RUNTIME reads the
+// field; the two persistent kernels fix the answer at compile time (MI_OWN: the builds every ordinary batch runs, the code they were before
+// the field existed; MI_FIRST: the builds of k_lcqp_run a shared batch runs, lcqp_nch.hip with -DLCQP_TU_SHARED) -- a runtime select moved
+// the SGPR spills of their 128-register builds (profiles/shared_matrices/).
+enum { MI_OWN, MI_FIRST, MI_RUNTIME };
+template <int MI = MI_RUNTIME>
+__host__ __device__ __forceinline__ size_t matrix_instance(const DevBatch& db, int b)
+{
+    if constexpr (MI == MI_OWN) return (size_t)b;
+    else if constexpr (MI == MI_FIRST) return 0;
+    else return db.shared ? (size_t)0 : (size_t)b;
+}
+
+static_assert(offsetof(DevBatch, opt) == 56 && offsetof(DevBatch, shared) == 52, "DevBatch::shared fills the padding in front of opt");
 
 template <int NCH>
 struct Ctx {
@@ -79,7 +100,7 @@ struct Ctx {
     __device__ __forceinline__ double* Sv(int k) const { return sv + (size_t)k * db->capS; }
 };
 
-template <int NCH>
+template <int NCH, int MI = MI_RUNTIME>
 __device__ __forceinline__ Ctx<NCH> make_ctx(const DevBatch& db, int b, Lds lds)
 {
     Ctx<NCH> c;
@@ -93,6 +114,14 @@ __device__ __forceinline__ Ctx<NCH> make_ctx(const DevBatch& db, int b, Lds lds)
     c.S2 = db.S2 + (size_t)b * db.capS * db.capS; c.DS = db.DS + (size_t)b * (db.capS / 64) * 4096;
     c.crow = db.crow + (size_t)b * db.capS;
     c.D1 = db.D1 + (size_t)b * db.nblk * 4096; c.dscr = db.dscr + (size_t)b * 4096;
+    if constexpr (MI != MI_OWN) {      // the matrix blocks again, through matrix_instance (the lines above are the MI_OWN builds' as they always were)
+        const size_t mb = matrix_instance<MI>(db, b);
+        c.Q = db.Q + mb * np * np; c.C = db.C + mb * np * np;
+        c.E = db.E + mb * db.mEcap * np; c.Et = db.Et + mb * db.mEcap * np;
+        c.F1 = db.F1 + mb * np * np;
+        c.MM = db.MM + mb * db.mMld * db.mMld;
+        c.D1 = db.D1 + mb * db.nblk * 4096;
+    }
     c.nv = db.nv + (size_t)b * V_NUM * np; c.mv = db.mv + (size_t)b * M_NUM * db.mEcap;
     c.sv = db.sv + (size_t)b * S_NUM * db.capS;
     c.mi = db.mi + (size_t)b * I_NUM * db.mEcap; c.idx = db.idx + (size_t)b * db.capS;
@@ -1317,8 +1346,8 @@ __device__ __forceinline__ void qp_export(Ctx<NCH>& c, double* xdst /*np or n*/,
 // ---------------------------------------------------------------------------------------------
 // LCQProblem::runSolver for one instance (oracle: orc_lcqp_solve).  src/LCQProblem.cpp:444-560.
 // ---------------------------------------------------------------------------------------------
-// LR: the row state of the subsolver lives in LDS (k_lcqp_run at np <= 256).
-template <int NCH, bool LR = false>
+// LR: the row state of the subsolver lives in LDS (k_lcqp_run at np <= 256).  MI: where the compressed rows of C are (matrix_instance).
+template <int NCH, bool LR = false, int MI = MI_RUNTIME>
 __device__ __forceinline__ void lcqp_run(Ctx<NCH>& c)
 {
     constexpr int np = 128 * NCH;
@@ -1403,6 +1432,10 @@ __device__ __forceinline__ void lcqp_run(Ctx<NCH>& c)
             const int* cp = db.Cp + (size_t)c.b * (np + 1);
             const int* ci = db.Ci + (size_t)c.b * db.capC;
             const double* ccv = db.Cv + (size_t)c.b * db.capC;
+            if constexpr (MI != MI_OWN) {      // (the three lines above are the MI_OWN builds' as they always were: their register allocation follows the text)
+                const size_t mb = matrix_instance<MI>(db, c.b);
+                cp = db.Cp + mb * (np + 1); ci = db.Ci + mb * db.capC; ccv = db.Cv + mb * db.capC;
+            }
             double vx[EPT], vp[EPT], vQx[EPT], vQp[EPT], vCx[EPT], vCp[EPT], vgt[EPT], vaty[EPT], vg[EPT], vgp[EPT];
             int c0[EPT], c1[EPT];
 #pragma unroll

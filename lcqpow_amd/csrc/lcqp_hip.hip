@@ -92,7 +92,17 @@ const RunKernels& run_kernels(const lcqp_hip_batch* h)
     return few ? *h->k->few : h->k->run;
 }
 
-extern "C" lcqp_hip_batch_t* lcqp_hip_batch_create(int batch, int nV, int nC, int nComp, int withBox, int device)
+// k_lcqp_run on the whole batch: a batch that holds one set of matrices takes the builds that read instance 0's matrix blocks
+static void launch_homotopy(lcqp_hip_batch* h)
+{
+    const RunKernels& rk = run_kernels(h);
+    if (!h->db.shared) rk.lcqp_run(h->db, h->db.B, h->stream);
+    else (&rk == &h->k->run ? h->k->shared_run : h->k->shared_run_few)(h->db, h->db.B, h->stream);
+}
+
+// shared: the batch holds ONE Q, A, L, R -- every pool of blocks that depend on the matrices, the box pattern and the options alone has one
+// block, instance 0's (DevBatch::shared, matrix_instance); what an instance writes during a solve is [B] as ever
+static lcqp_hip_batch_t* create_batch(int batch, int nV, int nC, int nComp, int withBox, int device, bool shared)
 { return guarded(g_err, [&]() -> lcqp_hip_batch_t* {
     if (batch <= 0 || nV <= 0 || nC < 0 || nComp < 0) { g_err = "invalid dimensions"; return nullptr; }
     if (nV > 4096) { g_err = "nV > 4096 is not supported by the dense kernels of this build (padded sizes 128 ... 4096; the sparse engine takes larger banded / bordered problems)"; return nullptr; }
@@ -104,6 +114,7 @@ extern "C" lcqp_hip_batch_t* lcqp_hip_batch_create(int batch, int nV, int nC, in
         if (e != hipSuccess) { hip_fail(g_err, "stream/event creation", e); return nullptr; }
     { int cu = 0; if (hipDeviceGetAttribute(&cu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && cu > 0) h->numCU = cu; }
     DevBatch& d = h->db;
+    d.shared = shared ? 1 : 0;
     d.B = batch; d.n = nV; d.nC = nC; d.nComp = nComp; d.mA = nC + 2 * nComp;
     h->k = kernels;
     h->nch = kernels->nch;        // 512 < nV <= 1024 runs the np = 1024 instantiation; 1024 < nV <= 2048: np = 2048 (96 KiB of LDS, one workgroup per CU, one row in flight per wave)
@@ -122,23 +133,55 @@ extern "C" lcqp_hip_batch_t* lcqp_hip_batch_create(int batch, int nV, int nC, in
     d.capC = 8 * d.np;                                     // C goes into compressed rows when it has at most 8 non-zeros per row on average
     lcqp_hip_options_default(&d.opt);
     const size_t B = batch, np = d.np, mE = d.mEcap, nLR = nComp ? nComp : 1;
+    const size_t Bm = shared ? 1 : B;      // blocks of a matrix pool
     DevMem& m = h->mem;      // zero-filled on the batch's stream
-    const bool ok = m.alloc(g_err, d.Q, B * np * np) && m.alloc(g_err, d.C, B * np * np) && m.alloc(g_err, d.E, B * mE * np) &&
-                    m.alloc(g_err, d.Et, B * mE * np) && m.alloc(g_err, d.F1, B * np * np) && m.alloc(g_err, d.FK, B * np * np) &&
-                    m.alloc(g_err, d.S, B * d.capS * d.capS) && m.alloc(g_err, d.MM, B * d.mMld * d.mMld) && m.alloc(g_err, d.crow, B * d.capS) &&
-                    m.alloc(g_err, d.Cp, B * (np + 1)) && m.alloc(g_err, d.Ci, B * d.capC) && m.alloc(g_err, d.Cv, B * d.capC) &&
-                    m.alloc(g_err, d.S2, B * d.capS * d.capS) && m.alloc(g_err, d.DS, B * (d.capS / 64) * 4096) &&
-                    m.alloc(g_err, d.D1, B * d.nblk * 4096) && m.alloc(g_err, d.dscr, B * 4096) && m.alloc(g_err, d.nv, B * V_NUM * np) &&
-                    m.alloc(g_err, d.mv, B * M_NUM * mE) && m.alloc(g_err, d.sv, B * S_NUM * d.capS) && m.alloc(g_err, d.mi, B * I_NUM * mE) &&
-                    m.alloc(g_err, d.idx, B * d.capS) && m.alloc(g_err, d.boxidx, B * np) && m.alloc(g_err, d.lbL, B * nLR) &&
-                    m.alloc(g_err, d.lbR, B * nLR) && m.alloc(g_err, d.yk, B * d.nd) && m.alloc(g_err, d.y0, B * d.nd) &&
-                    m.alloc(g_err, d.xout, B * nV) && m.alloc(g_err, d.yout, B * d.nd) && m.alloc(g_err, d.stats, B) &&
-                    m.alloc(g_err, d.info, B) && m.alloc(g_err, d.prof, B * 16);
-    if (!ok || !m.alloc(g_err, h->rs.rhoStart, B)) return nullptr;
-    h->rs.filled.assign(B, 0); h->boxed.assign(B * (size_t)nV, 0);
+    // every pool is counted where it is allocated (lcqp_hip_batch_device_bytes): `mat` a matrix pool -- Bm blocks, held once in a shared
+    // batch --, `inst` a pool with one block per instance.  (The trace buffers of set_options, the staging of the loads and the sensitivity
+    // buffers come and go with their calls and are not counted.)
+    auto mat = [&](auto*& p, size_t per) {
+        const size_t bytes = Bm * per * sizeof(*p);
+        h->bytesAll += bytes; if (shared) h->bytesOnce += bytes;
+        return m.alloc(g_err, p, Bm * per);
+    };
+    auto inst = [&](auto*& p, size_t per) {
+        h->bytesAll += B * per * sizeof(*p);
+        return m.alloc(g_err, p, B * per);
+    };
+    const size_t cS = d.capS, nd = d.nd;
+    const bool ok = mat(d.Q, np * np) && mat(d.C, np * np) && mat(d.E, mE * np) &&
+                    mat(d.Et, mE * np) && mat(d.F1, np * np) && inst(d.FK, np * np) &&
+                    inst(d.S, cS * cS) && mat(d.MM, (size_t)d.mMld * d.mMld) && inst(d.crow, cS) &&
+                    mat(d.Cp, np + 1) && mat(d.Ci, (size_t)d.capC) && mat(d.Cv, (size_t)d.capC) &&
+                    inst(d.S2, cS * cS) && inst(d.DS, (cS / 64) * 4096) &&
+                    mat(d.D1, (size_t)d.nblk * 4096) && inst(d.dscr, 4096) && inst(d.nv, V_NUM * np) &&
+                    inst(d.mv, M_NUM * mE) && inst(d.sv, S_NUM * cS) && inst(d.mi, I_NUM * mE) &&
+                    inst(d.idx, cS) && inst(d.boxidx, np) && inst(d.lbL, nLR) &&
+                    inst(d.lbR, nLR) && inst(d.yk, nd) && inst(d.y0, nd) &&
+                    inst(d.xout, (size_t)nV) && inst(d.yout, nd) && inst(d.stats, 1) &&
+                    inst(d.info, 1) && inst(d.prof, 16);
+    if (!ok || !inst(h->rs.rhoStart, 1)) return nullptr;
+    h->rs.filled.assign(B, 0); h->boxed.assign(B * (size_t)nV, 0); h->boxSet.assign((size_t)nV, 0);
     if (hipError_t e = hipStreamSynchronize(h->stream)) { hip_fail(g_err, "hipStreamSynchronize(h->stream)", e); return nullptr; }
     return h.release();
 }, nullptr); }
+
+extern "C" lcqp_hip_batch_t* lcqp_hip_batch_create(int batch, int nV, int nC, int nComp, int withBox, int device)
+{
+    return create_batch(batch, nV, nC, nComp, withBox, device, false);
+}
+
+extern "C" lcqp_hip_batch_t* lcqp_hip_batch_create_shared(int batch, int nV, int nC, int nComp, int withBox, int device)
+{
+    return create_batch(batch, nV, nC, nComp, withBox, device, true);
+}
+
+extern "C" int lcqp_hip_batch_device_bytes(lcqp_hip_batch_t* h, size_t out[2])
+{
+    if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
+    if (!out) return LCQP_INVALID_ARGUMENT;
+    out[0] = h->bytesAll; out[1] = h->bytesOnce;
+    return 0;
+}
 
 extern "C" void lcqp_hip_batch_destroy(lcqp_hip_batch_t* h)
 {
@@ -184,6 +227,18 @@ static int dense_upload(lcqp_hip_batch* h, int first, int count, const PackVecto
     });
 }
 
+// the one set of matrices of a shared batch from host arrays ([rows][nV] each, null: the block stays): the upload of one instance and
+// k_pack_matrices on instance 0, whose blocks are the batch's.  boxRows: as dense_pack_matrices.
+static int shared_upload_matrices(lcqp_hip_batch* h, const double* Q, const double* L, const double* R, const double* A, bool boxRows)
+{
+    const DevBatch& d = h->db;
+    const size_t n = d.n, nC = d.nC, nComp = d.nComp;
+    const RawArray raw[] = {{Q, n * n}, {A, nC * n}, {L, nComp * n}, {R, nComp * n}};
+    return upload_packed(g_err, h, 1, raw, [&](int, int, const double* const* p) {
+        return dense_pack_matrices(h, 0, 1, PackMatrices{{p[0], p[1], p[2], p[3]}, {n * n, nC * n, nComp * n, nComp * n}}, boxRows);
+    });
+}
+
 extern "C" int lcqp_hip_batch_load(lcqp_hip_batch_t* h, int first, int count,
                                    const double* Q, const double* g, const double* L, const double* R,
                                    const double* lbL, const double* ubL, const double* lbR, const double* ubR,
@@ -194,19 +249,37 @@ extern "C" int lcqp_hip_batch_load(lcqp_hip_batch_t* h, int first, int count,
     DevBatch& d = h->db;
     const size_t n = d.n, nC = d.nC, nComp = d.nComp;
     if (first < 0 || count <= 0 || first > d.B - count) return LCQP_INVALID_ARGUMENT;
+    // a batch that holds one set of matrices: Q, A, L, R are ONE [rows][nV] array each and replace the batch's, NULL keeps the one in place
+    const int given = given_matrices(Q, nC ? A : nullptr, L, R);
+    if (d.shared) {
+        if (!g) return shared_matrices_present(h, given) == LCQP_INVALID_ARGUMENT ? LCQP_INVALID_ARGUMENT : LCQP_INVALID_OBJECTIVE_LINEAR_TERM;
+        if (int rc = shared_matrices_present(h, given)) return rc;
+    } else {
     if (!Q) return LCQP_INVALID_ARGUMENT;
     if (!g) return LCQP_INVALID_OBJECTIVE_LINEAR_TERM;               // include/LCQProblem.ipp:44-45
     if (!A && nC > 0) return LCQP_INVALID_CONSTRAINT_MATRIX;         // src/LCQProblem.cpp:569-570
     if (!L || !R) return LCQP_INVALID_COMPLEMENTARITY_MATRIX;        // :611-612
+    }
     if ((lb || ub) && d.boxcap == 0) { g_err = "batch was created without box-bound capacity"; return LCQP_INVALID_ARGUMENT; }
     if (int rc = check_lower_bounds((size_t)count * nComp, lbL, lbR)) return rc;      // the last check: from here on the range is written
+    std::vector<char> boxSet;
+    if (d.shared) {      // (the last check of a shared batch: one set of box-bounded variables)
+        std::vector<char> flags((size_t)count * n);
+        for (size_t j = 0; j < flags.size(); j++) flags[j] = std::isfinite(bnd(lb, j, -INFINITY)) || std::isfinite(bnd(ub, j, INFINITY));
+        if (int rc = shared_box_check(g_err, h, first, count, flags.data(), given, boxSet)) return rc;
+    }
     HIPCHK(g_err, hipSetDevice(h->device));
     h->rs.invalidate();
     load_bound_flags(d, h->anyLoaded, first, lbL, lbR);
     for (size_t j = 0; j < (size_t)count * n; j++)      // setLB / setUB, include/LCQProblem.ipp:54-112
         h->boxed[(size_t)first * n + j] = std::isfinite(bnd(lb, j, -INFINITY)) || std::isfinite(bnd(ub, j, INFINITY));
     std::fill_n(h->rs.filled.begin() + first, count, 1);
-    if (int rc = dense_upload(h, first, count, PackVectors{g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0}, Q, A, L, R, false)) return rc;
+    if (d.shared) {
+        h->boxSet = boxSet; h->boxDefined = true; h->matsHeld |= given;
+        if (given) if (int rc = shared_upload_matrices(h, Q, L, R, A, true)) return rc;
+        if (int rc = dense_upload(h, first, count, PackVectors{g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0}, nullptr, nullptr, nullptr, nullptr, false)) return rc;
+    }
+    else if (int rc = dense_upload(h, first, count, PackVectors{g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0}, Q, A, L, R, false)) return rc;
     h->anyLoaded = true;
     return 0;
 }); }
@@ -216,6 +289,7 @@ extern "C" int lcqp_hip_batch_generate_synthetic(lcqp_hip_batch_t* h, uint64_t s
     if (!h) return LCQP_LCQPOBJECT_NOT_SETUP;
     HIPCHK(g_err, hipSetDevice(h->device));
     DevBatch& d = h->db;
+    if (d.shared) { g_err = "generate_synthetic: the generator draws matrices per instance; this batch holds one set of matrices (lcqp_hip_batch_create_shared)"; return LCQP_INVALID_ARGUMENT; }
     if (d.nComp * 2 > d.n) { g_err = "synthetic generator needs 2*nComp <= nV"; return LCQP_INVALID_ARGUMENT; }
     d.hasLbL = d.hasLbR = 0; h->anyLoaded = true;
     h->rs.invalidate();
@@ -234,8 +308,9 @@ extern "C" int lcqp_hip_batch_read_problem(lcqp_hip_batch_t* h, int b, double* Q
     DevBatch& d = h->db;
     const int n = d.n, nC = d.nC, nComp = d.nComp, np = d.np, mE = d.mEcap;
     std::vector<double> Qp((size_t)np * np), Ep((size_t)mE * np), nvb((size_t)V_NUM * np), mvb((size_t)M_NUM * mE);
-    HIPCHK(g_err, hipMemcpy(Qp.data(), d.Q + (size_t)b * np * np, sizeof(double) * np * np, hipMemcpyDeviceToHost));
-    HIPCHK(g_err, hipMemcpy(Ep.data(), d.E + (size_t)b * mE * np, sizeof(double) * mE * np, hipMemcpyDeviceToHost));
+    const size_t mb = matrix_instance(d, b);
+    HIPCHK(g_err, hipMemcpy(Qp.data(), d.Q + mb * np * np, sizeof(double) * np * np, hipMemcpyDeviceToHost));
+    HIPCHK(g_err, hipMemcpy(Ep.data(), d.E + mb * mE * np, sizeof(double) * mE * np, hipMemcpyDeviceToHost));
     HIPCHK(g_err, hipMemcpy(nvb.data(), d.nv + (size_t)b * V_NUM * np, sizeof(double) * V_NUM * np, hipMemcpyDeviceToHost));
     HIPCHK(g_err, hipMemcpy(mvb.data(), d.mv + (size_t)b * M_NUM * mE, sizeof(double) * M_NUM * mE, hipMemcpyDeviceToHost));
     for (int i = 0; i < n; i++) {
@@ -265,7 +340,16 @@ int launch_setup(lcqp_hip_batch* h, bool warm, const double* rho0)
     h->rs.nSetups++;
     const int ntile = d.nblk * (d.nblk + 1) / 2;
     const int nrb = (d.mEcap + 63) / 64, nb = (d.mMld + 127) / 128, nmt = nb * (nb + 1);      // k_build_M: 128 x 64 tiles of the lower triangle
-    if (warm) k.prepare_warm(d, d.B, on, rho0);
+    // a batch that holds one set of matrices: the chain below on a grid of ONE matrix instance (instance 0's blocks are the batch's), the
+    // matrix half of k_prepare in front of it, and behind it k_share_setup over the batch -- the marks of the chain and the vector half
+    const int nI = d.shared ? 1 : d.B;
+    if (d.shared) {
+        int src = 0;      // the lowest instance that holds a problem: its list of box-bounded variables is the batch's
+        while (src < d.B - 1 && !h->rs.filled[src]) src++;
+        if (!h->rs.filled[src]) src = 0;
+        k.prepare_shared(d, on, src);
+    }
+    else if (warm) k.prepare_warm(d, d.B, on, rho0);
     else k.prepare(d, d.B, on);
     // C and its compressed rows depend on L and R only, the chain L1 -> Et -> M on Q and E: two branches.  The short one goes to the side
     // stream and runs in the gaps of k_factor (one workgroup per instance, a life of dependent chains).  Measured alternatives, round 6
@@ -274,20 +358,21 @@ int launch_setup(lcqp_hip_batch* h, bool warm, const double* rho0)
     if (fork) {
         HIPCHK(g_err, hipEventRecord(h->evFork, on));
         HIPCHK(g_err, hipStreamWaitEvent(h->side, h->evFork, 0));
-        k.build_C(d, d.B * ntile, h->side);
-        k.compress_C(d, d.B, h->side);
+        k.build_C(d, nI * ntile, h->side);
+        k.compress_C(d, nI, h->side);
         HIPCHK(g_err, hipEventRecord(h->evJoin, h->side));
     }
     // more than three workgroups per CU (np <= 256: 36 KB of LDS each): the instantiation held to 128 registers, so that four are resident and
     // the batch needs one round
-    const BatchKernel factor = (h->nch <= 2 && d.B > 3 * h->numCU) ? k.factor_full : k.factor;
+    const BatchKernel factor = (h->nch <= 2 && nI > 3 * h->numCU) ? k.factor_full : k.factor;
     const BatchKernel trsm = h->overlapped ? k.trsm_streamed : k.trsm;
-    factor(d, d.B, on);
-    trsm(d, d.B * nrb, on);
+    factor(d, nI, on);
+    trsm(d, nI * nrb, on);
     // the join sits in front of the last setup kernel, not behind it: an event recorded right after a stream wait carried a late time stamp
     // (the homotopy kernel appeared 2 ms shorter than rocprofv3 and the wall clock say), and the side branch has long finished by then
     if (fork) HIPCHK(g_err, hipStreamWaitEvent(on, h->evJoin, 0));
-    k.build_M(d, d.B * nmt, on);
+    k.build_M(d, nI * nmt, on);
+    if (d.shared) k.share_setup(d, d.B, on, warm ? 1 : 0, rho0);
     HIPCHK(g_err, hipGetLastError());
     h->rs.setupValid = true;
     return 0;
@@ -319,7 +404,7 @@ extern "C" int lcqp_hip_batch_run(lcqp_hip_batch_t* h)
     int rc = launch_setup(h);   // the factorisations are part of runSolver's cost (initializeSolver :885)
     if (rc) return rc;
     HIPCHK(g_err, hipEventRecord(h->ev1, h->stream));
-    run_kernels(h).lcqp_run(h->db, h->db.B, h->stream);
+    launch_homotopy(h);
     h->rs.nLaunches++;
     HIPCHK(g_err, hipGetLastError());
     HIPCHK(g_err, hipEventRecord(h->ev2, h->stream));
@@ -362,6 +447,7 @@ extern "C" int lcqp_hip_batch_update_matrices(lcqp_hip_batch_t* h, int first, in
     const size_t n = d.n, nC = d.nC, nComp = d.nComp;
     HIPCHK(g_err, hipSetDevice(h->device));
     h->rs.matrices_changed();
+    if (d.shared) return shared_upload_matrices(h, Q, L, R, A, false);
     const RawArray raw[] = {{Q, n * n}, {A, nC * n}, {L, nComp * n}, {R, nComp * n}};
     return upload_packed(g_err, h, count, raw, [&](int c0, int cb, const double* const* p) {
         return dense_pack_matrices(h, first + c0, cb, PackMatrices{{p[0], p[1], p[2], p[3]}, {n * n, nC * n, nComp * n, nComp * n}}, false);
@@ -394,7 +480,7 @@ extern "C" int lcqp_hip_batch_resolve(lcqp_hip_batch_t* h, int mode, const doubl
         HIPCHK(g_err, hipGetLastError());
     }
     HIPCHK(g_err, hipEventRecord(h->ev1, h->stream));
-    run_kernels(h).lcqp_run(h->db, B, h->stream);
+    launch_homotopy(h);
     h->rs.nLaunches++;
     HIPCHK(g_err, hipGetLastError());
     HIPCHK(g_err, hipEventRecord(h->ev2, h->stream));
@@ -476,9 +562,10 @@ extern "C" int lcqp_hip_batch_read_setup(lcqp_hip_batch_t* h, int b, int dims[9]
     if (int rc = synchronize(g_err, h)) return rc;
     HIPCHK(g_err, hipStreamSynchronize(h->side));
     const DevBatch& d = h->db;
-    const size_t ib = b, np = d.np, mE = d.mEcap, ld = d.mMld;
+    const size_t np = d.np, mE = d.mEcap, ld = d.mMld;
     InstInfo info;
-    HIPCHK(g_err, hipMemcpy(&info, d.info + ib, sizeof(InstInfo), hipMemcpyDeviceToHost));
+    HIPCHK(g_err, hipMemcpy(&info, d.info + b, sizeof(InstInfo), hipMemcpyDeviceToHost));
+    const size_t ib = matrix_instance(d, b);      // every block below is a matrix block
     if (dims) {
         const int v[9] = {d.np, d.nblk, d.mEcap, d.mMld, d.capS, d.capC, info.mE, info.cNnz, info.setupFail};
         memcpy(dims, v, sizeof v);

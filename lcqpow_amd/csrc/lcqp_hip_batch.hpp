@@ -32,6 +32,12 @@ struct lcqp_hip_batch {
     // those are rows of E, hence of Et and M: an update must keep the set
     lcqp_rt::ResolveState rs;
     std::vector<char> boxed;              // [B][n]
+    // a batch that holds one set of matrices (db.shared): which of Q, A, L, R are in place (bits as `shared` of the device loads), and
+    // whether the set of box-bounded variables -- one for the batch, rows of the one E -- has been defined (it is boxed[] of every filled instance)
+    int matsHeld = 0;
+    bool boxDefined = false;
+    std::vector<char> boxSet;             // [n]
+    size_t bytesAll = 0, bytesOnce = 0;   // device memory lcqp_hip_batch_create(_shared) allocated, and the part of it held once for the batch
     lcqp_rt::SensState sn;                // sn.sens: of k_sensitivity
     lcqp_rt::SensBuffers sensBlk;         // of k_sensitivity_blk (another pitch of db, a varying number of instances)
     lcqp_rt::SensBuffers sensDual;        // of the dual Jacobian: capS staged rows per instance, no v, the row map behind `side`
@@ -84,6 +90,42 @@ inline std::string box_change_message(int variable, int instance, bool gains)
 {
     return "update: variable " + std::to_string(variable) + " of instance " + std::to_string(instance) + (gains ? " gains" : " loses") +
            " its box bound; the set of bounded variables is fixed by the load (they are rows of the factored matrices)";
+}
+
+// ---- a batch that holds one set of matrices (db.shared): the checks of its loads, host and device alike.  Nothing is written by them. ----
+// the bits of the matrices a load brings, in the order of `shared` of the device loads: Q, A, L, R
+inline int given_matrices(const double* Q, const double* A, const double* L, const double* R)
+{
+    return (Q ? 1 : 0) | (A ? 2 : 0) | (L ? 4 : 0) | (R ? 8 : 0);
+}
+// a matrix must be brought by the load or be in place: the missing-matrix codes of lcqp_hip_batch_load, in its order
+inline int shared_matrices_present(const lcqp_hip_batch* h, int given)
+{
+    const int have = h->matsHeld | given;
+    if (!(have & 1)) return LCQP_INVALID_ARGUMENT;
+    if (!(have & 2) && h->db.nC > 0) return LCQP_INVALID_CONSTRAINT_MATRIX;
+    if ((have & 12) != 12) return LCQP_INVALID_COMPLEMENTARITY_MATRIX;
+    return 0;
+}
+// The set of box-bounded variables is one for the batch (they are rows of the one E).  flags [count][n]: the set of each instance of the
+// load.  The load defines the set -- from its first instance -- when none is defined, or when it brings a matrix and no instance outside
+// its range holds a problem; otherwise every instance must have the set in place.  set [n]: the set the load leaves (to be stored with
+// boxDefined once the load goes ahead).  A difference: LCQP_INVALID_ARGUMENT and the lowest (instance, variable) in the message.
+inline int shared_box_check(std::string& err, const lcqp_hip_batch* h, int first, int count, const char* flags, int given, std::vector<char>& set)
+{
+    const size_t n = (size_t)h->db.n;
+    bool others = false;
+    for (int b = 0; b < h->db.B; b++) others = others || (h->rs.filled[b] && (b < first || b >= first + count));
+    const bool defines = !h->boxDefined || (given && !others);
+    if (defines) set.assign(flags, flags + n); else set = h->boxSet;
+    for (int k = 0; k < count; k++)
+        for (size_t i = 0; i < n; i++)
+            if ((flags[(size_t)k * n + i] != 0) != (set[i] != 0)) {
+                err = "load: variable " + std::to_string(i) + " of instance " + std::to_string(first + k) + (flags[(size_t)k * n + i] ? " has" : " has not") +
+                      " a box bound, against the set of the batch; a batch that holds one set of matrices has one set of bounded variables (they are rows of its E)";
+                return LCQP_INVALID_ARGUMENT;
+            }
+    return 0;
 }
 
 // (device_pointer_ok, device_call and read_back, which the device-pointer entry points and the readers of the three units are built on, are

@@ -203,7 +203,8 @@ int dense_pack_matrices(lcqp_hip_batch* h, int first, int count, const PackMatri
 int dense_pack(lcqp_hip_batch* h, int first, int count, const PackVectors& v, const PackMatrices& m, bool update)
 {
     const DevBatch& d = h->db;
-    if (!update) if (int rc = dense_pack_matrices(h, first, count, m, true)) return rc;
+    // (a batch that holds one set of matrices has one block per matrix pool: its loads pack instance 0 by themselves, never a range)
+    if (!update && !d.shared) if (int rc = dense_pack_matrices(h, first, count, m, true)) return rc;
     hipLaunchKernelGGL(k_pack_vectors, dim3(count), dim3(WG), 0, h->stream, d, first, count, v, update ? 1 : 0);
     HIPCHK(g_err, hipGetLastError());
     return 0;
@@ -218,6 +219,10 @@ int check_update_matrices(lcqp_hip_batch* h, int first, int count, const double*
     if (first < 0 || count <= 0 || first > h->db.B - count) return LCQP_INVALID_ARGUMENT;
     for (int k = 0; k < count; k++) if (!h->rs.filled[(size_t)first + k]) return LCQP_LCQPOBJECT_NOT_SETUP;
     if (!Q && !(A && h->db.nC) && !((L || R) && h->db.nComp)) return LCQP_INVALID_ARGUMENT;      // only matrices this batch has no rows of
+    if (h->db.shared && (first != 0 || count != h->db.B)) {
+        dense_err() = "update_matrices: this batch holds one set of matrices; they change for the whole batch (first = 0, count = batch)";
+        return LCQP_INVALID_ARGUMENT;
+    }
     return 0;
 }
 
@@ -270,10 +275,19 @@ extern "C" int lcqp_hip_batch_load_device(lcqp_hip_batch_t* h, int first, int co
     // a matrix that is not handed over stays as the pool holds it: every instance of the range must hold a problem then
     bool held = true;
     for (int k = 0; k < count; k++) held = held && h->rs.filled[(size_t)first + k];
+    const int given = given_matrices(Q, nC ? A : nullptr, nComp ? L : nullptr, nComp ? R : nullptr);
+    if (d.shared) {      // one [rows][nV] array per matrix, for the batch: every given matrix carries its shared bit; NULL keeps the one in place
+        if (given & ~shared) { g_err = "load_device: this batch holds one set of matrices; every matrix handed over needs its bit of `shared`"; return LCQP_INVALID_ARGUMENT; }
+        const int rc = shared_matrices_present(h, given | (nComp ? 0 : 12));
+        if (rc == LCQP_INVALID_ARGUMENT) return rc;
+        if (!g) return LCQP_INVALID_OBJECTIVE_LINEAR_TERM;
+        if (rc) return rc;
+    } else {
     if (!Q && !held) return LCQP_INVALID_ARGUMENT;
     if (!g) return LCQP_INVALID_OBJECTIVE_LINEAR_TERM;
     if (!A && nC > 0 && !held) return LCQP_INVALID_CONSTRAINT_MATRIX;
     if ((!L || !R) && !held) return LCQP_INVALID_COMPLEMENTARITY_MATRIX;
+    }
     if ((lb || ub) && d.boxcap == 0) { g_err = "batch was created without box-bound capacity"; return LCQP_INVALID_ARGUMENT; }
     HIPCHK(g_err, hipSetDevice(h->device));
     const PackVectors pv = {g, lbL, ubL, lbR, ubR, lbA, ubA, lb, ub, x0, y0};
@@ -293,6 +307,12 @@ extern "C" int lcqp_hip_batch_load_device(lcqp_hip_batch_t* h, int first, int co
         unsigned long long words[2];
         if (int rc = check_vectors(h, first, count, pv, false, words, (lb || ub) ? flags.data() : nullptr)) return rc;
         if (words[0] != ~0ull) return LCQP_INVALID_LOWER_COMPLEMENTARITY_BOUND;
+        if (d.shared) {
+            std::vector<char> set;
+            if (int rc = shared_box_check(g_err, h, first, count, flags.data(), given, set)) return rc;
+            h->boxSet = set; h->boxDefined = true; h->matsHeld |= given | (nComp ? 0 : 12);
+            if (given) if (int rc = dense_pack_matrices(h, 0, 1, pm, true)) return rc;
+        }
         // the host state of lcqp_hip_batch_load: the setup mark, the lbL / lbR flags, the box flags
         h->rs.invalidate();
         load_bound_flags(d, h->anyLoaded, first, lbL, lbR);
@@ -351,8 +371,12 @@ extern "C" int lcqp_hip_batch_update_matrices_device(lcqp_hip_batch_t* h, int fi
         pm.stride[k] = one ? 0 : rows[k] * d.n;
         if (!device_pointer_ok(g_err, h, names[k], mats[k], sizeof(double) * (one ? 1 : (size_t)count) * rows[k] * d.n)) return LCQP_INVALID_ARGUMENT;
     }
+    if (d.shared && (given_matrices(mats[0], mats[1], mats[2], mats[3]) & ~shared)) {
+        g_err = "update_matrices_device: this batch holds one set of matrices; every matrix handed over needs its bit of `shared`";
+        return LCQP_INVALID_ARGUMENT;
+    }
     return device_call(g_err, h, stream, [&] {
         h->rs.matrices_changed();
-        return dense_pack_matrices(h, first, count, pm, false);
+        return d.shared ? dense_pack_matrices(h, 0, 1, pm, false) : dense_pack_matrices(h, first, count, pm, false);
     });
 }); }

@@ -222,6 +222,64 @@ __global__ __launch_bounds__(WG) void k_prepare_warm(DevBatch db, const double* 
     if (t == 0) prepare_marks<NCH>(db, c, scale, phiConst);
 }
 
+// ---- the setup of a batch that holds ONE set of matrices (lcqp_hip_batch_create_shared; DESIGN.md section 3a, "One set of matrices") -------
+// The setup chain runs on a grid of one matrix instance, instance 0, whose blocks are the batch's: k_prepare_shared stands where k_prepare
+// stands and is its matrix half alone -- no vector, status, point or working set of instance 0 is touched --, then k_build_C, k_compress_C,
+// k_factor, k_trsm and k_build_M as they are.  k_share_setup, over all B instances, then hands every instance the marks the chain left in
+// InstInfo 0 and forms the vector half exactly as k_prepare / k_prepare_warm form it.
+// src: the instance whose list of box-bounded variables is the batch's (the lowest one that holds a problem; the set is one for the batch).
+template <int NCH>
+__global__ __launch_bounds__(WG) void k_prepare_shared(DevBatch db, int src)
+{
+    LCQP_LDS_N(NCH)
+    const int t = threadIdx.x;
+    Ctx<NCH> c = make_ctx<NCH>(db, 0, lds);
+    const int nfin = uniform_i(db.info[src].nfin), prevFail = uniform_i(c.info->setupFail);
+    __syncthreads();      // every thread has read the marks thread 0 rewrites below
+    c.boxidx = db.boxidx + (size_t)src * (128 * NCH);
+    if (t == 0) c.info->nfin = nfin;      // (prepare_matrices and prepare_marks read it; src == 0, or instance 0 holds no problem)
+    __syncthreads();
+    const double scale = prepare_matrices<NCH>(db, c, lds);
+    if (t == 0) {
+        c.info->prevFail = prevFail;
+        c.info->mE = db.mA + nfin;
+        c.info->scale = scale;
+        c.info->sigma = db.opt.admmSigma * scale;
+        c.info->cNnz = -1;
+        c.info->setupFail = 0;
+        c.info->isSetup = 1;
+    }
+}
+
+// mode 0: every instance starts cold (k_prepare); mode 1: the matrices changed under a stored point and an instance whose last run
+// returned 0 starts warm with an emptied inverse factor (k_prepare_warm).  rho0 [B] or null, as k_refresh takes it.
+template <int NCH>
+__global__ __launch_bounds__(WG) void k_share_setup(DevBatch db, int mode, const double* rho0)
+{
+    LCQP_LDS_N(NCH)
+    const int b = blockIdx.x, t = threadIdx.x;
+    Ctx<NCH> c = make_ctx<NCH>(db, b, lds);
+    const InstInfo* m = db.info;      // the matrix instance's marks; its own workgroup rewrites none of the fields read here
+    const int mE = uniform_i(m->mE), cNnz = uniform_i(m->cNnz), fail = uniform_i(m->setupFail), prevFail = uniform_i(m->prevFail);
+    const double scale = m->scale, sigma = m->sigma, spv = m->spv;
+    c.mE = mE;
+    const int warm = mode == 1 && c.info->haveSolution != 0 && db.stats[b].returnValue == 0 && prevFail == 0;      // warm_start, with the setup before this one
+    const double rhoStart = warm_penalty<NCH>(db, c, warm, rho0);
+    __syncthreads();      // every thread has read the marks thread 0 rewrites below
+    const double phiConst = prepare_vectors<NCH>(db, c, lds, scale);
+    if (warm) prepare_warm<NCH, true>(db, c, rhoStart);
+    else prepare_cold<NCH>(db, c);
+    if (t == 0) {
+        if (b != 0) {
+            c.info->mE = mE; c.info->scale = scale; c.info->sigma = sigma; c.info->spv = spv;
+            c.info->cNnz = cNnz; c.info->setupFail = fail; c.info->isSetup = 1;
+            c.info->kReady = 0; c.info->rnReady = 0;      // as k_factor leaves them
+        }
+        c.info->rhoAdmm = db.opt.admmRho * scale;
+        c.info->phiConst = phiConst;
+    }
+}
+
 // ---- the marks of a sensitivity call: `side` of every row in the working set and the flag bits of the instance (include/lcqp_hip.h) -----
 // One function for k_sensitivity and k_sensitivity_blk, so that the two kernels cannot disagree about a flag.  sd [nd]: zero on entry (every
 // thread's fill may still be in flight: the barrier inside block_max orders it before the marks); sflag: the instance's entry of `info`.
@@ -1132,7 +1190,8 @@ __global__ __launch_bounds__(WG, 4) void k_build_M(DevBatch db)
 // resident workgroups per CU win (28.6 against 31.9 ms at B = 1024).  profiles/round6/latency/.  (Eight rows in flight per wave instead of
 // four would take another 1 - 4 % off the small batches, but the compiler then contracts the dot products of the sweeps into other fused
 // multiply-adds: 1e-16 of difference and other iterate counts -- an instance must not depend on the size of the batch it is solved in.)
-// V only gives the instantiations of the two builds different names.
+// V gives the instantiations of the builds different names: 0 the standard one, 1 the second one; 2 and 3 are the same two builds of
+// k_lcqp_run for a batch that holds one set of matrices (lcqp_nch.hip with -DLCQP_TU_SHARED), where every matrix block is instance 0's.
 #ifndef LCQP_VARIANT
 #define LCQP_VARIANT 0
 #endif
@@ -1141,10 +1200,11 @@ template <int NCH, bool LR, int V>
 __global__ __launch_bounds__(WG, LCQP_MINWAVES) void k_lcqp_run(DevBatch db)
 {
     LCQP_LDS_N(NCH)
-    Ctx<NCH> c = make_ctx<NCH>(db, blockIdx.x, lds);
+    constexpr int MI = V >= 2 ? MI_FIRST : MI_OWN;
+    Ctx<NCH> c = make_ctx<NCH, MI>(db, blockIdx.x, lds);
     // the dependent-row rules are part of the subsolver here too (round 2 measured them behind a switch at 73.0 vs 72.0 ms, profiles/round2:
     // since the factor is updated instead of rebuilt they cost nothing), so the batched loop and the per-QP path are ONE algorithm
-    lcqp_run<NCH, LR>(c);
+    lcqp_run<NCH, LR, MI>(c);
 }
 
 // ---- one QP per workgroup with the SubsolverBase semantics ----------------------------------------
@@ -1152,7 +1212,7 @@ template <int NCH, int V>
 __global__ __launch_bounds__(WG, LCQP_MINWAVES) void k_qp_solve(DevBatch db, int initial)
 {
     LCQP_LDS_N(NCH)
-    Ctx<NCH> c = make_ctx<NCH>(db, blockIdx.x, lds);
+    Ctx<NCH> c = make_ctx<NCH, MI_OWN>(db, blockIdx.x, lds);      // the QP object's batch of one is never a shared one
     const double* y0 = (initial && c.info->hasY0) ? db.y0 + (size_t)c.b * db.nd : nullptr;
     int iters = 0;
     const int ef = qp_solve<NCH>(c, initial, c.V(V_GK), y0, &iters);   // single-QP path: dependent-row rules and rho adaptation
@@ -1321,7 +1381,15 @@ static void launch_qp_solve(const DevBatch& db, int grid, hipStream_t s, int ini
 }
 
 namespace lcqp {
-#ifdef LCQP_TU_FEW
+#ifdef LCQP_TU_SHARED
+// the translation units of a shared batch's builds hold k_lcqp_run only
+template <int NCH, int V>
+BatchKernel shared_run_kernel()
+{
+    static_assert(V == LCQP_VARIANT && V >= 2, "compile with -DLCQP_VARIANT=2 (standard) or 3 (second build)");
+    return launch_run<NCH>;
+}
+#elif defined(LCQP_TU_FEW)
 // the translation unit of the second build holds the two persistent kernels only
 template <int NCH>
 const RunKernels& few_kernels()
@@ -1340,6 +1408,8 @@ const SizeKernels& size_kernels()
         t.prepare = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_prepare<NCH>), dim3(grid), dim3(WG), 0, s, db); };
         t.refresh = [](const DevBatch& db, int grid, hipStream_t s, int mode, const double* rho0) { hipLaunchKernelGGL((k_refresh<NCH>), dim3(grid), dim3(WG), 0, s, db, mode, rho0); };
         t.prepare_warm = [](const DevBatch& db, int grid, hipStream_t s, const double* rho0) { hipLaunchKernelGGL((k_prepare_warm<NCH>), dim3(grid), dim3(WG), 0, s, db, rho0); };
+        t.prepare_shared = [](const DevBatch& db, hipStream_t s, int src) { hipLaunchKernelGGL((k_prepare_shared<NCH>), dim3(1), dim3(WG), 0, s, db, src); };
+        t.share_setup = [](const DevBatch& db, int grid, hipStream_t s, int mode, const double* rho0) { hipLaunchKernelGGL((k_share_setup<NCH>), dim3(grid), dim3(WG), 0, s, db, mode, rho0); };
         if constexpr (NCH <= 4)      // np <= 512 only: a panel of np >= 1024 does not fit LDS
         {
             t.sensitivity_blk = [](const DevBatch& db, int grid, hipStream_t s, int first, int nrhs, const double* v, double* dg, double* dbo, int* side, int* sinfo) {
@@ -1364,6 +1434,8 @@ const SizeKernels& size_kernels()
         t.trsm_streamed = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_trsm_streamed<NCH>), dim3(grid), dim3(WG), 0, s, db); };
         t.build_M = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_build_M<NCH>), dim3(grid), dim3(WG), 0, s, db); };
         t.run = {launch_run<NCH>, launch_qp_solve<NCH>};
+        t.shared_run = shared_run_kernel<NCH, 2>();
+        if constexpr (NCH <= 4) t.shared_run_few = shared_run_kernel<NCH, 3>();
         t.synth_fill = [](const DevBatch& db, int grid, hipStream_t s, uint64_t seed0, uint64_t first) { hipLaunchKernelGGL((k_synth_fill<NCH>), dim3(grid), dim3(WG), 0, s, db, seed0, first); };
         t.synth_Q = [](const DevBatch& db, int grid, hipStream_t s) { hipLaunchKernelGGL((k_synth_Q<NCH>), dim3(grid), dim3(WG), 0, s, db); };
         t.util_symv = [](int grid, hipStream_t s, int n, double alpha, const double* A, const double* b, const double* c, double* d) {

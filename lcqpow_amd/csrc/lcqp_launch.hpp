@@ -9,23 +9,29 @@ namespace lcqp {
 // nothing of the seam enters the dynamic symbol table of the library
 #pragma GCC visibility push(hidden)
 
+using BatchKernel = void (*)(const DevBatch& db, int grid, hipStream_t s);
+
 // the two persistent kernels: the standard unit and the second (256-register) build each define a pair
 struct RunKernels {
     void (*lcqp_run)(const DevBatch& db, int grid, hipStream_t s);
     void (*qp_solve)(const DevBatch& db, int grid, hipStream_t s, int initial);
 };
 
-using BatchKernel = void (*)(const DevBatch& db, int grid, hipStream_t s);
 
 struct SizeKernels {
     int nch;                    // np = 128 * nch
     RunKernels run;
     const RunKernels* few;      // the second build of the persistent kernels (np <= 512, at most three workgroups per CU), null for NCH > 4
+    BatchKernel shared_run, shared_run_few;      // k_lcqp_run of a batch that holds one set of matrices: the standard and the second build (null for NCH > 4)
     BatchKernel prepare;
     // mode 0: every instance cold, 1: warm where the last run succeeded; rho0 [B]: starting penalties of the warm instances (device), or null
     void (*refresh)(const DevBatch& db, int grid, hipStream_t s, int mode, const double* rho0);
     // k_prepare where the matrices changed under a stored point: warm where the last run succeeded, with an empty inverse factor; rho0 as above
     void (*prepare_warm)(const DevBatch& db, int grid, hipStream_t s, const double* rho0);
+    // a batch that holds one set of matrices: k_prepare_shared on a grid of one (src: the instance whose box list is the batch's), and
+    // k_share_setup over the batch behind the setup chain (mode 0: cold, 1: warm with an emptied factor; rho0 as above)
+    void (*prepare_shared)(const DevBatch& db, hipStream_t s, int src);
+    void (*share_setup)(const DevBatch& db, int grid, hipStream_t s, int mode, const double* rho0);
     BatchKernel build_C, compress_C;
     BatchKernel factor, factor_full;      // factor_full: held to 128 registers for np <= 256, so that four workgroups per CU are resident
     BatchKernel trsm, trsm_streamed, build_M;
@@ -52,6 +58,8 @@ struct SizeKernels {
 // the unit compiled with -DLCQP_TU_FEW
 template <int NCH> const SizeKernels& size_kernels();
 template <int NCH> const RunKernels& few_kernels();
+// the units compiled with -DLCQP_TU_SHARED -DLCQP_VARIANT=V: V = 2 the standard build, 3 the second one (with -DLCQP_MINWAVES=2)
+template <int NCH, int V> BatchKernel shared_run_kernel();
 
 #pragma GCC visibility pop
 }  // namespace lcqp

@@ -37,6 +37,22 @@ if sys.argv[1:] == ["sparse"]:      # the four kernel units of the sparse arm, o
         for o in report([], ("lcqp_sparse.hip", "-DLCQP_TU_G=%d" % G)): print(o[0] + "\n    " + "; ".join(o[1:]))
     sys.exit(0)
 
+if sys.argv[1:] == ["persistent"]:      # k_lcqp_run and k_qp_solve of every padded size, both builds: the report two commits are compared by
+    from concurrent.futures import ThreadPoolExecutor
+    FEW = ["-DLCQP_TU_FEW=1", "-DLCQP_VARIANT=1", "-DLCQP_MINWAVES=2"]
+    units = [(k, []) for k in g.NCH_LIST] + [(k, FEW) for k in g.NCH_LIST if k <= 4]
+    if "LCQP_TU_SHARED" in open(os.path.join(g.CSRC, "lcqp_nch.hip")).read():      # k_lcqp_run of a batch that holds one set of matrices: variants 2 and 3
+        units += [(k, ["-DLCQP_TU_SHARED=1", "-DLCQP_VARIANT=2"]) for k in g.NCH_LIST]
+        units += [(k, ["-DLCQP_TU_SHARED=1", "-DLCQP_VARIANT=3", "-DLCQP_MINWAVES=2"]) for k in g.NCH_LIST if k <= 4]
+    with ThreadPoolExecutor(8) as pool:
+        reports = list(pool.map(lambda u: report(u[1], ("lcqp_nch.hip", "-DLCQP_TU_NCH=%d" % u[0])), units))
+    print("Compiler resource usage of k_lcqp_run and k_qp_solve, every padded size, standard and 256-register build (tools/kernel_resources.py persistent).")
+    for (k, extra), rep in zip(units, reports):
+        print("\n-- np = %d, %s build%s" % (128 * k, "second" if "-DLCQP_MINWAVES=2" in extra else "standard", ", one set of matrices" if "-DLCQP_TU_SHARED=1" in extra else ""))
+        for o in rep:
+            if "k_lcqp_run" in o[0] or "k_qp_solve" in o[0]: print(o[0] + "\n    " + "; ".join(o[1:]))
+    sys.exit(0)
+
 print("Compiler resource usage of the np = 256 translation unit (hipcc -Rpass-analysis=kernel-resource-usage, flags of __graft_entry__.HIP_FLAGS; tools/kernel_resources.py).")
 print("Waves per SIMD = 512 / (VGPRs + AGPRs), rounded down; a 256-thread workgroup is one wave per SIMD, so this is also the workgroups per CU the registers allow.")
 print("(The VGPR column of rocprofv3 kernel traces in this directory shows about half of these figures.)")
